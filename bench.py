@@ -12,12 +12,21 @@ Multi-GPU (`--gpus N`): Llama-3-8B Q4_0 (4.2 GB) fits one GPU, so per BASELINE/S
 independent replicas decoding their own sequence (no data-path collective): weak scaling, value =
 total tokens / max-over-ranks time.
 
-Extra objects on the JSON line:
-  roofline      the Q4_0 GEMV kernel: algorithmic bytes / HIP-event kernel time, measured live in an
+A plain run does only what the headline needs: set-up, W warm-up steps, ONE timed region of K steps, the JSON
+line (`value`, `ms_per_step` = the milliseconds of one timed step).  `--dump-outputs DIR` then also writes what
+the timed path computed as DIR/<name>.npy: `tokens` (float64, the ids sampled in the K timed steps) and, through
+the reference's API, `logits` (float32, the last timed step's).  The inputs are seeded: the same arguments give
+the same inputs on every run.
+
+`--full` adds everything else: the K-step region is repeated `--repeats` times (default 5; value = the median
+region, all of them in `timed_regions`), and these extra objects are on the JSON line:
+  roofline     the Q4_0 GEMV kernel: algorithmic bytes / HIP-event kernel time, measured live in an
                 instrumented pass right after the timed region (event pairs on the kernel's own stream;
                 kept out of the timed region so they do not perturb tokens/s).  peak = 8.0 TB/s HBM3E.
   cpu_baseline  the reference's SIMD CPU path restated in C (oracle/, AVX2 lane order, crabml's row-split
                 thread pool) timed on this box's host cores on a bounded sample (rank 0, N=1 only).
+  and fused_entry_point, c3_positions_0_127, trait_path, prefill, context, gemv_points, parity_check /
+  value_strict (each can be switched off with its --no-* option).
 """
 import argparse
 import json
@@ -95,10 +104,16 @@ def parse():
                          "(per-rank kernel time; not a tokens/s result)")
     ap.add_argument("--tp-split-vocab", action="store_true",
                     help="with --tp-dry / --tp: the classifier split by vocabulary (each rank streams 1 / tp of output.weight)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement and check: the repeated timed region, the fused entry "
+                         "point, roofline, C3, the reference-API leg, prefill, context points, GEMV points, parity check, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prefill", action="store_true", help="skip the batched-prefill measurement")
     ap.add_argument("--cpu-seconds", type=float, default=24.0)
-    ap.add_argument("--repeats", type=int, default=5, help="the K-step timed region is repeated this many times (same positions)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the K-step timed region is repeated this many times (same positions); default 1, 5 with --full")
     ap.add_argument("--no-parity-check", action="store_true")
     ap.add_argument("--no-context", action="store_true", help="skip the long-context decode points")
     ap.add_argument("--no-c3", action="store_true",
@@ -106,7 +121,21 @@ def parse():
                          "back-to-back graph launches; tools/gpu_profile.sh passes this)")
     ap.add_argument("--no-gemv-points", action="store_true", help="skip the single-kernel GEMV points (SURVEY.md 8d)")
     ap.add_argument("--selftest-dist", action="store_true", help="CPU/gloo self test of the rank aggregation")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy for every array (float32 or float64, a few MB at most: logits of one step, one id per timed step)"""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def dist_env():
@@ -413,9 +442,11 @@ def tp_dry_run(args, ca, synth, local):
     r.decode_greedy(1, args.warmup)
     dev.sync()
     t0 = time.perf_counter()
-    r.decode_greedy(1, args.steps)
+    ids = r.decode_greedy(1, args.steps)
     dev.sync()
     ms = (time.perf_counter() - t0) * 1e3 / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tokens": [float(t) for t in ids]})
     local_bytes = sum(t.data.nbytes for name, t in model.tensors.items()
                       if not name.endswith("_norm.weight") and name != "token_embd.weight")
     # per-stage kernel times of the same rank (eager replay, dispatch-timestamp events)
@@ -549,6 +580,8 @@ def tp_group_run(args, ca, synth, dist, rank, world, local):
     dist.barrier()
     elapsed = time.perf_counter() - t0
     elapsed_max, _ = dist.max_sum(elapsed, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"tokens": [float(t) for t in ids]})
     ids_all = dist.gather([int(t) for t in ids])
     # the same rank with its exchanges skipped (same weights, same kernels, TP_DRY_RUN): step time minus this = what the
     # collectives (2 per layer + the sampler's pair exchange) cost per token on this node -- one run reports both
@@ -686,14 +719,16 @@ def main():
     headline = "fused" if (args.path == "fused" and path == "fused") else "reference"
 
     def decode(tok, n, which=None):
-        """n greedy decode steps, returns the last sampled token"""
+        """n greedy decode steps, returns the sampled tokens"""
         if (which or headline) == "fused":
-            return int(fused.decode_greedy(tok, n)[-1])
-        return int(trait.timed_decode(tok, n)[0][-1])
+            return fused.decode_greedy(tok, n)
+        return trait.timed_decode(tok, n)[0]
 
     # ---- warm-up (untimed), then the timed region: EXACTLY K steps between barrier + synchronize ------------------
-    # The region is repeated `--repeats` times over the SAME positions (the sequence is rewound: kv length back to 0,
-    # W warm-up steps, K timed steps), so the repeats are comparable; `value` is the MEDIAN region, all of them are listed.
+    # With --full the region is repeated `--repeats` times over the SAME positions (the sequence is rewound: kv length back
+    # to 0, W warm-up steps, K timed steps), so the repeats are comparable; `value` is the MEDIAN region, all of them are listed.
+    last_ids = []  # the tokens sampled in the last timed region
+
     def timed_regions(which):
         nonlocal trait
         out_r = []
@@ -702,27 +737,34 @@ def main():
                 fused.reset()
             elif rep > 0 or trait.kv_cache_len() > 0:
                 trait = ca.Llama2Runner(conf, weights, dev, trait_seq, True)  # (an empty cache: the runner has no rewind)
-            tok = decode(1, args.warmup, which) if args.warmup > 0 else 1
+            tok = int(decode(1, args.warmup, which)[-1]) if args.warmup > 0 else 1
             dev.sync()
             dist.barrier()
             t0 = time.perf_counter()
-            tok = decode(tok, args.steps, which)
+            ids = decode(tok, args.steps, which)
             dev.sync()
             dist.barrier()
             out_r.append(dist.max_sum(time.perf_counter() - t0, args.steps))
+            last_ids[:] = ids
         out_r.sort()
         return out_r
 
     regions = timed_regions(headline)
     elapsed_max, total_tokens = regions[len(regions) // 2]
-    fused_regions = timed_regions("fused") if (headline == "reference" and path == "fused") else None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the sampled ids and, through the reference's API, the last step's logits
+        outputs = {"tokens": [float(t) for t in last_ids]}
+        if headline == "reference":
+            outputs["logits"] = trait.logits()
+        dump_outputs(args.dump_outputs, outputs)
+    fused_regions = timed_regions("fused") if (args.full and headline == "reference" and path == "fused") else None
 
     # ---- instrumented pass: HIP event pairs around every GEMV-stage launch (same process, same weights),
     # taken RIGHT AFTER the timed regions (before the other legs create more contexts and devices) ---
     # Events cannot live inside the captured graph, so the fused step is replayed EAGERLY (identical kernels
     # and launch geometry) with one event pair per GEMV stage, on the backend's own stream.
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         STAGES = {0: "matmul_vec (per-op path)", 1: "k_qkv (wq|wk|wv + rope + KV append)", 2: "wo GEMV + residual (+ next rmsnorm/quantize epilogue)",
                   3: "k_gateup_q (gate|up + silu*mul + quantize)", 4: "ffn_down GEMV + residual (+ next rmsnorm/quantize epilogue)",
                   5: "k_gemv (classifier)"}
@@ -792,7 +834,7 @@ def main():
     # SURVEY.md config C3 quotes decode over positions 0..127 from an empty cache; the driver's arguments (--steps 20 --warmup 5)
     # time positions 5..24, where attention is nearly free.  Reported next to `value`: 128 steps from position 0, best of 3.
     c3 = None
-    if rank == 0 and path == "fused" and not args.no_c3:
+    if rank == 0 and args.full and path == "fused" and not args.no_c3:
         best = None
         for _ in range(3):
             fused.reset()
@@ -810,7 +852,7 @@ def main():
     # the same runner on a device that launches every call immediately (ABI version 1, "per-op") is timed next to it.
     trait_tps = None
     trait_info = None
-    if rank == 0 and path == "fused" and not args.no_trait:
+    if rank == 0 and args.full and path == "fused" and not args.no_trait:
         n_t = max(args.steps, 16)
         trait = ca.Llama2Runner(conf, weights, dev, trait_seq, True)  # (an empty cache for this leg)
         st0 = dev.lazy_stats()
@@ -856,7 +898,7 @@ def main():
 
     # ---- batched prefill of a 512-token prompt (crabml_hip_llama_prefill), reported next to the decode number ------
     prefill = None
-    if rank == 0 and path == "fused" and not args.no_prefill:
+    if rank == 0 and args.full and path == "fused" and not args.no_prefill:
         try:
             n_p = 512
             pr = ca.HipLlamaRunner(conf, weights, dev, n_p + 8, True)
@@ -896,7 +938,7 @@ def main():
 
     # ---- decode at longer contexts: the prompt is prefilled (batched pass), then 32 greedy steps are timed ------------------
     context = None
-    if rank == 0 and path == "fused" and not args.no_context and not args.gguf:
+    if rank == 0 and args.full and path == "fused" and not args.no_context and not args.gguf:
         context = {}
         for ctx_len in (256, 1024, 4096):
             try:
@@ -972,7 +1014,7 @@ def main():
             out["roofline"] = roof
         if prefill:
             out["prefill"] = prefill
-        if not args.no_gemv_points and args.gpus == 1 and args.wtype in ("Q4_0", "Q8_0", "Q4_1"):
+        if args.full and not args.no_gemv_points and args.gpus == 1 and args.wtype in ("Q4_0", "Q8_0", "Q4_1"):
             try:
                 out["gemv_points"] = gemv_points(ca, synth, dev, args.wtype)
             except Exception as e:
@@ -980,7 +1022,7 @@ def main():
         if args.gguf:
             out["data"] = "file: " + args.gguf
             out["config"]["workload"] = f"GGUF file {os.path.basename(args.gguf)} ({args.wtype} body), batch-1 greedy decode, f16 KV cache"
-        if not args.no_parity_check and args.gpus == 1 and model is not None and path == "fused":
+        if args.full and not args.no_parity_check and args.gpus == 1 and model is not None and path == "fused":
             try:
                 out["parity_check"] = parity_check(ca, synth, model, conf, weights, dev, local)
                 if "strict_tokens_per_s" in out["parity_check"]:  # the bit-identical tier as a first-class figure
@@ -988,7 +1030,7 @@ def main():
                     out["value_strict_through_reference_api"] = out["parity_check"].get("strict_reference_api_tokens_per_s")
             except Exception as e:
                 out["parity_check"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and args.gpus == 1 and model is not None:
+        if args.full and not args.no_cpu_baseline and args.gpus == 1 and model is not None:
             try:
                 out["cpu_baseline"] = cpu_baseline(model, args.cpu_seconds)
             except Exception as e:  # the baseline must never take the GPU number down with it

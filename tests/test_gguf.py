@@ -2,8 +2,8 @@
 
 CPU tests: the container parser against files written by synth.write_gguf (v1 / v2 / v3 length widths, alignment key
 of any integer type, data slices that run to the next tensor's offset, the "whole extra block" start of the data
-section) and -- when /root/reference is present -- against the reference's own fixture with the reference's own
-known answers (gguf.rs:838-965).  GPU tests: a model loaded from a GGUF file decodes bit-identically to the same
+section) and against the reference's own fixture (its copy in tests/golden/) with the reference's own known answers
+(gguf.rs:838-965).  GPU tests: a model loaded from a GGUF file decodes bit-identically to the same
 model uploaded tensor by tensor."""
 import os
 import struct
@@ -14,7 +14,7 @@ import pytest
 import crabml_amd as ca
 from crabml_amd import synth
 
-FIXTURE = "/root/reference/testdata/tinyllamas-stories-260k-f32.gguf"
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tinyllamas-stories-260k-f32.gguf")
 
 
 def small_model(fmt=synth.Q4_0, **kw):
@@ -105,7 +105,6 @@ def test_missing_tensor_and_missing_keys(tmp_path):
     assert gf.load_config().n_layers == model.shape.n_layers
 
 
-@pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference fixture only exists in the build container")
 def test_reference_fixture_known_answers():
     """The reference's own tests of its own fixture (gguf.rs:838-965), replayed against this parser."""
     gf = ca.GGUFFile(FIXTURE)

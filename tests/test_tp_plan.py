@@ -109,7 +109,9 @@ def _uid_worker(rank, world, port, q):
 
 
 def test_unique_id_broadcast_over_gloo():
-    import torch.multiprocessing as mp
+    # the standard library's spawn, not torch's: torch loaded into the test process brings a second HIP runtime next to the
+    # library's, and the process aborts at exit (the workers import torch in their own processes)
+    import multiprocessing as mp
     import socket
 
     s = socket.socket()

@@ -4,9 +4,9 @@ dominant kernel's sources (bench.kernel_code_hash): bench.py quotes `roofline.tr
 matches the code it runs, and reports null otherwise.
 
 usage (on the GPU box, counters in their OWN pass, per MI355X_MICROARCH.md "HBM"):
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -- python bench.py --steps 4 --warmup 1 --repeats 1 \
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d out/pmc_fetch -- python bench.py --full --steps 4 --warmup 1 --repeats 1 \
         --no-cpu-baseline --no-parity-check --no-context --no-prefill
-  python tools/pmc_traffic.py gpurun_out/pmc_fetch/*/*_results.db profiles/r02_pmc_fetch_size.md
+  python tools/pmc_traffic.py out/pmc_fetch/*/*_results.db profiles/r02_pmc_fetch_size.md
 FETCH_SIZE is in KiB and on gfx950 reports exactly 1/2 of the bytes of a wide coalesced streaming read: x 1024 x 2."""
 import glob
 import json
