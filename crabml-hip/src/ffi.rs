@@ -133,6 +133,7 @@ extern "C" {
     pub fn crabml_hip_llama_destroy(ctx: *mut crabml_hip_llama_t) -> i32;
     pub fn crabml_hip_llama_forward(ctx: *mut crabml_hip_llama_t, token: usize, pos: usize, logits: *mut f32) -> i32;
     pub fn crabml_hip_llama_decode_greedy(ctx: *mut crabml_hip_llama_t, token: usize, n_steps: usize, out_tokens: *mut u32) -> i32;
+    pub fn crabml_hip_llama_decode_sample(ctx: *mut crabml_hip_llama_t, token: usize, n_steps: usize, temperature: f32, topp: f32, coins: *const f32, out_tokens: *mut u32) -> i32;
     pub fn crabml_hip_llama_prefill(ctx: *mut crabml_hip_llama_t, tokens: *const u32, n: usize, logits: *mut f32) -> i32;
     pub fn crabml_hip_llama_kv_len(ctx: *const crabml_hip_llama_t) -> usize;
     pub fn crabml_hip_llama_reset(ctx: *mut crabml_hip_llama_t) -> i32;

@@ -188,6 +188,18 @@ impl HipLlamaRunner {
         Ok(out.into_iter().map(|t| t as usize).collect())
     }
 
+    /// The generate loop of llama2.rs:131-182 with `Llama2Sampler::sample` (sampler.rs:28-107) on the device: one token per
+    /// coin, starting from `token`, one host synchronisation at the end.  The caller draws the coins the way the reference
+    /// does (`rand::thread_rng().gen_range(0.0..1.0)`, sampler.rs:41-42), so with equal coins the tokens depend on the
+    /// logits alone.  Temperature 0 is `decode_greedy`.
+    pub fn decode_sample(&mut self, token: usize, temperature: f32, topp: f32, coins: &[f32]) -> Result<Vec<usize>> {
+        let mut out = vec![0u32; coins.len()];
+        self.device.check(unsafe {
+            ffi::crabml_hip_llama_decode_sample(self.raw, token, coins.len(), temperature, topp, coins.as_ptr(), out.as_mut_ptr())
+        })?;
+        Ok(out.into_iter().map(|t| t as usize).collect())
+    }
+
     /// empties the KV caches (a new conversation)
     pub fn reset(&mut self) -> Result<()> {
         self.device

@@ -22,11 +22,11 @@ if not _os.path.exists(LIB_PATH):
 from . import _host  # noqa: E402  (raises ImportError loudly if the extension was not built)
 from ._host import (  # noqa: E402,F401
     CrabmlError, GGMLType, GGUFFile, HipLlamaRunner, HipTensor, HipTensorDevice, Llama2Runner, LlamaConfig, LlamaWeights, RopeMode,
-    TensorStrider, TpComm, abi_version, sample_argmax,
+    TensorStrider, TpComm, abi_version, sample_argmax, sample_llama2,
 )
 
 __all__ = ["CrabmlError", "GGMLType", "GGUFFile", "HipLlamaRunner", "HipTensor", "HipTensorDevice", "Llama2Runner", "LlamaConfig", "LlamaWeights",
-           "RopeMode", "TensorStrider", "TpComm", "abi_version", "sample_argmax", "pin_host_to_device_node", "LIB_PATH"]
+           "RopeMode", "TensorStrider", "TpComm", "abi_version", "sample_argmax", "sample_llama2", "pin_host_to_device_node", "LIB_PATH"]
 
 
 def pin_host_to_device_node(device):

@@ -16,6 +16,7 @@
 //   k_gemv_res     wo / ffn_down matmul_vec + add_inplace(residual)
 //   k_gateup       ffn_gate/ffn_up matmul_vec + silu_inplace + mul_inplace
 //   k_argmax_step  greedy sampler (last maximum) + token/position advance
+//   k_sample_*     temperature / top-p sampler + advance (sampler.hpp; crabml_hip_llama_decode_sample)
 #include <chrono>
 #include <thread>
 #include <cmath>
@@ -23,6 +24,7 @@
 #include "fused_common.hpp"
 #include "fused_attention.hpp"
 #include "fused_ffn.hpp"
+#include "sampler.hpp"
 #include "prefill_rows.hpp"
 #include "lazy.hpp"
 
@@ -151,6 +153,16 @@ struct crabml_hip_llama {
   bool split_vocab = false;
   int vocab_l = 0, vocab_off = 0;
   int* am_best = nullptr;   // {max bits, index} of this rank's shard (single-device simulation: combined by the driver)
+  // temperature / top-p sampler (crabml_hip_llama_decode_sample), allocated on first use: block maxima, the keys of the
+  // vocabulary, the key histogram (zero between steps), {temperature, topp}, one coin per step
+  bool sampling = false;     // the final segment ends in the sampler instead of the arg-max (enqueue_classifier_and_sampler)
+  float* sm_bmax = nullptr;
+  unsigned short* sm_keys = nullptr;
+  unsigned* sm_hist = nullptr;
+  float* sm_par = nullptr;
+  float* sm_coins = nullptr;
+  hipGraph_t sgraph[3] = {nullptr, nullptr, nullptr};  // the step with the sampler, per attention variant, captured on first use
+  hipGraphExec_t sexec[3] = {nullptr, nullptr, nullptr};
   size_t kv_len = 0;
   // [0]: one attention workgroup per head; [1]: the long-context attention kernels (from attn_long_from positions)
   hipGraph_t graph[3] = {nullptr, nullptr, nullptr};
@@ -424,6 +436,19 @@ int enqueue_classifier_and_sampler(crabml_hip_llama* c, const void* cls_act, cra
       k_logits_to_host<<<64, 256, 0, st>>>((const f32x4*)out, (f32x4*)c->host_logits, n / 4, out, c->host_logits, n);
       k_host_flag<<<1, 1, 0, st>>>((unsigned*)(c->host_logits + c->cfg.vocab_size), (const int*)(c->state + 7), c->state + 5);
     }
+    CH_HIP(dev, hipGetLastError());
+    return 0;
+  }
+  if (c->sampling) {
+    const int n = c->vocab_l;
+    const SampleStep ss{c->sm_par, c->sm_coins, token_d, pos_d, step_d, c->state + 4, c->out_tokens, c->out_cap, c->state + 5};
+    k_sample_max<<<SAMPLE_BLOCKS, 256, 0, st>>>(out, n, c->sm_par, c->sm_bmax);
+    k_sample_keys<<<SAMPLE_BLOCKS, 256, 0, st>>>(out, n, c->sm_par, c->sm_bmax, SAMPLE_BLOCKS, (const unsigned short*)dev->exp_table,
+                                                 c->sm_keys, c->sm_hist);
+    if (dev->strict_order)
+      k_sample_pick<true><<<1, SAMPLE_PICK_THREADS, 0, st>>>(c->sm_keys, n, c->sm_hist, ss);
+    else
+      k_sample_pick<false><<<1, SAMPLE_PICK_THREADS, 0, st>>>(c->sm_keys, n, c->sm_hist, ss);
     CH_HIP(dev, hipGetLastError());
     return 0;
   }
@@ -1047,6 +1072,76 @@ int run_step(crabml_hip_llama* c, size_t pos) {
   c->attn_variant = variant;
   return enqueue_step(c);
 }
+
+// the same step ending in the temperature / top-p sampler: its own graphs (captured on first use, so the greedy ones stay as
+// they are), eager under CRABML_HIP_LLAMA_NO_GRAPH
+int run_step_sampled(crabml_hip_llama* c, size_t pos) {
+  const int variant = variant_of(c, pos);
+  crabml_hip_device* dev = c->dev;
+  int rc = 0;
+  c->sampling = true;
+  if (c->use_graph && !c->sexec[variant]) {
+    hipError_t e = hipStreamBeginCapture(dev->stream, hipStreamCaptureModeThreadLocal);
+    if (e != hipSuccess) {
+      c->sampling = false;
+      return hip_fail(dev, e, "llama: sampler graph capture", __FILE__, __LINE__);
+    }
+    c->capturing = true;
+    c->attn_variant = variant;
+    const int erc = enqueue_step(c);
+    c->capturing = false;
+    hipGraph_t graph = nullptr;
+    e = hipStreamEndCapture(dev->stream, &graph);
+    hipGraphExec_t exec = nullptr;
+    if (erc == 0 && e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+      c->sgraph[variant] = graph;
+      c->sexec[variant] = exec;
+    } else {
+      if (graph) (void)hipGraphDestroy(graph);
+      (void)hipGetLastError();
+      c->sampling = false;
+      CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: hipGraph capture/instantiate of the sampled step failed");
+    }
+  }
+  if (c->use_graph) {
+    const hipError_t e = hipGraphLaunch(c->sexec[variant], dev->stream);
+    if (e != hipSuccess) rc = hip_fail(dev, e, "hipGraphLaunch (sampled step)", __FILE__, __LINE__);
+  } else {
+    c->attn_variant = variant;
+    rc = enqueue_step(c);
+  }
+  c->sampling = false;
+  return rc;
+}
+
+// a few bytes host -> device in stream order, staged through the context's pinned ring (see set_state)
+int stage_h2d(crabml_hip_llama* c, void* dst, const void* src, size_t bytes) {
+  if (c->h_state_next == crabml_hip_llama::H_STATE_SLOTS) {
+    CH_HIP(c->dev, hipStreamSynchronize(c->dev->stream));
+    c->h_state_next = 0;
+  }
+  int* st = c->h_state + 4 * c->h_state_next++;
+  memcpy(st, src, bytes < 16 ? bytes : 16);
+  CH_HIP(c->dev, hipMemcpyAsync(dst, st, bytes < 16 ? bytes : 16, hipMemcpyHostToDevice, c->dev->stream));
+  return 0;
+}
+
+int sample_alloc(crabml_hip_llama* c) {
+  if (c->sm_hist) return 0;
+  const size_t n = c->cfg.vocab_size;
+  CH_TRY(dalloc(c, SAMPLE_BLOCKS * 4, (void**)&c->sm_bmax));
+  CH_TRY(dalloc(c, (n * 2 + 15) / 16 * 16, (void**)&c->sm_keys));
+  CH_TRY(dalloc(c, 16, (void**)&c->sm_par));
+  CH_TRY(dalloc(c, (size_t)c->out_cap * 4, (void**)&c->sm_coins));
+  void* h = nullptr;
+  CH_TRY(dalloc(c, SAMPLE_HIST * 4, &h));
+  CH_HIP(c->dev, hipMemsetAsync(h, 0, SAMPLE_HIST * 4, c->dev->stream));
+  c->sm_hist = (unsigned*)h;
+  return 0;
+}
+
+// the sampler's arguments (sampler.rs:28-52) that the reference panics on or mishandles are refused
+bool sample_args_ok(float temperature, float topp) { return temperature >= 0.f && topp > 0.f && !std::isnan(topp); }
 
 
 // ---- batched prefill ---------------------------------------------------------------------------------------
@@ -2198,6 +2293,8 @@ int crabml_hip_llama_destroy(crabml_hip_llama_t* c) {
   for (int v = 0; v < 3; v++) {
     if (c->exec[v]) (void)hipGraphExecDestroy(c->exec[v]);
     if (c->graph[v]) (void)hipGraphDestroy(c->graph[v]);
+    if (c->sexec[v]) (void)hipGraphExecDestroy(c->sexec[v]);
+    if (c->sgraph[v]) (void)hipGraphDestroy(c->sgraph[v]);
   }
   for (auto& a : c->allocs) pool_free(c->dev, a.first, a.second);
   for (auto* b : c->held) crabml_hip_buf_release(b);
@@ -2262,6 +2359,44 @@ int crabml_hip_llama_decode_greedy(crabml_hip_llama_t* c, size_t token, size_t n
   return 0;
 }
 
+int crabml_hip_llama_decode_sample(crabml_hip_llama_t* c, size_t token, size_t n_steps, float temperature, float topp, const float* coins,
+                                   uint32_t* out_tokens) {
+  if (!c || (!out_tokens && n_steps) || (!coins && n_steps)) return CRABML_HIP_BAD_INPUT;
+  crabml_hip_device* dev = c->dev;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  if (c->tp > 1) CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: decode_sample does not run on tensor-parallel ranks");
+  if (std::isnan(temperature) || temperature < 0.f) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: temperature %g must be >= 0", (double)temperature);
+  if (temperature == 0.0f) return crabml_hip_llama_decode_greedy(c, token, n_steps, out_tokens);  // sampler.rs:29-31
+  if (!sample_args_ok(temperature, topp)) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: topp %g must be > 0", (double)topp);
+  for (size_t s = 0; s < n_steps; s++)
+    if (!(coins[s] >= 0.f && coins[s] < 1.f)) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: coin %zu = %g is not in [0, 1)", s, (double)coins[s]);
+  if (c->ext_kv) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: a context of the recorded-op queue samples on the host");
+  if (token >= c->cfg.vocab_size) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: token %zu out of range", token);
+  if (c->kv_len + n_steps > c->cfg.seq_len || n_steps > (size_t)c->out_cap)
+    CH_BAIL(dev, CRABML_HIP_TENSOR_ERROR, "llama: %zu steps do not fit the kv cache (%zu of %zu used)", n_steps, c->kv_len, c->cfg.seq_len);
+  if (n_steps == 0) return 0;
+  CH_TRY(sample_alloc(c));
+  const float par[2] = {temperature, topp};
+  CH_TRY(stage_h2d(c, c->sm_par, par, sizeof par));
+  CH_HIP(dev, hipMemcpyAsync(c->sm_coins, coins, n_steps * 4, hipMemcpyHostToDevice, dev->stream));
+  CH_TRY(set_state(c, token, c->kv_len, 0));
+  for (size_t s = 0; s < n_steps; s++) CH_TRY(run_step_sampled(c, c->kv_len + s));
+  c->kv_len += n_steps;
+  int fault = 0;
+  CH_HIP(dev, hipMemcpyAsync(out_tokens, c->out_tokens, n_steps * 4, hipMemcpyDeviceToHost, dev->stream));
+  CH_HIP(dev, hipMemcpyAsync(&fault, c->state + 5, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+  CH_HIP(dev, hipStreamSynchronize(dev->stream));
+  if (fault == SAMPLE_FAULT) {  // the context stays usable: the word is cleared, the caller sees the error
+    CH_HIP(dev, hipMemsetAsync(c->state + 5, 0, sizeof(int), dev->stream));
+    CH_HIP(dev, hipStreamSynchronize(dev->stream));
+    CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: nothing to sample (the logits hold a NaN or +inf, or the nucleus is empty)");
+  }
+  if (fault == 2) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a tensor-parallel peer's partial sums never arrived (poll timed out)");
+  if (fault) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a norm-epilogue gather timed out (workgroups not co-resident?)");
+  return 0;
+}
 
 int crabml_hip_llama_prefill(crabml_hip_llama_t* c, const uint32_t* tokens, size_t n, float* logits) {
   if (!c || (!tokens && n)) return CRABML_HIP_BAD_INPUT;
@@ -2371,6 +2506,62 @@ int crabml_hip_llama_debug_kv(crabml_hip_llama_t* c, size_t layer, int32_t which
 }
 
 // parity hook (crabml_hip_debug.h): k_attn_flash by itself, on caller-supplied q / K / V
+int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_t n, float temperature, float topp, float coin,
+                            uint32_t* token) {
+  if (!dev || !logits || !token || n == 0 || n > ((size_t)1 << 24)) return CRABML_HIP_BAD_INPUT;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  if (std::isnan(temperature) || temperature < 0.f) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_sample: temperature %g must be >= 0", (double)temperature);
+  const bool greedy = temperature == 0.0f;
+  if (!greedy && !sample_args_ok(temperature, topp)) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_sample: topp %g must be > 0", (double)topp);
+  if (!greedy && !(coin >= 0.f && coin < 1.f)) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_sample: coin %g is not in [0, 1)", (double)coin);
+  const size_t o_x = 0, o_keys = align_up(n * 4, 256), o_hist = align_up(o_keys + n * 2, 256), o_bmax = align_up(o_hist + SAMPLE_HIST * 4, 256),
+               o_par = o_bmax + 1024, o_coin = o_par + 256, o_state = o_coin + 256, o_out = o_state + 256, o_amv = o_out + 256,
+               o_ami = o_amv + ARGMAX_BLOCKS * 4, total = o_ami + ARGMAX_BLOCKS * 4;
+  char* base = nullptr;
+  CH_HIP(dev, hipMalloc((void**)&base, total));
+  hipStream_t st = dev->stream;
+  const float par[2] = {temperature, topp};
+  int* state = (int*)(base + o_state);
+  unsigned* outp = (unsigned*)(base + o_out);
+  int fault = 0;
+  uint32_t tok = 0;
+  hipError_t e = hipMemsetAsync(base + o_hist, 0, SAMPLE_HIST * 4, st);
+  if (e == hipSuccess) e = hipMemsetAsync(state, 0, 256, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_x, logits, n * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_par, par, sizeof par, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_coin, &coin, 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    const float* x = (const float*)(base + o_x);
+    if (greedy) {
+      k_argmax_partial<<<ARGMAX_BLOCKS, 256, 0, st>>>(x, (int)n, (float*)(base + o_amv), (int*)(base + o_ami), 0);
+      k_argmax_step<<<1, 64, 0, st>>>((const float*)(base + o_amv), (const int*)(base + o_ami), ARGMAX_BLOCKS, state, state + 1, state + 2, outp, 1,
+                                      state + 4, (int*)nullptr);
+    } else {
+      const SampleStep ss{(const float*)(base + o_par), (const float*)(base + o_coin), state, state + 1, state + 2, state + 4, outp, 1, state + 5};
+      unsigned short* keys = (unsigned short*)(base + o_keys);
+      unsigned* hist = (unsigned*)(base + o_hist);
+      k_sample_max<<<SAMPLE_BLOCKS, 256, 0, st>>>(x, (int)n, ss.par, (float*)(base + o_bmax));
+      k_sample_keys<<<SAMPLE_BLOCKS, 256, 0, st>>>(x, (int)n, ss.par, (const float*)(base + o_bmax), SAMPLE_BLOCKS,
+                                                   (const unsigned short*)dev->exp_table, keys, hist);
+      if (dev->strict_order)
+        k_sample_pick<true><<<1, SAMPLE_PICK_THREADS, 0, st>>>(keys, (int)n, hist, ss);
+      else
+        k_sample_pick<false><<<1, SAMPLE_PICK_THREADS, 0, st>>>(keys, (int)n, hist, ss);
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&tok, outp, 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(&fault, state + 5, 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(base);
+  if (e != hipSuccess) return hip_fail(dev, e, "debug_sample", __FILE__, __LINE__);
+  if (fault) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "debug_sample: nothing to sample (the logits hold a NaN or +inf, or the nucleus is empty)");
+  *token = tok;
+  return 0;
+}
+
 int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
                                      size_t n_kv, size_t head_dim, size_t seq, size_t slices, float* out, float* out2) {
   if (!dev || !q || !k || !v || !out || seq == 0 || n_kv == 0 || n_heads % n_kv != 0) return CRABML_HIP_BAD_INPUT;

@@ -138,6 +138,12 @@ class HipLlamaRunner {
     device_->check(crabml_hip_llama_decode_greedy(ctx_, token, steps, ids.data()));
     return ids;
   }
+  // n = coins.size() decode steps with Llama2Sampler::sample on the device (crabml_hip_llama_decode_sample), coin s for step s
+  std::vector<uint32_t> decode_sample(size_t token, float temperature, float topp, const std::vector<float>& coins) {
+    std::vector<uint32_t> ids(coins.size());
+    device_->check(crabml_hip_llama_decode_sample(ctx_, token, coins.size(), temperature, topp, coins.data(), ids.data()));
+    return ids;
+  }
   std::vector<uint8_t> debug_kv(size_t layer, bool v, bool f16) {
     size_t n = conf_.n_kv_heads / tp_size_ * seq_cap() * conf_.head_size() * (f16 ? 2 : 4);
     std::vector<uint8_t> out(n);

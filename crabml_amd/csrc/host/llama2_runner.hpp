@@ -4,8 +4,10 @@
 // :527-603, forward_ffn :605-638), so running it over HipTensor is what "crabml-llama2 runs unchanged"
 // means on this side of the boundary.  Llama architecture only (gemma/qwen2/phi2 are out of scope).
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <optional>
 #include <string>
 #include <vector>
@@ -110,6 +112,89 @@ inline size_t sample_argmax(const std::vector<float>& p) {
     if (!(p[best] > p[i])) best = i;
   return best;
 }
+
+// f16 <-> f32 as the half crate converts (IEEE round-to-nearest-even; to_f32 exact)
+inline uint16_t f32_to_f16_bits(float f) {
+  uint32_t x;
+  memcpy(&x, &f, 4);
+  const uint32_t sign = (x >> 16) & 0x8000u, ax = x & 0x7fffffffu;
+  if (ax >= 0x7f800000u) return (uint16_t)(sign | (ax > 0x7f800000u ? 0x7e00u | ((ax >> 13) & 0x3ffu) : 0x7c00u));
+  if (ax >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);  // rounds to 65520 or beyond: infinity
+  if (ax < 0x38800000u) {  // below 2^-14: an f16 subnormal (or zero); x * 2^24 is exact, rint rounds to nearest even
+    float v;
+    memcpy(&v, &ax, 4);
+    return (uint16_t)(sign | (uint32_t)std::nearbyint(v * 16777216.0f));
+  }
+  return (uint16_t)(sign | ((ax - 0x38000000u + 0xfffu + ((ax >> 13) & 1u)) >> 13));
+}
+inline float f16_bits_to_f32(uint16_t h) {
+  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
+  float v;
+  if (e == 0) {
+    v = (float)m * (1.0f / 16777216.0f);  // subnormal: m * 2^-24, exact
+    return sign ? -v : v;
+  }
+  const uint32_t x = sign | (e == 31 ? 0x7f800000u | (m << 13) : ((e + 112) << 23) | (m << 13));
+  memcpy(&v, &x, 4);
+  return v;
+}
+
+// Llama2Sampler (crabml-llama2/src/sampler.rs:10-130) with the caller's coin (sampler.rs:41-42 draws it from
+// rand::thread_rng()): temperature 0 = sample_argmax; otherwise logits / T, softmax through the f16 exp table
+// (cpu_device.rs:108-115, buf_f32.rs:29-35) and sample_topp -- also for topp >= 1, where the reference discards
+// sample_multi's result (sampler.rs:46-49).  The host baseline of crabml_hip_llama_decode_sample.
+class Llama2Sampler {
+ public:
+  Llama2Sampler(float temperature, float topp) : temperature_(temperature), topp_(topp), exp_(65536) {
+    for (uint32_t x = 0; x < 65536; x++) exp_[x] = f32_to_f16_bits(expf(f16_bits_to_f32((uint16_t)x)));
+  }
+  // logits are overwritten with the probabilities, as the reference's sample(&mut logits) does
+  size_t sample(std::vector<float>& logits, float coin) {
+    if (temperature_ == 0.0f) return sample_argmax(logits);
+    for (auto& l : logits) l /= temperature_;
+    softmax(logits);
+    return sample_topp(logits, coin);
+  }
+
+ private:
+  void softmax(std::vector<float>& a) const {  // sampler.rs:119-129
+    float max = NAN;
+    for (float v : a) max = std::fmax(max, v);  // f32::max: a NaN operand is ignored
+    float sum = 0.0f;
+    for (auto& v : a) {
+      v = f16_bits_to_f32(exp_[f32_to_f16_bits(v - max)]);
+      sum += v;
+    }
+    for (auto& v : a) v /= sum;
+  }
+  size_t sample_topp(const std::vector<float>& probs, float coin) {  // sampler.rs:66-107
+    const float cutoff = (1.0f - topp_) / (float)(probs.size() - 1);
+    idx_.clear();
+    for (size_t i = 0; i < probs.size(); i++)
+      if (probs[i] >= cutoff) idx_.push_back({probs[i], i});
+    if (idx_.empty()) throw Error(ErrorKind::Unexpected, "sampler: no candidate (the reference panics here)");
+    std::stable_sort(idx_.begin(), idx_.end(), [](const std::pair<float, size_t>& a, const std::pair<float, size_t>& b) { return a.first < b.first; });
+    float cum = 0.0f;
+    size_t last = idx_.size() - 1;
+    for (size_t k = 0; k < idx_.size(); k++) {
+      cum += idx_[k].first;
+      if (cum > topp_) {
+        last = k;
+        break;
+      }
+    }
+    const float r = coin * cum;
+    float cdf = 0.0f;
+    for (size_t k = 0; k <= last; k++) {
+      cdf += idx_[k].first;
+      if (cdf > r) return idx_[k].second;
+    }
+    return idx_[last].second;
+  }
+  float temperature_, topp_;
+  std::vector<uint16_t> exp_;
+  std::vector<std::pair<float, size_t>> idx_;
+};
 
 template <class T>
 class Llama2Runner {

@@ -46,6 +46,12 @@ PYBIND11_MODULE(_host, m) {
     return sample_argmax(v);
   });
 
+  // the runner's temperature / top-p sampler (sampler.rs:28-107) with the caller's coin; the logits are not modified
+  m.def("sample_llama2", [](py::array_t<float, py::array::c_style | py::array::forcecast> a, float temperature, float topp, float coin) {
+    std::vector<float> v(a.data(), a.data() + a.size());
+    return Llama2Sampler(temperature, topp).sample(v, coin);
+  });
+
   py::enum_<GGMLType>(m, "GGMLType")
       .value("F32", GGMLType::F32).value("F16", GGMLType::F16).value("Q4_0", GGMLType::Q4_0)
       .value("Q4_1", GGMLType::Q4_1).value("Q8_0", GGMLType::Q8_0).value("Q8_1", GGMLType::Q8_1)
@@ -107,6 +113,13 @@ PYBIND11_MODULE(_host, m) {
              return v;
            },
            py::arg("bytes") = (size_t)1 << 30, py::arg("reps") = 5)
+      .def("debug_sample",
+           [](HipTensorDevice& d, py::array_t<float, py::array::c_style | py::array::forcecast> logits, float temperature, float topp,
+              float coin) {
+             uint32_t tok = 0;
+             d.check(crabml_hip_debug_sample(d.raw(), logits.data(), (size_t)logits.size(), temperature, topp, coin, &tok));
+             return (size_t)tok;
+           })
       .def("debug_flash_attention",
            [](HipTensorDevice& d, py::array_t<float, py::array::c_style | py::array::forcecast> q,
               py::array_t<uint16_t, py::array::c_style | py::array::forcecast> k,
@@ -440,6 +453,35 @@ PYBIND11_MODULE(_host, m) {
            [](HipLlamaRunner& r, size_t token, size_t steps) {
              py::gil_scoped_release rel;
              return r.decode_greedy(token, steps);
+           })
+      .def("decode_sample",
+           [](HipLlamaRunner& r, size_t token, size_t steps, float temperature, float topp,
+              py::array_t<float, py::array::c_style | py::array::forcecast> coins) {
+             if ((size_t)coins.size() != steps) throw Error(ErrorKind::BadInput, "decode_sample: expected one coin per step");
+             std::vector<float> c(coins.data(), coins.data() + coins.size());
+             py::gil_scoped_release rel;
+             return r.decode_sample(token, temperature, topp, c);
+           })
+      // the host baseline of decode_sample: forward (logits to the host) + Llama2Sampler per step; returns (ids, seconds,
+      // of which in the host sampler)
+      .def("timed_decode_host_sample",
+           [](HipLlamaRunner& r, size_t token, float temperature, float topp, py::array_t<float, py::array::c_style | py::array::forcecast> coins) {
+             std::vector<float> c(coins.data(), coins.data() + coins.size());
+             py::gil_scoped_release rel;
+             Llama2Sampler sampler(temperature, topp);
+             std::vector<size_t> ids;
+             double sample_sec = 0.0;
+             const size_t pos = r.kv_cache_len();
+             const auto t0 = std::chrono::steady_clock::now();
+             for (size_t s = 0; s < c.size(); s++) {
+               std::vector<float> lg = r.forward(token, pos + s);
+               const auto ta = std::chrono::steady_clock::now();
+               token = sampler.sample(lg, c[s]);
+               sample_sec += std::chrono::duration<double>(std::chrono::steady_clock::now() - ta).count();
+               ids.push_back(token);
+             }
+             const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+             return std::make_tuple(ids, sec, sample_sec);
            })
       .def("debug_kv", [](HipLlamaRunner& r, size_t layer, bool v, bool f16) {
         std::vector<uint8_t> b = r.debug_kv(layer, v, f16);

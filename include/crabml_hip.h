@@ -266,6 +266,17 @@ int crabml_hip_llama_forward(crabml_hip_llama_t* ctx, size_t token, size_t pos, 
 /* n_steps greedy decode steps on device: forward(token), token = argmax (last maximum), ...; the n_steps
  * sampled ids are written to out_tokens (BLOCKS once, at the end). */
 int crabml_hip_llama_decode_greedy(crabml_hip_llama_t* ctx, size_t token, size_t n_steps, uint32_t* out_tokens);
+/* n_steps decode steps on device with Llama2Sampler::sample (crabml-llama2/src/sampler.rs:28-107): logits / temperature,
+ * softmax through the exp table, top-p over the candidates in the reference's ASCENDING order, token = the first element whose
+ * cdf exceeds coins[s] * cumulative.  The caller draws the n_steps coins (the reference: rand::thread_rng().gen_range(0.0..1.0)
+ * per token, sampler.rs:41-42), so with equal coins the tokens are a function of the logits.  temperature == 0 is
+ * decode_greedy.  topp >= 1 samples the whole vocabulary (the reference discards sample_multi's result, sampler.rs:46-49).
+ * Strict-order device: the reference's tokens bit for bit; fast device: the sums in parallel order.
+ * CRABML_HIP_BAD_INPUT: temperature < 0 or NaN; with temperature > 0 also topp <= 0 or NaN, a coin outside [0, 1).
+ * CRABML_HIP_UNEXPECTED: the logits hold a NaN or +inf, or the nucleus is empty (the reference panics; the cache has
+ * advanced).  CRABML_HIP_NOT_IMPLEMENTED: tp_size > 1.  Otherwise decode_greedy's contract (BLOCKS once, at the end). */
+int crabml_hip_llama_decode_sample(crabml_hip_llama_t* ctx, size_t token, size_t n_steps, float temperature, float topp,
+                                   const float* coins, uint32_t* out_tokens);
 /* The token loop of Llama2Runner::prefill (llama2.rs:111-129: `for (pos, token) in prompt_tokens: forward(&[token],
  * base_pos + pos)`) as batched passes of up to prefill_chunk rows: same KV cache contents and, in logits (nullable,
  * BLOCKS), the logits of the last prompt token.  The reference's own `_batched` flag is ignored (llama2.rs:114)

@@ -76,6 +76,12 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
 int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
                                           size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, float* out);
 
+/* The decode step's sampler (crabml_hip_llama_decode_sample: k_sample_max / k_sample_keys / k_sample_pick, or the arg-max
+ * kernels at temperature 0) on n arbitrary f32 logits (host pointer) with one coin, on this device's tier (strict order:
+ * the reference's token bit for bit).  Same argument checks and errors as decode_sample.  Blocks. */
+int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_t n, float temperature, float topp, float coin,
+                            uint32_t* token);
+
 /* ---- A/B switches and test hooks of the fused decode step (crabml_hip_llama_config_t.flags; the public bits are in
  * crabml_hip.h).  Every variant pair is bit-identical unless its comment says otherwise. */
 #define CRABML_HIP_LLAMA_NO_NORM_EPILOGUE 4 /* A/B: keep RMSNorm + quantize as its own launch (fast mode runs it in

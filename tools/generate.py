@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Token-id level counterpart of `crabml-cli generate` for the hip backend: load a llama GGUF file through the C++
-loader (crabml_amd/csrc/host/gguf.hpp), prefill a prompt in batched passes, decode greedily on the device.
-The tokenizer and the samplers other than greedy stay on the reference's side of the boundary (out of scope here),
-so the prompt is given as token ids.
+loader (crabml_amd/csrc/host/gguf.hpp), prefill a prompt in batched passes, decode on the device: greedily by default, with
+Llama2Sampler's temperature / top-p (crabml-llama2/src/sampler.rs) under --temperature > 0 -- the first token from the prompt's
+logits on the host (C++ Llama2Sampler), the rest by crabml_hip_llama_decode_sample, coins from a seeded generator.
+The tokenizer stays on the reference's side of the boundary (out of scope here), so the prompt is given as token ids.
 
 usage: generate.py model.gguf [--prompt 1,15043,3186] [--steps 64] [--seq-len N] [--f32-kv] [--strict]
+                   [--temperature 1.0 --topp 0.9 --seed 0]
        generate.py --synth tiny-gqa:Q4_K_M   (writes a synthetic file to a temp dir first: a self-contained demo)"""
 import argparse
 import os
@@ -24,6 +26,9 @@ ap.add_argument("--steps", type=int, default=32)
 ap.add_argument("--seq-len", type=int, default=0)
 ap.add_argument("--f32-kv", action="store_true")
 ap.add_argument("--strict", action="store_true", help="strict-order device: the reference's scalar summation order, bit for bit")
+ap.add_argument("--temperature", type=float, default=0.0, help="0 (default): greedy; the CLI's default is 1.0")
+ap.add_argument("--topp", type=float, default=0.9)
+ap.add_argument("--seed", type=int, default=0, help="seed of the coins (one uniform [0, 1) f32 per token)")
 a = ap.parse_args()
 
 path = a.gguf
@@ -54,9 +59,20 @@ r = ca.HipLlamaRunner(conf, weights, dev, seq_len, not a.f32_kv)
 t0 = time.perf_counter()
 logits = r.prefill(prompt)
 t_prefill = time.perf_counter() - t0
-first = int(len(logits) - 1 - logits[::-1].argmax())  # the LAST maximum (sampler.rs:109-116)
+import numpy as np  # noqa: E402
+
+coins = np.random.default_rng(a.seed).random(max(a.steps, 1), dtype=np.float32)
+if a.temperature > 0:
+    first = int(ca.sample_llama2(logits, a.temperature, a.topp, float(coins[0])))
+else:
+    first = int(len(logits) - 1 - logits[::-1].argmax())  # the LAST maximum (sampler.rs:109-116)
 t0 = time.perf_counter()
-ids = [first] + [int(t) for t in r.decode_greedy(first, a.steps - 1)] if a.steps > 1 else [first]
+if a.steps <= 1:
+    ids = [first]
+elif a.temperature > 0:
+    ids = [first] + [int(t) for t in r.decode_sample(first, a.steps - 1, a.temperature, a.topp, coins[1:a.steps])]
+else:
+    ids = [first] + [int(t) for t in r.decode_greedy(first, a.steps - 1)]
 t_decode = time.perf_counter() - t0
 print(f"prefill: {len(prompt)} tokens in {t_prefill * 1e3:.2f} ms ({len(prompt) / t_prefill:.0f} tok/s)")
 if a.steps > 1:
