@@ -173,6 +173,9 @@ struct crabml_hip_buf {
   size_t cap = 0;       // pool capacity in bytes
   size_t m = 0, k = 0;  // logical 2-D shape of quantized weights
   crabml_hip::WeightLayout wl;
+  // the f16 prompt GEMM's A' range check of this buffer's scales (gemm_f16w.hip), valid while version == f16w_range_ver
+  mutable uint64_t f16w_range_ver = 0;
+  mutable bool f16w_range_ok = false;
   // activation-quantization cache: matmul_vec re-quantizes its rhs on every call in the reference
   // (matmul_vec.rs:37-40); here q/k/v and gate/up share one pass.  `version` is bumped by every
   // op that writes the buffer, which invalidates the cache.

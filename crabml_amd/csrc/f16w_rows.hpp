@@ -38,9 +38,16 @@ __device__ __forceinline__ int f16w_slot_elem(int slot) {
   const int s = slot >> 3, e = slot & 7;
   return (e >= 4 ? 16 : 0) + 4 * s + ((e >> 1) & 1) + 2 * (e & 1);
 }
+// B' range: |q d| past 65504 is written as +-inf.  Every B' writer raises the pass's flag (ovf, nullable: an ordinary store of 1)
+// when a value it writes is +-inf -- the prompt pass then recomputes the chunk on the int8 GEMM (fused.hip prefill_chunk)
+__device__ __forceinline__ bool f16w_is_inf(unsigned short h) { return (h & 0x7fffu) == 0x7c00u; }
+__device__ __forceinline__ void f16w_flag(bool inf, int* ovf) {
+  if (inf && ovf != nullptr) *ovf = 1;
+}
 // one 8-slot group t = 4 kb + s of a row's B' from its FINISHED planes p (q | d at off_d): xrow[kb * 32 + 8 s ..]
 template <int ORDER>
-__device__ __forceinline__ void rows_to_f16_piece(const char* __restrict__ p, size_t off_d, int t, unsigned short* __restrict__ xrow) {
+__device__ __forceinline__ void rows_to_f16_piece(const char* __restrict__ p, size_t off_d, int t, unsigned short* __restrict__ xrow,
+                                                  int* ovf) {
   const int kb = t >> 2, s = t & 3;
   float d;
   const signed char* q;
@@ -64,8 +71,13 @@ __device__ __forceinline__ void rows_to_f16_piece(const char* __restrict__ p, si
     for (int e = 0; e < 8; e++) at[e] = f16w_slot_elem(8 * s + e);
   }
   unsigned short o[8];
+  bool inf = false;
 #pragma unroll
-  for (int e = 0; e < 8; e++) o[e] = f2h((float)q[at[e]] * d);  // (Q8_0: 7-bit x 11-bit, exact in f32, one rounding; Q8_K: f32 d, two)
+  for (int e = 0; e < 8; e++) {
+    o[e] = f2h((float)q[at[e]] * d);  // (Q8_0: 7-bit x 11-bit, exact in f32, one rounding; Q8_K: f32 d, two)
+    inf |= f16w_is_inf(o[e]);
+  }
+  f16w_flag(inf, ovf);
   *(i32x4*)(xrow + kb * 32 + 8 * s) = i32x4{(int)(o[0] | ((unsigned)o[1] << 16)), (int)(o[2] | ((unsigned)o[3] << 16)),
                                             (int)(o[4] | ((unsigned)o[5] << 16)), (int)(o[6] | ((unsigned)o[7] << 16))};
 }

@@ -197,6 +197,7 @@ struct crabml_hip_llama {
   char *pf_act_dim = nullptr, *pf_act_hid = nullptr;
   float* pf_split = nullptr;  // ... and pf_split_floats of scratch for the partial tiles of its k pieces
   size_t pf_split_floats = 0;
+  int* pf_ovf = nullptr;   // raised by the writers of pf_xh / pf_xh2 when a B' value is +-inf (prefill_chunk recomputes the chunk)
   void* pf_xh2 = nullptr;  // a second one: the gate | up launch reads pf_xh while its epilogue writes ffn_down's
   void* pf_xh = nullptr;  // the fast pass's f16 GEMMs: the current rhs rows as pre-scaled f16 (gemm_f16w.hip), gemm_f16w_xh_bytes(cap, max(dim, hidden))
   float* pf_scores = nullptr;          // long prompts: [PF_LONG_ROWS][n_heads][seq_len] f32 scores
@@ -1177,6 +1178,8 @@ int prefill_alloc(crabml_hip_llama* c, size_t cap) {
     c->pf_split_floats = (cap + 1024) * (dim + 2 * kv_dim > hidden ? dim + 2 * kv_dim : hidden);
     CH_TRY(A(c->pf_split_floats * 4, (void**)&c->pf_split));
     CH_HIP(c->dev, hipMemsetAsync(c->pf_xh, 0, xb, c->dev->stream));
+    CH_TRY(A(16, (void**)&c->pf_ovf));
+    CH_HIP(c->dev, hipMemsetAsync(c->pf_ovf, 0, 16, c->dev->stream));
   }
   c->pf_cap = cap;
   return 0;
@@ -1263,7 +1266,8 @@ int launch_attn_long_rows(crabml_hip_llama* c, int l, int B) {
   return rc == 0 ? 1 : -1;
 }
 
-int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t pos0, bool want_logits) {
+// allow_f16w = false: the pass keeps the int8 GEMMs (prefill_chunk's recomputation of a chunk whose B' overflowed f16)
+int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t pos0, bool want_logits, bool allow_f16w, bool* f16w_used) {
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
   const auto& g = c->cfg;
@@ -1307,22 +1311,24 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
     const char* e = getenv("CRABML_HIP_F16W_MIN");
     return h && h[0] == '1' && e ? atoi(e) : 32;
   }();
-  const bool f16w = !strict && !gemm_exact_hook && !f16w_off && !(g.flags & CRABML_HIP_LLAMA_PREFILL_INT8_GEMM) &&
+  const bool f16w = allow_f16w && !strict && !gemm_exact_hook && !f16w_off && !(g.flags & CRABML_HIP_LLAMA_PREFILL_INT8_GEMM) &&
                     (c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1 || c->qt == CRABML_HIP_Q8_K) && c->pf_xh != nullptr && B >= f16w_min;  // (shorter passes: the int8 kernels / the GEMV)
+  *f16w_used = f16w;
+  int* const ovf = c->pf_ovf;
   // CpuTensorBuf::quantize for the rhs of matmul_vec (buf/api.rs:142-159): F32 weights take the rows as they are
   const void* xh_of = nullptr;  // the planes c->pf_xh was made from (reset whenever planes are rewritten) ...
   int xh_order = -1;            // ... and the k-slot order it is in (gemm_f16w_order of the weight format)
   auto rows_to_f16 = [&](const crabml_hip_buf* w, const void* act, int k) {
     const int order = gemm_f16w_order(w->dtype);
     if (xh_of == act && xh_order == order) return;
-    launch_rows_to_f16(st, c->qt, w->dtype, act, B, (size_t)k, c->pf_xh);
+    launch_rows_to_f16(st, c->qt, w->dtype, act, B, (size_t)k, c->pf_xh, ovf);
     xh_of = act;
     xh_order = order;
   };
   // ... written by the kernel that quantizes the rows when the GEMM that reads them next is the f16 one (f16w_rows.hpp: the same
   // bits as k_rows_to_f16 from the finished planes, one launch fewer per GEMM; A/B: CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS)
   auto xh_target = [&](const crabml_hip_buf* next, int k, int* order) -> void* {
-    if (!f16w || next == nullptr || (g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS) || !gemm_f16w_covers(next->dtype, c->qt) ||
+    if (!f16w || next == nullptr || (g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS) || !gemm_f16w_takes(dev, next, c->qt) ||
         (c->qt == CRABML_HIP_Q8_K && k % 256 != 0))
       return nullptr;
     *order = gemm_f16w_order(next->dtype);
@@ -1333,7 +1339,7 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
     if (c->qt == CRABML_HIP_F32) return src;
     int order = 0;
     void* xh = xh_target(next, n, &order);
-    launch_quantize_act_rows(st, c->qt, src, B, (size_t)n, planes, xh, order);
+    launch_quantize_act_rows(st, c->qt, src, B, (size_t)n, planes, xh, order, ovf);
     xh_of = xh ? planes : nullptr;
     xh_order = order;
     return planes;
@@ -1342,7 +1348,7 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
   auto gemm = [&](const crabml_hip_buf* w, int m, int k, const void* act, float* out, int* defer = nullptr) -> int {
     if (defer) *defer = 0;
     if (g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS) defer = nullptr;  // (A/B: every reduce its own launch)
-    if (f16w && gemm_f16w_covers(w->dtype, c->qt) && (c->qt != CRABML_HIP_Q8_K || k % 256 == 0)) {
+    if (f16w && gemm_f16w_takes(dev, w, c->qt) && (c->qt != CRABML_HIP_Q8_K || k % 256 == 0)) {
       rows_to_f16(w, act, k);
       const size_t mm = (size_t)m;
       if (launch_gemm_f16w(dev, &w, &mm, 1, (size_t)k, c->pf_xh, B, &out, c->pf_split, c->pf_split_floats, nullptr, nullptr, defer)) return 0;
@@ -1384,7 +1390,7 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
     if (!fuse_k && !rows_1024 && (dim == 4096 || dim == 8192) && !(g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS)) {
 #define CRABML_NQW(E_, Q_)                                                                                                            \
   k_norm_quant_rows_w<E_, Q_><<<rows, 256, 0, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux, \
-                                                    half, xh, c->pf_split, pstride, nparts)
+                                                    half, xh, c->pf_split, pstride, nparts, ovf)
       if (dim == 4096) {
         if (q81)
           CRABML_NQW(16, true);
@@ -1404,10 +1410,10 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
     if (fuse_k) {
       if (dim <= 4096)
         k_norm_quant_rows_k<4><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_xn, c->pf_act_dim, ald.total, ald.off_d,
-                                                            ald.off_aux, ald.off_p, half, xh, order, c->pf_split, pstride, nparts);
+                                                            ald.off_aux, ald.off_p, half, xh, order, c->pf_split, pstride, nparts, ovf);
       else
         k_norm_quant_rows_k<12><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_xn, c->pf_act_dim, ald.total, ald.off_d,
-                                                             ald.off_aux, ald.off_p, half, xh, order, c->pf_split, pstride, nparts);
+                                                             ald.off_aux, ald.off_p, half, xh, order, c->pf_split, pstride, nparts, ovf);
       xh_of = xh ? c->pf_act_dim : nullptr;
       xh_order = order;
       return c->pf_act_dim;
@@ -1415,7 +1421,7 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
 #define CRABML_NQR(NIT_, Q_)                                                                                                         \
   if (xh || nparts > 0)                                                                                                              \
     k_norm_quant_rows_h<NIT_, Q_><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d,  \
-                                                                ald.off_aux, half, xh, c->pf_split, pstride, nparts);                \
+                                                                ald.off_aux, half, xh, c->pf_split, pstride, nparts, ovf);           \
   else                                                                                                                               \
     k_norm_quant_rows<NIT_, Q_><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d,    \
                                                               ald.off_aux, half)
@@ -1448,7 +1454,7 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
       a = quant_rows(c->pf_xn, dim, c->pf_act_dim, c->wq[l]);
     }
     bool qkv_done = false;  // llama2.rs:244-246
-    if (f16w && gemm_f16w_covers(c->wq[l]->dtype, c->qt) && c->wk[l]->dtype == c->wq[l]->dtype && c->wv[l]->dtype == c->wq[l]->dtype) {
+    if (f16w && gemm_f16w_takes(dev, c->wq[l], c->qt) && c->wk[l]->dtype == c->wq[l]->dtype && c->wv[l]->dtype == c->wq[l]->dtype) {
       // the three GEMMs of the same rhs as ONE launch (the 1024-row k / v matrices alone leave most of the chip idle)
       rows_to_f16(c->wq[l], a, dim);
       const crabml_hip_buf* ws[3] = {c->wq[l], c->wk[l], c->wv[l]};
@@ -1507,7 +1513,7 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
     }
     bool gu_done = false;  // llama2.rs:620-630
     int h_done = 0;        // the launch stored h = silu(g) * u (pf_g) instead of g and u
-    if (f16w && gemm_f16w_covers(c->gate[l]->dtype, c->qt) && c->up[l]->dtype == c->gate[l]->dtype) {
+    if (f16w && gemm_f16w_takes(dev, c->gate[l], c->qt) && c->up[l]->dtype == c->gate[l]->dtype) {
       // gate and up as ONE launch: 2 x 448 workgroups fill the last round of the chip better than 448 twice -- and, where 64-row tiles
       // of both cover the chip, with SiLU * mul as the epilogue (a wave holds the same 16 rows of both matrices)
       rows_to_f16(c->gate[l], a, dim);
@@ -1526,6 +1532,7 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
         hq.off_aux = alh.off_aux;
         hq.q81 = c->qt == CRABML_HIP_Q8_1;
         hq.xh = xh_target(c->down[l], hidden, &hq_order) ? (unsigned short*)c->pf_xh2 : nullptr;
+        hq.ovf = ovf;
       }
       gu_done = launch_gemm_f16w(dev, ws, ms, 2, (size_t)dim, c->pf_xh, B, outs, c->pf_split, c->pf_split_floats,
                                  epi ? (const unsigned short*)dev->exp_table : nullptr, epi ? &h_done : nullptr, nullptr, &hq);
@@ -1550,10 +1557,10 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
       unsigned short* xh = (unsigned short*)xh_target(c->down[l], hidden, &order);
       if (c->qt == CRABML_HIP_Q8_1 && xh)
         k_gateup_epi_quant_h<true><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
-                                                       alh.off_d, alh.off_aux, xh);
+                                                       alh.off_d, alh.off_aux, xh, ovf);
       else if (xh)
         k_gateup_epi_quant_h<false><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
-                                                        alh.off_d, alh.off_aux, xh);
+                                                        alh.off_d, alh.off_aux, xh, ovf);
       else if (c->qt == CRABML_HIP_Q8_1)
         k_gateup_epi_quant<true><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
                                                      alh.off_d, alh.off_aux);
@@ -1590,6 +1597,22 @@ int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t 
   }
   CH_HIP(dev, hipGetLastError());
   return 0;
+}
+
+// One chunk of the prompt pass.  The f16 GEMM's B' = q * d overflows f16 where the int8 GEMM does not (activations past 65504 -- a
+// few massive channels of a real checkpoint; the rows' f16 scales reach about 8.3e6): the writers of B' raise pf_ovf, read here once
+// per chunk, and a chunk that raised it is computed again from its token embeddings with the int8 GEMMs -- it overwrites its own KV
+// rows and logits; the caller advances kv_len once.  Chunks that do not overflow keep their bits.
+int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t pos0, bool want_logits) {
+  bool f16w = false;
+  CH_TRY(prefill_chunk_pass(c, tokens, B, pos0, want_logits, true, &f16w));
+  if (!f16w) return 0;
+  int h = 0;
+  CH_HIP(c->dev, hipMemcpyAsync(&h, c->pf_ovf, sizeof h, hipMemcpyDeviceToHost, c->dev->stream));
+  CH_HIP(c->dev, hipStreamSynchronize(c->dev->stream));
+  if (h == 0) return 0;
+  CH_HIP(c->dev, hipMemsetAsync(c->pf_ovf, 0, sizeof h, c->dev->stream));
+  return prefill_chunk_pass(c, tokens, B, pos0, want_logits, false, &f16w);
 }
 
 int set_state(crabml_hip_llama* c, size_t token, size_t pos, int step, const unsigned* serial = nullptr) {
@@ -2016,6 +2039,11 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
     c->down.push_back(hold(w->ffn_down_weight[l]));
     c->up.push_back(hold(w->ffn_up_weight[l]));
   }
+  // the f16 prompt GEMM's A' range check of every matrix (gemm_f16w_takes: one reduction over the scale plane, read back), here
+  // once rather than inside the first prompt pass
+  if (rc == 0 && !dev->strict_order && tp == 1 && (qt == CRABML_HIP_Q8_0 || qt == CRABML_HIP_Q8_1 || qt == CRABML_HIP_Q8_K))
+    for (size_t l = 0; l < g.n_layers; l++)
+      for (const crabml_hip_buf* m : {c->wq[l], c->wk[l], c->wv[l], c->wo[l], c->gate[l], c->up[l], c->down[l]}) (void)gemm_f16w_takes(dev, m, qt);
   auto A = [&](size_t bytes, void** p) {
     if (rc == 0) rc = dalloc(c, bytes, p);
   };

@@ -51,23 +51,23 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // Q6_K weights: chunk cc = (super-block, half), g, step s: element 128 half + 32 (g >> 1) + 16 (g & 1) + 4 s + k (e < 4), + 64 (e >= 4)
 template <int ORDER>  // 0: Q8_0 / Q8_1 rows (block order); 1: Q8_K rows for Q4_K weights; 2: Q8_K rows for Q6_K weights
 __global__ __launch_bounds__(256) void k_rows_to_f16(const char* __restrict__ planes, size_t row_stride, size_t off_d, int nb,
-                                                     unsigned short* __restrict__ xh) {
+                                                     unsigned short* __restrict__ xh, int* __restrict__ ovf) {
   const size_t col = blockIdx.y;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;  // one thread per (block, 8-slot group)
   if (t >= nb * 4) return;
-  rows_to_f16_piece<ORDER>(planes + col * row_stride, off_d, t, xh + col * (size_t)nb * 32);
+  rows_to_f16_piece<ORDER>(planes + col * row_stride, off_d, t, xh + col * (size_t)nb * 32, ovf);
 }
 // planes: `rows` sets of activation planes (act_layout(act_qtype, k)); the slot order is the one the weight format w_dtype reads
 int gemm_f16w_order(uint32_t w_dtype) { return w_dtype == CRABML_HIP_Q4_K ? 1 : w_dtype == CRABML_HIP_Q6_K ? 2 : 0; }
-bool launch_rows_to_f16(hipStream_t st, uint32_t act_qtype, uint32_t w_dtype, const void* planes, size_t rows, size_t k, void* xh) {
+bool launch_rows_to_f16(hipStream_t st, uint32_t act_qtype, uint32_t w_dtype, const void* planes, size_t rows, size_t k, void* xh, int* ovf) {
   if (!gemm_f16w_covers(w_dtype, act_qtype) || (act_qtype == CRABML_HIP_Q8_K && k % 256 != 0)) return false;
   const ActLayout al = act_layout(act_qtype, k);
   const int nb = (int)(k / 32);
   const dim3 grid((unsigned)((nb * 4 + 255) / 256), (unsigned)rows);
   switch (gemm_f16w_order(w_dtype)) {
-    case 0: k_rows_to_f16<0><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh); break;
-    case 1: k_rows_to_f16<1><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh); break;
-    default: k_rows_to_f16<2><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh); break;
+    case 0: k_rows_to_f16<0><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh, ovf); break;
+    case 1: k_rows_to_f16<1><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh, ovf); break;
+    default: k_rows_to_f16<2><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh, ovf); break;
   }
   return true;
 }
@@ -310,7 +310,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
   // byte offset per thread, advanced by a chunk = 256 bytes per fetch (the fetches come in chunk order), against a scalar base per
   // piece -- 16 columns further each (global_load ... s[base], v offset: no per-piece pointer registers).  Columns past n (a ragged
   // last tile) and the look-ahead of the last iterations read whatever follows in xh -- launch_gemm_f16w's contract keeps that
-  // inside the allocation; finite or not, it meets only output columns that are never stored, zero weights, or is never consumed.
+  // inside the allocation; finite or not, it meets only output columns that are never stored, or is never consumed.  The k-slots
+  // past a ragged row's end (nb % KCH != 0) read the next column's first blocks -- finite B' (a pass whose B' overflowed is computed
+  // again without this GEMM: prefill_chunk) -- and, for the last column, the blocks behind it, which launch_gemm_f16w zeroes: zero
+  // weights times a finite value add exactly 0 (times +-inf or NaN they would make NaN).
   // register sets of B' pieces in flight (one wave per SIMD: the longer look-ahead; the 32-byte-per-lane formats with two fragments:
   // one set -- B' is L2-resident and a chunk of 64 MFMAs per wave is longer than an L2 round trip)
   constexpr int NBD = (F == 1 && WF == WF_Q4_0) ? 4 : (F == 2 && (WF == WF_Q8_0 || WF == WF_Q6_K)) ? 1 : 2;
@@ -487,14 +490,19 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
         if (hq.xh != nullptr) {
           const float ds = h2f(dh);
           unsigned short* xr = hq.xh + ((size_t)col * nbh + hb) * 32;
+          bool inf = false;
 #pragma unroll
           for (int s4 = 0; s4 < 4; s4++) {
             unsigned short o[8];
 #pragma unroll
-            for (int e = 0; e < 8; e++) o[e] = f16w_value(q[f16w_slot_elem(8 * s4 + e)], ds);
+            for (int e = 0; e < 8; e++) {
+              o[e] = f16w_value(q[f16w_slot_elem(8 * s4 + e)], ds);
+              inf |= f16w_is_inf(o[e]);
+            }
             *(i32x4*)(xr + 8 * s4) = i32x4{(int)(o[0] | ((unsigned)o[1] << 16)), (int)(o[2] | ((unsigned)o[3] << 16)),
                                            (int)(o[4] | ((unsigned)o[5] << 16)), (int)(o[6] | ((unsigned)o[7] << 16))};
           }
+          f16w_flag(inf, hq.ovf);
         }
       }
       return;
@@ -566,6 +574,60 @@ static bool launch_f16w_t(crabml_hip_device* dev, const F16wMats& mats, int row_
   return true;
 }
 size_t gemm_f16w_xh_bytes(size_t rows, size_t k) { return ((rows + 127) / 128 * 128) * k * 2 + 4096; }
+
+// A' range: 1 in *bad when some block's scales can put an |A'| above 65504 (f16: +-inf, and inf times a zero B' slot is NaN) -- the
+// largest quant magnitude of the format times the block's scale, as the kernel rounds it (Q4_K: the largest 6-bit scale and minimum,
+// 63; Q6_K: the super-block's own int8 scales); a non-finite scale counts as out of range
+__global__ __launch_bounds__(256) void k_f16w_range(const char* __restrict__ sc, const signed char* __restrict__ sc6,
+                                                    const unsigned short* __restrict__ d6, size_t nblk, int wf, int* __restrict__ bad) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nblk) return;
+  float a = 0.0f;
+  if (wf == WF_Q4_0 || wf == WF_Q8_0) {
+    a = (wf == WF_Q4_0 ? 8.0f : 128.0f) * fabsf(h2f(((const unsigned short*)sc)[i]));  // |q - 8| <= 8, |q| <= 128: exact products
+  } else if (wf == WF_Q4_1) {
+    const unsigned dm = ((const unsigned*)sc)[i];
+    a = 15.0f * fabsf(h2f((unsigned short)(dm & 0xffffu))) + fabsf(h2f((unsigned short)(dm >> 16)));  // n d + m, n <= 15
+  } else if (wf == WF_Q4_K) {
+    const unsigned h = ((const unsigned*)sc)[4 * i];
+    const float c1 = h2f(f2h(63.0f * h2f((unsigned short)(h & 0xffffu)))), c2 = h2f(f2h(63.0f * h2f((unsigned short)(h >> 16))));
+    a = 15.0f * fabsf(c1) + fabsf(c2);  // n c1 - c2, n <= 15
+  } else {
+    const float d = h2f(d6[i]);
+    for (int j = 0; j < 16; j++) a = fmaxf(a, 32.0f * fabsf(h2f(f2h(d * (float)sc6[16 * i + j]))));  // (q - 32) c, |q - 32| <= 32
+    if (!(fabsf(d) <= 65504.0f)) a = d;
+  }
+  if (!(a <= 65504.0f)) *bad = 1;
+}
+static int f16w_wf(uint32_t dt) {
+  return dt == CRABML_HIP_Q8_0 ? WF_Q8_0 : dt == CRABML_HIP_Q4_K ? WF_Q4_K : dt == CRABML_HIP_Q6_K ? WF_Q6_K : dt == CRABML_HIP_Q4_1 ? WF_Q4_1 : WF_Q4_0;
+}
+// once per weight buffer (and per version of its contents): one reduction over the scale plane, read back -- blocks the stream the
+// first time (a fast-device model context asks for every matrix when it is created)
+static bool f16w_range_ok(crabml_hip_device* dev, const crabml_hip_buf* w) {
+  if (w->f16w_range_ver == w->version) return w->f16w_range_ok;
+  void* d = nullptr;
+  size_t cap = 0;
+  if (pool_alloc(dev, 16, &d, &cap) != 0) return false;
+  const char* base = (const char*)w->ptr + w->wl.off_scale;
+  const size_t nblk = w->wl.n_blocks;
+  int bad = 1;
+  hipError_t e = hipMemsetAsync(d, 0, 4, dev->stream);
+  if (e == hipSuccess && nblk > 0)
+    k_f16w_range<<<(unsigned)((nblk + 255) / 256), 256, 0, dev->stream>>>(base, (const signed char*)(base + nblk * 64),
+                                                                          (const unsigned short*)(base + nblk * 80), nblk,
+                                                                          f16w_wf(w->dtype), (int*)d);
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, d, 4, hipMemcpyDeviceToHost, dev->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+  pool_free(dev, d, cap);
+  if (e != hipSuccess) return false;
+  w->f16w_range_ok = bad == 0;
+  w->f16w_range_ver = w->version;
+  return w->f16w_range_ok;
+}
+bool gemm_f16w_takes(crabml_hip_device* dev, const crabml_hip_buf* w, uint32_t act_qtype) {
+  return gemm_f16w_covers(w->dtype, act_qtype) && f16w_range_ok(dev, w);
+}
 // the weight formats the kernel covers, and the rows' format each pairs with (CpuTensorBuf::quantize's choice: buf/api.rs:142-159)
 bool gemm_f16w_covers(uint32_t w_dtype, uint32_t act_qtype) {
   if (act_qtype == CRABML_HIP_Q8_0) return w_dtype == CRABML_HIP_Q4_0 || w_dtype == CRABML_HIP_Q8_0;
@@ -596,9 +658,9 @@ static bool launch_f16w_fmt(crabml_hip_device* dev, const F16wMats& mats, int ro
 // row tiles, a long k), any short pass -- the k range is cut into 2 / 4 / 8 pieces, one workgroup each: piece 0 writes out, the
 // others their own partial buffers in ws, and k_addn_f32 adds them in piece order.  (Measured and not kept: the pieces added with
 // f32 atomics onto a zeroed output -- 32.4k -> 30.1k prompt tok/s, and the sum's order would vary from run to run.)
-bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, const size_t* m, int nw, size_t k, const void* xh, size_t b,
+bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, const size_t* m, int nw, size_t k, void* xh, size_t b,
                       float* const* out, float* ws, size_t ws_floats, const unsigned short* gu_exp_tab, int* gu_done, int* defer_parts,
-                      const F16wHQuant* hq) {
+                      const F16wHQuant* hq, F16wForce* force) {
   if (gu_done) *gu_done = 0;
   if (defer_parts) *defer_parts = 0;
   if (nw < 1 || nw > 3 || k % 32 != 0 || b < 16) return false;
@@ -606,7 +668,7 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
   if (dt != CRABML_HIP_Q4_0 && dt != CRABML_HIP_Q8_0 && dt != CRABML_HIP_Q4_K && dt != CRABML_HIP_Q6_K && dt != CRABML_HIP_Q4_1) return false;
   if ((dt == CRABML_HIP_Q4_K || dt == CRABML_HIP_Q6_K) && k % 256 != 0) return false;
   for (int j = 0; j < nw; j++)
-    if (w[j]->dtype != dt || m[j] % 4 != 0) return false;
+    if (w[j]->dtype != dt || m[j] % 4 != 0 || !f16w_range_ok(dev, w[j])) return false;
   static const int variant = [] {  // lab hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_F16W=n): 1 = two fragments, 3 = one; +8 = never split k; +16 = T = 8 always; +32 = k pieces of >= 8 chunks; +64 = no gate | up epilogue; +512 = T = 4 always; +1024 = narrow launches as <2, 4>
     const char* h = getenv("CRABML_HIP_TEST_HOOKS");
     const char* e = getenv("CRABML_HIP_F16W");
@@ -615,6 +677,10 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
   size_t mtot = 0;
   for (int j = 0; j < nw; j++) mtot += m[j];
   int T = f16w_col_tiles_per_wave(b, variant);
+  if (force && force->T > 0) {
+    if (force->T != 2 && force->T != 4 && force->T != 8) return false;
+    T = force->T;
+  }
   size_t cw = 16 * (size_t)T, col128 = (b + cw - 1) / cw;  // (column tiles of the launch)
   // two fragments per wave (every B' fragment read from LDS feeds two MFMAs) when 128-row tiles still cover the chip
   int F = ((mtot + 127) / 128) * col128 >= (size_t)dev->n_cu ? 2 : 1;
@@ -626,10 +692,18 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
   }
   if ((variant & 7) == 1) F = 2;
   if ((variant & 7) == 3) F = 1;
+  if (force && force->F > 0) {
+    if (force->F != 1 && force->F != 2) return false;
+    F = force->F;
+  }
   // gate | up with the SiLU * mul epilogue (out[0] = h, out[1] untouched): when 64-row tiles of both matrices cover the chip without
   // cutting k
-  const bool gu = gu_exp_tab != nullptr && gu_done != nullptr && nw == 2 && m[0] == m[1] && !(variant & 64) &&
-                  ((m[0] + 63) / 64) * col128 * 2 >= (size_t)dev->n_cu * 3;
+  const bool gu_ok = gu_exp_tab != nullptr && gu_done != nullptr && nw == 2 && m[0] == m[1];
+  bool gu = gu_ok && !(variant & 64) && ((m[0] + 63) / 64) * col128 * 2 >= (size_t)dev->n_cu * 3;
+  if (force && force->gu >= 0) {
+    if (force->gu > 0 && !gu_ok) return false;
+    gu = force->gu > 0;
+  }
   if (gu) F = 2;
   F16wMats mats{};
   mats.exp_tab = gu_exp_tab;
@@ -667,6 +741,23 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
     while (ksplit < 8 && (size_t)row_tiles * col128 * ksplit < (size_t)dev->n_cu * 3 / 2 && chunks % (size_t)(4 * ksplit) == 0 &&
            chunks / (size_t)(2 * ksplit) >= (size_t)((variant & 32) ? 8 : 4) && (size_t)(2 * ksplit - 1) * before <= ws_floats)
       ksplit *= 2;
+  if (force && force->ksplit > 0) {  // every piece must hold at least one chunk (the kernel's per_piece), the partials must fit ws
+    const int ks = force->ksplit, all_chunks = (int)((k / 32 + 3) / 4);
+    const int per_piece = (dt == CRABML_HIP_Q4_K || dt == CRABML_HIP_Q6_K) ? (((all_chunks + ks - 1) / ks + 1) & ~1) : (all_chunks + ks - 1) / ks;
+    if ((ks != 1 && ks != 2 && ks != 4 && ks != 8) || (ks > 1 && (gu || ws == nullptr || (size_t)(ks - 1) * before > ws_floats)) ||
+        (ks - 1) * per_piece >= all_chunks)
+      return false;
+    ksplit = ks;
+  }
+  if (force) {
+    force->used_F = F;
+    force->used_T = T;
+    force->used_ksplit = ksplit;
+    force->used_gu = gu ? 1 : 0;
+  }
+  // the last column's slots past the row's end read the blocks behind it: zeros, whatever a longer pass (or anything else) left there
+  const size_t nb = k / 32, pad = (nb + 3) / 4 * 4 - nb;
+  if (pad != 0 && hipMemsetAsync((char*)xh + b * k * 2, 0, pad * 64, dev->stream) != hipSuccess) return false;
   bool ok;
   if (dt == CRABML_HIP_Q8_0)
     ok = launch_f16w_fmt<WF_Q8_0>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);

@@ -375,6 +375,42 @@ class HipTensor {
     device_->check(crabml_hip_debug_gemm_ints(device_->raw(), buf_.get(), m, k, x.buf_.get(), b, ints.data(), out.data()));
     return {ints, out};
   }
+  // the fast prompt pass's f16 GEMM by itself (crabml_hip_debug_gemm_f16w): this weight and up to two more of its format against
+  // x = (b, k) rows; force = (F, T, ksplit, gate | up), 0 / -1 = the launcher's choice
+  struct F16wDebug {
+    std::vector<std::vector<float>> out;
+    std::vector<uint16_t> xh, hxh;
+    std::vector<uint8_t> hq;
+    std::vector<int32_t> used;
+  };
+  F16wDebug debug_gemm_f16w(const std::vector<HipTensor>& more, const HipTensor& x, size_t b, int rows_path, uint16_t junk,
+                            const std::vector<int32_t>& force) const {
+    if (more.size() > 2) throw Error(ErrorKind::TensorError, "debug_gemm_f16w: at most three matrices");
+    if (force.size() != 4) throw Error(ErrorKind::TensorError, "debug_gemm_f16w: force = (F, T, ksplit, gate | up)");
+    const size_t k = shape()[1];
+    std::vector<const crabml_hip_buf_t*> ws{buf_.get()};
+    std::vector<size_t> ms{shape()[0]};
+    for (const HipTensor& t : more) {
+      ws.push_back(t.buf_.get());
+      ms.push_back(t.shape()[0]);
+    }
+    F16wDebug r;
+    std::vector<float*> outs;
+    for (size_t m : ms) r.out.emplace_back(b * m);
+    for (auto& o : r.out) outs.push_back(o.data());
+    r.xh.resize(b * k);
+    r.used.resize(8);
+    const bool hplanes = force[3] == 2;
+    if (hplanes) {
+      r.hq.resize(b * (ms[0] + ms[0] / 4 + 768));  // >= act_layout's total: q | d | aux, each plane 256-byte aligned
+      r.hxh.resize(b * ms[0]);
+    }
+    device_->check(crabml_hip_debug_gemm_f16w(device_->raw(), ws.data(), ms.data(), ws.size(), k, x.buf_.get(), b, rows_path, junk,
+                                              force.data(), outs.data(), r.xh.data(), r.used.data(), hplanes ? r.hq.data() : nullptr,
+                                              hplanes ? r.hxh.data() : nullptr));
+    if (hplanes) r.hq.resize(b * (size_t)r.used[7]);
+    return r;
+  }
 
  private:
   HipTensor(BufRef buf, GGMLType dtype, TensorStrider strider, DeviceRef device)

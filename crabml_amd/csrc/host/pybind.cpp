@@ -250,6 +250,26 @@ PYBIND11_MODULE(_host, m) {
              auto r = w.debug_gemm_ints(x, b);
              return py::make_tuple(py::array_t<int32_t>(r.first.size(), r.first.data()), py::array_t<float>(r.second.size(), r.second.data()));
            })
+      .def("debug_gemm_f16w",
+           [](const HipTensor& w, std::vector<HipTensor> more, const HipTensor& x, size_t b, int rows_path, uint16_t junk,
+              std::vector<int32_t> force) {
+             auto r = w.debug_gemm_f16w(more, x, b, rows_path, junk, force);
+             py::list outs;
+             for (auto& o : r.out) outs.append(py::array_t<float>(o.size(), o.data()));
+             py::dict d;
+             d["out"] = outs;
+             d["xh"] = py::array_t<uint16_t>(r.xh.size(), r.xh.data());
+             d["used"] = py::make_tuple(r.used[0], r.used[1], r.used[2], r.used[3]);
+             d["overflow"] = r.used[4] != 0;
+             if (!r.hq.empty()) {
+               d["hq"] = py::array_t<uint8_t>(r.hq.size(), r.hq.data());
+               d["hq_layout"] = py::make_tuple(r.used[5], r.used[6], r.used[7]);
+               d["hxh"] = py::array_t<uint16_t>(r.hxh.size(), r.hxh.data());
+             }
+             return d;
+           },
+           py::arg("more"), py::arg("x"), py::arg("b"), py::arg("rows_path") = 0, py::arg("junk") = 0,
+           py::arg("force") = std::vector<int32_t>{0, 0, 0, -1})
       .def("debug_block_dots", [](const HipTensor& w, size_t row, const HipTensor& x) {
         std::vector<int32_t> v = w.debug_block_dots(row, x);
         return py::array_t<int32_t>(v.size(), v.data());

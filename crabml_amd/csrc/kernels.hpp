@@ -18,7 +18,8 @@ inline void launch_k(hipStream_t st, crabml_hip_device::ProfRec* rec, K kernel, 
 // ---- quantize.hip: activation quantizers (buf_q8_0.rs:87-134, buf_q8_1.rs:90-129, buf_q8_k.rs:84-131)
 void launch_quantize_act(hipStream_t st, uint32_t qtype, const float* x, size_t n, void* planes);
 void launch_quantize_act_rows(hipStream_t st, uint32_t qtype, const float* x, size_t rows, size_t n, void* planes, void* xh = nullptr,
-                              int xh_order = 0);  // xh: the rows' f16 planes for gemm_f16w.hip, written alongside (f16w_rows.hpp)
+                              int xh_order = 0, int* xh_ovf = nullptr);  // xh: the rows' f16 planes for gemm_f16w.hip, written alongside
+                                                                          // (f16w_rows.hpp); xh_ovf: raised when one of them is +-inf
 
 // ---- gemv.hip: W(m,k) x quantized activations (b,k) -> out (b,m)
 // wq: weight planes; aq: activation planes (one set per batch row, stride act_layout(qtype,k).total)
@@ -49,15 +50,27 @@ struct F16wHQuant {  // gate | up launches: where h goes as Q8_0 / Q8_1 row plan
   size_t stride = 0, off_d = 0, off_aux = 0;
   unsigned short* xh = nullptr;
   int q81 = 0;
+  int* ovf = nullptr;  // raised when a value written to xh is +-inf (f16w_rows.hpp)
+};
+// parity hook (crabml_hip_debug_gemm_f16w; nullptr in every product call): the launch's shape forced (0 / gu -1: the launcher's own
+// choice; a forced shape the kernel cannot take makes the launch return false) and the shape it used
+struct F16wForce {
+  int F = 0, T = 0, ksplit = 0, gu = -1;
+  int used_F = 0, used_T = 0, used_ksplit = 0, used_gu = 0;
 };
 bool gemm_f16w_covers(uint32_t w_dtype, uint32_t act_qtype);
+// covers + the weight buffer's scales keep every |A'| inside f16 (checked once per buffer: a reduction over its scale plane, read
+// back -- the first call blocks); the one predicate of the GEMM's launch and of the kernels that write its B' ahead of it
+bool gemm_f16w_takes(crabml_hip_device* dev, const crabml_hip_buf* w, uint32_t act_qtype);
 int gemm_f16w_order(uint32_t w_dtype);
 size_t gemm_f16w_xh_bytes(size_t rows, size_t k);  // the allocation behind xh: whole 128-row tiles + the look-ahead's slack
-bool launch_rows_to_f16(hipStream_t st, uint32_t act_qtype, uint32_t w_dtype, const void* planes, size_t rows, size_t k, void* xh);
-bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, const size_t* m, int nw, size_t k, const void* xh, size_t b,
+bool launch_rows_to_f16(hipStream_t st, uint32_t act_qtype, uint32_t w_dtype, const void* planes, size_t rows, size_t k, void* xh,
+                        int* ovf = nullptr);  // ovf: raised when a value written to xh is +-inf
+bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, const size_t* m, int nw, size_t k, void* xh, size_t b,
                       float* const* out, float* ws = nullptr, size_t ws_floats = 0,  // ws: scratch for the partial tiles of k pieces
                       const unsigned short* gu_exp_tab = nullptr, int* gu_done = nullptr, int* defer_parts = nullptr,
-                      const F16wHQuant* hq = nullptr);  // hq: *gu_done = 2 -- h left as quantized row planes, no f32 h
+                      const F16wHQuant* hq = nullptr,  // hq: *gu_done = 2 -- h left as quantized row planes, no f32 h
+                      F16wForce* force = nullptr);
 // defer_parts (one matrix): a launch cut into k pieces leaves piece 0 in out and pieces 1.. in ws (b * m floats apart) and returns
 // their number instead of launching the reduce: the row kernel that consumes out adds them first, in piece order (prefill_rows.hpp)
 // gu_exp_tab / gu_done (two matrices = ffn_gate, ffn_up): the launch may store h = silu(g) * u to out[0] instead of g and u (*gu_done = 1)

@@ -17,7 +17,7 @@ template <int NIT, bool Q81>
 __global__ __launch_bounds__(1024) void k_norm_quant_rows_h(float* __restrict__ x, float* __restrict__ addv, const float* __restrict__ w,
                                                            int cols, float eps, char* __restrict__ planes, size_t row_stride, size_t off_d,
                                                            size_t off_aux, int half, unsigned short* __restrict__ xh,
-                                                           const float* __restrict__ parts, size_t pstride, int nparts) {
+                                                           const float* __restrict__ parts, size_t pstride, int nparts, int* __restrict__ ovf) {
   extern __shared__ float lds[];
   __shared__ float s_rms;
   NormLds L{lds, lds + cols};
@@ -41,7 +41,7 @@ __global__ __launch_bounds__(1024) void k_norm_quant_rows_h(float* __restrict__ 
   __threadfence_block();
   __syncthreads();
   const int nb = cols / 32;
-  for (int t = threadIdx.x; t < nb * 4; t += blockDim.x) rows_to_f16_piece<0>(p, off_d, t, xh + r * (size_t)cols);
+  for (int t = threadIdx.x; t < nb * 4; t += blockDim.x) rows_to_f16_piece<0>(p, off_d, t, xh + r * (size_t)cols, ovf);
 }
 
 // The same row (residual add + k pieces + RMSNorm + Q8_0 / Q8_1 quantize + B'), 256 threads instead of 1024: a thread owns E = cols / 256
@@ -56,7 +56,7 @@ template <int E, bool Q81>
 __global__ __launch_bounds__(256) void k_norm_quant_rows_w(float* __restrict__ x, const float* __restrict__ addv, const float* __restrict__ w,
                                                           int cols, float eps, char* __restrict__ planes, size_t row_stride, size_t off_d,
                                                           size_t off_aux, int half, unsigned short* __restrict__ xh,
-                                                          const float* __restrict__ parts, size_t pstride, int nparts) {
+                                                          const float* __restrict__ parts, size_t pstride, int nparts, int* __restrict__ ovf) {
   static_assert(E == 16 || E == 32, "half a block or a whole one per thread");
   constexpr int V = E / 4;
   __shared__ float cs_lds[256];
@@ -172,17 +172,22 @@ __global__ __launch_bounds__(256) void k_norm_quant_rows_w(float* __restrict__ x
   if (xh != nullptr) {
     const float ds = h2f(dh);
     unsigned short* xr = xh + r * (size_t)cols + (size_t)blk * 32;
+    bool inf = false;
 #pragma unroll
     for (int hj = 0; hj < E / 16; hj++) {
       const int hi = E == 32 ? hj : (tid & 1);  // which 16 elements of the block
 #pragma unroll
       for (int s4 = 0; s4 < 4; s4++) {  // elements 16 hi + 4 s4 + {0, 2, 1, 3} -> slots 8 s4 + 4 hi + {0, 1, 2, 3} (f16w_slot_of_elem)
         const int b = 16 * hj + 4 * s4;
-        const unsigned lo = (unsigned)f16w_value(q[b], ds) | ((unsigned)f16w_value(q[b + 2], ds) << 16);
-        const unsigned hi2 = (unsigned)f16w_value(q[b + 1], ds) | ((unsigned)f16w_value(q[b + 3], ds) << 16);
+        const unsigned short h0 = f16w_value(q[b], ds), h1 = f16w_value(q[b + 2], ds), h2 = f16w_value(q[b + 1], ds),
+                             h3 = f16w_value(q[b + 3], ds);
+        inf |= f16w_is_inf(h0) | f16w_is_inf(h1) | f16w_is_inf(h2) | f16w_is_inf(h3);
+        const unsigned lo = (unsigned)h0 | ((unsigned)h1 << 16);
+        const unsigned hi2 = (unsigned)h2 | ((unsigned)h3 << 16);
         *(unsigned long long*)(xr + 8 * s4 + 4 * hi) = (unsigned long long)lo | ((unsigned long long)hi2 << 32);
       }
     }
+    f16w_flag(inf, ovf);
   }
 }
 
@@ -194,7 +199,8 @@ template <int NIT>
 __global__ __launch_bounds__(1024) void k_norm_quant_rows_k(float* __restrict__ x, float* __restrict__ addv, const float* __restrict__ w, int cols,
                                                            float eps, float* __restrict__ xn, char* __restrict__ planes, size_t row_stride,
                                                            size_t off_d, size_t off_aux, size_t off_p, int half, unsigned short* __restrict__ xh,
-                                                           int xh_order, const float* __restrict__ parts, size_t pstride, int nparts) {
+                                                           int xh_order, const float* __restrict__ parts, size_t pstride, int nparts,
+                                                           int* __restrict__ ovf) {
   extern __shared__ float lds[];
   __shared__ float s_rms;
   NormLds L{lds, lds + cols};
@@ -226,9 +232,14 @@ __global__ __launch_bounds__(1024) void k_norm_quant_rows_k(float* __restrict__ 
     if (lane == 0) ((float*)(p + off_d))[sb] = o.d;
     if (xh) {
       unsigned short* xo = xh + r * (size_t)cols;
+      bool inf = false;
 #pragma unroll
-      for (int i = 0; i < 4; i++)
-        xo[f16w_pos_q8k(xh_order, sb, 4 * lane + i)] = f16w_value((int)(signed char)((o.packed >> (8 * i)) & 0xffu), o.d);
+      for (int i = 0; i < 4; i++) {
+        const unsigned short h = f16w_value((int)(signed char)((o.packed >> (8 * i)) & 0xffu), o.d);
+        xo[f16w_pos_q8k(xh_order, sb, 4 * lane + i)] = h;
+        inf |= f16w_is_inf(h);
+      }
+      f16w_flag(inf, ovf);
     }
   }
 }
@@ -237,7 +248,8 @@ __global__ __launch_bounds__(1024) void k_norm_quant_rows_k(float* __restrict__ 
 template <bool Q81>
 __global__ __launch_bounds__(256) void k_gateup_epi_quant_h(const float* __restrict__ g, const float* __restrict__ u,
                                                             const unsigned short* __restrict__ exp_tab, int hidden, char* __restrict__ planes,
-                                                            size_t row_stride, size_t off_d, size_t off_aux, unsigned short* __restrict__ xh) {
+                                                            size_t row_stride, size_t off_d, size_t off_aux, unsigned short* __restrict__ xh,
+                                                            int* __restrict__ ovf) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;  // hidden % 32 == 0: half-waves are all-live or all-dead
   const size_t r = blockIdx.y;
   const bool live = i < hidden;
@@ -250,7 +262,9 @@ __global__ __launch_bounds__(256) void k_gateup_epi_quant_h(const float* __restr
     ((unsigned short*)(p + off_d))[i >> 5] = o.d;
     store_qaux<Q81>((void*)(p + off_aux), i >> 5, o.aux);
   }
-  xh[r * (size_t)hidden + (i & ~31) + f16w_slot_of_elem(i & 31)] = f16w_value((int)o.q, h2f(o.d));
+  const unsigned short hv = f16w_value((int)o.q, h2f(o.d));
+  xh[r * (size_t)hidden + (i & ~31) + f16w_slot_of_elem(i & 31)] = hv;
+  f16w_flag(f16w_is_inf(hv), ovf);
 }
 
 }  // namespace crabml_hip

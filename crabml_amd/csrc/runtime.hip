@@ -1010,6 +1010,101 @@ int crabml_hip_debug_gemm_ints(crabml_hip_device_t* dev, const crabml_hip_buf_t*
   return 0;
 }
 
+int crabml_hip_debug_gemm_f16w(crabml_hip_device_t* dev, const crabml_hip_buf_t* const* w, const size_t* m, size_t nw, size_t k,
+                               const crabml_hip_buf_t* x, size_t b, int32_t rows_path, uint16_t junk, const int32_t* force,
+                               float* const* out, uint16_t* xh, int32_t* used, void* hq, uint16_t* hxh) {
+  if (!dev || !w || !m || !x || !out || nw < 1 || nw > 3) return CRABML_HIP_BAD_INPUT;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  const uint32_t dt = w[0] ? w[0]->dtype : 0;
+  const uint32_t qt = dt == CRABML_HIP_Q4_1 ? CRABML_HIP_Q8_1 : (dt == CRABML_HIP_Q4_K || dt == CRABML_HIP_Q6_K) ? CRABML_HIP_Q8_K : CRABML_HIP_Q8_0;
+  size_t mtot = 0;
+  for (size_t j = 0; j < nw; j++) {
+    if (!w[j] || !out[j]) return CRABML_HIP_BAD_INPUT;
+    CH_TRY(observe(dev, w[j]));
+    if (!gemm_f16w_covers(w[j]->dtype, qt) || w[j]->dtype != dt || w[j]->k != k || m[j] * k > w[j]->n_elems)
+      CH_BAIL(dev, CRABML_HIP_TENSOR_ERROR, "debug_gemm_f16w: one of Q4_0 / Q8_0 / Q4_1 / Q4_K / Q6_K for every matrix, matching shapes");
+    mtot += m[j];
+  }
+  CH_TRY(observe(dev, x));
+  CH_TRY(need_f32(dev, x, b * k, "debug_gemm_f16w rhs"));
+  if (rows_path != 0 && rows_path != 1) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_gemm_f16w: rows_path 0 (quantizer) or 1 (k_rows_to_f16)");
+  F16wForce fc{};
+  if (force) {
+    fc.F = force[0];
+    fc.T = force[1];
+    fc.ksplit = force[2];
+    fc.gu = force[3];
+  }
+  const int want_gu = force ? force[3] : -1;
+  if (want_gu == 2 && (nw != 2 || qt == CRABML_HIP_Q8_K || m[0] % 32 != 0))
+    CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_gemm_f16w: h as row planes needs gate | up with Q8_0 / Q8_1 rows and m % 32 == 0");
+  const ActLayout al = act_layout(qt, k), alh = act_layout(qt == CRABML_HIP_Q8_K ? CRABML_HIP_Q8_0 : qt, m[0]);
+  const size_t xb = gemm_f16w_xh_bytes(b, k), ks = fc.ksplit > 1 ? (size_t)fc.ksplit : 1;
+  const size_t ws_floats = std::max((b + 1024) * mtot, (ks - 1) * b * mtot);
+  const size_t sizes[7] = {b * al.total, xb, b * mtot * 4, ws_floats * 4 + 16, 16, want_gu == 2 ? b * alh.total : 16, want_gu == 2 ? b * m[0] * 2 : 16};
+  void* d[7] = {};
+  size_t cap[7] = {};
+  int rc = 0;
+  for (int i = 0; i < 7 && rc == 0; i++) rc = pool_alloc(dev, sizes[i], &d[i], &cap[i]);
+  hipError_t e = hipSuccess;
+  bool ran = false;
+  int gu_done = 0, flag = 0;
+  hipStream_t st = dev->stream;
+  if (rc == 0) {
+    e = hipMemsetD16Async((hipDeviceptr_t)d[1], junk, xb / 2, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d[4], 0, 16, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d[2], 0, sizes[2], st);
+  }
+  if (rc == 0 && e == hipSuccess) {
+    const int order = gemm_f16w_order(dt);
+    if (rows_path == 0) {
+      launch_quantize_act_rows(st, qt, (const float*)x->ptr, b, k, d[0], d[1], order, (int*)d[4]);
+    } else {
+      launch_quantize_act_rows(st, qt, (const float*)x->ptr, b, k, d[0]);
+      launch_rows_to_f16(st, qt, dt, d[0], b, k, d[1], (int*)d[4]);
+    }
+    float* outs[3] = {};
+    size_t before = 0;
+    for (size_t j = 0; j < nw; j++) {
+      outs[j] = (float*)d[2] + before;
+      before += b * m[j];
+    }
+    F16wHQuant hqs{};
+    if (want_gu == 2) {
+      hqs.planes = (char*)d[5];
+      hqs.stride = alh.total;
+      hqs.off_d = alh.off_d;
+      hqs.off_aux = alh.off_aux;
+      hqs.q81 = qt == CRABML_HIP_Q8_1;
+      hqs.xh = (unsigned short*)d[6];
+      hqs.ovf = (int*)d[4];
+    }
+    const bool gu_asked = want_gu > 0 || (want_gu < 0 && nw == 2);
+    ran = launch_gemm_f16w(dev, w, m, (int)nw, k, d[1], b, outs, (float*)d[3], ws_floats, gu_asked ? dev->exp_table : nullptr,
+                           gu_asked ? &gu_done : nullptr, nullptr, want_gu == 2 ? &hqs : nullptr, &fc);
+    if (ran && want_gu > 0 && gu_done != want_gu) ran = false;
+    e = hipGetLastError();
+    for (size_t j = 0; j < nw && ran && e == hipSuccess; j++) e = hipMemcpyAsync(out[j], outs[j], b * m[j] * 4, hipMemcpyDeviceToHost, st);
+    if (ran && e == hipSuccess && xh) e = hipMemcpyAsync(xh, d[1], b * k * 2, hipMemcpyDeviceToHost, st);
+    if (ran && e == hipSuccess && hq && want_gu == 2) e = hipMemcpyAsync(hq, d[5], b * alh.total, hipMemcpyDeviceToHost, st);
+    if (ran && e == hipSuccess && hxh && want_gu == 2) e = hipMemcpyAsync(hxh, d[6], b * m[0] * 2, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d[4], 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  }
+  for (int i = 0; i < 7; i++)
+    if (d[i]) pool_free(dev, d[i], cap[i]);
+  if (rc != 0) return rc;
+  if (e != hipSuccess) return hip_fail(dev, e, "debug_gemm_f16w", __FILE__, __LINE__);
+  if (!ran) CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "debug_gemm_f16w: the f16 GEMM refused this shape, launch form or these weight scales");
+  if (used) {
+    const int32_t u[8] = {fc.used_F, fc.used_T, fc.used_ksplit, gu_done, flag, (int32_t)alh.off_d, (int32_t)alh.off_aux, (int32_t)alh.total};
+    memcpy(used, u, sizeof u);
+  }
+  return 0;
+}
+
 int crabml_hip_debug_read_ceiling(crabml_hip_device_t* dev, size_t bytes, int32_t reps, double* gbytes_per_s) {
   if (!dev || !gbytes_per_s || reps < 1) return CRABML_HIP_BAD_INPUT;
   CH_LIVE(dev);

@@ -55,6 +55,19 @@ int crabml_hip_debug_superblock_ints(crabml_hip_device_t* dev, const crabml_hip_
  * out (optional, b * m floats) receives the GEMM's f32 result. */
 int crabml_hip_debug_gemm_ints(crabml_hip_device_t* dev, const crabml_hip_buf_t* w, size_t m, size_t k,
                                const crabml_hip_buf_t* x, size_t b, int32_t* dst, float* out);
+/* The fast prompt pass's weight GEMM (k_gemm_f16w, gemm_f16w.hip) by itself.  w: nw = 1..3 weight buffers of one format (Q4_0,
+ * Q8_0, Q4_1, Q4_K, Q6_K), m[j] rows of k; x: b >= 16 f32 rows of k.  The rows are quantized to the format's row type (Q8_0 / Q8_1 /
+ * Q8_K) and B' (the pre-scaled f16 rows the GEMM reads) is written by the quantizer itself (rows_path 0) or made from the finished
+ * planes by k_rows_to_f16 (1) -- into an allocation of the product's size (gemm_f16w_xh_bytes) whose every 16-bit word holds `junk`
+ * before.  force[4] (nullable) = F (1 | 2), T (2 | 4 | 8), ksplit (1 | 2 | 4 | 8), gate | up (0 off, 1 h = silu(g) * u as f32, 2 h
+ * as row planes + ffn_down's B'); 0 (gate | up: -1) = the launcher's own choice.  out[j]: b * m[j] f32 (gate | up: out[0] = h,
+ * out[1] untouched).  xh (nullable): the b * k halfs of B' the kernel read, in its k-slot order.  used[8] (nullable): F, T, ksplit,
+ * gate | up as launched, the B' overflow flag (1: some value written to B' was +-inf), then off_d, off_aux, total of h's row planes.
+ * hq (nullable, gate | up 2): b * total bytes of h's row planes; hxh (nullable): b * m[0] halfs of ffn_down's B'.  A shape, forced
+ * launch form or weight scales the GEMM does not take: CRABML_HIP_NOT_IMPLEMENTED.  Host pointers; blocks. */
+int crabml_hip_debug_gemm_f16w(crabml_hip_device_t* dev, const crabml_hip_buf_t* const* w, const size_t* m, size_t nw, size_t k,
+                               const crabml_hip_buf_t* x, size_t b, int32_t rows_path, uint16_t junk, const int32_t* force,
+                               float* const* out, uint16_t* xh, int32_t* used, void* hq, uint16_t* hxh);
 /* Sustained HBM read rate of this device as a plain streaming kernel reaches it (16-byte non-temporal loads over `bytes`
  * bytes, best of `reps` launches, HIP events on the device stream): the practical ceiling bench.py quotes next to the
  * 8 TB/s datasheet peak. */

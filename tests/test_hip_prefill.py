@@ -387,3 +387,40 @@ def test_fast_prompt_pass_rows_write_their_own_f16_planes(ca, fmt, shape, n):
             assert np.array_equal(la.view(np.uint32), lb.view(np.uint32)), (fmt, shape, chunk, strict)
             nxt = int(np.argmax(la))
             assert list(a.decode_greedy(nxt, 6)) == list(b.decode_greedy(nxt, 6))
+
+
+@pytest.mark.parametrize("fmt,shape", [("Q4_K", "tiny-gqa")])
+def test_fast_prompt_pass_recomputes_a_chunk_whose_f16_rows_overflow(ca, fmt, shape):
+    """A few massive channels (two elements of every ffn_norm weight x 2^16, as real checkpoints have): the ffn input's quantized
+    rows hold values past 65504, which the f16 GEMM's B' = f16(q d) cannot, while the int8 GEMM -- and the oracle -- stay finite.
+    The writers of B' raise the pass's overflow flag, and the chunk is computed again with the int8 GEMMs: its logits are those of
+    the int8 pass bit for bit, the KV cache advances once, decoding continues identically; a second, shorter pass on the same
+    runner (stale +-inf behind its rows in the f16 planes) stays finite."""
+    model = synth.build_model(synth.SHAPES[shape], getattr(synth, fmt), seed=5)
+    s = model.shape
+    for l in range(s.n_layers):
+        t = model.tensors[f"blk.{l}.ffn_norm.weight"]
+        w = t.data.view(np.float32).copy()
+        w[[3, s.dim // 2 + 1]] *= np.float32(2.0 ** 16)
+        t.data = w.view(np.uint8)
+    n = 64
+    prompt = [(11 * i + 5) % s.vocab for i in range(n)]
+    ref, orr = oracle_run(model, True, prompt, seq_len=n + 16)
+    assert all(np.all(np.isfinite(r)) for r in ref), "the oracle must stay finite"
+    for l in range(s.n_layers):
+        assert np.all(np.isfinite(orr.key_cache[l].storage.view(np.float16)))
+        assert np.all(np.isfinite(orr.value_cache[l].storage.view(np.float16)))
+    dev = ca.HipTensorDevice(0)
+    conf, w = synth.to_hip(model, dev)
+    a = ca.HipLlamaRunner(conf, w, dev, n + 16, True, prefill_chunk=512)
+    b = ca.HipLlamaRunner(conf, w, dev, n + 16, True, prefill_chunk=512, extra_flags=PREFILL_INT8_GEMM)
+    la, lb = np.array(a.prefill(prompt)), np.array(b.prefill(prompt))
+    assert np.all(np.isfinite(lb))
+    assert np.all(np.isfinite(la)), "f16 pass: non-finite logits"
+    assert np.array_equal(la.view(np.uint32), lb.view(np.uint32))
+    assert a.kv_cache_len() == b.kv_cache_len() == n
+    nxt = int(np.argmax(ref[-1]))
+    assert list(a.decode_greedy(nxt, 4)) == list(b.decode_greedy(nxt, 4))
+    a.reset()
+    l2 = np.array(a.prefill(prompt[:40]))
+    assert np.all(np.isfinite(l2)) and a.kv_cache_len() == 40
