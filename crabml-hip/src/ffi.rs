@@ -90,6 +90,21 @@ pub struct crabml_hip_llama_weights_t {
     pub output_weight: *const crabml_hip_buf_t,
 }
 
+/// crabml-llama2/src/model.rs:22-27
+pub const CRABML_HIP_ARCH_LLAMA: u32 = 0;
+pub const CRABML_HIP_ARCH_GEMMA: u32 = 1;
+pub const CRABML_HIP_ARCH_QWEN2: u32 = 2;
+pub const CRABML_HIP_ARCH_PHI2: u32 = 3;
+
+/// the architecture of a decode step and its q / k / v biases (Qwen2: llama2.rs:315-317); per-layer arrays of n_layers handles
+#[repr(C)]
+pub struct crabml_hip_llama_arch_t {
+    pub architecture: u32,
+    pub bq: *const *const crabml_hip_buf_t,
+    pub bk: *const *const crabml_hip_buf_t,
+    pub bv: *const *const crabml_hip_buf_t,
+}
+
 extern "C" {
     // ---- device
     pub fn crabml_hip_abi_version() -> i32;
@@ -130,6 +145,7 @@ extern "C" {
 
     // ---- fused Llama decode step
     pub fn crabml_hip_llama_create(dev: *mut crabml_hip_device_t, cfg: *const crabml_hip_llama_config_t, w: *const crabml_hip_llama_weights_t, out: *mut *mut crabml_hip_llama_t) -> i32;
+    pub fn crabml_hip_llama_create_arch(dev: *mut crabml_hip_device_t, cfg: *const crabml_hip_llama_config_t, w: *const crabml_hip_llama_weights_t, arch: *const crabml_hip_llama_arch_t, out: *mut *mut crabml_hip_llama_t) -> i32;
     pub fn crabml_hip_llama_destroy(ctx: *mut crabml_hip_llama_t) -> i32;
     pub fn crabml_hip_llama_forward(ctx: *mut crabml_hip_llama_t, token: usize, pos: usize, logits: *mut f32) -> i32;
     pub fn crabml_hip_llama_decode_greedy(ctx: *mut crabml_hip_llama_t, token: usize, n_steps: usize, out_tokens: *mut u32) -> i32;

@@ -5,7 +5,7 @@
 //!
 //! The generic `Llama2Runner<HipTensor>` needs none of this (every `Tensor` method is a kernel launch); it is
 //! launch-bound on an MI355X (about 1000 launches per token for Llama-3-8B), which is what this path removes.
-//! Architectures other than Llama (gemma, qwen2, phi2: llama2.rs:283-524) stay on the generic runner.
+//! Qwen2 (llama2.rs:283-351: q / k / v biases, NEOX rope) takes the same path; gemma and phi2 stay on the generic runner.
 
 use std::ptr;
 use std::sync::Arc;
@@ -48,18 +48,18 @@ impl HipLlamaRunner {
         seq_len: usize,
         use_f16_kv_cache: bool,
     ) -> Result<Self> {
-        if conf.architecture != ModelArchitecture::Llama {
+        // Qwen2 = forward_llama + q / k / v biases + NEOX rope (llama2.rs:283-351)
+        let qwen2 = conf.architecture == ModelArchitecture::Qwen2;
+        if conf.architecture != ModelArchitecture::Llama && !qwen2 {
             bail!(
                 ErrorKind::NotImplemented,
-                "the fused hip decode step serves the llama architecture only, got {:?}",
+                "the fused hip decode step serves the llama and qwen2 architectures only, got {:?}",
                 conf.architecture
             );
         }
         let w = &weights;
         if !w.wqkv.is_empty()
-            || !w.bq.is_empty()
-            || !w.bk.is_empty()
-            || !w.bv.is_empty()
+            || (!qwen2 && (!w.bq.is_empty() || !w.bk.is_empty() || !w.bv.is_empty()))
             || !w.bo.is_empty()
             || !w.bqkv.is_empty()
             || !w.ffn_down_bias.is_empty()
@@ -69,10 +69,23 @@ impl HipLlamaRunner {
         {
             bail!(
                 ErrorKind::NotImplemented,
-                "the fused hip decode step takes no biases / fused qkv weights"
+                "the fused hip decode step takes no biases other than qwen2's q / k / v biases, and no fused qkv weights"
             );
         }
         let n = conf.n_layers;
+        if qwen2 {
+            for (name, v) in [("bq", &w.bq), ("bk", &w.bk), ("bv", &w.bv)] {
+                if v.len() != n {
+                    bail!(
+                        ErrorKind::ModelError,
+                        "{} holds {} tensors for {} layers",
+                        name,
+                        v.len(),
+                        n
+                    );
+                }
+            }
+        }
         for (name, v) in [
             ("wq", &w.wq),
             ("wk", &w.wk),
@@ -134,9 +147,20 @@ impl HipLlamaRunner {
             attn_long_from: 0,
             prefill_chunk: 0,
         };
+        let (bq, bk, bv) = (handles(&w.bq), handles(&w.bk), handles(&w.bv));
+        let c_arch = ffi::crabml_hip_llama_arch_t {
+            architecture: if qwen2 {
+                ffi::CRABML_HIP_ARCH_QWEN2
+            } else {
+                ffi::CRABML_HIP_ARCH_LLAMA
+            },
+            bq: if qwen2 { bq.as_ptr() } else { ptr::null() },
+            bk: if qwen2 { bk.as_ptr() } else { ptr::null() },
+            bv: if qwen2 { bv.as_ptr() } else { ptr::null() },
+        };
         let mut raw = ptr::null_mut();
         device.check(unsafe {
-            ffi::crabml_hip_llama_create(device.raw, &c_conf, &c_weights, &mut raw)
+            ffi::crabml_hip_llama_create_arch(device.raw, &c_conf, &c_weights, &c_arch, &mut raw)
         })?;
         Ok(Self {
             raw,

@@ -106,6 +106,9 @@ struct crabml_hip_llama {
   crabml_hip_buf* rms_final = nullptr;
   crabml_hip_buf* output = nullptr;
   std::vector<crabml_hip_buf*> rms_att, rms_ffn, wq, wk, wv, wo, gate, down, up;
+  // Qwen2 (crabml_hip_llama_create_arch): q / k / v biases per layer, NEOX rope (the q|k|v kernels' QKV_QWEN2 form)
+  bool qwen2 = false;
+  std::vector<crabml_hip_buf*> bq, bk, bv;
   // device state
   std::vector<void*> kc, vc;
   size_t kv_bytes = 0;
@@ -464,6 +467,19 @@ int enqueue_classifier_and_sampler(crabml_hip_llama* c, const void* cls_act, cra
   return 0;
 }
 
+// the q|k|v epilogue arguments of a Qwen2 layer: Llama's plus the layer's three bias vectors
+static QkvEpiB qwen2_epi(const crabml_hip_llama* c, const QkvEpi& e, int l) {
+  return QkvEpiB{e, (const float*)c->bq[l]->ptr, (const float*)c->bk[l]->ptr, (const float*)c->bv[l]->ptr};
+}
+template <class E>
+struct QkvArchOf {
+  static constexpr int value = QKV_LLAMA;
+};
+template <>
+struct QkvArchOf<QkvEpiB> {
+  static constexpr int value = QKV_QWEN2;
+};
+
 // enqueue segment `seg` of one decode step on the device stream (see the banner above): the fused kernels
 // (fast mode, Q4_0 / Q8_0 weights)
 template <int FMT>
@@ -663,18 +679,25 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     CH_TRY(P0(&pr, 1, total_rows, dim));
     // (the planes of layer l > 0 come from the previous layer's ffn_down launch, with its dim / 32 chunk sums)
     const RmsTail rtq{c->rsums, dim / 32, 1.0f / (float)dim, g.rms_norm_eps};
-    if (c->ord)
-      launch_k(st, R, k_qkv_ord<FMT>, dim3((total_rows / 2 + 3) / 4), dim3(256), (size_t)8 * ((dim / 32 + 3) & ~3) * sizeof(float), planes_of(c->wq[l]),
-               planes_of(c->wk[l]), planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, e, Planes6{nullptr, 0});
-    else if (defer_down && l > 0) {
-      if constexpr (!Q81)
-        launch_k(st, R, k_qkv<FMT, true>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
-                 planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, e, Planes6{nullptr, 0}, rtq, qkv_upfront);
-    } else
-      launch_k(st, R, k_qkv<FMT>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
-               planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, e, Planes6{nullptr, 0}, rtq,
-               // few, short waves (a tensor-parallel rank's rows; small models): two steps per request round
-               (qkv_upfront && total_rows / 2 <= 4 * dev->n_cu) ? 1 : 0);
+    auto qkv = [&](auto ep) {
+      constexpr int A = QkvArchOf<decltype(ep)>::value;
+      if (c->ord)
+        launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), (size_t)8 * ((dim / 32 + 3) & ~3) * sizeof(float),
+                 planes_of(c->wq[l]), planes_of(c->wk[l]), planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0});
+      else if (defer_down && l > 0) {
+        if constexpr (!Q81)
+          launch_k(st, R, k_qkv<FMT, true, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
+                   planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0}, rtq, qkv_upfront);
+      } else
+        launch_k(st, R, k_qkv<FMT, false, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
+                 planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0}, rtq,
+                 // few, short waves (a tensor-parallel rank's rows; small models): two steps per request round
+                 (qkv_upfront && total_rows / 2 <= 4 * dev->n_cu) ? 1 : 0);
+    };
+    if (c->qwen2)
+      qkv(qwen2_epi(c, e, l));
+    else
+      qkv(e);
     CH_TRY(P1(&pr));
     // attention (llama2.rs:571-590) -> attn (f32) [+ Q8_0 planes for wo]; spare CUs prefetch wo
     const bool attn_quant = (hd % 32) == 0;
@@ -780,7 +803,10 @@ int enqueue_segment_generic(crabml_hip_llama* c, int seg) {
     CH_TRY(gemv(c->wq[l], dim_l, dim, act, c->tmp, 1));
     CH_TRY(gemv(c->wk[l], kv_dim_l, dim, act, c->tmp + dim_l, 1));
     CH_TRY(gemv(c->wv[l], kv_dim_l, dim, act, c->tmp + dim_l + kv_dim_l, 1));
-    k_qkv_epi<<<(total_rows / 2 + 255) / 256, 256, 0, st>>>(c->tmp, e);
+    if (c->qwen2)
+      k_qkv_epi<QKV_QWEN2><<<(total_rows / 2 + 255) / 256, 256, 0, st>>>(c->tmp, qwen2_epi(c, e, l));
+    else
+      k_qkv_epi<QKV_LLAMA><<<(total_rows / 2 + 255) / 256, 256, 0, st>>>(c->tmp, e);
     enqueue_attention(c, l, nullptr, nullptr, nullptr, PrefetchPlan{}, 0, prof);
     const void* aact = quant(c->attn, dim_l, c->qt, c->act_attn);
     if (strict && !tp) {  // the residual inside the GEMV's own store: x = matmul_out + x (llama2.rs:266)
@@ -950,12 +976,19 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
              (int)g.rope_dim, c->npairs, seq_cap, kv16 ? 1 : 0};
     const int total_rows = dim_l + 2 * kv_dim_l;
     CH_TRY(P0(1, total_rows, dim));
-    if (ordk)
-      launch_k(st, R, k_qkv_ord<FMT>, dim3((total_rows / 2 + 3) / 4), dim3(256), (size_t)8 * (size_t)q4k_rec_stride(dim / BE) * sizeof(float),
-               planes_k(c->wq[l]), planes_k(c->wk[l]), planes_k(c->wv[l]), act_k(c->act_dim, dim), dim / BE, e, six(c->wv[l]));
+    auto qkv = [&](auto ep) {
+      constexpr int A = QkvArchOf<decltype(ep)>::value;
+      if (ordk)
+        launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), (size_t)8 * (size_t)q4k_rec_stride(dim / BE) * sizeof(float),
+                 planes_k(c->wq[l]), planes_k(c->wk[l]), planes_k(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]));
+      else
+        launch_k(st, R, k_qkv<FMT, false, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_k(c->wq[l]), planes_k(c->wk[l]),
+                 planes_k(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
+    };
+    if (c->qwen2)
+      qkv(qwen2_epi(c, e, l));
     else
-      launch_k(st, R, k_qkv<FMT>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_k(c->wq[l]), planes_k(c->wk[l]),
-               planes_k(c->wv[l]), act_k(c->act_dim, dim), dim / BE, e, six(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
+      qkv(e);
     CH_TRY(P1());
     // Q8_K producers: the (short-context) attention kernel assembles the planes of wo's rhs itself; wo copies them
     const bool aq8 = qout && (g.flags & CRABML_HIP_LLAMA_Q8K_ATTN_PRODUCER) && c->attn_variant == 0 && c->attn_s_rows > 0;
@@ -1470,7 +1503,10 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     QkvEpi e{c->pf_qr, c->kc[l], c->vc[l], c->rope, pos_d, 1.0f / std::sqrt((float)hd), dim, kv_dim, hd,
              (int)g.rope_dim, c->npairs, seq_cap, kv16 ? 1 : 0};
     const int pairs = (dim + 2 * kv_dim) / 2;
-    k_qkv_epi_rows<<<dim3((pairs + 255) / 256, rows), 256, 0, st>>>(c->pf_q, c->pf_k, c->pf_v, e);
+    if (c->qwen2)
+      k_qkv_epi_rows<QKV_QWEN2><<<dim3((pairs + 255) / 256, rows), 256, 0, st>>>(c->pf_q, c->pf_k, c->pf_v, qwen2_epi(c, e, l));
+    else
+      k_qkv_epi_rows<QKV_LLAMA><<<dim3((pairs + 255) / 256, rows), 256, 0, st>>>(c->pf_q, c->pf_k, c->pf_v, e);
     int along = 0;
     // (a pass whose every row sees fewer cached positions than the decode step's switch to the f32 kernels -- attn_long_from --
     // keeps the exact tile kernel, so that prefill(prompt) and a token loop over the same short prompt agree bit for bit)
@@ -1835,7 +1871,8 @@ int crabml_hip_tp_p2p_connect_local(crabml_hip_tp_comm_t* const* comms, int n) {
 // ext_kc / ext_vc (lazy.hip): the caller's KV caches, [n_kv_heads][seq_len][head_dim] in the configured element type -- the layout
 // of Llama2Runner's own cache tensors (llama2.rs:65-86) -- used in place
 static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_config_t* cfg, const crabml_hip_llama_weights_t* w,
-                             crabml_hip_buf* const* ext_kc, crabml_hip_buf* const* ext_vc, crabml_hip_llama_t** out) {
+                             crabml_hip_buf* const* ext_kc, crabml_hip_buf* const* ext_vc, crabml_hip_llama_t** out,
+                             const crabml_hip_llama_arch_t* arch = nullptr) {
   if (!dev || !cfg || !w || !out) return CRABML_HIP_BAD_INPUT;
   *out = nullptr;
   const bool dry = dev->dry;
@@ -1867,6 +1904,24 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   if (!w->token_embed || !w->rms_final_weight || !w->wq || !w->wk || !w->wv || !w->wo || !w->ffn_gate_weight ||
       !w->ffn_down_weight || !w->ffn_up_weight || !w->rms_att_weight || !w->rms_ffn_weight)
     CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: missing weights");
+  // the architecture (model.rs:22-27): Llama, or Qwen2 = Llama + q / k / v biases + NEOX rope (llama2.rs:283-351)
+  const uint32_t archv = arch ? arch->architecture : (uint32_t)CRABML_HIP_ARCH_LLAMA;
+  const bool qwen2 = archv == CRABML_HIP_ARCH_QWEN2;
+  if (archv == CRABML_HIP_ARCH_GEMMA || archv == CRABML_HIP_ARCH_PHI2)
+    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: architecture %u (Gemma / Phi2) has no decode step here", archv);
+  if (archv != CRABML_HIP_ARCH_LLAMA && !qwen2) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: unknown architecture %u", archv);
+  if (!qwen2 && arch && (arch->bq || arch->bk || arch->bv)) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: a Llama model has no q / k / v biases");
+  if (qwen2) {
+    if (tp > 1) CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "qwen2: tensor parallelism is not implemented");
+    if (!arch->bq || !arch->bk || !arch->bv) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "qwen2: missing q / k / v biases");
+    for (size_t l = 0; l < g.n_layers; l++) {
+      const crabml_hip_buf* b[3] = {arch->bq[l], arch->bk[l], arch->bv[l]};
+      const size_t n[3] = {dim_l, kv_dim_l, kv_dim_l};
+      for (int j = 0; j < 3; j++)
+        if (!b[j] || b[j]->dtype != CRABML_HIP_F32 || b[j]->n_elems != n[j])
+          CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "qwen2: layer %zu: the %c bias must be an f32 vector of %zu elements", l, "qkv"[j], n[j]);
+    }
+  }
   const crabml_hip_buf* outw = w->output_weight ? w->output_weight : w->token_embed;
   const uint32_t wt = w->wq[0]->dtype, out_wt = outw->dtype;
   const uint32_t qt = vec_dot_rhs_dtype(wt), out_qt = vec_dot_rhs_dtype(out_wt);
@@ -2038,7 +2093,13 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
     c->gate.push_back(hold(w->ffn_gate_weight[l]));
     c->down.push_back(hold(w->ffn_down_weight[l]));
     c->up.push_back(hold(w->ffn_up_weight[l]));
+    if (qwen2) {
+      c->bq.push_back(hold(arch->bq[l]));
+      c->bk.push_back(hold(arch->bk[l]));
+      c->bv.push_back(hold(arch->bv[l]));
+    }
   }
+  c->qwen2 = qwen2;
   // the f16 prompt GEMM's A' range check of every matrix (gemm_f16w_takes: one reduction over the scale plane, read back), here
   // once rather than inside the first prompt pass
   if (rc == 0 && !dev->strict_order && tp == 1 && (qt == CRABML_HIP_Q8_0 || qt == CRABML_HIP_Q8_1 || qt == CRABML_HIP_Q8_K))
@@ -2228,10 +2289,15 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   }
   // RoPE table with the reference's own recurrence (rope.rs:47-54: theta_scale = 10000^(-2/hd), theta = pos,
   // theta *= theta_scale per pair; base hard-coded) evaluated with the host libm, as the trait op does.
+  // Qwen2: NEOX's table (rope.rs:65-80: theta_i = pos / 10000^(2 i / hd), i < rope_dim / 2), the trait op's own code (lazy.hip)
   {
     std::vector<float> tab(g.seq_len * (size_t)(c->npairs ? c->npairs : 1) * 2, 0.f);
     const float theta_scale = powf(10000.0f, -2.0f / (float)hd);
     for (size_t p = 0; p < g.seq_len; p++) {
+      if (qwen2) {
+        rope_table_neox(tab.data() + p * c->npairs * 2, p, hd, (size_t)c->npairs);
+        continue;
+      }
       float theta = (float)p;
       for (int i = 0; i < c->npairs; i++) {
         tab[(p * c->npairs + i) * 2] = cosf(theta);
@@ -2310,6 +2376,16 @@ int crabml_hip_llama_create(crabml_hip_device_t* dev, const crabml_hip_llama_con
   CH_USE(dev);
   CH_FLUSH(dev);
   return llama_create_impl(dev, cfg, w, nullptr, nullptr, out);
+}
+
+int crabml_hip_llama_create_arch(crabml_hip_device_t* dev, const crabml_hip_llama_config_t* cfg, const crabml_hip_llama_weights_t* w,
+                                 const crabml_hip_llama_arch_t* arch, crabml_hip_llama_t** out) {
+  if (!dev || !cfg || !w || !out) return CRABML_HIP_BAD_INPUT;
+  *out = nullptr;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  return llama_create_impl(dev, cfg, w, nullptr, nullptr, out, arch);
 }
 
 int crabml_hip_llama_destroy(crabml_hip_llama_t* c) {
@@ -2718,14 +2794,17 @@ int lazy_ctx_create(crabml_hip_device* dev, const LazyModel& m, crabml_hip_llama
   if (m.rms_att.size() != L || m.rms_ffn.size() != L || m.wq.size() != L || m.wk.size() != L || m.wv.size() != L || m.wo.size() != L ||
       m.gate.size() != L || m.down.size() != L || m.up.size() != L || m.kc.size() != L || m.vc.size() != L)
     return CRABML_HIP_BAD_INPUT;
-  return llama_create_impl(dev, &m.cfg, &w, m.kc.data(), m.vc.data(), out);
+  if (!m.qwen2) return llama_create_impl(dev, &m.cfg, &w, m.kc.data(), m.vc.data(), out);
+  if (m.bq.size() != L || m.bk.size() != L || m.bv.size() != L) return CRABML_HIP_BAD_INPUT;
+  const crabml_hip_llama_arch_t arch{CRABML_HIP_ARCH_QWEN2, m.bq.data(), m.bk.data(), m.bv.data()};
+  return llama_create_impl(dev, &m.cfg, &w, m.kc.data(), m.vc.data(), out, &arch);
 }
 
 void lazy_ctx_destroy(crabml_hip_llama* c) { (void)crabml_hip_llama_destroy(c); }
 
 bool lazy_ctx_orphaned(const crabml_hip_llama* c) {
-  // one representative of the model (the first layer's wq) and one of the runner (its first K cache): a handle whose references are
-  // all the context's own holds has been released by the host
+  // one representative of the model (the first layer's wq; Qwen2: and of its biases, bq) and one of the runner (its first K cache): a
+  // handle whose references are all the context's own holds has been released by the host
   auto sole = [&](const crabml_hip_buf* b) {
     if (!b) return false;
     int holds = 0;
@@ -2733,7 +2812,7 @@ bool lazy_ctx_orphaned(const crabml_hip_llama* c) {
       if (h == b) holds++;
     return holds > 0 && b->refcnt.load() <= holds;
   };
-  return sole(c->wq.empty() ? nullptr : c->wq[0]) || (c->ext_kv && sole(c->ext_kc0));
+  return sole(c->wq.empty() ? nullptr : c->wq[0]) || (c->qwen2 && sole(c->bq[0])) || (c->ext_kv && sole(c->ext_kc0));
 }
 
 int lazy_ctx_n_segments(const crabml_hip_llama* c) { return n_segments(c); }

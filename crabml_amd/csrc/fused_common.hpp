@@ -379,6 +379,96 @@ __device__ __forceinline__ void qkv_epilogue(const QkvEpi& e, const QkvPre& pre,
   }
 }
 
+// ---- Qwen2's q|k|v stage (llama2.rs:283-351): forward_llama plus a bias per q / k / v row (:315-317) and NEOX rope (:325-326) ----
+// The architecture is a template parameter of the q|k|v kernels: the Llama instantiations are the code above, untouched.
+enum { QKV_LLAMA = 0, QKV_QWEN2 = 1 };
+struct QkvEpiB : QkvEpi {
+  const float* bq;  // (dim) f32: q = wq x + bq, one f32 add per row (add_inplace, arithmetic.rs)
+  const float* bk;  // (kv_dim)
+  const float* bv;  // (kv_dim)
+};
+struct QkvPreB : QkvPre {
+  float b0, b1;  // the biases of the pair's two rows
+};
+template <int ARCH>
+struct QkvArch {
+  typedef QkvEpi epi;
+  typedef QkvPre pre;
+};
+template <>
+struct QkvArch<QKV_QWEN2> {
+  typedef QkvEpiB epi;
+  typedef QkvPreB pre;
+};
+// NEOX rotates the pair (i, i + hd / 2) of every head, i < rope_dim / 2 (rope.rs:65-80): wave / thread `p` of the q and k rows owns
+// rows h hd + i and h hd + i + hd / 2 (h = head, i in [0, hd / 2)); the v rows keep adjacent pairs.  Returns the pair's first row (q|k|v
+// numbering, as 2 p is for Llama); *rs = the distance to its second row, the row stride the row loaders stream the pair with.
+__device__ __forceinline__ int neox_pair_row0(const QkvEpi& e, int p, int& rs) {
+  const int r = 2 * p;
+  if (r >= e.dim + e.kv_dim) {
+    rs = 1;
+    return r;
+  }
+  const int base = r < e.dim ? 0 : e.dim, half = e.hd >> 1;
+  const int lp = p - (base >> 1);
+  rs = half;
+  return base + (lp / half) * e.hd + lp % half;
+}
+// position, rotation and the two biases of the pair at (row0, row0 + rs), requested ahead of the weight stream by every lane (one
+// address each: a load inside a lane-predicated branch would make the wave wait for it before its first weight request)
+__device__ __forceinline__ QkvPreB qkv_preload_neox(const QkvEpiB& e, int row0, int rs, int row_of_batch = 0) {
+  QkvPreB p;
+  p.pos = *e.pos_d + row_of_batch;
+  const bool qk = row0 < e.dim + e.kv_dim;
+  const int local = row0 < e.dim ? row0 : qk ? row0 - e.dim : row0 - e.dim - e.kv_dim;
+  const int i = local % e.hd;
+  p.rot = qk && 2 * i < e.rope_dim;
+  const float* cs = e.rope + ((size_t)p.pos * e.npairs + (p.rot ? i : 0)) * 2;  // the NEOX table: entry i is theta_i (rope.rs:70-73)
+  p.c = cs[0];
+  p.s = cs[1];
+  const float* b = row0 < e.dim ? e.bq : qk ? e.bk : e.bv;
+  p.b0 = b[local];
+  p.b1 = b[local + rs];
+  return p;
+}
+__device__ __forceinline__ void qkv_epilogue_neox(const QkvEpiB& e, const QkvPreB& pre, int row0, int rs, float s0, float s1) {
+  const int pos = pre.pos;
+  s0 = s0 + pre.b0;  // the bias before rope and before the KV append (llama2.rs:315-317)
+  s1 = s1 + pre.b1;
+  if (row0 < e.dim + e.kv_dim) {
+    float r0 = s0, r1 = s1;
+    if (pre.rot) {
+      const float c = pre.c, s = pre.s;
+      r0 = s0 * c - s1 * s;
+      r1 = s0 * s + s1 * c;
+    }
+    if (row0 < e.dim) {
+      e.q_out[row0] = r0 * e.scale;
+      e.q_out[row0 + rs] = r1 * e.scale;
+    } else {
+      const int kr = row0 - e.dim;
+      const size_t o = ((size_t)(kr / e.hd) * e.seq_cap + pos) * e.hd + kr % e.hd;
+      if (e.kv16) {
+        ((unsigned short*)e.kc)[o] = f2h(r0);
+        ((unsigned short*)e.kc)[o + rs] = f2h(r1);
+      } else {
+        ((float*)e.kc)[o] = r0;
+        ((float*)e.kc)[o + rs] = r1;
+      }
+    }
+  } else {
+    const int vr = row0 - e.dim - e.kv_dim;
+    const size_t o = ((size_t)(vr / e.hd) * e.seq_cap + pos) * e.hd + (vr % e.hd);
+    if (e.kv16) {
+      ((unsigned short*)e.vc)[o] = f2h(s0);
+      ((unsigned short*)e.vc)[o + 1] = f2h(s1);
+    } else {
+      ((float*)e.vc)[o] = s0;
+      ((float*)e.vc)[o + 1] = s1;
+    }
+  }
+}
+
 struct Planes {
   const i32x4* q;
   const unsigned short* d;
@@ -390,14 +480,16 @@ struct Planes6 {
 };
 
 // DEFER: the rhs planes come from a hop-free ffn_down launch -- the row dots are multiplied by 1 / rms (RmsTail, gemv_core.hpp)
-template <int FMT, bool DEFER = false>
-__global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb, QkvEpi e,
-                                             Planes6 wv6, RmsTail rt, int upfront = 0) {
+// ARCH = QKV_QWEN2: the wave's two rows are a NEOX pair (neox_pair_row0), the biases are added after the 1 / rms multiply
+template <int FMT, bool DEFER = false, int ARCH = QKV_LLAMA>
+__global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb,
+                                             typename QkvArch<ARCH>::epi e, Planes6 wv6, RmsTail rt, int upfront = 0) {
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + wave_in_wg();
-  const int row0 = wave * 2;
+  int row0 = wave * 2, rs = 1;
   const int total = e.dim + 2 * e.kv_dim;
   if (row0 >= total) return;
+  if constexpr (ARCH != QKV_LLAMA) row0 = neox_pair_row0(e, wave, rs);
   Planes w;
   int local, m;
   if (row0 < e.dim) {
@@ -407,9 +499,12 @@ __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, ty
   } else {
     w = wv; local = row0 - e.dim - e.kv_dim; m = e.kv_dim;
   }
-  QkvPre pre{};
+  typename QkvArch<ARCH>::pre pre{};
   RmsReq rq{0.f, 0.f};
-  if constexpr (DEFER) {
+  if constexpr (ARCH != QKV_LLAMA) {
+    pre = qkv_preload_neox(e, row0, rs);
+    if constexpr (DEFER) rq = rms_request(rt, lane);
+  } else if constexpr (DEFER) {
     // (every lane loads the pair's rotation -- one address -- instead of lane 0 alone: with the chunk sums requested next to it, a
     // load inside a lane-predicated branch would make the wave wait for all of them before its first weight request)
     pre = qkv_preload_nb(e, row0);
@@ -421,43 +516,49 @@ __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, ty
   bool done = false;
   if constexpr (FMT == CRABML_HIP_Q4_K) {
     if (wv6.base != nullptr && row0 >= e.dim + e.kv_dim) {  // the V rows of this layer are Q6_K (wave-uniform)
-      rows_partial_q6k<2>(wv6.base, wv6.off_qh, act, local, m, nb, lane, acc);
+      rows_partial_q6k<2>(wv6.base, wv6.off_qh, act, local, m, nb, lane, acc, nullptr, rs);
       done = true;
     }
   }
   float inv_rms = 1.0f;
   if constexpr (DEFER && FMT != CRABML_HIP_Q4_K) {
     if (upfront && nb * BlockFmt<FMT>::UNITS == 128)
-      inv_rms = rows_partial_rms_128<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc, rt, rq);
+      inv_rms = rows_partial_rms_128<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc, rt, rq, rs);
     else
-      inv_rms = rows_partial_rms<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc, rt, rq);
+      inv_rms = rows_partial_rms<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc, rt, rq, rs);
   } else {
     if constexpr (FMT != CRABML_HIP_Q4_K) {
       if (!done && upfront && (nb * BlockFmt<FMT>::UNITS) % 128 == 0) {
-        rows_partial_2step<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc);
+        rows_partial_2step<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
         done = true;
       }
     }
-    if (!done) rows_dot<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc);
+    if (!done) rows_dot<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
   }
   float s0 = wave_sum_f32(acc[0]), s1 = wave_sum_f32(acc[1]);
   if constexpr (DEFER) {
     s0 *= inv_rms;
     s1 *= inv_rms;
   }
-  if (lane == 0) qkv_epilogue(e, pre, row0, s0, s1);
+  if constexpr (ARCH != QKV_LLAMA) {
+    if (lane == 0) qkv_epilogue_neox(e, pre, row0, rs, s0, s1);
+  } else {
+    if (lane == 0) qkv_epilogue(e, pre, row0, s0, s1);
+  }
 }
 // strict order (CRABML_HIP_FLAG_STRICT_ORDER, Q4_0 / Q8_0 / Q4_1 layers): the same launch with the block terms parked in LDS and
 // added in block order by one lane per row (rows_terms / ordered_sum, gemv_core.hpp) -- q, k and v rows bit-identical to the scalar
 // loops of the reference, then the same epilogue.  Workgroup = 4 waves x one (even, odd) row pair; dynamic LDS = 8 * nt floats.
-template <int FMT>
-__global__ __launch_bounds__(256) void k_qkv_ord(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb, QkvEpi e, Planes6 wv6) {
+template <int FMT, int ARCH = QKV_LLAMA>
+__global__ __launch_bounds__(256) void k_qkv_ord(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb,
+                                                 typename QkvArch<ARCH>::epi e, Planes6 wv6) {
   extern __shared__ __attribute__((aligned(16))) float ord_terms[];
   const int lane = threadIdx.x & 63, wv_i = wave_in_wg();
   const int wave = blockIdx.x * (blockDim.x >> 6) + wv_i;
-  const int row0 = wave * 2;
+  int row0 = wave * 2, rs = 1;
   const int total = e.dim + 2 * e.kv_dim;
   if (row0 >= total) return;
+  if constexpr (ARCH != QKV_LLAMA) row0 = neox_pair_row0(e, wave, rs);
   Planes w;
   int local, m;
   if (row0 < e.dim) {
@@ -467,49 +568,68 @@ __global__ __launch_bounds__(256) void k_qkv_ord(Planes wq, Planes wk, Planes wv
   } else {
     w = wv; local = row0 - e.dim - e.kv_dim; m = e.kv_dim;
   }
-  QkvPre pre{};
-  if (lane == 0) pre = qkv_preload(e, row0);
+  typename QkvArch<ARCH>::pre pre{};
+  if constexpr (ARCH != QKV_LLAMA)
+    pre = qkv_preload_neox(e, row0, rs);
+  else if (lane == 0)
+    pre = qkv_preload(e, row0);
   float s = 0.0f;
   if constexpr (FMT == CRABML_HIP_Q4_K) {
     // nb super-blocks, nine terms each (q4k_class_terms / q4k_ordered_sum, gemv_core.hpp); dynamic LDS = 8 * q4k_rec_stride(nb) floats
     const int stride = q4k_rec_stride(nb);
     float* T = ord_terms + (size_t)wv_i * 2 * stride;
     if (wv6.base != nullptr && row0 >= e.dim + e.kv_dim)  // the V rows of this layer are Q6_K (wave-uniform): the same records
-      rows_terms_q6k<2>(wv6.base, wv6.off_qh, act, local, m, nb, lane, T, stride);
+      rows_terms_q6k<2>(wv6.base, wv6.off_qh, act, local, m, nb, lane, T, stride, rs);
     else
-      rows_terms_q4k<2, true>(w.q, (const i32x4*)w.d, act, local, m, nb, lane, T, stride);
+      rows_terms_q4k<2, true>(w.q, (const i32x4*)w.d, act, local, m, nb, lane, T, stride, 0, rs);
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's own LDS stores have landed
     __builtin_amdgcn_wave_barrier();
     if (lane < 2) s = q4k_ordered_sum(T + lane * stride, nb);
   } else {
     const int nt = (nb + 3) & ~3;
     float* T = ord_terms + (size_t)wv_i * 2 * nt;
-    rows_terms<FMT, 2, typename ActOf<FMT>::type, true>(w.q, w.d, act, local, m, nb, lane, T, nt);
+    rows_terms<FMT, 2, typename ActOf<FMT>::type, true>(w.q, w.d, act, local, m, nb, lane, T, nt, rs);
     __builtin_amdgcn_wave_barrier();
     if (lane < 2) s = ordered_sum(T + lane * nt, nb);
   }
   const float s1 = __shfl(s, 1, 64);
-  if (lane == 0) qkv_epilogue(e, pre, row0, s, s1);
+  if constexpr (ARCH != QKV_LLAMA) {
+    if (lane == 0) qkv_epilogue_neox(e, pre, row0, rs, s, s1);
+  } else {
+    if (lane == 0) qkv_epilogue(e, pre, row0, s, s1);
+  }
 }
 // strict mode: the three GEMVs ran in scalar order into tmp[dim + 2 kv_dim]; apply the same epilogue
-__global__ __launch_bounds__(256) void k_qkv_epi(const float* __restrict__ tmp, QkvEpi e) {
+template <int ARCH = QKV_LLAMA>
+__global__ __launch_bounds__(256) void k_qkv_epi(const float* __restrict__ tmp, typename QkvArch<ARCH>::epi e) {
   int p = blockIdx.x * blockDim.x + threadIdx.x;
   int total = (e.dim + 2 * e.kv_dim) / 2;
-  if (p < total) qkv_epilogue(e, qkv_preload(e, 2 * p), 2 * p, tmp[2 * p], tmp[2 * p + 1]);
+  if constexpr (ARCH != QKV_LLAMA) {
+    int rs = 1;
+    const int r0 = p < total ? neox_pair_row0(e, p, rs) : 0;
+    if (p < total) qkv_epilogue_neox(e, qkv_preload_neox(e, r0, rs), r0, rs, tmp[r0], tmp[r0 + rs]);
+  } else {
+    if (p < total) qkv_epilogue(e, qkv_preload(e, 2 * p), 2 * p, tmp[2 * p], tmp[2 * p + 1]);
+  }
 }
 
 // batched prefill: the three GEMMs wrote qb (B, dim), kb / vb (B, kv_dim); row r is position *pos_d + r
+template <int ARCH = QKV_LLAMA>
 __global__ __launch_bounds__(256) void k_qkv_epi_rows(const float* __restrict__ qb, const float* __restrict__ kb,
-                                                     const float* __restrict__ vb, QkvEpi e) {
+                                                     const float* __restrict__ vb, typename QkvArch<ARCH>::epi e) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
   if (p >= (e.dim + 2 * e.kv_dim) / 2) return;
-  const int row0 = 2 * p;
+  int row0 = 2 * p, rs = 1;
+  if constexpr (ARCH != QKV_LLAMA) row0 = neox_pair_row0(e, p, rs);
   const float* src = row0 < e.dim              ? qb + (size_t)r * e.dim + row0
                      : row0 < e.dim + e.kv_dim ? kb + (size_t)r * e.kv_dim + (row0 - e.dim)
                                                : vb + (size_t)r * e.kv_dim + (row0 - e.dim - e.kv_dim);
-  QkvEpi er = e;
+  typename QkvArch<ARCH>::epi er = e;
   er.q_out = e.q_out + (size_t)r * e.dim;
-  qkv_epilogue(er, qkv_preload(e, row0, r), row0, src[0], src[1]);
+  if constexpr (ARCH != QKV_LLAMA)
+    qkv_epilogue_neox(er, qkv_preload_neox(e, row0, rs, r), row0, rs, src[0], src[rs]);
+  else
+    qkv_epilogue(er, qkv_preload(e, row0, r), row0, src[0], src[1]);
 }
 
 // softmax.rs:36-54 over scores[0..seq) in LDS, in place, by a workgroup of NW waves (4 or 16): max, exp through the f16

@@ -186,7 +186,7 @@ struct BlockFmt<CRABML_HIP_Q4_1> {  // planes qs[n][16] | (d, m)[n] f16 pairs; r
 // units l, l+64, ...  The R unit loads of a step are issued before any is consumed.
 template <int FMT, int R, class ACT>
 __device__ __forceinline__ void rows_partial(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd,
-                                             const ACT& act, int row0, int m, int nb, int lane, float acc[R]) {
+                                             const ACT& act, int row0, int m, int nb, int lane, float acc[R], int rs = 1) {
   using F = BlockFmt<FMT>;
 #pragma unroll
   for (int r = 0; r < R; r++) acc[r] = 0.f;
@@ -195,7 +195,7 @@ __device__ __forceinline__ void rows_partial(const i32x4* __restrict__ wq, const
     typename F::Blk blk[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      int row = row0 + r < m ? row0 + r : m - 1;
+      int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
       blk[r] = F::load(wq, wd, (size_t)row, nb, u);
     }
     const XUnit x = F::loadx(act, u);
@@ -209,7 +209,7 @@ __device__ __forceinline__ void rows_partial(const i32x4* __restrict__ wq, const
 // resident waves it only delays each wave's first use (profiles/r06_small_stage_ab.md).  Same terms, same per-lane order.
 template <int FMT, int R, class ACT>
 __device__ __forceinline__ void rows_partial_2step(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
-                                                   int row0, int m, int nb, int lane, float acc[R]) {
+                                                   int row0, int m, int nb, int lane, float acc[R], int rs = 1) {
   using F = BlockFmt<FMT>;
 #pragma unroll
   for (int r = 0; r < R; r++) acc[r] = 0.f;
@@ -218,7 +218,7 @@ __device__ __forceinline__ void rows_partial_2step(const i32x4* __restrict__ wq,
     typename F::Blk b0[R], b1[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      const int row = row0 + r < m ? row0 + r : m - 1;
+      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
       b0[r] = F::load(wq, wd, (size_t)row, nb, u);
       b1[r] = F::load(wq, wd, (size_t)row, nb, u + 64);
     }
@@ -237,7 +237,8 @@ __device__ __forceinline__ void rows_partial_2step(const i32x4* __restrict__ wq,
 // critical path; in the first step it is waiting for memory anyway.
 template <int FMT, int R, class ACT>
 __device__ __forceinline__ float rows_partial_rms(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
-                                                  int row0, int m, int nb, int lane, float acc[R], const RmsTail& rt, RmsReq rq) {
+                                                  int row0, int m, int nb, int lane, float acc[R], const RmsTail& rt, RmsReq rq,
+                                                  int rs = 1) {
   using F = BlockFmt<FMT>;
 #pragma unroll
   for (int r = 0; r < R; r++) acc[r] = 0.f;
@@ -250,7 +251,7 @@ __device__ __forceinline__ float rows_partial_rms(const i32x4* __restrict__ wq, 
     typename F::Blk blk[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      int row = row0 + r < m ? row0 + r : m - 1;
+      int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
       blk[r] = F::load(wq, wd, (size_t)row, nb, uu);
     }
     const XUnit x = F::loadx(act, uu);
@@ -275,12 +276,13 @@ __device__ __forceinline__ float rows_partial_rms(const i32x4* __restrict__ wq, 
 // to rows_partial_rms (k_qkv's default for such rows; profiles/r06_small_stage_ab.md).
 template <int FMT, int R, class ACT>
 __device__ __forceinline__ float rows_partial_rms_128(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
-                                                      int row0, int m, int nb, int lane, float acc[R], const RmsTail& rt, RmsReq rq) {
+                                                      int row0, int m, int nb, int lane, float acc[R], const RmsTail& rt, RmsReq rq,
+                                                      int rs = 1) {
   using F = BlockFmt<FMT>;
   typename F::Blk b0[R], b1[R];
 #pragma unroll
   for (int r = 0; r < R; r++) {
-    const int row = row0 + r < m ? row0 + r : m - 1;
+    const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
     b0[r] = F::load(wq, wd, (size_t)row, nb, lane);
     b1[r] = F::load(wq, wd, (size_t)row, nb, lane + 64);
   }
@@ -304,14 +306,14 @@ __device__ __forceinline__ float rows_partial_rms_128(const i32x4* __restrict__ 
 // ordered_sum.  Bit-identical to the one-thread-per-row loop (k_gemv_strict) and to the oracle.
 template <int FMT, int R, class ACT, bool UPFRONT = false>
 __device__ __forceinline__ void rows_terms(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act, int row0,
-                                           int m, int nb, int lane, float* __restrict__ T, int stride) {
+                                           int m, int nb, int lane, float* __restrict__ T, int stride, int rs = 1) {
   using F = BlockFmt<FMT>;
   const int nu = nb * F::UNITS;
   if (UPFRONT && nu == 128) {  // (uniform) rows of exactly two 64-unit steps: one round of requests (k_qkv_ord; as rows_partial_rms_128)
     typename F::Blk b0[R], b1[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      const int row = row0 + r < m ? row0 + r : m - 1;
+      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
       b0[r] = F::load(wq, wd, (size_t)row, nb, lane);
       b1[r] = F::load(wq, wd, (size_t)row, nb, lane + 64);
     }
@@ -333,7 +335,7 @@ __device__ __forceinline__ void rows_terms(const i32x4* __restrict__ wq, const u
     typename F::Blk blk[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      const int row = row0 + r < m ? row0 + r : m - 1;
+      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
       blk[r] = F::load(wq, wd, (size_t)row, nb, uu);
     }
     const XUnit x = F::loadx(act, uu);
@@ -549,7 +551,8 @@ __device__ __forceinline__ float q4k_ordered_sum(const float* __restrict__ t, in
 // the records of R rows of a Q4_K matrix: T[r * stride + sb * 12 ..]; lane = one 16-byte piece, as rows_partial_q4k
 template <int R, bool HDR_DPP>
 __device__ __forceinline__ void rows_terms_q4k(const i32x4* __restrict__ wq, const i32x4* __restrict__ wh, const ActQ8_K& act, int row0, int m,
-                                               int nsb, int lane, float* __restrict__ T, int stride, int cfirst = 0) {
+                                               int nsb, int lane, float* __restrict__ T, int stride, int cfirst = 0,
+                                               int rs = 1) {
   const int np = nsb * 8;
   for (int c0 = cfirst; c0 < np; c0 += 64) {  // cfirst: pieces below it were taken by the caller (a multiple of 64)
     const int c = c0 + lane;
@@ -557,7 +560,7 @@ __device__ __forceinline__ void rows_terms_q4k(const i32x4* __restrict__ wq, con
     const int cc = live ? c : np - 1;
     Q4KPiece<HDR_DPP> w[R];
 #pragma unroll
-    for (int r = 0; r < R; r++) w[r] = q4k_load<HDR_DPP>(wq, wh, (size_t)(row0 + r < m ? row0 + r : m - 1), nsb, cc, lane);
+    for (int r = 0; r < R; r++) w[r] = q4k_load<HDR_DPP>(wq, wh, (size_t)(row0 + r * rs < m ? row0 + r * rs : m - 1), nsb, cc, lane);
     const Q4KX x = q4k_loadx(act, cc);
 #pragma unroll
     for (int r = 0; r < R; r++) q4k_class_terms<HDR_DPP>(w[r], x, cc, live, T + (size_t)r * stride + (cc >> 3) * 12);
@@ -572,7 +575,7 @@ __device__ __forceinline__ void rows_terms_q4k(const i32x4* __restrict__ wq, con
 // lane = one 16-byte ql piece (8 per super-block); the levels are made signed bytes (q6 - 32), the v_dot4 sums split by byte position.
 template <int R>
 __device__ __forceinline__ void rows_terms_q6k(const char* __restrict__ w, size_t off_qh, const ActQ8_K& act, int row0, int m, int nsb, int lane,
-                                               float* __restrict__ T, int stride) {
+                                               float* __restrict__ T, int stride, int rs = 1) {
   const size_t n = off_qh / 128;
   const i32x4* wql = (const i32x4*)w;
   const i32x4* wqh = (const i32x4*)(w + off_qh);
@@ -590,7 +593,7 @@ __device__ __forceinline__ void rows_terms_q6k(const char* __restrict__ w, size_
     const float d8 = act.d[sb];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      const size_t blk = (size_t)(row0 + r < m ? row0 + r : m - 1) * nsb + sb;
+      const size_t blk = (size_t)(row0 + r * rs < m ? row0 + r * rs : m - 1) * nsb + sb;
       const i32x4 qv = __builtin_nontemporal_load(wql + blk * 8 + (cc & 7));
       const i32x4 hv = __builtin_nontemporal_load(wqh + blk * 4 + 2 * h + p);
       const i32x4 sc4 = __builtin_nontemporal_load(wsc + blk);
@@ -634,7 +637,8 @@ __device__ __forceinline__ void rows_terms_q6k(const char* __restrict__ w, size_
 
 template <int R, bool HDR_DPP = true, bool DBG = false>
 __device__ __forceinline__ void rows_partial_q4k(const i32x4* __restrict__ wq, const i32x4* __restrict__ wh, const ActQ8_K& act,
-                                                 int row0, int m, int nsb, int lane, float acc[R], int c0 = 0, int* dbg = nullptr) {
+                                                 int row0, int m, int nsb, int lane, float acc[R], int c0 = 0, int* dbg = nullptr,
+                                                 int rs = 1) {
   if (c0 == 0) {
 #pragma unroll
     for (int r = 0; r < R; r++) acc[r] = 0.f;
@@ -644,7 +648,7 @@ __device__ __forceinline__ void rows_partial_q4k(const i32x4* __restrict__ wq, c
     Q4KPiece<HDR_DPP> w[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      int row = row0 + r < m ? row0 + r : m - 1;
+      int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
       w[r] = q4k_load<HDR_DPP>(wq, wh, (size_t)row, nsb, c, lane);
     }
     const Q4KX x = q4k_loadx(act, c);
@@ -710,7 +714,7 @@ __device__ __forceinline__ void rows_partial_q5k(const char* __restrict__ w, siz
 // offset is applied as -32 * bsum (exact).  off_qh = byte offset of the qh plane = 128 * blocks in the tensor.
 template <int R, bool DBG = false>
 __device__ __forceinline__ void rows_partial_q6k(const char* __restrict__ w, size_t off_qh, const ActQ8_K& act, int row0, int m,
-                                                 int nsb, int lane, float acc[R], int* dbg = nullptr) {
+                                                 int nsb, int lane, float acc[R], int* dbg = nullptr, int rs = 1) {
   const size_t n = off_qh / 128;  // blocks in the tensor
   const i32x4* wql = (const i32x4*)w;
   const i32x4* wqh = (const i32x4*)(w + off_qh);
@@ -727,7 +731,7 @@ __device__ __forceinline__ void rows_partial_q6k(const char* __restrict__ w, siz
     unsigned short dw[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-      const int row = row0 + r < m ? row0 + r : m - 1;
+      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
       const size_t blk = (size_t)row * nsb + sb;
       qv[r] = __builtin_nontemporal_load(wql + blk * 8 + (c & 7));
       hv[r] = __builtin_nontemporal_load(wqh + blk * 4 + 2 * h + p);
@@ -768,11 +772,11 @@ __device__ __forceinline__ void rows_partial_q6k(const char* __restrict__ w, siz
 // Q4_K); `wd` is the format's second plane (f16 scales / 16-byte headers), `nu` the blocks per row
 template <int FMT, int R, class ACT>
 __device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
-                                         int row0, int m, int nu, int lane, float acc[R]) {
+                                         int row0, int m, int nu, int lane, float acc[R], int rs = 1) {
   if constexpr (FMT == CRABML_HIP_Q4_K)
-    rows_partial_q4k<R>(wq, (const i32x4*)wd, act, row0, m, nu, lane, acc);
+    rows_partial_q4k<R>(wq, (const i32x4*)wd, act, row0, m, nu, lane, acc, 0, nullptr, rs);
   else
-    rows_partial<FMT, R>(wq, wd, act, row0, m, nu, lane, acc);
+    rows_partial<FMT, R>(wq, wd, act, row0, m, nu, lane, acc, rs);
 }
 template <int FMT>
 struct ActOf {

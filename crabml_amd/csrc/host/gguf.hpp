@@ -337,16 +337,17 @@ inline bool ggml_block_geometry(uint32_t t, size_t* block_bytes, size_t* block_e
 }
 inline bool GGUFFile::ggml_block_geometry_(uint32_t t, size_t* bb, size_t* be) { return ggml_block_geometry(t, bb, be); }
 
-// CpuLlamaModelLoader::load_config (model.rs:545-625), llama architecture
+// CpuLlamaModelLoader::load_config (model.rs:545-625), llama and qwen2 architectures (the keys under the architecture's prefix)
 inline LlamaConfig load_llama_config(const GGUFFile& gf) {
-  if (gf.architecture() != "llama") throw Error(ErrorKind::ModelError, "unsupported architecture " + gf.architecture());
-  const std::string p = "llama";
+  const std::string p = gf.architecture();
+  if (p != "llama" && p != "qwen2") throw Error(ErrorKind::ModelError, "unsupported architecture " + p);
   auto need_u32 = [&](const std::string& k) -> size_t {
     auto v = gf.get_u32(k);
     if (!v) throw Error(ErrorKind::ModelError, "missing u32 metadata " + k);  // the reference unwrap()s here
     return *v;
   };
   LlamaConfig c;
+  c.architecture = p == "qwen2" ? ARCH_QWEN2 : ARCH_LLAMA;
   c.n_heads = need_u32(p + ".attention.head_count");
   c.n_layers = need_u32(p + ".block_count");
   c.hidden_dim = need_u32(p + ".feed_forward_length");
@@ -393,7 +394,8 @@ inline HipTensor load_gguf_tensor(const GGUFFile& gf, const std::string& name, c
   return HipTensor::from_cpu(info->data, nbytes, dims, (GGMLType)info->ggml_type, device);
 }
 
-// CpuLlamaModelLoader::load_weights (model.rs:140-300, "llama" arm) + output.weight optional (model.rs:437)
+// CpuLlamaModelLoader::load_weights (model.rs:140-300, "llama" arm; "qwen2" arm :285-360: + blk.N.attn_{q,k,v}.bias in their stored
+// type) + output.weight optional (model.rs:437)
 inline std::shared_ptr<LlamaWeights<HipTensor>> load_llama_weights(const GGUFFile& gf, const LlamaConfig& conf,
                                                                   const HipTensorDeviceRef& device) {
   auto w = std::make_shared<LlamaWeights<HipTensor>>();
@@ -413,6 +415,11 @@ inline std::shared_ptr<LlamaWeights<HipTensor>> load_llama_weights(const GGUFFil
     w->ffn_up_weight.push_back(load_gguf_tensor(gf, b + "ffn_up.weight", device));
     w->rms_att_weight.push_back(f32(b + "attn_norm.weight"));
     w->rms_ffn_weight.push_back(f32(b + "ffn_norm.weight"));
+    if (conf.architecture == ARCH_QWEN2) {
+      w->bq.push_back(load_gguf_tensor(gf, b + "attn_q.bias", device));
+      w->bk.push_back(load_gguf_tensor(gf, b + "attn_k.bias", device));
+      w->bv.push_back(load_gguf_tensor(gf, b + "attn_v.bias", device));
+    }
   }
   w->rms_final_weight = f32("output_norm.weight");
   if (gf.get_tensor_info("output.weight")) w->output_weight = load_gguf_tensor(gf, "output.weight", device);

@@ -61,10 +61,12 @@ class TpComm {
 
 class HipLlamaRunner {
  public:
+  // create_entry (tests): 0 = crabml_hip_llama_create for a Llama model without biases, crabml_hip_llama_create_arch otherwise;
+  // 1 = create_arch with the architecture struct always; 2 = create_arch(NULL) (Llama models)
   HipLlamaRunner(const LlamaConfig& conf, std::shared_ptr<LlamaWeights<HipTensor>> w, HipTensorDeviceRef device,
                  size_t seq_len, bool use_f16_kv_cache, bool use_graph = true, bool prefetch = true, int tp_size = 1,
                  int tp_rank = 0, std::shared_ptr<TpComm> comm = nullptr, bool norm_epilogue = true, int extra_flags = 0,
-                 size_t attn_long_from = 0, size_t prefill_chunk = 0)
+                 size_t attn_long_from = 0, size_t prefill_chunk = 0, int create_entry = 0)
       : conf_(conf), weights_(std::move(w)), device_(std::move(device)), comm_(std::move(comm)), tp_size_(tp_size > 1 ? tp_size : 1) {
     crabml_hip_llama_config_t c{};
     c.embedding_dim = conf.embedding_dim;
@@ -107,7 +109,24 @@ class HipLlamaRunner {
     cw.ffn_up_weight = up.data();
     cw.rms_final_weight = W.rms_final_weight.raw();
     cw.output_weight = W.output_weight ? W.output_weight->raw() : nullptr;
-    device_->check(crabml_hip_llama_create(device_->raw(), &c, &cw, &ctx_));
+    // the architecture and Qwen2's biases (crabml_hip_llama_create_arch; Llama: the plain create)
+    auto bq = raws(W.bq), bk = raws(W.bk), bv = raws(W.bv);
+    crabml_hip_llama_arch_t arch{};
+    arch.architecture = conf.architecture;
+    if (conf.architecture == ARCH_QWEN2 || !bq.empty() || !bk.empty() || !bv.empty()) {  // (biases on a Llama model: the C ABI refuses)
+      for (auto* v : {&bq, &bk, &bv})
+        if (v->size() != conf.n_layers) throw Error(ErrorKind::ModelError, "qwen2: the biases do not have n_layers entries");
+      arch.bq = bq.data();
+      arch.bk = bk.data();
+      arch.bv = bv.data();
+    }
+    const bool plain = conf.architecture == ARCH_LLAMA && bq.empty() && bk.empty() && bv.empty();
+    if (create_entry == 2)
+      device_->check(crabml_hip_llama_create_arch(device_->raw(), &c, &cw, nullptr, &ctx_));
+    else if (plain && create_entry == 0)
+      device_->check(crabml_hip_llama_create(device_->raw(), &c, &cw, &ctx_));
+    else
+      device_->check(crabml_hip_llama_create_arch(device_->raw(), &c, &cw, &arch, &ctx_));
   }
   ~HipLlamaRunner() {
     if (ctx_) crabml_hip_llama_destroy(ctx_);

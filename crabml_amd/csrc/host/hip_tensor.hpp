@@ -129,6 +129,7 @@ class HipTensor {
 
   HipTensor() = default;
   static RopeMode rope_mode_llama() { return RopeMode::Llama; }
+  static RopeMode rope_mode_neox() { return RopeMode::Neox; }
 
   // ---- constructors ------------------------------------------------------------------------------
   // Tensor::from_cpu (api.rs:14-19)

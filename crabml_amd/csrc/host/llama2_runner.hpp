@@ -2,7 +2,7 @@
 // reference: `Llama2Runner<T: Tensor>` (crabml-llama2/src/llama2.rs:26-43).  It issues the same op
 // sequence per decode step (forward :184-211, forward_llama :213-281, forward_multi_query_attention
 // :527-603, forward_ffn :605-638), so running it over HipTensor is what "crabml-llama2 runs unchanged"
-// means on this side of the boundary.  Llama architecture only (gemma/qwen2/phi2 are out of scope).
+// means on this side of the boundary.  Llama and Qwen2 (forward_qwen2 :283-351); gemma / phi2 are out of scope.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -16,8 +16,12 @@
 
 namespace crabml_host {
 
+// crabml-llama2/src/model.rs:22-27 (the values of crabml_hip_model_arch)
+enum ModelArchitecture : uint32_t { ARCH_LLAMA = 0, ARCH_GEMMA = 1, ARCH_QWEN2 = 2, ARCH_PHI2 = 3 };
+
 // crabml-llama2/src/model.rs:30-53
 struct LlamaConfig {
+  uint32_t architecture = ARCH_LLAMA;
   size_t embedding_dim = 0, hidden_dim = 0, n_layers = 0, n_heads = 0, n_kv_heads = 0, vocab_size = 0, seq_len = 0;
   float rms_norm_eps = 1e-5f;
   std::optional<size_t> rope_dim;
@@ -25,12 +29,13 @@ struct LlamaConfig {
   size_t head_size() const { return embedding_dim / n_heads; }
 };
 
-// crabml-llama2/src/model.rs:55-84 (Llama subset)
+// crabml-llama2/src/model.rs:55-84 (Llama subset + Qwen2's q / k / v biases)
 template <class T>
 struct LlamaWeights {
   T token_embed;
   std::vector<T> rms_att_weight, rms_ffn_weight;
   std::vector<T> wq, wk, wv, wo;
+  std::vector<T> bq, bk, bv;  // Qwen2: (dim), (kv_dim), (kv_dim) f32 per layer; empty for Llama
   std::vector<T> ffn_gate_weight, ffn_down_weight, ffn_up_weight;
   T rms_final_weight;
   std::optional<T> output_weight;
@@ -219,7 +224,9 @@ class Llama2Runner {
 
   // llama2.rs:184-211
   void forward(const std::vector<size_t>& tokens, size_t pos) {
-    T x = forward_llama(tokens, pos);
+    if (conf_.architecture != ARCH_LLAMA && conf_.architecture != ARCH_QWEN2)
+      throw Error(ErrorKind::NotImplemented, "Llama2Runner: only the llama and qwen2 architectures");
+    T x = conf_.architecture == ARCH_QWEN2 ? forward_qwen2(tokens, pos) : forward_llama(tokens, pos);
     T x_final = T::alloc({conf_.embedding_dim}, f32_, device_);
     x_final.copy_rows_from(x, {tokens.size() - 1});
     const T& ow = weights_->output_weight ? *weights_->output_weight : weights_->token_embed;
@@ -267,6 +274,41 @@ class Llama2Runner {
       k = k.reshape({n_batch, n_kv_heads, head_dim});
       q = q.rope_inplace(rope_llama(), pos, rope_dim);
       k = k.rope_inplace(rope_llama(), pos, rope_dim);
+      x = forward_multi_query_attention(q, k, v, l, n_kv_heads, n_heads, embed_dim, head_dim, n_batch);
+      x = x.with_name("attn_out:" + std::to_string(l) + ":" + std::to_string(pos));
+      x = x.add_inplace(x_attn_orig);
+      x = forward_ffn(x, l);
+      x = x.with_name("ffn_out:" + std::to_string(l) + ":" + std::to_string(pos));
+    }
+    x = x.rms_norm_inplace(conf_.rms_norm_eps);
+    x = x.mul_inplace(w.rms_final_weight);
+    return x.with_name("final_rmsnorm:" + std::to_string(pos));
+  }
+
+  // llama2.rs:283-351: forward_llama with the q / k / v biases (:315-317) and NEOX rope (:325-326)
+  T forward_qwen2(const std::vector<size_t>& tokens, size_t pos) {
+    const size_t embed_dim = conf_.embedding_dim, n_heads = conf_.n_heads, n_kv_heads = conf_.n_kv_heads;
+    const size_t head_dim = conf_.head_size();
+    const size_t rope_dim = conf_.rope_dim.value_or(head_dim);
+    const size_t n_batch = tokens.size();
+    const LlamaWeights<T>& w = *weights_;
+    T x = T::alloc({n_batch, embed_dim}, f32_, device_);
+    x.copy_rows_from(w.token_embed, tokens);
+    for (size_t l = 0; l < conf_.n_layers; l++) {
+      T x_attn_orig = x.dup();
+      x = x.rms_norm_inplace(conf_.rms_norm_eps);
+      x = x.mul_inplace(w.rms_att_weight[l]);
+      x = x.with_name("attn_rmsnorm:" + std::to_string(l) + ":" + std::to_string(pos));
+      T q = w.wq[l].matmul_vec(x);
+      T k = w.wk[l].matmul_vec(x);
+      T v = w.wv[l].matmul_vec(x);
+      q = q.add_inplace(w.bq[l]);
+      k = k.add_inplace(w.bk[l]);
+      v = v.add_inplace(w.bv[l]);
+      q = q.reshape({n_batch, n_heads, head_dim});
+      k = k.reshape({n_batch, n_kv_heads, head_dim});
+      q = q.rope_inplace(T::rope_mode_neox(), pos, rope_dim);
+      k = k.rope_inplace(T::rope_mode_neox(), pos, rope_dim);
       x = forward_multi_query_attention(q, k, v, l, n_kv_heads, n_heads, embed_dim, head_dim, n_batch);
       x = x.with_name("attn_out:" + std::to_string(l) + ":" + std::to_string(pos));
       x = x.add_inplace(x_attn_orig);

@@ -27,6 +27,15 @@ static std::vector<size_t> to_shape(const py::sequence& s) {
 using Runner = Llama2Runner<HipTensor>;
 using Weights = LlamaWeights<HipTensor>;
 
+// general.architecture names (model.rs:553-563) <-> crabml_hip_model_arch
+static const char* const ARCH_NAMES[] = {"llama", "gemma", "qwen2", "phi2"};
+static uint32_t arch_of_name(const std::string& n) {
+  for (uint32_t i = 0; i < 4; i++)
+    if (n == ARCH_NAMES[i]) return i;
+  throw Error(ErrorKind::BadInput, "unknown architecture '" + n + "'");
+}
+static std::string arch_name(uint32_t a) { return a < 4 ? ARCH_NAMES[a] : "unknown"; }
+
 PYBIND11_MODULE(_host, m) {
   m.doc() = "crabml-hip host mirror over the C ABI of libcrabml_hip.so";
 
@@ -277,8 +286,9 @@ PYBIND11_MODULE(_host, m) {
 
   py::class_<LlamaConfig>(m, "LlamaConfig")
       .def(py::init([](size_t embedding_dim, size_t hidden_dim, size_t n_layers, size_t n_heads, size_t n_kv_heads,
-                       size_t vocab_size, size_t seq_len, float rms_norm_eps, py::object rope_dim) {
+                       size_t vocab_size, size_t seq_len, float rms_norm_eps, py::object rope_dim, const std::string& architecture) {
              LlamaConfig c;
+             c.architecture = arch_of_name(architecture);
              c.embedding_dim = embedding_dim;
              c.hidden_dim = hidden_dim;
              c.n_layers = n_layers;
@@ -292,7 +302,8 @@ PYBIND11_MODULE(_host, m) {
            }),
            py::arg("embedding_dim"), py::arg("hidden_dim"), py::arg("n_layers"), py::arg("n_heads"),
            py::arg("n_kv_heads"), py::arg("vocab_size"), py::arg("seq_len"), py::arg("rms_norm_eps") = 1e-5f,
-           py::arg("rope_dim") = py::none())
+           py::arg("rope_dim") = py::none(), py::arg("architecture") = "llama")
+      .def_property_readonly("architecture", [](const LlamaConfig& c) { return arch_name(c.architecture); })
       .def_readonly("embedding_dim", &LlamaConfig::embedding_dim)
       .def_readonly("hidden_dim", &LlamaConfig::hidden_dim)
       .def_readonly("n_layers", &LlamaConfig::n_layers)
@@ -316,6 +327,9 @@ PYBIND11_MODULE(_host, m) {
       .def_readwrite("wk", &Weights::wk)
       .def_readwrite("wv", &Weights::wv)
       .def_readwrite("wo", &Weights::wo)
+      .def_readwrite("bq", &Weights::bq)
+      .def_readwrite("bk", &Weights::bk)
+      .def_readwrite("bv", &Weights::bv)
       .def_readwrite("ffn_gate_weight", &Weights::ffn_gate_weight)
       .def_readwrite("ffn_down_weight", &Weights::ffn_down_weight)
       .def_readwrite("ffn_up_weight", &Weights::ffn_up_weight)
@@ -428,17 +442,17 @@ PYBIND11_MODULE(_host, m) {
       .def(py::init([](const LlamaConfig& conf, std::shared_ptr<Weights> w, std::shared_ptr<HipTensorDevice> dev,
                        size_t seq_len, bool use_f16_kv_cache, bool use_graph, bool prefetch, int tp_size, int tp_rank,
                        std::shared_ptr<TpComm> comm, bool norm_epilogue, int extra_flags, size_t attn_long_from,
-                       size_t prefill_chunk) {
+                       size_t prefill_chunk, int create_entry) {
              auto* r = new HipLlamaRunner(conf, std::move(w), std::move(dev), seq_len, use_f16_kv_cache, use_graph, prefetch,
                                           tp_size, tp_rank, std::move(comm), norm_epilogue, extra_flags, attn_long_from,
-                                          prefill_chunk);
+                                          prefill_chunk, create_entry);
              r->set_seq_cap(seq_len);
              return r;
            }),
            py::arg("conf"), py::arg("weights"), py::arg("device"), py::arg("seq_len"), py::arg("use_f16_kv_cache"),
            py::arg("use_graph") = true, py::arg("prefetch") = true, py::arg("tp_size") = 1, py::arg("tp_rank") = 0,
            py::arg("comm") = std::shared_ptr<TpComm>(), py::arg("norm_epilogue") = true,
-           py::arg("extra_flags") = 0, py::arg("attn_long_from") = 0, py::arg("prefill_chunk") = 0)
+           py::arg("extra_flags") = 0, py::arg("attn_long_from") = 0, py::arg("prefill_chunk") = 0, py::arg("create_entry") = 0)
       .def("prefill",
            [](HipLlamaRunner& r, const std::vector<uint32_t>& tokens) {
              std::vector<float> lg;

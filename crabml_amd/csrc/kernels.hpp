@@ -95,6 +95,17 @@ void launch_softmax(hipStream_t st, float* x, size_t rows, size_t cols, const ui
 struct RopeTable {
   float cs[512];  // (cos, sin) pairs, up to 256 rotary pairs
 };
+// NEOX's (cos, sin) pairs at position `pos` into cs[0 .. 2 npairs) (rope.rs:65-80: f32 powf, a division, then cosf / sinf); shared by
+// the trait op (lazy.hip) and the Qwen2 decode step's table (fused.hip)
+inline void rope_table_neox(float* cs, size_t pos, size_t head_dim, size_t npairs) {
+  for (size_t i = 0; i < npairs; i++) {
+    float fe = 2.0f * (float)i / (float)head_dim;
+    float timescale = powf(10000.0f, fe);
+    float theta = (float)pos / timescale;
+    cs[2 * i] = cosf(theta);
+    cs[2 * i + 1] = sinf(theta);
+  }
+}
 void launch_rope(hipStream_t st, float* x, size_t n_heads, size_t head_dim, int mode, size_t rope_dims,
                  const RopeTable& tab);
 void launch_contiguous(hipStream_t st, const void* src, void* dst, int elem_size, const size_t shape[3],

@@ -104,13 +104,7 @@ int lazy_exec(crabml_hip_device* dev, LazyOp& o) {
             theta *= theta_scale;
           }
         } else {  // rope.rs:65-80
-          for (size_t i = 0; i < npairs; i++) {
-            float fe = 2.0f * (float)i / (float)head_dim;
-            float timescale = powf(10000.0f, fe);
-            float theta = (float)p / timescale;
-            tab.cs[2 * i] = cosf(theta);
-            tab.cs[2 * i + 1] = sinf(theta);
-          }
+          rope_table_neox(tab.cs, p, head_dim, npairs);
         }
         launch_rope(st, (float*)o.a->ptr + bi * bi_stride, n_heads, head_dim, (int)mode, rope_dims, tab);
       }
@@ -206,6 +200,9 @@ int run_queue(crabml_hip_device* dev, LazyState& L) {
 }
 
 // ---- learning: parse one complete token of Llama2Runner::forward (llama2.rs:184-281, 527-638; n_batch = 1) ----------------
+// Two sequences are accepted: forward_llama's, and forward_qwen2's (llama2.rs:283-351) -- the same with q / k / v.add_inplace(bias)
+// after the three GEMVs of EVERY layer and NEOX rope.  Adds with Llama rope, NEOX without adds, a layer without its adds, a bias that is
+// not an f32 vector of the GEMV's length: not learned (the token runs op by op).
 struct Learner {
   const std::vector<LazyOp>& q;
   size_t i;
@@ -271,6 +268,7 @@ bool learn_token(Learner& P, LazyModel& M, int* slot_xnorm, int* slot_xfinal, in
   M.token_embed = emb;
   size_t pos = 0, hd = 0, kv_dim = 0, hidden = 0, n_heads = 0, n_kv = 0, seq = 0, rope_dim = 0;
   uint32_t kv_dtype = 0;
+  bool qwen2 = false;
   float eps = 0.f;
   int l = 0;
   while (P.i < P.q.size() && P.q[P.i].kind == LZ_DUP) {
@@ -305,8 +303,24 @@ bool learn_token(Learner& P, LazyModel& M, int* slot_xnorm, int* slot_xfinal, in
     const crabml_hip_buf* vv = o->out;
     M.wv.push_back(o->a);
     P.push(*o);
-    o = P.take(LZ_ROPE);  // q.rope_inplace(Llama, pos, rope_dim)                        :255
-    NEED(o && o->a == qv && o->s[0] == 1 && o->s[1] == dim && o->s[3] == CRABML_HIP_ROPE_LLAMA);
+    // forward_qwen2: q / k / v.add_inplace(&bq / bk / bv[l])                                qwen2 :315-317
+    const bool adds = P.i < P.q.size() && P.q[P.i].kind == LZ_ADD;
+    if (first) qwen2 = adds;
+    NEED(adds == qwen2);
+    if (qwen2) {
+      const crabml_hip_buf* const outs[3] = {qv, kv, vv};
+      const size_t lens[3] = {dim, kv_dim, kv_dim};
+      std::vector<const crabml_hip_buf*>* const biases[3] = {&M.bq, &M.bk, &M.bv};
+      for (int j = 0; j < 3; j++) {
+        o = P.take(LZ_ADD);
+        NEED(o && o->a == outs[j] && o->s[0] == lens[j] && o->s[1] == lens[j] && is_f32_vec(o->b, lens[j]) && P.slot.count(o->b) == 0);
+        biases[j]->push_back(o->b);
+        P.push(*o);
+      }
+    }
+    const size_t rope_mode = qwen2 ? CRABML_HIP_ROPE_NEOX : CRABML_HIP_ROPE_LLAMA;
+    o = P.take(LZ_ROPE);  // q.rope_inplace(Llama | Neox, pos, rope_dim)                 :255, qwen2 :325
+    NEED(o && o->a == qv && o->s[0] == 1 && o->s[1] == dim && o->s[3] == rope_mode);
     if (first) {
       hd = o->s[2];
       pos = o->s[4];
@@ -319,7 +333,7 @@ bool learn_token(Learner& P, LazyModel& M, int* slot_xnorm, int* slot_xfinal, in
     NEED(o->s[2] == hd && o->s[4] == pos && o->s[5] == rope_dim);
     P.push(*o, LR_ROPE);
     o = P.take(LZ_ROPE);  // k.rope_inplace                                               :256
-    NEED(o && o->a == kv && o->s[0] == 1 && o->s[1] == kv_dim && o->s[2] == hd && o->s[3] == CRABML_HIP_ROPE_LLAMA && o->s[4] == pos &&
+    NEED(o && o->a == kv && o->s[0] == 1 && o->s[1] == kv_dim && o->s[2] == hd && o->s[3] == rope_mode && o->s[4] == pos &&
          o->s[5] == rope_dim);
     P.push(*o, LR_ROPE);
     // key_cache[l].concatenate(k.reshape.transpose([1, 0, 2]), 1)                         :542-554
@@ -443,6 +457,7 @@ bool learn_token(Learner& P, LazyModel& M, int* slot_xnorm, int* slot_xfinal, in
   c.use_f16_kv_cache = kv_dtype == CRABML_HIP_F16 ? 1 : 0;
   c.flags = 0;  // (the step's graph is captured: the whole token is launched as soon as its position is verified)
   c.tp_size = 1;
+  M.qwen2 = qwen2;
   return true;
 }
 #undef NEED

@@ -86,9 +86,13 @@ struct LazyModel {
   const crabml_hip_buf* output = nullptr;
   std::vector<const crabml_hip_buf*> rms_att, rms_ffn, wq, wk, wv, wo, gate, down, up;
   std::vector<crabml_hip_buf*> kc, vc;  // the runner's KV caches: [n_kv_heads][seq_len][head_dim], f16 or f32
+  // forward_qwen2 (llama2.rs:283-351): the q / k / v biases of every layer; empty for forward_llama
+  bool qwen2 = false;
+  std::vector<const crabml_hip_buf*> bq, bk, bv;
   bool same_buffers(const LazyModel& o) const {
     return token_embed == o.token_embed && rms_final == o.rms_final && output == o.output && rms_att == o.rms_att && rms_ffn == o.rms_ffn &&
-           wq == o.wq && wk == o.wk && wv == o.wv && wo == o.wo && gate == o.gate && down == o.down && up == o.up && kc == o.kc && vc == o.vc;
+           wq == o.wq && wk == o.wk && wv == o.wv && wo == o.wo && gate == o.gate && down == o.down && up == o.up && kc == o.kc && vc == o.vc &&
+           qwen2 == o.qwen2 && bq == o.bq && bk == o.bk && bv == o.bv;
   }
 };
 

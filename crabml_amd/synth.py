@@ -140,6 +140,8 @@ class ModelShape:
     seq_len: int
     rms_eps: float = 1e-5
     rope_dim: Optional[int] = None
+    arch: str = "llama"  # general.architecture: "llama" or "qwen2" (q / k / v biases, NEOX rope: llama2.rs:283-351)
+    tied: bool = False   # no output.weight: the classifier is token_embd (llama2.rs:203-207)
 
     @property
     def head_dim(self):
@@ -159,6 +161,12 @@ SHAPES = {
     "tiny-gqa": ModelShape("tiny-gqa", 512, 1024, 2, 8, 2, 1024, 64, 1e-5, None),
     # ... and one with Llama-3's head_dim of 128 (the kernels specialized for it: k_attn_s<128>, k_attn_wo)
     "tiny-hd128": ModelShape("tiny-hd128", 512, 1024, 2, 4, 2, 1024, 128, 1e-5, None),
+    # Qwen2 (seq_len: under the decode step's create-time cap, not the files' context_length of 32768)
+    "qwen2.5-7b": ModelShape("Qwen2.5-7B", 3584, 18944, 28, 28, 4, 152064, 8192, 1e-6, None, "qwen2"),
+    "qwen2.5-3b": ModelShape("Qwen2.5-3B", 2048, 11008, 36, 16, 2, 151936, 8192, 1e-6, None, "qwen2", True),
+    # tiny Qwen2 shapes for tests: GQA group 4 with head_dim 64, and Qwen2.5-7B's group of 7 with head_dim 128 (dims multiples of 256)
+    "tiny-qwen2": ModelShape("tiny-qwen2", 512, 1024, 2, 8, 2, 1024, 64, 1e-6, None, "qwen2"),
+    "tiny-qwen2-g7": ModelShape("tiny-qwen2-g7", 1792, 1024, 2, 14, 2, 1024, 64, 1e-6, None, "qwen2"),
 }
 
 
@@ -180,7 +188,7 @@ class RawModel:
         s = self.shape
         total = 0
         for name, t in self.tensors.items():
-            if name.endswith("_norm.weight") or name == "token_embd.weight":
+            if name.endswith("_norm.weight") or name.endswith(".bias") or name == "token_embd.weight":
                 continue
             n = 1
             for d in t.shape:
@@ -211,16 +219,20 @@ def flip_scale_signs(model: "RawModel", seed: int = 5) -> None:
 
 def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional[int] = None,
                 embed_type: Optional[int] = None, tp: int = 1, output_type: Optional[int] = None,
-                k_m_mix: bool = False, tp_split_vocab: bool = False) -> RawModel:
+                k_m_mix: bool = False, tp_split_vocab: bool = False, arch: Optional[str] = None) -> RawModel:
     """All-`wtype` synthetic Llama weights with GGUF tensor names (model.rs:228-283); norms are F32
     (the loader dequantizes them, model.rs:267-282).  tp > 1: the tensors get one rank's LOCAL shard shapes
     (what crabml_amd.tp.shard_model would cut; random bytes either way -- for timing one rank of a large model
     without materialising all of it).  k_m_mix (with wtype = Q4_K): the tensor-type recipe of llama.cpp's Q4_K_M
     files -- attn_v and ffn_down in Q6_K on the `use_more_bits` layers, output.weight in Q6_K -- i.e. different
-    GGML types inside one layer (all with the Q8_K rhs)."""
+    GGML types inside one layer (all with the Q8_K rhs).  arch = "qwen2" (default: the shape's): blk.N.attn_{q,k,v}.bias as F32
+    N(0, 1) with a few channels per vector 20-60x larger (real Qwen2 k biases reach the hundreds), from a generator of their own:
+    the weights are those of the same seed's Llama model, and Llama models stay byte-identical."""
     rng = np.random.default_rng(seed)
     L = shape.n_layers if n_layers is None else n_layers
-    shp = ModelShape(**{**shape.__dict__, "n_layers": L})
+    arch = shape.arch if arch is None else arch
+    assert arch in ("llama", "qwen2"), arch
+    shp = ModelShape(**{**shape.__dict__, "n_layers": L, "arch": arch})
     m = RawModel(shp, wtype)
     et = wtype if embed_type is None else embed_type
 
@@ -244,7 +256,17 @@ def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional
         add(f"blk.{l}.ffn_up.weight", hid_l, shape.dim, wtype)
         norm(f"blk.{l}.attn_norm.weight", shape.dim)
         norm(f"blk.{l}.ffn_norm.weight", shape.dim)
+    if arch == "qwen2":
+        brng = np.random.default_rng([seed, 2])
+        for l in range(L):
+            for nm, n in (("attn_q", dim_l), ("attn_k", kv_l), ("attn_v", kv_l)):
+                b = brng.standard_normal(n).astype(np.float32)
+                big = brng.choice(n, size=max(1, n // 128), replace=False)
+                b[big] *= brng.uniform(20.0, 60.0, size=big.size).astype(np.float32)
+                m.tensors[f"blk.{l}.{nm}.bias"] = RawTensor(b.view(np.uint8), [n], F32)
     norm("output_norm.weight", shape.dim)
+    if shape.tied and output_type is None and not k_m_mix:
+        return m
     # llama.cpp's "Q4_0" / "Q4_K_M" files keep output.weight in Q6_K: `output_type` builds that mix
     # tp_split_vocab (with tp > 1): one rank's vocabulary shard of the classifier (CRABML_HIP_LLAMA_TP_SPLIT_VOCAB)
     add("output.weight", shape.vocab // tp if tp_split_vocab else shape.vocab, shape.dim,
@@ -279,9 +301,13 @@ def to_hip(model: RawModel, device):
     w.rms_final_weight = up("output_norm.weight")
     if "output.weight" in model.tensors:
         w.output_weight = up("output.weight")
+    if s.arch == "qwen2":
+        w.bq = [up(f"blk.{l}.attn_q.bias") for l in range(s.n_layers)]
+        w.bk = [up(f"blk.{l}.attn_k.bias") for l in range(s.n_layers)]
+        w.bv = [up(f"blk.{l}.attn_v.bias") for l in range(s.n_layers)]
     conf = ca.LlamaConfig(embedding_dim=s.dim, hidden_dim=s.hidden, n_layers=s.n_layers, n_heads=s.n_heads,
                           n_kv_heads=s.n_kv_heads, vocab_size=s.vocab, seq_len=s.seq_len, rms_norm_eps=s.rms_eps,
-                          rope_dim=s.rope_dim)
+                          rope_dim=s.rope_dim, architecture=s.arch)
     return conf, w
 
 
@@ -296,7 +322,7 @@ _GGUF_FMT = {"u8": "<B", "i8": "<b", "u16": "<H", "i16": "<h", "u32": "<I", "i32
 
 def write_gguf(model: RawModel, path: str, version: int = 3, alignment: int = 32, write_alignment_key=None,
                extra_kv=None, tensor_order=None, data_start: str = "reference", pad_header_to_alignment: bool = False) -> None:
-    """Serialize a RawModel as a llama-architecture GGUF file.  write_alignment_key: None = omit general.alignment
+    """Serialize a RawModel as a GGUF file of its architecture ("llama" or "qwen2": the keys under that prefix, model.rs:553-633).  write_alignment_key: None = omit general.alignment
     (readers assume 32), or a value-type name ("u32", "u64", "i32", ...) to store `alignment` under that type.
     extra_kv: list of (key, type_name, value); arrays as (key, "arr", (elem_type_name, [values])).
     data_start: "reference" = always skip to the NEXT multiple of the alignment (gguf.rs:722-724: a whole extra block when
@@ -321,13 +347,14 @@ def write_gguf(model: RawModel, path: str, version: int = 3, alignment: int = 32
             return struct.pack("<I", _GGUF_T[et]) + wlen(len(items)) + b"".join(wval(et, i) for i in items)
         return struct.pack(_GGUF_FMT[t], v)
 
-    kv = [("general.architecture", "str", "llama"), ("general.name", "str", s.name),
-          ("llama.context_length", "u32", s.seq_len), ("llama.embedding_length", "u32", s.dim),
-          ("llama.block_count", "u32", s.n_layers), ("llama.feed_forward_length", "u32", s.hidden),
-          ("llama.attention.head_count", "u32", s.n_heads), ("llama.attention.head_count_kv", "u32", s.n_kv_heads),
-          ("llama.attention.layer_norm_rms_epsilon", "f32", s.rms_eps)]
+    a = s.arch
+    kv = [("general.architecture", "str", a), ("general.name", "str", s.name),
+          (a + ".context_length", "u32", s.seq_len), (a + ".embedding_length", "u32", s.dim),
+          (a + ".block_count", "u32", s.n_layers), (a + ".feed_forward_length", "u32", s.hidden),
+          (a + ".attention.head_count", "u32", s.n_heads), (a + ".attention.head_count_kv", "u32", s.n_kv_heads),
+          (a + ".attention.layer_norm_rms_epsilon", "f32", s.rms_eps)]
     if s.rope_dim is not None:
-        kv.append(("llama.rope.dimension_count", "u32", s.rope_dim))
+        kv.append((a + ".rope.dimension_count", "u32", s.rope_dim))
     kv += [("tokenizer.ggml.model", "str", "llama"),
            ("tokenizer.ggml.tokens", "arr", ("str", [f"<{i}>" for i in range(s.vocab)])),
            ("tokenizer.ggml.bos_token_id", "u32", 1), ("tokenizer.ggml.eos_token_id", "u32", 2)]
@@ -382,7 +409,7 @@ def write_gguf(model: RawModel, path: str, version: int = 3, alignment: int = 32
 
 
 def load_gguf_hip(path: str, device):
-    """(LlamaConfig, LlamaWeights<HipTensor>) of a llama GGUF file through the C++ loader (gguf.hpp)."""
+    """(LlamaConfig, LlamaWeights<HipTensor>) of a llama or qwen2 GGUF file through the C++ loader (gguf.hpp)."""
     import crabml_amd as ca
 
     gf = ca.GGUFFile(path)

@@ -259,6 +259,26 @@ typedef struct crabml_hip_llama_weights { /* crabml-llama2/src/model.rs:55-84; p
 } crabml_hip_llama_weights_t;
 int crabml_hip_llama_create(crabml_hip_device_t* dev, const crabml_hip_llama_config_t* cfg,
                             const crabml_hip_llama_weights_t* w, crabml_hip_llama_t** out);
+/* The model architectures of crabml-llama2 (model.rs:22-27). */
+typedef enum crabml_hip_model_arch {
+  CRABML_HIP_ARCH_LLAMA = 0,
+  CRABML_HIP_ARCH_GEMMA = 1,
+  CRABML_HIP_ARCH_QWEN2 = 2,
+  CRABML_HIP_ARCH_PHI2 = 3
+} crabml_hip_model_arch;
+typedef struct crabml_hip_llama_arch {
+  uint32_t architecture;             /* crabml_hip_model_arch */
+  const crabml_hip_buf_t* const* bq; /* Qwen2: n_layers x (dim) F32, q = wq x + bq (llama2.rs:315) */
+  const crabml_hip_buf_t* const* bk; /* n_layers x (kv_dim) F32 (llama2.rs:316) */
+  const crabml_hip_buf_t* const* bv; /* n_layers x (kv_dim) F32 (llama2.rs:317) */
+} crabml_hip_llama_arch_t;
+/* crabml_hip_llama_create for Llama2Runner::forward_qwen2 (llama2.rs:283-351): forward_llama with the q / k / v biases added to the
+ * GEMV outputs and NEOX rope (rope.rs:65-80).  arch == NULL, or LLAMA with NULL biases, is crabml_hip_llama_create.  The other calls
+ * (forward, decode_greedy, decode_sample, prefill, reset, destroy) serve the context unchanged; the biases are retained like the
+ * weights.  CRABML_HIP_NOT_IMPLEMENTED: GEMMA, PHI2, QWEN2 with tp_size > 1.  CRABML_HIP_BAD_INPUT: an unknown architecture, a
+ * missing bias, one that is not F32 or not of its row count, biases on a LLAMA model. */
+int crabml_hip_llama_create_arch(crabml_hip_device_t* dev, const crabml_hip_llama_config_t* cfg, const crabml_hip_llama_weights_t* w,
+                                 const crabml_hip_llama_arch_t* arch, crabml_hip_llama_t** out);
 int crabml_hip_llama_destroy(crabml_hip_llama_t* ctx);
 /* Llama2Runner::forward(&[token], pos): pos must equal the current KV length.  If logits != NULL the
  * vocab_size f32 logits are copied out (BLOCKS); otherwise the call only enqueues. */

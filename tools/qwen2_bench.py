@@ -1,0 +1,94 @@
+"""Qwen2 on the fused decode step against the per-op trait path and Llama-3-8B, in one process.
+Usage: python tools/qwen2_bench.py [--runs qwen2.5-7b:Q4_0,qwen2.5-7b:Q4_K_M,llama3-8b:Q4_0,qwen2.5-3b:Q4_0]
+Per SHAPE:FORMAT (synthetic weights, f16 KV cache), one markdown table row:
+  fused      crabml_hip_llama_decode_greedy tok/s over positions 0..127 (best of 3)
+  @1024      the same over positions 1024..1087, after a 1024-token prefill
+  unchanged  Llama2Runner<HipTensor>::forward + host arg-max per token (the recorded calls served by the fused step), 64 tokens
+  per-op     the same runner on a CRABML_HIP_FLAG_PER_OP device (one launch per Tensor call), 16 tokens
+  strict     decode_greedy on the strict-order device, positions 0..63
+  prompt     prefill tok/s of 512 rows
+  GB         weight bytes one decode step streams"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import crabml_amd as ca  # noqa: E402
+from crabml_amd import synth  # noqa: E402
+
+
+def timed(fn, n):
+    t0 = time.perf_counter()
+    fn()
+    return n / (time.perf_counter() - t0)
+
+
+def runner_rate(model, mode, strict, n):
+    dev = ca.HipTensorDevice(0, False, 0, strict, mode)
+    conf, w = synth.to_hip(model, dev)
+    r = ca.Llama2Runner(conf, w, dev, n + 8, True)
+
+    def loop(p0, k):
+        tok = 1
+        for i in range(k):
+            tok = int(ca.sample_argmax(np.asarray(r.forward([tok], p0 + i))))
+
+    loop(0, 4)  # warm-up (the unchanged runner learns its decode context from the first token)
+    return timed(lambda: loop(4, n), n)
+
+
+def row(spec, steps=128):
+    shape, fmt = spec.split(":")
+    mix = fmt == "Q4_K_M"
+    model = synth.build_model(synth.SHAPES[shape], synth.Q4_K if mix else synth.TYPE_BY_NAME[fmt], seed=1, k_m_mix=mix)
+    gb = model.gemv_weight_bytes_per_token() / 1e9
+    out = {"GB": gb}
+    dev = ca.HipTensorDevice(0)
+    conf, w = synth.to_hip(model, dev)
+    r = ca.HipLlamaRunner(conf, w, dev, 1024 + steps + 16, True)
+    r.decode_greedy(1, 8)
+    best = 0.0
+    for _ in range(3):
+        r.reset()
+        best = max(best, timed(lambda: r.decode_greedy(1, steps), steps))
+    out["fused"] = best
+    prompt = [(11 * i + 5) % conf.vocab_size for i in range(1024)]
+    r.reset()
+    r.prefill(prompt[:512])
+    r.reset()
+    out["prompt"] = timed(lambda: r.prefill(prompt[:512]), 512)
+    r.reset()
+    r.prefill(prompt)
+    out["@1024"] = timed(lambda: r.decode_greedy(1, 64), 64)
+    del r, w
+    out["unchanged"] = runner_rate(model, "lazy", False, 64)
+    out["per-op"] = runner_rate(model, "per-op", False, 16)
+    sdev = ca.HipTensorDevice(0, False, 0, True)
+    sconf, sw = synth.to_hip(model, sdev)
+    s = ca.HipLlamaRunner(sconf, sw, sdev, 80, True)
+    s.decode_greedy(1, 8)
+    s.reset()
+    out["strict"] = timed(lambda: s.decode_greedy(1, 64), 64)
+    return shape, fmt, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", default="qwen2.5-7b:Q4_0,qwen2.5-7b:Q4_K_M,llama3-8b:Q4_0,qwen2.5-3b:Q4_0")
+    a = ap.parse_args()
+    cols = ["fused", "@1024", "unchanged", "per-op", "strict", "prompt"]
+    print("| shape | format | GB / token | " + " | ".join(cols) + " | fused / per-op |")
+    print("|---|---|---|" + "---|" * len(cols) + "---|")
+    for spec in a.runs.split(","):
+        shape, fmt, o = row(spec)
+        print("| %s | %s | %.2f | " % (shape, fmt, o["GB"]) + " | ".join("%.1f" % o[c] for c in cols) +
+              " | %.2fx |" % (o["fused"] / o["per-op"]), flush=True)
+
+
+if __name__ == "__main__":
+    main()
