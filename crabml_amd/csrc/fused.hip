@@ -211,6 +211,13 @@ struct crabml_hip_llama {
   int* h_state = nullptr;
   unsigned h_state_next = 0;
   static constexpr unsigned H_STATE_SLOTS = 256;
+  // crabml_hip_llama_debug_tap (test hook, crabml_hip_debug.h): while tap_layer >= 0 the eager enqueue of enqueue_segment_t puts
+  // device-to-device copies of that layer's buffers between its launches (tap_copy); nothing is allocated before the first tap
+  int tap_layer = -1;
+  char* tap_buf = nullptr;
+  size_t tap_cap = 0, tap_used = 0;
+  size_t tap_off[CRABML_HIP_TAP_FIELDS] = {}, tap_len[CRABML_HIP_TAP_FIELDS] = {};
+  int32_t tap_plan[CRABML_HIP_TAP_PLAN_WORDS] = {};  // the launch plan of the tapped layer, noted where the enqueue code decides
 };
 
 // ---- lazy.hip's context: token / position / serial of a step straight from kernel arguments (a launch on the stream's own queue:
@@ -292,6 +299,19 @@ typename ActOf<FMT>::type act_view(const ActPtrs& a) {
 }
 
 int n_segments(const crabml_hip_llama* c) { return 2 * (int)c->cfg.n_layers + 1; }
+
+// the tap (crabml_hip_llama_debug_tap): field `f` = `bytes` bytes at `src` as the stream finds them here
+int tap_copy(crabml_hip_llama* c, int f, const void* src, size_t bytes) {
+  if (c->tap_layer < 0 || src == nullptr || bytes == 0) return 0;
+  if (c->capturing) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: a tapped step is never captured");
+  const size_t off = align_up(c->tap_used, 256);
+  if (f < 0 || f >= CRABML_HIP_TAP_FIELDS || off + bytes > c->tap_cap) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: scratch area too small");
+  CH_HIP(c->dev, hipMemcpyAsync(c->tap_buf + off, src, bytes, hipMemcpyDeviceToDevice, c->dev->stream));
+  c->tap_off[f] = off;
+  c->tap_len[f] = bytes;
+  c->tap_used = off + bytes;
+  return 0;
+}
 
 // attention of layer l (llama2.rs:571-590): qbuf x KV cache -> attn (f32), plus its Q8_0 planes for wo when xq != NULL.
 // Emits the variant selected in c->attn_variant (0: one workgroup per head, 1: the long-context kernels).
@@ -560,6 +580,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       NormGather ng{c->slots, c->slots + dim / 16, c->state + 4, c->state + 5, n_segments(c), seg, c->rsums};
       // long rows (ffn_down): two workgroups per chunk, so that every CU streams (a CU sustains ~26 GB/s here)
       const int split = split_of(k);
+      if (c->tap_layer == seg / 2) c->tap_plan[stage == 2 ? CRABML_HIP_PLAN_SPLIT_WO : CRABML_HIP_PLAN_SPLIT_DOWN] = split;
       const TpP2P tpv = tp_view(c, tp);
       if (xin != nullptr && !Q81) {  // (tensor-parallel ranks) the rhs arrives as f32 -- h from k_gateup_h -- and is quantized in the prologue
         if constexpr (!Q81) {
@@ -637,6 +658,9 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     return 0;
   };
 
+  // the tap (test hook): host-side copies between the launches of the tapped layer; a no-op unless a tapped step is being enqueued
+  const size_t ad_bytes = act_layout(qt, (size_t)dim).total, rs_bytes = c->rsums ? (size_t)(dim / 32) * 4 : 0;
+  auto TAP = [&](bool on, int f, const void* src, size_t bytes) -> int { return on && c->tap_layer >= 0 ? tap_copy(c, f, src, bytes) : 0; };
   if (seg == 2 * L) {  // final rmsnorm + classifier (llama2.rs:274-278, 199-208) + greedy sampler
     const void* cls_act = c->act_dim;
     if (c->out_qt != qt) {
@@ -655,7 +679,9 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       }
     } else if (!norm_epi) {
       norm_quant((const float*)c->rms_final->ptr, g.rms_norm_eps, tp, plan(nullptr, nullptr, nullptr));
+      CH_TRY(TAP(c->tap_layer == L - 1, CRABML_HIP_TAP_DOWN_ACT, c->act_dim, ad_bytes));
     }
+    CH_TRY(TAP(true, CRABML_HIP_TAP_CLS_ACT, cls_act, c->out_qt == CRABML_HIP_F32 ? (size_t)dim * 4 : act_layout(c->out_qt, (size_t)dim).total));
     if (prof)
       CH_TRY(prof_begin(dev, &pr, c->output->dtype, 5,
                         (double)c->vocab_l * (double)(dim / block_elems(c->output->dtype)) * (double)block_bytes(c->output->dtype) +
@@ -672,6 +698,12 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     // attention rmsnorm (llama2.rs:230-234)
     if (!norm_epi || l == 0)
       norm_quant((const float*)c->rms_att[l]->ptr, g.rms_norm_eps, tp && l > 0, plan(c->wq[l], c->wk[l], c->wv[l]));
+    const bool tl = c->tap_layer == l;
+    if (tl && (!norm_epi || l == 0)) c->tap_plan[CRABML_HIP_PLAN_NORM_NIT] = dim <= 4096 ? 4 : 12;
+    CH_TRY(TAP(!norm_epi && l > 0 && c->tap_layer == l - 1, CRABML_HIP_TAP_DOWN_ACT, c->act_dim, ad_bytes));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_X, c->x, (size_t)dim * 4));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_ACT, c->act_dim, ad_bytes));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_RSUMS, c->rsums, rs_bytes));
     // q, k, v + rope + scale + KV append (llama2.rs:244-256, 542-554, 561-565), local heads only
     QkvEpi e{c->qbuf, c->kc[l], c->vc[l], c->rope, pos_d, 1.0f / std::sqrt((float)hd), dim_l, kv_dim_l, hd,
              (int)g.rope_dim, c->npairs, seq_cap, kv16 ? 1 : 0};
@@ -679,6 +711,12 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     CH_TRY(P0(&pr, 1, total_rows, dim));
     // (the planes of layer l > 0 come from the previous layer's ffn_down launch, with its dim / 32 chunk sums)
     const RmsTail rtq{c->rsums, dim / 32, 1.0f / (float)dim, g.rms_norm_eps};
+    if (c->tap_layer == l && !c->ord) {  // (the predicates of k_qkv's own choice, on the arguments of the launch below)
+      const int nu = dim / 32 * BlockFmt<FMT>::UNITS;
+      const bool deferq = defer_down && l > 0 && !Q81;
+      const int upfront = deferq ? qkv_upfront : ((qkv_upfront && total_rows / 2 <= 4 * dev->n_cu) ? 1 : 0);
+      c->tap_plan[CRABML_HIP_PLAN_QKV_LOADER] = deferq ? (upfront && nu == 128 ? 4 : 3) : (upfront && nu % 128 == 0 ? 2 : 1);
+    }
     auto qkv = [&](auto ep) {
       constexpr int A = QkvArchOf<decltype(ep)>::value;
       if (c->ord)
@@ -699,16 +737,23 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     else
       qkv(e);
     CH_TRY(P1(&pr));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_QBUF, c->qbuf, (size_t)dim_l * 4));
     // attention (llama2.rs:571-590) -> attn (f32) [+ Q8_0 planes for wo]; spare CUs prefetch wo
     const bool attn_quant = (hd % 32) == 0;
     const int attn_spare = do_pf && dev->n_cu > n_heads_l ? dev->n_cu - n_heads_l : 0;
     enqueue_attention(c, l, attn_quant ? aa.q : (signed char*)nullptr, aa.d, aa.isum, plan(c->wo[l], nullptr, nullptr), attn_spare, prof);
     if (!attn_quant) launch_quantize_act(st, qt, c->attn, (size_t)dim_l, c->act_attn);
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_ATTN, c->attn, (size_t)dim_l * 4));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_ACT_ATTN, c->act_attn, act_layout(qt, (size_t)dim_l).total));
     // wo (+ residual, llama2.rs:600, 266): k = the local heads' slice
     CH_TRY(gemv_out(c->wo[l], aa, dim_l, 2, (const float*)c->rms_ffn[l]->ptr, 1e-5f, defer_wo));
   } else {
     // ffn rmsnorm, eps = the literal 1e-5 (llama2.rs:611)
     if (!norm_epi) norm_quant((const float*)c->rms_ffn[l]->ptr, 1e-5f, tp, plan(nullptr, nullptr, nullptr));
+    const bool tl = c->tap_layer == l;
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_WO_X, c->x, (size_t)dim * 4));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_WO_ACT, c->act_dim, ad_bytes));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_WO_RSUMS, c->rsums, rs_bytes));
     const float* wnext_down = (const float*)(l + 1 < L ? c->rms_att[l + 1] : c->rms_final)->ptr;
     // gate / up + silu * mul (llama2.rs:620-630), local rows
     CH_TRY(P0(&pr, 3, 2.0 * hidden_l, dim));
@@ -729,8 +774,12 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       launch_k(st, R, k_gateup_q<FMT>, dim3(hidden_l / 32), dim3(1024), 0, planes_of(c->gate[l]), planes_of(c->up[l]),
                act_view<FMT>(ad), dev->exp_table, ah.q, ah.d, ah.isum, dim / 32, rt);
     CH_TRY(P1(&pr));
+    CH_TRY(TAP(tl && !hq, CRABML_HIP_TAP_ACT_HID, c->act_hid, act_layout(qt, (size_t)hidden_l).total));
     // down (+ residual, llama2.rs:633-636): k = the local hidden slice
     CH_TRY(gemv_out(c->down[l], ah, hidden_l, 4, wnext_down, g.rms_norm_eps, defer_down && l + 1 < L, hq ? c->h : nullptr));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_DOWN_X, c->x, (size_t)dim * 4));
+    CH_TRY(TAP(tl && norm_epi, CRABML_HIP_TAP_DOWN_ACT, c->act_dim, ad_bytes));
+    CH_TRY(TAP(tl && norm_epi, CRABML_HIP_TAP_DOWN_RSUMS, c->rsums, rs_bytes));
   }
   CH_HIP(dev, hipGetLastError());
   return 0;
@@ -2606,6 +2655,110 @@ int crabml_hip_llama_debug_kv(crabml_hip_llama_t* c, size_t layer, int32_t which
   if (layer >= c->cfg.n_layers || nbytes > c->kv_bytes) CH_BAIL(c->dev, CRABML_HIP_BAD_INPUT, "llama debug_kv: bad layer/size");
   CH_HIP(c->dev, hipMemcpyAsync(dst, which_v ? c->vc[layer] : c->kc[layer], nbytes, hipMemcpyDeviceToHost, c->dev->stream));
   CH_HIP(c->dev, hipStreamSynchronize(c->dev->stream));
+  return 0;
+}
+
+// parity hook (crabml_hip_debug.h): one eager decode step with the buffers of one layer copied out between its launches
+int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, size_t layer, float* logits, void* dst, size_t dst_bytes,
+                               crabml_hip_tap_entry_t* dir, size_t* need) {
+  if (!c || (dst && !dir) || (!dst && !need)) return CRABML_HIP_BAD_INPUT;
+  crabml_hip_device* dev = c->dev;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  if (c->tp > 1 || c->kfused || c->generic || c->ord || dev->strict_order || c->ext_kv ||
+      !(c->wtype == CRABML_HIP_Q4_0 || c->wtype == CRABML_HIP_Q8_0 || c->wtype == CRABML_HIP_Q4_1))
+    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama debug_tap: only the five-launch Q4_0 / Q8_0 / Q4_1 layers of the fast step on one device");
+  if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
+  const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim;
+  // the row type and the element count of every field (0 elements = f32 of `bytes`)
+  const uint32_t qt = c->qt, cq = c->out_qt;
+  struct Fld {
+    uint32_t qtype;
+    size_t n;
+  };
+  Fld fld[CRABML_HIP_TAP_FIELDS];
+  for (auto& f : fld) f = Fld{CRABML_HIP_F32, 0};
+  fld[CRABML_HIP_TAP_QKV_IN_ACT] = fld[CRABML_HIP_TAP_WO_ACT] = fld[CRABML_HIP_TAP_DOWN_ACT] = fld[CRABML_HIP_TAP_ACT_ATTN] = Fld{qt, dim};
+  fld[CRABML_HIP_TAP_ACT_HID] = Fld{qt, hidden};
+  if (cq == CRABML_HIP_Q8_0 || cq == CRABML_HIP_Q8_1 || cq == CRABML_HIP_Q8_K) fld[CRABML_HIP_TAP_CLS_ACT] = Fld{cq, dim};
+  const size_t cls_raw = fld[CRABML_HIP_TAP_CLS_ACT].n ? act_layout(cq, dim).total : dim * 4;
+  // the scratch area, in the device's plane layout: four x, four sets of act_dim planes, three rsums, qbuf, attn, act_attn, act_hid
+  const size_t adb = act_layout(qt, dim).total, ahb = act_layout(qt, hidden).total;
+  const size_t raw_cap = 6 * align_up(dim * 4, 256) + 4 * adb + 3 * align_up(dim / 32 * 4, 256) + ahb + align_up(cls_raw, 256) + 512;
+  // what the host receives: the same fields with the planes re-packed as blocks (never larger than the planes)
+  if (need) *need = raw_cap;
+  if (!dst) return 0;
+  if (dst_bytes < raw_cap) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: dst holds %zu bytes, %zu needed", dst_bytes, raw_cap);
+  CH_TRY(check_step(c, token, pos));
+  if (!c->tap_buf) {
+    CH_TRY(dalloc(c, raw_cap, (void**)&c->tap_buf));
+    c->tap_cap = raw_cap;
+  }
+  c->tap_used = 0;
+  for (int f = 0; f < CRABML_HIP_TAP_FIELDS; f++) c->tap_off[f] = c->tap_len[f] = 0;
+  CH_TRY(set_state(c, token, pos, 0));
+  // the eager step (run_step without the graph replay)
+  c->attn_variant = variant_of(c, pos);
+  for (auto& v : c->tap_plan) v = 0;
+  c->tap_plan[CRABML_HIP_PLAN_N_CU] = dev->n_cu;
+  c->tap_plan[CRABML_HIP_PLAN_DEFER_NORM] = c->defer_norm ? 1 : 0;
+  c->tap_plan[CRABML_HIP_PLAN_NORM_EPILOGUE] = c->norm_epi ? 1 : 0;
+  c->tap_plan[CRABML_HIP_PLAN_ATTN_VARIANT] = c->attn_variant + (c->attn_variant >= 1 && c->attn_flash ? 16 : 0);
+  c->tap_layer = (int)layer;
+  const int rc = enqueue_step(c);
+  c->tap_layer = -1;
+  if (rc != 0) return rc;
+  c->kv_len++;
+  std::vector<uint8_t> h(c->tap_used ? c->tap_used : 1);
+  int fault = 0;
+  if (logits) CH_HIP(dev, hipMemcpyAsync(logits, c->logits, c->cfg.vocab_size * 4, hipMemcpyDeviceToHost, dev->stream));
+  CH_HIP(dev, hipMemcpyAsync(&fault, c->state + 5, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
+  if (c->tap_used) CH_HIP(dev, hipMemcpyAsync(h.data(), c->tap_buf, c->tap_used, hipMemcpyDeviceToHost, dev->stream));
+  CH_HIP(dev, hipStreamSynchronize(dev->stream));
+  if (fault) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a norm-epilogue gather timed out (workgroups not co-resident?)");
+  uint8_t* o = (uint8_t*)dst;
+  size_t at = 0;
+  for (int f = 0; f < CRABML_HIP_TAP_FIELDS; f++) {
+    dir[f] = crabml_hip_tap_entry_t{at, 0, fld[f].qtype, 0};
+    if (f == CRABML_HIP_TAP_PLAN) {  // host words, not a device buffer
+      if (at + sizeof c->tap_plan > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: the plan does not fit dst");
+      memcpy(o + at, c->tap_plan, sizeof c->tap_plan);
+      dir[f].bytes = sizeof c->tap_plan;
+      at += align_up(sizeof c->tap_plan, 8);
+      continue;
+    }
+    if (c->tap_len[f] == 0) continue;
+    const uint8_t* src = h.data() + c->tap_off[f];
+    size_t out_bytes = c->tap_len[f];
+    if (fld[f].n == 0) {
+      if (at + out_bytes > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: field %d does not fit dst", f);
+      memcpy(o + at, src, out_bytes);
+    } else {  // planes -> blocks, as crabml_hip_debug_quantize lays them out
+      const uint32_t t = fld[f].qtype;
+      const size_t n = f == CRABML_HIP_TAP_ACT_HID ? hidden : dim, nb = n / block_elems(t);
+      const ActLayout al = act_layout(t, n);
+      out_bytes = nb * block_bytes(t);
+      if (c->tap_len[f] != al.total || at + out_bytes > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: field %d has an unexpected size", f);
+      uint8_t* b = o + at;
+      for (size_t i = 0; i < nb; i++) {
+        if (t == CRABML_HIP_Q8_0) {
+          memcpy(b + i * 34, src + al.off_d + i * 2, 2);
+          memcpy(b + i * 34 + 2, src + i * 32, 32);
+        } else if (t == CRABML_HIP_Q8_1) {
+          memcpy(b + i * 36, src + al.off_d + i * 2, 2);
+          memcpy(b + i * 36 + 2, src + al.off_aux + i * 2, 2);
+          memcpy(b + i * 36 + 4, src + i * 32, 32);
+        } else {
+          memcpy(b + i * 292, src + al.off_d + i * 4, 4);
+          memcpy(b + i * 292 + 4, src + i * 256, 256);
+          memcpy(b + i * 292 + 260, src + al.off_aux + i * 32, 32);
+        }
+      }
+    }
+    dir[f].bytes = out_bytes;
+    at += align_up(out_bytes, 8);
+  }
   return 0;
 }
 

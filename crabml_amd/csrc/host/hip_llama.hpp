@@ -169,6 +169,27 @@ class HipLlamaRunner {
     device_->check(crabml_hip_llama_debug_kv(ctx_, layer, v ? 1 : 0, out.data(), n));
     return out;
   }
+  // crabml_hip_llama_debug_tap: one eager step with layer `layer` tapped; the logits, and per field (CRABML_HIP_TAP_*) its row type
+  // and bytes (f32 values, or blocks in the reference's layout)
+  struct Tap {
+    std::vector<float> logits;
+    std::vector<uint32_t> qtype;
+    std::vector<std::vector<uint8_t>> field;
+  };
+  Tap debug_tap(size_t token, size_t pos, size_t layer) {
+    size_t need = 0;
+    device_->check(crabml_hip_llama_debug_tap(ctx_, token, pos, layer, nullptr, nullptr, 0, nullptr, &need));
+    std::vector<uint8_t> buf(need);
+    crabml_hip_tap_entry_t dir[CRABML_HIP_TAP_FIELDS];
+    Tap t;
+    t.logits.resize(conf_.vocab_size);
+    device_->check(crabml_hip_llama_debug_tap(ctx_, token, pos, layer, t.logits.data(), buf.data(), buf.size(), dir, nullptr));
+    for (int f = 0; f < CRABML_HIP_TAP_FIELDS; f++) {
+      t.qtype.push_back(dir[f].qtype);
+      t.field.emplace_back(buf.begin() + dir[f].offset, buf.begin() + dir[f].offset + dir[f].bytes);
+    }
+    return t;
+  }
   // one decode step of a single-device simulated tp group (crabml_hip_llama_tp_sim_forward); logits from rank 0
   static std::vector<float> tp_sim_forward(const std::vector<HipLlamaRunner*>& ranks, size_t token, size_t pos) {
     if (ranks.empty()) throw Error(ErrorKind::BadInput, "tp_sim_forward: no ranks");

@@ -520,6 +520,36 @@ PYBIND11_MODULE(_host, m) {
       .def("debug_kv", [](HipLlamaRunner& r, size_t layer, bool v, bool f16) {
         std::vector<uint8_t> b = r.debug_kv(layer, v, f16);
         return py::array_t<uint8_t>(b.size(), b.data());
+      })
+      // one eager step with `layer` tapped (crabml_hip_llama_debug_tap): {"logits": f32, name: f32 array | uint8 blocks, "qtype": {name: type}}
+      .def("debug_tap", [](HipLlamaRunner& r, size_t token, size_t pos, size_t layer) {
+        static const char* names[CRABML_HIP_TAP_FIELDS] = {"qkv_in.x", "qkv_in.act_dim", "qkv_in.rsums", "qkv.qbuf", "attn.attn", "attn.act_attn", "wo.x",
+                                                           "wo.act_dim", "wo.rsums", "gateup.act_hid", "down.x", "down.act_dim", "down.rsums", "cls.act", "plan"};
+        HipLlamaRunner::Tap t;
+        {
+          py::gil_scoped_release rel;
+          t = r.debug_tap(token, pos, layer);
+        }
+        py::dict d, qt;
+        d["logits"] = py::array_t<float>(t.logits.size(), t.logits.data());
+        for (int f = 0; f < CRABML_HIP_TAP_FIELDS; f++) {
+          const auto& b = t.field[f];
+          if (b.empty()) continue;
+          if (f == CRABML_HIP_TAP_PLAN) {  // {word name: value}
+            static const char* words[CRABML_HIP_TAP_PLAN_WORDS] = {"n_cu", "defer_norm", "norm_epilogue", "attn_variant", "split_wo", "split_down", "qkv_loader", "norm_nit"};
+            py::dict p;
+            for (int i = 0; i < CRABML_HIP_TAP_PLAN_WORDS; i++) p[words[i]] = ((const int32_t*)b.data())[i];
+            d[names[f]] = p;
+            continue;
+          }
+          if (t.qtype[f] == CRABML_HIP_F32)
+            d[names[f]] = py::array_t<float>(b.size() / 4, (const float*)b.data());
+          else
+            d[names[f]] = py::array_t<uint8_t>(b.size(), b.data());
+          qt[names[f]] = t.qtype[f];
+        }
+        d["qtype"] = qt;
+        return d;
       });
 
   py::class_<Runner>(m, "Llama2Runner")

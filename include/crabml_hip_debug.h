@@ -138,6 +138,58 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
 /* parity hook: copies the layer's K or V cache (raw f16/f32 bytes, [n_kv_heads][seq_len][head_dim]) */
 int crabml_hip_llama_debug_kv(crabml_hip_llama_t* ctx, size_t layer, int32_t which_v, void* dst, size_t nbytes);
 
+/* parity hook: ONE decode step for (token, pos) -- the same checks and the same effect on the context as
+ * crabml_hip_llama_forward -- enqueued EAGERLY (never replayed from the step's hipGraph, never while capturing), with the buffers
+ * of layer `layer` copied out as each launch of that layer left them: stream-ordered device-to-device copies into a scratch area
+ * (allocated on the first tap of a context) placed between the launches, brought to the host after the step.  The step runs to
+ * its end as always; logits (vocab_size floats, nullable) come back as from forward.  Serves the five-launch layers of
+ * enqueue_segment_t (Q4_0 / Q8_0 / Q4_1 on one device, fast tier); tensor-parallel ranks, the K-quant path, the per-op path, the
+ * strict-order device and a context the recorded-op queue drives on the runner's own KV cache return CRABML_HIP_NOT_IMPLEMENTED.
+ * dst / dir: field f occupies dir[f].bytes bytes at dst + dir[f].offset (bytes = 0: the context has no such buffer, e.g. rsums
+ * outside the hop-free form).  f32 fields are raw floats.  Quantized rows come back in the reference's block byte layout, as
+ * crabml_hip_debug_quantize returns them: Q8_0 block i = d plane [i] (f16) | q plane [32 i .. 32 i + 31]; Q8_1 = d plane [i] |
+ * third plane [i] (s, f16) | q plane; Q8_K = d plane [i] (f32) | q plane [256 i ..] | bsums plane [16 i ..] -- the Q8_0 layout's
+ * third plane (the blocks' integer sums, a kernel-side convenience) is not part of a block and is left out.
+ * dst == NULL: nothing runs, *need receives the bytes dst must hold. */
+enum {
+  CRABML_HIP_TAP_QKV_IN_X = 0,      /* what the q|k|v launch of the layer reads: x (f32, dim), */
+  CRABML_HIP_TAP_QKV_IN_ACT = 1,    /*   the act_dim planes (layer row type), */
+  CRABML_HIP_TAP_QKV_IN_RSUMS = 2,  /*   rsums (f32, dim / 32 chunk sums of squares; stale bytes in front of layer 0) */
+  CRABML_HIP_TAP_QBUF = 3,          /* after q|k|v: qbuf (f32, dim); the K / V rows at pos: crabml_hip_llama_debug_kv */
+  CRABML_HIP_TAP_ATTN = 4,          /* after attention (and the stand-alone quantizer, head_dim % 32 != 0): attn (f32, dim), */
+  CRABML_HIP_TAP_ACT_ATTN = 5,      /*   the act_attn planes */
+  CRABML_HIP_TAP_WO_X = 6,          /* what the gate|up launch reads, i.e. after wo (and the norm launch, NO_NORM_EPILOGUE): x, */
+  CRABML_HIP_TAP_WO_ACT = 7,        /*   the act_dim planes, */
+  CRABML_HIP_TAP_WO_RSUMS = 8,      /*   rsums */
+  CRABML_HIP_TAP_ACT_HID = 9,       /* after gate|up: the act_hid planes (hidden) */
+  CRABML_HIP_TAP_DOWN_X = 10,       /* after ffn_down: x, */
+  CRABML_HIP_TAP_DOWN_ACT = 11,     /*   the act_dim planes (NO_NORM_EPILOGUE: after the norm launch of the next segment; 0 bytes when
+                                         that launch writes another row type, i.e. in front of a classifier of its own format), */
+  CRABML_HIP_TAP_DOWN_RSUMS = 12,   /*   rsums */
+  CRABML_HIP_TAP_CLS_ACT = 13,      /* last segment, any `layer`: what the classifier reads (the classifier's row type; f32 for an F32 / F16 classifier) */
+  CRABML_HIP_TAP_PLAN = 14,         /* CRABML_HIP_TAP_PLAN_WORDS int32 words: the launch plan of the tapped step as the host took it (below) */
+  CRABML_HIP_TAP_FIELDS = 15
+};
+/* the words of CRABML_HIP_TAP_PLAN, written by the enqueue code where it decides (0 where the tapped layer never got there) */
+enum {
+  CRABML_HIP_PLAN_N_CU = 0,         /* compute units of the device (what dim / 32 and split_of() are compared with) */
+  CRABML_HIP_PLAN_DEFER_NORM = 1,   /* 1: the context runs the hop-free norm */
+  CRABML_HIP_PLAN_NORM_EPILOGUE = 2,/* 1: RMSNorm + quantize run in the wo / ffn_down epilogue */
+  CRABML_HIP_PLAN_ATTN_VARIANT = 3, /* 0 one workgroup per head, 1 the long-context kernels, 2 the same with the merge in the launch; + 16 when those are k_attn_flash */
+  CRABML_HIP_PLAN_SPLIT_WO = 4,     /* workgroups per 32-row chunk of the layer's wo launch (split_of(k)), 0 without the norm epilogue */
+  CRABML_HIP_PLAN_SPLIT_DOWN = 5,   /* ... of its ffn_down launch */
+  CRABML_HIP_PLAN_QKV_LOADER = 6,   /* the row loader k_qkv takes: 1 rows_dot, 2 rows_partial_2step, 3 rows_partial_rms, 4 rows_partial_rms_128 */
+  CRABML_HIP_PLAN_NORM_NIT = 7,     /* template argument of the layer's own norm launch in front of q|k|v (4, or 12 for rows past 4096), 0 = none */
+  CRABML_HIP_TAP_PLAN_WORDS = 8
+};
+typedef struct crabml_hip_tap_entry {
+  uint64_t offset, bytes;
+  uint32_t qtype;     /* CRABML_HIP_F32 or the row type of the blocks */
+  uint32_t reserved;
+} crabml_hip_tap_entry_t;
+int crabml_hip_llama_debug_tap(crabml_hip_llama_t* ctx, size_t token, size_t pos, size_t layer, float* logits, void* dst,
+                               size_t dst_bytes, crabml_hip_tap_entry_t* dir, size_t* need);
+
 /* ---- measurement hook (bench.py `roofline` object) -------------------------------------------------
  * While enabled, every matmul_vec GEMV kernel launch is bracketed by a pair of HIP events recorded on
  * the device's own stream (the stream the kernel runs on); crabml_hip_prof_read() drains them and

@@ -93,27 +93,34 @@ FAST_TOL.update({"FLASH:Q4_0": (8.6e-3, 1.2e-2), "FLASH:Q4_K": (7e-3, 3e-2), "FL
 _OBSERVED = {}
 
 
-def check_fast(key, fmt, err):
-    """records the observed per-step errors under `key` and asserts the format's tolerance"""
+def record_observed(entries, fname="fast_path_errors.json"):
+    """merges `entries` into the JSON file `fname` of observed figures, in the directory the fast-path errors go to (evidence
+    beside the gates, never a gate; a directory that cannot be written is not an error)"""
     import json
     import os
 
-    err = np.asarray(err, dtype=np.float64)
-    _OBSERVED[key] = {"median": float(np.median(err)), "max": float(np.max(err)), "steps": int(err.size)}
     try:
         os.makedirs("gpurun_out", exist_ok=True)
         path = os.path.join("gpurun_out", "fast_path_errors.json")
+        path = os.path.join(os.path.dirname(path), fname)
         prev = {}
         if os.path.exists(path):
             try:
                 prev = json.load(open(path))
             except ValueError:
                 prev = {}
-        prev.update(_OBSERVED)
+        prev.update(entries)
         with open(path, "w") as f:
             json.dump(prev, f, indent=1, sort_keys=True)
     except OSError:
         pass
+
+
+def check_fast(key, fmt, err):
+    """records the observed per-step errors under `key` and asserts the format's tolerance"""
+    err = np.asarray(err, dtype=np.float64)
+    _OBSERVED[key] = {"median": float(np.median(err)), "max": float(np.max(err)), "steps": int(err.size)}
+    record_observed(_OBSERVED)
     med, mx = FAST_TOL[fmt]
     parts = key.split("/")
     if len(parts) > 1 and (parts[1], fmt) in FAST_TOL_MODEL:
