@@ -8,6 +8,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -66,6 +67,15 @@ inline uint32_t vec_dot_rhs_dtype(uint32_t t) {
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// A/B, tuning and test hooks are environment variables that count only when CRABML_HIP_TEST_HOOKS=1 is set as well (a stray variable
+// alone is ignored): the text of hook `name` when it is armed, else null.  The one place that arms them; each reader says what its
+// hook is for.
+inline bool test_hooks_armed() {
+  const char* h = getenv("CRABML_HIP_TEST_HOOKS");
+  return h && h[0] == '1';
+}
+inline const char* test_hook(const char* name) { return test_hooks_armed() ? getenv(name) : nullptr; }
 
 // ---- device-resident layouts -----------------------------------------------------------------
 // Quantized WEIGHTS are re-laid-out once at upload ("planes"): all quants of the tensor first

@@ -17,6 +17,12 @@
 //   k_gateup       ffn_gate/ffn_up matmul_vec + silu_inplace + mul_inplace
 //   k_argmax_step  greedy sampler (last maximum) + token/position advance
 //   k_sample_*     temperature / top-p sampler + advance (sampler.hpp; crabml_hip_llama_decode_sample)
+//
+// Which instantiation a context launches, with which grid and how much LDS, is decided once and read by both llama_create_impl
+// (which checks that the LDS fits and raises the kernels' limits) and the enqueue code: chunk_split (workgroups per chunk of wo /
+// ffn_down), norm_nit, the *_lds_bytes functions beside their kernels, and the *_kernel selectors that hand out the function pointer
+// of every kernel whose limit is raised.  with_const / with_const_else (kernels.hpp) turn a run-time value into the template argument, so a launch's
+// argument list is written once; test_hook (common.hpp) is what arms an A/B or tuning hook.
 #include <chrono>
 #include <thread>
 #include <cmath>
@@ -300,6 +306,65 @@ typename ActOf<FMT>::type act_view(const ActPtrs& a) {
 
 int n_segments(const crabml_hip_llama* c) { return 2 * (int)c->cfg.n_layers + 1; }
 
+// Workgroups per 32-row chunk of a wo / ffn_down launch whose rows are k elements long: two for long rows (ffn_down), so that every
+// CU streams (a CU sustains ~26 GB/s here) -- while the dim / 32 chunks still fit the chip twice.  x_only (the fast Q4_K wo that
+// leaves x alone, k_norm_in): no hop pairs the halves of a chunk, so two 16-row workgroups per chunk whenever that fits.
+// The one place that decides it: the launches, the LDS checks of llama_create_impl and gate | up's sum_parts all ask here
+// (the plan words CRABML_HIP_PLAN_SPLIT_WO / _DOWN of crabml_hip_debug.h record it, under its former name split_of).
+int chunk_split(uint64_t flags, int k, int dim, int n_cu, bool x_only = false) {
+  return (flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_ALWAYS)  ? 2
+         : (flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_NEVER) ? 1
+         : (k / 32 >= 256 && dim / 32 <= n_cu)           ? 2
+         : (x_only && dim / 32 <= n_cu)                  ? 2
+                                                         : 1;
+}
+
+// The norm kernels walk a row with 1024 threads x NIT float4 iterations: rows past 4096 elements take 12 (llama_create_impl stops at
+// 12288).  The one place that knows; CRABML_HIP_PLAN_NORM_NIT records this value.
+int norm_nit(int dim) { return dim <= 4096 ? 4 : 12; }
+void launch_norm_f32(hipStream_t st, float* x, const float* addv, const float* wn, int dim, float eps, float* out, int half) {
+  with_const_else<4, 12>(norm_nit(dim), [&](auto nit) {
+    k_norm_f32<decltype(nit)::value><<<1, 1024, norm_lds_bytes(dim), st>>>(x, addv, wn, dim, eps, out, half);
+  });
+}
+
+// The kernels whose dynamic-LDS limit llama_create_impl raises: create and the launch site take the function pointer from the same
+// selector (as flash_kernel below), so the instantiation that was raised is the one that runs.
+typedef decltype(&k_attn_pv_split<1>) PvSplitFn;
+struct PvSplitKernel {
+  PvSplitFn fn = nullptr;
+  int nsub = 0, threads = 0;
+  size_t lds = 0;
+};
+PvSplitKernel pv_split_kernel(int grp) {
+  PvSplitKernel k;
+  with_const_else<1, 2, 4, 8>(grp, [&](auto g) {
+    typedef PvSplit<decltype(g)::value> P;
+    k = PvSplitKernel{k_attn_pv_split<decltype(g)::value>, P::NSUB, P::THREADS, P::LDS};
+  });
+  return k;
+}
+typedef decltype(&k_attn_s<0>) AttnSFn;
+AttnSFn attn_s_kernel(int hd) { return hd == 128 ? k_attn_s<128> : k_attn_s<0>; }
+typedef decltype(&k_attn_flash_rows<64>) FlashRowsFn;
+FlashRowsFn flash_rows_kernel(int hd) { return hd == 128 ? k_attn_flash_rows<128> : hd == 64 ? k_attn_flash_rows<64> : nullptr; }
+// strict-order Q4_K step: k_gemv_res_nq<Q4_K, SPLIT, QIN, .., ORD> (qin 1 = quantize the f32 rhs, 2 = copy finished planes) ...
+typedef decltype(&k_gemv_res_nq<CRABML_HIP_Q4_K, 1, 1, false, false, true>) NqOrdKFn;
+NqOrdKFn nq_ord_k_kernel(int split, int qin) {
+  NqOrdKFn fn = nullptr;
+  with_const_else<2, 1>(split, [&](auto s) {
+    with_const_else<2, 1>(qin, [&](auto q) { fn = k_gemv_res_nq<CRABML_HIP_Q4_K, decltype(s)::value, decltype(q)::value, false, false, true>; });
+  });
+  return fn;
+}
+// ... and the forms of k_gateup_k_lds<QOUT, ORD, NORMIN> that exist (NORMIN writes planes and has no ordered form)
+typedef decltype(&k_gateup_k_lds<false>) GateupKFn;
+GateupKFn gateup_k_kernel(bool qout, bool ord, bool normin) {
+  if (ord) return qout ? k_gateup_k_lds<true, true> : k_gateup_k_lds<false, true>;
+  if (normin) return k_gateup_k_lds<true, false, true>;
+  return qout ? k_gateup_k_lds<true> : k_gateup_k_lds<false>;
+}
+
 // the tap (crabml_hip_llama_debug_tap): field `f` = `bytes` bytes at `src` as the stream finds them here
 int tap_copy(crabml_hip_llama* c, int f, const void* src, size_t bytes) {
   if (c->tap_layer < 0 || src == nullptr || bytes == 0) return 0;
@@ -329,8 +394,9 @@ void launch_attn_long(crabml_hip_llama* c, int l, signed char* xq, unsigned shor
            (const float*)c->qbuf, (const unsigned short*)c->kc[l], pos_d, c->scores_g, n_kv, hd, seq_cap, nsplit, 0);
   launch_k(st, prof ? &r[1] : nullptr, k_attn_softmax<16>, dim3(c->n_heads_l), dim3(1024), (size_t)seq_cap * sizeof(float),
            (const float*)c->scores_g, pos_d, (const unsigned short*)dev->exp_table, c->p16, seq_cap, 0, dev->strict_order ? 1 : 0);
+  const PvSplitKernel pv = pv_split_kernel(G);
   if (c->pv_split)
-    launch_k(st, prof ? &r[2] : nullptr, k_attn_pv_split<G>, dim3(n_kv * (hd / 32) * PvSplit<G>::NSUB), dim3(PvSplit<G>::THREADS), PvSplit<G>::LDS,
+    launch_k(st, prof ? &r[2] : nullptr, pv.fn, dim3(n_kv * (hd / 32) * pv.nsub), dim3(pv.threads), pv.lds,
              (const unsigned short*)c->p16, (const unsigned short*)c->vc[l], pos_d, c->attn, xq, xd, xisum, hd, seq_cap,
              c->qt == CRABML_HIP_Q8_1 ? 1 : 0, 0);
   else
@@ -385,14 +451,13 @@ void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
   if (prof) prof_begin(dev, &r[1], CRABML_HIP_F32, 8, 0.0);
   crabml_hip_device::ProfRec* R1 = prof ? &r[1] : nullptr;
   const int* pos_d = c->state + 1;
-  if (hd == 128 && q81)
-    launch_k(st, R1, k_attn_flash_merge<128, true>, dim3(c->n_heads_l), dim3(128), 0, (const float*)c->flash_part, pos_d, c->attn, xq, xd, xisum, grp, c->flash_S, c->flash_min_rows);
-  else if (hd == 128)
-    launch_k(st, R1, k_attn_flash_merge<128, false>, dim3(c->n_heads_l), dim3(128), 0, (const float*)c->flash_part, pos_d, c->attn, xq, xd, xisum, grp, c->flash_S, c->flash_min_rows);
-  else if (q81)
-    launch_k(st, R1, k_attn_flash_merge<64, true>, dim3(c->n_heads_l), dim3(64), 0, (const float*)c->flash_part, pos_d, c->attn, xq, xd, xisum, grp, c->flash_S, c->flash_min_rows);
-  else
-    launch_k(st, R1, k_attn_flash_merge<64, false>, dim3(c->n_heads_l), dim3(64), 0, (const float*)c->flash_part, pos_d, c->attn, xq, xd, xisum, grp, c->flash_S, c->flash_min_rows);
+  with_const_else<128, 64>(hd, [&](auto hdc) {  // (flash_kernel has no other head_dim)
+    with_const_else<0, 1>(q81, [&](auto q) {
+      constexpr int HD = decltype(hdc)::value;
+      launch_k(st, R1, k_attn_flash_merge<HD, decltype(q)::value != 0>, dim3(c->n_heads_l), dim3(HD), 0, (const float*)c->flash_part, pos_d,
+               c->attn, xq, xd, xisum, grp, c->flash_S, c->flash_min_rows);
+    });
+  });
   if (prof) prof_end(dev, &r[1]);
 }
 
@@ -406,13 +471,8 @@ void enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
     launch_attn_flash(c, l, xq, xd, xisum, prof);
     return;
   }
-  if (c->attn_variant >= 1) {
-    switch (n_heads / n_kv) {
-      case 1: launch_attn_long<1>(c, l, xq, xd, xisum, prof); break;
-      case 2: launch_attn_long<2>(c, l, xq, xd, xisum, prof); break;
-      case 4: launch_attn_long<4>(c, l, xq, xd, xisum, prof); break;
-      default: launch_attn_long<8>(c, l, xq, xd, xisum, prof); break;
-    }
+  if (c->attn_variant >= 1) {  // (attn_long_ok: the group size is one of these)
+    with_const_else<1, 2, 4, 8>(n_heads / n_kv, [&](auto grp) { launch_attn_long<decltype(grp)::value>(c, l, xq, xd, xisum, prof); });
     return;
   }
   const size_t attn_lds = (size_t)(seq_cap + hd) * sizeof(float);
@@ -420,38 +480,37 @@ void enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
   crabml_hip_device::ProfRec ar{};
   crabml_hip_device::ProfRec* AR = prof ? &ar : nullptr;
   if (prof) prof_begin(dev, &ar, CRABML_HIP_F32, 7, 0.0);
-  if (c->attn_s_rows > 0 && hd == 128)
-    launch_k(st, AR, k_attn_s<128>, dim3(n_heads + spare), dim3(256), c->attn_s_lds, (const float*)c->qbuf, (const unsigned short*)c->kc[l],
+  if (c->attn_s_rows > 0)
+    launch_k(st, AR, attn_s_kernel(hd), dim3(n_heads + spare), dim3(256), c->attn_s_lds, (const float*)c->qbuf, (const unsigned short*)c->kc[l],
              (const unsigned short*)c->vc[l], pos_d, (const unsigned short*)dev->exp_table, c->attn, xq, xd, xisum, n_heads, n_kv, hd, seq_cap,
              c->attn_s_rows, pf, (k8 ? 2 : c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr, k8 ? *k8 : AttnQ8K{});
-  else if (c->attn_s_rows > 0)
-    launch_k(st, AR, k_attn_s<0>, dim3(n_heads + spare), dim3(256), c->attn_s_lds, (const float*)c->qbuf, (const unsigned short*)c->kc[l],
-             (const unsigned short*)c->vc[l], pos_d, (const unsigned short*)dev->exp_table, c->attn, xq, xd, xisum, n_heads, n_kv, hd, seq_cap,
-             c->attn_s_rows, pf, (k8 ? 2 : c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr, k8 ? *k8 : AttnQ8K{});
-  else if (c->cfg.use_f16_kv_cache)
-    launch_k(st, AR, k_attn<true>, dim3(n_heads + spare), dim3(256), attn_lds, (const float*)c->qbuf, (const void*)c->kc[l],
-             (const void*)c->vc[l], pos_d, (const unsigned short*)dev->exp_table, c->attn, xq, xd, xisum, n_heads, n_kv, hd,
-             seq_cap, pf, (c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr);
   else
-    launch_k(st, AR, k_attn<false>, dim3(n_heads + spare), dim3(256), attn_lds, (const float*)c->qbuf, (const void*)c->kc[l],
-             (const void*)c->vc[l], pos_d, (const unsigned short*)dev->exp_table, c->attn, xq, xd, xisum, n_heads, n_kv, hd,
-             seq_cap, pf, (c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr);
+    with_const_else<0, 1>(c->cfg.use_f16_kv_cache != 0, [&](auto kv16) {
+      launch_k(st, AR, k_attn<decltype(kv16)::value != 0>, dim3(n_heads + spare), dim3(256), attn_lds, (const float*)c->qbuf, (const void*)c->kc[l],
+               (const void*)c->vc[l], pos_d, (const unsigned short*)dev->exp_table, c->attn, xq, xd, xisum, n_heads, n_kv, hd,
+               seq_cap, pf, (c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr);
+    });
   if (prof) prof_end(dev, &ar);
 }
 
 // the tail of the final segment: classifier GEMV over this rank's rows (all of them unless the vocabulary is split,
-// llama2.rs:199-208) + greedy sampler + advance
-int enqueue_classifier_and_sampler(crabml_hip_llama* c, const void* cls_act, crabml_hip_device::ProfRec* R) {
+// llama2.rs:199-208) + greedy sampler + advance.  prof: the classifier launch carries an event pair (stage 5)
+int enqueue_classifier_and_sampler(crabml_hip_llama* c, const void* cls_act, bool prof) {
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
   const auto& g = c->cfg;
   const int dim = (int)g.embedding_dim;
   int *token_d = c->state, *pos_d = c->state + 1, *step_d = c->state + 2;
   float* out = c->logits + c->vocab_off;
+  crabml_hip_device::ProfRec pr{};
+  const uint32_t ot = c->output->dtype;
+  if (prof)
+    CH_TRY(prof_begin(dev, &pr, ot, 5, (double)c->vocab_l * (double)(dim / block_elems(ot)) * (double)block_bytes(ot) + 4.0 * dim + 4.0 * c->vocab_l));
   if (dev->strict_order)
     CH_TRY(launch_gemv_strict(dev, c->output, (size_t)c->vocab_l, dim, cls_act, 1, out));
   else
-    CH_TRY(launch_gemv(dev, c->output, (size_t)c->vocab_l, dim, cls_act, 1, out, R));
+    CH_TRY(launch_gemv(dev, c->output, (size_t)c->vocab_l, dim, cls_act, 1, out, prof ? &pr : nullptr));
+  if (prof) CH_TRY(prof_end(dev, &pr));
   if (c->ext_kv) {
     // a context driven by the recorded-op queue (lazy.hip): the HOST samples (Llama2Runner exports the logits and runs its own
     // sampler, llama2.rs:208), token / position / serial of the next step come from the host (lazy_ctx_begin) -- no sampler launch
@@ -499,6 +558,33 @@ template <>
 struct QkvArchOf<QkvEpiB> {
   static constexpr int value = QKV_QWEN2;
 };
+// f(the epilogue arguments of layer l's q|k|v launch): e itself, or Qwen2's; QkvArchOf<decltype(ep)> is the kernels' ARCH
+template <class F>
+void with_qkv_epi(const crabml_hip_llama* c, const QkvEpi& e, int l, F&& f) {
+  if (c->qwen2)
+    f(qwen2_epi(c, e, l));
+  else
+    f(e);
+}
+// what the three segment enqueuers share: the decode step's q|k|v epilogue arguments (rope + scale + KV append, llama2.rs:244-256,
+// 542-554, 561-565; local heads only) and the embedding row in front of layer 0
+QkvEpi decode_qkv_epi(const crabml_hip_llama* c, int l) {
+  return QkvEpi{c->qbuf, c->kc[l], c->vc[l], c->rope, c->state + 1, 1.0f / std::sqrt((float)c->hd), c->dim_l, c->kv_dim_l, c->hd,
+                (int)c->cfg.rope_dim, c->npairs, (int)c->cfg.seq_len, c->cfg.use_f16_kv_cache ? 1 : 0};
+}
+void launch_embed(const crabml_hip_llama* c) {
+  const int dim = (int)c->cfg.embedding_dim;
+  k_embed<<<(dim + 255) / 256, 256, 0, c->dev->stream>>>((const char*)c->token_embed->ptr, (int)c->token_embed->dtype,
+                                                         c->token_embed->wl.off_scale, c->state, dim, c->x);
+}
+
+// the form <QIN, TP, DEFER> of a k_gemv_res_nq launch, as a value: the caller branches between forms, SPLIT is folded at the launch
+template <int QIN, bool TP = false, bool DEFER = false>
+struct NqForm {};
+template <int FMT, int SPLIT, int QIN, bool TP, bool DEFER>
+constexpr auto nq_kernel(NqForm<QIN, TP, DEFER>) {
+  return &k_gemv_res_nq<FMT, SPLIT, QIN, TP, DEFER>;
+}
 
 // enqueue segment `seg` of one decode step on the device stream (see the banner above): the fused kernels
 // (fast mode, Q4_0 / Q8_0 weights)
@@ -507,14 +593,11 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
   const auto& g = c->cfg;
-  const int dim = (int)g.embedding_dim, hd = c->hd, seq_cap = (int)g.seq_len;
+  const int dim = (int)g.embedding_dim, hd = c->hd;
   const int dim_l = c->dim_l, kv_dim_l = c->kv_dim_l, hidden_l = c->hidden_l;
   const int n_heads_l = c->n_heads_l;
-  const bool kv16 = g.use_f16_kv_cache != 0;
   const bool tp = c->tp > 1;
   const int L = (int)g.n_layers;
-  int* token_d = c->state;
-  int* pos_d = c->state + 1;
   constexpr bool Q81 = FMT == CRABML_HIP_Q4_1;
   const uint32_t qt = c->qt;
   ActPtrs ad = act_ptrs(c->act_dim, dim, qt), aa = act_ptrs(c->act_attn, dim_l, qt), ah = act_ptrs(c->act_hid, hidden_l, qt);
@@ -545,27 +628,19 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     crabml_hip_device::ProfRec nr{};
     if (prof) prof_begin(dev, &nr, CRABML_HIP_F32, 6, 8.0 * dim);
     const float* addv = add_pending ? c->partial : nullptr;
-    if (dim <= 4096)
-      launch_k(st, prof ? &nr : nullptr, k_norm_quant<4, Q81>, dim3(1 + spare), dim3(1024), norm_lds, c->x, addv, wn, dim, eps, ad.q, ad.d, ad.isum, pf, c->ord ? 0 : 1);
-    else
-      launch_k(st, prof ? &nr : nullptr, k_norm_quant<12, Q81>, dim3(1 + spare), dim3(1024), norm_lds, c->x, addv, wn, dim, eps, ad.q, ad.d, ad.isum, pf, c->ord ? 0 : 1);
+    with_const_else<4, 12>(norm_nit(dim), [&](auto nit) {
+      launch_k(st, prof ? &nr : nullptr, k_norm_quant<decltype(nit)::value, Q81>, dim3(1 + spare), dim3(1024), norm_lds, c->x, addv, wn, dim, eps, ad.q,
+               ad.d, ad.isum, pf, c->ord ? 0 : 1);
+    });
     if (prof) prof_end(dev, &nr);
   };
   // W(dim x k_local) . act -> x (+= residual) or partial (tp)
   const bool norm_epi = c->norm_epi;
-  // workgroups per 32-row chunk of a wo / ffn_down launch: two for long rows (ffn_down), so that every CU streams
-  auto split_of = [&](int k) {
-    return (g.flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_ALWAYS)  ? 2
-           : (g.flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_NEVER) ? 1
-           : (k / 32 >= 256 && dim / 32 <= dev->n_cu)        ? 2
-                                                             : 1;
-  };
   // q / k / v rows of exactly 128 units: both 64-unit steps requested up front (5.29 -> 4.66 us per launch on the 8B shape,
   // profiles/r06_small_stage_ab.md; bit-identical).  A/B hook: CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_QKV_UPFRONT=0 keeps the two rounds.
   static const int qkv_upfront = [] {
-    const char* h = getenv("CRABML_HIP_TEST_HOOKS");
-    const char* e = getenv("CRABML_HIP_QKV_UPFRONT");
-    return h && h[0] == '1' && e && e[0] == '0' ? 0 : 1;
+    const char* e = test_hook("CRABML_HIP_QKV_UPFRONT");
+    return e && e[0] == '0' ? 0 : 1;
   }();
   // the hop-free norm between wo and gate/up of a layer: decided once, for the producer and the consumer alike
   const bool defer_wo = c->defer_norm && !Q81;
@@ -578,77 +653,46 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     float* dst = tp ? c->partial : c->x;
     if (norm_epi) {
       NormGather ng{c->slots, c->slots + dim / 16, c->state + 4, c->state + 5, n_segments(c), seg, c->rsums};
-      // long rows (ffn_down): two workgroups per chunk, so that every CU streams (a CU sustains ~26 GB/s here)
-      const int split = split_of(k);
+      const int split = chunk_split(g.flags, k, dim, dev->n_cu);
       if (c->tap_layer == seg / 2) c->tap_plan[stage == 2 ? CRABML_HIP_PLAN_SPLIT_WO : CRABML_HIP_PLAN_SPLIT_DOWN] = split;
       const TpP2P tpv = tp_view(c, tp);
+      // one k_gemv_res_nq launch of the given form: `split` workgroups for each of the dim / 32 chunks
+      auto nq = [&](auto form, size_t lds, const float* rhs, auto tparg) {
+        with_const_else<2, 1>(split, [&](auto s) {
+          launch_k(st, R, nq_kernel<FMT, decltype(s)::value>(form), dim3(dim / 32 * split), dim3(1024), lds, planes_of(w), act_view<FMT>(a), rhs, c->x,
+                   wnext, eps_next, ad.q, ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, tparg);
+        });
+      };
       if (xin != nullptr && !Q81) {  // (tensor-parallel ranks) the rhs arrives as f32 -- h from k_gateup_h -- and is quantized in the prologue
         if constexpr (!Q81) {
-          const size_t qlds = q8_0_lds_bytes(k / 32);
-          if (tpv.n > 1 && split == 2)
-            launch_k(st, R, k_gemv_res_nq<FMT, 2, 1, true>, dim3(dim / 16), dim3(1024), qlds, planes_of(w), act_view<FMT>(a), xin, c->x, wnext, eps_next, ad.q,
-                     ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, tpv);
-          else if (tpv.n > 1)
-            launch_k(st, R, k_gemv_res_nq<FMT, 1, 1, true>, dim3(dim / 32), dim3(1024), qlds, planes_of(w), act_view<FMT>(a), xin, c->x, wnext, eps_next, ad.q,
-                     ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, tpv);
-          else if (split == 2)
-            launch_k(st, R, k_gemv_res_nq<FMT, 2, 1>, dim3(dim / 16), dim3(1024), qlds, planes_of(w), act_view<FMT>(a), xin, c->x, wnext, eps_next, ad.q,
-                     ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, NoTp{});
+          if (tpv.n > 1)
+            nq(NqForm<1, true>{}, q8_0_lds_bytes(k / 32), xin, tpv);
           else
-            launch_k(st, R, k_gemv_res_nq<FMT, 1, 1>, dim3(dim / 32), dim3(1024), qlds, planes_of(w), act_view<FMT>(a), xin, c->x, wnext, eps_next, ad.q,
-                     ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, NoTp{});
+            nq(NqForm<1>{}, q8_0_lds_bytes(k / 32), xin, NoTp{});
         }
       } else if (tpv.n > 1) {  // tensor parallel over a P2P group: the collective runs inside this launch
-        if (split == 2)
-          launch_k(st, R, k_gemv_res_nq<FMT, 2, false, true>, dim3(dim / 16), dim3(1024), 0, planes_of(w), act_view<FMT>(a), (const float*)nullptr,
-                   c->x, wnext, eps_next, ad.q, ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, tpv);
-        else
-          launch_k(st, R, k_gemv_res_nq<FMT, 1, false, true>, dim3(dim / 32), dim3(1024), 0, planes_of(w), act_view<FMT>(a), (const float*)nullptr,
-                   c->x, wnext, eps_next, ad.q, ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, tpv);
+        nq(NqForm<0, true>{}, 0, nullptr, tpv);
       } else if (c->ord) {  // strict order: the same launch with block-ordered GEMV sums and the reference's norm order
-        const size_t lds = (size_t)(32 / split) * (((k / 32 + 3) & ~3) + 4) * sizeof(float);
         static const int pipe_mode = [] {  // tuning hook: 0 = never, 1 = ffn_down only, 2 = wo too (-1 / unset: the default below)
-          const char* h = getenv("CRABML_HIP_TEST_HOOKS");
-          const char* e = getenv("CRABML_HIP_ORD_PIPE");
-          return h && h[0] == '1' && e ? atoi(e) : -1;
+          const char* e = test_hook("CRABML_HIP_ORD_PIPE");
+          return e ? atoi(e) : -1;
         }();
         // measured (profiles/r04_strict_order_decode.md): the pipelined chain pays in ffn_down for every format, in wo for Q8_0 only
         const int pipe = pipe_mode >= 0 ? pipe_mode : FMT == CRABML_HIP_Q8_0 ? 2 : 1;
-        if (split == 2) {
-          if (pipe >= 1)
-            launch_k(st, R, k_gemv_res_nq_ord<FMT, 2, true>, dim3(dim / 16), dim3(1024), lds, planes_of(w), act_view<FMT>(a), c->x, wnext, eps_next, ad.q,
-                     ad.d, ad.isum, ng, k / 32);
-          else
-            launch_k(st, R, k_gemv_res_nq_ord<FMT, 2, false>, dim3(dim / 16), dim3(1024), lds, planes_of(w), act_view<FMT>(a), c->x, wnext, eps_next, ad.q,
-                     ad.d, ad.isum, ng, k / 32);
-        } else {
-          if (pipe >= 2)
-            launch_k(st, R, k_gemv_res_nq_ord<FMT, 1, true>, dim3(dim / 32), dim3(1024), lds, planes_of(w), act_view<FMT>(a), c->x, wnext, eps_next, ad.q,
-                     ad.d, ad.isum, ng, k / 32);
-          else
-            launch_k(st, R, k_gemv_res_nq_ord<FMT, 1, false>, dim3(dim / 32), dim3(1024), lds, planes_of(w), act_view<FMT>(a), c->x, wnext, eps_next, ad.q,
-                     ad.d, ad.isum, ng, k / 32);
-        }
+        const bool piped = pipe >= (split == 2 ? 1 : 2);  // (two workgroups per chunk: ffn_down)
+        with_const_else<2, 1>(split, [&](auto s) {
+          with_const_else<0, 1>(piped, [&](auto p) {
+            launch_k(st, R, k_gemv_res_nq_ord<FMT, decltype(s)::value, decltype(p)::value != 0>, dim3(dim / 32 * split), dim3(1024),
+                     nq_ord_lds_bytes(k / 32, split), planes_of(w), act_view<FMT>(a), c->x, wnext, eps_next, ad.q, ad.d, ad.isum, ng, k / 32);
+          });
+        });
       } else if (defer && !Q81) {  // hop-free: the consumer applies 1 / rms
-        if constexpr (!Q81) {
-          if (split == 2)
-            launch_k(st, R, k_gemv_res_nq<FMT, 2, 0, false, true>, dim3(dim / 16), dim3(1024), 0, planes_of(w), act_view<FMT>(a), (const float*)nullptr,
-                     c->x, wnext, eps_next, ad.q, ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, NoTp{});
-          else
-            launch_k(st, R, k_gemv_res_nq<FMT, 1, 0, false, true>, dim3(dim / 32), dim3(1024), 0, planes_of(w), act_view<FMT>(a), (const float*)nullptr,
-                     c->x, wnext, eps_next, ad.q, ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, NoTp{});
-        }
-      } else if (split == 2)
-        launch_k(st, R, k_gemv_res_nq<FMT, 2>, dim3(dim / 16), dim3(1024), 0, planes_of(w), act_view<FMT>(a), (const float*)nullptr, c->x, wnext,
-                 eps_next,
-                 ad.q, ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, NoTp{});
-      else
-        launch_k(st, R, k_gemv_res_nq<FMT, 1>, dim3(dim / 32), dim3(1024), 0, planes_of(w), act_view<FMT>(a), (const float*)nullptr, c->x, wnext,
-                 eps_next,
-                 ad.q, ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, NoTp{});
+        if constexpr (!Q81) nq(NqForm<0, false, true>{}, 0, nullptr, NoTp{});
+      } else {
+        nq(NqForm<0>{}, 0, nullptr, NoTp{});
+      }
     } else if (c->ord) {
-      launch_k(st, R, k_gemv_res_ord<FMT>, dim3((dim + 7) / 8), dim3(256), (size_t)8 * ((k / 32 + 3) & ~3) * sizeof(float), planes_of(w), act_view<FMT>(a),
-               c->x, dim, k / 32);
+      launch_k(st, R, k_gemv_res_ord<FMT>, dim3((dim + 7) / 8), dim3(256), ord_terms_lds_bytes(k / 32), planes_of(w), act_view<FMT>(a), c->x, dim, k / 32);
     } else if (tp) {
       launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), act_view<FMT>(a), dst, dim, k / 32);
     } else {
@@ -666,12 +710,8 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     if (c->out_qt != qt) {
       // the classifier has its own rhs type (e.g. Q6_K -> Q8_K): normalize the final x to f32 and quantize for it (the
       // planes the last ffn_down epilogue wrote are in the layers' type and stay unused)
-      const size_t nlds = norm_lds_bytes(dim);
       const float* addv = tp && !norm_epi ? c->partial : nullptr;  // (fused collective: x is already final)
-      if (dim <= 4096)
-        k_norm_f32<4><<<1, 1024, nlds, st>>>(c->x, addv, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, c->ord ? 0 : 1);
-      else
-        k_norm_f32<12><<<1, 1024, nlds, st>>>(c->x, addv, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, c->ord ? 0 : 1);
+      launch_norm_f32(st, c->x, addv, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, c->ord ? 0 : 1);
       if (c->out_qt == CRABML_HIP_F32) {
         cls_act = c->xn;
       } else {
@@ -682,60 +722,47 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       CH_TRY(TAP(c->tap_layer == L - 1, CRABML_HIP_TAP_DOWN_ACT, c->act_dim, ad_bytes));
     }
     CH_TRY(TAP(true, CRABML_HIP_TAP_CLS_ACT, cls_act, c->out_qt == CRABML_HIP_F32 ? (size_t)dim * 4 : act_layout(c->out_qt, (size_t)dim).total));
-    if (prof)
-      CH_TRY(prof_begin(dev, &pr, c->output->dtype, 5,
-                        (double)c->vocab_l * (double)(dim / block_elems(c->output->dtype)) * (double)block_bytes(c->output->dtype) +
-                            4.0 * dim + 4.0 * c->vocab_l));
-    CH_TRY(enqueue_classifier_and_sampler(c, cls_act, R));
-    CH_TRY(P1(&pr));
-    return 0;
+    return enqueue_classifier_and_sampler(c, cls_act, prof);
   }
   const int l = seg / 2;
   if ((seg & 1) == 0) {
-    if (l == 0)
-      k_embed<<<(dim + 255) / 256, 256, 0, st>>>((const char*)c->token_embed->ptr, (int)c->token_embed->dtype,
-                                                  c->token_embed->wl.off_scale, token_d, dim, c->x);
+    if (l == 0) launch_embed(c);
     // attention rmsnorm (llama2.rs:230-234)
     if (!norm_epi || l == 0)
       norm_quant((const float*)c->rms_att[l]->ptr, g.rms_norm_eps, tp && l > 0, plan(c->wq[l], c->wk[l], c->wv[l]));
     const bool tl = c->tap_layer == l;
-    if (tl && (!norm_epi || l == 0)) c->tap_plan[CRABML_HIP_PLAN_NORM_NIT] = dim <= 4096 ? 4 : 12;
+    if (tl && (!norm_epi || l == 0)) c->tap_plan[CRABML_HIP_PLAN_NORM_NIT] = norm_nit(dim);
     CH_TRY(TAP(!norm_epi && l > 0 && c->tap_layer == l - 1, CRABML_HIP_TAP_DOWN_ACT, c->act_dim, ad_bytes));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_X, c->x, (size_t)dim * 4));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_ACT, c->act_dim, ad_bytes));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_RSUMS, c->rsums, rs_bytes));
-    // q, k, v + rope + scale + KV append (llama2.rs:244-256, 542-554, 561-565), local heads only
-    QkvEpi e{c->qbuf, c->kc[l], c->vc[l], c->rope, pos_d, 1.0f / std::sqrt((float)hd), dim_l, kv_dim_l, hd,
-             (int)g.rope_dim, c->npairs, seq_cap, kv16 ? 1 : 0};
+    // q, k, v + rope + scale + KV append, local heads only
+    const QkvEpi e = decode_qkv_epi(c, l);
     const int total_rows = dim_l + 2 * kv_dim_l;
     CH_TRY(P0(&pr, 1, total_rows, dim));
     // (the planes of layer l > 0 come from the previous layer's ffn_down launch, with its dim / 32 chunk sums)
     const RmsTail rtq{c->rsums, dim / 32, 1.0f / (float)dim, g.rms_norm_eps};
-    if (c->tap_layer == l && !c->ord) {  // (the predicates of k_qkv's own choice, on the arguments of the launch below)
+    // the two arguments that pick k_qkv's loader: DEFER (1 / rms applied here) and `upfront` -- without DEFER only for few, short
+    // waves (a tensor-parallel rank's rows; small models): two steps per request round
+    const bool deferq = defer_down && l > 0;  // (defer_down: never Q4_1)
+    const int upfront = deferq ? qkv_upfront : (qkv_upfront && total_rows / 2 <= 4 * dev->n_cu) ? 1 : 0;
+    if (c->tap_layer == l && !c->ord) {  // (what the kernel makes of them: rows_partial_rms / rows_partial, gemv_core.hpp)
       const int nu = dim / 32 * BlockFmt<FMT>::UNITS;
-      const bool deferq = defer_down && l > 0 && !Q81;
-      const int upfront = deferq ? qkv_upfront : ((qkv_upfront && total_rows / 2 <= 4 * dev->n_cu) ? 1 : 0);
       c->tap_plan[CRABML_HIP_PLAN_QKV_LOADER] = deferq ? (upfront && nu == 128 ? 4 : 3) : (upfront && nu % 128 == 0 ? 2 : 1);
     }
-    auto qkv = [&](auto ep) {
+    with_qkv_epi(c, e, l, [&](auto ep) {
       constexpr int A = QkvArchOf<decltype(ep)>::value;
       if (c->ord)
-        launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), (size_t)8 * ((dim / 32 + 3) & ~3) * sizeof(float),
-                 planes_of(c->wq[l]), planes_of(c->wk[l]), planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0});
-      else if (defer_down && l > 0) {
+        launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), ord_terms_lds_bytes(dim / 32), planes_of(c->wq[l]),
+                 planes_of(c->wk[l]), planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0});
+      else if (deferq) {
         if constexpr (!Q81)
           launch_k(st, R, k_qkv<FMT, true, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
-                   planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0}, rtq, qkv_upfront);
+                   planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0}, rtq, upfront);
       } else
         launch_k(st, R, k_qkv<FMT, false, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
-                 planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0}, rtq,
-                 // few, short waves (a tensor-parallel rank's rows; small models): two steps per request round
-                 (qkv_upfront && total_rows / 2 <= 4 * dev->n_cu) ? 1 : 0);
-    };
-    if (c->qwen2)
-      qkv(qwen2_epi(c, e, l));
-    else
-      qkv(e);
+                 planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0}, rtq, upfront);
+    });
     CH_TRY(P1(&pr));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_QBUF, c->qbuf, (size_t)dim_l * 4));
     // attention (llama2.rs:571-590) -> attn (f32) [+ Q8_0 planes for wo]; spare CUs prefetch wo
@@ -764,7 +791,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
         launch_k(st, R, k_gateup_h<FMT>, dim3(hidden_l / c->gu_rows), dim3(c->gu_rows / 2 * 64), 0, planes_of(c->gate[l]), planes_of(c->up[l]),
                  act_view<FMT>(ad), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 32);
     } else if (c->ord)
-      launch_k(st, R, k_gateup_q_ord<FMT>, dim3(hidden_l / 32), dim3(1024), (size_t)64 * (((dim / 32 + 3) & ~3) + 4) * sizeof(float), planes_of(c->gate[l]),
+      launch_k(st, R, k_gateup_q_ord<FMT>, dim3(hidden_l / 32), dim3(1024), gateup_q_ord_lds_bytes(dim / 32), planes_of(c->gate[l]),
                planes_of(c->up[l]), act_view<FMT>(ad), dev->exp_table, ah.q, ah.d, ah.isum, dim / 32);
     else if (defer_wo) {
       if constexpr (!Q81)
@@ -793,14 +820,11 @@ int enqueue_segment_generic(crabml_hip_llama* c, int seg) {
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
   const auto& g = c->cfg;
-  const int dim = (int)g.embedding_dim, hd = c->hd, seq_cap = (int)g.seq_len;
+  const int dim = (int)g.embedding_dim;
   const int dim_l = c->dim_l, kv_dim_l = c->kv_dim_l, hidden_l = c->hidden_l;
-  const bool kv16 = g.use_f16_kv_cache != 0;
   const bool strict = dev->strict_order;
   const bool tp = c->tp > 1;
   const int L = (int)g.n_layers;
-  int* token_d = c->state;
-  int* pos_d = c->state + 1;
   const bool prof = dev->prof_on && !c->use_graph && !c->capturing && !strict;
   crabml_hip_device::ProfRec pr{};
   auto gemv = [&](const crabml_hip_buf* w, int m, int k, const void* act, float* out, uint32_t stage) -> int {
@@ -818,44 +842,28 @@ int enqueue_segment_generic(crabml_hip_llama* c, int seg) {
     launch_quantize_act(st, qt, src, (size_t)n, planes);
     return planes;
   };
-  const size_t norm_lds = norm_lds_bytes(dim);
   auto norm = [&](const float* wn, float eps, bool add_pending) {
-    const float* addv = add_pending ? c->partial : nullptr;
-    if (dim <= 4096)
-      k_norm_f32<4><<<1, 1024, norm_lds, st>>>(c->x, addv, wn, dim, eps, c->xn, strict ? 0 : 1);
-    else
-      k_norm_f32<12><<<1, 1024, norm_lds, st>>>(c->x, addv, wn, dim, eps, c->xn, strict ? 0 : 1);
+    launch_norm_f32(st, c->x, add_pending ? c->partial : nullptr, wn, dim, eps, c->xn, strict ? 0 : 1);
   };
   float* dst = tp ? c->partial : c->x;
 
   if (seg == 2 * L) {
     norm((const float*)c->rms_final->ptr, g.rms_norm_eps, tp);
     const void* act = quant(c->xn, dim, c->out_qt, c->act_dim);
-    if (prof)
-      CH_TRY(prof_begin(dev, &pr, c->output->dtype, 5,
-                        (double)c->vocab_l * (double)(dim / block_elems(c->output->dtype)) * (double)block_bytes(c->output->dtype) + 4.0 * dim +
-                            4.0 * c->vocab_l));
-    CH_TRY(enqueue_classifier_and_sampler(c, act, prof ? &pr : nullptr));
-    if (prof) CH_TRY(prof_end(dev, &pr));
-    return 0;
+    return enqueue_classifier_and_sampler(c, act, prof);
   }
   const int l = seg / 2;
   if ((seg & 1) == 0) {
-    if (l == 0)
-      k_embed<<<(dim + 255) / 256, 256, 0, st>>>((const char*)c->token_embed->ptr, (int)c->token_embed->dtype,
-                                                  c->token_embed->wl.off_scale, token_d, dim, c->x);
+    if (l == 0) launch_embed(c);
     norm((const float*)c->rms_att[l]->ptr, g.rms_norm_eps, tp && l > 0);
     const void* act = quant(c->xn, dim, c->qt, c->act_dim);
-    QkvEpi e{c->qbuf, c->kc[l], c->vc[l], c->rope, pos_d, 1.0f / std::sqrt((float)hd), dim_l, kv_dim_l, hd,
-             (int)g.rope_dim, c->npairs, seq_cap, kv16 ? 1 : 0};
     const int total_rows = dim_l + 2 * kv_dim_l;
     CH_TRY(gemv(c->wq[l], dim_l, dim, act, c->tmp, 1));
     CH_TRY(gemv(c->wk[l], kv_dim_l, dim, act, c->tmp + dim_l, 1));
     CH_TRY(gemv(c->wv[l], kv_dim_l, dim, act, c->tmp + dim_l + kv_dim_l, 1));
-    if (c->qwen2)
-      k_qkv_epi<QKV_QWEN2><<<(total_rows / 2 + 255) / 256, 256, 0, st>>>(c->tmp, qwen2_epi(c, e, l));
-    else
-      k_qkv_epi<QKV_LLAMA><<<(total_rows / 2 + 255) / 256, 256, 0, st>>>(c->tmp, e);
+    with_qkv_epi(c, decode_qkv_epi(c, l), l, [&](auto ep) {
+      k_qkv_epi<QkvArchOf<decltype(ep)>::value><<<(total_rows / 2 + 255) / 256, 256, 0, st>>>(c->tmp, ep);
+    });
     enqueue_attention(c, l, nullptr, nullptr, nullptr, PrefetchPlan{}, 0, prof);
     const void* aact = quant(c->attn, dim_l, c->qt, c->act_attn);
     if (strict && !tp) {  // the residual inside the GEMV's own store: x = matmul_out + x (llama2.rs:266)
@@ -893,13 +901,10 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
   const auto& g = c->cfg;
-  const int dim = (int)g.embedding_dim, hd = c->hd, seq_cap = (int)g.seq_len;
+  const int dim = (int)g.embedding_dim;
   const int dim_l = c->dim_l, kv_dim_l = c->kv_dim_l, hidden_l = c->hidden_l;
-  const bool kv16 = g.use_f16_kv_cache != 0;
   const bool tp = c->tp > 1;
   const int L = (int)g.n_layers;
-  int* token_d = c->state;
-  int* pos_d = c->state + 1;
   const bool prof = dev->prof_on && !c->use_graph && !c->capturing;
   crabml_hip_device::ProfRec pr{};
   crabml_hip_device::ProfRec* R = prof ? &pr : nullptr;
@@ -922,14 +927,9 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
   auto six = [&](const crabml_hip_buf* b) {
     return b->dtype == CRABML_HIP_Q6_K ? Planes6{(const char*)b->ptr, b->wl.off_scale} : Planes6{nullptr, 0};
   };
-  const size_t norm_lds = norm_lds_bytes(dim);
   // rmsnorm * weight -> xn -> Q8_K planes (buf_q8_k.rs:84-131)
   auto norm_quant = [&](const float* wn, float eps, bool add_pending, uint32_t qt) -> const void* {
-    const float* addv = add_pending ? c->partial : nullptr;
-    if (dim <= 4096)
-      k_norm_f32<4><<<1, 1024, norm_lds, st>>>(c->x, addv, wn, dim, eps, c->xn, c->ord ? 0 : 1);
-    else
-      k_norm_f32<12><<<1, 1024, norm_lds, st>>>(c->x, addv, wn, dim, eps, c->xn, c->ord ? 0 : 1);
+    launch_norm_f32(st, c->x, add_pending ? c->partial : nullptr, wn, dim, eps, c->xn, c->ord ? 0 : 1);
     if (qt == CRABML_HIP_F32) return c->xn;
     launch_quantize_act(st, qt, c->xn, (size_t)dim, c->act_dim);
     return c->act_dim;
@@ -956,45 +956,18 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         signed char* oq = x_only ? nullptr : (signed char*)c->act_dim;  // (x_only: the consumer quantizes, nq_epilogue)
         void* od = (void*)(c->act_dim + al.off_d);
         void* ob = (void*)(c->act_dim + al.off_aux);
-        // (x_only: no hop pairs the halves of a chunk -- two 16-row workgroups per chunk whenever that still fits the chip twice)
-        const int split = (g.flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_ALWAYS)  ? 2
-                          : (g.flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_NEVER) ? 1
-                          : (k / 32 >= 256 && dim / 32 <= dev->n_cu)        ? 2
-                          : (x_only && dim / 32 <= dev->n_cu)               ? 2
-                                                                            : 1;
-        const size_t lds = (size_t)k + (size_t)(k / 256) * 4 + (size_t)(k / 16) * 2;
+        const int split = chunk_split(g.flags, k, dim, dev->n_cu, x_only);
         if (ordk) {  // (qmode is 1 or 2 here: `qin` holds on every ordered context)
-          const size_t ldso = ((lds + 15) & ~(size_t)15) + (size_t)(32 / split) * (size_t)q4k_rec_stride(k / 256) * sizeof(float);
-#define CRABML_NQ_KO(SPLIT_, QIN_, GRID_)                                                                                                \
-  launch_k(st, R, k_gemv_res_nq<FMT, SPLIT_, QIN_, false, false, true>, dim3(GRID_), dim3(1024), ldso, planes_k(w), a, xin, c->x, wnext, \
-           eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{})
-          if (split == 2 && qmode == 2)
-            CRABML_NQ_KO(2, 2, dim / 16);
-          else if (split == 2)
-            CRABML_NQ_KO(2, 1, dim / 16);
-          else if (qmode == 2)
-            CRABML_NQ_KO(1, 2, dim / 32);
-          else
-            CRABML_NQ_KO(1, 1, dim / 32);
-#undef CRABML_NQ_KO
+          launch_k(st, R, nq_ord_k_kernel(split, qmode == 2 ? 2 : 1), dim3(dim / 32 * split), dim3(1024), q8k_ord_lds_bytes(k, 32 / split), planes_k(w), a,
+                   xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
           return P1();
         }
-#define CRABML_NQ_K(SPLIT_, QIN_, GRID_, LDS_)                                                                                          \
-  launch_k(st, R, k_gemv_res_nq<FMT, SPLIT_, QIN_>, dim3(GRID_), dim3(1024), LDS_, planes_k(w), a, xin, c->x, wnext, eps_next, oq, od, ob, \
-           ng, k / BE, six(w), NoTp{})
-        if (split == 2 && qmode == 2)
-          CRABML_NQ_K(2, 2, dim / 16, lds);
-        else if (split == 2 && qmode == 1)
-          CRABML_NQ_K(2, 1, dim / 16, lds);
-        else if (split == 2)
-          CRABML_NQ_K(2, 0, dim / 16, 0);
-        else if (qmode == 2)
-          CRABML_NQ_K(1, 2, dim / 32, lds);
-        else if (qmode == 1)
-          CRABML_NQ_K(1, 1, dim / 32, lds);
-        else
-          CRABML_NQ_K(1, 0, dim / 32, 0);
-#undef CRABML_NQ_K
+        with_const_else<2, 1>(split, [&](auto s) {
+          with_const_else<2, 1, 0>(qmode, [&](auto q) {  // (the rhs planes in LDS unless they are read from global memory)
+            launch_k(st, R, k_gemv_res_nq<FMT, decltype(s)::value, decltype(q)::value>, dim3(dim / 32 * split), dim3(1024), qmode ? q8k_lds_bytes(k) : 0,
+                     planes_k(w), a, xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
+          });
+        });
         return P1();
       }
     }
@@ -1007,37 +980,23 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
 
   if (seg == 2 * L) {
     const void* act = nepi ? (const void*)c->act_dim : norm_quant((const float*)c->rms_final->ptr, g.rms_norm_eps, tp, c->out_qt);
-    if (prof)
-      CH_TRY(prof_begin(dev, &pr, c->output->dtype, 5,
-                        (double)c->vocab_l * (double)(dim / block_elems(c->output->dtype)) * (double)block_bytes(c->output->dtype) +
-                            4.0 * dim + 4.0 * c->vocab_l));
-    CH_TRY(enqueue_classifier_and_sampler(c, act, R));
-    CH_TRY(P1());
-    return 0;
+    return enqueue_classifier_and_sampler(c, act, prof);
   }
   const int l = seg / 2;
   if ((seg & 1) == 0) {
-    if (l == 0)
-      k_embed<<<(dim + 255) / 256, 256, 0, st>>>((const char*)c->token_embed->ptr, (int)c->token_embed->dtype,
-                                                  c->token_embed->wl.off_scale, token_d, dim, c->x);
+    if (l == 0) launch_embed(c);
     if (!nepi || l == 0) norm_quant((const float*)c->rms_att[l]->ptr, g.rms_norm_eps, tp && l > 0, QT);
-    QkvEpi e{c->qbuf, c->kc[l], c->vc[l], c->rope, pos_d, 1.0f / std::sqrt((float)hd), dim_l, kv_dim_l, hd,
-             (int)g.rope_dim, c->npairs, seq_cap, kv16 ? 1 : 0};
     const int total_rows = dim_l + 2 * kv_dim_l;
     CH_TRY(P0(1, total_rows, dim));
-    auto qkv = [&](auto ep) {
+    with_qkv_epi(c, decode_qkv_epi(c, l), l, [&](auto ep) {
       constexpr int A = QkvArchOf<decltype(ep)>::value;
       if (ordk)
-        launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), (size_t)8 * (size_t)q4k_rec_stride(dim / BE) * sizeof(float),
-                 planes_k(c->wq[l]), planes_k(c->wk[l]), planes_k(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]));
+        launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), ord_terms_k_lds_bytes(dim / BE), planes_k(c->wq[l]),
+                 planes_k(c->wk[l]), planes_k(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]));
       else
         launch_k(st, R, k_qkv<FMT, false, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_k(c->wq[l]), planes_k(c->wk[l]),
                  planes_k(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
-    };
-    if (c->qwen2)
-      qkv(qwen2_epi(c, e, l));
-    else
-      qkv(e);
+    });
     CH_TRY(P1());
     // Q8_K producers: the (short-context) attention kernel assembles the planes of wo's rhs itself; wo copies them
     const bool aq8 = qout && (g.flags & CRABML_HIP_LLAMA_Q8K_ATTN_PRODUCER) && c->attn_variant == 0 && c->attn_s_rows > 0;
@@ -1060,31 +1019,24 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     if (!nepi) norm_quant((const float*)c->rms_ffn[l]->ptr, 1e-5f, tp, QT);  // llama2.rs:611
     CH_TRY(P0(3, 2.0 * hidden_l, dim));
     if constexpr (FMT == CRABML_HIP_Q4_K) {
-      const size_t lds = (size_t)dim + (size_t)(dim / 256) * 4 + (size_t)(dim / 16) * 2;
       const ActLayout alh = act_layout(QT, (size_t)hidden_l);
       const Q8KExchange hx{c->h8gran, c->state + 4, c->state + 5, n_segments(c), seg};
-      const size_t ldso = ((lds + 15) & ~(size_t)15) + (size_t)64 * (size_t)q4k_rec_stride(dim / 256) * sizeof(float);
-      if (ordk && qout)
-        launch_k(st, R, k_gateup_k_lds<true, true>, dim3(hidden_l / 32), dim3(1024), ldso, planes_k(c->gate[l]), planes_k(c->up[l]),
-                 act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 256, hx, (signed char*)c->act_hid,
-                 (float*)(c->act_hid + alh.off_d), (short*)(c->act_hid + alh.off_aux), (signed char*)(c->act_hid + alh.off_p), (const float*)nullptr, (const float*)nullptr, 0.f, (const float*)nullptr, 1);
-      else if (ordk)
-        launch_k(st, R, k_gateup_k_lds<false, true>, dim3(hidden_l / 32), dim3(1024), ldso, planes_k(c->gate[l]), planes_k(c->up[l]),
-                 act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 256, hx, (signed char*)nullptr,
-                 (float*)nullptr, (short*)nullptr, (signed char*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f, (const float*)nullptr, 1);
-      else if (qout && c->k_norm_in)  // wo left x only (below): this launch normalizes and quantizes the row itself
-        launch_k(st, R, k_gateup_k_lds<true, false, true>, dim3(hidden_l / 32), dim3(1024), lds, planes_k(c->gate[l]), planes_k(c->up[l]),
-                 act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 256, hx, (signed char*)c->act_hid,
-                 (float*)(c->act_hid + alh.off_d), (short*)(c->act_hid + alh.off_aux), (signed char*)(c->act_hid + alh.off_p), (const float*)c->x,
-                 (const float*)c->rms_ffn[l]->ptr, 1e-5f, (const float*)c->rsums, dim / 32 <= dev->n_cu ? 2 : 1);
-      else if (qout)
-        launch_k(st, R, k_gateup_k_lds<true>, dim3(hidden_l / 32), dim3(1024), lds, planes_k(c->gate[l]), planes_k(c->up[l]),
-                 act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 256, hx, (signed char*)c->act_hid,
-                 (float*)(c->act_hid + alh.off_d), (short*)(c->act_hid + alh.off_aux), (signed char*)(c->act_hid + alh.off_p), (const float*)nullptr, (const float*)nullptr, 0.f, (const float*)nullptr, 1);
-      else
-        launch_k(st, R, k_gateup_k_lds<false>, dim3((hidden_l + 31) / 32), dim3(1024), lds, planes_k(c->gate[l]), planes_k(c->up[l]),
-                 act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 256, hx, (signed char*)nullptr,
-                 (float*)nullptr, (short*)nullptr, (signed char*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f, (const float*)nullptr, 1);
+      // the form <QOUT, ORD, NORMIN>: h leaves as Q8_K planes too / strict order / wo left x only (above) and this launch normalizes
+      // and quantizes the row itself from wo's chunk sums, as many per chunk as wo had workgroups
+      const bool normin = !ordk && qout && c->k_norm_in;
+      char* const hp = qout ? c->act_hid : nullptr;  // (no planes without QOUT; hidden_l % 32 == 0: llama_create_impl)
+      const float *nx = nullptr, *nw = nullptr, *nsums = nullptr;
+      int sum_parts = 1;
+      if (normin) {
+        nx = c->x;
+        nw = (const float*)c->rms_ffn[l]->ptr;
+        nsums = c->rsums;
+        sum_parts = chunk_split(g.flags, dim_l, dim, dev->n_cu, true);
+      }
+      launch_k(st, R, gateup_k_kernel(qout, ordk, normin), dim3(hidden_l / 32), dim3(1024), ordk ? q8k_ord_lds_bytes(dim, 64) : q8k_lds_bytes(dim),
+               planes_k(c->gate[l]), planes_k(c->up[l]), act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 256, hx,
+               (signed char*)hp, (float*)(hp ? hp + alh.off_d : nullptr), (short*)(hp ? hp + alh.off_aux : nullptr),
+               (signed char*)(hp ? hp + alh.off_p : nullptr), nx, nw, normin ? 1e-5f : 0.f, nsums, sum_parts);
     } else {
       launch_k(st, R, k_gateup<FMT>, dim3((hidden_l + 1) / 2), dim3(128), 0, planes_k(c->gate[l]), planes_k(c->up[l]),
                act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / BE);
@@ -1285,22 +1237,14 @@ bool launch_attn_tile(crabml_hip_llama* c, int l, int B, int pos0) {
   const bool kv16 = c->cfg.use_f16_kv_cache != 0;
   if (c->cfg.flags & CRABML_HIP_LLAMA_NO_TILE_ATTENTION) return false;
   if (pos0 + B > 1024 || hd > (kv16 ? 256 : 128) || hd % (kv16 ? 16 : 4) != 0 || c->n_heads_l % c->n_kv_l != 0) return false;
-  if (kv16) {
-    switch (g) {
-      case 1: return launch_attn_tile_t<true, 1, 4>(c, l, B, pos0);
-      case 2: return launch_attn_tile_t<true, 2, 4>(c, l, B, pos0);
-      case 4: return launch_attn_tile_t<true, 4, 4>(c, l, B, pos0);
-      case 8: return launch_attn_tile_t<true, 8, 2>(c, l, B, pos0);
-      default: return false;
-    }
-  }
-  switch (g) {
-    case 1: return launch_attn_tile_t<false, 1, 4>(c, l, B, pos0);
-    case 2: return launch_attn_tile_t<false, 2, 4>(c, l, B, pos0);
-    case 4: return launch_attn_tile_t<false, 4, 4>(c, l, B, pos0);
-    case 8: return launch_attn_tile_t<false, 8, 2>(c, l, B, pos0);
-    default: return false;
-  }
+  bool ok = false;  // (other group sizes: not covered)
+  with_const_else<0, 1>(kv16, [&](auto kv) {
+    with_const<1, 2, 4, 8>(g, [&](auto grp) {
+      constexpr int G = decltype(grp)::value;
+      ok = launch_attn_tile_t<decltype(kv)::value != 0, G, (G == 8 ? 2 : 4)>(c, l, B, pos0);  // rows per workgroup: G = 8 fills the lanes with two
+    });
+  });
+  return ok;
 }
 
 // prompts past 1024 positions: the three long-context kernels with a row dimension (grid.y), PF_LONG_ROWS rows at a time
@@ -1337,14 +1281,8 @@ int launch_attn_long_rows_t(crabml_hip_llama* c, int l, int B) {
 // 1 = launched, 0 = not covered, < 0 = error
 int launch_attn_long_rows(crabml_hip_llama* c, int l, int B) {
   if (!c->exact_long_ok || (c->cfg.flags & CRABML_HIP_LLAMA_NO_TILE_ATTENTION)) return 0;
-  int rc;
-  switch (c->n_heads_l / c->n_kv_l) {
-    case 1: rc = launch_attn_long_rows_t<1>(c, l, B); break;
-    case 2: rc = launch_attn_long_rows_t<2>(c, l, B); break;
-    case 4: rc = launch_attn_long_rows_t<4>(c, l, B); break;
-    case 8: rc = launch_attn_long_rows_t<8>(c, l, B); break;
-    default: return 0;
-  }
+  int rc = 0;
+  if (!with_const<1, 2, 4, 8>(c->n_heads_l / c->n_kv_l, [&](auto grp) { rc = launch_attn_long_rows_t<decltype(grp)::value>(c, l, B); })) return 0;
   return rc == 0 ? 1 : -1;
 }
 
@@ -1369,29 +1307,25 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   const int* pos_d = c->state + 6;
   const size_t norm_lds = norm_lds_bytes(dim);
   auto norm_rows = [&](const float* wn, float eps) {
-    if (dim <= 4096)
-      k_norm_f32_rows<4><<<rows, 1024, norm_lds, st>>>(c->pf_x, wn, dim, eps, c->pf_xn, half);
-    else
-      k_norm_f32_rows<12><<<rows, 1024, norm_lds, st>>>(c->pf_x, wn, dim, eps, c->pf_xn, half);
+    with_const_else<4, 12>(norm_nit(dim), [&](auto nit) {
+      k_norm_f32_rows<decltype(nit)::value><<<rows, 1024, norm_lds, st>>>(c->pf_x, wn, dim, eps, c->pf_xn, half);
+    });
   };
   static const bool gemm_exact_hook = [] {  // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_EXACT=1): the fast pass with matmul_vec's own scaling
-    const char* h = getenv("CRABML_HIP_TEST_HOOKS");
-    const char* e = getenv("CRABML_HIP_GEMM_EXACT");
-    return h && h[0] == '1' && e && e[0] == '1';
+    const char* e = test_hook("CRABML_HIP_GEMM_EXACT");
+    return e && e[0] == '1';
   }();
   // The fast pass, Q4_0 / Q8_0 weights x Q8_0 rows, Q4_1 x Q8_1, Q4_K / Q6_K x Q8_K, >= 32 rows: the weight-stationary f16 GEMM
   // (gemm_f16w.hip; block scales folded into f16 operands, f32 accumulation inside the matrix core -- a stated deviation of the fast
   // tier).  The rows' pre-scaled f16 planes are made once per rhs and k-slot order (q / k / v and gate / up share theirs): xh_of /
   // xh_order remember what pf_xh currently holds.
   static const bool f16w_off = [] {  // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_INT8=1): the int8 kernels in the fast pass too
-    const char* h = getenv("CRABML_HIP_TEST_HOOKS");
-    const char* e = getenv("CRABML_HIP_GEMM_INT8");
-    return h && h[0] == '1' && e && e[0] == '1';
+    const char* e = test_hook("CRABML_HIP_GEMM_INT8");
+    return e && e[0] == '1';
   }();
   static const int f16w_min = [] {  // lab hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_F16W_MIN=rows): the smallest pass that takes it
-    const char* h = getenv("CRABML_HIP_TEST_HOOKS");
-    const char* e = getenv("CRABML_HIP_F16W_MIN");
-    return h && h[0] == '1' && e ? atoi(e) : 32;
+    const char* e = test_hook("CRABML_HIP_F16W_MIN");
+    return e ? atoi(e) : 32;
   }();
   const bool f16w = allow_f16w && !strict && !gemm_exact_hook && !f16w_off && !(g.flags & CRABML_HIP_LLAMA_PREFILL_INT8_GEMM) &&
                     (c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1 || c->qt == CRABML_HIP_Q8_K) && c->pf_xh != nullptr && B >= f16w_min;  // (shorter passes: the int8 kernels / the GEMV)
@@ -1465,60 +1399,36 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     const size_t pstride = B * (size_t)dim;
     // Q8_0 / Q8_1 rows of 4096 / 8192 elements: the 256-thread form (a thread owns half a quant block / a whole one; prefill_rows.hpp)
     static const bool rows_1024 = [] {  // lab hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_NORM_ROWS_1024=1): the 1024-thread kernel
-      const char* h = getenv("CRABML_HIP_TEST_HOOKS");
-      const char* e = getenv("CRABML_HIP_NORM_ROWS_1024");
-      return h && h[0] == '1' && e && e[0] == '1';
+      const char* e = test_hook("CRABML_HIP_NORM_ROWS_1024");
+      return e && e[0] == '1';
     }();
     if (!fuse_k && !rows_1024 && (dim == 4096 || dim == 8192) && !(g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS)) {
-#define CRABML_NQW(E_, Q_)                                                                                                            \
-  k_norm_quant_rows_w<E_, Q_><<<rows, 256, 0, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux, \
-                                                    half, xh, c->pf_split, pstride, nparts, ovf)
-      if (dim == 4096) {
-        if (q81)
-          CRABML_NQW(16, true);
-        else
-          CRABML_NQW(16, false);
-      } else {
-        if (q81)
-          CRABML_NQW(32, true);
-        else
-          CRABML_NQW(32, false);
-      }
-#undef CRABML_NQW
-      xh_of = xh ? c->pf_act_dim : nullptr;
-      xh_order = order;
-      return c->pf_act_dim;
-    }
-    if (fuse_k) {
-      if (dim <= 4096)
-        k_norm_quant_rows_k<4><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_xn, c->pf_act_dim, ald.total, ald.off_d,
-                                                            ald.off_aux, ald.off_p, half, xh, order, c->pf_split, pstride, nparts, ovf);
-      else
-        k_norm_quant_rows_k<12><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_xn, c->pf_act_dim, ald.total, ald.off_d,
-                                                             ald.off_aux, ald.off_p, half, xh, order, c->pf_split, pstride, nparts, ovf);
-      xh_of = xh ? c->pf_act_dim : nullptr;
-      xh_order = order;
-      return c->pf_act_dim;
-    }
-#define CRABML_NQR(NIT_, Q_)                                                                                                         \
-  if (xh || nparts > 0)                                                                                                              \
-    k_norm_quant_rows_h<NIT_, Q_><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d,  \
-                                                                ald.off_aux, half, xh, c->pf_split, pstride, nparts, ovf);           \
-  else                                                                                                                               \
-    k_norm_quant_rows<NIT_, Q_><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d,    \
-                                                              ald.off_aux, half)
-    if (dim <= 4096) {
-      if (q81)
-        CRABML_NQR(4, true);
-      else
-        CRABML_NQR(4, false);
+      with_const_else<16, 32>(dim / 256, [&](auto ec) {  // elements per thread
+        with_const_else<0, 1>(q81, [&](auto q) {
+          k_norm_quant_rows_w<decltype(ec)::value, decltype(q)::value != 0><<<rows, 256, 0, st>>>(
+              c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux, half, xh, c->pf_split, pstride, nparts, ovf);
+        });
+      });
+    } else if (fuse_k) {
+      with_const_else<4, 12>(norm_nit(dim), [&](auto nit) {
+        k_norm_quant_rows_k<decltype(nit)::value><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_xn, c->pf_act_dim, ald.total,
+                                                                                ald.off_d, ald.off_aux, ald.off_p, half, xh, order, c->pf_split,
+                                                                                pstride, nparts, ovf);
+      });
     } else {
-      if (q81)
-        CRABML_NQR(12, true);
-      else
-        CRABML_NQR(12, false);
+      with_const_else<4, 12>(norm_nit(dim), [&](auto nit) {
+        with_const_else<0, 1>(q81, [&](auto q) {
+          constexpr int NIT = decltype(nit)::value;
+          constexpr bool Q = decltype(q)::value != 0;
+          if (xh || nparts > 0)  // (f16 planes alongside, or pieces of a cut GEMM to add first: prefill_rows.hpp)
+            k_norm_quant_rows_h<NIT, Q><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux,
+                                                                      half, xh, c->pf_split, pstride, nparts, ovf);
+          else
+            k_norm_quant_rows<NIT, Q><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux,
+                                                                    half);
+        });
+      });
     }
-#undef CRABML_NQR
     xh_of = xh ? c->pf_act_dim : nullptr;
     xh_order = order;
     return c->pf_act_dim;
@@ -1552,22 +1462,17 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     QkvEpi e{c->pf_qr, c->kc[l], c->vc[l], c->rope, pos_d, 1.0f / std::sqrt((float)hd), dim, kv_dim, hd,
              (int)g.rope_dim, c->npairs, seq_cap, kv16 ? 1 : 0};
     const int pairs = (dim + 2 * kv_dim) / 2;
-    if (c->qwen2)
-      k_qkv_epi_rows<QKV_QWEN2><<<dim3((pairs + 255) / 256, rows), 256, 0, st>>>(c->pf_q, c->pf_k, c->pf_v, qwen2_epi(c, e, l));
-    else
-      k_qkv_epi_rows<QKV_LLAMA><<<dim3((pairs + 255) / 256, rows), 256, 0, st>>>(c->pf_q, c->pf_k, c->pf_v, e);
+    with_qkv_epi(c, e, l, [&](auto ep) {
+      k_qkv_epi_rows<QkvArchOf<decltype(ep)>::value><<<dim3((pairs + 255) / 256, rows), 256, 0, st>>>(c->pf_q, c->pf_k, c->pf_v, ep);
+    });
     int along = 0;
     // (a pass whose every row sees fewer cached positions than the decode step's switch to the f32 kernels -- attn_long_from --
     // keeps the exact tile kernel, so that prefill(prompt) and a token loop over the same short prompt agree bit for bit)
     if (c->attn_flash_rows && kv16 && pos0 + B >= c->attn_long_from) {
       // fast step: causal flash attention on the f16 matrix cores (k_attn_flash_rows; the deviation stated for k_attn_flash)
       const dim3 fg((unsigned)((B + 63) / 64), (unsigned)n_heads);
-      if (hd == 128)
-        k_attn_flash_rows<128><<<fg, 512, flash_rows_lds_bytes(128), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l], (const unsigned short*)c->vc[l], pos_d,
-                                                   c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
-      else
-        k_attn_flash_rows<64><<<fg, 512, flash_rows_lds_bytes(64), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l], (const unsigned short*)c->vc[l], pos_d,
-                                                  c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
+      flash_rows_kernel(hd)<<<fg, 512, flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
+                                                                        (const unsigned short*)c->vc[l], pos_d, c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
       along = 1;
     } else if (!launch_attn_tile(c, l, (int)B, (int)pos0)) {
       along = launch_attn_long_rows(c, l, (int)B);  // past 1024 positions: the long-context kernels, rows in grid.y
@@ -1577,14 +1482,12 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     }
     if (!along) {  // unusual shapes (f32 cache past 1024 positions, odd group sizes): one workgroup per (head, row)
       const size_t attn_lds = (size_t)(seq_cap + hd) * sizeof(float);
-      if (kv16)
-        k_attn<true><<<dim3(n_heads, rows), 256, attn_lds, st>>>(c->pf_qr, c->kc[l], c->vc[l], pos_d, (const unsigned short*)dev->exp_table,
-                                                                  c->pf_attn, nullptr, nullptr, nullptr, n_heads, n_kv, hd, seq_cap,
-                                                                  PrefetchPlan{}, dev->strict_order ? 256 : 0);
-      else
-        k_attn<false><<<dim3(n_heads, rows), 256, attn_lds, st>>>(c->pf_qr, c->kc[l], c->vc[l], pos_d, (const unsigned short*)dev->exp_table,
-                                                                   c->pf_attn, nullptr, nullptr, nullptr, n_heads, n_kv, hd, seq_cap,
-                                                                   PrefetchPlan{}, dev->strict_order ? 256 : 0);
+      with_const_else<0, 1>(kv16, [&](auto kv) {
+        k_attn<decltype(kv)::value != 0><<<dim3(n_heads, rows), 256, attn_lds, st>>>(c->pf_qr, c->kc[l], c->vc[l], pos_d,
+                                                                                     (const unsigned short*)dev->exp_table, c->pf_attn, nullptr, nullptr,
+                                                                                     nullptr, n_heads, n_kv, hd, seq_cap, PrefetchPlan{},
+                                                                                     dev->strict_order ? 256 : 0);
+      });
     }
     a = quant_rows(c->pf_attn, dim, c->pf_act_dim, c->wo[l]);
     int wo_parts = 0;
@@ -1640,18 +1543,15 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       const dim3 gq((unsigned)((hidden + 255) / 256), rows);
       int order = 0;
       unsigned short* xh = (unsigned short*)xh_target(c->down[l], hidden, &order);
-      if (c->qt == CRABML_HIP_Q8_1 && xh)
-        k_gateup_epi_quant_h<true><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
-                                                       alh.off_d, alh.off_aux, xh, ovf);
-      else if (xh)
-        k_gateup_epi_quant_h<false><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
-                                                        alh.off_d, alh.off_aux, xh, ovf);
-      else if (c->qt == CRABML_HIP_Q8_1)
-        k_gateup_epi_quant<true><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
-                                                     alh.off_d, alh.off_aux);
-      else
-        k_gateup_epi_quant<false><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
-                                                      alh.off_d, alh.off_aux);
+      with_const_else<0, 1>(c->qt == CRABML_HIP_Q8_1, [&](auto q) {
+        constexpr bool Q = decltype(q)::value != 0;
+        if (xh)  // (ffn_down's f16 planes alongside)
+          k_gateup_epi_quant_h<Q><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
+                                                      alh.off_d, alh.off_aux, xh, ovf);
+        else
+          k_gateup_epi_quant<Q><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
+                                                    alh.off_d, alh.off_aux);
+      });
       xh_of = xh ? c->pf_act_hid : nullptr;
       xh_order = order;
       a = c->pf_act_hid;
@@ -1668,10 +1568,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   }
   if (want_logits) {  // final rmsnorm + classifier of the last row only (llama2.rs:274-278, 199-208)
     CH_HIP(dev, hipMemcpyAsync(c->x, c->pf_x + (B - 1) * (size_t)dim, (size_t)dim * 4, hipMemcpyDeviceToDevice, st));
-    if (dim <= 4096)
-      k_norm_f32<4><<<1, 1024, norm_lds, st>>>(c->x, nullptr, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, half);
-    else
-      k_norm_f32<12><<<1, 1024, norm_lds, st>>>(c->x, nullptr, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, half);
+    launch_norm_f32(st, c->x, nullptr, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, half);
     const void* act = c->xn;
     if (c->out_qt != CRABML_HIP_F32) {
       launch_quantize_act(st, c->out_qt, c->xn, (size_t)dim, c->act_dim);
@@ -1983,12 +1880,14 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   // strict order, one device, a format whose dot is one term per block: the fused launches in their block-ordered form (7 per
   // layer: norm + quantize stay their own launches); everything else strict runs the per-op segments
   bool ord = dev->strict_order && fused_fmt && tp == 1;
-  if (ord) {  // the term tables must fit LDS: 64 rows of gate|up (k_gateup_q_ord), a workgroup's 16 / 32 rows of the longest k (ffn_down)
-    const size_t gu = (size_t)64 * (((g.embedding_dim / 32 + 3) & ~(size_t)3) + 4) * 4, 
-                 dn = (size_t)((hidden_l / 32 >= 256 && (int)(g.embedding_dim / 32) <= dev->n_cu) ? 16 : 32) * (((hidden_l / 32 + 3) & ~(size_t)3) + 4) * 4;
-    const void* fn = wt == CRABML_HIP_Q4_0   ? (const void*)k_gateup_q_ord<CRABML_HIP_Q4_0>
-                     : wt == CRABML_HIP_Q8_0 ? (const void*)k_gateup_q_ord<CRABML_HIP_Q8_0>
-                                             : (const void*)k_gateup_q_ord<CRABML_HIP_Q4_1>;
+  if (ord) {  // the term tables must fit LDS: 64 rows of gate|up (k_gateup_q_ord), a workgroup's 16 / 32 rows of wo and ffn_down
+    const int dim = (int)g.embedding_dim;
+    const size_t gu = gateup_q_ord_lds_bytes(dim / 32);
+    // (k_gemv_res_nq_ord keeps the default limit; the split is the launch's own, A/B flags included.  wo's rows are at most 12288
+    // long: 32 x 388 floats, inside the limit)
+    const size_t dn = nq_ord_lds_bytes((int)hidden_l / 32, chunk_split(g.flags, (int)hidden_l, dim, dev->n_cu));
+    const void* fn = nullptr;  // (enqueue_segment launches k_gateup_q_ord<FMT> of the same weight type)
+    with_const_else<CRABML_HIP_Q4_0, CRABML_HIP_Q8_0, CRABML_HIP_Q4_1>((int)wt, [&](auto fmt) { fn = (const void*)k_gateup_q_ord<decltype(fmt)::value>; });
     if (gu > 150 * 1024 || dn > 60 * 1024 || (gu > 60 * 1024 && raise_dyn_lds(dev, fn, (int)gu) != hipSuccess)) ord = false;
     (void)hipGetLastError();
   }
@@ -2077,22 +1976,18 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
               !(g.flags & (CRABML_HIP_LLAMA_NO_NORM_EPILOGUE | CRABML_HIP_LLAMA_NO_KQUANT_FUSION | CRABML_HIP_LLAMA_NO_RHS_PROLOGUE)) &&
               g.embedding_dim % 256 == 0 && dim_l % 256 == 0 && hidden_l % 256 == 0 && (int)(g.embedding_dim / 32) <= dev->n_cu;
   if (ordk && !dry) {
-    auto planes_b = [](size_t k) { return ((k + k / 256 * 4 + k / 16 * 2) + 15) & ~(size_t)15; };
-    const int split_dn = (g.flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_ALWAYS) ? 2 : (g.flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_NEVER) ? 1 : hidden_l / 32 >= 256 ? 2 : 1;
-    const int split_wo = (g.flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_ALWAYS) ? 2 : (g.flags & CRABML_HIP_LLAMA_SPLIT_CHUNKS_NEVER) ? 1 : dim_l / 32 >= 256 ? 2 : 1;
-    const size_t gu = planes_b(g.embedding_dim) + (size_t)64 * (size_t)q4k_rec_stride((int)(g.embedding_dim / 256)) * 4;
-    const size_t dn = planes_b(hidden_l) + (size_t)(32 / split_dn) * (size_t)q4k_rec_stride((int)(hidden_l / 256)) * 4;
-    const size_t wo = planes_b(dim_l) + (size_t)(32 / split_wo) * (size_t)q4k_rec_stride((int)(dim_l / 256)) * 4;
+    // (wo never runs x_only here: k_norm_in is off on a strict-order device)
+    const int dim = (int)g.embedding_dim;
+    const size_t gu = q8k_ord_lds_bytes(dim, 64);
+    const size_t dn = q8k_ord_lds_bytes((int)hidden_l, 32 / chunk_split(g.flags, (int)hidden_l, dim, dev->n_cu));
+    const size_t wo = q8k_ord_lds_bytes((int)dim_l, 32 / chunk_split(g.flags, (int)dim_l, dim, dev->n_cu));
     const size_t nq = dn > wo ? dn : wo;
     bool fits = gu <= 150 * 1024 && nq <= 150 * 1024;
-    if (fits && gu > 48 * 1024)
-      fits = raise_dyn_lds(dev, (const void*)k_gateup_k_lds<true, true>, (int)gu) == hipSuccess &&
-             raise_dyn_lds(dev, (const void*)k_gateup_k_lds<false, true>, (int)gu) == hipSuccess;
-    if (fits && nq > 48 * 1024)
-      fits = raise_dyn_lds(dev, (const void*)k_gemv_res_nq<CRABML_HIP_Q4_K, 1, 1, false, false, true>, (int)nq) == hipSuccess &&
-             raise_dyn_lds(dev, (const void*)k_gemv_res_nq<CRABML_HIP_Q4_K, 1, 2, false, false, true>, (int)nq) == hipSuccess &&
-             raise_dyn_lds(dev, (const void*)k_gemv_res_nq<CRABML_HIP_Q4_K, 2, 1, false, false, true>, (int)nq) == hipSuccess &&
-             raise_dyn_lds(dev, (const void*)k_gemv_res_nq<CRABML_HIP_Q4_K, 2, 2, false, false, true>, (int)nq) == hipSuccess;
+    if (fits && gu > 48 * 1024)  // both QOUT forms: q8k_producers is decided further down
+      for (int qout = 0; qout < 2; qout++) fits = fits && raise_dyn_lds(dev, (const void*)gateup_k_kernel(qout != 0, true, false), (int)gu) == hipSuccess;
+    if (fits && nq > 48 * 1024)  // every <SPLIT, QIN> the ordered wo / ffn_down launches can ask nq_ord_k_kernel for
+      for (int split = 1; split <= 2; split++)
+        for (int qin = 1; qin <= 2; qin++) fits = fits && raise_dyn_lds(dev, (const void*)nq_ord_k_kernel(split, qin), (int)nq) == hipSuccess;
     (void)hipGetLastError();
     if (!fits) ordk = false;
   }
@@ -2218,14 +2113,8 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
       A(n_heads_l * g.seq_len * 4, (void**)&c->scores_g);
       A(n_heads_l * g.seq_len * 2, (void**)&c->p16);
       if (!(g.flags & CRABML_HIP_LLAMA_NO_PV_PRODUCER_WAVES) && g.seq_len % 4 == 0) {
-        hipError_t e = hipErrorInvalidValue;
-        switch (grp) {
-          case 1: e = raise_dyn_lds(dev, (const void*)k_attn_pv_split<1>, (int)PvSplit<1>::LDS); break;
-          case 2: e = raise_dyn_lds(dev, (const void*)k_attn_pv_split<2>, (int)PvSplit<2>::LDS); break;
-          case 4: e = raise_dyn_lds(dev, (const void*)k_attn_pv_split<4>, (int)PvSplit<4>::LDS); break;
-          default: e = raise_dyn_lds(dev, (const void*)k_attn_pv_split<8>, (int)PvSplit<8>::LDS); break;
-        }
-        c->pv_split = e == hipSuccess;
+        const PvSplitKernel pv = pv_split_kernel((int)grp);
+        c->pv_split = raise_dyn_lds(dev, (const void*)pv.fn, (int)pv.lds) == hipSuccess;
         (void)hipGetLastError();
       }
     }
@@ -2238,19 +2127,15 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
       if (fn != nullptr && raise_dyn_lds(dev, (const void*)fn, (int)flash_lds_bytes((int)grp, (int)hd)) == hipSuccess) {
         int S = dev->n_cu / (int)n_kv_l;
         S = S < 1 ? 1 : S > FLASH_MAX_SLICES ? FLASH_MAX_SLICES : S;
-        if (const char* hooks = getenv("CRABML_HIP_TEST_HOOKS"))  // tuning hook (tools/flash_sweep.py): slices per kv head in the grid
-          if (hooks[0] == '1')
-            if (const char* e = getenv("CRABML_HIP_FLASH_SLICES")) {
-              const int v = atoi(e);
-              if (v >= 1 && v <= FLASH_MAX_SLICES) S = v;
-            }
+        if (const char* e = test_hook("CRABML_HIP_FLASH_SLICES")) {  // tuning hook (tools/flash_sweep.py): slices per kv head in the grid
+          const int v = atoi(e);
+          if (v >= 1 && v <= FLASH_MAX_SLICES) S = v;
+        }
         c->flash_S = S;
-        if (const char* hooks = getenv("CRABML_HIP_TEST_HOOKS"))  // tuning hook (tools/flash_sweep.py); armed like ASSUME_CUS
-          if (hooks[0] == '1')
-            if (const char* e = getenv("CRABML_HIP_FLASH_MIN_ROWS")) {
-              const int v = atoi(e);
-              if (v >= 8 && v <= 65536) c->flash_min_rows = v;
-            }
+        if (const char* e = test_hook("CRABML_HIP_FLASH_MIN_ROWS")) {  // tuning hook (tools/flash_sweep.py); armed like ASSUME_CUS
+          const int v = atoi(e);
+          if (v >= 8 && v <= 65536) c->flash_min_rows = v;
+        }
         A(n_kv_l * (size_t)S * flash_part_floats((int)grp, (int)hd) * 4, (void**)&c->flash_part);
         A(n_kv_l * 4, (void**)&c->flash_tick);
         if (rc == 0 && !dry && hipMemsetAsync(c->flash_tick, 0, n_kv_l * 4, dev->stream) != hipSuccess) rc = CRABML_HIP_UNEXPECTED;
@@ -2261,18 +2146,15 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
         // (profiles/r05_flash_ticket_sweep.md; same partials, same merge order: bit-identical): a third graph variant serves that range.
         if (c->attn_flash && !c->flash_ticket) {
           size_t until = 768;
-          if (const char* hooks = getenv("CRABML_HIP_TEST_HOOKS"))  // tuning hook: 0 = never
-            if (hooks[0] == '1')
-              if (const char* e = getenv("CRABML_HIP_FLASH_TICKET_UNTIL")) until = (size_t)atol(e);
+          if (const char* e = test_hook("CRABML_HIP_FLASH_TICKET_UNTIL")) until = (size_t)atol(e);  // tuning hook: 0 = never
           const FlashFn tfn = flash_kernel((int)grp, (int)hd, qt == CRABML_HIP_Q8_1, true);
           if (until > 0 && tfn != nullptr && raise_dyn_lds(dev, (const void*)tfn, (int)flash_lds_bytes((int)grp, (int)hd)) == hipSuccess)
             c->flash_ticket_until = until;
           (void)hipGetLastError();
         }
         // the prompt pass's causal attention of the fast step (k_attn_flash_rows): 70 KB of LDS at head_dim 128
-        if (c->attn_flash && (hd == 128 || hd == 64) &&
-            raise_dyn_lds(dev, hd == 128 ? (const void*)k_attn_flash_rows<128> : (const void*)k_attn_flash_rows<64>,
-                          (int)flash_rows_lds_bytes((int)hd)) == hipSuccess)
+        if (c->attn_flash && flash_rows_kernel((int)hd) != nullptr &&
+            raise_dyn_lds(dev, (const void*)flash_rows_kernel((int)hd), (int)flash_rows_lds_bytes((int)hd)) == hipSuccess)
           c->attn_flash_rows = true;
         (void)hipGetLastError();
         // k_attn_flash + merge overtake the staged one-workgroup kernel between 64 and 96 cached positions (8B shape, per layer:
@@ -2285,9 +2167,7 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
     if (g.use_f16_kv_cache && hd % 8 == 0 && !(g.flags & CRABML_HIP_LLAMA_NO_STAGED_ATTENTION)) {
       const size_t S = c->attn_long_ok && c->attn_long_from < g.seq_len ? c->attn_long_from : g.seq_len;
       const size_t lds = attn_s_lds_bytes((int)S, (int)hd);
-      if (lds <= 150 * 1024 &&
-          raise_dyn_lds(dev, (const void*)k_attn_s<128>, (int)lds) == hipSuccess &&
-          raise_dyn_lds(dev, (const void*)k_attn_s<0>, (int)lds) == hipSuccess) {
+      if (lds <= 150 * 1024 && raise_dyn_lds(dev, (const void*)attn_s_kernel((int)hd), (int)lds) == hipSuccess) {
         c->attn_s_rows = (int)S;
         c->attn_s_lds = lds;
       }
@@ -2886,8 +2766,8 @@ int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float*
   CH_LIVE(dev);
   CH_USE(dev);
   CH_FLUSH(dev);
-  if (raise_dyn_lds(dev, head_dim == 128 ? (const void*)k_attn_flash_rows<128> : (const void*)k_attn_flash_rows<64>,
-                    (int)flash_rows_lds_bytes((int)head_dim)) != hipSuccess)
+  const FlashRowsFn fn = flash_rows_kernel((int)head_dim);
+  if (raise_dyn_lds(dev, (const void*)fn, (int)flash_rows_lds_bytes((int)head_dim)) != hipSuccess)
     CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "debug_flash_attention_rows: LDS");
   const size_t seq = seq_cap;
   const size_t nq = rows * n_heads * head_dim * 4, nkv = n_kv * seq * head_dim * 2;
@@ -2904,12 +2784,8 @@ int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float*
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e == hipSuccess) {
     const dim3 fg((unsigned)((rows + 63) / 64), (unsigned)n_heads);
-    if (head_dim == 128)
-      k_attn_flash_rows<128><<<fg, 512, flash_rows_lds_bytes(128), st>>>((const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
-                                                 (const int*)(base + o_pos), (float*)(base + o_out), (int)n_heads, (int)n_kv, (int)seq, (int)rows);
-    else
-      k_attn_flash_rows<64><<<fg, 512, flash_rows_lds_bytes(64), st>>>((const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
-                                                (const int*)(base + o_pos), (float*)(base + o_out), (int)n_heads, (int)n_kv, (int)seq, (int)rows);
+    fn<<<fg, 512, flash_rows_lds_bytes((int)head_dim), st>>>((const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
+                                                             (const int*)(base + o_pos), (float*)(base + o_out), (int)n_heads, (int)n_kv, (int)seq, (int)rows);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, base + o_out, nq, hipMemcpyDeviceToHost, st);
@@ -3008,13 +2884,9 @@ int lazy_ctx_final_norm(crabml_hip_llama* c, float* dst) {
   crabml_hip_device* dev = c->dev;
   if (dev->dry) return 0;
   const int dim = (int)c->cfg.embedding_dim;
-  const size_t lds = norm_lds_bytes(dim);
   // the order of the step's own final norm: the reference's scan on a strict-order device, the fast split otherwise
   const int half = dev->strict_order ? 0 : 1;
-  if (dim <= 4096)
-    k_norm_f32<4><<<1, 1024, lds, dev->stream>>>(c->x, nullptr, (const float*)c->rms_final->ptr, dim, c->cfg.rms_norm_eps, dst, half);
-  else
-    k_norm_f32<12><<<1, 1024, lds, dev->stream>>>(c->x, nullptr, (const float*)c->rms_final->ptr, dim, c->cfg.rms_norm_eps, dst, half);
+  launch_norm_f32(dev->stream, c->x, nullptr, (const float*)c->rms_final->ptr, dim, c->cfg.rms_norm_eps, dst, half);
   CH_HIP(dev, hipGetLastError());
   return 0;
 }

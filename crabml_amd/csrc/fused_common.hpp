@@ -549,6 +549,10 @@ __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, ty
 // strict order (CRABML_HIP_FLAG_STRICT_ORDER, Q4_0 / Q8_0 / Q4_1 layers): the same launch with the block terms parked in LDS and
 // added in block order by one lane per row (rows_terms / ordered_sum, gemv_core.hpp) -- q, k and v rows bit-identical to the scalar
 // loops of the reference, then the same epilogue.  Workgroup = 4 waves x one (even, odd) row pair; dynamic LDS = 8 * nt floats.
+// (k_gemv_res_ord, fused_ffn.hpp, parks its 8 rows the same way)
+__host__ __device__ inline size_t ord_terms_lds_bytes(int nb) { return (size_t)8 * ((nb + 3) & ~3) * sizeof(float); }
+// ... and of the Q4_K form: 8 rows of nine-term records
+__host__ __device__ inline size_t ord_terms_k_lds_bytes(int nsb) { return (size_t)8 * (size_t)q4k_rec_stride(nsb) * sizeof(float); }
 template <int FMT, int ARCH = QKV_LLAMA>
 __global__ __launch_bounds__(256) void k_qkv_ord(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb,
                                                  typename QkvArch<ARCH>::epi e, Planes6 wv6) {

@@ -224,6 +224,13 @@ __device__ __forceinline__ void stage_quant_q8_0_store(const StageQ8Regs& r, int
   }
 }
 __host__ __device__ inline size_t q8_0_lds_bytes(int nb) { return (size_t)nb * 32 + (size_t)((nb + 1) & ~1) * 2 + (size_t)nb * 4; }
+// the Q8_K planes of a k-element rhs in LDS (k_gemv_res_nq<Q4_K, .., QIN 1 / 2>, k_gateup_k_lds): q[k] | d[k/256] f32 | bsums[k/16] i16
+__host__ __device__ inline size_t q8k_lds_bytes(int k) { return (size_t)k + (size_t)(k / 256) * 4 + (size_t)(k / 16) * 2; }
+// ... and of their ORD forms: the planes rounded up to 16 bytes + the nine-term records of `rows` rows (32 / SPLIT of k_gemv_res_nq,
+// the 64 gate and up rows of k_gateup_k_lds)
+__host__ __device__ inline size_t q8k_ord_lds_bytes(int k, int rows) {
+  return ((q8k_lds_bytes(k) + 15) & ~(size_t)15) + (size_t)rows * (size_t)q4k_rec_stride(k / 256) * sizeof(float);
+}
 
 struct NormGather {
   unsigned long long* slots;  // dim/16 granules: each workgroup's ordered sum of squares over its rows
@@ -681,6 +688,7 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
 //     first one's scan from its granule (one more dependent round trip, for that half of the workgroups);
 //   * the chunk sums added strictly in chunk order through v_readlane (rms_norm.rs:38-40), as norm_quant_block does with half = 0.
 // Same outputs as k_gemv_res_ord + k_norm_quant(half = 0), bit for bit, in one launch instead of two.
+__host__ __device__ inline size_t nq_ord_lds_bytes(int nb, int split) { return (size_t)(32 / split) * (((nb + 3) & ~3) + 4) * sizeof(float); }
 template <int FMT, int SPLIT, bool PIPE>  // PIPE: the chain follows the stream step by step (below); else one chain behind the last load
 __global__ __launch_bounds__(1024) void k_gemv_res_nq_ord(Planes w, typename ActOf<FMT>::type act, float* __restrict__ x,
                                                           const float* __restrict__ wnext, float eps, signed char* __restrict__ q,
@@ -1134,6 +1142,7 @@ __global__ __launch_bounds__(1024) void k_gateup_h(Planes wg, Planes wu, typenam
 // strict order: k_gateup_q with the block terms of the 32 gate and 32 up rows parked in LDS (row stride nt + 4 floats: the 64 chain
 // lanes read 16-byte pieces four banks apart) and added in block order by one lane per (matrix, row); SiLU * mul and the Q8_0 / Q8_1
 // block of h as in k_gateup_q.  Dynamic LDS = 64 * (nt + 4) floats.
+__host__ __device__ inline size_t gateup_q_ord_lds_bytes(int nb) { return (size_t)64 * (((nb + 3) & ~3) + 4) * sizeof(float); }
 template <int FMT>
 __global__ __launch_bounds__(1024) void k_gateup_q_ord(Planes wg, Planes wu, typename ActOf<FMT>::type act,
                                                        const unsigned short* __restrict__ exp_tab, signed char* __restrict__ q,

@@ -670,9 +670,8 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
   for (int j = 0; j < nw; j++)
     if (w[j]->dtype != dt || m[j] % 4 != 0 || !f16w_range_ok(dev, w[j])) return false;
   static const int variant = [] {  // lab hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_F16W=n): 1 = two fragments, 3 = one; +8 = never split k; +16 = T = 8 always; +32 = k pieces of >= 8 chunks; +64 = no gate | up epilogue; +512 = T = 4 always; +1024 = narrow launches as <2, 4>
-    const char* h = getenv("CRABML_HIP_TEST_HOOKS");
-    const char* e = getenv("CRABML_HIP_F16W");
-    return h && h[0] == '1' && e ? atoi(e) : 0;
+    const char* e = test_hook("CRABML_HIP_F16W");
+    return e ? atoi(e) : 0;
   }();
   size_t mtot = 0;
   for (int j = 0; j < nw; j++) mtot += m[j];

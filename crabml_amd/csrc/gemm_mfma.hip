@@ -887,9 +887,8 @@ bool launch_gemm_mfma(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m,
   // 64-column tiles amortize a weight tile over more batch rows; when that grid leaves the chip under-occupied
   // (m = 4096: 64 row tiles) 32-column tiles double the workgroups per CU -- the k loop is latency-bound per wave
   static const int narrow_wgs_per_cu = [] {  // tuning hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_NARROW=n): default 4
-    const char* hooks = getenv("CRABML_HIP_TEST_HOOKS");
-    const char* e = getenv("CRABML_HIP_GEMM_NARROW");
-    const int v = hooks && hooks[0] == '1' && e ? atoi(e) : 4;
+    const char* e = test_hook("CRABML_HIP_GEMM_NARROW");
+    const int v = e ? atoi(e) : 4;
     return v >= 0 && v <= 16 ? v : 4;
   }();
   const bool narrow = (size_t)row_tiles * ((b + 63) / 64) < (size_t)narrow_wgs_per_cu * dev->n_cu && b > 16;

@@ -703,9 +703,8 @@ int launch_gemv_strict(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m
   const unsigned grid = (unsigned)((m + R * WAVES - 1) / (R * WAVES));
   // CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_STRICT_SCALAR=1: every format through the one-thread-per-row kernel (the A/B of the tests)
   static const bool scalar_only = [] {
-    const char* h = getenv("CRABML_HIP_TEST_HOOKS");
-    const char* e = getenv("CRABML_HIP_STRICT_SCALAR");
-    return h && h[0] == '1' && e && e[0] == '1';
+    const char* e = test_hook("CRABML_HIP_STRICT_SCALAR");
+    return e && e[0] == '1';
   }();
   for (size_t bi = 0; bi < b; bi++) {
     const char* ap = (const char*)act + bi * act_stride;

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace crabml_hip {
@@ -13,6 +15,19 @@ inline void launch_k(hipStream_t st, crabml_hip_device::ProfRec* rec, K kernel, 
     hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, st, rec->e0, rec->e1, 0, args...);
   else
     hipLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, st, args...);
+}
+// a run-time value as a template argument: calls f(std::integral_constant<int, V>{}) for the V among Vs... that equals v; false if
+// none does.  Range it over exactly the values a launch site may see: every V instantiates what f launches.
+template <int... Vs, class F>
+inline bool with_const(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// ... with the last V as the `else` arm: a v that equals none of them takes it, so f always runs (what a ladder's final `else` /
+// `default:` did; the sites' preconditions rule such a v out)
+template <int... Vs, class F>
+inline void with_const_else(int v, F&& f) {
+  constexpr int vs[] = {Vs...};
+  if (!with_const<Vs...>(v, f)) f(std::integral_constant<int, vs[sizeof...(Vs) - 1]>{});
 }
 
 // ---- quantize.hip: activation quantizers (buf_q8_0.rs:87-134, buf_q8_1.rs:90-129, buf_q8_k.rs:84-131)

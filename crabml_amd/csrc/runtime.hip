@@ -219,13 +219,11 @@ int crabml_hip_device_create(const crabml_hip_device_options_t* opts, crabml_hip
   dev->lazy = !(opts && (opts->flags & CRABML_HIP_FLAG_PER_OP));
   dev->fuse = dev->lazy && !(opts && (opts->flags & CRABML_HIP_FLAG_LAZY_NO_FUSION));
   dev->lz = new LazyState();
-  const char* hooks = getenv("CRABML_HIP_TEST_HOOKS");
-  const bool hooks_on = hooks != nullptr && hooks[0] == '1';
   if (opts && (opts->flags & CRABML_HIP_FLAG_DRY)) {
     // test hook (tests/test_lazy_queue.py): a device object with NO HIP device behind it -- Tensor calls are recorded, matched
     // against the decode template and counted; nothing is computed and export() hands out zeros.  Armed only together with
     // CRABML_HIP_TEST_HOOKS=1, and it says so: this is not a CPU fallback, it cannot produce a single logit.
-    if (!hooks_on) {
+    if (!test_hooks_armed()) {
       lazy_destroy(dev);
       delete dev;
       return CRABML_HIP_UNEXPECTED;
@@ -266,13 +264,11 @@ int crabml_hip_device_create(const crabml_hip_device_options_t* opts, crabml_hip
   // test hook (tests/test_hip_fault_paths.py): claim this many CUs whatever the device reports, so that a CU-masked process
   // (HSA_CU_MASK) loses the co-residency the in-launch hand-offs rely on -- their bounded polls must raise, not hang
   // Armed only when CRABML_HIP_TEST_HOOKS=1 is set as well (a stray CRABML_HIP_ASSUME_CUS alone is ignored), and it says so.
-  if (hooks_on) {
-    if (const char* e = getenv("CRABML_HIP_ASSUME_CUS")) {
-      const int v = atoi(e);
-      if (v > 0 && v <= 1024) {
-        fprintf(stderr, "crabml_hip: TEST HOOK active: assuming %d CUs (device reports %d)\n", v, dev->n_cu);
-        dev->n_cu = v;
-      }
+  if (const char* e = test_hook("CRABML_HIP_ASSUME_CUS")) {
+    const int v = atoi(e);
+    if (v > 0 && v <= 1024) {
+      fprintf(stderr, "crabml_hip: TEST HOOK active: assuming %d CUs (device reports %d)\n", v, dev->n_cu);
+      dev->n_cu = v;
     }
   }
   if (opts && opts->stream) {
