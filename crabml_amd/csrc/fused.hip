@@ -224,6 +224,13 @@ struct crabml_hip_llama {
   size_t tap_cap = 0, tap_used = 0;
   size_t tap_off[CRABML_HIP_TAP_FIELDS] = {}, tap_len[CRABML_HIP_TAP_FIELDS] = {};
   int32_t tap_plan[CRABML_HIP_TAP_PLAN_WORDS] = {};  // the launch plan of the tapped layer, noted where the enqueue code decides
+  // crabml_hip_llama_debug_prefill_tap: the same for one chunk pass of the prompt path (prefill_chunk_pass, pf_tap_copy); a scratch
+  // area of its own (every field holds all rows of the pass), allocated on the first prefill tap
+  int pft_layer = -1;
+  char* pft_buf = nullptr;
+  size_t pft_cap = 0, pft_used = 0;
+  size_t pft_off[CRABML_HIP_PFTAP_FIELDS] = {}, pft_len[CRABML_HIP_PFTAP_FIELDS] = {};
+  int32_t pft_plan[CRABML_HIP_PFTAP_PLAN_WORDS] = {};
 };
 
 // ---- lazy.hip's context: token / position / serial of a step straight from kernel arguments (a launch on the stream's own queue:
@@ -375,6 +382,22 @@ int tap_copy(crabml_hip_llama* c, int f, const void* src, size_t bytes) {
   c->tap_off[f] = off;
   c->tap_len[f] = bytes;
   c->tap_used = off + bytes;
+  return 0;
+}
+// ... of the prompt pass (crabml_hip_llama_debug_prefill_tap)
+int pf_tap_copy(crabml_hip_llama* c, int f, const void* src, size_t bytes) {
+  if (c->pft_layer < 0 || src == nullptr || bytes == 0) return 0;
+  if (f < 0 || f >= CRABML_HIP_PFTAP_FIELDS) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: no field %d", f);
+  // a field copied a second time in one pass (the one-launch GEMM declined after its B' was tapped: the separate launches tap it again)
+  // takes its slot again -- the area holds every field once
+  const bool again = c->pft_len[f] == bytes;
+  const size_t off = again ? c->pft_off[f] : align_up(c->pft_used, 256);
+  if (off + bytes > c->pft_cap) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: scratch area too small");
+  CH_HIP(c->dev, hipMemcpyAsync(c->pft_buf + off, src, bytes, hipMemcpyDeviceToDevice, c->dev->stream));
+  if (again) return 0;
+  c->pft_off[f] = off;
+  c->pft_len[f] = bytes;
+  c->pft_used = off + bytes;
   return 0;
 }
 
@@ -1361,13 +1384,17 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     return planes;
   };
   // defer (nullable): a GEMM cut into k pieces may leave the sum of its pieces to the row kernel that consumes `out` (pf_split holds them)
-  auto gemm = [&](const crabml_hip_buf* w, int m, int k, const void* act, float* out, int* defer = nullptr) -> int {
+  // fc / xh_field (prefill tap only): the launch form as taken, and the tap field B' goes to as this GEMM finds it
+  auto gemm = [&](const crabml_hip_buf* w, int m, int k, const void* act, float* out, int* defer = nullptr, F16wForce* fc = nullptr,
+                  int xh_field = -1) -> int {
     if (defer) *defer = 0;
     if (g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS) defer = nullptr;  // (A/B: every reduce its own launch)
     if (f16w && gemm_f16w_takes(dev, w, c->qt) && (c->qt != CRABML_HIP_Q8_K || k % 256 == 0)) {
       rows_to_f16(w, act, k);
+      if (xh_field >= 0) CH_TRY(pf_tap_copy(c, xh_field, c->pf_xh, B * (size_t)k * 2));
       const size_t mm = (size_t)m;
-      if (launch_gemm_f16w(dev, &w, &mm, 1, (size_t)k, c->pf_xh, B, &out, c->pf_split, c->pf_split_floats, nullptr, nullptr, defer)) return 0;
+      if (launch_gemm_f16w(dev, &w, &mm, 1, (size_t)k, c->pf_xh, B, &out, c->pf_split, c->pf_split_floats, nullptr, nullptr, defer, nullptr, fc))
+        return 0;
     }
     if (!strict) {
       return launch_gemv(dev, w, m, k, act, B, out, nullptr, !gemm_exact_hook);
@@ -1392,6 +1419,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   const ActLayout alh = act_layout(c->qt == CRABML_HIP_F32 ? CRABML_HIP_Q8_0 : c->qt, (size_t)hidden);
   // pending = the wo / ffn_down output that has not been added to x yet (folded into the next norm)
   // nparts: `pending` is piece 0 of a GEMM cut into k pieces, the others wait in pf_split (gemm's defer)
+  int norm_kernel = 0;  // (prefill tap: which of them the last call launched -- CRABML_HIP_PFPLAN_NORM_KERNEL, read after the first norm)
   auto norm_quant_rows = [&](const float* wn, float eps, float* pending, const crabml_hip_buf* next, int nparts = 0) -> const void* {
     const bool q81 = c->qt == CRABML_HIP_Q8_1;
     int order = 0;
@@ -1403,6 +1431,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       return e && e[0] == '1';
     }();
     if (!fuse_k && !rows_1024 && (dim == 4096 || dim == 8192) && !(g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS)) {
+      norm_kernel = 3;
       with_const_else<16, 32>(dim / 256, [&](auto ec) {  // elements per thread
         with_const_else<0, 1>(q81, [&](auto q) {
           k_norm_quant_rows_w<decltype(ec)::value, decltype(q)::value != 0><<<rows, 256, 0, st>>>(
@@ -1410,6 +1439,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
         });
       });
     } else if (fuse_k) {
+      norm_kernel = 4;
       with_const_else<4, 12>(norm_nit(dim), [&](auto nit) {
         k_norm_quant_rows_k<decltype(nit)::value><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_xn, c->pf_act_dim, ald.total,
                                                                                 ald.off_d, ald.off_aux, ald.off_p, half, xh, order, c->pf_split,
@@ -1420,12 +1450,15 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
         with_const_else<0, 1>(q81, [&](auto q) {
           constexpr int NIT = decltype(nit)::value;
           constexpr bool Q = decltype(q)::value != 0;
-          if (xh || nparts > 0)  // (f16 planes alongside, or pieces of a cut GEMM to add first: prefill_rows.hpp)
+          if (xh || nparts > 0) {  // (f16 planes alongside, or pieces of a cut GEMM to add first: prefill_rows.hpp)
+            norm_kernel = 2;
             k_norm_quant_rows_h<NIT, Q><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux,
                                                                       half, xh, c->pf_split, pstride, nparts, ovf);
-          else
+          } else {
+            norm_kernel = 1;
             k_norm_quant_rows<NIT, Q><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux,
                                                                     half);
+          }
         });
       });
     }
@@ -1435,37 +1468,68 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   };
   bool pending_down = false;  // (fuse_rows) the previous layer's ffn_down output sits in pf_tmp, not yet added to pf_x
   int down_parts = 0;         // ... as piece 0 of this many + 1 k pieces
+  // the prefill tap (test hook): host-side copies between the launches of the tapped layer, the launch plan noted where it is decided;
+  // a no-op unless a tapped pass is being enqueued
+  const size_t xb_dim = B * (size_t)dim * 4, xb_kv = B * (size_t)kv_dim * 4, xb_hid = B * (size_t)hidden * 4;
+  auto PT = [&](bool on, int f, const void* src, size_t bytes) -> int { return on && c->pft_layer >= 0 ? pf_tap_copy(c, f, src, bytes) : 0; };
+  int32_t* const plan = c->pft_plan;
+  auto note_form = [&](int word_f, const F16wForce& fc) {
+    plan[word_f] = fc.used_F;
+    plan[word_f + 1] = fc.used_T;
+    plan[word_f + 2] = fc.used_ksplit;
+  };
+  if (c->pft_layer >= 0) plan[CRABML_HIP_PFPLAN_F16W] = f16w ? 1 : 0;
   for (int l = 0; l < L; l++) {
+    const bool tl = c->pft_layer == l;
     const void* a;
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_IN_X, c->pf_x, xb_dim));
     if (fuse_norm) {
-      a = norm_quant_rows((const float*)c->rms_att[l]->ptr, g.rms_norm_eps, pending_down ? c->pf_tmp : nullptr, c->wq[l],
-                          pending_down ? down_parts : 0);
+      const int in_parts = pending_down ? down_parts : 0;
+      CH_TRY(PT(tl && pending_down, CRABML_HIP_PFTAP_IN_TMP, c->pf_tmp, xb_dim));
+      CH_TRY(PT(tl && in_parts > 0, CRABML_HIP_PFTAP_IN_PARTS, c->pf_split, (size_t)in_parts * xb_dim));
+      if (tl) plan[CRABML_HIP_PFPLAN_IN_PARTS] = in_parts;
+      a = norm_quant_rows((const float*)c->rms_att[l]->ptr, g.rms_norm_eps, pending_down ? c->pf_tmp : nullptr, c->wq[l], in_parts);
       pending_down = false;
     } else {
       norm_rows((const float*)c->rms_att[l]->ptr, g.rms_norm_eps);  // llama2.rs:230-234
       a = quant_rows(c->pf_xn, dim, c->pf_act_dim, c->wq[l]);
     }
+    if (tl) plan[CRABML_HIP_PFPLAN_NORM_KERNEL] = fuse_norm ? norm_kernel : 0;
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_N1_X, c->pf_x, xb_dim));
+    CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_N1_ACT, c->pf_act_dim, B * ald.total));
+    F16wForce fc_qkv{}, fc_wo{}, fc_gu{}, fc_down{};  // (all zero: the launcher's own choice; read back for the plan)
     bool qkv_done = false;  // llama2.rs:244-246
     if (f16w && gemm_f16w_takes(dev, c->wq[l], c->qt) && c->wk[l]->dtype == c->wq[l]->dtype && c->wv[l]->dtype == c->wq[l]->dtype) {
       // the three GEMMs of the same rhs as ONE launch (the 1024-row k / v matrices alone leave most of the chip idle)
       rows_to_f16(c->wq[l], a, dim);
+      CH_TRY(PT(tl, CRABML_HIP_PFTAP_N1_XH, c->pf_xh, B * (size_t)dim * 2));
       const crabml_hip_buf* ws[3] = {c->wq[l], c->wk[l], c->wv[l]};
       const size_t ms[3] = {(size_t)dim, (size_t)kv_dim, (size_t)kv_dim};
       float* outs[3] = {c->pf_q, c->pf_k, c->pf_v};
-      qkv_done = launch_gemm_f16w(dev, ws, ms, 3, (size_t)dim, c->pf_xh, B, outs, c->pf_split, c->pf_split_floats);
+      qkv_done = launch_gemm_f16w(dev, ws, ms, 3, (size_t)dim, c->pf_xh, B, outs, c->pf_split, c->pf_split_floats, nullptr, nullptr, nullptr,
+                                  nullptr, tl ? &fc_qkv : nullptr);
     }
     if (!qkv_done) {
-      CH_TRY(gemm(c->wq[l], dim, dim, a, c->pf_q));
+      CH_TRY(gemm(c->wq[l], dim, dim, a, c->pf_q, nullptr, tl ? &fc_qkv : nullptr, tl ? CRABML_HIP_PFTAP_N1_XH : -1));
       CH_TRY(gemm(c->wk[l], kv_dim, dim, a, c->pf_k));
       CH_TRY(gemm(c->wv[l], kv_dim, dim, a, c->pf_v));
     }
+    if (tl) {
+      plan[CRABML_HIP_PFPLAN_QKV_ONE] = qkv_done ? 1 : 0;
+      note_form(CRABML_HIP_PFPLAN_QKV_F, fc_qkv);
+    }
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_Q, c->pf_q, xb_dim));
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_K, c->pf_k, xb_kv));
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_V, c->pf_v, xb_kv));
     QkvEpi e{c->pf_qr, c->kc[l], c->vc[l], c->rope, pos_d, 1.0f / std::sqrt((float)hd), dim, kv_dim, hd,
              (int)g.rope_dim, c->npairs, seq_cap, kv16 ? 1 : 0};
     const int pairs = (dim + 2 * kv_dim) / 2;
     with_qkv_epi(c, e, l, [&](auto ep) {
       k_qkv_epi_rows<QkvArchOf<decltype(ep)>::value><<<dim3((pairs + 255) / 256, rows), 256, 0, st>>>(c->pf_q, c->pf_k, c->pf_v, ep);
     });
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_QR, c->pf_qr, xb_dim));
     int along = 0;
+    int attn_kernel = 0;  // (prefill tap: CRABML_HIP_PFPLAN_ATTN_KERNEL)
     // (a pass whose every row sees fewer cached positions than the decode step's switch to the f32 kernels -- attn_long_from --
     // keeps the exact tile kernel, so that prefill(prompt) and a token loop over the same short prompt agree bit for bit)
     if (c->attn_flash_rows && kv16 && pos0 + B >= c->attn_long_from) {
@@ -1474,13 +1538,17 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       flash_rows_kernel(hd)<<<fg, 512, flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
                                                                         (const unsigned short*)c->vc[l], pos_d, c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
       along = 1;
+      attn_kernel = 1;
     } else if (!launch_attn_tile(c, l, (int)B, (int)pos0)) {
       along = launch_attn_long_rows(c, l, (int)B);  // past 1024 positions: the long-context kernels, rows in grid.y
       if (along < 0) return CRABML_HIP_UNEXPECTED;
+      attn_kernel = 3;
     } else {
       along = 1;
+      attn_kernel = 2;
     }
     if (!along) {  // unusual shapes (f32 cache past 1024 positions, odd group sizes): one workgroup per (head, row)
+      attn_kernel = 4;
       const size_t attn_lds = (size_t)(seq_cap + hd) * sizeof(float);
       with_const_else<0, 1>(kv16, [&](auto kv) {
         k_attn<decltype(kv)::value != 0><<<dim3(n_heads, rows), 256, attn_lds, st>>>(c->pf_qr, c->kc[l], c->vc[l], pos_d,
@@ -1489,9 +1557,19 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
                                                                                      dev->strict_order ? 256 : 0);
       });
     }
+    if (tl) plan[CRABML_HIP_PFPLAN_ATTN_KERNEL] = attn_kernel;
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_ATTN, c->pf_attn, xb_dim));
     a = quant_rows(c->pf_attn, dim, c->pf_act_dim, c->wo[l]);
+    CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_ATTN_ACT, c->pf_act_dim, B * ald.total));
     int wo_parts = 0;
-    CH_TRY(gemm(c->wo[l], dim, dim, a, c->pf_tmp, fuse_norm ? &wo_parts : nullptr));  // llama2.rs:600
+    CH_TRY(gemm(c->wo[l], dim, dim, a, c->pf_tmp, fuse_norm ? &wo_parts : nullptr, tl ? &fc_wo : nullptr,
+                tl ? CRABML_HIP_PFTAP_ATTN_XH : -1));  // llama2.rs:600
+    if (tl) {
+      plan[CRABML_HIP_PFPLAN_WO_PARTS] = wo_parts;
+      note_form(CRABML_HIP_PFPLAN_WO_F, fc_wo);
+    }
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_WO_TMP, c->pf_tmp, xb_dim));
+    CH_TRY(PT(tl && wo_parts > 0, CRABML_HIP_PFTAP_WO_PARTS, c->pf_split, (size_t)wo_parts * xb_dim));
     if (fuse_norm) {
       a = norm_quant_rows((const float*)c->rms_ffn[l]->ptr, 1e-5f, c->pf_tmp, c->gate[l], wo_parts);  // x += wo out (:266), FFN norm (:611), quantize
     } else {
@@ -1499,12 +1577,15 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       norm_rows((const float*)c->rms_ffn[l]->ptr, 1e-5f);  // llama2.rs:611
       a = quant_rows(c->pf_xn, dim, c->pf_act_dim, c->gate[l]);
     }
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_N2_X, c->pf_x, xb_dim));
+    CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_N2_ACT, c->pf_act_dim, B * ald.total));
     bool gu_done = false;  // llama2.rs:620-630
     int h_done = 0;        // the launch stored h = silu(g) * u (pf_g) instead of g and u
     if (f16w && gemm_f16w_takes(dev, c->gate[l], c->qt) && c->up[l]->dtype == c->gate[l]->dtype) {
       // gate and up as ONE launch: 2 x 448 workgroups fill the last round of the chip better than 448 twice -- and, where 64-row tiles
       // of both cover the chip, with SiLU * mul as the epilogue (a wave holds the same 16 rows of both matrices)
       rows_to_f16(c->gate[l], a, dim);
+      CH_TRY(PT(tl, CRABML_HIP_PFTAP_N2_XH, c->pf_xh, B * (size_t)dim * 2));
       const crabml_hip_buf* ws[2] = {c->gate[l], c->up[l]};
       const size_t ms[2] = {(size_t)hidden, (size_t)hidden};
       float* outs[2] = {c->pf_g, c->pf_u};
@@ -1523,7 +1604,8 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
         hq.ovf = ovf;
       }
       gu_done = launch_gemm_f16w(dev, ws, ms, 2, (size_t)dim, c->pf_xh, B, outs, c->pf_split, c->pf_split_floats,
-                                 epi ? (const unsigned short*)dev->exp_table : nullptr, epi ? &h_done : nullptr, nullptr, &hq);
+                                 epi ? (const unsigned short*)dev->exp_table : nullptr, epi ? &h_done : nullptr, nullptr, &hq,
+                                 tl ? &fc_gu : nullptr);
       if (h_done == 2) {
         a = c->pf_act_hid;
         if (hq.xh) std::swap(c->pf_xh, c->pf_xh2);  // (ffn_down's GEMM reads what this launch wrote)
@@ -1532,9 +1614,16 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       }
     }
     if (!gu_done) {
-      CH_TRY(gemm(c->gate[l], hidden, dim, a, c->pf_g));
+      CH_TRY(gemm(c->gate[l], hidden, dim, a, c->pf_g, nullptr, tl ? &fc_gu : nullptr, tl ? CRABML_HIP_PFTAP_N2_XH : -1));
       CH_TRY(gemm(c->up[l], hidden, dim, a, c->pf_u));
     }
+    if (tl) {
+      plan[CRABML_HIP_PFPLAN_GU_ONE] = gu_done ? 1 : 0;
+      plan[CRABML_HIP_PFPLAN_H_DONE] = h_done;
+      note_form(CRABML_HIP_PFPLAN_GU_F, fc_gu);
+    }
+    CH_TRY(PT(tl && h_done != 2, CRABML_HIP_PFTAP_G, c->pf_g, xb_hid));
+    CH_TRY(PT(tl && h_done == 0, CRABML_HIP_PFTAP_U, c->pf_u, xb_hid));
     if (h_done == 2) {
       // (quantized by the launch itself)
     } else if (h_done) {  // h sits in pf_g: quantize it (the quantizer launch's arithmetic is quant_lane32's, bit for bit)
@@ -1560,20 +1649,32 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
                                                                                  c->pf_g, (int)(B * hidden));
       a = quant_rows(c->pf_g, hidden, c->pf_act_hid, c->down[l]);
     }
-    CH_TRY(gemm(c->down[l], dim, hidden, a, c->pf_tmp, fuse_norm && l + 1 < L ? &down_parts : nullptr));  // llama2.rs:633-636
-    if (fuse_norm && l + 1 < L)
+    CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_HID_ACT, c->pf_act_hid, B * alh.total));
+    CH_TRY(gemm(c->down[l], dim, hidden, a, c->pf_tmp, fuse_norm && l + 1 < L ? &down_parts : nullptr, tl ? &fc_down : nullptr,
+                tl ? CRABML_HIP_PFTAP_HID_XH : -1));  // llama2.rs:633-636
+    if (tl) {
+      plan[CRABML_HIP_PFPLAN_DOWN_PARTS] = fuse_norm && l + 1 < L ? down_parts : 0;
+      note_form(CRABML_HIP_PFPLAN_DOWN_F, fc_down);
+    }
+    CH_TRY(PT(tl, CRABML_HIP_PFTAP_DOWN_TMP, c->pf_tmp, xb_dim));
+    CH_TRY(PT(tl && fuse_norm && l + 1 < L && down_parts > 0, CRABML_HIP_PFTAP_DOWN_PARTS, c->pf_split, (size_t)down_parts * xb_dim));
+    if (fuse_norm && l + 1 < L) {
       pending_down = true;  // added by the next layer's norm launch
-    else
+    } else {
       k_res_epi<<<(unsigned)(((size_t)B * dim + 255) / 256), 256, 0, st>>>(c->pf_tmp, c->pf_x, (int)(B * dim), 1);
+      CH_TRY(PT(tl, CRABML_HIP_PFTAP_DOWN_X, c->pf_x, xb_dim));
+    }
   }
   if (want_logits) {  // final rmsnorm + classifier of the last row only (llama2.rs:274-278, 199-208)
     CH_HIP(dev, hipMemcpyAsync(c->x, c->pf_x + (B - 1) * (size_t)dim, (size_t)dim * 4, hipMemcpyDeviceToDevice, st));
+    CH_TRY(PT(true, CRABML_HIP_PFTAP_LAST_X, c->x, (size_t)dim * 4));
     launch_norm_f32(st, c->x, nullptr, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, half);
     const void* act = c->xn;
     if (c->out_qt != CRABML_HIP_F32) {
       launch_quantize_act(st, c->out_qt, c->xn, (size_t)dim, c->act_dim);
       act = c->act_dim;
     }
+    CH_TRY(PT(true, CRABML_HIP_PFTAP_CLS_ACT, act, c->out_qt != CRABML_HIP_F32 ? act_layout(c->out_qt, (size_t)dim).total : (size_t)dim * 4));
     CH_TRY(strict ? launch_gemv_strict(dev, c->output, g.vocab_size, dim, act, 1, c->logits)
                   : launch_gemv(dev, c->output, g.vocab_size, dim, act, 1, c->logits, nullptr));
   }
@@ -1585,16 +1686,51 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
 // few massive channels of a real checkpoint; the rows' f16 scales reach about 8.3e6): the writers of B' raise pf_ovf, read here once
 // per chunk, and a chunk that raised it is computed again from its token embeddings with the int8 GEMMs -- it overwrites its own KV
 // rows and logits; the caller advances kv_len once.  Chunks that do not overflow keep their bits.
-int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t pos0, bool want_logits) {
+// tap_layer >= 0 (crabml_hip_llama_debug_prefill_tap): each pass is enqueued with the copies of that layer switched on, the plan and the
+// scratch area started afresh -- after a recomputation they hold the recomputation's
+int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t pos0, bool want_logits, int tap_layer = -1) {
   bool f16w = false;
-  CH_TRY(prefill_chunk_pass(c, tokens, B, pos0, want_logits, true, &f16w));
+  auto pass = [&](bool allow_f16w, int recomputed) -> int {
+    if (tap_layer >= 0) {
+      c->pft_used = 0;
+      for (int f = 0; f < CRABML_HIP_PFTAP_FIELDS; f++) c->pft_off[f] = c->pft_len[f] = 0;
+      for (auto& v : c->pft_plan) v = 0;
+      c->pft_plan[CRABML_HIP_PFPLAN_N_CU] = c->dev->n_cu;
+      c->pft_plan[CRABML_HIP_PFPLAN_ROWS] = (int32_t)B;
+      c->pft_plan[CRABML_HIP_PFPLAN_POS0] = (int32_t)pos0;
+      c->pft_plan[CRABML_HIP_PFPLAN_RECOMPUTED] = recomputed;
+      c->pft_layer = tap_layer;
+    }
+    const int rc = prefill_chunk_pass(c, tokens, B, pos0, want_logits, allow_f16w, &f16w);
+    c->pft_layer = -1;
+    return rc;
+  };
+  CH_TRY(pass(true, 0));
   if (!f16w) return 0;
   int h = 0;
   CH_HIP(c->dev, hipMemcpyAsync(&h, c->pf_ovf, sizeof h, hipMemcpyDeviceToHost, c->dev->stream));
   CH_HIP(c->dev, hipStreamSynchronize(c->dev->stream));
   if (h == 0) return 0;
   CH_HIP(c->dev, hipMemsetAsync(c->pf_ovf, 0, sizeof h, c->dev->stream));
-  return prefill_chunk_pass(c, tokens, B, pos0, want_logits, false, &f16w);
+  return pass(false, 1);
+}
+
+// what crabml_hip_llama_prefill (and the tap of one of its passes) checks before anything is enqueued (llama2.rs:117-122)
+int prefill_check(crabml_hip_llama* c, const uint32_t* tokens, size_t n) {
+  crabml_hip_device* dev = c->dev;
+  if (n == 0) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama prefill: expected at least 1 prompt token");
+  for (size_t i = 0; i < n; i++)
+    if (tokens[i] >= c->cfg.vocab_size) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: token %u out of range", tokens[i]);
+  if (c->kv_len + n > c->cfg.seq_len)
+    CH_BAIL(dev, CRABML_HIP_TENSOR_ERROR, "llama: %zu prompt tokens do not fit the kv cache (%zu of %zu used)", n, c->kv_len, c->cfg.seq_len);
+  return 0;
+}
+// rows per pass: 1024 on the fast device (8B shape Q4_0: 31.5k / 38k / 45k / 46k prompt tok/s at 256 / 512 / 1024 / 2048 rows -- the
+// narrow GEMMs get their column tiles; the row buffers are ~0.5 GB), 512 on the strict one (its exact attention tiles hold 1024
+// positions in LDS), never more than the cache holds
+size_t prefill_chunk_rows(const crabml_hip_llama* c) {
+  const size_t chunk0 = c->cfg.prefill_chunk ? c->cfg.prefill_chunk : c->dev->strict_order ? 512 : 1024;
+  return chunk0 < c->cfg.seq_len ? chunk0 : c->cfg.seq_len;
 }
 
 int set_state(crabml_hip_llama* c, size_t token, size_t pos, int step, const unsigned* serial = nullptr) {
@@ -2437,20 +2573,12 @@ int crabml_hip_llama_prefill(crabml_hip_llama_t* c, const uint32_t* tokens, size
   CH_LIVE(dev);
   CH_USE(dev);
   CH_FLUSH(dev);
-  if (n == 0) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama prefill: expected at least 1 prompt token");  // llama2.rs:117-122
-  for (size_t i = 0; i < n; i++)
-    if (tokens[i] >= c->cfg.vocab_size) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: token %u out of range", tokens[i]);
-  if (c->kv_len + n > c->cfg.seq_len)
-    CH_BAIL(dev, CRABML_HIP_TENSOR_ERROR, "llama: %zu prompt tokens do not fit the kv cache (%zu of %zu used)", n, c->kv_len, c->cfg.seq_len);
+  CH_TRY(prefill_check(c, tokens, n));
   if (c->tp > 1) {  // token loop
     for (size_t i = 0; i < n; i++) CH_TRY(crabml_hip_llama_forward(c, tokens[i], c->kv_len, i + 1 == n ? logits : nullptr));
     return 0;
   }
-  // rows per pass: 1024 on the fast device (8B shape Q4_0: 31.5k / 38k / 45k / 46k prompt tok/s at 256 / 512 / 1024 / 2048 rows -- the
-  // narrow GEMMs get their column tiles; the row buffers are ~0.5 GB), 512 on the strict one (its exact attention tiles hold 1024
-  // positions in LDS), never more than the cache holds
-  const size_t chunk0 = c->cfg.prefill_chunk ? c->cfg.prefill_chunk : dev->strict_order ? 512 : 1024;
-  const size_t chunk = chunk0 < c->cfg.seq_len ? chunk0 : c->cfg.seq_len;
+  const size_t chunk = prefill_chunk_rows(c);
   CH_TRY(prefill_alloc(c, chunk));
   for (size_t i = 0; i < n; i += chunk) {
     const size_t B = n - i < chunk ? n - i : chunk;
@@ -2633,6 +2761,104 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
           memcpy(b + i * 292, src + al.off_d + i * 4, 4);
           memcpy(b + i * 292 + 4, src + i * 256, 256);
           memcpy(b + i * 292 + 260, src + al.off_aux + i * 32, 32);
+        }
+      }
+    }
+    dir[f].bytes = out_bytes;
+    at += align_up(out_bytes, 8);
+  }
+  return 0;
+}
+
+// parity hook (crabml_hip_debug.h): one chunk pass of the prompt path with the row buffers of one layer copied out between its launches
+int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* c, const uint32_t* tokens, size_t n, size_t layer, float* logits, void* dst,
+                                       size_t dst_bytes, crabml_hip_tap_entry_t* dir, size_t* need) {
+  if (!c || (!tokens && n) || (dst && !dir) || (!dst && !need)) return CRABML_HIP_BAD_INPUT;
+  crabml_hip_device* dev = c->dev;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  if (c->tp > 1 || dev->strict_order || c->ext_kv || !(c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1) ||
+      !(c->wtype == CRABML_HIP_Q4_0 || c->wtype == CRABML_HIP_Q8_0 || c->wtype == CRABML_HIP_Q4_1))
+    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama debug_prefill_tap: only Q4_0 / Q8_0 / Q4_1 layers of the fast prompt pass on one device");
+  if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_prefill_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
+  CH_TRY(prefill_check(c, tokens, n));
+  const size_t chunk = prefill_chunk_rows(c);
+  if (n > chunk) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_prefill_tap: %zu rows, one chunk pass holds %zu", n, chunk);
+  const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim, kv_dim = (size_t)c->kv_dim_l;
+  const uint32_t qt = c->qt, cq = c->out_qt;
+  const bool cls_q = cq == CRABML_HIP_Q8_0 || cq == CRABML_HIP_Q8_1 || cq == CRABML_HIP_Q8_K;
+  struct Fld {
+    uint32_t qtype;
+    size_t cols;  // 0: raw bytes (f32 values, f16 planes, plan words)
+  };
+  Fld fld[CRABML_HIP_PFTAP_FIELDS];
+  for (auto& f : fld) f = Fld{CRABML_HIP_F32, 0};
+  fld[CRABML_HIP_PFTAP_N1_ACT] = fld[CRABML_HIP_PFTAP_ATTN_ACT] = fld[CRABML_HIP_PFTAP_N2_ACT] = Fld{qt, dim};
+  fld[CRABML_HIP_PFTAP_HID_ACT] = Fld{qt, hidden};
+  for (int f : {CRABML_HIP_PFTAP_N1_XH, CRABML_HIP_PFTAP_ATTN_XH, CRABML_HIP_PFTAP_N2_XH, CRABML_HIP_PFTAP_HID_XH}) fld[f].qtype = CRABML_HIP_F16;
+  if (cls_q) fld[CRABML_HIP_PFTAP_CLS_ACT] = Fld{cq, dim};
+  // the scratch area, in the device's layout: ten (n, dim) f32 buffers, three sets of up to 7 k pieces, k and v, g and u, three sets of
+  // act_dim planes and one of act_hid, their f16 planes, the last row and the classifier's input; every field 256-aligned
+  const size_t adb = act_layout(qt, dim).total, ahb = act_layout(qt, hidden).total;
+  const size_t cls_raw = cls_q ? act_layout(cq, dim).total : dim * 4;
+  const size_t raw_cap = (10 + 21) * n * dim * 4 + 2 * n * kv_dim * 4 + 2 * n * hidden * 4 + 3 * n * adb + n * ahb + 3 * n * dim * 2 +
+                         n * hidden * 2 + dim * 4 + cls_raw + 256 * (size_t)CRABML_HIP_PFTAP_FIELDS + sizeof c->pft_plan;
+  if (need) *need = raw_cap;  // (the host's copy has the planes re-packed as blocks: never larger)
+  if (!dst) return 0;
+  if (dst_bytes < raw_cap) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_prefill_tap: dst holds %zu bytes, %zu needed", dst_bytes, raw_cap);
+  CH_TRY(prefill_alloc(c, chunk));
+  if (c->pft_cap < raw_cap) {  // (a shorter area of an earlier tap stays with the context until it is destroyed)
+    c->pft_cap = 0;
+    CH_TRY(dalloc(c, raw_cap, (void**)&c->pft_buf));
+    c->pft_cap = raw_cap;
+  }
+  CH_TRY(prefill_chunk(c, tokens, n, c->kv_len, true, (int)layer));
+  c->kv_len += n;
+  std::vector<uint8_t> h(c->pft_used ? c->pft_used : 1);
+  if (logits) CH_HIP(dev, hipMemcpyAsync(logits, c->logits, c->cfg.vocab_size * 4, hipMemcpyDeviceToHost, dev->stream));
+  if (c->pft_used) CH_HIP(dev, hipMemcpyAsync(h.data(), c->pft_buf, c->pft_used, hipMemcpyDeviceToHost, dev->stream));
+  CH_HIP(dev, hipStreamSynchronize(dev->stream));
+  uint8_t* o = (uint8_t*)dst;
+  size_t at = 0;
+  for (int f = 0; f < CRABML_HIP_PFTAP_FIELDS; f++) {
+    dir[f] = crabml_hip_tap_entry_t{at, 0, fld[f].qtype, 0};
+    if (f == CRABML_HIP_PFTAP_PLAN) {  // host words, not a device buffer
+      if (at + sizeof c->pft_plan > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: the plan does not fit dst");
+      memcpy(o + at, c->pft_plan, sizeof c->pft_plan);
+      dir[f].bytes = sizeof c->pft_plan;
+      at += align_up(sizeof c->pft_plan, 8);
+      continue;
+    }
+    if (c->pft_len[f] == 0) continue;
+    const uint8_t* src = h.data() + c->pft_off[f];
+    size_t out_bytes = c->pft_len[f];
+    if (fld[f].cols == 0) {
+      if (at + out_bytes > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: field %d does not fit dst", f);
+      memcpy(o + at, src, out_bytes);
+    } else {  // rows of planes -> rows of blocks, as crabml_hip_debug_quantize lays them out
+      const uint32_t t = fld[f].qtype;
+      const size_t cols = fld[f].cols, nb = cols / block_elems(t), nrows = f == CRABML_HIP_PFTAP_CLS_ACT ? 1 : n;
+      const ActLayout al = act_layout(t, cols);
+      out_bytes = nrows * nb * block_bytes(t);
+      if (c->pft_len[f] != nrows * al.total || at + out_bytes > dst_bytes)
+        CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: field %d has an unexpected size", f);
+      for (size_t r = 0; r < nrows; r++) {
+        const uint8_t* s = src + r * al.total;
+        uint8_t* b = o + at + r * nb * block_bytes(t);
+        for (size_t i = 0; i < nb; i++) {
+          if (t == CRABML_HIP_Q8_0) {
+            memcpy(b + i * 34, s + al.off_d + i * 2, 2);
+            memcpy(b + i * 34 + 2, s + i * 32, 32);
+          } else if (t == CRABML_HIP_Q8_1) {
+            memcpy(b + i * 36, s + al.off_d + i * 2, 2);
+            memcpy(b + i * 36 + 2, s + al.off_aux + i * 2, 2);
+            memcpy(b + i * 36 + 4, s + i * 32, 32);
+          } else {
+            memcpy(b + i * 292, s + al.off_d + i * 4, 4);
+            memcpy(b + i * 292 + 4, s + i * 256, 256);
+            memcpy(b + i * 292 + 260, s + al.off_aux + i * 32, 32);
+          }
         }
       }
     }

@@ -190,6 +190,23 @@ class HipLlamaRunner {
     }
     return t;
   }
+  // crabml_hip_llama_debug_prefill_tap: one chunk pass of `tokens` at the current cache length with layer `layer` tapped
+  // (fields: CRABML_HIP_PFTAP_*)
+  Tap debug_prefill_tap(const std::vector<uint32_t>& tokens, size_t layer) {
+    size_t need = 0;
+    device_->check(crabml_hip_llama_debug_prefill_tap(ctx_, tokens.data(), tokens.size(), layer, nullptr, nullptr, 0, nullptr, &need));
+    std::vector<uint8_t> buf(need);
+    crabml_hip_tap_entry_t dir[CRABML_HIP_PFTAP_FIELDS];
+    Tap t;
+    t.logits.resize(conf_.vocab_size);
+    device_->check(crabml_hip_llama_debug_prefill_tap(ctx_, tokens.data(), tokens.size(), layer, t.logits.data(), buf.data(), buf.size(), dir,
+                                                      nullptr));
+    for (int f = 0; f < CRABML_HIP_PFTAP_FIELDS; f++) {
+      t.qtype.push_back(dir[f].qtype);
+      t.field.emplace_back(buf.begin() + dir[f].offset, buf.begin() + dir[f].offset + dir[f].bytes);
+    }
+    return t;
+  }
   // one decode step of a single-device simulated tp group (crabml_hip_llama_tp_sim_forward); logits from rank 0
   static std::vector<float> tp_sim_forward(const std::vector<HipLlamaRunner*>& ranks, size_t token, size_t pos) {
     if (ranks.empty()) throw Error(ErrorKind::BadInput, "tp_sim_forward: no ranks");

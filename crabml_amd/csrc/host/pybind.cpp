@@ -550,6 +550,43 @@ PYBIND11_MODULE(_host, m) {
         }
         d["qtype"] = qt;
         return d;
+      })
+      // one chunk pass of `tokens` at the current cache length with `layer` tapped (crabml_hip_llama_debug_prefill_tap): {"logits": f32,
+      // name: f32 array | uint16 f16 planes | uint8 blocks, "qtype": {name: type}, "plan": {word: value}}; every field holds all rows
+      .def("debug_prefill_tap", [](HipLlamaRunner& r, const std::vector<uint32_t>& tokens, size_t layer) {
+        static const char* names[CRABML_HIP_PFTAP_FIELDS] = {
+            "in.x", "in.tmp", "in.parts", "n1.x", "n1.act", "n1.xh", "q", "k", "v", "qr", "attn", "attn.act", "attn.xh", "wo.tmp", "wo.parts",
+            "n2.x", "n2.act", "n2.xh", "g", "u", "hid.act", "hid.xh", "down.tmp", "down.parts", "down.x", "last.x", "cls.act", "plan"};
+        static const char* words[CRABML_HIP_PFTAP_PLAN_WORDS] = {
+            "n_cu", "rows", "pos0", "f16w", "recomputed", "norm_kernel", "in_parts", "qkv_one", "gu_one", "h_done", "wo_parts", "down_parts",
+            "qkv_F", "qkv_T", "qkv_ksplit", "wo_F", "wo_T", "wo_ksplit", "gu_F", "gu_T", "gu_ksplit", "down_F", "down_T", "down_ksplit",
+            "attn_kernel"};
+        HipLlamaRunner::Tap t;
+        {
+          py::gil_scoped_release rel;
+          t = r.debug_prefill_tap(tokens, layer);
+        }
+        py::dict d, qt;
+        d["logits"] = py::array_t<float>(t.logits.size(), t.logits.data());
+        for (int f = 0; f < CRABML_HIP_PFTAP_FIELDS; f++) {
+          const auto& b = t.field[f];
+          if (b.empty()) continue;
+          if (f == CRABML_HIP_PFTAP_PLAN) {
+            py::dict p;
+            for (int i = 0; i < CRABML_HIP_PFTAP_PLAN_WORDS; i++) p[words[i]] = ((const int32_t*)b.data())[i];
+            d[names[f]] = p;
+            continue;
+          }
+          if (t.qtype[f] == CRABML_HIP_F32)
+            d[names[f]] = py::array_t<float>(b.size() / 4, (const float*)b.data());
+          else if (t.qtype[f] == CRABML_HIP_F16)
+            d[names[f]] = py::array_t<uint16_t>(b.size() / 2, (const uint16_t*)b.data());
+          else
+            d[names[f]] = py::array_t<uint8_t>(b.size(), b.data());
+          qt[names[f]] = t.qtype[f];
+        }
+        d["qtype"] = qt;
+        return d;
       });
 
   py::class_<Runner>(m, "Llama2Runner")

@@ -190,6 +190,86 @@ typedef struct crabml_hip_tap_entry {
 int crabml_hip_llama_debug_tap(crabml_hip_llama_t* ctx, size_t token, size_t pos, size_t layer, float* logits, void* dst,
                                size_t dst_bytes, crabml_hip_tap_entry_t* dir, size_t* need);
 
+/* parity hook: ONE chunk pass of the batched prompt path (prefill_chunk_pass) for `n` tokens appended at the current cache length
+ * (pos0 = crabml_hip_llama_kv_len) -- the same checks and the same effect on the context as crabml_hip_llama_prefill, including the
+ * recomputation of a chunk whose f16 rows overflowed --, with the row buffers of layer `layer` (all n rows of each) copied out as each
+ * launch of that layer left them: stream-ordered device-to-device copies into a scratch area (allocated on the first prefill tap of a
+ * context, grown when a longer pass is tapped) placed between the launches, brought to the host after the pass.  n larger than the
+ * context's chunk capacity (prefill_chunk, else 1024, never more than seq_len): CRABML_HIP_BAD_INPUT -- multi-chunk situations are made
+ * by calling prefill / forward first.  Serves Q4_0 / Q8_0 / Q4_1 layers (Q8_0 / Q8_1 rows) on one fast device, Llama and Qwen2, f16 and
+ * f32 cache; K-quant layers, tensor-parallel ranks, the strict-order device and a context on the runner's own KV cache return
+ * CRABML_HIP_NOT_IMPLEMENTED.  dst / dir / need as for crabml_hip_llama_debug_tap; a field the pass did not produce has bytes = 0.
+ * f32 fields are [n][cols] floats.  Quantized rows come back as n rows of blocks in the reference's byte layout (as debug_tap).  The
+ * XH fields are the rows' pre-scaled f16 planes B' ([n][cols] halfs, in the GEMM's k-slot order: within a 32-element block the order
+ * is the kernel's own business) as the GEMM that reads them next finds them; 0 bytes in an int8 / GEMV pass.  PARTS fields are
+ * `parts` consecutive [n][dim] f32 pieces of a GEMM cut along k whose sum was left to the norm launch (piece 0 is the TMP field).
+ * The K / V rows come through crabml_hip_llama_debug_kv. */
+enum {
+  CRABML_HIP_PFTAP_IN_X = 0,       /* what the layer's first norm launch reads: pf_x (f32, dim), */
+  CRABML_HIP_PFTAP_IN_TMP = 1,     /*   the previous layer's ffn_down output not yet added (f32, dim; 0 bytes when none is pending), */
+  CRABML_HIP_PFTAP_IN_PARTS = 2,   /*   and its k pieces 1.. (PLAN_IN_PARTS of them) */
+  CRABML_HIP_PFTAP_N1_X = 3,       /* what it leaves: pf_x, */
+  CRABML_HIP_PFTAP_N1_ACT = 4,     /*   the act_dim planes (layer row type), */
+  CRABML_HIP_PFTAP_N1_XH = 5,      /*   B' as the q|k|v GEMM reads it */
+  CRABML_HIP_PFTAP_Q = 6,          /* after the q|k|v GEMM(s): pf_q (dim), */
+  CRABML_HIP_PFTAP_K = 7,          /*   pf_k (kv_dim), */
+  CRABML_HIP_PFTAP_V = 8,          /*   pf_v (kv_dim) */
+  CRABML_HIP_PFTAP_QR = 9,         /* after k_qkv_epi_rows: pf_qr (roped, scaled q; dim) */
+  CRABML_HIP_PFTAP_ATTN = 10,      /* after attention: pf_attn (dim), */
+  CRABML_HIP_PFTAP_ATTN_ACT = 11,  /*   then its planes */
+  CRABML_HIP_PFTAP_ATTN_XH = 12,   /*   and B' as wo's GEMM reads it */
+  CRABML_HIP_PFTAP_WO_TMP = 13,    /* after wo: pf_tmp (dim; piece 0 when PLAN_WO_PARTS > 0), */
+  CRABML_HIP_PFTAP_WO_PARTS = 14,  /*   the pieces left to the norm launch */
+  CRABML_HIP_PFTAP_N2_X = 15,      /* after the residual add + FFN norm: pf_x, */
+  CRABML_HIP_PFTAP_N2_ACT = 16,    /*   the act_dim planes, */
+  CRABML_HIP_PFTAP_N2_XH = 17,     /*   B' as the gate|up GEMM reads it */
+  CRABML_HIP_PFTAP_G = 18,         /* after gate|up: pf_g (hidden): g, or h = silu(g) * u when PLAN_H_DONE == 1; 0 bytes when PLAN_H_DONE == 2 */
+  CRABML_HIP_PFTAP_U = 19,         /*   pf_u (hidden); 0 bytes when PLAN_H_DONE != 0 */
+  CRABML_HIP_PFTAP_HID_ACT = 20,   /* the act_hid planes (hidden) */
+  CRABML_HIP_PFTAP_HID_XH = 21,    /*   and B' as ffn_down's GEMM reads it */
+  CRABML_HIP_PFTAP_DOWN_TMP = 22,  /* after ffn_down: pf_tmp (piece 0 when PLAN_DOWN_PARTS > 0), */
+  CRABML_HIP_PFTAP_DOWN_PARTS = 23,/*   the pieces left to the next layer's norm launch */
+  CRABML_HIP_PFTAP_DOWN_X = 24,    /*   pf_x where the residual was added by k_res_epi right behind it (the last layer; every layer without row fusion) */
+  CRABML_HIP_PFTAP_LAST_X = 25,    /* any `layer`: the row the final norm reads (f32, dim), */
+  CRABML_HIP_PFTAP_CLS_ACT = 26,   /*   what the classifier reads (one row of the classifier's row type; f32 for an F32 / F16 classifier) */
+  CRABML_HIP_PFTAP_PLAN = 27,      /* CRABML_HIP_PFTAP_PLAN_WORDS int32 words (below) */
+  CRABML_HIP_PFTAP_FIELDS = 28
+};
+/* the words of CRABML_HIP_PFTAP_PLAN, written by prefill_chunk_pass where it decides (0 where the tapped layer never got there) */
+enum {
+  CRABML_HIP_PFPLAN_N_CU = 0,        /* compute units of the device */
+  CRABML_HIP_PFPLAN_ROWS = 1,        /* rows of the pass */
+  CRABML_HIP_PFPLAN_POS0 = 2,        /* position of row 0 */
+  CRABML_HIP_PFPLAN_F16W = 3,        /* 1: the weight-stationary f16 GEMM; 0: the int8 matrix-core GEMM / the GEMV */
+  CRABML_HIP_PFPLAN_RECOMPUTED = 4,  /* 1: the tapped pass is the int8 recomputation after an f16 pass raised the overflow flag */
+  CRABML_HIP_PFPLAN_NORM_KERNEL = 5, /* the layer's FIRST norm launch (attention norm), noted in the arm that launches it: 0 separate launches
+                                        (k_res_epi, k_norm_f32_rows, the quantizer), 1 k_norm_quant_rows, 2 k_norm_quant_rows_h, 3 k_norm_quant_rows_w
+                                        (4 k_norm_quant_rows_k: K-quant rows, which the tap refuses, so never returned).  The FFN norm's kernel is
+                                        not recorded: it goes through the same arms with wo's pending output and pieces */
+  CRABML_HIP_PFPLAN_IN_PARTS = 6,    /* k pieces the layer's first norm launch added to the pending ffn_down output */
+  CRABML_HIP_PFPLAN_QKV_ONE = 7,     /* 1: q | k | v as one GEMM launch */
+  CRABML_HIP_PFPLAN_GU_ONE = 8,      /* 1: gate | up as one GEMM launch */
+  CRABML_HIP_PFPLAN_H_DONE = 9,      /* 0 the launch left g and u, 1 h as f32, 2 h as row planes (+ ffn_down's B') */
+  CRABML_HIP_PFPLAN_WO_PARTS = 10,   /* pieces of wo's GEMM left to the norm launch (0: none cut, or added by the GEMM's own reduce launch) */
+  CRABML_HIP_PFPLAN_DOWN_PARTS = 11, /* ... of ffn_down's */
+  CRABML_HIP_PFPLAN_QKV_F = 12,      /* F (row fragments per wave), T (column tiles per wave), ksplit of the f16 GEMM as launched: q|k|v */
+  CRABML_HIP_PFPLAN_QKV_T = 13,      /*   (three separate launches: q's), */
+  CRABML_HIP_PFPLAN_QKV_KSPLIT = 14,
+  CRABML_HIP_PFPLAN_WO_F = 15,       /*   wo, */
+  CRABML_HIP_PFPLAN_WO_T = 16,
+  CRABML_HIP_PFPLAN_WO_KSPLIT = 17,
+  CRABML_HIP_PFPLAN_GU_F = 18,       /*   gate|up (two separate launches: gate's), */
+  CRABML_HIP_PFPLAN_GU_T = 19,
+  CRABML_HIP_PFPLAN_GU_KSPLIT = 20,
+  CRABML_HIP_PFPLAN_DOWN_F = 21,     /*   ffn_down; all 0 in an int8 / GEMV pass */
+  CRABML_HIP_PFPLAN_DOWN_T = 22,
+  CRABML_HIP_PFPLAN_DOWN_KSPLIT = 23,
+  CRABML_HIP_PFPLAN_ATTN_KERNEL = 24,/* 1 k_attn_flash_rows, 2 the exact tile kernel, 3 the exact long-row kernels, 4 k_attn per (head, row) */
+  CRABML_HIP_PFTAP_PLAN_WORDS = 25
+};
+int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* ctx, const uint32_t* tokens, size_t n, size_t layer, float* logits, void* dst,
+                                       size_t dst_bytes, crabml_hip_tap_entry_t* dir, size_t* need);
+
 /* ---- measurement hook (bench.py `roofline` object) -------------------------------------------------
  * While enabled, every matmul_vec GEMV kernel launch is bracketed by a pair of HIP events recorded on
  * the device's own stream (the stream the kernel runs on); crabml_hip_prof_read() drains them and

@@ -172,13 +172,8 @@ def weight_rows(t, r0, r1):
     raise ValueError(f"weight type {typ}")
 
 
-def row_dots(t, act, chunk=256, drop_last_block=False):
-    """W . x for every row of t against the activation blocks `act`: (exact f64 [rows], bound f64 [rows]) -- the bound of the module
-    docstring for an f32 evaluation of the reference's block expression in ANY order of the blocks.  drop_last_block: the dot
-    without each row's last 32 elements (what a kernel whose block loop stops one early computes; the checker's own tests)"""
-    rows, k = t.shape
-    typ = t.typ
-    exact, bound = np.empty(rows), np.empty(rows)
+def _chunk_dots(w, typ, act, k, drop_last_block):
+    """(exact, bound) of the weight rows `w` (weight_rows) against one row's activation blocks: row_dots' arithmetic"""
     if typ == synth.Q4_1:
         assert act["qt"] == o.Q8_1
         nb = k // 32
@@ -187,16 +182,13 @@ def row_dots(t, act, chunk=256, drop_last_block=False):
             keep[-1] = 0.0
         xq = act["q"].astype(np.float64)
         xd = (act["q"] * act["d"][:, None]).astype(np.float64)
-        for r0 in range(0, rows, chunk):
-            w = weight_rows(t, r0, min(rows, r0 + chunk))
-            sumi = np.einsum("rbi,bi->rb", w["q"], xq)
-            P = (w["d"] * act["d"][None, :]).astype(np.float16).astype(np.float64)  # f16 products, rounded once (the exact product fits f64)
-            M = (w["m"] * act["s"][None, :]).astype(np.float16).astype(np.float64)
-            exact[r0:r0 + chunk] = ((P * sumi + M) * keep).sum(axis=1)
-            deq = np.einsum("rbi,bi->r", np.abs(w["q"] * w["d"][:, :, None] + w["m"][:, :, None]), np.abs(xd))
-            terms = (np.abs(P * sumi) + np.abs(M)).sum(axis=1)
-            bound[r0:r0 + chunk] = np.minimum(8 * GEMV_REL * deq, (nb + C_DOT) * U * terms)
-        return exact, bound
+        sumi = np.einsum("rbi,bi->rb", w["q"], xq)
+        P = (w["d"] * act["d"][None, :]).astype(np.float16).astype(np.float64)  # f16 products, rounded once (the exact product fits f64)
+        M = (w["m"] * act["s"][None, :]).astype(np.float16).astype(np.float64)
+        exact = ((P * sumi + M) * keep).sum(axis=1)
+        deq = np.einsum("rbi,bi->r", np.abs(w["q"] * w["d"][:, :, None] + w["m"][:, :, None]), np.abs(xd))
+        terms = (np.abs(P * sumi) + np.abs(M)).sum(axis=1)
+        return exact, np.minimum(8 * GEMV_REL * deq, (nb + C_DOT) * U * terms)
     # Q4_0 / Q8_0 x Q8_0; Q6_K x Q8_K (a classifier of its own format): products of exact small integers and f16 / f32 scales
     x = act_values(act)
     assert x.size == k, (x.size, k)
@@ -205,15 +197,35 @@ def row_dots(t, act, chunk=256, drop_last_block=False):
         x[-32:] = 0.0
     nblk = k // 32
     x3 = x.reshape(nblk, 32)
+    wd = (w["q"] * w["d"][:, :, None]).reshape(w["q"].shape[0], nblk, 32)  # exact in f64
+    terms = np.einsum("rbi,bi->rb", wd, x3)
+    if typ == synth.Q6_K:  # the per-op GEMV (launch_gemv), pinned by tests/test_hip_gemv.py with the project's re-association bound
+        return terms.sum(axis=1), GEMV_REL * np.einsum("rbi,bi->r", np.abs(wd), np.abs(x3))
+    return terms.sum(axis=1), (nblk + C_DOT) * U * np.abs(terms).sum(axis=1)
+
+
+def row_dots(t, act, chunk=256, drop_last_block=False):
+    """W . x for every row of t against the activation blocks `act`: (exact f64 [rows], bound f64 [rows]) -- the bound of the module
+    docstring for an f32 evaluation of the reference's block expression in ANY order of the blocks.  drop_last_block: the dot
+    without each row's last 32 elements (what a kernel whose block loop stops one early computes; the checker's own tests)"""
+    e, b = row_dots_many(t, [act], None, chunk, drop_last_block)
+    return e[0], b[0]
+
+
+def row_dots_many(t, acts, wrows=None, chunk=256, drop_last_block=False):
+    """row_dots for several rhs rows (the prompt pass): (exact [len(acts), rows], bound) -- the weight rows are unpacked once per chunk.
+    wrows: the weight rows to take (sorted indices; None = all)"""
+    rows, k = t.shape
+    sel = np.arange(rows) if wrows is None else np.asarray(wrows)
+    exact, bound = np.empty((len(acts), sel.size)), np.empty((len(acts), sel.size))
     for r0 in range(0, rows, chunk):
+        at = np.flatnonzero((sel >= r0) & (sel < r0 + chunk))
+        if at.size == 0:
+            continue
         w = weight_rows(t, r0, min(rows, r0 + chunk))
-        wd = (w["q"] * w["d"][:, :, None]).reshape(w["q"].shape[0], nblk, 32)  # exact in f64
-        terms = np.einsum("rbi,bi->rb", wd, x3)
-        exact[r0:r0 + chunk] = terms.sum(axis=1)
-        if typ == synth.Q6_K:  # the per-op GEMV (launch_gemv), pinned by tests/test_hip_gemv.py with the project's re-association bound
-            bound[r0:r0 + chunk] = GEMV_REL * np.einsum("rbi,bi->r", np.abs(wd), np.abs(x3))
-        else:
-            bound[r0:r0 + chunk] = (nblk + C_DOT) * U * np.abs(terms).sum(axis=1)
+        w = {key: (v[sel[at] - r0] if isinstance(v, np.ndarray) else v) for key, v in w.items()}
+        for i, act in enumerate(acts):
+            exact[i, at], bound[i, at] = _chunk_dots(w, t.typ, act, k, drop_last_block)
     return exact, bound
 
 
