@@ -76,6 +76,20 @@ inline bool test_hooks_armed() {
   return h && h[0] == '1';
 }
 inline const char* test_hook(const char* name) { return test_hooks_armed() ? getenv(name) : nullptr; }
+// the three shapes a hook takes: armed with '1' (default off), disarmed with '0' (default on), a number (default `fallback`).
+// A reader keeps the answer in a function-local static, so each hook is read once per process.
+inline bool test_hook_on(const char* name) {
+  const char* e = test_hook(name);
+  return e && e[0] == '1';
+}
+inline bool test_hook_off(const char* name) {
+  const char* e = test_hook(name);
+  return e && e[0] == '0';
+}
+inline int test_hook_int(const char* name, int fallback) {
+  const char* e = test_hook(name);
+  return e ? atoi(e) : fallback;
+}
 
 // ---- device-resident layouts -----------------------------------------------------------------
 // Quantized WEIGHTS are re-laid-out once at upload ("planes"): all quants of the tensor first
@@ -125,6 +139,9 @@ struct ActLayout {
 // element 8 k + l sits at byte 4 l + k)
 __host__ __device__ inline int q4k_perm_index(int e) { return 4 * (e & 7) + (e >> 3); }
 ActLayout act_layout(uint32_t qtype, size_t n_elems);
+// one row of `cols` Q8_0 / Q8_1 / Q8_K elements from its planes (act_layout(type, cols), host memory) to the reference's blocks
+// (block_bytes(type) each): what the parity hooks hand out (crabml_hip_debug_quantize, the taps' export_fields)
+void planes_to_blocks(uint32_t type, size_t cols, const uint8_t* src_planes, uint8_t* dst_blocks);
 
 }  // namespace crabml_hip
 

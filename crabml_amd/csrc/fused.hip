@@ -99,6 +99,43 @@ Rccl* rccl() {
 }
 }  // namespace
 
+// A parity tap: while armed for a layer, the enqueue code puts device-to-device copies of that layer's buffers between its launches
+// (copy) and notes the launch plan where it decides it (note); the hook's entry point reads both back (export_fields).  Disarmed,
+// copy and note do nothing, so the enqueue code calls them unconditionally.
+struct TapRec {
+  static constexpr int FIELDS = CRABML_HIP_PFTAP_FIELDS > CRABML_HIP_TAP_FIELDS ? CRABML_HIP_PFTAP_FIELDS : CRABML_HIP_TAP_FIELDS;
+  static constexpr int WORDS = CRABML_HIP_PFTAP_PLAN_WORDS > CRABML_HIP_TAP_PLAN_WORDS ? CRABML_HIP_PFTAP_PLAN_WORDS : CRABML_HIP_TAP_PLAN_WORDS;
+  const char* const hook;  // the entry point's name, for its error texts
+  int layer = -1;          // the armed layer, -1 = disarmed
+  char* buf = nullptr;     // the scratch area (device), in the device's own layouts; every field 256-aligned
+  size_t cap = 0, used = 0;
+  size_t off[FIELDS] = {}, len[FIELDS] = {};
+  int32_t plan[WORDS] = {};
+  // a fresh directory and plan, then armed (the overflow recomputation of a prompt chunk arms again: it starts afresh)
+  void arm(int l) {
+    used = 0;
+    for (int f = 0; f < FIELDS; f++) off[f] = len[f] = 0;
+    for (auto& v : plan) v = 0;
+    layer = l;
+  }
+  void disarm() { layer = -1; }
+  bool armed() const { return layer >= 0; }
+  void note(int word, int32_t value) {
+    if (armed()) plan[word] = value;
+  }
+  void note(int l, int word, int32_t value) {  // a decision of layer l
+    if (layer == l) plan[word] = value;
+  }
+  int ensure(crabml_hip_llama* c, size_t bytes);
+  int copy(crabml_hip_llama* c, int f, const void* src, size_t bytes);
+  int read_back(crabml_hip_device* dev, std::vector<uint8_t>* host) const;
+};
+// what a hook's entry point says of a field: raw bytes (f32 values, f16 planes; cols = 0) or `rows` rows of `cols` elements as `qtype` planes
+struct TapField {
+  uint32_t qtype = CRABML_HIP_F32;
+  size_t cols = 0, rows = 1;
+};
+
 struct crabml_hip_llama {
   crabml_hip_device* dev = nullptr;
   crabml_hip_llama_config_t cfg{};
@@ -217,20 +254,10 @@ struct crabml_hip_llama {
   int* h_state = nullptr;
   unsigned h_state_next = 0;
   static constexpr unsigned H_STATE_SLOTS = 256;
-  // crabml_hip_llama_debug_tap (test hook, crabml_hip_debug.h): while tap_layer >= 0 the eager enqueue of enqueue_segment_t puts
-  // device-to-device copies of that layer's buffers between its launches (tap_copy); nothing is allocated before the first tap
-  int tap_layer = -1;
-  char* tap_buf = nullptr;
-  size_t tap_cap = 0, tap_used = 0;
-  size_t tap_off[CRABML_HIP_TAP_FIELDS] = {}, tap_len[CRABML_HIP_TAP_FIELDS] = {};
-  int32_t tap_plan[CRABML_HIP_TAP_PLAN_WORDS] = {};  // the launch plan of the tapped layer, noted where the enqueue code decides
-  // crabml_hip_llama_debug_prefill_tap: the same for one chunk pass of the prompt path (prefill_chunk_pass, pf_tap_copy); a scratch
-  // area of its own (every field holds all rows of the pass), allocated on the first prefill tap
-  int pft_layer = -1;
-  char* pft_buf = nullptr;
-  size_t pft_cap = 0, pft_used = 0;
-  size_t pft_off[CRABML_HIP_PFTAP_FIELDS] = {}, pft_len[CRABML_HIP_PFTAP_FIELDS] = {};
-  int32_t pft_plan[CRABML_HIP_PFTAP_PLAN_WORDS] = {};
+  // the two parity taps (test hooks, crabml_hip_debug.h): crabml_hip_llama_debug_tap arms `tap` for one eager decode step
+  // (enqueue_segment_t), crabml_hip_llama_debug_prefill_tap arms `pftap` for one chunk pass of the prompt path (prefill_chunk_pass,
+  // where every field holds all rows of the pass); a scratch area each, allocated on the hook's first call
+  TapRec tap{"llama debug_tap"}, pftap{"llama debug_prefill_tap"};
 };
 
 // ---- lazy.hip's context: token / position / serial of a step straight from kernel arguments (a launch on the stream's own queue:
@@ -372,32 +399,72 @@ GateupKFn gateup_k_kernel(bool qout, bool ord, bool normin) {
   return qout ? k_gateup_k_lds<true> : k_gateup_k_lds<false>;
 }
 
-// the tap (crabml_hip_llama_debug_tap): field `f` = `bytes` bytes at `src` as the stream finds them here
-int tap_copy(crabml_hip_llama* c, int f, const void* src, size_t bytes) {
-  if (c->tap_layer < 0 || src == nullptr || bytes == 0) return 0;
-  if (c->capturing) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: a tapped step is never captured");
-  const size_t off = align_up(c->tap_used, 256);
-  if (f < 0 || f >= CRABML_HIP_TAP_FIELDS || off + bytes > c->tap_cap) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: scratch area too small");
-  CH_HIP(c->dev, hipMemcpyAsync(c->tap_buf + off, src, bytes, hipMemcpyDeviceToDevice, c->dev->stream));
-  c->tap_off[f] = off;
-  c->tap_len[f] = bytes;
-  c->tap_used = off + bytes;
+}  // namespace
+
+// (a shorter area of an earlier call stays with the context until it is destroyed)
+int TapRec::ensure(crabml_hip_llama* c, size_t bytes) {
+  if (cap >= bytes) return 0;
+  cap = 0;
+  CH_TRY(dalloc(c, bytes, (void**)&buf));
+  cap = bytes;
   return 0;
 }
-// ... of the prompt pass (crabml_hip_llama_debug_prefill_tap)
-int pf_tap_copy(crabml_hip_llama* c, int f, const void* src, size_t bytes) {
-  if (c->pft_layer < 0 || src == nullptr || bytes == 0) return 0;
-  if (f < 0 || f >= CRABML_HIP_PFTAP_FIELDS) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: no field %d", f);
-  // a field copied a second time in one pass (the one-launch GEMM declined after its B' was tapped: the separate launches tap it again)
-  // takes its slot again -- the area holds every field once
-  const bool again = c->pft_len[f] == bytes;
-  const size_t off = again ? c->pft_off[f] : align_up(c->pft_used, 256);
-  if (off + bytes > c->pft_cap) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: scratch area too small");
-  CH_HIP(c->dev, hipMemcpyAsync(c->pft_buf + off, src, bytes, hipMemcpyDeviceToDevice, c->dev->stream));
+// field `f` = `bytes` bytes at `src` as the stream finds them here
+int TapRec::copy(crabml_hip_llama* c, int f, const void* src, size_t bytes) {
+  if (!armed() || src == nullptr || bytes == 0) return 0;
+  if (c->capturing) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "%s: a tapped step is never captured", hook);
+  if (f < 0 || f >= FIELDS) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "%s: no field %d", hook, f);
+  // a field copied a second time with the same length (the prompt pass's one-launch GEMM declined after its B' was tapped: the separate
+  // launches tap it again) takes its slot again -- the area holds every field once
+  const bool again = len[f] == bytes;
+  const size_t at = again ? off[f] : align_up(used, 256);
+  if (at + bytes > cap) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "%s: scratch area too small", hook);
+  CH_HIP(c->dev, hipMemcpyAsync(buf + at, src, bytes, hipMemcpyDeviceToDevice, c->dev->stream));
   if (again) return 0;
-  c->pft_off[f] = off;
-  c->pft_len[f] = bytes;
-  c->pft_used = off + bytes;
+  off[f] = at;
+  len[f] = bytes;
+  used = at + bytes;
+  return 0;
+}
+// the used part of the scratch area to `host`, in stream order (the caller synchronizes)
+int TapRec::read_back(crabml_hip_device* dev, std::vector<uint8_t>* host) const {
+  host->resize(used ? used : 1);
+  if (used) CH_HIP(dev, hipMemcpyAsync(host->data(), buf, used, hipMemcpyDeviceToHost, dev->stream));
+  return 0;
+}
+
+namespace {
+
+// What the host receives of a tap: field after field (8-aligned) in `dst` with its place in `dir`, raw fields as they are, planes
+// re-packed as the reference's blocks (never larger than the planes), and the first `nwords` plan words as field `plan_field`.
+// `host` = the scratch area as read_back left it.
+int export_fields(crabml_hip_device* dev, const TapRec& t, const std::vector<uint8_t>& host, const TapField* fld, int nfields, int plan_field,
+                  int nwords, void* dst, size_t dst_bytes, crabml_hip_tap_entry_t* dir) {
+  uint8_t* o = (uint8_t*)dst;
+  size_t at = 0;
+  for (int f = 0; f < nfields; f++) {
+    dir[f] = crabml_hip_tap_entry_t{at, 0, fld[f].qtype, 0};
+    const uint8_t* src = host.data() + t.off[f];
+    size_t out_bytes = t.len[f];
+    if (f == plan_field) {  // host words, not a device buffer
+      src = (const uint8_t*)t.plan;
+      out_bytes = (size_t)nwords * sizeof(int32_t);
+    }
+    if (out_bytes == 0) continue;
+    if (fld[f].cols == 0) {
+      if (at + out_bytes > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "%s: field %d does not fit dst", t.hook, f);
+      memcpy(o + at, src, out_bytes);
+    } else {  // rows of planes -> rows of blocks
+      const uint32_t qt = fld[f].qtype;
+      const size_t row_planes = act_layout(qt, fld[f].cols).total, row_blocks = fld[f].cols / block_elems(qt) * block_bytes(qt);
+      out_bytes = fld[f].rows * row_blocks;
+      if (t.len[f] != fld[f].rows * row_planes || at + out_bytes > dst_bytes)
+        CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "%s: field %d has an unexpected size", t.hook, f);
+      for (size_t r = 0; r < fld[f].rows; r++) planes_to_blocks(qt, fld[f].cols, src + r * row_planes, o + at + r * row_blocks);
+    }
+    dir[f].bytes = out_bytes;
+    at += align_up(out_bytes, 8);
+  }
   return 0;
 }
 
@@ -661,10 +728,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
   const bool norm_epi = c->norm_epi;
   // q / k / v rows of exactly 128 units: both 64-unit steps requested up front (5.29 -> 4.66 us per launch on the 8B shape,
   // profiles/r06_small_stage_ab.md; bit-identical).  A/B hook: CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_QKV_UPFRONT=0 keeps the two rounds.
-  static const int qkv_upfront = [] {
-    const char* e = test_hook("CRABML_HIP_QKV_UPFRONT");
-    return e && e[0] == '0' ? 0 : 1;
-  }();
+  static const int qkv_upfront = test_hook_off("CRABML_HIP_QKV_UPFRONT") ? 0 : 1;
   // the hop-free norm between wo and gate/up of a layer: decided once, for the producer and the consumer alike
   const bool defer_wo = c->defer_norm && !Q81;
   // ... and between ffn_down of layer l and q/k/v of layer l + 1 (the last ffn_down feeds the classifier launch: exact planes)
@@ -677,7 +741,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     if (norm_epi) {
       NormGather ng{c->slots, c->slots + dim / 16, c->state + 4, c->state + 5, n_segments(c), seg, c->rsums};
       const int split = chunk_split(g.flags, k, dim, dev->n_cu);
-      if (c->tap_layer == seg / 2) c->tap_plan[stage == 2 ? CRABML_HIP_PLAN_SPLIT_WO : CRABML_HIP_PLAN_SPLIT_DOWN] = split;
+      c->tap.note(seg / 2, stage == 2 ? CRABML_HIP_PLAN_SPLIT_WO : CRABML_HIP_PLAN_SPLIT_DOWN, split);
       const TpP2P tpv = tp_view(c, tp);
       // one k_gemv_res_nq launch of the given form: `split` workgroups for each of the dim / 32 chunks
       auto nq = [&](auto form, size_t lds, const float* rhs, auto tparg) {
@@ -696,10 +760,8 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       } else if (tpv.n > 1) {  // tensor parallel over a P2P group: the collective runs inside this launch
         nq(NqForm<0, true>{}, 0, nullptr, tpv);
       } else if (c->ord) {  // strict order: the same launch with block-ordered GEMV sums and the reference's norm order
-        static const int pipe_mode = [] {  // tuning hook: 0 = never, 1 = ffn_down only, 2 = wo too (-1 / unset: the default below)
-          const char* e = test_hook("CRABML_HIP_ORD_PIPE");
-          return e ? atoi(e) : -1;
-        }();
+        // tuning hook: 0 = never, 1 = ffn_down only, 2 = wo too (-1 / unset: the default below)
+        static const int pipe_mode = test_hook_int("CRABML_HIP_ORD_PIPE", -1);
         // measured (profiles/r04_strict_order_decode.md): the pipelined chain pays in ffn_down for every format, in wo for Q8_0 only
         const int pipe = pipe_mode >= 0 ? pipe_mode : FMT == CRABML_HIP_Q8_0 ? 2 : 1;
         const bool piped = pipe >= (split == 2 ? 1 : 2);  // (two workgroups per chunk: ffn_down)
@@ -727,7 +789,8 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
 
   // the tap (test hook): host-side copies between the launches of the tapped layer; a no-op unless a tapped step is being enqueued
   const size_t ad_bytes = act_layout(qt, (size_t)dim).total, rs_bytes = c->rsums ? (size_t)(dim / 32) * 4 : 0;
-  auto TAP = [&](bool on, int f, const void* src, size_t bytes) -> int { return on && c->tap_layer >= 0 ? tap_copy(c, f, src, bytes) : 0; };
+  TapRec& tap = c->tap;
+  auto TAP = [&](bool on, int f, const void* src, size_t bytes) -> int { return on ? tap.copy(c, f, src, bytes) : 0; };
   if (seg == 2 * L) {  // final rmsnorm + classifier (llama2.rs:274-278, 199-208) + greedy sampler
     const void* cls_act = c->act_dim;
     if (c->out_qt != qt) {
@@ -742,7 +805,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       }
     } else if (!norm_epi) {
       norm_quant((const float*)c->rms_final->ptr, g.rms_norm_eps, tp, plan(nullptr, nullptr, nullptr));
-      CH_TRY(TAP(c->tap_layer == L - 1, CRABML_HIP_TAP_DOWN_ACT, c->act_dim, ad_bytes));
+      CH_TRY(TAP(tap.layer == L - 1, CRABML_HIP_TAP_DOWN_ACT, c->act_dim, ad_bytes));
     }
     CH_TRY(TAP(true, CRABML_HIP_TAP_CLS_ACT, cls_act, c->out_qt == CRABML_HIP_F32 ? (size_t)dim * 4 : act_layout(c->out_qt, (size_t)dim).total));
     return enqueue_classifier_and_sampler(c, cls_act, prof);
@@ -753,9 +816,9 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     // attention rmsnorm (llama2.rs:230-234)
     if (!norm_epi || l == 0)
       norm_quant((const float*)c->rms_att[l]->ptr, g.rms_norm_eps, tp && l > 0, plan(c->wq[l], c->wk[l], c->wv[l]));
-    const bool tl = c->tap_layer == l;
-    if (tl && (!norm_epi || l == 0)) c->tap_plan[CRABML_HIP_PLAN_NORM_NIT] = norm_nit(dim);
-    CH_TRY(TAP(!norm_epi && l > 0 && c->tap_layer == l - 1, CRABML_HIP_TAP_DOWN_ACT, c->act_dim, ad_bytes));
+    const bool tl = tap.layer == l;
+    if (!norm_epi || l == 0) tap.note(l, CRABML_HIP_PLAN_NORM_NIT, norm_nit(dim));
+    CH_TRY(TAP(!norm_epi && l > 0 && tap.layer == l - 1, CRABML_HIP_TAP_DOWN_ACT, c->act_dim, ad_bytes));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_X, c->x, (size_t)dim * 4));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_ACT, c->act_dim, ad_bytes));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_RSUMS, c->rsums, rs_bytes));
@@ -769,9 +832,9 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     // waves (a tensor-parallel rank's rows; small models): two steps per request round
     const bool deferq = defer_down && l > 0;  // (defer_down: never Q4_1)
     const int upfront = deferq ? qkv_upfront : (qkv_upfront && total_rows / 2 <= 4 * dev->n_cu) ? 1 : 0;
-    if (c->tap_layer == l && !c->ord) {  // (what the kernel makes of them: rows_partial_rms / rows_partial, gemv_core.hpp)
+    if (!c->ord) {  // (what the kernel makes of them: rows_partial_rms / rows_partial, gemv_core.hpp)
       const int nu = dim / 32 * BlockFmt<FMT>::UNITS;
-      c->tap_plan[CRABML_HIP_PLAN_QKV_LOADER] = deferq ? (upfront && nu == 128 ? 4 : 3) : (upfront && nu % 128 == 0 ? 2 : 1);
+      tap.note(l, CRABML_HIP_PLAN_QKV_LOADER, deferq ? (upfront && nu == 128 ? 4 : 3) : (upfront && nu % 128 == 0 ? 2 : 1));
     }
     with_qkv_epi(c, e, l, [&](auto ep) {
       constexpr int A = QkvArchOf<decltype(ep)>::value;
@@ -800,7 +863,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
   } else {
     // ffn rmsnorm, eps = the literal 1e-5 (llama2.rs:611)
     if (!norm_epi) norm_quant((const float*)c->rms_ffn[l]->ptr, 1e-5f, tp, plan(nullptr, nullptr, nullptr));
-    const bool tl = c->tap_layer == l;
+    const bool tl = tap.layer == l;
     CH_TRY(TAP(tl, CRABML_HIP_TAP_WO_X, c->x, (size_t)dim * 4));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_WO_ACT, c->act_dim, ad_bytes));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_WO_RSUMS, c->rsums, rs_bytes));
@@ -1172,13 +1235,22 @@ int run_step_sampled(crabml_hip_llama* c, size_t pos) {
   return rc;
 }
 
-// a few bytes host -> device in stream order, staged through the context's pinned ring (see set_state)
-int stage_h2d(crabml_hip_llama* c, void* dst, const void* src, size_t bytes) {
-  if (c->h_state_next == crabml_hip_llama::H_STATE_SLOTS) {
+// `slots` consecutive 4-int slots of the context's pinned ring.  Past the end every slot may still be waiting for its copy: drain the
+// stream, start over.
+int next_state_slot(crabml_hip_llama* c, unsigned slots, int** out) {
+  if (c->h_state_next + slots > crabml_hip_llama::H_STATE_SLOTS) {
     CH_HIP(c->dev, hipStreamSynchronize(c->dev->stream));
     c->h_state_next = 0;
   }
-  int* st = c->h_state + 4 * c->h_state_next++;
+  *out = c->h_state + 4 * c->h_state_next;
+  c->h_state_next += slots;
+  return 0;
+}
+
+// a few bytes host -> device in stream order, staged through the context's pinned ring (see set_state)
+int stage_h2d(crabml_hip_llama* c, void* dst, const void* src, size_t bytes) {
+  int* st = nullptr;
+  CH_TRY(next_state_slot(c, 1, &st));
   memcpy(st, src, bytes < 16 ? bytes : 16);
   CH_HIP(c->dev, hipMemcpyAsync(dst, st, bytes < 16 ? bytes : 16, hipMemcpyHostToDevice, c->dev->stream));
   return 0;
@@ -1309,13 +1381,58 @@ int launch_attn_long_rows(crabml_hip_llama* c, int l, int B) {
   return rc == 0 ? 1 : -1;
 }
 
+// The causal attention of a prompt pass for layer l (pf_qr x KV cache -> pf_attn): the one place that chooses among the four forms.
+// Returns the kernel as CRABML_HIP_PFPLAN_ATTN_KERNEL names it (1 flash rows, 2 tile, 3 long rows, 4 per (head, row)), < 0 = error.
+int launch_prefill_attention(crabml_hip_llama* c, int l, size_t B, size_t pos0) {
+  crabml_hip_device* dev = c->dev;
+  hipStream_t st = dev->stream;
+  const int hd = c->hd, n_heads = c->n_heads_l, n_kv = c->n_kv_l, seq_cap = (int)c->cfg.seq_len;
+  const bool kv16 = c->cfg.use_f16_kv_cache != 0;
+  const int* pos_d = c->state + 6;
+  // (a pass whose every row sees fewer cached positions than the decode step's switch to the f32 kernels -- attn_long_from --
+  // keeps the exact tile kernel, so that prefill(prompt) and a token loop over the same short prompt agree bit for bit)
+  if (c->attn_flash_rows && kv16 && pos0 + B >= c->attn_long_from) {
+    // fast step: causal flash attention on the f16 matrix cores (k_attn_flash_rows; the deviation stated for k_attn_flash)
+    const dim3 fg((unsigned)((B + 63) / 64), (unsigned)n_heads);
+    flash_rows_kernel(hd)<<<fg, 512, flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
+                                                                      (const unsigned short*)c->vc[l], pos_d, c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
+    return 1;
+  }
+  if (launch_attn_tile(c, l, (int)B, (int)pos0)) return 2;
+  const int along = launch_attn_long_rows(c, l, (int)B);  // past 1024 positions: the long-context kernels, rows in grid.y
+  if (along != 0) return along < 0 ? -1 : 3;
+  // unusual shapes (f32 cache past 1024 positions, odd group sizes): one workgroup per (head, row)
+  const size_t attn_lds = (size_t)(seq_cap + hd) * sizeof(float);
+  with_const_else<0, 1>(kv16, [&](auto kv) {
+    k_attn<decltype(kv)::value != 0><<<dim3(n_heads, (unsigned)B), 256, attn_lds, st>>>(c->pf_qr, c->kc[l], c->vc[l], pos_d,
+                                                                                        (const unsigned short*)dev->exp_table, c->pf_attn, nullptr, nullptr,
+                                                                                        nullptr, n_heads, n_kv, hd, seq_cap, PrefetchPlan{},
+                                                                                        dev->strict_order ? 256 : 0);
+  });
+  return 4;
+}
+
+// What c->pf_xh holds: the planes it mirrors as pre-scaled f16 (null = nothing usable) and the k-slot order it is in
+// (gemm_f16w_order of the weight format that reads it)
+struct XhHolds {
+  const void* planes = nullptr;
+  int order = -1;
+  bool holds(const void* p, int o) const { return planes == p && order == o; }
+  void set(const void* p, int o) {
+    planes = p;
+    order = o;
+  }
+  // ffn_down's planes were written to pf_xh2 while pf_xh was the gate | up launch's own rhs: ffn_down's GEMM reads what that launch wrote
+  static void swap(crabml_hip_llama* c) { std::swap(c->pf_xh, c->pf_xh2); }
+};
+
 // allow_f16w = false: the pass keeps the int8 GEMMs (prefill_chunk's recomputation of a chunk whose B' overflowed f16)
 int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t pos0, bool want_logits, bool allow_f16w, bool* f16w_used) {
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
   const auto& g = c->cfg;
   const int dim = (int)g.embedding_dim, kv_dim = c->kv_dim_l, hidden = (int)g.hidden_dim, hd = c->hd, seq_cap = (int)g.seq_len;
-  const int n_heads = c->n_heads_l, n_kv = c->n_kv_l, L = (int)g.n_layers;
+  const int L = (int)g.n_layers;
   const bool kv16 = g.use_f16_kv_cache != 0, strict = dev->strict_order;
   const int half = strict ? 0 : 1;
   const unsigned rows = (unsigned)B;
@@ -1334,64 +1451,59 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       k_norm_f32_rows<decltype(nit)::value><<<rows, 1024, norm_lds, st>>>(c->pf_x, wn, dim, eps, c->pf_xn, half);
     });
   };
-  static const bool gemm_exact_hook = [] {  // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_EXACT=1): the fast pass with matmul_vec's own scaling
-    const char* e = test_hook("CRABML_HIP_GEMM_EXACT");
-    return e && e[0] == '1';
-  }();
+  // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_EXACT=1): the fast pass with matmul_vec's own scaling
+  static const bool gemm_exact_hook = test_hook_on("CRABML_HIP_GEMM_EXACT");
   // The fast pass, Q4_0 / Q8_0 weights x Q8_0 rows, Q4_1 x Q8_1, Q4_K / Q6_K x Q8_K, >= 32 rows: the weight-stationary f16 GEMM
   // (gemm_f16w.hip; block scales folded into f16 operands, f32 accumulation inside the matrix core -- a stated deviation of the fast
-  // tier).  The rows' pre-scaled f16 planes are made once per rhs and k-slot order (q / k / v and gate / up share theirs): xh_of /
-  // xh_order remember what pf_xh currently holds.
-  static const bool f16w_off = [] {  // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_INT8=1): the int8 kernels in the fast pass too
-    const char* e = test_hook("CRABML_HIP_GEMM_INT8");
-    return e && e[0] == '1';
-  }();
-  static const int f16w_min = [] {  // lab hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_F16W_MIN=rows): the smallest pass that takes it
-    const char* e = test_hook("CRABML_HIP_F16W_MIN");
-    return e ? atoi(e) : 32;
-  }();
+  // tier).  The rows' pre-scaled f16 planes are made once per rhs and k-slot order (q / k / v and gate / up share theirs): `xh`
+  // remembers what pf_xh currently holds.
+  // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_INT8=1): the int8 kernels in the fast pass too
+  static const bool f16w_off = test_hook_on("CRABML_HIP_GEMM_INT8");
+  // lab hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_F16W_MIN=rows): the smallest pass that takes it
+  static const int f16w_min = test_hook_int("CRABML_HIP_F16W_MIN", 32);
   const bool f16w = allow_f16w && !strict && !gemm_exact_hook && !f16w_off && !(g.flags & CRABML_HIP_LLAMA_PREFILL_INT8_GEMM) &&
                     (c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1 || c->qt == CRABML_HIP_Q8_K) && c->pf_xh != nullptr && B >= f16w_min;  // (shorter passes: the int8 kernels / the GEMV)
   *f16w_used = f16w;
   int* const ovf = c->pf_ovf;
-  // CpuTensorBuf::quantize for the rhs of matmul_vec (buf/api.rs:142-159): F32 weights take the rows as they are
-  const void* xh_of = nullptr;  // the planes c->pf_xh was made from (reset whenever planes are rewritten) ...
-  int xh_order = -1;            // ... and the k-slot order it is in (gemm_f16w_order of the weight format)
+  // the f16 GEMM takes matrix w, whose rows are k elements long (Q8_K rows: whole super-blocks only).  The one predicate: the GEMMs,
+  // the kernels that write pf_xh ahead of them and the two one-launch sites all ask here.
+  auto takes_f16w = [&](const crabml_hip_buf* w, int k) {
+    return f16w && gemm_f16w_takes(dev, w, c->qt) && (c->qt != CRABML_HIP_Q8_K || k % 256 == 0);
+  };
+  XhHolds xh;
   auto rows_to_f16 = [&](const crabml_hip_buf* w, const void* act, int k) {
     const int order = gemm_f16w_order(w->dtype);
-    if (xh_of == act && xh_order == order) return;
+    if (xh.holds(act, order)) return;
     launch_rows_to_f16(st, c->qt, w->dtype, act, B, (size_t)k, c->pf_xh, ovf);
-    xh_of = act;
-    xh_order = order;
+    xh.set(act, order);
   };
   // ... written by the kernel that quantizes the rows when the GEMM that reads them next is the f16 one (f16w_rows.hpp: the same
   // bits as k_rows_to_f16 from the finished planes, one launch fewer per GEMM; A/B: CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS)
   auto xh_target = [&](const crabml_hip_buf* next, int k, int* order) -> void* {
-    if (!f16w || next == nullptr || (g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS) || !gemm_f16w_takes(dev, next, c->qt) ||
-        (c->qt == CRABML_HIP_Q8_K && k % 256 != 0))
-      return nullptr;
+    if (next == nullptr || (g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS) || !takes_f16w(next, k)) return nullptr;
     *order = gemm_f16w_order(next->dtype);
     return c->pf_xh;
   };
+  // CpuTensorBuf::quantize for the rhs of matmul_vec (buf/api.rs:142-159): F32 weights take the rows as they are
   // next: the weight matrix whose GEMM reads these planes first
   auto quant_rows = [&](const float* src, int n, char* planes, const crabml_hip_buf* next) -> const void* {
     if (c->qt == CRABML_HIP_F32) return src;
     int order = 0;
-    void* xh = xh_target(next, n, &order);
-    launch_quantize_act_rows(st, c->qt, src, B, (size_t)n, planes, xh, order, ovf);
-    xh_of = xh ? planes : nullptr;
-    xh_order = order;
+    void* mirror = xh_target(next, n, &order);
+    launch_quantize_act_rows(st, c->qt, src, B, (size_t)n, planes, mirror, order, ovf);
+    xh.set(mirror ? planes : nullptr, order);
     return planes;
   };
   // defer (nullable): a GEMM cut into k pieces may leave the sum of its pieces to the row kernel that consumes `out` (pf_split holds them)
   // fc / xh_field (prefill tap only): the launch form as taken, and the tap field B' goes to as this GEMM finds it
+  TapRec& tap = c->pftap;
   auto gemm = [&](const crabml_hip_buf* w, int m, int k, const void* act, float* out, int* defer = nullptr, F16wForce* fc = nullptr,
                   int xh_field = -1) -> int {
     if (defer) *defer = 0;
     if (g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS) defer = nullptr;  // (A/B: every reduce its own launch)
-    if (f16w && gemm_f16w_takes(dev, w, c->qt) && (c->qt != CRABML_HIP_Q8_K || k % 256 == 0)) {
+    if (takes_f16w(w, k)) {
       rows_to_f16(w, act, k);
-      if (xh_field >= 0) CH_TRY(pf_tap_copy(c, xh_field, c->pf_xh, B * (size_t)k * 2));
+      if (xh_field >= 0) CH_TRY(tap.copy(c, xh_field, c->pf_xh, B * (size_t)k * 2));
       const size_t mm = (size_t)m;
       if (launch_gemm_f16w(dev, &w, &mm, 1, (size_t)k, c->pf_xh, B, &out, c->pf_split, c->pf_split_floats, nullptr, nullptr, defer, nullptr, fc))
         return 0;
@@ -1423,26 +1535,24 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   auto norm_quant_rows = [&](const float* wn, float eps, float* pending, const crabml_hip_buf* next, int nparts = 0) -> const void* {
     const bool q81 = c->qt == CRABML_HIP_Q8_1;
     int order = 0;
-    unsigned short* xh = (unsigned short*)xh_target(next, dim, &order);
+    unsigned short* mirror = (unsigned short*)xh_target(next, dim, &order);
     const size_t pstride = B * (size_t)dim;
     // Q8_0 / Q8_1 rows of 4096 / 8192 elements: the 256-thread form (a thread owns half a quant block / a whole one; prefill_rows.hpp)
-    static const bool rows_1024 = [] {  // lab hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_NORM_ROWS_1024=1): the 1024-thread kernel
-      const char* e = test_hook("CRABML_HIP_NORM_ROWS_1024");
-      return e && e[0] == '1';
-    }();
+    // lab hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_NORM_ROWS_1024=1): the 1024-thread kernel
+    static const bool rows_1024 = test_hook_on("CRABML_HIP_NORM_ROWS_1024");
     if (!fuse_k && !rows_1024 && (dim == 4096 || dim == 8192) && !(g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS)) {
       norm_kernel = 3;
       with_const_else<16, 32>(dim / 256, [&](auto ec) {  // elements per thread
         with_const_else<0, 1>(q81, [&](auto q) {
           k_norm_quant_rows_w<decltype(ec)::value, decltype(q)::value != 0><<<rows, 256, 0, st>>>(
-              c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux, half, xh, c->pf_split, pstride, nparts, ovf);
+              c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux, half, mirror, c->pf_split, pstride, nparts, ovf);
         });
       });
     } else if (fuse_k) {
       norm_kernel = 4;
       with_const_else<4, 12>(norm_nit(dim), [&](auto nit) {
         k_norm_quant_rows_k<decltype(nit)::value><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_xn, c->pf_act_dim, ald.total,
-                                                                                ald.off_d, ald.off_aux, ald.off_p, half, xh, order, c->pf_split,
+                                                                                ald.off_d, ald.off_aux, ald.off_p, half, mirror, order, c->pf_split,
                                                                                 pstride, nparts, ovf);
       });
     } else {
@@ -1450,10 +1560,10 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
         with_const_else<0, 1>(q81, [&](auto q) {
           constexpr int NIT = decltype(nit)::value;
           constexpr bool Q = decltype(q)::value != 0;
-          if (xh || nparts > 0) {  // (f16 planes alongside, or pieces of a cut GEMM to add first: prefill_rows.hpp)
+          if (mirror || nparts > 0) {  // (f16 planes alongside, or pieces of a cut GEMM to add first: prefill_rows.hpp)
             norm_kernel = 2;
             k_norm_quant_rows_h<NIT, Q><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux,
-                                                                      half, xh, c->pf_split, pstride, nparts, ovf);
+                                                                      half, mirror, c->pf_split, pstride, nparts, ovf);
           } else {
             norm_kernel = 1;
             k_norm_quant_rows<NIT, Q><<<rows, 1024, norm_lds, st>>>(c->pf_x, pending, wn, dim, eps, c->pf_act_dim, ald.total, ald.off_d, ald.off_aux,
@@ -1462,44 +1572,43 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
         });
       });
     }
-    xh_of = xh ? c->pf_act_dim : nullptr;
-    xh_order = order;
+    xh.set(mirror ? c->pf_act_dim : nullptr, order);
     return c->pf_act_dim;
   };
   bool pending_down = false;  // (fuse_rows) the previous layer's ffn_down output sits in pf_tmp, not yet added to pf_x
   int down_parts = 0;         // ... as piece 0 of this many + 1 k pieces
   // the prefill tap (test hook): host-side copies between the launches of the tapped layer, the launch plan noted where it is decided;
-  // a no-op unless a tapped pass is being enqueued
+  // no-ops unless a tapped pass is being enqueued
   const size_t xb_dim = B * (size_t)dim * 4, xb_kv = B * (size_t)kv_dim * 4, xb_hid = B * (size_t)hidden * 4;
-  auto PT = [&](bool on, int f, const void* src, size_t bytes) -> int { return on && c->pft_layer >= 0 ? pf_tap_copy(c, f, src, bytes) : 0; };
-  int32_t* const plan = c->pft_plan;
-  auto note_form = [&](int word_f, const F16wForce& fc) {
-    plan[word_f] = fc.used_F;
-    plan[word_f + 1] = fc.used_T;
-    plan[word_f + 2] = fc.used_ksplit;
+  auto PT = [&](bool on, int f, const void* src, size_t bytes) -> int { return on ? tap.copy(c, f, src, bytes) : 0; };
+  auto note_form = [&](int l, int word_f, const F16wForce& fc) {
+    tap.note(l, word_f, fc.used_F);
+    tap.note(l, word_f + 1, fc.used_T);
+    tap.note(l, word_f + 2, fc.used_ksplit);
   };
-  if (c->pft_layer >= 0) plan[CRABML_HIP_PFPLAN_F16W] = f16w ? 1 : 0;
+  tap.note(CRABML_HIP_PFPLAN_F16W, f16w ? 1 : 0);
   for (int l = 0; l < L; l++) {
-    const bool tl = c->pft_layer == l;
+    const bool tl = tap.layer == l;
+    const bool down_deferred = fuse_norm && l + 1 < L;  // ffn_down's add is left to the next layer's norm
     const void* a;
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_IN_X, c->pf_x, xb_dim));
     if (fuse_norm) {
       const int in_parts = pending_down ? down_parts : 0;
       CH_TRY(PT(tl && pending_down, CRABML_HIP_PFTAP_IN_TMP, c->pf_tmp, xb_dim));
       CH_TRY(PT(tl && in_parts > 0, CRABML_HIP_PFTAP_IN_PARTS, c->pf_split, (size_t)in_parts * xb_dim));
-      if (tl) plan[CRABML_HIP_PFPLAN_IN_PARTS] = in_parts;
+      tap.note(l, CRABML_HIP_PFPLAN_IN_PARTS, in_parts);
       a = norm_quant_rows((const float*)c->rms_att[l]->ptr, g.rms_norm_eps, pending_down ? c->pf_tmp : nullptr, c->wq[l], in_parts);
       pending_down = false;
     } else {
       norm_rows((const float*)c->rms_att[l]->ptr, g.rms_norm_eps);  // llama2.rs:230-234
       a = quant_rows(c->pf_xn, dim, c->pf_act_dim, c->wq[l]);
     }
-    if (tl) plan[CRABML_HIP_PFPLAN_NORM_KERNEL] = fuse_norm ? norm_kernel : 0;
+    tap.note(l, CRABML_HIP_PFPLAN_NORM_KERNEL, fuse_norm ? norm_kernel : 0);
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_N1_X, c->pf_x, xb_dim));
     CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_N1_ACT, c->pf_act_dim, B * ald.total));
     F16wForce fc_qkv{}, fc_wo{}, fc_gu{}, fc_down{};  // (all zero: the launcher's own choice; read back for the plan)
     bool qkv_done = false;  // llama2.rs:244-246
-    if (f16w && gemm_f16w_takes(dev, c->wq[l], c->qt) && c->wk[l]->dtype == c->wq[l]->dtype && c->wv[l]->dtype == c->wq[l]->dtype) {
+    if (takes_f16w(c->wq[l], dim) && c->wk[l]->dtype == c->wq[l]->dtype && c->wv[l]->dtype == c->wq[l]->dtype) {
       // the three GEMMs of the same rhs as ONE launch (the 1024-row k / v matrices alone leave most of the chip idle)
       rows_to_f16(c->wq[l], a, dim);
       CH_TRY(PT(tl, CRABML_HIP_PFTAP_N1_XH, c->pf_xh, B * (size_t)dim * 2));
@@ -1514,10 +1623,8 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       CH_TRY(gemm(c->wk[l], kv_dim, dim, a, c->pf_k));
       CH_TRY(gemm(c->wv[l], kv_dim, dim, a, c->pf_v));
     }
-    if (tl) {
-      plan[CRABML_HIP_PFPLAN_QKV_ONE] = qkv_done ? 1 : 0;
-      note_form(CRABML_HIP_PFPLAN_QKV_F, fc_qkv);
-    }
+    tap.note(l, CRABML_HIP_PFPLAN_QKV_ONE, qkv_done ? 1 : 0);
+    note_form(l, CRABML_HIP_PFPLAN_QKV_F, fc_qkv);
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_Q, c->pf_q, xb_dim));
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_K, c->pf_k, xb_kv));
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_V, c->pf_v, xb_kv));
@@ -1528,46 +1635,17 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       k_qkv_epi_rows<QkvArchOf<decltype(ep)>::value><<<dim3((pairs + 255) / 256, rows), 256, 0, st>>>(c->pf_q, c->pf_k, c->pf_v, ep);
     });
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_QR, c->pf_qr, xb_dim));
-    int along = 0;
-    int attn_kernel = 0;  // (prefill tap: CRABML_HIP_PFPLAN_ATTN_KERNEL)
-    // (a pass whose every row sees fewer cached positions than the decode step's switch to the f32 kernels -- attn_long_from --
-    // keeps the exact tile kernel, so that prefill(prompt) and a token loop over the same short prompt agree bit for bit)
-    if (c->attn_flash_rows && kv16 && pos0 + B >= c->attn_long_from) {
-      // fast step: causal flash attention on the f16 matrix cores (k_attn_flash_rows; the deviation stated for k_attn_flash)
-      const dim3 fg((unsigned)((B + 63) / 64), (unsigned)n_heads);
-      flash_rows_kernel(hd)<<<fg, 512, flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
-                                                                        (const unsigned short*)c->vc[l], pos_d, c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
-      along = 1;
-      attn_kernel = 1;
-    } else if (!launch_attn_tile(c, l, (int)B, (int)pos0)) {
-      along = launch_attn_long_rows(c, l, (int)B);  // past 1024 positions: the long-context kernels, rows in grid.y
-      if (along < 0) return CRABML_HIP_UNEXPECTED;
-      attn_kernel = 3;
-    } else {
-      along = 1;
-      attn_kernel = 2;
-    }
-    if (!along) {  // unusual shapes (f32 cache past 1024 positions, odd group sizes): one workgroup per (head, row)
-      attn_kernel = 4;
-      const size_t attn_lds = (size_t)(seq_cap + hd) * sizeof(float);
-      with_const_else<0, 1>(kv16, [&](auto kv) {
-        k_attn<decltype(kv)::value != 0><<<dim3(n_heads, rows), 256, attn_lds, st>>>(c->pf_qr, c->kc[l], c->vc[l], pos_d,
-                                                                                     (const unsigned short*)dev->exp_table, c->pf_attn, nullptr, nullptr,
-                                                                                     nullptr, n_heads, n_kv, hd, seq_cap, PrefetchPlan{},
-                                                                                     dev->strict_order ? 256 : 0);
-      });
-    }
-    if (tl) plan[CRABML_HIP_PFPLAN_ATTN_KERNEL] = attn_kernel;
+    const int attn_kernel = launch_prefill_attention(c, l, B, pos0);  // llama2.rs:571-590
+    if (attn_kernel < 0) return CRABML_HIP_UNEXPECTED;
+    tap.note(l, CRABML_HIP_PFPLAN_ATTN_KERNEL, attn_kernel);
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_ATTN, c->pf_attn, xb_dim));
     a = quant_rows(c->pf_attn, dim, c->pf_act_dim, c->wo[l]);
     CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_ATTN_ACT, c->pf_act_dim, B * ald.total));
     int wo_parts = 0;
     CH_TRY(gemm(c->wo[l], dim, dim, a, c->pf_tmp, fuse_norm ? &wo_parts : nullptr, tl ? &fc_wo : nullptr,
                 tl ? CRABML_HIP_PFTAP_ATTN_XH : -1));  // llama2.rs:600
-    if (tl) {
-      plan[CRABML_HIP_PFPLAN_WO_PARTS] = wo_parts;
-      note_form(CRABML_HIP_PFPLAN_WO_F, fc_wo);
-    }
+    tap.note(l, CRABML_HIP_PFPLAN_WO_PARTS, wo_parts);
+    note_form(l, CRABML_HIP_PFPLAN_WO_F, fc_wo);
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_WO_TMP, c->pf_tmp, xb_dim));
     CH_TRY(PT(tl && wo_parts > 0, CRABML_HIP_PFTAP_WO_PARTS, c->pf_split, (size_t)wo_parts * xb_dim));
     if (fuse_norm) {
@@ -1581,7 +1659,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_N2_ACT, c->pf_act_dim, B * ald.total));
     bool gu_done = false;  // llama2.rs:620-630
     int h_done = 0;        // the launch stored h = silu(g) * u (pf_g) instead of g and u
-    if (f16w && gemm_f16w_takes(dev, c->gate[l], c->qt) && c->up[l]->dtype == c->gate[l]->dtype) {
+    if (takes_f16w(c->gate[l], dim) && c->up[l]->dtype == c->gate[l]->dtype) {
       // gate and up as ONE launch: 2 x 448 workgroups fill the last round of the chip better than 448 twice -- and, where 64-row tiles
       // of both cover the chip, with SiLU * mul as the epilogue (a wave holds the same 16 rows of both matrices)
       rows_to_f16(c->gate[l], a, dim);
@@ -1608,20 +1686,17 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
                                  tl ? &fc_gu : nullptr);
       if (h_done == 2) {
         a = c->pf_act_hid;
-        if (hq.xh) std::swap(c->pf_xh, c->pf_xh2);  // (ffn_down's GEMM reads what this launch wrote)
-        xh_of = hq.xh ? (const void*)c->pf_act_hid : nullptr;
-        xh_order = hq_order;
+        if (hq.xh) XhHolds::swap(c);
+        xh.set(hq.xh ? c->pf_act_hid : nullptr, hq_order);
       }
     }
     if (!gu_done) {
       CH_TRY(gemm(c->gate[l], hidden, dim, a, c->pf_g, nullptr, tl ? &fc_gu : nullptr, tl ? CRABML_HIP_PFTAP_N2_XH : -1));
       CH_TRY(gemm(c->up[l], hidden, dim, a, c->pf_u));
     }
-    if (tl) {
-      plan[CRABML_HIP_PFPLAN_GU_ONE] = gu_done ? 1 : 0;
-      plan[CRABML_HIP_PFPLAN_H_DONE] = h_done;
-      note_form(CRABML_HIP_PFPLAN_GU_F, fc_gu);
-    }
+    tap.note(l, CRABML_HIP_PFPLAN_GU_ONE, gu_done ? 1 : 0);
+    tap.note(l, CRABML_HIP_PFPLAN_H_DONE, h_done);
+    note_form(l, CRABML_HIP_PFPLAN_GU_F, fc_gu);
     CH_TRY(PT(tl && h_done != 2, CRABML_HIP_PFTAP_G, c->pf_g, xb_hid));
     CH_TRY(PT(tl && h_done == 0, CRABML_HIP_PFTAP_U, c->pf_u, xb_hid));
     if (h_done == 2) {
@@ -1631,18 +1706,17 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     } else if (fuse_rows) {
       const dim3 gq((unsigned)((hidden + 255) / 256), rows);
       int order = 0;
-      unsigned short* xh = (unsigned short*)xh_target(c->down[l], hidden, &order);
+      unsigned short* mirror = (unsigned short*)xh_target(c->down[l], hidden, &order);
       with_const_else<0, 1>(c->qt == CRABML_HIP_Q8_1, [&](auto q) {
         constexpr bool Q = decltype(q)::value != 0;
-        if (xh)  // (ffn_down's f16 planes alongside)
+        if (mirror)  // (ffn_down's f16 planes alongside)
           k_gateup_epi_quant_h<Q><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
-                                                      alh.off_d, alh.off_aux, xh, ovf);
+                                                      alh.off_d, alh.off_aux, mirror, ovf);
         else
           k_gateup_epi_quant<Q><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
                                                     alh.off_d, alh.off_aux);
       });
-      xh_of = xh ? c->pf_act_hid : nullptr;
-      xh_order = order;
+      xh.set(mirror ? c->pf_act_hid : nullptr, order);
       a = c->pf_act_hid;
     } else {
       k_gateup_epi<<<(unsigned)(((size_t)B * hidden + 255) / 256), 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table,
@@ -1650,15 +1724,13 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       a = quant_rows(c->pf_g, hidden, c->pf_act_hid, c->down[l]);
     }
     CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_HID_ACT, c->pf_act_hid, B * alh.total));
-    CH_TRY(gemm(c->down[l], dim, hidden, a, c->pf_tmp, fuse_norm && l + 1 < L ? &down_parts : nullptr, tl ? &fc_down : nullptr,
+    CH_TRY(gemm(c->down[l], dim, hidden, a, c->pf_tmp, down_deferred ? &down_parts : nullptr, tl ? &fc_down : nullptr,
                 tl ? CRABML_HIP_PFTAP_HID_XH : -1));  // llama2.rs:633-636
-    if (tl) {
-      plan[CRABML_HIP_PFPLAN_DOWN_PARTS] = fuse_norm && l + 1 < L ? down_parts : 0;
-      note_form(CRABML_HIP_PFPLAN_DOWN_F, fc_down);
-    }
+    tap.note(l, CRABML_HIP_PFPLAN_DOWN_PARTS, down_deferred ? down_parts : 0);
+    note_form(l, CRABML_HIP_PFPLAN_DOWN_F, fc_down);
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_DOWN_TMP, c->pf_tmp, xb_dim));
-    CH_TRY(PT(tl && fuse_norm && l + 1 < L && down_parts > 0, CRABML_HIP_PFTAP_DOWN_PARTS, c->pf_split, (size_t)down_parts * xb_dim));
-    if (fuse_norm && l + 1 < L) {
+    CH_TRY(PT(tl && down_deferred && down_parts > 0, CRABML_HIP_PFTAP_DOWN_PARTS, c->pf_split, (size_t)down_parts * xb_dim));
+    if (down_deferred) {
       pending_down = true;  // added by the next layer's norm launch
     } else {
       k_res_epi<<<(unsigned)(((size_t)B * dim + 255) / 256), 256, 0, st>>>(c->pf_tmp, c->pf_x, (int)(B * dim), 1);
@@ -1691,18 +1763,14 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
 int prefill_chunk(crabml_hip_llama* c, const uint32_t* tokens, size_t B, size_t pos0, bool want_logits, int tap_layer = -1) {
   bool f16w = false;
   auto pass = [&](bool allow_f16w, int recomputed) -> int {
-    if (tap_layer >= 0) {
-      c->pft_used = 0;
-      for (int f = 0; f < CRABML_HIP_PFTAP_FIELDS; f++) c->pft_off[f] = c->pft_len[f] = 0;
-      for (auto& v : c->pft_plan) v = 0;
-      c->pft_plan[CRABML_HIP_PFPLAN_N_CU] = c->dev->n_cu;
-      c->pft_plan[CRABML_HIP_PFPLAN_ROWS] = (int32_t)B;
-      c->pft_plan[CRABML_HIP_PFPLAN_POS0] = (int32_t)pos0;
-      c->pft_plan[CRABML_HIP_PFPLAN_RECOMPUTED] = recomputed;
-      c->pft_layer = tap_layer;
-    }
+    TapRec& tap = c->pftap;
+    if (tap_layer >= 0) tap.arm(tap_layer);
+    tap.note(CRABML_HIP_PFPLAN_N_CU, c->dev->n_cu);
+    tap.note(CRABML_HIP_PFPLAN_ROWS, (int32_t)B);
+    tap.note(CRABML_HIP_PFPLAN_POS0, (int32_t)pos0);
+    tap.note(CRABML_HIP_PFPLAN_RECOMPUTED, recomputed);
     const int rc = prefill_chunk_pass(c, tokens, B, pos0, want_logits, allow_f16w, &f16w);
-    c->pft_layer = -1;
+    tap.disarm();
     return rc;
   };
   CH_TRY(pass(true, 0));
@@ -1733,29 +1801,14 @@ size_t prefill_chunk_rows(const crabml_hip_llama* c) {
   return chunk0 < c->cfg.seq_len ? chunk0 : c->cfg.seq_len;
 }
 
+// token, pos, step[, (prefetch sink), serial: the serial set from the host (lazy_ctx_begin) -- five ints, two slots of the ring]
 int set_state(crabml_hip_llama* c, size_t token, size_t pos, int step, const unsigned* serial = nullptr) {
-  if (c->h_state_next == crabml_hip_llama::H_STATE_SLOTS) {  // every slot may still be waiting for its copy: drain, start over
-    CH_HIP(c->dev, hipStreamSynchronize(c->dev->stream));
-    c->h_state_next = 0;
-  }
-  int* st = c->h_state + 4 * c->h_state_next++;
-  st[0] = (int)token;
-  st[1] = (int)pos;
-  st[2] = step;
-  if (serial != nullptr) {  // token, pos, step, (prefetch sink), serial: the serial set from the host (lazy_ctx_begin)
-    int st5[5] = {st[0], st[1], st[2], 0, (int)*serial};
-    // the ring slot holds 4 ints: the 5-int form takes two consecutive slots
-    if (c->h_state_next == crabml_hip_llama::H_STATE_SLOTS) {
-      CH_HIP(c->dev, hipStreamSynchronize(c->dev->stream));
-      c->h_state_next = 1;
-      st = c->h_state;
-    }
-    c->h_state_next++;
-    memcpy(st, st5, sizeof st5);
-    CH_HIP(c->dev, hipMemcpyAsync(c->state, st, 5 * sizeof(int), hipMemcpyHostToDevice, c->dev->stream));
-    return 0;
-  }
-  CH_HIP(c->dev, hipMemcpyAsync(c->state, st, 3 * sizeof(int), hipMemcpyHostToDevice, c->dev->stream));
+  const int st5[5] = {(int)token, (int)pos, step, 0, serial ? (int)*serial : 0};
+  const size_t n = serial ? 5 : 3;
+  int* st = nullptr;
+  CH_TRY(next_state_slot(c, serial ? 2 : 1, &st));
+  memcpy(st, st5, n * sizeof(int));
+  CH_HIP(c->dev, hipMemcpyAsync(c->state, st, n * sizeof(int), hipMemcpyHostToDevice, c->dev->stream));
   return 0;
 }
 
@@ -2679,95 +2732,42 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama debug_tap: only the five-launch Q4_0 / Q8_0 / Q4_1 layers of the fast step on one device");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim;
-  // the row type and the element count of every field (0 elements = f32 of `bytes`)
+  // the row type of every field that leaves as blocks (the others: f32 values, the plan words)
   const uint32_t qt = c->qt, cq = c->out_qt;
-  struct Fld {
-    uint32_t qtype;
-    size_t n;
-  };
-  Fld fld[CRABML_HIP_TAP_FIELDS];
-  for (auto& f : fld) f = Fld{CRABML_HIP_F32, 0};
-  fld[CRABML_HIP_TAP_QKV_IN_ACT] = fld[CRABML_HIP_TAP_WO_ACT] = fld[CRABML_HIP_TAP_DOWN_ACT] = fld[CRABML_HIP_TAP_ACT_ATTN] = Fld{qt, dim};
-  fld[CRABML_HIP_TAP_ACT_HID] = Fld{qt, hidden};
-  if (cq == CRABML_HIP_Q8_0 || cq == CRABML_HIP_Q8_1 || cq == CRABML_HIP_Q8_K) fld[CRABML_HIP_TAP_CLS_ACT] = Fld{cq, dim};
-  const size_t cls_raw = fld[CRABML_HIP_TAP_CLS_ACT].n ? act_layout(cq, dim).total : dim * 4;
+  TapField fld[CRABML_HIP_TAP_FIELDS];
+  fld[CRABML_HIP_TAP_QKV_IN_ACT] = fld[CRABML_HIP_TAP_WO_ACT] = fld[CRABML_HIP_TAP_DOWN_ACT] = fld[CRABML_HIP_TAP_ACT_ATTN] = TapField{qt, dim};
+  fld[CRABML_HIP_TAP_ACT_HID] = TapField{qt, hidden};
+  if (cq == CRABML_HIP_Q8_0 || cq == CRABML_HIP_Q8_1 || cq == CRABML_HIP_Q8_K) fld[CRABML_HIP_TAP_CLS_ACT] = TapField{cq, dim};
+  const size_t cls_raw = fld[CRABML_HIP_TAP_CLS_ACT].cols ? act_layout(cq, dim).total : dim * 4;
   // the scratch area, in the device's plane layout: four x, four sets of act_dim planes, three rsums, qbuf, attn, act_attn, act_hid
   const size_t adb = act_layout(qt, dim).total, ahb = act_layout(qt, hidden).total;
   const size_t raw_cap = 6 * align_up(dim * 4, 256) + 4 * adb + 3 * align_up(dim / 32 * 4, 256) + ahb + align_up(cls_raw, 256) + 512;
-  // what the host receives: the same fields with the planes re-packed as blocks (never larger than the planes)
   if (need) *need = raw_cap;
   if (!dst) return 0;
   if (dst_bytes < raw_cap) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: dst holds %zu bytes, %zu needed", dst_bytes, raw_cap);
   CH_TRY(check_step(c, token, pos));
-  if (!c->tap_buf) {
-    CH_TRY(dalloc(c, raw_cap, (void**)&c->tap_buf));
-    c->tap_cap = raw_cap;
-  }
-  c->tap_used = 0;
-  for (int f = 0; f < CRABML_HIP_TAP_FIELDS; f++) c->tap_off[f] = c->tap_len[f] = 0;
+  TapRec& tap = c->tap;
+  CH_TRY(tap.ensure(c, raw_cap));
   CH_TRY(set_state(c, token, pos, 0));
   // the eager step (run_step without the graph replay)
   c->attn_variant = variant_of(c, pos);
-  for (auto& v : c->tap_plan) v = 0;
-  c->tap_plan[CRABML_HIP_PLAN_N_CU] = dev->n_cu;
-  c->tap_plan[CRABML_HIP_PLAN_DEFER_NORM] = c->defer_norm ? 1 : 0;
-  c->tap_plan[CRABML_HIP_PLAN_NORM_EPILOGUE] = c->norm_epi ? 1 : 0;
-  c->tap_plan[CRABML_HIP_PLAN_ATTN_VARIANT] = c->attn_variant + (c->attn_variant >= 1 && c->attn_flash ? 16 : 0);
-  c->tap_layer = (int)layer;
+  tap.arm((int)layer);
+  tap.note(CRABML_HIP_PLAN_N_CU, dev->n_cu);
+  tap.note(CRABML_HIP_PLAN_DEFER_NORM, c->defer_norm ? 1 : 0);
+  tap.note(CRABML_HIP_PLAN_NORM_EPILOGUE, c->norm_epi ? 1 : 0);
+  tap.note(CRABML_HIP_PLAN_ATTN_VARIANT, c->attn_variant + (c->attn_variant >= 1 && c->attn_flash ? 16 : 0));
   const int rc = enqueue_step(c);
-  c->tap_layer = -1;
+  tap.disarm();
   if (rc != 0) return rc;
   c->kv_len++;
-  std::vector<uint8_t> h(c->tap_used ? c->tap_used : 1);
+  std::vector<uint8_t> h;
   int fault = 0;
   if (logits) CH_HIP(dev, hipMemcpyAsync(logits, c->logits, c->cfg.vocab_size * 4, hipMemcpyDeviceToHost, dev->stream));
   CH_HIP(dev, hipMemcpyAsync(&fault, c->state + 5, sizeof(int), hipMemcpyDeviceToHost, dev->stream));
-  if (c->tap_used) CH_HIP(dev, hipMemcpyAsync(h.data(), c->tap_buf, c->tap_used, hipMemcpyDeviceToHost, dev->stream));
+  CH_TRY(tap.read_back(dev, &h));
   CH_HIP(dev, hipStreamSynchronize(dev->stream));
   if (fault) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a norm-epilogue gather timed out (workgroups not co-resident?)");
-  uint8_t* o = (uint8_t*)dst;
-  size_t at = 0;
-  for (int f = 0; f < CRABML_HIP_TAP_FIELDS; f++) {
-    dir[f] = crabml_hip_tap_entry_t{at, 0, fld[f].qtype, 0};
-    if (f == CRABML_HIP_TAP_PLAN) {  // host words, not a device buffer
-      if (at + sizeof c->tap_plan > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: the plan does not fit dst");
-      memcpy(o + at, c->tap_plan, sizeof c->tap_plan);
-      dir[f].bytes = sizeof c->tap_plan;
-      at += align_up(sizeof c->tap_plan, 8);
-      continue;
-    }
-    if (c->tap_len[f] == 0) continue;
-    const uint8_t* src = h.data() + c->tap_off[f];
-    size_t out_bytes = c->tap_len[f];
-    if (fld[f].n == 0) {
-      if (at + out_bytes > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: field %d does not fit dst", f);
-      memcpy(o + at, src, out_bytes);
-    } else {  // planes -> blocks, as crabml_hip_debug_quantize lays them out
-      const uint32_t t = fld[f].qtype;
-      const size_t n = f == CRABML_HIP_TAP_ACT_HID ? hidden : dim, nb = n / block_elems(t);
-      const ActLayout al = act_layout(t, n);
-      out_bytes = nb * block_bytes(t);
-      if (c->tap_len[f] != al.total || at + out_bytes > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_tap: field %d has an unexpected size", f);
-      uint8_t* b = o + at;
-      for (size_t i = 0; i < nb; i++) {
-        if (t == CRABML_HIP_Q8_0) {
-          memcpy(b + i * 34, src + al.off_d + i * 2, 2);
-          memcpy(b + i * 34 + 2, src + i * 32, 32);
-        } else if (t == CRABML_HIP_Q8_1) {
-          memcpy(b + i * 36, src + al.off_d + i * 2, 2);
-          memcpy(b + i * 36 + 2, src + al.off_aux + i * 2, 2);
-          memcpy(b + i * 36 + 4, src + i * 32, 32);
-        } else {
-          memcpy(b + i * 292, src + al.off_d + i * 4, 4);
-          memcpy(b + i * 292 + 4, src + i * 256, 256);
-          memcpy(b + i * 292 + 260, src + al.off_aux + i * 32, 32);
-        }
-      }
-    }
-    dir[f].bytes = out_bytes;
-    at += align_up(out_bytes, 8);
-  }
-  return 0;
+  return export_fields(dev, tap, h, fld, CRABML_HIP_TAP_FIELDS, CRABML_HIP_TAP_PLAN, CRABML_HIP_TAP_PLAN_WORDS, dst, dst_bytes, dir);
 }
 
 // parity hook (crabml_hip_debug.h): one chunk pass of the prompt path with the row buffers of one layer copied out between its launches
@@ -2788,84 +2788,29 @@ int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* c, const uint32_t* to
   const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim, kv_dim = (size_t)c->kv_dim_l;
   const uint32_t qt = c->qt, cq = c->out_qt;
   const bool cls_q = cq == CRABML_HIP_Q8_0 || cq == CRABML_HIP_Q8_1 || cq == CRABML_HIP_Q8_K;
-  struct Fld {
-    uint32_t qtype;
-    size_t cols;  // 0: raw bytes (f32 values, f16 planes, plan words)
-  };
-  Fld fld[CRABML_HIP_PFTAP_FIELDS];
-  for (auto& f : fld) f = Fld{CRABML_HIP_F32, 0};
-  fld[CRABML_HIP_PFTAP_N1_ACT] = fld[CRABML_HIP_PFTAP_ATTN_ACT] = fld[CRABML_HIP_PFTAP_N2_ACT] = Fld{qt, dim};
-  fld[CRABML_HIP_PFTAP_HID_ACT] = Fld{qt, hidden};
+  TapField fld[CRABML_HIP_PFTAP_FIELDS];  // (every field holds the n rows of the pass; the classifier's input is the last row's)
+  fld[CRABML_HIP_PFTAP_N1_ACT] = fld[CRABML_HIP_PFTAP_ATTN_ACT] = fld[CRABML_HIP_PFTAP_N2_ACT] = TapField{qt, dim, n};
+  fld[CRABML_HIP_PFTAP_HID_ACT] = TapField{qt, hidden, n};
   for (int f : {CRABML_HIP_PFTAP_N1_XH, CRABML_HIP_PFTAP_ATTN_XH, CRABML_HIP_PFTAP_N2_XH, CRABML_HIP_PFTAP_HID_XH}) fld[f].qtype = CRABML_HIP_F16;
-  if (cls_q) fld[CRABML_HIP_PFTAP_CLS_ACT] = Fld{cq, dim};
+  if (cls_q) fld[CRABML_HIP_PFTAP_CLS_ACT] = TapField{cq, dim, 1};
   // the scratch area, in the device's layout: ten (n, dim) f32 buffers, three sets of up to 7 k pieces, k and v, g and u, three sets of
   // act_dim planes and one of act_hid, their f16 planes, the last row and the classifier's input; every field 256-aligned
   const size_t adb = act_layout(qt, dim).total, ahb = act_layout(qt, hidden).total;
   const size_t cls_raw = cls_q ? act_layout(cq, dim).total : dim * 4;
   const size_t raw_cap = (10 + 21) * n * dim * 4 + 2 * n * kv_dim * 4 + 2 * n * hidden * 4 + 3 * n * adb + n * ahb + 3 * n * dim * 2 +
-                         n * hidden * 2 + dim * 4 + cls_raw + 256 * (size_t)CRABML_HIP_PFTAP_FIELDS + sizeof c->pft_plan;
-  if (need) *need = raw_cap;  // (the host's copy has the planes re-packed as blocks: never larger)
+                         n * hidden * 2 + dim * 4 + cls_raw + 256 * (size_t)CRABML_HIP_PFTAP_FIELDS + CRABML_HIP_PFTAP_PLAN_WORDS * sizeof(int32_t);
+  if (need) *need = raw_cap;
   if (!dst) return 0;
   if (dst_bytes < raw_cap) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_prefill_tap: dst holds %zu bytes, %zu needed", dst_bytes, raw_cap);
   CH_TRY(prefill_alloc(c, chunk));
-  if (c->pft_cap < raw_cap) {  // (a shorter area of an earlier tap stays with the context until it is destroyed)
-    c->pft_cap = 0;
-    CH_TRY(dalloc(c, raw_cap, (void**)&c->pft_buf));
-    c->pft_cap = raw_cap;
-  }
+  CH_TRY(c->pftap.ensure(c, raw_cap));
   CH_TRY(prefill_chunk(c, tokens, n, c->kv_len, true, (int)layer));
   c->kv_len += n;
-  std::vector<uint8_t> h(c->pft_used ? c->pft_used : 1);
+  std::vector<uint8_t> h;
   if (logits) CH_HIP(dev, hipMemcpyAsync(logits, c->logits, c->cfg.vocab_size * 4, hipMemcpyDeviceToHost, dev->stream));
-  if (c->pft_used) CH_HIP(dev, hipMemcpyAsync(h.data(), c->pft_buf, c->pft_used, hipMemcpyDeviceToHost, dev->stream));
+  CH_TRY(c->pftap.read_back(dev, &h));
   CH_HIP(dev, hipStreamSynchronize(dev->stream));
-  uint8_t* o = (uint8_t*)dst;
-  size_t at = 0;
-  for (int f = 0; f < CRABML_HIP_PFTAP_FIELDS; f++) {
-    dir[f] = crabml_hip_tap_entry_t{at, 0, fld[f].qtype, 0};
-    if (f == CRABML_HIP_PFTAP_PLAN) {  // host words, not a device buffer
-      if (at + sizeof c->pft_plan > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: the plan does not fit dst");
-      memcpy(o + at, c->pft_plan, sizeof c->pft_plan);
-      dir[f].bytes = sizeof c->pft_plan;
-      at += align_up(sizeof c->pft_plan, 8);
-      continue;
-    }
-    if (c->pft_len[f] == 0) continue;
-    const uint8_t* src = h.data() + c->pft_off[f];
-    size_t out_bytes = c->pft_len[f];
-    if (fld[f].cols == 0) {
-      if (at + out_bytes > dst_bytes) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: field %d does not fit dst", f);
-      memcpy(o + at, src, out_bytes);
-    } else {  // rows of planes -> rows of blocks, as crabml_hip_debug_quantize lays them out
-      const uint32_t t = fld[f].qtype;
-      const size_t cols = fld[f].cols, nb = cols / block_elems(t), nrows = f == CRABML_HIP_PFTAP_CLS_ACT ? 1 : n;
-      const ActLayout al = act_layout(t, cols);
-      out_bytes = nrows * nb * block_bytes(t);
-      if (c->pft_len[f] != nrows * al.total || at + out_bytes > dst_bytes)
-        CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_prefill_tap: field %d has an unexpected size", f);
-      for (size_t r = 0; r < nrows; r++) {
-        const uint8_t* s = src + r * al.total;
-        uint8_t* b = o + at + r * nb * block_bytes(t);
-        for (size_t i = 0; i < nb; i++) {
-          if (t == CRABML_HIP_Q8_0) {
-            memcpy(b + i * 34, s + al.off_d + i * 2, 2);
-            memcpy(b + i * 34 + 2, s + i * 32, 32);
-          } else if (t == CRABML_HIP_Q8_1) {
-            memcpy(b + i * 36, s + al.off_d + i * 2, 2);
-            memcpy(b + i * 36 + 2, s + al.off_aux + i * 2, 2);
-            memcpy(b + i * 36 + 4, s + i * 32, 32);
-          } else {
-            memcpy(b + i * 292, s + al.off_d + i * 4, 4);
-            memcpy(b + i * 292 + 4, s + i * 256, 256);
-            memcpy(b + i * 292 + 260, s + al.off_aux + i * 32, 32);
-          }
-        }
-      }
-    }
-    dir[f].bytes = out_bytes;
-    at += align_up(out_bytes, 8);
-  }
-  return 0;
+  return export_fields(dev, c->pftap, h, fld, CRABML_HIP_PFTAP_FIELDS, CRABML_HIP_PFTAP_PLAN, CRABML_HIP_PFTAP_PLAN_WORDS, dst, dst_bytes, dir);
 }
 
 // parity hook (crabml_hip_debug.h): k_attn_flash by itself, on caller-supplied q / K / V

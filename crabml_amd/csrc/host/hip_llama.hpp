@@ -177,35 +177,16 @@ class HipLlamaRunner {
     std::vector<std::vector<uint8_t>> field;
   };
   Tap debug_tap(size_t token, size_t pos, size_t layer) {
-    size_t need = 0;
-    device_->check(crabml_hip_llama_debug_tap(ctx_, token, pos, layer, nullptr, nullptr, 0, nullptr, &need));
-    std::vector<uint8_t> buf(need);
-    crabml_hip_tap_entry_t dir[CRABML_HIP_TAP_FIELDS];
-    Tap t;
-    t.logits.resize(conf_.vocab_size);
-    device_->check(crabml_hip_llama_debug_tap(ctx_, token, pos, layer, t.logits.data(), buf.data(), buf.size(), dir, nullptr));
-    for (int f = 0; f < CRABML_HIP_TAP_FIELDS; f++) {
-      t.qtype.push_back(dir[f].qtype);
-      t.field.emplace_back(buf.begin() + dir[f].offset, buf.begin() + dir[f].offset + dir[f].bytes);
-    }
-    return t;
+    return tap_call(CRABML_HIP_TAP_FIELDS, [&](float* logits, void* dst, size_t dst_bytes, crabml_hip_tap_entry_t* dir, size_t* need) {
+      return crabml_hip_llama_debug_tap(ctx_, token, pos, layer, logits, dst, dst_bytes, dir, need);
+    });
   }
   // crabml_hip_llama_debug_prefill_tap: one chunk pass of `tokens` at the current cache length with layer `layer` tapped
   // (fields: CRABML_HIP_PFTAP_*)
   Tap debug_prefill_tap(const std::vector<uint32_t>& tokens, size_t layer) {
-    size_t need = 0;
-    device_->check(crabml_hip_llama_debug_prefill_tap(ctx_, tokens.data(), tokens.size(), layer, nullptr, nullptr, 0, nullptr, &need));
-    std::vector<uint8_t> buf(need);
-    crabml_hip_tap_entry_t dir[CRABML_HIP_PFTAP_FIELDS];
-    Tap t;
-    t.logits.resize(conf_.vocab_size);
-    device_->check(crabml_hip_llama_debug_prefill_tap(ctx_, tokens.data(), tokens.size(), layer, t.logits.data(), buf.data(), buf.size(), dir,
-                                                      nullptr));
-    for (int f = 0; f < CRABML_HIP_PFTAP_FIELDS; f++) {
-      t.qtype.push_back(dir[f].qtype);
-      t.field.emplace_back(buf.begin() + dir[f].offset, buf.begin() + dir[f].offset + dir[f].bytes);
-    }
-    return t;
+    return tap_call(CRABML_HIP_PFTAP_FIELDS, [&](float* logits, void* dst, size_t dst_bytes, crabml_hip_tap_entry_t* dir, size_t* need) {
+      return crabml_hip_llama_debug_prefill_tap(ctx_, tokens.data(), tokens.size(), layer, logits, dst, dst_bytes, dir, need);
+    });
   }
   // one decode step of a single-device simulated tp group (crabml_hip_llama_tp_sim_forward); logits from rank 0
   static std::vector<float> tp_sim_forward(const std::vector<HipLlamaRunner*>& ranks, size_t token, size_t pos) {
@@ -220,6 +201,23 @@ class HipLlamaRunner {
   size_t seq_cap() const { return seq_cap_; }
 
  private:
+  // a tap hook's two calls: ask for the size, then run it into a buffer of that size and slice the buffer by the directory
+  template <typename Hook>
+  Tap tap_call(int fields, Hook hook) {
+    size_t need = 0;
+    device_->check(hook(nullptr, nullptr, 0, nullptr, &need));
+    std::vector<uint8_t> buf(need);
+    std::vector<crabml_hip_tap_entry_t> dir(fields);
+    Tap t;
+    t.logits.resize(conf_.vocab_size);
+    device_->check(hook(t.logits.data(), buf.data(), buf.size(), dir.data(), nullptr));
+    for (const auto& e : dir) {
+      t.qtype.push_back(e.qtype);
+      t.field.emplace_back(buf.begin() + e.offset, buf.begin() + e.offset + e.bytes);
+    }
+    return t;
+  }
+
   LlamaConfig conf_;
   std::shared_ptr<LlamaWeights<HipTensor>> weights_;
   HipTensorDeviceRef device_;  // declared before ctx_ is destroyed in ~HipLlamaRunner

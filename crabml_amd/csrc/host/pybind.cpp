@@ -36,6 +36,32 @@ static uint32_t arch_of_name(const std::string& n) {
 }
 static std::string arch_name(uint32_t a) { return a < 4 ? ARCH_NAMES[a] : "unknown"; }
 
+// what a tap hook returns: {"logits": f32, field name: f32 array | uint16 f16 planes | uint8 blocks, "qtype": {field name: row type},
+// "plan": {word name: value}}; a field the step did not produce has no key
+static py::dict tap_dict(const HipLlamaRunner::Tap& t, const char* const* names, const char* const* words, int n_words, int plan_field) {
+  py::dict d, qt;
+  d["logits"] = py::array_t<float>(t.logits.size(), t.logits.data());
+  for (int f = 0; f < (int)t.field.size(); f++) {
+    const auto& b = t.field[f];
+    if (b.empty()) continue;
+    if (f == plan_field) {
+      py::dict p;
+      for (int i = 0; i < n_words; i++) p[words[i]] = ((const int32_t*)b.data())[i];
+      d[names[f]] = p;
+      continue;
+    }
+    if (t.qtype[f] == CRABML_HIP_F32)
+      d[names[f]] = py::array_t<float>(b.size() / 4, (const float*)b.data());
+    else if (t.qtype[f] == CRABML_HIP_F16)
+      d[names[f]] = py::array_t<uint16_t>(b.size() / 2, (const uint16_t*)b.data());
+    else
+      d[names[f]] = py::array_t<uint8_t>(b.size(), b.data());
+    qt[names[f]] = t.qtype[f];
+  }
+  d["qtype"] = qt;
+  return d;
+}
+
 PYBIND11_MODULE(_host, m) {
   m.doc() = "crabml-hip host mirror over the C ABI of libcrabml_hip.so";
 
@@ -521,38 +547,20 @@ PYBIND11_MODULE(_host, m) {
         std::vector<uint8_t> b = r.debug_kv(layer, v, f16);
         return py::array_t<uint8_t>(b.size(), b.data());
       })
-      // one eager step with `layer` tapped (crabml_hip_llama_debug_tap): {"logits": f32, name: f32 array | uint8 blocks, "qtype": {name: type}}
+      // one eager step with `layer` tapped (crabml_hip_llama_debug_tap); the dictionary: tap_dict
       .def("debug_tap", [](HipLlamaRunner& r, size_t token, size_t pos, size_t layer) {
         static const char* names[CRABML_HIP_TAP_FIELDS] = {"qkv_in.x", "qkv_in.act_dim", "qkv_in.rsums", "qkv.qbuf", "attn.attn", "attn.act_attn", "wo.x",
                                                            "wo.act_dim", "wo.rsums", "gateup.act_hid", "down.x", "down.act_dim", "down.rsums", "cls.act", "plan"};
+        static const char* words[CRABML_HIP_TAP_PLAN_WORDS] = {"n_cu", "defer_norm", "norm_epilogue", "attn_variant", "split_wo", "split_down", "qkv_loader", "norm_nit"};
         HipLlamaRunner::Tap t;
         {
           py::gil_scoped_release rel;
           t = r.debug_tap(token, pos, layer);
         }
-        py::dict d, qt;
-        d["logits"] = py::array_t<float>(t.logits.size(), t.logits.data());
-        for (int f = 0; f < CRABML_HIP_TAP_FIELDS; f++) {
-          const auto& b = t.field[f];
-          if (b.empty()) continue;
-          if (f == CRABML_HIP_TAP_PLAN) {  // {word name: value}
-            static const char* words[CRABML_HIP_TAP_PLAN_WORDS] = {"n_cu", "defer_norm", "norm_epilogue", "attn_variant", "split_wo", "split_down", "qkv_loader", "norm_nit"};
-            py::dict p;
-            for (int i = 0; i < CRABML_HIP_TAP_PLAN_WORDS; i++) p[words[i]] = ((const int32_t*)b.data())[i];
-            d[names[f]] = p;
-            continue;
-          }
-          if (t.qtype[f] == CRABML_HIP_F32)
-            d[names[f]] = py::array_t<float>(b.size() / 4, (const float*)b.data());
-          else
-            d[names[f]] = py::array_t<uint8_t>(b.size(), b.data());
-          qt[names[f]] = t.qtype[f];
-        }
-        d["qtype"] = qt;
-        return d;
+        return tap_dict(t, names, words, CRABML_HIP_TAP_PLAN_WORDS, CRABML_HIP_TAP_PLAN);
       })
-      // one chunk pass of `tokens` at the current cache length with `layer` tapped (crabml_hip_llama_debug_prefill_tap): {"logits": f32,
-      // name: f32 array | uint16 f16 planes | uint8 blocks, "qtype": {name: type}, "plan": {word: value}}; every field holds all rows
+      // one chunk pass of `tokens` at the current cache length with `layer` tapped (crabml_hip_llama_debug_prefill_tap); every field
+      // holds all rows
       .def("debug_prefill_tap", [](HipLlamaRunner& r, const std::vector<uint32_t>& tokens, size_t layer) {
         static const char* names[CRABML_HIP_PFTAP_FIELDS] = {
             "in.x", "in.tmp", "in.parts", "n1.x", "n1.act", "n1.xh", "q", "k", "v", "qr", "attn", "attn.act", "attn.xh", "wo.tmp", "wo.parts",
@@ -566,27 +574,7 @@ PYBIND11_MODULE(_host, m) {
           py::gil_scoped_release rel;
           t = r.debug_prefill_tap(tokens, layer);
         }
-        py::dict d, qt;
-        d["logits"] = py::array_t<float>(t.logits.size(), t.logits.data());
-        for (int f = 0; f < CRABML_HIP_PFTAP_FIELDS; f++) {
-          const auto& b = t.field[f];
-          if (b.empty()) continue;
-          if (f == CRABML_HIP_PFTAP_PLAN) {
-            py::dict p;
-            for (int i = 0; i < CRABML_HIP_PFTAP_PLAN_WORDS; i++) p[words[i]] = ((const int32_t*)b.data())[i];
-            d[names[f]] = p;
-            continue;
-          }
-          if (t.qtype[f] == CRABML_HIP_F32)
-            d[names[f]] = py::array_t<float>(b.size() / 4, (const float*)b.data());
-          else if (t.qtype[f] == CRABML_HIP_F16)
-            d[names[f]] = py::array_t<uint16_t>(b.size() / 2, (const uint16_t*)b.data());
-          else
-            d[names[f]] = py::array_t<uint8_t>(b.size(), b.data());
-          qt[names[f]] = t.qtype[f];
-        }
-        d["qtype"] = qt;
-        return d;
+        return tap_dict(t, names, words, CRABML_HIP_PFTAP_PLAN_WORDS, CRABML_HIP_PFTAP_PLAN);
       });
 
   py::class_<Runner>(m, "Llama2Runner")

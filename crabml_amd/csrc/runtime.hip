@@ -84,7 +84,26 @@ ActLayout act_layout(uint32_t qtype, size_t n) {
   return al;
 }
 
-// ---- pool --------------------------------------------------------------------------------------------
+void planes_to_blocks(uint32_t type, size_t cols, const uint8_t* src, uint8_t* b) {
+  const ActLayout al = act_layout(type, cols);
+  const size_t nb = cols / block_elems(type);
+  for (size_t i = 0; i < nb; i++) {
+    if (type == CRABML_HIP_Q8_0) {  // d f16 | qs[32]
+      memcpy(b + i * 34, src + al.off_d + i * 2, 2);
+      memcpy(b + i * 34 + 2, src + i * 32, 32);
+    } else if (type == CRABML_HIP_Q8_1) {  // d f16 | s f16 | qs[32]
+      memcpy(b + i * 36, src + al.off_d + i * 2, 2);
+      memcpy(b + i * 36 + 2, src + al.off_aux + i * 2, 2);
+      memcpy(b + i * 36 + 4, src + i * 32, 32);
+    } else {  // Q8_K: d f32 | qs[256] | bsums[16] i16
+      memcpy(b + i * 292, src + al.off_d + i * 4, 4);
+      memcpy(b + i * 292 + 4, src + i * 256, 256);
+      memcpy(b + i * 292 + 260, src + al.off_aux + i * 32, 32);
+    }
+  }
+}
+
+// ---- pool--------------------------------------------------------------------------------------------
 static size_t size_class(size_t bytes) {
   if (bytes < 256) bytes = 256;
   if (bytes <= ((size_t)1 << 20)) {
@@ -882,21 +901,7 @@ int crabml_hip_debug_quantize(crabml_hip_device_t* dev, const crabml_hip_buf_t* 
   if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
   pool_free(dev, planes, cap);
   if (e != hipSuccess) return hip_fail(dev, e, "debug_quantize", __FILE__, __LINE__);
-  uint8_t* o = (uint8_t*)dst;
-  for (size_t i = 0; i < nb; i++) {
-    if (qt == CRABML_HIP_Q8_0) {
-      memcpy(o + i * 34, h.data() + al.off_d + i * 2, 2);
-      memcpy(o + i * 34 + 2, h.data() + i * 32, 32);
-    } else if (qt == CRABML_HIP_Q8_1) {
-      memcpy(o + i * 36, h.data() + al.off_d + i * 2, 2);
-      memcpy(o + i * 36 + 2, h.data() + al.off_aux + i * 2, 2);
-      memcpy(o + i * 36 + 4, h.data() + i * 32, 32);
-    } else {
-      memcpy(o + i * 292, h.data() + al.off_d + i * 4, 4);
-      memcpy(o + i * 292 + 4, h.data() + i * 256, 256);
-      memcpy(o + i * 292 + 260, h.data() + al.off_aux + i * 32, 32);
-    }
-  }
+  planes_to_blocks(qt, n, h.data(), (uint8_t*)dst);
   return 0;
 }
 
