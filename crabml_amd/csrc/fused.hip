@@ -317,7 +317,7 @@ int dalloc(crabml_hip_llama* c, size_t bytes, void** out) {
 }
 
 Planes planes_of(const crabml_hip_buf* b) {
-  return Planes{(const i32x4*)b->ptr, (const unsigned short*)((const char*)b->ptr + b->wl.off_scale)};
+  return Planes{(const i32x4*)b->ptr, scale_plane<unsigned short>(b)};
 }
 
 // the planes of a 32-block activation (Q8_0: q | d | isum i32;  Q8_1: q | d | s f16) as the kernels write them
@@ -330,12 +330,13 @@ ActPtrs act_ptrs(char* p, size_t n, uint32_t qt) {
   ActLayout al = act_layout(qt, n);
   return ActPtrs{(signed char*)p, (unsigned short*)(p + al.off_d), (void*)(p + al.off_aux)};
 }
+// the same planes as the view a kernel reads: act_at over the offsets act_ptrs applied
 template <int FMT>
 typename ActOf<FMT>::type act_view(const ActPtrs& a) {
-  if constexpr (FMT == CRABML_HIP_Q4_1)
-    return ActQ8_1{(const i32x4*)a.q, a.d, (const unsigned short*)a.isum};
-  else
-    return ActQ8_0{(const i32x4*)a.q, a.d, (const int*)a.isum};
+  ActLayout al;
+  al.off_d = (size_t)((const char*)a.d - (const char*)a.q);
+  al.off_aux = (size_t)((const char*)a.isum - (const char*)a.q);
+  return act_at<typename ActOf<FMT>::type>((const char*)a.q, al);
 }
 
 int n_segments(const crabml_hip_llama* c) { return 2 * (int)c->cfg.n_layers + 1; }
@@ -999,16 +1000,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     return prof ? prof_begin(dev, &pr, FMT, stage, rows * k * blk_b + 4.0 * k + 4.0 * rows) : 0;
   };
   auto P1 = [&]() { return prof ? prof_end(dev, &pr) : 0; };
-  auto act_k = [&](char* planes, int n) {
-    ActLayout al = act_layout(QT, (size_t)n);
-    if constexpr (FMT == CRABML_HIP_Q4_K)
-      return act_q8k_at(planes, al.off_d, al.off_aux, al.off_p);
-    else
-      return ActQ8_1{(const i32x4*)planes, (const unsigned short*)(planes + al.off_d), (const unsigned short*)(planes + al.off_aux)};
-  };
-  auto planes_k = [&](const crabml_hip_buf* b) {
-    return Planes{(const i32x4*)b->ptr, (const unsigned short*)((const char*)b->ptr + b->wl.off_scale)};
-  };
+  auto act_k = [&](char* planes, int n) { return act_at<Act>(planes, act_layout(QT, (size_t)n)); };
   // a Q6_K tensor inside a Q4_K layer (attn_v / ffn_down of the *_K_M mixes): handed to the kernel beside the planes
   auto six = [&](const crabml_hip_buf* b) {
     return b->dtype == CRABML_HIP_Q6_K ? Planes6{(const char*)b->ptr, b->wl.off_scale} : Planes6{nullptr, 0};
@@ -1044,23 +1036,23 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         void* ob = (void*)(c->act_dim + al.off_aux);
         const int split = chunk_split(g.flags, k, dim, dev->n_cu, x_only);
         if (ordk) {  // (qmode is 1 or 2 here: `qin` holds on every ordered context)
-          launch_k(st, R, nq_ord_k_kernel(split, qmode == 2 ? 2 : 1), dim3(dim / 32 * split), dim3(1024), q8k_ord_lds_bytes(k, 32 / split), planes_k(w), a,
+          launch_k(st, R, nq_ord_k_kernel(split, qmode == 2 ? 2 : 1), dim3(dim / 32 * split), dim3(1024), q8k_ord_lds_bytes(k, 32 / split), planes_of(w), a,
                    xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
           return P1();
         }
         with_const_else<2, 1>(split, [&](auto s) {
           with_const_else<2, 1, 0>(qmode, [&](auto q) {  // (the rhs planes in LDS unless they are read from global memory)
             launch_k(st, R, k_gemv_res_nq<FMT, decltype(s)::value, decltype(q)::value>, dim3(dim / 32 * split), dim3(1024), qmode ? q8k_lds_bytes(k) : 0,
-                     planes_k(w), a, xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
+                     planes_of(w), a, xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
           });
         });
         return P1();
       }
     }
     if (tp)
-      launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_k(w), a, dst, dim, k / BE);
+      launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), a, dst, dim, k / BE);
     else
-      launch_k(st, R, k_gemv_res<FMT, 1, true>, dim3((dim + 1) / 2), dim3(128), 0, planes_k(w), a, dst, dim, k / BE);
+      launch_k(st, R, k_gemv_res<FMT, 1, true>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), a, dst, dim, k / BE);
     return P1();
   };
 
@@ -1077,11 +1069,11 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     with_qkv_epi(c, decode_qkv_epi(c, l), l, [&](auto ep) {
       constexpr int A = QkvArchOf<decltype(ep)>::value;
       if (ordk)
-        launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), ord_terms_k_lds_bytes(dim / BE), planes_k(c->wq[l]),
-                 planes_k(c->wk[l]), planes_k(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]));
+        launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), ord_terms_k_lds_bytes(dim / BE), planes_of(c->wq[l]),
+                 planes_of(c->wk[l]), planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]));
       else
-        launch_k(st, R, k_qkv<FMT, false, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_k(c->wq[l]), planes_k(c->wk[l]),
-                 planes_k(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
+        launch_k(st, R, k_qkv<FMT, false, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
+                 planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
     });
     CH_TRY(P1());
     // Q8_K producers: the (short-context) attention kernel assembles the planes of wo's rhs itself; wo copies them
@@ -1120,11 +1112,11 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         sum_parts = chunk_split(g.flags, dim_l, dim, dev->n_cu, true);
       }
       launch_k(st, R, gateup_k_kernel(qout, ordk, normin), dim3(hidden_l / 32), dim3(1024), ordk ? q8k_ord_lds_bytes(dim, 64) : q8k_lds_bytes(dim),
-               planes_k(c->gate[l]), planes_k(c->up[l]), act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 256, hx,
+               planes_of(c->gate[l]), planes_of(c->up[l]), act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 256, hx,
                (signed char*)hp, (float*)(hp ? hp + alh.off_d : nullptr), (short*)(hp ? hp + alh.off_aux : nullptr),
                (signed char*)(hp ? hp + alh.off_p : nullptr), nx, nw, normin ? 1e-5f : 0.f, nsums, sum_parts);
     } else {
-      launch_k(st, R, k_gateup<FMT>, dim3((hidden_l + 1) / 2), dim3(128), 0, planes_k(c->gate[l]), planes_k(c->up[l]),
+      launch_k(st, R, k_gateup<FMT>, dim3((hidden_l + 1) / 2), dim3(128), 0, planes_of(c->gate[l]), planes_of(c->up[l]),
                act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / BE);
     }
     CH_TRY(P1());

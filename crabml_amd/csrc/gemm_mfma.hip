@@ -871,14 +871,11 @@ bool launch_gemm_mfma(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m,
     const int nsb = (int)(k / 256), rtl = (int)((m + 63) / 64);
     const bool narrow_k = (size_t)rtl * ((b + 63) / 64) < (size_t)4 * dev->n_cu && b > 16;
     const int cwk = narrow_k ? 32 : 64, ctl = (int)((b + cwk - 1) / cwk);
-    const i32x4* wqk = (const i32x4*)wp;
-    const i32x4* whk = (const i32x4*)(wp + w->wl.off_scale);
-    if (narrow_k)
-      launch_k(st, rec, k_gemm_mfma_q4k<2>, dim3(rtl * ctl), dim3(256), GemmGeoK<2>::LDS_BYTES, wqk, whk, (const char*)act, alk.total,
-               alk.off_d, alk.off_aux, alk.off_p, out, (int)m, nsb, (int)b, rtl, dbg);
-    else
-      launch_k(st, rec, k_gemm_mfma_q4k<4>, dim3(rtl * ctl), dim3(256), GemmGeoK<4>::LDS_BYTES, wqk, whk, (const char*)act, alk.total,
-               alk.off_d, alk.off_aux, alk.off_p, out, (int)m, nsb, (int)b, rtl, dbg);
+    with_const<2, 4>(narrow_k ? 2 : 4, [&](auto nt) {
+      constexpr int N = decltype(nt)::value;
+      launch_k(st, rec, k_gemm_mfma_q4k<N>, dim3(rtl * ctl), dim3(256), GemmGeoK<N>::LDS_BYTES, (const i32x4*)wp, scale_plane<i32x4>(w),
+               (const char*)act, alk.total, alk.off_d, alk.off_aux, alk.off_p, out, (int)m, nsb, (int)b, rtl, dbg);
+    });
     return true;
   }
   const ActLayout al = act_layout(w->dtype == CRABML_HIP_Q4_1 ? CRABML_HIP_Q8_1 : CRABML_HIP_Q8_0, k);
@@ -894,42 +891,21 @@ bool launch_gemm_mfma(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m,
   const bool narrow = (size_t)row_tiles * ((b + 63) / 64) < (size_t)narrow_wgs_per_cu * dev->n_cu && b > 16;
   const int cw = narrow ? 32 : 64;
   const int col_tiles = (int)((b + cw - 1) / cw);
-  const unsigned short* wd = (const unsigned short*)(wp + w->wl.off_scale);
-#define CRABML_GEMM_LAUNCH(F, N)                                                                                              \
-  launch_k(st, rec, k_gemm_mfma<F, N>, dim3(row_tiles * col_tiles), dim3(256), GemmGeo<F, N>::LDS_BYTES, wp, wd, (const char*)act, \
-           al.total, al.off_d, al.off_aux, out, (int)m, nb, (int)b, row_tiles)
-#define CRABML_GEMM_LAUNCH_FMA(F, N)                                                                                                    \
-  launch_k(st, rec, k_gemm_mfma<F, N, true>, dim3(row_tiles * col_tiles), dim3(256), GemmGeo<F, N>::LDS_BYTES, wp, wd, (const char*)act, \
-           al.total, al.off_d, al.off_aux, out, (int)m, nb, (int)b, row_tiles)
-  const bool fma = fused_add && !dev->strict_order;
-  if (w->dtype == CRABML_HIP_Q4_0 && fma) {
-    if (narrow)
-      CRABML_GEMM_LAUNCH_FMA(CRABML_HIP_Q4_0, 2);
-    else
-      CRABML_GEMM_LAUNCH_FMA(CRABML_HIP_Q4_0, 4);
-  } else if (w->dtype == CRABML_HIP_Q8_0 && fma) {
-    if (narrow)
-      CRABML_GEMM_LAUNCH_FMA(CRABML_HIP_Q8_0, 2);
-    else
-      CRABML_GEMM_LAUNCH_FMA(CRABML_HIP_Q8_0, 4);
-  } else if (w->dtype == CRABML_HIP_Q4_0) {
-    if (narrow)
-      CRABML_GEMM_LAUNCH(CRABML_HIP_Q4_0, 2);
-    else
-      CRABML_GEMM_LAUNCH(CRABML_HIP_Q4_0, 4);
-  } else if (w->dtype == CRABML_HIP_Q4_1) {
-    if (narrow)
-      CRABML_GEMM_LAUNCH(CRABML_HIP_Q4_1, 2);
-    else
-      CRABML_GEMM_LAUNCH(CRABML_HIP_Q4_1, 4);
-  } else {
-    if (narrow)
-      CRABML_GEMM_LAUNCH(CRABML_HIP_Q8_0, 2);
-    else
-      CRABML_GEMM_LAUNCH(CRABML_HIP_Q8_0, 4);
-  }
-#undef CRABML_GEMM_LAUNCH
-#undef CRABML_GEMM_LAUNCH_FMA
+  auto launch = [&](auto f, auto n, auto fma) {  // F the block format, N the column tiles per workgroup, FMA the fused block term
+    constexpr int F = decltype(f)::value, N = decltype(n)::value;
+    launch_k(st, rec, k_gemm_mfma<F, N, decltype(fma)::value>, dim3(row_tiles * col_tiles), dim3(256), GemmGeo<F, N>::LDS_BYTES, wp,
+             scale_plane<unsigned short>(w), (const char*)act, al.total, al.off_d, al.off_aux, out, (int)m, nb, (int)b, row_tiles);
+  };
+  // the fused block term exists for Q4_0 / Q8_0 only; a Q4_1 launch with fused_add takes the plain form.  Each with_const ranges over
+  // exactly the formats of its form, so no other k_gemm_mfma is instantiated.
+  if (fused_add && !dev->strict_order && w->dtype != CRABML_HIP_Q4_1)
+    with_const<CRABML_HIP_Q4_0, CRABML_HIP_Q8_0>((int)w->dtype, [&](auto f) {
+      with_const<2, 4>(narrow ? 2 : 4, [&](auto n) { launch(f, n, std::true_type{}); });
+    });
+  else
+    with_const<CRABML_HIP_Q4_0, CRABML_HIP_Q8_0, CRABML_HIP_Q4_1>((int)w->dtype, [&](auto f) {
+      with_const<2, 4>(narrow ? 2 : 4, [&](auto n) { launch(f, n, std::false_type{}); });
+    });
   return true;
 }
 

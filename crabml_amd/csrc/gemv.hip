@@ -15,6 +15,7 @@
 // `(sumi as f32 * d_w) * d_x`; only the ORDER in which block terms are added differs from the scalar
 // CPU loop (lane-strided partial sums + a 64-lane butterfly), which is why logits carry an fp tolerance.
 // The kernel is HBM-bound (~3.6 flop/byte): no LDS round trip, no MFMA; x is re-read from L1/L2.
+// Host side: launch_wave_rows decides R, the grid and the block for every format; launch_gemv states each format's kernel and arguments once.
 #include "gemv_core.hpp"
 #include "kernels.hpp"
 
@@ -252,24 +253,33 @@ __global__ __launch_bounds__(256) void k_gemv_f16(const unsigned short* __restri
 }
 
 // ---- host launcher -------------------------------------------------------------------------------
-template <typename F>
-static void launch_rows(hipStream_t st, int m, int n_cu, F&& f) {
+// One launch of a wave-per-R-rows kernel: the one place that decides R, the grid and the block.  `form` names the kernel's R form
+// (CRABML_R_FORM below), `args` are its arguments, the same for every R.
+template <class Form, class... A>
+static void launch_wave_rows(hipStream_t st, crabml_hip_device::ProfRec* rec, int m, Form form, A... args) {
   // R rows per wave: enough waves to cover the chip a few times over, otherwise fewer rows per wave
   // (lab: R=2 is best from ~14k rows, R=1 below).
-  int R = m >= 8192 ? 2 : 1;
-  int waves = (m + R - 1) / R;
-  int tpb = 128;  // 2 waves per workgroup (lab: 64/128/256 within noise; 128 best on the classifier)
-  int wpb = tpb / 64;
-  int grid = (waves + wpb - 1) / wpb;
-  f(R, grid, tpb);
-  (void)n_cu;
+  const int R = m >= 8192 ? 2 : 1;
+  const int waves = (m + R - 1) / R;
+  const int tpb = 128;  // 2 waves per workgroup (lab: 64/128/256 within noise; 128 best on the classifier)
+  const int wpb = tpb / 64;
+  const int grid = (waves + wpb - 1) / wpb;
+  with_const<2, 1>(R, [&](auto r) { launch_k(st, rec, form(r), dim3(grid), dim3(tpb), 0, args...); });
 }
+// a kernel template's R form for launch_wave_rows: CRABML_R_FORM(k_gemv_q4_0<R>)
+#define CRABML_R_FORM(...)                 \
+  [](auto r) {                             \
+    constexpr int R = decltype(r)::value;  \
+    return __VA_ARGS__;                    \
+  }
 
 int launch_gemv(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m_, size_t k_, const void* act, size_t b,
                 float* out, crabml_hip_device::ProfRec* rec0, bool fused_add) {
   hipStream_t st = dev->stream;
   const int m = (int)m_, k = (int)k_;
   const char* wp = (const char*)w->ptr;
+  const i32x4* wq = (const i32x4*)wp;
+  const size_t off = w->wl.off_scale;
   const uint32_t qt = vec_dot_rhs_dtype(w->dtype);
   const ActLayout al = act_layout(qt, k_);
   // F32 weights take the dense f32 rhs as is (row stride k*4); quantized planes are padded per row
@@ -281,139 +291,52 @@ int launch_gemv(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m_, size
     float* o = out + bi * m_;
     crabml_hip_device::ProfRec* rec = bi == 0 ? rec0 : nullptr;
     switch (w->dtype) {
-      case CRABML_HIP_Q4_0: {
-        ActQ8_0 a{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const int*)(ap + al.off_aux)};
-        const int nb = k / 32;
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_q4_0<2>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const unsigned short*)(wp + w->wl.off_scale), a, o, m, nb);
-          else
-            launch_k(st, rec, k_gemv_q4_0<1>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const unsigned short*)(wp + w->wl.off_scale), a, o, m, nb);
-        });
+      case CRABML_HIP_Q4_0:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_q4_0<R>), wq, scale_plane<unsigned short>(w), act_at<ActQ8_0>(ap, al), o, m, k / 32);
         break;
-      }
-      case CRABML_HIP_Q8_0: {
-        ActQ8_0 a{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const int*)(ap + al.off_aux)};
-        const int nb = k / 32;
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_q8_0<2>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const unsigned short*)(wp + w->wl.off_scale), a, o, m, nb);
-          else
-            launch_k(st, rec, k_gemv_q8_0<1>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const unsigned short*)(wp + w->wl.off_scale), a, o, m, nb);
-        });
+      case CRABML_HIP_Q8_0:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_q8_0<R>), wq, scale_plane<unsigned short>(w), act_at<ActQ8_0>(ap, al), o, m, k / 32);
         break;
-      }
-      case CRABML_HIP_Q4_1: {
-        ActQ8_1 a{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const unsigned short*)(ap + al.off_aux)};
-        const int nb = k / 32;
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_q4_1<2>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const unsigned*)(wp + w->wl.off_scale), a, o, m, nb);
-          else
-            launch_k(st, rec, k_gemv_q4_1<1>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const unsigned*)(wp + w->wl.off_scale), a, o, m, nb);
-        });
+      case CRABML_HIP_Q4_1:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_q4_1<R>), wq, scale_plane<unsigned>(w), act_at<ActQ8_1>(ap, al), o, m, k / 32);
         break;
-      }
-      case CRABML_HIP_Q4_K: {
-        const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
-        const int nsb = k / 256;
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_q4_k<2>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const i32x4*)(wp + w->wl.off_scale), a, o, m, nsb);
-          else
-            launch_k(st, rec, k_gemv_q4_k<1>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const i32x4*)(wp + w->wl.off_scale), a, o, m, nsb);
-        });
+      case CRABML_HIP_Q4_K:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_q4_k<R>), wq, scale_plane<i32x4>(w), act_at<ActQ8_K>(ap, al), o, m, k / 256);
         break;
-      }
-      case CRABML_HIP_Q5_K: {
-        const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
-        const int nsb = k / 256;
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_q5_k<2>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, a, o, m, nsb);
-          else
-            launch_k(st, rec, k_gemv_q5_k<1>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, a, o, m, nsb);
-        });
+      case CRABML_HIP_Q5_K:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_q5_k<R>), wp, off, act_at<ActQ8_K>(ap, al), o, m, k / 256);
         break;
-      }
-      case CRABML_HIP_Q6_K: {
-        const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
-        const int nsb = k / 256;
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_q6_k<2>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, a, o, m, nsb);
-          else
-            launch_k(st, rec, k_gemv_q6_k<1>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, a, o, m, nsb);
-        });
+      case CRABML_HIP_Q6_K:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_q6_k<R>), wp, off, act_at<ActQ8_K>(ap, al), o, m, k / 256);
         break;
-      }
-      case CRABML_HIP_Q8_K: {
-        const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
-        const int nsb = k / 256;
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_q8_k<2>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const float*)(wp + w->wl.off_scale), a, o, m, nsb);
-          else
-            launch_k(st, rec, k_gemv_q8_k<1>, dim3(grid), dim3(tpb), 0, (const i32x4*)wp, (const float*)(wp + w->wl.off_scale), a, o, m, nsb);
-        });
+      case CRABML_HIP_Q8_K:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_q8_k<R>), wq, scale_plane<float>(w), act_at<ActQ8_K>(ap, al), o, m, k / 256);
         break;
-      }
-      case CRABML_HIP_Q5_0: {
-        ActQ8_0 a{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const int*)(ap + al.off_aux)};
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_pieces<PieceQ5_0, 2>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, w->wl.n_blocks, a, o, m, k / 32);
-          else
-            launch_k(st, rec, k_gemv_pieces<PieceQ5_0, 1>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, w->wl.n_blocks, a, o, m, k / 32);
-        });
+      case CRABML_HIP_Q5_0:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_pieces<PieceQ5_0, R>), wp, off, w->wl.n_blocks, act_at<ActQ8_0>(ap, al), o, m, k / 32);
         break;
-      }
-      case CRABML_HIP_Q5_1: {
-        ActQ8_1 a{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const unsigned short*)(ap + al.off_aux)};
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_pieces<PieceQ5_1, 2>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, w->wl.n_blocks, a, o, m, k / 32);
-          else
-            launch_k(st, rec, k_gemv_pieces<PieceQ5_1, 1>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, w->wl.n_blocks, a, o, m, k / 32);
-        });
+      case CRABML_HIP_Q5_1:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_pieces<PieceQ5_1, R>), wp, off, w->wl.n_blocks, act_at<ActQ8_1>(ap, al), o, m, k / 32);
         break;
-      }
-      case CRABML_HIP_Q2_K: {
-        const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_pieces<PieceQ2_K, 2>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, w->wl.n_blocks, a, o, m, k / 256);
-          else
-            launch_k(st, rec, k_gemv_pieces<PieceQ2_K, 1>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, w->wl.n_blocks, a, o, m, k / 256);
-        });
+      case CRABML_HIP_Q2_K:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_pieces<PieceQ2_K, R>), wp, off, w->wl.n_blocks, act_at<ActQ8_K>(ap, al), o, m, k / 256);
         break;
-      }
-      case CRABML_HIP_Q3_K: {
-        const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
-        launch_rows(st, m, dev->n_cu, [&](int R, int grid, int tpb) {
-          if (R == 2)
-            launch_k(st, rec, k_gemv_pieces<PieceQ3_K, 2>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, w->wl.n_blocks, a, o, m, k / 256);
-          else
-            launch_k(st, rec, k_gemv_pieces<PieceQ3_K, 1>, dim3(grid), dim3(tpb), 0, wp, w->wl.off_scale, w->wl.n_blocks, a, o, m, k / 256);
-        });
+      case CRABML_HIP_Q3_K:
+        launch_wave_rows(st, rec, m, CRABML_R_FORM(k_gemv_pieces<PieceQ3_K, R>), wp, off, w->wl.n_blocks, act_at<ActQ8_K>(ap, al), o, m, k / 256);
         break;
-      }
-      case CRABML_HIP_F32: {
-        int grid = (m + 3) / 4;
-        launch_k(st, rec, k_gemv_f32, dim3(grid), dim3(256), 0, (const float*)wp, (const float*)ap, o, m, k);
+      case CRABML_HIP_F32:
+        launch_k(st, rec, k_gemv_f32, dim3((m + 3) / 4), dim3(256), 0, (const float*)wp, (const float*)ap, o, m, k);
         break;
-      }
-      case CRABML_HIP_F16: {
-        int grid = (m + 3) / 4;
-        launch_k(st, rec, k_gemv_f16, dim3(grid), dim3(256), 0, (const unsigned short*)wp, (const unsigned short*)ap, o, m, k);
+      case CRABML_HIP_F16:
+        launch_k(st, rec, k_gemv_f16, dim3((m + 3) / 4), dim3(256), 0, (const unsigned short*)wp, (const unsigned short*)ap, o, m, k);
         break;
-      }
       default:
         return set_error(dev, CRABML_HIP_TENSOR_ERROR, "matmul_vec: unsupported weight dtype %u", w->dtype);
     }
   }
   return 0;
 }
+#undef CRABML_R_FORM
 
 // ---- parity hook: the exact integer part per 32-element group, through the SAME unpack code ----------
 __global__ void k_block_dots_32(const i32x4* __restrict__ wq, int wtype, ActQ8_0 a0, ActQ8_1 a1, size_t row_block0,
@@ -511,18 +434,13 @@ __global__ __launch_bounds__(64) void k_piece_ints_q6k(const char* __restrict__ 
 }
 int launch_piece_ints(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m, size_t k, size_t row, const void* act, int variant,
                       int32_t* out, float* fout) {
-  const char* wp = (const char*)w->ptr;
-  const char* ap = (const char*)act;
-  const ActLayout al = act_layout(CRABML_HIP_Q8_K, k);
-  const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
+  const ActQ8_K a = act_at<ActQ8_K>((const char*)act, act_layout(CRABML_HIP_Q8_K, k));
   const int nsb = (int)(k / 256);
   if (w->dtype == CRABML_HIP_Q4_K) {
-    if (variant == 0)
-      k_piece_ints_q4k<<<1, 64, 0, dev->stream>>>((const i32x4*)wp, (const i32x4*)(wp + w->wl.off_scale), a, (int)row, (int)m, nsb, out, fout);
-    else
-      k_piece_ints_q4k_lds<<<1, 64, 0, dev->stream>>>((const i32x4*)wp, (const i32x4*)(wp + w->wl.off_scale), a, (int)row, (int)m, nsb, out, fout);
+    launch_k(dev->stream, nullptr, variant == 0 ? k_piece_ints_q4k : k_piece_ints_q4k_lds, dim3(1), dim3(64), 0, (const i32x4*)w->ptr,
+             scale_plane<i32x4>(w), a, (int)row, (int)m, nsb, out, fout);
   } else if (w->dtype == CRABML_HIP_Q6_K) {
-    k_piece_ints_q6k<<<1, 64, 0, dev->stream>>>(wp, w->wl.off_scale, a, (int)row, (int)m, nsb, out, fout);
+    k_piece_ints_q6k<<<1, 64, 0, dev->stream>>>((const char*)w->ptr, w->wl.off_scale, a, (int)row, (int)m, nsb, out, fout);
   } else {
     return set_error(dev, CRABML_HIP_TENSOR_ERROR, "debug_superblock_ints: Q4_K / Q6_K weights only");
   }
@@ -532,36 +450,21 @@ int launch_piece_ints(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m,
 void launch_block_dots(hipStream_t st, const crabml_hip_buf* w, size_t k, size_t row, const void* act, int32_t* out) {
   const char* wp = (const char*)w->ptr;
   const char* ap = (const char*)act;
-  const uint32_t qt = vec_dot_rhs_dtype(w->dtype);
-  const ActLayout al = act_layout(qt, k);
+  const ActLayout al = act_layout(vec_dot_rhs_dtype(w->dtype), k);
+  const int nb = (int)(k / 32), nsb = (int)(k / 256);
   if (w->dtype == CRABML_HIP_Q5_0) {
-    ActQ8_0 a{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const int*)(ap + al.off_aux)};
-    const int nb = (int)(k / 32);
-    k_block_dots_pieces<PieceQ5_0><<<(nb + 63) / 64, 64, 0, st>>>(wp, w->wl.off_scale, w->wl.n_blocks, a, row * nb, nb, out);
+    k_block_dots_pieces<PieceQ5_0><<<(nb + 63) / 64, 64, 0, st>>>(wp, w->wl.off_scale, w->wl.n_blocks, act_at<ActQ8_0>(ap, al), row * nb, nb, out);
   } else if (w->dtype == CRABML_HIP_Q5_1) {
-    ActQ8_1 a{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const unsigned short*)(ap + al.off_aux)};
-    const int nb = (int)(k / 32);
-    k_block_dots_pieces<PieceQ5_1><<<(nb + 63) / 64, 64, 0, st>>>(wp, w->wl.off_scale, w->wl.n_blocks, a, row * nb, nb, out);
+    k_block_dots_pieces<PieceQ5_1><<<(nb + 63) / 64, 64, 0, st>>>(wp, w->wl.off_scale, w->wl.n_blocks, act_at<ActQ8_1>(ap, al), row * nb, nb, out);
   } else if (w->dtype == CRABML_HIP_Q2_K || w->dtype == CRABML_HIP_Q3_K) {
-    const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
-    const int nsb = (int)(k / 256);
-    if (w->dtype == CRABML_HIP_Q2_K)
-      k_block_dots_pieces<PieceQ2_K><<<(nsb * 4 + 63) / 64, 64, 0, st>>>(wp, w->wl.off_scale, w->wl.n_blocks, a, row * nsb, nsb * 4, out);
-    else
-      k_block_dots_pieces<PieceQ3_K><<<(nsb * 4 + 63) / 64, 64, 0, st>>>(wp, w->wl.off_scale, w->wl.n_blocks, a, row * nsb, nsb * 4, out);
+    launch_k(st, nullptr, w->dtype == CRABML_HIP_Q2_K ? k_block_dots_pieces<PieceQ2_K> : k_block_dots_pieces<PieceQ3_K>, dim3((nsb * 4 + 63) / 64),
+             dim3(64), 0, wp, w->wl.off_scale, w->wl.n_blocks, act_at<ActQ8_K>(ap, al), row * nsb, nsb * 4, out);
   } else if (w->dtype == CRABML_HIP_Q6_K) {
-    const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
-    int nsb = (int)(k / 256);
-    k_block_dots_q6k<<<(nsb * 8 + 63) / 64, 64, 0, st>>>(wp, w->wl.off_scale, a, row * nsb, nsb, out);
+    k_block_dots_q6k<<<(nsb * 8 + 63) / 64, 64, 0, st>>>(wp, w->wl.off_scale, act_at<ActQ8_K>(ap, al), row * nsb, nsb, out);
   } else if (w->dtype == CRABML_HIP_Q4_K || w->dtype == CRABML_HIP_Q5_K || w->dtype == CRABML_HIP_Q8_K) {
-    const ActQ8_K a = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
-    int nsb = (int)(k / 256);
-    k_block_dots_k<<<(nsb * 8 + 63) / 64, 64, 0, st>>>((const unsigned char*)wp, (int)w->dtype, a, row * nsb, nsb, out, w->wl.off_scale);
-  } else {
-    ActQ8_0 a0{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const int*)(ap + al.off_aux)};
-    ActQ8_1 a1{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const unsigned short*)(ap + al.off_aux)};
-    int nb = (int)(k / 32);
-    k_block_dots_32<<<(nb + 63) / 64, 64, 0, st>>>((const i32x4*)wp, (int)w->dtype, a0, a1, row * nb, nb, out);
+    k_block_dots_k<<<(nsb * 8 + 63) / 64, 64, 0, st>>>((const unsigned char*)wp, (int)w->dtype, act_at<ActQ8_K>(ap, al), row * nsb, nsb, out, w->wl.off_scale);
+  } else {  // Q4_0 / Q8_0 read a0, Q4_1 reads a1: the kernel takes both views of the same planes
+    k_block_dots_32<<<(nb + 63) / 64, 64, 0, st>>>((const i32x4*)wp, (int)w->dtype, act_at<ActQ8_0>(ap, al), act_at<ActQ8_1>(ap, al), row * nb, nb, out);
   }
 }
 

@@ -55,9 +55,21 @@ struct ActQ8_K {
   const short* bsums;
   const i32x4* qp;  // the same quants class-major inside every 32-element group (common.hpp): what the Q4_K kernels read
 };
-// the planes of one Q8_K vector (act_layout(Q8_K, n): q | d | bsums | qp)
-__host__ __device__ inline ActQ8_K act_q8k_at(const char* planes, size_t off_d, size_t off_aux, size_t off_p) {
-  return ActQ8_K{(const i32x4*)planes, (const float*)(planes + off_d), (const short*)(planes + off_aux), (const i32x4*)(planes + off_p)};
+// The planes of one quantized vector, laid out by act_layout(Q8_0 | Q8_1 | Q8_K, n), as the view A (host side).  The one place that
+// says which plane a field of a view reads: q | d | isum (Q8_0),  q | d | s (Q8_1),  q | d | bsums | qp (Q8_K)
+template <class A>
+A act_at(const char* planes, const ActLayout& al);
+template <>
+inline ActQ8_0 act_at<ActQ8_0>(const char* planes, const ActLayout& al) {
+  return ActQ8_0{(const i32x4*)planes, (const unsigned short*)(planes + al.off_d), (const int*)(planes + al.off_aux)};
+}
+template <>
+inline ActQ8_1 act_at<ActQ8_1>(const char* planes, const ActLayout& al) {
+  return ActQ8_1{(const i32x4*)planes, (const unsigned short*)(planes + al.off_d), (const unsigned short*)(planes + al.off_aux)};
+}
+template <>
+inline ActQ8_K act_at<ActQ8_K>(const char* planes, const ActLayout& al) {
+  return ActQ8_K{(const i32x4*)planes, (const float*)(planes + al.off_d), (const short*)(planes + al.off_aux), (const i32x4*)(planes + al.off_p)};
 }
 
 // ---- the fast step's hop-free norm: 1 / rms applied by the CONSUMER of the quantized row ------------------------------------

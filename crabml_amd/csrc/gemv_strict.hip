@@ -698,9 +698,20 @@ int launch_gemv_strict(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m
   const size_t act_stride = qt == CRABML_HIP_F32 ? k * 4 : al.total;
   constexpr int R = 2, WAVES = 4;
   const char* wp = (const char*)w->ptr;
-  const size_t nterms = k / block_elems(w->dtype);
-  const size_t lds = (size_t)WAVES * R * ((nterms + 3) & ~(size_t)3) * sizeof(float);
+  const i32x4* wq = (const i32x4*)wp;
+  const size_t off = w->wl.off_scale;
+  // the term tables of a workgroup's WAVES * R rows: one f32 per block (rounded up to whole float4s), 12 per Q4_K / Q5_K
+  // super-block, 8 per Q6_K / Q3_K super-block
+  const size_t nterms = k / block_elems(w->dtype), rows_f32 = (size_t)WAVES * R * sizeof(float);
+  const size_t lds = rows_f32 * ((nterms + 3) & ~(size_t)3), lds12 = rows_f32 * (k / 256) * 12, lds8 = rows_f32 * (k / 256) * 8;
   const unsigned grid = (unsigned)((m + R * WAVES - 1) / (R * WAVES));
+  const int mi = (int)m, nb = (int)(k / 32), nsb = (int)(k / 256);
+  // one streaming launch; false (nothing launched) when its term tables do not fit the 48 KiB of LDS a launch gets without opting in
+  auto stream_rows = [&](auto kernel, size_t lds_bytes, auto... args) {
+    if (lds_bytes > 48 * 1024) return false;
+    launch_k(dev->stream, nullptr, kernel, dim3(grid), dim3(64 * WAVES), lds_bytes, args...);
+    return true;
+  };
   // CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_STRICT_SCALAR=1: every format through the one-thread-per-row kernel (the A/B of the tests)
   static const bool scalar_only = [] {
     const char* e = test_hook("CRABML_HIP_STRICT_SCALAR");
@@ -710,67 +721,27 @@ int launch_gemv_strict(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m
     const char* ap = (const char*)act + bi * act_stride;
     float* o = out + bi * m;
     const float* add = add_all ? add_all + bi * m : nullptr;  // the residual row of THIS batch row
-    bool done = false;
-    if (!scalar_only && lds <= 48 * 1024 && block_elems(w->dtype) > 1) {
-      done = true;
-      const ActQ8_0 a0{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const int*)(ap + al.off_aux)};
-      const ActQ8_1 a1{(const i32x4*)ap, (const unsigned short*)(ap + al.off_d), (const unsigned short*)(ap + al.off_aux)};
-      const ActQ8_K ak = act_q8k_at(ap, al.off_d, al.off_aux, al.off_p);
+    const ActQ8_0 a0 = act_at<ActQ8_0>(ap, al);
+    const ActQ8_1 a1 = act_at<ActQ8_1>(ap, al);
+    const ActQ8_K ak = act_at<ActQ8_K>(ap, al);
+    auto streamed = [&] {
       switch (w->dtype) {
-        case CRABML_HIP_Q4_0:
-          k_gemv_exact_blk<CRABML_HIP_Q4_0, R><<<grid, 64 * WAVES, lds, dev->stream>>>((const i32x4*)wp, (const unsigned short*)(wp + w->wl.off_scale), a0, o, add, (int)m, (int)(k / 32));
-          break;
-        case CRABML_HIP_Q8_0:
-          k_gemv_exact_blk<CRABML_HIP_Q8_0, R><<<grid, 64 * WAVES, lds, dev->stream>>>((const i32x4*)wp, (const unsigned short*)(wp + w->wl.off_scale), a0, o, add, (int)m, (int)(k / 32));
-          break;
-        case CRABML_HIP_Q4_1:
-          k_gemv_exact_blk<CRABML_HIP_Q4_1, R><<<grid, 64 * WAVES, lds, dev->stream>>>((const i32x4*)wp, (const unsigned short*)(wp + w->wl.off_scale), a1, o, add, (int)m, (int)(k / 32));
-          break;
-        case CRABML_HIP_Q5_0:
-          k_gemv_exact_pieces<PieceQ5_0, R><<<grid, 64 * WAVES, lds, dev->stream>>>(wp, w->wl.off_scale, w->wl.n_blocks, a0, o, add, (int)m, (int)(k / 32));
-          break;
-        case CRABML_HIP_Q5_1:
-          k_gemv_exact_pieces<PieceQ5_1, R><<<grid, 64 * WAVES, lds, dev->stream>>>(wp, w->wl.off_scale, w->wl.n_blocks, a1, o, add, (int)m, (int)(k / 32));
-          break;
-        case CRABML_HIP_Q2_K:
-          k_gemv_exact_pieces<PieceQ2_K, R><<<grid, 64 * WAVES, lds, dev->stream>>>(wp, w->wl.off_scale, w->wl.n_blocks, ak, o, add, (int)m, (int)(k / 256));
-          break;
-        case CRABML_HIP_Q4_K:
-        case CRABML_HIP_Q5_K: {
-          const size_t lk = (size_t)WAVES * R * (k / 256) * 12 * sizeof(float);
-          if (lk > 48 * 1024) {
-            done = false;
-          } else if (w->dtype == CRABML_HIP_Q4_K) {
-            k_gemv_exact_q4k<false, R><<<grid, 64 * WAVES, lk, dev->stream>>>(wp, w->wl.off_scale, ak, o, add, (int)m, (int)(k / 256));
-          } else {
-            k_gemv_exact_q4k<true, R><<<grid, 64 * WAVES, lk, dev->stream>>>(wp, w->wl.off_scale, ak, o, add, (int)m, (int)(k / 256));
-          }
-          break;
-        }
-        case CRABML_HIP_Q6_K: {
-          const size_t lk = (size_t)WAVES * R * (k / 256) * 8 * sizeof(float);
-          if (lk > 48 * 1024)
-            done = false;
-          else
-            k_gemv_exact_q6k<R><<<grid, 64 * WAVES, lk, dev->stream>>>(wp, w->wl.off_scale, ak, o, add, (int)m, (int)(k / 256));
-          break;
-        }
-        case CRABML_HIP_Q3_K: {
-          const size_t lk = (size_t)WAVES * R * (k / 256) * 8 * sizeof(float);
-          if (lk > 48 * 1024)
-            done = false;
-          else
-            k_gemv_exact_q3k<R><<<grid, 64 * WAVES, lk, dev->stream>>>(wp, w->wl.off_scale, w->wl.n_blocks, ak, o, add, (int)m, (int)(k / 256));
-          break;
-        }
-        case CRABML_HIP_Q8_K:
-          k_gemv_exact_q8k<R><<<grid, 64 * WAVES, lds, dev->stream>>>((const i32x4*)wp, (const float*)(wp + w->wl.off_scale), ak, o, add, (int)m, (int)(k / 256));
-          break;
-        default: done = false;
+        case CRABML_HIP_Q4_0: return stream_rows(k_gemv_exact_blk<CRABML_HIP_Q4_0, R>, lds, wq, scale_plane<unsigned short>(w), a0, o, add, mi, nb);
+        case CRABML_HIP_Q8_0: return stream_rows(k_gemv_exact_blk<CRABML_HIP_Q8_0, R>, lds, wq, scale_plane<unsigned short>(w), a0, o, add, mi, nb);
+        case CRABML_HIP_Q4_1: return stream_rows(k_gemv_exact_blk<CRABML_HIP_Q4_1, R>, lds, wq, scale_plane<unsigned short>(w), a1, o, add, mi, nb);
+        case CRABML_HIP_Q5_0: return stream_rows(k_gemv_exact_pieces<PieceQ5_0, R>, lds, wp, off, w->wl.n_blocks, a0, o, add, mi, nb);
+        case CRABML_HIP_Q5_1: return stream_rows(k_gemv_exact_pieces<PieceQ5_1, R>, lds, wp, off, w->wl.n_blocks, a1, o, add, mi, nb);
+        case CRABML_HIP_Q2_K: return stream_rows(k_gemv_exact_pieces<PieceQ2_K, R>, lds, wp, off, w->wl.n_blocks, ak, o, add, mi, nsb);
+        case CRABML_HIP_Q4_K: return stream_rows(k_gemv_exact_q4k<false, R>, lds12, wp, off, ak, o, add, mi, nsb);
+        case CRABML_HIP_Q5_K: return stream_rows(k_gemv_exact_q4k<true, R>, lds12, wp, off, ak, o, add, mi, nsb);
+        case CRABML_HIP_Q6_K: return stream_rows(k_gemv_exact_q6k<R>, lds8, wp, off, ak, o, add, mi, nsb);
+        case CRABML_HIP_Q3_K: return stream_rows(k_gemv_exact_q3k<R>, lds8, wp, off, w->wl.n_blocks, ak, o, add, mi, nsb);
+        case CRABML_HIP_Q8_K: return stream_rows(k_gemv_exact_q8k<R>, lds, wq, scale_plane<float>(w), ak, o, add, mi, nsb);
+        default: return false;  // F32 / F16 (block_elems == 1): the scalar kernel
       }
-    }
-    if (!done)
-      k_gemv_strict<<<(unsigned)((m + 63) / 64), 64, 0, dev->stream>>>(wp, (int)w->dtype, w->wl.off_scale, ap, al.off_d, al.off_aux, o, add, (int)m, (int)k);
+    };
+    if (scalar_only || block_elems(w->dtype) <= 1 || !streamed())
+      k_gemv_strict<<<(unsigned)((m + 63) / 64), 64, 0, dev->stream>>>(wp, (int)w->dtype, off, ap, al.off_d, al.off_aux, o, add, mi, (int)k);
   }
   return 0;
 }

@@ -29,6 +29,11 @@ inline void with_const_else(int v, F&& f) {
   constexpr int vs[] = {Vs...};
   if (!with_const<Vs...>(v, f)) f(std::integral_constant<int, vs[sizeof...(Vs) - 1]>{});
 }
+// a weight buffer's scale plane (wl.off_scale bytes behind its quants, common.hpp) as the type the kernel reads it in
+template <class T>
+inline const T* scale_plane(const crabml_hip_buf* w) {
+  return (const T*)((const char*)w->ptr + w->wl.off_scale);
+}
 
 // ---- quantize.hip: activation quantizers (buf_q8_0.rs:87-134, buf_q8_1.rs:90-129, buf_q8_k.rs:84-131)
 void launch_quantize_act(hipStream_t st, uint32_t qtype, const float* x, size_t n, void* planes);

@@ -29,10 +29,12 @@ def make(fmt, m, k, seed):
     return typ, raw, x
 
 
-# shapes: 15M model (9 / 24 blocks per row: not a multiple of 64 lanes), ragged m (odd, < R), 8B layer shapes
+# shapes: 15M model (9 / 24 blocks per row: not a multiple of 64 lanes), ragged m (odd, < R), 8B layer shapes; last, one block
+# per row times 8193 rows: the two-rows-per-wave form every launch takes from 8192 rows, its last wave with one live row
+# (test_block_dots_bit_exact takes the first six of each list)
 SHAPES_32 = [(288, 288), (768, 288), (288, 768), (1, 32), (3, 64), (5, 2080), (1000, 4096), (4096, 4096),
-             (1024, 4096), (300, 14336)]
-SHAPES_256 = [(3, 256), (5, 768), (512, 512), (1000, 4096), (257, 14336), (1024, 1024)]
+             (1024, 4096), (300, 14336), (8193, 64)]
+SHAPES_256 = [(3, 256), (5, 768), (512, 512), (1000, 4096), (257, 14336), (1024, 1024), (8193, 256)]
 
 
 def shapes_for(fmt):
