@@ -5,7 +5,8 @@
 //!
 //! The generic `Llama2Runner<HipTensor>` needs none of this (every `Tensor` method is a kernel launch); it is
 //! launch-bound on an MI355X (about 1000 launches per token for Llama-3-8B), which is what this path removes.
-//! Qwen2 (llama2.rs:283-351: q / k / v biases, NEOX rope) takes the same path; gemma and phi2 stay on the generic runner.
+//! Qwen2 (llama2.rs:283-351: q / k / v biases, NEOX rope) and Gemma (llama2.rs:455-524: the embedding scaled by sqrt(dim), NEOX rope,
+//! GELU) take the same path; phi2 stays on the generic runner.
 
 use std::ptr;
 use std::sync::Arc;
@@ -50,10 +51,12 @@ impl HipLlamaRunner {
     ) -> Result<Self> {
         // Qwen2 = forward_llama + q / k / v biases + NEOX rope (llama2.rs:283-351)
         let qwen2 = conf.architecture == ModelArchitecture::Qwen2;
-        if conf.architecture != ModelArchitecture::Llama && !qwen2 {
+        // Gemma = forward_llama with the scaled embedding, NEOX rope and GELU, no biases (llama2.rs:455-524)
+        let gemma = conf.architecture == ModelArchitecture::Gemma;
+        if conf.architecture != ModelArchitecture::Llama && !qwen2 && !gemma {
             bail!(
                 ErrorKind::NotImplemented,
-                "the fused hip decode step serves the llama and qwen2 architectures only, got {:?}",
+                "the fused hip decode step serves the llama, qwen2 and gemma architectures only, got {:?}",
                 conf.architecture
             );
         }
@@ -151,6 +154,8 @@ impl HipLlamaRunner {
         let c_arch = ffi::crabml_hip_llama_arch_t {
             architecture: if qwen2 {
                 ffi::CRABML_HIP_ARCH_QWEN2
+            } else if gemma {
+                ffi::CRABML_HIP_ARCH_GEMMA
             } else {
                 ffi::CRABML_HIP_ARCH_LLAMA
             },

@@ -131,6 +131,11 @@ struct WeightLayout {
 };
 WeightLayout weight_layout(uint32_t dtype, size_t n_elems);
 
+// the activation of the FFN's h = act(g) * u as the gate | up kernels take it (ffn_act_mul, devutil.hpp)
+struct FfnAct {
+  const unsigned short* tab;  // SiLU: the f16 exp table (cpu_device.rs:108-115); GELU: the f16 gelu table (:117-124)
+  int gelu;
+};
 struct ActLayout {
   size_t off_d = 0, off_aux = 0, total = 0;
   size_t off_p = 0;  // Q8_K: the class-major copy of the quants (read by the Q4_K kernels)

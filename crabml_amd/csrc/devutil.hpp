@@ -24,6 +24,15 @@ __device__ __forceinline__ unsigned short f2h(float f) {
 __device__ __forceinline__ unsigned short h_mul(unsigned short a, unsigned short b) { return f2h(h2f(a) * h2f(b)); }
 __device__ __forceinline__ unsigned short h_add(unsigned short a, unsigned short b) { return f2h(h2f(a) + h2f(b)); }
 
+// The FFN's h = act(g) * u (llama2.rs:624-630), the one helper every gate | up site calls.  SiLU (silu.rs:6-13): g / (1 + exp(-g)) with
+// the exponential through the reference's f16 table; GELU (Gemma; gelu.rs:10-22): f32(table[f16(g)]), the reference's own lookup.
+// `gelu` is a kernel argument, uniform over the launch: the SiLU arithmetic is the code it always was.  (FfnAct: common.hpp)
+__device__ __forceinline__ float ffn_act_mul(float g, float u, FfnAct a) {
+  if (a.gelu) return h2f(a.tab[f2h(g)]) * u;
+  const float nexp = h2f(a.tab[f2h(-g)]);
+  return (g / (1.0f + nexp)) * u;
+}
+
 // Native f16 arithmetic.  The half crate computes `a * b` / `a + b` in f32 and rounds once to f16; for + and * that
 // double rounding is innocuous (24 >= 2 * 11 + 2 significand bits), so it equals ONE correctly rounded f16
 // operation: v_mul_f16 / v_add_f16.  Used by the f16-accumulated PV chain of attention (buf_f16.rs:152-163), where

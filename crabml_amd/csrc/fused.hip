@@ -152,6 +152,10 @@ struct crabml_hip_llama {
   // Qwen2 (crabml_hip_llama_create_arch): q / k / v biases per layer, NEOX rope (the q|k|v kernels' QKV_QWEN2 form)
   bool qwen2 = false;
   std::vector<crabml_hip_buf*> bq, bk, bv;
+  // Gemma (llama2.rs:455-524): the embedded row times sqrtf(dim), NEOX rope without biases (QKV_GEMMA), h = gelu(g) * u
+  bool gemma = false;
+  float embed_scale = 1.0f;    // k_embed's factor: 1.0f = none
+  FfnAct ffn_act{nullptr, 0};  // what every gate | up launch of this context is handed: SiLU + the exp table, or GELU + the gelu table
   // device state
   std::vector<void*> kc, vc;
   size_t kv_bytes = 0;
@@ -503,10 +507,12 @@ typedef void (*FlashFn)(const float*, const unsigned short*, const unsigned shor
 template <int G>
 FlashFn flash_kernel_g(int hd, bool q81, bool ticket) {
   if (ticket) {
+    if (hd == 256) return q81 ? (FlashFn)k_attn_flash<G, 256, true, true> : (FlashFn)k_attn_flash<G, 256, false, true>;
     if (hd == 128) return q81 ? (FlashFn)k_attn_flash<G, 128, true, true> : (FlashFn)k_attn_flash<G, 128, false, true>;
     if (hd == 64) return q81 ? (FlashFn)k_attn_flash<G, 64, true, true> : (FlashFn)k_attn_flash<G, 64, false, true>;
     return nullptr;
   }
+  if (hd == 256) return (FlashFn)k_attn_flash<G, 256, false, false>;
   if (hd == 128) return (FlashFn)k_attn_flash<G, 128, false, false>;
   if (hd == 64) return (FlashFn)k_attn_flash<G, 64, false, false>;
   return nullptr;
@@ -542,7 +548,7 @@ void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
   if (prof) prof_begin(dev, &r[1], CRABML_HIP_F32, 8, 0.0);
   crabml_hip_device::ProfRec* R1 = prof ? &r[1] : nullptr;
   const int* pos_d = c->state + 1;
-  with_const_else<128, 64>(hd, [&](auto hdc) {  // (flash_kernel has no other head_dim)
+  with_const_else<256, 128, 64>(hd, [&](auto hdc) {  // (flash_kernel has no other head_dim)
     with_const_else<0, 1>(q81, [&](auto q) {
       constexpr int HD = decltype(hdc)::value;
       launch_k(st, R1, k_attn_flash_merge<HD, decltype(q)::value != 0>, dim3(c->n_heads_l), dim3(HD), 0, (const float*)c->flash_part, pos_d,
@@ -649,11 +655,17 @@ template <>
 struct QkvArchOf<QkvEpiB> {
   static constexpr int value = QKV_QWEN2;
 };
-// f(the epilogue arguments of layer l's q|k|v launch): e itself, or Qwen2's; QkvArchOf<decltype(ep)> is the kernels' ARCH
+template <>
+struct QkvArchOf<QkvEpiN> {
+  static constexpr int value = QKV_GEMMA;
+};
+// f(the epilogue arguments of layer l's q|k|v launch): e itself, Qwen2's, or Gemma's; QkvArchOf<decltype(ep)> is the kernels' ARCH
 template <class F>
 void with_qkv_epi(const crabml_hip_llama* c, const QkvEpi& e, int l, F&& f) {
   if (c->qwen2)
     f(qwen2_epi(c, e, l));
+  else if (c->gemma)
+    f(QkvEpiN{e});
   else
     f(e);
 }
@@ -666,7 +678,7 @@ QkvEpi decode_qkv_epi(const crabml_hip_llama* c, int l) {
 void launch_embed(const crabml_hip_llama* c) {
   const int dim = (int)c->cfg.embedding_dim;
   k_embed<<<(dim + 255) / 256, 256, 0, c->dev->stream>>>((const char*)c->token_embed->ptr, (int)c->token_embed->dtype,
-                                                         c->token_embed->wl.off_scale, c->state, dim, c->x);
+                                                         c->token_embed->wl.off_scale, c->state, dim, c->x, c->embed_scale);
 }
 
 // the form <QIN, TP, DEFER> of a k_gemv_res_nq launch, as a value: the caller branches between forms, SPLIT is folded at the launch
@@ -876,17 +888,17 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     if (hq) {
       if constexpr (!Q81)
         launch_k(st, R, k_gateup_h<FMT>, dim3(hidden_l / c->gu_rows), dim3(c->gu_rows / 2 * 64), 0, planes_of(c->gate[l]), planes_of(c->up[l]),
-                 act_view<FMT>(ad), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 32);
+                 act_view<FMT>(ad), c->ffn_act, c->h, hidden_l, dim / 32);
     } else if (c->ord)
       launch_k(st, R, k_gateup_q_ord<FMT>, dim3(hidden_l / 32), dim3(1024), gateup_q_ord_lds_bytes(dim / 32), planes_of(c->gate[l]),
-               planes_of(c->up[l]), act_view<FMT>(ad), dev->exp_table, ah.q, ah.d, ah.isum, dim / 32);
+               planes_of(c->up[l]), act_view<FMT>(ad), c->ffn_act, ah.q, ah.d, ah.isum, dim / 32);
     else if (defer_wo) {
       if constexpr (!Q81)
         launch_k(st, R, k_gateup_q<FMT, true>, dim3(hidden_l / 32), dim3(1024), 0, planes_of(c->gate[l]), planes_of(c->up[l]), act_view<FMT>(ad),
-                 dev->exp_table, ah.q, ah.d, ah.isum, dim / 32, rt);
+                 c->ffn_act, ah.q, ah.d, ah.isum, dim / 32, rt);
     } else
       launch_k(st, R, k_gateup_q<FMT>, dim3(hidden_l / 32), dim3(1024), 0, planes_of(c->gate[l]), planes_of(c->up[l]),
-               act_view<FMT>(ad), dev->exp_table, ah.q, ah.d, ah.isum, dim / 32, rt);
+               act_view<FMT>(ad), c->ffn_act, ah.q, ah.d, ah.isum, dim / 32, rt);
     CH_TRY(P1(&pr));
     CH_TRY(TAP(tl && !hq, CRABML_HIP_TAP_ACT_HID, c->act_hid, act_layout(qt, (size_t)hidden_l).total));
     // down (+ residual, llama2.rs:633-636): k = the local hidden slice
@@ -964,7 +976,7 @@ int enqueue_segment_generic(crabml_hip_llama* c, int seg) {
     const void* act = quant(c->xn, dim, c->qt, c->act_dim);
     CH_TRY(gemv(c->gate[l], hidden_l, dim, act, c->tmp, 3));
     CH_TRY(gemv(c->up[l], hidden_l, dim, act, c->tmp + hidden_l, 3));
-    k_gateup_epi<<<(hidden_l + 255) / 256, 256, 0, st>>>(c->tmp, c->tmp + hidden_l, dev->exp_table, c->h, hidden_l);
+    k_gateup_epi<<<(hidden_l + 255) / 256, 256, 0, st>>>(c->tmp, c->tmp + hidden_l, c->ffn_act, c->h, hidden_l);
     const void* hact = quant(c->h, hidden_l, c->qt, c->act_hid);
     if (strict && !tp) {
       CH_TRY(launch_gemv_strict(dev, c->down[l], dim, hidden_l, hact, 1, c->x, c->x));
@@ -1112,12 +1124,12 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         sum_parts = chunk_split(g.flags, dim_l, dim, dev->n_cu, true);
       }
       launch_k(st, R, gateup_k_kernel(qout, ordk, normin), dim3(hidden_l / 32), dim3(1024), ordk ? q8k_ord_lds_bytes(dim, 64) : q8k_lds_bytes(dim),
-               planes_of(c->gate[l]), planes_of(c->up[l]), act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / 256, hx,
+               planes_of(c->gate[l]), planes_of(c->up[l]), act_k(c->act_dim, dim), c->ffn_act, c->h, hidden_l, dim / 256, hx,
                (signed char*)hp, (float*)(hp ? hp + alh.off_d : nullptr), (short*)(hp ? hp + alh.off_aux : nullptr),
                (signed char*)(hp ? hp + alh.off_p : nullptr), nx, nw, normin ? 1e-5f : 0.f, nsums, sum_parts);
     } else {
       launch_k(st, R, k_gateup<FMT>, dim3((hidden_l + 1) / 2), dim3(128), 0, planes_of(c->gate[l]), planes_of(c->up[l]),
-               act_k(c->act_dim, dim), (const unsigned short*)dev->exp_table, c->h, hidden_l, dim / BE);
+               act_k(c->act_dim, dim), c->ffn_act, c->h, hidden_l, dim / BE);
     }
     CH_TRY(P1());
     if (!qin) launch_quantize_act(st, QT, c->h, (size_t)hidden_l, c->act_hid);
@@ -1511,7 +1523,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     return launch_gemv_strict(dev, w, m, k, act, B, out);
   };
   k_embed<<<dim3((dim + 255) / 256, rows), 256, 0, st>>>((const char*)c->token_embed->ptr, (int)c->token_embed->dtype,
-                                                         c->token_embed->wl.off_scale, c->pf_tokens, dim, c->pf_x);
+                                                         c->token_embed->wl.off_scale, c->pf_tokens, dim, c->pf_x, c->embed_scale);
   // Q8_0 / Q8_1 rhs: residual add + RMSNorm + quantize as one launch per row (k_norm_quant_rows), SiLU * mul + quantize as one
   // (k_gateup_epi_quant): the (rows, dim) / (rows, hidden) f32 intermediates make one trip through memory instead of three
   const bool fuse_rows = (c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1) && !(g.flags & CRABML_HIP_LLAMA_NO_PREFILL_ROW_FUSION);
@@ -1674,7 +1686,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
         hq.ovf = ovf;
       }
       gu_done = launch_gemm_f16w(dev, ws, ms, 2, (size_t)dim, c->pf_xh, B, outs, c->pf_split, c->pf_split_floats,
-                                 epi ? (const unsigned short*)dev->exp_table : nullptr, epi ? &h_done : nullptr, nullptr, &hq,
+                                 epi ? &c->ffn_act : nullptr, epi ? &h_done : nullptr, nullptr, &hq,
                                  tl ? &fc_gu : nullptr);
       if (h_done == 2) {
         a = c->pf_act_hid;
@@ -1702,17 +1714,16 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       with_const_else<0, 1>(c->qt == CRABML_HIP_Q8_1, [&](auto q) {
         constexpr bool Q = decltype(q)::value != 0;
         if (mirror)  // (ffn_down's f16 planes alongside)
-          k_gateup_epi_quant_h<Q><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
+          k_gateup_epi_quant_h<Q><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, c->ffn_act, hidden, c->pf_act_hid, alh.total,
                                                       alh.off_d, alh.off_aux, mirror, ovf);
         else
-          k_gateup_epi_quant<Q><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table, hidden, c->pf_act_hid, alh.total,
+          k_gateup_epi_quant<Q><<<gq, 256, 0, st>>>(c->pf_g, c->pf_u, c->ffn_act, hidden, c->pf_act_hid, alh.total,
                                                     alh.off_d, alh.off_aux);
       });
       xh.set(mirror ? c->pf_act_hid : nullptr, order);
       a = c->pf_act_hid;
     } else {
-      k_gateup_epi<<<(unsigned)(((size_t)B * hidden + 255) / 256), 256, 0, st>>>(c->pf_g, c->pf_u, (const unsigned short*)dev->exp_table,
-                                                                                 c->pf_g, (int)(B * hidden));
+      k_gateup_epi<<<(unsigned)(((size_t)B * hidden + 255) / 256), 256, 0, st>>>(c->pf_g, c->pf_u, c->ffn_act, c->pf_g, (int)(B * hidden));
       a = quant_rows(c->pf_g, hidden, c->pf_act_hid, c->down[l]);
     }
     CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_HID_ACT, c->pf_act_hid, B * alh.total));
@@ -2007,6 +2018,9 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   const int tp = g.tp_size > 1 ? g.tp_size : 1;
   if (!g.n_heads || !g.n_kv_heads || !g.n_layers || g.embedding_dim % g.n_heads || g.n_heads % g.n_kv_heads)
     CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: inconsistent head configuration");
+  // (asked before the divisibility checks: Gemma-2B has ONE kv head, which no tp_size > 1 divides -- the answer is "not implemented")
+  if (arch && arch->architecture == CRABML_HIP_ARCH_GEMMA && tp > 1)
+    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "gemma: tensor parallelism is not implemented");
   if (tp > 8 || g.tp_rank < 0 || g.tp_rank >= tp || g.n_kv_heads % tp || g.hidden_dim % tp)
     CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: tp_size %d must divide n_kv_heads and hidden_dim (and be <= 8)", tp);
   if (g.tp_comm) {
@@ -2031,12 +2045,13 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   if (!w->token_embed || !w->rms_final_weight || !w->wq || !w->wk || !w->wv || !w->wo || !w->ffn_gate_weight ||
       !w->ffn_down_weight || !w->ffn_up_weight || !w->rms_att_weight || !w->rms_ffn_weight)
     CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: missing weights");
-  // the architecture (model.rs:22-27): Llama, or Qwen2 = Llama + q / k / v biases + NEOX rope (llama2.rs:283-351)
+  // the architecture (model.rs:22-27): Llama; Qwen2 = Llama + q / k / v biases + NEOX rope (llama2.rs:283-351); Gemma = Llama with the
+  // embedding scaled by sqrt(dim), NEOX rope and GELU (llama2.rs:455-524; its classifier is whatever the weights say, as everywhere)
   const uint32_t archv = arch ? arch->architecture : (uint32_t)CRABML_HIP_ARCH_LLAMA;
-  const bool qwen2 = archv == CRABML_HIP_ARCH_QWEN2;
-  if (archv == CRABML_HIP_ARCH_GEMMA || archv == CRABML_HIP_ARCH_PHI2)
-    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: architecture %u (Gemma / Phi2) has no decode step here", archv);
-  if (archv != CRABML_HIP_ARCH_LLAMA && !qwen2) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: unknown architecture %u", archv);
+  const bool qwen2 = archv == CRABML_HIP_ARCH_QWEN2, gemma = archv == CRABML_HIP_ARCH_GEMMA;
+  if (archv == CRABML_HIP_ARCH_PHI2) CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: architecture %u (Phi2) has no decode step here", archv);
+  if (archv != CRABML_HIP_ARCH_LLAMA && !qwen2 && !gemma) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: unknown architecture %u", archv);
+  if (gemma && (arch->bq || arch->bk || arch->bv)) CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "gemma: there is no decode step with q / k / v biases");
   if (!qwen2 && arch && (arch->bq || arch->bk || arch->bv)) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: a Llama model has no q / k / v biases");
   if (qwen2) {
     if (tp > 1) CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "qwen2: tensor parallelism is not implemented");
@@ -2225,6 +2240,14 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
     }
   }
   c->qwen2 = qwen2;
+  c->gemma = gemma;
+  if (gemma) {  // (the table at create, not on the first gelu_inplace call: the step's graph is captured below)
+    if (rc == 0) rc = crabml_hip::ensure_gelu_table(dev);
+    c->embed_scale = std::sqrt((float)g.embedding_dim);  // (embed_dim as f32).sqrt(), llama2.rs:468
+    c->ffn_act = FfnAct{dev->gelu_table, 1};
+  } else {
+    c->ffn_act = FfnAct{dev->exp_table, 0};
+  }
   // the f16 prompt GEMM's A' range check of every matrix (gemm_f16w_takes: one reduction over the scale plane, read back), here
   // once rather than inside the first prompt pass
   if (rc == 0 && !dev->strict_order && tp == 1 && (qt == CRABML_HIP_Q8_0 || qt == CRABML_HIP_Q8_1 || qt == CRABML_HIP_Q8_K))
@@ -2399,12 +2422,12 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   }
   // RoPE table with the reference's own recurrence (rope.rs:47-54: theta_scale = 10000^(-2/hd), theta = pos,
   // theta *= theta_scale per pair; base hard-coded) evaluated with the host libm, as the trait op does.
-  // Qwen2: NEOX's table (rope.rs:65-80: theta_i = pos / 10000^(2 i / hd), i < rope_dim / 2), the trait op's own code (lazy.hip)
+  // Qwen2 and Gemma: NEOX's table (rope.rs:65-80: theta_i = pos / 10000^(2 i / hd), i < rope_dim / 2), the trait op's own code (lazy.hip)
   {
     std::vector<float> tab(g.seq_len * (size_t)(c->npairs ? c->npairs : 1) * 2, 0.f);
     const float theta_scale = powf(10000.0f, -2.0f / (float)hd);
     for (size_t p = 0; p < g.seq_len; p++) {
-      if (qwen2) {
+      if (qwen2 || gemma) {
         rope_table_neox(tab.data() + p * c->npairs * 2, p, hd, (size_t)c->npairs);
         continue;
       }
@@ -2896,14 +2919,12 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
                        (const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
                        (const int*)(base + o_pos), (float*)(base + o_part), (unsigned*)(base + o_tick), (float*)(base + o_out),
                        (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, (int)seq, (int)slices, FLASH_MIN_ROWS);
-    if (hd == 128)
-      hipLaunchKernelGGL((k_attn_flash_merge<128, false>), dim3((unsigned)n_heads), dim3(128), 0, st, (const float*)(base + o_part),
+    with_const_else<256, 128, 64>(hd, [&](auto hdc) {  // (flash_kernel has no other head_dim)
+      constexpr int HD = decltype(hdc)::value;
+      hipLaunchKernelGGL((k_attn_flash_merge<HD, false>), dim3((unsigned)n_heads), dim3(HD), 0, st, (const float*)(base + o_part),
                          (const int*)(base + o_pos), (float*)(base + o_out), (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, grp,
                          (int)slices, FLASH_MIN_ROWS);
-    else
-      hipLaunchKernelGGL((k_attn_flash_merge<64, false>), dim3((unsigned)n_heads), dim3(64), 0, st, (const float*)(base + o_part),
-                         (const int*)(base + o_pos), (float*)(base + o_out), (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, grp,
-                         (int)slices, FLASH_MIN_ROWS);
+    });
     if (ticket_form) {
       e = hipMemcpyAsync(out2, base + o_out, nq, hipMemcpyDeviceToHost, st);  // (stream order: before the next launches overwrite it)
       for (int rep = 0; rep < 2 && e == hipSuccess; rep++)
@@ -2986,7 +3007,11 @@ int lazy_ctx_create(crabml_hip_device* dev, const LazyModel& m, crabml_hip_llama
   if (m.rms_att.size() != L || m.rms_ffn.size() != L || m.wq.size() != L || m.wk.size() != L || m.wv.size() != L || m.wo.size() != L ||
       m.gate.size() != L || m.down.size() != L || m.up.size() != L || m.kc.size() != L || m.vc.size() != L)
     return CRABML_HIP_BAD_INPUT;
-  if (!m.qwen2) return llama_create_impl(dev, &m.cfg, &w, m.kc.data(), m.vc.data(), out);
+  if (m.arch == CRABML_HIP_ARCH_LLAMA) return llama_create_impl(dev, &m.cfg, &w, m.kc.data(), m.vc.data(), out);
+  if (m.arch == CRABML_HIP_ARCH_GEMMA) {
+    const crabml_hip_llama_arch_t arch{CRABML_HIP_ARCH_GEMMA, nullptr, nullptr, nullptr};
+    return llama_create_impl(dev, &m.cfg, &w, m.kc.data(), m.vc.data(), out, &arch);
+  }
   if (m.bq.size() != L || m.bk.size() != L || m.bv.size() != L) return CRABML_HIP_BAD_INPUT;
   const crabml_hip_llama_arch_t arch{CRABML_HIP_ARCH_QWEN2, m.bq.data(), m.bk.data(), m.bv.data()};
   return llama_create_impl(dev, &m.cfg, &w, m.kc.data(), m.vc.data(), out, &arch);

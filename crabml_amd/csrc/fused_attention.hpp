@@ -870,7 +870,10 @@ __device__ __forceinline__ float flash_row_sum(float v) {
   v += dpp_f<0xB1>(v);
   v += dpp_f<0x4E>(v);
   v += dpp_f<0x141>(v);
-  if constexpr (LPR == 16) v += dpp_f<0x140>(v);
+  if constexpr (LPR >= 16) v += dpp_f<0x140>(v);
+  // head_dim 256: a row is the two 16-lane DPP rows of a 32-lane half, and no DPP row operation crosses them -- one swizzle (bit mode:
+  // and 0x1f, or 0, xor 0x10, i.e. lane ^ 16 inside every group of 32) adds the other row's sum
+  if constexpr (LPR == 32) v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), 0x401F));
   return v;
 }
 #define FLASH_MIN_ROWS 64  /* measured on MI355X, 8B shape: 64 <= 128 <= 256 at every context (profiles/r04_flash_sweep.log) */
@@ -892,7 +895,7 @@ __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const floa
                                                                      unsigned short* __restrict__ xd, void* __restrict__ xisum, int seq_cap,
                                                                      int Smax, int min_rows) {
   constexpr int NW = FlashGeom<G>::NW, LPR = HD / 8, RPI = 64 / LPR, NCLS = NW * RPI, U = 4, NT = NW * 64;
-  static_assert(HD == 64 || HD == 128, "a K / V row is 8 or 16 lanes x 16 bytes");
+  static_assert(HD == 64 || HD == 128 || HD == 256, "a K / V row is 8, 16 or 32 lanes x 16 bytes");
   typedef _Float16 h2 __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) float fl_lds[];
   float* sacc = fl_lds;                 // [NCLS][G][HD]

@@ -138,12 +138,18 @@ __device__ __forceinline__ void prefetch_wg(const PrefetchPlan& pf, int wg, int 
 }
 
 // ---- embedding lookup: copy_rows_from(token_embed, [token]) (llama2.rs:222-223) ----------------------
+// scale: Gemma's x.scale_inplace(sqrt(embed_dim)) (llama2.rs:468) -- one f32 multiply of the dequantized value, a rounding of its own;
+// 1.0f (every other architecture) takes the path without it (a kernel-uniform branch)
 __global__ __launch_bounds__(256) void k_embed(const char* __restrict__ w, int dtype, size_t off_scale,
-                                               const int* __restrict__ token_d, int dim, float* __restrict__ x) {
+                                               const int* __restrict__ token_d, int dim, float* __restrict__ x, float scale) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= dim) return;
   // blockIdx.y: row of a prefill batch (token ids and output rows are consecutive); 0 for a decode step
-  x[(size_t)blockIdx.y * dim + i] = dequant_elem(w, dtype, off_scale, (size_t)token_d[blockIdx.y] * dim + i);
+  const float v = dequant_elem(w, dtype, off_scale, (size_t)token_d[blockIdx.y] * dim + i);
+  if (scale != 1.0f)
+    x[(size_t)blockIdx.y * dim + i] = v * scale;
+  else
+    x[(size_t)blockIdx.y * dim + i] = v;
 }
 
 // ---- rmsnorm * weight -> Q8_0 planes ------------------------------------------------------------------
@@ -381,7 +387,9 @@ __device__ __forceinline__ void qkv_epilogue(const QkvEpi& e, const QkvPre& pre,
 
 // ---- Qwen2's q|k|v stage (llama2.rs:283-351): forward_llama plus a bias per q / k / v row (:315-317) and NEOX rope (:325-326) ----
 // The architecture is a template parameter of the q|k|v kernels: the Llama instantiations are the code above, untouched.
-enum { QKV_LLAMA = 0, QKV_QWEN2 = 1 };
+// QKV_GEMMA (llama2.rs:484-502): the NEOX pairs WITHOUT the bias loads and adds -- not Qwen2's form fed zeros: -0.0 + 0.0 is +0.0, and
+// the strict-order device matches the reference bit for bit.
+enum { QKV_LLAMA = 0, QKV_QWEN2 = 1, QKV_GEMMA = 2 };
 struct QkvEpiB : QkvEpi {
   const float* bq;  // (dim) f32: q = wq x + bq, one f32 add per row (add_inplace, arithmetic.rs)
   const float* bk;  // (kv_dim)
@@ -390,6 +398,8 @@ struct QkvEpiB : QkvEpi {
 struct QkvPreB : QkvPre {
   float b0, b1;  // the biases of the pair's two rows
 };
+// Gemma's epilogue arguments: Llama's fields, a type of their own (the launch sites pick the kernels' ARCH by the argument type)
+struct QkvEpiN : QkvEpi {};
 template <int ARCH>
 struct QkvArch {
   typedef QkvEpi epi;
@@ -399,6 +409,11 @@ template <>
 struct QkvArch<QKV_QWEN2> {
   typedef QkvEpiB epi;
   typedef QkvPreB pre;
+};
+template <>
+struct QkvArch<QKV_GEMMA> {
+  typedef QkvEpiN epi;
+  typedef QkvPre pre;
 };
 // NEOX rotates the pair (i, i + hd / 2) of every head, i < rope_dim / 2 (rope.rs:65-80): wave / thread `p` of the q and k rows owns
 // rows h hd + i and h hd + i + hd / 2 (h = head, i in [0, hd / 2)); the v rows keep adjacent pairs.  Returns the pair's first row (q|k|v
@@ -416,8 +431,10 @@ __device__ __forceinline__ int neox_pair_row0(const QkvEpi& e, int p, int& rs) {
 }
 // position, rotation and the two biases of the pair at (row0, row0 + rs), requested ahead of the weight stream by every lane (one
 // address each: a load inside a lane-predicated branch would make the wave wait for it before its first weight request)
-__device__ __forceinline__ QkvPreB qkv_preload_neox(const QkvEpiB& e, int row0, int rs, int row_of_batch = 0) {
-  QkvPreB p;
+template <class E>  // QkvEpiB (Qwen2) or QkvEpiN (Gemma: no bias loads)
+__device__ __forceinline__ auto qkv_preload_neox(const E& e, int row0, int rs, int row_of_batch = 0) {
+  constexpr bool BIAS = std::is_same<E, QkvEpiB>::value;
+  typename std::conditional<BIAS, QkvPreB, QkvPre>::type p;
   p.pos = *e.pos_d + row_of_batch;
   const bool qk = row0 < e.dim + e.kv_dim;
   const int local = row0 < e.dim ? row0 : qk ? row0 - e.dim : row0 - e.dim - e.kv_dim;
@@ -426,15 +443,20 @@ __device__ __forceinline__ QkvPreB qkv_preload_neox(const QkvEpiB& e, int row0, 
   const float* cs = e.rope + ((size_t)p.pos * e.npairs + (p.rot ? i : 0)) * 2;  // the NEOX table: entry i is theta_i (rope.rs:70-73)
   p.c = cs[0];
   p.s = cs[1];
-  const float* b = row0 < e.dim ? e.bq : qk ? e.bk : e.bv;
-  p.b0 = b[local];
-  p.b1 = b[local + rs];
+  if constexpr (BIAS) {
+    const float* b = row0 < e.dim ? e.bq : qk ? e.bk : e.bv;
+    p.b0 = b[local];
+    p.b1 = b[local + rs];
+  }
   return p;
 }
-__device__ __forceinline__ void qkv_epilogue_neox(const QkvEpiB& e, const QkvPreB& pre, int row0, int rs, float s0, float s1) {
+template <class E, class P>
+__device__ __forceinline__ void qkv_epilogue_neox(const E& e, const P& pre, int row0, int rs, float s0, float s1) {
   const int pos = pre.pos;
-  s0 = s0 + pre.b0;  // the bias before rope and before the KV append (llama2.rs:315-317)
-  s1 = s1 + pre.b1;
+  if constexpr (std::is_same<E, QkvEpiB>::value) {
+    s0 = s0 + pre.b0;  // the bias before rope and before the KV append (llama2.rs:315-317)
+    s1 = s1 + pre.b1;
+  }
   if (row0 < e.dim + e.kv_dim) {
     float r0 = s0, r1 = s1;
     if (pre.rot) {
@@ -480,7 +502,7 @@ struct Planes6 {
 };
 
 // DEFER: the rhs planes come from a hop-free ffn_down launch -- the row dots are multiplied by 1 / rms (RmsTail, gemv_core.hpp)
-// ARCH = QKV_QWEN2: the wave's two rows are a NEOX pair (neox_pair_row0), the biases are added after the 1 / rms multiply
+// ARCH = QKV_QWEN2 / QKV_GEMMA: the wave's two rows are a NEOX pair (neox_pair_row0); Qwen2's biases are added after the 1 / rms multiply
 template <int FMT, bool DEFER = false, int ARCH = QKV_LLAMA>
 __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb,
                                              typename QkvArch<ARCH>::epi e, Planes6 wv6, RmsTail rt, int upfront = 0) {

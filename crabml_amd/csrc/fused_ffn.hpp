@@ -856,14 +856,11 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq_ord(Planes w, typename Act
   }
 }
 
-// ---- gate/up GEMV + SiLU * mul: h[i] = silu(Wg[i].xq) * (Wu[i].xq)   (silu.rs:6-13, arithmetic.rs:57-66) ---
-__device__ __forceinline__ float silu_mul(float g, float u, const unsigned short* __restrict__ exp_tab) {
-  float nexp = exp_cached_f(-g, exp_tab);
-  return (g / (1.0f + nexp)) * u;
-}
+// ---- gate/up GEMV + activation * mul: h[i] = act(Wg[i].xq) * (Wu[i].xq)   (silu.rs:6-13 / gelu.rs:10-22, arithmetic.rs:57-66) ---
+// (ffn_act_mul, devutil.hpp: SiLU, or Gemma's GELU lookup, by the launch's FfnAct argument)
 template <int FMT>
 __global__ __launch_bounds__(128) void k_gateup(Planes wg, Planes wu, typename ActOf<FMT>::type act,
-                                                const unsigned short* __restrict__ exp_tab, float* __restrict__ h, int m, int nb) {
+                                                FfnAct fa, float* __restrict__ h, int m, int nb) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * (blockDim.x >> 6) + wave_in_wg();
   if (row >= m) return;
@@ -871,7 +868,7 @@ __global__ __launch_bounds__(128) void k_gateup(Planes wg, Planes wu, typename A
   rows_dot<FMT, 1>(wg.q, wg.d, act, row, m, nb, lane, ag);
   rows_dot<FMT, 1>(wu.q, wu.d, act, row, m, nb, lane, au);
   const float g = wave_sum_f32(ag[0]), u = wave_sum_f32(au[0]);
-  if (lane == 0) h[row] = silu_mul(g, u, exp_tab);
+  if (lane == 0) h[row] = ffn_act_mul(g, u, fa);
 }
 // Q4_K gate/up with the Q8_K activation planes staged in LDS once per workgroup (1024 threads = 32 hidden rows x
 // {gate, up}): the per-lane activation reads (2 x 16 B + d + 2 bsums per 16 B of quants) leave the vector-memory
@@ -888,7 +885,7 @@ __global__ __launch_bounds__(128) void k_gateup(Planes wg, Planes wu, typename A
 // (nq_epilogue: a chunk = its halves; 64 chunks per round through wave_sum_f32; rounds added in order), so the planes are bit for
 // bit the ones wo used to leave.
 template <bool QOUT, bool ORD = false, bool NORMIN = false>
-__global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, ActQ8_K act, const unsigned short* __restrict__ exp_tab,
+__global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, ActQ8_K act, FfnAct fa,
                                                        float* __restrict__ h, int m, int nsb, Q8KExchange ex, signed char* __restrict__ oq,
                                                        float* __restrict__ od, short* __restrict__ obs, signed char* __restrict__ oqp,
                                                        const float* __restrict__ xin, const float* __restrict__ wnorm, float eps,
@@ -983,7 +980,7 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
       const float s = q4k_ordered_sum(T + (size_t)lane * stride, nsb);  // lane < 32: gate row `lane`; else up row `lane - 32`
       const float u = __shfl(s, (lane & 31) + 32, 64);
       if (lane < 32) {
-        const float hval = silu_mul(s, u, exp_tab);
+        const float hval = ffn_act_mul(s, u, fa);
         h[(int)blockIdx.x * 32 + lane] = hval;
         hv[lane] = hval;
       }
@@ -1010,7 +1007,7 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
   for (int r = 0; r < 2; r++) {
     const float g = wave_sum_f32(ag[r]), u = wave_sum_f32(au[r]);
     if (lane == 0 && row0 + r < m) {
-      const float hval = silu_mul(g, u, exp_tab);
+      const float hval = ffn_act_mul(g, u, fa);
       h[row0 + r] = hval;
       if (QOUT) hv[wave * 2 + r] = hval;
     }
@@ -1030,7 +1027,7 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
 // DEFER: the rhs planes come from a hop-free wo launch -- the row dots are multiplied by 1 / rms (RmsTail, gemv_core.hpp)
 template <int FMT, bool DEFER = false>
 __global__ __launch_bounds__(1024) void k_gateup_q(Planes wg, Planes wu, typename ActOf<FMT>::type act,
-                                                   const unsigned short* __restrict__ exp_tab, signed char* __restrict__ q,
+                                                   FfnAct fa, signed char* __restrict__ q,
                                                    unsigned short* __restrict__ d, void* __restrict__ isum, int nb, RmsTail rt) {
   using F = BlockFmt<FMT>;
   constexpr bool Q81 = FMT == CRABML_HIP_Q4_1;
@@ -1093,8 +1090,8 @@ __global__ __launch_bounds__(1024) void k_gateup_q(Planes wg, Planes wu, typenam
     u1 *= inv_rms;
   }
   if (lane == 0) {
-    hv[wave * 2] = silu_mul(g0, u0, exp_tab);
-    hv[wave * 2 + 1] = silu_mul(g1, u1, exp_tab);
+    hv[wave * 2] = ffn_act_mul(g0, u0, fa);
+    hv[wave * 2 + 1] = ffn_act_mul(g1, u1, fa);
   }
   __syncthreads();
   if (threadIdx.x < 32) {
@@ -1111,7 +1108,7 @@ __global__ __launch_bounds__(1024) void k_gateup_q(Planes wg, Planes wu, typenam
 // CUs (112 of 256 at the 70B / 8 shape: 10.8 us for 33 MB, a CU streams ~26 GB/s whatever is resident), the host picks a row
 // count that gives one workgroup per CU.  Same dots, same SiLU * mul: h -- and the planes ffn_down makes of it -- bit for bit.
 template <int FMT>
-__global__ __launch_bounds__(1024) void k_gateup_h(Planes wg, Planes wu, typename ActOf<FMT>::type act, const unsigned short* __restrict__ exp_tab,
+__global__ __launch_bounds__(1024) void k_gateup_h(Planes wg, Planes wu, typename ActOf<FMT>::type act, FfnAct fa,
                                                    float* __restrict__ h, int m, int nb) {
   using F = BlockFmt<FMT>;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1135,8 +1132,8 @@ __global__ __launch_bounds__(1024) void k_gateup_h(Planes wg, Planes wu, typenam
   g1 = wave_sum_f32(g1);
   u1 = wave_sum_f32(u1);
   if (lane == 0) {
-    h[row] = silu_mul(g0, u0, exp_tab);
-    h[row + 1] = silu_mul(g1, u1, exp_tab);
+    h[row] = ffn_act_mul(g0, u0, fa);
+    h[row + 1] = ffn_act_mul(g1, u1, fa);
   }
 }
 // strict order: k_gateup_q with the block terms of the 32 gate and 32 up rows parked in LDS (row stride nt + 4 floats: the 64 chain
@@ -1145,7 +1142,7 @@ __global__ __launch_bounds__(1024) void k_gateup_h(Planes wg, Planes wu, typenam
 __host__ __device__ inline size_t gateup_q_ord_lds_bytes(int nb) { return (size_t)64 * (((nb + 3) & ~3) + 4) * sizeof(float); }
 template <int FMT>
 __global__ __launch_bounds__(1024) void k_gateup_q_ord(Planes wg, Planes wu, typename ActOf<FMT>::type act,
-                                                       const unsigned short* __restrict__ exp_tab, signed char* __restrict__ q,
+                                                       FfnAct fa, signed char* __restrict__ q,
                                                        unsigned short* __restrict__ d, void* __restrict__ isum, int nb) {
   constexpr bool Q81 = FMT == CRABML_HIP_Q4_1;
   extern __shared__ __attribute__((aligned(16))) float ord_terms[];
@@ -1160,7 +1157,7 @@ __global__ __launch_bounds__(1024) void k_gateup_q_ord(Planes wg, Planes wu, typ
   if (wave == 0) {
     const float s = ordered_sum(ord_terms + (size_t)lane * nt, nb);  // lane < 32: gate row `lane`; else up row `lane - 32`
     const float u = __shfl(s, (lane & 31) + 32, 64);
-    const float h = lane < 32 ? silu_mul(s, u, exp_tab) : 0.0f;
+    const float h = lane < 32 ? ffn_act_mul(s, u, fa) : 0.0f;
     const QLane o = quant_lane32<Q81>(h, lane < 32);  // (whole wave: the upper half quantizes zeros and stores nothing)
     if (lane < 32) {
       q[blk * 32 + lane] = o.q;
@@ -1172,21 +1169,21 @@ __global__ __launch_bounds__(1024) void k_gateup_q_ord(Planes wg, Planes wu, typ
   }
 }
 __global__ __launch_bounds__(256) void k_gateup_epi(const float* __restrict__ g, const float* __restrict__ u,
-                                                    const unsigned short* __restrict__ exp_tab, float* __restrict__ h, int m) {
+                                                    FfnAct fa, float* __restrict__ h, int m) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) h[i] = silu_mul(g[i], u[i], exp_tab);
+  if (i < m) h[i] = ffn_act_mul(g[i], u[i], fa);
 }
 
 // batched prefill, Q8_0 / Q8_1 rhs: h = silu(g) * u quantized straight into the rows' planes (one 32-lane half-wave per block:
 // quant_lane32 = the quantizer launch's arithmetic) -- the (rows, hidden) f32 h never goes to memory and back
 template <bool Q81>
 __global__ __launch_bounds__(256) void k_gateup_epi_quant(const float* __restrict__ g, const float* __restrict__ u,
-                                                          const unsigned short* __restrict__ exp_tab, int hidden, char* __restrict__ planes,
+                                                          FfnAct fa, int hidden, char* __restrict__ planes,
                                                           size_t row_stride, size_t off_d, size_t off_aux) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;  // hidden % 32 == 0: half-waves are all-live or all-dead
   const size_t r = blockIdx.y;
   const bool live = i < hidden;
-  const float h = live ? silu_mul(g[r * hidden + i], u[r * hidden + i], exp_tab) : 0.0f;
+  const float h = live ? ffn_act_mul(g[r * hidden + i], u[r * hidden + i], fa) : 0.0f;
   const QLane o = quant_lane32<Q81>(h, live);
   if (!live) return;
   char* p = planes + r * row_stride;

@@ -189,16 +189,11 @@ struct F16wMats {
   float* out[3];
   float* out2[3];    // ksplit > 1: k piece s >= 1 writes its partial tiles to out2[j] + (s - 1) pstride (k_addn_f32 adds them)
   size_t pstride;
-  const unsigned short* exp_tab;  // GU launches: the f16 exp table of silu (silu.rs:6-13)
+  FfnAct act;                      // GU launches: the activation of h = act(g) * u and its f16 table (ffn_act_mul, devutil.hpp)
   F16wHQuant hq;                   // GU launches: h leaves as Q8_0 / Q8_1 planes (+ ffn_down's B') instead of f32 (planes == nullptr: f32)
   int m[3];
   int tiles_end[3];  // cumulative row tiles
 };
-// h = silu(g) * u (silu.rs:6-13, arithmetic.rs:57-66; fused_ffn.hpp silu_mul: the exp through the reference's f16 table)
-__device__ __forceinline__ float f16w_silu_mul(float g, float u, const unsigned short* __restrict__ exp_tab) {
-  const float nexp = h2f(exp_tab[f2h(-g)]);
-  return (g / (1.0f + nexp)) * u;
-}
 // GU (F = 2, two matrices of the same shape: ffn_gate and ffn_up): fragment 0 holds 16 rows of the FIRST matrix, fragment 1 the same
 // 16 rows of the SECOND -- the workgroup owns 64 rows of both -- and the epilogue stores h = silu(g) * u (out[0]) instead of g and u:
 // the (rows, hidden) f32 pair never makes its trip through memory (llama2.rs:620-630).  One k piece only (silu is not linear).
@@ -444,7 +439,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
       for (int t = 0; t < T; t++) {
         f32x4 hv;
 #pragma unroll
-        for (int r = 0; r < 4; r++) hv[r] = f16w_silu_mul(acc[0][t][r], acc[1][t][r], mats.exp_tab);
+        for (int r = 0; r < 4; r++) hv[r] = ffn_act_mul(acc[0][t][r], acc[1][t][r], mats.act);
         *(f32x4*)(H + (16 * t + i) * CS + wave * 16 + 4 * g) = hv;
       }
       __syncthreads();
@@ -514,7 +509,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
       const int row = r0 + 4 * g;
       f32x4 hv;
 #pragma unroll
-      for (int r = 0; r < 4; r++) hv[r] = f16w_silu_mul(acc[0][t][r], acc[1][t][r], mats.exp_tab);
+      for (int r = 0; r < 4; r++) hv[r] = ffn_act_mul(acc[0][t][r], acc[1][t][r], mats.act);
       float* o = out + (size_t)col * m + row;
       if (row + 3 < m) {
         *(f32x4*)o = hv;
@@ -659,7 +654,7 @@ static bool launch_f16w_fmt(crabml_hip_device* dev, const F16wMats& mats, int ro
 // others their own partial buffers in ws, and k_addn_f32 adds them in piece order.  (Measured and not kept: the pieces added with
 // f32 atomics onto a zeroed output -- 32.4k -> 30.1k prompt tok/s, and the sum's order would vary from run to run.)
 bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, const size_t* m, int nw, size_t k, void* xh, size_t b,
-                      float* const* out, float* ws, size_t ws_floats, const unsigned short* gu_exp_tab, int* gu_done, int* defer_parts,
+                      float* const* out, float* ws, size_t ws_floats, const FfnAct* gu_act, int* gu_done, int* defer_parts,
                       const F16wHQuant* hq, F16wForce* force) {
   if (gu_done) *gu_done = 0;
   if (defer_parts) *defer_parts = 0;
@@ -697,7 +692,7 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
   }
   // gate | up with the SiLU * mul epilogue (out[0] = h, out[1] untouched): when 64-row tiles of both matrices cover the chip without
   // cutting k
-  const bool gu_ok = gu_exp_tab != nullptr && gu_done != nullptr && nw == 2 && m[0] == m[1];
+  const bool gu_ok = gu_act != nullptr && gu_done != nullptr && nw == 2 && m[0] == m[1];
   bool gu = gu_ok && !(variant & 64) && ((m[0] + 63) / 64) * col128 * 2 >= (size_t)dev->n_cu * 3;
   if (force && force->gu >= 0) {
     if (force->gu > 0 && !gu_ok) return false;
@@ -705,7 +700,7 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
   }
   if (gu) F = 2;
   F16wMats mats{};
-  mats.exp_tab = gu_exp_tab;
+  mats.act = gu_act ? *gu_act : FfnAct{nullptr, 0};
   const bool hquant = gu && hq != nullptr && hq->planes != nullptr && m[0] % 32 == 0;
   if (hquant) mats.hq = *hq;
   F16wParts parts{};

@@ -337,17 +337,17 @@ inline bool ggml_block_geometry(uint32_t t, size_t* block_bytes, size_t* block_e
 }
 inline bool GGUFFile::ggml_block_geometry_(uint32_t t, size_t* bb, size_t* be) { return ggml_block_geometry(t, bb, be); }
 
-// CpuLlamaModelLoader::load_config (model.rs:545-625), llama and qwen2 architectures (the keys under the architecture's prefix)
+// CpuLlamaModelLoader::load_config (model.rs:545-625), llama, gemma and qwen2 architectures (the keys under the architecture's prefix)
 inline LlamaConfig load_llama_config(const GGUFFile& gf) {
   const std::string p = gf.architecture();
-  if (p != "llama" && p != "qwen2") throw Error(ErrorKind::ModelError, "unsupported architecture " + p);
+  if (p != "llama" && p != "qwen2" && p != "gemma") throw Error(ErrorKind::ModelError, "unsupported architecture " + p);
   auto need_u32 = [&](const std::string& k) -> size_t {
     auto v = gf.get_u32(k);
     if (!v) throw Error(ErrorKind::ModelError, "missing u32 metadata " + k);  // the reference unwrap()s here
     return *v;
   };
   LlamaConfig c;
-  c.architecture = p == "qwen2" ? ARCH_QWEN2 : ARCH_LLAMA;
+  c.architecture = p == "qwen2" ? ARCH_QWEN2 : p == "gemma" ? ARCH_GEMMA : ARCH_LLAMA;
   c.n_heads = need_u32(p + ".attention.head_count");
   c.n_layers = need_u32(p + ".block_count");
   c.hidden_dim = need_u32(p + ".feed_forward_length");
@@ -394,7 +394,7 @@ inline HipTensor load_gguf_tensor(const GGUFFile& gf, const std::string& name, c
   return HipTensor::from_cpu(info->data, nbytes, dims, (GGMLType)info->ggml_type, device);
 }
 
-// CpuLlamaModelLoader::load_weights (model.rs:140-300, "llama" arm; "qwen2" arm :285-360: + blk.N.attn_{q,k,v}.bias in their stored
+// CpuLlamaModelLoader::load_weights (model.rs:140-300, the "llama" | "gemma" arm :229; "qwen2" arm :285-360: + blk.N.attn_{q,k,v}.bias in their stored
 // type) + output.weight optional (model.rs:437)
 inline std::shared_ptr<LlamaWeights<HipTensor>> load_llama_weights(const GGUFFile& gf, const LlamaConfig& conf,
                                                                   const HipTensorDeviceRef& device) {

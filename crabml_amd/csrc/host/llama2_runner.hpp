@@ -2,7 +2,7 @@
 // reference: `Llama2Runner<T: Tensor>` (crabml-llama2/src/llama2.rs:26-43).  It issues the same op
 // sequence per decode step (forward :184-211, forward_llama :213-281, forward_multi_query_attention
 // :527-603, forward_ffn :605-638), so running it over HipTensor is what "crabml-llama2 runs unchanged"
-// means on this side of the boundary.  Llama and Qwen2 (forward_qwen2 :283-351); gemma / phi2 are out of scope.
+// means on this side of the boundary.  Llama, Qwen2 (forward_qwen2 :283-351) and Gemma (forward_gemma :455-524); phi2 is out of scope.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -224,9 +224,11 @@ class Llama2Runner {
 
   // llama2.rs:184-211
   void forward(const std::vector<size_t>& tokens, size_t pos) {
-    if (conf_.architecture != ARCH_LLAMA && conf_.architecture != ARCH_QWEN2)
-      throw Error(ErrorKind::NotImplemented, "Llama2Runner: only the llama and qwen2 architectures");
-    T x = conf_.architecture == ARCH_QWEN2 ? forward_qwen2(tokens, pos) : forward_llama(tokens, pos);
+    if (conf_.architecture != ARCH_LLAMA && conf_.architecture != ARCH_QWEN2 && conf_.architecture != ARCH_GEMMA)
+      throw Error(ErrorKind::NotImplemented, "Llama2Runner: only the llama, qwen2 and gemma architectures");
+    T x = conf_.architecture == ARCH_QWEN2   ? forward_qwen2(tokens, pos)
+          : conf_.architecture == ARCH_GEMMA ? forward_gemma(tokens, pos)
+                                             : forward_llama(tokens, pos);
     T x_final = T::alloc({conf_.embedding_dim}, f32_, device_);
     x_final.copy_rows_from(x, {tokens.size() - 1});
     const T& ow = weights_->output_weight ? *weights_->output_weight : weights_->token_embed;
@@ -320,6 +322,40 @@ class Llama2Runner {
     return x.with_name("final_rmsnorm:" + std::to_string(pos));
   }
 
+  // llama2.rs:455-524: forward_llama with the embedding scaled by sqrt(embed_dim) (:468), NEOX rope (:499-500), GELU (:512) and its own
+  // with_name placement (none after attention)
+  T forward_gemma(const std::vector<size_t>& tokens, size_t pos) {
+    const size_t embed_dim = conf_.embedding_dim, n_heads = conf_.n_heads, n_kv_heads = conf_.n_kv_heads;
+    const size_t head_dim = conf_.head_size();
+    const size_t rope_dim = conf_.rope_dim.value_or(head_dim);
+    const size_t n_batch = tokens.size();
+    const LlamaWeights<T>& w = *weights_;
+    T x = T::alloc({n_batch, embed_dim}, f32_, device_);
+    x.copy_rows_from(w.token_embed, tokens);
+    x = x.scale_inplace(std::sqrt((float)embed_dim));
+    x = x.with_name("scaled_embed");
+    for (size_t l = 0; l < conf_.n_layers; l++) {
+      T x_attn_orig = x.dup();
+      x = x.rms_norm_inplace(conf_.rms_norm_eps);
+      x = x.mul_inplace(w.rms_att_weight[l]);
+      x = x.with_name("attn_rmsnorm:" + std::to_string(l) + ":" + std::to_string(pos));
+      T q = w.wq[l].matmul_vec(x);
+      T k = w.wk[l].matmul_vec(x);
+      T v = w.wv[l].matmul_vec(x);
+      q = q.reshape({n_heads, head_dim});
+      k = k.reshape({n_kv_heads, head_dim});
+      q = q.rope_inplace(T::rope_mode_neox(), pos, rope_dim);
+      k = k.rope_inplace(T::rope_mode_neox(), pos, rope_dim);
+      x = forward_multi_query_attention(q, k, v, l, n_kv_heads, n_heads, embed_dim, head_dim, n_batch);
+      x = x.add_inplace(x_attn_orig);
+      x = forward_ffn(x, l, Activation::GeLU);
+      x = x.with_name("ffn_out:" + std::to_string(l) + ":" + std::to_string(pos));
+    }
+    x = x.rms_norm_inplace(conf_.rms_norm_eps);
+    x = x.mul_inplace(w.rms_final_weight);
+    return x.with_name("final_rmsnorm:" + std::to_string(pos));
+  }
+
   // llama2.rs:527-603
   T forward_multi_query_attention(T q, T k, T v, size_t l, size_t n_kv_heads, size_t n_heads, size_t embed_dim,
                                   size_t head_dim, size_t n_batch) {
@@ -347,14 +383,15 @@ class Llama2Runner {
   }
 
   // llama2.rs:605-638 -- the FFN norm's eps is the literal 1e-5
-  T forward_ffn(T x, size_t l) {
+  enum class Activation { SiLU, GeLU };
+  T forward_ffn(T x, size_t l, Activation activation = Activation::SiLU) {
     const LlamaWeights<T>& w = *weights_;
     T x_orig_ffn = x.dup();
     x = x.rms_norm_inplace(1e-5f);
     x = x.mul_inplace(w.rms_ffn_weight[l]);
     T h1 = w.ffn_gate_weight[l].matmul_vec(x);
     T h2 = w.ffn_up_weight[l].matmul_vec(x);
-    h1 = h1.silu_inplace();
+    h1 = activation == Activation::SiLU ? h1.silu_inplace() : h1.gelu_inplace();
     h1 = h1.mul_inplace(h2);
     x = w.ffn_down_weight[l].matmul_vec(h1);
     return x.add_inplace(x_orig_ffn);

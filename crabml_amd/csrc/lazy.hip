@@ -61,6 +61,18 @@ static float gelu_single(float x) {  // gelu.rs:19-22
   return 0.5f * x * (1.0f + tanhf(S * x * (1.0f + COEF_A * x * x)));
 }
 
+// the device's f16 GELU table, built on first use: OnceLock<Vec<f16>> (cpu_device.rs:117-124).  The first gelu_inplace call asks, and
+// so does the creation of a Gemma decode context (fused.hip), whose gate | up kernels read it.
+int ensure_gelu_table(crabml_hip_device* dev) {
+  if (dev->gelu_table || dev->dry) return 0;
+  std::vector<uint16_t> tab(65536);
+  for (uint32_t i = 0; i < 65536; i++) tab[i] = host_f2h(gelu_single(host_h2f((uint16_t)i)));
+  CH_HIP(dev, hipMalloc((void**)&dev->gelu_table, 65536 * 2));
+  CH_HIP(dev, hipMemcpyAsync(dev->gelu_table, tab.data(), 65536 * 2, hipMemcpyHostToDevice, dev->stream));
+  CH_HIP(dev, hipStreamSynchronize(dev->stream));
+  return 0;
+}
+
 // ---- the launches of one recorded op (arguments were validated when the op was recorded) ----------------------------------
 int lazy_exec(crabml_hip_device* dev, LazyOp& o) {
   if (o.a) CH_TRY(ensure_mem(dev, o.a));
@@ -124,13 +136,7 @@ int lazy_exec(crabml_hip_device* dev, LazyOp& o) {
       touch(o.a);
       break;
     case LZ_GELU:
-      if (!dev->gelu_table) {  // OnceLock<Vec<f16>> (cpu_device.rs:117-124)
-        std::vector<uint16_t> tab(65536);
-        for (uint32_t i = 0; i < 65536; i++) tab[i] = host_f2h(gelu_single(host_h2f((uint16_t)i)));
-        CH_HIP(dev, hipMalloc((void**)&dev->gelu_table, 65536 * 2));
-        CH_HIP(dev, hipMemcpyAsync(dev->gelu_table, tab.data(), 65536 * 2, hipMemcpyHostToDevice, st));
-        CH_HIP(dev, hipStreamSynchronize(st));
-      }
+      CH_TRY(ensure_gelu_table(dev));
       launch_gelu(st, (float*)o.a->ptr, s[0], dev->gelu_table);
       touch(o.a);
       break;
@@ -200,9 +206,11 @@ int run_queue(crabml_hip_device* dev, LazyState& L) {
 }
 
 // ---- learning: parse one complete token of Llama2Runner::forward (llama2.rs:184-281, 527-638; n_batch = 1) ----------------
-// Two sequences are accepted: forward_llama's, and forward_qwen2's (llama2.rs:283-351) -- the same with q / k / v.add_inplace(bias)
-// after the three GEMVs of EVERY layer and NEOX rope.  Adds with Llama rope, NEOX without adds, a layer without its adds, a bias that is
-// not an f32 vector of the GEMV's length: not learned (the token runs op by op).
+// Three sequences are accepted: forward_llama's, forward_qwen2's (llama2.rs:283-351) -- the same with q / k / v.add_inplace(bias)
+// after the three GEMVs of EVERY layer and NEOX rope -- and forward_gemma's (llama2.rs:455-524): x.scale_inplace(sqrt(dim)) right after
+// the embedding copy, NEOX rope without adds, gelu_inplace in EVERY layer.  Adds with Llama rope, NEOX without adds (and without all of
+// Gemma's other marks), a layer without its adds, a bias that is not an f32 vector of the GEMV's length, a scale that is not exactly
+// sqrtf(dim), SiLU in a Gemma layer: not learned (the token runs op by op).
 struct Learner {
   const std::vector<LazyOp>& q;
   size_t i;
@@ -269,6 +277,13 @@ bool learn_token(Learner& P, LazyModel& M, int* slot_xnorm, int* slot_xfinal, in
   size_t pos = 0, hd = 0, kv_dim = 0, hidden = 0, n_heads = 0, n_kv = 0, seq = 0, rope_dim = 0;
   uint32_t kv_dtype = 0;
   bool qwen2 = false;
+  // forward_gemma: x.scale_inplace((embed_dim as f32).sqrt())                             gemma :468
+  const bool gemma = P.i < P.q.size() && P.q[P.i].kind == LZ_SCALE;
+  if (gemma) {
+    o = P.take(LZ_SCALE);
+    NEED(o->a == x && o->s[0] == dim && o->f == std::sqrt((float)dim));
+    P.push(*o);
+  }
   float eps = 0.f;
   int l = 0;
   while (P.i < P.q.size() && P.q[P.i].kind == LZ_DUP) {
@@ -306,7 +321,7 @@ bool learn_token(Learner& P, LazyModel& M, int* slot_xnorm, int* slot_xfinal, in
     // forward_qwen2: q / k / v.add_inplace(&bq / bk / bv[l])                                qwen2 :315-317
     const bool adds = P.i < P.q.size() && P.q[P.i].kind == LZ_ADD;
     if (first) qwen2 = adds;
-    NEED(adds == qwen2);
+    NEED(adds == qwen2 && !(gemma && adds));
     if (qwen2) {
       const crabml_hip_buf* const outs[3] = {qv, kv, vv};
       const size_t lens[3] = {dim, kv_dim, kv_dim};
@@ -318,8 +333,8 @@ bool learn_token(Learner& P, LazyModel& M, int* slot_xnorm, int* slot_xfinal, in
         P.push(*o);
       }
     }
-    const size_t rope_mode = qwen2 ? CRABML_HIP_ROPE_NEOX : CRABML_HIP_ROPE_LLAMA;
-    o = P.take(LZ_ROPE);  // q.rope_inplace(Llama | Neox, pos, rope_dim)                 :255, qwen2 :325
+    const size_t rope_mode = qwen2 || gemma ? CRABML_HIP_ROPE_NEOX : CRABML_HIP_ROPE_LLAMA;
+    o = P.take(LZ_ROPE);  // q.rope_inplace(Llama | Neox, pos, rope_dim)                 :255, qwen2 :325, gemma :499
     NEED(o && o->a == qv && o->s[0] == 1 && o->s[1] == dim && o->s[3] == rope_mode);
     if (first) {
       hd = o->s[2];
@@ -406,7 +421,7 @@ bool learn_token(Learner& P, LazyModel& M, int* slot_xnorm, int* slot_xfinal, in
     const crabml_hip_buf* h2 = o->out;
     M.up.push_back(o->a);
     P.push(*o);
-    o = P.take(LZ_SILU);  // h1.silu_inplace()                                             :626
+    o = P.take(gemma ? LZ_GELU : LZ_SILU);  // h1.silu_inplace() | gelu_inplace()          :625-626
     NEED(o && o->a == h1 && o->s[0] == hidden);
     P.push(*o);
     o = P.take(LZ_MUL);  // h1.mul_inplace(h2)                                             :628
@@ -457,7 +472,7 @@ bool learn_token(Learner& P, LazyModel& M, int* slot_xnorm, int* slot_xfinal, in
   c.use_f16_kv_cache = kv_dtype == CRABML_HIP_F16 ? 1 : 0;
   c.flags = 0;  // (the step's graph is captured: the whole token is launched as soon as its position is verified)
   c.tp_size = 1;
-  M.qwen2 = qwen2;
+  M.arch = gemma ? CRABML_HIP_ARCH_GEMMA : qwen2 ? CRABML_HIP_ARCH_QWEN2 : CRABML_HIP_ARCH_LLAMA;
   return true;
 }
 #undef NEED

@@ -8,7 +8,7 @@
 // data -- export / sync / debug hooks, the same contract as the wgpu backend (crabml-wgpu/src/wgpu_tensor.rs:293-333) -- run
 // the queue.  Two ways to run it:
 //   * op by op, exactly the launches of the eager path (anything the matcher does not know, CRABML_HIP_FLAG_LAZY_NO_FUSION);
-//   * as the fused step: the first complete token of a Llama model is parsed against the op sequence of forward_llama /
+//   * as the fused step: the first complete token of a Llama (Qwen2, Gemma) model is parsed against the op sequence of forward_llama /
 //     forward_multi_query_attention / forward_ffn (every operand identity, shape and scalar is checked: see learn_token), a
 //     decode context is built over the runner's OWN weight and KV-cache buffers, and a template of the token is kept.  From the
 //     next token on every recorded op is compared with the template as it arrives, and as soon as the ops of a SEGMENT are in
@@ -86,13 +86,14 @@ struct LazyModel {
   const crabml_hip_buf* output = nullptr;
   std::vector<const crabml_hip_buf*> rms_att, rms_ffn, wq, wk, wv, wo, gate, down, up;
   std::vector<crabml_hip_buf*> kc, vc;  // the runner's KV caches: [n_kv_heads][seq_len][head_dim], f16 or f32
-  // forward_qwen2 (llama2.rs:283-351): the q / k / v biases of every layer; empty for forward_llama
-  bool qwen2 = false;
+  // which forward the token was (crabml_hip_model_arch): the same buffers under another op sequence are another model
+  uint32_t arch = CRABML_HIP_ARCH_LLAMA;
+  // forward_qwen2 (llama2.rs:283-351): the q / k / v biases of every layer; empty for forward_llama and forward_gemma
   std::vector<const crabml_hip_buf*> bq, bk, bv;
   bool same_buffers(const LazyModel& o) const {
     return token_embed == o.token_embed && rms_final == o.rms_final && output == o.output && rms_att == o.rms_att && rms_ffn == o.rms_ffn &&
            wq == o.wq && wk == o.wk && wv == o.wv && wo == o.wo && gate == o.gate && down == o.down && up == o.up && kc == o.kc && vc == o.vc &&
-           qwen2 == o.qwen2 && bq == o.bq && bk == o.bk && bv == o.bv;
+           arch == o.arch && bq == o.bq && bk == o.bk && bv == o.bv;
   }
 };
 
@@ -180,6 +181,7 @@ inline float host_h2f(uint16_t u) {
 }
 
 // ---- lazy.hip
+int ensure_gelu_table(crabml_hip_device* dev);  // dev->gelu_table, built on first use (gelu_inplace, a Gemma decode context)
 // the rhs of matmul_vec quantized to `qt` (cached per buffer version: q/k/v and gate/up share one pass)
 int ensure_act(crabml_hip_device* dev, const crabml_hip_buf* x, size_t b, size_t k, uint32_t qt, const void** act);
 int lazy_record(crabml_hip_device* dev, const LazyOp& op);  // retains the operands, feeds the matcher

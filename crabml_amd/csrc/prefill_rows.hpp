@@ -247,13 +247,13 @@ __global__ __launch_bounds__(1024) void k_norm_quant_rows_k(float* __restrict__ 
 // k_gateup_epi_quant (h = silu(g) * u quantized straight into the rows' Q8_0 / Q8_1 planes) + the rows' B' (order 0)
 template <bool Q81>
 __global__ __launch_bounds__(256) void k_gateup_epi_quant_h(const float* __restrict__ g, const float* __restrict__ u,
-                                                            const unsigned short* __restrict__ exp_tab, int hidden, char* __restrict__ planes,
+                                                            FfnAct fa, int hidden, char* __restrict__ planes,
                                                             size_t row_stride, size_t off_d, size_t off_aux, unsigned short* __restrict__ xh,
                                                             int* __restrict__ ovf) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;  // hidden % 32 == 0: half-waves are all-live or all-dead
   const size_t r = blockIdx.y;
   const bool live = i < hidden;
-  const float h = live ? silu_mul(g[r * hidden + i], u[r * hidden + i], exp_tab) : 0.0f;
+  const float h = live ? ffn_act_mul(g[r * hidden + i], u[r * hidden + i], fa) : 0.0f;
   const QLane o = quant_lane32<Q81>(h, live);
   if (!live) return;
   char* p = planes + r * row_stride;

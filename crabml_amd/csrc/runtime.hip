@@ -1083,7 +1083,8 @@ int crabml_hip_debug_gemm_f16w(crabml_hip_device_t* dev, const crabml_hip_buf_t*
       hqs.ovf = (int*)d[4];
     }
     const bool gu_asked = want_gu > 0 || (want_gu < 0 && nw == 2);
-    ran = launch_gemm_f16w(dev, w, m, (int)nw, k, d[1], b, outs, (float*)d[3], ws_floats, gu_asked ? dev->exp_table : nullptr,
+    const FfnAct silu{dev->exp_table, 0};
+    ran = launch_gemm_f16w(dev, w, m, (int)nw, k, d[1], b, outs, (float*)d[3], ws_floats, gu_asked ? &silu : nullptr,
                            gu_asked ? &gu_done : nullptr, nullptr, want_gu == 2 ? &hqs : nullptr, &fc);
     if (ran && want_gu > 0 && gu_done != want_gu) ran = false;
     e = hipGetLastError();

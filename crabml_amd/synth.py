@@ -140,7 +140,9 @@ class ModelShape:
     seq_len: int
     rms_eps: float = 1e-5
     rope_dim: Optional[int] = None
-    arch: str = "llama"  # general.architecture: "llama" or "qwen2" (q / k / v biases, NEOX rope: llama2.rs:283-351)
+    # general.architecture: "llama", "qwen2" (q / k / v biases, NEOX rope: llama2.rs:283-351) or "gemma" (embedding x sqrt(dim), NEOX
+    # rope, GELU: llama2.rs:455-524)
+    arch: str = "llama"
     tied: bool = False   # no output.weight: the classifier is token_embd (llama2.rs:203-207)
 
     @property
@@ -167,6 +169,11 @@ SHAPES = {
     # tiny Qwen2 shapes for tests: GQA group 4 with head_dim 64, and Qwen2.5-7B's group of 7 with head_dim 128 (dims multiples of 256)
     "tiny-qwen2": ModelShape("tiny-qwen2", 512, 1024, 2, 8, 2, 1024, 64, 1e-6, None, "qwen2"),
     "tiny-qwen2-g7": ModelShape("tiny-qwen2-g7", 1792, 1024, 2, 14, 2, 1024, 64, 1e-6, None, "qwen2"),
+    # Gemma-2B: multi-query attention with head_dim 256 (8 heads on 1 kv head), tied classifier (seq_len as for Qwen2) ...
+    "gemma-2b": ModelShape("Gemma-2B", 2048, 16384, 18, 8, 1, 256000, 8192, 1e-6, None, "gemma", True),
+    # ... and tiny shapes with its head_dim for tests: group 2, and Gemma-2B's group of 8
+    "tiny-gemma": ModelShape("tiny-gemma", 512, 1024, 2, 2, 1, 1024, 256, 1e-6, None, "gemma", True),
+    "tiny-gemma-g8": ModelShape("tiny-gemma-g8", 2048, 1024, 2, 8, 1, 1024, 256, 1e-6, None, "gemma", True),
 }
 
 
@@ -227,12 +234,15 @@ def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional
     files -- attn_v and ffn_down in Q6_K on the `use_more_bits` layers, output.weight in Q6_K -- i.e. different
     GGML types inside one layer (all with the Q8_K rhs).  arch = "qwen2" (default: the shape's): blk.N.attn_{q,k,v}.bias as F32
     N(0, 1) with a few channels per vector 20-60x larger (real Qwen2 k biases reach the hundreds), from a generator of their own:
-    the weights are those of the same seed's Llama model, and Llama models stay byte-identical."""
+    the weights are those of the same seed's Llama model, and Llama models stay byte-identical.  arch = "gemma": no biases, and the
+    classifier tied (no output.weight) unless the shape says otherwise -- a Gemma shape's own `tied` decides, any other shape built as
+    Gemma is tied."""
     rng = np.random.default_rng(seed)
     L = shape.n_layers if n_layers is None else n_layers
     arch = shape.arch if arch is None else arch
-    assert arch in ("llama", "qwen2"), arch
-    shp = ModelShape(**{**shape.__dict__, "n_layers": L, "arch": arch})
+    assert arch in ("llama", "qwen2", "gemma"), arch
+    tied = shape.tied or (arch == "gemma" and shape.arch != "gemma")
+    shp = ModelShape(**{**shape.__dict__, "n_layers": L, "arch": arch, "tied": tied})
     m = RawModel(shp, wtype)
     et = wtype if embed_type is None else embed_type
 
@@ -265,7 +275,7 @@ def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional
                 b[big] *= brng.uniform(20.0, 60.0, size=big.size).astype(np.float32)
                 m.tensors[f"blk.{l}.{nm}.bias"] = RawTensor(b.view(np.uint8), [n], F32)
     norm("output_norm.weight", shape.dim)
-    if shape.tied and output_type is None and not k_m_mix:
+    if tied and output_type is None and not k_m_mix:
         return m
     # llama.cpp's "Q4_0" / "Q4_K_M" files keep output.weight in Q6_K: `output_type` builds that mix
     # tp_split_vocab (with tp > 1): one rank's vocabulary shard of the classifier (CRABML_HIP_LLAMA_TP_SPLIT_VOCAB)
@@ -322,7 +332,7 @@ _GGUF_FMT = {"u8": "<B", "i8": "<b", "u16": "<H", "i16": "<h", "u32": "<I", "i32
 
 def write_gguf(model: RawModel, path: str, version: int = 3, alignment: int = 32, write_alignment_key=None,
                extra_kv=None, tensor_order=None, data_start: str = "reference", pad_header_to_alignment: bool = False) -> None:
-    """Serialize a RawModel as a GGUF file of its architecture ("llama" or "qwen2": the keys under that prefix, model.rs:553-633).  write_alignment_key: None = omit general.alignment
+    """Serialize a RawModel as a GGUF file of its architecture ("llama", "qwen2" or "gemma": the keys under that prefix, model.rs:553-633).  write_alignment_key: None = omit general.alignment
     (readers assume 32), or a value-type name ("u32", "u64", "i32", ...) to store `alignment` under that type.
     extra_kv: list of (key, type_name, value); arrays as (key, "arr", (elem_type_name, [values])).
     data_start: "reference" = always skip to the NEXT multiple of the alignment (gguf.rs:722-724: a whole extra block when
@@ -409,7 +419,7 @@ def write_gguf(model: RawModel, path: str, version: int = 3, alignment: int = 32
 
 
 def load_gguf_hip(path: str, device):
-    """(LlamaConfig, LlamaWeights<HipTensor>) of a llama or qwen2 GGUF file through the C++ loader (gguf.hpp)."""
+    """(LlamaConfig, LlamaWeights<HipTensor>) of a llama, qwen2 or gemma GGUF file through the C++ loader (gguf.hpp)."""
     import crabml_amd as ca
 
     gf = ca.GGUFFile(path)

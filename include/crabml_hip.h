@@ -272,11 +272,14 @@ typedef struct crabml_hip_llama_arch {
   const crabml_hip_buf_t* const* bk; /* n_layers x (kv_dim) F32 (llama2.rs:316) */
   const crabml_hip_buf_t* const* bv; /* n_layers x (kv_dim) F32 (llama2.rs:317) */
 } crabml_hip_llama_arch_t;
-/* crabml_hip_llama_create for Llama2Runner::forward_qwen2 (llama2.rs:283-351): forward_llama with the q / k / v biases added to the
- * GEMV outputs and NEOX rope (rope.rs:65-80).  arch == NULL, or LLAMA with NULL biases, is crabml_hip_llama_create.  The other calls
- * (forward, decode_greedy, decode_sample, prefill, reset, destroy) serve the context unchanged; the biases are retained like the
- * weights.  CRABML_HIP_NOT_IMPLEMENTED: GEMMA, PHI2, QWEN2 with tp_size > 1.  CRABML_HIP_BAD_INPUT: an unknown architecture, a
- * missing bias, one that is not F32 or not of its row count, biases on a LLAMA model. */
+/* crabml_hip_llama_create for the other architectures.  QWEN2, Llama2Runner::forward_qwen2 (llama2.rs:283-351): forward_llama with the
+ * q / k / v biases added to the GEMV outputs and NEOX rope (rope.rs:65-80).  GEMMA, forward_gemma (llama2.rs:455-524): forward_llama
+ * with the embedded row multiplied by sqrtf(embedding_dim), NEOX rope, no biases (bq / bk / bv NULL) and h = gelu(g) * u through the
+ * f16 GELU table (gelu.rs:10-22); the classifier is output_weight, or token_embed where it is NULL (real Gemma files are tied).
+ * arch == NULL, or LLAMA with NULL biases, is crabml_hip_llama_create.  The other calls (forward, decode_greedy, decode_sample, prefill,
+ * reset, destroy) serve the context unchanged; the biases are retained like the weights.  CRABML_HIP_NOT_IMPLEMENTED: PHI2, QWEN2 or
+ * GEMMA with tp_size > 1, GEMMA with biases.  CRABML_HIP_BAD_INPUT: an unknown architecture, a missing Qwen2 bias, one that is not
+ * F32 or not of its row count, biases on a LLAMA model. */
 int crabml_hip_llama_create_arch(crabml_hip_device_t* dev, const crabml_hip_llama_config_t* cfg, const crabml_hip_llama_weights_t* w,
                                  const crabml_hip_llama_arch_t* arch, crabml_hip_llama_t** out);
 int crabml_hip_llama_destroy(crabml_hip_llama_t* ctx);

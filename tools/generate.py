@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Token-id level counterpart of `crabml-cli generate` for the hip backend: load a llama or qwen2 GGUF file through the C++
+"""Token-id level counterpart of `crabml-cli generate` for the hip backend: load a llama, qwen2 or gemma GGUF file through the C++
 loader (crabml_amd/csrc/host/gguf.hpp), prefill a prompt in batched passes, decode on the device: greedily by default, with
 Llama2Sampler's temperature / top-p (crabml-llama2/src/sampler.rs) under --temperature > 0 -- the first token from the prompt's
 logits on the host (C++ Llama2Sampler), the rest by crabml_hip_llama_decode_sample, coins from a seeded generator.
@@ -8,7 +8,8 @@ The tokenizer stays on the reference's side of the boundary (out of scope here),
 usage: generate.py model.gguf [--prompt 1,15043,3186] [--steps 64] [--seq-len N] [--f32-kv] [--strict]
                    [--temperature 1.0 --topp 0.9 --seed 0]
        generate.py --synth tiny-gqa:Q4_K_M   (writes a synthetic file to a temp dir first: a self-contained demo)
-       generate.py --synth qwen2.5-7b:Q4_0   (a Qwen2 file: q / k / v biases, NEOX rope)"""
+       generate.py --synth qwen2.5-7b:Q4_0   (a Qwen2 file: q / k / v biases, NEOX rope)
+       generate.py --synth gemma-2b:Q8_0     (a Gemma file: scaled embedding, NEOX rope, GELU, tied classifier)"""
 import argparse
 import os
 import sys
@@ -21,7 +22,7 @@ from crabml_amd import synth
 
 ap = argparse.ArgumentParser()
 ap.add_argument("gguf", nargs="?")
-ap.add_argument("--synth", default=None, help="SHAPE:TYPE, e.g. tiny-gqa:Q4_0, llama3-8b:Q4_K_M, qwen2.5-7b:Q4_0")
+ap.add_argument("--synth", default=None, help="SHAPE:TYPE, e.g. tiny-gqa:Q4_0, llama3-8b:Q4_K_M, qwen2.5-7b:Q4_0, gemma-2b:Q8_0")
 ap.add_argument("--prompt", default="1,365,400,282,7,9,11,13")
 ap.add_argument("--steps", type=int, default=32)
 ap.add_argument("--seq-len", type=int, default=0)
