@@ -23,6 +23,10 @@
 // ffn_down), norm_nit, the *_lds_bytes functions beside their kernels, and the *_kernel selectors that hand out the function pointer
 // of every kernel whose limit is raised.  with_const / with_const_else (kernels.hpp) turn a run-time value into the template argument, so a launch's
 // argument list is written once; test_hook (common.hpp) is what arms an A/B or tuning hook.
+// Which launches a context runs at all -- the segment path, its ordered form, the segment forms and the attention forms -- is decided once,
+// by decide_step at create, as one value (StepPlan, c->plan); crabml_hip_debug_step_plan (crabml_hip_debug.h) reads it out for any
+// configuration, on the record-only test device too, and tests/test_step_plan.py / tests/test_hip_step_plan.py hold the table.
+#include <algorithm>
 #include <chrono>
 #include <thread>
 #include <cmath>
@@ -136,10 +140,43 @@ struct TapField {
   size_t cols = 0, rows = 1;
 };
 
+// What a context runs, as one value: decide_step makes it at create, every reader goes through c->plan, and
+// crabml_hip_debug_step_plan (crabml_hip_debug.h) hands it out.
+enum class SegPath { PerOp = 0, Fused5 = 1, FusedK = 2 };  // enqueue_segment_generic / enqueue_segment_t / enqueue_segment_k
+struct StepPlan {
+  SegPath path = SegPath::PerOp;
+  bool ordered = false;        // strict-order device: the fused launches with block-ordered sums (Fused5: k_*_ord; FusedK: the ORD forms)
+  // ---- the segment forms
+  bool norm_epi = false;       // Fused5: RMSNorm + quantize run in the wo / ffn_down epilogue (tp > 1: over a P2P group or in the dry run,
+                               // where the epilogue hosts the collective too)
+  bool norm_epi_k = false;     // the same for Q4_K layers (Q8_K planes out of the epilogue)
+  // the hop-free norm of the fast step (Q4_0 / Q8_0 layers, one GPU): wo quantizes x * w_norm block by block and leaves 1 / rms to
+  // the gate/up launch (RmsTail, gemv_core.hpp) -- no in-launch gather.  Off: CRABML_HIP_LLAMA_EXACT_NORM, strict order, tp.
+  bool defer_norm = false;
+  int gu_rows = 0;             // > 0 (tensor-parallel ranks): gate/up leaves h as f32 from workgroups of this many rows, ffn_down quantizes it
+  bool q8k_producers = false;  // attention / gate-up emit the Q8_K planes of wo's / ffn_down's rhs themselves
+  bool k_norm_in = false;      // fast Q4_K step: gate | up normalizes and quantizes wo's f32 row itself (k_gateup_k_lds<.., NORMIN>)
+  // ---- the attention forms (attn_variant 0 = one workgroup per head, 1 = the long-context kernels, 2 = variant 1's ticket form)
+  bool attn_long_ok = false;   // variant 1 exists: exact_long_ok or attn_flash
+  bool exact_long_ok = false;  // the exact long-context kernels (score / probability rows of seq_len elements read as 16-byte vectors):
+                               // f16 cache, head_dim % 32 == 0, group size in {1, 2, 4, 8}, seq_len % 8 == 0
+  size_t attn_long_from = 0;   // cached positions (pos + 1) from which variant 1 is used
+  bool pv_split = false;       // variant 1, exact: k_attn_pv_split (products by producer waves) instead of k_attn_pv
+  bool attn_flash = false;     // variant 1 of the FAST step: k_attn_flash (split-KV, f32 accumulation) instead of the three exact kernels
+  bool flash_ticket = false;   // A/B: the merge by the last-arriving workgroup inside k_attn_flash instead of its own launch
+  size_t flash_ticket_until = 0;  // > 0: positions [attn_long_from, this) run variant 2
+  bool attn_flash_rows = false;   // the batched prefill's attention runs k_attn_flash_rows (fast step, f16 cache, head_dim 64 / 128)
+  int flash_S = 0;                // position slices (workgroups) per kv head
+  int flash_min_rows = FLASH_MIN_ROWS;  // cached rows per active slice, at least
+  int attn_s_rows = 0;         // > 0: variant 0 runs k_attn_s (K / V staged through LDS) with room for this many cached rows
+  size_t attn_s_lds = 0;
+};
+
 struct crabml_hip_llama {
   crabml_hip_device* dev = nullptr;
   crabml_hip_llama_config_t cfg{};
   uint32_t wtype = 0;
+  StepPlan plan;  // which launches the context runs (decide_step)
   int tp = 1, tp_rank = 0;
   crabml_hip_tp_comm* comm = nullptr;
   // local (per-rank) geometry
@@ -163,7 +200,7 @@ struct crabml_hip_llama {
   float* partial = nullptr;  // tp > 1: this rank's wo / ffn_down partial sums (dim), all-reduced in place
   float* qbuf = nullptr;     // roped, scaled q (dim_l)
   float* attn = nullptr;     // attention output (dim_l)
-  float* h = nullptr;        // ffn hidden (hidden_l), strict mode only
+  float* h = nullptr;        // ffn hidden as f32 (hidden_l): the per-op and K-quant segments, and ffn_down's prologue under gu_rows
   float* logits = nullptr;   // vocab
   float* host_logits = nullptr; // lazy.hip: pinned host copy of the logits, written by a kernel behind the classifier; the two words
                                 // behind the vocab_size floats are {sequence number of the step that wrote them, its fault word}
@@ -171,30 +208,20 @@ struct crabml_hip_llama {
   unsigned lazy_serial = 0;     // lazy.hip: the step serial is set by the host at every begin (see lazy_ctx_begin)
   bool ext_kv = false;          // lazy.hip: kc / vc are the runner's own cache buffers (retained in `held`), not allocations of ours
   const crabml_hip_buf* ext_kc0 = nullptr;  // ... the first layer's K cache handle (lazy_ctx_orphaned)
-  float* tmp = nullptr;      // strict-mode GEMV outputs
-  char* act_dim = nullptr;   // Q8_0 planes of the normalized residual (dim)
-  char* act_attn = nullptr;  // Q8_0 planes of the attention output (dim_l)
-  char* act_hid = nullptr;   // Q8_0 planes of the ffn hidden vector (hidden_l)
+  float* tmp = nullptr;      // per-op segments: the GEMV outputs (q | k | v, gate | up, wo / ffn_down in front of the residual add)
+  char* act_dim = nullptr;   // planes of the normalized residual (dim) in the rhs type `qt` (the final row: `out_qt`)
+  char* act_attn = nullptr;  // `qt` planes of the attention output (dim_l)
+  char* act_hid = nullptr;   // `qt` planes of the ffn hidden vector (hidden_l)
   float* rope = nullptr;     // [seq_len][npairs][2]
   int* state = nullptr;      // token, pos, step, sink, serial (never reset), fault
   unsigned long long* slots = nullptr;  // dim/32 {chunk sum, epoch} granules of the norm epilogue
   unsigned long long* a8gran = nullptr;  // Q4_K layers: granules of the attention output (dim_l) and of h (hidden_l), through which
   unsigned long long* h8gran = nullptr;  // the producing kernels assemble Q8_K super-blocks (q8k_exchange_store)
-  bool q8k_producers = false;            // attention / gate-up emit the Q8_K planes of wo's / ffn_down's rhs themselves
   unsigned tp_salt = 0;      // P2P group: epoch salt of this context (see TpP2P::salt)
   bool tp_dry = false;       // CRABML_HIP_LLAMA_TP_DRY_RUN: a lone rank that skips the all-reduces (timing only)
-  bool k_norm_in = false;    // fast Q4_K step: gate | up normalizes and quantizes wo's f32 row itself (k_gateup_k_lds<.., NORMIN>)
-  bool kfused = false;       // Q4_K layers, fast mode: fused GEMV kernels with the Q4_K inner loop (enqueue_segment_k)
-  bool generic = false;      // per-op launches (strict-order device, or a weight format without fused kernels)
-  bool ord = false;          // strict-order device, Q4_0 / Q8_0 / Q4_1 layers: the fused launches with block-ordered sums (k_*_ord)
   uint32_t qt = 0, out_qt = 0;  // vec_dot_rhs_dtype of the layer weights / of the classifier
   float* xn = nullptr;       // generic path: normalized residual (f32, dim)
-  bool norm_epi = false;     // fast mode, tp == 1: RMSNorm + quantize run in the wo / ffn_down epilogue
-  // the hop-free norm of the fast step (Q4_0 / Q8_0 layers, one GPU): wo quantizes x * w_norm block by block and leaves 1 / rms to
-  // the gate/up launch (RmsTail, gemv_core.hpp) -- no in-launch gather.  Off: CRABML_HIP_LLAMA_EXACT_NORM, strict order, tp.
-  bool defer_norm = false;
   float* rsums = nullptr;    // [dim / 16] chunk sums of squares of the residual stream
-  bool norm_epi_k = false;   // the same for Q4_K layers (Q8_K planes out of the epilogue)
   unsigned* out_tokens = nullptr;
   int out_cap = 0;
   float* am_val = nullptr;  // argmax partials
@@ -221,22 +248,8 @@ struct crabml_hip_llama {
   bool capturing = false;
   int attn_variant = 0;         // which of them the next enqueue emits: 0 = one workgroup per head, 1 = the long-context kernels,
                                 // 2 = split-KV attention with the merge inside the launch (ticket form: the mid range)
-  size_t flash_ticket_until = 0;  // > 0: positions [attn_long_from, this) run variant 2
-  bool attn_long_ok = false;    // f16 cache, head_dim % 32 == 0, group size in {1, 2, 4, 8}; and seq_len % 8 == 0 (exact kernels) or k_attn_flash
-  bool exact_long_ok = false;   // the exact long-context kernels (score / probability rows of seq_len elements read as 16-byte vectors)
-  size_t attn_long_from = 0;    // cached positions (pos + 1) from which variant 1 is used
-  bool pv_split = false;        // variant 1: k_attn_pv_split (products by producer waves) instead of k_attn_pv
-  // variant 1 of the FAST step: k_attn_flash (split-KV, f32 accumulation) instead of the three exact kernels
-  bool attn_flash = false;
-  bool flash_ticket = false;    // A/B: the merge by the last-arriving workgroup inside k_attn_flash instead of its own launch
-  bool attn_flash_rows = false; // the batched prefill's attention runs k_attn_flash_rows (fast step, f16 cache, head_dim 64 / 128)
-  int flash_S = 0;              // position slices (workgroups) per kv head
-  int flash_min_rows = FLASH_MIN_ROWS;  // cached rows per active slice, at least
   float* flash_part = nullptr;  // [n_kv_l][flash_S][G][hd + 2] partial {O, m, l}
   unsigned* flash_tick = nullptr;  // [n_kv_l] arrival counters (monotonic)
-  int gu_rows = 0;              // > 0 (tensor-parallel ranks): gate/up leaves h as f32 from workgroups of this many rows, ffn_down quantizes it
-  int attn_s_rows = 0;          // > 0: variant 0 runs k_attn_s (K / V staged through LDS) with room for this many cached rows
-  size_t attn_s_lds = 0;
   float* scores_g = nullptr;    // [n_heads_l][seq_len] f32
   unsigned short* p16 = nullptr;  // [n_heads_l][seq_len] f16 probabilities
   // batched prefill (crabml_hip_llama_prefill): row buffers for pf_cap prompt rows, allocated on first use
@@ -490,7 +503,7 @@ void launch_attn_long(crabml_hip_llama* c, int l, signed char* xq, unsigned shor
   launch_k(st, prof ? &r[1] : nullptr, k_attn_softmax<16>, dim3(c->n_heads_l), dim3(1024), (size_t)seq_cap * sizeof(float),
            (const float*)c->scores_g, pos_d, (const unsigned short*)dev->exp_table, c->p16, seq_cap, 0, dev->strict_order ? 1 : 0);
   const PvSplitKernel pv = pv_split_kernel(G);
-  if (c->pv_split)
+  if (c->plan.pv_split)
     launch_k(st, prof ? &r[2] : nullptr, pv.fn, dim3(n_kv * (hd / 32) * pv.nsub), dim3(pv.threads), pv.lds,
              (const unsigned short*)c->p16, (const unsigned short*)c->vc[l], pos_d, c->attn, xq, xd, xisum, hd, seq_cap,
              c->qt == CRABML_HIP_Q8_1 ? 1 : 0, 0);
@@ -528,21 +541,21 @@ FlashFn flash_kernel(int grp, int hd, bool q81, bool ticket) {
 }
 // which attention form serves cache position `pos` (see attn_variant)
 int variant_of(const crabml_hip_llama* c, size_t pos) {
-  if (!(c->attn_long_ok && pos + 1 >= c->attn_long_from)) return 0;
-  return c->flash_ticket_until > 0 && pos + 1 < c->flash_ticket_until ? 2 : 1;
+  if (!(c->plan.attn_long_ok && pos + 1 >= c->plan.attn_long_from)) return 0;
+  return c->plan.flash_ticket_until > 0 && pos + 1 < c->plan.flash_ticket_until ? 2 : 1;
 }
 void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned short* xd, void* xisum, bool prof) {
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
   const int hd = c->hd, grp = c->n_heads_l / c->n_kv_l;
   const bool q81 = c->qt == CRABML_HIP_Q8_1;
-  const bool ticket = c->flash_ticket || c->attn_variant == 2;
+  const bool ticket = c->plan.flash_ticket || c->attn_variant == 2;
   const FlashFn fn = flash_kernel(grp, hd, q81, ticket);
   crabml_hip_device::ProfRec r[2];
   if (prof) prof_begin(dev, &r[0], CRABML_HIP_F32, 7, 0.0);
-  launch_k(st, prof ? &r[0] : nullptr, fn, dim3(c->n_kv_l * c->flash_S), dim3((grp == 8 ? 4 : 8) * 64), flash_lds_bytes(grp, hd),
+  launch_k(st, prof ? &r[0] : nullptr, fn, dim3(c->n_kv_l * c->plan.flash_S), dim3((grp == 8 ? 4 : 8) * 64), flash_lds_bytes(grp, hd),
            (const float*)c->qbuf, (const unsigned short*)c->kc[l], (const unsigned short*)c->vc[l], (const int*)(c->state + 1), c->flash_part,
-           c->flash_tick, c->attn, xq, xd, xisum, (int)c->cfg.seq_len, c->flash_S, c->flash_min_rows);
+           c->flash_tick, c->attn, xq, xd, xisum, (int)c->cfg.seq_len, c->plan.flash_S, c->plan.flash_min_rows);
   if (prof) prof_end(dev, &r[0]);
   if (ticket) return;
   if (prof) prof_begin(dev, &r[1], CRABML_HIP_F32, 8, 0.0);
@@ -552,7 +565,7 @@ void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
     with_const_else<0, 1>(q81, [&](auto q) {
       constexpr int HD = decltype(hdc)::value;
       launch_k(st, R1, k_attn_flash_merge<HD, decltype(q)::value != 0>, dim3(c->n_heads_l), dim3(HD), 0, (const float*)c->flash_part, pos_d,
-               c->attn, xq, xd, xisum, grp, c->flash_S, c->flash_min_rows);
+               c->attn, xq, xd, xisum, grp, c->plan.flash_S, c->plan.flash_min_rows);
     });
   });
   if (prof) prof_end(dev, &r[1]);
@@ -564,7 +577,7 @@ void enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
   hipStream_t st = dev->stream;
   const int hd = c->hd, seq_cap = (int)c->cfg.seq_len, n_heads = c->n_heads_l, n_kv = c->n_kv_l;
   const int* pos_d = c->state + 1;
-  if (c->attn_variant >= 1 && c->attn_flash) {
+  if (c->attn_variant >= 1 && c->plan.attn_flash) {
     launch_attn_flash(c, l, xq, xd, xisum, prof);
     return;
   }
@@ -577,10 +590,10 @@ void enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
   crabml_hip_device::ProfRec ar{};
   crabml_hip_device::ProfRec* AR = prof ? &ar : nullptr;
   if (prof) prof_begin(dev, &ar, CRABML_HIP_F32, 7, 0.0);
-  if (c->attn_s_rows > 0)
-    launch_k(st, AR, attn_s_kernel(hd), dim3(n_heads + spare), dim3(256), c->attn_s_lds, (const float*)c->qbuf, (const unsigned short*)c->kc[l],
+  if (c->plan.attn_s_rows > 0)
+    launch_k(st, AR, attn_s_kernel(hd), dim3(n_heads + spare), dim3(256), c->plan.attn_s_lds, (const float*)c->qbuf, (const unsigned short*)c->kc[l],
              (const unsigned short*)c->vc[l], pos_d, (const unsigned short*)dev->exp_table, c->attn, xq, xd, xisum, n_heads, n_kv, hd, seq_cap,
-             c->attn_s_rows, pf, (k8 ? 2 : c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr, k8 ? *k8 : AttnQ8K{});
+             c->plan.attn_s_rows, pf, (k8 ? 2 : c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr, k8 ? *k8 : AttnQ8K{});
   else
     with_const_else<0, 1>(c->cfg.use_f16_kv_cache != 0, [&](auto kv16) {
       launch_k(st, AR, k_attn<decltype(kv16)::value != 0>, dim3(n_heads + spare), dim3(256), attn_lds, (const float*)c->qbuf, (const void*)c->kc[l],
@@ -733,19 +746,19 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     const float* addv = add_pending ? c->partial : nullptr;
     with_const_else<4, 12>(norm_nit(dim), [&](auto nit) {
       launch_k(st, prof ? &nr : nullptr, k_norm_quant<decltype(nit)::value, Q81>, dim3(1 + spare), dim3(1024), norm_lds, c->x, addv, wn, dim, eps, ad.q,
-               ad.d, ad.isum, pf, c->ord ? 0 : 1);
+               ad.d, ad.isum, pf, c->plan.ordered ? 0 : 1);
     });
     if (prof) prof_end(dev, &nr);
   };
   // W(dim x k_local) . act -> x (+= residual) or partial (tp)
-  const bool norm_epi = c->norm_epi;
+  const bool norm_epi = c->plan.norm_epi;
   // q / k / v rows of exactly 128 units: both 64-unit steps requested up front (5.29 -> 4.66 us per launch on the 8B shape,
   // profiles/r06_small_stage_ab.md; bit-identical).  A/B hook: CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_QKV_UPFRONT=0 keeps the two rounds.
   static const int qkv_upfront = test_hook_off("CRABML_HIP_QKV_UPFRONT") ? 0 : 1;
   // the hop-free norm between wo and gate/up of a layer: decided once, for the producer and the consumer alike
-  const bool defer_wo = c->defer_norm && !Q81;
+  const bool defer_wo = c->plan.defer_norm && !Q81;
   // ... and between ffn_down of layer l and q/k/v of layer l + 1 (the last ffn_down feeds the classifier launch: exact planes)
-  const bool defer_down = c->defer_norm && !Q81;
+  const bool defer_down = c->plan.defer_norm && !Q81;
   // wnext / eps_next: the RMSNorm that consumes this GEMV's output (norm epilogue only)
   auto gemv_out = [&](const crabml_hip_buf* w, const ActPtrs& a, int k, uint32_t stage, const float* wnext, float eps_next, bool defer = false,
                       const float* xin = nullptr) -> int {
@@ -772,7 +785,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
         }
       } else if (tpv.n > 1) {  // tensor parallel over a P2P group: the collective runs inside this launch
         nq(NqForm<0, true>{}, 0, nullptr, tpv);
-      } else if (c->ord) {  // strict order: the same launch with block-ordered GEMV sums and the reference's norm order
+      } else if (c->plan.ordered) {  // strict order: the same launch with block-ordered GEMV sums and the reference's norm order
         // tuning hook: 0 = never, 1 = ffn_down only, 2 = wo too (-1 / unset: the default below)
         static const int pipe_mode = test_hook_int("CRABML_HIP_ORD_PIPE", -1);
         // measured (profiles/r04_strict_order_decode.md): the pipelined chain pays in ffn_down for every format, in wo for Q8_0 only
@@ -789,7 +802,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       } else {
         nq(NqForm<0>{}, 0, nullptr, NoTp{});
       }
-    } else if (c->ord) {
+    } else if (c->plan.ordered) {
       launch_k(st, R, k_gemv_res_ord<FMT>, dim3((dim + 7) / 8), dim3(256), ord_terms_lds_bytes(k / 32), planes_of(w), act_view<FMT>(a), c->x, dim, k / 32);
     } else if (tp) {
       launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), act_view<FMT>(a), dst, dim, k / 32);
@@ -810,7 +823,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       // the classifier has its own rhs type (e.g. Q6_K -> Q8_K): normalize the final x to f32 and quantize for it (the
       // planes the last ffn_down epilogue wrote are in the layers' type and stay unused)
       const float* addv = tp && !norm_epi ? c->partial : nullptr;  // (fused collective: x is already final)
-      launch_norm_f32(st, c->x, addv, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, c->ord ? 0 : 1);
+      launch_norm_f32(st, c->x, addv, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, c->plan.ordered ? 0 : 1);
       if (c->out_qt == CRABML_HIP_F32) {
         cls_act = c->xn;
       } else {
@@ -845,13 +858,13 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     // waves (a tensor-parallel rank's rows; small models): two steps per request round
     const bool deferq = defer_down && l > 0;  // (defer_down: never Q4_1)
     const int upfront = deferq ? qkv_upfront : (qkv_upfront && total_rows / 2 <= 4 * dev->n_cu) ? 1 : 0;
-    if (!c->ord) {  // (what the kernel makes of them: rows_partial_rms / rows_partial, gemv_core.hpp)
+    if (!c->plan.ordered) {  // (what the kernel makes of them: rows_partial_rms / rows_partial, gemv_core.hpp)
       const int nu = dim / 32 * BlockFmt<FMT>::UNITS;
       tap.note(l, CRABML_HIP_PLAN_QKV_LOADER, deferq ? (upfront && nu == 128 ? 4 : 3) : (upfront && nu % 128 == 0 ? 2 : 1));
     }
     with_qkv_epi(c, e, l, [&](auto ep) {
       constexpr int A = QkvArchOf<decltype(ep)>::value;
-      if (c->ord)
+      if (c->plan.ordered)
         launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), ord_terms_lds_bytes(dim / 32), planes_of(c->wq[l]),
                  planes_of(c->wk[l]), planes_of(c->wv[l]), act_view<FMT>(ad), dim / 32, ep, Planes6{nullptr, 0});
       else if (deferq) {
@@ -884,12 +897,12 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     // gate / up + silu * mul (llama2.rs:620-630), local rows
     CH_TRY(P0(&pr, 3, 2.0 * hidden_l, dim));
     const RmsTail rt{c->rsums, dim / 32, 1.0f / (float)dim, 1e-5f};  // eps: the literal 1e-5 (llama2.rs:611)
-    const bool hq = c->gu_rows > 0 && !c->ord && norm_epi && !Q81 && !defer_wo;
+    const bool hq = c->plan.gu_rows > 0 && !c->plan.ordered && norm_epi && !Q81 && !defer_wo;
     if (hq) {
       if constexpr (!Q81)
-        launch_k(st, R, k_gateup_h<FMT>, dim3(hidden_l / c->gu_rows), dim3(c->gu_rows / 2 * 64), 0, planes_of(c->gate[l]), planes_of(c->up[l]),
+        launch_k(st, R, k_gateup_h<FMT>, dim3(hidden_l / c->plan.gu_rows), dim3(c->plan.gu_rows / 2 * 64), 0, planes_of(c->gate[l]), planes_of(c->up[l]),
                  act_view<FMT>(ad), c->ffn_act, c->h, hidden_l, dim / 32);
-    } else if (c->ord)
+    } else if (c->plan.ordered)
       launch_k(st, R, k_gateup_q_ord<FMT>, dim3(hidden_l / 32), dim3(1024), gateup_q_ord_lds_bytes(dim / 32), planes_of(c->gate[l]),
                planes_of(c->up[l]), act_view<FMT>(ad), c->ffn_act, ah.q, ah.d, ah.isum, dim / 32);
     else if (defer_wo) {
@@ -1019,20 +1032,20 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
   };
   // rmsnorm * weight -> xn -> Q8_K planes (buf_q8_k.rs:84-131)
   auto norm_quant = [&](const float* wn, float eps, bool add_pending, uint32_t qt) -> const void* {
-    launch_norm_f32(st, c->x, add_pending ? c->partial : nullptr, wn, dim, eps, c->xn, c->ord ? 0 : 1);
+    launch_norm_f32(st, c->x, add_pending ? c->partial : nullptr, wn, dim, eps, c->xn, c->plan.ordered ? 0 : 1);
     if (qt == CRABML_HIP_F32) return c->xn;
     launch_quantize_act(st, qt, c->xn, (size_t)dim, c->act_dim);
     return c->act_dim;
   };
   float* dst = tp ? c->partial : c->x;
-  const bool nepi = FMT == CRABML_HIP_Q4_K && c->norm_epi_k;
-  // strict-order device, Q4_K layers (c->ord): the same five launches with every sum in the reference's order -- nine-term records per
+  const bool nepi = FMT == CRABML_HIP_Q4_K && c->plan.norm_epi_k;
+  // strict-order device, Q4_K layers (c->plan.ordered): the same five launches with every sum in the reference's order -- nine-term records per
   // super-block added in order (q4k_class_terms / q4k_ordered_sum, gemv_core.hpp), the reference's norm order in the epilogue
-  const bool ordk = FMT == CRABML_HIP_Q4_K && c->ord;
+  const bool ordk = FMT == CRABML_HIP_Q4_K && c->plan.ordered;
   // wnext / eps_next: the RMSNorm that consumes this GEMV's output (norm epilogue only)
   // the rhs of wo / ffn_down quantized by the consuming kernel itself (no quantizer launch)
   const bool qin = nepi && !(g.flags & CRABML_HIP_LLAMA_NO_RHS_PROLOGUE) && dim_l % 256 == 0 && hidden_l % 256 == 0;
-  const bool qout = qin && c->q8k_producers;  // attention / gate-up write the planes, wo / ffn_down copy them
+  const bool qout = qin && c->plan.q8k_producers;  // attention / gate-up write the planes, wo / ffn_down copy them
   // wnext / eps_next: the RMSNorm that consumes this GEMV's output (norm epilogue only); xin: the f32 rhs
   // qmode: 0 = rhs planes from global memory, 1 = quantize the f32 rhs in the kernel's prologue, 2 = copy finished planes
   auto gemv_out = [&](const crabml_hip_buf* w, const Act& a, const float* xin, int k, uint32_t stage, const float* wnext,
@@ -1089,7 +1102,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     });
     CH_TRY(P1());
     // Q8_K producers: the (short-context) attention kernel assembles the planes of wo's rhs itself; wo copies them
-    const bool aq8 = qout && (g.flags & CRABML_HIP_LLAMA_Q8K_ATTN_PRODUCER) && c->attn_variant == 0 && c->attn_s_rows > 0;
+    const bool aq8 = qout && (g.flags & CRABML_HIP_LLAMA_Q8K_ATTN_PRODUCER) && c->attn_variant == 0 && c->plan.attn_s_rows > 0;
     if constexpr (FMT == CRABML_HIP_Q4_K) {
       if (aq8) {
         const ActLayout ala = act_layout(QT, (size_t)dim_l);
@@ -1104,7 +1117,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     }
     if (!qin) launch_quantize_act(st, QT, c->attn, (size_t)dim_l, c->act_attn);
     CH_TRY(gemv_out(c->wo[l], act_k(c->act_attn, dim_l), c->attn, dim_l, 2, (const float*)c->rms_ffn[l]->ptr, 1e-5f, aq8 ? 2 : qin ? 1 : 0,
-                    qout && c->k_norm_in));
+                    qout && c->plan.k_norm_in));
   } else {
     if (!nepi) norm_quant((const float*)c->rms_ffn[l]->ptr, 1e-5f, tp, QT);  // llama2.rs:611
     CH_TRY(P0(3, 2.0 * hidden_l, dim));
@@ -1113,7 +1126,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
       const Q8KExchange hx{c->h8gran, c->state + 4, c->state + 5, n_segments(c), seg};
       // the form <QOUT, ORD, NORMIN>: h leaves as Q8_K planes too / strict order / wo left x only (above) and this launch normalizes
       // and quantizes the row itself from wo's chunk sums, as many per chunk as wo had workgroups
-      const bool normin = !ordk && qout && c->k_norm_in;
+      const bool normin = !ordk && qout && c->plan.k_norm_in;
       char* const hp = qout ? c->act_hid : nullptr;  // (no planes without QOUT; hidden_l % 32 == 0: llama_create_impl)
       const float *nx = nullptr, *nw = nullptr, *nsums = nullptr;
       int sum_parts = 1;
@@ -1141,12 +1154,17 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
 }
 
 int enqueue_segment(crabml_hip_llama* c, int seg) {
-  if (c->kfused)
-    return c->wtype == CRABML_HIP_Q4_K ? enqueue_segment_k<CRABML_HIP_Q4_K>(c, seg) : enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
-  if (c->generic) return enqueue_segment_generic(c, seg);
-  return c->wtype == CRABML_HIP_Q4_0   ? enqueue_segment_t<CRABML_HIP_Q4_0>(c, seg)
-         : c->wtype == CRABML_HIP_Q8_0 ? enqueue_segment_t<CRABML_HIP_Q8_0>(c, seg)
-                                       : enqueue_segment_t<CRABML_HIP_Q4_1>(c, seg);
+  switch (c->plan.path) {
+    case SegPath::FusedK:
+      return c->wtype == CRABML_HIP_Q4_K ? enqueue_segment_k<CRABML_HIP_Q4_K>(c, seg) : enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
+    case SegPath::Fused5:
+      return c->wtype == CRABML_HIP_Q4_0   ? enqueue_segment_t<CRABML_HIP_Q4_0>(c, seg)
+             : c->wtype == CRABML_HIP_Q8_0 ? enqueue_segment_t<CRABML_HIP_Q8_0>(c, seg)
+                                           : enqueue_segment_t<CRABML_HIP_Q4_1>(c, seg);
+    case SegPath::PerOp:
+      break;
+  }
+  return enqueue_segment_generic(c, seg);
 }
 
 TpP2P p2p_view(const crabml_hip_tp_comm* m) {
@@ -1165,7 +1183,7 @@ int allreduce(crabml_hip_llama* c, int seg) {
   crabml_hip_device* dev = c->dev;
   if (c->tp_dry) return 0;  // timing-only rank: the partial sums are left as they are
   if (c->comm && c->comm->p2p) {  // one-shot P2P all-reduce as its own launch (per-op segment path)
-    if (c->norm_epi) return 0;    // fast path: the collective is fused into the wo / ffn_down epilogue
+    if (c->plan.norm_epi) return 0;    // fast path: the collective is fused into the wo / ffn_down epilogue
     const int n = (int)c->cfg.embedding_dim;
     k_tp_allreduce<<<(n + 255) / 256, 256, 0, dev->stream>>>(c->partial, n, tp_view(c, true), c->state + 4, n_segments(c), seg, 0u, 0);
     CH_HIP(dev, hipGetLastError());
@@ -1187,6 +1205,30 @@ int enqueue_step(crabml_hip_llama* c) {
   return 0;
 }
 
+// One decode step with attention variant `variant`, captured into a graph and instantiated (llama_create_impl: the greedy step, per
+// variant; run_step_sampled: the step that ends in the sampler, c->sampling set around the call).  False: nothing is left behind, and
+// the caller decides what that means.  begin_error (optional): what hipStreamBeginCapture answered.
+bool capture_step(crabml_hip_llama* c, int variant, hipGraph_t* graph_out, hipGraphExec_t* exec_out, hipError_t* begin_error = nullptr) {
+  hipStream_t st = c->dev->stream;
+  const hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+  if (begin_error) *begin_error = e;
+  if (e != hipSuccess) return false;
+  c->capturing = true;
+  c->attn_variant = variant;
+  const int erc = enqueue_step(c);
+  c->capturing = false;
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  const hipError_t e2 = hipStreamEndCapture(st, &graph);
+  if (erc == 0 && e2 == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+    *graph_out = graph;
+    *exec_out = exec;
+    return true;
+  }
+  if (graph) (void)hipGraphDestroy(graph);
+  return false;
+}
+
 // one decode step at cache position `pos` (the host tracks it; the kernels read their own copy from device memory)
 int run_step(crabml_hip_llama* c, size_t pos) {
   const int variant = variant_of(c, pos);
@@ -1206,25 +1248,11 @@ int run_step_sampled(crabml_hip_llama* c, size_t pos) {
   int rc = 0;
   c->sampling = true;
   if (c->use_graph && !c->sexec[variant]) {
-    hipError_t e = hipStreamBeginCapture(dev->stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) {
+    hipError_t begin = hipSuccess;
+    if (!capture_step(c, variant, &c->sgraph[variant], &c->sexec[variant], &begin)) {
       c->sampling = false;
-      return hip_fail(dev, e, "llama: sampler graph capture", __FILE__, __LINE__);
-    }
-    c->capturing = true;
-    c->attn_variant = variant;
-    const int erc = enqueue_step(c);
-    c->capturing = false;
-    hipGraph_t graph = nullptr;
-    e = hipStreamEndCapture(dev->stream, &graph);
-    hipGraphExec_t exec = nullptr;
-    if (erc == 0 && e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-      c->sgraph[variant] = graph;
-      c->sexec[variant] = exec;
-    } else {
-      if (graph) (void)hipGraphDestroy(graph);
+      if (begin != hipSuccess) return hip_fail(dev, begin, "llama: sampler graph capture", __FILE__, __LINE__);
       (void)hipGetLastError();
-      c->sampling = false;
       CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: hipGraph capture/instantiate of the sampled step failed");
     }
   }
@@ -1379,7 +1407,7 @@ int launch_attn_long_rows_t(crabml_hip_llama* c, int l, int B) {
 }
 // 1 = launched, 0 = not covered, < 0 = error
 int launch_attn_long_rows(crabml_hip_llama* c, int l, int B) {
-  if (!c->exact_long_ok || (c->cfg.flags & CRABML_HIP_LLAMA_NO_TILE_ATTENTION)) return 0;
+  if (!c->plan.exact_long_ok || (c->cfg.flags & CRABML_HIP_LLAMA_NO_TILE_ATTENTION)) return 0;
   int rc = 0;
   if (!with_const<1, 2, 4, 8>(c->n_heads_l / c->n_kv_l, [&](auto grp) { rc = launch_attn_long_rows_t<decltype(grp)::value>(c, l, B); })) return 0;
   return rc == 0 ? 1 : -1;
@@ -1395,7 +1423,7 @@ int launch_prefill_attention(crabml_hip_llama* c, int l, size_t B, size_t pos0) 
   const int* pos_d = c->state + 6;
   // (a pass whose every row sees fewer cached positions than the decode step's switch to the f32 kernels -- attn_long_from --
   // keeps the exact tile kernel, so that prefill(prompt) and a token loop over the same short prompt agree bit for bit)
-  if (c->attn_flash_rows && kv16 && pos0 + B >= c->attn_long_from) {
+  if (c->plan.attn_flash_rows && kv16 && pos0 + B >= c->plan.attn_long_from) {
     // fast step: causal flash attention on the f16 matrix cores (k_attn_flash_rows; the deviation stated for k_attn_flash)
     const dim3 fg((unsigned)((B + 63) / 64), (unsigned)n_heads);
     flash_rows_kernel(hd)<<<fg, 512, flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
@@ -2006,16 +2034,27 @@ int crabml_hip_tp_p2p_connect_local(crabml_hip_tp_comm_t* const* comms, int n) {
 
 }  // extern "C"
 
-// ext_kc / ext_vc (lazy.hip): the caller's KV caches, [n_kv_heads][seq_len][head_dim] in the configured element type -- the layout
-// of Llama2Runner's own cache tensors (llama2.rs:65-86) -- used in place
-static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_config_t* cfg, const crabml_hip_llama_weights_t* w,
-                             crabml_hip_buf* const* ext_kc, crabml_hip_buf* const* ext_vc, crabml_hip_llama_t** out,
-                             const crabml_hip_llama_arch_t* arch = nullptr) {
-  if (!dev || !cfg || !w || !out) return CRABML_HIP_BAD_INPUT;
-  *out = nullptr;
-  const bool dry = dev->dry;
-  const auto& g = *cfg;
-  const int tp = g.tp_size > 1 ? g.tp_size : 1;
+// ---- creating a context: validate, decide, retain, allocate, initialise, capture (llama_create_impl calls them in this order) ----
+
+// what validation learns of a model: the facts decide_step and the later stages work from
+struct ModelFacts {
+  int tp = 1;
+  bool p2p_comm = false;  // the group is the P2P kind: the wo / ffn_down epilogue can host the collective
+  bool tp_dry = false;    // CRABML_HIP_LLAMA_TP_DRY_RUN: a lone rank that skips the all-reduces
+  bool qwen2 = false, gemma = false;
+  size_t hd = 0, n_heads_l = 0, n_kv_l = 0, dim_l = 0, kv_dim_l = 0, hidden_l = 0;  // local (per-rank) geometry
+  const crabml_hip_buf* outw = nullptr;                                             // the classifier: output.weight, else the embedding
+  uint32_t wt = 0, out_wt = 0, qt = 0, out_qt = 0;  // weight type of the layers / the classifier, and their vec_dot_rhs_dtype
+  bool mixed = false;                               // some layer matrix has another type than wq[0] (with the same rhs type)
+  bool mix_v_down_q6k = true;  // every deviating tensor is an attn_v / ffn_down in Q6_K inside a Q4_K layer (the *_K_M recipe)
+  bool split_vocab = false;
+  size_t vocab_l = 0;
+};
+
+// the configuration, the architecture and its biases, and that every weight is there
+static int validate_config(crabml_hip_device_t* dev, const crabml_hip_llama_config_t& g, const crabml_hip_llama_weights_t* w,
+                           const crabml_hip_llama_arch_t* arch, ModelFacts* f) {
+  const int tp = f->tp = g.tp_size > 1 ? g.tp_size : 1;
   if (!g.n_heads || !g.n_kv_heads || !g.n_layers || g.embedding_dim % g.n_heads || g.n_heads % g.n_kv_heads)
     CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: inconsistent head configuration");
   // (asked before the divisibility checks: Gemma-2B has ONE kv head, which no tp_size > 1 divides -- the answer is "not implemented")
@@ -2028,15 +2067,20 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
     if (m->p2p && (!m->connected || m->nranks != tp || m->rank != g.tp_rank || m->cap < g.embedding_dim || m->dev != dev))
       CH_BAIL(dev, CRABML_HIP_BAD_INPUT,
               "llama: the p2p group must be connected, match tp_size / tp_rank, live on this device and hold rows of >= embedding_dim");
+    f->p2p_comm = m->p2p;
   }
+  f->tp_dry = tp > 1 && !g.tp_comm && (g.flags & CRABML_HIP_LLAMA_TP_DRY_RUN);
   // the F32 KV cache pairs head h with kv head h % n_kv (the batch_matmul broadcast quirk): those sets are not
   // contiguous head slices, so a GQA model shards by heads only with the F16 cache (h / (n_heads / n_kv))
   if (tp > 1 && !g.use_f16_kv_cache && g.n_heads != g.n_kv_heads)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: tensor-parallel GQA needs the f16 kv cache");
-  const size_t hd = g.embedding_dim / g.n_heads;
-  const size_t n_heads_l = g.n_heads / tp, n_kv_l = g.n_kv_heads / tp;
-  const size_t dim_l = n_heads_l * hd, kv_dim_l = n_kv_l * hd, hidden_l = g.hidden_dim / tp;
-  if (g.embedding_dim % 32 || hidden_l % 32 || dim_l % 32 || (hd & 1) || hd > 256 || (g.rope_dim & 1) || g.rope_dim > hd || !g.seq_len)
+  const size_t hd = f->hd = g.embedding_dim / g.n_heads;
+  f->n_heads_l = g.n_heads / tp;
+  f->n_kv_l = g.n_kv_heads / tp;
+  f->dim_l = f->n_heads_l * hd;
+  f->kv_dim_l = f->n_kv_l * hd;
+  f->hidden_l = g.hidden_dim / tp;
+  if (g.embedding_dim % 32 || f->hidden_l % 32 || f->dim_l % 32 || (hd & 1) || hd > 256 || (g.rope_dim & 1) || g.rope_dim > hd || !g.seq_len)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: needs dim, local dims % 32 == 0, even head_dim <= 256, even rope_dim");
   if (g.embedding_dim > 12288)  // k_norm_quant keeps the row in 64 KiB of LDS
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: embedding_dim %zu > 12288", g.embedding_dim);
@@ -2048,7 +2092,7 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   // the architecture (model.rs:22-27): Llama; Qwen2 = Llama + q / k / v biases + NEOX rope (llama2.rs:283-351); Gemma = Llama with the
   // embedding scaled by sqrt(dim), NEOX rope and GELU (llama2.rs:455-524; its classifier is whatever the weights say, as everywhere)
   const uint32_t archv = arch ? arch->architecture : (uint32_t)CRABML_HIP_ARCH_LLAMA;
-  const bool qwen2 = archv == CRABML_HIP_ARCH_QWEN2, gemma = archv == CRABML_HIP_ARCH_GEMMA;
+  const bool qwen2 = f->qwen2 = archv == CRABML_HIP_ARCH_QWEN2, gemma = f->gemma = archv == CRABML_HIP_ARCH_GEMMA;
   if (archv == CRABML_HIP_ARCH_PHI2) CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: architecture %u (Phi2) has no decode step here", archv);
   if (archv != CRABML_HIP_ARCH_LLAMA && !qwen2 && !gemma) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: unknown architecture %u", archv);
   if (gemma && (arch->bq || arch->bk || arch->bv)) CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "gemma: there is no decode step with q / k / v biases");
@@ -2058,41 +2102,30 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
     if (!arch->bq || !arch->bk || !arch->bv) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "qwen2: missing q / k / v biases");
     for (size_t l = 0; l < g.n_layers; l++) {
       const crabml_hip_buf* b[3] = {arch->bq[l], arch->bk[l], arch->bv[l]};
-      const size_t n[3] = {dim_l, kv_dim_l, kv_dim_l};
+      const size_t n[3] = {f->dim_l, f->kv_dim_l, f->kv_dim_l};
       for (int j = 0; j < 3; j++)
         if (!b[j] || b[j]->dtype != CRABML_HIP_F32 || b[j]->n_elems != n[j])
           CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "qwen2: layer %zu: the %c bias must be an f32 vector of %zu elements", l, "qkv"[j], n[j]);
     }
   }
-  const crabml_hip_buf* outw = w->output_weight ? w->output_weight : w->token_embed;
-  const uint32_t wt = w->wq[0]->dtype, out_wt = outw->dtype;
-  const uint32_t qt = vec_dot_rhs_dtype(wt), out_qt = vec_dot_rhs_dtype(out_wt);
+  return 0;
+}
+
+// type and shape of every weight.  Fused kernels exist for Q4_0 / Q8_0 / Q4_1 and Q4_K layers; a classifier of another format --
+// llama.cpp's "Q4_0" files keep output.weight in Q6_K -- does not take the layers off them: the final segment quantizes the
+// normalized row for the classifier's own rhs type.
+static int validate_weights(crabml_hip_device_t* dev, const crabml_hip_llama_config_t& g, const crabml_hip_llama_weights_t* w, ModelFacts* f) {
+  const int tp = f->tp;
+  const size_t dim = g.embedding_dim, dim_l = f->dim_l, kv_dim_l = f->kv_dim_l, hidden_l = f->hidden_l;
+  const crabml_hip_buf* outw = f->outw = w->output_weight ? w->output_weight : w->token_embed;
+  const uint32_t wt = f->wt = w->wq[0]->dtype, out_wt = f->out_wt = outw->dtype;
+  const uint32_t qt = f->qt = vec_dot_rhs_dtype(wt), out_qt = f->out_qt = vec_dot_rhs_dtype(out_wt);
   if (qt == 0xffffffffu || out_qt == 0xffffffffu)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: weight dtype %u / classifier dtype %u has no matmul_vec", wt, out_wt);
-  // fused kernels exist for Q4_0 / Q8_0 layers (fast mode); everything else runs the per-op segment path
-  // (a classifier of another format -- llama.cpp's "Q4_0" files keep output.weight in Q6_K -- does not take the layers
-  // off the fused kernels: the final segment quantizes the normalized row for the classifier's own rhs type)
-  const bool fused_fmt = wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0 || wt == CRABML_HIP_Q4_1;
-  // strict order, one device, a format whose dot is one term per block: the fused launches in their block-ordered form (7 per
-  // layer: norm + quantize stay their own launches); everything else strict runs the per-op segments
-  bool ord = dev->strict_order && fused_fmt && tp == 1;
-  if (ord) {  // the term tables must fit LDS: 64 rows of gate|up (k_gateup_q_ord), a workgroup's 16 / 32 rows of wo and ffn_down
-    const int dim = (int)g.embedding_dim;
-    const size_t gu = gateup_q_ord_lds_bytes(dim / 32);
-    // (k_gemv_res_nq_ord keeps the default limit; the split is the launch's own, A/B flags included.  wo's rows are at most 12288
-    // long: 32 x 388 floats, inside the limit)
-    const size_t dn = nq_ord_lds_bytes((int)hidden_l / 32, chunk_split(g.flags, (int)hidden_l, dim, dev->n_cu));
-    const void* fn = nullptr;  // (enqueue_segment launches k_gateup_q_ord<FMT> of the same weight type)
-    with_const_else<CRABML_HIP_Q4_0, CRABML_HIP_Q8_0, CRABML_HIP_Q4_1>((int)wt, [&](auto fmt) { fn = (const void*)k_gateup_q_ord<decltype(fmt)::value>; });
-    if (gu > 150 * 1024 || dn > 60 * 1024 || (gu > 60 * 1024 && raise_dyn_lds(dev, fn, (int)gu) != hipSuccess)) ord = false;
-    (void)hipGetLastError();
-  }
-  bool generic = (dev->strict_order && !ord) || !fused_fmt;
-  const bool out_differs = out_wt != wt;
   {
     const size_t be = block_elems(wt) > block_elems(qt) ? block_elems(wt) : block_elems(qt);
     const size_t obe = block_elems(out_wt) > block_elems(out_qt) ? block_elems(out_wt) : block_elems(out_qt);
-    if (g.embedding_dim % be || dim_l % be || hidden_l % be || g.embedding_dim % obe)
+    if (dim % be || dim_l % be || hidden_l % be || dim % obe)
       CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: dim / local dims are not multiples of the %zu-element blocks of dtype %u", be, wt);
   }
   auto check = [&](const crabml_hip_buf* b, size_t m, size_t k, uint32_t t) {
@@ -2100,52 +2133,216 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   };
   // a layer's matrices may differ in GGML type (llama.cpp's *_K_M files: attn_v / ffn_down in Q6_K on some layers) as
   // long as they share the rhs type (buf/api.rs:142-159: every K-quant takes Q8_K): such a model runs the per-op
-  // segments, each GEMV picking its kernel by the tensor's own dtype
-  bool mixed = false;
-  bool mix_v_down_q6k = true;  // every deviating tensor is an attn_v / ffn_down in Q6_K inside a Q4_K layer (the *_K_M recipe)
+  // segments, each GEMV picking its kernel by the tensor's own dtype -- unless it is the *_K_M recipe, which the Q4_K kernels take
   auto check_w = [&](const crabml_hip_buf* b, size_t m, size_t k, bool v_or_down) {
     if (!b) return false;
     if (b->dtype != wt) {
       if (vec_dot_rhs_dtype(b->dtype) != qt || k % block_elems(b->dtype)) return false;
-      mixed = true;
-      if (!(v_or_down && wt == CRABML_HIP_Q4_K && b->dtype == CRABML_HIP_Q6_K)) mix_v_down_q6k = false;
+      f->mixed = true;
+      if (!(v_or_down && wt == CRABML_HIP_Q4_K && b->dtype == CRABML_HIP_Q6_K)) f->mix_v_down_q6k = false;
     }
     return check(b, m, k, b->dtype);
   };
   for (size_t l = 0; l < g.n_layers; l++) {
-    if (!check_w(w->wq[l], dim_l, g.embedding_dim, false) || !check_w(w->wk[l], kv_dim_l, g.embedding_dim, false) ||
-        !check_w(w->wv[l], kv_dim_l, g.embedding_dim, true) || !check_w(w->wo[l], g.embedding_dim, dim_l, false) ||
-        !check_w(w->ffn_gate_weight[l], hidden_l, g.embedding_dim, false) ||
-        !check_w(w->ffn_up_weight[l], hidden_l, g.embedding_dim, false) ||
-        !check_w(w->ffn_down_weight[l], g.embedding_dim, hidden_l, true) ||
-        !check(w->rms_att_weight[l], 1, g.embedding_dim, CRABML_HIP_F32) ||
-        !check(w->rms_ffn_weight[l], 1, g.embedding_dim, CRABML_HIP_F32))
+    if (!check_w(w->wq[l], dim_l, dim, false) || !check_w(w->wk[l], kv_dim_l, dim, false) || !check_w(w->wv[l], kv_dim_l, dim, true) ||
+        !check_w(w->wo[l], dim, dim_l, false) || !check_w(w->ffn_gate_weight[l], hidden_l, dim, false) ||
+        !check_w(w->ffn_up_weight[l], hidden_l, dim, false) || !check_w(w->ffn_down_weight[l], dim, hidden_l, true) ||
+        !check(w->rms_att_weight[l], 1, dim, CRABML_HIP_F32) || !check(w->rms_ffn_weight[l], 1, dim, CRABML_HIP_F32))
       CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
               "llama fused path: layer %zu weights have an unexpected shape, or dtypes that do not share one rhs dtype (tp=%d)", l, tp);
   }
   // the classifier split by vocabulary: this rank holds rows [tp_rank V / tp, (tp_rank + 1) V / tp)
-  const bool split_vocab = tp > 1 && (g.flags & CRABML_HIP_LLAMA_TP_SPLIT_VOCAB) != 0;
-  if (split_vocab) {
+  f->split_vocab = tp > 1 && (g.flags & CRABML_HIP_LLAMA_TP_SPLIT_VOCAB) != 0;
+  if (f->split_vocab) {
     if (!w->output_weight || g.vocab_size % tp)
       CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: the vocabulary split needs an untied output.weight and vocab_size %% tp_size == 0");
-    if (g.tp_comm && !((const crabml_hip_tp_comm*)g.tp_comm)->p2p)
+    if (g.tp_comm && !f->p2p_comm)
       CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: the vocabulary split exchanges its arg-max pairs through a P2P group (crabml_hip_tp_p2p_*)");
   }
-  const size_t vocab_l = split_vocab ? g.vocab_size / tp : g.vocab_size;
-  if (!check(outw, vocab_l, g.embedding_dim, out_wt) || !check(w->rms_final_weight, 1, g.embedding_dim, CRABML_HIP_F32) ||
-      w->token_embed->n_elems != g.vocab_size * g.embedding_dim)
+  f->vocab_l = f->split_vocab ? g.vocab_size / tp : g.vocab_size;
+  if (!check(outw, f->vocab_l, dim, out_wt) || !check(w->rms_final_weight, 1, dim, CRABML_HIP_F32) || w->token_embed->n_elems != g.vocab_size * dim)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: classifier / final norm / embedding dtype or shape");
+  return 0;
+}
 
-  if (!dry) CH_USE(dev);
+// the three tuning hooks of the split-KV attention (tools/flash_sweep.py; armed like ASSUME_CUS), as values
+struct FlashHooks {
+  int slices = 0;             // CRABML_HIP_FLASH_SLICES: slices per kv head in the grid (0 = not set)
+  int min_rows = 0;           // CRABML_HIP_FLASH_MIN_ROWS (0 = not set)
+  size_t ticket_until = 768;  // CRABML_HIP_FLASH_TICKET_UNTIL: 0 = never
+};
+static FlashHooks read_flash_hooks() {
+  FlashHooks h;
+  h.slices = test_hook_int("CRABML_HIP_FLASH_SLICES", 0);
+  h.min_rows = test_hook_int("CRABML_HIP_FLASH_MIN_ROWS", 0);
+  if (const char* e = test_hook("CRABML_HIP_FLASH_TICKET_UNTIL")) h.ticket_until = (size_t)atol(e);
+  return h;
+}
+
+// The one question decide_step asks of the device: does kernel `fn` get `bytes` of dynamic LDS?  Yes when that is under `cap` and, if
+// it is above `granted` (what a launch gets without asking), the kernel's limit could be raised -- which the record-only device refuses.
+constexpr size_t LDS_CAP = 150 * 1024, LDS_NO_CAP = ~(size_t)0;
+static bool lds_fits(const crabml_hip_device* dev, const void* fn, size_t bytes, size_t cap, size_t granted) {
+  if (bytes > cap) return false;
+  if (bytes <= granted) return true;
+  const bool ok = raise_dyn_lds(dev, fn, (int)bytes) == hipSuccess;
+  (void)hipGetLastError();
+  return ok;
+}
+
+// The attention forms of a plan.  Each kernel's limit is asked for where the plan first needs that kernel, in this order: the exact
+// softmax, k_attn_pv_split, k_attn_flash, its ticket form, k_attn_flash_rows, k_attn_s -- a refusal turns that form off, nothing else.
+static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llama_config_t& g, const ModelFacts& f, const FlashHooks& hooks,
+                             StepPlan* p) {
+  const auto has = [&](int bits) { return (g.flags & bits) != 0; };
+  const int grp = (int)(f.n_heads_l / f.n_kv_l), hd = (int)f.hd, n_kv_l = (int)f.n_kv_l;
+  const size_t seq = g.seq_len;
+  const bool kv16 = g.use_f16_kv_cache != 0, q81 = f.qt == CRABML_HIP_Q8_1;
+  const bool long_geom = kv16 && hd % 32 == 0 && (grp == 1 || grp == 2 || grp == 4 || grp == 8) && !has(CRABML_HIP_LLAMA_NO_LONG_ATTENTION);
+  // the exact kernels: the softmax kernels keep a head's score row in LDS -- rows past 16384 positions need the raised limit, rows
+  // past ~38000 do not fit at all (the step then stays on the one-workgroup-per-head kernel)
+  p->exact_long_ok = long_geom && seq % 8 == 0 && lds_fits(dev, (const void*)k_attn_softmax<16>, seq * 4, LDS_CAP, 64 * 1024) &&
+                     lds_fits(dev, (const void*)k_attn_softmax<4>, seq * 4, LDS_CAP, 64 * 1024);
+  p->pv_split = p->exact_long_ok && !has(CRABML_HIP_LLAMA_NO_PV_PRODUCER_WAVES) && [&] {
+    const PvSplitKernel pv = pv_split_kernel(grp);
+    return lds_fits(dev, (const void*)pv.fn, pv.lds, LDS_NO_CAP, 0);
+  }();
+  // the fast step's long-context attention: split-KV with f32 accumulation (k_attn_flash) unless the exact chain is asked for
+  // (k_attn_flash reads the cache rows only -- head_dim halves each --, so any seq_len will do: a cache of 1001 positions must not
+  // fall back to one workgroup per head, 45 us per layer at 900 positions)
+  const bool want_flash = long_geom && !dev->strict_order && !has(CRABML_HIP_LLAMA_EXACT_ATTENTION);
+  p->flash_ticket = want_flash && has(CRABML_HIP_LLAMA_FLASH_TICKET);
+  const FlashFn fn = want_flash ? flash_kernel(grp, hd, q81, p->flash_ticket) : nullptr;
+  p->attn_flash = fn != nullptr && lds_fits(dev, (const void*)fn, flash_lds_bytes(grp, hd), LDS_NO_CAP, 0);
+  if (p->attn_flash) {
+    const int S = dev->n_cu / n_kv_l;
+    p->flash_S = hooks.slices >= 1 && hooks.slices <= FLASH_MAX_SLICES ? hooks.slices : S < 1 ? 1 : S > FLASH_MAX_SLICES ? FLASH_MAX_SLICES : S;
+    if (hooks.min_rows >= 8 && hooks.min_rows <= 65536) p->flash_min_rows = hooks.min_rows;
+    // Below ~768 cached positions the merge inside the launch (last-arriving workgroup of a kv head, ticket word) beats the
+    // second launch -- 7.4 vs 5.1 + 4.1 us per layer at 128 positions, 8.7 vs 10.0 at 512, 10.8 vs 9.95 at 1024
+    // (profiles/r05_flash_ticket_sweep.md; same partials, same merge order: bit-identical): a third graph variant serves that range.
+    const FlashFn tfn = flash_kernel(grp, hd, q81, true);
+    if (!p->flash_ticket && hooks.ticket_until > 0 && tfn != nullptr && lds_fits(dev, (const void*)tfn, flash_lds_bytes(grp, hd), LDS_NO_CAP, 0))
+      p->flash_ticket_until = hooks.ticket_until;
+    // the prompt pass's causal attention of the fast step (k_attn_flash_rows): 70 KB of LDS at head_dim 128
+    p->attn_flash_rows =
+        flash_rows_kernel(hd) != nullptr && lds_fits(dev, (const void*)flash_rows_kernel(hd), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
+  }
+  p->attn_long_ok = p->exact_long_ok || p->attn_flash;
+  // the exact kernels: measured crossover on MI355X (Llama-3-8B shape) ~200-220.  k_attn_flash + merge overtake the staged one-workgroup
+  // kernel between 64 and 96 cached positions (8B shape, per layer: 51.0 vs 51.6 us at 64, 52.2 vs 51.4 at 96, 59.0 vs 51.8 at 224;
+  // profiles/r04_flash_sweep.log)
+  p->attn_long_from = g.attn_long_from ? g.attn_long_from : p->attn_flash ? 96 : 224;
+  // short-context attention with K / V staged through LDS (f16 cache): variant 0 serves positions < S
+  if (kv16 && hd % 8 == 0 && !has(CRABML_HIP_LLAMA_NO_STAGED_ATTENTION)) {
+    const size_t S = p->attn_long_ok && p->attn_long_from < seq ? p->attn_long_from : seq;
+    const size_t lds = attn_s_lds_bytes((int)S, hd);
+    if (lds_fits(dev, (const void*)attn_s_kernel(hd), lds, LDS_CAP, 0)) {
+      p->attn_s_rows = (int)S;
+      p->attn_s_lds = lds;
+    }
+  }
+}
+
+// What a context runs (StepPlan), from values: the configuration, the device's mode and size, and what validation found.  The one
+// place that decides it; crabml_hip_debug_step_plan reads it out, tests/test_step_plan.py holds the table.  Every clause that more
+// than one decision needs is named once.  The LDS-dependent choices fall back where they always did: the ordered five launches to the
+// per-op segments, the ordered Q4_K launches to what an unordered context of the flags gets (on a strict device: per-op).
+static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama_config_t& g, const ModelFacts& f, const FlashHooks& hooks) {
+  const auto has = [&](int bits) { return (g.flags & bits) != 0; };
+  const bool strict = dev->strict_order;
+  const int n_cu = dev->n_cu, tp = f.tp, dim = (int)g.embedding_dim, dim_l = (int)f.dim_l, hidden_l = (int)f.hidden_l, hd = (int)f.hd;
+  const uint32_t wt = f.wt;
+  const bool fused_fmt = wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0 || wt == CRABML_HIP_Q4_1;  // a dot of one term per block
+  const bool chunks_resident = dim / 32 <= n_cu;  // every workgroup of a wo / ffn_down gather must be resident
+  // the Q4_K norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on
+  const bool k_epilogue_eligible = wt == CRABML_HIP_Q4_K && f.out_qt == CRABML_HIP_Q8_K && tp == 1 && !has(CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) &&
+                                   dim % 256 == 0 && chunks_resident;
+  const bool k_fusion = !has(CRABML_HIP_LLAMA_NO_KQUANT_FUSION);
+  // the Q4_K fused kernels take a Q6_K attn_v / ffn_down beside the Q4_K planes (the *_K_M recipe), but only in the norm-epilogue form
+  const bool mix_fused = f.mixed && f.mix_v_down_q6k && !strict && k_epilogue_eligible && k_fusion;
+
+  // Strict order, one device, Q4_0 / Q8_0 / Q4_1: the fused launches in their block-ordered form (7 per layer: norm + quantize stay
+  // their own launches).  The term tables must fit LDS: 64 rows of gate | up (k_gateup_q_ord, raised past 60 KiB), a workgroup's 16 / 32
+  // rows of ffn_down (k_gemv_res_nq_ord keeps the default limit; wo's rows are at most 12288 long: 32 x 388 floats, inside it).
+  const auto ord5_fits = [&] {
+    const void* fn = nullptr;  // (enqueue_segment_t launches k_gateup_q_ord<FMT> of the same weight type)
+    with_const_else<CRABML_HIP_Q4_0, CRABML_HIP_Q8_0, CRABML_HIP_Q4_1>((int)wt, [&](auto fmt) { fn = (const void*)k_gateup_q_ord<decltype(fmt)::value>; });
+    return nq_ord_lds_bytes(hidden_l / 32, chunk_split(g.flags, hidden_l, dim, n_cu)) <= 60 * 1024 &&
+           lds_fits(dev, fn, gateup_q_ord_lds_bytes(dim / 32), LDS_CAP, 60 * 1024);
+  };
+  const bool ord5 = strict && fused_fmt && tp == 1 && ord5_fits() && !f.mixed;  // (a mixed file: per-op segments)
+  // Strict order, Q4_K layers on one device (a *_K_M mix too: its Q6_K rows leave the same records, rows_terms_q6k): the five launches
+  // of the fast Q4_K step in their ORDERED form -- nine f32 terms per super-block parked in LDS and added in super-block order, the
+  // reference's norm order in the wo / ffn_down epilogue; bit-identical to the per-op segments they replace (16 launches per layer).
+  // Both QOUT forms of gate | up and every <SPLIT, QIN> of wo / ffn_down are raised: q8k_producers and the splits are the launches' own.
+  const auto ordk_fits = [&] {  // (wo never runs x_only here: k_norm_in is off on a strict-order device)
+    if (dev->dry) return true;  // (record-only device: nothing to raise, nothing launched)
+    const size_t gu = q8k_ord_lds_bytes(dim, 64);
+    const size_t dn = q8k_ord_lds_bytes(hidden_l, 32 / chunk_split(g.flags, hidden_l, dim, n_cu));
+    const size_t wo = q8k_ord_lds_bytes(dim_l, 32 / chunk_split(g.flags, dim_l, dim, n_cu));
+    const size_t nq = dn > wo ? dn : wo;
+    bool fits = gu <= LDS_CAP && nq <= LDS_CAP;
+    for (int qout = 0; qout < 2; qout++) fits = fits && lds_fits(dev, (const void*)gateup_k_kernel(qout != 0, true, false), gu, LDS_CAP, 48 * 1024);
+    for (int split = 1; split <= 2; split++)
+      for (int qin = 1; qin <= 2; qin++) fits = fits && lds_fits(dev, (const void*)nq_ord_k_kernel(split, qin), nq, LDS_CAP, 48 * 1024);
+    return fits;
+  };
+  const bool ordk = strict && k_epilogue_eligible && k_fusion && !has(CRABML_HIP_LLAMA_NO_RHS_PROLOGUE) && (!f.mixed || f.mix_v_down_q6k) &&
+                    dim_l % 256 == 0 && hidden_l % 256 == 0 && ordk_fits();
+  // the fast K-quant segments: Q4_K always; Q4_1 when it cannot take the five launches (a classifier of another format) or for the A/B flag
+  const bool fast_k = !strict && (!f.mixed || mix_fused) && k_fusion &&
+                      (wt == CRABML_HIP_Q4_K || (wt == CRABML_HIP_Q4_1 && (f.out_wt != wt || has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS))));
+  // per-op launches: a strict-order device without an ordered form, a weight format without fused kernels, a mix they do not take
+  const bool per_op = (strict && !ord5) || !fused_fmt || (f.mixed && !mix_fused);
+
+  StepPlan p;
+  p.path = ordk || fast_k ? SegPath::FusedK : per_op ? SegPath::PerOp : SegPath::Fused5;
+  p.ordered = ord5 || ordk;
+  // (So Fused5 && !ordered says: Q4_0 / Q8_0 / Q4_1 layers, no mix, not a strict-order device -- Fused5 needs fused_fmt and, on a
+  // strict device, ord5.  FusedK && !ordered says: not a strict-order device.  The tap hooks and the forms below rely on both.)
+  const bool five = p.path == SegPath::Fused5;
+  const bool fast_q40_q80 = !p.ordered && (wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0);  // beside norm_epi: the hop-free forms' step
+  // tp > 1: the epilogue also hosts the collective when the group is the P2P kind (or in the collective-free dry run).  Not for the
+  // K-quant segments -- a Q4_1 body with a classifier of another format runs them: their wo / ffn_down launches host neither the norm
+  // epilogue nor the collective, so over a P2P group the stand-alone all-reduce launch must run.
+  p.norm_epi = five && (tp == 1 || f.p2p_comm || f.tp_dry) && !has(CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) && chunks_resident;
+  p.norm_epi_k = p.path == SegPath::FusedK && k_epilogue_eligible;
+  p.defer_norm = p.norm_epi && tp == 1 && fast_q40_q80 && !has(CRABML_HIP_LLAMA_EXACT_NORM);
+  // A tensor-parallel rank's gate/up: hidden / tp / 32 workgroups of 32 rows would leave most CUs idle.  h stays f32 from workgroups
+  // of `gu_rows` rows (the largest even divisor of the rank's rows, at most 32, that gives at least one workgroup per CU) and
+  // ffn_down quantizes it in its prologue.  (Never picked on the record-only device.)
+  const auto pick_gu_rows = [&] {
+    for (int r = 30; r >= 2; r -= 2)
+      if (hidden_l % r == 0 && hidden_l / r >= n_cu && hidden_l / r <= 2 * n_cu) return q8_0_lds_bytes(hidden_l / 32) <= 60 * 1024 ? r : 0;
+    return 0;
+  };
+  p.gu_rows = p.norm_epi && tp > 1 && fast_q40_q80 && !has(CRABML_HIP_LLAMA_NO_H_CONSUMER_QUANT) && hidden_l % 32 == 0 &&
+                      hidden_l / 32 * 2 <= n_cu && !dev->dry
+                  ? pick_gu_rows()
+                  : 0;
+  p.q8k_producers = p.norm_epi_k && !has(CRABML_HIP_LLAMA_NO_RHS_PROLOGUE | CRABML_HIP_LLAMA_NO_Q8K_PRODUCERS) && dim_l % 256 == 0 &&
+                    hidden_l % 256 == 0 && (hd == 64 || hd == 128 || hd == 256) && hidden_l / 32 <= 2 * n_cu;
+  // the fast Q4_K step: wo leaves x only, gate | up normalizes and quantizes the row itself (k_gateup_k_lds<.., NORMIN>; the same bits)
+  p.k_norm_in = p.q8k_producers && !p.ordered && dim / 256 <= 32 &&
+                !has(CRABML_HIP_LLAMA_NO_K_NORM_IN | CRABML_HIP_LLAMA_SPLIT_CHUNKS_ALWAYS | CRABML_HIP_LLAMA_SPLIT_CHUNKS_NEVER);
+  decide_attention(dev, g, f, hooks, &p);
+  return p;
+}
+
+// a fresh context with its identity, geometry and plan; on a live device, the pinned state ring (and lazy.hip's logits copy)
+static int new_context(crabml_hip_device_t* dev, const crabml_hip_llama_config_t& g, const ModelFacts& f, const StepPlan& plan, bool ext_kv,
+                       crabml_hip_llama** out) {
   crabml_hip_llama* c = new crabml_hip_llama();
   c->dev = dev;
-  if (!dry && hipHostMalloc((void**)&c->h_state, (crabml_hip_llama::H_STATE_SLOTS * 4 + 4) * sizeof(int), hipHostMallocDefault) != hipSuccess) {
+  if (!dev->dry && hipHostMalloc((void**)&c->h_state, (crabml_hip_llama::H_STATE_SLOTS * 4 + 4) * sizeof(int), hipHostMallocDefault) != hipSuccess) {
     delete c;
     CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: hipHostMalloc of the state staging ring failed");
   }
   c->cfg = g;
-  c->wtype = wt;
-  if (ext_kc != nullptr && !dry) {
+  c->wtype = f.wt;
+  c->plan = plan;
+  if (ext_kv && !dev->dry) {
     static const bool on = [] { const char* e = getenv("CRABML_HIP_LAZY_NO_HOST_LOGITS"); return !(e && e[0] == '1'); }();
     if (on && hipHostMalloc((void**)&c->host_logits, g.vocab_size * 4 + 64, hipHostMallocDefault) == hipSuccess)
       memset(c->host_logits + g.vocab_size, 0, 64);
@@ -2153,114 +2350,93 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
       c->host_logits = nullptr;
     (void)hipGetLastError();
   }
-  // the Q4_K fused kernels take a Q6_K attn_v / ffn_down beside the Q4_K planes, but only in the norm-epilogue form
-  const bool nepi_k_possible = !dev->strict_order && wt == CRABML_HIP_Q4_K && out_qt == CRABML_HIP_Q8_K && tp == 1 &&
-                               !(g.flags & (CRABML_HIP_LLAMA_NO_NORM_EPILOGUE | CRABML_HIP_LLAMA_NO_KQUANT_FUSION)) &&
-                               g.embedding_dim % 256 == 0 && (int)(g.embedding_dim / 32) <= dev->n_cu;
-  const bool mix_fused = mixed && mix_v_down_q6k && nepi_k_possible;
-  if (mixed && ord) {  // (a mixed file: per-op segments)
-    ord = false;
-    generic = true;
-  }
-  generic = generic || (mixed && !mix_fused);
-  // strict order, pure Q4_K layers on one device (round 6): the five fused launches of the fast Q4_K step in their ORDERED form -- nine
-  // f32 terms per super-block (eight exact class sums x d, and dmin x sumi) parked in LDS and added in super-block order, the
-  // reference's norm order in the wo / ffn_down epilogue (k_qkv_ord, k_gemv_res_nq<.., ORD>, k_gateup_k_lds<.., ORD>); bit-identical
-  // to the per-op segments they replace (16 launches per layer).  The term tables must fit LDS.
-  // (a *_K_M mix too: its Q6_K attn_v / ffn_down rows leave the same records, rows_terms_q6k)
-  bool ordk = dev->strict_order && wt == CRABML_HIP_Q4_K && (!mixed || mix_v_down_q6k) && out_qt == CRABML_HIP_Q8_K && tp == 1 &&
-              !(g.flags & (CRABML_HIP_LLAMA_NO_NORM_EPILOGUE | CRABML_HIP_LLAMA_NO_KQUANT_FUSION | CRABML_HIP_LLAMA_NO_RHS_PROLOGUE)) &&
-              g.embedding_dim % 256 == 0 && dim_l % 256 == 0 && hidden_l % 256 == 0 && (int)(g.embedding_dim / 32) <= dev->n_cu;
-  if (ordk && !dry) {
-    // (wo never runs x_only here: k_norm_in is off on a strict-order device)
-    const int dim = (int)g.embedding_dim;
-    const size_t gu = q8k_ord_lds_bytes(dim, 64);
-    const size_t dn = q8k_ord_lds_bytes((int)hidden_l, 32 / chunk_split(g.flags, (int)hidden_l, dim, dev->n_cu));
-    const size_t wo = q8k_ord_lds_bytes((int)dim_l, 32 / chunk_split(g.flags, (int)dim_l, dim, dev->n_cu));
-    const size_t nq = dn > wo ? dn : wo;
-    bool fits = gu <= 150 * 1024 && nq <= 150 * 1024;
-    if (fits && gu > 48 * 1024)  // both QOUT forms: q8k_producers is decided further down
-      for (int qout = 0; qout < 2; qout++) fits = fits && raise_dyn_lds(dev, (const void*)gateup_k_kernel(qout != 0, true, false), (int)gu) == hipSuccess;
-    if (fits && nq > 48 * 1024)  // every <SPLIT, QIN> the ordered wo / ffn_down launches can ask nq_ord_k_kernel for
-      for (int split = 1; split <= 2; split++)
-        for (int qin = 1; qin <= 2; qin++) fits = fits && raise_dyn_lds(dev, (const void*)nq_ord_k_kernel(split, qin), (int)nq) == hipSuccess;
-    (void)hipGetLastError();
-    if (!fits) ordk = false;
-  }
-  if (ordk) ord = true;
-  if (ordk && mixed) generic = false;
-  c->generic = generic;
-  c->ord = ord;
-  // Q4_K always; Q4_1 when it cannot take the 5-kernel path (mixed classifier format) or for the A/B flag
-  c->kfused = ordk ||
-              (!dev->strict_order && (!mixed || mix_fused) && !(g.flags & CRABML_HIP_LLAMA_NO_KQUANT_FUSION) &&
-               (wt == CRABML_HIP_Q4_K || (wt == CRABML_HIP_Q4_1 && (generic || out_differs || (g.flags & CRABML_HIP_LLAMA_Q4_1_SEGMENTS)))));
-  c->qt = qt;
-  c->out_qt = out_qt;
-  c->tp = tp;
+  c->qt = f.qt;
+  c->out_qt = f.out_qt;
+  c->tp = f.tp;
   c->tp_rank = g.tp_rank;
   c->comm = (crabml_hip_tp_comm*)g.tp_comm;
-  c->tp_dry = tp > 1 && !g.tp_comm && (g.flags & CRABML_HIP_LLAMA_TP_DRY_RUN);
-  if (c->comm && c->comm->p2p) c->tp_salt = (++c->comm->sessions) * 0x9E3779B1u;
-  c->split_vocab = split_vocab;
-  c->vocab_l = (int)vocab_l;
-  c->vocab_off = split_vocab ? (int)(vocab_l * (size_t)g.tp_rank) : 0;
-  c->hd = (int)hd;
+  c->tp_dry = f.tp_dry;
+  if (f.p2p_comm) c->tp_salt = (++c->comm->sessions) * 0x9E3779B1u;
+  c->split_vocab = f.split_vocab;
+  c->vocab_l = (int)f.vocab_l;
+  c->vocab_off = f.split_vocab ? (int)(f.vocab_l * (size_t)g.tp_rank) : 0;
+  c->hd = (int)f.hd;
   c->npairs = (int)(g.rope_dim / 2);
-  c->n_heads_l = (int)n_heads_l;
-  c->n_kv_l = (int)n_kv_l;
-  c->dim_l = (int)dim_l;
-  c->kv_dim_l = (int)kv_dim_l;
-  c->hidden_l = (int)hidden_l;
+  c->n_heads_l = (int)f.n_heads_l;
+  c->n_kv_l = (int)f.n_kv_l;
+  c->dim_l = (int)f.dim_l;
+  c->kv_dim_l = (int)f.kv_dim_l;
+  c->hidden_l = (int)f.hidden_l;
+  c->qwen2 = f.qwen2;
+  c->gemma = f.gemma;
+  c->ext_kv = ext_kv;
+  *out = c;
+  return 0;
+}
+
+// retains `b` for the context's lifetime and makes sure its bytes are on the device; *rc keeps the first error
+static crabml_hip_buf* hold(crabml_hip_llama* c, const crabml_hip_buf* b, int* rc) {
+  crabml_hip_buf* m = const_cast<crabml_hip_buf*>(b);
+  crabml_hip_buf_retain(m);
+  c->held.push_back(m);
+  if (*rc == 0) *rc = ensure_mem(c->dev, m);
+  return m;
+}
+
+// the weights (every one is retained even behind an error: destroy releases what `held` lists), the activation table of the
+// architecture, and the f16 prompt GEMM's A' range check of every matrix.  Returns the first error.
+static int retain_weights(crabml_hip_llama* c, const crabml_hip_llama_weights_t* w, const crabml_hip_llama_arch_t* arch, const ModelFacts& f) {
+  crabml_hip_device* dev = c->dev;
+  const auto& g = c->cfg;
   int rc = 0;
-  auto hold = [&](const crabml_hip_buf* b) {
-    crabml_hip_buf* m = const_cast<crabml_hip_buf*>(b);
-    crabml_hip_buf_retain(m);
-    c->held.push_back(m);
-    if (rc == 0) rc = ensure_mem(dev, m);
-    return m;
-  };
-  c->token_embed = hold(w->token_embed);
-  c->rms_final = hold(w->rms_final_weight);
-  c->output = hold(outw);
+  c->token_embed = hold(c, w->token_embed, &rc);
+  c->rms_final = hold(c, w->rms_final_weight, &rc);
+  c->output = hold(c, f.outw, &rc);
   for (size_t l = 0; l < g.n_layers; l++) {
-    c->rms_att.push_back(hold(w->rms_att_weight[l]));
-    c->rms_ffn.push_back(hold(w->rms_ffn_weight[l]));
-    c->wq.push_back(hold(w->wq[l]));
-    c->wk.push_back(hold(w->wk[l]));
-    c->wv.push_back(hold(w->wv[l]));
-    c->wo.push_back(hold(w->wo[l]));
-    c->gate.push_back(hold(w->ffn_gate_weight[l]));
-    c->down.push_back(hold(w->ffn_down_weight[l]));
-    c->up.push_back(hold(w->ffn_up_weight[l]));
-    if (qwen2) {
-      c->bq.push_back(hold(arch->bq[l]));
-      c->bk.push_back(hold(arch->bk[l]));
-      c->bv.push_back(hold(arch->bv[l]));
+    c->rms_att.push_back(hold(c, w->rms_att_weight[l], &rc));
+    c->rms_ffn.push_back(hold(c, w->rms_ffn_weight[l], &rc));
+    c->wq.push_back(hold(c, w->wq[l], &rc));
+    c->wk.push_back(hold(c, w->wk[l], &rc));
+    c->wv.push_back(hold(c, w->wv[l], &rc));
+    c->wo.push_back(hold(c, w->wo[l], &rc));
+    c->gate.push_back(hold(c, w->ffn_gate_weight[l], &rc));
+    c->down.push_back(hold(c, w->ffn_down_weight[l], &rc));
+    c->up.push_back(hold(c, w->ffn_up_weight[l], &rc));
+    if (f.qwen2) {
+      c->bq.push_back(hold(c, arch->bq[l], &rc));
+      c->bk.push_back(hold(c, arch->bk[l], &rc));
+      c->bv.push_back(hold(c, arch->bv[l], &rc));
     }
   }
-  c->qwen2 = qwen2;
-  c->gemma = gemma;
-  if (gemma) {  // (the table at create, not on the first gelu_inplace call: the step's graph is captured below)
+  if (f.gemma) {  // (the table at create, not on the first gelu_inplace call: the step's graph is captured at create)
     if (rc == 0) rc = crabml_hip::ensure_gelu_table(dev);
     c->embed_scale = std::sqrt((float)g.embedding_dim);  // (embed_dim as f32).sqrt(), llama2.rs:468
     c->ffn_act = FfnAct{dev->gelu_table, 1};
   } else {
     c->ffn_act = FfnAct{dev->exp_table, 0};
   }
-  // the f16 prompt GEMM's A' range check of every matrix (gemm_f16w_takes: one reduction over the scale plane, read back), here
-  // once rather than inside the first prompt pass
-  if (rc == 0 && !dev->strict_order && tp == 1 && (qt == CRABML_HIP_Q8_0 || qt == CRABML_HIP_Q8_1 || qt == CRABML_HIP_Q8_K))
+  // gemm_f16w_takes: one reduction over the scale plane, read back -- here once rather than inside the first prompt pass
+  if (rc == 0 && !dev->strict_order && f.tp == 1 && (f.qt == CRABML_HIP_Q8_0 || f.qt == CRABML_HIP_Q8_1 || f.qt == CRABML_HIP_Q8_K))
     for (size_t l = 0; l < g.n_layers; l++)
-      for (const crabml_hip_buf* m : {c->wq[l], c->wk[l], c->wv[l], c->wo[l], c->gate[l], c->up[l], c->down[l]}) (void)gemm_f16w_takes(dev, m, qt);
-  auto A = [&](size_t bytes, void** p) {
-    if (rc == 0) rc = dalloc(c, bytes, p);
+      for (const crabml_hip_buf* m : {c->wq[l], c->wk[l], c->wv[l], c->wo[l], c->gate[l], c->up[l], c->down[l]}) (void)gemm_f16w_takes(dev, m, f.qt);
+  return rc;
+}
+
+// the KV caches (ours, or lazy.hip's runner's own: [n_kv_heads][seq_len][head_dim] in the configured element type, the layout of
+// Llama2Runner's cache tensors, llama2.rs:65-86, used in place) and every buffer of the step, sized from the plan.  `rc`: the first
+// error so far -- behind one nothing more is allocated; returns the first error.
+static int alloc_step_buffers(crabml_hip_llama* c, crabml_hip_buf* const* ext_kc, crabml_hip_buf* const* ext_vc, int rc) {
+  crabml_hip_device* dev = c->dev;
+  const auto& g = c->cfg;
+  const StepPlan& p = c->plan;
+  const size_t dim = g.embedding_dim, dim_l = c->dim_l, kv_dim_l = c->kv_dim_l, hidden_l = c->hidden_l, n_kv_l = c->n_kv_l, n_heads_l = c->n_heads_l;
+  auto A = [&](size_t bytes, auto** ptr) {
+    if (rc == 0) rc = dalloc(c, bytes, (void**)ptr);
   };
   const size_t es = g.use_f16_kv_cache ? 2 : 4;
-  c->kv_bytes = n_kv_l * g.seq_len * hd * es;
+  c->kv_bytes = n_kv_l * g.seq_len * c->hd * es;
   c->kc.resize(g.n_layers);
   c->vc.resize(g.n_layers);
-  c->ext_kv = ext_kc != nullptr;
   for (size_t l = 0; l < g.n_layers; l++) {
     if (c->ext_kv) {
       const uint32_t kvt = g.use_f16_kv_cache ? CRABML_HIP_F16 : CRABML_HIP_F32;
@@ -2270,230 +2446,137 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
         continue;
       }
       if (l == 0) c->ext_kc0 = ext_kc[l];
-      c->kc[l] = hold(ext_kc[l])->ptr;
-      c->vc[l] = hold(ext_vc[l])->ptr;
+      c->kc[l] = hold(c, ext_kc[l], &rc)->ptr;
+      c->vc[l] = hold(c, ext_vc[l], &rc)->ptr;
     } else {
       A(c->kv_bytes, &c->kc[l]);
       A(c->kv_bytes, &c->vc[l]);
     }
   }
-  A(g.embedding_dim * 4, (void**)&c->x);
-  A(g.embedding_dim * 4, (void**)&c->partial);
-  A(dim_l * 4, (void**)&c->qbuf);
-  A(dim_l * 4, (void**)&c->attn);
-  A(hidden_l * 4, (void**)&c->h);
-  A(g.vocab_size * 4, (void**)&c->logits);
-  size_t tmp_n = dim_l + 2 * kv_dim_l;
-  if (2 * hidden_l > tmp_n) tmp_n = 2 * hidden_l;
-  if (g.embedding_dim > tmp_n) tmp_n = g.embedding_dim;
-  A(tmp_n * 4, (void**)&c->tmp);
-  {
-    auto act_bytes = [](uint32_t t, size_t n) { return t == CRABML_HIP_F32 ? (size_t)16 : act_layout(t, n).total; };
-    size_t a_dim = act_bytes(qt, g.embedding_dim), a_out = act_bytes(out_qt, g.embedding_dim);
-    A(a_dim > a_out ? a_dim : a_out, (void**)&c->act_dim);
-    A(act_bytes(qt, dim_l), (void**)&c->act_attn);
-    A(act_bytes(qt, hidden_l), (void**)&c->act_hid);
-    A(g.embedding_dim * 4, (void**)&c->xn);
+  A(dim * 4, &c->x);
+  A(dim * 4, &c->partial);
+  A(dim_l * 4, &c->qbuf);
+  A(dim_l * 4, &c->attn);
+  A(hidden_l * 4, &c->h);
+  A(g.vocab_size * 4, &c->logits);
+  A(std::max({dim_l + 2 * kv_dim_l, 2 * hidden_l, dim}) * 4, &c->tmp);
+  const auto act_bytes = [](uint32_t t, size_t n) { return t == CRABML_HIP_F32 ? (size_t)16 : act_layout(t, n).total; };
+  A(std::max(act_bytes(c->qt, dim), act_bytes(c->out_qt, dim)), &c->act_dim);
+  A(act_bytes(c->qt, dim_l), &c->act_attn);
+  A(act_bytes(c->qt, hidden_l), &c->act_hid);
+  A(dim * 4, &c->xn);
+  A(g.seq_len * (size_t)(c->npairs ? c->npairs : 1) * 2 * 4, &c->rope);
+  if (p.exact_long_ok) {
+    A(n_heads_l * g.seq_len * 4, &c->scores_g);
+    A(n_heads_l * g.seq_len * 2, &c->p16);
   }
-  A(g.seq_len * (size_t)(c->npairs ? c->npairs : 1) * 2 * 4, (void**)&c->rope);
-  {
-    const size_t grp = n_heads_l / n_kv_l;
-    const bool long_geom = g.use_f16_kv_cache && hd % 32 == 0 && (grp == 1 || grp == 2 || grp == 4 || grp == 8) &&
-                           !(g.flags & CRABML_HIP_LLAMA_NO_LONG_ATTENTION);
-    c->attn_long_ok = long_geom && g.seq_len % 8 == 0;
-    c->attn_long_from = g.attn_long_from ? g.attn_long_from : 224;  // exact kernels: measured crossover on MI355X (Llama-3-8B shape) ~200-220
-    if (c->attn_long_ok && g.seq_len * 4 > 64 * 1024) {
-      // the softmax kernels keep a head's score row in LDS: rows past 16384 positions need the raised dynamic-LDS limit,
-      // rows past ~38000 do not fit at all (the step then stays on the one-workgroup-per-head kernel)
-      const int lds = (int)(g.seq_len * 4);
-      if (lds > 150 * 1024 ||
-          raise_dyn_lds(dev, (const void*)k_attn_softmax<16>, lds) != hipSuccess ||
-          raise_dyn_lds(dev, (const void*)k_attn_softmax<4>, lds) != hipSuccess)
-        c->attn_long_ok = false;
-      (void)hipGetLastError();
-    }
-    c->exact_long_ok = c->attn_long_ok;
-    if (c->attn_long_ok) {
-      A(n_heads_l * g.seq_len * 4, (void**)&c->scores_g);
-      A(n_heads_l * g.seq_len * 2, (void**)&c->p16);
-      if (!(g.flags & CRABML_HIP_LLAMA_NO_PV_PRODUCER_WAVES) && g.seq_len % 4 == 0) {
-        const PvSplitKernel pv = pv_split_kernel((int)grp);
-        c->pv_split = raise_dyn_lds(dev, (const void*)pv.fn, (int)pv.lds) == hipSuccess;
-        (void)hipGetLastError();
-      }
-    }
-    // the fast step's long-context attention: split-KV with f32 accumulation (k_attn_flash) unless the exact chain is asked for
-    // (k_attn_flash reads the cache rows only -- head_dim halves each --, so any seq_len will do: a cache of 1001 positions must not
-    // fall back to one workgroup per head, 45 us per layer at 900 positions)
-    if (long_geom && !dev->strict_order && !(g.flags & CRABML_HIP_LLAMA_EXACT_ATTENTION)) {
-      c->flash_ticket = (g.flags & CRABML_HIP_LLAMA_FLASH_TICKET) != 0;
-      const FlashFn fn = flash_kernel((int)grp, (int)hd, qt == CRABML_HIP_Q8_1, c->flash_ticket);
-      if (fn != nullptr && raise_dyn_lds(dev, (const void*)fn, (int)flash_lds_bytes((int)grp, (int)hd)) == hipSuccess) {
-        int S = dev->n_cu / (int)n_kv_l;
-        S = S < 1 ? 1 : S > FLASH_MAX_SLICES ? FLASH_MAX_SLICES : S;
-        if (const char* e = test_hook("CRABML_HIP_FLASH_SLICES")) {  // tuning hook (tools/flash_sweep.py): slices per kv head in the grid
-          const int v = atoi(e);
-          if (v >= 1 && v <= FLASH_MAX_SLICES) S = v;
-        }
-        c->flash_S = S;
-        if (const char* e = test_hook("CRABML_HIP_FLASH_MIN_ROWS")) {  // tuning hook (tools/flash_sweep.py); armed like ASSUME_CUS
-          const int v = atoi(e);
-          if (v >= 8 && v <= 65536) c->flash_min_rows = v;
-        }
-        A(n_kv_l * (size_t)S * flash_part_floats((int)grp, (int)hd) * 4, (void**)&c->flash_part);
-        A(n_kv_l * 4, (void**)&c->flash_tick);
-        if (rc == 0 && !dry && hipMemsetAsync(c->flash_tick, 0, n_kv_l * 4, dev->stream) != hipSuccess) rc = CRABML_HIP_UNEXPECTED;
-        c->attn_flash = rc == 0;
-        if (c->attn_flash) c->attn_long_ok = true;
-        // Below ~768 cached positions the merge inside the launch (last-arriving workgroup of a kv head, ticket word) beats the
-        // second launch -- 7.4 vs 5.1 + 4.1 us per layer at 128 positions, 8.7 vs 10.0 at 512, 10.8 vs 9.95 at 1024
-        // (profiles/r05_flash_ticket_sweep.md; same partials, same merge order: bit-identical): a third graph variant serves that range.
-        if (c->attn_flash && !c->flash_ticket) {
-          size_t until = 768;
-          if (const char* e = test_hook("CRABML_HIP_FLASH_TICKET_UNTIL")) until = (size_t)atol(e);  // tuning hook: 0 = never
-          const FlashFn tfn = flash_kernel((int)grp, (int)hd, qt == CRABML_HIP_Q8_1, true);
-          if (until > 0 && tfn != nullptr && raise_dyn_lds(dev, (const void*)tfn, (int)flash_lds_bytes((int)grp, (int)hd)) == hipSuccess)
-            c->flash_ticket_until = until;
-          (void)hipGetLastError();
-        }
-        // the prompt pass's causal attention of the fast step (k_attn_flash_rows): 70 KB of LDS at head_dim 128
-        if (c->attn_flash && flash_rows_kernel((int)hd) != nullptr &&
-            raise_dyn_lds(dev, (const void*)flash_rows_kernel((int)hd), (int)flash_rows_lds_bytes((int)hd)) == hipSuccess)
-          c->attn_flash_rows = true;
-        (void)hipGetLastError();
-        // k_attn_flash + merge overtake the staged one-workgroup kernel between 64 and 96 cached positions (8B shape, per layer:
-        // 51.0 vs 51.6 us at 64, 52.2 vs 51.4 at 96, 59.0 vs 51.8 at 224; profiles/r04_flash_sweep.log)
-        if (c->attn_flash && g.attn_long_from == 0) c->attn_long_from = 96;
-      }
-      (void)hipGetLastError();
-    }
-    // short-context attention with K / V staged through LDS (f16 cache): variant 0 serves positions < S
-    if (g.use_f16_kv_cache && hd % 8 == 0 && !(g.flags & CRABML_HIP_LLAMA_NO_STAGED_ATTENTION)) {
-      const size_t S = c->attn_long_ok && c->attn_long_from < g.seq_len ? c->attn_long_from : g.seq_len;
-      const size_t lds = attn_s_lds_bytes((int)S, (int)hd);
-      if (lds <= 150 * 1024 && raise_dyn_lds(dev, (const void*)attn_s_kernel((int)hd), (int)lds) == hipSuccess) {
-        c->attn_s_rows = (int)S;
-        c->attn_s_lds = lds;
-      }
-      (void)hipGetLastError();
-    }
+  if (p.attn_flash) {
+    A(n_kv_l * (size_t)p.flash_S * flash_part_floats((int)(n_heads_l / n_kv_l), c->hd) * 4, &c->flash_part);
+    A(n_kv_l * 4, &c->flash_tick);
+    if (rc == 0 && !dev->dry && hipMemsetAsync(c->flash_tick, 0, n_kv_l * 4, dev->stream) != hipSuccess) rc = CRABML_HIP_UNEXPECTED;
   }
-  A(8 * sizeof(int), (void**)&c->state);
-  A((g.embedding_dim / 16 + g.embedding_dim) * 8, (void**)&c->slots);
-  // tp > 1: the epilogue also hosts the collective when the group is the P2P kind (or in the collective-free dry run)
-  const bool p2p_comm = c->comm != nullptr && c->comm->p2p;
-  // (not for the K-quant segment path -- a Q4_1 body with a classifier of another format runs it: its wo / ffn_down launches
-  // host neither the norm epilogue nor the collective, so over a P2P group the stand-alone all-reduce launch must run)
-  c->norm_epi = !generic && !c->kfused && (tp == 1 || p2p_comm || c->tp_dry) && !(g.flags & CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) &&
-                (int)(g.embedding_dim / 32) <= dev->n_cu;  // every workgroup of the gather must be resident
-  c->norm_epi_k = c->kfused && wt == CRABML_HIP_Q4_K && out_qt == CRABML_HIP_Q8_K && tp == 1 &&
-                  !(g.flags & CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) && g.embedding_dim % 256 == 0 && (int)(g.embedding_dim / 32) <= dev->n_cu;
-  c->defer_norm = c->norm_epi && tp == 1 && !ord && !dev->strict_order && (wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0) &&
-                  !(g.flags & CRABML_HIP_LLAMA_EXACT_NORM) && (int)(g.embedding_dim / 32) <= dev->n_cu;
-  if (c->defer_norm) A(g.embedding_dim / 16 * 4, (void**)&c->rsums);
-  // A tensor-parallel rank's gate/up: hidden / tp / 32 workgroups of 32 rows would leave most CUs idle.  h stays f32 from workgroups
-  // of `gu_rows` rows (the largest even divisor of the rank's rows, at most 32, that gives at least one workgroup per CU) and
-  // ffn_down quantizes it in its prologue.
-  if (c->norm_epi && tp > 1 && !ord && !dev->strict_order && (wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0) &&
-      !(g.flags & CRABML_HIP_LLAMA_NO_H_CONSUMER_QUANT) && hidden_l % 32 == 0 && (int)(hidden_l / 32) * 2 <= dev->n_cu && !dry) {
-    int pick = 0;
-    for (int r = 30; r >= 2 && !pick; r -= 2)
-      if (hidden_l % r == 0 && (int)(hidden_l / r) >= dev->n_cu && (int)(hidden_l / r) <= 2 * dev->n_cu) pick = r;
-    if (pick && q8_0_lds_bytes((int)(hidden_l / 32)) <= 60 * 1024) c->gu_rows = pick;
-  }
-  c->q8k_producers = c->norm_epi_k && !(g.flags & (CRABML_HIP_LLAMA_NO_RHS_PROLOGUE | CRABML_HIP_LLAMA_NO_Q8K_PRODUCERS)) && dim_l % 256 == 0 &&
-                     hidden_l % 256 == 0 && (hd == 64 || hd == 128 || hd == 256) && (int)(hidden_l / 32) <= 2 * dev->n_cu;
-  // the fast Q4_K step: wo leaves x only, gate | up normalizes and quantizes the row itself (k_gateup_k_lds<.., NORMIN>; the same bits)
-  c->k_norm_in = c->q8k_producers && wt == CRABML_HIP_Q4_K && tp == 1 && !ord && !dev->strict_order && g.embedding_dim % 256 == 0 && g.embedding_dim / 256 <= 32 &&
-                 !(g.flags & (CRABML_HIP_LLAMA_NO_K_NORM_IN | CRABML_HIP_LLAMA_SPLIT_CHUNKS_ALWAYS | CRABML_HIP_LLAMA_SPLIT_CHUNKS_NEVER));
-  if (c->k_norm_in && !c->rsums) A(g.embedding_dim / 16 * 4, (void**)&c->rsums);
-  if (c->q8k_producers) {
-    A(dim_l * 8, (void**)&c->a8gran);
-    A(hidden_l * 8, (void**)&c->h8gran);
+  A(8 * sizeof(int), &c->state);
+  A((dim / 16 + dim) * 8, &c->slots);
+  if (p.defer_norm || p.k_norm_in) A(dim / 16 * 4, &c->rsums);
+  if (p.q8k_producers) {
+    A(dim_l * 8, &c->a8gran);
+    A(hidden_l * 8, &c->h8gran);
   }
   c->out_cap = (int)g.seq_len;
-  A((size_t)c->out_cap * 4, (void**)&c->out_tokens);
-  A(ARGMAX_BLOCKS * 4, (void**)&c->am_val);
-  A(ARGMAX_BLOCKS * 4, (void**)&c->am_idx);
-  A(2 * sizeof(int), (void**)&c->am_best);
+  A((size_t)c->out_cap * 4, &c->out_tokens);
+  A(ARGMAX_BLOCKS * 4, &c->am_val);
+  A(ARGMAX_BLOCKS * 4, &c->am_idx);
+  A(2 * sizeof(int), &c->am_best);
+  return rc;
+}
+
+// RoPE table with the reference's own recurrence (rope.rs:47-54: theta_scale = 10000^(-2/hd), theta = pos,
+// theta *= theta_scale per pair; base hard-coded) evaluated with the host libm, as the trait op does.
+// Qwen2 and Gemma: NEOX's table (rope.rs:65-80: theta_i = pos / 10000^(2 i / hd), i < rope_dim / 2), the trait op's own code (lazy.hip)
+static std::vector<float> rope_table(const crabml_hip_llama* c) {
+  const size_t seq = c->cfg.seq_len, hd = (size_t)c->hd;
+  std::vector<float> tab(seq * (size_t)(c->npairs ? c->npairs : 1) * 2, 0.f);
+  const float theta_scale = powf(10000.0f, -2.0f / (float)hd);
+  for (size_t p = 0; p < seq; p++) {
+    if (c->qwen2 || c->gemma) {
+      rope_table_neox(tab.data() + p * c->npairs * 2, p, hd, (size_t)c->npairs);
+      continue;
+    }
+    float theta = (float)p;
+    for (int i = 0; i < c->npairs; i++) {
+      tab[(p * c->npairs + i) * 2] = cosf(theta);
+      tab[(p * c->npairs + i) * 2 + 1] = sinf(theta);
+      theta *= theta_scale;
+    }
+  }
+  return tab;
+}
+
+// the rope table to the device, the step's state and hand-off words zeroed; blocks until done (`tab` is the caller's)
+static hipError_t init_state(crabml_hip_llama* c, const std::vector<float>& tab) {
+  const auto& g = c->cfg;
+  hipStream_t st = c->dev->stream;
+  hipError_t e = hipMemcpyAsync(c->rope, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(c->state, 0, 8 * sizeof(int), st);
+  // vocabulary split: the entries of the other ranks' shards read -inf (an element-wise max over the ranks is the all-gather)
+  if (e == hipSuccess && c->split_vocab) e = hipMemsetD32Async((hipDeviceptr_t)c->logits, (int)0xff800000u, g.vocab_size, st);
+  if (e == hipSuccess) e = hipMemsetAsync(c->slots, 0, (g.embedding_dim / 16 + g.embedding_dim) * 8, st);
+  if (e == hipSuccess && c->a8gran) e = hipMemsetAsync(c->a8gran, 0, (size_t)c->dim_l * 8, st);
+  if (e == hipSuccess && c->h8gran) e = hipMemsetAsync(c->h8gran, 0, (size_t)c->hidden_l * 8, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
+}
+
+// One decode step per attention variant into a graph (token / pos / step are read from device memory by the kernels).
+// tp > 1 without a communicator = a rank of the single-device simulation: driven segment by segment, no graph.
+// tp > 1 over RCCL launches eagerly unless CRABML_HIP_LLAMA_TP_GRAPH asks for the collectives to be captured too.
+// False: the caller asked for the graph path on one device and it could not be had.
+static bool capture_graphs(crabml_hip_llama* c, const ModelFacts& f) {
+  const auto& g = c->cfg;
+  const bool want_graph = !(g.flags & CRABML_HIP_LLAMA_NO_GRAPH) &&
+                          (f.tp == 1 || f.tp_dry || f.p2p_comm || (c->comm != nullptr && (g.flags & CRABML_HIP_LLAMA_TP_GRAPH)));
+  if (!want_graph) return true;
+  const int nvar = c->plan.attn_long_ok ? (c->plan.flash_ticket_until > 0 ? 3 : 2) : 1;
+  bool ok = true;
+  for (int v = 0; v < nvar && ok; v++) ok = capture_step(c, v, &c->graph[v], &c->exec[v]);
+  (void)hipGetLastError();
+  c->use_graph = ok;
+  c->attn_variant = 0;
+  return ok || f.tp > 1;  // tp > 1: if RCCL could not be captured the step simply runs eagerly
+}
+
+// ext_kc / ext_vc (lazy.hip): the caller's KV caches, used in place (alloc_step_buffers)
+static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_config_t* cfg, const crabml_hip_llama_weights_t* w,
+                             crabml_hip_buf* const* ext_kc, crabml_hip_buf* const* ext_vc, crabml_hip_llama_t** out,
+                             const crabml_hip_llama_arch_t* arch = nullptr) {
+  if (!dev || !cfg || !w || !out) return CRABML_HIP_BAD_INPUT;
+  *out = nullptr;
+  ModelFacts f;
+  CH_TRY(validate_config(dev, *cfg, w, arch, &f));
+  CH_TRY(validate_weights(dev, *cfg, w, &f));
+  if (!dev->dry) CH_USE(dev);
+  const StepPlan plan = decide_step(dev, *cfg, f, read_flash_hooks());
+  crabml_hip_llama* c = nullptr;
+  CH_TRY(new_context(dev, *cfg, f, plan, ext_kc != nullptr, &c));
+  int rc = retain_weights(c, w, arch, f);
+  rc = alloc_step_buffers(c, ext_kc, ext_vc, rc);
   if (rc != 0) {
     crabml_hip_llama_destroy(c);
     return rc;
   }
-  // RoPE table with the reference's own recurrence (rope.rs:47-54: theta_scale = 10000^(-2/hd), theta = pos,
-  // theta *= theta_scale per pair; base hard-coded) evaluated with the host libm, as the trait op does.
-  // Qwen2 and Gemma: NEOX's table (rope.rs:65-80: theta_i = pos / 10000^(2 i / hd), i < rope_dim / 2), the trait op's own code (lazy.hip)
-  {
-    std::vector<float> tab(g.seq_len * (size_t)(c->npairs ? c->npairs : 1) * 2, 0.f);
-    const float theta_scale = powf(10000.0f, -2.0f / (float)hd);
-    for (size_t p = 0; p < g.seq_len; p++) {
-      if (qwen2 || gemma) {
-        rope_table_neox(tab.data() + p * c->npairs * 2, p, hd, (size_t)c->npairs);
-        continue;
-      }
-      float theta = (float)p;
-      for (int i = 0; i < c->npairs; i++) {
-        tab[(p * c->npairs + i) * 2] = cosf(theta);
-        tab[(p * c->npairs + i) * 2 + 1] = sinf(theta);
-        theta *= theta_scale;
-      }
-    }
-    hipError_t e = dry ? hipErrorUnknown : hipMemcpyAsync(c->rope, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, dev->stream);
-    if (dry) {  // record-only test device: nothing to initialize
-      *out = c;
-      return 0;
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(c->state, 0, 8 * sizeof(int), dev->stream);
-    // vocabulary split: the entries of the other ranks' shards read -inf (an element-wise max over the ranks is the all-gather)
-    if (e == hipSuccess && c->split_vocab) e = hipMemsetD32Async((hipDeviceptr_t)c->logits, (int)0xff800000u, g.vocab_size, dev->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->slots, 0, (g.embedding_dim / 16 + g.embedding_dim) * 8, dev->stream);
-    if (e == hipSuccess && c->a8gran) e = hipMemsetAsync(c->a8gran, 0, dim_l * 8, dev->stream);
-    if (e == hipSuccess && c->h8gran) e = hipMemsetAsync(c->h8gran, 0, hidden_l * 8, dev->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
-    if (e != hipSuccess) {
-      crabml_hip_llama_destroy(c);
-      return hip_fail(dev, e, "llama init", __FILE__, __LINE__);
-    }
+  const std::vector<float> tab = rope_table(c);
+  if (dev->dry) {  // record-only test device: nothing to initialize, nothing to capture
+    *out = c;
+    return 0;
   }
-  // capture one decode step into a graph (token / pos / step are read from device memory by the kernels).
-  // tp > 1 without a communicator = a rank of the single-device simulation: driven segment by segment, no graph.
-  // tp > 1 over RCCL launches eagerly unless CRABML_HIP_LLAMA_TP_GRAPH asks for the collectives to be captured too.
-  const bool want_graph = !(g.flags & CRABML_HIP_LLAMA_NO_GRAPH) &&
-                          (tp == 1 || c->tp_dry || p2p_comm || (c->comm != nullptr && (g.flags & CRABML_HIP_LLAMA_TP_GRAPH)));
-  if (want_graph) {
-    const int nvar = c->attn_long_ok ? (c->flash_ticket_until > 0 ? 3 : 2) : 1;
-    bool ok = true;
-    for (int v = 0; v < nvar && ok; v++) {
-      ok = false;
-      hipError_t e = hipStreamBeginCapture(dev->stream, hipStreamCaptureModeThreadLocal);
-      if (e != hipSuccess) break;
-      c->capturing = true;
-      c->attn_variant = v;
-      int erc = enqueue_step(c);
-      c->capturing = false;
-      hipGraph_t graph = nullptr;
-      hipError_t e2 = hipStreamEndCapture(dev->stream, &graph);
-      if (erc == 0 && e2 == hipSuccess && graph) {
-        hipGraphExec_t exec = nullptr;
-        if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-          c->graph[v] = graph;
-          c->exec[v] = exec;
-          ok = true;
-        } else {
-          (void)hipGraphDestroy(graph);
-        }
-      } else if (graph) {
-        (void)hipGraphDestroy(graph);
-      }
-    }
-    (void)hipGetLastError();
-    c->use_graph = ok;
-    c->attn_variant = 0;
-    if (!ok && tp == 1) {  // fail loudly: the caller asked for the graph path
-      crabml_hip_llama_destroy(c);
-      CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: hipGraph capture/instantiate failed");
-    }
-    // tp > 1: if RCCL could not be captured the step simply runs eagerly
+  const hipError_t e = init_state(c, tab);
+  if (e != hipSuccess) {
+    crabml_hip_llama_destroy(c);
+    return hip_fail(dev, e, "llama init", __FILE__, __LINE__);
+  }
+  if (!capture_graphs(c, f)) {  // fail loudly: the caller asked for the graph path
+    crabml_hip_llama_destroy(c);
+    CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: hipGraph capture/instantiate failed");
   }
   *out = c;
   return 0;
@@ -2742,8 +2825,7 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   CH_LIVE(dev);
   CH_USE(dev);
   CH_FLUSH(dev);
-  if (c->tp > 1 || c->kfused || c->generic || c->ord || dev->strict_order || c->ext_kv ||
-      !(c->wtype == CRABML_HIP_Q4_0 || c->wtype == CRABML_HIP_Q8_0 || c->wtype == CRABML_HIP_Q4_1))
+  if (c->plan.path != SegPath::Fused5 || c->plan.ordered || c->tp > 1 || c->ext_kv)  // (decide_step: what Fused5 and !ordered imply)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama debug_tap: only the five-launch Q4_0 / Q8_0 / Q4_1 layers of the fast step on one device");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim;
@@ -2768,9 +2850,9 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   c->attn_variant = variant_of(c, pos);
   tap.arm((int)layer);
   tap.note(CRABML_HIP_PLAN_N_CU, dev->n_cu);
-  tap.note(CRABML_HIP_PLAN_DEFER_NORM, c->defer_norm ? 1 : 0);
-  tap.note(CRABML_HIP_PLAN_NORM_EPILOGUE, c->norm_epi ? 1 : 0);
-  tap.note(CRABML_HIP_PLAN_ATTN_VARIANT, c->attn_variant + (c->attn_variant >= 1 && c->attn_flash ? 16 : 0));
+  tap.note(CRABML_HIP_PLAN_DEFER_NORM, c->plan.defer_norm ? 1 : 0);
+  tap.note(CRABML_HIP_PLAN_NORM_EPILOGUE, c->plan.norm_epi ? 1 : 0);
+  tap.note(CRABML_HIP_PLAN_ATTN_VARIANT, c->attn_variant + (c->attn_variant >= 1 && c->plan.attn_flash ? 16 : 0));
   const int rc = enqueue_step(c);
   tap.disarm();
   if (rc != 0) return rc;
@@ -2826,6 +2908,26 @@ int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* c, const uint32_t* to
   CH_TRY(c->pftap.read_back(dev, &h));
   CH_HIP(dev, hipStreamSynchronize(dev->stream));
   return export_fields(dev, c->pftap, h, fld, CRABML_HIP_PFTAP_FIELDS, CRABML_HIP_PFTAP_PLAN, CRABML_HIP_PFTAP_PLAN_WORDS, dst, dst_bytes, dir);
+}
+
+// test hook (crabml_hip_debug.h): the step plan of the context this configuration creates; the record-only device is welcome
+int crabml_hip_debug_step_plan(crabml_hip_device_t* dev, const crabml_hip_llama_config_t* cfg, const crabml_hip_llama_weights_t* w,
+                               const crabml_hip_llama_arch_t* arch, int32_t* words, size_t n_words) {
+  if (!dev || !cfg || !w || !words || n_words < CRABML_HIP_STEPPLAN_WORDS) return CRABML_HIP_BAD_INPUT;
+  if (!dev->dry) CH_USE(dev);
+  CH_FLUSH(dev);
+  crabml_hip_llama* c = nullptr;
+  CH_TRY(llama_create_impl(dev, cfg, w, nullptr, nullptr, &c, arch));
+  const StepPlan& p = c->plan;
+  int graphs = 0;
+  for (int v = 0; v < 3; v++) graphs += c->exec[v] != nullptr;
+  const int32_t v[CRABML_HIP_STEPPLAN_WORDS] = {
+      (int32_t)p.path, p.ordered, p.norm_epi, p.norm_epi_k, p.defer_norm, p.gu_rows, p.q8k_producers, p.k_norm_in, p.attn_long_ok,
+      p.exact_long_ok, (int32_t)p.attn_long_from, p.pv_split, p.attn_flash, p.flash_ticket, (int32_t)p.flash_ticket_until, p.attn_flash_rows,
+      p.flash_S, p.flash_min_rows, p.attn_s_rows, (int32_t)p.attn_s_lds, c->use_graph, graphs, dev->n_cu};  // CRABML_HIP_STEPPLAN_* order
+  memcpy(words, v, sizeof v);
+  (void)crabml_hip_llama_destroy(c);
+  return 0;
 }
 
 // parity hook (crabml_hip_debug.h): k_attn_flash by itself, on caller-supplied q / K / V

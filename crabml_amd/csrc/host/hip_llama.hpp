@@ -61,6 +61,67 @@ class TpComm {
 
 class HipLlamaRunner {
  public:
+  // what crabml_hip_llama_create* is handed for a model: the C structs and the pointer arrays behind them
+  struct CreateArgs {
+    crabml_hip_llama_config_t c{};
+    crabml_hip_llama_weights_t cw{};
+    crabml_hip_llama_arch_t arch{};
+    bool plain = false;  // a Llama model without biases: the plain create serves it
+    std::vector<const crabml_hip_buf_t*> att, ffn, wq, wk, wv, wo, gate, down, up, bq, bk, bv;
+    CreateArgs(const LlamaConfig& conf, const LlamaWeights<HipTensor>& W, size_t seq_len, bool use_f16_kv_cache, bool use_graph, bool prefetch,
+               int tp_size, int tp_rank, const TpComm* comm, bool norm_epilogue, int extra_flags, size_t attn_long_from, size_t prefill_chunk) {
+      c.embedding_dim = conf.embedding_dim;
+      c.hidden_dim = conf.hidden_dim;
+      c.n_layers = conf.n_layers;
+      c.n_heads = conf.n_heads;
+      c.n_kv_heads = conf.n_kv_heads;
+      c.vocab_size = conf.vocab_size;
+      c.seq_len = seq_len;
+      c.rope_dim = conf.rope_dim.value_or(conf.head_size());
+      c.rms_norm_eps = conf.rms_norm_eps;
+      c.use_f16_kv_cache = use_f16_kv_cache ? 1 : 0;
+      c.flags = (use_graph ? 0 : CRABML_HIP_LLAMA_NO_GRAPH) | (prefetch ? 0 : CRABML_HIP_LLAMA_NO_PREFETCH) |
+                (norm_epilogue ? 0 : CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) | extra_flags;
+      c.tp_size = tp_size;
+      c.tp_rank = tp_rank;
+      c.tp_comm = comm ? comm->raw() : nullptr;
+      c.attn_long_from = attn_long_from;
+      c.prefill_chunk = prefill_chunk;
+      auto raws = [](const std::vector<HipTensor>& v) {
+        std::vector<const crabml_hip_buf_t*> r;
+        for (const auto& t : v) r.push_back(t.raw());
+        return r;
+      };
+      att = raws(W.rms_att_weight), ffn = raws(W.rms_ffn_weight), wq = raws(W.wq), wk = raws(W.wk), wv = raws(W.wv), wo = raws(W.wo),
+      gate = raws(W.ffn_gate_weight), down = raws(W.ffn_down_weight), up = raws(W.ffn_up_weight);
+      for (auto* v : {&att, &ffn, &wq, &wk, &wv, &wo, &gate, &down, &up})
+        if (v->size() != conf.n_layers) throw Error(ErrorKind::ModelError, "weights do not have n_layers entries");
+      cw.token_embed = W.token_embed.raw();
+      cw.rms_att_weight = att.data();
+      cw.rms_ffn_weight = ffn.data();
+      cw.wq = wq.data();
+      cw.wk = wk.data();
+      cw.wv = wv.data();
+      cw.wo = wo.data();
+      cw.ffn_gate_weight = gate.data();
+      cw.ffn_down_weight = down.data();
+      cw.ffn_up_weight = up.data();
+      cw.rms_final_weight = W.rms_final_weight.raw();
+      cw.output_weight = W.output_weight ? W.output_weight->raw() : nullptr;
+      // the architecture and Qwen2's biases (crabml_hip_llama_create_arch; Llama: the plain create)
+      bq = raws(W.bq), bk = raws(W.bk), bv = raws(W.bv);
+      arch.architecture = conf.architecture;
+      if (conf.architecture == ARCH_QWEN2 || !bq.empty() || !bk.empty() || !bv.empty()) {  // (biases on a Llama model: the C ABI refuses)
+        for (auto* v : {&bq, &bk, &bv})
+          if (v->size() != conf.n_layers) throw Error(ErrorKind::ModelError, "qwen2: the biases do not have n_layers entries");
+        arch.bq = bq.data();
+        arch.bk = bk.data();
+        arch.bv = bv.data();
+      }
+      plain = conf.architecture == ARCH_LLAMA && bq.empty() && bk.empty() && bv.empty();
+    }
+    CreateArgs(const CreateArgs&) = delete;
+  };
   // create_entry (tests): 0 = crabml_hip_llama_create for a Llama model without biases, crabml_hip_llama_create_arch otherwise;
   // 1 = create_arch with the architecture struct always; 2 = create_arch(NULL) (Llama models)
   HipLlamaRunner(const LlamaConfig& conf, std::shared_ptr<LlamaWeights<HipTensor>> w, HipTensorDeviceRef device,
@@ -68,65 +129,24 @@ class HipLlamaRunner {
                  int tp_rank = 0, std::shared_ptr<TpComm> comm = nullptr, bool norm_epilogue = true, int extra_flags = 0,
                  size_t attn_long_from = 0, size_t prefill_chunk = 0, int create_entry = 0)
       : conf_(conf), weights_(std::move(w)), device_(std::move(device)), comm_(std::move(comm)), tp_size_(tp_size > 1 ? tp_size : 1) {
-    crabml_hip_llama_config_t c{};
-    c.embedding_dim = conf.embedding_dim;
-    c.hidden_dim = conf.hidden_dim;
-    c.n_layers = conf.n_layers;
-    c.n_heads = conf.n_heads;
-    c.n_kv_heads = conf.n_kv_heads;
-    c.vocab_size = conf.vocab_size;
-    c.seq_len = seq_len;
-    c.rope_dim = conf.rope_dim.value_or(conf.head_size());
-    c.rms_norm_eps = conf.rms_norm_eps;
-    c.use_f16_kv_cache = use_f16_kv_cache ? 1 : 0;
-    c.flags = (use_graph ? 0 : CRABML_HIP_LLAMA_NO_GRAPH) | (prefetch ? 0 : CRABML_HIP_LLAMA_NO_PREFETCH) |
-              (norm_epilogue ? 0 : CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) | extra_flags;
-    c.tp_size = tp_size;
-    c.tp_rank = tp_rank;
-    c.tp_comm = comm_ ? comm_->raw() : nullptr;
-    c.attn_long_from = attn_long_from;
-    c.prefill_chunk = prefill_chunk;
-    auto raws = [](const std::vector<HipTensor>& v) {
-      std::vector<const crabml_hip_buf_t*> r;
-      for (const auto& t : v) r.push_back(t.raw());
-      return r;
-    };
-    const auto& W = *weights_;
-    auto att = raws(W.rms_att_weight), ffn = raws(W.rms_ffn_weight), wq = raws(W.wq), wk = raws(W.wk), wv = raws(W.wv),
-         wo = raws(W.wo), gate = raws(W.ffn_gate_weight), down = raws(W.ffn_down_weight), up = raws(W.ffn_up_weight);
-    for (auto* v : {&att, &ffn, &wq, &wk, &wv, &wo, &gate, &down, &up})
-      if (v->size() != conf.n_layers) throw Error(ErrorKind::ModelError, "weights do not have n_layers entries");
-    crabml_hip_llama_weights_t cw{};
-    cw.token_embed = W.token_embed.raw();
-    cw.rms_att_weight = att.data();
-    cw.rms_ffn_weight = ffn.data();
-    cw.wq = wq.data();
-    cw.wk = wk.data();
-    cw.wv = wv.data();
-    cw.wo = wo.data();
-    cw.ffn_gate_weight = gate.data();
-    cw.ffn_down_weight = down.data();
-    cw.ffn_up_weight = up.data();
-    cw.rms_final_weight = W.rms_final_weight.raw();
-    cw.output_weight = W.output_weight ? W.output_weight->raw() : nullptr;
-    // the architecture and Qwen2's biases (crabml_hip_llama_create_arch; Llama: the plain create)
-    auto bq = raws(W.bq), bk = raws(W.bk), bv = raws(W.bv);
-    crabml_hip_llama_arch_t arch{};
-    arch.architecture = conf.architecture;
-    if (conf.architecture == ARCH_QWEN2 || !bq.empty() || !bk.empty() || !bv.empty()) {  // (biases on a Llama model: the C ABI refuses)
-      for (auto* v : {&bq, &bk, &bv})
-        if (v->size() != conf.n_layers) throw Error(ErrorKind::ModelError, "qwen2: the biases do not have n_layers entries");
-      arch.bq = bq.data();
-      arch.bk = bk.data();
-      arch.bv = bv.data();
-    }
-    const bool plain = conf.architecture == ARCH_LLAMA && bq.empty() && bk.empty() && bv.empty();
+    const CreateArgs a(conf, *weights_, seq_len, use_f16_kv_cache, use_graph, prefetch, tp_size, tp_rank, comm_.get(), norm_epilogue, extra_flags,
+                       attn_long_from, prefill_chunk);
     if (create_entry == 2)
-      device_->check(crabml_hip_llama_create_arch(device_->raw(), &c, &cw, nullptr, &ctx_));
-    else if (plain && create_entry == 0)
-      device_->check(crabml_hip_llama_create(device_->raw(), &c, &cw, &ctx_));
+      device_->check(crabml_hip_llama_create_arch(device_->raw(), &a.c, &a.cw, nullptr, &ctx_));
+    else if (a.plain && create_entry == 0)
+      device_->check(crabml_hip_llama_create(device_->raw(), &a.c, &a.cw, &ctx_));
     else
-      device_->check(crabml_hip_llama_create_arch(device_->raw(), &c, &cw, &arch, &ctx_));
+      device_->check(crabml_hip_llama_create_arch(device_->raw(), &a.c, &a.cw, &a.arch, &ctx_));
+  }
+  // crabml_hip_debug_step_plan: the plan words (CRABML_HIP_STEPPLAN_*) of the context the constructor would create for these arguments
+  static std::vector<int32_t> step_plan(const LlamaConfig& conf, const LlamaWeights<HipTensor>& w, HipTensorDevice& device, size_t seq_len,
+                                        bool use_f16_kv_cache, bool use_graph, bool prefetch, int tp_size, int tp_rank, bool norm_epilogue,
+                                        int extra_flags, size_t attn_long_from) {
+    const CreateArgs a(conf, w, seq_len, use_f16_kv_cache, use_graph, prefetch, tp_size, tp_rank, nullptr, norm_epilogue, extra_flags,
+                       attn_long_from, 0);
+    std::vector<int32_t> words(CRABML_HIP_STEPPLAN_WORDS);
+    device.check(crabml_hip_debug_step_plan(device.raw(), &a.c, &a.cw, a.plain ? nullptr : &a.arch, words.data(), words.size()));
+    return words;
   }
   ~HipLlamaRunner() {
     if (ctx_) crabml_hip_llama_destroy(ctx_);

@@ -577,6 +577,25 @@ PYBIND11_MODULE(_host, m) {
         return tap_dict(t, names, words, CRABML_HIP_PFTAP_PLAN_WORDS, CRABML_HIP_PFTAP_PLAN);
       });
 
+  // what the context HipLlamaRunner(conf, weights, device, ...) would create runs (crabml_hip_debug_step_plan; the record-only device too)
+  m.def(
+      "debug_step_plan",
+      [](const LlamaConfig& conf, std::shared_ptr<Weights> w, std::shared_ptr<HipTensorDevice> dev, size_t seq_len, bool use_f16_kv_cache,
+         bool use_graph, bool prefetch, int tp_size, int tp_rank, bool norm_epilogue, int extra_flags, size_t attn_long_from) {
+        static const char* names[CRABML_HIP_STEPPLAN_WORDS] = {
+            "path", "ordered", "norm_epi", "norm_epi_k", "defer_norm", "gu_rows", "q8k_producers", "k_norm_in", "attn_long_ok", "exact_long_ok",
+            "attn_long_from", "pv_split", "attn_flash", "flash_ticket", "flash_ticket_until", "attn_flash_rows", "flash_S", "flash_min_rows",
+            "attn_s_rows", "attn_s_lds", "use_graph", "graphs", "n_cu"};
+        const std::vector<int32_t> words = HipLlamaRunner::step_plan(conf, *w, *dev, seq_len, use_f16_kv_cache, use_graph, prefetch, tp_size, tp_rank,
+                                                                     norm_epilogue, extra_flags, attn_long_from);
+        py::dict d;
+        for (int i = 0; i < CRABML_HIP_STEPPLAN_WORDS; i++) d[names[i]] = words[i];
+        return d;
+      },
+      py::arg("conf"), py::arg("weights"), py::arg("device"), py::arg("seq_len"), py::arg("use_f16_kv_cache"), py::arg("use_graph") = true,
+      py::arg("prefetch") = true, py::arg("tp_size") = 1, py::arg("tp_rank") = 0, py::arg("norm_epilogue") = true, py::arg("extra_flags") = 0,
+      py::arg("attn_long_from") = 0);
+
   py::class_<Runner>(m, "Llama2Runner")
       .def(py::init([](const LlamaConfig& conf, std::shared_ptr<Weights> w, std::shared_ptr<HipTensorDevice> dev,
                        size_t seq_len, bool use_f16_kv_cache) {

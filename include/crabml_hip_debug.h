@@ -270,6 +270,42 @@ enum {
 int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* ctx, const uint32_t* tokens, size_t n, size_t layer, float* logits, void* dst,
                                        size_t dst_bytes, crabml_hip_tap_entry_t* dir, size_t* need);
 
+/* test hook: what a decode context of this configuration would run.  Creates the context exactly as crabml_hip_llama_create_arch
+ * does (arch nullable = Llama), copies its step plan -- the one value that says which segment enqueuer, which segment forms and which
+ * attention forms the context takes -- into `words` (CRABML_HIP_STEPPLAN_WORDS of them; n_words smaller: CRABML_HIP_BAD_INPUT),
+ * destroys the context and returns create's own return code (on an error the words are left alone and the device holds create's
+ * message).  Unlike the create entry points it accepts the record-only device (CRABML_HIP_FLAG_DRY), where no kernel's LDS limit
+ * can be raised: the forms that need a raise read 0 there. */
+enum {
+  CRABML_HIP_STEPPLAN_PATH = 0,        /* 0 per-op segments (enqueue_segment_generic), 1 the five fused launches (enqueue_segment_t),
+                                          2 the K-quant fused launches (enqueue_segment_k) */
+  CRABML_HIP_STEPPLAN_ORDERED = 1,     /* strict-order device: the fused launches in their block-ordered form */
+  CRABML_HIP_STEPPLAN_NORM_EPI = 2,
+  CRABML_HIP_STEPPLAN_NORM_EPI_K = 3,
+  CRABML_HIP_STEPPLAN_DEFER_NORM = 4,
+  CRABML_HIP_STEPPLAN_GU_ROWS = 5,
+  CRABML_HIP_STEPPLAN_Q8K_PRODUCERS = 6,
+  CRABML_HIP_STEPPLAN_K_NORM_IN = 7,
+  CRABML_HIP_STEPPLAN_ATTN_LONG_OK = 8,
+  CRABML_HIP_STEPPLAN_EXACT_LONG_OK = 9,
+  CRABML_HIP_STEPPLAN_ATTN_LONG_FROM = 10,
+  CRABML_HIP_STEPPLAN_PV_SPLIT = 11,
+  CRABML_HIP_STEPPLAN_ATTN_FLASH = 12,
+  CRABML_HIP_STEPPLAN_FLASH_TICKET = 13,
+  CRABML_HIP_STEPPLAN_FLASH_TICKET_UNTIL = 14,
+  CRABML_HIP_STEPPLAN_ATTN_FLASH_ROWS = 15,
+  CRABML_HIP_STEPPLAN_FLASH_S = 16,
+  CRABML_HIP_STEPPLAN_FLASH_MIN_ROWS = 17,
+  CRABML_HIP_STEPPLAN_ATTN_S_ROWS = 18,
+  CRABML_HIP_STEPPLAN_ATTN_S_LDS = 19,
+  CRABML_HIP_STEPPLAN_USE_GRAPH = 20,  /* 1: the step is replayed from captured graphs, */
+  CRABML_HIP_STEPPLAN_GRAPHS = 21,     /*   this many (one per attention variant) */
+  CRABML_HIP_STEPPLAN_N_CU = 22,       /* compute units of the device */
+  CRABML_HIP_STEPPLAN_WORDS = 23
+};
+int crabml_hip_debug_step_plan(crabml_hip_device_t* dev, const crabml_hip_llama_config_t* cfg, const crabml_hip_llama_weights_t* w,
+                               const crabml_hip_llama_arch_t* arch, int32_t* words, size_t n_words);
+
 /* ---- measurement hook (bench.py `roofline` object) -------------------------------------------------
  * While enabled, every matmul_vec GEMV kernel launch is bracketed by a pair of HIP events recorded on
  * the device's own stream (the stream the kernel runs on); crabml_hip_prof_read() drains them and

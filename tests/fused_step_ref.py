@@ -60,10 +60,10 @@ def r_ss(n):
 @dataclass
 class Form:
     """which form of the step a context runs (the launch plan, from the code's own predicates in fused.hip)"""
-    defer: bool            # hop-free norm: c->defer_norm (Q4_0 / Q8_0, norm epilogue, not EXACT_NORM)
+    defer: bool            # hop-free norm: c->plan.defer_norm (Q4_0 / Q8_0, norm epilogue, not EXACT_NORM)
     kv_f16: bool
     seq_cap: int
-    flash_from: int = 0    # > 0: cached positions (pos + 1) from which k_attn_flash runs (c->attn_long_from with attn_flash)
+    flash_from: int = 0    # > 0: cached positions (pos + 1) from which k_attn_flash runs (c->plan.attn_long_from with attn_flash)
 
 
 @dataclass
