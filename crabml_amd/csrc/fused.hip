@@ -272,7 +272,7 @@ struct crabml_hip_llama {
   unsigned h_state_next = 0;
   static constexpr unsigned H_STATE_SLOTS = 256;
   // the two parity taps (test hooks, crabml_hip_debug.h): crabml_hip_llama_debug_tap arms `tap` for one eager decode step
-  // (enqueue_segment_t), crabml_hip_llama_debug_prefill_tap arms `pftap` for one chunk pass of the prompt path (prefill_chunk_pass,
+  // (enqueue_segment_t / enqueue_segment_k), crabml_hip_llama_debug_prefill_tap arms `pftap` for one chunk pass of the prompt path (prefill_chunk_pass,
   // where every field holds all rows of the pass); a scratch area each, allocated on the hook's first call
   TapRec tap{"llama debug_tap"}, pftap{"llama debug_prefill_tap"};
 };
@@ -1046,6 +1046,10 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
   // the rhs of wo / ffn_down quantized by the consuming kernel itself (no quantizer launch)
   const bool qin = nepi && !(g.flags & CRABML_HIP_LLAMA_NO_RHS_PROLOGUE) && dim_l % 256 == 0 && hidden_l % 256 == 0;
   const bool qout = qin && c->plan.q8k_producers;  // attention / gate-up write the planes, wo / ffn_down copy them
+  // wo leaves x and its chunk sums only -- wo_parts per 32-row chunk -- and gate | up runs its NORMIN form: one value for the wo launch,
+  // the gate | up launch and the tap (k_norm_in is never set on a strict-order device: decide_step)
+  const bool wo_x_only = !ordk && qout && c->plan.k_norm_in;
+  const int wo_parts = wo_x_only ? chunk_split(g.flags, dim_l, dim, dev->n_cu, true) : 1;
   // wnext / eps_next: the RMSNorm that consumes this GEMV's output (norm epilogue only); xin: the f32 rhs
   // qmode: 0 = rhs planes from global memory, 1 = quantize the f32 rhs in the kernel's prologue, 2 = copy finished planes
   auto gemv_out = [&](const crabml_hip_buf* w, const Act& a, const float* xin, int k, uint32_t stage, const float* wnext,
@@ -1060,6 +1064,9 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         void* od = (void*)(c->act_dim + al.off_d);
         void* ob = (void*)(c->act_dim + al.off_aux);
         const int split = chunk_split(g.flags, k, dim, dev->n_cu, x_only);
+        c->tap.note(seg / 2, stage == 2 ? CRABML_HIP_PLAN_SPLIT_WO : CRABML_HIP_PLAN_SPLIT_DOWN, split);
+        c->tap.note(seg / 2, stage == 2 ? CRABML_HIP_PLAN_QMODE_WO : CRABML_HIP_PLAN_QMODE_DOWN, qmode);
+        if (stage == 2) c->tap.note(seg / 2, CRABML_HIP_PLAN_WO_X_ONLY, x_only ? 1 : 0);
         if (ordk) {  // (qmode is 1 or 2 here: `qin` holds on every ordered context)
           launch_k(st, R, nq_ord_k_kernel(split, qmode == 2 ? 2 : 1), dim3(dim / 32 * split), dim3(1024), q8k_ord_lds_bytes(k, 32 / split), planes_of(w), a,
                    xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
@@ -1081,14 +1088,33 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     return P1();
   };
 
+  // the tap (test hook): host-side copies between the launches of the tapped layer; a no-op unless a tapped step is being enqueued.
+  // A set of planes is copied where a launch wrote it to global memory, a Q8_K set's class-major plane as a field of its own.
+  TapRec& tap = c->tap;
+  auto TAP = [&](bool on, int f, const void* src, size_t bytes) -> int { return on ? tap.copy(c, f, src, bytes) : 0; };
+  auto TAPQ = [&](bool on, int f, int f_qp, const void* planes, uint32_t qt, int n) -> int {
+    if (!on) return 0;
+    const ActLayout al = act_layout(qt, (size_t)n);
+    CH_TRY(tap.copy(c, f, planes, qt == CRABML_HIP_F32 ? (size_t)n * 4 : al.total));
+    if (qt == CRABML_HIP_Q8_K) CH_TRY(tap.copy(c, f_qp, (const char*)planes + al.off_p, (size_t)n));
+    return 0;
+  };
+  tap.note(CRABML_HIP_PLAN_QIN, qin ? 1 : 0);
   if (seg == 2 * L) {
     const void* act = nepi ? (const void*)c->act_dim : norm_quant((const float*)c->rms_final->ptr, g.rms_norm_eps, tp, c->out_qt);
+    CH_TRY(TAP(!nepi, CRABML_HIP_TAP_CLS_XN, c->xn, (size_t)dim * 4));
+    CH_TRY(TAPQ(true, CRABML_HIP_TAP_CLS_ACT, CRABML_HIP_TAP_CLS_QP, act, c->out_qt, dim));
     return enqueue_classifier_and_sampler(c, act, prof);
   }
   const int l = seg / 2;
+  const bool tl = tap.layer == l;
   if ((seg & 1) == 0) {
     if (l == 0) launch_embed(c);
     if (!nepi || l == 0) norm_quant((const float*)c->rms_att[l]->ptr, g.rms_norm_eps, tp && l > 0, QT);
+    CH_TRY(TAP(tl && (!nepi || l == 0), CRABML_HIP_TAP_QKV_IN_XN, c->xn, (size_t)dim * 4));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_QKV_IN_X, c->x, (size_t)dim * 4));
+    CH_TRY(TAPQ(tl, CRABML_HIP_TAP_QKV_IN_ACT, CRABML_HIP_TAP_QKV_IN_QP, c->act_dim, QT, dim));
+    tap.note(l, CRABML_HIP_PLAN_V_Q6K, c->wv[l]->dtype == CRABML_HIP_Q6_K ? 1 : 0);
     const int total_rows = dim_l + 2 * kv_dim_l;
     CH_TRY(P0(1, total_rows, dim));
     with_qkv_epi(c, decode_qkv_epi(c, l), l, [&](auto ep) {
@@ -1101,8 +1127,10 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
                  planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
     });
     CH_TRY(P1());
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_QBUF, c->qbuf, (size_t)dim_l * 4));
     // Q8_K producers: the (short-context) attention kernel assembles the planes of wo's rhs itself; wo copies them
     const bool aq8 = qout && (g.flags & CRABML_HIP_LLAMA_Q8K_ATTN_PRODUCER) && c->attn_variant == 0 && c->plan.attn_s_rows > 0;
+    tap.note(l, CRABML_HIP_PLAN_AQ8, aq8 ? 1 : 0);
     if constexpr (FMT == CRABML_HIP_Q4_K) {
       if (aq8) {
         const ActLayout ala = act_layout(QT, (size_t)dim_l);
@@ -1116,17 +1144,25 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
       enqueue_attention(c, l, nullptr, nullptr, nullptr, PrefetchPlan{}, 0, prof);
     }
     if (!qin) launch_quantize_act(st, QT, c->attn, (size_t)dim_l, c->act_attn);
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_ATTN, c->attn, (size_t)dim_l * 4));
+    CH_TRY(TAPQ(tl && (aq8 || !qin), CRABML_HIP_TAP_ACT_ATTN, CRABML_HIP_TAP_ACT_ATTN_QP, c->act_attn, QT, dim_l));  // (else: wo's prologue quantizes)
     CH_TRY(gemv_out(c->wo[l], act_k(c->act_attn, dim_l), c->attn, dim_l, 2, (const float*)c->rms_ffn[l]->ptr, 1e-5f, aq8 ? 2 : qin ? 1 : 0,
-                    qout && c->plan.k_norm_in));
+                    wo_x_only));
   } else {
     if (!nepi) norm_quant((const float*)c->rms_ffn[l]->ptr, 1e-5f, tp, QT);  // llama2.rs:611
+    // what gate | up reads: wo left x and its chunk sums only (the NORMIN form below), or planes in global memory
+    CH_TRY(TAP(tl && !nepi, CRABML_HIP_TAP_WO_XN, c->xn, (size_t)dim * 4));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_WO_X, c->x, (size_t)dim * 4));
+    CH_TRY(TAPQ(tl && !wo_x_only, CRABML_HIP_TAP_WO_ACT, CRABML_HIP_TAP_WO_QP, c->act_dim, QT, dim));
+    CH_TRY(TAP(tl && wo_x_only, CRABML_HIP_TAP_WO_RSUMS, c->rsums, (size_t)(dim / 32) * wo_parts * 4));
+    tap.note(l, CRABML_HIP_PLAN_DOWN_Q6K, c->down[l]->dtype == CRABML_HIP_Q6_K ? 1 : 0);
     CH_TRY(P0(3, 2.0 * hidden_l, dim));
     if constexpr (FMT == CRABML_HIP_Q4_K) {
       const ActLayout alh = act_layout(QT, (size_t)hidden_l);
       const Q8KExchange hx{c->h8gran, c->state + 4, c->state + 5, n_segments(c), seg};
       // the form <QOUT, ORD, NORMIN>: h leaves as Q8_K planes too / strict order / wo left x only (above) and this launch normalizes
       // and quantizes the row itself from wo's chunk sums, as many per chunk as wo had workgroups
-      const bool normin = !ordk && qout && c->plan.k_norm_in;
+      const bool normin = wo_x_only;
       char* const hp = qout ? c->act_hid : nullptr;  // (no planes without QOUT; hidden_l % 32 == 0: llama_create_impl)
       const float *nx = nullptr, *nw = nullptr, *nsums = nullptr;
       int sum_parts = 1;
@@ -1134,7 +1170,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         nx = c->x;
         nw = (const float*)c->rms_ffn[l]->ptr;
         nsums = c->rsums;
-        sum_parts = chunk_split(g.flags, dim_l, dim, dev->n_cu, true);
+        sum_parts = wo_parts;
       }
       launch_k(st, R, gateup_k_kernel(qout, ordk, normin), dim3(hidden_l / 32), dim3(1024), ordk ? q8k_ord_lds_bytes(dim, 64) : q8k_lds_bytes(dim),
                planes_of(c->gate[l]), planes_of(c->up[l]), act_k(c->act_dim, dim), c->ffn_act, c->h, hidden_l, dim / 256, hx,
@@ -1146,8 +1182,12 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     }
     CH_TRY(P1());
     if (!qin) launch_quantize_act(st, QT, c->h, (size_t)hidden_l, c->act_hid);
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_GATEUP_H, c->h, (size_t)hidden_l * 4));
+    CH_TRY(TAPQ(tl && (qout || !qin), CRABML_HIP_TAP_ACT_HID, CRABML_HIP_TAP_ACT_HID_QP, c->act_hid, QT, hidden_l));  // (else: ffn_down's prologue quantizes)
     CH_TRY(gemv_out(c->down[l], act_k(c->act_hid, hidden_l), c->h, hidden_l, 4,
                     (const float*)(l + 1 < L ? c->rms_att[l + 1] : c->rms_final)->ptr, g.rms_norm_eps, qout ? 2 : qin ? 1 : 0));
+    CH_TRY(TAP(tl, CRABML_HIP_TAP_DOWN_X, c->x, (size_t)dim * 4));
+    CH_TRY(TAPQ(tl && nepi, CRABML_HIP_TAP_DOWN_ACT, CRABML_HIP_TAP_DOWN_QP, c->act_dim, QT, dim));
   }
   CH_HIP(dev, hipGetLastError());
   return 0;
@@ -2825,8 +2865,10 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   CH_LIVE(dev);
   CH_USE(dev);
   CH_FLUSH(dev);
-  if (c->plan.path != SegPath::Fused5 || c->plan.ordered || c->tp > 1 || c->ext_kv)  // (decide_step: what Fused5 and !ordered imply)
-    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama debug_tap: only the five-launch Q4_0 / Q8_0 / Q4_1 layers of the fast step on one device");
+  // (decide_step: what Fused5 / FusedK and !ordered imply)
+  if ((c->plan.path != SegPath::Fused5 && c->plan.path != SegPath::FusedK) || c->plan.ordered || c->tp > 1 || c->ext_kv)
+    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
+            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 / Q4_K layers, the Q4_K_M mix) on one device with its own KV cache");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim;
   // the row type of every field that leaves as blocks (the others: f32 values, the plan words)
@@ -2835,10 +2877,17 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   fld[CRABML_HIP_TAP_QKV_IN_ACT] = fld[CRABML_HIP_TAP_WO_ACT] = fld[CRABML_HIP_TAP_DOWN_ACT] = fld[CRABML_HIP_TAP_ACT_ATTN] = TapField{qt, dim};
   fld[CRABML_HIP_TAP_ACT_HID] = TapField{qt, hidden};
   if (cq == CRABML_HIP_Q8_0 || cq == CRABML_HIP_Q8_1 || cq == CRABML_HIP_Q8_K) fld[CRABML_HIP_TAP_CLS_ACT] = TapField{cq, dim};
+  for (int f : {CRABML_HIP_TAP_QKV_IN_QP, CRABML_HIP_TAP_ACT_ATTN_QP, CRABML_HIP_TAP_WO_QP, CRABML_HIP_TAP_ACT_HID_QP, CRABML_HIP_TAP_DOWN_QP,
+                CRABML_HIP_TAP_CLS_QP})
+    fld[f] = TapField{CRABML_HIP_Q8_K, 0};  // raw bytes: one per element, class-major inside every 32-group
   const size_t cls_raw = fld[CRABML_HIP_TAP_CLS_ACT].cols ? act_layout(cq, dim).total : dim * 4;
-  // the scratch area, in the device's plane layout: four x, four sets of act_dim planes, three rsums, qbuf, attn, act_attn, act_hid
+  // the scratch area, in the device's plane layout (every term a multiple of 256, the fields' alignment): three x, qbuf, attn and the
+  // three xn of the K-quant path (one to spare); h; the four dim-long plane sets (in front of q|k|v, act_attn, behind wo, behind
+  // ffn_down), act_hid, the classifier's; three rsums of up to two sums per chunk; the class-major planes of those five dim-long sets
+  // and of act_hid
   const size_t adb = act_layout(qt, dim).total, ahb = act_layout(qt, hidden).total;
-  const size_t raw_cap = 6 * align_up(dim * 4, 256) + 4 * adb + 3 * align_up(dim / 32 * 4, 256) + ahb + align_up(cls_raw, 256) + 512;
+  const size_t raw_cap = 9 * align_up(dim * 4, 256) + align_up(hidden * 4, 256) + 4 * adb + 3 * align_up(dim / 16 * 4, 256) + ahb +
+                         align_up(cls_raw, 256) + 5 * align_up(dim, 256) + align_up(hidden, 256) + 512;
   if (need) *need = raw_cap;
   if (!dst) return 0;
   if (dst_bytes < raw_cap) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: dst holds %zu bytes, %zu needed", dst_bytes, raw_cap);
@@ -2853,6 +2902,10 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   tap.note(CRABML_HIP_PLAN_DEFER_NORM, c->plan.defer_norm ? 1 : 0);
   tap.note(CRABML_HIP_PLAN_NORM_EPILOGUE, c->plan.norm_epi ? 1 : 0);
   tap.note(CRABML_HIP_PLAN_ATTN_VARIANT, c->attn_variant + (c->attn_variant >= 1 && c->plan.attn_flash ? 16 : 0));
+  tap.note(CRABML_HIP_PLAN_PATH, (int32_t)c->plan.path);
+  tap.note(CRABML_HIP_PLAN_NORM_EPI_K, c->plan.norm_epi_k ? 1 : 0);
+  tap.note(CRABML_HIP_PLAN_Q8K_PRODUCERS, c->plan.q8k_producers ? 1 : 0);
+  tap.note(CRABML_HIP_PLAN_K_NORM_IN, c->plan.k_norm_in ? 1 : 0);
   const int rc = enqueue_step(c);
   tap.disarm();
   if (rc != 0) return rc;

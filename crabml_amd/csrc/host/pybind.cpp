@@ -550,8 +550,12 @@ PYBIND11_MODULE(_host, m) {
       // one eager step with `layer` tapped (crabml_hip_llama_debug_tap); the dictionary: tap_dict
       .def("debug_tap", [](HipLlamaRunner& r, size_t token, size_t pos, size_t layer) {
         static const char* names[CRABML_HIP_TAP_FIELDS] = {"qkv_in.x", "qkv_in.act_dim", "qkv_in.rsums", "qkv.qbuf", "attn.attn", "attn.act_attn", "wo.x",
-                                                           "wo.act_dim", "wo.rsums", "gateup.act_hid", "down.x", "down.act_dim", "down.rsums", "cls.act", "plan"};
-        static const char* words[CRABML_HIP_TAP_PLAN_WORDS] = {"n_cu", "defer_norm", "norm_epilogue", "attn_variant", "split_wo", "split_down", "qkv_loader", "norm_nit"};
+                                                           "wo.act_dim", "wo.rsums", "gateup.act_hid", "down.x", "down.act_dim", "down.rsums", "cls.act", "plan",
+                                                           "gateup.h", "qkv_in.xn", "wo.xn", "cls.xn", "qkv_in.act_dim.qp", "attn.act_attn.qp",
+                                                           "wo.act_dim.qp", "gateup.act_hid.qp", "down.act_dim.qp", "cls.act.qp"};
+        static const char* words[CRABML_HIP_TAP_PLAN_WORDS] = {"n_cu", "defer_norm", "norm_epilogue", "attn_variant", "split_wo", "split_down", "qkv_loader", "norm_nit",
+                                                               "path", "norm_epi_k", "q8k_producers", "k_norm_in", "qin", "qmode_wo", "qmode_down", "wo_x_only",
+                                                               "aq8", "v_q6k", "down_q6k"};
         HipLlamaRunner::Tap t;
         {
           py::gil_scoped_release rel;

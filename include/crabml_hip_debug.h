@@ -143,13 +143,17 @@ int crabml_hip_llama_debug_kv(crabml_hip_llama_t* ctx, size_t layer, int32_t whi
  * of layer `layer` copied out as each launch of that layer left them: stream-ordered device-to-device copies into a scratch area
  * (allocated on the first tap of a context) placed between the launches, brought to the host after the step.  The step runs to
  * its end as always; logits (vocab_size floats, nullable) come back as from forward.  Serves the five-launch layers of
- * enqueue_segment_t (Q4_0 / Q8_0 / Q4_1 on one device, fast tier); tensor-parallel ranks, the K-quant path, the per-op path, the
- * strict-order device and a context the recorded-op queue drives on the runner's own KV cache return CRABML_HIP_NOT_IMPLEMENTED.
+ * enqueue_segment_t (Q4_0 / Q8_0 / Q4_1) and the K-quant layers of enqueue_segment_k (Q4_K, the Q4_K_M mix, Q4_1 in front of a
+ * classifier of another format) on one device, fast tier; tensor-parallel ranks, the per-op path, the strict-order device and a
+ * context the recorded-op queue drives on the runner's own KV cache return CRABML_HIP_NOT_IMPLEMENTED.
  * dst / dir: field f occupies dir[f].bytes bytes at dst + dir[f].offset (bytes = 0: the context has no such buffer, e.g. rsums
  * outside the hop-free form).  f32 fields are raw floats.  Quantized rows come back in the reference's block byte layout, as
  * crabml_hip_debug_quantize returns them: Q8_0 block i = d plane [i] (f16) | q plane [32 i .. 32 i + 31]; Q8_1 = d plane [i] |
  * third plane [i] (s, f16) | q plane; Q8_K = d plane [i] (f32) | q plane [256 i ..] | bsums plane [16 i ..] -- the Q8_0 layout's
- * third plane (the blocks' integer sums, a kernel-side convenience) is not part of a block and is left out.
+ * third plane (the blocks' integer sums, a kernel-side convenience) is not part of a block and is left out.  The fourth plane of a
+ * Q8_K set (the class-major copy of the quants that the Q4_K kernels read, common.hpp) leaves as a raw field of its own (the _QP
+ * fields: cols bytes).  On the K-quant path a plane field is copied only where a launch wrote the set to global memory (bytes = 0
+ * where the consuming kernel quantizes in its prologue or in LDS).
  * dst == NULL: nothing runs, *need receives the bytes dst must hold. */
 enum {
   CRABML_HIP_TAP_QKV_IN_X = 0,      /* what the q|k|v launch of the layer reads: x (f32, dim), */
@@ -168,8 +172,21 @@ enum {
   CRABML_HIP_TAP_DOWN_RSUMS = 12,   /*   rsums */
   CRABML_HIP_TAP_CLS_ACT = 13,      /* last segment, any `layer`: what the classifier reads (the classifier's row type; f32 for an F32 / F16 classifier) */
   CRABML_HIP_TAP_PLAN = 14,         /* CRABML_HIP_TAP_PLAN_WORDS int32 words: the launch plan of the tapped step as the host took it (below) */
-  CRABML_HIP_TAP_FIELDS = 15
+  /* the K-quant layers (enqueue_segment_k) */
+  CRABML_HIP_TAP_GATEUP_H = 15,     /* after gate|up: h (f32, hidden), which every K form of the launch writes */
+  CRABML_HIP_TAP_QKV_IN_XN = 16,    /* the f32 row of the stand-alone norm launch in front of q|k|v (layer 0; every layer without the norm epilogue), */
+  CRABML_HIP_TAP_WO_XN = 17,        /*   ... in front of gate|up (without the norm epilogue), */
+  CRABML_HIP_TAP_CLS_XN = 18,       /*   ... in front of the classifier (without the norm epilogue) */
+  CRABML_HIP_TAP_QKV_IN_QP = 19,    /* the class-major plane of QKV_IN_ACT, */
+  CRABML_HIP_TAP_ACT_ATTN_QP = 20,  /*   of ACT_ATTN, */
+  CRABML_HIP_TAP_WO_QP = 21,        /*   of WO_ACT, */
+  CRABML_HIP_TAP_ACT_HID_QP = 22,   /*   of ACT_HID, */
+  CRABML_HIP_TAP_DOWN_QP = 23,      /*   of DOWN_ACT, */
+  CRABML_HIP_TAP_CLS_QP = 24,       /*   of CLS_ACT; each 0 bytes where the set is not Q8_K or was not written */
+  CRABML_HIP_TAP_FIELDS = 25
 };
+/* On the K-quant path WO_RSUMS is what the NORMIN gate|up launch reads: wo's chunk sums of squares, PLAN_SPLIT_WO per 32-row chunk
+ * (f32, dim / 32 * split; 0 bytes unless PLAN_WO_X_ONLY), and WO_ACT is 0 bytes there (the planes exist in LDS only). */
 /* the words of CRABML_HIP_TAP_PLAN, written by the enqueue code where it decides (0 where the tapped layer never got there) */
 enum {
   CRABML_HIP_PLAN_N_CU = 0,         /* compute units of the device (what dim / 32 and split_of() are compared with) */
@@ -180,7 +197,18 @@ enum {
   CRABML_HIP_PLAN_SPLIT_DOWN = 5,   /* ... of its ffn_down launch */
   CRABML_HIP_PLAN_QKV_LOADER = 6,   /* the row loader k_qkv takes: 1 rows_dot, 2 rows_partial_2step, 3 rows_partial_rms, 4 rows_partial_rms_128 */
   CRABML_HIP_PLAN_NORM_NIT = 7,     /* template argument of the layer's own norm launch in front of q|k|v (4, or 12 for rows past 4096), 0 = none */
-  CRABML_HIP_TAP_PLAN_WORDS = 8
+  CRABML_HIP_PLAN_PATH = 8,         /* 1 the five launches (enqueue_segment_t), 2 the K-quant launches (enqueue_segment_k); the words below: path 2 */
+  CRABML_HIP_PLAN_NORM_EPI_K = 9,   /* 1: wo / ffn_down of the Q4_K layers normalize and quantize to Q8_K in their epilogue */
+  CRABML_HIP_PLAN_Q8K_PRODUCERS = 10, /* 1: the context lets attention / gate|up emit the Q8_K planes of wo's / ffn_down's rhs */
+  CRABML_HIP_PLAN_K_NORM_IN = 11,   /* 1: the context lets gate|up normalize and quantize wo's f32 row itself */
+  CRABML_HIP_PLAN_QIN = 12,         /* 1: wo / ffn_down take their rhs in the prologue (f32 or finished planes), no quantizer launch */
+  CRABML_HIP_PLAN_QMODE_WO = 13,    /* the layer's wo launch: 0 rhs planes from global memory, 1 the f32 rhs quantized in the prologue, 2 finished planes copied */
+  CRABML_HIP_PLAN_QMODE_DOWN = 14,  /* ... its ffn_down launch */
+  CRABML_HIP_PLAN_WO_X_ONLY = 15,   /* 1: wo left x and its chunk sums only, gate|up ran its NORMIN form */
+  CRABML_HIP_PLAN_AQ8 = 16,         /* 1: the attention launch produced wo's Q8_K planes */
+  CRABML_HIP_PLAN_V_Q6K = 17,       /* 1: the layer's attn_v is Q6_K (a *_K_M mix), */
+  CRABML_HIP_PLAN_DOWN_Q6K = 18,    /*   its ffn_down */
+  CRABML_HIP_TAP_PLAN_WORDS = 19
 };
 typedef struct crabml_hip_tap_entry {
   uint64_t offset, bytes;

@@ -101,7 +101,7 @@ def qkv_reference(tap, model, l, pos, form):
     qkv_reference with NEOX pairs and without a bias"""
     s = model.shape
     hd, dim, kvd = s.head_dim, s.dim, s.kv_dim
-    act = R.parse_act(tap["qkv_in.act_dim"], tap["qtype"]["qkv_in.act_dim"])
+    act = R.tap_act(tap, "qkv_in.act_dim")
     out = {}
     deferred = form.defer and l > 0
     if deferred:
@@ -177,6 +177,8 @@ def check_layer(tap, kc_raw, vc_raw, model, l, pos, form, ctx, token=None):
         out["norm+quantize"] = R.check_planes_in_front(tap, model, l, form, ctx)
     out["q|k|v"] = check_qkv(tap, kc_raw, vc_raw, model, l, pos, form, ctx)
     out["attention"] = R.check_attention(tap, kc_raw, vc_raw, model, l, pos, form, ctx)
+    if "attn.act_attn" not in tap:  # (the five launches always store wo's rhs)
+        out["attention"].fails.append(f"{ctx} attention: the tap holds no act_attn planes")
     out["wo"] = R.check_gemv_out(tap, model, l, "wo", form, ctx)
     out["gate|up"] = check_gateup(tap, model, l, form, ctx)
     out["ffn_down"] = R.check_gemv_out(tap, model, l, "down", form, ctx)

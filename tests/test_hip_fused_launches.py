@@ -9,8 +9,9 @@ equal, bit for bit, those of a twin runner that took the same tokens from the gr
 
 Not pinned here (stated, not hidden): attention without k_attn_flash past 1024 cached positions (f32 cache / head_dim 48): its
 softmax row sum is a block tree there, not the reference's scalar loop, so "bit for bit" does not apply and no f32 bound is
-derived for it yet; the K-quant path, tensor-parallel ranks, the strict device (other kernels; see the module docstrings of
-tests/test_hip_fused.py).  The other half of the fast tier, the prompt pass, is pinned the same way, row by row, in
+derived for it yet; tensor-parallel ranks, the strict device (other kernels; see the module docstrings of
+tests/test_hip_fused.py).  The step's other body, the K-quant launches of enqueue_segment_k, is pinned the same way in
+tests/test_hip_fused_k_launches.py.  The other half of the fast tier, the prompt pass, is pinned the same way, row by row, in
 tests/test_hip_prefill_launches.py (there the long-row kernels past 1024 cached positions are held to the hull of the reference's f16
 chain over every admissible row sum: prefill_pass_ref.long_row_hull)."""
 import numpy as np

@@ -8,8 +8,9 @@ float64 restatement of what it computes FROM THE BYTES IT READ, within bounds de
 K / V caches of every layer equal, bit for bit, those of a twin runner's plain prefill of the same tokens (the tap moves nothing); and
 each case asserts from the launch plan -- written by the enqueue code where it decides -- that the path it is named for was taken.
 
-Not pinned here (stated, not hidden): K-quant (Q8_K row) passes, tensor-parallel ranks and the strict device (bit-exact against the
-oracle: tests/test_hip_prefill.py).  What the cases were seen to leave of their bounds on a device: profiles/prefill_launch_pins.md and
+Not pinned here (stated, not hidden): K-quant (Q8_K row) passes -- the K-quant DECODE step is pinned launch by launch in
+tests/test_hip_fused_k_launches.py, the prompt pass of those formats is not --, tensor-parallel ranks and the strict device (bit-exact
+against the oracle: tests/test_hip_prefill.py).  What the cases were seen to leave of their bounds on a device: profiles/prefill_launch_pins.md and
 tests/golden/prefill_launch_pins_observed.json (evidence only; the gates are the derived bounds)."""
 import numpy as np
 import pytest
