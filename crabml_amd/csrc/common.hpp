@@ -24,6 +24,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));  // two halves of a dword: the operand of the packed f16 instructions
 
 // ---- GGML block geometry (crabml-core/src/cpu/buf/buf_q*.rs) ---------------------------------
 inline size_t block_elems(uint32_t t) {

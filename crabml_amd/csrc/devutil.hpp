@@ -131,6 +131,32 @@ __device__ __forceinline__ int rs_f32_as_i32(float v) {
   return (int)v;
 }
 
+// ---- the rhs quantizer of matmul_vec, per element: every Q8_0 / Q8_1 quantizer site calls these (each keeps its own block maximum and
+// integer sum).  dd = max|x| / 127 (f32, unrounded), v an element of the block.
+// Q81 = false: Q8_0 (buf_q8_0.rs:87-134): q = trunc(x / d), true division, the simd cast's NaN -> 0, then `as i8` of the i32, which wraps.
+// Q81 = true: Q8_1 (buf_q8_1.rs:90-129): q = trunc(clamp(x / d, -128, 127)); Rust f32::max / min return the non-NaN operand, so
+// NaN.max(-128) = -128; |c| <= 128: the truncation is exact.  Returns the quant sign-extended (what the block's integer sum adds).
+template <bool Q81>
+__device__ __forceinline__ int q8_quant(float v, float dd) {
+  if constexpr (Q81)
+    return (int)fminf(fmaxf(v / dd, -128.0f), 127.0f);
+  else
+    return (int)(signed char)(unsigned char)((unsigned)rs_f32_as_i32(v / dd) & 0xffu);
+}
+// the block's aux word from the integer sum of its quants.  Q8_0: the i32 sum itself (exact, derived: Q4_0's -8 offset uses it).  Q8_1: the
+// bits of the f16 s -- the reference accumulates small integers in f32 (exact), then `s *= d` (buf_q8_1.rs:90-129)
+template <bool Q81>
+__device__ __forceinline__ int q8_aux(int sum, float dd) {
+  if constexpr (Q81)
+    return (int)f2h((float)sum * dd);
+  else
+    return sum;
+}
+// four quants -> the dword of their low bytes, first quant lowest
+__device__ __forceinline__ unsigned pack_q8x4(int q0, int q1, int q2, int q3) {
+  return ((unsigned)q0 & 0xffu) | (((unsigned)q1 & 0xffu) << 8) | (((unsigned)q2 & 0xffu) << 16) | (((unsigned)q3 & 0xffu) << 24);
+}
+
 template <bool NT, typename T>
 __device__ __forceinline__ T ld(const T* p) {
   if constexpr (NT)
@@ -181,8 +207,7 @@ __device__ __forceinline__ Q8KLane q8k_wave_quant(const f32x4 v, int lane) {
     qi[i] = t;
     s += t;
   }
-  o.packed = ((unsigned)qi[0] & 0xffu) | (((unsigned)qi[1] & 0xffu) << 8) | (((unsigned)qi[2] & 0xffu) << 16) |
-             (((unsigned)qi[3] & 0xffu) << 24);
+  o.packed = pack_q8x4(qi[0], qi[1], qi[2], qi[3]);
   s += dpp_i<0xB1>(s);
   s += dpp_i<0x4E>(s);
   o.quad_sum = s;

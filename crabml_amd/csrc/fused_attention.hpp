@@ -5,6 +5,59 @@
 #include "fused_common.hpp"
 
 namespace crabml_hip {
+// ---- the arithmetic steps of the f16-cache kernels, one copy each: a kernel below is loads, layout and calls to these ------------------
+// Score step: eight halves of a K row (k8) against eight halves of q (q8), the products added to acc in k order (buf_f16.rs:83-97).
+// One v_fma_mix_f32 per element: acc <- fl32(q[i] * k[i] + acc) with both factors taken as f16 straight from packed
+// registers.  That IS the reference's `acc += q[i] * k[i]` bit for bit: q (rounded to f16, batch_matmul.rs:39) and k carry
+// 11-bit significands, so the f32 product is exact and the fused operation rounds once where the separate multiply would
+// not have rounded at all.  (v_readlane + v_cvt + v_mul + v_add per element made the 128-element dot 3500 cycles of
+// instruction issue -- a lone wave per SIMD issues one instruction per ~5 cycles; the chain of 128 dependent operations is
+// ~1000.)
+__device__ __forceinline__ float score_dot8(float acc, const i32x4& k8, const i32x4& q8) {
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const h16x2 kh = __builtin_bit_cast(h16x2, (unsigned)k8[j]), qh = __builtin_bit_cast(h16x2, (unsigned)q8[j]);
+    acc = __builtin_fmaf((float)qh[0], (float)kh[0], acc);
+    acc = __builtin_fmaf((float)qh[1], (float)kh[1], acc);
+  }
+  return acc;
+}
+// PV chain step of two adjacent columns: c <- fl16(c + fl16(v * p)) per half (v_pk_mul_f16 + v_pk_add_f16 = the half crate's product and
+// sum roundings, buf_f16.rs:152-163; devutil.hpp on why native f16 is exact here).  v2: the two columns' V halves of one position, pp: the
+// position's probability as the pair {p, p}.  Both are SCALAR dwords: a caller that loads vectors extracts the element first (k_attn_tile).
+__device__ __forceinline__ void pv_step(h16x2& c, unsigned v2, unsigned pp) {
+  const h16x2 prod = __builtin_bit_cast(h16x2, v2) * __builtin_bit_cast(h16x2, pp);
+  c = c + prod;
+}
+// eight f16 probabilities (16 bytes of a p16 row) -> their eight {p, p} words, the packed multiplier of pv_step ready-made
+__device__ __forceinline__ void p_pairs8(const i32x4& p8, unsigned (&pp)[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned w = (unsigned)p8[i];
+    const unsigned a = w & 0xffffu, b = w >> 16;
+    pp[2 * i] = a | (a << 16);
+    pp[2 * i + 1] = b | (b << 16);
+  }
+}
+// NB rounds of 8 positions of a chain from LDS rows (vrow: the column pair's V words, prow: the {p, p} words, both by position): all the
+// LDS reads of a round go out before its (serial) packed adds, so the LDS latency is paid once per round.  Advances t while a whole
+// round fits below nt.
+template <int NB>
+__device__ __forceinline__ void pv_rounds(h16x2& c, const unsigned* vrow, const unsigned* prow, int& t, int nt) {
+  for (; t + 8 * NB <= nt; t += 8 * NB) {
+    i32x4 vq[2 * NB], pq[2 * NB];
+#pragma unroll
+    for (int b = 0; b < 2 * NB; b++) {
+      vq[b] = *(const i32x4*)(vrow + t + 4 * b);
+      pq[b] = *(const i32x4*)(prow + t + 4 * b);
+    }
+#pragma unroll
+    for (int b = 0; b < 2 * NB; b++)
+#pragma unroll
+      for (int u = 0; u < 4; u++) pv_step(c, (unsigned)vq[b][u], (unsigned)pq[b][u]);
+  }
+}
+
 // ---- attention: one workgroup per head -------------------------------------------------------------------
 // batch_matmul.rs: f16 cache -> q rounded to f16, f32-accumulated QK^T in k order (buf_f16.rs:83-97),
 // GQA head = h / (n_heads/n_kv); PV accumulated in f16 with a rounding after the product and after the sum
@@ -169,16 +222,13 @@ __global__ __launch_bounds__(256) void k_attn(const float* __restrict__ q, const
   if (xq != nullptr) {
     const bool live = n < hd;  // hd % 32 == 0 here, so 32-lane groups are all-live or all-dead
     const float vq = live ? val : 0.f;
-    const QLane o = q81 ? quant_lane32<true>(vq, live) : quant_lane32<false>(vq, live);
+    const QLane o = quant_lane32(q81, vq, live);
     if (live) {
       int e = head * hd + n;
       xq[e] = o.q;
       if ((n & 31) == 0) {
         xd[e >> 5] = o.d;
-        if (q81)
-          store_qaux<true>(xisum, e >> 5, o.aux);
-        else
-          store_qaux<false>(xisum, e >> 5, o.aux);
+        store_qaux(q81, xisum, e >> 5, o.aux);
       }
     }
   }
@@ -296,13 +346,7 @@ __global__ __launch_bounds__(256) void k_attn_s(const float* __restrict__ q, con
   __syncthreads();
   stamp(1);
   // ---- scores[t] = q . K[t], f32 accumulation in k order (one cached position per thread)
-  // One v_fma_mix_f32 per element: acc <- fl32(q[i] * k[i] + acc) with both factors taken as f16 straight from packed
-  // registers.  That IS the reference's `acc += q[i] * k[i]` bit for bit: q (rounded to f16, batch_matmul.rs:39) and k carry
-  // 11-bit significands, so the f32 product is exact and the fused operation rounds once where the separate multiply would
-  // not have rounded at all.  (v_readlane + v_cvt + v_mul + v_add per element made the 128-element dot 3500 cycles of
-  // instruction issue -- a lone wave per SIMD issues one instruction per ~5 cycles; the chain of 128 dependent operations is
-  // ~1000.)  q comes out of LDS as broadcast 16-byte reads issued together with the K row's.
-  typedef _Float16 h2q __attribute__((ext_vector_type(2)));
+  // (score_dot8: one v_fma_mix_f32 per element.)  q comes out of LDS as broadcast 16-byte reads issued together with the K row's.
   auto score_of = [&](int t) -> float {
     const unsigned short* kr = Ks + (size_t)t * kstr;
     float acc = 0.0f;
@@ -314,24 +358,9 @@ __global__ __launch_bounds__(256) void k_attn_s(const float* __restrict__ q, con
         qq[i] = *(const i32x4*)(q16 + 8 * i);
       }
 #pragma unroll
-      for (int i = 0; i < 16; i++) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const h2q kh = __builtin_bit_cast(h2q, (unsigned)kv[i][j]), qh = __builtin_bit_cast(h2q, (unsigned)qq[i][j]);
-          acc = __builtin_fmaf((float)qh[0], (float)kh[0], acc);
-          acc = __builtin_fmaf((float)qh[1], (float)kh[1], acc);
-        }
-      }
+      for (int i = 0; i < 16; i++) acc = score_dot8(acc, kv[i], qq[i]);
     } else {
-      for (int i = 0; i < hd; i += 8) {
-        const i32x4 kv = *(const i32x4*)(kr + i), qq = *(const i32x4*)(q16 + i);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-          const h2q kh = __builtin_bit_cast(h2q, (unsigned)kv[j]), qh = __builtin_bit_cast(h2q, (unsigned)qq[j]);
-          acc = __builtin_fmaf((float)qh[0], (float)kh[0], acc);
-          acc = __builtin_fmaf((float)qh[1], (float)kh[1], acc);
-        }
-      }
+      for (int i = 0; i < hd; i += 8) acc = score_dot8(acc, *(const i32x4*)(kr + i), *(const i32x4*)(q16 + i));
     }
     return acc;
   };
@@ -358,15 +387,17 @@ __global__ __launch_bounds__(256) void k_attn_s(const float* __restrict__ q, con
   }
   stamp(3);
   // ---- out[n] = sum_t p[t] * V[t][n]: f16 product and f16 sum per position, in position order (buf_f16.rs:152-163).
-  // A lane carries the chains of TWO adjacent output columns on packed f16 math (v_pk_mul_f16 + v_pk_add_f16 = the half
-  // crate's product / sum roundings, one instruction pair per position for both columns): hd / 2 lanes, one LDS dword of V
-  // and one broadcast probability per position.
-  typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+  // A lane carries the chains of TWO adjacent output columns on packed f16 math (pv_step: one instruction pair per position for
+  // both columns): hd / 2 lanes, one LDS dword of V and one broadcast probability per position.
   const int npair = hd >> 1;
   float v0 = 0.0f, v1 = 0.0f;
   if (tid < npair) {
     const unsigned* vr = (const unsigned*)Vs + tid;  // row stride hd / 2 dwords
-    h2v c = {(_Float16)0.0f, (_Float16)0.0f};
+    const auto pair_of = [](float p) {  // scores hold f16-representable values
+      const _Float16 ph = (_Float16)p;
+      return __builtin_bit_cast(unsigned, h16x2{ph, ph});
+    };
+    h16x2 c = {(_Float16)0.0f, (_Float16)0.0f};
     int t = 0;
     for (; t + 8 <= seq; t += 8) {
       unsigned vv[8];
@@ -377,19 +408,9 @@ __global__ __launch_bounds__(256) void k_attn_s(const float* __restrict__ q, con
         pp[u] = scores[t + u];
       }
 #pragma unroll
-      for (int u = 0; u < 8; u++) {
-        const _Float16 ph = (_Float16)pp[u];  // scores hold f16-representable values
-        const h2v p2 = {ph, ph};
-        const h2v prod = __builtin_bit_cast(h2v, vv[u]) * p2;
-        c = c + prod;
-      }
+      for (int u = 0; u < 8; u++) pv_step(c, vv[u], pair_of(pp[u]));
     }
-    for (; t < seq; t++) {
-      const _Float16 ph = (_Float16)scores[t];
-      const h2v p2 = {ph, ph};
-      const h2v prod = __builtin_bit_cast(h2v, vr[(size_t)t * npair]) * p2;
-      c = c + prod;
-    }
+    for (; t < seq; t++) pv_step(c, vr[(size_t)t * npair], pair_of(scores[t]));
     v0 = (float)c[0];
     v1 = (float)c[1];
     *(f32x2*)(out + head * hd + 2 * tid) = f32x2{v0, v1};
@@ -405,31 +426,16 @@ __global__ __launch_bounds__(256) void k_attn_s(const float* __restrict__ q, con
     __syncthreads();
     if (wave == 0) q8k_exchange_store(k8.ex, qs, head * hd, hd, lane, xq, k8.d, k8.bs, k8.qp);
   } else if (xq != nullptr && wave * 64 < npair) {
-  // ---- quantize the head's output for wo: a 32-element block = the 16 lanes of one DPP row (two columns each)  // whole waves (hd % 32 == 0 here: rows of 16 lanes are all-live or all-dead)
+    // ---- quantize the head's output for wo: a 32-element block = the 16 lanes of one DPP row (two columns each: quant_pair16), by
+    // whole waves (hd % 32 == 0 here: rows of 16 lanes are all-live or all-dead)
     const bool live = tid < npair;
-    const float a0 = live ? v0 : 0.f, a1 = live ? v1 : 0.f;
-    const float amax = row16_max_f32(fmaxf(fabsf(a0), fabsf(a1)));
-    const float dd = amax / 127.0f;
-    int q0, q1, aux;
-    if (!q81) {  // buf_q8_0.rs:87-134: q = trunc(x / d) (`as i8` of the i32 wraps), aux = the block's quant sum
-      q0 = (int)(signed char)(unsigned char)((unsigned)rs_f32_as_i32(a0 / dd) & 0xffu);
-      q1 = (int)(signed char)(unsigned char)((unsigned)rs_f32_as_i32(a1 / dd) & 0xffu);
-      aux = row16_sum_i32(live ? q0 + q1 : 0);
-    } else {  // buf_q8_1.rs:90-129: clamp, NaN -> -128, s = f16(d * sum q)
-      q0 = (int)fminf(fmaxf(a0 / dd, -128.0f), 127.0f);
-      q1 = (int)fminf(fmaxf(a1 / dd, -128.0f), 127.0f);
-      const int sum = row16_sum_i32(live ? q0 + q1 : 0);
-      aux = (int)f2h((float)sum * dd);
-    }
+    const QPair o = quant_pair16(q81, live ? v0 : 0.f, live ? v1 : 0.f, live);
     if (live) {
       const int e = head * hd + 2 * tid;
-      *(unsigned short*)(xq + e) = (unsigned short)(((unsigned)q0 & 0xffu) | (((unsigned)q1 & 0xffu) << 8));
+      *(unsigned short*)(xq + e) = (unsigned short)(((unsigned)o.q0 & 0xffu) | (((unsigned)o.q1 & 0xffu) << 8));
       if ((tid & 15) == 0) {
-        xd[e >> 5] = f2h(dd);
-        if (q81)
-          store_qaux<true>(xisum, e >> 5, aux);
-        else
-          store_qaux<false>(xisum, e >> 5, aux);
+        xd[e >> 5] = o.d;
+        store_qaux(q81, xisum, e >> 5, o.aux);
       }
     }
   }
@@ -466,7 +472,7 @@ __global__ __launch_bounds__(256) void k_attn_scores(const float* __restrict__ q
   scores_g += (size_t)blockIdx.y * n_kv * G * seq_cap;
   if (sp * TS >= seq) return;
   // q staged as f16 (quantize_f32_f16(bufa), batch_matmul.rs:39): the dot is one v_fma_mix_f32 per element -- the f32
-  // product of two f16 values is exact, so fl32(q k + acc) is the reference's `acc += q * k` bit for bit (k_attn_s)
+  // product of two f16 values is exact, so fl32(q k + acc) is the reference's `acc += q * k` bit for bit (score_dot8)
   unsigned short* q16 = (unsigned short*)lds;
   const int g = tid % G;
   const int t = sp * TS + tid / G;
@@ -484,7 +490,6 @@ __global__ __launch_bounds__(256) void k_attn_scores(const float* __restrict__ q
   __syncthreads();
   if (t >= seq) return;
   const unsigned short* qg = q16 + g * hd;
-  typedef _Float16 h2q __attribute__((ext_vector_type(2)));
   float acc = 0.0f;
   int i = 0;
   for (; i + 64 <= hd; i += 64) {  // 8 x 16-byte loads in flight; products still added in k order
@@ -495,23 +500,9 @@ __global__ __launch_bounds__(256) void k_attn_scores(const float* __restrict__ q
       qq[u] = *(const i32x4*)(qg + i + 8 * u);
     }
 #pragma unroll
-    for (int u = 0; u < 8; u++)
-#pragma unroll
-      for (int w4 = 0; w4 < 4; w4++) {
-        const h2q kh = __builtin_bit_cast(h2q, (unsigned)kv[u][w4]), qh = __builtin_bit_cast(h2q, (unsigned)qq[u][w4]);
-        acc = __builtin_fmaf((float)qh[0], (float)kh[0], acc);
-        acc = __builtin_fmaf((float)qh[1], (float)kh[1], acc);
-      }
+    for (int u = 0; u < 8; u++) acc = score_dot8(acc, kv[u], qq[u]);
   }
-  for (; i + 8 <= hd; i += 8) {
-    const i32x4 kv = *(const i32x4*)(kr + i), qq = *(const i32x4*)(qg + i);
-#pragma unroll
-    for (int w4 = 0; w4 < 4; w4++) {
-      const h2q kh = __builtin_bit_cast(h2q, (unsigned)kv[w4]), qh = __builtin_bit_cast(h2q, (unsigned)qq[w4]);
-      acc = __builtin_fmaf((float)qh[0], (float)kh[0], acc);
-      acc = __builtin_fmaf((float)qh[1], (float)kh[1], acc);
-    }
-  }
+  for (; i + 8 <= hd; i += 8) acc = score_dot8(acc, *(const i32x4*)(kr + i), *(const i32x4*)(qg + i));
   for (; i < hd; i++) acc = __builtin_fmaf(h2f(qg[i]), h2f(kr[i]), acc);
   scores_g[(size_t)(j * G + g) * seq_cap + t] = acc;
 }
@@ -532,33 +523,41 @@ __global__ __launch_bounds__(NW * 64) void k_attn_softmax(const float* __restric
   for (int t = threadIdx.x; t < seq; t += NW * 64) p16[(size_t)head * seq_cap + t] = f2h(lds[t]);  // exact: already f16 values
 }
 
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 #define ATTN_PV_TILE 256
 #define ATTN_PV_ROW (ATTN_PV_TILE + 4)  // words per LDS row: 16-byte aligned rows, shifted by 4 banks from each other
-template <int G>
-__global__ __launch_bounds__(256) void k_attn_pv(const unsigned short* __restrict__ p16, const unsigned short* __restrict__ vc,
-                                                 const int* __restrict__ pos_d, float* __restrict__ out,
-                                                 signed char* __restrict__ xq, unsigned short* __restrict__ xd,
-                                                 void* __restrict__ xisum, int hd, int seq_cap, int q81, int row0) {
+// The body of k_attn_pv (R = 1: one row per workgroup, grid.y = row of a prefill batch or 0 for the decode step, and the rhs blocks of
+// wo where xq is given) and of k_attn_pv_rows (R consecutive prompt rows per workgroup, batched prefill past 1024 positions): row r of
+// the tile sees seq0 + r cached positions.  The V tile is fetched and transposed ONCE for the R rows x G heads -- every lane of the
+// workgroup carries a chain (R * G * 16 = 256 for Llama-3's G = 4, R = 4) instead of 64 of 256, and V is read R times less
+// often (a 4096-token prompt re-read V once per row: 340 of 582 ms).  Per (row, head, column) the arithmetic and its order do not
+// depend on R: bit-identical (test_long_prompt_attention_paths_are_bit_identical).
+template <int G, int R>
+__device__ __forceinline__ void pv_pass(const unsigned short* __restrict__ p16, const unsigned short* __restrict__ vc,
+                                        const int* __restrict__ pos_d, float* __restrict__ out, signed char* __restrict__ xq,
+                                        unsigned short* __restrict__ xd, void* __restrict__ xisum, int hd, int seq_cap, int q81,
+                                        int row0, int nrows) {
+  static_assert(R * G * 16 <= 256, "one chain per lane");
   constexpr int T = ATTN_PV_TILE, ROW = ATTN_PV_ROW;
   // LDS, two buffers each: V tile transposed to [16 dim pairs][T] words (a chain lane reads 4 consecutive positions
-  // of its dim pair with one ds_read_b128), P tile [G][T] words holding {p, p} (the packed multiplier, ready-made)
+  // of its dim pair with one ds_read_b128), P tile [R * G][T] words holding {p, p} (the packed multiplier, ready-made)
   __shared__ __attribute__((aligned(16))) unsigned vt[2][16 * ROW];
-  __shared__ __attribute__((aligned(16))) unsigned pt[2][G * ROW];
+  __shared__ __attribute__((aligned(16))) unsigned pt[2][R * G * ROW];
   const int tid = threadIdx.x;
   const int nslice = hd / 32;
   const int j = blockIdx.x / nslice, sl = blockIdx.x % nslice;
-  const int seq = *pos_d + 1 + row0 + (int)blockIdx.y;
-  {  // blockIdx.y: row of a prefill batch (xq is null there)
-    const size_t n_heads = (size_t)(gridDim.x / nslice) * G;
-    p16 += (size_t)blockIdx.y * n_heads * seq_cap;
-    out += (size_t)(row0 + blockIdx.y) * n_heads * hd;
-  }
+  const int rt0 = (int)blockIdx.y * R;                                          // first row of this tile within the launch
+  const int rows_here = R == 1 ? 1 : (nrows - rt0 < R ? nrows - rt0 : R);       // >= 1
+  const int seq0 = *pos_d + 1 + row0 + rt0;                                     // cached positions of the tile's first row
+  const int seq_max = seq0 + rows_here - 1;
+  const size_t n_heads = (size_t)(gridDim.x / nslice) * G;
+  p16 += (size_t)rt0 * n_heads * seq_cap;
+  out += (size_t)(row0 + rt0) * n_heads * hd;
   const unsigned short* vbase = vc + (size_t)j * seq_cap * hd + sl * 32;
-  const int ntiles = (seq + T - 1) / T;
+  const int ntiles = (seq_max + T - 1) / T;
   // loader role (all threads): V piece = 16 B (4 dim pairs) of row (tid / 4) + 64 r, piece tid % 4;
-  // P piece = 16 B = 8 positions of one head
-  i32x4 vreg[4], preg;
+  // P piece = 16 B = 8 positions of one (row, head)
+  constexpr int PP = (R * G * (T / 8) + 255) / 256;  // probability pieces per thread
+  i32x4 vreg[4], preg[PP];
   auto issue = [&](int tile) {
     const int t0 = tile * T;
 #pragma unroll
@@ -567,11 +566,16 @@ __global__ __launch_bounds__(256) void k_attn_pv(const unsigned short* __restric
       t = t < seq_cap ? t : seq_cap - 1;  // rows past seq are read (inside the cache allocation) but never used
       vreg[r] = *(const i32x4*)(vbase + (size_t)t * hd + (tid & 3) * 8);
     }
-    if (tid < G * (T / 8)) {
-      const int g = tid / (T / 8), c8 = tid % (T / 8);
-      int t = t0 + c8 * 8;
-      t = t + 8 <= seq_cap ? t : seq_cap - 8;  // only past the end of the cache: those positions are never consumed
-      preg = *(const i32x4*)(p16 + (size_t)(j * G + g) * seq_cap + t);
+#pragma unroll
+    for (int u = 0; u < PP; u++) {
+      const int pc = tid + 256 * u;
+      if (pc < R * G * (T / 8)) {
+        const int rg = pc / (T / 8), c8 = pc % (T / 8), r = R == 1 ? 0 : rg / G, g = R == 1 ? rg : rg % G;
+        const int rr = r < rows_here ? r : rows_here - 1;  // rows past the batch: re-read the last row (never consumed)
+        int t = t0 + c8 * 8;
+        t = t + 8 <= seq_cap ? t : seq_cap - 8;  // only past the end of the cache: those positions are never consumed
+        preg[u] = *(const i32x4*)(p16 + ((size_t)rr * n_heads + (j * G + g)) * seq_cap + t);
+      }
     }
   };
   auto commit = [&](int buf) {
@@ -581,23 +585,22 @@ __global__ __launch_bounds__(256) void k_attn_pv(const unsigned short* __restric
 #pragma unroll
       for (int i = 0; i < 4; i++) vt[buf][((tid & 3) * 4 + i) * ROW + tl] = (unsigned)vreg[r][i];
     }
-    if (tid < G * (T / 8)) {
-      const int g = tid / (T / 8), c8 = tid % (T / 8);
-      unsigned pp[8];
 #pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const unsigned w = (unsigned)preg[i];
-        const unsigned a = w & 0xffffu, b = w >> 16;
-        pp[2 * i] = a | (a << 16);
-        pp[2 * i + 1] = b | (b << 16);
+    for (int u = 0; u < PP; u++) {
+      const int pc = tid + 256 * u;
+      if (pc < R * G * (T / 8)) {
+        const int rg = pc / (T / 8), c8 = pc % (T / 8);
+        unsigned pp[8];
+        p_pairs8(preg[u], pp);
+        *(i32x4*)(&pt[buf][rg * ROW + c8 * 8]) = i32x4{(int)pp[0], (int)pp[1], (int)pp[2], (int)pp[3]};
+        *(i32x4*)(&pt[buf][rg * ROW + c8 * 8 + 4]) = i32x4{(int)pp[4], (int)pp[5], (int)pp[6], (int)pp[7]};
       }
-      *(i32x4*)(&pt[buf][g * ROW + c8 * 8]) = i32x4{(int)pp[0], (int)pp[1], (int)pp[2], (int)pp[3]};
-      *(i32x4*)(&pt[buf][g * ROW + c8 * 8 + 4]) = i32x4{(int)pp[4], (int)pp[5], (int)pp[6], (int)pp[7]};
     }
   };
-  // chain role: lane c < G * 16 owns dims 2 dp, 2 dp + 1 of head j * G + g
-  const bool chain = tid < G * 16;
-  const int g = tid >> 4, dp = tid & 15;
+  // chain role: lane = (row r, head g, dim pair dp) owns dims 2 dp, 2 dp + 1 of head j * G + g
+  const int rg = tid >> 4, dp = tid & 15, r = R == 1 ? 0 : rg / G, g = R == 1 ? rg : rg % G;
+  const bool chain = tid < R * G * 16 && r < rows_here;
+  const int seq = seq0 + r;
   h16x2 c2 = {(_Float16)0.0f, (_Float16)0.0f};
   issue(0);
   commit(0);
@@ -605,32 +608,14 @@ __global__ __launch_bounds__(256) void k_attn_pv(const unsigned short* __restric
   for (int tile = 0; tile < ntiles; tile++) {
     const int buf = tile & 1;
     if (tile + 1 < ntiles) issue(tile + 1);
-    if (chain) {
+    if (chain && tile * T < seq) {
       const int nt = seq - tile * T < T ? seq - tile * T : T;
       const unsigned* vrow = &vt[buf][dp * ROW];
-      const unsigned* prow = &pt[buf][g * ROW];
+      const unsigned* prow = &pt[buf][rg * ROW];
       int t = 0;
-      // NB rounds of 8 positions: all the LDS reads of a round go out before its (serial) packed adds, so the LDS
-      // latency is paid once per round
-#define PV_ROUND(NB)                                                                                         \
-  for (; t + 8 * NB <= nt; t += 8 * NB) {                                                                    \
-    i32x4 vq[2 * NB], pq[2 * NB];                                                                            \
-    _Pragma("unroll") for (int b = 0; b < 2 * NB; b++) {                                                     \
-      vq[b] = *(const i32x4*)(vrow + t + 4 * b);                                                             \
-      pq[b] = *(const i32x4*)(prow + t + 4 * b);                                                             \
-    }                                                                                                        \
-    _Pragma("unroll") for (int b = 0; b < 2 * NB; b++) _Pragma("unroll") for (int u = 0; u < 4; u++) {       \
-      const h16x2 pr = __builtin_bit_cast(h16x2, (unsigned)vq[b][u]) * __builtin_bit_cast(h16x2, (unsigned)pq[b][u]); \
-      c2 = c2 + pr;                                                                                          \
-    }                                                                                                        \
-  }
-      PV_ROUND(4)
-      PV_ROUND(1)
-#undef PV_ROUND
-      for (; t < nt; t++) {
-        const h16x2 pr = __builtin_bit_cast(h16x2, vrow[t]) * __builtin_bit_cast(h16x2, prow[t]);
-        c2 = c2 + pr;
-      }
+      pv_rounds<4>(c2, vrow, prow, t, nt);
+      pv_rounds<1>(c2, vrow, prow, t, nt);
+      for (; t < nt; t++) pv_step(c2, vrow[t], prow[t]);
     }
     if (tile + 1 < ntiles) commit(buf ^ 1);  // the other buffer was last read one iteration ago (barrier below)
     __syncthreads();
@@ -639,32 +624,34 @@ __global__ __launch_bounds__(256) void k_attn_pv(const unsigned short* __restric
   const float v0 = (float)c2[0], v1 = (float)c2[1];
   const int head = j * G + g;
   const int e0 = head * hd + sl * 32 + 2 * dp;
-  out[e0] = v0;
-  out[e0 + 1] = v1;
-  if (xq != nullptr) {  // the rhs block of the 32 dims held by this 16-lane DPP row (quant_lane32's arithmetic)
-    const float amax = row16_max_f32(fmaxf(fabsf(v0), fabsf(v1)));
-    const float dd = amax / 127.0f;
-    int q0, q1;
-    if (q81) {  // Q8_1 (buf_q8_1.rs:90-129)
-      q0 = (int)fminf(fmaxf(v0 / dd, -128.0f), 127.0f);
-      q1 = (int)fminf(fmaxf(v1 / dd, -128.0f), 127.0f);
-    } else {  // Q8_0 (buf_q8_0.rs:87-134)
-      q0 = (int)(signed char)(unsigned char)((unsigned)rs_f32_as_i32(v0 / dd) & 0xffu);
-      q1 = (int)(signed char)(unsigned char)((unsigned)rs_f32_as_i32(v1 / dd) & 0xffu);
-    }
-    const int qs = row16_sum_i32(q0 + q1);
-    xq[e0] = (signed char)q0;
-    xq[e0 + 1] = (signed char)q1;
-    if (dp == 0) {
-      xd[e0 >> 5] = f2h(dd);
-      if (q81)
-        store_qaux<true>(xisum, e0 >> 5, (int)f2h((float)qs * dd));
-      else
-        store_qaux<false>(xisum, e0 >> 5, qs);
+  float* o = out + (size_t)r * n_heads * hd;
+  o[e0] = v0;
+  o[e0 + 1] = v1;
+  if constexpr (R == 1) {
+    if (xq != nullptr) {  // the rhs block of the 32 dims held by this 16-lane DPP row (xq is null for a prefill batch)
+      const QPair q = quant_pair16(q81, v0, v1, true);
+      xq[e0] = (signed char)q.q0;
+      xq[e0 + 1] = (signed char)q.q1;
+      if (dp == 0) {
+        xd[e0 >> 5] = q.d;
+        store_qaux(q81, xisum, e0 >> 5, q.aux);
+      }
     }
   }
 }
-
+template <int G>
+__global__ __launch_bounds__(256) void k_attn_pv(const unsigned short* __restrict__ p16, const unsigned short* __restrict__ vc,
+                                                 const int* __restrict__ pos_d, float* __restrict__ out,
+                                                 signed char* __restrict__ xq, unsigned short* __restrict__ xd,
+                                                 void* __restrict__ xisum, int hd, int seq_cap, int q81, int row0) {
+  pv_pass<G, 1>(p16, vc, pos_d, out, xq, xd, xisum, hd, seq_cap, q81, row0, 1);
+}
+template <int G, int R>
+__global__ __launch_bounds__(256) void k_attn_pv_rows(const unsigned short* __restrict__ p16, const unsigned short* __restrict__ vc,
+                                                      const int* __restrict__ pos_d, float* __restrict__ out, int hd, int seq_cap,
+                                                      int row0, int nrows) {
+  pv_pass<G, R>(p16, vc, pos_d, out, nullptr, nullptr, nullptr, hd, seq_cap, 0, row0, nrows);
+}
 
 // ---- the PV pass with the products made by other waves ------------------------------------------------------------------
 // A column's value is ONE f16 chain over the cached positions: c <- fl16(c + fl16(p_t * v_t)) (the half crate's product and
@@ -832,15 +819,12 @@ __global__ __launch_bounds__(320) void k_attn_pv_split(const unsigned short* __r
   const int head = j * G + hsub * HG + (tid >> 5);
   const int e = head * hd + sl * 32 + (tid & 31);
   out[e] = v;
-  if (xq != nullptr) {  // the rhs block of the 32 columns held by this half-wave (k_attn_pv's epilogue: quant_lane32's arithmetic)
-    const QLane o = q81 ? quant_lane32<true>(v, true) : quant_lane32<false>(v, true);
+  if (xq != nullptr) {  // the rhs block of the 32 columns held by this half-wave
+    const QLane o = quant_lane32(q81, v, true);
     xq[e] = o.q;
     if ((tid & 31) == 0) {
       xd[e >> 5] = o.d;
-      if (q81)
-        store_qaux<true>(xisum, e >> 5, o.aux);
-      else
-        store_qaux<false>(xisum, e >> 5, o.aux);
+      store_qaux(q81, xisum, e >> 5, o.aux);
     }
   }
 }
@@ -896,7 +880,6 @@ __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const floa
                                                                      int Smax, int min_rows) {
   constexpr int NW = FlashGeom<G>::NW, LPR = HD / 8, RPI = 64 / LPR, NCLS = NW * RPI, U = 4, NT = NW * 64;
   static_assert(HD == 64 || HD == 128 || HD == 256, "a K / V row is 8, 16 or 32 lanes x 16 bytes");
-  typedef _Float16 h2 __attribute__((ext_vector_type(2)));
   extern __shared__ __attribute__((aligned(16))) float fl_lds[];
   float* sacc = fl_lds;                 // [NCLS][G][HD]
   float* sm = sacc + NCLS * G * HD;     // [NCLS][G]
@@ -958,7 +941,7 @@ __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const floa
       float vf[8];
 #pragma unroll
       for (int i = 0; i < 4; i++) {
-        const h2 t = __builtin_bit_cast(h2, (unsigned)vv[u][i]);
+        const h16x2 t = __builtin_bit_cast(h16x2, (unsigned)vv[u][i]);
         vf[2 * i] = (float)t[0];
         vf[2 * i + 1] = (float)t[1];
       }
@@ -967,7 +950,7 @@ __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const floa
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; i++)
-          s = __builtin_amdgcn_fdot2(__builtin_bit_cast(h2, (unsigned)kk[u][i]), __builtin_bit_cast(h2, (unsigned)qh[g][i]), s, false);
+          s = __builtin_amdgcn_fdot2(__builtin_bit_cast(h16x2, (unsigned)kk[u][i]), __builtin_bit_cast(h16x2, (unsigned)qh[g][i]), s, false);
         s = flash_row_sum<HD>(s);
         s = live ? s : -INFINITY;
         const float mn = fmaxf(m[g], s);
@@ -1090,7 +1073,7 @@ __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const floa
     const float val = o / L;
     const int e = (j * G + g) * HD + d;
     out[e] = val;
-    if (xq != nullptr) {  // the rhs block of wo: 32 consecutive dims = one half-wave (quant_lane32's arithmetic)
+    if (xq != nullptr) {  // the rhs block of wo: 32 consecutive dims = one half-wave (quant_lane32)
       const QLane ql = quant_lane32<Q81>(val, true);
       xq[e] = ql.q;
       if ((lane & 31) == 0) {
@@ -1329,125 +1312,6 @@ __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict
   }
 }
 
-// The same PV pass for R consecutive prompt rows per workgroup (batched prefill past 1024 positions): row r of the tile
-// sees seq0 + r cached positions.  The V tile is fetched and transposed ONCE for the R rows x G heads -- every lane of the
-// workgroup carries a chain (R * G * 16 = 256 for Llama-3's G = 4, R = 4) instead of 64 of 256, and V is read R times less
-// often (a 4096-token prompt re-read V once per row: 340 of 582 ms).  Per (row, head, column) the arithmetic and its order
-// are k_attn_pv's: bit-identical (test_long_prompt_attention_paths_are_bit_identical).
-template <int G, int R>
-__global__ __launch_bounds__(256) void k_attn_pv_rows(const unsigned short* __restrict__ p16, const unsigned short* __restrict__ vc,
-                                                      const int* __restrict__ pos_d, float* __restrict__ out, int hd, int seq_cap,
-                                                      int row0, int nrows) {
-  static_assert(R * G * 16 <= 256, "one chain per lane");
-  constexpr int T = ATTN_PV_TILE, ROW = ATTN_PV_ROW;
-  __shared__ __attribute__((aligned(16))) unsigned vt[2][16 * ROW];
-  __shared__ __attribute__((aligned(16))) unsigned pt[2][R * G * ROW];
-  const int tid = threadIdx.x;
-  const int nslice = hd / 32;
-  const int j = blockIdx.x / nslice, sl = blockIdx.x % nslice;
-  const int rt0 = (int)blockIdx.y * R;                       // first row of this tile within the launch
-  const int rows_here = nrows - rt0 < R ? nrows - rt0 : R;   // >= 1
-  const int seq0 = *pos_d + 1 + row0 + rt0;                  // cached positions of the tile's first row
-  const int seq_max = seq0 + rows_here - 1;
-  const size_t n_heads = (size_t)(gridDim.x / nslice) * G;
-  p16 += (size_t)rt0 * n_heads * seq_cap;
-  out += (size_t)(row0 + rt0) * n_heads * hd;
-  const unsigned short* vbase = vc + (size_t)j * seq_cap * hd + sl * 32;
-  const int ntiles = (seq_max + T - 1) / T;
-  constexpr int PP = (R * G * (T / 8) + 255) / 256;  // probability pieces (8 positions of one (row, head)) per thread
-  i32x4 vreg[4], preg[PP];
-  auto issue = [&](int tile) {
-    const int t0 = tile * T;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      int t = t0 + (tid >> 2) + 64 * r;
-      t = t < seq_cap ? t : seq_cap - 1;
-      vreg[r] = *(const i32x4*)(vbase + (size_t)t * hd + (tid & 3) * 8);
-    }
-#pragma unroll
-    for (int u = 0; u < PP; u++) {
-      const int pc = tid + 256 * u;
-      if (pc < R * G * (T / 8)) {
-        const int rg = pc / (T / 8), c8 = pc % (T / 8), r = rg / G, g = rg % G;
-        const int rr = r < rows_here ? r : rows_here - 1;  // rows past the batch: re-read the last row (never consumed)
-        int t = t0 + c8 * 8;
-        t = t + 8 <= seq_cap ? t : seq_cap - 8;
-        preg[u] = *(const i32x4*)(p16 + ((size_t)rr * n_heads + (j * G + g)) * seq_cap + t);
-      }
-    }
-  };
-  auto commit = [&](int buf) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int tl = (tid >> 2) + 64 * r;
-#pragma unroll
-      for (int i = 0; i < 4; i++) vt[buf][((tid & 3) * 4 + i) * ROW + tl] = (unsigned)vreg[r][i];
-    }
-#pragma unroll
-    for (int u = 0; u < PP; u++) {
-      const int pc = tid + 256 * u;
-      if (pc < R * G * (T / 8)) {
-        const int rg = pc / (T / 8), c8 = pc % (T / 8);
-        unsigned pp[8];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const unsigned w = (unsigned)preg[u][i];
-          const unsigned a = w & 0xffffu, b = w >> 16;
-          pp[2 * i] = a | (a << 16);
-          pp[2 * i + 1] = b | (b << 16);
-        }
-        *(i32x4*)(&pt[buf][rg * ROW + c8 * 8]) = i32x4{(int)pp[0], (int)pp[1], (int)pp[2], (int)pp[3]};
-        *(i32x4*)(&pt[buf][rg * ROW + c8 * 8 + 4]) = i32x4{(int)pp[4], (int)pp[5], (int)pp[6], (int)pp[7]};
-      }
-    }
-  };
-  // chain role: lane = (row r, head g, dim pair dp)
-  const int rg = tid >> 4, dp = tid & 15, r = rg / G, g = rg % G;
-  const bool chain = tid < R * G * 16 && r < rows_here;
-  const int seq = seq0 + r;
-  h16x2 c2 = {(_Float16)0.0f, (_Float16)0.0f};
-  issue(0);
-  commit(0);
-  __syncthreads();
-  for (int tile = 0; tile < ntiles; tile++) {
-    const int buf = tile & 1;
-    if (tile + 1 < ntiles) issue(tile + 1);
-    if (chain && tile * T < seq) {
-      const int nt = seq - tile * T < T ? seq - tile * T : T;
-      const unsigned* vrow = &vt[buf][dp * ROW];
-      const unsigned* prow = &pt[buf][rg * ROW];
-      int t = 0;
-#define PV_ROUND(NB)                                                                                         \
-  for (; t + 8 * NB <= nt; t += 8 * NB) {                                                                    \
-    i32x4 vq[2 * NB], pq[2 * NB];                                                                            \
-    _Pragma("unroll") for (int b = 0; b < 2 * NB; b++) {                                                     \
-      vq[b] = *(const i32x4*)(vrow + t + 4 * b);                                                             \
-      pq[b] = *(const i32x4*)(prow + t + 4 * b);                                                             \
-    }                                                                                                        \
-    _Pragma("unroll") for (int b = 0; b < 2 * NB; b++) _Pragma("unroll") for (int u = 0; u < 4; u++) {       \
-      const h16x2 pr = __builtin_bit_cast(h16x2, (unsigned)vq[b][u]) * __builtin_bit_cast(h16x2, (unsigned)pq[b][u]); \
-      c2 = c2 + pr;                                                                                          \
-    }                                                                                                        \
-  }
-      PV_ROUND(4)
-      PV_ROUND(1)
-#undef PV_ROUND
-      for (; t < nt; t++) {
-        const h16x2 pr = __builtin_bit_cast(h16x2, vrow[t]) * __builtin_bit_cast(h16x2, prow[t]);
-        c2 = c2 + pr;
-      }
-    }
-    if (tile + 1 < ntiles) commit(buf ^ 1);
-    __syncthreads();
-  }
-  if (!chain) return;
-  const int head = j * G + g;
-  const int e0 = head * hd + sl * 32 + 2 * dp;
-  float* o = out + (size_t)r * n_heads * hd;
-  o[e0] = (float)c2[0];
-  o[e0 + 1] = (float)c2[1];
-}
-
 // ---- batched-prefill attention: one workgroup = one kv head x R consecutive prompt rows x the G q heads of its
 // group (Q = G * R queries).  Per (row, head) the arithmetic is k_attn's, value for value -- f32 dots in k order,
 // softmax_row's table exp / sequential row sum (rows up to 1024 positions; longer prompts use k_attn) / true
@@ -1473,7 +1337,7 @@ __global__ __launch_bounds__(256) void k_attn_tile(const float* __restrict__ q, 
     const int qi = e / hd, i = e - qi * hd, r = qi / G, j = qi - r * G;
     const float v = r < rows_here ? q[(size_t)(r0 + r) * dim + head_of(j) * hd + i] : 0.0f;
     if (KV16)
-      ((unsigned short*)qs)[e] = f2h(v);  // f16 cache: q staged as f16, the dots run on v_fma_mix_f32 (exact: see k_attn_s)
+      ((unsigned short*)qs)[e] = f2h(v);  // f16 cache: q staged as f16, the dots run on v_fma_mix_f32 (exact: see score_dot8)
     else
       qs[e] = v;
   }
@@ -1492,22 +1356,22 @@ __global__ __launch_bounds__(256) void k_attn_tile(const float* __restrict__ q, 
         for (int u = 0; u < QW; u++) acc[u] = 0.0f;
         if (KV16) {
           const unsigned short* kr = (const unsigned short*)kc + ((size_t)kvh * seq_cap + t) * hd;
-          typedef _Float16 h2q __attribute__((ext_vector_type(2)));
           const unsigned short* q16 = (const unsigned short*)qs;
           for (int i = 0; i < hd; i += 16) {  // hd % 16 == 0 (host check); products added in k order per query
             const i32x4 k0 = *(const i32x4*)(kr + i), k1 = *(const i32x4*)(kr + i + 8);
 #pragma unroll
             for (int u = 0; u < QW; u++) {
               const i32x4 qa = *(const i32x4*)(q16 + (q0 + u) * hd + i), qb = *(const i32x4*)(q16 + (q0 + u) * hd + i + 8);
+              // (score_dot8's two fmas per word, written out: through the helper this kernel's <true, 4, 4> form took 96 VGPRs for 74)
 #pragma unroll
               for (int w4 = 0; w4 < 4; w4++) {
-                const h2q kh = __builtin_bit_cast(h2q, (unsigned)k0[w4]), qh = __builtin_bit_cast(h2q, (unsigned)qa[w4]);
+                const h16x2 kh = __builtin_bit_cast(h16x2, (unsigned)k0[w4]), qh = __builtin_bit_cast(h16x2, (unsigned)qa[w4]);
                 acc[u] = __builtin_fmaf((float)qh[0], (float)kh[0], acc[u]);
                 acc[u] = __builtin_fmaf((float)qh[1], (float)kh[1], acc[u]);
               }
 #pragma unroll
               for (int w4 = 0; w4 < 4; w4++) {
-                const h2q kh = __builtin_bit_cast(h2q, (unsigned)k1[w4]), qh = __builtin_bit_cast(h2q, (unsigned)qb[w4]);
+                const h16x2 kh = __builtin_bit_cast(h16x2, (unsigned)k1[w4]), qh = __builtin_bit_cast(h16x2, (unsigned)qb[w4]);
                 acc[u] = __builtin_fmaf((float)qh[0], (float)kh[0], acc[u]);
                 acc[u] = __builtin_fmaf((float)qh[1], (float)kh[1], acc[u]);
               }
@@ -1597,12 +1461,11 @@ __global__ __launch_bounds__(256) void k_attn_tile(const float* __restrict__ q, 
   }
   if (lim_hi == 0) return;
   if (KV16) {
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
     const unsigned* vr = (const unsigned*)((const unsigned short*)vc + (size_t)kvh * seq_cap * hd) + n;
     const int vs = hd / 2;  // dwords per V row
-    h2v c[QS];
+    h16x2 c[QS];
 #pragma unroll
-    for (int s2 = 0; s2 < QS; s2++) c[s2] = h2v{(_Float16)0.0f, (_Float16)0.0f};
+    for (int s2 = 0; s2 < QS; s2++) c[s2] = h16x2{(_Float16)0.0f, (_Float16)0.0f};
     // the common case: every chain of the thread has the same causal length (one row) and QS / 2 live chains
     const bool uniform = lim_lo == lim_hi;
     int t0 = 0;
@@ -1621,22 +1484,16 @@ __global__ __launch_bounds__(256) void k_attn_tile(const float* __restrict__ q, 
 #pragma unroll
             for (int u = 0; u < 4; u++) pp[u] = pq[u];
 #pragma unroll
-            for (int u = 0; u < 4; u++) {
-              const h2v prod = __builtin_bit_cast(h2v, vv[u]) * __builtin_bit_cast(h2v, pp[u]);
-              c[s2] = c[s2] + prod;
-            }
+            for (int u = 0; u < 4; u++) pv_step(c[s2], vv[u], pp[u]);
           }
         }
       }
     }
     for (; t0 < lim_hi; t0++) {  // tail / mixed lengths
-      const h2v vp = __builtin_bit_cast(h2v, vr[(size_t)t0 * vs]);
+      const unsigned vp = vr[(size_t)t0 * vs];
 #pragma unroll
       for (int s2 = 0; s2 < QS; s2++) {
-        if (t0 < lim[s2]) {
-          const h2v prod = vp * __builtin_bit_cast(h2v, ((const unsigned*)prow[s2])[t0]);
-          c[s2] = c[s2] + prod;
-        }
+        if (t0 < lim[s2]) pv_step(c[s2], vp, ((const unsigned*)prow[s2])[t0]);
       }
     }
 #pragma unroll

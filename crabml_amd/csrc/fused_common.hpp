@@ -14,10 +14,9 @@ __device__ __forceinline__ float exp_cached_f(float x, const unsigned short* __r
 }
 
 // ---- the rhs quantizer of matmul_vec, one 32-lane half-wave per 32-element block ------------------------------
-// Q81 = false: Q8_0 (buf_q8_0.rs:87-134: d = max|x| / 127, q = trunc(x / d) with the simd cast's NaN -> 0; aux = the
-// i32 sum of the block's quants -- exact, derived, used for Q4_0's -8 offset).  Q81 = true: Q8_1 (buf_q8_1.rs:90-129:
-// q = trunc(clamp(x / d, -128, 127)) with NaN -> -128, aux = the f16 s = d * sum q).  All 32 lanes of the half-wave
-// call it (dead lanes with live = false and v = 0).
+// d = max|x| / 127 rounded to f16; the quants and the aux word (Q8_0: the i32 sum of the block's quants, Q8_1: the f16 s = d * sum q) by
+// the per-element rules q8_quant / q8_aux (devutil.hpp, where buf_q8_0.rs:87-134 and buf_q8_1.rs:90-129 are cited).  All 32 lanes of
+// the half-wave call it (dead lanes with live = false and v = 0).
 struct QLane {
   signed char q;
   unsigned short d;
@@ -29,17 +28,34 @@ __device__ __forceinline__ QLane quant_lane32(float v, bool live) {
   const float amax = half_max_f32(fabsf(v));
   const float dd = amax / 127.0f;
   o.d = f2h(dd);
-  if constexpr (!Q81) {
-    const int qi = rs_f32_as_i32(v / dd);
-    o.q = (signed char)(unsigned char)((unsigned)qi & 0xffu);  // `as i8` from i32 wraps
-    o.aux = half_sum_i32(live ? (int)o.q : 0);
-  } else {
-    const float c = fminf(fmaxf(v / dd, -128.0f), 127.0f);  // Rust f32::max / min return the non-NaN operand
-    const int qi = (int)c;
-    o.q = (signed char)qi;
-    const int s = half_sum_i32(live ? qi : 0);
-    o.aux = (int)f2h((float)s * dd);
-  }
+  const int qi = q8_quant<Q81>(v, dd);
+  o.q = (signed char)qi;
+  o.aux = q8_aux<Q81>(half_sum_i32(live ? qi : 0), dd);
+  return o;
+}
+// The same block held by the 16 lanes of ONE DPP row, two adjacent columns per lane (the packed-f16 PV chains of attention leave their
+// outputs that way): the block maximum and the integer sum are row operations, no v_readlane.  All 16 lanes of the row call it (rows are
+// all-live or all-dead where the block size divides the head: dead lanes with live = false and v0 = v1 = 0).
+struct QPair {
+  int q0, q1;  // sign-extended quants of the lane's two columns
+  unsigned short d;
+  int aux;
+};
+template <bool Q81>
+__device__ __forceinline__ QPair pair16_rules(float v0, float v1, bool live, float dd) {
+  QPair o;
+  o.q0 = q8_quant<Q81>(v0, dd);
+  o.q1 = q8_quant<Q81>(v1, dd);
+  o.aux = q8_aux<Q81>(row16_sum_i32(live ? o.q0 + o.q1 : 0), dd);
+  return o;
+}
+// q81: the format as a run-time value (a kernel argument, uniform over the launch).  The block maximum, the division and the f16 rounding
+// of d stand outside the branch: the compiler does not merge the DPP row operations of the two arms.
+__device__ __forceinline__ QPair quant_pair16(int q81, float v0, float v1, bool live) {
+  const float amax = row16_max_f32(fmaxf(fabsf(v0), fabsf(v1)));
+  const float dd = amax / 127.0f;
+  QPair o = q81 ? pair16_rules<true>(v0, v1, live, dd) : pair16_rules<false>(v0, v1, live, dd);
+  o.d = f2h(dd);
   return o;
 }
 template <bool Q81>
@@ -49,13 +65,23 @@ __device__ __forceinline__ void store_qaux(void* aux, int blk, int v) {
   else
     ((int*)aux)[blk] = v;
 }
+// quant_lane32 and store_qaux with the format as a run-time value, like quant_pair16 (the attention kernels)
+__device__ __forceinline__ QLane quant_lane32(int q81, float v, bool live) {
+  return q81 ? quant_lane32<true>(v, live) : quant_lane32<false>(v, live);
+}
+__device__ __forceinline__ void store_qaux(int q81, void* aux, int blk, int v) {
+  if (q81)
+    store_qaux<true>(aux, blk, v);
+  else
+    store_qaux<false>(aux, blk, v);
+}
 
 // ---- Q8_K planes straight from the kernels that produce the vector ------------------------------------------------------
 // A Q8_K super-block is 256 elements and its scale comes from the FIRST element of maximal |x| among them
 // (buf_q8_k.rs:84-131), but the producers own less: an attention workgroup one head (head_dim values), a gate/up workgroup
 // 32 rows.  Every producer publishes its values as 8-byte {f32, epoch} granules (one write-through store carries data and
 // tag), gathers the rest of its super-block from its neighbours' granules (bounded polls), runs the whole block's quantizer
-// (q8k_wave_quant: the arithmetic of the stand-alone quantizer launch, bit for bit) and stores the part that is its own.
+// (q8k_wave_quant, devutil.hpp: the function the stand-alone quantizer launch calls) and stores the part that is its own.
 // The consuming GEMV then only copies finished planes into LDS instead of quantizing the f32 vector in its prologue
 // (56 super-blocks per workgroup for ffn_down).  All producers of a super-block are co-resident by construction.
 struct Q8KExchange {
@@ -276,7 +302,7 @@ __global__ __launch_bounds__(1024) void k_norm_f32(float* __restrict__ x, const 
 
 // batched prefill, Q8_0 / Q8_1 rhs: x[row] (+= addv[row]: the pending wo / ffn_down output, llama2.rs:266 / :636) -> RMSNorm ->
 // the row's quantized planes, one workgroup per row.  Replaces residual-add, norm and quantize launches (three passes over
-// the (rows, cols) activations) by one; per row the arithmetic is norm_quant_block's, i.e. the decode step's.
+// the (rows, cols) activations) by one; per row it calls norm_quant_block, the decode step's row body.
 template <int NIT, bool Q81>
 __global__ __launch_bounds__(1024) void k_norm_quant_rows(float* __restrict__ x, const float* __restrict__ addv, const float* __restrict__ w,
                                                          int cols, float eps, char* __restrict__ planes, size_t row_stride, size_t off_d,

@@ -42,7 +42,7 @@
 namespace crabml_hip {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef h16x2 f16x2;  // (common.hpp; named like f16x8 here)
 
 // ---- B': the rows of a prompt pass as pre-scaled f16, in the GEMM's k-slot order: xh[col][kb][32] f16 ------------------------
 // (the slot orders and the conversion of one 8-slot group: f16w_rows.hpp, shared with the row kernels that write B' themselves)
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
   if constexpr (GU) {
     if (mats.hq.planes != nullptr) {
       // h = silu(g) * u of the workgroup's 64 rows x CW columns through LDS (the B' buffers are done), then ONE THREAD per
-      // (column, 32-row block) runs the row quantizer on it (quant_lane32's arithmetic, buf_q8_0.rs:87-134 / buf_q8_1.rs:90-129: the
+      // (column, 32-row block) runs the row quantizer on it (q8_quant / q8_aux, devutil.hpp: buf_q8_0.rs:87-134 / buf_q8_1.rs:90-129; the
       // block maximum and the integer sum do not depend on the order) and writes the block's quants, scale, sum and -- in the slot
       // order of ffn_down's GEMM -- its 32 pre-scaled halfs: h never exists as f32 in memory
       constexpr int CS = 68;  // floats per column (64 rows + 4: 16-byte aligned columns, four banks apart)
@@ -462,26 +462,20 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
 #pragma unroll
         for (int e = 0; e < 32; e++) {
           const float x = v[e >> 2][e & 3];
-          if (hq.q81) {
-            q[e] = (int)fminf(fmaxf(x / dd, -128.0f), 127.0f);
-          } else {
-            q[e] = (int)(signed char)(unsigned char)((unsigned)rs_f32_as_i32(x / dd) & 0xffu);
-          }
+          q[e] = hq.q81 ? q8_quant<true>(x, dd) : q8_quant<false>(x, dd);
           sum += q[e];
         }
         char* p = hq.planes + (size_t)col * hq.stride;
         i32x4 pk[2];
 #pragma unroll
-        for (int e = 0; e < 8; e++)
-          pk[e >> 2][e & 3] = (int)(((unsigned)q[4 * e] & 0xffu) | (((unsigned)q[4 * e + 1] & 0xffu) << 8) | (((unsigned)q[4 * e + 2] & 0xffu) << 16) |
-                                    (((unsigned)q[4 * e + 3] & 0xffu) << 24));
+        for (int e = 0; e < 8; e++) pk[e >> 2][e & 3] = (int)pack_q8x4(q[4 * e], q[4 * e + 1], q[4 * e + 2], q[4 * e + 3]);
         ((i32x4*)(p + (size_t)hb * 32))[0] = pk[0];
         ((i32x4*)(p + (size_t)hb * 32))[1] = pk[1];
         ((unsigned short*)(p + hq.off_d))[hb] = dh;
         if (hq.q81)
-          ((unsigned short*)(p + hq.off_aux))[hb] = f2h((float)sum * dd);
+          ((unsigned short*)(p + hq.off_aux))[hb] = (unsigned short)q8_aux<true>(sum, dd);
         else
-          ((int*)(p + hq.off_aux))[hb] = sum;
+          ((int*)(p + hq.off_aux))[hb] = q8_aux<false>(sum, dd);
         if (hq.xh != nullptr) {
           const float ds = h2f(dh);
           unsigned short* xr = hq.xh + ((size_t)col * nbh + hb) * 32;

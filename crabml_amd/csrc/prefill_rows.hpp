@@ -1,6 +1,7 @@
 // prefill_rows.hpp -- row kernels of the FAST prompt pass that also leave the row's pre-scaled f16 plane B' for the weight GEMM that
-// reads it next (gemm_f16w.hip; slot orders: f16w_rows.hpp): the same arithmetic as the kernels they wrap, one k_rows_to_f16 launch
-// fewer per GEMM.  B' is bit for bit what k_rows_to_f16 makes from the finished planes.
+// reads it next (gemm_f16w.hip; slot orders: f16w_rows.hpp): they call the row bodies and rule helpers of the kernels they stand in for
+// (norm_quant_block, q8_quant / q8_aux, q8k_wave_quant), one k_rows_to_f16 launch fewer per GEMM.  B' is bit for bit what k_rows_to_f16
+// makes from the finished planes.
 #pragma once
 #include "f16w_rows.hpp"
 #include "fused_common.hpp"
@@ -50,8 +51,8 @@ __global__ __launch_bounds__(1024) void k_norm_quant_rows_h(float* __restrict__ 
 // lane; nothing but the chunk sums goes through LDS (two barriers where norm_quant_block has four, and eight rows per CU in flight
 // instead of two).  Arithmetic = norm_quant_block's, bit for bit: a chunk's squares from -0.0 in element order (half: rows 0..15 and
 // 16..31 separately, then added -- the fast step's order; else one 32-element scan, rms_norm.rs:35-38); the chunk sums added as there
-// (half: 64 per round through wave_sum_f32, rounds in order; else strictly in chunk order); (x / rms) * w; quant_lane32's quantizer
-// (maximum and integer sum do not depend on the order).
+// (half: 64 per round through wave_sum_f32, rounds in order; else strictly in chunk order); (x / rms) * w; then the rhs quantizer's
+// rules (q8_quant / q8_aux, devutil.hpp) on a block maximum and integer sum from the register scan (neither depends on the order).
 template <int E, bool Q81>
 __global__ __launch_bounds__(256) void k_norm_quant_rows_w(float* __restrict__ x, const float* __restrict__ addv, const float* __restrict__ w,
                                                           int cols, float eps, char* __restrict__ planes, size_t row_stride, size_t off_d,
@@ -143,11 +144,7 @@ __global__ __launch_bounds__(256) void k_norm_quant_rows_w(float* __restrict__ x
   int q[E], sum = 0;
 #pragma unroll
   for (int e = 0; e < E; e++) {
-    const float v = xv[e >> 2][e & 3];
-    if constexpr (Q81)
-      q[e] = (int)fminf(fmaxf(v / dd, -128.0f), 127.0f);
-    else
-      q[e] = (int)(signed char)(unsigned char)((unsigned)rs_f32_as_i32(v / dd) & 0xffu);
+    q[e] = q8_quant<Q81>(xv[e >> 2][e & 3], dd);
     sum += q[e];
   }
   if constexpr (E == 16) sum += dpp_i<0xB1>(sum);
@@ -156,18 +153,13 @@ __global__ __launch_bounds__(256) void k_norm_quant_rows_w(float* __restrict__ x
   for (int j = 0; j < E / 16; j++) {
     i32x4 pk;
 #pragma unroll
-    for (int i = 0; i < 4; i++)
-      pk[i] = (int)(((unsigned)q[16 * j + 4 * i] & 0xffu) | (((unsigned)q[16 * j + 4 * i + 1] & 0xffu) << 8) |
-                    (((unsigned)q[16 * j + 4 * i + 2] & 0xffu) << 16) | (((unsigned)q[16 * j + 4 * i + 3] & 0xffu) << 24));
+    for (int i = 0; i < 4; i++) pk[i] = (int)pack_q8x4(q[16 * j + 4 * i], q[16 * j + 4 * i + 1], q[16 * j + 4 * i + 2], q[16 * j + 4 * i + 3]);
     ((i32x4*)(p + (size_t)E * tid))[j] = pk;
   }
   const int blk = E == 32 ? tid : tid >> 1;
   if (E == 32 || (tid & 1) == 0) {
     ((unsigned short*)(p + off_d))[blk] = dh;
-    if constexpr (Q81)
-      ((unsigned short*)(p + off_aux))[blk] = f2h((float)sum * dd);
-    else
-      ((int*)(p + off_aux))[blk] = sum;
+    store_qaux<Q81>(p + off_aux, blk, q8_aux<Q81>(sum, dd));
   }
   if (xh != nullptr) {
     const float ds = h2f(dh);

@@ -34,18 +34,16 @@ __global__ __launch_bounds__(256) void k_quantize_q8_0(const float* __restrict__
   float v = live ? x[blk * 32 + j] : 0.f;
   float amax = half_max_f32(fabsf(v));  // (256-thread blocks of whole waves: all lanes converged)
   float dd = amax / 127.0f;
-  float t = v / dd;
-  int qi = rs_f32_as_i32(t);
-  signed char q8 = (signed char)(unsigned char)((unsigned)qi & 0xffu);  // `as i8` from i32 wraps
-  int s = half_sum_i32((int)q8);
+  const int qi = q8_quant<false>(v, dd);  // devutil.hpp
+  int s = half_sum_i32(qi);
   if (live) {
-    q[blk * 32 + j] = q8;
+    q[blk * 32 + j] = (signed char)qi;
     if (j == 0) {
       d[blk] = f2h(dd);
-      isum[blk] = s;
+      isum[blk] = q8_aux<false>(s, dd);
     }
     if (xh) {
-      const unsigned short h = f16w_value((int)q8, h2f(f2h(dd)));
+      const unsigned short h = f16w_value(qi, h2f(f2h(dd)));
       xh[blockIdx.y * row_elems + blk * 32 + f16w_slot_of_elem(j)] = h;
       f16w_flag(f16w_is_inf(h), ovf);
     }
@@ -67,17 +65,13 @@ __global__ __launch_bounds__(256) void k_quantize_q8_1(const float* __restrict__
   float v = live ? x[blk * 32 + j] : 0.f;
   float amax = half_max_f32(fabsf(v));
   float dd = amax / 127.0f;
-  float sv = v / dd;
-  // Rust f32::max / f32::min return the non-NaN operand: NaN.max(-128) = -128
-  float c = fminf(fmaxf(sv, -128.0f), 127.0f);
-  int qi = (int)c;  // |c| <= 128: exact truncation
+  const int qi = q8_quant<true>(v, dd);  // devutil.hpp
   int s = half_sum_i32(qi);
   if (live) {
     q[blk * 32 + j] = (signed char)qi;
     if (j == 0) {
       d[blk] = f2h(dd);
-      // s accumulates small integers in f32 in the reference (exact), then `s *= d`
-      sp[blk] = f2h((float)s * dd);
+      sp[blk] = (unsigned short)q8_aux<true>(s, dd);
     }
     if (xh) {
       const unsigned short h = f16w_value(qi, h2f(f2h(dd)));

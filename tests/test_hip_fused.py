@@ -428,6 +428,22 @@ def test_q4_1_five_kernel_layers_equal_the_segment_path(ca):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), f"step {i}"
 
 
+def test_q8_1_epilogues_of_the_exact_pv_kernels_equal_the_quantizer_launch(ca):
+    """The Q8_1 blocks of wo's rhs as the exact long-context PV kernels leave them: k_attn_pv_split (quant_lane32 on a half-wave) and
+    k_attn_pv (flag 131072: quant_pair16 on a 16-lane row, two columns per lane), against Q4_1_SEGMENTS, where attention writes f32
+    and the stand-alone quantizer launch makes the planes.  The same per-element and aux rules (q8_quant / q8_aux), so the logits are
+    bit-identical at every step; positions 0 .. 299 cross the 256-position tile and take every tail length modulo 8."""
+    model = synth.build_model(synth.SHAPES["tiny-gqa"], synth.Q4_1, seed=62, n_layers=2)
+    dev = ca.HipTensorDevice(0)
+    conf, w = synth.to_hip(model, dev)
+    ref, split, pv = (ca.HipLlamaRunner(conf, w, dev, 320, True, attn_long_from=1, extra_flags=EXACT + f) for f in (512, 0, 131072))
+    rng = np.random.default_rng(19)
+    for i, t in enumerate(int(v) for v in rng.integers(0, 1024, size=300)):
+        r = ref.forward(t, i).view(np.uint32).copy()
+        assert np.array_equal(split.forward(t, i).view(np.uint32), r), f"k_attn_pv_split, step {i}"
+        assert np.array_equal(pv.forward(t, i).view(np.uint32), r), f"k_attn_pv, step {i}"
+
+
 def test_q4_k_m_mix_mixed_dtypes_inside_a_layer(ca):
     """llama.cpp's Q4_K_M recipe: a Q4_K body with attn_v / ffn_down in Q6_K on the `use_more_bits` layers and a Q6_K
     classifier -- different GGML types inside one layer, all with the Q8_K rhs (buf/api.rs:142-159).  The fused step
