@@ -149,7 +149,7 @@ struct StepPlan {
   // ---- the segment forms
   bool norm_epi = false;       // Fused5: RMSNorm + quantize run in the wo / ffn_down epilogue (tp > 1: over a P2P group or in the dry run,
                                // where the epilogue hosts the collective too)
-  bool norm_epi_k = false;     // the same for Q4_K layers (Q8_K planes out of the epilogue)
+  bool norm_epi_k = false;     // the same for Q4_K / Q5_K layers (Q8_K planes out of the epilogue)
   // the hop-free norm of the fast step (Q4_0 / Q8_0 layers, one GPU): wo quantizes x * w_norm block by block and leaves 1 / rms to
   // the gate/up launch (RmsTail, gemv_core.hpp) -- no in-launch gather.  Off: CRABML_HIP_LLAMA_EXACT_NORM, strict order, tp.
   bool defer_norm = false;
@@ -409,9 +409,10 @@ NqOrdKFn nq_ord_k_kernel(int split, int qin) {
   });
   return fn;
 }
-// ... and the forms of k_gateup_k_lds<QOUT, ORD, NORMIN> that exist (NORMIN writes planes and has no ordered form)
+// ... and the forms of k_gateup_k_lds<QOUT, ORD, NORMIN, Q5> that exist (NORMIN writes planes and has no ordered form; nor has a Q5_K body)
 typedef decltype(&k_gateup_k_lds<false>) GateupKFn;
-GateupKFn gateup_k_kernel(bool qout, bool ord, bool normin) {
+GateupKFn gateup_k_kernel(bool qout, bool ord, bool normin, bool q5 = false) {
+  if (q5) return normin ? k_gateup_k_lds<true, false, true, true> : qout ? k_gateup_k_lds<true, false, false, true> : k_gateup_k_lds<false, false, false, true>;
   if (ord) return qout ? k_gateup_k_lds<true, true> : k_gateup_k_lds<false, true>;
   if (normin) return k_gateup_k_lds<true, false, true>;
   return qout ? k_gateup_k_lds<true> : k_gateup_k_lds<false>;
@@ -1002,13 +1003,16 @@ int enqueue_segment_generic(crabml_hip_llama* c, int seg) {
   return 0;
 }
 
-// Q4_K and Q4_1 layers (fast mode): the fused GEMV kernels with the format's inner loop against Q8_K / Q8_1
+// Q4_K, Q5_K and Q4_1 layers (fast mode): the fused GEMV kernels with the format's inner loop against Q8_K / Q8_1
 // activation planes.  The rhs quantizer is its own launch here (a Q8_K super-block spans 256 rows: eight 32-row
 // workgroups; Q8_1 keeps the same structure), so a layer is 11 launches instead of the per-op path's 18.
 template <int FMT>
 int enqueue_segment_k(crabml_hip_llama* c, int seg) {
-  constexpr uint32_t QT = FMT == CRABML_HIP_Q4_K ? CRABML_HIP_Q8_K : CRABML_HIP_Q8_1;
-  constexpr int BE = FMT == CRABML_HIP_Q4_K ? 256 : 32;  // elements per weight block
+  // a K-quant body: Q4_K, or Q5_K -- the same five launches with the Q5_K row loader, built in the norm-epilogue form only (decide_step)
+  constexpr bool KF = FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K;
+  constexpr bool Q5 = FMT == CRABML_HIP_Q5_K;
+  constexpr uint32_t QT = KF ? CRABML_HIP_Q8_K : CRABML_HIP_Q8_1;
+  constexpr int BE = KF ? 256 : 32;  // elements per weight block
   typedef typename ActOf<FMT>::type Act;
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
@@ -1038,7 +1042,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     return c->act_dim;
   };
   float* dst = tp ? c->partial : c->x;
-  const bool nepi = FMT == CRABML_HIP_Q4_K && c->plan.norm_epi_k;
+  const bool nepi = KF && c->plan.norm_epi_k;
   // strict-order device, Q4_K layers (c->plan.ordered): the same five launches with every sum in the reference's order -- nine-term records per
   // super-block added in order (q4k_class_terms / q4k_ordered_sum, gemv_core.hpp), the reference's norm order in the epilogue
   const bool ordk = FMT == CRABML_HIP_Q4_K && c->plan.ordered;
@@ -1055,7 +1059,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
   auto gemv_out = [&](const crabml_hip_buf* w, const Act& a, const float* xin, int k, uint32_t stage, const float* wnext,
                       float eps_next, int qmode, bool x_only = false) -> int {
     CH_TRY(P0(stage, dim, k));
-    if constexpr (FMT == CRABML_HIP_Q4_K) {
+    if constexpr (KF) {
       if (nepi) {
         NormGather ng{c->slots, c->slots + dim / 16, c->state + 4, c->state + 5, n_segments(c), seg, c->rsums};
         ActLayout al = act_layout(QT, (size_t)dim);
@@ -1067,11 +1071,12 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         c->tap.note(seg / 2, stage == 2 ? CRABML_HIP_PLAN_SPLIT_WO : CRABML_HIP_PLAN_SPLIT_DOWN, split);
         c->tap.note(seg / 2, stage == 2 ? CRABML_HIP_PLAN_QMODE_WO : CRABML_HIP_PLAN_QMODE_DOWN, qmode);
         if (stage == 2) c->tap.note(seg / 2, CRABML_HIP_PLAN_WO_X_ONLY, x_only ? 1 : 0);
-        if (ordk) {  // (qmode is 1 or 2 here: `qin` holds on every ordered context)
-          launch_k(st, R, nq_ord_k_kernel(split, qmode == 2 ? 2 : 1), dim3(dim / 32 * split), dim3(1024), q8k_ord_lds_bytes(k, 32 / split), planes_of(w), a,
-                   xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
-          return P1();
-        }
+        if constexpr (!Q5)
+          if (ordk) {  // (qmode is 1 or 2 here: `qin` holds on every ordered context)
+            launch_k(st, R, nq_ord_k_kernel(split, qmode == 2 ? 2 : 1), dim3(dim / 32 * split), dim3(1024), q8k_ord_lds_bytes(k, 32 / split), planes_of(w),
+                     a, xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
+            return P1();
+          }
         with_const_else<2, 1>(split, [&](auto s) {
           with_const_else<2, 1, 0>(qmode, [&](auto q) {  // (the rhs planes in LDS unless they are read from global memory)
             launch_k(st, R, k_gemv_res_nq<FMT, decltype(s)::value, decltype(q)::value>, dim3(dim / 32 * split), dim3(1024), qmode ? q8k_lds_bytes(k) : 0,
@@ -1081,11 +1086,15 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         return P1();
       }
     }
-    if (tp)
-      launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), a, dst, dim, k / BE);
-    else
-      launch_k(st, R, k_gemv_res<FMT, 1, true>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), a, dst, dim, k / BE);
-    return P1();
+    if constexpr (Q5) {
+      CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a Q5_K body outside the norm-epilogue form (decide_step sends it to the per-op segments)");
+    } else {
+      if (tp)
+        launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), a, dst, dim, k / BE);
+      else
+        launch_k(st, R, k_gemv_res<FMT, 1, true>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), a, dst, dim, k / BE);
+      return P1();
+    }
   };
 
   // the tap (test hook): host-side copies between the launches of the tapped layer; a no-op unless a tapped step is being enqueued.
@@ -1119,19 +1128,21 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     CH_TRY(P0(1, total_rows, dim));
     with_qkv_epi(c, decode_qkv_epi(c, l), l, [&](auto ep) {
       constexpr int A = QkvArchOf<decltype(ep)>::value;
-      if (ordk)
-        launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), ord_terms_k_lds_bytes(dim / BE), planes_of(c->wq[l]),
-                 planes_of(c->wk[l]), planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]));
-      else
-        launch_k(st, R, k_qkv<FMT, false, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
-                 planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
+      if constexpr (!Q5)
+        if (ordk) {
+          launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), ord_terms_k_lds_bytes(dim / BE), planes_of(c->wq[l]),
+                   planes_of(c->wk[l]), planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]));
+          return;
+        }
+      launch_k(st, R, k_qkv<FMT, false, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
+               planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
     });
     CH_TRY(P1());
     CH_TRY(TAP(tl, CRABML_HIP_TAP_QBUF, c->qbuf, (size_t)dim_l * 4));
     // Q8_K producers: the (short-context) attention kernel assembles the planes of wo's rhs itself; wo copies them
     const bool aq8 = qout && (g.flags & CRABML_HIP_LLAMA_Q8K_ATTN_PRODUCER) && c->attn_variant == 0 && c->plan.attn_s_rows > 0;
     tap.note(l, CRABML_HIP_PLAN_AQ8, aq8 ? 1 : 0);
-    if constexpr (FMT == CRABML_HIP_Q4_K) {
+    if constexpr (KF) {
       if (aq8) {
         const ActLayout ala = act_layout(QT, (size_t)dim_l);
         const AttnQ8K k8{Q8KExchange{c->a8gran, c->state + 4, c->state + 5, n_segments(c), seg}, (float*)(c->act_attn + ala.off_d),
@@ -1157,7 +1168,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     CH_TRY(TAP(tl && wo_x_only, CRABML_HIP_TAP_WO_RSUMS, c->rsums, (size_t)(dim / 32) * wo_parts * 4));
     tap.note(l, CRABML_HIP_PLAN_DOWN_Q6K, c->down[l]->dtype == CRABML_HIP_Q6_K ? 1 : 0);
     CH_TRY(P0(3, 2.0 * hidden_l, dim));
-    if constexpr (FMT == CRABML_HIP_Q4_K) {
+    if constexpr (KF) {
       const ActLayout alh = act_layout(QT, (size_t)hidden_l);
       const Q8KExchange hx{c->h8gran, c->state + 4, c->state + 5, n_segments(c), seg};
       // the form <QOUT, ORD, NORMIN>: h leaves as Q8_K planes too / strict order / wo left x only (above) and this launch normalizes
@@ -1172,7 +1183,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         nsums = c->rsums;
         sum_parts = wo_parts;
       }
-      launch_k(st, R, gateup_k_kernel(qout, ordk, normin), dim3(hidden_l / 32), dim3(1024), ordk ? q8k_ord_lds_bytes(dim, 64) : q8k_lds_bytes(dim),
+      launch_k(st, R, gateup_k_kernel(qout, ordk, normin, Q5), dim3(hidden_l / 32), dim3(1024), ordk ? q8k_ord_lds_bytes(dim, 64) : q8k_lds_bytes(dim),
                planes_of(c->gate[l]), planes_of(c->up[l]), act_k(c->act_dim, dim), c->ffn_act, c->h, hidden_l, dim / 256, hx,
                (signed char*)hp, (float*)(hp ? hp + alh.off_d : nullptr), (short*)(hp ? hp + alh.off_aux : nullptr),
                (signed char*)(hp ? hp + alh.off_p : nullptr), nx, nw, normin ? 1e-5f : 0.f, nsums, sum_parts);
@@ -1196,7 +1207,9 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
 int enqueue_segment(crabml_hip_llama* c, int seg) {
   switch (c->plan.path) {
     case SegPath::FusedK:
-      return c->wtype == CRABML_HIP_Q4_K ? enqueue_segment_k<CRABML_HIP_Q4_K>(c, seg) : enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
+      return c->wtype == CRABML_HIP_Q4_K   ? enqueue_segment_k<CRABML_HIP_Q4_K>(c, seg)
+             : c->wtype == CRABML_HIP_Q5_K ? enqueue_segment_k<CRABML_HIP_Q5_K>(c, seg)
+                                           : enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
     case SegPath::Fused5:
       return c->wtype == CRABML_HIP_Q4_0   ? enqueue_segment_t<CRABML_HIP_Q4_0>(c, seg)
              : c->wtype == CRABML_HIP_Q8_0 ? enqueue_segment_t<CRABML_HIP_Q8_0>(c, seg)
@@ -2086,7 +2099,7 @@ struct ModelFacts {
   const crabml_hip_buf* outw = nullptr;                                             // the classifier: output.weight, else the embedding
   uint32_t wt = 0, out_wt = 0, qt = 0, out_qt = 0;  // weight type of the layers / the classifier, and their vec_dot_rhs_dtype
   bool mixed = false;                               // some layer matrix has another type than wq[0] (with the same rhs type)
-  bool mix_v_down_q6k = true;  // every deviating tensor is an attn_v / ffn_down in Q6_K inside a Q4_K layer (the *_K_M recipe)
+  bool mix_v_down_q6k = true;  // every deviating tensor is an attn_v / ffn_down in Q6_K inside a Q4_K / Q5_K layer (the *_K_M recipe)
   bool split_vocab = false;
   size_t vocab_l = 0;
 };
@@ -2151,7 +2164,7 @@ static int validate_config(crabml_hip_device_t* dev, const crabml_hip_llama_conf
   return 0;
 }
 
-// type and shape of every weight.  Fused kernels exist for Q4_0 / Q8_0 / Q4_1 and Q4_K layers; a classifier of another format --
+// type and shape of every weight.  Fused kernels exist for Q4_0 / Q8_0 / Q4_1, Q4_K and Q5_K layers; a classifier of another format --
 // llama.cpp's "Q4_0" files keep output.weight in Q6_K -- does not take the layers off them: the final segment quantizes the
 // normalized row for the classifier's own rhs type.
 static int validate_weights(crabml_hip_device_t* dev, const crabml_hip_llama_config_t& g, const crabml_hip_llama_weights_t* w, ModelFacts* f) {
@@ -2173,13 +2186,13 @@ static int validate_weights(crabml_hip_device_t* dev, const crabml_hip_llama_con
   };
   // a layer's matrices may differ in GGML type (llama.cpp's *_K_M files: attn_v / ffn_down in Q6_K on some layers) as
   // long as they share the rhs type (buf/api.rs:142-159: every K-quant takes Q8_K): such a model runs the per-op
-  // segments, each GEMV picking its kernel by the tensor's own dtype -- unless it is the *_K_M recipe, which the Q4_K kernels take
+  // segments, each GEMV picking its kernel by the tensor's own dtype -- unless it is the *_K_M recipe, which the Q4_K / Q5_K kernels take
   auto check_w = [&](const crabml_hip_buf* b, size_t m, size_t k, bool v_or_down) {
     if (!b) return false;
     if (b->dtype != wt) {
       if (vec_dot_rhs_dtype(b->dtype) != qt || k % block_elems(b->dtype)) return false;
       f->mixed = true;
-      if (!(v_or_down && wt == CRABML_HIP_Q4_K && b->dtype == CRABML_HIP_Q6_K)) f->mix_v_down_q6k = false;
+      if (!(v_or_down && (wt == CRABML_HIP_Q4_K || wt == CRABML_HIP_Q5_K) && b->dtype == CRABML_HIP_Q6_K)) f->mix_v_down_q6k = false;
     }
     return check(b, m, k, b->dtype);
   };
@@ -2295,11 +2308,14 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   const uint32_t wt = f.wt;
   const bool fused_fmt = wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0 || wt == CRABML_HIP_Q4_1;  // a dot of one term per block
   const bool chunks_resident = dim / 32 <= n_cu;  // every workgroup of a wo / ffn_down gather must be resident
-  // the Q4_K norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on
-  const bool k_epilogue_eligible = wt == CRABML_HIP_Q4_K && f.out_qt == CRABML_HIP_Q8_K && tp == 1 && !has(CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) &&
+  // the K-quant norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on, and the ONLY form a Q5_K body is
+  // built in -- a Q5_K context that misses a clause of it (a classifier with another rhs, NO_NORM_EPILOGUE, a dim that is no multiple
+  // of 256, chunks that are not resident) runs the per-op segments
+  const bool k_body = wt == CRABML_HIP_Q4_K || wt == CRABML_HIP_Q5_K;
+  const bool k_epilogue_eligible = k_body && f.out_qt == CRABML_HIP_Q8_K && tp == 1 && !has(CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) &&
                                    dim % 256 == 0 && chunks_resident;
   const bool k_fusion = !has(CRABML_HIP_LLAMA_NO_KQUANT_FUSION);
-  // the Q4_K fused kernels take a Q6_K attn_v / ffn_down beside the Q4_K planes (the *_K_M recipe), but only in the norm-epilogue form
+  // the K-quant fused kernels take a Q6_K attn_v / ffn_down beside the body's planes (the *_K_M recipe), but only in the norm-epilogue form
   const bool mix_fused = f.mixed && f.mix_v_down_q6k && !strict && k_epilogue_eligible && k_fusion;
 
   // Strict order, one device, Q4_0 / Q8_0 / Q4_1: the fused launches in their block-ordered form (7 per layer: norm + quantize stay
@@ -2328,11 +2344,12 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
       for (int qin = 1; qin <= 2; qin++) fits = fits && lds_fits(dev, (const void*)nq_ord_k_kernel(split, qin), nq, LDS_CAP, 48 * 1024);
     return fits;
   };
-  const bool ordk = strict && k_epilogue_eligible && k_fusion && !has(CRABML_HIP_LLAMA_NO_RHS_PROLOGUE) && (!f.mixed || f.mix_v_down_q6k) &&
+  const bool ordk = strict && wt == CRABML_HIP_Q4_K && k_epilogue_eligible && k_fusion && !has(CRABML_HIP_LLAMA_NO_RHS_PROLOGUE) && (!f.mixed || f.mix_v_down_q6k) &&
                     dim_l % 256 == 0 && hidden_l % 256 == 0 && ordk_fits();
-  // the fast K-quant segments: Q4_K always; Q4_1 when it cannot take the five launches (a classifier of another format) or for the A/B flag
+  // the fast K-quant segments: Q4_K always; Q5_K in the norm-epilogue form (there is no ordered Q5_K form: a strict-order device keeps
+  // it on the per-op segments); Q4_1 when it cannot take the five launches (a classifier of another format) or for the A/B flag
   const bool fast_k = !strict && (!f.mixed || mix_fused) && k_fusion &&
-                      (wt == CRABML_HIP_Q4_K || (wt == CRABML_HIP_Q4_1 && (f.out_wt != wt || has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS))));
+                      (wt == CRABML_HIP_Q4_K || (wt == CRABML_HIP_Q5_K && k_epilogue_eligible) || (wt == CRABML_HIP_Q4_1 && (f.out_wt != wt || has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS))));
   // per-op launches: a strict-order device without an ordered form, a weight format without fused kernels, a mix they do not take
   const bool per_op = (strict && !ord5) || !fused_fmt || (f.mixed && !mix_fused);
 
@@ -2868,7 +2885,7 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   // (decide_step: what Fused5 / FusedK and !ordered imply)
   if ((c->plan.path != SegPath::Fused5 && c->plan.path != SegPath::FusedK) || c->plan.ordered || c->tp > 1 || c->ext_kv)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
-            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 / Q4_K layers, the Q4_K_M mix) on one device with its own KV cache");
+            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 / Q4_K / Q5_K layers, the Q4_K_M / Q5_K_M mixes) on one device with its own KV cache");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim;
   // the row type of every field that leaves as blocks (the others: f32 values, the plan words)

@@ -521,7 +521,7 @@ struct Planes {
   const i32x4* q;
   const unsigned short* d;
 };
-// a Q6_K matrix standing in for one of a Q4_K layer's (llama.cpp *_K_M mixes): base = nullptr means "not used"
+// a Q6_K matrix standing in for one of a Q4_K / Q5_K layer's (llama.cpp *_K_M mixes): base = nullptr means "not used"
 struct Planes6 {
   const char* base;
   size_t off_qh;
@@ -532,6 +532,7 @@ struct Planes6 {
 template <int FMT, bool DEFER = false, int ARCH = QKV_LLAMA>
 __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb,
                                              typename QkvArch<ARCH>::epi e, Planes6 wv6, RmsTail rt, int upfront = 0) {
+  constexpr bool KF = FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K;  // a K-quant body: nb counts super-blocks, rows_dot has its loader
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + wave_in_wg();
   int row0 = wave * 2, rs = 1;
@@ -562,20 +563,20 @@ __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, ty
   }
   float acc[2];
   bool done = false;
-  if constexpr (FMT == CRABML_HIP_Q4_K) {
+  if constexpr (KF) {
     if (wv6.base != nullptr && row0 >= e.dim + e.kv_dim) {  // the V rows of this layer are Q6_K (wave-uniform)
       rows_partial_q6k<2>(wv6.base, wv6.off_qh, act, local, m, nb, lane, acc, nullptr, rs);
       done = true;
     }
   }
   float inv_rms = 1.0f;
-  if constexpr (DEFER && FMT != CRABML_HIP_Q4_K) {
+  if constexpr (DEFER && !KF) {
     if (upfront && nb * BlockFmt<FMT>::UNITS == 128)
       inv_rms = rows_partial_rms_128<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc, rt, rq, rs);
     else
       inv_rms = rows_partial_rms<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc, rt, rq, rs);
   } else {
-    if constexpr (FMT != CRABML_HIP_Q4_K) {
+    if constexpr (!KF) {
       if (!done && upfront && (nb * BlockFmt<FMT>::UNITS) % 128 == 0) {
         rows_partial_2step<FMT, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
         done = true;

@@ -498,7 +498,10 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
                                                       signed char* __restrict__ q, void* __restrict__ d,
                                                       void* __restrict__ isum, NormGather ng, int nb, Planes6 w6,
                                                       typename TpArg<TP>::type tp) {
-  constexpr bool KQ = FMT == CRABML_HIP_Q4_K;  // Q4_K weights: nb counts super-blocks, the output is Q8_K
+  constexpr bool Q5 = FMT == CRABML_HIP_Q5_K;
+  constexpr bool KQ = FMT == CRABML_HIP_Q4_K || Q5;  // Q4_K / Q5_K weights: nb counts super-blocks, the output is Q8_K
+  constexpr int EF = Q5 ? CRABML_HIP_Q4_K : FMT;     // (the epilogue knows the K-quant body by Q4_K's name: same rows, same planes out)
+  static_assert(!Q5 || (!TP && !DEFER && !ORD), "the Q5_K body: the fast step on one device");
   constexpr int RW = 2 / SPLIT;         // rows per wave
   constexpr int ROWS = 32 / SPLIT;      // rows per workgroup
   __shared__ __attribute__((aligned(16))) float hv[32];
@@ -540,16 +543,48 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
         rows_terms_q6k<RW>(w6.base, w6.off_qh, la6, row, nchunks * 32, nb, lane, T + (size_t)(wave * RW) * stride, stride);
         __syncthreads();
         if (wave == 0 && lane < ROWS) hv[part * ROWS + lane] = q4k_ordered_sum(T + (size_t)lane * stride, nb);
-        nq_epilogue<FMT, SPLIT, TP, false, true>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
-                                                 (int)blockIdx.x, (int)gridDim.x, tp);
+        nq_epilogue<EF, SPLIT, TP, false, true>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
+                                                (int)blockIdx.x, (int)gridDim.x, tp);
         return;
       }
       rows_partial_q6k<RW>(w6.base, w6.off_qh, la6, row, nchunks * 32, nb, lane, acc);
-      nq_epilogue<FMT, SPLIT, TP>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
-                                  (int)blockIdx.x, (int)gridDim.x, tp);
+      nq_epilogue<EF, SPLIT, TP>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
+                                 (int)blockIdx.x, (int)gridDim.x, tp);
       return;
     }
     constexpr int PRE = 2;
+    if constexpr (Q5) {
+      // the Q5_K body: the same two rounds of pieces requested ahead of the prologue (whole header, one dword of qh per lane), the
+      // rhs staged in ELEMENT order (Q5_K's planes keep the file's order), every row's pieces added in ascending order
+      const PlanesQ5 w5 = planes_q5k(w.q, w.d);
+      Q5KPiece<false> p5[PRE][RW];
+#pragma unroll
+      for (int it = 0; it < PRE; it++) {
+        const int c = it * 64 + lane;
+#pragma unroll
+        for (int r = 0; r < RW; r++) p5[it][r] = q5k_load<false>(w5, (size_t)(row + r), nb, c < nb * 8 ? c : nb * 8 - 1, lane);
+      }
+      if constexpr (QIN == 2)
+        stage_copy_q8k(act, nb, lds_act, sd, sbs, false);
+      else
+        stage_quant_q8k(xin, nb, (unsigned*)lds_act, sd, sbs, false);
+      const ActQ8_K la5{lds_act, sd, sbs, lds_act};
+#pragma unroll
+      for (int r = 0; r < RW; r++) acc[r] = 0.f;
+#pragma unroll
+      for (int it = 0; it < PRE; it++) {
+        const int c = it * 64 + lane;
+        if (c < nb * 8) {  // (a super-block's eight lanes together: the qh exchange stays among live lanes)
+          const Q4KX xx = q4k_loadx<false>(la5, c);
+#pragma unroll
+          for (int r = 0; r < RW; r++) acc[r] += q5k_term<false>(p5[it][r], xx, c, lane);
+        }
+      }
+      rows_partial_q5k_planes<RW, false>(w5, la5, row, nchunks * 32, nb, lane, acc, PRE * 64);
+      nq_epilogue<EF, SPLIT, TP>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
+                                 (int)blockIdx.x, (int)gridDim.x, tp);
+      return;
+    }
     Q4KPiece<false> pw[PRE][RW];
 #pragma unroll
     for (int it = 0; it < PRE; it++) {
@@ -578,8 +613,8 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
       rows_terms_q4k<RW, false>(w.q, (const i32x4*)w.d, la, row, nchunks * 32, nb, lane, Tw, stride, PRE * 64);
       __syncthreads();
       if (wave == 0 && lane < ROWS) hv[part * ROWS + lane] = q4k_ordered_sum(T + (size_t)lane * stride, nb);
-      nq_epilogue<FMT, SPLIT, TP, false, true>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
-                                               (int)blockIdx.x, (int)gridDim.x, tp);
+      nq_epilogue<EF, SPLIT, TP, false, true>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
+                                              (int)blockIdx.x, (int)gridDim.x, tp);
       return;
     }
 #pragma unroll
@@ -597,6 +632,8 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
   } else if constexpr (KQ) {
     if (w6.base != nullptr)
       rows_partial_q6k<RW>(w6.base, w6.off_qh, act, row, nchunks * 32, nb, lane, acc);
+    else if constexpr (Q5)
+      rows_partial_q5k_planes<RW>(planes_q5k(w.q, w.d), act, row, nchunks * 32, nb, lane, acc);
     else
       rows_partial_q4k<RW>(w.q, (const i32x4*)w.d, act, row, nchunks * 32, nb, lane, acc);
   } else if constexpr (QIN == 1) {
@@ -677,8 +714,8 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
       }
     }
   }
-  nq_epilogue<FMT, SPLIT, TP, DEFER>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
-                                     (int)blockIdx.x, (int)gridDim.x, tp);
+  nq_epilogue<EF, SPLIT, TP, DEFER>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
+                                    (int)blockIdx.x, (int)gridDim.x, tp);
 }
 
 // ---- strict order: wo / ffn_down + residual + the next RMSNorm + quantize in ONE launch, every sum in the reference's order ----------
@@ -884,7 +921,8 @@ __global__ __launch_bounds__(128) void k_gateup(Planes wg, Planes wu, typename A
 // for all others' sums, then for its super-block's seven neighbours).  The sums keep the order the gathering epilogue used
 // (nq_epilogue: a chunk = its halves; 64 chunks per round through wave_sum_f32; rounds added in order), so the planes are bit for
 // bit the ones wo used to leave.
-template <bool QOUT, bool ORD = false, bool NORMIN = false>
+// Q5 (a Q5_K body): the same launch over Q5_K rows -- the staged quants in element order, q5k_term's pieces (gemv_core.hpp).
+template <bool QOUT, bool ORD = false, bool NORMIN = false, bool Q5 = false>
 __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, ActQ8_K act, FfnAct fa,
                                                        float* __restrict__ h, int m, int nsb, Q8KExchange ex, signed char* __restrict__ oq,
                                                        float* __restrict__ od, short* __restrict__ obs, signed char* __restrict__ oqp,
@@ -923,10 +961,17 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
       wv[u] = ((const f32x4*)wnorm)[(sb < nsb ? sb : 0) * 64 + lane];
     }
   }
-  Q4KPiece<false> pw[2];
+  static_assert(!Q5 || !ORD, "the Q5_K body has no ordered form");
+  typename std::conditional<Q5, Q5KPiece<false>, Q4KPiece<false>>::type pw[2];
 #pragma unroll
-  for (int r = 0; r < 2; r++)
-    pw[r] = q4k_load<false>(wg.q, (const i32x4*)wg.d, (size_t)(row0 + r < m ? row0 + r : m - 1), nsb, lane < nch ? lane : nch - 1, lane);
+  for (int r = 0; r < 2; r++) {
+    const size_t prow = (size_t)(row0 + r < m ? row0 + r : m - 1);
+    const int pc = lane < nch ? lane : nch - 1;
+    if constexpr (Q5)
+      pw[r] = q5k_load<false>(planes_q5k(wg.q, wg.d), prow, nsb, pc, lane);
+    else
+      pw[r] = q4k_load<false>(wg.q, (const i32x4*)wg.d, prow, nsb, pc, lane);
+  }
   if constexpr (NORMIN) {
     const int nch32 = k / 32, nrounds = (nch32 + 63) / 64;
     // round r of the chunk sums = chunks 64 r .. + 63, one per lane of wave r (lanes past the row add +0.0, as the gather did), rounds
@@ -950,19 +995,22 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
 #pragma unroll
       for (int i = 0; i < 4; i++) xn[i] = (xv[u][i] / rms) * wv[u][i];  // rms_norm.rs:41-45, then the weight (llama2.rs:611)
       const Q8KLane o = q8k_wave_quant(xn, lane);
-      q8k_store_class_major((signed char*)sq + sb * 256, lane, o.packed);
+      if constexpr (Q5)  // (element order: the rhs of Q5_K rows)
+        ((unsigned*)sq)[sb * 64 + lane] = o.packed;
+      else
+        q8k_store_class_major((signed char*)sq + sb * 256, lane, o.packed);
       if ((lane & 3) == 0) sbs[sb * 16 + (lane >> 2)] = (short)o.quad_sum;
       if (lane == 0) sd[sb] = o.d;
     }
   } else {
-    for (int i = threadIdx.x; i < k / 16; i += 1024) sq[i] = act.qp[i];  // (class-major: the rhs of Q4_K rows)
+    for (int i = threadIdx.x; i < k / 16; i += 1024) sq[i] = Q5 ? act.q[i] : act.qp[i];  // (class-major: the rhs of Q4_K rows)
     for (int i = threadIdx.x; i < nsb; i += 1024) sd[i] = act.d[i];
     for (int i = threadIdx.x; i < k / 16; i += 1024) sbs[i] = act.bsums[i];
   }
   __syncthreads();
   const ActQ8_K la{sq, sd, sbs, sq};
   __shared__ float hv[32];
-  if constexpr (ORD) {
+  if constexpr (ORD && !Q5) {
     const int stride = q4k_rec_stride(nsb);
     float* T = (float*)((char*)lds_act + (((size_t)nsb * 292 + 15) & ~(size_t)15));  // rows 0..31: gate, 32..63: up
     float* Tg = T + (size_t)(wave * 2) * stride;
@@ -996,13 +1044,23 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
   // (Round 6, measured and not kept: gate and up rows advancing together with quad-exchanged headers -- four pieces per lane and
   // step, two request rounds instead of four, 48 VGPRs: 17.1 us against 15.8.  Round 4's whole-header form of the same idea: 18.0.)
   float ag[2] = {0.f, 0.f}, au[2];
-  if (lane < nch) {
-    const Q4KX x = q4k_loadx(la, lane);
+  if constexpr (Q5) {  // the Q5_K body: the same passes over element-order planes (a super-block's eight lanes live or dead together)
+    if (lane < nch) {
+      const Q4KX x = q4k_loadx<false>(la, lane);
 #pragma unroll
-    for (int r = 0; r < 2; r++) ag[r] += q4k_term<false>(pw[r], x, lane);
+      for (int r = 0; r < 2; r++) ag[r] += q5k_term<false>(pw[r], x, lane, lane);
+    }
+    rows_partial_q5k_planes<2, false>(planes_q5k(wg.q, wg.d), la, row0, m, nsb, lane, ag, 64);
+    rows_partial_q5k_planes<2, false>(planes_q5k(wu.q, wu.d), la, row0, m, nsb, lane, au);
+  } else {
+    if (lane < nch) {
+      const Q4KX x = q4k_loadx(la, lane);
+#pragma unroll
+      for (int r = 0; r < 2; r++) ag[r] += q4k_term<false>(pw[r], x, lane);
+    }
+    rows_partial_q4k<2, false>(wg.q, (const i32x4*)wg.d, la, row0, m, nsb, lane, ag, 64);
+    rows_partial_q4k<2, false>(wu.q, (const i32x4*)wu.d, la, row0, m, nsb, lane, au);
   }
-  rows_partial_q4k<2, false>(wg.q, (const i32x4*)wg.d, la, row0, m, nsb, lane, ag, 64);
-  rows_partial_q4k<2, false>(wu.q, (const i32x4*)wu.d, la, row0, m, nsb, lane, au);
 #pragma unroll
   for (int r = 0; r < 2; r++) {
     const float g = wave_sum_f32(ag[r]), u = wave_sum_f32(au[r]);

@@ -423,34 +423,55 @@ __device__ __forceinline__ Q4KX q4k_loadx(const ActQ8_K& act, int c) {
 // The exact integer part of piece c (buf_q4_k.rs:212-263): isum = sc_lo * sum(q4 q8 | low nibbles) + sc_hi * sum(q4 q8 | high
 // nibbles), msum = m_lo * bsum_lo + m_hi * bsum_hi; h0 = the header's first dword (d | dmin << 16).  Every Q4_K GEMV kernel
 // (k_gemv_q4_k, k_qkv, k_gemv_res_nq, k_gateup_k_lds) gets its integers from here; crabml_hip_debug_superblock_ints dumps them.
+// The pieces of it that Q5_K shares (q5k_ints below) are functions of their own: the field decode of pair p, the two scaled sums
+// from the nibble halves' dots, and the f32 part of the term.
+struct Q4KFields {
+  int sc_lo, sc_hi, m_lo, m_hi;
+  unsigned h0;
+};
 template <bool HDR_DPP>
-__device__ __forceinline__ void q4k_ints(const Q4KPiece<HDR_DPP>& w, const Q4KX& x, int c, int& isum, int& msum, unsigned& h0) {
-  const int p = (c & 7) >> 1;
+__device__ __forceinline__ Q4KFields q4k_fields(const Q4KPiece<HDR_DPP>& w, int p) {
+  Q4KFields o;
   unsigned h1, h2, h3;
   if constexpr (HDR_DPP) {  // quad_perm broadcasts of dword 0..3
-    h0 = (unsigned)dpp_i<0x00>((int)w.hw);
+    o.h0 = (unsigned)dpp_i<0x00>((int)w.hw);
     h1 = (unsigned)dpp_i<0x55>((int)w.hw);
     h2 = (unsigned)dpp_i<0xAA>((int)w.hw);
     h3 = (unsigned)dpp_i<0xFF>((int)w.hw);
   } else {
-    h0 = (unsigned)w.hdr[0];
+    o.h0 = (unsigned)w.hdr[0];
     h1 = (unsigned)w.hdr[1];
     h2 = (unsigned)w.hdr[2];
     h3 = (unsigned)w.hdr[3];
   }
   const unsigned f = q4k_pair_field(h1, h2, h3, p);
-  const int sc_lo = (int)(f & 63u), sc_hi = (int)((f >> 6) & 63u);
-  const int m_lo = (int)((f >> 12) & 63u), m_hi = (int)(f >> 18);
+  o.sc_lo = (int)(f & 63u), o.sc_hi = (int)((f >> 6) & 63u);
+  o.m_lo = (int)((f >> 12) & 63u), o.m_hi = (int)(f >> 18);
+  return o;
+}
+// (v_mul_i32_i24 / v_mad_i32_i24: every factor is below 2^23 -- |lo|, |hi| <= 16 * 15 * 128 (Q5_K: 16 * 31 * 128), the 6-bit fields,
+// |bsum| <= 16 * 128 -- where a plain 32-bit multiply is a quarter-rate instruction)
+__device__ __forceinline__ void q4k_scaled_sums(const Q4KFields& f, const Q4KX& x, int lo, int hi, int& isum, int& msum) {
+  isum = __mul24(f.sc_lo, lo) + __mul24(f.sc_hi, hi);          // exact (the reference's aux32 lanes hold integers < 2^24)
+  msum = __mul24(f.m_lo, x.bs_lo) + __mul24(f.m_hi, x.bs_hi);  // i32: the intended math of buf_q4_k.rs:238-241
+}
+// the f32 part: d * d8 and dmin * d8, the two conversions' products, one subtraction -- five roundings (the conversions are exact)
+__device__ __forceinline__ float q4k_term_f32(unsigned h0, float d8, int isum, int msum) {
+  const float dd = h2f((unsigned short)(h0 & 0xffff)) * d8;
+  const float dmin = h2f((unsigned short)(h0 >> 16)) * d8;
+  return dd * (float)isum - dmin * (float)msum;
+}
+template <bool HDR_DPP>
+__device__ __forceinline__ void q4k_ints(const Q4KPiece<HDR_DPP>& w, const Q4KX& x, int c, int& isum, int& msum, unsigned& h0) {
+  const Q4KFields f = q4k_fields<HDR_DPP>(w, (c & 7) >> 1);
+  h0 = f.h0;
   int lo = 0, hi = 0;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     lo = __builtin_amdgcn_sdot4(w.qv[i] & 0x0F0F0F0F, x.xl[i], lo, false);
     hi = __builtin_amdgcn_sdot4((w.qv[i] >> 4) & 0x0F0F0F0F, x.xh[i], hi, false);
   }
-  // (v_mul_i32_i24 / v_mad_i32_i24: every factor is below 2^23 -- |lo|, |hi| <= 16 * 15 * 128, the 6-bit fields, |bsum| <= 16 * 128 --
-  // where a plain 32-bit multiply is a quarter-rate instruction)
-  isum = __mul24(sc_lo, lo) + __mul24(sc_hi, hi);          // exact (the reference's aux32 lanes hold integers < 2^24)
-  msum = __mul24(m_lo, x.bs_lo) + __mul24(m_hi, x.bs_hi);  // i32: the intended math of buf_q4_k.rs:238-241
+  q4k_scaled_sums(f, x, lo, hi, isum, msum);
 }
 template <bool HDR_DPP>
 __device__ __forceinline__ float q4k_term(const Q4KPiece<HDR_DPP>& w, const Q4KX& x, int c, int* dbg = nullptr) {
@@ -461,9 +482,7 @@ __device__ __forceinline__ float q4k_term(const Q4KPiece<HDR_DPP>& w, const Q4KX
     dbg[0] = isum;
     dbg[1] = msum;
   }
-  const float dd = h2f((unsigned short)(h0 & 0xffff)) * x.d8;
-  const float dmin = h2f((unsigned short)(h0 >> 16)) * x.d8;
-  return dd * (float)isum - dmin * (float)msum;
+  return q4k_term_f32(h0, x.d8, isum, msum);
 }
 // ---- Q4_K in the reference's order (strict-order device) ---------------------------------------------------------------------
 // buf_q4_k.rs:192-277 keeps EIGHT f32 lanes per row: inside a super-block `aux32[l] += scale * (q8 * q4)` for the elements e of every
@@ -674,50 +693,96 @@ __device__ __forceinline__ void rows_partial_q4k(const i32x4* __restrict__ wq, c
   }
 }
 
-// Q5_K rows (planes qs[n][128] | qh[n][32] | hdr[n][16], the reference's own block contents: buf_q5_k.rs:13-21) against a Q8_K
-// activation vector: Q4_K's mapping (lane = one 16-byte qs piece j of a super-block: pair p = j / 2, positions 16 (j & 1) .. +16)
-// plus the piece's 16 bytes of qh, whose bits 2p / 2p + 1 are the fifth bit of the low / high nibbles (buf_q5_k.rs:246-262).
-// Levels 0 .. 31 fit the signed bytes of v_dot4; scales, minimums and the float part are Q4_K's.  Not a tuned path (three
-// 16-byte loads per lane and piece): Q5_K runs as per-op segments.
+// Q5_K rows (planes qs[n][128] | qh[n][32] | hdr[n][16], the reference's own block contents in element order: buf_q5_k.rs:13-21)
+// against a Q8_K activation vector in element order (q4k_loadx<false>): Q4_K's mapping -- lane = one 16-byte qs piece j of a
+// super-block, pair p = j / 2, half h = j & 1 = positions 16 h .. +16 of the pair's 32 -- plus the fifth bits: bits 2p / 2p + 1 of qh
+// byte 16 h + b belong to the low / high nibble of qs byte b of the piece (buf_q5_k.rs:246-262).  A super-block's 32 bytes of qh are
+// requested ONCE: lane j of its eight takes dword j, and the group hands them round in registers -- the neighbouring quad's dword by
+// row_shl:4 / row_shr:4, then quad_perm broadcasts of both, each lane keeping the four of its half (dwords 4 h .. 4 h + 3).  The
+// exchange never leaves the aligned 8-lane group, whose lanes are live or dead together (pieces come in eights; a clamped dead
+// group takes the row's last super-block as a whole: dword lane & 7 of it).  Levels 0 .. 31 fit the signed bytes of v_dot4; the
+// field decode, the scaled sums and the f32 part are Q4_K's own functions.  |isum| <= 2 * 63 * 16 * 31 * 128 = 7999488 < 2^23: the
+// 24-bit multiplies of q4k_scaled_sums and the exact f32 conversion of q4k_term_f32 hold as they do for Q4_K.
+struct PlanesQ5 {
+  const i32x4* qs;
+  const unsigned* qh;
+  const i32x4* hdr;
+};
+// a Q5_K buffer from its first two planes (off_scale = n * 128 exactly, common.hpp: the header plane follows the n * 32 bytes of qh)
+__device__ __forceinline__ PlanesQ5 planes_q5k(const void* qs, const void* qh) {
+  const size_t n128 = (size_t)((const char*)qh - (const char*)qs);
+  return PlanesQ5{(const i32x4*)qs, (const unsigned*)qh, (const i32x4*)((const char*)qh + n128 / 4)};
+}
+template <bool HDR_DPP>
+struct Q5KPiece {
+  Q4KPiece<HDR_DPP> w4;  // the qs piece and the header, as Q4_K's kernels take them
+  unsigned qh;           // dword lane & 7 of the super-block's qh
+};
+template <bool HDR_DPP>
+__device__ __forceinline__ Q5KPiece<HDR_DPP> q5k_load(const PlanesQ5& w, size_t row, int nsb, int c, int lane) {
+  Q5KPiece<HDR_DPP> o;
+  o.w4 = q4k_load<HDR_DPP>(w.qs, w.hdr, row, nsb, c, lane);
+  o.qh = __builtin_nontemporal_load(w.qh + (row * nsb + (c >> 3)) * 8 + (lane & 7));
+  return o;
+}
+// (all lanes of the piece's 8-lane group take part: see above)
+template <bool HDR_DPP>
+__device__ __forceinline__ void q5k_ints(const Q5KPiece<HDR_DPP>& w, const Q4KX& x, int c, int lane, int& isum, int& msum, unsigned& h0) {
+  const int p = (c & 7) >> 1, h = c & 1;
+  const Q4KFields f = q4k_fields<HDR_DPP>(w.w4, p);
+  h0 = f.h0;
+  const int up = dpp_i<0x104>((int)w.qh), dn = dpp_i<0x114>((int)w.qh);  // row_shl:4 / row_shr:4: lane + 4 / lane - 4 of the row
+  const int nb = (lane & 4) ? dn : up;                                   // the other quad of the group: lane ^ 4
+  const bool own = ((lane >> 2) & 1) == h;                               // this lane's quad holds dwords 4 h ..
+  // (every exchange is evaluated by every lane, outside any lane-dependent branch; the select comes after)
+  const int a0 = dpp_i<0x00>((int)w.qh), a1 = dpp_i<0x55>((int)w.qh), a2 = dpp_i<0xAA>((int)w.qh), a3 = dpp_i<0xFF>((int)w.qh);
+  const int b0 = dpp_i<0x00>(nb), b1 = dpp_i<0x55>(nb), b2 = dpp_i<0xAA>(nb), b3 = dpp_i<0xFF>(nb);
+  const unsigned hq[4] = {(unsigned)(own ? a0 : b0), (unsigned)(own ? a1 : b1), (unsigned)(own ? a2 : b2), (unsigned)(own ? a3 : b3)};
+  int lo = 0, hi = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned q = (unsigned)w.w4.qv[i], hb = hq[i] >> (2 * p);
+    const unsigned l5 = (q & 0x0F0F0F0Fu) | ((hb & 0x01010101u) << 4);
+    const unsigned h5 = ((q >> 4) & 0x0F0F0F0Fu) | (((hb >> 1) & 0x01010101u) << 4);
+    lo = __builtin_amdgcn_sdot4((int)l5, x.xl[i], lo, false);
+    hi = __builtin_amdgcn_sdot4((int)h5, x.xh[i], hi, false);
+  }
+  q4k_scaled_sums(f, x, lo, hi, isum, msum);
+}
+template <bool HDR_DPP>
+__device__ __forceinline__ float q5k_term(const Q5KPiece<HDR_DPP>& w, const Q4KX& x, int c, int lane) {
+  int isum, msum;
+  unsigned h0;
+  q5k_ints<HDR_DPP>(w, x, c, lane, isum, msum, h0);
+  return q4k_term_f32(h0, x.d8, isum, msum);
+}
+// a lane adds its pieces in ascending order (then the caller's wave tree), as rows_partial_q4k does; c0: pieces below it were taken
+// by the caller (a multiple of 64)
+template <int R, bool HDR_DPP = true>
+__device__ __forceinline__ void rows_partial_q5k_planes(const PlanesQ5& w, const ActQ8_K& act, int row0, int m, int nsb, int lane,
+                                                        float acc[R], int c0 = 0, int rs = 1) {
+  if (c0 == 0) {
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = 0.f;
+  }
+  const int nchunks = nsb * 8;
+  for (int c = c0 + lane; c < nchunks; c += 64) {
+    Q5KPiece<HDR_DPP> pw[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
+      pw[r] = q5k_load<HDR_DPP>(w, (size_t)row, nsb, c, lane);
+    }
+    const Q4KX x = q4k_loadx<false>(act, c);
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] += q5k_term<HDR_DPP>(pw[r], x, c, lane);
+  }
+}
+// the per-op kernel's entry (k_gemv_q5_k): the same pieces on the same lanes, added in the same order
 template <int R>
 __device__ __forceinline__ void rows_partial_q5k(const char* __restrict__ w, size_t off_qh, const ActQ8_K& act, int row0, int m,
                                                  int nsb, int lane, float acc[R]) {
-  const size_t n = off_qh / 128;  // blocks in the tensor
-  const i32x4* wq = (const i32x4*)w;
-  const i32x4* wqh = (const i32x4*)(w + off_qh);
-  const i32x4* wh = (const i32x4*)(w + off_qh + n * 32);
-#pragma unroll
-  for (int r = 0; r < R; r++) acc[r] = 0.f;
-  const int nchunks = nsb * 8;
-  for (int c = lane; c < nchunks; c += 64) {
-    const int sb = c >> 3, j = c & 7, p = j >> 1, h = j & 1;
-    const Q4KX x = q4k_loadx<false>(act, c);
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      const size_t blk = (size_t)(row0 + r < m ? row0 + r : m - 1) * nsb + sb;
-      const i32x4 qv = __builtin_nontemporal_load(wq + blk * 8 + j);
-      const i32x4 hv = __builtin_nontemporal_load(wqh + blk * 2 + h);
-      const i32x4 hd = __builtin_nontemporal_load(wh + blk);
-      const unsigned f = q4k_pair_field((unsigned)hd[1], (unsigned)hd[2], (unsigned)hd[3], p);
-      const int sc_lo = (int)(f & 63u), sc_hi = (int)((f >> 6) & 63u);
-      const int m_lo = (int)((f >> 12) & 63u), m_hi = (int)(f >> 18);
-      int lo = 0, hi = 0;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const unsigned q = (unsigned)qv[i], hb = (unsigned)hv[i] >> (2 * p);
-        const unsigned l5 = (q & 0x0F0F0F0Fu) | ((hb & 0x01010101u) << 4);
-        const unsigned h5 = ((q >> 4) & 0x0F0F0F0Fu) | (((hb >> 1) & 0x01010101u) << 4);
-        lo = __builtin_amdgcn_sdot4((int)l5, x.xl[i], lo, false);
-        hi = __builtin_amdgcn_sdot4((int)h5, x.xh[i], hi, false);
-      }
-      const int isum = sc_lo * lo + sc_hi * hi;
-      const int msum = m_lo * x.bs_lo + m_hi * x.bs_hi;
-      const unsigned h0 = (unsigned)hd[0];
-      const float dd = h2f((unsigned short)(h0 & 0xffff)) * x.d8;
-      const float dmin = h2f((unsigned short)(h0 >> 16)) * x.d8;
-      acc[r] += dd * (float)isum - dmin * (float)msum;
-    }
-  }
+  rows_partial_q5k_planes<R, true>(planes_q5k(w, w + off_qh), act, row0, m, nsb, lane, acc);
 }
 
 // Q6_K rows (planes ql[n][128] | qh[n][64] | scales[n][16] | d[n] f16; common.hpp) against a Q8_K activation vector:
@@ -781,12 +846,14 @@ __device__ __forceinline__ void rows_partial_q6k(const char* __restrict__ w, siz
 }
 
 // R rows of a weight matrix in format FMT against its activation planes (ActQ8_0 for Q4_0 / Q8_0, ActQ8_K for
-// Q4_K); `wd` is the format's second plane (f16 scales / 16-byte headers), `nu` the blocks per row
+// Q4_K / Q5_K); `wd` is the format's second plane (f16 scales / 16-byte headers / Q5_K's qh), `nu` the blocks per row
 template <int FMT, int R, class ACT>
 __device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
                                          int row0, int m, int nu, int lane, float acc[R], int rs = 1) {
   if constexpr (FMT == CRABML_HIP_Q4_K)
     rows_partial_q4k<R>(wq, (const i32x4*)wd, act, row0, m, nu, lane, acc, 0, nullptr, rs);
+  else if constexpr (FMT == CRABML_HIP_Q5_K)  // (wd: the qh plane, planes_q5k)
+    rows_partial_q5k_planes<R>(planes_q5k(wq, wd), act, row0, m, nu, lane, acc, 0, rs);
   else
     rows_partial<FMT, R>(wq, wd, act, row0, m, nu, lane, acc, rs);
 }
@@ -796,6 +863,10 @@ struct ActOf {
 };
 template <>
 struct ActOf<CRABML_HIP_Q4_K> {
+  typedef ActQ8_K type;
+};
+template <>
+struct ActOf<CRABML_HIP_Q5_K> {
   typedef ActQ8_K type;
 };
 template <>

@@ -230,7 +230,7 @@ def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional
     """All-`wtype` synthetic Llama weights with GGUF tensor names (model.rs:228-283); norms are F32
     (the loader dequantizes them, model.rs:267-282).  tp > 1: the tensors get one rank's LOCAL shard shapes
     (what crabml_amd.tp.shard_model would cut; random bytes either way -- for timing one rank of a large model
-    without materialising all of it).  k_m_mix (with wtype = Q4_K): the tensor-type recipe of llama.cpp's Q4_K_M
+    without materialising all of it).  k_m_mix (with wtype = Q4_K or Q5_K): the tensor-type recipe of llama.cpp's Q4_K_M / Q5_K_M
     files -- attn_v and ffn_down in Q6_K on the `use_more_bits` layers, output.weight in Q6_K -- i.e. different
     GGML types inside one layer (all with the Q8_K rhs).  arch = "qwen2" (default: the shape's): blk.N.attn_{q,k,v}.bias as F32
     N(0, 1) with a few channels per vector 20-60x larger (real Qwen2 k biases reach the hundreds), from a generator of their own:

@@ -22,7 +22,7 @@ from crabml_amd import synth
 
 ap = argparse.ArgumentParser()
 ap.add_argument("gguf", nargs="?")
-ap.add_argument("--synth", default=None, help="SHAPE:TYPE, e.g. tiny-gqa:Q4_0, llama3-8b:Q4_K_M, qwen2.5-7b:Q4_0, gemma-2b:Q8_0")
+ap.add_argument("--synth", default=None, help="SHAPE:TYPE, e.g. tiny-gqa:Q4_0, llama3-8b:Q4_K_M, llama3-8b:Q5_K_M, qwen2.5-7b:Q4_0, gemma-2b:Q8_0")
 ap.add_argument("--prompt", default="1,365,400,282,7,9,11,13")
 ap.add_argument("--steps", type=int, default=32)
 ap.add_argument("--seq-len", type=int, default=0)
@@ -37,8 +37,8 @@ path = a.gguf
 tmp = None
 if a.synth:
     shape_name, typ = a.synth.split(":")
-    k_m = typ.upper() == "Q4_K_M"
-    model = synth.build_model(synth.SHAPES[shape_name], synth.Q4_K if k_m else synth.TYPE_BY_NAME[typ], seed=8, k_m_mix=k_m)
+    k_m = typ.upper() in ("Q4_K_M", "Q5_K_M")  # llama.cpp's recipes: the body type with attn_v / ffn_down / output.weight in Q6_K
+    model = synth.build_model(synth.SHAPES[shape_name], synth.TYPE_BY_NAME[typ.upper()[:4]] if k_m else synth.TYPE_BY_NAME[typ], seed=8, k_m_mix=k_m)
     tmp = tempfile.TemporaryDirectory()
     path = os.path.join(tmp.name, "model.gguf")
     synth.write_gguf(model, path)

@@ -44,8 +44,8 @@ def runner_rate(model, mode, strict, n):
 
 def row(spec, steps=128):
     shape, fmt = spec.split(":")
-    mix = fmt == "Q4_K_M"
-    model = synth.build_model(synth.SHAPES[shape], synth.Q4_K if mix else synth.TYPE_BY_NAME[fmt], seed=1, k_m_mix=mix)
+    mix = fmt in ("Q4_K_M", "Q5_K_M")
+    model = synth.build_model(synth.SHAPES[shape], synth.TYPE_BY_NAME[fmt[:4]] if mix else synth.TYPE_BY_NAME[fmt], seed=1, k_m_mix=mix)
     gb = model.gemv_weight_bytes_per_token() / 1e9
     out = {"GB": gb}
     dev = ca.HipTensorDevice(0)
