@@ -138,6 +138,7 @@ struct TapRec {
 struct TapField {
   uint32_t qtype = CRABML_HIP_F32;
   size_t cols = 0, rows = 1;
+  int qp_of = -1;  // >= 0: no copy of its own -- the class-major plane (cols bytes per row) inside the Q8_K planes field `qp_of` copied
 };
 
 // What a context runs, as one value: decide_step makes it at create, every reader goes through c->plan, and
@@ -468,6 +469,18 @@ int export_fields(crabml_hip_device* dev, const TapRec& t, const std::vector<uin
     if (f == plan_field) {  // host words, not a device buffer
       src = (const uint8_t*)t.plan;
       out_bytes = (size_t)nwords * sizeof(int32_t);
+    }
+    if (fld[f].qp_of >= 0) {  // rows of Q8_K planes -> their class-major planes, as the device holds them
+      const int pf = fld[f].qp_of;
+      const ActLayout al = act_layout(CRABML_HIP_Q8_K, fld[f].cols);
+      out_bytes = fld[f].rows * fld[f].cols;
+      if (t.len[pf] == 0) continue;
+      if (t.len[pf] != fld[f].rows * al.total || at + out_bytes > dst_bytes)
+        CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "%s: field %d has an unexpected size", t.hook, f);
+      for (size_t r = 0; r < fld[f].rows; r++) memcpy(o + at + r * fld[f].cols, host.data() + t.off[pf] + r * al.total + al.off_p, fld[f].cols);
+      dir[f].bytes = out_bytes;
+      at += align_up(out_bytes, 8);
+      continue;
     }
     if (out_bytes == 0) continue;
     if (fld[f].cols == 0) {
@@ -1556,11 +1569,12 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     return f16w && gemm_f16w_takes(dev, w, c->qt) && (c->qt != CRABML_HIP_Q8_K || k % 256 == 0);
   };
   XhHolds xh;
-  auto rows_to_f16 = [&](const crabml_hip_buf* w, const void* act, int k) {
+  auto rows_to_f16 = [&](const crabml_hip_buf* w, const void* act, int k) -> bool {  // true: pf_xh was made here
     const int order = gemm_f16w_order(w->dtype);
-    if (xh.holds(act, order)) return;
+    if (xh.holds(act, order)) return false;
     launch_rows_to_f16(st, c->qt, w->dtype, act, B, (size_t)k, c->pf_xh, ovf);
     xh.set(act, order);
+    return true;
   };
   // ... written by the kernel that quantizes the rows when the GEMM that reads them next is the f16 one (f16w_rows.hpp: the same
   // bits as k_rows_to_f16 from the finished planes, one launch fewer per GEMM; A/B: CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS)
@@ -1580,20 +1594,33 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     return planes;
   };
   // defer (nullable): a GEMM cut into k pieces may leave the sum of its pieces to the row kernel that consumes `out` (pf_split holds them)
-  // fc / xh_field (prefill tap only): the launch form as taken, and the tap field B' goes to as this GEMM finds it
+  // fc / xh_field / kword (prefill tap only): the launch form as taken, the tap field B' goes to as this GEMM finds it (xh_if_made: only
+  // where this GEMM had to re-make pf_xh), and the plan word that says which kernel the matrix took (CRABML_HIP_PFPLAN_KERNEL_*)
   TapRec& tap = c->pftap;
   auto gemm = [&](const crabml_hip_buf* w, int m, int k, const void* act, float* out, int* defer = nullptr, F16wForce* fc = nullptr,
-                  int xh_field = -1) -> int {
+                  int xh_field = -1, int kword = -1, bool xh_if_made = false) -> int {
+    auto took = [&](int kernel) {
+      if (kword >= 0) tap.note(kword, kernel);
+    };
     if (defer) *defer = 0;
     if (g.flags & CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS) defer = nullptr;  // (A/B: every reduce its own launch)
     if (takes_f16w(w, k)) {
-      rows_to_f16(w, act, k);
-      if (xh_field >= 0) CH_TRY(tap.copy(c, xh_field, c->pf_xh, B * (size_t)k * 2));
+      const bool made = rows_to_f16(w, act, k);
+      if (xh_field >= 0 && (made || !xh_if_made)) CH_TRY(tap.copy(c, xh_field, c->pf_xh, B * (size_t)k * 2));
       const size_t mm = (size_t)m;
-      if (launch_gemm_f16w(dev, &w, &mm, 1, (size_t)k, c->pf_xh, B, &out, c->pf_split, c->pf_split_floats, nullptr, nullptr, defer, nullptr, fc))
+      if (launch_gemm_f16w(dev, &w, &mm, 1, (size_t)k, c->pf_xh, B, &out, c->pf_split, c->pf_split_floats, nullptr, nullptr, defer, nullptr, fc)) {
+        took(1);
         return 0;
+      }
     }
     if (!strict) {
+      if (kword >= 0 && tap.armed()) {  // launch_gemv's own first question, asked here so that the plan can say what it answered
+        if (B >= 16 && launch_gemm_mfma(dev, w, m, k, act, B, out, nullptr, nullptr, !gemm_exact_hook)) {
+          took(2);
+          return 0;
+        }
+        took(3);
+      }
       return launch_gemv(dev, w, m, k, act, B, out, nullptr, !gemm_exact_hook);
     }
     // strict order: the Q4_0 / Q8_0 / Q4_1 MFMA GEMM scales its exact integer tiles block by block in the reference's scalar
@@ -1689,6 +1716,8 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       a = quant_rows(c->pf_xn, dim, c->pf_act_dim, c->wq[l]);
     }
     tap.note(l, CRABML_HIP_PFPLAN_NORM_KERNEL, fuse_norm ? norm_kernel : 0);
+    const bool xn_stored = !fuse_norm || fuse_k;  // (k_norm_f32_rows and k_norm_quant_rows_k leave the f32 norm in pf_xn)
+    CH_TRY(PT(tl && xn_stored, CRABML_HIP_PFTAP_N1_XN, c->pf_xn, xb_dim));
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_N1_X, c->pf_x, xb_dim));
     CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_N1_ACT, c->pf_act_dim, B * ald.total));
     F16wForce fc_qkv{}, fc_wo{}, fc_gu{}, fc_down{};  // (all zero: the launcher's own choice; read back for the plan)
@@ -1702,11 +1731,15 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       float* outs[3] = {c->pf_q, c->pf_k, c->pf_v};
       qkv_done = launch_gemm_f16w(dev, ws, ms, 3, (size_t)dim, c->pf_xh, B, outs, c->pf_split, c->pf_split_floats, nullptr, nullptr, nullptr,
                                   nullptr, tl ? &fc_qkv : nullptr);
+      if (qkv_done)
+        for (int kw : {CRABML_HIP_PFPLAN_KERNEL_Q, CRABML_HIP_PFPLAN_KERNEL_K, CRABML_HIP_PFPLAN_KERNEL_V}) tap.note(l, kw, 1);
     }
     if (!qkv_done) {
-      CH_TRY(gemm(c->wq[l], dim, dim, a, c->pf_q, nullptr, tl ? &fc_qkv : nullptr, tl ? CRABML_HIP_PFTAP_N1_XH : -1));
-      CH_TRY(gemm(c->wk[l], kv_dim, dim, a, c->pf_k));
-      CH_TRY(gemm(c->wv[l], kv_dim, dim, a, c->pf_v));
+      CH_TRY(gemm(c->wq[l], dim, dim, a, c->pf_q, nullptr, tl ? &fc_qkv : nullptr, tl ? CRABML_HIP_PFTAP_N1_XH : -1,
+                  tl ? CRABML_HIP_PFPLAN_KERNEL_Q : -1));
+      CH_TRY(gemm(c->wk[l], kv_dim, dim, a, c->pf_k, nullptr, nullptr, -1, tl ? CRABML_HIP_PFPLAN_KERNEL_K : -1));
+      CH_TRY(gemm(c->wv[l], kv_dim, dim, a, c->pf_v, nullptr, nullptr, tl ? CRABML_HIP_PFTAP_N1_XH_V : -1,
+                  tl ? CRABML_HIP_PFPLAN_KERNEL_V : -1, true));
     }
     tap.note(l, CRABML_HIP_PFPLAN_QKV_ONE, qkv_done ? 1 : 0);
     note_form(l, CRABML_HIP_PFPLAN_QKV_F, fc_qkv);
@@ -1728,7 +1761,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_ATTN_ACT, c->pf_act_dim, B * ald.total));
     int wo_parts = 0;
     CH_TRY(gemm(c->wo[l], dim, dim, a, c->pf_tmp, fuse_norm ? &wo_parts : nullptr, tl ? &fc_wo : nullptr,
-                tl ? CRABML_HIP_PFTAP_ATTN_XH : -1));  // llama2.rs:600
+                tl ? CRABML_HIP_PFTAP_ATTN_XH : -1, tl ? CRABML_HIP_PFPLAN_KERNEL_WO : -1));  // llama2.rs:600
     tap.note(l, CRABML_HIP_PFPLAN_WO_PARTS, wo_parts);
     note_form(l, CRABML_HIP_PFPLAN_WO_F, fc_wo);
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_WO_TMP, c->pf_tmp, xb_dim));
@@ -1740,6 +1773,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       norm_rows((const float*)c->rms_ffn[l]->ptr, 1e-5f);  // llama2.rs:611
       a = quant_rows(c->pf_xn, dim, c->pf_act_dim, c->gate[l]);
     }
+    CH_TRY(PT(tl && xn_stored, CRABML_HIP_PFTAP_N2_XN, c->pf_xn, xb_dim));
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_N2_X, c->pf_x, xb_dim));
     CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_N2_ACT, c->pf_act_dim, B * ald.total));
     bool gu_done = false;  // llama2.rs:620-630
@@ -1774,10 +1808,13 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
         if (hq.xh) XhHolds::swap(c);
         xh.set(hq.xh ? c->pf_act_hid : nullptr, hq_order);
       }
+      if (gu_done)
+        for (int kw : {CRABML_HIP_PFPLAN_KERNEL_GATE, CRABML_HIP_PFPLAN_KERNEL_UP}) tap.note(l, kw, 1);
     }
     if (!gu_done) {
-      CH_TRY(gemm(c->gate[l], hidden, dim, a, c->pf_g, nullptr, tl ? &fc_gu : nullptr, tl ? CRABML_HIP_PFTAP_N2_XH : -1));
-      CH_TRY(gemm(c->up[l], hidden, dim, a, c->pf_u));
+      CH_TRY(gemm(c->gate[l], hidden, dim, a, c->pf_g, nullptr, tl ? &fc_gu : nullptr, tl ? CRABML_HIP_PFTAP_N2_XH : -1,
+                  tl ? CRABML_HIP_PFPLAN_KERNEL_GATE : -1));
+      CH_TRY(gemm(c->up[l], hidden, dim, a, c->pf_u, nullptr, nullptr, -1, tl ? CRABML_HIP_PFPLAN_KERNEL_UP : -1));
     }
     tap.note(l, CRABML_HIP_PFPLAN_GU_ONE, gu_done ? 1 : 0);
     tap.note(l, CRABML_HIP_PFPLAN_H_DONE, h_done);
@@ -1805,11 +1842,12 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       a = c->pf_act_hid;
     } else {
       k_gateup_epi<<<(unsigned)(((size_t)B * hidden + 255) / 256), 256, 0, st>>>(c->pf_g, c->pf_u, c->ffn_act, c->pf_g, (int)(B * hidden));
+      CH_TRY(PT(tl, CRABML_HIP_PFTAP_HID_H, c->pf_g, xb_hid));
       a = quant_rows(c->pf_g, hidden, c->pf_act_hid, c->down[l]);
     }
     CH_TRY(PT(tl && c->qt != CRABML_HIP_F32, CRABML_HIP_PFTAP_HID_ACT, c->pf_act_hid, B * alh.total));
     CH_TRY(gemm(c->down[l], dim, hidden, a, c->pf_tmp, down_deferred ? &down_parts : nullptr, tl ? &fc_down : nullptr,
-                tl ? CRABML_HIP_PFTAP_HID_XH : -1));  // llama2.rs:633-636
+                tl ? CRABML_HIP_PFTAP_HID_XH : -1, tl ? CRABML_HIP_PFPLAN_KERNEL_DOWN : -1));  // llama2.rs:633-636
     tap.note(l, CRABML_HIP_PFPLAN_DOWN_PARTS, down_deferred ? down_parts : 0);
     note_form(l, CRABML_HIP_PFPLAN_DOWN_F, fc_down);
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_DOWN_TMP, c->pf_tmp, xb_dim));
@@ -1825,6 +1863,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     CH_HIP(dev, hipMemcpyAsync(c->x, c->pf_x + (B - 1) * (size_t)dim, (size_t)dim * 4, hipMemcpyDeviceToDevice, st));
     CH_TRY(PT(true, CRABML_HIP_PFTAP_LAST_X, c->x, (size_t)dim * 4));
     launch_norm_f32(st, c->x, nullptr, (const float*)c->rms_final->ptr, dim, g.rms_norm_eps, c->xn, half);
+    CH_TRY(PT(true, CRABML_HIP_PFTAP_CLS_XN, c->xn, (size_t)dim * 4));
     const void* act = c->xn;
     if (c->out_qt != CRABML_HIP_F32) {
       launch_quantize_act(st, c->out_qt, c->xn, (size_t)dim, c->act_dim);
@@ -2945,9 +2984,17 @@ int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* c, const uint32_t* to
   CH_LIVE(dev);
   CH_USE(dev);
   CH_FLUSH(dev);
-  if (c->tp > 1 || dev->strict_order || c->ext_kv || !(c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1) ||
-      !(c->wtype == CRABML_HIP_Q4_0 || c->wtype == CRABML_HIP_Q8_0 || c->wtype == CRABML_HIP_Q4_1))
-    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama debug_prefill_tap: only Q4_0 / Q8_0 / Q4_1 layers of the fast prompt pass on one device");
+  const bool rows_8 = (c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1) &&
+                      (c->wtype == CRABML_HIP_Q4_0 || c->wtype == CRABML_HIP_Q8_0 || c->wtype == CRABML_HIP_Q4_1);
+  // Q8_K rows: every layer matrix Q4_K, Q5_K or Q6_K (the *_K_M mixes), the classifier one of them too
+  bool rows_k = c->qt == CRABML_HIP_Q8_K;
+  auto k_body = [](const crabml_hip_buf* w) { return w->dtype == CRABML_HIP_Q4_K || w->dtype == CRABML_HIP_Q5_K || w->dtype == CRABML_HIP_Q6_K; };
+  for (size_t l = 0; rows_k && l < c->cfg.n_layers; l++)
+    for (const crabml_hip_buf* w : {c->wq[l], c->wk[l], c->wv[l], c->wo[l], c->gate[l], c->up[l], c->down[l]}) rows_k = rows_k && k_body(w);
+  rows_k = rows_k && k_body(c->output);
+  if (c->tp > 1 || dev->strict_order || c->ext_kv || !(rows_8 || rows_k))
+    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
+            "llama debug_prefill_tap: only Q4_0 / Q8_0 / Q4_1 and Q4_K / Q5_K / Q6_K layers (the *_K_M mixes) of the fast prompt pass on one device");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_prefill_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   CH_TRY(prefill_check(c, tokens, n));
   const size_t chunk = prefill_chunk_rows(c);
@@ -2960,12 +3007,23 @@ int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* c, const uint32_t* to
   fld[CRABML_HIP_PFTAP_HID_ACT] = TapField{qt, hidden, n};
   for (int f : {CRABML_HIP_PFTAP_N1_XH, CRABML_HIP_PFTAP_ATTN_XH, CRABML_HIP_PFTAP_N2_XH, CRABML_HIP_PFTAP_HID_XH}) fld[f].qtype = CRABML_HIP_F16;
   if (cls_q) fld[CRABML_HIP_PFTAP_CLS_ACT] = TapField{cq, dim, 1};
-  // the scratch area, in the device's layout: ten (n, dim) f32 buffers, three sets of up to 7 k pieces, k and v, g and u, three sets of
-  // act_dim planes and one of act_hid, their f16 planes, the last row and the classifier's input; every field 256-aligned
+  if (qt == CRABML_HIP_Q8_K) {
+    fld[CRABML_HIP_PFTAP_N1_QP] = TapField{CRABML_HIP_Q8_K, dim, n, CRABML_HIP_PFTAP_N1_ACT};
+    fld[CRABML_HIP_PFTAP_ATTN_QP] = TapField{CRABML_HIP_Q8_K, dim, n, CRABML_HIP_PFTAP_ATTN_ACT};
+    fld[CRABML_HIP_PFTAP_N2_QP] = TapField{CRABML_HIP_Q8_K, dim, n, CRABML_HIP_PFTAP_N2_ACT};
+    fld[CRABML_HIP_PFTAP_HID_QP] = TapField{CRABML_HIP_Q8_K, hidden, n, CRABML_HIP_PFTAP_HID_ACT};
+  }
+  if (cq == CRABML_HIP_Q8_K) fld[CRABML_HIP_PFTAP_CLS_QP] = TapField{CRABML_HIP_Q8_K, dim, 1, CRABML_HIP_PFTAP_CLS_ACT};
+  fld[CRABML_HIP_PFTAP_N1_XH_V].qtype = CRABML_HIP_F16;
+  // the scratch area, in the device's layout: twelve (n, dim) f32 buffers (the two f32 norms among them), three sets of up to 7 k
+  // pieces, k and v, g, u and h, three sets of act_dim planes and one of act_hid, their f16 planes (v's own among them), the last row,
+  // the final norm's row and the classifier's input; every field 256-aligned.  The class-major planes are part of the Q8_K planes in
+  // the area (a row's blocks and its class-major plane together are never larger than its planes: dst needs no more for them)
   const size_t adb = act_layout(qt, dim).total, ahb = act_layout(qt, hidden).total;
   const size_t cls_raw = cls_q ? act_layout(cq, dim).total : dim * 4;
-  const size_t raw_cap = (10 + 21) * n * dim * 4 + 2 * n * kv_dim * 4 + 2 * n * hidden * 4 + 3 * n * adb + n * ahb + 3 * n * dim * 2 +
-                         n * hidden * 2 + dim * 4 + cls_raw + 256 * (size_t)CRABML_HIP_PFTAP_FIELDS + CRABML_HIP_PFTAP_PLAN_WORDS * sizeof(int32_t);
+  const size_t raw_cap = (12 + 21) * n * dim * 4 + 2 * n * kv_dim * 4 + 3 * n * hidden * 4 + 3 * n * adb + n * ahb + 4 * n * dim * 2 +
+                         n * hidden * 2 + 2 * dim * 4 + cls_raw + 256 * (size_t)CRABML_HIP_PFTAP_FIELDS +
+                         CRABML_HIP_PFTAP_PLAN_WORDS * sizeof(int32_t);
   if (need) *need = raw_cap;
   if (!dst) return 0;
   if (dst_bytes < raw_cap) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_prefill_tap: dst holds %zu bytes, %zu needed", dst_bytes, raw_cap);

@@ -568,11 +568,12 @@ PYBIND11_MODULE(_host, m) {
       .def("debug_prefill_tap", [](HipLlamaRunner& r, const std::vector<uint32_t>& tokens, size_t layer) {
         static const char* names[CRABML_HIP_PFTAP_FIELDS] = {
             "in.x", "in.tmp", "in.parts", "n1.x", "n1.act", "n1.xh", "q", "k", "v", "qr", "attn", "attn.act", "attn.xh", "wo.tmp", "wo.parts",
-            "n2.x", "n2.act", "n2.xh", "g", "u", "hid.act", "hid.xh", "down.tmp", "down.parts", "down.x", "last.x", "cls.act", "plan"};
+            "n2.x", "n2.act", "n2.xh", "g", "u", "hid.act", "hid.xh", "down.tmp", "down.parts", "down.x", "last.x", "cls.act", "plan",
+            "n1.xn", "n2.xn", "hid.h", "n1.xh.v", "cls.xn", "n1.act.qp", "attn.act.qp", "n2.act.qp", "hid.act.qp", "cls.act.qp"};
         static const char* words[CRABML_HIP_PFTAP_PLAN_WORDS] = {
             "n_cu", "rows", "pos0", "f16w", "recomputed", "norm_kernel", "in_parts", "qkv_one", "gu_one", "h_done", "wo_parts", "down_parts",
             "qkv_F", "qkv_T", "qkv_ksplit", "wo_F", "wo_T", "wo_ksplit", "gu_F", "gu_T", "gu_ksplit", "down_F", "down_T", "down_ksplit",
-            "attn_kernel"};
+            "attn_kernel", "kernel_q", "kernel_k", "kernel_v", "kernel_wo", "kernel_gate", "kernel_up", "kernel_down"};
         HipLlamaRunner::Tap t;
         {
           py::gil_scoped_release rel;

@@ -224,9 +224,10 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* ctx, size_t token, size_t pos
  * launch of that layer left them: stream-ordered device-to-device copies into a scratch area (allocated on the first prefill tap of a
  * context, grown when a longer pass is tapped) placed between the launches, brought to the host after the pass.  n larger than the
  * context's chunk capacity (prefill_chunk, else 1024, never more than seq_len): CRABML_HIP_BAD_INPUT -- multi-chunk situations are made
- * by calling prefill / forward first.  Serves Q4_0 / Q8_0 / Q4_1 layers (Q8_0 / Q8_1 rows) on one fast device, Llama and Qwen2, f16 and
- * f32 cache; K-quant layers, tensor-parallel ranks, the strict-order device and a context on the runner's own KV cache return
- * CRABML_HIP_NOT_IMPLEMENTED.  dst / dir / need as for crabml_hip_llama_debug_tap; a field the pass did not produce has bytes = 0.
+ * by calling prefill / forward first.  Serves Q4_0 / Q8_0 / Q4_1 layers (Q8_0 / Q8_1 rows) and Q8_K-row passes
+ * whose layer matrices are Q4_K, Q5_K or Q6_K (the Q4_K_M / Q5_K_M mixes and a Q6_K classifier included) on one fast device, Llama and
+ * Qwen2, f16 and f32 cache; every other format (Q8_K weights, Q2_K, Q3_K, Q5_0, Q5_1, F32), tensor-parallel ranks, the strict-order
+ * device and a context on the runner's own KV cache return CRABML_HIP_NOT_IMPLEMENTED.  dst / dir / need as for crabml_hip_llama_debug_tap; a field the pass did not produce has bytes = 0.
  * f32 fields are [n][cols] floats.  Quantized rows come back as n rows of blocks in the reference's byte layout (as debug_tap).  The
  * XH fields are the rows' pre-scaled f16 planes B' ([n][cols] halfs, in the GEMM's k-slot order: within a 32-element block the order
  * is the kernel's own business) as the GEMM that reads them next finds them; 0 bytes in an int8 / GEMV pass.  PARTS fields are
@@ -261,7 +262,22 @@ enum {
   CRABML_HIP_PFTAP_LAST_X = 25,    /* any `layer`: the row the final norm reads (f32, dim), */
   CRABML_HIP_PFTAP_CLS_ACT = 26,   /*   what the classifier reads (one row of the classifier's row type; f32 for an F32 / F16 classifier) */
   CRABML_HIP_PFTAP_PLAN = 27,      /* CRABML_HIP_PFTAP_PLAN_WORDS int32 words (below) */
-  CRABML_HIP_PFTAP_FIELDS = 28
+  /* the fields below: 0 bytes where the arm that makes them did not run */
+  CRABML_HIP_PFTAP_N1_XN = 28,     /* pf_xn after the layer's first norm (f32, dim): written by k_norm_f32_rows (separate launches) and by
+                                      k_norm_quant_rows_k; 0 bytes behind the Q8_0 / Q8_1 row kernels, which never store it */
+  CRABML_HIP_PFTAP_N2_XN = 29,     /*   ... after the FFN norm */
+  CRABML_HIP_PFTAP_HID_H = 30,     /* pf_g after k_gateup_epi (f32, hidden): h over g, in the arm where g and u were stored (PLAN_H_DONE == 0,
+                                      no SiLU * mul + quantize row kernel) */
+  CRABML_HIP_PFTAP_N1_XH_V = 31,   /* B' as v's GEMM reads it, where that GEMM re-made pf_xh (another k-slot order than q's: a Q6_K attn_v
+                                      behind a Q4_K attn_q; or q took no f16 GEMM at all: a Q5_K attn_q) */
+  CRABML_HIP_PFTAP_CLS_XN = 32,    /* the final norm's f32 row (dim) */
+  CRABML_HIP_PFTAP_N1_QP = 33,     /* Q8_K rows only: the class-major plane of the N1_ACT planes, [n][dim] bytes (byte 4 (e % 8) + e / 8 of a
+                                      32-group holds element e), */
+  CRABML_HIP_PFTAP_ATTN_QP = 34,   /*   of ATTN_ACT, */
+  CRABML_HIP_PFTAP_N2_QP = 35,     /*   of N2_ACT, */
+  CRABML_HIP_PFTAP_HID_QP = 36,    /*   of HID_ACT ([n][hidden]), */
+  CRABML_HIP_PFTAP_CLS_QP = 37,    /*   of CLS_ACT (a Q8_K classifier row; [dim]) */
+  CRABML_HIP_PFTAP_FIELDS = 38
 };
 /* the words of CRABML_HIP_PFTAP_PLAN, written by prefill_chunk_pass where it decides (0 where the tapped layer never got there) */
 enum {
@@ -272,8 +288,9 @@ enum {
   CRABML_HIP_PFPLAN_RECOMPUTED = 4,  /* 1: the tapped pass is the int8 recomputation after an f16 pass raised the overflow flag */
   CRABML_HIP_PFPLAN_NORM_KERNEL = 5, /* the layer's FIRST norm launch (attention norm), noted in the arm that launches it: 0 separate launches
                                         (k_res_epi, k_norm_f32_rows, the quantizer), 1 k_norm_quant_rows, 2 k_norm_quant_rows_h, 3 k_norm_quant_rows_w
-                                        (4 k_norm_quant_rows_k: K-quant rows, which the tap refuses, so never returned).  The FFN norm's kernel is
-                                        not recorded: it goes through the same arms with wo's pending output and pieces */
+                                        4 k_norm_quant_rows_k (Q8_K rows, from 192 rows of a pass whose dim is whole super-blocks: residual add, the k
+                                        pieces, RMSNorm and the wave-per-super-block Q8_K quantizer as one launch).  The FFN norm's kernel is not
+                                        recorded: it goes through the same arms with wo's pending output and pieces */
   CRABML_HIP_PFPLAN_IN_PARTS = 6,    /* k pieces the layer's first norm launch added to the pending ffn_down output */
   CRABML_HIP_PFPLAN_QKV_ONE = 7,     /* 1: q | k | v as one GEMM launch */
   CRABML_HIP_PFPLAN_GU_ONE = 8,      /* 1: gate | up as one GEMM launch */
@@ -293,7 +310,14 @@ enum {
   CRABML_HIP_PFPLAN_DOWN_T = 22,
   CRABML_HIP_PFPLAN_DOWN_KSPLIT = 23,
   CRABML_HIP_PFPLAN_ATTN_KERNEL = 24,/* 1 k_attn_flash_rows, 2 the exact tile kernel, 3 the exact long-row kernels, 4 k_attn per (head, row) */
-  CRABML_HIP_PFTAP_PLAN_WORDS = 25
+  CRABML_HIP_PFPLAN_KERNEL_Q = 25,   /* the kernel each matrix of the layer took: 1 k_gemm_f16w, 2 the int8 matrix-core GEMM (k_gemm_mfma*), 3 the */
+  CRABML_HIP_PFPLAN_KERNEL_K = 26,   /*   wave-per-row GEMV, row by row.  One word per matrix: a launch_gemm_f16w that declines falls through to */
+  CRABML_HIP_PFPLAN_KERNEL_V = 27,   /*   launch_gemv, which takes the int8 GEMM from 16 rows where the format has one.  PLAN_F16W says what the */
+  CRABML_HIP_PFPLAN_KERNEL_WO = 28,  /*   pass allows, these words what ran (a Q5_K matrix: always 3; the Q6_K matrices of the same layer: 1) */
+  CRABML_HIP_PFPLAN_KERNEL_GATE = 29,
+  CRABML_HIP_PFPLAN_KERNEL_UP = 30,
+  CRABML_HIP_PFPLAN_KERNEL_DOWN = 31,
+  CRABML_HIP_PFTAP_PLAN_WORDS = 32
 };
 int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* ctx, const uint32_t* tokens, size_t n, size_t layer, float* logits, void* dst,
                                        size_t dst_bytes, crabml_hip_tap_entry_t* dir, size_t* need);

@@ -31,7 +31,41 @@ silu_mul_interval) or one the project already states for that kernel:
   the tail        last layer: pf_x = x + ffn_down (one rounding); the final norm reads row B - 1 of it; the classifier's planes pass
                   the interval check; the logits are within row_dots' bound.
 
-Host cost: `Sample` picks weight rows and prompt rows of the GEMM checks before any device value is looked at (None = every row)."""
+Host cost: `Sample` picks weight rows and prompt rows of the GEMM checks before any device value is looked at (None = every row).
+
+Q8_K-ROW PASSES (Q4_K / Q5_K / Q6_K layer matrices, the Q4_K_M / Q5_K_M mixes).  Which kernel a matrix took is READ from the plan
+(kernel_q .. kernel_down: 1 k_gemm_f16w, 2 the int8 matrix-core GEMM, 3 the wave-per-row GEMV), never inferred: in a Q5_K_M layer v
+takes the f16 GEMM while q takes the GEMV, and plan["f16w"] says 1 either way.  With the f32 rows the tap stores (n1.xn / n2.xn, hid.h,
+cls.xn) no K launch needs an interval excuse:
+
+  norm launch     both arms (k_norm_f32_rows + quantizer; k_norm_quant_rows_k): x as above; xn inside norm_interval(x_out); the Q8_K
+                  planes = the reference quantizer of the STORED xn, byte for byte (d with its sign, the first holder of the maximum,
+                  ties away from zero, the sixteen 16-element sums); the class-major plane = the permutation of q.
+  B'              f16(f32(q d)) with d the plane's f32 -- TWO roundings, restated as such (not f16 of the float64 product) --, as a
+                  sorted multiset per super-block (b_groups of the reading weight's format; n1.xh.v against attn_v's).  The k-slot
+                  order itself is held by the GEMM check, which multiplies by A' in element order.
+  f16 GEMM        GEMV_REL sum |A' B'| with A' = f16(n c1 - c2), c1 = f16(d sc), c2 = f16(dmin m) (Q4_K), f16((q - 32) f16(d sc)) (Q6_K):
+                  weight_operands of tests/test_hip_f16w_gemm.py.
+  row-by-row GEMV fused_step_ref.row_dots / q5k_step_ref.row_dots: (8 nsb + C_K) U sum A over the kernels' pieces.
+  int8 GEMM       k_gemm_mfma_q4k, per super-block and output: the integers isum = sum_j sc_j dot_j (|isum| <= 256 * 15 * 127 * 63 = 3.1e7,
+                  past 2^24: its conversion to f32 ROUNDS) and msum = sum_j m_j bsum_j (<= 8 * 63 * 32 * 127 = 2.0e6: exact), then
+                  F += (d_w d8) (float)isum - (dmin_w d8) (float)msum with -ffp-contract=off: 2 conversions (one of which can round), 2
+                  scale products, 2 products, 1 subtraction, 1 add into the accumulator = 8 operations, at most 7 roundings.  With
+                  A_sb = |d_w d8 isum| + |dmin_w d8 msum| the term is off by at most 3 U |d_w d8 isum| + 3 U |dmin_w d8 msum| + U |term|
+                  <= 4 U A_sb (1 + 3 U), and the nsb adds (in super-block order) by U times a partial sum of |terms| each:
+                      |f32 - exact| <= (nsb + 4) U sum_sb A_sb (1 + small).
+                  k_gemm_mfma_q6k: v = (float)(sum_g sc_g dot_g - 32 sum_g sc_g bsum_g) (|v| < 2^25: may round), F += (d_w d8) v: 1
+                  conversion, 1 scale product, 1 product, 1 add: (nsb + 3) U sum_sb |d_w d8 v|.
+                  row_dots' bound is (8 nsb + C_K) U sum over the 8 PIECES of a super-block of A_piece, and sum_pieces A_piece >= A_sb
+                  (the pieces' integers add up to the super-block's: triangle inequality on both parts).  8 nsb + 3 >= 2 (nsb + 4) - 3
+                  for every nsb >= 1, so row_dots' bound DOMINATES the derived one with a factor of at least 11 / 5 (nsb = 1) and
+                  towards 8 for long rows: it is used for the int8 GEMM as it stands (C_K not raised); no new constant.  It stays
+                  a sharp check of what it must see: one quant off by a step moves a dot by |w_i| d8, one sub-block's minimum term by
+                  dmin m |bsum| d8 -- both orders of magnitude above (8 nsb + 3) 6e-8 of the row's sum A.
+  SiLU * mul      h_done == 0: g and u within their GEMM bounds; hid.h (pf_g after k_gateup_epi) inside silu_mul_interval(g, 0, u, 0) of the
+                  stored g and u; planes = the reference quantizer of the stored h, byte for byte.  h_done == 1 as above.  h_done == 2 (the
+                  row quantizer inside the GEMM) exists for Q8_0 / Q8_1 rows only: a Q8_K tap that says 2 fails.
+  the tail        cls.xn inside norm_interval(last.x); the classifier's planes = the reference quantizer of cls.xn byte for byte."""
 import functools
 from dataclasses import dataclass
 
@@ -40,12 +74,17 @@ import numpy as np
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import fused_step_ref as R
+from tests import q5k_step_ref as Q5
 from tests.fused_step_ref import U, Result, check_f32
 from tests.helpers import GEMV_REL
 from tests.test_hip_f16w_gemm import b_groups, weight_operands
 
 FLASH_ROWS_REL = 1.5e-3  # tests/test_hip_flash_attention.py: k_attn_flash_rows against float64 on the same f16 inputs, of max|out|
 ATTN_FLASH_ROWS, ATTN_TILE, ATTN_LONG_ROWS, ATTN_PER_ROW = 1, 2, 3, 4  # CRABML_HIP_PFPLAN_ATTN_KERNEL
+KERNEL_F16W, KERNEL_INT8, KERNEL_GEMV = 1, 2, 3  # CRABML_HIP_PFPLAN_KERNEL_*
+KERNEL_WORD = {"attn_q": "kernel_q", "attn_k": "kernel_k", "attn_v": "kernel_v", "attn_output": "kernel_wo", "ffn_gate": "kernel_gate",
+               "ffn_up": "kernel_up", "ffn_down": "kernel_down"}
+F16W_FMT = {synth.Q4_0: "Q4_0", synth.Q8_0: "Q8_0", synth.Q4_1: "Q4_1", synth.Q4_K: "Q4_K", synth.Q6_K: "Q6_K"}  # formats k_gemm_f16w takes
 
 
 @dataclass
@@ -86,17 +125,28 @@ def rows_of(tap, name, cols):
 
 
 def act_rows(tap, name):
-    """the tapped planes of every row -> [parse_act per row]"""
+    """the tapped planes of every row -> [parse_act per row]; a Q8_K set with its class-major plane (field name + ".qp", which the Q4_K
+    int8 kernels read) put back in element order as "qp_q" (fused_step_ref.tap_act)"""
     qt = tap["qtype"][name]
     n = tap["plan"]["rows"] if name != "cls.act" else 1
     raw = np.asarray(tap[name]).reshape(n, -1)
-    return [R.parse_act(raw[r], qt) for r in range(n)]
+    acts = [R.parse_act(raw[r], qt) for r in range(n)]
+    if qt == o.Q8_K and name + ".qp" in tap:
+        qp = np.ascontiguousarray(tap[name + ".qp"]).view(np.int8).astype(np.int64).reshape(n, -1)
+        for r, a in enumerate(acts):
+            a["qp_q"] = R.from_class_major(qp[r]).reshape(a["q"].shape)
+    return acts
 
 
 def b_prime(acts):
-    """B' = f16(q d) of the rows' blocks, element order: (f16 bits [B, k], float64 values)"""
+    """B' of the rows' blocks, element order: (f16 bits [B, k], float64 values).  Q8_0 / Q8_1 rows: f16(q d), one rounding (7 bits x
+    11 bits is exact in f32).  Q8_K rows: d is an f32, so f16(f32(q d)) -- the product rounded to f32, THEN to f16: two roundings, and
+    not the same value as f16 of the exact product wherever the f32 rounding lands on an f16 tie"""
     with np.errstate(over="ignore"):
-        h = np.stack([(a["q"] * a["d"][:, None]).reshape(-1) for a in acts]).astype(np.float16)
+        if acts[0]["qt"] == o.Q8_K:
+            h = np.stack([(a["q"].astype(np.float32) * a["d"].astype(np.float32)[:, None]).reshape(-1) for a in acts]).astype(np.float16)
+        else:
+            h = np.stack([(a["q"] * a["d"][:, None]).reshape(-1) for a in acts]).astype(np.float16)
     return h.view(np.uint16), h.astype(np.float64)
 
 
@@ -120,17 +170,34 @@ def norm_intervals(x, w, eps, n):
     return tuple(np.stack([p[i] for p in parts]) for i in range(3))
 
 
-def check_xh(res, tap, xh_name, act_name, ctx):
+def check_xh(res, tap, xh_name, act_name, ctx, model=None, wname=None):
+    """wname: the weight whose GEMM reads this B' (its format decides the slot groups: a 32-element block, a K-quant super-block)"""
     if xh_name not in tap:
         return
     acts = act_rows(tap, act_name)
     bits, _ = b_prime(acts)
     b, k = bits.shape
+    fmt = "Q4_0"
+    if acts[0]["qt"] == o.Q8_K:
+        fmt = F16W_FMT.get(_w(model, wname).typ)
+        if fmt not in ("Q4_K", "Q6_K"):
+            res.fails.append(f"{ctx} {res.launch}: {xh_name} is present, but {wname} is of a format the f16 GEMM does not take")
+            return
     got = np.asarray(tap[xh_name], dtype=np.uint16).reshape(b, k)
-    same = np.all(b_groups(got, "Q4_0", b, k) == b_groups(bits, "Q4_0", b, k), axis=2)
+    same = np.all(b_groups(got, fmt, b, k) == b_groups(bits, fmt, b, k), axis=2)
     if not same.all():
         r, blk = np.argwhere(~same)[0]
         res.fails.append(f"{ctx} {res.launch}: {xh_name} row {r} block {blk}: B' is not f16(q d) of the tapped planes ({int((~same).sum())} blocks)")
+
+
+def check_in_interval(res, got, lo, hi, what, ctx):
+    """every row of the stored f32 values lies inside [lo, hi] (as an f32 value: distance from the middle against the half width)"""
+    got = np.asarray(got, dtype=np.float64)
+    if not np.all(np.isfinite(got)):
+        res.fails.append(f"{ctx} {res.launch}: {what}: non-finite values")
+        return
+    mid, half = (lo + hi) / 2, (hi - lo) / 2
+    res.ratio(np.abs(got - mid).reshape(-1), half.reshape(-1) + 1e-37, what, ctx)
 
 
 def check_norm(tap, model, l, which, ctx):
@@ -160,32 +227,48 @@ def check_norm(tap, model, l, which, ctx):
             res.fails.append(f"{ctx} {res.launch}: x changed with nothing pending ({int((~same).sum())} elements)")
     name = which + ".act"
     lo, hi, ref = norm_intervals(x1, wn, eps, dim)
-    R.QuantIntervals(lo, hi, ref, tap["qtype"][name]).check(tap[name], res, "act_dim", ctx)
-    check_xh(res, tap, which + ".xh", name, ctx)
+    if which + ".xn" in tap:  # the f32 norm is stored (k_norm_f32_rows, k_norm_quant_rows_k): no interval excuse
+        xn = rows_of(tap, which + ".xn", dim)
+        check_in_interval(res, xn, lo, hi, "xn", ctx)
+        check_planes_of(res, tap, name, xn, "act_dim (of the stored xn)", ctx)
+    elif tap["qtype"][name] == o.Q8_K:
+        res.fails.append(f"{ctx} {res.launch}: a Q8_K-row pass stores {which}.xn in both arms; the tap has none")
+    else:
+        R.QuantIntervals(lo, hi, ref, tap["qtype"][name]).check(tap[name], res, "act_dim", ctx)
+    first, second = ("attn_q", "attn_v") if which == "n1" else ("ffn_gate", None)
+    check_xh(res, tap, which + ".xh", name, ctx, model, f"blk.{l}.{first}.weight")
+    if second:
+        check_xh(res, tap, which + ".xh.v", name, ctx, model, f"blk.{l}.{second}.weight")
     return res
 
 
 # ---- the GEMMs ----
-XH_OF = {"n1.act": "n1.xh", "attn.act": "attn.xh", "n2.act": "n2.xh", "hid.act": "hid.xh"}
+def kernel_of(tap, wname):
+    """the kernel the plan says this matrix took (KERNEL_*); 0 where the tapped layer never got there"""
+    return tap["plan"][KERNEL_WORD[wname.split(".")[2]]]
 
 
-def gemm_reference(tap, model, wname, act_name, sample=None, drop_last_block=False):
-    """(exact [rows, m], bound, prompt rows, weight rows) of W . planes for the pass's form (plan["f16w"])"""
+def gemm_reference(tap, model, wname, act_name, sample=None, drop_last_block=False, wrong=None):
+    """(exact [rows, m], bound, prompt rows, weight rows) of W . planes for the kernel the plan names for this matrix.
+    drop_last_block / wrong: a kernel that is subtly wrong (the checker's own tests; wrong: fused_step_ref / q5k_step_ref k_pieces)"""
     t = _w(model, wname)
     m, k = t.shape
     acts = act_rows(tap, act_name)
     pr = np.arange(len(acts)) if sample is None else sample.prows(len(acts))
     wr = np.arange(m) if sample is None else sample.wrows(m)
     acts = [acts[r] for r in pr]
-    if tap["plan"]["f16w"] and XH_OF[act_name] in tap:  # (the f16 GEMM read B'; otherwise the int8 kernels read the planes)
-        fmt = {synth.Q4_0: "Q4_0", synth.Q8_0: "Q8_0", synth.Q4_1: "Q4_1"}[t.typ]
-        ap = weight_operands(np.ascontiguousarray(t.data).view(np.uint8).reshape(-1), fmt, list(wr), k)[0]
+    kern = kernel_of(tap, wname)
+    assert kern in (KERNEL_F16W, KERNEL_INT8, KERNEL_GEMV), (wname, tap["plan"])
+    if kern == KERNEL_F16W:  # (the f16 GEMM read B'; otherwise the int8 kernels read the planes)
+        assert wrong is None
+        ap = weight_operands(np.ascontiguousarray(t.data).view(np.uint8).reshape(-1), F16W_FMT[t.typ], list(wr), k)[0]
         _, bp = b_prime(acts)
         if drop_last_block:
             bp = bp.copy()
-            bp[:, -32:] = 0.0
+            bp[:, -synth.BLOCK_ELEMS[t.typ]:] = 0.0
         return bp @ ap.T, GEMV_REL * (np.abs(bp) @ np.abs(ap).T) + 1e-30, pr, wr
-    e, b = R.row_dots_many(t, acts, wr, drop_last_block=drop_last_block)
+    with Q5.q5k_rows():  # (Q5_K rows through q5k_step_ref; every other format dispatches back)
+        e, b = R.row_dots_many(t, acts, wr, drop_last_block=drop_last_block, wrong=wrong)
     return e, b + 1e-30, pr, wr
 
 
@@ -356,12 +439,13 @@ def check_attention(tap, kv_after, model, l, form, ctx):
                                  f"({int((~same).sum())} of {same.size} differ)")
                 break
     check_planes_of(res, tap, "attn.act", got, "act_attn", ctx)
-    check_xh(res, tap, "attn.xh", "attn.act", ctx)
+    check_xh(res, tap, "attn.xh", "attn.act", ctx, model, f"blk.{l}.attn_output.weight")
     return res
 
 
 def check_planes_of(res, tap, name, values, what, ctx):
-    """the tapped planes are the reference quantizer of rows we hold, byte for byte"""
+    """the tapped planes are the reference quantizer of rows we hold, byte for byte (a Q8_K set: d with its sign, the quants, the sixteen
+    16-element sums); its class-major plane (name + ".qp") the permutation of its q"""
     qt = tap["qtype"][name]
     raw = np.asarray(tap[name]).reshape(values.shape[0], -1)
     for r in range(values.shape[0]):
@@ -370,6 +454,17 @@ def check_planes_of(res, tap, name, values, what, ctx):
             i = int(np.flatnonzero(exp != raw[r])[0])
             res.fails.append(f"{ctx} {res.launch}: {what} row {r} differs from the reference quantizer at byte {i} (block {i // synth.BLOCK_BYTES[qt]})")
             return
+    if qt == o.Q8_K:
+        if name + ".qp" not in tap:
+            res.fails.append(f"{ctx} {res.launch}: {what}: the Q8_K planes came without their class-major plane")
+            return
+        qp = np.ascontiguousarray(tap[name + ".qp"]).view(np.int8).reshape(values.shape[0], -1)
+        for r in range(values.shape[0]):
+            a = R.parse_act(raw[r], qt)
+            n0 = len(res.fails)
+            R.check_q8k_own(res, a, qp[r], f"{what} row {r}", ctx)
+            if len(res.fails) > n0:
+                return
 
 
 # ---- wo / ffn_down ----
@@ -396,12 +491,22 @@ def check_gateup(tap, model, l, ctx, sample=None, twin=None):
     hidden = model.shape.hidden
     h_done = tap["plan"]["h_done"]
     qt = tap["qtype"]["hid.act"]
+    if qt == o.Q8_K and h_done == 2:
+        res.fails.append(f"{ctx} gate|up: h_done == 2 (the row quantizer inside the GEMM) does not exist for Q8_K rows")
+        return res
     if h_done == 0:
         for nm, wn in (("g", "ffn_gate"), ("u", "ffn_up")):
             check_gemm(res, tap, model, f"blk.{l}.{wn}.weight", "n2.act", nm, None, nm, ctx, sample)
         g, u = np.asarray(tap["g"], dtype=np.float64), np.asarray(tap["u"], dtype=np.float64)
         lo, hi, ref = R.silu_mul_interval(g, 0.0, u, 0.0)
-        R.QuantIntervals(lo, hi, ref, qt).check(tap["hid.act"], res, "act_hid", ctx)
+        if "hid.h" in tap:  # k_gateup_epi left h as f32 (over g): no interval excuse
+            h = rows_of(tap, "hid.h", hidden)
+            check_in_interval(res, h, lo.reshape(h.shape), hi.reshape(h.shape), "h", ctx)
+            check_planes_of(res, tap, "hid.act", h, "act_hid (of the stored h)", ctx)
+        elif qt == o.Q8_K:
+            res.fails.append(f"{ctx} gate|up: a Q8_K-row pass that leaves g and u stores hid.h; the tap has none")
+        else:
+            R.QuantIntervals(lo, hi, ref, qt).check(tap["hid.act"], res, "act_hid", ctx)
     else:
         src = tap if h_done == 1 else twin
         if src is None:
@@ -421,7 +526,7 @@ def check_gateup(tap, model, l, ctx, sample=None, twin=None):
         # (as an f32 value inside the hull: distance from its middle against its half width)
         check_f32(res, hs.reshape(-1), ((lo + hi) / 2).reshape(-1), ((hi - lo) / 2).reshape(-1) + 1e-37, "h", ctx)
         check_planes_of(res, tap, "hid.act", h, "act_hid (of the stored h)", ctx)
-    check_xh(res, tap, "hid.xh", "hid.act", ctx)
+    check_xh(res, tap, "hid.xh", "hid.act", ctx, model, f"blk.{l}.ffn_down.weight")
     return res
 
 
@@ -435,9 +540,17 @@ def check_tail(tap, model, l, ctx):
         if not np.array_equal(last.view(np.uint32), want.view(np.uint32)):
             res.fails.append(f"{ctx} {res.launch}: the final norm did not read row B - 1 of pf_x")
     lo, hi, ref = R.norm_interval(last, _f32(model, "output_norm.weight"), s.rms_eps, s.dim)
-    R.QuantIntervals(lo, hi, ref, tap["qtype"]["cls.act"]).check(tap["cls.act"], res, "cls.act", ctx)
+    if "cls.xn" in tap:  # the final norm's f32 row is stored: no interval excuse
+        xn = np.asarray(tap["cls.xn"], dtype=np.float32).reshape(1, -1)
+        check_in_interval(res, xn, lo[None, :], hi[None, :], "cls.xn", ctx)
+        check_planes_of(res, tap, "cls.act", xn, "cls.act (of the stored cls.xn)", ctx)
+    elif tap["qtype"]["cls.act"] == o.Q8_K:
+        res.fails.append(f"{ctx} {res.launch}: a Q8_K classifier row comes with cls.xn; the tap has none")
+    else:
+        R.QuantIntervals(lo, hi, ref, tap["qtype"]["cls.act"]).check(tap["cls.act"], res, "cls.act", ctx)
     t = model.tensors["output.weight"] if "output.weight" in model.tensors else model.tensors["token_embd.weight"]
-    e, b = R.row_dots(t, R.parse_act(tap["cls.act"], tap["qtype"]["cls.act"]))
+    with Q5.q5k_rows():
+        e, b = R.row_dots(t, act_rows(tap, "cls.act")[0])
     check_f32(res, tap["logits"], e, b + 1e-30, "logits", ctx)
     return res
 

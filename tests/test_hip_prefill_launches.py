@@ -8,9 +8,9 @@ float64 restatement of what it computes FROM THE BYTES IT READ, within bounds de
 K / V caches of every layer equal, bit for bit, those of a twin runner's plain prefill of the same tokens (the tap moves nothing); and
 each case asserts from the launch plan -- written by the enqueue code where it decides -- that the path it is named for was taken.
 
-Not pinned here (stated, not hidden): K-quant (Q8_K row) passes -- the K-quant DECODE step is pinned launch by launch in
-tests/test_hip_fused_k_launches.py, the prompt pass of those formats is not --, tensor-parallel ranks and the strict device (bit-exact
-against the oracle: tests/test_hip_prefill.py).  What the cases were seen to leave of their bounds on a device: profiles/prefill_launch_pins.md and
+K-quant (Q8_K row) passes -- Q4_K, Q5_K, Q6_K layers and the Q4_K_M / Q5_K_M mixes -- are pinned the same way, through this file's
+run_case, in tests/test_hip_prefill_k_launches.py.  Not pinned here (stated, not hidden): Gemma passes, Q8_K / Q2_K / Q3_K / Q5_0 / Q5_1 /
+F32 weights, tensor-parallel ranks and the strict device (bit-exact against the oracle: tests/test_hip_prefill.py).  What the cases were seen to leave of their bounds on a device: profiles/prefill_launch_pins.md and
 tests/golden/prefill_launch_pins_observed.json (evidence only; the gates are the derived bounds)."""
 import numpy as np
 import pytest
@@ -38,8 +38,9 @@ def tokens_of(model, n, salt=0):
     return [(7 * i + 3 + 13 * salt) % model.shape.vocab for i in range(n)]
 
 
-def run_case(ca, key, model, seq, kv_f16, n, layers, setup=None, flags=0, chunk=0, attn_long_from=0, sample=None):
-    """-> {layer: the tapped pass's launch plan}"""
+def run_case(ca, key, model, seq, kv_f16, n, layers, setup=None, flags=0, chunk=0, attn_long_from=0, sample=None, rec=None):
+    """-> {layer: the tapped pass's launch plan, with the names of the fields the tap returned under "fields"}.  rec: where the observed
+    ratios go (default: this file's record)"""
     dev = ca.HipTensorDevice(0)
     conf, w = synth.to_hip(model, dev)
     mk = lambda extra=0: ca.HipLlamaRunner(conf, w, dev, seq, kv_f16, extra_flags=flags | extra, attn_long_from=attn_long_from, prefill_chunk=chunk)
@@ -64,7 +65,7 @@ def run_case(ca, key, model, seq, kv_f16, n, layers, setup=None, flags=0, chunk=
         before = (r.debug_kv(layer, False, kv_f16), r.debug_kv(layer, True, kv_f16))
         tap = r.debug_prefill_tap(toks, layer)
         assert r.kv_cache_len() == pos0 + n == twin.kv_cache_len(), ctx
-        plan = plans[layer] = tap["plan"]
+        plan = plans[layer] = dict(tap["plan"], fields=frozenset(k for k in tap if k not in ("plan", "qtype", "logits")))
         assert (plan["rows"], plan["pos0"]) == (n, pos0), (ctx, plan)
         # the tap moves nothing: logits and every layer's cache are the plain prefill's, bit for bit
         assert np.array_equal(tap["logits"].view(np.uint32), want.view(np.uint32)), f"{ctx}: the tapped pass's logits differ from prefill's"
@@ -83,7 +84,7 @@ def run_case(ca, key, model, seq, kv_f16, n, layers, setup=None, flags=0, chunk=
         res = P.check_pass(tap, toks, before, after, model, layer, form, ctx, sample, other)
         for name, rr in res.items():
             print(f"{ctx} {name}: error / bound {rr.worst:.3f} excused {rr.excused}")
-        record(f"{key}/L{layer}/n{n}/p{pos0}", res)
+        (rec or record)(f"{key}/L{layer}/n{n}/p{pos0}", res)
         fails += P.failures(res)
     assert not fails, "\n".join(fails[:40])
     return plans
@@ -295,7 +296,8 @@ def error_kind(ca, call):
 
 def test_tap_rejects_what_it_does_not_serve(ca):
     """BAD_INPUT for a pass longer than one chunk and for a layer the model does not have; NOT_IMPLEMENTED on the strict device, on a
-    tensor-parallel rank and for K-quant layers, as the decode tap.  (An ext_kv context is refused by the same test of the hook; no
+    tensor-parallel rank and for formats it does not serve (Q2_K layers: Q8_K rows, but no restated kernel).  A Q4_K runner's tap
+    succeeds and advances the cache by the pass.  (An ext_kv context is refused by the same test of the hook; no
     HipLlamaRunner owns one, so it is not tried here.)  A refused tap leaves the context as it was."""
     BAD_INPUT, NOT_IMPLEMENTED = 5, 9  # crabml_hip_status
     from crabml_amd import tp as tp_mod
@@ -314,8 +316,13 @@ def test_tap_rejects_what_it_does_not_serve(ca):
     tconf, tw = synth.to_hip(tp_mod.shard_model(model, 2, 0, True), dev)
     rank = ca.HipLlamaRunner(tconf, tw, dev, 64, True, True, True, 2, 0)
     assert error_kind(ca, lambda: rank.debug_prefill_tap(tokens_of(model, 8), 0)) == NOT_IMPLEMENTED  # a tensor-parallel rank
-    kq = synth.build_model(synth.SHAPES["tiny-gqa"], synth.Q4_K, seed=51)
+    kq = synth.build_model(synth.SHAPES["tiny-gqa"], synth.Q2_K, seed=51)
     kconf, kw = synth.to_hip(kq, dev)
     kr = ca.HipLlamaRunner(kconf, kw, dev, 64, True)
-    assert error_kind(ca, lambda: kr.debug_prefill_tap(tokens_of(kq, 40), 0)) == NOT_IMPLEMENTED  # K-quant layers
+    assert error_kind(ca, lambda: kr.debug_prefill_tap(tokens_of(kq, 40), 0)) == NOT_IMPLEMENTED  # a format the tap does not serve
     assert strict.kv_cache_len() == rank.kv_cache_len() == kr.kv_cache_len() == 0
+    k4 = synth.build_model(synth.SHAPES["tiny-gqa"], synth.Q4_K, seed=51)
+    k4conf, k4w = synth.to_hip(k4, dev)
+    k4r = ca.HipLlamaRunner(k4conf, k4w, dev, 64, True)
+    tap = k4r.debug_prefill_tap(tokens_of(k4, 40), 0)  # K-quant layers are served
+    assert tap["plan"]["rows"] == 40 and k4r.kv_cache_len() == 40
