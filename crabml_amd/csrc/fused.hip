@@ -150,7 +150,7 @@ struct StepPlan {
   // ---- the segment forms
   bool norm_epi = false;       // Fused5: RMSNorm + quantize run in the wo / ffn_down epilogue (tp > 1: over a P2P group or in the dry run,
                                // where the epilogue hosts the collective too)
-  bool norm_epi_k = false;     // the same for Q4_K / Q5_K layers (Q8_K planes out of the epilogue)
+  bool norm_epi_k = false;     // the same for Q4_K / Q5_K / Q6_K layers (Q8_K planes out of the epilogue)
   // the hop-free norm of the fast step (Q4_0 / Q8_0 layers, one GPU): wo quantizes x * w_norm block by block and leaves 1 / rms to
   // the gate/up launch (RmsTail, gemv_core.hpp) -- no in-launch gather.  Off: CRABML_HIP_LLAMA_EXACT_NORM, strict order, tp.
   bool defer_norm = false;
@@ -410,10 +410,16 @@ NqOrdKFn nq_ord_k_kernel(int split, int qin) {
   });
   return fn;
 }
-// ... and the forms of k_gateup_k_lds<QOUT, ORD, NORMIN, Q5> that exist (NORMIN writes planes and has no ordered form; nor has a Q5_K body)
+// ... and the forms of k_gateup_k_lds<QOUT, ORD, NORMIN, BODY> that exist (NORMIN writes planes and has no ordered form; nor has a Q5_K
+// or a Q6_K body)
 typedef decltype(&k_gateup_k_lds<false>) GateupKFn;
-GateupKFn gateup_k_kernel(bool qout, bool ord, bool normin, bool q5 = false) {
-  if (q5) return normin ? k_gateup_k_lds<true, false, true, true> : qout ? k_gateup_k_lds<true, false, false, true> : k_gateup_k_lds<false, false, false, true>;
+template <int BODY>
+GateupKFn gateup_k_body_kernel(bool qout, bool normin) {
+  return normin ? k_gateup_k_lds<true, false, true, BODY> : qout ? k_gateup_k_lds<true, false, false, BODY> : k_gateup_k_lds<false, false, false, BODY>;
+}
+GateupKFn gateup_k_kernel(bool qout, bool ord, bool normin, int body = CRABML_HIP_Q4_K) {
+  if (body == CRABML_HIP_Q5_K) return gateup_k_body_kernel<CRABML_HIP_Q5_K>(qout, normin);
+  if (body == CRABML_HIP_Q6_K) return gateup_k_body_kernel<CRABML_HIP_Q6_K>(qout, normin);
   if (ord) return qout ? k_gateup_k_lds<true, true> : k_gateup_k_lds<false, true>;
   if (normin) return k_gateup_k_lds<true, false, true>;
   return qout ? k_gateup_k_lds<true> : k_gateup_k_lds<false>;
@@ -1016,14 +1022,15 @@ int enqueue_segment_generic(crabml_hip_llama* c, int seg) {
   return 0;
 }
 
-// Q4_K, Q5_K and Q4_1 layers (fast mode): the fused GEMV kernels with the format's inner loop against Q8_K / Q8_1
+// Q4_K, Q5_K, Q6_K and Q4_1 layers (fast mode): the fused GEMV kernels with the format's inner loop against Q8_K / Q8_1
 // activation planes.  The rhs quantizer is its own launch here (a Q8_K super-block spans 256 rows: eight 32-row
 // workgroups; Q8_1 keeps the same structure), so a layer is 11 launches instead of the per-op path's 18.
 template <int FMT>
 int enqueue_segment_k(crabml_hip_llama* c, int seg) {
-  // a K-quant body: Q4_K, or Q5_K -- the same five launches with the Q5_K row loader, built in the norm-epilogue form only (decide_step)
-  constexpr bool KF = FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K;
-  constexpr bool Q5 = FMT == CRABML_HIP_Q5_K;
+  // a K-quant body: Q4_K, or Q5_K / Q6_K -- the same five launches with the format's own row loader, built in the norm-epilogue form only
+  // (decide_step)
+  constexpr bool KF = FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
+  constexpr bool EPI_ONLY = FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
   constexpr uint32_t QT = KF ? CRABML_HIP_Q8_K : CRABML_HIP_Q8_1;
   constexpr int BE = KF ? 256 : 32;  // elements per weight block
   typedef typename ActOf<FMT>::type Act;
@@ -1044,8 +1051,9 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
   auto P1 = [&]() { return prof ? prof_end(dev, &pr) : 0; };
   auto act_k = [&](char* planes, int n) { return act_at<Act>(planes, act_layout(QT, (size_t)n)); };
   // a Q6_K tensor inside a Q4_K layer (attn_v / ffn_down of the *_K_M mixes): handed to the kernel beside the planes
+  // (a Q6_K BODY hands over nothing: its planes are the kernel's own)
   auto six = [&](const crabml_hip_buf* b) {
-    return b->dtype == CRABML_HIP_Q6_K ? Planes6{(const char*)b->ptr, b->wl.off_scale} : Planes6{nullptr, 0};
+    return FMT != CRABML_HIP_Q6_K && b->dtype == CRABML_HIP_Q6_K ? Planes6{(const char*)b->ptr, b->wl.off_scale} : Planes6{nullptr, 0};
   };
   // rmsnorm * weight -> xn -> Q8_K planes (buf_q8_k.rs:84-131)
   auto norm_quant = [&](const float* wn, float eps, bool add_pending, uint32_t qt) -> const void* {
@@ -1084,7 +1092,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         c->tap.note(seg / 2, stage == 2 ? CRABML_HIP_PLAN_SPLIT_WO : CRABML_HIP_PLAN_SPLIT_DOWN, split);
         c->tap.note(seg / 2, stage == 2 ? CRABML_HIP_PLAN_QMODE_WO : CRABML_HIP_PLAN_QMODE_DOWN, qmode);
         if (stage == 2) c->tap.note(seg / 2, CRABML_HIP_PLAN_WO_X_ONLY, x_only ? 1 : 0);
-        if constexpr (!Q5)
+        if constexpr (!EPI_ONLY)
           if (ordk) {  // (qmode is 1 or 2 here: `qin` holds on every ordered context)
             launch_k(st, R, nq_ord_k_kernel(split, qmode == 2 ? 2 : 1), dim3(dim / 32 * split), dim3(1024), q8k_ord_lds_bytes(k, 32 / split), planes_of(w),
                      a, xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
@@ -1099,8 +1107,8 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         return P1();
       }
     }
-    if constexpr (Q5) {
-      CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a Q5_K body outside the norm-epilogue form (decide_step sends it to the per-op segments)");
+    if constexpr (EPI_ONLY) {
+      CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a Q5_K / Q6_K body outside the norm-epilogue form (decide_step sends it to the per-op segments)");
     } else {
       if (tp)
         launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), a, dst, dim, k / BE);
@@ -1141,7 +1149,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
     CH_TRY(P0(1, total_rows, dim));
     with_qkv_epi(c, decode_qkv_epi(c, l), l, [&](auto ep) {
       constexpr int A = QkvArchOf<decltype(ep)>::value;
-      if constexpr (!Q5)
+      if constexpr (!EPI_ONLY)
         if (ordk) {
           launch_k(st, R, k_qkv_ord<FMT, A>, dim3((total_rows / 2 + 3) / 4), dim3(256), ord_terms_k_lds_bytes(dim / BE), planes_of(c->wq[l]),
                    planes_of(c->wk[l]), planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]));
@@ -1196,7 +1204,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         nsums = c->rsums;
         sum_parts = wo_parts;
       }
-      launch_k(st, R, gateup_k_kernel(qout, ordk, normin, Q5), dim3(hidden_l / 32), dim3(1024), ordk ? q8k_ord_lds_bytes(dim, 64) : q8k_lds_bytes(dim),
+      launch_k(st, R, gateup_k_kernel(qout, ordk, normin, KF ? FMT : CRABML_HIP_Q4_K), dim3(hidden_l / 32), dim3(1024), ordk ? q8k_ord_lds_bytes(dim, 64) : q8k_lds_bytes(dim),
                planes_of(c->gate[l]), planes_of(c->up[l]), act_k(c->act_dim, dim), c->ffn_act, c->h, hidden_l, dim / 256, hx,
                (signed char*)hp, (float*)(hp ? hp + alh.off_d : nullptr), (short*)(hp ? hp + alh.off_aux : nullptr),
                (signed char*)(hp ? hp + alh.off_p : nullptr), nx, nw, normin ? 1e-5f : 0.f, nsums, sum_parts);
@@ -1222,6 +1230,7 @@ int enqueue_segment(crabml_hip_llama* c, int seg) {
     case SegPath::FusedK:
       return c->wtype == CRABML_HIP_Q4_K   ? enqueue_segment_k<CRABML_HIP_Q4_K>(c, seg)
              : c->wtype == CRABML_HIP_Q5_K ? enqueue_segment_k<CRABML_HIP_Q5_K>(c, seg)
+             : c->wtype == CRABML_HIP_Q6_K ? enqueue_segment_k<CRABML_HIP_Q6_K>(c, seg)
                                            : enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
     case SegPath::Fused5:
       return c->wtype == CRABML_HIP_Q4_0   ? enqueue_segment_t<CRABML_HIP_Q4_0>(c, seg)
@@ -2203,7 +2212,7 @@ static int validate_config(crabml_hip_device_t* dev, const crabml_hip_llama_conf
   return 0;
 }
 
-// type and shape of every weight.  Fused kernels exist for Q4_0 / Q8_0 / Q4_1, Q4_K and Q5_K layers; a classifier of another format --
+// type and shape of every weight.  Fused kernels exist for Q4_0 / Q8_0 / Q4_1, Q4_K, Q5_K and Q6_K layers; a classifier of another format --
 // llama.cpp's "Q4_0" files keep output.weight in Q6_K -- does not take the layers off them: the final segment quantizes the
 // normalized row for the classifier's own rhs type.
 static int validate_weights(crabml_hip_device_t* dev, const crabml_hip_llama_config_t& g, const crabml_hip_llama_weights_t* w, ModelFacts* f) {
@@ -2347,10 +2356,11 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   const uint32_t wt = f.wt;
   const bool fused_fmt = wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0 || wt == CRABML_HIP_Q4_1;  // a dot of one term per block
   const bool chunks_resident = dim / 32 <= n_cu;  // every workgroup of a wo / ffn_down gather must be resident
-  // the K-quant norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on, and the ONLY form a Q5_K body is
-  // built in -- a Q5_K context that misses a clause of it (a classifier with another rhs, NO_NORM_EPILOGUE, a dim that is no multiple
-  // of 256, chunks that are not resident) runs the per-op segments
-  const bool k_body = wt == CRABML_HIP_Q4_K || wt == CRABML_HIP_Q5_K;
+  // the K-quant norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on, and the ONLY form a Q5_K or a
+  // Q6_K body is built in -- such a context that misses a clause of it (a classifier with another rhs, NO_NORM_EPILOGUE, a dim that is
+  // no multiple of 256, chunks that are not resident) runs the per-op segments
+  const bool k_body = wt == CRABML_HIP_Q4_K || wt == CRABML_HIP_Q5_K || wt == CRABML_HIP_Q6_K;
+  const bool k_body_epi_only = wt == CRABML_HIP_Q5_K || wt == CRABML_HIP_Q6_K;
   const bool k_epilogue_eligible = k_body && f.out_qt == CRABML_HIP_Q8_K && tp == 1 && !has(CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) &&
                                    dim % 256 == 0 && chunks_resident;
   const bool k_fusion = !has(CRABML_HIP_LLAMA_NO_KQUANT_FUSION);
@@ -2385,10 +2395,10 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   };
   const bool ordk = strict && wt == CRABML_HIP_Q4_K && k_epilogue_eligible && k_fusion && !has(CRABML_HIP_LLAMA_NO_RHS_PROLOGUE) && (!f.mixed || f.mix_v_down_q6k) &&
                     dim_l % 256 == 0 && hidden_l % 256 == 0 && ordk_fits();
-  // the fast K-quant segments: Q4_K always; Q5_K in the norm-epilogue form (there is no ordered Q5_K form: a strict-order device keeps
-  // it on the per-op segments); Q4_1 when it cannot take the five launches (a classifier of another format) or for the A/B flag
+  // the fast K-quant segments: Q4_K always; Q5_K / Q6_K in the norm-epilogue form (neither has an ordered form: a strict-order device
+  // keeps them on the per-op segments; no mix recipe has a Q6_K body: mix_v_down_q6k is about Q4_K / Q5_K bodies); Q4_1 when it cannot take the five launches (a classifier of another format) or for the A/B flag
   const bool fast_k = !strict && (!f.mixed || mix_fused) && k_fusion &&
-                      (wt == CRABML_HIP_Q4_K || (wt == CRABML_HIP_Q5_K && k_epilogue_eligible) || (wt == CRABML_HIP_Q4_1 && (f.out_wt != wt || has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS))));
+                      (wt == CRABML_HIP_Q4_K || (k_body_epi_only && k_epilogue_eligible) || (wt == CRABML_HIP_Q4_1 && (f.out_wt != wt || has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS))));
   // per-op launches: a strict-order device without an ordered form, a weight format without fused kernels, a mix they do not take
   const bool per_op = (strict && !ord5) || !fused_fmt || (f.mixed && !mix_fused);
 
@@ -2924,7 +2934,7 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   // (decide_step: what Fused5 / FusedK and !ordered imply)
   if ((c->plan.path != SegPath::Fused5 && c->plan.path != SegPath::FusedK) || c->plan.ordered || c->tp > 1 || c->ext_kv)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
-            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 / Q4_K / Q5_K layers, the Q4_K_M / Q5_K_M mixes) on one device with its own KV cache");
+            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 / Q4_K / Q5_K / Q6_K layers, the Q4_K_M / Q5_K_M mixes) on one device with its own KV cache");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim;
   // the row type of every field that leaves as blocks (the others: f32 values, the plan words)

@@ -532,7 +532,8 @@ struct Planes6 {
 template <int FMT, bool DEFER = false, int ARCH = QKV_LLAMA>
 __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb,
                                              typename QkvArch<ARCH>::epi e, Planes6 wv6, RmsTail rt, int upfront = 0) {
-  constexpr bool KF = FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K;  // a K-quant body: nb counts super-blocks, rows_dot has its loader
+  // a K-quant body: nb counts super-blocks, rows_dot has its loader (a Q6_K body comes with wv6.base = nullptr: its V rows are the body's)
+  constexpr bool KF = FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + wave_in_wg();
   int row0 = wave * 2, rs = 1;
@@ -563,7 +564,7 @@ __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, ty
   }
   float acc[2];
   bool done = false;
-  if constexpr (KF) {
+  if constexpr (KF && FMT != CRABML_HIP_Q6_K) {
     if (wv6.base != nullptr && row0 >= e.dim + e.kv_dim) {  // the V rows of this layer are Q6_K (wave-uniform)
       rows_partial_q6k<2>(wv6.base, wv6.off_qh, act, local, m, nb, lane, acc, nullptr, rs);
       done = true;

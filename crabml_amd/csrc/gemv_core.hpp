@@ -845,8 +845,117 @@ __device__ __forceinline__ void rows_partial_q6k(const char* __restrict__ w, siz
   }
 }
 
+// ---- the Q6_K BODY loader (every layer matrix Q6_K: k_qkv, k_gemv_res_nq, k_gateup_k_lds) -----------------------------------
+// The same pieces on the same lanes with the same arithmetic as rows_partial_q6k above -- piece j = lane & 7 of a super-block, half
+// h = j >> 2, a = (j >> 1) & 1, p = j & 1, scale groups gi = 8 h + 2 a + p and gi + 4 -- but every weight byte of the super-block's 210
+// is requested ONCE, non-temporal, and handed round its eight lanes in registers:
+//   ql      lane j takes its own 16 bytes;
+//   qh      lane j takes bytes 8 j .. 8 j + 7 (dwords 2 j, 2 j + 1).  Piece j wants the 16 bytes 16 (2 h + p) .. = dwords 4 (2 h + p) .. + 3,
+//           which lanes 2 (2 h + p) and 2 (2 h + p) + 1 hold: inside the lane's own quad, quad lanes (0, 1) for p = 0 and (2, 3) for p = 1
+//           -- quad_perm [0,2,0,2] and [1,3,1,3] of the two dwords, no select;
+//   scales  piece j wants byte j & 3 of dwords 2 h and 2 h + 1: quad lanes 0 and 1 of each quad take them (lanes 0, 1, 4, 5 of the
+//           group), quad_perm broadcasts hand them round;
+//   d       lane 2 of the group takes the two bytes; a quad broadcast, then row_shr:4 for the upper quad.
+// Lanes 3, 6 and 7 request nothing beyond ql and qh.  No exchange leaves the aligned 8-lane group, whose lanes are live or dead
+// together (pieces come in eights); a clamped dead group takes the row's last super-block whole (qh, scales and d by lane & 7).
+struct PlanesQ6 {
+  const i32x4* ql;
+  const i32x2* qh;
+  const unsigned* sc;
+  const unsigned short* d;
+};
+// a Q6_K buffer from its first two planes (off_scale = n * 128 exactly, common.hpp: qh[n][64] | scales[n][16] | d[n] follow)
+__device__ __forceinline__ PlanesQ6 planes_q6k(const void* ql, const void* qh) {
+  const size_t n128 = (size_t)((const char*)qh - (const char*)ql);
+  return PlanesQ6{(const i32x4*)ql, (const i32x2*)qh, (const unsigned*)((const char*)qh + n128 / 2),
+                  (const unsigned short*)((const char*)qh + n128 / 8 * 5)};
+}
+struct Q6KPiece {
+  i32x4 ql;     // the lane's own piece
+  i32x2 qh;     // dwords 2 (lane & 7), + 1 of the super-block's qh
+  unsigned sw;  // group lanes 0, 1, 4, 5: a dword of the scales (0, 1, 2, 3); lane 2: d; else 0
+};
+__device__ __forceinline__ Q6KPiece q6k_load(const PlanesQ6& w, size_t row, int nsb, int c, int lane) {
+  Q6KPiece o;
+  const size_t blk = row * nsb + (c >> 3);
+  const int g = lane & 7;
+  o.ql = __builtin_nontemporal_load(w.ql + blk * 8 + (c & 7));
+  o.qh = __builtin_nontemporal_load(w.qh + blk * 8 + g);
+  o.sw = 0;
+  if ((g & 2) == 0)
+    o.sw = __builtin_nontemporal_load(w.sc + blk * 4 + (g >> 2) * 2 + (g & 1));
+  else if (g == 2)
+    o.sw = (unsigned)__builtin_nontemporal_load(w.d + blk);
+  return o;
+}
+// the activation side of piece c: groups gi and gi + 4 of the element-order plane, their bsums
+__device__ __forceinline__ Q4KX q6k_loadx(const ActQ8_K& act, int c) {
+  const int sb = c >> 3, gi = 8 * ((c >> 2) & 1) + (c & 3);
+  Q4KX x;
+  const i32x4* xq = act.q + (size_t)sb * 16 + gi;
+  x.xl = xq[0];
+  x.xh = xq[4];
+  x.d8 = act.d[sb];
+  const short* bs = act.bsums + sb * 16 + gi;
+  x.bs_lo = (int)bs[0];
+  x.bs_hi = (int)bs[4];
+  return x;
+}
+// (all lanes of the piece's 8-lane group take part, outside any lane-dependent branch; dbg: the parity hook's two scaled sums)
+__device__ __forceinline__ float q6k_term(const Q6KPiece& w, const Q4KX& x, int c, int lane, int* dbg = nullptr) {
+  const int a = (c >> 1) & 1;
+  const unsigned hq[4] = {(unsigned)dpp_i<0x88>(w.qh[0]), (unsigned)dpp_i<0x88>(w.qh[1]), (unsigned)dpp_i<0xDD>(w.qh[0]),
+                          (unsigned)dpp_i<0xDD>(w.qh[1])};
+  const unsigned s_lo = (unsigned)dpp_i<0x00>((int)w.sw), s_hi = (unsigned)dpp_i<0x55>((int)w.sw);
+  const int dq = dpp_i<0xAA>((int)w.sw), dn = dpp_i<0x114>(dq);  // row_shr:4: lane - 4 of the row
+  const unsigned short dw = (unsigned short)((lane & 4) ? dn : dq);
+  int lo = 0, hi = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned q = (unsigned)w.ql[i], hb = hq[i] >> (2 * a);
+    const unsigned ql4 = (q & 0x0F0F0F0Fu) | ((hb & 0x03030303u) << 4);
+    const unsigned qh4 = ((q >> 4) & 0x0F0F0F0Fu) | (((hb >> 4) & 0x03030303u) << 4);
+    lo = __builtin_amdgcn_sdot4((int)ql4, x.xl[i], lo, false);
+    hi = __builtin_amdgcn_sdot4((int)qh4, x.xh[i], hi, false);
+  }
+  lo -= 32 * x.bs_lo;  // sum (q6 - 32) * q8, exact
+  hi -= 32 * x.bs_hi;
+  const int sh = 8 * (c & 3);
+  const int sc_lo = (int)(signed char)((s_lo >> sh) & 0xffu), sc_hi = (int)(signed char)((s_hi >> sh) & 0xffu);
+  // (24-bit multiplies: |sc| <= 128, |lo|, |hi| <= 16 * 63 * 128 + 32 * 16 * 128 < 2^23 -- the same integers as the plain product)
+  const int slo = __mul24(sc_lo, lo), shi = __mul24(sc_hi, hi);
+  if (dbg) {
+    dbg[0] = slo;
+    dbg[1] = shi;
+  }
+  const float dd = h2f(dw) * x.d8;
+  return dd * ((float)slo + (float)shi);
+}
+// a lane adds its pieces in ascending order (then the caller's wave tree), as rows_partial_q6k does; c0: pieces below it were taken
+// by the caller (a multiple of 64)
+template <int R>
+__device__ __forceinline__ void rows_partial_q6k_planes(const PlanesQ6& w, const ActQ8_K& act, int row0, int m, int nsb, int lane,
+                                                        float acc[R], int c0 = 0, int rs = 1) {
+  if (c0 == 0) {
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = 0.f;
+  }
+  const int nchunks = nsb * 8;
+  for (int c = c0 + lane; c < nchunks; c += 64) {
+    Q6KPiece pw[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
+      pw[r] = q6k_load(w, (size_t)row, nsb, c, lane);
+    }
+    const Q4KX x = q6k_loadx(act, c);
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] += q6k_term(pw[r], x, c, lane);
+  }
+}
+
 // R rows of a weight matrix in format FMT against its activation planes (ActQ8_0 for Q4_0 / Q8_0, ActQ8_K for
-// Q4_K / Q5_K); `wd` is the format's second plane (f16 scales / 16-byte headers / Q5_K's qh), `nu` the blocks per row
+// Q4_K / Q5_K / Q6_K); `wd` is the format's second plane (f16 scales / 16-byte headers / Q5_K's and Q6_K's qh), `nu` the blocks per row
 template <int FMT, int R, class ACT>
 __device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
                                          int row0, int m, int nu, int lane, float acc[R], int rs = 1) {
@@ -854,6 +963,8 @@ __device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const uns
     rows_partial_q4k<R>(wq, (const i32x4*)wd, act, row0, m, nu, lane, acc, 0, nullptr, rs);
   else if constexpr (FMT == CRABML_HIP_Q5_K)  // (wd: the qh plane, planes_q5k)
     rows_partial_q5k_planes<R>(planes_q5k(wq, wd), act, row0, m, nu, lane, acc, 0, rs);
+  else if constexpr (FMT == CRABML_HIP_Q6_K)  // (wd: the qh plane, planes_q6k)
+    rows_partial_q6k_planes<R>(planes_q6k(wq, wd), act, row0, m, nu, lane, acc, 0, rs);
   else
     rows_partial<FMT, R>(wq, wd, act, row0, m, nu, lane, acc, rs);
 }
@@ -867,6 +978,10 @@ struct ActOf<CRABML_HIP_Q4_K> {
 };
 template <>
 struct ActOf<CRABML_HIP_Q5_K> {
+  typedef ActQ8_K type;
+};
+template <>
+struct ActOf<CRABML_HIP_Q6_K> {
   typedef ActQ8_K type;
 };
 template <>

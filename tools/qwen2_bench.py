@@ -1,5 +1,6 @@
 """Qwen2 on the fused decode step against the per-op trait path and Llama-3-8B, in one process.
 Usage: python tools/qwen2_bench.py [--runs qwen2.5-7b:Q4_0,qwen2.5-7b:Q4_K_M,llama3-8b:Q4_0,qwen2.5-3b:Q4_0]
+(FORMAT: a name of synth.TYPE_BY_NAME -- llama3-8b:Q6_K, llama3-8b:Q5_K -- or the recipes Q4_K_M / Q5_K_M)
 Per SHAPE:FORMAT (synthetic weights, f16 KV cache), one markdown table row:
   fused      crabml_hip_llama_decode_greedy tok/s over positions 0..127 (best of 3)
   @1024      the same over positions 1024..1087, after a 1024-token prefill
