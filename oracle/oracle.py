@@ -213,6 +213,15 @@ def q4k_overflow_count(w_raw: np.ndarray, x_raw: np.ndarray, n_elems: int) -> in
     return int(cnt.value)
 
 
+def q5k_overflow_count(w_raw: np.ndarray, x_raw: np.ndarray, n_elems: int) -> int:
+    """Q4_K's twin: the `bsums * mins` products of buf_q5_k.rs that do not fit the reference's i16"""
+    cnt = C.c_size_t(0)
+    w_raw = np.ascontiguousarray(w_raw).view(np.uint8)
+    x_raw = np.ascontiguousarray(x_raw).view(np.uint8)
+    lib().co_vec_dot_q5_k_q8_k(_p(w_raw), _p(x_raw), n_elems // 256, 0, C.byref(cnt))
+    return int(cnt.value)
+
+
 def block_dots(w_raw: np.ndarray, wtyp: int, x_raw: np.ndarray, n_elems: int) -> np.ndarray:
     w_raw = np.ascontiguousarray(w_raw).view(np.uint8)
     x_raw = np.ascontiguousarray(x_raw).view(np.uint8)

@@ -238,9 +238,10 @@ def wide_rows(rng, b, k):
     return (rng.standard_normal((b, k // 32, 32)) * mag).astype(np.float32).reshape(-1)
 
 
-def check_f16_operands(ca, hdev, fmt, m, k, b, force, seed, rows=None, x=None, rows_path=0):
+def check_f16_operands(ca, hdev, fmt, m, k, b, force, seed, rows=None, x=None, rows_path=0, raw=None):
     rng = np.random.default_rng(seed)
-    raw = synth.random_blocks(rng, m * k, synth.TYPE_BY_NAME[fmt])
+    if raw is None:
+        raw = synth.random_blocks(rng, m * k, synth.TYPE_BY_NAME[fmt])
     if x is None:
         x = wide_rows(rng, b, k)
     w = upload(ca, hdev, raw, fmt, m, k)

@@ -184,6 +184,21 @@ def test_block_scales_of_either_sign(ca):
     run_case(ca, "signs/tiny-gqa/k-m-mix", flip_signs(synth.build_model(synth.SHAPES["tiny-gqa"], synth.Q4_K, seed=47, k_m_mix=True)), 64, [5], [0, 1])
 
 
+@pytest.mark.parametrize("shape,mix", [("tiny-gqa", False), ("tiny-gqa", True), ("tiny-hd128", False)])
+def test_mixed_sign_block_fields(ca, shape, mix):
+    """d / dmin flipped independently and a few d = +-0 (tests/edge_blocks.flip_scale_signs), Q4_K and the Q4_K_M mix: the default
+    forms, as the plain models take them"""
+    from tests import edge_blocks as eb
+    kw = {"k_m_mix": True} if mix else {"output_type": synth.Q6_K}
+    model = eb.mixed_sign_model(shape, synth.Q4_K, eb.MIXED_SIGN_SEEDS["fused_k"], **kw)
+    plans = run_case(ca, f"mixed-signs/{shape}/{'k-m-mix' if mix else 'Q4_K'}", model, 64, [0, 5], [0, 1])
+    for plan in plans.values():
+        assert plan["qin"] == 1 and plan["norm_epi_k"] == 1, plan
+        if not mix:
+            assert (plan["norm_epi_k"], plan["q8k_producers"], plan["k_norm_in"], plan["wo_x_only"], plan["qin"]) == (1, 1, 1, 1, 1), plan
+            assert (plan["qmode_wo"], plan["qmode_down"], plan["aq8"], plan["split_wo"]) == (1, 2, 0, 2), plan
+
+
 @pytest.mark.parametrize("mix", [False, True])
 def test_shrunk_residual_stream(ca, mix):
     """a residual stream small enough for RMSNorm's eps to matter in every launch (fused_step_ref.shrink_residual).  By 2^-9 here: the

@@ -149,6 +149,15 @@ def test_block_scales_of_either_sign(ca, fmt):
     run_case(ca, f"signs/tiny-gqa/{fmt}", model, 64, True, [0, 5], [0, 1])
 
 
+@pytest.mark.parametrize("shape,fmt", [("tiny-gqa", "Q4_0"), ("tiny-gqa", "Q8_0"), ("tiny-gqa", "Q4_1"), ("tiny-hd128", "Q4_1")])
+def test_mixed_sign_block_fields(ca, shape, fmt):
+    """d and Q4_1's m flipped INDEPENDENTLY (flip_signs above moves d alone, so m stays tied to it), and a few blocks with d = +-0
+    (tests/edge_blocks.flip_scale_signs).  run_case holds the plan words against the case: the same launches as the plain model's."""
+    from tests import edge_blocks as eb
+    model = eb.mixed_sign_model(shape, synth.TYPE_BY_NAME[fmt], eb.MIXED_SIGN_SEEDS["fused"])
+    run_case(ca, f"mixed-signs/{shape}/{fmt}", model, 64, True, [0, 5], [0, 1])
+
+
 def test_q4_0_body_with_a_q6_k_classifier(ca):
     """out_qt != qt: the classifier reads Q8_K planes of its own (k_norm_f32 + the quantizer launch); the layers stay hop-free"""
     model = synth.build_model(synth.SHAPES["tiny-gqa"], synth.Q4_0, seed=36, output_type=synth.Q6_K)

@@ -221,6 +221,17 @@ def test_super_block_scales_of_either_sign(ca, n):
         expect_f16_layer(plan, model, layer, n)
 
 
+@pytest.mark.parametrize("fmt", ["Q4_K", "Q4_K_M"])
+def test_mixed_sign_block_fields(ca, fmt):
+    """d / dmin flipped independently and a few d = +-0 (tests/edge_blocks.flip_scale_signs): the default pass at 77 rows"""
+    from tests import edge_blocks as eb
+    wtype, mix = FMTS[fmt]
+    model = eb.mixed_sign_model("tiny-gqa", wtype, eb.MIXED_SIGN_SEEDS["prefill_k"], k_m_mix=mix)
+    plans = case(ca, f"mixed-signs/tiny-gqa/{fmt}", model, 256, 77, [0, 1])
+    for layer, plan in plans.items():
+        expect_f16_layer(plan, model, layer, 77)
+
+
 @pytest.mark.parametrize("n", [77, 200])
 @pytest.mark.parametrize("fmt", ["Q4_K_M", "Q5_K_M"])
 def test_shrunk_residual_stream(ca, fmt, n):

@@ -260,6 +260,17 @@ def test_block_scales_of_either_sign(ca, fmt):
         expect_f16(plan, model)
 
 
+@pytest.mark.parametrize("shape,fmt", [("tiny-gqa", "Q4_0"), ("tiny-gqa", "Q8_0"), ("tiny-gqa", "Q4_1"), ("tiny-hd128", "Q4_1")])
+def test_mixed_sign_block_fields(ca, shape, fmt):
+    """d and Q4_1's m flipped independently, a few d = +-0 (tests/edge_blocks.flip_scale_signs): the default f16 pass, as for the
+    plain model"""
+    from tests import edge_blocks as eb
+    model = eb.mixed_sign_model(shape, synth.TYPE_BY_NAME[fmt], eb.MIXED_SIGN_SEEDS["prefill"])
+    plans = run_case(ca, f"mixed-signs/{shape}/{fmt}", model, 128, True, 77, [0, 1])
+    for plan in plans.values():
+        expect_f16(plan, model)
+
+
 def test_shrunk_residual_stream(ca):
     """a residual stream small enough for RMSNorm's eps to matter in every norm launch (fused_step_ref.shrink_residual)"""
     for fmt in ("Q4_0", "Q8_0"):

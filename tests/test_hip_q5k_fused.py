@@ -160,6 +160,14 @@ def test_block_scales_of_either_sign(ca):
     run_listed(ca, "signs/tiny-gqa")
 
 
+def test_mixed_sign_block_fields(ca):
+    """d and dmin of either sign, flipped independently tensor by tensor, and a few d = +-0 (tests/edge_blocks.flip_scale_signs): the same
+    launches as the plain model's (run_case holds the plan against want_path), the same caps"""
+    plans = run_listed(ca, "mixed-signs/tiny-gqa")
+    for plan in plans.values():  # (the Q5_K_M mix, as the `signs` case)
+        assert plan["qin"] == 1 and plan["norm_epi_k"] == 1, plan
+
+
 def test_shrunk_residual_stream(ca):
     """a residual stream small enough for RMSNorm's eps to matter in every launch (by 2^-9, as for the Q4_K body), on the mix"""
     run_listed(ca, "shrunk/tiny-gqa")

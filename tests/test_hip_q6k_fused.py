@@ -153,6 +153,14 @@ def test_block_scales_of_either_sign(ca):
     run_listed(ca, "signs/tiny-gqa")
 
 
+def test_mixed_sign_block_fields(ca):
+    """d of either sign, flipped independently tensor by tensor, and a few d = +-0 (tests/edge_blocks.flip_scale_signs): the same
+    launches as the plain model's (run_case holds the plan against want_path), the same caps"""
+    plans = run_listed(ca, "mixed-signs/tiny-gqa")
+    for plan in plans.values():
+        assert (plan["norm_epi_k"], plan["q8k_producers"], plan["k_norm_in"], plan["wo_x_only"], plan["qin"]) == (1, 1, 1, 1, 1), plan
+
+
 def test_shrunk_residual_stream(ca):
     """a residual stream small enough for RMSNorm's eps to matter in every launch (by 2^-9, as for the Q4_K body)"""
     run_listed(ca, "shrunk/tiny-gqa")

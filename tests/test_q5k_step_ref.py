@@ -28,6 +28,8 @@ CASES = [
     ("switch/tiny-gqa", "tiny-gqa", 55, {"output_type": synth.Q6_K}, 256, [94, 95, 96, 200], [0, 1]),
     ("signs/tiny-gqa", "tiny-gqa", 57, {"k_m_mix": True}, 64, [0, 5], [0, 1]),
     ("shrunk/tiny-gqa", "tiny-gqa", 58, {"k_m_mix": True}, 64, [0, 5], [0, 1]),
+    # d and dmin flipped independently, some d = +-0 (tests/edge_blocks.flip_scale_signs)
+    ("mixed-signs/tiny-gqa", "tiny-gqa", 59, {"k_m_mix": True}, 64, [0, 5], [0, 1]),
 ]
 
 
@@ -43,6 +45,9 @@ def build(case):
         Q.flip_signs(model)
     if key.startswith("shrunk/"):
         Q.shrink_residual(model, log2=9)
+    if key.startswith("mixed-signs/"):
+        from tests import edge_blocks as eb
+        model = eb.flip_scale_signs(model, np.random.default_rng([seed, 1]))
     return model
 
 

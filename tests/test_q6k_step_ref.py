@@ -25,6 +25,8 @@ CASES = [
     ("switch/tiny-gqa", "tiny-gqa", 65, {}, 256, [94, 95, 96, 200], [0, 1]),
     ("signs/tiny-gqa", "tiny-gqa", 67, {}, 64, [0, 5], [0, 1]),
     ("shrunk/tiny-gqa", "tiny-gqa", 68, {}, 64, [0, 5], [0, 1]),
+    # d and dmin flipped independently, some d = +-0 (tests/edge_blocks.flip_scale_signs)
+    ("mixed-signs/tiny-gqa", "tiny-gqa", 69, {}, 64, [0, 5], [0, 1]),
 ]
 
 
@@ -35,6 +37,9 @@ def build(case):
         Q.flip_signs(model)
     if key.startswith("shrunk/"):
         Q.shrink_residual(model, log2=9)
+    if key.startswith("mixed-signs/"):
+        from tests import edge_blocks as eb
+        model = eb.flip_scale_signs(model, np.random.default_rng([seed, 1]))
     return model
 
 
