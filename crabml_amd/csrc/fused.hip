@@ -389,9 +389,10 @@ struct PvSplitKernel {
   int nsub = 0, threads = 0;
   size_t lds = 0;
 };
+// (two heads per workgroup from group 2 on: an odd group has no such kernel and keeps k_attn_pv, which is bit-identical)
 PvSplitKernel pv_split_kernel(int grp) {
   PvSplitKernel k;
-  with_const_else<1, 2, 4, 8>(grp, [&](auto g) {
+  with_const<1, 2, 4, 6, 8>(grp, [&](auto g) {
     typedef PvSplit<decltype(g)::value> P;
     k = PvSplitKernel{k_attn_pv_split<decltype(g)::value>, P::NSUB, P::THREADS, P::LDS};
   });
@@ -522,12 +523,12 @@ void launch_attn_long(crabml_hip_llama* c, int l, signed char* xq, unsigned shor
            (const float*)c->qbuf, (const unsigned short*)c->kc[l], pos_d, c->scores_g, n_kv, hd, seq_cap, nsplit, 0);
   launch_k(st, prof ? &r[1] : nullptr, k_attn_softmax<16>, dim3(c->n_heads_l), dim3(1024), (size_t)seq_cap * sizeof(float),
            (const float*)c->scores_g, pos_d, (const unsigned short*)dev->exp_table, c->p16, seq_cap, 0, dev->strict_order ? 1 : 0);
-  const PvSplitKernel pv = pv_split_kernel(G);
-  if (c->plan.pv_split)
+  if (c->plan.pv_split) {
+    const PvSplitKernel pv = pv_split_kernel(G);
     launch_k(st, prof ? &r[2] : nullptr, pv.fn, dim3(n_kv * (hd / 32) * pv.nsub), dim3(pv.threads), pv.lds,
              (const unsigned short*)c->p16, (const unsigned short*)c->vc[l], pos_d, c->attn, xq, xd, xisum, hd, seq_cap,
              c->qt == CRABML_HIP_Q8_1 ? 1 : 0, 0);
-  else
+  } else
     launch_k(st, prof ? &r[2] : nullptr, k_attn_pv<G>, dim3(n_kv * (hd / 32)), dim3(256), 0, (const unsigned short*)c->p16,
              (const unsigned short*)c->vc[l], pos_d, c->attn, xq, xd, xisum, hd, seq_cap, c->qt == CRABML_HIP_Q8_1 ? 1 : 0, 0);
   for (int i = 0; i < 3; i++)
@@ -537,27 +538,26 @@ void launch_attn_long(crabml_hip_llama* c, int l, signed char* xq, unsigned shor
 // the k_attn_flash instantiation for (G, hd, rhs type of wo); nullptr = no such kernel
 typedef void (*FlashFn)(const float*, const unsigned short*, const unsigned short*, const int*, float*, unsigned*, float*, signed char*,
                         unsigned short*, void*, int, int, int);
+template <int G, int HD>
+FlashFn flash_kernel_gh(bool q81, bool ticket) {
+  if (ticket) return q81 ? (FlashFn)k_attn_flash<G, HD, true, true> : (FlashFn)k_attn_flash<G, HD, false, true>;
+  return (FlashFn)k_attn_flash<G, HD, false, false>;
+}
+// (groups 3, 5, 6 and 7 -- Llama-3.2-3B; Qwen2.5-14B / 32B; 1.5B; 7B / 0.5B -- exist at head_dim 64 and 128 only: no model served has one
+// of them at 256)
 template <int G>
 FlashFn flash_kernel_g(int hd, bool q81, bool ticket) {
-  if (ticket) {
-    if (hd == 256) return q81 ? (FlashFn)k_attn_flash<G, 256, true, true> : (FlashFn)k_attn_flash<G, 256, false, true>;
-    if (hd == 128) return q81 ? (FlashFn)k_attn_flash<G, 128, true, true> : (FlashFn)k_attn_flash<G, 128, false, true>;
-    if (hd == 64) return q81 ? (FlashFn)k_attn_flash<G, 64, true, true> : (FlashFn)k_attn_flash<G, 64, false, true>;
-    return nullptr;
+  if constexpr (G == 1 || G == 2 || G == 4 || G == 8) {
+    if (hd == 256) return flash_kernel_gh<G, 256>(q81, ticket);
   }
-  if (hd == 256) return (FlashFn)k_attn_flash<G, 256, false, false>;
-  if (hd == 128) return (FlashFn)k_attn_flash<G, 128, false, false>;
-  if (hd == 64) return (FlashFn)k_attn_flash<G, 64, false, false>;
+  if (hd == 128) return flash_kernel_gh<G, 128>(q81, ticket);
+  if (hd == 64) return flash_kernel_gh<G, 64>(q81, ticket);
   return nullptr;
 }
 FlashFn flash_kernel(int grp, int hd, bool q81, bool ticket) {
-  switch (grp) {
-    case 1: return flash_kernel_g<1>(hd, q81, ticket);
-    case 2: return flash_kernel_g<2>(hd, q81, ticket);
-    case 4: return flash_kernel_g<4>(hd, q81, ticket);
-    case 8: return flash_kernel_g<8>(hd, q81, ticket);
-    default: return nullptr;
-  }
+  FlashFn fn = nullptr;
+  with_const<1, 2, 3, 4, 5, 6, 7, 8>(grp, [&](auto g) { fn = flash_kernel_g<decltype(g)::value>(hd, q81, ticket); });
+  return fn;
 }
 // which attention form serves cache position `pos` (see attn_variant)
 int variant_of(const crabml_hip_llama* c, size_t pos) {
@@ -573,7 +573,7 @@ void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
   const FlashFn fn = flash_kernel(grp, hd, q81, ticket);
   crabml_hip_device::ProfRec r[2];
   if (prof) prof_begin(dev, &r[0], CRABML_HIP_F32, 7, 0.0);
-  launch_k(st, prof ? &r[0] : nullptr, fn, dim3(c->n_kv_l * c->plan.flash_S), dim3((grp == 8 ? 4 : 8) * 64), flash_lds_bytes(grp, hd),
+  launch_k(st, prof ? &r[0] : nullptr, fn, dim3(c->n_kv_l * c->plan.flash_S), dim3(flash_threads(grp)), flash_lds_bytes(grp, hd),
            (const float*)c->qbuf, (const unsigned short*)c->kc[l], (const unsigned short*)c->vc[l], (const int*)(c->state + 1), c->flash_part,
            c->flash_tick, c->attn, xq, xd, xisum, (int)c->cfg.seq_len, c->plan.flash_S, c->plan.flash_min_rows);
   if (prof) prof_end(dev, &r[0]);
@@ -602,7 +602,7 @@ void enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
     return;
   }
   if (c->attn_variant >= 1) {  // (attn_long_ok: the group size is one of these)
-    with_const_else<1, 2, 4, 8>(n_heads / n_kv, [&](auto grp) { launch_attn_long<decltype(grp)::value>(c, l, xq, xd, xisum, prof); });
+    with_const_else<1, 2, 3, 4, 5, 6, 7, 8>(n_heads / n_kv, [&](auto grp) { launch_attn_long<decltype(grp)::value>(c, l, xq, xd, xisum, prof); });
     return;
   }
   const size_t attn_lds = (size_t)(seq_cap + hd) * sizeof(float);
@@ -2299,14 +2299,19 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
   const int grp = (int)(f.n_heads_l / f.n_kv_l), hd = (int)f.hd, n_kv_l = (int)f.n_kv_l;
   const size_t seq = g.seq_len;
   const bool kv16 = g.use_f16_kv_cache != 0, q81 = f.qt == CRABML_HIP_Q8_1;
-  const bool long_geom = kv16 && hd % 32 == 0 && (grp == 1 || grp == 2 || grp == 4 || grp == 8) && !has(CRABML_HIP_LLAMA_NO_LONG_ATTENTION);
+  // One predicate per use.  The decode step's kernels (k_attn_flash; k_attn_scores / k_attn_softmax / k_attn_pv) serve every group up to 8;
+  // the prompt pass's (k_attn_flash_rows here, the tile and long-rows kernels through their own lists) serve 1, 2, 4 and 8 only -- any
+  // other group keeps its prompt on the per-(head, row) kernel.
+  const bool long_cache = kv16 && hd % 32 == 0 && !has(CRABML_HIP_LLAMA_NO_LONG_ATTENTION);
+  const bool long_geom = long_cache && grp >= 1 && grp <= 8;
+  const bool rows_geom = long_cache && (grp == 1 || grp == 2 || grp == 4 || grp == 8);
   // the exact kernels: the softmax kernels keep a head's score row in LDS -- rows past 16384 positions need the raised limit, rows
   // past ~38000 do not fit at all (the step then stays on the one-workgroup-per-head kernel)
   p->exact_long_ok = long_geom && seq % 8 == 0 && lds_fits(dev, (const void*)k_attn_softmax<16>, seq * 4, LDS_CAP, 64 * 1024) &&
                      lds_fits(dev, (const void*)k_attn_softmax<4>, seq * 4, LDS_CAP, 64 * 1024);
   p->pv_split = p->exact_long_ok && !has(CRABML_HIP_LLAMA_NO_PV_PRODUCER_WAVES) && [&] {
     const PvSplitKernel pv = pv_split_kernel(grp);
-    return lds_fits(dev, (const void*)pv.fn, pv.lds, LDS_NO_CAP, 0);
+    return pv.fn != nullptr && lds_fits(dev, (const void*)pv.fn, pv.lds, LDS_NO_CAP, 0);
   }();
   // the fast step's long-context attention: split-KV with f32 accumulation (k_attn_flash) unless the exact chain is asked for
   // (k_attn_flash reads the cache rows only -- head_dim halves each --, so any seq_len will do: a cache of 1001 positions must not
@@ -2327,7 +2332,7 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
       p->flash_ticket_until = hooks.ticket_until;
     // the prompt pass's causal attention of the fast step (k_attn_flash_rows): 70 KB of LDS at head_dim 128
     p->attn_flash_rows =
-        flash_rows_kernel(hd) != nullptr && lds_fits(dev, (const void*)flash_rows_kernel(hd), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
+        rows_geom && flash_rows_kernel(hd) != nullptr && lds_fits(dev, (const void*)flash_rows_kernel(hd), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
   }
   p->attn_long_ok = p->exact_long_ok || p->attn_flash;
   // the exact kernels: measured crossover on MI355X (Llama-3-8B shape) ~200-220.  k_attn_flash + merge overtake the staged one-workgroup
@@ -3155,7 +3160,7 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
   if (e == hipSuccess) {
     // the shipped form first (partials, then the merge launch), then the single-launch form (last arriver merges) twice on the
     // same ticket words -- the second launch finds them re-armed by the first; all three write the same `out`
-    hipLaunchKernelGGL(fn, dim3((unsigned)(n_kv * slices)), dim3((grp == 8 ? 4 : 8) * 64), (uint32_t)flash_lds_bytes(grp, hd), st,
+    hipLaunchKernelGGL(fn, dim3((unsigned)(n_kv * slices)), dim3(flash_threads(grp)), (uint32_t)flash_lds_bytes(grp, hd), st,
                        (const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
                        (const int*)(base + o_pos), (float*)(base + o_part), (unsigned*)(base + o_tick), (float*)(base + o_out),
                        (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, (int)seq, (int)slices, FLASH_MIN_ROWS);
@@ -3168,7 +3173,7 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
     if (ticket_form) {
       e = hipMemcpyAsync(out2, base + o_out, nq, hipMemcpyDeviceToHost, st);  // (stream order: before the next launches overwrite it)
       for (int rep = 0; rep < 2 && e == hipSuccess; rep++)
-        hipLaunchKernelGGL(fnt, dim3((unsigned)(n_kv * slices)), dim3((grp == 8 ? 4 : 8) * 64), (uint32_t)flash_lds_bytes(grp, hd), st,
+        hipLaunchKernelGGL(fnt, dim3((unsigned)(n_kv * slices)), dim3(flash_threads(grp)), (uint32_t)flash_lds_bytes(grp, hd), st,
                            (const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
                            (const int*)(base + o_pos), (float*)(base + o_part), (unsigned*)(base + o_tick), (float*)(base + o_out),
                            (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, (int)seq, (int)slices, FLASH_MIN_ROWS);

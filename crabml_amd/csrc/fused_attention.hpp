@@ -448,7 +448,7 @@ __host__ __device__ inline size_t attn_s_lds_bytes(int S, int hd) {
 // ---- attention at long context: the same arithmetic over every CU ----------------------------------------------
 // One workgroup per head streams its whole K and V through one CU (~26 GB/s): 223 us per layer at 4000 cached
 // positions.  From `attn_long_from` positions on the step uses three kernels instead (f16 cache, head_dim % 32
-// == 0, n_heads / n_kv in {1, 2, 4, 8}); every rounding point and summation order is unchanged:
+// == 0, n_heads / n_kv from 1 to 8; the prompt pass's row forms: 1, 2, 4 and 8); every rounding point and summation order is unchanged:
 //   k_attn_scores   (kv head, 128-position split): each thread scores ONE cached position against the G q heads
 //                   that share the kv head -- K is read once, f32 accumulation in k order (buf_f16.rs:83-97);
 //   k_attn_softmax  (head): softmax_row over the score row, probabilities rounded to f16;
@@ -489,6 +489,10 @@ __global__ __launch_bounds__(256) void k_attn_scores(const float* __restrict__ q
   }
   __syncthreads();
   if (t >= seq) return;
+  // a group that does not divide 256 leaves 256 - TS * G threads over: their position is the next split's first, scored there
+  if constexpr (256 % G != 0) {
+    if (tid / G >= TS) return;
+  }
   const unsigned short* qg = q16 + g * hd;
   float acc = 0.0f;
   int i = 0;
@@ -862,12 +866,18 @@ __device__ __forceinline__ float flash_row_sum(float v) {
 }
 #define FLASH_MIN_ROWS 64  /* measured on MI355X, 8B shape: 64 <= 128 <= 256 at every context (profiles/r04_flash_sweep.log) */
 #define FLASH_MAX_SLICES 32
+// The one place that maps a GQA group to the workgroup of k_attn_flash: the kernel (FlashGeom<G>::NW), its launch sites and its LDS size
+// (flash_geom_waves) read it.
+__host__ __device__ constexpr int flash_geom_waves(int G) {
+  return G == 8 ? 4 : 8;  // waves per workgroup (LDS: NW * RPI classes x G x HD floats)
+}
 template <int G>
 struct FlashGeom {
-  static constexpr int NW = G == 8 ? 4 : 8;  // waves per workgroup (LDS: NW * RPI classes x G x HD floats)
+  static constexpr int NW = flash_geom_waves(G);
 };
+__host__ __device__ inline unsigned flash_threads(int G) { return (unsigned)flash_geom_waves(G) * 64; }
 __host__ __device__ inline size_t flash_lds_bytes(int G, int hd) {
-  const int nw = G == 8 ? 4 : 8, rpi = 64 / (hd / 8), ncls = nw * rpi;
+  const int nw = flash_geom_waves(G), rpi = 64 / (hd / 8), ncls = nw * rpi;
   return (size_t)ncls * G * hd * 4 + (size_t)ncls * G * 4 * 3 + 64;
 }
 __host__ __device__ inline size_t flash_part_floats(int G, int hd) { return (size_t)G * (hd + 2); }

@@ -166,6 +166,10 @@ SHAPES = {
     # Qwen2 (seq_len: under the decode step's create-time cap, not the files' context_length of 32768)
     "qwen2.5-7b": ModelShape("Qwen2.5-7B", 3584, 18944, 28, 28, 4, 152064, 8192, 1e-6, None, "qwen2"),
     "qwen2.5-3b": ModelShape("Qwen2.5-3B", 2048, 11008, 36, 16, 2, 151936, 8192, 1e-6, None, "qwen2", True),
+    # GQA groups 3, 6 and 5 (tools/qwen2_bench.py; only the group and head_dim of 128 matter there)
+    "llama3.2-3b": ModelShape("Llama-3.2-3B", 3072, 8192, 28, 24, 8, 128256, 8192, 1e-5, None, "llama", True),
+    "qwen2.5-1.5b": ModelShape("Qwen2.5-1.5B", 1536, 8960, 28, 12, 2, 151936, 8192, 1e-6, None, "qwen2", True),
+    "qwen2.5-14b": ModelShape("Qwen2.5-14B", 5120, 13824, 48, 40, 8, 152064, 8192, 1e-5, None, "qwen2"),
     # tiny Qwen2 shapes for tests: GQA group 4 with head_dim 64, and Qwen2.5-7B's group of 7 with head_dim 128 (dims multiples of 256)
     "tiny-qwen2": ModelShape("tiny-qwen2", 512, 1024, 2, 8, 2, 1024, 64, 1e-6, None, "qwen2"),
     "tiny-qwen2-g7": ModelShape("tiny-qwen2-g7", 1792, 1024, 2, 14, 2, 1024, 64, 1e-6, None, "qwen2"),

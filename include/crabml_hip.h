@@ -190,7 +190,8 @@ int crabml_hip_batch_matmul(crabml_hip_device_t* dev, const crabml_hip_buf_t* a,
  *   wo GEMV + residual + the ffn RMSNorm + quantize | gate/up GEMV + SiLU*mul + quantize |
  *   ffn_down GEMV + residual + the next layer's RMSNorm + quantize
  * (the norms run in the producing GEMV's epilogue through one in-launch gather; attention switches to three
- * multi-workgroup kernels from `attn_long_from` cached positions), with token id
+ * multi-workgroup kernels from `attn_long_from` cached positions: f16 KV cache, head_dim a multiple of 32, n_heads / n_kv_heads
+ * from 1 to 8 -- the fast step's split-KV kernels at head_dim 64 / 128, and 256 for groups 1 / 2 / 4 / 8), with token id
  * and position living in device memory (greedy argmax on device, sampler.rs:109-116).
  * Arithmetic is the reference's (same rounding points; RoPE cos/sin tabulated on the host with the same
  * libm + iterated-theta recurrence); only GEMV block terms (and, fast mode, the RMSNorm chunk sums and softmax
@@ -242,7 +243,8 @@ typedef struct crabml_hip_llama_config { /* crabml-llama2/src/model.rs:30-53 */
   int32_t tp_size, tp_rank;
   void* tp_comm; /* crabml_hip_tp_comm_t*; NULL with tp_size > 1 = a rank of the single-device simulation */
   size_t attn_long_from; /* cached positions from which attention runs as the multi-workgroup kernels (0 = default: 96 for the
-                          * fast step's split-KV kernels, 224 for the exact ones) */
+                          * fast step's split-KV kernels, 224 for the exact ones; GQA groups 1 to 8, a larger group keeps one
+                          * workgroup per head) */
   size_t prefill_chunk;  /* rows per batched prefill pass (0 = default: 1024, 512 on a strict-order device; never more than seq_len) */
 } crabml_hip_llama_config_t;
 typedef struct crabml_hip_llama_weights { /* crabml-llama2/src/model.rs:55-84; per-layer arrays of n_layers */

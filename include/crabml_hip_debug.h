@@ -78,7 +78,8 @@ int crabml_hip_debug_read_ceiling(crabml_hip_device_t* dev, size_t bytes, int32_
  * batch_matmul.rs:39 does); k, v: [n_kv][seq][head_dim] f16 bits; slices: the grid's position slices per kv head (1 .. 32; a
  * step uses as many as the context repays); out: n_heads * head_dim f32 = softmax(q k^T) v in f32 arithmetic, from the shipped
  * two-launch form.  out2 (nullable): the same from the single-launch form (the last-arriving workgroup of a kv head merges;
- * launched twice on the same ticket words, which the last arriver re-arms).  Host pointers; blocks. */
+ * launched twice on the same ticket words, which the last arriver re-arms).  n_heads / n_kv from 1 to 8 at head_dim 64 / 128,
+ * 1 / 2 / 4 / 8 at head_dim 256; anything else: BAD_INPUT.  Host pointers; blocks. */
 int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
                                      size_t n_kv, size_t head_dim, size_t seq, size_t slices, float* out, float* out2);
 

@@ -1,9 +1,9 @@
 """Qwen2 on the fused decode step against the per-op trait path and Llama-3-8B, in one process.
-Usage: python tools/qwen2_bench.py [--runs qwen2.5-7b:Q4_0,qwen2.5-7b:Q4_K_M,llama3-8b:Q4_0,qwen2.5-3b:Q4_0]
+Usage: python tools/qwen2_bench.py [--runs qwen2.5-7b:Q4_0,qwen2.5-7b:Q4_K_M,llama3-8b:Q4_0,qwen2.5-3b:Q4_0] [--at 1024[,4096...]]
 (FORMAT: a name of synth.TYPE_BY_NAME -- llama3-8b:Q6_K, llama3-8b:Q5_K -- or the recipes Q4_K_M / Q5_K_M)
 Per SHAPE:FORMAT (synthetic weights, f16 KV cache), one markdown table row:
   fused      crabml_hip_llama_decode_greedy tok/s over positions 0..127 (best of 3)
-  @1024      the same over positions 1024..1087, after a 1024-token prefill
+  @1024      the same over positions 1024..1087, after a 1024-token prefill (--at POS[,POS...]: one such column per position)
   unchanged  Llama2Runner<HipTensor>::forward + host arg-max per token (the recorded calls served by the fused step), 64 tokens
   per-op     the same runner on a CRABML_HIP_FLAG_PER_OP device (one launch per Tensor call), 16 tokens
   strict     decode_greedy on the strict-order device, positions 0..63
@@ -43,7 +43,7 @@ def runner_rate(model, mode, strict, n):
     return timed(lambda: loop(4, n), n)
 
 
-def row(spec, steps=128):
+def row(spec, steps=128, at=(1024,)):
     shape, fmt = spec.split(":")
     mix = fmt in ("Q4_K_M", "Q5_K_M")
     model = synth.build_model(synth.SHAPES[shape], synth.TYPE_BY_NAME[fmt[:4]] if mix else synth.TYPE_BY_NAME[fmt], seed=1, k_m_mix=mix)
@@ -51,21 +51,22 @@ def row(spec, steps=128):
     out = {"GB": gb}
     dev = ca.HipTensorDevice(0)
     conf, w = synth.to_hip(model, dev)
-    r = ca.HipLlamaRunner(conf, w, dev, 1024 + steps + 16, True)
+    r = ca.HipLlamaRunner(conf, w, dev, max(at) + steps + 16, True)
     r.decode_greedy(1, 8)
     best = 0.0
     for _ in range(3):
         r.reset()
         best = max(best, timed(lambda: r.decode_greedy(1, steps), steps))
     out["fused"] = best
-    prompt = [(11 * i + 5) % conf.vocab_size for i in range(1024)]
+    prompt = [(11 * i + 5) % conf.vocab_size for i in range(max(at))]
     r.reset()
     r.prefill(prompt[:512])
     r.reset()
     out["prompt"] = timed(lambda: r.prefill(prompt[:512]), 512)
-    r.reset()
-    r.prefill(prompt)
-    out["@1024"] = timed(lambda: r.decode_greedy(1, 64), 64)
+    for pos in at:
+        r.reset()
+        r.prefill(prompt[:pos])
+        out["@%d" % pos] = timed(lambda: r.decode_greedy(1, 64), 64)
     del r, w
     out["unchanged"] = runner_rate(model, "lazy", False, 64)
     out["per-op"] = runner_rate(model, "per-op", False, 16)
@@ -81,12 +82,14 @@ def row(spec, steps=128):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", default="qwen2.5-7b:Q4_0,qwen2.5-7b:Q4_K_M,llama3-8b:Q4_0,qwen2.5-3b:Q4_0")
+    ap.add_argument("--at", default="1024", help="cached positions of the long-context column(s), comma-separated")
     a = ap.parse_args()
-    cols = ["fused", "@1024", "unchanged", "per-op", "strict", "prompt"]
+    at = tuple(int(p) for p in a.at.split(","))
+    cols = ["fused"] + ["@%d" % p for p in at] + ["unchanged", "per-op", "strict", "prompt"]
     print("| shape | format | GB / token | " + " | ".join(cols) + " | fused / per-op |")
     print("|---|---|---|" + "---|" * len(cols) + "---|")
     for spec in a.runs.split(","):
-        shape, fmt, o = row(spec)
+        shape, fmt, o = row(spec, at=at)
         print("| %s | %s | %.2f | " % (shape, fmt, o["GB"]) + " | ".join("%.1f" % o[c] for c in cols) +
               " | %.2fx |" % (o["fused"] / o["per-op"]), flush=True)
 
