@@ -150,7 +150,7 @@ struct StepPlan {
   // ---- the segment forms
   bool norm_epi = false;       // Fused5: RMSNorm + quantize run in the wo / ffn_down epilogue (tp > 1: over a P2P group or in the dry run,
                                // where the epilogue hosts the collective too)
-  bool norm_epi_k = false;     // the same for Q4_K / Q5_K / Q6_K layers (Q8_K planes out of the epilogue)
+  bool norm_epi_k = false;     // the same for Q3_K / Q4_K / Q5_K / Q6_K layers (Q8_K planes out of the epilogue)
   // the hop-free norm of the fast step (Q4_0 / Q8_0 layers, one GPU): wo quantizes x * w_norm block by block and leaves 1 / rms to
   // the gate/up launch (RmsTail, gemv_core.hpp) -- no in-launch gather.  Off: CRABML_HIP_LLAMA_EXACT_NORM, strict order, tp.
   bool defer_norm = false;
@@ -411,8 +411,8 @@ NqOrdKFn nq_ord_k_kernel(int split, int qin) {
   });
   return fn;
 }
-// ... and the forms of k_gateup_k_lds<QOUT, ORD, NORMIN, BODY> that exist (NORMIN writes planes and has no ordered form; nor has a Q5_K
-// or a Q6_K body)
+// ... and the forms of k_gateup_k_lds<QOUT, ORD, NORMIN, BODY> that exist (NORMIN writes planes and has no ordered form; nor has a Q3_K,
+// a Q5_K or a Q6_K body)
 typedef decltype(&k_gateup_k_lds<false>) GateupKFn;
 template <int BODY>
 GateupKFn gateup_k_body_kernel(bool qout, bool normin) {
@@ -421,6 +421,7 @@ GateupKFn gateup_k_body_kernel(bool qout, bool normin) {
 GateupKFn gateup_k_kernel(bool qout, bool ord, bool normin, int body = CRABML_HIP_Q4_K) {
   if (body == CRABML_HIP_Q5_K) return gateup_k_body_kernel<CRABML_HIP_Q5_K>(qout, normin);
   if (body == CRABML_HIP_Q6_K) return gateup_k_body_kernel<CRABML_HIP_Q6_K>(qout, normin);
+  if (body == CRABML_HIP_Q3_K) return gateup_k_body_kernel<CRABML_HIP_Q3_K>(qout, normin);
   if (ord) return qout ? k_gateup_k_lds<true, true> : k_gateup_k_lds<false, true>;
   if (normin) return k_gateup_k_lds<true, false, true>;
   return qout ? k_gateup_k_lds<true> : k_gateup_k_lds<false>;
@@ -1022,15 +1023,17 @@ int enqueue_segment_generic(crabml_hip_llama* c, int seg) {
   return 0;
 }
 
-// Q4_K, Q5_K, Q6_K and Q4_1 layers (fast mode): the fused GEMV kernels with the format's inner loop against Q8_K / Q8_1
+// Q3_K, Q4_K, Q5_K, Q6_K and Q4_1 layers (fast mode): the fused GEMV kernels with the format's inner loop against Q8_K / Q8_1
 // activation planes.  The rhs quantizer is its own launch here (a Q8_K super-block spans 256 rows: eight 32-row
 // workgroups; Q8_1 keeps the same structure), so a layer is 11 launches instead of the per-op path's 18.
 template <int FMT>
 int enqueue_segment_k(crabml_hip_llama* c, int seg) {
-  // a K-quant body: Q4_K, or Q5_K / Q6_K -- the same five launches with the format's own row loader, built in the norm-epilogue form only
-  // (decide_step)
-  constexpr bool KF = FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
-  constexpr bool EPI_ONLY = FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
+  // a K-quant body: Q4_K, or Q3_K / Q5_K / Q6_K -- the same five launches with the format's own row loader, built in the norm-epilogue
+  // form only (decide_step).  A Q3_K body (the Q3_K_S / _M / _L recipes) has attn_v, attn_output and ffn_down in Q3_K, Q4_K or Q5_K,
+  // each tensor its own: wo and ffn_down are launched with the instantiation of the TENSOR's format, the V rows take k_qkv's hand-over.
+  constexpr bool Q3 = FMT == CRABML_HIP_Q3_K;
+  constexpr bool KF = Q3 || FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
+  constexpr bool EPI_ONLY = Q3 || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
   constexpr uint32_t QT = KF ? CRABML_HIP_Q8_K : CRABML_HIP_Q8_1;
   constexpr int BE = KF ? 256 : 32;  // elements per weight block
   typedef typename ActOf<FMT>::type Act;
@@ -1052,8 +1055,16 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
   auto act_k = [&](char* planes, int n) { return act_at<Act>(planes, act_layout(QT, (size_t)n)); };
   // a Q6_K tensor inside a Q4_K layer (attn_v / ffn_down of the *_K_M mixes): handed to the kernel beside the planes
   // (a Q6_K BODY hands over nothing: its planes are the kernel's own)
+  // (a Q3_K body never holds a Q6_K tensor: validate_weights)
   auto six = [&](const crabml_hip_buf* b) {
     return FMT != CRABML_HIP_Q6_K && b->dtype == CRABML_HIP_Q6_K ? Planes6{(const char*)b->ptr, b->wl.off_scale} : Planes6{nullptr, 0};
+  };
+  // ... and what the V matrix hands k_qkv (VOther, fused_common.hpp): a Q3_K body's, its format
+  auto v_other = [&](const crabml_hip_buf* b) {
+    if constexpr (Q3)
+      return VFormat{(int)b->dtype};
+    else
+      return six(b);
   };
   // rmsnorm * weight -> xn -> Q8_K planes (buf_q8_k.rs:84-131)
   auto norm_quant = [&](const float* wn, float eps, bool add_pending, uint32_t qt) -> const void* {
@@ -1098,17 +1109,24 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
                      a, xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
             return P1();
           }
-        with_const_else<2, 1>(split, [&](auto s) {
-          with_const_else<2, 1, 0>(qmode, [&](auto q) {  // (the rhs planes in LDS unless they are read from global memory)
-            launch_k(st, R, k_gemv_res_nq<FMT, decltype(s)::value, decltype(q)::value>, dim3(dim / 32 * split), dim3(1024), qmode ? q8k_lds_bytes(k) : 0,
-                     planes_of(w), a, xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
+        // the instantiation: the body's -- a Q3_K body's wo / ffn_down by the tensor's own dtype (Q3_K, Q4_K or Q5_K: validate_weights)
+        auto launch_nq = [&](auto wf) {
+          with_const_else<2, 1>(split, [&](auto s) {
+            with_const_else<2, 1, 0>(qmode, [&](auto q) {  // (the rhs planes in LDS unless they are read from global memory)
+              launch_k(st, R, k_gemv_res_nq<decltype(wf)::value, decltype(s)::value, decltype(q)::value>, dim3(dim / 32 * split), dim3(1024),
+                       qmode ? q8k_lds_bytes(k) : 0, planes_of(w), a, xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
+            });
           });
-        });
+        };
+        if constexpr (Q3)
+          with_const_else<CRABML_HIP_Q4_K, CRABML_HIP_Q5_K, CRABML_HIP_Q3_K>((int)w->dtype, launch_nq);
+        else
+          launch_nq(std::integral_constant<int, FMT>{});
         return P1();
       }
     }
     if constexpr (EPI_ONLY) {
-      CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a Q5_K / Q6_K body outside the norm-epilogue form (decide_step sends it to the per-op segments)");
+      CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a Q3_K / Q5_K / Q6_K body outside the norm-epilogue form (decide_step sends it to the per-op segments)");
     } else {
       if (tp)
         launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), a, dst, dim, k / BE);
@@ -1156,7 +1174,7 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
           return;
         }
       launch_k(st, R, k_qkv<FMT, false, A>, dim3((total_rows / 2 + 1) / 2), dim3(128), 0, planes_of(c->wq[l]), planes_of(c->wk[l]),
-               planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, six(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
+               planes_of(c->wv[l]), act_k(c->act_dim, dim), dim / BE, ep, v_other(c->wv[l]), RmsTail{nullptr, 0, 0.f, 0.f}, 0);
     });
     CH_TRY(P1());
     CH_TRY(TAP(tl, CRABML_HIP_TAP_QBUF, c->qbuf, (size_t)dim_l * 4));
@@ -1231,6 +1249,7 @@ int enqueue_segment(crabml_hip_llama* c, int seg) {
       return c->wtype == CRABML_HIP_Q4_K   ? enqueue_segment_k<CRABML_HIP_Q4_K>(c, seg)
              : c->wtype == CRABML_HIP_Q5_K ? enqueue_segment_k<CRABML_HIP_Q5_K>(c, seg)
              : c->wtype == CRABML_HIP_Q6_K ? enqueue_segment_k<CRABML_HIP_Q6_K>(c, seg)
+             : c->wtype == CRABML_HIP_Q3_K ? enqueue_segment_k<CRABML_HIP_Q3_K>(c, seg)
                                            : enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
     case SegPath::Fused5:
       return c->wtype == CRABML_HIP_Q4_0   ? enqueue_segment_t<CRABML_HIP_Q4_0>(c, seg)
@@ -2148,6 +2167,9 @@ struct ModelFacts {
   uint32_t wt = 0, out_wt = 0, qt = 0, out_qt = 0;  // weight type of the layers / the classifier, and their vec_dot_rhs_dtype
   bool mixed = false;                               // some layer matrix has another type than wq[0] (with the same rhs type)
   bool mix_v_down_q6k = true;  // every deviating tensor is an attn_v / ffn_down in Q6_K inside a Q4_K / Q5_K layer (the *_K_M recipe)
+  // the Q3_K recipe family (Q3_K_S / _M / _L and whatever lies between): attn_q, attn_k, ffn_gate and ffn_up Q3_K in every layer;
+  // attn_v, attn_output and ffn_down each Q3_K, Q4_K or Q5_K, chosen per layer and per tensor
+  bool q3k_family = true;
   bool split_vocab = false;
   size_t vocab_l = 0;
 };
@@ -2212,7 +2234,7 @@ static int validate_config(crabml_hip_device_t* dev, const crabml_hip_llama_conf
   return 0;
 }
 
-// type and shape of every weight.  Fused kernels exist for Q4_0 / Q8_0 / Q4_1, Q4_K, Q5_K and Q6_K layers; a classifier of another format --
+// type and shape of every weight.  Fused kernels exist for Q4_0 / Q8_0 / Q4_1, Q3_K, Q4_K, Q5_K and Q6_K layers; a classifier of another format --
 // llama.cpp's "Q4_0" files keep output.weight in Q6_K -- does not take the layers off them: the final segment quantizes the
 // normalized row for the classifier's own rhs type.
 static int validate_weights(crabml_hip_device_t* dev, const crabml_hip_llama_config_t& g, const crabml_hip_llama_weights_t* w, ModelFacts* f) {
@@ -2234,19 +2256,22 @@ static int validate_weights(crabml_hip_device_t* dev, const crabml_hip_llama_con
   };
   // a layer's matrices may differ in GGML type (llama.cpp's *_K_M files: attn_v / ffn_down in Q6_K on some layers) as
   // long as they share the rhs type (buf/api.rs:142-159: every K-quant takes Q8_K): such a model runs the per-op
-  // segments, each GEMV picking its kernel by the tensor's own dtype -- unless it is the *_K_M recipe, which the Q4_K / Q5_K kernels take
-  auto check_w = [&](const crabml_hip_buf* b, size_t m, size_t k, bool v_or_down) {
+  // segments, each GEMV picking its kernel by the tensor's own dtype -- unless it is the *_K_M recipe, which the Q4_K / Q5_K kernels
+  // take, or a member of the Q3_K recipe family (wo: attn_output, which that family lets deviate beside attn_v and ffn_down)
+  f->q3k_family = wt == CRABML_HIP_Q3_K;
+  auto check_w = [&](const crabml_hip_buf* b, size_t m, size_t k, bool v_or_down, bool wo = false) {
     if (!b) return false;
     if (b->dtype != wt) {
       if (vec_dot_rhs_dtype(b->dtype) != qt || k % block_elems(b->dtype)) return false;
       f->mixed = true;
       if (!(v_or_down && (wt == CRABML_HIP_Q4_K || wt == CRABML_HIP_Q5_K) && b->dtype == CRABML_HIP_Q6_K)) f->mix_v_down_q6k = false;
+      if (!((v_or_down || wo) && (b->dtype == CRABML_HIP_Q4_K || b->dtype == CRABML_HIP_Q5_K))) f->q3k_family = false;
     }
     return check(b, m, k, b->dtype);
   };
   for (size_t l = 0; l < g.n_layers; l++) {
     if (!check_w(w->wq[l], dim_l, dim, false) || !check_w(w->wk[l], kv_dim_l, dim, false) || !check_w(w->wv[l], kv_dim_l, dim, true) ||
-        !check_w(w->wo[l], dim, dim_l, false) || !check_w(w->ffn_gate_weight[l], hidden_l, dim, false) ||
+        !check_w(w->wo[l], dim, dim_l, false, true) || !check_w(w->ffn_gate_weight[l], hidden_l, dim, false) ||
         !check_w(w->ffn_up_weight[l], hidden_l, dim, false) || !check_w(w->ffn_down_weight[l], dim, hidden_l, true) ||
         !check(w->rms_att_weight[l], 1, dim, CRABML_HIP_F32) || !check(w->rms_ffn_weight[l], 1, dim, CRABML_HIP_F32))
       CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
@@ -2361,16 +2386,18 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   const uint32_t wt = f.wt;
   const bool fused_fmt = wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0 || wt == CRABML_HIP_Q4_1;  // a dot of one term per block
   const bool chunks_resident = dim / 32 <= n_cu;  // every workgroup of a wo / ffn_down gather must be resident
-  // the K-quant norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on, and the ONLY form a Q5_K or a
-  // Q6_K body is built in -- such a context that misses a clause of it (a classifier with another rhs, NO_NORM_EPILOGUE, a dim that is
+  // the K-quant norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on, and the ONLY form a Q3_K, a Q5_K
+  // or a Q6_K body is built in -- such a context that misses a clause of it (a classifier with another rhs, NO_NORM_EPILOGUE, a dim that is
   // no multiple of 256, chunks that are not resident) runs the per-op segments
-  const bool k_body = wt == CRABML_HIP_Q4_K || wt == CRABML_HIP_Q5_K || wt == CRABML_HIP_Q6_K;
-  const bool k_body_epi_only = wt == CRABML_HIP_Q5_K || wt == CRABML_HIP_Q6_K;
+  const bool k_body = wt == CRABML_HIP_Q3_K || wt == CRABML_HIP_Q4_K || wt == CRABML_HIP_Q5_K || wt == CRABML_HIP_Q6_K;
+  const bool k_body_epi_only = wt == CRABML_HIP_Q3_K || wt == CRABML_HIP_Q5_K || wt == CRABML_HIP_Q6_K;
   const bool k_epilogue_eligible = k_body && f.out_qt == CRABML_HIP_Q8_K && tp == 1 && !has(CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) &&
                                    dim % 256 == 0 && chunks_resident;
   const bool k_fusion = !has(CRABML_HIP_LLAMA_NO_KQUANT_FUSION);
   // the K-quant fused kernels take a Q6_K attn_v / ffn_down beside the body's planes (the *_K_M recipe), but only in the norm-epilogue form
-  const bool mix_fused = f.mixed && f.mix_v_down_q6k && !strict && k_epilogue_eligible && k_fusion;
+  // ... and a Q3_K body takes attn_v / attn_output / ffn_down in Q4_K or Q5_K (the Q3_K recipe family; f.q3k_family also holds for a plain
+  // Q3_K body, which is not mixed).  A Q3_K body with any other deviation has neither fact: per-op segments.
+  const bool mix_fused = f.mixed && (f.mix_v_down_q6k || f.q3k_family) && !strict && k_epilogue_eligible && k_fusion;
 
   // Strict order, one device, Q4_0 / Q8_0 / Q4_1: the fused launches in their block-ordered form (7 per layer: norm + quantize stay
   // their own launches).  The term tables must fit LDS: 64 rows of gate | up (k_gateup_q_ord, raised past 60 KiB), a workgroup's 16 / 32
@@ -2400,7 +2427,7 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   };
   const bool ordk = strict && wt == CRABML_HIP_Q4_K && k_epilogue_eligible && k_fusion && !has(CRABML_HIP_LLAMA_NO_RHS_PROLOGUE) && (!f.mixed || f.mix_v_down_q6k) &&
                     dim_l % 256 == 0 && hidden_l % 256 == 0 && ordk_fits();
-  // the fast K-quant segments: Q4_K always; Q5_K / Q6_K in the norm-epilogue form (neither has an ordered form: a strict-order device
+  // the fast K-quant segments: Q4_K always; Q3_K / Q5_K / Q6_K in the norm-epilogue form (none has an ordered form: a strict-order device
   // keeps them on the per-op segments; no mix recipe has a Q6_K body: mix_v_down_q6k is about Q4_K / Q5_K bodies); Q4_1 when it cannot take the five launches (a classifier of another format) or for the A/B flag
   const bool fast_k = !strict && (!f.mixed || mix_fused) && k_fusion &&
                       (wt == CRABML_HIP_Q4_K || (k_body_epi_only && k_epilogue_eligible) || (wt == CRABML_HIP_Q4_1 && (f.out_wt != wt || has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS))));
@@ -2939,7 +2966,7 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   // (decide_step: what Fused5 / FusedK and !ordered imply)
   if ((c->plan.path != SegPath::Fused5 && c->plan.path != SegPath::FusedK) || c->plan.ordered || c->tp > 1 || c->ext_kv)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
-            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 / Q4_K / Q5_K / Q6_K layers, the Q4_K_M / Q5_K_M mixes) on one device with its own KV cache");
+            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 / Q3_K / Q4_K / Q5_K / Q6_K layers, the Q4_K_M / Q5_K_M and Q3_K_S / _M / _L mixes) on one device with its own KV cache");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim;
   // the row type of every field that leaves as blocks (the others: f32 values, the plan words)

@@ -526,14 +526,28 @@ struct Planes6 {
   const char* base;
   size_t off_qh;
 };
+// What a layer's V matrix hands k_qkv beside its planes when its format is not the body's.  A Q6_K tensor in a Q4_K / Q5_K layer comes
+// whole (Planes6: its four planes do not fit Planes); the V rows of a Q3_K body (Q4_K / Q5_K: the Q3_K_M / Q3_K_L recipes) are read
+// through wv's own two planes and hand over their format only (fmt = the body's: nothing to hand over).
+struct VFormat {
+  int fmt;
+};
+template <int FMT>
+struct VOther {
+  typedef Planes6 type;
+};
+template <>
+struct VOther<CRABML_HIP_Q3_K> {
+  typedef VFormat type;
+};
 
 // DEFER: the rhs planes come from a hop-free ffn_down launch -- the row dots are multiplied by 1 / rms (RmsTail, gemv_core.hpp)
 // ARCH = QKV_QWEN2 / QKV_GEMMA: the wave's two rows are a NEOX pair (neox_pair_row0); Qwen2's biases are added after the 1 / rms multiply
 template <int FMT, bool DEFER = false, int ARCH = QKV_LLAMA>
 __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb,
-                                             typename QkvArch<ARCH>::epi e, Planes6 wv6, RmsTail rt, int upfront = 0) {
+                                             typename QkvArch<ARCH>::epi e, typename VOther<FMT>::type wv6, RmsTail rt, int upfront = 0) {
   // a K-quant body: nb counts super-blocks, rows_dot has its loader (a Q6_K body comes with wv6.base = nullptr: its V rows are the body's)
-  constexpr bool KF = FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
+  constexpr bool KF = FMT == CRABML_HIP_Q3_K || FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + wave_in_wg();
   int row0 = wave * 2, rs = 1;
@@ -564,7 +578,15 @@ __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, ty
   }
   float acc[2];
   bool done = false;
-  if constexpr (KF && FMT != CRABML_HIP_Q6_K) {
+  if constexpr (FMT == CRABML_HIP_Q3_K) {
+    if (wv6.fmt != CRABML_HIP_Q3_K && row0 >= e.dim + e.kv_dim) {  // the V rows of this layer are Q4_K or Q5_K (wave-uniform)
+      if (wv6.fmt == CRABML_HIP_Q4_K)
+        rows_dot<CRABML_HIP_Q4_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
+      else
+        rows_dot<CRABML_HIP_Q5_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
+      done = true;
+    }
+  } else if constexpr (KF && FMT != CRABML_HIP_Q6_K) {
     if (wv6.base != nullptr && row0 >= e.dim + e.kv_dim) {  // the V rows of this layer are Q6_K (wave-uniform)
       rows_partial_q6k<2>(wv6.base, wv6.off_qh, act, local, m, nb, lane, acc, nullptr, rs);
       done = true;

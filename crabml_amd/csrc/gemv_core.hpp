@@ -954,8 +954,14 @@ __device__ __forceinline__ void rows_partial_q6k_planes(const PlanesQ6& w, const
   }
 }
 
+// (the Q3_K body's rows, defined behind PieceQ3_K below: its pieces are that policy's)
+template <int R>
+__device__ __forceinline__ void rows_q3k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
+                                              int m, int nsb, int lane, float acc[R], int rs);
+
 // R rows of a weight matrix in format FMT against its activation planes (ActQ8_0 for Q4_0 / Q8_0, ActQ8_K for
-// Q4_K / Q5_K / Q6_K); `wd` is the format's second plane (f16 scales / 16-byte headers / Q5_K's and Q6_K's qh), `nu` the blocks per row
+// Q3_K / Q4_K / Q5_K / Q6_K); `wd` is the format's second plane (f16 scales / 16-byte headers / Q5_K's and Q6_K's qh / Q3_K's hmask),
+// `nu` the blocks per row
 template <int FMT, int R, class ACT>
 __device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
                                          int row0, int m, int nu, int lane, float acc[R], int rs = 1) {
@@ -965,6 +971,8 @@ __device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const uns
     rows_partial_q5k_planes<R>(planes_q5k(wq, wd), act, row0, m, nu, lane, acc, 0, rs);
   else if constexpr (FMT == CRABML_HIP_Q6_K)  // (wd: the qh plane, planes_q6k)
     rows_partial_q6k_planes<R>(planes_q6k(wq, wd), act, row0, m, nu, lane, acc, 0, rs);
+  else if constexpr (FMT == CRABML_HIP_Q3_K)  // (wd: the hmask plane, planes_q3k)
+    rows_q3k_body<R>(wq, wd, act, row0, m, nu, lane, acc, rs);
   else
     rows_partial<FMT, R>(wq, wd, act, row0, m, nu, lane, acc, rs);
 }
@@ -982,6 +990,10 @@ struct ActOf<CRABML_HIP_Q5_K> {
 };
 template <>
 struct ActOf<CRABML_HIP_Q6_K> {
+  typedef ActQ8_K type;
+};
+template <>
+struct ActOf<CRABML_HIP_Q3_K> {
   typedef ActQ8_K type;
 };
 template <>
@@ -1208,6 +1220,135 @@ struct PieceQ3_K {  // planes qs[n][64] | hmask[n][32] | (scales[12], d f16, 2 u
     return (lane & 3) == 0 ? t : 0.0f;
   }
 };
+
+// ---- the Q3_K BODY loader (attn_q / attn_k / ffn_gate / ffn_up Q3_K: k_qkv, k_gemv_res_nq, k_gateup_k_lds) -----------------------
+// PieceQ3_K's pieces on the same lanes with the same arithmetic -- piece j = lane & 3 of a super-block, (half, h) = (j >> 1, j & 1),
+// its four 2-bit fields the groups 8 half + 2 s + h -- but every byte of the super-block's 112 (110 and the record's two unused) is
+// requested ONCE, non-temporal, in 16-byte requests, and handed round its four lanes in registers:
+//   qs      lane j takes its own 16 bytes;
+//   hmask   piece j wants bytes 16 h .. + 16: quad lanes 0 and 1 take the two pieces, quad_perm [0,1,0,1] hands them to lanes 2 and 3;
+//   record  (scales[12], d, 2 unused) quad lane 2 takes it, a quad_perm broadcast hands it round.
+// Quad lane 3 requests nothing beyond qs: 28 bytes per lane instead of PieceQ3_K::load's 48.  No exchange leaves the aligned quad,
+// whose lanes are live or dead together (pieces come in fours); a clamped dead lane re-requests the row's last qs piece and nothing
+// else (its c & 3 is 3), and its values are never used.
+struct PlanesQ3 {
+  const i32x4* qs;
+  const i32x4* hm;
+  const i32x4* rec;
+};
+// a Q3_K buffer from its first two planes (off_scale = n * 64 exactly, common.hpp: the records follow the n * 32 bytes of hmask)
+__device__ __forceinline__ PlanesQ3 planes_q3k(const void* qs, const void* hm) {
+  const size_t n64 = (size_t)((const char*)hm - (const char*)qs);
+  return PlanesQ3{(const i32x4*)qs, (const i32x4*)hm, (const i32x4*)((const char*)hm + n64 / 2)};
+}
+struct Q3KPiece {
+  i32x4 qv;   // the lane's own piece
+  i32x4 aux;  // quad lanes 0, 1: a piece of hmask (0, 1); quad lane 2: the record; quad lane 3: 0
+};
+// (Addresses: a wave-uniform 64-bit row base per plane plus a 32-bit lane offset -- the hmask pieces and the record share ONE base,
+// the record's distance from it folded into the lane offset: n * 32 bytes at most, any layer matrix below 2^35 elements -- so a row
+// costs the loop two offset registers instead of three 64-bit pointers: gate | up has 64 registers for two rows in flight.)
+__device__ __forceinline__ Q3KPiece q3k_load(const PlanesQ3& w, size_t row, int nsb, int c) {
+  Q3KPiece o;
+  const size_t rb = row * (size_t)nsb;  // the row's first super-block (wave-uniform)
+  const unsigned sb = (unsigned)c >> 2, g = (unsigned)c & 3u;  // (c & 3 = lane & 3 on every live lane: rounds are 64 pieces)
+  const char* qb = (const char*)(w.qs + rb * 4);
+  const char* hb = (const char*)(w.hm + rb * 2);
+  const unsigned rec_at = (unsigned)((const char*)(w.rec + rb) - hb);
+  o.qv = __builtin_nontemporal_load((const i32x4*)(qb + (size_t)((unsigned)c * 16u)));
+  o.aux = i32x4{0, 0, 0, 0};
+  const unsigned off = g < 2u ? sb * 32u + g * 16u : rec_at + sb * 16u;
+  if (g != 3u) o.aux = __builtin_nontemporal_load((const i32x4*)(hb + (size_t)off));
+  return o;
+}
+// a quad_perm move whose every source lane is live (the quad's lanes are live or dead together): no old value to keep
+template <int CTRL>
+__device__ __forceinline__ unsigned quad_move(int v) {
+  return (unsigned)__builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, true);
+}
+// The terms of piece c of R rows (all lanes of the piece's quad take part, outside any lane-dependent branch): PieceQ3_K's integers
+// and its f32 expression -- the quad's exact integer on quad lane 0 times (f32(d) * d8), 0 on the others.  Written for gate | up's 64
+// registers with two rows in flight:
+//   - everything that depends on the lane's place in its quad is ONE shift per field kind, applied once to the exchanged words: the
+//     record's dwords by 8 h + 4 half (PieceQ3_K::scale's byte j & 3 = 2 (s & 1) + h, its nibble `half` and the two high bits at
+//     2 (2 half + s / 2) then sit at the constant bits 16 (s & 1), and 16 (s & 1) + 2 (s / 2)), hmask by 4 half (bit 4 half + s of
+//     every byte becomes bit s); the per-field shifts are immediates;
+//   - the record leaves as one register of four 6-bit scales and one of d before the hmask words are fetched;
+//   - the activation side comes group by group, each group's 16 quants and bsum serving all R rows before the next is read.
+template <int R>
+__device__ __forceinline__ void q3k_terms(const Q3KPiece (&p)[R], const ActQ8_K& act, int c, float (&t)[R]) {
+  const int sb = c >> 2, half = (c >> 1) & 1, h = c & 1;
+  const unsigned sh_rec = 8u * (unsigned)h + 4u * (unsigned)half, sh_hm = 4u * (unsigned)half;
+  unsigned scp[R];  // the piece's four 6-bit scales, field s in byte s (before the - 32)
+  unsigned dw[R];
+  unsigned hm[R][4];
+  int tot[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const unsigned a0 = quad_move<0xAA>(p[r].aux[0]) >> sh_rec, a1 = quad_move<0xAA>(p[r].aux[1]) >> sh_rec;  // quad_perm [2,2,2,2]
+    const unsigned a2 = quad_move<0xAA>(p[r].aux[2]) >> sh_rec;
+    scp[r] = 0;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+      const unsigned lo = ((s < 2 ? a0 : a1) >> (16 * (s & 1))) & 0xFu, hi = (a2 >> (16 * (s & 1) + 2 * (s >> 1))) & 3u;
+      scp[r] |= (lo | (hi << 4)) << (8 * s);
+    }
+    dw[r] = quad_move<0xAA>(p[r].aux[3]) & 0xffffu;
+#pragma unroll
+    for (int i = 0; i < 4; i++) hm[r][i] = quad_move<0x44>(p[r].aux[i]) >> sh_hm;  // quad_perm [0,1,0,1]: hmask piece c & 1
+    tot[r] = 0;
+  }
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    const int g = 8 * half + 2 * s + h;  // (kgroups_loadx's group of field s)
+    const i32x4 xq = act.q[(size_t)sb * 16 + g];
+    const int bs = (int)act.bsums[sb * 16 + g];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      int d = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const unsigned u = (((unsigned)p[r].qv[i] >> (2 * s)) & 0x03030303u) | (((hm[r][i] >> s) & 0x01010101u) << 2);
+        d = __builtin_amdgcn_sdot4((int)u, xq[i], d, false);
+      }
+      tot[r] += ((int)((scp[r] >> (8 * s)) & 0x3Fu) - 32) * (d - 4 * bs);
+    }
+  }
+  const float d8 = act.d[sb];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const float v = (h2f((unsigned short)dw[r]) * d8) * (float)quad_sum_i32(tot[r]);
+    t[r] = (c & 3) == 0 ? v : 0.0f;
+  }
+}
+// a lane adds its pieces in ascending order (then the caller's wave tree), as rows_partial_pieces does; c0: pieces below it were
+// taken by the caller (a multiple of 64)
+template <int R>
+__device__ __forceinline__ void rows_partial_q3k_planes(const PlanesQ3& w, const ActQ8_K& act, int row0, int m, int nsb, int lane,
+                                                        float acc[R], int c0 = 0, int rs = 1) {
+  if (c0 == 0) {
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = 0.f;
+  }
+  const int np = nsb * 4;
+  for (int c = c0 + lane; c < np; c += 64) {
+    Q3KPiece pw[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
+      pw[r] = q3k_load(w, (size_t)row, nsb, c);
+    }
+    float t[R];
+    q3k_terms<R>(pw, act, c, t);
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] += t[r];
+  }
+}
+template <int R>
+__device__ __forceinline__ void rows_q3k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
+                                              int m, int nsb, int lane, float acc[R], int rs) {
+  rows_partial_q3k_planes<R>(planes_q3k(wq, wd), act, row0, m, nsb, lane, acc, 0, rs);
+}
 
 // R rows of a matrix in one of those formats against its activation planes; lane l owns pieces l, l + 64, ...
 template <class P, int R>

@@ -216,6 +216,17 @@ def use_more_bits(i_layer: int, n_layers: int) -> bool:
     return i_layer < n_layers // 8 or i_layer >= 7 * n_layers // 8 or (i_layer - n_layers // 8) % 3 == 2
 
 
+def q3_k_mix_types(mix: str, i_layer: int, n_layers: int) -> Dict[str, int]:
+    """The tensors of layer `i_layer` that are not Q3_K in a dense llama model's Q3_K_S / Q3_K_M / Q3_K_L recipe (DESIGN.md holds the
+    table and where it comes from); output.weight is Q6_K in all three."""
+    assert mix in ("S", "M", "L"), mix
+    if mix == "S":
+        return {}
+    if mix == "L":
+        return {"attn_v": Q5_K, "attn_output": Q5_K, "ffn_down": Q5_K}
+    return {"attn_v": Q5_K if i_layer < 2 else Q4_K, "attn_output": Q4_K, "ffn_down": Q5_K if i_layer < n_layers // 16 else Q4_K}
+
+
 def flip_scale_signs(model: "RawModel", seed: int = 5) -> None:
     """Q4_0 blocks with d of EITHER sign, in place (what a quantizer that divides by the signed maximum produces,
     buf_q4_0.rs:96-104).  random_blocks draws every d > 0, i.e. a mean level of -0.5 d: a common-mode component in every GEMV,
@@ -230,13 +241,17 @@ def flip_scale_signs(model: "RawModel", seed: int = 5) -> None:
 
 def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional[int] = None,
                 embed_type: Optional[int] = None, tp: int = 1, output_type: Optional[int] = None,
-                k_m_mix: bool = False, tp_split_vocab: bool = False, arch: Optional[str] = None) -> RawModel:
+                k_m_mix: bool = False, tp_split_vocab: bool = False, arch: Optional[str] = None,
+                q3_k_mix: Optional[str] = None, layer_types: Optional[Dict[int, Dict[str, int]]] = None) -> RawModel:
     """All-`wtype` synthetic Llama weights with GGUF tensor names (model.rs:228-283); norms are F32
     (the loader dequantizes them, model.rs:267-282).  tp > 1: the tensors get one rank's LOCAL shard shapes
     (what crabml_amd.tp.shard_model would cut; random bytes either way -- for timing one rank of a large model
     without materialising all of it).  k_m_mix (with wtype = Q4_K or Q5_K): the tensor-type recipe of llama.cpp's Q4_K_M / Q5_K_M
     files -- attn_v and ffn_down in Q6_K on the `use_more_bits` layers, output.weight in Q6_K -- i.e. different
-    GGML types inside one layer (all with the Q8_K rhs).  arch = "qwen2" (default: the shape's): blk.N.attn_{q,k,v}.bias as F32
+    GGML types inside one layer (all with the Q8_K rhs).  q3_k_mix = "S" | "M" | "L" (with wtype = Q3_K): the recipe of llama.cpp's
+    Q3_K_S / Q3_K_M / Q3_K_L files (q3_k_mix_types), output.weight in Q6_K.  layer_types = {layer: {"attn_v": Q5_K, ...}} sets the type
+    of single layer matrices (attn_q, attn_k, attn_v, attn_output, ffn_gate, ffn_down, ffn_up) over whatever the recipe says -- a
+    2-layer test model can hold a Q5_K ffn_down, which the recipe gives to the layers below n_layers / 16 only.  arch = "qwen2" (default: the shape's): blk.N.attn_{q,k,v}.bias as F32
     N(0, 1) with a few channels per vector 20-60x larger (real Qwen2 k biases reach the hundreds), from a generator of their own:
     the weights are those of the same seed's Llama model, and Llama models stay byte-identical.  arch = "gemma": no biases, and the
     classifier tied (no output.weight) unless the shape says otherwise -- a Gemma shape's own `tied` decides, any other shape built as
@@ -259,15 +274,20 @@ def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional
 
     add("token_embd.weight", shape.vocab, shape.dim, et, 4.0)
     dim_l, kv_l, hid_l = shape.dim // tp, shape.kv_dim // tp, shape.hidden // tp
+    assert q3_k_mix is None or (wtype == Q3_K and not k_m_mix), "q3_k_mix: a Q3_K body"
     for l in range(L):
-        add(f"blk.{l}.attn_q.weight", dim_l, shape.dim, wtype)
-        add(f"blk.{l}.attn_k.weight", kv_l, shape.dim, wtype)
         wide = Q6_K if (k_m_mix and use_more_bits(l, L)) else wtype
-        add(f"blk.{l}.attn_v.weight", kv_l, shape.dim, wide)
-        add(f"blk.{l}.attn_output.weight", shape.dim, dim_l, wtype)
-        add(f"blk.{l}.ffn_gate.weight", hid_l, shape.dim, wtype)
-        add(f"blk.{l}.ffn_down.weight", shape.dim, hid_l, wide)
-        add(f"blk.{l}.ffn_up.weight", hid_l, shape.dim, wtype)
+        ty = {"attn_v": wide, "ffn_down": wide}
+        if q3_k_mix is not None:
+            ty.update(q3_k_mix_types(q3_k_mix, l, L))
+        ty.update((layer_types or {}).get(l, {}))
+        add(f"blk.{l}.attn_q.weight", dim_l, shape.dim, ty.get("attn_q", wtype))
+        add(f"blk.{l}.attn_k.weight", kv_l, shape.dim, ty.get("attn_k", wtype))
+        add(f"blk.{l}.attn_v.weight", kv_l, shape.dim, ty["attn_v"])
+        add(f"blk.{l}.attn_output.weight", shape.dim, dim_l, ty.get("attn_output", wtype))
+        add(f"blk.{l}.ffn_gate.weight", hid_l, shape.dim, ty.get("ffn_gate", wtype))
+        add(f"blk.{l}.ffn_down.weight", shape.dim, hid_l, ty["ffn_down"])
+        add(f"blk.{l}.ffn_up.weight", hid_l, shape.dim, ty.get("ffn_up", wtype))
         norm(f"blk.{l}.attn_norm.weight", shape.dim)
         norm(f"blk.{l}.ffn_norm.weight", shape.dim)
     if arch == "qwen2":
@@ -279,12 +299,12 @@ def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional
                 b[big] *= brng.uniform(20.0, 60.0, size=big.size).astype(np.float32)
                 m.tensors[f"blk.{l}.{nm}.bias"] = RawTensor(b.view(np.uint8), [n], F32)
     norm("output_norm.weight", shape.dim)
-    if tied and output_type is None and not k_m_mix:
+    if tied and output_type is None and not k_m_mix and q3_k_mix is None:
         return m
     # llama.cpp's "Q4_0" / "Q4_K_M" files keep output.weight in Q6_K: `output_type` builds that mix
     # tp_split_vocab (with tp > 1): one rank's vocabulary shard of the classifier (CRABML_HIP_LLAMA_TP_SPLIT_VOCAB)
     add("output.weight", shape.vocab // tp if tp_split_vocab else shape.vocab, shape.dim,
-        (Q6_K if k_m_mix else wtype) if output_type is None else output_type)
+        (Q6_K if (k_m_mix or q3_k_mix is not None) else wtype) if output_type is None else output_type)
     return m
 
 
