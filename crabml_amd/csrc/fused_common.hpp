@@ -528,7 +528,8 @@ struct Planes6 {
 };
 // What a layer's V matrix hands k_qkv beside its planes when its format is not the body's.  A Q6_K tensor in a Q4_K / Q5_K layer comes
 // whole (Planes6: its four planes do not fit Planes); the V rows of a Q3_K body (Q4_K / Q5_K: the Q3_K_M / Q3_K_L recipes) are read
-// through wv's own two planes and hand over their format only (fmt = the body's: nothing to hand over).
+// through wv's own two planes and hand over their format only (fmt = the body's: nothing to hand over); so are those of a Q2_K body
+// (Q3_K / Q4_K: the Q2_K and Q2_K_S recipes).
 struct VFormat {
   int fmt;
 };
@@ -540,6 +541,10 @@ template <>
 struct VOther<CRABML_HIP_Q3_K> {
   typedef VFormat type;
 };
+template <>
+struct VOther<CRABML_HIP_Q2_K> {
+  typedef VFormat type;
+};
 
 // DEFER: the rhs planes come from a hop-free ffn_down launch -- the row dots are multiplied by 1 / rms (RmsTail, gemv_core.hpp)
 // ARCH = QKV_QWEN2 / QKV_GEMMA: the wave's two rows are a NEOX pair (neox_pair_row0); Qwen2's biases are added after the 1 / rms multiply
@@ -547,7 +552,7 @@ template <int FMT, bool DEFER = false, int ARCH = QKV_LLAMA>
 __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb,
                                              typename QkvArch<ARCH>::epi e, typename VOther<FMT>::type wv6, RmsTail rt, int upfront = 0) {
   // a K-quant body: nb counts super-blocks, rows_dot has its loader (a Q6_K body comes with wv6.base = nullptr: its V rows are the body's)
-  constexpr bool KF = FMT == CRABML_HIP_Q3_K || FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
+  constexpr bool KF = FMT == CRABML_HIP_Q2_K || FMT == CRABML_HIP_Q3_K || FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + wave_in_wg();
   int row0 = wave * 2, rs = 1;
@@ -584,6 +589,14 @@ __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, ty
         rows_dot<CRABML_HIP_Q4_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
       else
         rows_dot<CRABML_HIP_Q5_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
+      done = true;
+    }
+  } else if constexpr (FMT == CRABML_HIP_Q2_K) {
+    if (wv6.fmt != CRABML_HIP_Q2_K && row0 >= e.dim + e.kv_dim) {  // the V rows of this layer are Q3_K or Q4_K (wave-uniform)
+      if (wv6.fmt == CRABML_HIP_Q4_K)
+        rows_dot<CRABML_HIP_Q4_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
+      else
+        rows_dot<CRABML_HIP_Q3_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
       done = true;
     }
   } else if constexpr (KF && FMT != CRABML_HIP_Q6_K) {

@@ -958,10 +958,14 @@ __device__ __forceinline__ void rows_partial_q6k_planes(const PlanesQ6& w, const
 template <int R>
 __device__ __forceinline__ void rows_q3k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
                                               int m, int nsb, int lane, float acc[R], int rs);
+// (and the Q2_K body's, behind PieceQ2_K)
+template <int R>
+__device__ __forceinline__ void rows_q2k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
+                                              int m, int nsb, int lane, float acc[R], int rs);
 
 // R rows of a weight matrix in format FMT against its activation planes (ActQ8_0 for Q4_0 / Q8_0, ActQ8_K for
-// Q3_K / Q4_K / Q5_K / Q6_K); `wd` is the format's second plane (f16 scales / 16-byte headers / Q5_K's and Q6_K's qh / Q3_K's hmask),
-// `nu` the blocks per row
+// Q2_K / Q3_K / Q4_K / Q5_K / Q6_K); `wd` is the format's second plane (f16 scales / 16-byte headers / Q5_K's and Q6_K's qh / Q3_K's hmask /
+// Q2_K's scale bytes), `nu` the blocks per row
 template <int FMT, int R, class ACT>
 __device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
                                          int row0, int m, int nu, int lane, float acc[R], int rs = 1) {
@@ -973,6 +977,8 @@ __device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const uns
     rows_partial_q6k_planes<R>(planes_q6k(wq, wd), act, row0, m, nu, lane, acc, 0, rs);
   else if constexpr (FMT == CRABML_HIP_Q3_K)  // (wd: the hmask plane, planes_q3k)
     rows_q3k_body<R>(wq, wd, act, row0, m, nu, lane, acc, rs);
+  else if constexpr (FMT == CRABML_HIP_Q2_K)  // (wd: the plane of scale bytes, planes_q2k)
+    rows_q2k_body<R>(wq, wd, act, row0, m, nu, lane, acc, rs);
   else
     rows_partial<FMT, R>(wq, wd, act, row0, m, nu, lane, acc, rs);
 }
@@ -994,6 +1000,10 @@ struct ActOf<CRABML_HIP_Q6_K> {
 };
 template <>
 struct ActOf<CRABML_HIP_Q3_K> {
+  typedef ActQ8_K type;
+};
+template <>
+struct ActOf<CRABML_HIP_Q2_K> {
   typedef ActQ8_K type;
 };
 template <>
@@ -1348,6 +1358,120 @@ template <int R>
 __device__ __forceinline__ void rows_q3k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
                                               int m, int nsb, int lane, float acc[R], int rs) {
   rows_partial_q3k_planes<R>(planes_q3k(wq, wd), act, row0, m, nsb, lane, acc, 0, rs);
+}
+
+// ---- the Q2_K BODY loader (attn_q / attn_k / ffn_gate / ffn_up Q2_K: k_qkv, k_gemv_res_nq, k_gateup_k_lds) -----------------------
+// PieceQ2_K's pieces on the same lanes with the same arithmetic -- piece j = lane & 3 of a super-block, (half, h) = (j >> 1, j & 1),
+// its four 2-bit fields the groups 8 half + 2 s + h -- but every byte of the super-block's 84 is requested ONCE, non-temporal, and
+// handed round its four lanes in registers:
+//   qs      lane j takes its own 16 bytes;
+//   scales  piece j wants the eight (scale | min << 4) bytes of its half: the h = 0 lanes (quad lanes 0 and 2) take them in one 8-byte
+//           request each, quad_perm [0,0,2,2] hands them to the h = 1 neighbours;
+//   record  (d f16, dmin f16): quad lane 1 takes the dword, a quad_perm broadcast hands it round.
+// Quad lane 3 requests nothing beyond qs: 21 bytes per lane on average (24 / 20 / 24 / 16) instead of PieceQ2_K::load's 28.  No exchange
+// leaves the aligned quad, whose lanes are live or dead together (pieces come in fours); a clamped dead lane re-requests the row's last
+// qs piece and nothing else (its c & 3 is 3), and its values are never used.
+struct PlanesQ2 {
+  const i32x4* qs;
+  const i32x4* sc;
+  const unsigned* rec;
+};
+// a Q2_K buffer from its first two planes (off_scale = n * 64 exactly, common.hpp: the records follow the n * 16 scale bytes)
+__device__ __forceinline__ PlanesQ2 planes_q2k(const void* qs, const void* sc) {
+  const size_t n64 = (size_t)((const char*)sc - (const char*)qs);
+  return PlanesQ2{(const i32x4*)qs, (const i32x4*)sc, (const unsigned*)((const char*)sc + n64 / 4)};
+}
+struct Q2KPiece {
+  i32x4 qv;     // the lane's own piece
+  i32x2 sc;     // quad lanes 0, 2: the eight scale bytes of half 0, 1; quad lanes 1, 3: 0
+  unsigned dm;  // quad lane 1: d | dmin << 16; the others: 0
+};
+// (Addresses as q3k_load's: a wave-uniform 64-bit row base per plane plus a 32-bit lane offset, the scale bytes and the record sharing
+// ONE base -- the record's distance from it is n * 16 bytes at most.)
+__device__ __forceinline__ Q2KPiece q2k_load(const PlanesQ2& w, size_t row, int nsb, int c) {
+  Q2KPiece o;
+  const size_t rb = row * (size_t)nsb;  // the row's first super-block (wave-uniform)
+  const unsigned sb = (unsigned)c >> 2, g = (unsigned)c & 3u;  // (c & 3 = lane & 3 on every live lane: rounds are 64 pieces)
+  const char* qb = (const char*)(w.qs + rb * 4);
+  const char* sbase = (const char*)(w.sc + rb);
+  const unsigned rec_at = (unsigned)((const char*)(w.rec + rb) - sbase);
+  o.qv = __builtin_nontemporal_load((const i32x4*)(qb + (size_t)((unsigned)c * 16u)));
+  o.sc = i32x2{0, 0};
+  o.dm = 0u;
+  if ((g & 1u) == 0u) o.sc = __builtin_nontemporal_load((const i32x2*)(sbase + (size_t)(sb * 16u + g * 4u)));  // (g * 4 = 8 half)
+  if (g == 1u) o.dm = __builtin_nontemporal_load((const unsigned*)(sbase + (size_t)(rec_at + sb * 4u)));
+  return o;
+}
+// The terms of piece c of R rows (all lanes of the piece's quad take part, outside any lane-dependent branch): PieceQ2_K's integers
+// and its ONE f32 expression per super-block -- (d8 * d) * isum - (d8 * dmin) * summs on quad lane 0, 0 on the others.  The only
+// lane-dependent shift is 8 h on the exchanged scale words (PieceQ2_K::scale_byte's byte 2 (s & 1) + h then sits at the constant bit
+// 16 (s & 1)); the activation side comes group by group, each group's 16 quants and bsum serving all R rows before the next is read.
+template <int R>
+__device__ __forceinline__ void q2k_terms(const Q2KPiece (&p)[R], const ActQ8_K& act, int c, float (&t)[R]) {
+  const int sb = c >> 2, half = (c >> 1) & 1, h = c & 1;
+  const unsigned sh = 8u * (unsigned)h;
+  unsigned s01[R], s23[R];  // the scale bytes of fields 0, 1 (bits 0 and 16) and 2, 3
+  unsigned dm[R];
+  int isum[R], summs[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    s01[r] = quad_move<0xA0>(p[r].sc[0]) >> sh;  // quad_perm [0,0,2,2]: the half's scale bytes
+    s23[r] = quad_move<0xA0>(p[r].sc[1]) >> sh;
+    dm[r] = quad_move<0x55>((int)p[r].dm);  // quad_perm [1,1,1,1]
+    isum[r] = 0;
+    summs[r] = 0;
+  }
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    const int g = 8 * half + 2 * s + h;  // (kgroups_loadx's group of field s)
+    const i32x4 xq = act.q[(size_t)sb * 16 + g];
+    const int bs = (int)act.bsums[sb * 16 + g];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      int d = 0;
+#pragma unroll
+      for (int i = 0; i < 4; i++) d = __builtin_amdgcn_sdot4((int)(((unsigned)p[r].qv[i] >> (2 * s)) & 0x03030303u), xq[i], d, false);
+      const unsigned sc = ((s < 2 ? s01[r] : s23[r]) >> (16 * (s & 1))) & 0xFFu;
+      isum[r] += (int)(sc & 15u) * d;
+      summs[r] += bs * (int)(sc >> 4);
+    }
+  }
+  const float d8 = act.d[sb];
+#pragma unroll
+  for (int r = 0; r < R; r++) {
+    const int is = quad_sum_i32(isum[r]), ms = quad_sum_i32(summs[r]);
+    const float dall = d8 * h2f((unsigned short)(dm[r] & 0xffffu)), dmin = d8 * h2f((unsigned short)(dm[r] >> 16));
+    const float v = dall * (float)is - dmin * (float)ms;
+    t[r] = (c & 3) == 0 ? v : 0.0f;
+  }
+}
+// a lane adds its pieces in ascending order (then the caller's wave tree), as rows_partial_pieces does; c0: pieces below it were
+// taken by the caller (a multiple of 64)
+template <int R>
+__device__ __forceinline__ void rows_partial_q2k_planes(const PlanesQ2& w, const ActQ8_K& act, int row0, int m, int nsb, int lane,
+                                                        float acc[R], int c0 = 0, int rs = 1) {
+  if (c0 == 0) {
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = 0.f;
+  }
+  const int np = nsb * 4;
+  for (int c = c0 + lane; c < np; c += 64) {
+    Q2KPiece pw[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
+      pw[r] = q2k_load(w, (size_t)row, nsb, c);
+    }
+    float t[R];
+    q2k_terms<R>(pw, act, c, t);
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] += t[r];
+  }
+}
+template <int R>
+__device__ __forceinline__ void rows_q2k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
+                                              int m, int nsb, int lane, float acc[R], int rs) {
+  rows_partial_q2k_planes<R>(planes_q2k(wq, wd), act, row0, m, nsb, lane, acc, 0, rs);
 }
 
 // R rows of a matrix in one of those formats against its activation planes; lane l owns pieces l, l + 64, ...

@@ -227,6 +227,15 @@ def q3_k_mix_types(mix: str, i_layer: int, n_layers: int) -> Dict[str, int]:
     return {"attn_v": Q5_K if i_layer < 2 else Q4_K, "attn_output": Q4_K, "ffn_down": Q5_K if i_layer < n_layers // 16 else Q4_K}
 
 
+def q2_k_mix_types(mix: str, i_layer: int, n_layers: int, gqa_group: int) -> Dict[str, int]:
+    """The tensors of layer `i_layer` that are not Q2_K in a dense llama model's Q2_K ("K") / Q2_K_S ("S") recipe (DESIGN.md holds the
+    table and where it comes from); gqa_group = n_heads / n_kv_heads; output.weight is Q6_K in both."""
+    assert mix in ("K", "S"), mix
+    if mix == "S":
+        return {"ffn_down": Q4_K} if i_layer < n_layers // 8 else {}
+    return {"attn_v": Q4_K if gqa_group >= 4 else Q3_K, "attn_output": Q3_K, "ffn_down": Q3_K}
+
+
 def flip_scale_signs(model: "RawModel", seed: int = 5) -> None:
     """Q4_0 blocks with d of EITHER sign, in place (what a quantizer that divides by the signed maximum produces,
     buf_q4_0.rs:96-104).  random_blocks draws every d > 0, i.e. a mean level of -0.5 d: a common-mode component in every GEMV,
@@ -242,14 +251,16 @@ def flip_scale_signs(model: "RawModel", seed: int = 5) -> None:
 def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional[int] = None,
                 embed_type: Optional[int] = None, tp: int = 1, output_type: Optional[int] = None,
                 k_m_mix: bool = False, tp_split_vocab: bool = False, arch: Optional[str] = None,
-                q3_k_mix: Optional[str] = None, layer_types: Optional[Dict[int, Dict[str, int]]] = None) -> RawModel:
+                q3_k_mix: Optional[str] = None, layer_types: Optional[Dict[int, Dict[str, int]]] = None,
+                q2_k_mix: Optional[str] = None) -> RawModel:
     """All-`wtype` synthetic Llama weights with GGUF tensor names (model.rs:228-283); norms are F32
     (the loader dequantizes them, model.rs:267-282).  tp > 1: the tensors get one rank's LOCAL shard shapes
     (what crabml_amd.tp.shard_model would cut; random bytes either way -- for timing one rank of a large model
     without materialising all of it).  k_m_mix (with wtype = Q4_K or Q5_K): the tensor-type recipe of llama.cpp's Q4_K_M / Q5_K_M
     files -- attn_v and ffn_down in Q6_K on the `use_more_bits` layers, output.weight in Q6_K -- i.e. different
     GGML types inside one layer (all with the Q8_K rhs).  q3_k_mix = "S" | "M" | "L" (with wtype = Q3_K): the recipe of llama.cpp's
-    Q3_K_S / Q3_K_M / Q3_K_L files (q3_k_mix_types), output.weight in Q6_K.  layer_types = {layer: {"attn_v": Q5_K, ...}} sets the type
+    Q3_K_S / Q3_K_M / Q3_K_L files (q3_k_mix_types), output.weight in Q6_K.  q2_k_mix = "K" | "S" (with wtype = Q2_K): the recipe of
+    llama.cpp's Q2_K / Q2_K_S files (q2_k_mix_types), output.weight in Q6_K.  layer_types = {layer: {"attn_v": Q5_K, ...}} sets the type
     of single layer matrices (attn_q, attn_k, attn_v, attn_output, ffn_gate, ffn_down, ffn_up) over whatever the recipe says -- a
     2-layer test model can hold a Q5_K ffn_down, which the recipe gives to the layers below n_layers / 16 only.  arch = "qwen2" (default: the shape's): blk.N.attn_{q,k,v}.bias as F32
     N(0, 1) with a few channels per vector 20-60x larger (real Qwen2 k biases reach the hundreds), from a generator of their own:
@@ -275,11 +286,14 @@ def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional
     add("token_embd.weight", shape.vocab, shape.dim, et, 4.0)
     dim_l, kv_l, hid_l = shape.dim // tp, shape.kv_dim // tp, shape.hidden // tp
     assert q3_k_mix is None or (wtype == Q3_K and not k_m_mix), "q3_k_mix: a Q3_K body"
+    assert q2_k_mix is None or (wtype == Q2_K and not k_m_mix and q3_k_mix is None), "q2_k_mix: a Q2_K body"
     for l in range(L):
         wide = Q6_K if (k_m_mix and use_more_bits(l, L)) else wtype
         ty = {"attn_v": wide, "ffn_down": wide}
         if q3_k_mix is not None:
             ty.update(q3_k_mix_types(q3_k_mix, l, L))
+        if q2_k_mix is not None:
+            ty.update(q2_k_mix_types(q2_k_mix, l, L, shape.n_heads // shape.n_kv_heads))
         ty.update((layer_types or {}).get(l, {}))
         add(f"blk.{l}.attn_q.weight", dim_l, shape.dim, ty.get("attn_q", wtype))
         add(f"blk.{l}.attn_k.weight", kv_l, shape.dim, ty.get("attn_k", wtype))
@@ -299,12 +313,13 @@ def build_model(shape: ModelShape, wtype: int, seed: int = 8, n_layers: Optional
                 b[big] *= brng.uniform(20.0, 60.0, size=big.size).astype(np.float32)
                 m.tensors[f"blk.{l}.{nm}.bias"] = RawTensor(b.view(np.uint8), [n], F32)
     norm("output_norm.weight", shape.dim)
-    if tied and output_type is None and not k_m_mix and q3_k_mix is None:
+    recipe = k_m_mix or q3_k_mix is not None or q2_k_mix is not None
+    if tied and output_type is None and not recipe:
         return m
     # llama.cpp's "Q4_0" / "Q4_K_M" files keep output.weight in Q6_K: `output_type` builds that mix
     # tp_split_vocab (with tp > 1): one rank's vocabulary shard of the classifier (CRABML_HIP_LLAMA_TP_SPLIT_VOCAB)
     add("output.weight", shape.vocab // tp if tp_split_vocab else shape.vocab, shape.dim,
-        (Q6_K if (k_m_mix or q3_k_mix is not None) else wtype) if output_type is None else output_type)
+        (Q6_K if recipe else wtype) if output_type is None else output_type)
     return m
 
 

@@ -198,10 +198,11 @@ int crabml_hip_batch_matmul(crabml_hip_device_t* dev, const crabml_hip_buf_t* a,
  * row sums past 1024 positions) are summed wave-parallel, exactly like crabml_hip_matmul_vec.  With
  * CRABML_HIP_FLAG_STRICT_ORDER every sum runs in the reference's scalar order and the step is bit-identical
  * to the reference at every context length.
- * Weights: layer matrices in any matmul_vec format (Q4_0, Q8_0, Q4_1, Q3_K, Q4_K, Q5_K and Q6_K run fused kernels, Q4_K and Q5_K also
+ * Weights: layer matrices in any matmul_vec format (Q4_0, Q8_0, Q4_1, Q2_K, Q3_K, Q4_K, Q5_K and Q6_K run fused kernels, Q4_K and Q5_K also
  * with attn_v / ffn_down in Q6_K -- llama.cpp's *_K_M mixes --, Q3_K also with attn_v / attn_output / ffn_down in Q4_K or Q5_K --
- * its Q3_K_S / _M / _L recipes; Q3_K, Q5_K and an all-Q6_K body on one device without
- * CRABML_HIP_FLAG_STRICT_ORDER and with a K-quant classifier, else as below; Q5_0, Q5_1, Q2_K, Q8_K, F16, F32, a Q3_K or Q6_K body
+ * its Q3_K_S / _M / _L recipes --, Q2_K also with those three tensors in Q3_K or Q4_K -- its Q2_K / Q2_K_S recipes; Q2_K, Q3_K, Q5_K
+ * and an all-Q6_K body on one device without
+ * CRABML_HIP_FLAG_STRICT_ORDER and with a K-quant classifier, else as below; Q5_0, Q5_1, Q8_K, F16, F32, a Q2_K, Q3_K or Q6_K body
  * with a layer tensor outside those sets and any other mix sharing
  * one rhs dtype run as per-op segments inside the same graph); the classifier may have another format; norm
  * weights F32.  Tensor types whose rhs dtypes differ inside a layer: CRABML_HIP_NOT_IMPLEMENTED (use the

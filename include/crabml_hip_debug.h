@@ -144,7 +144,8 @@ int crabml_hip_llama_debug_kv(crabml_hip_llama_t* ctx, size_t layer, int32_t whi
  * of layer `layer` copied out as each launch of that layer left them: stream-ordered device-to-device copies into a scratch area
  * (allocated on the first tap of a context) placed between the launches, brought to the host after the step.  The step runs to
  * its end as always; logits (vocab_size floats, nullable) come back as from forward.  Serves the five-launch layers of
- * enqueue_segment_t (Q4_0 / Q8_0 / Q4_1) and the K-quant layers of enqueue_segment_k (Q4_K, the Q4_K_M mix, Q4_1 in front of a
+ * enqueue_segment_t (Q4_0 / Q8_0 / Q4_1) and the K-quant layers of enqueue_segment_k (Q4_K, the Q4_K_M mix, Q5_K and Q5_K_M, an
+ * all-Q6_K body, the Q3_K family (Q3_K_S / _M / _L) and the Q2_K family (plain Q2_K, the Q2_K / Q2_K_S recipes), Q4_1 in front of a
  * classifier of another format) on one device, fast tier; tensor-parallel ranks, the per-op path, the strict-order device and a
  * context the recorded-op queue drives on the runner's own KV cache return CRABML_HIP_NOT_IMPLEMENTED.
  * dst / dir: field f occupies dir[f].bytes bytes at dst + dir[f].offset (bytes = 0: the context has no such buffer, e.g. rsums

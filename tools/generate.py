@@ -22,7 +22,7 @@ from crabml_amd import synth
 
 ap = argparse.ArgumentParser()
 ap.add_argument("gguf", nargs="?")
-ap.add_argument("--synth", default=None, help="SHAPE:TYPE, e.g. tiny-gqa:Q4_0, llama3-8b:Q4_K_M, llama3-8b:Q5_K_M, llama3-8b:Q6_K, llama3-8b:Q3_K_M, qwen2.5-7b:Q4_0, gemma-2b:Q8_0")
+ap.add_argument("--synth", default=None, help="SHAPE:TYPE, e.g. tiny-gqa:Q4_0, llama3-8b:Q4_K_M, llama3-8b:Q5_K_M, llama3-8b:Q6_K, llama3-8b:Q3_K_M, llama3-8b:Q2_K, llama3-8b:Q2_K_MIX (llama.cpp's Q2_K recipe), llama3-8b:Q2_K_S, qwen2.5-7b:Q4_0, gemma-2b:Q8_0")
 ap.add_argument("--prompt", default="1,365,400,282,7,9,11,13")
 ap.add_argument("--steps", type=int, default=32)
 ap.add_argument("--seq-len", type=int, default=0)
@@ -39,8 +39,9 @@ if a.synth:
     shape_name, typ = a.synth.split(":")
     k_m = typ.upper() in ("Q4_K_M", "Q5_K_M")  # llama.cpp's recipes: the body type with attn_v / ffn_down / output.weight in Q6_K
     q3 = typ.upper()[5:] if typ.upper() in ("Q3_K_S", "Q3_K_M", "Q3_K_L") else None  # ... and the Q3_K recipes (synth.q3_k_mix_types)
-    model = synth.build_model(synth.SHAPES[shape_name], synth.TYPE_BY_NAME[typ.upper()[:4]] if k_m or q3 else synth.TYPE_BY_NAME[typ], seed=8,
-                              k_m_mix=k_m, q3_k_mix=q3)
+    q2 = {"Q2_K_MIX": "K", "Q2_K_S": "S"}.get(typ.upper())  # ... and the Q2_K recipes (synth.q2_k_mix_types; plain Q2_K: every matrix Q2_K)
+    model = synth.build_model(synth.SHAPES[shape_name], synth.TYPE_BY_NAME[typ.upper()[:4]] if k_m or q3 or q2 else synth.TYPE_BY_NAME[typ], seed=8,
+                              k_m_mix=k_m, q3_k_mix=q3, q2_k_mix=q2)
     tmp = tempfile.TemporaryDirectory()
     path = os.path.join(tmp.name, "model.gguf")
     synth.write_gguf(model, path)

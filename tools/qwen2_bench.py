@@ -1,6 +1,7 @@
 """Qwen2 on the fused decode step against the per-op trait path and Llama-3-8B, in one process.
 Usage: python tools/qwen2_bench.py [--runs qwen2.5-7b:Q4_0,qwen2.5-7b:Q4_K_M,llama3-8b:Q4_0,qwen2.5-3b:Q4_0] [--at 1024[,4096...]]
-(FORMAT: a name of synth.TYPE_BY_NAME -- llama3-8b:Q6_K, llama3-8b:Q5_K -- or the recipes Q4_K_M / Q5_K_M / Q3_K_S / Q3_K_M / Q3_K_L)
+(FORMAT: a name of synth.TYPE_BY_NAME -- llama3-8b:Q6_K, llama3-8b:Q5_K -- or the recipes Q4_K_M / Q5_K_M / Q3_K_S / Q3_K_M / Q3_K_L / Q2_K_MIX (llama.cpp's "Q2_K"
+file type; plain Q2_K is every layer matrix in Q2_K) / Q2_K_S)
 Per SHAPE:FORMAT (synthetic weights, f16 KV cache), one markdown table row:
   fused      crabml_hip_llama_decode_greedy tok/s over positions 0..127 (best of 3)
   @1024      the same over positions 1024..1087, after a 1024-token prefill (--at POS[,POS...]: one such column per position)
@@ -47,8 +48,9 @@ def row(spec, steps=128, at=(1024,)):
     shape, fmt = spec.split(":")
     mix = fmt in ("Q4_K_M", "Q5_K_M")
     q3 = fmt[5:] if fmt in ("Q3_K_S", "Q3_K_M", "Q3_K_L") else None
-    model = synth.build_model(synth.SHAPES[shape], synth.TYPE_BY_NAME[fmt[:4]] if mix or q3 else synth.TYPE_BY_NAME[fmt], seed=1, k_m_mix=mix,
-                              q3_k_mix=q3)
+    q2 = {"Q2_K_MIX": "K", "Q2_K_S": "S"}.get(fmt)
+    model = synth.build_model(synth.SHAPES[shape], synth.TYPE_BY_NAME[fmt[:4]] if mix or q3 or q2 else synth.TYPE_BY_NAME[fmt], seed=1, k_m_mix=mix,
+                              q3_k_mix=q3, q2_k_mix=q2)
     gb = model.gemv_weight_bytes_per_token() / 1e9
     out = {"GB": gb}
     dev = ca.HipTensorDevice(0)
