@@ -150,7 +150,7 @@ struct StepPlan {
   // ---- the segment forms
   bool norm_epi = false;       // Fused5: RMSNorm + quantize run in the wo / ffn_down epilogue (tp > 1: over a P2P group or in the dry run,
                                // where the epilogue hosts the collective too)
-  bool norm_epi_k = false;     // the same for Q2_K / Q3_K / Q4_K / Q5_K / Q6_K layers (Q8_K planes out of the epilogue)
+  bool norm_epi_k = false;     // the same for a K-quant body's layers (Q8_K planes out of the epilogue)
   // the hop-free norm of the fast step (Q4_0 / Q8_0 layers, one GPU): wo quantizes x * w_norm block by block and leaves 1 / rms to
   // the gate/up launch (RmsTail, gemv_core.hpp) -- no in-launch gather.  Off: CRABML_HIP_LLAMA_EXACT_NORM, strict order, tp.
   bool defer_norm = false;
@@ -411,21 +411,57 @@ NqOrdKFn nq_ord_k_kernel(int split, int qin) {
   });
   return fn;
 }
-// ... and the forms of k_gateup_k_lds<QOUT, ORD, NORMIN, BODY> that exist (NORMIN writes planes and has no ordered form; nor has a Q2_K,
-// a Q3_K, a Q5_K or a Q6_K body)
-typedef decltype(&k_gateup_k_lds<false>) GateupKFn;
-template <int BODY>
-GateupKFn gateup_k_body_kernel(bool qout, bool normin) {
-  return normin ? k_gateup_k_lds<true, false, true, BODY> : qout ? k_gateup_k_lds<true, false, false, BODY> : k_gateup_k_lds<false, false, false, BODY>;
+// ---- the K-quant bodies of the fused step: THE list ----------------------------------------------------------------------------
+// A format named here has its launches instantiated, dispatched (enqueue_segment, gateup_k_kernel, gemv_out), admitted with its mixes
+// (validate_weights) and routed (decide_step).  Everything a row says comes from the format's device policy (KBody, gemv_core.hpp).
+typedef FmtList<CRABML_HIP_Q4_K, CRABML_HIP_Q5_K, CRABML_HIP_Q6_K, CRABML_HIP_Q3_K, CRABML_HIP_Q2_K> KBodies;
+struct KBodyRow {
+  int fmt;
+  bool epi_only;  // built in the norm-epilogue form only
+  bool v_whole;   // an alternate comes as its whole buffer, attn_v and ffn_down only; else attn_v, attn_output and ffn_down by their own format
+  int n_alt;
+  int alt[2];     // VAlt: the formats those tensors may have beside fmt
+  bool takes(uint32_t t) const {
+    for (int i = 0; i < n_alt; i++)
+      if ((uint32_t)alt[i] == t) return true;
+    return false;
+  }
+};
+template <int FMT, int... ALT>
+constexpr KBodyRow k_body_row(FmtList<ALT...>) {
+  return KBodyRow{FMT, KBody<FMT>::EPI_ONLY, KBody<FMT>::V_WHOLE, (int)sizeof...(ALT), {ALT...}};
 }
+template <int... FMTS>
+const KBodyRow* k_body_of(FmtList<FMTS...>, uint32_t t) {
+  static constexpr KBodyRow rows[] = {k_body_row<FMTS>(typename KBody<FMTS>::VAlt{})...};
+  for (const KBodyRow& r : rows)
+    if ((uint32_t)r.fmt == t) return &r;
+  return nullptr;
+}
+// the row of format t, nullptr when t is no K-quant body
+const KBodyRow* k_body_of(uint32_t t) { return k_body_of(KBodies{}, t); }
+// f(integral_constant<format>) for the format of the list that v names; false when it names none
+template <int... FMTS, class F>
+bool with_fmt(FmtList<FMTS...>, int v, F&& f) {
+  return with_const<FMTS...>(v, f);
+}
+// ... and for a tensor of a BODY's layer that is launched by its own format: one of the body's alternates, else the body's
+template <int BODY, int... ALT, class F>
+void with_body_or_alt(FmtList<ALT...>, int v, F&& f) {
+  with_const_else<ALT..., BODY>(v, f);
+}
+
+// ... and the forms of k_gateup_k_lds<QOUT, ORD, NORMIN, BODY> that exist (NORMIN writes planes and has no ordered form; nor has a body
+// other than Q4_K)
+typedef decltype(&k_gateup_k_lds<false>) GateupKFn;
 GateupKFn gateup_k_kernel(bool qout, bool ord, bool normin, int body = CRABML_HIP_Q4_K) {
-  if (body == CRABML_HIP_Q5_K) return gateup_k_body_kernel<CRABML_HIP_Q5_K>(qout, normin);
-  if (body == CRABML_HIP_Q6_K) return gateup_k_body_kernel<CRABML_HIP_Q6_K>(qout, normin);
-  if (body == CRABML_HIP_Q3_K) return gateup_k_body_kernel<CRABML_HIP_Q3_K>(qout, normin);
-  if (body == CRABML_HIP_Q2_K) return gateup_k_body_kernel<CRABML_HIP_Q2_K>(qout, normin);
   if (ord) return qout ? k_gateup_k_lds<true, true> : k_gateup_k_lds<false, true>;
-  if (normin) return k_gateup_k_lds<true, false, true>;
-  return qout ? k_gateup_k_lds<true> : k_gateup_k_lds<false>;
+  GateupKFn fn = nullptr;
+  with_fmt(KBodies{}, body, [&](auto b) {
+    constexpr int BODY = decltype(b)::value;
+    fn = normin ? k_gateup_k_lds<true, false, true, BODY> : qout ? k_gateup_k_lds<true, false, false, BODY> : k_gateup_k_lds<false, false, false, BODY>;
+  });
+  return fn;
 }
 
 }  // namespace
@@ -1024,18 +1060,16 @@ int enqueue_segment_generic(crabml_hip_llama* c, int seg) {
   return 0;
 }
 
-// Q2_K, Q3_K, Q4_K, Q5_K, Q6_K and Q4_1 layers (fast mode): the fused GEMV kernels with the format's inner loop against Q8_K / Q8_1
+// K-quant bodies (KBodies above) and Q4_1 layers (fast mode): the fused GEMV kernels with the format's inner loop against Q8_K / Q8_1
 // activation planes.  The rhs quantizer is its own launch here (a Q8_K super-block spans 256 rows: eight 32-row
 // workgroups; Q8_1 keeps the same structure), so a layer is 11 launches instead of the per-op path's 18.
 template <int FMT>
 int enqueue_segment_k(crabml_hip_llama* c, int seg) {
-  // a K-quant body: Q4_K, or Q2_K / Q3_K / Q5_K / Q6_K -- the same five launches with the format's own row loader, built in the norm-epilogue
-  // form only (decide_step).  A Q3_K body (the Q3_K_S / _M / _L recipes) has attn_v, attn_output and ffn_down in Q3_K, Q4_K or Q5_K,
-  // each tensor its own: wo and ffn_down are launched with the instantiation of the TENSOR's format, the V rows take k_qkv's hand-over.
-  // A Q2_K body (plain, the Q2_K / Q2_K_S recipes) has the same three tensors in Q2_K, Q3_K or Q4_K, served the same way.
-  constexpr bool Q3 = FMT == CRABML_HIP_Q3_K, Q2 = FMT == CRABML_HIP_Q2_K;
-  constexpr bool KF = Q2 || Q3 || FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
-  constexpr bool EPI_ONLY = Q2 || Q3 || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
+  // a K-quant body: the same five launches with the format's own row loader (its policy, KBody); an EPI_ONLY body is built in the
+  // norm-epilogue form only (decide_step).  A body whose alternates do not come whole (V_WHOLE false: the Q3_K and the Q2_K recipe
+  // families) has attn_v, attn_output and ffn_down each in its own format or one of VAlt: wo and ffn_down are launched with the
+  // instantiation of the TENSOR's format, the V rows take k_qkv's hand-over.
+  constexpr bool KF = KBody<FMT>::IS, EPI_ONLY = KBody<FMT>::EPI_ONLY;
   constexpr uint32_t QT = KF ? CRABML_HIP_Q8_K : CRABML_HIP_Q8_1;
   constexpr int BE = KF ? 256 : 32;  // elements per weight block
   typedef typename ActOf<FMT>::type Act;
@@ -1055,15 +1089,14 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
   };
   auto P1 = [&]() { return prof ? prof_end(dev, &pr) : 0; };
   auto act_k = [&](char* planes, int n) { return act_at<Act>(planes, act_layout(QT, (size_t)n)); };
-  // a Q6_K tensor inside a Q4_K layer (attn_v / ffn_down of the *_K_M mixes): handed to the kernel beside the planes
-  // (a Q6_K BODY hands over nothing: its planes are the kernel's own)
-  // (a Q2_K or Q3_K body never holds a Q6_K tensor: validate_weights)
+  // a Q6_K tensor inside a layer whose body takes it whole (attn_v / ffn_down of the *_K_M mixes): handed to the kernel beside the planes
+  // (no other body ever holds one beside its own format: validate_weights)
   auto six = [&](const crabml_hip_buf* b) {
-    return FMT != CRABML_HIP_Q6_K && b->dtype == CRABML_HIP_Q6_K ? Planes6{(const char*)b->ptr, b->wl.off_scale} : Planes6{nullptr, 0};
+    return kbody_takes_q6k<FMT> && b->dtype == CRABML_HIP_Q6_K ? Planes6{(const char*)b->ptr, b->wl.off_scale} : Planes6{nullptr, 0};
   };
-  // ... and what the V matrix hands k_qkv (VOther, fused_common.hpp): a Q2_K or Q3_K body's, its format
+  // ... and what the V matrix hands k_qkv (VOther, fused_common.hpp): its format where the alternates do not come whole
   auto v_other = [&](const crabml_hip_buf* b) {
-    if constexpr (Q3 || Q2)
+    if constexpr (!KBody<FMT>::V_WHOLE)
       return VFormat{(int)b->dtype};
     else
       return six(b);
@@ -1111,8 +1144,8 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
                      a, xin, c->x, wnext, eps_next, oq, od, ob, ng, k / BE, six(w), NoTp{});
             return P1();
           }
-        // the instantiation: the body's -- a Q3_K body's wo / ffn_down by the tensor's own dtype (Q3_K, Q4_K or Q5_K: validate_weights),
-        // a Q2_K body's likewise (Q2_K, Q3_K or Q4_K)
+        // the instantiation: the body's -- or the tensor's own (the body's format or one of its VAlt: validate_weights) where the
+        // alternates do not come whole
         auto launch_nq = [&](auto wf) {
           with_const_else<2, 1>(split, [&](auto s) {
             with_const_else<2, 1, 0>(qmode, [&](auto q) {  // (the rhs planes in LDS unless they are read from global memory)
@@ -1121,17 +1154,15 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
             });
           });
         };
-        if constexpr (Q3)
-          with_const_else<CRABML_HIP_Q4_K, CRABML_HIP_Q5_K, CRABML_HIP_Q3_K>((int)w->dtype, launch_nq);
-        else if constexpr (Q2)
-          with_const_else<CRABML_HIP_Q4_K, CRABML_HIP_Q3_K, CRABML_HIP_Q2_K>((int)w->dtype, launch_nq);
+        if constexpr (!KBody<FMT>::V_WHOLE)
+          with_body_or_alt<FMT>(typename KBody<FMT>::VAlt{}, (int)w->dtype, launch_nq);
         else
           launch_nq(std::integral_constant<int, FMT>{});
         return P1();
       }
     }
     if constexpr (EPI_ONLY) {
-      CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a Q2_K / Q3_K / Q5_K / Q6_K body outside the norm-epilogue form (decide_step sends it to the per-op segments)");
+      CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a K-quant body that exists in the norm-epilogue form only, outside it (decide_step sends it to the per-op segments)");
     } else {
       if (tp)
         launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), a, dst, dim, k / BE);
@@ -1251,12 +1282,11 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
 int enqueue_segment(crabml_hip_llama* c, int seg) {
   switch (c->plan.path) {
     case SegPath::FusedK:
-      return c->wtype == CRABML_HIP_Q4_K   ? enqueue_segment_k<CRABML_HIP_Q4_K>(c, seg)
-             : c->wtype == CRABML_HIP_Q5_K ? enqueue_segment_k<CRABML_HIP_Q5_K>(c, seg)
-             : c->wtype == CRABML_HIP_Q6_K ? enqueue_segment_k<CRABML_HIP_Q6_K>(c, seg)
-             : c->wtype == CRABML_HIP_Q3_K ? enqueue_segment_k<CRABML_HIP_Q3_K>(c, seg)
-             : c->wtype == CRABML_HIP_Q2_K ? enqueue_segment_k<CRABML_HIP_Q2_K>(c, seg)
-                                           : enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
+    {
+      int rc = 0;
+      if (with_fmt(KBodies{}, (int)c->wtype, [&](auto body) { rc = enqueue_segment_k<decltype(body)::value>(c, seg); })) return rc;
+      return enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
+    }
     case SegPath::Fused5:
       return c->wtype == CRABML_HIP_Q4_0   ? enqueue_segment_t<CRABML_HIP_Q4_0>(c, seg)
              : c->wtype == CRABML_HIP_Q8_0 ? enqueue_segment_t<CRABML_HIP_Q8_0>(c, seg)
@@ -2172,13 +2202,10 @@ struct ModelFacts {
   const crabml_hip_buf* outw = nullptr;                                             // the classifier: output.weight, else the embedding
   uint32_t wt = 0, out_wt = 0, qt = 0, out_qt = 0;  // weight type of the layers / the classifier, and their vec_dot_rhs_dtype
   bool mixed = false;                               // some layer matrix has another type than wq[0] (with the same rhs type)
-  bool mix_v_down_q6k = true;  // every deviating tensor is an attn_v / ffn_down in Q6_K inside a Q4_K / Q5_K layer (the *_K_M recipe)
-  // the Q3_K recipe family (Q3_K_S / _M / _L and whatever lies between): attn_q, attn_k, ffn_gate and ffn_up Q3_K in every layer;
-  // attn_v, attn_output and ffn_down each Q3_K, Q4_K or Q5_K, chosen per layer and per tensor
-  bool q3k_family = true;
-  // the Q2_K recipe family (plain Q2_K, the Q2_K / Q2_K_S recipes and whatever lies between): the same four tensors Q2_K in every layer;
-  // attn_v, attn_output and ffn_down each Q2_K, Q3_K or Q4_K
-  bool q2k_family = true;
+  // every deviating tensor is one the layers' K-quant body takes beside its own format (its row of the table: k_body_of / KBody::VAlt)
+  // -- attn_v or ffn_down, and attn_output too where the alternates do not come whole -- in one of the row's formats
+  bool family_ok = true;
+  bool mix_v_down_q6k = true;  // ... and they come whole: an attn_v / ffn_down in Q6_K inside a Q4_K / Q5_K layer (the *_K_M recipe)
   bool split_vocab = false;
   size_t vocab_l = 0;
 };
@@ -2243,7 +2270,7 @@ static int validate_config(crabml_hip_device_t* dev, const crabml_hip_llama_conf
   return 0;
 }
 
-// type and shape of every weight.  Fused kernels exist for Q4_0 / Q8_0 / Q4_1, Q2_K, Q3_K, Q4_K, Q5_K and Q6_K layers; a classifier of another format --
+// type and shape of every weight.  Fused kernels exist for Q4_0 / Q8_0 / Q4_1 and the K-quant bodies (KBodies); a classifier of another format --
 // llama.cpp's "Q4_0" files keep output.weight in Q6_K -- does not take the layers off them: the final segment quantizes the
 // normalized row for the classifier's own rhs type.
 static int validate_weights(crabml_hip_device_t* dev, const crabml_hip_llama_config_t& g, const crabml_hip_llama_weights_t* w, ModelFacts* f) {
@@ -2265,19 +2292,18 @@ static int validate_weights(crabml_hip_device_t* dev, const crabml_hip_llama_con
   };
   // a layer's matrices may differ in GGML type (llama.cpp's *_K_M files: attn_v / ffn_down in Q6_K on some layers) as
   // long as they share the rhs type (buf/api.rs:142-159: every K-quant takes Q8_K): such a model runs the per-op
-  // segments, each GEMV picking its kernel by the tensor's own dtype -- unless it is the *_K_M recipe, which the Q4_K / Q5_K kernels
-  // take, or a member of the Q3_K or of the Q2_K recipe family (wo: attn_output, which those families let deviate beside attn_v and
-  // ffn_down)
-  f->q3k_family = wt == CRABML_HIP_Q3_K;
-  f->q2k_family = wt == CRABML_HIP_Q2_K;
+  // segments, each GEMV picking its kernel by the tensor's own dtype -- unless every deviating tensor is one the body takes (its
+  // row: the *_K_M recipes of a Q4_K / Q5_K body, the Q3_K and the Q2_K recipe families; wo: attn_output, which may deviate beside
+  // attn_v and ffn_down where the alternates do not come whole)
+  const KBodyRow* const body = k_body_of(wt);
   auto check_w = [&](const crabml_hip_buf* b, size_t m, size_t k, bool v_or_down, bool wo = false) {
     if (!b) return false;
     if (b->dtype != wt) {
       if (vec_dot_rhs_dtype(b->dtype) != qt || k % block_elems(b->dtype)) return false;
       f->mixed = true;
-      if (!(v_or_down && (wt == CRABML_HIP_Q4_K || wt == CRABML_HIP_Q5_K) && b->dtype == CRABML_HIP_Q6_K)) f->mix_v_down_q6k = false;
-      if (!((v_or_down || wo) && (b->dtype == CRABML_HIP_Q4_K || b->dtype == CRABML_HIP_Q5_K))) f->q3k_family = false;
-      if (!((v_or_down || wo) && (b->dtype == CRABML_HIP_Q3_K || b->dtype == CRABML_HIP_Q4_K))) f->q2k_family = false;
+      const bool taken = body && (v_or_down || (wo && !body->v_whole)) && body->takes(b->dtype);
+      if (!taken) f->family_ok = false;
+      if (!(taken && body->v_whole)) f->mix_v_down_q6k = false;
     }
     return check(b, m, k, b->dtype);
   };
@@ -2398,19 +2424,17 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   const uint32_t wt = f.wt;
   const bool fused_fmt = wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0 || wt == CRABML_HIP_Q4_1;  // a dot of one term per block
   const bool chunks_resident = dim / 32 <= n_cu;  // every workgroup of a wo / ffn_down gather must be resident
-  // the K-quant norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on, and the ONLY form a Q2_K, a Q3_K,
-  // a Q5_K or a Q6_K body is built in -- such a context that misses a clause of it (a classifier with another rhs, NO_NORM_EPILOGUE, a dim that is
-  // no multiple of 256, chunks that are not resident) runs the per-op segments
-  const bool k_body_epi_only = wt == CRABML_HIP_Q2_K || wt == CRABML_HIP_Q3_K || wt == CRABML_HIP_Q5_K || wt == CRABML_HIP_Q6_K;
-  const bool k_body = wt == CRABML_HIP_Q4_K || k_body_epi_only;
+  // the K-quant norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on, and the ONLY form an EPI_ONLY
+  // body (its row of the table, k_body_of) is built in -- such a context that misses a clause of it (a classifier with another rhs,
+  // NO_NORM_EPILOGUE, a dim that is no multiple of 256, chunks that are not resident) runs the per-op segments
+  const KBodyRow* const body = k_body_of(wt);
+  const bool k_body = body != nullptr, k_body_epi_only = k_body && body->epi_only;
   const bool k_epilogue_eligible = k_body && f.out_qt == CRABML_HIP_Q8_K && tp == 1 && !has(CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) &&
                                    dim % 256 == 0 && chunks_resident;
   const bool k_fusion = !has(CRABML_HIP_LLAMA_NO_KQUANT_FUSION);
-  // the K-quant fused kernels take a Q6_K attn_v / ffn_down beside the body's planes (the *_K_M recipe), but only in the norm-epilogue form
-  // ... and a Q3_K body takes attn_v / attn_output / ffn_down in Q4_K or Q5_K (the Q3_K recipe family; f.q3k_family also holds for a plain
-  // Q3_K body, which is not mixed).  A Q3_K body with any other deviation has neither fact: per-op segments.
-  // ... and a Q2_K body takes the same three tensors in Q3_K or Q4_K (f.q2k_family, the same way).
-  const bool mix_fused = f.mixed && (f.mix_v_down_q6k || f.q3k_family || f.q2k_family) && !strict && k_epilogue_eligible && k_fusion;
+  // the K-quant fused kernels take the tensors a body's row admits beside its own format (f.family_ok: the *_K_M recipes, the Q3_K and
+  // the Q2_K recipe families), but only in the norm-epilogue form.  A body with any other deviation: per-op segments.
+  const bool mix_fused = f.mixed && f.family_ok && !strict && k_epilogue_eligible && k_fusion;
 
   // Strict order, one device, Q4_0 / Q8_0 / Q4_1: the fused launches in their block-ordered form (7 per layer: norm + quantize stay
   // their own launches).  The term tables must fit LDS: 64 rows of gate | up (k_gateup_q_ord, raised past 60 KiB), a workgroup's 16 / 32
@@ -2440,10 +2464,10 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   };
   const bool ordk = strict && wt == CRABML_HIP_Q4_K && k_epilogue_eligible && k_fusion && !has(CRABML_HIP_LLAMA_NO_RHS_PROLOGUE) && (!f.mixed || f.mix_v_down_q6k) &&
                     dim_l % 256 == 0 && hidden_l % 256 == 0 && ordk_fits();
-  // the fast K-quant segments: Q4_K always; Q2_K / Q3_K / Q5_K / Q6_K in the norm-epilogue form (none has an ordered form: a strict-order device
-  // keeps them on the per-op segments; no mix recipe has a Q6_K body: mix_v_down_q6k is about Q4_K / Q5_K bodies); Q4_1 when it cannot take the five launches (a classifier of another format) or for the A/B flag
+  // the fast K-quant segments: Q4_K always; an EPI_ONLY body in the norm-epilogue form (none has an ordered form: a strict-order device
+  // keeps them on the per-op segments); Q4_1 when it cannot take the five launches (a classifier of another format) or for the A/B flag
   const bool fast_k = !strict && (!f.mixed || mix_fused) && k_fusion &&
-                      (wt == CRABML_HIP_Q4_K || (k_body_epi_only && k_epilogue_eligible) || (wt == CRABML_HIP_Q4_1 && (f.out_wt != wt || has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS))));
+                      ((k_body && (!k_body_epi_only || k_epilogue_eligible)) || (wt == CRABML_HIP_Q4_1 && (f.out_wt != wt || has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS))));
   // per-op launches: a strict-order device without an ordered form, a weight format without fused kernels, a mix they do not take
   const bool per_op = (strict && !ord5) || !fused_fmt || (f.mixed && !mix_fused);
 
@@ -2979,7 +3003,7 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   // (decide_step: what Fused5 / FusedK and !ordered imply)
   if ((c->plan.path != SegPath::Fused5 && c->plan.path != SegPath::FusedK) || c->plan.ordered || c->tp > 1 || c->ext_kv)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
-            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 / Q2_K / Q3_K / Q4_K / Q5_K / Q6_K layers, the Q4_K_M / Q5_K_M, Q3_K_S / _M / _L and Q2_K / Q2_K_S mixes) on one device with its own KV cache");
+            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 layers, a K-quant body and the mixes it takes: KBodies) on one device with its own KV cache");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim;
   // the row type of every field that leaves as blocks (the others: f32 values, the plan words)

@@ -526,33 +526,39 @@ struct Planes6 {
   const char* base;
   size_t off_qh;
 };
-// What a layer's V matrix hands k_qkv beside its planes when its format is not the body's.  A Q6_K tensor in a Q4_K / Q5_K layer comes
-// whole (Planes6: its four planes do not fit Planes); the V rows of a Q3_K body (Q4_K / Q5_K: the Q3_K_M / Q3_K_L recipes) are read
-// through wv's own two planes and hand over their format only (fmt = the body's: nothing to hand over); so are those of a Q2_K body
-// (Q3_K / Q4_K: the Q2_K and Q2_K_S recipes).
+// What a layer's V matrix hands k_qkv beside its planes when its format is not the body's (KBody::VAlt, gemv_core.hpp).  A V_WHOLE
+// body takes such a tensor whole (Planes6: a Q6_K tensor's four planes do not fit Planes); the others read the V rows through wv's own
+// two planes and are handed their format only (fmt = the body's: nothing to hand over).  A format that is no K-quant body hands
+// over nothing: Planes6 with base = nullptr.
 struct VFormat {
   int fmt;
 };
 template <int FMT>
 struct VOther {
-  typedef Planes6 type;
+  typedef typename std::conditional<KBody<FMT>::V_WHOLE, Planes6, VFormat>::type type;
 };
-template <>
-struct VOther<CRABML_HIP_Q3_K> {
-  typedef VFormat type;
-};
-template <>
-struct VOther<CRABML_HIP_Q2_K> {
-  typedef VFormat type;
-};
+// the V rows of a body whose alternates come through wv's planes: the one of VAlt that `fmt` names (wave-uniform; validate_weights
+// admits no other, so the last of the list needs no test)
+template <int A, int... REST>
+__device__ __forceinline__ void rows_dot_valt(FmtList<A, REST...>, int fmt, const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd,
+                                              const ActQ8_K& act, int row0, int m, int nb, int lane, float acc[2], int rs) {
+  if constexpr (sizeof...(REST) == 0) {
+    rows_dot<A, 2>(wq, wd, act, row0, m, nb, lane, acc, rs);
+  } else {
+    if (fmt == A)
+      rows_dot<A, 2>(wq, wd, act, row0, m, nb, lane, acc, rs);
+    else
+      rows_dot_valt(FmtList<REST...>{}, fmt, wq, wd, act, row0, m, nb, lane, acc, rs);
+  }
+}
 
 // DEFER: the rhs planes come from a hop-free ffn_down launch -- the row dots are multiplied by 1 / rms (RmsTail, gemv_core.hpp)
 // ARCH = QKV_QWEN2 / QKV_GEMMA: the wave's two rows are a NEOX pair (neox_pair_row0); Qwen2's biases are added after the 1 / rms multiply
 template <int FMT, bool DEFER = false, int ARCH = QKV_LLAMA>
 __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, typename ActOf<FMT>::type act, int nb,
                                              typename QkvArch<ARCH>::epi e, typename VOther<FMT>::type wv6, RmsTail rt, int upfront = 0) {
-  // a K-quant body: nb counts super-blocks, rows_dot has its loader (a Q6_K body comes with wv6.base = nullptr: its V rows are the body's)
-  constexpr bool KF = FMT == CRABML_HIP_Q2_K || FMT == CRABML_HIP_Q3_K || FMT == CRABML_HIP_Q4_K || FMT == CRABML_HIP_Q5_K || FMT == CRABML_HIP_Q6_K;
+  // a K-quant body: nb counts super-blocks, rows_dot has its loader
+  constexpr bool KF = KBody<FMT>::IS;
   const int lane = threadIdx.x & 63;
   const int wave = blockIdx.x * (blockDim.x >> 6) + wave_in_wg();
   int row0 = wave * 2, rs = 1;
@@ -583,24 +589,14 @@ __global__ __launch_bounds__(128) void k_qkv(Planes wq, Planes wk, Planes wv, ty
   }
   float acc[2];
   bool done = false;
-  if constexpr (FMT == CRABML_HIP_Q3_K) {
-    if (wv6.fmt != CRABML_HIP_Q3_K && row0 >= e.dim + e.kv_dim) {  // the V rows of this layer are Q4_K or Q5_K (wave-uniform)
-      if (wv6.fmt == CRABML_HIP_Q4_K)
-        rows_dot<CRABML_HIP_Q4_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
-      else
-        rows_dot<CRABML_HIP_Q5_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
+  // the V rows of this layer in one of the body's alternates (wave-uniform; a format with no alternates has neither branch)
+  if constexpr (!KBody<FMT>::V_WHOLE) {
+    if (wv6.fmt != FMT && row0 >= e.dim + e.kv_dim) {
+      rows_dot_valt(typename KBody<FMT>::VAlt{}, wv6.fmt, w.q, w.d, act, local, m, nb, lane, acc, rs);
       done = true;
     }
-  } else if constexpr (FMT == CRABML_HIP_Q2_K) {
-    if (wv6.fmt != CRABML_HIP_Q2_K && row0 >= e.dim + e.kv_dim) {  // the V rows of this layer are Q3_K or Q4_K (wave-uniform)
-      if (wv6.fmt == CRABML_HIP_Q4_K)
-        rows_dot<CRABML_HIP_Q4_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
-      else
-        rows_dot<CRABML_HIP_Q3_K, 2>(w.q, w.d, act, local, m, nb, lane, acc, rs);
-      done = true;
-    }
-  } else if constexpr (KF && FMT != CRABML_HIP_Q6_K) {
-    if (wv6.base != nullptr && row0 >= e.dim + e.kv_dim) {  // the V rows of this layer are Q6_K (wave-uniform)
+  } else if constexpr (kbody_takes_q6k<FMT>) {
+    if (wv6.base != nullptr && row0 >= e.dim + e.kv_dim) {
       rows_partial_q6k<2>(wv6.base, wv6.off_qh, act, local, m, nb, lane, acc, nullptr, rs);
       done = true;
     }

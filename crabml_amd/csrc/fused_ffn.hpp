@@ -498,10 +498,10 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
                                                       signed char* __restrict__ q, void* __restrict__ d,
                                                       void* __restrict__ isum, NormGather ng, int nb, Planes6 w6,
                                                       typename TpArg<TP>::type tp) {
-  constexpr bool Q5 = FMT == CRABML_HIP_Q5_K, Q6 = FMT == CRABML_HIP_Q6_K, Q3 = FMT == CRABML_HIP_Q3_K, Q2 = FMT == CRABML_HIP_Q2_K;
-  constexpr bool KQ = FMT == CRABML_HIP_Q4_K || Q5 || Q6 || Q3 || Q2;  // Q2_K .. Q6_K weights: nb counts super-blocks, the output is Q8_K
-  constexpr int EF = (Q5 || Q6 || Q3 || Q2) ? CRABML_HIP_Q4_K : FMT;   // (the epilogue knows the K-quant body by Q4_K's name: same rows, same planes out)
-  static_assert(!(Q5 || Q6 || Q3 || Q2) || (!TP && !DEFER && !ORD), "the Q2_K / Q3_K / Q5_K / Q6_K body: the fast step on one device");
+  constexpr bool KQ = KBody<FMT>::IS;                  // a K-quant body (gemv_core.hpp): nb counts super-blocks, the output is Q8_K
+  constexpr int EF = KQ ? CRABML_HIP_Q4_K : FMT;       // (the epilogue knows every K-quant body by Q4_K's name: same rows, same planes out)
+  constexpr bool W6 = kbody_takes_q6k<FMT>;            // this layer's matrix may be a Q6_K tensor handed over whole (w6; a *_K_M mix)
+  static_assert(!KBody<FMT>::EPI_ONLY || (!TP && !DEFER && !ORD), "a K-quant body of the norm-epilogue form only: the fast step on one device");
   constexpr int RW = 2 / SPLIT;         // rows per wave
   constexpr int ROWS = 32 / SPLIT;      // rows per workgroup
   __shared__ __attribute__((aligned(16))) float hv[32];
@@ -531,7 +531,7 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
     short* sbs = (short*)(sd + nb);
     // the first weight pieces are requested before the prologue (they do not depend on it): its L2 round trip
     // and the quantizer run under the HBM latency of the stream's head
-    if (!Q6 && !Q3 && !Q2 && w6.base != nullptr) {  // this layer's matrix is Q6_K (a *_K_M mix): same rhs, its own inner loop
+    if (W6 && w6.base != nullptr) {  // this layer's matrix is Q6_K (a *_K_M mix): same rhs, its own inner loop
       if constexpr (QIN == 2)
         stage_copy_q8k(act, nb, lds_act, sd, sbs, false);
       else
@@ -552,157 +552,30 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
                                  (int)blockIdx.x, (int)gridDim.x, tp);
       return;
     }
+    // the body's own rows: two rounds of pieces requested ahead of the prologue (whole headers), the rhs staged in the body's order,
+    // every row's pieces added in ascending order
     constexpr int PRE = 2;
-    if constexpr (Q5) {
-      // the Q5_K body: the same two rounds of pieces requested ahead of the prologue (whole header, one dword of qh per lane), the
-      // rhs staged in ELEMENT order (Q5_K's planes keep the file's order), every row's pieces added in ascending order
-      const PlanesQ5 w5 = planes_q5k(w.q, w.d);
-      Q5KPiece<false> p5[PRE][RW];
-#pragma unroll
-      for (int it = 0; it < PRE; it++) {
-        const int c = it * 64 + lane;
-#pragma unroll
-        for (int r = 0; r < RW; r++) p5[it][r] = q5k_load<false>(w5, (size_t)(row + r), nb, c < nb * 8 ? c : nb * 8 - 1, lane);
-      }
-      if constexpr (QIN == 2)
-        stage_copy_q8k(act, nb, lds_act, sd, sbs, false);
-      else
-        stage_quant_q8k(xin, nb, (unsigned*)lds_act, sd, sbs, false);
-      const ActQ8_K la5{lds_act, sd, sbs, lds_act};
-#pragma unroll
-      for (int r = 0; r < RW; r++) acc[r] = 0.f;
-#pragma unroll
-      for (int it = 0; it < PRE; it++) {
-        const int c = it * 64 + lane;
-        if (c < nb * 8) {  // (a super-block's eight lanes together: the qh exchange stays among live lanes)
-          const Q4KX xx = q4k_loadx<false>(la5, c);
-#pragma unroll
-          for (int r = 0; r < RW; r++) acc[r] += q5k_term<false>(p5[it][r], xx, c, lane);
-        }
-      }
-      rows_partial_q5k_planes<RW, false>(w5, la5, row, nchunks * 32, nb, lane, acc, PRE * 64);
-      nq_epilogue<EF, SPLIT, TP>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
-                                 (int)blockIdx.x, (int)gridDim.x, tp);
-      return;
-    }
-    if constexpr (Q6) {
-      // the Q6_K body (w6.base is nullptr: the planes are w's own): two rounds of pieces requested ahead of the prologue, every weight
-      // byte once (q6k_load), the rhs staged in element order, every row's pieces added in ascending order
-      const PlanesQ6 wp6 = planes_q6k(w.q, w.d);
-      Q6KPiece p6[PRE][RW];
-#pragma unroll
-      for (int it = 0; it < PRE; it++) {
-        const int c = it * 64 + lane;
-#pragma unroll
-        for (int r = 0; r < RW; r++) p6[it][r] = q6k_load(wp6, (size_t)(row + r), nb, c < nb * 8 ? c : nb * 8 - 1, lane);
-      }
-      if constexpr (QIN == 2)
-        stage_copy_q8k(act, nb, lds_act, sd, sbs, false);
-      else
-        stage_quant_q8k(xin, nb, (unsigned*)lds_act, sd, sbs, false);
-      const ActQ8_K la6{lds_act, sd, sbs, lds_act};
-#pragma unroll
-      for (int r = 0; r < RW; r++) acc[r] = 0.f;
-#pragma unroll
-      for (int it = 0; it < PRE; it++) {
-        const int c = it * 64 + lane;
-        if (c < nb * 8) {  // (a super-block's eight lanes together: the exchanges stay among live lanes)
-          const Q4KX xx = q6k_loadx(la6, c);
-#pragma unroll
-          for (int r = 0; r < RW; r++) acc[r] += q6k_term(p6[it][r], xx, c, lane);
-        }
-      }
-      rows_partial_q6k_planes<RW>(wp6, la6, row, nchunks * 32, nb, lane, acc, PRE * 64);
-      nq_epilogue<EF, SPLIT, TP>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
-                                 (int)blockIdx.x, (int)gridDim.x, tp);
-      return;
-    }
-    if constexpr (Q3) {
-      // the Q3_K body (w6.base is nullptr: a wo / ffn_down of another format runs its own instantiation): two rounds of pieces requested
-      // ahead of the prologue, every weight byte once (q3k_load), the rhs staged in element order, every row's pieces added in
-      // ascending order.  A super-block is FOUR pieces here: a round the row does not reach (wave-uniform) requests nothing.
-      const PlanesQ3 w3 = planes_q3k(w.q, w.d);
-      const int np = nb * 4;
-      Q3KPiece p3[PRE][RW];
-#pragma unroll
-      for (int it = 0; it < PRE; it++) {
-        const int c = it * 64 + lane;
-#pragma unroll
-        for (int r = 0; r < RW; r++) {
-          p3[it][r] = Q3KPiece{i32x4{0, 0, 0, 0}, i32x4{0, 0, 0, 0}};
-          if (it * 64 < np) p3[it][r] = q3k_load(w3, (size_t)(row + r), nb, c < np ? c : np - 1);
-        }
-      }
-      if constexpr (QIN == 2)
-        stage_copy_q8k(act, nb, lds_act, sd, sbs, false);
-      else
-        stage_quant_q8k(xin, nb, (unsigned*)lds_act, sd, sbs, false);
-      const ActQ8_K la3{lds_act, sd, sbs, lds_act};
-#pragma unroll
-      for (int r = 0; r < RW; r++) acc[r] = 0.f;
-#pragma unroll
-      for (int it = 0; it < PRE; it++) {
-        const int c = it * 64 + lane;
-        if (c < np) {  // (a super-block's four lanes together: the exchanges stay among live lanes)
-          float t[RW];
-          q3k_terms<RW>(p3[it], la3, c, t);
-#pragma unroll
-          for (int r = 0; r < RW; r++) acc[r] += t[r];
-        }
-      }
-      rows_partial_q3k_planes<RW>(w3, la3, row, nchunks * 32, nb, lane, acc, PRE * 64);
-      nq_epilogue<EF, SPLIT, TP>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
-                                 (int)blockIdx.x, (int)gridDim.x, tp);
-      return;
-    }
-    if constexpr (Q2) {
-      // the Q2_K body, as the Q3_K body above: two rounds of FOUR-piece super-blocks requested ahead of the prologue, every weight byte
-      // once (q2k_load); a round the row does not reach (wave-uniform) requests nothing
-      const PlanesQ2 w2 = planes_q2k(w.q, w.d);
-      const int np = nb * 4;
-      Q2KPiece p2[PRE][RW];
-#pragma unroll
-      for (int it = 0; it < PRE; it++) {
-        const int c = it * 64 + lane;
-#pragma unroll
-        for (int r = 0; r < RW; r++) {
-          p2[it][r] = Q2KPiece{i32x4{0, 0, 0, 0}, i32x2{0, 0}, 0u};
-          if (it * 64 < np) p2[it][r] = q2k_load(w2, (size_t)(row + r), nb, c < np ? c : np - 1);
-        }
-      }
-      if constexpr (QIN == 2)
-        stage_copy_q8k(act, nb, lds_act, sd, sbs, false);
-      else
-        stage_quant_q8k(xin, nb, (unsigned*)lds_act, sd, sbs, false);
-      const ActQ8_K la2{lds_act, sd, sbs, lds_act};
-#pragma unroll
-      for (int r = 0; r < RW; r++) acc[r] = 0.f;
-#pragma unroll
-      for (int it = 0; it < PRE; it++) {
-        const int c = it * 64 + lane;
-        if (c < np) {  // (a super-block's four lanes together: the exchanges stay among live lanes)
-          float t[RW];
-          q2k_terms<RW>(p2[it], la2, c, t);
-#pragma unroll
-          for (int r = 0; r < RW; r++) acc[r] += t[r];
-        }
-      }
-      rows_partial_q2k_planes<RW>(w2, la2, row, nchunks * 32, nb, lane, acc, PRE * 64);
-      nq_epilogue<EF, SPLIT, TP>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
-                                 (int)blockIdx.x, (int)gridDim.x, tp);
-      return;
-    }
-    Q4KPiece<false> pw[PRE][RW];
+    using B = KBody<FMT, false>;
+    const typename B::Planes wp = B::planes(w.q, w.d);
+    const int np = nb * B::PIECES;
+    typename B::Piece pw[PRE][RW];
 #pragma unroll
     for (int it = 0; it < PRE; it++) {
       const int c = it * 64 + lane;
 #pragma unroll
-      for (int r = 0; r < RW; r++) pw[it][r] = q4k_load<false>(w.q, (const i32x4*)w.d, (size_t)(row + r), nb, c < nb * 8 ? c : nb * 8 - 1, lane);
+      for (int r = 0; r < RW; r++) {
+        if constexpr (B::SKIP_UNREACHED) {  // a round the row does not reach (wave-uniform) requests nothing
+          pw[it][r] = typename B::Piece{};
+          if (it * 64 < np) pw[it][r] = B::load(wp, (size_t)(row + r), nb, c < np ? c : np - 1, lane);
+        } else {
+          pw[it][r] = B::load(wp, (size_t)(row + r), nb, c < np ? c : np - 1, lane);
+        }
+      }
     }
     if constexpr (QIN == 2)
-      stage_copy_q8k(act, nb, lds_act, sd, sbs, true);
+      stage_copy_q8k(act, nb, lds_act, sd, sbs, B::CLASS_MAJOR);
     else
-      stage_quant_q8k(xin, nb, (unsigned*)lds_act, sd, sbs, true);
+      stage_quant_q8k(xin, nb, (unsigned*)lds_act, sd, sbs, B::CLASS_MAJOR);
     const ActQ8_K la{lds_act, sd, sbs, lds_act};
     if constexpr (ORD) {
       const int stride = q4k_rec_stride(nb);
@@ -729,26 +602,20 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
 #pragma unroll
     for (int it = 0; it < PRE; it++) {
       const int c = it * 64 + lane;
-      if (c < nb * 8) {
-        const Q4KX xx = q4k_loadx(la, c);
-#pragma unroll
-        for (int r = 0; r < RW; r++) acc[r] += q4k_term<false>(pw[it][r], xx, c);
-      }
+      if (c < np) KBODY_ADD_TERMS(B, RW, pw[it], la, c, lane, acc);  // (a super-block's lanes together: the exchanges stay among live lanes)
     }
-    rows_partial_q4k<RW, false>(w.q, (const i32x4*)w.d, la, row, nchunks * 32, nb, lane, acc, PRE * 64);
+    rows_partial_kbody<B, RW>(wp, la, row, nchunks * 32, nb, lane, acc, PRE * 64);
+    if constexpr (B::EPI_ONLY) {  // (these bodies end here, the others at the common call below: each as it always has -- the compiler's code for the
+                                  // Q5_K forms follows which of the two it is, profiles/kquant_body_policy.md)
+      nq_epilogue<EF, SPLIT, TP>(acc, res, wn, wn4, epoch, hv, x, q, d, isum, ng, eps, blk, part, nchunks, row, lane, wave,
+                                 (int)blockIdx.x, (int)gridDim.x, tp);
+      return;
+    }
   } else if constexpr (KQ) {
-    if (!Q6 && !Q3 && !Q2 && w6.base != nullptr)
+    if (W6 && w6.base != nullptr)
       rows_partial_q6k<RW>(w6.base, w6.off_qh, act, row, nchunks * 32, nb, lane, acc);
-    else if constexpr (Q5)
-      rows_partial_q5k_planes<RW>(planes_q5k(w.q, w.d), act, row, nchunks * 32, nb, lane, acc);
-    else if constexpr (Q6)
-      rows_partial_q6k_planes<RW>(planes_q6k(w.q, w.d), act, row, nchunks * 32, nb, lane, acc);
-    else if constexpr (Q3)
-      rows_partial_q3k_planes<RW>(planes_q3k(w.q, w.d), act, row, nchunks * 32, nb, lane, acc);
-    else if constexpr (Q2)
-      rows_partial_q2k_planes<RW>(planes_q2k(w.q, w.d), act, row, nchunks * 32, nb, lane, acc);
     else
-      rows_partial_q4k<RW>(w.q, (const i32x4*)w.d, act, row, nchunks * 32, nb, lane, acc);
+      rows_partial_kbody<KBody<FMT>, RW>(KBody<FMT>::planes(w.q, w.d), act, row, nchunks * 32, nb, lane, acc);
   } else if constexpr (QIN == 1) {
     // the rhs arrives as f32 (h from k_gateup_h): quantized to Q8_0 into LDS by this workgroup, under the first weight requests
     static_assert(KQ || QIN != 1 || FMT == CRABML_HIP_Q4_0 || FMT == CRABML_HIP_Q8_0, "Q8_0 rhs");
@@ -1034,8 +901,8 @@ __global__ __launch_bounds__(128) void k_gateup(Planes wg, Planes wu, typename A
 // for all others' sums, then for its super-block's seven neighbours).  The sums keep the order the gathering epilogue used
 // (nq_epilogue: a chunk = its halves; 64 chunks per round through wave_sum_f32; rounds added in order), so the planes are bit for
 // bit the ones wo used to leave.
-// BODY (the layers' format): Q2_K / Q3_K / Q5_K / Q6_K run the same launch over their own rows -- the staged quants in element order,
-// q2k_terms' / q3k_terms' / q5k_term's / q6k_term's pieces (gemv_core.hpp; a Q2_K or Q3_K super-block is four pieces, the others' eight).
+// BODY (the layers' format): every K-quant body runs the same launch over its own rows through its policy (KBody, gemv_core.hpp) --
+// the staged quants in the body's order, its pieces (four or eight per super-block) added in ascending order.
 template <bool QOUT, bool ORD = false, bool NORMIN = false, int BODY = CRABML_HIP_Q4_K>
 __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, ActQ8_K act, FfnAct fa,
                                                        float* __restrict__ h, int m, int nsb, Q8KExchange ex, signed char* __restrict__ oq,
@@ -1054,7 +921,10 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
   // row's pieces are still added in ascending order.  (Measured and not kept: gate and up rows advancing together, four pieces
   // per lane in flight with a second register set -- 90 VGPRs, ONE workgroup per CU, 18.0 us instead of 17.1; pinned to 64
   // VGPRs it spills.)
-  const int nch = nsb * (BODY == CRABML_HIP_Q3_K || BODY == CRABML_HIP_Q2_K ? 4 : 8);
+  using B = KBody<BODY, false>;  // (whole headers)
+  static_assert(B::IS, "a K-quant body");
+  static_assert(!B::EPI_ONLY || !ORD, "only the Q4_K body has an ordered form");
+  const int nch = nsb * B::PIECES;
   // NORMIN: the row, the norm weights and wo's chunk sums are requested BEFORE the first weight pieces (loads return in order: behind
   // the pieces they would wait for an HBM round trip instead of an L2 one).  (host: nsb <= 32 -- at most two super-blocks per wave,
   // four rounds of 64 chunks)
@@ -1075,28 +945,12 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
       wv[u] = ((const f32x4*)wnorm)[(sb < nsb ? sb : 0) * 64 + lane];
     }
   }
-  static_assert(BODY == CRABML_HIP_Q2_K || BODY == CRABML_HIP_Q3_K || BODY == CRABML_HIP_Q4_K || BODY == CRABML_HIP_Q5_K || BODY == CRABML_HIP_Q6_K,
-                "a K-quant body");
-  constexpr bool Q5 = BODY == CRABML_HIP_Q5_K, Q6 = BODY == CRABML_HIP_Q6_K, Q3 = BODY == CRABML_HIP_Q3_K, Q2 = BODY == CRABML_HIP_Q2_K;
-  static_assert(!Q5 || !ORD, "the Q5_K body has no ordered form");
-  static_assert(!Q6 || !ORD, "the Q6_K body has no ordered form");
-  static_assert(!Q3 || !ORD, "the Q3_K body has no ordered form");
-  static_assert(!Q2 || !ORD, "the Q2_K body has no ordered form");
-  typename std::conditional<Q2, Q2KPiece, typename std::conditional<Q3, Q3KPiece, typename std::conditional<Q6, Q6KPiece, typename std::conditional<Q5, Q5KPiece<false>, Q4KPiece<false>>::type>::type>::type>::type pw[2];
+  typename B::Piece pw[2];
 #pragma unroll
   for (int r = 0; r < 2; r++) {
     const size_t prow = (size_t)(row0 + r < m ? row0 + r : m - 1);
     const int pc = lane < nch ? lane : nch - 1;
-    if constexpr (Q2)
-      pw[r] = q2k_load(planes_q2k(wg.q, wg.d), prow, nsb, pc);
-    else if constexpr (Q3)
-      pw[r] = q3k_load(planes_q3k(wg.q, wg.d), prow, nsb, pc);
-    else if constexpr (Q6)
-      pw[r] = q6k_load(planes_q6k(wg.q, wg.d), prow, nsb, pc, lane);
-    else if constexpr (Q5)
-      pw[r] = q5k_load<false>(planes_q5k(wg.q, wg.d), prow, nsb, pc, lane);
-    else
-      pw[r] = q4k_load<false>(wg.q, (const i32x4*)wg.d, prow, nsb, pc, lane);
+    pw[r] = B::load(B::planes(wg.q, wg.d), prow, nsb, pc, lane);
   }
   if constexpr (NORMIN) {
     const int nch32 = k / 32, nrounds = (nch32 + 63) / 64;
@@ -1121,22 +975,22 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
 #pragma unroll
       for (int i = 0; i < 4; i++) xn[i] = (xv[u][i] / rms) * wv[u][i];  // rms_norm.rs:41-45, then the weight (llama2.rs:611)
       const Q8KLane o = q8k_wave_quant(xn, lane);
-      if constexpr (Q5 || Q6 || Q3 || Q2)  // (element order: the rhs of Q2_K / Q3_K / Q5_K / Q6_K rows)
-        ((unsigned*)sq)[sb * 64 + lane] = o.packed;
-      else
+      if constexpr (B::CLASS_MAJOR)
         q8k_store_class_major((signed char*)sq + sb * 256, lane, o.packed);
+      else
+        ((unsigned*)sq)[sb * 64 + lane] = o.packed;
       if ((lane & 3) == 0) sbs[sb * 16 + (lane >> 2)] = (short)o.quad_sum;
       if (lane == 0) sd[sb] = o.d;
     }
   } else {
-    for (int i = threadIdx.x; i < k / 16; i += 1024) sq[i] = (Q5 || Q6 || Q3 || Q2) ? act.q[i] : act.qp[i];  // (class-major: the rhs of Q4_K rows)
+    for (int i = threadIdx.x; i < k / 16; i += 1024) sq[i] = B::CLASS_MAJOR ? act.qp[i] : act.q[i];
     for (int i = threadIdx.x; i < nsb; i += 1024) sd[i] = act.d[i];
     for (int i = threadIdx.x; i < k / 16; i += 1024) sbs[i] = act.bsums[i];
   }
   __syncthreads();
   const ActQ8_K la{sq, sd, sbs, sq};
   __shared__ float hv[32];
-  if constexpr (ORD && !Q5 && !Q6 && !Q3 && !Q2) {
+  if constexpr (ORD) {
     const int stride = q4k_rec_stride(nsb);
     float* T = (float*)((char*)lds_act + (((size_t)nsb * 292 + 15) & ~(size_t)15));  // rows 0..31: gate, 32..63: up
     float* Tg = T + (size_t)(wave * 2) * stride;
@@ -1170,49 +1024,10 @@ __global__ __launch_bounds__(1024, 8) void k_gateup_k_lds(Planes wg, Planes wu, 
   // (Round 6, measured and not kept: gate and up rows advancing together with quad-exchanged headers -- four pieces per lane and
   // step, two request rounds instead of four, 48 VGPRs: 17.1 us against 15.8.  Round 4's whole-header form of the same idea: 18.0.)
   float ag[2] = {0.f, 0.f}, au[2];
-  if constexpr (Q2) {  // the Q2_K body: the same passes, every weight byte requested once (a super-block's four lanes live or dead together)
-    if (lane < nch) {
-      float t[2];
-      q2k_terms<2>(pw, la, lane, t);
-#pragma unroll
-      for (int r = 0; r < 2; r++) ag[r] += t[r];
-    }
-    rows_partial_q2k_planes<2>(planes_q2k(wg.q, wg.d), la, row0, m, nsb, lane, ag, 64);
-    rows_partial_q2k_planes<2>(planes_q2k(wu.q, wu.d), la, row0, m, nsb, lane, au);
-  } else if constexpr (Q3) {  // the Q3_K body: the same passes, every weight byte requested once (a super-block's four lanes live or dead together)
-    if (lane < nch) {
-      float t[2];
-      q3k_terms<2>(pw, la, lane, t);
-#pragma unroll
-      for (int r = 0; r < 2; r++) ag[r] += t[r];
-    }
-    rows_partial_q3k_planes<2>(planes_q3k(wg.q, wg.d), la, row0, m, nsb, lane, ag, 64);
-    rows_partial_q3k_planes<2>(planes_q3k(wu.q, wu.d), la, row0, m, nsb, lane, au);
-  } else if constexpr (Q6) {  // the Q6_K body: the same passes, every weight byte requested once (a super-block's eight lanes live or dead together)
-    if (lane < nch) {
-      const Q4KX x = q6k_loadx(la, lane);
-#pragma unroll
-      for (int r = 0; r < 2; r++) ag[r] += q6k_term(pw[r], x, lane, lane);
-    }
-    rows_partial_q6k_planes<2>(planes_q6k(wg.q, wg.d), la, row0, m, nsb, lane, ag, 64);
-    rows_partial_q6k_planes<2>(planes_q6k(wu.q, wu.d), la, row0, m, nsb, lane, au);
-  } else if constexpr (Q5) {  // the Q5_K body: the same passes over element-order planes (a super-block's eight lanes live or dead together)
-    if (lane < nch) {
-      const Q4KX x = q4k_loadx<false>(la, lane);
-#pragma unroll
-      for (int r = 0; r < 2; r++) ag[r] += q5k_term<false>(pw[r], x, lane, lane);
-    }
-    rows_partial_q5k_planes<2, false>(planes_q5k(wg.q, wg.d), la, row0, m, nsb, lane, ag, 64);
-    rows_partial_q5k_planes<2, false>(planes_q5k(wu.q, wu.d), la, row0, m, nsb, lane, au);
-  } else {
-    if (lane < nch) {
-      const Q4KX x = q4k_loadx(la, lane);
-#pragma unroll
-      for (int r = 0; r < 2; r++) ag[r] += q4k_term<false>(pw[r], x, lane);
-    }
-    rows_partial_q4k<2, false>(wg.q, (const i32x4*)wg.d, la, row0, m, nsb, lane, ag, 64);
-    rows_partial_q4k<2, false>(wu.q, (const i32x4*)wu.d, la, row0, m, nsb, lane, au);
-  }
+  // the first round from pw, then gate from piece 64, then up (a super-block's lanes are live or dead together: the exchanges stay among live lanes)
+  if (lane < nch) KBODY_ADD_TERMS(B, 2, pw, la, lane, lane, ag);
+  rows_partial_kbody<B, 2>(B::planes(wg.q, wg.d), la, row0, m, nsb, lane, ag, 64);
+  rows_partial_kbody<B, 2>(B::planes(wu.q, wu.d), la, row0, m, nsb, lane, au);
 #pragma unroll
   for (int r = 0; r < 2; r++) {
     const float g = wave_sum_f32(ag[r]), u = wave_sum_f32(au[r]);

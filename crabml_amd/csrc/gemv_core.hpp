@@ -1,6 +1,8 @@
 // gemv_core.hpp -- device building blocks shared by gemv.hip (one launch per matmul_vec) and fused.hip
 // (the fused decode step): exact integer block dots and per-format block load / term evaluation.
 #pragma once
+#include <type_traits>
+
 #include "devutil.hpp"
 
 namespace crabml_hip {
@@ -756,35 +758,6 @@ __device__ __forceinline__ float q5k_term(const Q5KPiece<HDR_DPP>& w, const Q4KX
   q5k_ints<HDR_DPP>(w, x, c, lane, isum, msum, h0);
   return q4k_term_f32(h0, x.d8, isum, msum);
 }
-// a lane adds its pieces in ascending order (then the caller's wave tree), as rows_partial_q4k does; c0: pieces below it were taken
-// by the caller (a multiple of 64)
-template <int R, bool HDR_DPP = true>
-__device__ __forceinline__ void rows_partial_q5k_planes(const PlanesQ5& w, const ActQ8_K& act, int row0, int m, int nsb, int lane,
-                                                        float acc[R], int c0 = 0, int rs = 1) {
-  if (c0 == 0) {
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] = 0.f;
-  }
-  const int nchunks = nsb * 8;
-  for (int c = c0 + lane; c < nchunks; c += 64) {
-    Q5KPiece<HDR_DPP> pw[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
-      pw[r] = q5k_load<HDR_DPP>(w, (size_t)row, nsb, c, lane);
-    }
-    const Q4KX x = q4k_loadx<false>(act, c);
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] += q5k_term<HDR_DPP>(pw[r], x, c, lane);
-  }
-}
-// the per-op kernel's entry (k_gemv_q5_k): the same pieces on the same lanes, added in the same order
-template <int R>
-__device__ __forceinline__ void rows_partial_q5k(const char* __restrict__ w, size_t off_qh, const ActQ8_K& act, int row0, int m,
-                                                 int nsb, int lane, float acc[R]) {
-  rows_partial_q5k_planes<R, true>(planes_q5k(w, w + off_qh), act, row0, m, nsb, lane, acc);
-}
-
 // Q6_K rows (planes ql[n][128] | qh[n][64] | scales[n][16] | d[n] f16; common.hpp) against a Q8_K activation vector:
 // lane = one 16-byte ql piece of a super-block (8 lanes per super-block), which carries the low nibbles of scale group
 // gi and the high nibbles of group gi + 4 (buf_q6_k.rs:21-48).  6-bit values are rebuilt as bytes for v_dot4; the -32
@@ -931,86 +904,6 @@ __device__ __forceinline__ float q6k_term(const Q6KPiece& w, const Q4KX& x, int 
   const float dd = h2f(dw) * x.d8;
   return dd * ((float)slo + (float)shi);
 }
-// a lane adds its pieces in ascending order (then the caller's wave tree), as rows_partial_q6k does; c0: pieces below it were taken
-// by the caller (a multiple of 64)
-template <int R>
-__device__ __forceinline__ void rows_partial_q6k_planes(const PlanesQ6& w, const ActQ8_K& act, int row0, int m, int nsb, int lane,
-                                                        float acc[R], int c0 = 0, int rs = 1) {
-  if (c0 == 0) {
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] = 0.f;
-  }
-  const int nchunks = nsb * 8;
-  for (int c = c0 + lane; c < nchunks; c += 64) {
-    Q6KPiece pw[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
-      pw[r] = q6k_load(w, (size_t)row, nsb, c, lane);
-    }
-    const Q4KX x = q6k_loadx(act, c);
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] += q6k_term(pw[r], x, c, lane);
-  }
-}
-
-// (the Q3_K body's rows, defined behind PieceQ3_K below: its pieces are that policy's)
-template <int R>
-__device__ __forceinline__ void rows_q3k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
-                                              int m, int nsb, int lane, float acc[R], int rs);
-// (and the Q2_K body's, behind PieceQ2_K)
-template <int R>
-__device__ __forceinline__ void rows_q2k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
-                                              int m, int nsb, int lane, float acc[R], int rs);
-
-// R rows of a weight matrix in format FMT against its activation planes (ActQ8_0 for Q4_0 / Q8_0, ActQ8_K for
-// Q2_K / Q3_K / Q4_K / Q5_K / Q6_K); `wd` is the format's second plane (f16 scales / 16-byte headers / Q5_K's and Q6_K's qh / Q3_K's hmask /
-// Q2_K's scale bytes), `nu` the blocks per row
-template <int FMT, int R, class ACT>
-__device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
-                                         int row0, int m, int nu, int lane, float acc[R], int rs = 1) {
-  if constexpr (FMT == CRABML_HIP_Q4_K)
-    rows_partial_q4k<R>(wq, (const i32x4*)wd, act, row0, m, nu, lane, acc, 0, nullptr, rs);
-  else if constexpr (FMT == CRABML_HIP_Q5_K)  // (wd: the qh plane, planes_q5k)
-    rows_partial_q5k_planes<R>(planes_q5k(wq, wd), act, row0, m, nu, lane, acc, 0, rs);
-  else if constexpr (FMT == CRABML_HIP_Q6_K)  // (wd: the qh plane, planes_q6k)
-    rows_partial_q6k_planes<R>(planes_q6k(wq, wd), act, row0, m, nu, lane, acc, 0, rs);
-  else if constexpr (FMT == CRABML_HIP_Q3_K)  // (wd: the hmask plane, planes_q3k)
-    rows_q3k_body<R>(wq, wd, act, row0, m, nu, lane, acc, rs);
-  else if constexpr (FMT == CRABML_HIP_Q2_K)  // (wd: the plane of scale bytes, planes_q2k)
-    rows_q2k_body<R>(wq, wd, act, row0, m, nu, lane, acc, rs);
-  else
-    rows_partial<FMT, R>(wq, wd, act, row0, m, nu, lane, acc, rs);
-}
-template <int FMT>
-struct ActOf {
-  typedef ActQ8_0 type;
-};
-template <>
-struct ActOf<CRABML_HIP_Q4_K> {
-  typedef ActQ8_K type;
-};
-template <>
-struct ActOf<CRABML_HIP_Q5_K> {
-  typedef ActQ8_K type;
-};
-template <>
-struct ActOf<CRABML_HIP_Q6_K> {
-  typedef ActQ8_K type;
-};
-template <>
-struct ActOf<CRABML_HIP_Q3_K> {
-  typedef ActQ8_K type;
-};
-template <>
-struct ActOf<CRABML_HIP_Q2_K> {
-  typedef ActQ8_K type;
-};
-template <>
-struct ActOf<CRABML_HIP_Q4_1> {
-  typedef ActQ8_1 type;
-};
-
 // ---- Q5_0 / Q5_1 / Q2_K / Q3_K: the formats the reference serves with scalar code only --------------------------------------
 // (buf_q5_0.rs, buf_q5_1.rs, buf_q2_k.rs, buf_q3_k.rs).  They run the per-op path (matmul_vec, embedding rows, the generic
 // decode step); one policy per format describes a lane's 16-byte PIECE of quants: what it loads, the exact integers it yields,
@@ -1331,34 +1224,6 @@ __device__ __forceinline__ void q3k_terms(const Q3KPiece (&p)[R], const ActQ8_K&
     t[r] = (c & 3) == 0 ? v : 0.0f;
   }
 }
-// a lane adds its pieces in ascending order (then the caller's wave tree), as rows_partial_pieces does; c0: pieces below it were
-// taken by the caller (a multiple of 64)
-template <int R>
-__device__ __forceinline__ void rows_partial_q3k_planes(const PlanesQ3& w, const ActQ8_K& act, int row0, int m, int nsb, int lane,
-                                                        float acc[R], int c0 = 0, int rs = 1) {
-  if (c0 == 0) {
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] = 0.f;
-  }
-  const int np = nsb * 4;
-  for (int c = c0 + lane; c < np; c += 64) {
-    Q3KPiece pw[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
-      pw[r] = q3k_load(w, (size_t)row, nsb, c);
-    }
-    float t[R];
-    q3k_terms<R>(pw, act, c, t);
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] += t[r];
-  }
-}
-template <int R>
-__device__ __forceinline__ void rows_q3k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
-                                              int m, int nsb, int lane, float acc[R], int rs) {
-  rows_partial_q3k_planes<R>(planes_q3k(wq, wd), act, row0, m, nsb, lane, acc, 0, rs);
-}
 
 // ---- the Q2_K BODY loader (attn_q / attn_k / ffn_gate / ffn_up Q2_K: k_qkv, k_gemv_res_nq, k_gateup_k_lds) -----------------------
 // PieceQ2_K's pieces on the same lanes with the same arithmetic -- piece j = lane & 3 of a super-block, (half, h) = (j >> 1, j & 1),
@@ -1445,34 +1310,6 @@ __device__ __forceinline__ void q2k_terms(const Q2KPiece (&p)[R], const ActQ8_K&
     t[r] = (c & 3) == 0 ? v : 0.0f;
   }
 }
-// a lane adds its pieces in ascending order (then the caller's wave tree), as rows_partial_pieces does; c0: pieces below it were
-// taken by the caller (a multiple of 64)
-template <int R>
-__device__ __forceinline__ void rows_partial_q2k_planes(const PlanesQ2& w, const ActQ8_K& act, int row0, int m, int nsb, int lane,
-                                                        float acc[R], int c0 = 0, int rs = 1) {
-  if (c0 == 0) {
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] = 0.f;
-  }
-  const int np = nsb * 4;
-  for (int c = c0 + lane; c < np; c += 64) {
-    Q2KPiece pw[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
-      pw[r] = q2k_load(w, (size_t)row, nsb, c);
-    }
-    float t[R];
-    q2k_terms<R>(pw, act, c, t);
-#pragma unroll
-    for (int r = 0; r < R; r++) acc[r] += t[r];
-  }
-}
-template <int R>
-__device__ __forceinline__ void rows_q2k_body(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ActQ8_K& act, int row0,
-                                              int m, int nsb, int lane, float acc[R], int rs) {
-  rows_partial_q2k_planes<R>(planes_q2k(wq, wd), act, row0, m, nsb, lane, acc, 0, rs);
-}
 
 // R rows of a matrix in one of those formats against its activation planes; lane l owns pieces l, l + 64, ...
 template <class P, int R>
@@ -1503,5 +1340,165 @@ __device__ __forceinline__ void rows_partial_pieces(const char* __restrict__ w, 
     }
   }
 }
+
+// ---- the K-quant BODY policies (the fused decode step: k_qkv, k_gemv_res_nq, k_gateup_k_lds) ----------------------------------
+// One policy per format a layer's attn_q / attn_k / ffn_gate / ffn_up may have there: what the kernels and the host need to know about
+// the format beside its loader and its term expression, which stand above.  A lane owns the pieces c = lane, lane + 64, ... of a row
+// (PIECES per super-block) and adds their terms in ascending order.
+//   Planes, planes(q, d)   the format's planes, from its first two as the launches pass them (fused_common.hpp's Planes)
+//   Piece, load            what a lane requests for piece c of a row; Piece{} stands for a piece that was not requested
+//   ROWS_TOGETHER          how the terms of piece c of R rows come: terms<R>(pieces, act, c, t) for all rows at once (the four-piece
+//                          formats, whose activation side is read group by group for all rows), or X, loadx(act, c) once and
+//                          term(piece, x, c, lane) per row (the eight-piece ones).  KBODY_ADD_TERMS below adds them into acc[R].
+//   CLASS_MAJOR            the rhs quants are read class-major (act.qp) and staged that way; else in element order (act.q)
+//   SKIP_UNREACHED         a prologue round the row does not reach (wave-uniform) requests nothing, instead of the row's last piece
+//                          again.  It decides which memory requests a launch makes: the format's, not the kernels', to choose.
+//   VAlt, V_WHOLE          the formats attn_v, attn_output and ffn_down may have beside the body's, in the order k_qkv asks for them;
+//                          V_WHOLE: such a tensor (attn_v, ffn_down) comes as its whole buffer (Planes6, fused_common.hpp:
+//                          rows_partial_q6k / rows_terms_q6k), else through the two-plane argument with its format (VFormat) and
+//                          that format's own policy
+//   EPI_ONLY               the body exists in the fast step's norm-epilogue form only (one device, no strict-order form: decide_step)
+// HDR_DPP (Q4_K, Q5_K): a lane takes one dword of the header and the quad hands them round, instead of every lane the whole header.
+// Everything here only forwards: the compiler's code for a launch follows the shape of the function that holds the accumulate step,
+// and with these members it is instruction for instruction what the per-format copies gave (profiles/kquant_body_policy.md).
+template <int... FMTS>
+struct FmtList {};
+template <int FMT, bool HDR_DPP = true>
+struct KBody {  // not a K-quant body: a 32-element format (BlockFmt), whose layers hold no other format
+  static constexpr bool IS = false, EPI_ONLY = false, V_WHOLE = true;
+  typedef FmtList<> VAlt;
+};
+struct PlanesQ4 {
+  const i32x4* q;
+  const i32x4* hdr;
+};
+template <bool HDR_DPP>
+struct KBody<CRABML_HIP_Q4_K, HDR_DPP> {
+  static constexpr bool IS = true, EPI_ONLY = false, ROWS_TOGETHER = false, CLASS_MAJOR = true, SKIP_UNREACHED = false, V_WHOLE = true;
+  static constexpr int PIECES = 8;
+  typedef FmtList<CRABML_HIP_Q6_K> VAlt;  // (the Q4_K_M recipe)
+  typedef PlanesQ4 Planes;
+  typedef Q4KPiece<HDR_DPP> Piece;
+  typedef Q4KX X;
+  static __device__ __forceinline__ Planes planes(const void* q, const void* d) { return Planes{(const i32x4*)q, (const i32x4*)d}; }
+  static __device__ __forceinline__ Piece load(const Planes& w, size_t row, int nsb, int c, int lane) {
+    return q4k_load<HDR_DPP>(w.q, w.hdr, row, nsb, c, lane);
+  }
+  static __device__ __forceinline__ X loadx(const ActQ8_K& act, int c) { return q4k_loadx(act, c); }
+  static __device__ __forceinline__ float term(const Piece& w, const X& x, int c, int lane) { return q4k_term<HDR_DPP>(w, x, c); }
+};
+template <bool HDR_DPP>
+struct KBody<CRABML_HIP_Q5_K, HDR_DPP> {
+  static constexpr bool IS = true, EPI_ONLY = true, ROWS_TOGETHER = false, CLASS_MAJOR = false, SKIP_UNREACHED = false, V_WHOLE = true;
+  static constexpr int PIECES = 8;
+  typedef FmtList<CRABML_HIP_Q6_K> VAlt;  // (the Q5_K_M recipe)
+  typedef PlanesQ5 Planes;
+  typedef Q5KPiece<HDR_DPP> Piece;
+  typedef Q4KX X;
+  static __device__ __forceinline__ Planes planes(const void* q, const void* d) { return planes_q5k(q, d); }  // (d: the qh plane)
+  static __device__ __forceinline__ Piece load(const Planes& w, size_t row, int nsb, int c, int lane) {
+    return q5k_load<HDR_DPP>(w, row, nsb, c, lane);
+  }
+  static __device__ __forceinline__ X loadx(const ActQ8_K& act, int c) { return q4k_loadx<false>(act, c); }
+  static __device__ __forceinline__ float term(const Piece& w, const X& x, int c, int lane) { return q5k_term<HDR_DPP>(w, x, c, lane); }
+};
+template <bool HDR_DPP>
+struct KBody<CRABML_HIP_Q6_K, HDR_DPP> {
+  static constexpr bool IS = true, EPI_ONLY = true, ROWS_TOGETHER = false, CLASS_MAJOR = false, SKIP_UNREACHED = false, V_WHOLE = true;
+  static constexpr int PIECES = 8;
+  typedef FmtList<> VAlt;  // (no recipe puts another format into a Q6_K body)
+  typedef PlanesQ6 Planes;
+  typedef Q6KPiece Piece;
+  typedef Q4KX X;
+  static __device__ __forceinline__ Planes planes(const void* q, const void* d) { return planes_q6k(q, d); }  // (d: the qh plane)
+  static __device__ __forceinline__ Piece load(const Planes& w, size_t row, int nsb, int c, int lane) { return q6k_load(w, row, nsb, c, lane); }
+  static __device__ __forceinline__ X loadx(const ActQ8_K& act, int c) { return q6k_loadx(act, c); }
+  static __device__ __forceinline__ float term(const Piece& w, const X& x, int c, int lane) { return q6k_term(w, x, c, lane); }
+};
+template <bool HDR_DPP>
+struct KBody<CRABML_HIP_Q3_K, HDR_DPP> {
+  static constexpr bool IS = true, EPI_ONLY = true, ROWS_TOGETHER = true, CLASS_MAJOR = false, SKIP_UNREACHED = true, V_WHOLE = false;
+  static constexpr int PIECES = 4;
+  typedef FmtList<CRABML_HIP_Q4_K, CRABML_HIP_Q5_K> VAlt;  // (the Q3_K_S / _M / _L recipes)
+  typedef PlanesQ3 Planes;
+  typedef Q3KPiece Piece;
+  static __device__ __forceinline__ Planes planes(const void* q, const void* d) { return planes_q3k(q, d); }  // (d: the hmask plane)
+  static __device__ __forceinline__ Piece load(const Planes& w, size_t row, int nsb, int c, int lane) { return q3k_load(w, row, nsb, c); }
+  template <int R>
+  static __device__ __forceinline__ void terms(const Piece (&p)[R], const ActQ8_K& act, int c, float (&t)[R]) { q3k_terms<R>(p, act, c, t); }
+};
+template <bool HDR_DPP>
+struct KBody<CRABML_HIP_Q2_K, HDR_DPP> {
+  static constexpr bool IS = true, EPI_ONLY = true, ROWS_TOGETHER = true, CLASS_MAJOR = false, SKIP_UNREACHED = true, V_WHOLE = false;
+  static constexpr int PIECES = 4;
+  typedef FmtList<CRABML_HIP_Q4_K, CRABML_HIP_Q3_K> VAlt;  // (plain Q2_K and the Q2_K / Q2_K_S recipes)
+  typedef PlanesQ2 Planes;
+  typedef Q2KPiece Piece;
+  static __device__ __forceinline__ Planes planes(const void* q, const void* d) { return planes_q2k(q, d); }  // (d: the plane of scale bytes)
+  static __device__ __forceinline__ Piece load(const Planes& w, size_t row, int nsb, int c, int lane) { return q2k_load(w, row, nsb, c); }
+  template <int R>
+  static __device__ __forceinline__ void terms(const Piece (&p)[R], const ActQ8_K& act, int c, float (&t)[R]) { q2k_terms<R>(p, act, c, t); }
+};
+// a Q6_K tensor among the body's alternates, which comes whole (the *_K_M mixes of a Q4_K / Q5_K body)
+template <int FMT>
+inline constexpr bool kbody_takes_q6k = KBody<FMT>::V_WHOLE && !std::is_same<typename KBody<FMT>::VAlt, FmtList<>>::value;
+
+// acc[0 .. R) += the terms of piece c of R rows of body B (pw: their pieces).  The one statement of the accumulate step, for the three
+// places that take it (rows_partial_kbody, k_gemv_res_nq's and k_gateup_k_lds' first rounds).  A macro and not a function: the step
+// has to stand IN the function that holds the pieces and the sums -- behind a call boundary of its own the compiler orders the same
+// instructions differently (profiles/kquant_body_policy.md has the counts).
+#define KBODY_ADD_TERMS(B, R, pw, act, c, lane, acc)                                                  \
+  do {                                                                                                \
+    if constexpr (B::ROWS_TOGETHER) {                                                                 \
+      float t_[R];                                                                                    \
+      B::template terms<R>(pw, act, c, t_);                                                           \
+      _Pragma("unroll") for (int r_ = 0; r_ < R; r_++) acc[r_] += t_[r_];                              \
+    } else {                                                                                          \
+      const typename B::X x_ = B::loadx(act, c);                                                      \
+      _Pragma("unroll") for (int r_ = 0; r_ < R; r_++) acc[r_] += B::term(pw[r_], x_, c, lane);        \
+    }                                                                                                 \
+  } while (0)
+
+// R rows of a K-quant body: a lane adds its pieces in ascending order (then the caller's wave tree); c0: pieces below it were taken
+// by the caller (a multiple of 64)
+template <class B, int R>
+__device__ __forceinline__ void rows_partial_kbody(const typename B::Planes& w, const ActQ8_K& act, int row0, int m, int nsb, int lane,
+                                                   float acc[R], int c0 = 0, int rs = 1) {
+  if (c0 == 0) {
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = 0.f;
+  }
+  const int np = nsb * B::PIECES;
+  for (int c = c0 + lane; c < np; c += 64) {
+    typename B::Piece pw[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const int row = row0 + r * rs < m ? row0 + r * rs : m - 1;
+      pw[r] = B::load(w, (size_t)row, nsb, c, lane);
+    }
+    KBODY_ADD_TERMS(B, R, pw, act, c, lane, acc);
+  }
+}
+// the per-op kernel's entry (k_gemv_q5_k): the same pieces on the same lanes, added in the same order
+template <int R>
+__device__ __forceinline__ void rows_partial_q5k(const char* __restrict__ w, size_t off_qh, const ActQ8_K& act, int row0, int m,
+                                                 int nsb, int lane, float acc[R]) {
+  rows_partial_kbody<KBody<CRABML_HIP_Q5_K>, R>(planes_q5k(w, w + off_qh), act, row0, m, nsb, lane, acc);
+}
+
+// R rows of a weight matrix in format FMT against its activation planes (ActQ8_0 / ActQ8_1 for the 32-element formats, ActQ8_K for
+// a K-quant body); `wd` is the format's second plane (BlockFmt's f16 scales, KBody::planes' second argument), `nu` the blocks per row
+template <int FMT, int R, class ACT>
+__device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
+                                         int row0, int m, int nu, int lane, float acc[R], int rs = 1) {
+  if constexpr (KBody<FMT>::IS)
+    rows_partial_kbody<KBody<FMT>, R>(KBody<FMT>::planes(wq, wd), act, row0, m, nu, lane, acc, 0, rs);
+  else
+    rows_partial<FMT, R>(wq, wd, act, row0, m, nu, lane, acc, rs);
+}
+template <int FMT>
+struct ActOf {
+  typedef typename std::conditional<KBody<FMT>::IS, ActQ8_K, typename std::conditional<FMT == CRABML_HIP_Q4_1, ActQ8_1, ActQ8_0>::type>::type type;
+};
 
 }  // namespace crabml_hip
