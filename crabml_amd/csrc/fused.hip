@@ -372,6 +372,21 @@ int chunk_split(uint64_t flags, int k, int dim, int n_cu, bool x_only = false) {
                                                          : 1;
 }
 
+// Whether a wo / ffn_down launch (k_gemv_res_nq over a 32-element format, its rhs planes in global memory) copies those planes into
+// LDS once per workgroup and requests a row's weights NQ_DEEP steps ahead (rows_partial_deep): the depth, or 0 = every wave reads its
+// units from global memory, two per request round -- the loop every such launch had.  Inputs: the row's length, the rows per
+// wave, the resident waves per CU.  Measured (profiles/request_rounds.md): with one row per wave and one 1024-thread workgroup per CU
+// (ffn_down: two workgroups per chunk, 16 waves on a CU and nothing else to cover their waits) the copy pays, 8.55 -> 7.97 us on the
+// 8B shape.  Two rows per wave (one workgroup per chunk: wo) keep the old loop: at k = 4096 in Q4_0 that is the whole row in one
+// round already, and its blocks of 4 steps x 2 rows do not fit the workgroup's 128 VGPRs.  No threshold on the steps: chunk_split
+// gives two workgroups per chunk from 256 blocks on, four steps and more; shorter rows come here under SPLIT_CHUNKS_ALWAYS alone.
+// k <= ACT_STAGE_MAX_K: what the copy's two pieces per thread cover.  The one place that decides it;
+// A/B: CRABML_HIP_LLAMA_NQ_TWO_UNIT_ROUNDS.
+int nq_request_depth(uint64_t flags, int k, int rows_per_wave, int waves_per_cu) {
+  if ((flags & CRABML_HIP_LLAMA_NQ_TWO_UNIT_ROUNDS) || rows_per_wave != 1 || waves_per_cu > 16 || k > ACT_STAGE_MAX_K) return 0;
+  return NQ_DEEP;
+}
+
 // The norm kernels walk a row with 1024 threads x NIT float4 iterations: rows past 4096 elements take 12 (llama_create_impl stops at
 // 12288).  The one place that knows; CRABML_HIP_PLAN_NORM_NIT records this value.
 int norm_nit(int dim) { return dim <= 4096 ? 4 : 12; }
@@ -755,9 +770,10 @@ void launch_embed(const crabml_hip_llama* c) {
 // the form <QIN, TP, DEFER> of a k_gemv_res_nq launch, as a value: the caller branches between forms, SPLIT is folded at the launch
 template <int QIN, bool TP = false, bool DEFER = false>
 struct NqForm {};
-template <int FMT, int SPLIT, int QIN, bool TP, bool DEFER>
+// (DEEP, the request depth, is read by the forms whose rhs planes lie in global memory, at one row per wave: QIN 0, SPLIT 2)
+template <int FMT, int SPLIT, int DEEP, int QIN, bool TP, bool DEFER>
 constexpr auto nq_kernel(NqForm<QIN, TP, DEFER>) {
-  return &k_gemv_res_nq<FMT, SPLIT, QIN, TP, DEFER>;
+  return &k_gemv_res_nq<FMT, SPLIT, QIN, TP, DEFER, false, QIN == 0 && SPLIT == 2 ? DEEP : 0>;
 }
 
 // enqueue segment `seg` of one decode step on the device stream (see the banner above): the fused kernels
@@ -827,11 +843,16 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       const int split = chunk_split(g.flags, k, dim, dev->n_cu);
       c->tap.note(seg / 2, stage == 2 ? CRABML_HIP_PLAN_SPLIT_WO : CRABML_HIP_PLAN_SPLIT_DOWN, split);
       const TpP2P tpv = tp_view(c, tp);
-      // one k_gemv_res_nq launch of the given form: `split` workgroups for each of the dim / 32 chunks
+      // one k_gemv_res_nq launch of the given form: `split` workgroups for each of the dim / 32 chunks, 16 waves each
+      const int nwg = dim / 32 * split;
+      const int depth = nq_request_depth(g.flags, k, 2 / split, (nwg + dev->n_cu - 1) / dev->n_cu * 16);
       auto nq = [&](auto form, size_t lds, const float* rhs, auto tparg) {
         with_const_else<2, 1>(split, [&](auto s) {
-          launch_k(st, R, nq_kernel<FMT, decltype(s)::value>(form), dim3(dim / 32 * split), dim3(1024), lds, planes_of(w), act_view<FMT>(a), rhs, c->x,
-                   wnext, eps_next, ad.q, ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, tparg);
+          with_const_else<NQ_DEEP, 0>(depth, [&](auto dp) {
+            launch_k(st, R, nq_kernel<FMT, decltype(s)::value, decltype(dp)::value>(form), dim3(nwg), dim3(1024),
+                     decltype(dp)::value > 0 && lds == 0 ? q8_0_lds_bytes(k / 32) : lds, planes_of(w), act_view<FMT>(a),
+                     rhs, c->x, wnext, eps_next, ad.q, ad.d, ad.isum, ng, k / 32, Planes6{nullptr, 0}, tparg);
+          });
         });
       };
       if (xin != nullptr && !Q81) {  // (tensor-parallel ranks) the rhs arrives as f32 -- h from k_gateup_h -- and is quantized in the prologue

@@ -224,6 +224,9 @@ __device__ __forceinline__ void stage_quant_q8_0_store(const StageQ8Regs& r, int
   }
 }
 __host__ __device__ inline size_t q8_0_lds_bytes(int nb) { return (size_t)nb * 32 + (size_t)((nb + 1) & ~1) * 2 + (size_t)nb * 4; }
+// k_gemv_res_nq's rows over rhs planes staged in LDS (rows_partial_deep): the steps of weights requested ahead -- the shallowest of
+// the depths that tie, profiles/request_rounds.md
+constexpr int NQ_DEEP = 2;
 // the Q8_K planes of a k-element rhs in LDS (k_gemv_res_nq<Q4_K, .., QIN 1 / 2>, k_gateup_k_lds): q[k] | d[k/256] f32 | bsums[k/16] i16
 __host__ __device__ inline size_t q8k_lds_bytes(int k) { return (size_t)k + (size_t)(k / 256) * 4 + (size_t)(k / 16) * 2; }
 // ... and of their ORD forms: the planes rounded up to 16 bytes + the nine-term records of `rows` rows (32 / SPLIT of k_gemv_res_nq,
@@ -491,7 +494,10 @@ __device__ __forceinline__ void nq_epilogue(float (&acc)[2 / SPLIT], float res, 
 // ORD (strict-order device, Q4_K with QIN 1 / 2): the rows' nine-term records go to LDS behind the rhs planes (q4k_class_terms; dynamic
 // LDS = the planes rounded up to 16 bytes + ROWS * q4k_rec_stride(nb) floats), wave 0 adds them in super-block order, the epilogue keeps the
 // reference's norm order: every bit equals the per-op launches (k_gemv_exact_q4k + k_norm_f32 + k_quantize_q8_k).
-template <int FMT, int SPLIT, int QIN = 0, bool TP = false, bool DEFER = false, bool ORD = false>
+// DEEP (the 32-element formats with QIN 0, one row per wave): 0 = the rhs units from global memory, two per request round; D > 0 = the
+// rhs planes copied into LDS (dynamic LDS: q8_0_lds_bytes(nb)) and the row's weights requested D steps ahead (rows_partial_deep).
+// The host decides: nq_request_depth.
+template <int FMT, int SPLIT, int QIN = 0, bool TP = false, bool DEFER = false, bool ORD = false, int DEEP = 0>
 __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<FMT>::type act, const float* __restrict__ xin,
                                                       float* __restrict__ x,
                                                       const float* __restrict__ wnext, float eps,
@@ -670,6 +676,15 @@ __global__ __launch_bounds__(1024) void k_gemv_res_nq(Planes w, typename ActOf<F
         for (int r = 0; r < RW; r++) acc[r] += F::term(kb[r], xb);
       }
     }
+  } else if constexpr (DEEP > 0) {
+    // the rhs planes through LDS, once per workgroup: requested ahead of the weights (they arrive first), parked behind the first
+    // batch's weight requests (gemv_core.hpp: rows_partial_deep)
+    extern __shared__ i32x4 lds_act[];
+    const ActStage stg = act_stage_request(act, nb);
+    rows_partial_deep<FMT, RW, DEEP>(w.q, w.d, act_stage_view(act, nb, lds_act), row, nchunks * 32, nb, lane, acc, [&]() {
+      act_stage_store(act, stg, nb, lds_act);
+      __syncthreads();
+    });
   } else {
     using F = BlockFmt<FMT>;
 #pragma unroll

@@ -245,6 +245,129 @@ __device__ __forceinline__ void rows_partial_2step(const i32x4* __restrict__ wq,
   }
 }
 
+// ---- ffn_down of the fused step: the activation vector through LDS, the row's weights D steps ahead ---------------------------------
+// k_gemv_res_nq with one row per wave (16 waves per CU, nothing else resident) walks rows of seven and more 64-unit steps.  With
+// rows_partial's mapping every wave reads the WHOLE activation vector through the vector-memory path, 32 bytes per lane and step --
+// twice the weight bytes, sixteen times over per workgroup --, and those loads share the in-order counter of the weight loads.  Here
+// the workgroup copies the planes into LDS once (act_stage_*, requested ahead of the first weights: they complete first; parked by
+// `mid`, which runs behind the first batch's requests while they are in flight), and a step's unit is read from LDS when the step is
+// consumed: a counter of its own, no VGPRs ahead.  The weight loads of D steps x R rows are issued before any is consumed, and a row of
+// more than D steps is pipelined: step s + D is requested into the registers of step s as soon as step s is consumed.
+// Measured on the 8B shape (profiles/request_rounds.md): the LDS copy is what pays (8.55 -> 7.97 us per launch); how far ahead the
+// weights are requested does not -- D = 2 and 4 tie, 6 and the whole row at once (7) are SLOWER than the loop this replaces, as is any
+// depth with the units kept in registers.  D = 2 ships.
+// No load stands in a lane-dependent branch (see rms_request): a unit index past the row's end is clamped to the row's own last unit
+// nu - 1 -- never an address outside the planes; the only branches are wave-uniform and hold no global load.  A dead lane adds
+// `live ? t : 0.0f`: acc starts at +0.0 and can never become -0.0, so this equals a skipped add bit for bit.  Same terms, same
+// ascending per-lane order as rows_partial and the two-unit loop of k_gemv_res_nq: bit-identical to both.
+
+// (keeps a requested block's first use where it stands: otherwise the compiler hoists every step's scale conversion above the first
+// step, and with it the wait for the batch's last scale)
+__device__ __forceinline__ void pin_scale(unsigned short& d) {
+  unsigned s = d;
+  asm volatile("" : "+v"(s));
+  d = (unsigned short)s;
+}
+__device__ __forceinline__ void pin_scale(unsigned& dm) { asm volatile("" : "+v"(dm)); }
+
+// act: the planes in LDS; mid(): parks them and syncs the workgroup
+template <int FMT, int R, int D, class ACT, class MID>
+__device__ __forceinline__ void rows_partial_deep(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
+                                                  int row0, int m, int nb, int lane, float acc[R], MID mid) {
+  using F = BlockFmt<FMT>;
+#pragma unroll
+  for (int r = 0; r < R; r++) acc[r] = 0.f;
+  const int nu = nb * F::UNITS;
+  const int nsteps = (nu + 63) >> 6;
+  size_t rows[R];
+#pragma unroll
+  for (int r = 0; r < R; r++) rows[r] = (size_t)(row0 + r < m ? row0 + r : m - 1);
+  typename F::Blk blk[D][R];
+  // the first batch: steps 0 .. D - 1
+#pragma unroll
+  for (int j = 0; j < D; j++) {
+    const int u = j * 64 + lane, uu = u < nu ? u : nu - 1;
+#pragma unroll
+    for (int r = 0; r < R; r++) blk[j][r] = F::load(wq, wd, rows[r], nb, uu);
+  }
+  mid();
+  int s0 = 0;
+  for (; s0 + D < nsteps; s0 += D) {  // a batch with steps behind it (all of its own are whole): consume step s, request step s + D
+#pragma unroll
+    for (int j = 0; j < D; j++) {
+      const XUnit x = F::loadx(act, (s0 + j) * 64 + lane);
+#pragma unroll
+      for (int r = 0; r < R; r++) acc[r] += F::term(blk[j][r], x);
+      const int u = (s0 + D + j) * 64 + lane, uu = u < nu ? u : nu - 1;
+#pragma unroll
+      for (int r = 0; r < R; r++) blk[j][r] = F::load(wq, wd, rows[r], nb, uu);
+    }
+  }
+  // the last batch (wave-uniform skips of the steps the row does not have; the row's last step may be ragged)
+#pragma unroll
+  for (int j = 0; j < D; j++) {
+    if (s0 + j < nsteps) {
+      const int u = (s0 + j) * 64 + lane;
+      const bool live = u < nu;  // (Q8_0: nu is even, the two lanes of a block are live or dead together)
+      const XUnit x = F::loadx(act, live ? u : nu - 1);
+#pragma unroll
+      for (int r = 0; r < R; r++) {
+        if constexpr (FMT == CRABML_HIP_Q4_1)
+          pin_scale(blk[j][r].dm);
+        else
+          pin_scale(blk[j][r].d);
+        const float t = F::term(blk[j][r], x);
+        acc[r] += live ? t : 0.0f;
+      }
+    }
+  }
+}
+
+// The planes of a quantized activation vector (Q8_0: q | d | isum i32, Q8_1: q | d | s f16) copied into LDS by a 1024-thread workgroup
+// (the layout of q8_0_lds_bytes: q[nb][32] | d[(nb + 1) & ~1] | third plane): act_stage_request asks for this thread's share --
+// unconditional loads of clamped indices, up to 2048 16-byte pieces of q and 1024 blocks: k <= ACT_STAGE_MAX_K --, act_stage_store
+// parks it, act_stage_view is the view of the copy.  The caller syncs.
+constexpr int ACT_STAGE_MAX_K = 32768;
+struct ActStage {
+  i32x4 q0, q1;
+  unsigned short d;
+  int aux;
+};
+__device__ __forceinline__ int act_aux(const ActQ8_0& a, int b) { return a.isum[b]; }
+__device__ __forceinline__ int act_aux(const ActQ8_1& a, int b) { return (int)a.s[b]; }
+template <class ACT>
+__device__ __forceinline__ ActStage act_stage_request(const ACT& act, int nb) {
+  const int t = (int)threadIdx.x, nq = 2 * nb;
+  ActStage s{act.q[t < nq ? t : nq - 1], i32x4{0, 0, 0, 0}, act.d[t < nb ? t : nb - 1], act_aux(act, t < nb ? t : nb - 1)};
+  if (nq > 1024) s.q1 = act.q[t + 1024 < nq ? t + 1024 : nq - 1];  // (uniform)
+  __builtin_amdgcn_sched_barrier(0);  // the caller's weight requests stay behind these
+  return s;
+}
+__device__ __forceinline__ void act_stage_put(const ActStage& s, int nb, i32x4* sq, unsigned short* sd) {
+  const int t = (int)threadIdx.x, nq = 2 * nb;
+  if (t < nq) sq[t] = s.q0;
+  if (t + 1024 < nq) sq[t + 1024] = s.q1;
+  if (t < nb) sd[t] = s.d;
+}
+__device__ __forceinline__ ActQ8_0 act_stage_view(const ActQ8_0&, int nb, i32x4* lds) {
+  unsigned short* sd = (unsigned short*)(lds + 2 * nb);
+  return ActQ8_0{lds, sd, (const int*)(sd + ((nb + 1) & ~1))};
+}
+__device__ __forceinline__ ActQ8_1 act_stage_view(const ActQ8_1&, int nb, i32x4* lds) {
+  unsigned short* sd = (unsigned short*)(lds + 2 * nb);
+  return ActQ8_1{lds, sd, sd + ((nb + 1) & ~1)};
+}
+__device__ __forceinline__ void act_stage_store(const ActQ8_0&, const ActStage& s, int nb, i32x4* lds) {
+  unsigned short* sd = (unsigned short*)(lds + 2 * nb);
+  act_stage_put(s, nb, lds, sd);
+  if ((int)threadIdx.x < nb) ((int*)(sd + ((nb + 1) & ~1)))[threadIdx.x] = s.aux;
+}
+__device__ __forceinline__ void act_stage_store(const ActQ8_1&, const ActStage& s, int nb, i32x4* lds) {
+  unsigned short* sd = (unsigned short*)(lds + 2 * nb);
+  act_stage_put(s, nb, lds, sd);
+  if ((int)threadIdx.x < nb) (sd + ((nb + 1) & ~1))[threadIdx.x] = (unsigned short)s.aux;
+}
+
 // rows_partial for a wave that also has to form 1 / rms from the chunk sums it requested when it started (RmsTail): a uniform trip
 // count (lanes past the row's units redo the last one and add nothing) so that the whole wave can run the reduction INSIDE the
 // first step -- behind that step's weight requests, while they are in flight.  After its last step a wave is on the launch's

@@ -135,6 +135,10 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
                                                   in-launch hops) instead of leaving x for gate | up to normalize and quantize (bit-identical) */
 #define CRABML_HIP_LLAMA_SPLIT_CHUNKS_ALWAYS 16 /* test / tuning hooks for the norm epilogue: two workgroups per */
 #define CRABML_HIP_LLAMA_SPLIT_CHUNKS_NEVER 32  /* 32-row chunk always / never (default: only for long rows)   */
+#define CRABML_HIP_LLAMA_NQ_TWO_UNIT_ROUNDS 134217728 /* A/B, fast Q4_0 / Q8_0 / Q4_1 step: ffn_down / wo keep two-unit request rounds (every wave reads
+                                                         its rhs units from global memory: request two 64-unit steps of a row, wait, consume,
+                                                         repeat) where the launch would copy the rhs planes into LDS once per workgroup and
+                                                         request the row's weights ahead (rows_partial_deep; bit-identical) */
 
 /* parity hook: copies the layer's K or V cache (raw f16/f32 bytes, [n_kv_heads][seq_len][head_dim]) */
 int crabml_hip_llama_debug_kv(crabml_hip_llama_t* ctx, size_t layer, int32_t which_v, void* dst, size_t nbytes);
