@@ -11,10 +11,18 @@ __device__ __forceinline__ int f16w_slot_of_elem(int j) {
   const int hi = j >> 4, s = (j >> 2) & 3, r = j & 3;
   return 8 * s + 4 * hi + ((r >> 1) | ((r & 1) << 1));
 }
-// orders 1 (Q4_K weights) / 2 (Q6_K weights), Q8_K rows: position (halfs from the row's start) of element E of super-block sb
+// orders 1 (Q4_K weights) / 2 (Q6_K weights) / 3 (Q2_K and Q3_K weights), Q8_K rows: position (halfs from the row's start) of
+// element E of super-block sb
 __device__ __forceinline__ int f16w_pos_q8k(int order, int sb, int E) {
   int cc, g, s, hi, k;
-  if (order == 1) {
+  if (order == 3) {  // E = 128 h + 32 j + l (bits 2 j of qs[32 h + l]): piece g = 2 h + l / 16, dword s, chunk j / 2, slots 4 (j & 1) ..
+    const int l = E & 31, j = (E >> 5) & 3;
+    g = 2 * (E >> 7) + (l >> 4);
+    s = (l >> 2) & 3;
+    k = l & 3;
+    hi = j & 1;
+    cc = 2 * sb + (j >> 1);
+  } else if (order == 1) {
     const int l = E & 7;
     g = E >> 6;
     hi = (E >> 5) & 1;
@@ -52,7 +60,13 @@ __device__ __forceinline__ void rows_to_f16_piece(const char* __restrict__ p, si
   float d;
   const signed char* q;
   int at[8];
-  if constexpr (ORDER == 2) {
+  if constexpr (ORDER == 3) {
+    const int cc = kb >> 2, g = kb & 3, sb = cc >> 1;
+    d = ((const float*)(p + off_d))[sb];
+    q = (const signed char*)p + sb * 256 + 128 * (g >> 1) + 64 * (cc & 1) + 16 * (g & 1) + 4 * s;
+#pragma unroll
+    for (int e = 0; e < 8; e++) at[e] = (e >= 4 ? 32 : 0) + ((e >> 1) & 1) + 2 * (e & 1);
+  } else if constexpr (ORDER == 2) {
     const int cc = kb >> 2, g = kb & 3, sb = cc >> 1;
     d = ((const float*)(p + off_d))[sb];
     q = (const signed char*)p + sb * 256 + 128 * (cc & 1) + 32 * (g >> 1) + 16 * (g & 1) + 4 * s;

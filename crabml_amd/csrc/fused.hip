@@ -1636,7 +1636,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   };
   // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_EXACT=1): the fast pass with matmul_vec's own scaling
   static const bool gemm_exact_hook = test_hook_on("CRABML_HIP_GEMM_EXACT");
-  // The fast pass, Q4_0 / Q8_0 weights x Q8_0 rows, Q4_1 x Q8_1, Q4_K / Q6_K x Q8_K, >= 32 rows: the weight-stationary f16 GEMM
+  // The fast pass, Q4_0 / Q8_0 weights x Q8_0 rows, Q4_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K x Q8_K, >= 32 rows: the weight-stationary f16 GEMM
   // (gemm_f16w.hip; block scales folded into f16 operands, f32 accumulation inside the matrix core -- a stated deviation of the fast
   // tier).  The rows' pre-scaled f16 planes are made once per rhs and k-slot order (q / k / v and gate / up share theirs): `xh`
   // remembers what pf_xh currently holds.
@@ -3086,15 +3086,20 @@ int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* c, const uint32_t* to
   CH_FLUSH(dev);
   const bool rows_8 = (c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1) &&
                       (c->wtype == CRABML_HIP_Q4_0 || c->wtype == CRABML_HIP_Q8_0 || c->wtype == CRABML_HIP_Q4_1);
-  // Q8_K rows: every layer matrix Q4_K, Q5_K or Q6_K (the *_K_M mixes), the classifier one of them too
+  // Q8_K rows: every layer matrix Q4_K, Q5_K or Q6_K (the *_K_M mixes), the classifier one of them too; a context created with
+  // CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K: Q2_K and Q3_K matrices as well (the Q2_K / Q3_K recipes)
   bool rows_k = c->qt == CRABML_HIP_Q8_K;
-  auto k_body = [](const crabml_hip_buf* w) { return w->dtype == CRABML_HIP_Q4_K || w->dtype == CRABML_HIP_Q5_K || w->dtype == CRABML_HIP_Q6_K; };
+  const bool q23 = (c->cfg.flags & CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K) != 0;
+  auto k_body = [q23](const crabml_hip_buf* w) {
+    return w->dtype == CRABML_HIP_Q4_K || w->dtype == CRABML_HIP_Q5_K || w->dtype == CRABML_HIP_Q6_K ||
+           (q23 && (w->dtype == CRABML_HIP_Q2_K || w->dtype == CRABML_HIP_Q3_K));
+  };
   for (size_t l = 0; rows_k && l < c->cfg.n_layers; l++)
     for (const crabml_hip_buf* w : {c->wq[l], c->wk[l], c->wv[l], c->wo[l], c->gate[l], c->up[l], c->down[l]}) rows_k = rows_k && k_body(w);
   rows_k = rows_k && k_body(c->output);
   if (c->tp > 1 || dev->strict_order || c->ext_kv || !(rows_8 || rows_k))
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
-            "llama debug_prefill_tap: only Q4_0 / Q8_0 / Q4_1 and Q4_K / Q5_K / Q6_K layers (the *_K_M mixes) of the fast prompt pass on one device");
+            "llama debug_prefill_tap: only Q4_0 / Q8_0 / Q4_1 and Q4_K / Q5_K / Q6_K layers (the *_K_M mixes; Q2_K / Q3_K: PREFILL_TAP_Q2K_Q3K) of the fast prompt pass on one device");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_prefill_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   CH_TRY(prefill_check(c, tokens, n));
   const size_t chunk = prefill_chunk_rows(c);

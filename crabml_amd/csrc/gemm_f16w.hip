@@ -1,5 +1,5 @@
 // gemm_f16w.hip -- the FAST prompt pass's weight GEMM (crabml_hip_llama_prefill on the fast device; Q4_0 / Q8_0 weights x Q8_0 rows,
-// Q4_1 x Q8_1, Q4_K / Q6_K x Q8_K): weight-stationary on the f16 matrix cores.
+// Q4_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K x Q8_K): weight-stationary on the f16 matrix cores.
 //
 // matmul_vec with a batched rhs is `C[b, m] = W[m, k] . x[b, k]` (matmul_vec.rs:41-76: the (b, k) rhs contract; llama2.rs:111-129).
 // The bit-exact form (gemm_mfma.hip: exact int8 tiles, then the reference's per-block `sumf += (sumi as f32 * d_w) * d_x`) pays
@@ -32,6 +32,17 @@
 // the low nibbles are quarter 0, the high ones quarter 2; g >= 2: ql[32..63], quarters 1 and 3; buf_q6_k.rs:21-48) and the 16 bytes
 // of qh that carry the same l's two high bits, and once per super-block the 16 int8 scales and d.  A' = (q - 32) * fl16(d * sc),
 // q - 32 exact.  Its own B' slot order (k_rows_to_f16<2>): a Q4_K_M layer converts the rows once per order it needs.
+// Q2_K / Q3_K weights (Q8_K rows): element 128 h + 32 j + l of a super-block sits in bits 2 j of qs[32 h + l] (buf_q2_k.rs:35-66,
+// buf_q3_k.rs:37-84), so lane (i, g) loads the 16-byte piece g of qs (h = g >> 1, l = 16 (g & 1) .. + 16) ONCE per super-block -- with
+// the ring slot of its odd chunk -- and chunk c = 0, 1 of the super-block takes shifts 2 c (slots 0-3 of a step) and 2 c + 1 (slots
+// 4-7) out of dword s in step s: the c_lo / c_hi split of the Q4_K unpack with a 2-bit mask.  The scale group of shift j is
+// 8 h + 2 j + (g & 1).
+//   Q2_K: the eight (scale | min << 4) bytes of half h and the (d, dmin) dword ride with qs.  A' = n * fl16(d * (sc & 15)) -
+//   fl16(dmin * (sc >> 4)), n = 0..3 exact, the product exact inside ONE v_pk_fma_f16: three f16 roundings, as for Q4_K.
+//   Q3_K: 16 bytes of hmask (bytes 16 (g & 1) .., bit 4 h + j of byte l) and the 16-byte record (scales[12], d) ride with qs.  The
+//   high bit is ORed in at bit 2 of 0x6400 | low2, the bias -1028 makes it q = low2 - (hbit ? 0 : 4) exactly; A' = q * fl16(d *
+//   (sc - 32)), the 6-bit sc taken out of the record as the reference's aux[] shuffle does: two roundings.
+// ONE B' slot order for both (k_rows_to_f16<3>): a Q2_K-mix layer whose attn_v is Q3_K converts the rows once.
 #include <cstdlib>
 #include <type_traits>
 
@@ -49,7 +60,8 @@ typedef h16x2 f16x2;  // (common.hpp; named like f16x8 here)
 // Q8_K rows (Q4_K weights): slot group kb = 4 cc + g of chunk cc = (super-block, half h), step s = class l = 4 h + s of pair g;
 // slot e: k = 0, 2, 1, 3 of sub-block 2 g (e < 4) / 2 g + 1 (e >= 4), element 8 k + l -- unpack_q4_k_f16's order
 // Q6_K weights: chunk cc = (super-block, half), g, step s: element 128 half + 32 (g >> 1) + 16 (g & 1) + 4 s + k (e < 4), + 64 (e >= 4)
-template <int ORDER>  // 0: Q8_0 / Q8_1 rows (block order); 1: Q8_K rows for Q4_K weights; 2: Q8_K rows for Q6_K weights
+// Q2_K / Q3_K weights: chunk cc = (super-block, c), g = (h, l / 16), step s: element 128 h + 32 (2 c) + 16 (g & 1) + 4 s + k (e < 4), + 32 (e >= 4)
+template <int ORDER>  // 0: Q8_0 / Q8_1 rows (block order); Q8_K rows for 1: Q4_K, 2: Q6_K, 3: Q2_K / Q3_K weights
 __global__ __launch_bounds__(256) void k_rows_to_f16(const char* __restrict__ planes, size_t row_stride, size_t off_d, int nb,
                                                      unsigned short* __restrict__ xh, int* __restrict__ ovf) {
   const size_t col = blockIdx.y;
@@ -58,7 +70,9 @@ __global__ __launch_bounds__(256) void k_rows_to_f16(const char* __restrict__ pl
   rows_to_f16_piece<ORDER>(planes + col * row_stride, off_d, t, xh + col * (size_t)nb * 32, ovf);
 }
 // planes: `rows` sets of activation planes (act_layout(act_qtype, k)); the slot order is the one the weight format w_dtype reads
-int gemm_f16w_order(uint32_t w_dtype) { return w_dtype == CRABML_HIP_Q4_K ? 1 : w_dtype == CRABML_HIP_Q6_K ? 2 : 0; }
+int gemm_f16w_order(uint32_t w_dtype) {
+  return w_dtype == CRABML_HIP_Q4_K ? 1 : w_dtype == CRABML_HIP_Q6_K ? 2 : (w_dtype == CRABML_HIP_Q2_K || w_dtype == CRABML_HIP_Q3_K) ? 3 : 0;
+}
 bool launch_rows_to_f16(hipStream_t st, uint32_t act_qtype, uint32_t w_dtype, const void* planes, size_t rows, size_t k, void* xh, int* ovf) {
   if (!gemm_f16w_covers(w_dtype, act_qtype) || (act_qtype == CRABML_HIP_Q8_K && k % 256 != 0)) return false;
   const ActLayout al = act_layout(act_qtype, k);
@@ -67,7 +81,8 @@ bool launch_rows_to_f16(hipStream_t st, uint32_t act_qtype, uint32_t w_dtype, co
   switch (gemm_f16w_order(w_dtype)) {
     case 0: k_rows_to_f16<0><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh, ovf); break;
     case 1: k_rows_to_f16<1><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh, ovf); break;
-    default: k_rows_to_f16<2><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh, ovf); break;
+    case 2: k_rows_to_f16<2><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh, ovf); break;
+    default: k_rows_to_f16<3><<<grid, 256, 0, st>>>((const char*)planes, al.total, al.off_d, nb, (unsigned short*)xh, ovf); break;
   }
   return true;
 }
@@ -96,9 +111,11 @@ __global__ __launch_bounds__(256) void k_addn_f32(F16wParts a) {
 // -> the lane's eight f16 k-slots (q - 8) * d.  0x6400 | n is the f16 number 1024 + n; -1032 makes it n - 8 exactly.
 // (x & 0x000F000F) | 0x64006400 as ONE v_and_or_b32: a VOP3 instruction takes a single scalar / literal operand, so the compiler
 // splits it unless one constant sits in a VGPR -- `magic` (loop-invariant, one register)
+// (BITS: the width of the field at the bottom of each 16-bit half -- 4: a nibble; 2: a Q2_K / Q3_K level)
+template <int BITS = 4>
 __device__ __forceinline__ unsigned and_or_magic(unsigned x, unsigned magic) {
   unsigned r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(0x000F000Fu), "v"(magic));
+  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(((1u << BITS) - 1u) * 0x00010001u), "v"(magic));
   return r;
 }
 __device__ __forceinline__ f16x8 unpack_q4_0_f16(unsigned w, f16x2 d2, unsigned magic) {
@@ -129,10 +146,12 @@ __device__ __forceinline__ f16x8 unpack_q8_0_f16(unsigned w0, unsigned w1, f16x2
 struct Q4KF16Consts {
   f16x2 c_lo, o_lo, c_hi, o_hi;
 };
+// (BITS = 2: Q2_K -- the dword already shifted so that bits 0-1 of each byte are the chunk's first shift and bits 2-3 its second)
+template <int BITS = 4>
 __device__ __forceinline__ f16x8 unpack_q4_k_f16(unsigned w, const Q4KF16Consts& cs, unsigned magic) {
   const f16x2 bias = {(_Float16)-1024.0f, (_Float16)-1024.0f};
-  const unsigned u0 = and_or_magic(w, magic), u1 = and_or_magic(w >> 8, magic);
-  const unsigned u2 = and_or_magic(w >> 4, magic), u3 = and_or_magic(w >> 12, magic);
+  const unsigned u0 = and_or_magic<BITS>(w, magic), u1 = and_or_magic<BITS>(w >> 8, magic);
+  const unsigned u2 = and_or_magic<BITS>(w >> BITS, magic), u3 = and_or_magic<BITS>(w >> (8 + BITS), magic);
   const f16x2 p0 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u0) + bias, cs.c_lo, cs.o_lo);
   const f16x2 p1 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u1) + bias, cs.c_lo, cs.o_lo);
   const f16x2 p2 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u2) + bias, cs.c_hi, cs.o_hi);
@@ -163,7 +182,48 @@ __device__ __forceinline__ f16x8 unpack_q6_k_f16(unsigned w, unsigned hw, f16x2 
   return f16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
 
-enum { WF_Q4_0 = 0, WF_Q8_0 = 1, WF_Q4_K = 2, WF_Q6_K = 3, WF_Q4_1 = 4 };  // the weight format of a GEMM
+
+// Q2_K: unpack_q4_k_f16<2>; the constants of chunk c of the lane's piece: scale bytes 2 (2 c + u) + (g & 1), u = 0, 1, of its half's eight (sc: dword c of them)
+__device__ __forceinline__ Q4KF16Consts q2k_f16_consts(unsigned sc, unsigned dm, int g) {
+  const unsigned b = sc >> (8 * (g & 1));  // the two bytes at bits 0 and 16
+  const float d = h2f((unsigned short)(dm & 0xffffu)), dmin = h2f((unsigned short)(dm >> 16));
+  const _Float16 c_lo = (_Float16)(d * (float)(b & 15u)), c_hi = (_Float16)(d * (float)((b >> 16) & 15u));  // (11 x 4 bits: exact in f32)
+  const _Float16 o_lo = (_Float16)-(dmin * (float)((b >> 4) & 15u)), o_hi = (_Float16)-(dmin * (float)((b >> 20) & 15u));
+  return Q4KF16Consts{f16x2{c_lo, c_lo}, f16x2{o_lo, o_lo}, f16x2{c_hi, c_hi}, f16x2{o_hi, o_hi}};
+}
+// Q3_K: hw = the matching dword of hmask, already shifted so that bit 0 of each byte belongs to the first shift and bit 1 to the
+// second; ORed in at bit 2 (the way and_or_hi2 does for Q6_K): 1024 + low2 + 4 hbit, -1028 makes it q = low2 - (hbit ? 0 : 4)
+__device__ __forceinline__ unsigned and_or_hbit(unsigned x, unsigned acc) {
+  unsigned r;
+  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(0x00040004u), "v"(acc));
+  return r;
+}
+__device__ __forceinline__ f16x8 unpack_q3_k_f16(unsigned w, unsigned hw, f16x2 c_lo, f16x2 c_hi, unsigned magic) {
+  const f16x2 bias = {(_Float16)-1028.0f, (_Float16)-1028.0f};
+  const unsigned u0 = and_or_hbit(hw << 2, and_or_magic<2>(w, magic)), u1 = and_or_hbit(hw >> 6, and_or_magic<2>(w >> 8, magic));
+  const unsigned u2 = and_or_hbit(hw << 1, and_or_magic<2>(w >> 2, magic)), u3 = and_or_hbit(hw >> 7, and_or_magic<2>(w >> 10, magic));
+  const f16x2 p0 = (__builtin_bit_cast(f16x2, u0) + bias) * c_lo, p1 = (__builtin_bit_cast(f16x2, u1) + bias) * c_lo;
+  const f16x2 p2 = (__builtin_bit_cast(f16x2, u2) + bias) * c_hi, p3 = (__builtin_bit_cast(f16x2, u3) + bias) * c_hi;
+  return f16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+// the two constants fl16(d * (sc - 32)) of chunk c of the lane's piece: scale indices 8 h + 2 (2 c + u) + (g & 1), u = 0, 1, of the record
+// (scales[12], d): index j's low nibble is nibble j / 8 of byte j % 8, its two high bits sit at bit 2 (j / 4) of byte 8 + j % 4
+// (buf_q3_k.rs's aux[] shuffle)
+template <int C>
+__device__ __forceinline__ void q3k_f16_consts(i32x4 rec, int g, f16x2& c_lo, f16x2& c_hi) {
+  const int h = g >> 1;
+  const unsigned lo = (unsigned)rec[C] >> (8 * (g & 1) + 4 * h), hi = (unsigned)rec[2] >> (8 * (g & 1) + 2 * (2 * h + C));
+  const int s0 = (int)((lo & 15u) | ((hi & 3u) << 4)) - 32, s1 = (int)(((lo >> 16) & 15u) | (((hi >> 16) & 3u) << 4)) - 32;
+  const float d = h2f((unsigned short)((unsigned)rec[3] & 0xffffu));
+  const _Float16 a = (_Float16)(d * (float)s0), b = (_Float16)(d * (float)s1);  // (11 x 6 bits: exact in f32)
+  c_lo = f16x2{a, a};
+  c_hi = f16x2{b, b};
+}
+
+enum { WF_Q4_0 = 0, WF_Q8_0 = 1, WF_Q4_K = 2, WF_Q6_K = 3, WF_Q4_1 = 4, WF_Q2_K = 5, WF_Q3_K = 6 };  // the weight format of a GEMM
+// the forms whose rows are Q8_K: a chunk is half a super-block, so k is whole super-blocks and the k pieces of a split launch start on
+// super-block boundaries
+constexpr bool f16w_wf_superblock(int wf) { return wf == WF_Q4_K || wf == WF_Q6_K || wf == WF_Q2_K || wf == WF_Q3_K; }
 
 template <int T_>
 struct GemmF16Geo {
@@ -183,8 +243,8 @@ struct GemmF16Geo {
 // chip idle for a whole serial k loop): row tile rt belongs to the first matrix whose cumulative tile count exceeds it.
 struct F16wMats {
   const i32x4* wq[3];  // the quant plane
-  const char* wd[3];   // the scale plane (f16 per block; Q4_1: (d, m); Q4_K: the 16-byte headers; Q6_K: the qh plane)
-  const char* ws2[3];  // Q6_K: the int8 scales (16 per super-block) ...
+  const char* wd[3];   // the scale plane (f16 per block; Q4_1: (d, m); Q4_K: the 16-byte headers; Q6_K: the qh plane; Q2_K: the scale bytes; Q3_K: hmask)
+  const char* ws2[3];  // Q6_K: the int8 scales (16 per super-block) ...; Q2_K: the (d, dmin) dwords; Q3_K: the 16-byte records
   const char* ws3[3];  // ... and d (f16 per super-block)
   float* out[3];
   float* out2[3];    // ksplit > 1: k piece s >= 1 writes its partial tiles to out2[j] + (s - 1) pstride (k_addn_f32 adds them)
@@ -243,18 +303,20 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
   // this workgroup's chunks: [ch_lo, ch_lo + nchunks) of the row's ceil(nb / KCH)
   // (Q4_K: an even chunk is half 0 of its super-block -- the pieces start on super-block boundaries)
   const int all_chunks = (nb + KCH - 1) / KCH;
-  const int per_piece = (WF == WF_Q4_K || WF == WF_Q6_K) ? (((all_chunks + ksplit - 1) / ksplit + 1) & ~1) : (all_chunks + ksplit - 1) / ksplit;
+  const int per_piece = f16w_wf_superblock(WF) ? (((all_chunks + ksplit - 1) / ksplit + 1) & ~1) : (all_chunks + ksplit - 1) / ksplit;
   const int ch_lo = ks * per_piece;
   const int nchunks = all_chunks - ch_lo < per_piece ? all_chunks - ch_lo : per_piece;  // (>= 1: the launcher splits only long rows)
 
   // A: the lane's block (row i of fragment f, block kb0 + g) and its scale.  HBM latency is several chunk times (a chunk is ~0.4 us of
   // MFMAs and a workgroup has the SIMD almost to itself): a RING of four register sets, chunk c + 3 requested while chunk c is
   // multiplied; B' (L2-resident) two chunks ahead in two register sets.  All ring indices are compile-time (chunk loop unrolled by 4).
-  constexpr int NQ = (WF == WF_Q8_0 || WF == WF_Q6_K) ? 2 : 1;  // 16-byte quant loads per fragment and chunk
+  // (Q2_K / Q3_K: per SUPER-BLOCK, in the ring slot of its odd chunk -- the even chunk reads its neighbour's slot; the even slots stay empty)
+  constexpr int NQ = (WF == WF_Q8_0 || WF == WF_Q6_K || WF == WF_Q3_K) ? 2 : 1;  // 16-byte quant loads per fragment and chunk
   i32x4 aq[4][NQ * F];
   unsigned ad[4][F];   // Q4_0 / Q8_0: the block's scale; Q4_1: d | m << 16
   i32x4 hq[2][F];      // Q4_K: the super-block header of ring slots (0, 1) / (2, 3), fetched with the even slot; Q6_K: the 16 scales
-  unsigned hd[2][F];   // Q6_K: d
+                       // Q2_K: the half's eight scale bytes ([0], [1]), fetched with the ODD slot; Q3_K: the record, likewise
+  unsigned hd[2][F];   // Q6_K: d; Q2_K: d | dmin << 16
   auto fetch_a = [&](auto Jc, int ch) {
     constexpr int J = decltype(Jc)::value;
     const int cc = ch_lo + (ch < nchunks ? ch : nchunks - 1);  // (past the end: re-read the last chunk, never consumed)
@@ -267,6 +329,27 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
         const size_t blk = (size_t)(row < m ? row : m - 1) * nsb + sb;
         aq[J][f] = __builtin_nontemporal_load(wq + blk * 8 + 2 * g + h);
         if constexpr ((J & 1) == 0) hq[J >> 1][f] = __builtin_nontemporal_load(wh + blk);
+      }
+    } else if constexpr (WF == WF_Q2_K || WF == WF_Q3_K) {
+      // the super-block of chunks (ch - 1, ch), asked for with the odd one: requested while chunk ch - 3 is multiplied, first consumed
+      // two chunks later, and not overwritten before chunk ch + 1 (the slot's next fetch comes with chunk ch + 1's)
+      if constexpr ((J & 1) == 1) {
+        const int nsb = nb >> 3, sb = cc >> 1;
+#pragma unroll
+        for (int f = 0; f < F; f++) {
+          F16W_PTRS(f);
+          const int row = r0 + FSTEP * f + i;
+          const size_t blk = (size_t)(row < m ? row : m - 1) * nsb + sb;
+          aq[J][NQ * f] = __builtin_nontemporal_load(wq + blk * 4 + g);
+          if constexpr (WF == WF_Q3_K) {
+            aq[J][NQ * f + 1] = __builtin_nontemporal_load(wh + blk * 2 + (g & 1));  // (wh: the hmask plane, 32 bytes per super-block)
+            hq[J >> 1][f] = __builtin_nontemporal_load(w6s + blk);
+          } else {
+            const i32x2 sc = __builtin_nontemporal_load((const i32x2*)(wsc + blk * 16) + (g >> 1));
+            hq[J >> 1][f] = i32x4{sc[0], sc[1], 0, 0};
+            hd[J >> 1][f] = __builtin_nontemporal_load((const unsigned*)w6s + blk);
+          }
+        }
       }
     } else if constexpr (WF == WF_Q6_K) {
       const int nsb = nb >> 3, sb = cc >> 1, half = cc & 1;
@@ -344,6 +427,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
   fetch_a(std::integral_constant<int, 1>{}, 1);
   fetch_a(std::integral_constant<int, 2>{}, 2);
   Q4KF16Consts cs[F];  // Q4_K: the lane's pair's constants of the current super-block (made in the even slot); Q4_1: (d, m); Q6_K: d sc
+                       // Q2_K / Q3_K: the constants of the current CHUNK (Q3_K: c_lo and c_hi only)
   commit_b(rb[0], 0);
   // chunk c sits in rb[c % NBD] from NBD chunks before it is committed (the fetches come in chunk order: pb advances)
 #pragma unroll
@@ -373,6 +457,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
           cs[f].o_lo = f16x2{c[2], c[2]};
           cs[f].o_hi = f16x2{c[3], c[3]};
         }
+      } else if constexpr (WF == WF_Q2_K) {
+        cs[f] = q2k_f16_consts((unsigned)hq[J >> 1][f][J & 1], hd[J >> 1][f], g);
+      } else if constexpr (WF == WF_Q3_K) {
+        q3k_f16_consts<(J & 1)>(hq[J >> 1][f], g, cs[f].c_lo, cs[f].c_hi);
       } else if constexpr (WF == WF_Q4_1) {
         const unsigned dm = ad[J][f];
         cs[f].c_lo = cs[f].c_hi = __builtin_bit_cast(f16x2, (dm & 0xffffu) | (dm << 16));
@@ -403,6 +491,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
           if constexpr (WF == WF_Q4_0) a[f] = unpack_q4_0_f16((unsigned)aq[J][f][s], d2[f], magic);
           if constexpr (WF == WF_Q8_0) a[f] = unpack_q8_0_f16((unsigned)aq[J][2 * f][s], (unsigned)aq[J][2 * f + 1][s], d2[f], magic);
           if constexpr (WF == WF_Q4_K || WF == WF_Q4_1) a[f] = unpack_q4_k_f16((unsigned)aq[J][f][s], cs[f], magic);
+          if constexpr (WF == WF_Q2_K) a[f] = unpack_q4_k_f16<2>((unsigned)aq[J | 1][f][s] >> (4 * (J & 1)), cs[f], magic);
+          if constexpr (WF == WF_Q3_K)
+            a[f] = unpack_q3_k_f16((unsigned)aq[J | 1][2 * f][s] >> (4 * (J & 1)), (unsigned)aq[J | 1][2 * f + 1][s] >> (4 * (g >> 1) + 2 * (J & 1)),
+                                   cs[f].c_lo, cs[f].c_hi, magic);
           if constexpr (WF == WF_Q6_K)
             a[f] = unpack_q6_k_f16((unsigned)aq[J][2 * f][s], (unsigned)aq[J][2 * f + 1][s] >> (2 * (g >> 1)), (J & 1) ? cs[f].o_lo : cs[f].c_lo,
                                    (J & 1) ? cs[f].o_hi : cs[f].c_hi, magic);
@@ -566,7 +658,8 @@ size_t gemm_f16w_xh_bytes(size_t rows, size_t k) { return ((rows + 127) / 128 * 
 
 // A' range: 1 in *bad when some block's scales can put an |A'| above 65504 (f16: +-inf, and inf times a zero B' slot is NaN) -- the
 // largest quant magnitude of the format times the block's scale, as the kernel rounds it (Q4_K: the largest 6-bit scale and minimum,
-// 63; Q6_K: the super-block's own int8 scales); a non-finite scale counts as out of range
+// 63; Q6_K: the super-block's own int8 scales; Q2_K: n c1 - c2 with the largest 4-bit scale and minimum, 15, and n <= 3; Q3_K: q c with
+// |sc - 32| <= 32 and |q| <= 4); a non-finite scale counts as out of range
 __global__ __launch_bounds__(256) void k_f16w_range(const char* __restrict__ sc, const signed char* __restrict__ sc6,
                                                     const unsigned short* __restrict__ d6, size_t nblk, int wf, int* __restrict__ bad) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -581,6 +674,13 @@ __global__ __launch_bounds__(256) void k_f16w_range(const char* __restrict__ sc,
     const unsigned h = ((const unsigned*)sc)[4 * i];
     const float c1 = h2f(f2h(63.0f * h2f((unsigned short)(h & 0xffffu)))), c2 = h2f(f2h(63.0f * h2f((unsigned short)(h >> 16))));
     a = 15.0f * fabsf(c1) + fabsf(c2);  // n c1 - c2, n <= 15
+  } else if (wf == WF_Q2_K) {
+    const unsigned h = ((const unsigned*)(sc + nblk * 16))[i];  // (the (d, dmin) dwords follow the scale bytes)
+    const float c1 = h2f(f2h(15.0f * h2f((unsigned short)(h & 0xffffu)))), c2 = h2f(f2h(15.0f * h2f((unsigned short)(h >> 16))));
+    a = 3.0f * fabsf(c1) + fabsf(c2);
+  } else if (wf == WF_Q3_K) {
+    const unsigned short dh = ((const unsigned short*)(sc + nblk * 32))[8 * i + 6];  // (the records follow hmask; d behind scales[12])
+    a = 4.0f * fabsf(h2f(f2h(32.0f * h2f(dh))));
   } else {
     const float d = h2f(d6[i]);
     for (int j = 0; j < 16; j++) a = fmaxf(a, 32.0f * fabsf(h2f(f2h(d * (float)sc6[16 * i + j]))));  // (q - 32) c, |q - 32| <= 32
@@ -589,7 +689,15 @@ __global__ __launch_bounds__(256) void k_f16w_range(const char* __restrict__ sc,
   if (!(a <= 65504.0f)) *bad = 1;
 }
 static int f16w_wf(uint32_t dt) {
-  return dt == CRABML_HIP_Q8_0 ? WF_Q8_0 : dt == CRABML_HIP_Q4_K ? WF_Q4_K : dt == CRABML_HIP_Q6_K ? WF_Q6_K : dt == CRABML_HIP_Q4_1 ? WF_Q4_1 : WF_Q4_0;
+  switch (dt) {
+    case CRABML_HIP_Q8_0: return WF_Q8_0;
+    case CRABML_HIP_Q4_K: return WF_Q4_K;
+    case CRABML_HIP_Q6_K: return WF_Q6_K;
+    case CRABML_HIP_Q4_1: return WF_Q4_1;
+    case CRABML_HIP_Q2_K: return WF_Q2_K;
+    case CRABML_HIP_Q3_K: return WF_Q3_K;
+    default: return WF_Q4_0;
+  }
 }
 // once per weight buffer (and per version of its contents): one reduction over the scale plane, read back -- blocks the stream the
 // first time (a fast-device model context asks for every matrix when it is created)
@@ -621,7 +729,8 @@ bool gemm_f16w_takes(crabml_hip_device* dev, const crabml_hip_buf* w, uint32_t a
 bool gemm_f16w_covers(uint32_t w_dtype, uint32_t act_qtype) {
   if (act_qtype == CRABML_HIP_Q8_0) return w_dtype == CRABML_HIP_Q4_0 || w_dtype == CRABML_HIP_Q8_0;
   if (act_qtype == CRABML_HIP_Q8_1) return w_dtype == CRABML_HIP_Q4_1;
-  return act_qtype == CRABML_HIP_Q8_K && (w_dtype == CRABML_HIP_Q4_K || w_dtype == CRABML_HIP_Q6_K);
+  return act_qtype == CRABML_HIP_Q8_K &&
+         (w_dtype == CRABML_HIP_Q4_K || w_dtype == CRABML_HIP_Q6_K || w_dtype == CRABML_HIP_Q2_K || w_dtype == CRABML_HIP_Q3_K);
 }
 // wave tile: T column tiles of 16 prompt rows -- 8 (128-row workgroup tiles) from 65 rows up; short passes (a short prompt, the ragged
 // tail of a long one) take 4 / 2: the MFMAs of an empty column tile cost what a full one's do
@@ -654,8 +763,9 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
   if (defer_parts) *defer_parts = 0;
   if (nw < 1 || nw > 3 || k % 32 != 0 || b < 16) return false;
   const uint32_t dt = w[0]->dtype;
-  if (dt != CRABML_HIP_Q4_0 && dt != CRABML_HIP_Q8_0 && dt != CRABML_HIP_Q4_K && dt != CRABML_HIP_Q6_K && dt != CRABML_HIP_Q4_1) return false;
-  if ((dt == CRABML_HIP_Q4_K || dt == CRABML_HIP_Q6_K) && k % 256 != 0) return false;
+  if (!gemm_f16w_covers(dt, vec_dot_rhs_dtype(dt))) return false;  // (the one format list)
+  const bool superblock = f16w_wf_superblock(f16w_wf(dt));
+  if (superblock && k % 256 != 0) return false;
   for (int j = 0; j < nw; j++)
     if (w[j]->dtype != dt || m[j] % 4 != 0 || !f16w_range_ok(dev, w[j])) return false;
   static const int variant = [] {  // lab hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_F16W=n): 1 = two fragments, 3 = one; +8 = never split k; +16 = T = 8 always; +32 = k pieces of >= 8 chunks; +64 = no gate | up epilogue; +512 = T = 4 always; +1024 = narrow launches as <2, 4>
@@ -705,7 +815,8 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
     const char* wp = (const char*)w[jj]->ptr;
     mats.wq[j] = (const i32x4*)wp;
     mats.wd[j] = wp + w[jj]->wl.off_scale;
-    mats.ws2[j] = wp + w[jj]->wl.off_scale + w[jj]->wl.n_blocks * 64;  // (Q6_K: ql | qh | scales | d, common.hpp)
+    // (Q6_K: ql | qh | scales | d; Q2_K: qs | scales | (d, dmin); Q3_K: qs | hmask | records, common.hpp)
+    mats.ws2[j] = wp + w[jj]->wl.off_scale + w[jj]->wl.n_blocks * (dt == CRABML_HIP_Q2_K ? 16 : dt == CRABML_HIP_Q3_K ? 32 : 64);
     mats.ws3[j] = wp + w[jj]->wl.off_scale + w[jj]->wl.n_blocks * 80;
     mats.out[j] = out[jj];
     mats.out2[j] = ws + before;
@@ -731,7 +842,7 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
       ksplit *= 2;
   if (force && force->ksplit > 0) {  // every piece must hold at least one chunk (the kernel's per_piece), the partials must fit ws
     const int ks = force->ksplit, all_chunks = (int)((k / 32 + 3) / 4);
-    const int per_piece = (dt == CRABML_HIP_Q4_K || dt == CRABML_HIP_Q6_K) ? (((all_chunks + ks - 1) / ks + 1) & ~1) : (all_chunks + ks - 1) / ks;
+    const int per_piece = superblock ? (((all_chunks + ks - 1) / ks + 1) & ~1) : (all_chunks + ks - 1) / ks;
     if ((ks != 1 && ks != 2 && ks != 4 && ks != 8) || (ks > 1 && (gu || ws == nullptr || (size_t)(ks - 1) * before > ws_floats)) ||
         (ks - 1) * per_piece >= all_chunks)
       return false;
@@ -755,6 +866,10 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
     ok = launch_f16w_fmt<WF_Q6_K>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
   else if (dt == CRABML_HIP_Q4_1)
     ok = launch_f16w_fmt<WF_Q4_1>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
+  else if (dt == CRABML_HIP_Q2_K)
+    ok = launch_f16w_fmt<WF_Q2_K>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
+  else if (dt == CRABML_HIP_Q3_K)
+    ok = launch_f16w_fmt<WF_Q3_K>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
   else
     ok = launch_f16w_fmt<WF_Q4_0>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
   if (ok && gu) *gu_done = hquant ? 2 : 1;

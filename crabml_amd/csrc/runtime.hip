@@ -1019,13 +1019,13 @@ int crabml_hip_debug_gemm_f16w(crabml_hip_device_t* dev, const crabml_hip_buf_t*
   CH_USE(dev);
   CH_FLUSH(dev);
   const uint32_t dt = w[0] ? w[0]->dtype : 0;
-  const uint32_t qt = dt == CRABML_HIP_Q4_1 ? CRABML_HIP_Q8_1 : (dt == CRABML_HIP_Q4_K || dt == CRABML_HIP_Q6_K) ? CRABML_HIP_Q8_K : CRABML_HIP_Q8_0;
+  const uint32_t qt = vec_dot_rhs_dtype(dt);  // (a format the GEMM does not cover is refused below)
   size_t mtot = 0;
   for (size_t j = 0; j < nw; j++) {
     if (!w[j] || !out[j]) return CRABML_HIP_BAD_INPUT;
     CH_TRY(observe(dev, w[j]));
     if (!gemm_f16w_covers(w[j]->dtype, qt) || w[j]->dtype != dt || w[j]->k != k || m[j] * k > w[j]->n_elems)
-      CH_BAIL(dev, CRABML_HIP_TENSOR_ERROR, "debug_gemm_f16w: one of Q4_0 / Q8_0 / Q4_1 / Q4_K / Q6_K for every matrix, matching shapes");
+      CH_BAIL(dev, CRABML_HIP_TENSOR_ERROR, "debug_gemm_f16w: one of Q4_0 / Q8_0 / Q4_1 / Q4_K / Q6_K / Q2_K / Q3_K for every matrix, matching shapes");
     mtot += m[j];
   }
   CH_TRY(observe(dev, x));

@@ -123,8 +123,12 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
                                                    instead of leaving h as f32 from one workgroup per CU for ffn_down's prologue (bit-identical) */
 #define CRABML_HIP_LLAMA_PREFILL_INT8_GEMM 524288 /* A/B: the fast prompt pass keeps the bit-exact int8 matrix-core GEMM (with the fused last
                                                      product) at every pass size, instead of the weight-stationary f16 GEMM that Q4_0 / Q8_0 /
-                                                     Q4_1 / Q4_K / Q6_K weights take from 32 rows (gemm_f16w.hip; a stated deviation of the
+                                                     Q4_1 / Q4_K / Q6_K / Q2_K / Q3_K weights take from 32 rows (gemm_f16w.hip; a stated deviation of the
                                                      fast tier) */
+#define CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K 268435456 /* test hook: crabml_hip_llama_debug_prefill_tap also serves contexts whose layer
+                                                         matrices or classifier are Q2_K / Q3_K (the checker restates their kernels:
+                                                         tests/q23k_f16w_ref.py).  Off, the tap refuses such a context with
+                                                         NOT_IMPLEMENTED, as it always has.  Changes nothing the pass computes */
 #define CRABML_HIP_LLAMA_PREFILL_SEPARATE_F16_ROWS 33554432 /* A/B, fast prompt pass: the rows' f16 planes for the weight GEMM are made by their
                                                               own launch (k_rows_to_f16) instead of by the kernels that quantize the rows,
                                                               and the k pieces of a split wo / ffn_down GEMM are added by their own launch

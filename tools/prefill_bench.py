@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Prompt-processing throughput of the batched prefill (crabml_hip_llama_prefill) against the token loop.
 usage: prefill_bench.py [--model llama3-8b] [--wtype Q4_0] [--n 512] [--chunks 64,128,256,512] [--layers N]
+--wtype: a name of synth.TYPE_BY_NAME or a recipe: Q4_K_M, Q3_K_S, Q3_K_M, Q3_K_L, Q2_K_MIX (llama.cpp's "Q2_K" file type), Q2_K_S.
 Prints one line per chunk size: prompt tokens/s (host clock around the blocking call, 2nd of 2 runs) and the int8
 MFMA rate the weight GEMMs reach (2 * m * k ops per prompt row and weight element)."""
 import argparse
@@ -21,8 +22,12 @@ ap.add_argument("--loop", type=int, default=64, help="tokens of the token-loop b
 ap.add_argument("--flags", type=int, default=0, help="extra CRABML_HIP_LLAMA_* flags (A/B runs)")
 a = ap.parse_args()
 shape = synth.SHAPES[a.model]
-k_m = a.wtype.upper() == "Q4_K_M"  # llama.cpp's mix: Q4_K body, attn_v / ffn_down in Q6_K on some layers, Q6_K classifier
-model = synth.build_model(shape, synth.Q4_K if k_m else synth.TYPE_BY_NAME[a.wtype], seed=8, n_layers=a.layers or None, k_m_mix=k_m)
+wt = a.wtype.upper()
+k_m = wt == "Q4_K_M"  # llama.cpp's mix: Q4_K body, attn_v / ffn_down in Q6_K on some layers, Q6_K classifier
+q3 = wt[5:] if wt in ("Q3_K_S", "Q3_K_M", "Q3_K_L") else None  # the Q3_K recipes (synth.q3_k_mix_types), named as tools/generate.py --synth names them
+q2 = {"Q2_K_MIX": "K", "Q2_K_S": "S"}.get(wt)  # the Q2_K recipes (synth.q2_k_mix_types; plain Q2_K: every matrix Q2_K)
+model = synth.build_model(shape, synth.TYPE_BY_NAME[wt[:4]] if k_m or q3 or q2 else synth.TYPE_BY_NAME[a.wtype], seed=8, n_layers=a.layers or None,
+                          k_m_mix=k_m, q3_k_mix=q3, q2_k_mix=q2)
 dev = ca.HipTensorDevice(0)
 conf, w = synth.to_hip(model, dev)
 L = a.layers or shape.n_layers
