@@ -3013,6 +3013,54 @@ int crabml_hip_llama_debug_kv(crabml_hip_llama_t* c, size_t layer, int32_t which
   return 0;
 }
 
+// test hook (crabml_hip_debug.h, where the classes are listed): the cache rows past kv_len, the step's data scratch and the prompt
+// pass's row buffers filled with a pattern, in stream order.  A buffer is filled as the whole pool block dalloc gave it.
+int crabml_hip_llama_debug_poison(crabml_hip_llama_t* c, uint32_t what, uint16_t fill16, uint32_t fill32) {
+  if (!c || (what & ~7u)) return CRABML_HIP_BAD_INPUT;
+  crabml_hip_device* dev = c->dev;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  if (c->tp > 1 || c->ext_kv)
+    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama debug_poison: one device and the context's own KV cache only");
+  hipStream_t st = dev->stream;
+  auto words = [&](void* p, size_t bytes, bool half) -> int {
+    if (half)
+      CH_HIP(dev, hipMemsetD16Async((hipDeviceptr_t)p, fill16, bytes / 2, st));
+    else
+      CH_HIP(dev, hipMemsetD32Async((hipDeviceptr_t)p, (int)fill32, bytes / 4, st));
+    return 0;
+  };
+  auto fill = [&](void* p, bool half) -> int {
+    if (!p) return 0;
+    for (const auto& a : c->allocs)
+      if (a.first == p) return words(p, a.second, half);
+    CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama debug_poison: a buffer that is no allocation of the context");
+  };
+  if (what & 1) {
+    const auto& g = c->cfg;
+    const bool kv16 = g.use_f16_kv_cache != 0;
+    const size_t es = kv16 ? 2 : 4, hd = (size_t)c->hd, live = c->kv_len < g.seq_len ? c->kv_len : g.seq_len;
+    const size_t tail = (g.seq_len - live) * hd * es;
+    for (size_t l = 0; l < g.n_layers && tail; l++)
+      for (void* base : {c->kc[l], c->vc[l]})
+        for (size_t h = 0; h < (size_t)c->n_kv_l; h++) CH_TRY(words((char*)base + (h * g.seq_len + live) * hd * es, tail, kv16));
+  }
+  if (what & 2) {
+    for (void* p : {(void*)c->x, (void*)c->partial, (void*)c->qbuf, (void*)c->attn, (void*)c->h, (void*)c->tmp, (void*)c->xn, (void*)c->logits,
+                    (void*)c->rsums, (void*)c->scores_g, (void*)c->flash_part, (void*)c->am_val, (void*)c->out_tokens})
+      CH_TRY(fill(p, false));
+    for (void* p : {(void*)c->act_dim, (void*)c->act_attn, (void*)c->act_hid, (void*)c->p16}) CH_TRY(fill(p, true));
+  }
+  if ((what & 4) && c->pf_cap) {
+    for (void* p : {(void*)c->pf_x, (void*)c->pf_xn, (void*)c->pf_q, (void*)c->pf_k, (void*)c->pf_v, (void*)c->pf_qr, (void*)c->pf_attn,
+                    (void*)c->pf_tmp, (void*)c->pf_g, (void*)c->pf_u, (void*)c->pf_split, (void*)c->pf_scores})
+      CH_TRY(fill(p, false));
+    for (void* p : {(void*)c->pf_act_dim, (void*)c->pf_act_hid, c->pf_xh, c->pf_xh2, (void*)c->pf_p16}) CH_TRY(fill(p, true));
+  }
+  return 0;
+}
+
 // parity hook (crabml_hip_debug.h): one eager decode step with the buffers of one layer copied out between its launches
 int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, size_t layer, float* logits, void* dst, size_t dst_bytes,
                                crabml_hip_tap_entry_t* dir, size_t* need) {
@@ -3221,8 +3269,8 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
 }
 
 int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
-                                     size_t n_kv, size_t head_dim, size_t seq, size_t slices, float* out, float* out2) {
-  if (!dev || !q || !k || !v || !out || seq == 0 || n_kv == 0 || n_heads % n_kv != 0) return CRABML_HIP_BAD_INPUT;
+                                     size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap, size_t slices, float* out, float* out2) {
+  if (!dev || !q || !k || !v || !out || seq == 0 || seq_cap < seq || n_kv == 0 || n_heads % n_kv != 0) return CRABML_HIP_BAD_INPUT;
   CH_LIVE(dev);
   CH_USE(dev);
   CH_FLUSH(dev);
@@ -3233,7 +3281,7 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
   if (raise_dyn_lds(dev, (const void*)fn, (int)flash_lds_bytes(grp, hd)) != hipSuccess ||
       raise_dyn_lds(dev, (const void*)fnt, (int)flash_lds_bytes(grp, hd)) != hipSuccess)
     CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "debug_flash_attention: LDS");
-  const size_t nq = n_heads * head_dim * 4, nkv = n_kv * seq * head_dim * 2, npart = n_kv * slices * flash_part_floats(grp, hd) * 4;
+  const size_t nq = n_heads * head_dim * 4, nkv = n_kv * seq_cap * head_dim * 2, npart = n_kv * slices * flash_part_floats(grp, hd) * 4;
   char* base = nullptr;
   const size_t o_q = 0, o_k = align_up(o_q + nq, 256), o_v = align_up(o_k + nkv, 256), o_out = align_up(o_v + nkv, 256),
                o_part = align_up(o_out + nq, 256), o_tick = align_up(o_part + npart, 256), o_pos = o_tick + align_up(n_kv * 4, 256),
@@ -3253,7 +3301,7 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
     hipLaunchKernelGGL(fn, dim3((unsigned)(n_kv * slices)), dim3(flash_threads(grp)), (uint32_t)flash_lds_bytes(grp, hd), st,
                        (const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
                        (const int*)(base + o_pos), (float*)(base + o_part), (unsigned*)(base + o_tick), (float*)(base + o_out),
-                       (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, (int)seq, (int)slices, FLASH_MIN_ROWS);
+                       (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, (int)seq_cap, (int)slices, FLASH_MIN_ROWS);
     with_const_else<256, 128, 64>(hd, [&](auto hdc) {  // (flash_kernel has no other head_dim)
       constexpr int HD = decltype(hdc)::value;
       hipLaunchKernelGGL((k_attn_flash_merge<HD, false>), dim3((unsigned)n_heads), dim3(HD), 0, st, (const float*)(base + o_part),
@@ -3266,7 +3314,7 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
         hipLaunchKernelGGL(fnt, dim3((unsigned)(n_kv * slices)), dim3(flash_threads(grp)), (uint32_t)flash_lds_bytes(grp, hd), st,
                            (const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
                            (const int*)(base + o_pos), (float*)(base + o_part), (unsigned*)(base + o_tick), (float*)(base + o_out),
-                           (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, (int)seq, (int)slices, FLASH_MIN_ROWS);
+                           (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, (int)seq_cap, (int)slices, FLASH_MIN_ROWS);
     }
     e = hipGetLastError();
   }

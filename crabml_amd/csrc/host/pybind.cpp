@@ -159,14 +159,17 @@ PYBIND11_MODULE(_host, m) {
            [](HipTensorDevice& d, py::array_t<float, py::array::c_style | py::array::forcecast> q,
               py::array_t<uint16_t, py::array::c_style | py::array::forcecast> k,
               py::array_t<uint16_t, py::array::c_style | py::array::forcecast> v, size_t n_heads, size_t n_kv, size_t head_dim,
-              size_t seq, size_t slices) {
-             if ((size_t)q.size() != n_heads * head_dim || (size_t)k.size() != n_kv * seq * head_dim || k.size() != v.size())
+              size_t seq, size_t slices, size_t seq_cap) {
+             if (seq_cap == 0) seq_cap = seq;  // k, v: [n_kv][seq_cap][head_dim], the rows past seq dead
+             if ((size_t)q.size() != n_heads * head_dim || (size_t)k.size() != n_kv * seq_cap * head_dim || k.size() != v.size())
                throw Error(ErrorKind::BadInput, "debug_flash_attention: array sizes");
              py::array_t<float> out(n_heads * head_dim), out2(n_heads * head_dim);
-             d.check(crabml_hip_debug_flash_attention(d.raw(), q.data(), k.data(), v.data(), n_heads, n_kv, head_dim, seq, slices,
+             d.check(crabml_hip_debug_flash_attention(d.raw(), q.data(), k.data(), v.data(), n_heads, n_kv, head_dim, seq, seq_cap, slices,
                                                       out.mutable_data(), out2.mutable_data()));
              return py::make_tuple(out, out2);
-           })
+           },
+           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("n_heads"), py::arg("n_kv"), py::arg("head_dim"), py::arg("seq"), py::arg("slices"),
+           py::arg("seq_cap") = 0)
       .def("debug_flash_attention_rows",
            [](HipTensorDevice& d, py::array_t<float, py::array::c_style | py::array::forcecast> q,
               py::array_t<uint16_t, py::array::c_style | py::array::forcecast> k,
@@ -543,6 +546,10 @@ PYBIND11_MODULE(_host, m) {
              const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
              return std::make_tuple(ids, sec, sample_sec);
            })
+      // crabml_hip_llama_debug_poison: what = 1 the cache tail | 2 the step's data scratch | 4 the prompt pass's row buffers
+      .def("debug_poison", [](HipLlamaRunner& r, uint32_t what, uint16_t fill16, uint32_t fill32) {
+        r.device()->check(crabml_hip_llama_debug_poison(r.raw(), what, fill16, fill32));
+      })
       .def("debug_kv", [](HipLlamaRunner& r, size_t layer, bool v, bool f16) {
         std::vector<uint8_t> b = r.debug_kv(layer, v, f16);
         return py::array_t<uint8_t>(b.size(), b.data());

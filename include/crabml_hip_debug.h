@@ -75,13 +75,15 @@ int crabml_hip_debug_read_ceiling(crabml_hip_device_t* dev, size_t bytes, int32_
 
 /* The fast step's long-context attention (k_attn_flash + k_attn_flash_merge, fused_attention.hpp) by itself: one query row per
  * head against `seq` cached positions.  q: n_heads * head_dim f32 (already scaled; rounded to f16 by the kernel as
- * batch_matmul.rs:39 does); k, v: [n_kv][seq][head_dim] f16 bits; slices: the grid's position slices per kv head (1 .. 32; a
+ * batch_matmul.rs:39 does); k, v: [n_kv][seq_cap][head_dim] f16 bits; slices: the grid's position slices per kv head (1 .. 32; a
  * step uses as many as the context repays); out: n_heads * head_dim f32 = softmax(q k^T) v in f32 arithmetic, from the shipped
  * two-launch form.  out2 (nullable): the same from the single-launch form (the last-arriving workgroup of a kv head merges;
  * launched twice on the same ticket words, which the last arriver re-arms).  n_heads / n_kv from 1 to 8 at head_dim 64 / 128,
- * 1 / 2 / 4 / 8 at head_dim 256; anything else: BAD_INPUT.  Host pointers; blocks. */
+ * 1 / 2 / 4 / 8 at head_dim 256; anything else: BAD_INPUT.  seq_cap >= seq: the rows of a kv head in k and v, [n_kv][seq_cap][head_dim],
+ * handed to both kernels as the cache row stride -- positions 0 .. seq - 1 are live, whatever lies beyond must not matter.  Host
+ * pointers; blocks. */
 int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
-                                     size_t n_kv, size_t head_dim, size_t seq, size_t slices, float* out, float* out2);
+                                     size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap, size_t slices, float* out, float* out2);
 
 /* The fast prompt pass's causal attention (k_attn_flash_rows: flash attention on the f16 matrix cores) by itself.  q: rows *
  * n_heads * head_dim f32 (row r is the prompt row at position pos0 + r); k, v: [n_kv][seq_cap][head_dim] f16 bits (the cache
@@ -146,6 +148,31 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
 
 /* parity hook: copies the layer's K or V cache (raw f16/f32 bytes, [n_kv_heads][seq_len][head_dim]) */
 int crabml_hip_llama_debug_kv(crabml_hip_llama_t* ctx, size_t layer, int32_t which_v, void* dst, size_t nbytes);
+
+/* test hook: fills what no launch may consume, on the context's stream (stream-ordered with the steps and passes around it; does
+ * not block).  The invariant it serves: no launch's result depends on cache rows past the live positions or on
+ * scratch bytes it did not write in the same step or pass.  fill16 goes to f16 data and, repeated, to the quantized activation
+ * planes (their scale fields then read as the pattern); fill32 to f32 data.  A buffer is filled as the whole allocation behind it.
+ *   what & 1, the cache tail: rows kv_len .. seq_len - 1 of every layer and kv head, K and V (f16 cache: fill16, f32 cache: fill32).
+ *   what & 2, the step's data scratch -- every buffer a step writes before it reads it:
+ *     fill32: x (k_embed writes it first), partial (unused on one device), qbuf, attn, h, tmp, xn, logits, rsums, scores_g,
+ *             flash_part (the merge reads the active slices' partials only), am_val (all ARGMAX_BLOCKS written by k_argmax_partial),
+ *             out_tokens (read by the host only, the entries of the call's own steps);
+ *     fill16: act_dim, act_attn, act_hid (every plane of a set is written by its producer), p16.
+ *   what & 4, the prompt pass's row buffers, if allocated (otherwise nothing):
+ *     fill32: pf_x, pf_xn, pf_q, pf_k, pf_v, pf_qr, pf_attn, pf_tmp, pf_g, pf_u, pf_split, pf_scores;
+ *     fill16: pf_act_dim, pf_act_hid, pf_xh, pf_xh2 (B': rows past the pass feed output rows nobody reads), pf_p16.
+ * Never written, in any mode:
+ *   state, slots, a8gran, h8gran, flash_tick, pf_ovf, the sampler's histogram, the inboxes of a P2P group: words that kernels poll or
+ *     count on from one launch to the next (epochs, tickets, the fault word, token / pos / step);
+ *   am_best (what a vocabulary-split group combines after the step), am_idx and pf_tokens (indices: the next launch addresses the
+ *     embedding table with them -- a stale one must not become an address), the rope, exp and gelu tables, the weights;
+ *   the sampler's sm_bmax / sm_keys / sm_par / sm_coins: allocated by the first decode_sample, not at create; par and coins are
+ *     uploaded by every call (reuse of a sampling context is held by tests/test_hip_reuse_equals_fresh.py without the hook);
+ *   the tap scratch areas (written and read back inside one hook call).
+ * No buffer of a context carries DATA from one step to the next outside the cache and the words above.
+ * Tensor-parallel ranks and a context on the runner's own KV cache (the recorded-op queue owns those): CRABML_HIP_NOT_IMPLEMENTED. */
+int crabml_hip_llama_debug_poison(crabml_hip_llama_t* ctx, uint32_t what, uint16_t fill16, uint32_t fill32);
 
 /* parity hook: ONE decode step for (token, pos) -- the same checks and the same effect on the context as
  * crabml_hip_llama_forward -- enqueued EAGERLY (never replayed from the step's hipGraph, never while capturing), with the buffers
