@@ -25,6 +25,9 @@ pub const CRABML_HIP_LLAMA_TP_GRAPH: i32 = 8;
 pub const CRABML_HIP_LLAMA_EXACT_ATTENTION: i32 = 4194304;
 /// fast mode: RMSNorm's division stays in the producing launch (no deferred 1 / rms)
 pub const CRABML_HIP_LLAMA_EXACT_NORM: i32 = 8388608;
+/// fast mode, one device: Q5_K matrices of prompt passes of 32 rows or more take the f16 matrix-core GEMM (opt-in kernel variant,
+/// declared in crabml_hip_debug.h: the public header's flag bits are taken)
+pub const CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM: i32 = 536870912;
 /// tensor parallelism: `output_weight` is the rank's vocabulary shard of the classifier (P2P group)
 pub const CRABML_HIP_LLAMA_TP_SPLIT_VOCAB: i32 = 1048576;
 

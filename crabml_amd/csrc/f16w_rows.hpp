@@ -11,8 +11,10 @@ __device__ __forceinline__ int f16w_slot_of_elem(int j) {
   const int hi = j >> 4, s = (j >> 2) & 3, r = j & 3;
   return 8 * s + 4 * hi + ((r >> 1) | ((r & 1) << 1));
 }
-// orders 1 (Q4_K weights) / 2 (Q6_K weights) / 3 (Q2_K and Q3_K weights), Q8_K rows: position (halfs from the row's start) of
+// orders 1 (Q4_K weights) / 2 (Q6_K weights) / 3 (Q2_K, Q3_K and Q5_K weights), Q8_K rows: position (halfs from the row's start) of
 // element E of super-block sb
+// (Q5_K reads order 3 too: its element 64 p + 32 hi + l -- nibble hi of qs[32 p + l] -- is order 3's E with h = p / 2, j = 2 (p & 1) + hi:
+// chunk p & 1, slots 4 hi .., piece 2 (p / 2) + l / 16, which is what lane group g loads in that chunk, gemm_f16w.hip)
 __device__ __forceinline__ int f16w_pos_q8k(int order, int sb, int E) {
   int cc, g, s, hi, k;
   if (order == 3) {  // E = 128 h + 32 j + l (bits 2 j of qs[32 h + l]): piece g = 2 h + l / 16, dword s, chunk j / 2, slots 4 (j & 1) ..

@@ -1636,7 +1636,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   };
   // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_EXACT=1): the fast pass with matmul_vec's own scaling
   static const bool gemm_exact_hook = test_hook_on("CRABML_HIP_GEMM_EXACT");
-  // The fast pass, Q4_0 / Q8_0 weights x Q8_0 rows, Q4_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K x Q8_K, >= 32 rows: the weight-stationary f16 GEMM
+  // The fast pass, Q4_0 / Q8_0 weights x Q8_0 rows, Q4_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K (Q5_K: opt-in) x Q8_K, >= 32 rows: the weight-stationary f16 GEMM
   // (gemm_f16w.hip; block scales folded into f16 operands, f32 accumulation inside the matrix core -- a stated deviation of the fast
   // tier).  The rows' pre-scaled f16 planes are made once per rhs and k-slot order (q / k / v and gate / up share theirs): `xh`
   // remembers what pf_xh currently holds.
@@ -1650,7 +1650,10 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   int* const ovf = c->pf_ovf;
   // the f16 GEMM takes matrix w, whose rows are k elements long (Q8_K rows: whole super-blocks only).  The one predicate: the GEMMs,
   // the kernels that write pf_xh ahead of them and the two one-launch sites all ask here.
+  // (a Q5_K matrix: only in a context created with CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM on one device -- without it Q5_K keeps the row GEMV
+  // in every body, as the launch pins of the K-quant passes state)
   auto takes_f16w = [&](const crabml_hip_buf* w, int k) {
+    if (w->dtype == CRABML_HIP_Q5_K && !((g.flags & CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM) && c->tp == 1)) return false;
     return f16w && gemm_f16w_takes(dev, w, c->qt) && (c->qt != CRABML_HIP_Q8_K || k % 256 == 0);
   };
   XhHolds xh;
@@ -2614,7 +2617,8 @@ static int retain_weights(crabml_hip_llama* c, const crabml_hip_llama_weights_t*
   // gemm_f16w_takes: one reduction over the scale plane, read back -- here once rather than inside the first prompt pass
   if (rc == 0 && !dev->strict_order && f.tp == 1 && (f.qt == CRABML_HIP_Q8_0 || f.qt == CRABML_HIP_Q8_1 || f.qt == CRABML_HIP_Q8_K))
     for (size_t l = 0; l < g.n_layers; l++)
-      for (const crabml_hip_buf* m : {c->wq[l], c->wk[l], c->wv[l], c->wo[l], c->gate[l], c->up[l], c->down[l]}) (void)gemm_f16w_takes(dev, m, f.qt);
+      for (const crabml_hip_buf* m : {c->wq[l], c->wk[l], c->wv[l], c->wo[l], c->gate[l], c->up[l], c->down[l]})
+        if (m->dtype != CRABML_HIP_Q5_K || (g.flags & CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM)) (void)gemm_f16w_takes(dev, m, f.qt);  // (Q5_K: opt-in)
   return rc;
 }
 

@@ -1,5 +1,6 @@
 // gemm_f16w.hip -- the FAST prompt pass's weight GEMM (crabml_hip_llama_prefill on the fast device; Q4_0 / Q8_0 weights x Q8_0 rows,
-// Q4_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K x Q8_K): weight-stationary on the f16 matrix cores.
+// Q4_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K x Q8_K, and -- in a context created with CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM -- Q5_K x Q8_K):
+// weight-stationary on the f16 matrix cores.
 //
 // matmul_vec with a batched rhs is `C[b, m] = W[m, k] . x[b, k]` (matmul_vec.rs:41-76: the (b, k) rhs contract; llama2.rs:111-129).
 // The bit-exact form (gemm_mfma.hip: exact int8 tiles, then the reference's per-block `sumf += (sumi as f32 * d_w) * d_x`) pays
@@ -43,6 +44,16 @@
 //   high bit is ORed in at bit 2 of 0x6400 | low2, the bias -1028 makes it q = low2 - (hbit ? 0 : 4) exactly; A' = q * fl16(d *
 //   (sc - 32)), the 6-bit sc taken out of the record as the reference's aux[] shuffle does: two roundings.
 // ONE B' slot order for both (k_rows_to_f16<3>): a Q2_K-mix layer whose attn_v is Q3_K converts the rows once.
+// Q5_K weights (Q8_K rows; opt-in, see fused.hip takes_f16w): element 64 p + 32 hi + l of a super-block is nibble hi of qs[32 p + l] with
+// bit 2 p + hi of qh[l] on top (buf_q5_k.rs:24-63; qs in FILE order here, not class-major like Q4_K's).  Chunk c of the super-block: lane
+// (i, g) loads the 16-byte piece g & 1 of pair p = 2 (g >> 1) + c (qs + 32 p + 16 (g & 1)) -- the low nibbles of dword s are elements
+// 128 (g >> 1) + 64 c + 16 (g & 1) + 4 s + k, the high ones those + 32: exactly slot order 3, so Q5_K reads the B' of Q2_K / Q3_K (a
+// Q3_K_M / Q3_K_L layer converts its rows once).  The 16 bytes of qh at 16 (g & 1) and the 16-byte header (Q4_K's: d, dmin, pair-major
+// fields) ride ONCE per super-block in the ring slot of its odd chunk, as Q3_K's hmask and record do (asked for with the even slot, as
+// Q4_K asks for its header, the odd slot's fetch of the NEXT super-block would overwrite qh while the odd chunk still reads it).  The qh
+// dword s, shifted right by 4 (g >> 1) + 2 c, has the low-nibble element's fifth bit at bit 0 of every byte and the high-nibble
+// element's at bit 1; it is ORed in at bit 4 of 0x6400 | nibble, bias -1024 makes it q = nibble + 16 hbit (0..31) exactly.  A' = q *
+// fl16(d * sc) - fl16(dmin * m): Q4_K's c_lo / c_hi fma with the pair's four constants made per chunk, three f16 roundings.
 #include <cstdlib>
 #include <type_traits>
 
@@ -60,8 +71,8 @@ typedef h16x2 f16x2;  // (common.hpp; named like f16x8 here)
 // Q8_K rows (Q4_K weights): slot group kb = 4 cc + g of chunk cc = (super-block, half h), step s = class l = 4 h + s of pair g;
 // slot e: k = 0, 2, 1, 3 of sub-block 2 g (e < 4) / 2 g + 1 (e >= 4), element 8 k + l -- unpack_q4_k_f16's order
 // Q6_K weights: chunk cc = (super-block, half), g, step s: element 128 half + 32 (g >> 1) + 16 (g & 1) + 4 s + k (e < 4), + 64 (e >= 4)
-// Q2_K / Q3_K weights: chunk cc = (super-block, c), g = (h, l / 16), step s: element 128 h + 32 (2 c) + 16 (g & 1) + 4 s + k (e < 4), + 32 (e >= 4)
-template <int ORDER>  // 0: Q8_0 / Q8_1 rows (block order); Q8_K rows for 1: Q4_K, 2: Q6_K, 3: Q2_K / Q3_K weights
+// Q2_K / Q3_K / Q5_K weights: chunk cc = (super-block, c), g = (h, l / 16), step s: element 128 h + 32 (2 c) + 16 (g & 1) + 4 s + k (e < 4), + 32 (e >= 4)
+template <int ORDER>  // 0: Q8_0 / Q8_1 rows (block order); Q8_K rows for 1: Q4_K, 2: Q6_K, 3: Q2_K / Q3_K / Q5_K weights
 __global__ __launch_bounds__(256) void k_rows_to_f16(const char* __restrict__ planes, size_t row_stride, size_t off_d, int nb,
                                                      unsigned short* __restrict__ xh, int* __restrict__ ovf) {
   const size_t col = blockIdx.y;
@@ -71,7 +82,10 @@ __global__ __launch_bounds__(256) void k_rows_to_f16(const char* __restrict__ pl
 }
 // planes: `rows` sets of activation planes (act_layout(act_qtype, k)); the slot order is the one the weight format w_dtype reads
 int gemm_f16w_order(uint32_t w_dtype) {
-  return w_dtype == CRABML_HIP_Q4_K ? 1 : w_dtype == CRABML_HIP_Q6_K ? 2 : (w_dtype == CRABML_HIP_Q2_K || w_dtype == CRABML_HIP_Q3_K) ? 3 : 0;
+  return w_dtype == CRABML_HIP_Q4_K ? 1
+         : w_dtype == CRABML_HIP_Q6_K ? 2
+         : (w_dtype == CRABML_HIP_Q2_K || w_dtype == CRABML_HIP_Q3_K || w_dtype == CRABML_HIP_Q5_K) ? 3
+                                                                                                      : 0;
 }
 bool launch_rows_to_f16(hipStream_t st, uint32_t act_qtype, uint32_t w_dtype, const void* planes, size_t rows, size_t k, void* xh, int* ovf) {
   if (!gemm_f16w_covers(w_dtype, act_qtype) || (act_qtype == CRABML_HIP_Q8_K && k % 256 != 0)) return false;
@@ -220,10 +234,28 @@ __device__ __forceinline__ void q3k_f16_consts(i32x4 rec, int g, f16x2& c_lo, f1
   c_hi = f16x2{b, b};
 }
 
-enum { WF_Q4_0 = 0, WF_Q8_0 = 1, WF_Q4_K = 2, WF_Q6_K = 3, WF_Q4_1 = 4, WF_Q2_K = 5, WF_Q3_K = 6 };  // the weight format of a GEMM
+// Q5_K: one dword of the lane's piece of qs and the matching dword of qh, already shifted so that bit 0 of each byte belongs to the low
+// nibbles' sub-block and bit 1 to the high nibbles'; ORed in at bit 4: 1024 + nibble + 16 hbit, -1024 makes it q = 0..31; then Q4_K's fma
+__device__ __forceinline__ unsigned and_or_bit4(unsigned x, unsigned acc) {
+  unsigned r;
+  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(0x00100010u), "v"(acc));
+  return r;
+}
+__device__ __forceinline__ f16x8 unpack_q5_k_f16(unsigned w, unsigned hw, const Q4KF16Consts& cs, unsigned magic) {
+  const f16x2 bias = {(_Float16)-1024.0f, (_Float16)-1024.0f};
+  const unsigned u0 = and_or_bit4(hw << 4, and_or_magic(w, magic)), u1 = and_or_bit4(hw >> 4, and_or_magic(w >> 8, magic));
+  const unsigned u2 = and_or_bit4(hw << 3, and_or_magic(w >> 4, magic)), u3 = and_or_bit4(hw >> 5, and_or_magic(w >> 12, magic));
+  const f16x2 p0 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u0) + bias, cs.c_lo, cs.o_lo);
+  const f16x2 p1 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u1) + bias, cs.c_lo, cs.o_lo);
+  const f16x2 p2 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u2) + bias, cs.c_hi, cs.o_hi);
+  const f16x2 p3 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u3) + bias, cs.c_hi, cs.o_hi);
+  return f16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
+enum { WF_Q4_0 = 0, WF_Q8_0 = 1, WF_Q4_K = 2, WF_Q6_K = 3, WF_Q4_1 = 4, WF_Q2_K = 5, WF_Q3_K = 6, WF_Q5_K = 7 };  // the weight format of a GEMM
 // the forms whose rows are Q8_K: a chunk is half a super-block, so k is whole super-blocks and the k pieces of a split launch start on
 // super-block boundaries
-constexpr bool f16w_wf_superblock(int wf) { return wf == WF_Q4_K || wf == WF_Q6_K || wf == WF_Q2_K || wf == WF_Q3_K; }
+constexpr bool f16w_wf_superblock(int wf) { return wf == WF_Q4_K || wf == WF_Q6_K || wf == WF_Q2_K || wf == WF_Q3_K || wf == WF_Q5_K; }
 
 template <int T_>
 struct GemmF16Geo {
@@ -243,8 +275,8 @@ struct GemmF16Geo {
 // chip idle for a whole serial k loop): row tile rt belongs to the first matrix whose cumulative tile count exceeds it.
 struct F16wMats {
   const i32x4* wq[3];  // the quant plane
-  const char* wd[3];   // the scale plane (f16 per block; Q4_1: (d, m); Q4_K: the 16-byte headers; Q6_K: the qh plane; Q2_K: the scale bytes; Q3_K: hmask)
-  const char* ws2[3];  // Q6_K: the int8 scales (16 per super-block) ...; Q2_K: the (d, dmin) dwords; Q3_K: the 16-byte records
+  const char* wd[3];   // the scale plane (f16 per block; Q4_1: (d, m); Q4_K: the 16-byte headers; Q6_K / Q5_K: the qh plane; Q2_K: the scale bytes; Q3_K: hmask)
+  const char* ws2[3];  // Q6_K: the int8 scales (16 per super-block) ...; Q2_K: the (d, dmin) dwords; Q3_K: the 16-byte records; Q5_K: the 16-byte headers
   const char* ws3[3];  // ... and d (f16 per super-block)
   float* out[3];
   float* out2[3];    // ksplit > 1: k piece s >= 1 writes its partial tiles to out2[j] + (s - 1) pstride (k_addn_f32 adds them)
@@ -311,11 +343,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
   // MFMAs and a workgroup has the SIMD almost to itself): a RING of four register sets, chunk c + 3 requested while chunk c is
   // multiplied; B' (L2-resident) two chunks ahead in two register sets.  All ring indices are compile-time (chunk loop unrolled by 4).
   // (Q2_K / Q3_K: per SUPER-BLOCK, in the ring slot of its odd chunk -- the even chunk reads its neighbour's slot; the even slots stay empty)
-  constexpr int NQ = (WF == WF_Q8_0 || WF == WF_Q6_K || WF == WF_Q3_K) ? 2 : 1;  // 16-byte quant loads per fragment and chunk
+  // (Q5_K: qs per chunk in [2 f]; qh and the header per SUPER-BLOCK in the ring slot of its odd chunk, [2 f + 1] and hq)
+  constexpr int NQ = (WF == WF_Q8_0 || WF == WF_Q6_K || WF == WF_Q3_K || WF == WF_Q5_K) ? 2 : 1;  // 16-byte quant loads per fragment and chunk
   i32x4 aq[4][NQ * F];
   unsigned ad[4][F];   // Q4_0 / Q8_0: the block's scale; Q4_1: d | m << 16
   i32x4 hq[2][F];      // Q4_K: the super-block header of ring slots (0, 1) / (2, 3), fetched with the even slot; Q6_K: the 16 scales
-                       // Q2_K: the half's eight scale bytes ([0], [1]), fetched with the ODD slot; Q3_K: the record, likewise
+                       // Q2_K: the half's eight scale bytes ([0], [1]), fetched with the ODD slot; Q3_K: the record, Q5_K: the header, likewise
   unsigned hd[2][F];   // Q6_K: d; Q2_K: d | dmin << 16
   auto fetch_a = [&](auto Jc, int ch) {
     constexpr int J = decltype(Jc)::value;
@@ -349,6 +382,19 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
             hq[J >> 1][f] = i32x4{sc[0], sc[1], 0, 0};
             hd[J >> 1][f] = __builtin_nontemporal_load((const unsigned*)w6s + blk);
           }
+        }
+      }
+    } else if constexpr (WF == WF_Q5_K) {
+      const int nsb = nb >> 3, sb = cc >> 1, c = cc & 1;
+#pragma unroll
+      for (int f = 0; f < F; f++) {
+        F16W_PTRS(f);
+        const int row = r0 + FSTEP * f + i;
+        const size_t blk = (size_t)(row < m ? row : m - 1) * nsb + sb;
+        aq[J][2 * f] = __builtin_nontemporal_load(wq + blk * 8 + 4 * (g >> 1) + 2 * c + (g & 1));  // piece g & 1 of pair 2 (g >> 1) + c
+        if constexpr ((J & 1) == 1) {  // the super-block of chunks (ch - 1, ch): two chunks of look-ahead, as for Q2_K / Q3_K
+          aq[J][2 * f + 1] = __builtin_nontemporal_load(wh + blk * 2 + (g & 1));  // (wh: the qh plane, 32 bytes per super-block)
+          hq[J >> 1][f] = __builtin_nontemporal_load(w6s + blk);
         }
       }
     } else if constexpr (WF == WF_Q6_K) {
@@ -394,7 +440,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
   // weights times a finite value add exactly 0 (times +-inf or NaN they would make NaN).
   // register sets of B' pieces in flight (one wave per SIMD: the longer look-ahead; the 32-byte-per-lane formats with two fragments:
   // one set -- B' is L2-resident and a chunk of 64 MFMAs per wave is longer than an L2 round trip)
-  constexpr int NBD = (F == 1 && WF == WF_Q4_0) ? 4 : (F == 2 && (WF == WF_Q8_0 || WF == WF_Q6_K)) ? 1 : 2;
+  // (Q5_K with two fragments: qs per chunk AND qh + header per super-block are in flight -- one set, or F = 2, T = 8 does not fit 256 VGPRs)
+  constexpr int NBD = (F == 1 && WF == WF_Q4_0) ? 4 : (F == 2 && (WF == WF_Q8_0 || WF == WF_Q6_K || WF == WF_Q5_K)) ? 1 : 2;
   i32x4 rb[NBD][G::B_LOADS];
   const char* xbase = (const char*)xh + ((size_t)c0 * nb + (size_t)ch_lo * KCH) * 64;  // (uniform)
   const unsigned xstep = 16u * (unsigned)nb * 64u;                                        // 16 columns
@@ -427,7 +474,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
   fetch_a(std::integral_constant<int, 1>{}, 1);
   fetch_a(std::integral_constant<int, 2>{}, 2);
   Q4KF16Consts cs[F];  // Q4_K: the lane's pair's constants of the current super-block (made in the even slot); Q4_1: (d, m); Q6_K: d sc
-                       // Q2_K / Q3_K: the constants of the current CHUNK (Q3_K: c_lo and c_hi only)
+                       // Q2_K / Q3_K / Q5_K: the constants of the current CHUNK (Q3_K: c_lo and c_hi only)
   commit_b(rb[0], 0);
   // chunk c sits in rb[c % NBD] from NBD chunks before it is committed (the fetches come in chunk order: pb advances)
 #pragma unroll
@@ -461,6 +508,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
         cs[f] = q2k_f16_consts((unsigned)hq[J >> 1][f][J & 1], hd[J >> 1][f], g);
       } else if constexpr (WF == WF_Q3_K) {
         q3k_f16_consts<(J & 1)>(hq[J >> 1][f], g, cs[f].c_lo, cs[f].c_hi);
+      } else if constexpr (WF == WF_Q5_K) {
+        cs[f] = q4k_f16_consts(hq[J >> 1][f], 2 * (g >> 1) + (J & 1));  // the chunk's pair
       } else if constexpr (WF == WF_Q4_1) {
         const unsigned dm = ad[J][f];
         cs[f].c_lo = cs[f].c_hi = __builtin_bit_cast(f16x2, (dm & 0xffffu) | (dm << 16));
@@ -495,6 +544,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
           if constexpr (WF == WF_Q3_K)
             a[f] = unpack_q3_k_f16((unsigned)aq[J | 1][2 * f][s] >> (4 * (J & 1)), (unsigned)aq[J | 1][2 * f + 1][s] >> (4 * (g >> 1) + 2 * (J & 1)),
                                    cs[f].c_lo, cs[f].c_hi, magic);
+          if constexpr (WF == WF_Q5_K)
+            a[f] = unpack_q5_k_f16((unsigned)aq[J][2 * f][s], (unsigned)aq[J | 1][2 * f + 1][s] >> (4 * (g >> 1) + 2 * (J & 1)), cs[f], magic);
           if constexpr (WF == WF_Q6_K)
             a[f] = unpack_q6_k_f16((unsigned)aq[J][2 * f][s], (unsigned)aq[J][2 * f + 1][s] >> (2 * (g >> 1)), (J & 1) ? cs[f].o_lo : cs[f].c_lo,
                                    (J & 1) ? cs[f].o_hi : cs[f].c_hi, magic);
@@ -659,7 +710,7 @@ size_t gemm_f16w_xh_bytes(size_t rows, size_t k) { return ((rows + 127) / 128 * 
 // A' range: 1 in *bad when some block's scales can put an |A'| above 65504 (f16: +-inf, and inf times a zero B' slot is NaN) -- the
 // largest quant magnitude of the format times the block's scale, as the kernel rounds it (Q4_K: the largest 6-bit scale and minimum,
 // 63; Q6_K: the super-block's own int8 scales; Q2_K: n c1 - c2 with the largest 4-bit scale and minimum, 15, and n <= 3; Q3_K: q c with
-// |sc - 32| <= 32 and |q| <= 4); a non-finite scale counts as out of range
+// |sc - 32| <= 32 and |q| <= 4; Q5_K: Q4_K's with q <= 31); a non-finite scale counts as out of range
 __global__ __launch_bounds__(256) void k_f16w_range(const char* __restrict__ sc, const signed char* __restrict__ sc6,
                                                     const unsigned short* __restrict__ d6, size_t nblk, int wf, int* __restrict__ bad) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -674,6 +725,10 @@ __global__ __launch_bounds__(256) void k_f16w_range(const char* __restrict__ sc,
     const unsigned h = ((const unsigned*)sc)[4 * i];
     const float c1 = h2f(f2h(63.0f * h2f((unsigned short)(h & 0xffffu)))), c2 = h2f(f2h(63.0f * h2f((unsigned short)(h >> 16))));
     a = 15.0f * fabsf(c1) + fabsf(c2);  // n c1 - c2, n <= 15
+  } else if (wf == WF_Q5_K) {
+    const unsigned h = ((const unsigned*)(sc + nblk * 32))[4 * i];  // (the headers follow qh)
+    const float c1 = h2f(f2h(63.0f * h2f((unsigned short)(h & 0xffffu)))), c2 = h2f(f2h(63.0f * h2f((unsigned short)(h >> 16))));
+    a = 31.0f * fabsf(c1) + fabsf(c2);  // q c1 - c2, q <= 31
   } else if (wf == WF_Q2_K) {
     const unsigned h = ((const unsigned*)(sc + nblk * 16))[i];  // (the (d, dmin) dwords follow the scale bytes)
     const float c1 = h2f(f2h(15.0f * h2f((unsigned short)(h & 0xffffu)))), c2 = h2f(f2h(15.0f * h2f((unsigned short)(h >> 16))));
@@ -696,6 +751,7 @@ static int f16w_wf(uint32_t dt) {
     case CRABML_HIP_Q4_1: return WF_Q4_1;
     case CRABML_HIP_Q2_K: return WF_Q2_K;
     case CRABML_HIP_Q3_K: return WF_Q3_K;
+    case CRABML_HIP_Q5_K: return WF_Q5_K;
     default: return WF_Q4_0;
   }
 }
@@ -730,7 +786,8 @@ bool gemm_f16w_covers(uint32_t w_dtype, uint32_t act_qtype) {
   if (act_qtype == CRABML_HIP_Q8_0) return w_dtype == CRABML_HIP_Q4_0 || w_dtype == CRABML_HIP_Q8_0;
   if (act_qtype == CRABML_HIP_Q8_1) return w_dtype == CRABML_HIP_Q4_1;
   return act_qtype == CRABML_HIP_Q8_K &&
-         (w_dtype == CRABML_HIP_Q4_K || w_dtype == CRABML_HIP_Q6_K || w_dtype == CRABML_HIP_Q2_K || w_dtype == CRABML_HIP_Q3_K);
+         (w_dtype == CRABML_HIP_Q4_K || w_dtype == CRABML_HIP_Q6_K || w_dtype == CRABML_HIP_Q2_K || w_dtype == CRABML_HIP_Q3_K ||
+          w_dtype == CRABML_HIP_Q5_K);
 }
 // wave tile: T column tiles of 16 prompt rows -- 8 (128-row workgroup tiles) from 65 rows up; short passes (a short prompt, the ragged
 // tail of a long one) take 4 / 2: the MFMAs of an empty column tile cost what a full one's do
@@ -815,8 +872,9 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
     const char* wp = (const char*)w[jj]->ptr;
     mats.wq[j] = (const i32x4*)wp;
     mats.wd[j] = wp + w[jj]->wl.off_scale;
-    // (Q6_K: ql | qh | scales | d; Q2_K: qs | scales | (d, dmin); Q3_K: qs | hmask | records, common.hpp)
-    mats.ws2[j] = wp + w[jj]->wl.off_scale + w[jj]->wl.n_blocks * (dt == CRABML_HIP_Q2_K ? 16 : dt == CRABML_HIP_Q3_K ? 32 : 64);
+    // (Q6_K: ql | qh | scales | d; Q2_K: qs | scales | (d, dmin); Q3_K: qs | hmask | records; Q5_K: qs | qh | headers, common.hpp)
+    mats.ws2[j] = wp + w[jj]->wl.off_scale +
+                  w[jj]->wl.n_blocks * (dt == CRABML_HIP_Q2_K ? 16 : (dt == CRABML_HIP_Q3_K || dt == CRABML_HIP_Q5_K) ? 32 : 64);
     mats.ws3[j] = wp + w[jj]->wl.off_scale + w[jj]->wl.n_blocks * 80;
     mats.out[j] = out[jj];
     mats.out2[j] = ws + before;
@@ -870,6 +928,8 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
     ok = launch_f16w_fmt<WF_Q2_K>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
   else if (dt == CRABML_HIP_Q3_K)
     ok = launch_f16w_fmt<WF_Q3_K>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
+  else if (dt == CRABML_HIP_Q5_K)
+    ok = launch_f16w_fmt<WF_Q5_K>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
   else
     ok = launch_f16w_fmt<WF_Q4_0>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
   if (ok && gu) *gu_done = hquant ? 2 : 1;

@@ -63,8 +63,9 @@ struct RepackPlan {
 void launch_repack(hipStream_t st, const void* raw, void* base, size_t blk0, size_t n_blocks, int bb, const RepackPlan& plan);
 void launch_q4k_pack_scales(hipStream_t st, void* hdr_plane, size_t blk0, size_t n_blocks);
 void launch_q4k_class_major(hipStream_t st, void* qs_plane, size_t blk0, size_t n_blocks);
-// gemm_f16w.hip: the fast prompt pass's weight-stationary f16 GEMM (Q4_0 / Q8_0 weights x Q8_0 rows, Q4_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K x Q8_K)
-// and the rows' pre-scaled f16 planes it reads, in the k-slot order of the weight format (gemm_f16w_order: Q4_K and Q6_K have their own, Q2_K and Q3_K share one)
+// gemm_f16w.hip: the fast prompt pass's weight-stationary f16 GEMM (Q4_0 / Q8_0 weights x Q8_0 rows, Q4_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K / Q5_K x Q8_K;
+// the prompt pass sends a Q5_K matrix here only in a context created with CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM)
+// and the rows' pre-scaled f16 planes it reads, in the k-slot order of the weight format (gemm_f16w_order: Q4_K and Q6_K have their own, Q2_K, Q3_K and Q5_K share one)
 struct F16wHQuant {  // gate | up launches: where h goes as Q8_0 / Q8_1 row planes (act_layout) and, optionally, as ffn_down's f16 planes
   char* planes = nullptr;
   size_t stride = 0, off_d = 0, off_aux = 0;

@@ -56,7 +56,7 @@ int crabml_hip_debug_superblock_ints(crabml_hip_device_t* dev, const crabml_hip_
 int crabml_hip_debug_gemm_ints(crabml_hip_device_t* dev, const crabml_hip_buf_t* w, size_t m, size_t k,
                                const crabml_hip_buf_t* x, size_t b, int32_t* dst, float* out);
 /* The fast prompt pass's weight GEMM (k_gemm_f16w, gemm_f16w.hip) by itself.  w: nw = 1..3 weight buffers of one format (Q4_0,
- * Q8_0, Q4_1, Q4_K, Q6_K), m[j] rows of k; x: b >= 16 f32 rows of k.  The rows are quantized to the format's row type (Q8_0 / Q8_1 /
+ * Q8_0, Q4_1, Q4_K, Q6_K, Q2_K, Q3_K, Q5_K), m[j] rows of k; x: b >= 16 f32 rows of k.  The rows are quantized to the format's row type (Q8_0 / Q8_1 /
  * Q8_K) and B' (the pre-scaled f16 rows the GEMM reads) is written by the quantizer itself (rows_path 0) or made from the finished
  * planes by k_rows_to_f16 (1) -- into an allocation of the product's size (gemm_f16w_xh_bytes) whose every 16-bit word holds `junk`
  * before.  force[4] (nullable) = F (1 | 2), T (2 | 4 | 8), ksplit (1 | 2 | 4 | 8), gate | up (0 off, 1 h = silu(g) * u as f32, 2 h
@@ -126,7 +126,17 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
 #define CRABML_HIP_LLAMA_PREFILL_INT8_GEMM 524288 /* A/B: the fast prompt pass keeps the bit-exact int8 matrix-core GEMM (with the fused last
                                                      product) at every pass size, instead of the weight-stationary f16 GEMM that Q4_0 / Q8_0 /
                                                      Q4_1 / Q4_K / Q6_K / Q2_K / Q3_K weights take from 32 rows (gemm_f16w.hip; a stated deviation of the
-                                                     fast tier) */
+                                                     fast tier) -- and Q5_K weights in a context created with
+                                                     CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM, which this flag overrides */
+#define CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM 536870912 /* opt-in kernel variant (NOT bit-identical): fast mode, one device, prompt passes of 32 rows
+                                                      or more run Q5_K matrices on the weight-stationary f16 matrix-core GEMM the other
+                                                      K-quants take by default (gemm_f16w.hip; A' = f16(q f16(d sc) - f16(dmin m)), a stated
+                                                      deviation of the fast tier like Q4_K's) instead of the row-by-row GEMV.
+                                                      Off, a Q5_K matrix runs exactly as it always has (the launch pins of the K-quant passes
+                                                      state that); on a model without Q5_K tensors the flag changes nothing.  Strict-order
+                                                      devices, tensor parallelism, matmul_vec, shorter passes and decode ignore it;
+                                                      CRABML_HIP_LLAMA_PREFILL_INT8_GEMM overrides it.  Declared here because the public
+                                                      header holds its eight flag bits already; tools/generate.py --q5k-gemm sets it */
 #define CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K 268435456 /* test hook: crabml_hip_llama_debug_prefill_tap also serves contexts whose layer
                                                          matrices or classifier are Q2_K / Q3_K (the checker restates their kernels:
                                                          tests/q23k_f16w_ref.py).  Off, the tap refuses such a context with

@@ -6,7 +6,7 @@ logits on the host (C++ Llama2Sampler), the rest by crabml_hip_llama_decode_samp
 The tokenizer stays on the reference's side of the boundary (out of scope here), so the prompt is given as token ids.
 
 usage: generate.py model.gguf [--prompt 1,15043,3186] [--steps 64] [--seq-len N] [--f32-kv] [--strict]
-                   [--temperature 1.0 --topp 0.9 --seed 0]
+                   [--temperature 1.0 --topp 0.9 --seed 0] [--q5k-gemm]
        generate.py --synth tiny-gqa:Q4_K_M   (writes a synthetic file to a temp dir first: a self-contained demo)
        generate.py --synth qwen2.5-7b:Q4_0   (a Qwen2 file: q / k / v biases, NEOX rope)
        generate.py --synth gemma-2b:Q8_0     (a Gemma file: scaled embedding, NEOX rope, GELU, tied classifier)"""
@@ -31,6 +31,8 @@ ap.add_argument("--strict", action="store_true", help="strict-order device: the 
 ap.add_argument("--temperature", type=float, default=0.0, help="0 (default): greedy; the CLI's default is 1.0")
 ap.add_argument("--topp", type=float, default=0.9)
 ap.add_argument("--seed", type=int, default=0, help="seed of the coins (one uniform [0, 1) f32 per token)")
+ap.add_argument("--q5k-gemm", action="store_true", help="CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM: prompt passes of 32 rows or more run Q5_K matrices on "
+                "the f16 matrix-core GEMM instead of the row-by-row GEMV (opt-in; a stated deviation of the fast tier like the other K-quants')")
 a = ap.parse_args()
 
 path = a.gguf
@@ -60,7 +62,7 @@ dev.sync()
 print(f"loaded + uploaded in {time.perf_counter() - t0:.2f} s")
 prompt = [int(t) for t in a.prompt.split(",") if t]
 seq_len = a.seq_len or min(conf.seq_len, len(prompt) + a.steps + 8)
-r = ca.HipLlamaRunner(conf, weights, dev, seq_len, not a.f32_kv)
+r = ca.HipLlamaRunner(conf, weights, dev, seq_len, not a.f32_kv, extra_flags=536870912 if a.q5k_gemm else 0)
 t0 = time.perf_counter()
 logits = r.prefill(prompt)
 t_prefill = time.perf_counter() - t0

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Prompt-processing throughput of the batched prefill (crabml_hip_llama_prefill) against the token loop.
 usage: prefill_bench.py [--model llama3-8b] [--wtype Q4_0] [--n 512] [--chunks 64,128,256,512] [--layers N]
---wtype: a name of synth.TYPE_BY_NAME or a recipe: Q4_K_M, Q3_K_S, Q3_K_M, Q3_K_L, Q2_K_MIX (llama.cpp's "Q2_K" file type), Q2_K_S.
+--wtype: a name of synth.TYPE_BY_NAME or a recipe: Q4_K_M, Q5_K_M, Q3_K_S, Q3_K_M, Q3_K_L, Q2_K_MIX (llama.cpp's "Q2_K" file type), Q2_K_S.
+--flags 536870912 (CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM): the Q5_K matrices of Q5_K, Q5_K_M, Q3_K_M, Q3_K_L on the f16 GEMM (opt-in).
 Prints one line per chunk size: prompt tokens/s (host clock around the blocking call, 2nd of 2 runs) and the int8
 MFMA rate the weight GEMMs reach (2 * m * k ops per prompt row and weight element)."""
 import argparse
@@ -23,7 +24,7 @@ ap.add_argument("--flags", type=int, default=0, help="extra CRABML_HIP_LLAMA_* f
 a = ap.parse_args()
 shape = synth.SHAPES[a.model]
 wt = a.wtype.upper()
-k_m = wt == "Q4_K_M"  # llama.cpp's mix: Q4_K body, attn_v / ffn_down in Q6_K on some layers, Q6_K classifier
+k_m = wt in ("Q4_K_M", "Q5_K_M")  # llama.cpp's mixes: Q4_K / Q5_K body, attn_v / ffn_down in Q6_K on some layers, Q6_K classifier
 q3 = wt[5:] if wt in ("Q3_K_S", "Q3_K_M", "Q3_K_L") else None  # the Q3_K recipes (synth.q3_k_mix_types), named as tools/generate.py --synth names them
 q2 = {"Q2_K_MIX": "K", "Q2_K_S": "S"}.get(wt)  # the Q2_K recipes (synth.q2_k_mix_types; plain Q2_K: every matrix Q2_K)
 model = synth.build_model(shape, synth.TYPE_BY_NAME[wt[:4]] if k_m or q3 or q2 else synth.TYPE_BY_NAME[a.wtype], seed=8, n_layers=a.layers or None,
