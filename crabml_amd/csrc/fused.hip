@@ -327,6 +327,10 @@ hipError_t raise_dyn_lds(const crabml_hip_device* dev, const void* fn, int bytes
   return e;
 }
 
+// k_attn (one workgroup per head): a score row of `row` positions and q, f32, in the dynamic LDS a launch gets without asking
+constexpr size_t K_ATTN_LDS = 64 * 1024;
+constexpr size_t k_attn_lds_bytes(size_t row, size_t hd) { return (row + hd) * sizeof(float); }
+
 int dalloc(crabml_hip_llama* c, size_t bytes, void** out) {
   size_t cap = 0;
   CH_TRY(pool_alloc(c->dev, bytes, out, &cap));
@@ -644,21 +648,24 @@ void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
   if (prof) prof_end(dev, &r[1]);
 }
 
-void enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned short* xd, void* xisum, const PrefetchPlan& pf,
-                       int spare, bool prof, const AttnQ8K* k8 = nullptr) {
+int enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned short* xd, void* xisum, const PrefetchPlan& pf,
+                      int spare, bool prof, const AttnQ8K* k8 = nullptr) {
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
   const int hd = c->hd, seq_cap = (int)c->cfg.seq_len, n_heads = c->n_heads_l, n_kv = c->n_kv_l;
   const int* pos_d = c->state + 1;
   if (c->attn_variant >= 1 && c->plan.attn_flash) {
     launch_attn_flash(c, l, xq, xd, xisum, prof);
-    return;
+    return 0;
   }
   if (c->attn_variant >= 1) {  // (attn_long_ok: the group size is one of these)
     with_const_else<1, 2, 3, 4, 5, 6, 7, 8>(n_heads / n_kv, [&](auto grp) { launch_attn_long<decltype(grp)::value>(c, l, xq, xd, xisum, prof); });
-    return;
+    return 0;
   }
-  const size_t attn_lds = (size_t)(seq_cap + hd) * sizeof(float);
+  // (k_attn's score row spans the cache here: create admits a cache past K_ATTN_LDS only where k_attn_s serves this variant)
+  const size_t attn_lds = k_attn_lds_bytes(seq_cap, hd);
+  if (c->plan.attn_s_rows == 0 && attn_lds > K_ATTN_LDS)
+    CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: decode attention would need a score row of %d positions in LDS", seq_cap);
   const int sbit = dev->strict_order ? 256 : 0;  // strict device: sequential softmax row sums at any length (softmax.rs:43-48)
   crabml_hip_device::ProfRec ar{};
   crabml_hip_device::ProfRec* AR = prof ? &ar : nullptr;
@@ -671,9 +678,10 @@ void enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
     with_const_else<0, 1>(c->cfg.use_f16_kv_cache != 0, [&](auto kv16) {
       launch_k(st, AR, k_attn<decltype(kv16)::value != 0>, dim3(n_heads + spare), dim3(256), attn_lds, (const float*)c->qbuf, (const void*)c->kc[l],
                (const void*)c->vc[l], pos_d, (const unsigned short*)dev->exp_table, c->attn, xq, xd, xisum, n_heads, n_kv, hd,
-               seq_cap, pf, (c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr);
+               seq_cap, seq_cap, pf, (c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr);
     });
   if (prof) prof_end(dev, &ar);
+  return 0;
 }
 
 // the tail of the final segment: classifier GEMV over this rank's rows (all of them unless the vocabulary is split,
@@ -959,7 +967,7 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     // attention (llama2.rs:571-590) -> attn (f32) [+ Q8_0 planes for wo]; spare CUs prefetch wo
     const bool attn_quant = (hd % 32) == 0;
     const int attn_spare = do_pf && dev->n_cu > n_heads_l ? dev->n_cu - n_heads_l : 0;
-    enqueue_attention(c, l, attn_quant ? aa.q : (signed char*)nullptr, aa.d, aa.isum, plan(c->wo[l], nullptr, nullptr), attn_spare, prof);
+    CH_TRY(enqueue_attention(c, l, attn_quant ? aa.q : (signed char*)nullptr, aa.d, aa.isum, plan(c->wo[l], nullptr, nullptr), attn_spare, prof));
     if (!attn_quant) launch_quantize_act(st, qt, c->attn, (size_t)dim_l, c->act_attn);
     CH_TRY(TAP(tl, CRABML_HIP_TAP_ATTN, c->attn, (size_t)dim_l * 4));
     CH_TRY(TAP(tl, CRABML_HIP_TAP_ACT_ATTN, c->act_attn, act_layout(qt, (size_t)dim_l).total));
@@ -1055,7 +1063,7 @@ int enqueue_segment_generic(crabml_hip_llama* c, int seg) {
     with_qkv_epi(c, decode_qkv_epi(c, l), l, [&](auto ep) {
       k_qkv_epi<QkvArchOf<decltype(ep)>::value><<<(total_rows / 2 + 255) / 256, 256, 0, st>>>(c->tmp, ep);
     });
-    enqueue_attention(c, l, nullptr, nullptr, nullptr, PrefetchPlan{}, 0, prof);
+    CH_TRY(enqueue_attention(c, l, nullptr, nullptr, nullptr, PrefetchPlan{}, 0, prof));
     const void* aact = quant(c->attn, dim_l, c->qt, c->act_attn);
     if (strict && !tp) {  // the residual inside the GEMV's own store: x = matmul_out + x (llama2.rs:266)
       CH_TRY(launch_gemv_strict(dev, c->wo[l], dim, dim_l, aact, 1, c->x, c->x));
@@ -1243,12 +1251,12 @@ int enqueue_segment_k(crabml_hip_llama* c, int seg) {
         const ActLayout ala = act_layout(QT, (size_t)dim_l);
         const AttnQ8K k8{Q8KExchange{c->a8gran, c->state + 4, c->state + 5, n_segments(c), seg}, (float*)(c->act_attn + ala.off_d),
                          (short*)(c->act_attn + ala.off_aux), (signed char*)(c->act_attn + ala.off_p)};
-        enqueue_attention(c, l, (signed char*)c->act_attn, nullptr, nullptr, PrefetchPlan{}, 0, prof, &k8);
+        CH_TRY(enqueue_attention(c, l, (signed char*)c->act_attn, nullptr, nullptr, PrefetchPlan{}, 0, prof, &k8));
       } else {
-        enqueue_attention(c, l, nullptr, nullptr, nullptr, PrefetchPlan{}, 0, prof);
+        CH_TRY(enqueue_attention(c, l, nullptr, nullptr, nullptr, PrefetchPlan{}, 0, prof));
       }
     } else {
-      enqueue_attention(c, l, nullptr, nullptr, nullptr, PrefetchPlan{}, 0, prof);
+      CH_TRY(enqueue_attention(c, l, nullptr, nullptr, nullptr, PrefetchPlan{}, 0, prof));
     }
     if (!qin) launch_quantize_act(st, QT, c->attn, (size_t)dim_l, c->act_attn);
     CH_TRY(TAP(tl, CRABML_HIP_TAP_ATTN, c->attn, (size_t)dim_l * 4));
@@ -1498,6 +1506,13 @@ int prefill_alloc(crabml_hip_llama* c, size_t cap) {
 }
 
 
+// The prompt pass's exact kernels (k_attn_tile, the long-rows kernels) exist for these GQA groups, and NO_TILE_ATTENTION switches both
+// off.  The launch sites dispatch through this list and create's long_cache_refusal asks it: one list, one flag test.
+template <class F>
+bool with_exact_rows_group(int grp, F&& f) { return with_const<1, 2, 4, 8>(grp, f); }
+bool exact_rows_group(int grp) { return with_exact_rows_group(grp, [](auto) {}); }
+bool exact_rows_on(const crabml_hip_llama_config_t& g) { return !(g.flags & CRABML_HIP_LLAMA_NO_TILE_ATTENTION); }
+
 // the row-tiled causal attention of a prefill pass; false = not covered (the caller launches k_attn per (head, row))
 template <bool KV16, int G, int R>
 bool launch_attn_tile_t(crabml_hip_llama* c, int l, int B, int pos0) {
@@ -1513,11 +1528,11 @@ bool launch_attn_tile_t(crabml_hip_llama* c, int l, int B, int pos0) {
 bool launch_attn_tile(crabml_hip_llama* c, int l, int B, int pos0) {
   const int hd = c->hd, g = c->n_heads_l / c->n_kv_l;
   const bool kv16 = c->cfg.use_f16_kv_cache != 0;
-  if (c->cfg.flags & CRABML_HIP_LLAMA_NO_TILE_ATTENTION) return false;
+  if (!exact_rows_on(c->cfg)) return false;
   if (pos0 + B > 1024 || hd > (kv16 ? 256 : 128) || hd % (kv16 ? 16 : 4) != 0 || c->n_heads_l % c->n_kv_l != 0) return false;
   bool ok = false;  // (other group sizes: not covered)
   with_const_else<0, 1>(kv16, [&](auto kv) {
-    with_const<1, 2, 4, 8>(g, [&](auto grp) {
+    with_exact_rows_group(g, [&](auto grp) {
       constexpr int G = decltype(grp)::value;
       ok = launch_attn_tile_t<decltype(kv)::value != 0, G, (G == 8 ? 2 : 4)>(c, l, B, pos0);  // rows per workgroup: G = 8 fills the lanes with two
     });
@@ -1558,9 +1573,9 @@ int launch_attn_long_rows_t(crabml_hip_llama* c, int l, int B) {
 }
 // 1 = launched, 0 = not covered, < 0 = error
 int launch_attn_long_rows(crabml_hip_llama* c, int l, int B) {
-  if (!c->plan.exact_long_ok || (c->cfg.flags & CRABML_HIP_LLAMA_NO_TILE_ATTENTION)) return 0;
+  if (!c->plan.exact_long_ok || !exact_rows_on(c->cfg)) return 0;
   int rc = 0;
-  if (!with_const<1, 2, 4, 8>(c->n_heads_l / c->n_kv_l, [&](auto grp) { rc = launch_attn_long_rows_t<decltype(grp)::value>(c, l, B); })) return 0;
+  if (!with_exact_rows_group(c->n_heads_l / c->n_kv_l, [&](auto grp) { rc = launch_attn_long_rows_t<decltype(grp)::value>(c, l, B); })) return 0;
   return rc == 0 ? 1 : -1;
 }
 
@@ -1584,12 +1599,19 @@ int launch_prefill_attention(crabml_hip_llama* c, int l, size_t B, size_t pos0) 
   if (launch_attn_tile(c, l, (int)B, (int)pos0)) return 2;
   const int along = launch_attn_long_rows(c, l, (int)B);  // past 1024 positions: the long-context kernels, rows in grid.y
   if (along != 0) return along < 0 ? -1 : 3;
-  // unusual shapes (f32 cache past 1024 positions, odd group sizes): one workgroup per (head, row)
-  const size_t attn_lds = (size_t)(seq_cap + hd) * sizeof(float);
+  // unusual shapes (f32 cache past 1024 positions, odd group sizes): one workgroup per (head, row), its score row sized by the positions
+  // the pass's last row sees (rounded as k_attn_tile's sstride, never past the cache), not by the cache
+  const int row_cap = std::min((int)((pos0 + B + 3) & ~(size_t)3), seq_cap);
+  const size_t attn_lds = k_attn_lds_bytes(row_cap, hd);
+  if (attn_lds > K_ATTN_LDS) {
+    (void)set_error(dev, CRABML_HIP_UNEXPECTED, "llama prefill: no attention kernel of this context takes a pass that sees %zu positions",
+                    pos0 + B);
+    return -1;
+  }
   with_const_else<0, 1>(kv16, [&](auto kv) {
     k_attn<decltype(kv)::value != 0><<<dim3(n_heads, (unsigned)B), 256, attn_lds, st>>>(c->pf_qr, c->kc[l], c->vc[l], pos_d,
                                                                                         (const unsigned short*)dev->exp_table, c->pf_attn, nullptr, nullptr,
-                                                                                        nullptr, n_heads, n_kv, hd, seq_cap, PrefetchPlan{},
+                                                                                        nullptr, n_heads, n_kv, hd, seq_cap, row_cap, PrefetchPlan{},
                                                                                         dev->strict_order ? 256 : 0);
   });
   return 4;
@@ -2267,8 +2289,6 @@ static int validate_config(crabml_hip_device_t* dev, const crabml_hip_llama_conf
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: needs dim, local dims % 32 == 0, even head_dim <= 256, even rope_dim");
   if (g.embedding_dim > 12288)  // k_norm_quant keeps the row in 64 KiB of LDS
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: embedding_dim %zu > 12288", g.embedding_dim);
-  if ((g.seq_len + hd) * sizeof(float) > 64 * 1024)
-    CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: seq_len %zu needs more than 64 KiB of LDS for the score row", g.seq_len);
   if (!w->token_embed || !w->rms_final_weight || !w->wq || !w->wk || !w->wv || !w->wo || !w->ffn_gate_weight ||
       !w->ffn_down_weight || !w->ffn_up_weight || !w->rms_att_weight || !w->rms_ffn_weight)
     CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: missing weights");
@@ -2378,6 +2398,9 @@ static bool lds_fits(const crabml_hip_device* dev, const void* fn, size_t bytes,
   return ok;
 }
 
+// a cache whose positions k_attn's score row (one workgroup per head, the whole row and q in LDS) cannot span
+static bool past_k_attn_row(size_t seq, size_t hd) { return k_attn_lds_bytes(seq, hd) > K_ATTN_LDS; }
+
 // The attention forms of a plan.  Each kernel's limit is asked for where the plan first needs that kernel, in this order: the exact
 // softmax, k_attn_pv_split, k_attn_flash, its ticket form, k_attn_flash_rows, k_attn_s -- a refusal turns that form off, nothing else.
 static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llama_config_t& g, const ModelFacts& f, const FlashHooks& hooks,
@@ -2388,10 +2411,12 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
   const bool kv16 = g.use_f16_kv_cache != 0, q81 = f.qt == CRABML_HIP_Q8_1;
   // One predicate per use.  The decode step's kernels (k_attn_flash; k_attn_scores / k_attn_softmax / k_attn_pv) serve every group up to 8;
   // the prompt pass's (k_attn_flash_rows here, the tile and long-rows kernels through their own lists) serve 1, 2, 4 and 8 only -- any
-  // other group keeps its prompt on the per-(head, row) kernel.
+  // other group keeps its prompt on the per-(head, row) kernel.  That kernel's score row ends at 64 KiB, so in a cache past
+  // past_k_attn_row() k_attn_flash_rows (group-agnostic: kv head = head / (n_heads / n_kv)) takes groups 3, 5, 6 and 7 as well; under
+  // that bound they stay where the launch pins hold them.
   const bool long_cache = kv16 && hd % 32 == 0 && !has(CRABML_HIP_LLAMA_NO_LONG_ATTENTION);
   const bool long_geom = long_cache && grp >= 1 && grp <= 8;
-  const bool rows_geom = long_cache && (grp == 1 || grp == 2 || grp == 4 || grp == 8);
+  const bool rows_geom = past_k_attn_row(seq, f.hd) ? long_geom : long_cache && exact_rows_group(grp);
   // the exact kernels: the softmax kernels keep a head's score row in LDS -- rows past 16384 positions need the raised limit, rows
   // past ~38000 do not fit at all (the step then stays on the one-workgroup-per-head kernel)
   p->exact_long_ok = long_geom && seq % 8 == 0 && lds_fits(dev, (const void*)k_attn_softmax<16>, seq * 4, LDS_CAP, 64 * 1024) &&
@@ -2435,6 +2460,33 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
       p->attn_s_lds = lds;
     }
   }
+}
+
+// The longest cache a context is created with: the context length of the Qwen2.5 / Mistral / Llama-3.1 files this is for, inside the
+// 38400 positions (LDS_CAP) of the exact softmax kernels.  tests/test_hip_fused.py::test_fused_errors holds a fast f16 context of
+// 65536 positions to a refusal: going further has to touch that test.
+constexpr size_t MAX_SEQ_LEN = 32768;
+
+// Why a plan cannot serve its cache (nullptr: it can).  Up to the 64 KiB score row of k_attn every plan can: that kernel is what
+// every other form falls back to.  Past it a context exists only if no launch its plan can choose is k_attn with a cache-sized row:
+// the decode step goes k_attn_s -> the long-context kernels, the prompt pass goes k_attn_flash_rows (short passes: the tile kernel, or
+// k_attn with a pass-sized row) or the exact tile / long-rows kernels.  The kernels' own limits are decide_attention's; this reads its words.
+// plan == nullptr: the clauses the configuration alone settles, asked before decide_step -- which raises kernels' LDS limits -- runs
+// for a context that cannot exist.
+static const char* long_cache_refusal(const crabml_hip_llama_config_t& g, const ModelFacts& f, const StepPlan* plan) {
+  if (!past_k_attn_row(g.seq_len, f.hd)) return nullptr;
+  if (g.seq_len > MAX_SEQ_LEN) return "more positions than the limit";
+  if (f.tp > 1) return "tensor-parallel ranks keep the one-workgroup-per-head attention within reach";
+  if (!g.use_f16_kv_cache) return "an f32 kv cache has no long-context attention kernels";
+  if (!plan) return nullptr;
+  const StepPlan& p = *plan;
+  if (!p.attn_long_ok) return "the decode step has no long-context attention (flags, head_dim, a group above 8, seq_len % 8 on the exact kernels)";
+  if (p.attn_long_from >= g.seq_len) return "attn_long_from leaves the whole cache to the short-context attention";
+  if (p.attn_s_rows <= 0) return "the decode step's short-context attention would need the whole score row in LDS (k_attn_s is off or does not fit)";
+  const bool exact_rows = p.exact_long_ok && exact_rows_group((int)(f.n_heads_l / f.n_kv_l)) && exact_rows_on(g);
+  if (!p.attn_flash_rows && !exact_rows)
+    return "the prompt pass has no attention kernel for this cache (exact kernels: groups 1, 2, 4, 8, seq_len % 8 == 0, tile attention on)";
+  return nullptr;
 }
 
 // What a context runs (StepPlan), from values: the configuration, the device's mode and size, and what validation found.  The one
@@ -2755,7 +2807,13 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   CH_TRY(validate_config(dev, *cfg, w, arch, &f));
   CH_TRY(validate_weights(dev, *cfg, w, &f));
   if (!dev->dry) CH_USE(dev);
+  const auto refuse = [&](const char* why) {
+    return set_error(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: seq_len %zu is past the %zu positions of a one-workgroup score row (limit %zu): %s",
+                     cfg->seq_len, (size_t)(K_ATTN_LDS / 4 - f.hd), MAX_SEQ_LEN, why);
+  };
+  if (const char* why = long_cache_refusal(*cfg, f, nullptr)) return refuse(why);
   const StepPlan plan = decide_step(dev, *cfg, f, read_flash_hooks());
+  if (const char* why = long_cache_refusal(*cfg, f, &plan)) return refuse(why);
   crabml_hip_llama* c = nullptr;
   CH_TRY(new_context(dev, *cfg, f, plan, ext_kc != nullptr, &c));
   int rc = retain_weights(c, w, arch, f);

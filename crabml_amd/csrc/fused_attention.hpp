@@ -71,7 +71,9 @@ __global__ __launch_bounds__(256) void k_attn(const float* __restrict__ q, const
                                               const unsigned short* __restrict__ exp_tab, float* __restrict__ out,
                                               signed char* __restrict__ xq, unsigned short* __restrict__ xd,
                                               void* __restrict__ xisum, int n_heads, int n_kv, int hd, int seq_cap,
-                                              PrefetchPlan pf, int q81_in, long long* __restrict__ stamps = nullptr) {
+                                              int row_cap, PrefetchPlan pf, int q81_in, long long* __restrict__ stamps = nullptr) {
+  // seq_cap: the cache's stride in positions.  row_cap: floats of the score row in LDS (q follows it) -- at least the positions the launch's
+  // last row sees; the size of the row enters no arithmetic.
   // q81_in: bits 0-7 = the output quantizer (0 Q8_0, 1 Q8_1), bit 8 = sequential softmax row sum at any length (strict device)
   const int q81 = q81_in & 255;
   const bool strict_sum = (q81_in & 256) != 0;
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(256) void k_attn(const float* __restrict__ q, const
   __shared__ float s_red[4];
   __shared__ float s_val;
   float* scores = lds;
-  float* qs = lds + seq_cap;
+  float* qs = lds + row_cap;
   const int tid = threadIdx.x;
   const int head = blockIdx.x;
   const int kvh = KV16 ? head / (n_heads / n_kv) : head % n_kv;

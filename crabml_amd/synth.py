@@ -163,7 +163,7 @@ SHAPES = {
     "tiny-gqa": ModelShape("tiny-gqa", 512, 1024, 2, 8, 2, 1024, 64, 1e-5, None),
     # ... and one with Llama-3's head_dim of 128 (the kernels specialized for it: k_attn_s<128>, k_attn_wo)
     "tiny-hd128": ModelShape("tiny-hd128", 512, 1024, 2, 4, 2, 1024, 128, 1e-5, None),
-    # Qwen2 (seq_len: under the decode step's create-time cap, not the files' context_length of 32768)
+    # Qwen2 (seq_len: the benchmarks' cache, not the files' context_length of 32768 -- which the decode step serves: tools/long_context_bench.py)
     "qwen2.5-7b": ModelShape("Qwen2.5-7B", 3584, 18944, 28, 28, 4, 152064, 8192, 1e-6, None, "qwen2"),
     "qwen2.5-3b": ModelShape("Qwen2.5-3B", 2048, 11008, 36, 16, 2, 151936, 8192, 1e-6, None, "qwen2", True),
     # GQA groups 3, 6 and 5 (tools/qwen2_bench.py; only the group and head_dim of 128 matter there)

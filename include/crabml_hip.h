@@ -198,6 +198,14 @@ int crabml_hip_batch_matmul(crabml_hip_device_t* dev, const crabml_hip_buf_t* a,
  * row sums past 1024 positions) are summed wave-parallel, exactly like crabml_hip_matmul_vec.  With
  * CRABML_HIP_FLAG_STRICT_ORDER every sum runs in the reference's scalar order and the step is bit-identical
  * to the reference at every context length.
+ * Context length: the one-workgroup attention kernel keeps a head's score row and q in 64 KiB of LDS, (seq_len + head_dim) * 4
+ * bytes -- every configuration is created up to that (16256 positions at head_dim 128, 16320 at 64).  Longer caches, up to 32768
+ * positions (the context_length of the Qwen2.5 / Mistral / Llama-3.1 files), are created where no launch falls back to that
+ * kernel: one device (tp_size <= 1), f16 KV cache, the staged short-context kernel up to attn_long_from < seq_len and the
+ * long-context kernels from there (GQA groups 1 to 8), and a prompt pass on the fast step's flash kernel (head_dim 64 / 128, every
+ * group 1 to 8) or on the exact tile / long-row kernels (strict-order device, EXACT_ATTENTION, head_dim 256: groups 1 / 2 / 4 / 8,
+ * seq_len % 8 == 0).  Everything else past the 64 KiB row -- an f32 cache, tensor-parallel ranks, the A/B flags that switch those
+ * kernels off, more than 32768 positions -- is CRABML_HIP_NOT_IMPLEMENTED, and the message names the reason.
  * Weights: layer matrices in any matmul_vec format (Q4_0, Q8_0, Q4_1, Q2_K, Q3_K, Q4_K, Q5_K and Q6_K run fused kernels, Q4_K and Q5_K also
  * with attn_v / ffn_down in Q6_K -- llama.cpp's *_K_M mixes --, Q3_K also with attn_v / attn_output / ffn_down in Q4_K or Q5_K --
  * its Q3_K_S / _M / _L recipes --, Q2_K also with those three tensors in Q3_K or Q4_K -- its Q2_K / Q2_K_S recipes; Q2_K, Q3_K, Q5_K
@@ -233,7 +241,9 @@ typedef struct crabml_hip_llama crabml_hip_llama_t;
                                           (an element-wise max over the ranks' buffers is the all-gather) */
 typedef struct crabml_hip_llama_config { /* crabml-llama2/src/model.rs:30-53 */
   size_t embedding_dim, hidden_dim, n_layers, n_heads, n_kv_heads, vocab_size;
-  size_t seq_len;  /* KV cache capacity (Llama2Runner::new seq_len, llama2.rs:46-86) */
+  size_t seq_len;  /* KV cache capacity (Llama2Runner::new seq_len, llama2.rs:46-86).  Any context with (seq_len + head_dim) * 4
+                    * <= 64 KiB (16256 positions at head_dim 128); past that up to 32768 positions where the long-context kernels
+                    * serve the whole cache (the fused-step block above), else CRABML_HIP_NOT_IMPLEMENTED */
   size_t rope_dim; /* conf.rope_dim.unwrap_or(head_dim) */
   float rms_norm_eps;
   int32_t use_f16_kv_cache;
@@ -246,7 +256,7 @@ typedef struct crabml_hip_llama_config { /* crabml-llama2/src/model.rs:30-53 */
   void* tp_comm; /* crabml_hip_tp_comm_t*; NULL with tp_size > 1 = a rank of the single-device simulation */
   size_t attn_long_from; /* cached positions from which attention runs as the multi-workgroup kernels (0 = default: 96 for the
                           * fast step's split-KV kernels, 224 for the exact ones; GQA groups 1 to 8, a larger group keeps one
-                          * workgroup per head) */
+                          * workgroup per head).  Must be < seq_len where seq_len is past the 64 KiB score row (above) */
   size_t prefill_chunk;  /* rows per batched prefill pass (0 = default: 1024, 512 on a strict-order device; never more than seq_len) */
 } crabml_hip_llama_config_t;
 typedef struct crabml_hip_llama_weights { /* crabml-llama2/src/model.rs:55-84; per-layer arrays of n_layers */

@@ -84,7 +84,7 @@ int main() {
     for (int it = 0; it < 9; it++) {
       const int l = it % L;
       k_attn<true, true><<<dim3(n_heads), 256, lds, st>>>(q, kc + l * kvb, vc + l * kvb, pos_d, d_tab, out, xq, xd, (void*)xs, n_heads, n_kv, hd,
-                                                          seq_cap, PrefetchPlan{}, 0, stamps);
+                                                          seq_cap, seq_cap, PrefetchPlan{}, 0, stamps);
       CK(hipStreamSynchronize(st));
       std::vector<long long> s(6);
       CK(hipMemcpy(s.data(), stamps, 48, hipMemcpyDeviceToHost));
@@ -145,7 +145,7 @@ int main() {
             pf.sink = sink;
           }
           k_attn<true, false><<<dim3(n_heads + spare), 256, lds, st>>>(q, kc + l * kvb, vc + l * kvb, pos_d, d_tab, out, xq, xd, (void*)xs, n_heads, n_kv,
-                                                                       hd, seq_cap, pf, 0, nullptr);
+                                                                       hd, seq_cap, seq_cap, pf, 0, nullptr);
         }
         CK(hipEventRecord(e1, st));
         CK(hipEventSynchronize(e1));
