@@ -796,7 +796,11 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
   const int n_heads_l = c->n_heads_l;
   const bool tp = c->tp > 1;
   const int L = (int)g.n_layers;
-  constexpr bool Q81 = FMT == CRABML_HIP_Q4_1;
+  constexpr bool Q81 = rhs_is_q8_1<FMT>;
+  // Q5_0 / Q5_1 layers come here on one device only (decide_step): none of the tensor-parallel forms -- k_gateup_h, the f32-rhs
+  // prologue, the in-launch collective -- is built for them
+  constexpr bool ONE_DEVICE = !has_tp_forms<FMT>;
+  if (ONE_DEVICE && c->tp > 1) CH_BAIL(c->dev, CRABML_HIP_UNEXPECTED, "llama: a tensor-parallel rank of a format without tensor-parallel launch forms on the fused segments (decide_step sends it to the per-op segments)");
   const uint32_t qt = c->qt;
   ActPtrs ad = act_ptrs(c->act_dim, dim, qt), aa = act_ptrs(c->act_attn, dim_l, qt), ah = act_ptrs(c->act_hid, hidden_l, qt);
   // measurement hook: only meaningful for eager launches (events cannot live inside the captured graph)
@@ -863,15 +867,15 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
           });
         });
       };
-      if (xin != nullptr && !Q81) {  // (tensor-parallel ranks) the rhs arrives as f32 -- h from k_gateup_h -- and is quantized in the prologue
-        if constexpr (!Q81) {
+      if (xin != nullptr && !Q81 && !ONE_DEVICE) {  // (tensor-parallel ranks) the rhs arrives as f32 -- h from k_gateup_h -- and is quantized in the prologue
+        if constexpr (!Q81 && !ONE_DEVICE) {
           if (tpv.n > 1)
             nq(NqForm<1, true>{}, q8_0_lds_bytes(k / 32), xin, tpv);
           else
             nq(NqForm<1>{}, q8_0_lds_bytes(k / 32), xin, NoTp{});
         }
-      } else if (tpv.n > 1) {  // tensor parallel over a P2P group: the collective runs inside this launch
-        nq(NqForm<0, true>{}, 0, nullptr, tpv);
+      } else if (tpv.n > 1 && !ONE_DEVICE) {  // tensor parallel over a P2P group: the collective runs inside this launch
+        if constexpr (!ONE_DEVICE) nq(NqForm<0, true>{}, 0, nullptr, tpv);
       } else if (c->plan.ordered) {  // strict order: the same launch with block-ordered GEMV sums and the reference's norm order
         // tuning hook: 0 = never, 1 = ffn_down only, 2 = wo too (-1 / unset: the default below)
         static const int pipe_mode = test_hook_int("CRABML_HIP_ORD_PIPE", -1);
@@ -891,8 +895,9 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
       }
     } else if (c->plan.ordered) {
       launch_k(st, R, k_gemv_res_ord<FMT>, dim3((dim + 7) / 8), dim3(256), ord_terms_lds_bytes(k / 32), planes_of(w), act_view<FMT>(a), c->x, dim, k / 32);
-    } else if (tp) {
-      launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), act_view<FMT>(a), dst, dim, k / 32);
+    } else if (tp && !ONE_DEVICE) {
+      if constexpr (!ONE_DEVICE)
+        launch_k(st, R, k_gemv_res<FMT, 1, false>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), act_view<FMT>(a), dst, dim, k / 32);
     } else {
       launch_k(st, R, k_gemv_res<FMT, 1, true>, dim3((dim + 1) / 2), dim3(128), 0, planes_of(w), act_view<FMT>(a), dst, dim, k / 32);
     }
@@ -984,9 +989,9 @@ int enqueue_segment_t(crabml_hip_llama* c, int seg) {
     // gate / up + silu * mul (llama2.rs:620-630), local rows
     CH_TRY(P0(&pr, 3, 2.0 * hidden_l, dim));
     const RmsTail rt{c->rsums, dim / 32, 1.0f / (float)dim, 1e-5f};  // eps: the literal 1e-5 (llama2.rs:611)
-    const bool hq = c->plan.gu_rows > 0 && !c->plan.ordered && norm_epi && !Q81 && !defer_wo;
+    const bool hq = c->plan.gu_rows > 0 && !c->plan.ordered && norm_epi && !Q81 && !ONE_DEVICE && !defer_wo;
     if (hq) {
-      if constexpr (!Q81)
+      if constexpr (!Q81 && !ONE_DEVICE)
         launch_k(st, R, k_gateup_h<FMT>, dim3(hidden_l / c->plan.gu_rows), dim3(c->plan.gu_rows / 2 * 64), 0, planes_of(c->gate[l]), planes_of(c->up[l]),
                  act_view<FMT>(ad), c->ffn_act, c->h, hidden_l, dim / 32);
     } else if (c->plan.ordered)
@@ -1314,11 +1319,13 @@ int enqueue_segment(crabml_hip_llama* c, int seg) {
     {
       int rc = 0;
       if (with_fmt(KBodies{}, (int)c->wtype, [&](auto body) { rc = enqueue_segment_k<decltype(body)::value>(c, seg); })) return rc;
-      return enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
+      return c->wtype == CRABML_HIP_Q5_1 ? enqueue_segment_k<CRABML_HIP_Q5_1>(c, seg) : enqueue_segment_k<CRABML_HIP_Q4_1>(c, seg);
     }
     case SegPath::Fused5:
       return c->wtype == CRABML_HIP_Q4_0   ? enqueue_segment_t<CRABML_HIP_Q4_0>(c, seg)
              : c->wtype == CRABML_HIP_Q8_0 ? enqueue_segment_t<CRABML_HIP_Q8_0>(c, seg)
+             : c->wtype == CRABML_HIP_Q5_0 ? enqueue_segment_t<CRABML_HIP_Q5_0>(c, seg)
+             : c->wtype == CRABML_HIP_Q5_1 ? enqueue_segment_t<CRABML_HIP_Q5_1>(c, seg)
                                            : enqueue_segment_t<CRABML_HIP_Q4_1>(c, seg);
     case SegPath::PerOp:
       break;
@@ -1658,7 +1665,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   };
   // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_GEMM_EXACT=1): the fast pass with matmul_vec's own scaling
   static const bool gemm_exact_hook = test_hook_on("CRABML_HIP_GEMM_EXACT");
-  // The fast pass, Q4_0 / Q8_0 weights x Q8_0 rows, Q4_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K (Q5_K: opt-in) x Q8_K, >= 32 rows: the weight-stationary f16 GEMM
+  // The fast pass, Q4_0 / Q8_0 / Q5_0 weights x Q8_0 rows, Q4_1 / Q5_1 x Q8_1, Q4_K / Q6_K / Q2_K / Q3_K (Q5_K: opt-in) x Q8_K, >= 32 rows: the weight-stationary f16 GEMM
   // (gemm_f16w.hip; block scales folded into f16 operands, f32 accumulation inside the matrix core -- a stated deviation of the fast
   // tier).  The rows' pre-scaled f16 planes are made once per rhs and k-slot order (q / k / v and gate / up share theirs): `xh`
   // remembers what pf_xh currently holds.
@@ -2331,8 +2338,11 @@ static int validate_weights(crabml_hip_device_t* dev, const crabml_hip_llama_con
     if (dim % be || dim_l % be || hidden_l % be || dim % obe)
       CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama: dim / local dims are not multiples of the %zu-element blocks of dtype %u", be, wt);
   }
+  // (a Q5_0 tensor: BlockFmt<Q5_0>::load finds the d plane (qh plane - qs plane) / 4 bytes behind the qh plane, which holds only while
+  // the qs plane is n * 16 bytes exactly -- a layout with padding there is refused here, not read out of bounds)
   auto check = [&](const crabml_hip_buf* b, size_t m, size_t k, uint32_t t) {
-    return b && b->dtype == t && b->n_elems == m * k && (block_elems(t) == 1 || b->k == k);
+    return b && b->dtype == t && b->n_elems == m * k && (block_elems(t) == 1 || b->k == k) &&
+           (t != CRABML_HIP_Q5_0 || b->wl.off_scale == b->wl.n_blocks * 16);
   };
   // a layer's matrices may differ in GGML type (llama.cpp's *_K_M files: attn_v / ffn_down in Q6_K on some layers) as
   // long as they share the rhs type (buf/api.rs:142-159: every K-quant takes Q8_K): such a model runs the per-op
@@ -2498,7 +2508,11 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   const bool strict = dev->strict_order;
   const int n_cu = dev->n_cu, tp = f.tp, dim = (int)g.embedding_dim, dim_l = (int)f.dim_l, hidden_l = (int)f.hidden_l, hd = (int)f.hd;
   const uint32_t wt = f.wt;
-  const bool fused_fmt = wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0 || wt == CRABML_HIP_Q4_1;  // a dot of one term per block
+  // Q5_0 follows Q4_0 and Q5_1 follows Q4_1 in every clause below, on one device: a tensor-parallel rank of either keeps the per-op
+  // segments (none of the tensor-parallel launch forms is built for them)
+  const bool q5_fmt = wt == CRABML_HIP_Q5_0 || wt == CRABML_HIP_Q5_1;
+  const bool like_q4_0 = wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q5_0, like_q4_1 = wt == CRABML_HIP_Q4_1 || wt == CRABML_HIP_Q5_1;
+  const bool fused_fmt = wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0 || wt == CRABML_HIP_Q4_1 || (q5_fmt && tp == 1);  // a dot of one term per block
   const bool chunks_resident = dim / 32 <= n_cu;  // every workgroup of a wo / ffn_down gather must be resident
   // the K-quant norm epilogue (Q8_K planes out of wo / ffn_down): what every Q4_K form below builds on, and the ONLY form an EPI_ONLY
   // body (its row of the table, k_body_of) is built in -- such a context that misses a clause of it (a classifier with another rhs,
@@ -2517,7 +2531,8 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   // rows of ffn_down (k_gemv_res_nq_ord keeps the default limit; wo's rows are at most 12288 long: 32 x 388 floats, inside it).
   const auto ord5_fits = [&] {
     const void* fn = nullptr;  // (enqueue_segment_t launches k_gateup_q_ord<FMT> of the same weight type)
-    with_const_else<CRABML_HIP_Q4_0, CRABML_HIP_Q8_0, CRABML_HIP_Q4_1>((int)wt, [&](auto fmt) { fn = (const void*)k_gateup_q_ord<decltype(fmt)::value>; });
+    with_const_else<CRABML_HIP_Q4_0, CRABML_HIP_Q8_0, CRABML_HIP_Q5_0, CRABML_HIP_Q5_1, CRABML_HIP_Q4_1>(
+        (int)wt, [&](auto fmt) { fn = (const void*)k_gateup_q_ord<decltype(fmt)::value>; });
     return nq_ord_lds_bytes(hidden_l / 32, chunk_split(g.flags, hidden_l, dim, n_cu)) <= 60 * 1024 &&
            lds_fits(dev, fn, gateup_q_ord_lds_bytes(dim / 32), LDS_CAP, 60 * 1024);
   };
@@ -2543,7 +2558,7 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   // the fast K-quant segments: Q4_K always; an EPI_ONLY body in the norm-epilogue form (none has an ordered form: a strict-order device
   // keeps them on the per-op segments); Q4_1 when it cannot take the five launches (a classifier of another format) or for the A/B flag
   const bool fast_k = !strict && (!f.mixed || mix_fused) && k_fusion &&
-                      ((k_body && (!k_body_epi_only || k_epilogue_eligible)) || (wt == CRABML_HIP_Q4_1 && (f.out_wt != wt || has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS))));
+                      ((k_body && (!k_body_epi_only || k_epilogue_eligible)) || (fused_fmt && like_q4_1 && (f.out_wt != wt || (wt == CRABML_HIP_Q4_1 && has(CRABML_HIP_LLAMA_Q4_1_SEGMENTS)))));
   // per-op launches: a strict-order device without an ordered form, a weight format without fused kernels, a mix they do not take
   const bool per_op = (strict && !ord5) || !fused_fmt || (f.mixed && !mix_fused);
 
@@ -2553,7 +2568,7 @@ static StepPlan decide_step(const crabml_hip_device* dev, const crabml_hip_llama
   // (So Fused5 && !ordered says: Q4_0 / Q8_0 / Q4_1 layers, no mix, not a strict-order device -- Fused5 needs fused_fmt and, on a
   // strict device, ord5.  FusedK && !ordered says: not a strict-order device.  The tap hooks and the forms below rely on both.)
   const bool five = p.path == SegPath::Fused5;
-  const bool fast_q40_q80 = !p.ordered && (wt == CRABML_HIP_Q4_0 || wt == CRABML_HIP_Q8_0);  // beside norm_epi: the hop-free forms' step
+  const bool fast_q40_q80 = !p.ordered && (like_q4_0 || wt == CRABML_HIP_Q8_0);  // beside norm_epi: the hop-free forms' step
   // tp > 1: the epilogue also hosts the collective when the group is the P2P kind (or in the collective-free dry run).  Not for the
   // K-quant segments -- a Q4_1 body with a classifier of another format runs them: their wo / ffn_down launches host neither the norm
   // epilogue nor the collective, so over a P2P group the stand-alone all-reduce launch must run.
@@ -3134,7 +3149,7 @@ int crabml_hip_llama_debug_tap(crabml_hip_llama_t* c, size_t token, size_t pos, 
   // (decide_step: what Fused5 / FusedK and !ordered imply)
   if ((c->plan.path != SegPath::Fused5 && c->plan.path != SegPath::FusedK) || c->plan.ordered || c->tp > 1 || c->ext_kv)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
-            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 layers, a K-quant body and the mixes it takes: KBodies) on one device with its own KV cache");
+            "llama debug_tap: only the fused launches of the fast step (Q4_0 / Q8_0 / Q4_1 / Q5_0 / Q5_1 layers, a K-quant body and the mixes it takes: KBodies) on one device with its own KV cache");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   const size_t dim = c->cfg.embedding_dim, hidden = c->cfg.hidden_dim;
   // the row type of every field that leaves as blocks (the others: f32 values, the plan words)
@@ -3195,7 +3210,8 @@ int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* c, const uint32_t* to
   CH_USE(dev);
   CH_FLUSH(dev);
   const bool rows_8 = (c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1) &&
-                      (c->wtype == CRABML_HIP_Q4_0 || c->wtype == CRABML_HIP_Q8_0 || c->wtype == CRABML_HIP_Q4_1);
+                      (c->wtype == CRABML_HIP_Q4_0 || c->wtype == CRABML_HIP_Q8_0 || c->wtype == CRABML_HIP_Q4_1 || c->wtype == CRABML_HIP_Q5_0 ||
+                       c->wtype == CRABML_HIP_Q5_1);  // (Q5_0 / Q5_1: the same Q8_0 / Q8_1 row fields and plan words; no checker pins their rows yet)
   // Q8_K rows: every layer matrix Q4_K, Q5_K or Q6_K (the *_K_M mixes), the classifier one of them too; a context created with
   // CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K: Q2_K and Q3_K matrices as well (the Q2_K / Q3_K recipes)
   bool rows_k = c->qt == CRABML_HIP_Q8_K;
@@ -3209,7 +3225,7 @@ int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* c, const uint32_t* to
   rows_k = rows_k && k_body(c->output);
   if (c->tp > 1 || dev->strict_order || c->ext_kv || !(rows_8 || rows_k))
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED,
-            "llama debug_prefill_tap: only Q4_0 / Q8_0 / Q4_1 and Q4_K / Q5_K / Q6_K layers (the *_K_M mixes; Q2_K / Q3_K: PREFILL_TAP_Q2K_Q3K) of the fast prompt pass on one device");
+            "llama debug_prefill_tap: only Q4_0 / Q8_0 / Q4_1 / Q5_0 / Q5_1 and Q4_K / Q5_K / Q6_K layers (the *_K_M mixes; Q2_K / Q3_K: PREFILL_TAP_Q2K_Q3K) of the fast prompt pass on one device");
   if (layer >= c->cfg.n_layers) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_prefill_tap: layer %zu of %zu", layer, (size_t)c->cfg.n_layers);
   CH_TRY(prefill_check(c, tokens, n));
   const size_t chunk = prefill_chunk_rows(c);

@@ -263,7 +263,7 @@ __device__ __forceinline__ void nq_epilogue(float (&acc)[2 / SPLIT], float res, 
                                             void* __restrict__ isum, const NormGather& ng, float eps, int blk, int part, int nchunks,
                                             int row, int lane, int wave, int wg_index, int nwg_all,
                                             const typename TpArg<TP>::type& tp = typename TpArg<TP>::type{}) {
-  constexpr bool Q81 = FMT == CRABML_HIP_Q4_1;
+  constexpr bool Q81 = rhs_is_q8_1<FMT>;
   constexpr bool KQ = FMT == CRABML_HIP_Q4_K;
   constexpr int RW = 2 / SPLIT;
   constexpr int ROWS = 32 / SPLIT;
@@ -725,7 +725,7 @@ template <int FMT, int SPLIT, bool PIPE>  // PIPE: the chain follows the stream 
 __global__ __launch_bounds__(1024) void k_gemv_res_nq_ord(Planes w, typename ActOf<FMT>::type act, float* __restrict__ x,
                                                           const float* __restrict__ wnext, float eps, signed char* __restrict__ q,
                                                           void* __restrict__ d, void* __restrict__ isum, NormGather ng, int nb) {
-  constexpr bool Q81 = FMT == CRABML_HIP_Q4_1;
+  constexpr bool Q81 = rhs_is_q8_1<FMT>;
   constexpr int RW = 2 / SPLIT, ROWS = 32 / SPLIT;
   extern __shared__ __attribute__((aligned(16))) float ord_terms[];
   __shared__ __attribute__((aligned(16))) float hv[32];
@@ -1070,7 +1070,7 @@ __global__ __launch_bounds__(1024) void k_gateup_q(Planes wg, Planes wu, typenam
                                                    FfnAct fa, signed char* __restrict__ q,
                                                    unsigned short* __restrict__ d, void* __restrict__ isum, int nb, RmsTail rt) {
   using F = BlockFmt<FMT>;
-  constexpr bool Q81 = FMT == CRABML_HIP_Q4_1;
+  constexpr bool Q81 = rhs_is_q8_1<FMT>;
   __shared__ float hv[32];
   const int lane = threadIdx.x & 63, wave = wave_in_wg();
   const int blk = blockIdx.x;
@@ -1184,7 +1184,7 @@ template <int FMT>
 __global__ __launch_bounds__(1024) void k_gateup_q_ord(Planes wg, Planes wu, typename ActOf<FMT>::type act,
                                                        FfnAct fa, signed char* __restrict__ q,
                                                        unsigned short* __restrict__ d, void* __restrict__ isum, int nb) {
-  constexpr bool Q81 = FMT == CRABML_HIP_Q4_1;
+  constexpr bool Q81 = rhs_is_q8_1<FMT>;
   extern __shared__ __attribute__((aligned(16))) float ord_terms[];
   const int lane = threadIdx.x & 63, wave = wave_in_wg();
   const int blk = blockIdx.x;

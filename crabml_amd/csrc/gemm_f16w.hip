@@ -252,7 +252,34 @@ __device__ __forceinline__ f16x8 unpack_q5_k_f16(unsigned w, unsigned hw, const 
   return f16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
 }
 
-enum { WF_Q4_0 = 0, WF_Q8_0 = 1, WF_Q4_K = 2, WF_Q6_K = 3, WF_Q4_1 = 4, WF_Q2_K = 5, WF_Q3_K = 6, WF_Q5_K = 7 };  // the weight format of a GEMM
+// Q5_0 / Q5_1: dword s of a block's qs (elements 4 s .. 4 s + 3 in the low nibbles, 16 + 4 s .. in the high ones; buf_q5_0.rs:22-37) with
+// their fifth bits -- qh bits 4 s .. 4 s + 3 (hl) and 16 + 4 s .. (hh), four bits each -- ORed in at bit 4 of 0x6400 | nibble as the
+// Q5_K form does.  A slot pair holds bytes (0, 2) or (1, 3) of the dword: h << 4 | h << 18 has bit 0 of h at bit 4 and bit 2 at bit 20,
+// and one position down bits 1 and 3.
+__device__ __forceinline__ unsigned q5_bit4_pairs(unsigned h) { return (h << 4) | (h << 18); }
+template <bool Q51>  // Q5_0: A' = (q5 - 16) * d, one f16 rounding; Q5_1: A' = q5 * d + m in one v_pk_fma_f16, one rounding
+__device__ __forceinline__ f16x8 unpack_q5_01_f16(unsigned w, unsigned hl, unsigned hh, f16x2 d2, f16x2 m2, unsigned magic) {
+  const _Float16 b = Q51 ? (_Float16)-1024.0f : (_Float16)-1040.0f;  // 1024 + q5 -> q5, or q5 - 16, exactly
+  const f16x2 bias = {b, b};
+  const unsigned xl = q5_bit4_pairs(hl), xh = q5_bit4_pairs(hh);
+  const unsigned u0 = and_or_bit4(xl, and_or_magic(w, magic)), u1 = and_or_bit4(xl >> 1, and_or_magic(w >> 8, magic));
+  const unsigned u2 = and_or_bit4(xh, and_or_magic(w >> 4, magic)), u3 = and_or_bit4(xh >> 1, and_or_magic(w >> 12, magic));
+  f16x2 p0, p1, p2, p3;
+  if constexpr (Q51) {
+    p0 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u0) + bias, d2, m2);
+    p1 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u1) + bias, d2, m2);
+    p2 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u2) + bias, d2, m2);
+    p3 = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, u3) + bias, d2, m2);
+  } else {
+    p0 = (__builtin_bit_cast(f16x2, u0) + bias) * d2;
+    p1 = (__builtin_bit_cast(f16x2, u1) + bias) * d2;
+    p2 = (__builtin_bit_cast(f16x2, u2) + bias) * d2;
+    p3 = (__builtin_bit_cast(f16x2, u3) + bias) * d2;
+  }
+  return f16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
+enum { WF_Q4_0 = 0, WF_Q8_0 = 1, WF_Q4_K = 2, WF_Q6_K = 3, WF_Q4_1 = 4, WF_Q2_K = 5, WF_Q3_K = 6, WF_Q5_K = 7, WF_Q5_0 = 8, WF_Q5_1 = 9 };  // the weight format of a GEMM
 // the forms whose rows are Q8_K: a chunk is half a super-block, so k is whole super-blocks and the k pieces of a split launch start on
 // super-block boundaries
 constexpr bool f16w_wf_superblock(int wf) { return wf == WF_Q4_K || wf == WF_Q6_K || wf == WF_Q2_K || wf == WF_Q3_K || wf == WF_Q5_K; }
@@ -346,7 +373,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
   // (Q5_K: qs per chunk in [2 f]; qh and the header per SUPER-BLOCK in the ring slot of its odd chunk, [2 f + 1] and hq)
   constexpr int NQ = (WF == WF_Q8_0 || WF == WF_Q6_K || WF == WF_Q3_K || WF == WF_Q5_K) ? 2 : 1;  // 16-byte quant loads per fragment and chunk
   i32x4 aq[4][NQ * F];
-  unsigned ad[4][F];   // Q4_0 / Q8_0: the block's scale; Q4_1: d | m << 16
+  unsigned ad[4][F];   // Q4_0 / Q8_0 / Q5_0: the block's scale; Q4_1 / Q5_1: d | m << 16
+  unsigned aqh[4][(WF == WF_Q5_0 || WF == WF_Q5_1) ? F : 1];  // Q5_0 / Q5_1: the block's qh dword, riding with its quants and scale
   i32x4 hq[2][F];      // Q4_K: the super-block header of ring slots (0, 1) / (2, 3), fetched with the even slot; Q6_K: the 16 scales
                        // Q2_K: the half's eight scale bytes ([0], [1]), fetched with the ODD slot; Q3_K: the record, Q5_K: the header, likewise
   unsigned hd[2][F];   // Q6_K: d; Q2_K: d | dmin << 16
@@ -422,10 +450,18 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
 #pragma unroll
         for (int u = 0; u < NQ; u++) aq[J][NQ * f + u] = __builtin_nontemporal_load(wq + blk * NQ + u);
         unsigned dv;
-        if constexpr (WF == WF_Q4_1)
+        if constexpr (WF == WF_Q4_1) {
           dv = __builtin_nontemporal_load((const unsigned*)wsc + blk);
-        else
+        } else if constexpr (WF == WF_Q5_1) {  // (d, m, qh): eight bytes per block
+          const i32x2 rec = __builtin_nontemporal_load((const i32x2*)wsc + blk);
+          dv = (unsigned)rec[0];
+          aqh[J][f] = (unsigned)rec[1];
+        } else if constexpr (WF == WF_Q5_0) {  // qh[n] u32 (wsc) | d[n] f16 (ws2)
+          aqh[J][f] = __builtin_nontemporal_load((const unsigned*)wsc + blk);
+          dv = __builtin_nontemporal_load((const unsigned short*)w6s + blk);
+        } else {
           dv = __builtin_nontemporal_load(wd + blk);
+        }
         ad[J][f] = kb < nb ? dv : 0u;  // past the row's end: scale 0 (and m 0), the slots add nothing
       }
     }
@@ -510,7 +546,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
         q3k_f16_consts<(J & 1)>(hq[J >> 1][f], g, cs[f].c_lo, cs[f].c_hi);
       } else if constexpr (WF == WF_Q5_K) {
         cs[f] = q4k_f16_consts(hq[J >> 1][f], 2 * (g >> 1) + (J & 1));  // the chunk's pair
-      } else if constexpr (WF == WF_Q4_1) {
+      } else if constexpr (WF == WF_Q4_1 || WF == WF_Q5_1) {
         const unsigned dm = ad[J][f];
         cs[f].c_lo = cs[f].c_hi = __builtin_bit_cast(f16x2, (dm & 0xffffu) | (dm << 16));
         cs[f].o_lo = cs[f].o_hi = __builtin_bit_cast(f16x2, (dm >> 16) | (dm & 0xffff0000u));
@@ -544,6 +580,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16w(F16wMats mats, const i32x4
           if constexpr (WF == WF_Q3_K)
             a[f] = unpack_q3_k_f16((unsigned)aq[J | 1][2 * f][s] >> (4 * (J & 1)), (unsigned)aq[J | 1][2 * f + 1][s] >> (4 * (g >> 1) + 2 * (J & 1)),
                                    cs[f].c_lo, cs[f].c_hi, magic);
+          if constexpr (WF == WF_Q5_0)
+            a[f] = unpack_q5_01_f16<false>((unsigned)aq[J][f][s], (aqh[J][f] >> (4 * s)) & 0xFu, (aqh[J][f] >> (16 + 4 * s)) & 0xFu, d2[f], d2[f], magic);
+          if constexpr (WF == WF_Q5_1)
+            a[f] = unpack_q5_01_f16<true>((unsigned)aq[J][f][s], (aqh[J][f] >> (4 * s)) & 0xFu, (aqh[J][f] >> (16 + 4 * s)) & 0xFu, cs[f].c_lo, cs[f].o_lo,
+                                          magic);
           if constexpr (WF == WF_Q5_K)
             a[f] = unpack_q5_k_f16((unsigned)aq[J][2 * f][s], (unsigned)aq[J | 1][2 * f + 1][s] >> (4 * (g >> 1) + 2 * (J & 1)), cs[f], magic);
           if constexpr (WF == WF_Q6_K)
@@ -721,6 +762,15 @@ __global__ __launch_bounds__(256) void k_f16w_range(const char* __restrict__ sc,
   } else if (wf == WF_Q4_1) {
     const unsigned dm = ((const unsigned*)sc)[i];
     a = 15.0f * fabsf(h2f((unsigned short)(dm & 0xffffu))) + fabsf(h2f((unsigned short)(dm >> 16)));  // n d + m, n <= 15
+  } else if (wf == WF_Q5_0) {
+    a = 16.0f * fabsf(h2f(((const unsigned short*)(sc + nblk * 4))[i]));  // (d follows qh) |q5 - 16| <= 16: an exact product
+  } else if (wf == WF_Q5_1) {
+    // q d + m is linear in q = 0 .. 31: the ends, as the kernel rounds them (31 d is exact in f32; one rounding to f16)
+    const unsigned dm = ((const unsigned*)sc)[2 * i];
+    const float d = h2f((unsigned short)(dm & 0xffffu)), m = h2f((unsigned short)(dm >> 16));
+    const float top = fabsf(h2f(f2h(fmaf(31.0f, d, m))));
+    a = fabsf(m) > top ? fabsf(m) : top;
+    if (!(fabsf(d) <= 65504.0f) || !(fabsf(m) <= 65504.0f) || !(top <= 65504.0f)) a = __builtin_inff();  // (a non-finite field: out of range)
   } else if (wf == WF_Q4_K) {
     const unsigned h = ((const unsigned*)sc)[4 * i];
     const float c1 = h2f(f2h(63.0f * h2f((unsigned short)(h & 0xffffu)))), c2 = h2f(f2h(63.0f * h2f((unsigned short)(h >> 16))));
@@ -752,6 +802,8 @@ static int f16w_wf(uint32_t dt) {
     case CRABML_HIP_Q2_K: return WF_Q2_K;
     case CRABML_HIP_Q3_K: return WF_Q3_K;
     case CRABML_HIP_Q5_K: return WF_Q5_K;
+    case CRABML_HIP_Q5_0: return WF_Q5_0;
+    case CRABML_HIP_Q5_1: return WF_Q5_1;
     default: return WF_Q4_0;
   }
 }
@@ -783,8 +835,8 @@ bool gemm_f16w_takes(crabml_hip_device* dev, const crabml_hip_buf* w, uint32_t a
 }
 // the weight formats the kernel covers, and the rows' format each pairs with (CpuTensorBuf::quantize's choice: buf/api.rs:142-159)
 bool gemm_f16w_covers(uint32_t w_dtype, uint32_t act_qtype) {
-  if (act_qtype == CRABML_HIP_Q8_0) return w_dtype == CRABML_HIP_Q4_0 || w_dtype == CRABML_HIP_Q8_0;
-  if (act_qtype == CRABML_HIP_Q8_1) return w_dtype == CRABML_HIP_Q4_1;
+  if (act_qtype == CRABML_HIP_Q8_0) return w_dtype == CRABML_HIP_Q4_0 || w_dtype == CRABML_HIP_Q8_0 || w_dtype == CRABML_HIP_Q5_0;
+  if (act_qtype == CRABML_HIP_Q8_1) return w_dtype == CRABML_HIP_Q4_1 || w_dtype == CRABML_HIP_Q5_1;
   return act_qtype == CRABML_HIP_Q8_K &&
          (w_dtype == CRABML_HIP_Q4_K || w_dtype == CRABML_HIP_Q6_K || w_dtype == CRABML_HIP_Q2_K || w_dtype == CRABML_HIP_Q3_K ||
           w_dtype == CRABML_HIP_Q5_K);
@@ -872,9 +924,9 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
     const char* wp = (const char*)w[jj]->ptr;
     mats.wq[j] = (const i32x4*)wp;
     mats.wd[j] = wp + w[jj]->wl.off_scale;
-    // (Q6_K: ql | qh | scales | d; Q2_K: qs | scales | (d, dmin); Q3_K: qs | hmask | records; Q5_K: qs | qh | headers, common.hpp)
+    // (Q5_0: qs | qh | d; Q6_K: ql | qh | scales | d; Q2_K: qs | scales | (d, dmin); Q3_K: qs | hmask | records; Q5_K: qs | qh | headers, common.hpp)
     mats.ws2[j] = wp + w[jj]->wl.off_scale +
-                  w[jj]->wl.n_blocks * (dt == CRABML_HIP_Q2_K ? 16 : (dt == CRABML_HIP_Q3_K || dt == CRABML_HIP_Q5_K) ? 32 : 64);
+                  w[jj]->wl.n_blocks * (dt == CRABML_HIP_Q5_0 ? 4 : dt == CRABML_HIP_Q2_K ? 16 : (dt == CRABML_HIP_Q3_K || dt == CRABML_HIP_Q5_K) ? 32 : 64);
     mats.ws3[j] = wp + w[jj]->wl.off_scale + w[jj]->wl.n_blocks * 80;
     mats.out[j] = out[jj];
     mats.out2[j] = ws + before;
@@ -930,6 +982,10 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
     ok = launch_f16w_fmt<WF_Q3_K>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
   else if (dt == CRABML_HIP_Q5_K)
     ok = launch_f16w_fmt<WF_Q5_K>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
+  else if (dt == CRABML_HIP_Q5_0)
+    ok = launch_f16w_fmt<WF_Q5_0>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
+  else if (dt == CRABML_HIP_Q5_1)
+    ok = launch_f16w_fmt<WF_Q5_1>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
   else
     ok = launch_f16w_fmt<WF_Q4_0>(dev, mats, row_tiles, k, xh, b, ksplit, F, variant, gu, T);
   if (ok && gu) *gu_done = hquant ? 2 : 1;

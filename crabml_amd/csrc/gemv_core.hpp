@@ -30,6 +30,21 @@ __device__ __forceinline__ int dot_u4(i32x4 q, i32x4 xlo, i32x4 xhi) {
   }
   return s;
 }
+// four bits b -> bit 4 of four bytes (the fifth bit of four 5-bit levels)
+__device__ __forceinline__ unsigned spread4_to_bit4(unsigned b) { return ((b * 0x00204081u) & 0x01010101u) << 4; }
+// unsigned 5-bit levels (Q5_0, Q5_1): dword i of q = elements 4i .. 4i + 3 (low nibbles) | 16 + 4i .. (high nibbles), their fifth bits
+// qh bits 4i .. and 16 + 4i ..  (buf_q5_0.rs:148-157, buf_q5_1.rs:146-155).  The one copy of the unpack: the per-op pieces
+// (PieceQ5_0 / PieceQ5_1) and the fused step's row loaders (BlockFmt) both take their integers here.
+__device__ __forceinline__ int dot_u5(i32x4 q, unsigned qh, i32x4 xlo, i32x4 xhi) {
+  int s = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned v = (unsigned)q[i];
+    s = __builtin_amdgcn_sdot4((int)((v & 0x0F0F0F0Fu) | spread4_to_bit4((qh >> (4 * i)) & 0xFu)), xlo[i], s, false);
+    s = __builtin_amdgcn_sdot4((int)(((v >> 4) & 0x0F0F0F0Fu) | spread4_to_bit4((qh >> (16 + 4 * i)) & 0xFu)), xhi[i], s, false);
+  }
+  return s;
+}
 __device__ __forceinline__ int dot_i8x32(i32x4 a0, i32x4 a1, i32x4 b0, i32x4 b1) {
   int s = 0;
 #pragma unroll
@@ -119,6 +134,24 @@ struct XUnit {  // the activation side of one unit
   float dx;
   int xs;  // Q4_0: sum of the block's quants; Q4_1: the Q8_1 block's raw f16 pair d | s << 16
 };
+// (keeps a requested block's first use where it stands: otherwise the compiler hoists every step's scale conversion above the first
+// step, and with it the wait for the batch's last scale)
+__device__ __forceinline__ void pin_scale(unsigned short& d) {
+  unsigned s = d;
+  asm volatile("" : "+v"(s));
+  d = (unsigned short)s;
+}
+__device__ __forceinline__ void pin_scale(unsigned& dm) { asm volatile("" : "+v"(dm)); }
+
+// the rhs of a 32-element weight format: Q8_1 rows for the formats with a block minimum, Q8_0 rows for the others
+// (vec_dot_rhs_dtype, common.hpp).  Stated once: every `Q81` of the fused kernels and their host asks here.
+template <int FMT>
+inline constexpr bool rhs_is_q8_1 = FMT == CRABML_HIP_Q4_1 || FMT == CRABML_HIP_Q5_1;
+// ... and whether the fused step's tensor-parallel launch forms (k_gateup_h, the f32-rhs prologue, the in-launch collective) are built
+// for a format: not for Q5_0 / Q5_1, whose tensor-parallel ranks run the per-op segments (decide_step)
+template <int FMT>
+inline constexpr bool has_tp_forms = FMT != CRABML_HIP_Q5_0 && FMT != CRABML_HIP_Q5_1;
+
 template <int FMT>
 struct BlockFmt;
 
@@ -138,6 +171,7 @@ struct BlockFmt<CRABML_HIP_Q4_0> {
   static __device__ __forceinline__ XUnit loadx(const ActQ8_0& act, int u) {
     return XUnit{act.q[2 * u], act.q[2 * u + 1], h2f(act.d[u]), act.isum[u]};
   }
+  static __device__ __forceinline__ void pin(Blk& b) { pin_scale(b.d); }
   // buf_q4_0.rs:249: sumi as f32 * d_w * d_x
   static __device__ __forceinline__ float term(const Blk& b, const XUnit& x) {
     return ((float)dot_q4_0(b.q, x.x0, x.x1, x.xs) * h2f(b.d)) * x.dx;
@@ -160,6 +194,7 @@ struct BlockFmt<CRABML_HIP_Q8_0> {
   static __device__ __forceinline__ XUnit loadx(const ActQ8_0& act, int u) {
     return XUnit{act.q[u], i32x4{0, 0, 0, 0}, h2f(act.d[u >> 1]), 0};
   }
+  static __device__ __forceinline__ void pin(Blk& b) { pin_scale(b.d); }
   // buf_q8_0.rs:282; lanes 2j / 2j+1 hold the two halves of a block (both active: nu is even)
   static __device__ __forceinline__ float term(const Blk& b, const XUnit& x) {
     int s = 0;
@@ -187,12 +222,73 @@ struct BlockFmt<CRABML_HIP_Q4_1> {  // planes qs[n][16] | (d, m)[n] f16 pairs; r
   static __device__ __forceinline__ XUnit loadx(const ActQ8_1& act, int u) {
     return XUnit{act.q[2 * u], act.q[2 * u + 1], 0.0f, (int)((unsigned)act.d[u] | ((unsigned)act.s[u] << 16))};
   }
+  static __device__ __forceinline__ void pin(Blk& b) { pin_scale(b.dm); }
   // buf_q4_1.rs:276: (d_w * d_x) and (m * s) are f16 products rounded to f16 by the half crate
   static __device__ __forceinline__ float term(const Blk& b, const XUnit& x) {
     const int si = dot_u4(b.q, x.x0, x.x1);
     const unsigned short dwh = (unsigned short)(b.dm & 0xffffu), mwh = (unsigned short)(b.dm >> 16);
     const unsigned short dxh = (unsigned short)((unsigned)x.xs & 0xffffu), sxh = (unsigned short)((unsigned)x.xs >> 16);
     return h2f(h_mul(dwh, dxh)) * (float)si + h2f(h_mul(mwh, sxh));
+  }
+};
+
+// Q5_0: planes qs[n][16] | qh[n] u32 | d[n] f16 (common.hpp), rhs Q8_0.  `wd` is the qh plane; the qs plane is n * 16 bytes exactly
+// (off_scale = n * 16, no padding), so the d plane -- n * 4 bytes behind qh -- lies (wd - wq) / 4 bytes behind wd: a uniform offset
+// from the two pointers every launch already carries.  A row streams 16 + 4 + 2 bytes per block.
+template <>
+struct BlockFmt<CRABML_HIP_Q5_0> {
+  static constexpr int UNITS = 1;
+  struct Blk {
+    i32x4 q;
+    unsigned qh;
+    unsigned short d;
+  };
+  static __device__ __forceinline__ Blk load(const i32x4* wq, const unsigned short* wd, size_t row, int nb, int u) {
+    const unsigned short* dp = (const unsigned short*)((const char*)wd + (((const char*)wd - (const char*)wq) >> 2));
+    Blk b;
+    b.q = __builtin_nontemporal_load(wq + row * nb + u);
+    b.qh = __builtin_nontemporal_load((const unsigned*)wd + row * nb + u);
+    b.d = __builtin_nontemporal_load(dp + row * nb + u);
+    return b;
+  }
+  static __device__ __forceinline__ XUnit loadx(const ActQ8_0& act, int u) {
+    return XUnit{act.q[2 * u], act.q[2 * u + 1], h2f(act.d[u]), act.isum[u]};
+  }
+  static __device__ __forceinline__ void pin(Blk& b) { pin_scale(b.d); }
+  // buf_q5_0.rs:158: sumi as f32 * d_w * d_x, sumi = sum (q5 - 16) * q8 exactly
+  static __device__ __forceinline__ float term(const Blk& b, const XUnit& x) {
+    return ((float)(dot_u5(b.q, b.qh, x.x0, x.x1) - 16 * x.xs) * h2f(b.d)) * x.dx;
+  }
+};
+
+// Q5_1: planes qs[n][16] | (d f16, m f16, qh u32)[n], rhs Q8_1 (q | d | s).  16 + 8 bytes per block.
+template <>
+struct BlockFmt<CRABML_HIP_Q5_1> {
+  static constexpr int UNITS = 1;
+  struct Blk {
+    i32x4 q;
+    i32x2 h;  // d | m << 16, qh
+  };
+  static __device__ __forceinline__ Blk load(const i32x4* wq, const unsigned short* wd, size_t row, int nb, int u) {
+    Blk b;
+    b.q = __builtin_nontemporal_load(wq + row * nb + u);
+    b.h = __builtin_nontemporal_load((const i32x2*)wd + row * nb + u);
+    return b;
+  }
+  static __device__ __forceinline__ XUnit loadx(const ActQ8_1& act, int u) {
+    return XUnit{act.q[2 * u], act.q[2 * u + 1], 0.0f, (int)((unsigned)act.d[u] | ((unsigned)act.s[u] << 16))};
+  }
+  static __device__ __forceinline__ void pin(Blk& b) {
+    unsigned dm = (unsigned)b.h[0];
+    pin_scale(dm);
+    b.h[0] = (int)dm;
+  }
+  // buf_q5_1.rs:156: sumi as f32 * f16(d_w * d_x) + f16(m * s), the two f16 products rounded to f16 as Q4_1's
+  static __device__ __forceinline__ float term(const Blk& b, const XUnit& x) {
+    const int si = dot_u5(b.q, (unsigned)b.h[1], x.x0, x.x1);
+    const unsigned dm = (unsigned)b.h[0];
+    const unsigned short dxh = (unsigned short)((unsigned)x.xs & 0xffffu), sxh = (unsigned short)((unsigned)x.xs >> 16);
+    return (float)si * h2f(h_mul((unsigned short)(dm & 0xffffu), dxh)) + h2f(h_mul((unsigned short)(dm >> 16), sxh));
   }
 };
 
@@ -261,15 +357,6 @@ __device__ __forceinline__ void rows_partial_2step(const i32x4* __restrict__ wq,
 // `live ? t : 0.0f`: acc starts at +0.0 and can never become -0.0, so this equals a skipped add bit for bit.  Same terms, same
 // ascending per-lane order as rows_partial and the two-unit loop of k_gemv_res_nq: bit-identical to both.
 
-// (keeps a requested block's first use where it stands: otherwise the compiler hoists every step's scale conversion above the first
-// step, and with it the wait for the batch's last scale)
-__device__ __forceinline__ void pin_scale(unsigned short& d) {
-  unsigned s = d;
-  asm volatile("" : "+v"(s));
-  d = (unsigned short)s;
-}
-__device__ __forceinline__ void pin_scale(unsigned& dm) { asm volatile("" : "+v"(dm)); }
-
 // act: the planes in LDS; mid(): parks them and syncs the workgroup
 template <int FMT, int R, int D, class ACT, class MID>
 __device__ __forceinline__ void rows_partial_deep(const i32x4* __restrict__ wq, const unsigned short* __restrict__ wd, const ACT& act,
@@ -312,10 +399,7 @@ __device__ __forceinline__ void rows_partial_deep(const i32x4* __restrict__ wq, 
       const XUnit x = F::loadx(act, live ? u : nu - 1);
 #pragma unroll
       for (int r = 0; r < R; r++) {
-        if constexpr (FMT == CRABML_HIP_Q4_1)
-          pin_scale(blk[j][r].dm);
-        else
-          pin_scale(blk[j][r].d);
+        F::pin(blk[j][r]);
         const float t = F::term(blk[j][r], x);
         acc[r] += live ? t : 0.0f;
       }
@@ -1032,8 +1116,6 @@ __device__ __forceinline__ float q6k_term(const Q6KPiece& w, const Q4KX& x, int 
 // decode step); one policy per format describes a lane's 16-byte PIECE of quants: what it loads, the exact integers it yields,
 // and the f32 term in the reference's own expression.  Planes (common.hpp): the first plane holds QB bytes of quants per block,
 // `off` = n * QB is where the second starts (n = blocks of the tensor), the others follow.
-// four bits b -> bit 4 of four bytes (the fifth bit of four 5-bit levels)
-__device__ __forceinline__ unsigned spread4_to_bit4(unsigned b) { return ((b * 0x00204081u) & 0x01010101u) << 4; }
 __device__ __forceinline__ int quad_sum_i32(int v) {
   v += dpp_i<0xB1>(v);
   v += dpp_i<0x4E>(v);
@@ -1064,14 +1146,7 @@ struct PieceQ5_0 {  // planes qs[n][16] | qh[n] u32 | d[n] f16; rhs Q8_0
   static __device__ __forceinline__ X loadx(const Act& a, int c) { return X{a.q[2 * c], a.q[2 * c + 1], h2f(a.d[c]), a.isum[c]}; }
   // sum (q5 - 16) * q8, exact (buf_q5_0.rs:148-157)
   static __device__ __forceinline__ void ints(const W& w, const X& x, int c, int* o) {
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const unsigned v = (unsigned)w.q[i];
-      s = __builtin_amdgcn_sdot4((int)((v & 0x0F0F0F0Fu) | spread4_to_bit4((w.qh >> (4 * i)) & 0xFu)), x.x0[i], s, false);
-      s = __builtin_amdgcn_sdot4((int)(((v >> 4) & 0x0F0F0F0Fu) | spread4_to_bit4((w.qh >> (16 + 4 * i)) & 0xFu)), x.x1[i], s, false);
-    }
-    o[0] = s - 16 * x.xs;
+    o[0] = dot_u5(w.q, w.qh, x.x0, x.x1) - 16 * x.xs;
   }
   static __device__ __forceinline__ int group_index(int c, int g) { return c; }
   static __device__ __forceinline__ float term(const W& w, const X& x, int lane) {  // buf_q5_0.rs:158
@@ -1103,15 +1178,7 @@ struct PieceQ5_1 {  // planes qs[n][16] | (d f16, m f16, qh u32)[n]; rhs Q8_1
     return X{a.q[2 * c], a.q[2 * c + 1], (unsigned)a.d[c] | ((unsigned)a.s[c] << 16)};
   }
   static __device__ __forceinline__ void ints(const W& w, const X& x, int c, int* o) {  // sum q5 * q8 (buf_q5_1.rs:146-155)
-    const unsigned qh = (unsigned)w.h[1];
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const unsigned v = (unsigned)w.q[i];
-      s = __builtin_amdgcn_sdot4((int)((v & 0x0F0F0F0Fu) | spread4_to_bit4((qh >> (4 * i)) & 0xFu)), x.x0[i], s, false);
-      s = __builtin_amdgcn_sdot4((int)(((v >> 4) & 0x0F0F0F0Fu) | spread4_to_bit4((qh >> (16 + 4 * i)) & 0xFu)), x.x1[i], s, false);
-    }
-    o[0] = s;
+    o[0] = dot_u5(w.q, (unsigned)w.h[1], x.x0, x.x1);
   }
   static __device__ __forceinline__ int group_index(int c, int g) { return c; }
   // buf_q5_1.rs:156: sumi as f32 * f16(d_w * d_x) + f16(m * s) -- the two products are f16 * f16 rounded to f16, as Q4_1's
@@ -1621,7 +1688,7 @@ __device__ __forceinline__ void rows_dot(const i32x4* __restrict__ wq, const uns
 }
 template <int FMT>
 struct ActOf {
-  typedef typename std::conditional<KBody<FMT>::IS, ActQ8_K, typename std::conditional<FMT == CRABML_HIP_Q4_1, ActQ8_1, ActQ8_0>::type>::type type;
+  typedef typename std::conditional<KBody<FMT>::IS, ActQ8_K, typename std::conditional<rhs_is_q8_1<FMT>, ActQ8_1, ActQ8_0>::type>::type type;
 };
 
 }  // namespace crabml_hip

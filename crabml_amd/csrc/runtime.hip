@@ -1025,7 +1025,7 @@ int crabml_hip_debug_gemm_f16w(crabml_hip_device_t* dev, const crabml_hip_buf_t*
     if (!w[j] || !out[j]) return CRABML_HIP_BAD_INPUT;
     CH_TRY(observe(dev, w[j]));
     if (!gemm_f16w_covers(w[j]->dtype, qt) || w[j]->dtype != dt || w[j]->k != k || m[j] * k > w[j]->n_elems)
-      CH_BAIL(dev, CRABML_HIP_TENSOR_ERROR, "debug_gemm_f16w: one of Q4_0 / Q8_0 / Q4_1 / Q4_K / Q6_K / Q2_K / Q3_K / Q5_K for every matrix, matching shapes");
+      CH_BAIL(dev, CRABML_HIP_TENSOR_ERROR, "debug_gemm_f16w: one of Q4_0 / Q8_0 / Q4_1 / Q5_0 / Q5_1 / Q4_K / Q6_K / Q2_K / Q3_K / Q5_K for every matrix, matching shapes");
     mtot += m[j];
   }
   CH_TRY(observe(dev, x));

@@ -206,11 +206,13 @@ int crabml_hip_batch_matmul(crabml_hip_device_t* dev, const crabml_hip_buf_t* a,
  * group 1 to 8) or on the exact tile / long-row kernels (strict-order device, EXACT_ATTENTION, head_dim 256: groups 1 / 2 / 4 / 8,
  * seq_len % 8 == 0).  Everything else past the 64 KiB row -- an f32 cache, tensor-parallel ranks, the A/B flags that switch those
  * kernels off, more than 32768 positions -- is CRABML_HIP_NOT_IMPLEMENTED, and the message names the reason.
- * Weights: layer matrices in any matmul_vec format (Q4_0, Q8_0, Q4_1, Q2_K, Q3_K, Q4_K, Q5_K and Q6_K run fused kernels, Q4_K and Q5_K also
+ * Weights: layer matrices in any matmul_vec format (Q4_0, Q8_0, Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, Q4_K, Q5_K and Q6_K run fused kernels --
+ * Q5_0 as Q4_0 and Q5_1 as Q4_1 in every form, the strict-order one included, but on one device only: a tensor-parallel rank of
+ * either runs the per-op segments --, Q4_K and Q5_K also
  * with attn_v / ffn_down in Q6_K -- llama.cpp's *_K_M mixes --, Q3_K also with attn_v / attn_output / ffn_down in Q4_K or Q5_K --
  * its Q3_K_S / _M / _L recipes --, Q2_K also with those three tensors in Q3_K or Q4_K -- its Q2_K / Q2_K_S recipes; Q2_K, Q3_K, Q5_K
  * and an all-Q6_K body on one device without
- * CRABML_HIP_FLAG_STRICT_ORDER and with a K-quant classifier, else as below; Q5_0, Q5_1, Q8_K, F16, F32, a Q2_K, Q3_K or Q6_K body
+ * CRABML_HIP_FLAG_STRICT_ORDER and with a K-quant classifier, else as below; Q8_K, F16, F32, a Q2_K, Q3_K or Q6_K body
  * with a layer tensor outside those sets and any other mix sharing
  * one rhs dtype run as per-op segments inside the same graph); the classifier may have another format; norm
  * weights F32.  Tensor types whose rhs dtypes differ inside a layer: CRABML_HIP_NOT_IMPLEMENTED (use the
@@ -226,7 +228,7 @@ typedef struct crabml_hip_llama crabml_hip_llama_t;
                                           f16-accumulated PV chain (buf_f16.rs:152-163) instead of the split-KV kernels that
                                           accumulate the same f16 products in f32 (DESIGN.md 2.2 states the deviation and its
                                           measured size).  Strict-order devices always run the exact chain. */
-#define CRABML_HIP_LLAMA_EXACT_NORM 8388608 /* fast mode, Q4_0 / Q8_0 layers: keep RMSNorm's division inside the launch that produces the row
+#define CRABML_HIP_LLAMA_EXACT_NORM 8388608 /* fast mode, Q4_0 / Q8_0 / Q5_0 layers: keep RMSNorm's division inside the launch that produces the row
                                           (one in-launch gather of the chunk sums per wo launch) instead of handing 1 / rms to the consuming
                                           launch -- which quantizes x * w per block first and scales the block scale afterwards: the same
                                           levels up to the 126-vs-127 rounding of a block's largest element.  Strict-order
@@ -321,7 +323,8 @@ int crabml_hip_llama_decode_sample(crabml_hip_llama_t* ctx, size_t token, size_t
  * BLOCKS), the logits of the last prompt token.  The reference's own `_batched` flag is ignored (llama2.rs:114)
  * and its batch_matmul has no causal mask for n_batch > 1; here every row attends to the cache up to its own
  * position, which is what the token loop computes.  Weight matrices see the prompt as a (rows, k) rhs: the
- * matmul_vec contract (matmul_vec.rs:6-8), on the matrix cores for Q4_0 / Q8_0 weights and >= 16 rows.  Strict-order
+ * matmul_vec contract (matmul_vec.rs:6-8), on the matrix cores for Q4_0 / Q8_0 weights and >= 16 rows (Q5_0 / Q5_1 matrices: on
+ * the f16 matrix-core GEMM from 32 rows, as Q4_0 / Q4_1; a shorter pass runs them row by row on the GEMV).  Strict-order
  * devices: bit-identical to the token loop.  tp_size > 1: falls back to the token loop. */
 int crabml_hip_llama_prefill(crabml_hip_llama_t* ctx, const uint32_t* tokens, size_t n, float* logits);
 size_t crabml_hip_llama_kv_len(const crabml_hip_llama_t* ctx);

@@ -22,7 +22,7 @@ from crabml_amd import synth
 
 ap = argparse.ArgumentParser()
 ap.add_argument("gguf", nargs="?")
-ap.add_argument("--synth", default=None, help="SHAPE:TYPE, e.g. tiny-gqa:Q4_0, llama3-8b:Q4_K_M, llama3-8b:Q5_K_M, llama3-8b:Q6_K, llama3-8b:Q3_K_M, llama3-8b:Q2_K, llama3-8b:Q2_K_MIX (llama.cpp's Q2_K recipe), llama3-8b:Q2_K_S, qwen2.5-7b:Q4_0, gemma-2b:Q8_0")
+ap.add_argument("--synth", default=None, help="SHAPE:TYPE, e.g. tiny-gqa:Q4_0, llama3-8b:Q4_K_M, llama3-8b:Q5_K_M, llama3-8b:Q6_K, llama3-8b:Q5_0, llama3-8b:Q5_1, llama3-8b:Q3_K_M, llama3-8b:Q2_K, llama3-8b:Q2_K_MIX (llama.cpp's Q2_K recipe), llama3-8b:Q2_K_S, qwen2.5-7b:Q4_0, gemma-2b:Q8_0")
 ap.add_argument("--prompt", default="1,365,400,282,7,9,11,13")
 ap.add_argument("--steps", type=int, default=32)
 ap.add_argument("--seq-len", type=int, default=0)
