@@ -3211,7 +3211,7 @@ int crabml_hip_llama_debug_prefill_tap(crabml_hip_llama_t* c, const uint32_t* to
   CH_FLUSH(dev);
   const bool rows_8 = (c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1) &&
                       (c->wtype == CRABML_HIP_Q4_0 || c->wtype == CRABML_HIP_Q8_0 || c->wtype == CRABML_HIP_Q4_1 || c->wtype == CRABML_HIP_Q5_0 ||
-                       c->wtype == CRABML_HIP_Q5_1);  // (Q5_0 / Q5_1: the same Q8_0 / Q8_1 row fields and plan words; no checker pins their rows yet)
+                       c->wtype == CRABML_HIP_Q5_1);  // (Q5_0 / Q5_1: the same Q8_0 / Q8_1 row fields and plan words; tests/test_hip_prefill_q5_01_launches.py)
   // Q8_K rows: every layer matrix Q4_K, Q5_K or Q6_K (the *_K_M mixes), the classifier one of them too; a context created with
   // CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K: Q2_K and Q3_K matrices as well (the Q2_K / Q3_K recipes)
   bool rows_k = c->qt == CRABML_HIP_Q8_K;

@@ -18,13 +18,13 @@ import numpy as np
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import test_hip_f16w_gemm as G
-from tests.q5_01_step_ref import levels
+from tests.q5_01_step_ref import WRONG, levels
 from tests.test_hip_f16w_gemm import _f16, _u
 
 FMTS = ["Q5_0", "Q5_1"]
 
 
-def _fields(raw, fmt, rows, k):
+def _fields(raw, fmt, rows, k, wrong=None):
     typ = synth.TYPE_BY_NAME[fmt]
     bb = o.BLOCK_BYTES[typ]
     rb = k // 32 * bb
@@ -32,16 +32,23 @@ def _fields(raw, fmt, rows, k):
     blk = np.stack([raw[r * rb:(r + 1) * rb] for r in rows]).reshape(-1, bb)
     h = 2 if fmt == "Q5_0" else 4
     f16at = lambda a: blk[:, a:a + 2].copy().view(np.float16).astype(np.float64)[:, 0:1]  # noqa: E731
-    qh = np.ascontiguousarray(blk[:, h:h + 4]).view("<u4")[:, 0]
-    return f16at(0), (f16at(2) if fmt == "Q5_1" else None), levels(blk[:, h + 4:], qh).astype(np.float64)
+    nr, nb = len(rows), k // 32
+    qh = np.ascontiguousarray(blk[:, h:h + 4]).view("<u4")[:, 0].reshape(nr, nb)  # (per row: a neighbour is the next block of the ROW)
+    lv = levels(blk[:, h + 4:].reshape(nr, nb, 16), qh, wrong).astype(np.float64).reshape(-1, 32)
+    d = f16at(0)
+    if wrong == "scale_neighbour":
+        d = np.roll(d.reshape(nr, nb), -1, axis=1).reshape(-1, 1)
+    return d, (f16at(2) if fmt == "Q5_1" else None), lv
 
 
-def weight_operands(raw, fmt, rows, k):
-    """(A' f16 as float64, W exact float64, error bound of A' against W), each (len(rows), k)"""
-    assert fmt in FMTS, fmt
-    d, m, q = _fields(raw, fmt, rows, k)
+def weight_operands(raw, fmt, rows, k, wrong=None):
+    """(A' f16 as float64, W exact float64, error bound of A' against W), each (len(rows), k); wrong: the operands of a kernel whose
+    loader is subtly wrong in the named way (q5_01_step_ref.WRONG: the checker's own tests)"""
+    assert fmt in FMTS and (wrong is None or wrong in WRONG), (fmt, wrong)
+    d, m, q = _fields(raw, fmt, rows, k, wrong)
+    off = wrong == "offset_dropped"
     with np.errstate(invalid="ignore", over="ignore"):
-        w = (q - 16.0) * d if fmt == "Q5_0" else q * d + m
+        w = (q - (0.0 if off else 16.0)) * d if fmt == "Q5_0" else q * d + (m * 0.0 if off else m)
     nr = len(rows)
     return _f16(w).astype(np.float64).reshape(nr, k), w.reshape(nr, k), _u(w).reshape(nr, k)
 
@@ -74,6 +81,29 @@ def edge_level_blocks(rng, fmt, m, k):
     return raw.reshape(-1)
 
 
+def refuse_matrix(model, wname, block=37):
+    """one block of the named Q5_0 / Q5_1 tensor rewritten so that the f16 GEMM's range check refuses the matrix while every weight of
+    the block is exactly 0 (the edge values of tests/test_hip_f16w_gemm_q5_01.EDGE):
+      Q5_0: d = 4096, qh = 0xFFFFFFFF, qs = 0 -- every level is 16, (16 - 16) d = 0, yet 16 |d| = 65536 > 65504;
+      Q5_1: d = 2114, m = 0, qh = 0, qs = 0 -- every level is 0, 0 d + 0 = 0, yet f16(31 * 2114 = 65534) is inf.
+    The matrix then takes the row-by-row GEMV inside a pass whose other matrices take the GEMM, and its values stay ordinary"""
+    t = model.tensors[wname]
+    fmt = synth.TYPE_NAMES[t.typ]
+    assert fmt in FMTS, (wname, fmt)
+    blk = np.array(t.data, dtype=np.uint8).reshape(-1, o.BLOCK_BYTES[t.typ])
+    assert block < blk.shape[0]
+    blk[block] = 0
+    if fmt == "Q5_0":
+        blk[block, 0:2] = np.array([4096.0], np.float16).view(np.uint8)
+        blk[block, 2:6] = 0xFF
+    else:
+        blk[block, 0:2] = np.array([2114.0], np.float16).view(np.uint8)
+    t.data = blk.reshape(-1)
+    w = weight_operands(t.data, fmt, [block * 32 // t.shape[1]], t.shape[1])[1].reshape(-1, 32)[block % (t.shape[1] // 32)]
+    assert np.all(w == 0.0), w
+    return model
+
+
 @contextlib.contextmanager
 def q5_01_operands():
     """tests/test_hip_f16w_gemm.py's checkers read Q5_0 and Q5_1 inside this block"""
@@ -96,3 +126,33 @@ def q5_01_operands():
         for tab, old in ((G.HT, saved_tabs[0]), (G.ROWS, saved_tabs[1])):
             tab.clear()
             tab.update(old)
+
+
+class _RowReaders:
+    """what prefill_pass_ref calls Q5 inside q5_01_pass: its row readers are q5_01_step_ref's, which read Q5_0 / Q5_1 rows and hand every
+    other format on to fused_step_ref's own"""
+
+    @staticmethod
+    def q5k_rows():
+        from tests import q5_01_step_ref as S
+        return S.q5_rows()
+
+
+@contextlib.contextmanager
+def q5_01_pass():
+    """tests/prefill_pass_ref.py's check_pass reads passes over Q5_0 / Q5_1 bodies inside this block: q5_01_operands for the f16 GEMM's A',
+    the two formats in F16W_FMT, the GEMV and classifier rows through q5_01_step_ref.q5_rows.  B' is Q4_0's 32-element-block multiset,
+    as check_xh already holds it for Q8_0 / Q8_1 rows.  Nothing else of the checker changes -- its bounds and its excused-share cap are
+    its own"""
+    from tests import prefill_pass_ref as P
+    saved = P.weight_operands, P.Q5
+    saved_fmt = dict(P.F16W_FMT)
+    with q5_01_operands():
+        P.weight_operands, P.Q5 = G.weight_operands, _RowReaders
+        P.F16W_FMT.update({synth.Q5_0: "Q5_0", synth.Q5_1: "Q5_1"})
+        try:
+            yield
+        finally:
+            P.weight_operands, P.Q5 = saved
+            P.F16W_FMT.clear()
+            P.F16W_FMT.update(saved_fmt)

@@ -242,6 +242,25 @@ def test_mixed_sign_models_stay_under_the_decode_and_prompt_caps(oracle, shape, 
         _under_the_cap(P.check_pass(tap, TP.PASS_TOKS[:n], kvb, kva, model, layer, form, ctx, None, twin), R.EXCUSED_CAP, ctx, P.failures)
 
 
+@pytest.mark.parametrize("fmt", ["Q5_0", "Q5_1"])
+@pytest.mark.parametrize("shape", ["tiny-gqa", "tiny-hd128"])
+def test_mixed_sign_q5_01_models_stay_under_the_prompt_cap(oracle, shape, fmt):
+    """the Q5_0 / Q5_1 models of tests/test_hip_prefill_q5_01_launches.test_mixed_sign_block_fields (the same builder, the same seed: the
+    first tried), read by the prompt-pass checker inside q5_01_pass: every launch of the f16 pass accepted, every excused share of the
+    Q8_0 / Q8_1 interval checks under the cap, from the reference alone"""
+    from tests import fused_step_ref as R
+    from tests import prefill_pass_ref as P
+    from tests import test_prefill_pass_ref as TP
+    from tests.test_q5_01_pass_ref import all_on, q5_pass
+    model = eb.mixed_sign_model(shape, synth.TYPE_BY_NAME[fmt], eb.MIXED_SIGN_SEEDS["prefill"])
+    n = len(TP.PASS_TOKS)
+    with q5_pass():
+        for layer in (0, 1):
+            ctx = f"mixed-signs {shape} {fmt} f16 pass layer {layer}"
+            tap, kvb, kva, form, aux = TP.oracle_pass(model, 0, n, layer, True, True, 1, kernel_of=all_on(P.KERNEL_F16W))
+            _under_the_cap(P.check_pass(tap, TP.PASS_TOKS[:n], kvb, kva, model, layer, form, ctx, None, None), R.EXCUSED_CAP, ctx, P.failures)
+
+
 @pytest.mark.parametrize("shape,mix", [("tiny-gqa", False), ("tiny-gqa", True), ("tiny-hd128", False)])
 def test_mixed_sign_k_quant_models_stay_under_the_decode_and_prompt_caps(oracle, shape, mix):
     from tests import fused_step_ref as R

@@ -9,8 +9,8 @@ K / V caches of every layer equal, bit for bit, those of a twin runner's plain p
 each case asserts from the launch plan -- written by the enqueue code where it decides -- that the path it is named for was taken.
 
 K-quant (Q8_K row) passes -- Q4_K, Q5_K, Q6_K layers and the Q4_K_M / Q5_K_M mixes -- are pinned the same way, through this file's
-run_case, in tests/test_hip_prefill_k_launches.py.  Not pinned here (stated, not hidden): Gemma passes, Q8_K / Q2_K / Q3_K / Q5_0 / Q5_1 /
-F32 weights, tensor-parallel ranks and the strict device (bit-exact against the oracle: tests/test_hip_prefill.py).  What the cases were seen to leave of their bounds on a device: profiles/prefill_launch_pins.md and
+run_case, in tests/test_hip_prefill_k_launches.py; Q2_K / Q3_K bodies in tests/test_hip_prefill_q23k_launches.py; Q5_0 / Q5_1 bodies in
+tests/test_hip_prefill_q5_01_launches.py.  Not pinned here (stated, not hidden): Gemma passes, Q8_K / F32 weights, tensor-parallel ranks and the strict device (bit-exact against the oracle: tests/test_hip_prefill.py).  What the cases were seen to leave of their bounds on a device: profiles/prefill_launch_pins.md and
 tests/golden/prefill_launch_pins_observed.json (evidence only; the gates are the derived bounds)."""
 import numpy as np
 import pytest

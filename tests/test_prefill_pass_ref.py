@@ -41,10 +41,11 @@ def kernel_for(t, f16w):
     return P.KERNEL_F16W if f16w else P.KERNEL_INT8
 
 
-def gemm_pieces(t, planes_rows, qt, f16w, pieces):
-    """W . rows as `pieces` k pieces of f32 [B, m] (their sum in piece order is the GEMM's output)"""
+def gemm_pieces(t, planes_rows, qt, f16w, pieces, kern=None):
+    """W . rows as `pieces` k pieces of f32 [B, m] (their sum in piece order is the GEMM's output); kern: the kernel this matrix takes
+    (default: kernel_for)"""
     m, k = t.shape
-    if kernel_for(t, f16w) != P.KERNEL_F16W:
+    if (kernel_for(t, f16w) if kern is None else kern) != P.KERNEL_F16W:
         return [np.stack([mv(t, p) for p in planes_rows])]
     ap = weight_operands(np.ascontiguousarray(t.data).view(np.uint8).reshape(-1), P.F16W_FMT[t.typ], list(range(m)), k)[0].astype(np.float32)
     bp = P.b_prime([R.parse_act(p, qt) for p in planes_rows])[1].astype(np.float32)
@@ -53,25 +54,28 @@ def gemm_pieces(t, planes_rows, qt, f16w, pieces):
     return [bp[:, a:b] @ ap[:, a:b].T for a, b in zip(cut[:-1], cut[1:])]
 
 
-def oracle_pass(model, pos0, n, layer, kv_f16, f16w, h_done, fused=True):
+def oracle_pass(model, pos0, n, layer, kv_f16, f16w, h_done, fused=True, kernel_of=None, toks=None, seq=SEQ):
     """(tap, kv_before, kv_after, form, aux) of one pass of n rows at pos0 with `layer` tapped, from the oracle's ops.  fused: residual
     add + norm + quantize as one launch per row (the pending ffn_down output and the k pieces of a cut GEMM are left to it); not fused:
     the separate launches -- k_res_epi right behind wo and ffn_down, nothing pending, no pieces left over.  Q8_K rows (K-quant
-    layers): the f32 norms, h and the class-major planes are stored as the device's tap stores them"""
+    layers): the f32 norms, h and the class-major planes are stored as the device's tap stores them.  kernel_of(matrix name, tensor,
+    layer) -> KERNEL_*: the kernel each matrix takes, one by one (default: kernel_for, the same answer for every matrix of a format).
+    toks / seq: the pass's own tokens and cache length (default: PASS_TOKS[:n], SEQ).  aux["h_absmax"]: max |silu(g) * u| per layer"""
     s = model.shape
     odev = o.OracleDevice(thread_num=1)
     qwen2 = s.arch == "qwen2"
     conf, w = (to_oracle_qwen2 if qwen2 else to_oracle)(model, odev)
-    runner = (OracleQwen2Runner if qwen2 else o.OracleLlamaRunner)(conf, w, odev, SEQ, kv_f16)
+    runner = (OracleQwen2Runner if qwen2 else o.OracleLlamaRunner)(conf, w, odev, seq, kv_f16)
     for i in range(pos0):
         runner.forward_llama([TOKS[i]], i)
     kdt = np.uint16 if kv_f16 else np.float32
-    kcs = [np.array(c.storage, dtype=kdt).reshape(s.n_kv_heads, SEQ, s.head_dim) for c in runner.key_cache]
-    vcs = [np.array(c.storage, dtype=kdt).reshape(s.n_kv_heads, SEQ, s.head_dim) for c in runner.value_cache]
+    kcs = [np.array(c.storage, dtype=kdt).reshape(s.n_kv_heads, seq, s.head_dim) for c in runner.key_cache]
+    vcs = [np.array(c.storage, dtype=kdt).reshape(s.n_kv_heads, seq, s.head_dim) for c in runner.value_cache]
     qt = o.rhs_dtype(model.wtype)
     dim, hd, L = s.dim, s.head_dim, s.n_layers
     rope_dim = s.rope_dim if s.rope_dim is not None else hd
-    toks = PASS_TOKS[:n]
+    toks = PASS_TOKS[:n] if toks is None else [int(t) for t in toks]
+    assert len(toks) == n and pos0 + n <= seq
     emb = model.tensors["token_embd.weight"]
     x = np.stack([o.dequantize(emb.data, emb.typ, t * dim, dim) for t in toks])
     kq = qt == o.Q8_K
@@ -80,7 +84,7 @@ def oracle_pass(model, pos0, n, layer, kv_f16, f16w, h_done, fused=True):
             "norm_kernel": (4 if fused else 0) if kq else (2 if f16w else 1), "in_parts": 0,
             "qkv_one": 0, "gu_one": 0, "h_done": h_done, "wo_parts": 0, "down_parts": 0, "attn_kernel": P.ATTN_TILE}
     tap, aux = {"qtype": {}, "plan": plan}, {"odev": odev}
-    form = P.Form(kv_f16=kv_f16, seq_cap=SEQ)
+    form = P.Form(kv_f16=kv_f16, seq_cap=seq)
 
     def put(name, v, t=None):
         tap[name] = np.ascontiguousarray(v).reshape(-1)
@@ -117,11 +121,11 @@ def oracle_pass(model, pos0, n, layer, kv_f16, f16w, h_done, fused=True):
         wn1 = f32w(model, f"blk.{l}.attn_norm.weight")
         planes, xn1 = norm_rows(x, wn1, s.rms_eps)
         W = {nm: model.tensors[f"blk.{l}.{nm}.weight"] for nm in P.KERNEL_WORD}
-        kern = {nm: kernel_for(t, f16w) for nm, t in W.items()}
+        kern = {nm: (kernel_of(nm, t, l) if kernel_of else kernel_for(t, f16w)) for nm, t in W.items()}
         f16 = {nm: k_ == P.KERNEL_F16W for nm, k_ in kern.items()}
         lin = {}
         for nm, wn_ in (("q", "attn_q"), ("k", "attn_k"), ("v", "attn_v")):
-            lin[nm] = gemm_pieces(model.tensors[f"blk.{l}.{wn_}.weight"], planes, qt, f16w, 1)[0]
+            lin[nm] = gemm_pieces(model.tensors[f"blk.{l}.{wn_}.weight"], planes, qt, f16w, 1, kern[wn_])[0]
         withb = {nm: (v + f32w(model, f"blk.{l}.attn_{nm}.bias")[None, :] if qwen2 else v) for nm, v in lin.items()}
         scale = np.float32(1.0) / np.sqrt(np.float32(hd))
         qr = np.stack([rope(withb["q"][r], s.n_heads, hd, pos0 + r, rope_dim, qwen2, odev) * scale for r in range(n)])
@@ -130,21 +134,22 @@ def oracle_pass(model, pos0, n, layer, kv_f16, f16w, h_done, fused=True):
         for cache, rows_ in ((kcs[l], kr), (vcs[l], withb["v"])):
             for r in range(n):
                 cache[:, pos0 + r, :] = (o.f32_to_f16_bits(rows_[r]) if kv_f16 else rows_[r]).reshape(s.n_kv_heads, hd)
-        attn = np.stack([R.oracle_attention(qr[r], kcs[l], vcs[l], s.n_heads, s.n_kv_heads, hd, SEQ, pos0 + r, kv_f16) for r in range(n)])
+        attn = np.stack([R.oracle_attention(qr[r], kcs[l], vcs[l], s.n_heads, s.n_kv_heads, hd, seq, pos0 + r, kv_f16) for r in range(n)])
         act_attn = quant_rows(attn)
-        wo = gemm_pieces(model.tensors[f"blk.{l}.attn_output.weight"], act_attn, qt, f16w, 2 if fused else 1)
+        wo = gemm_pieces(model.tensors[f"blk.{l}.attn_output.weight"], act_attn, qt, f16w, 2 if fused else 1, kern["attn_output"])
         acc = wo[0]
         for p in wo[1:]:
             acc = acc + p
         x1 = acc + x
         planes1, xn2 = norm_rows(x1, f32w(model, f"blk.{l}.ffn_norm.weight"), 1e-5)
-        g = gemm_pieces(model.tensors[f"blk.{l}.ffn_gate.weight"], planes1, qt, f16w, 1)[0]
-        u = gemm_pieces(model.tensors[f"blk.{l}.ffn_up.weight"], planes1, qt, f16w, 1)[0]
+        g = gemm_pieces(model.tensors[f"blk.{l}.ffn_gate.weight"], planes1, qt, f16w, 1, kern["ffn_gate"])[0]
+        u = gemm_pieces(model.tensors[f"blk.{l}.ffn_up.weight"], planes1, qt, f16w, 1, kern["ffn_up"])[0]
         h = np.stack([silu_mul(g[r], u[r], odev) for r in range(n)])
+        aux.setdefault("h_absmax", []).append(float(np.max(np.abs(h))))
         act_hid = quant_rows(h)
         last = l + 1 == L
         deferred = fused and not last
-        down = gemm_pieces(model.tensors[f"blk.{l}.ffn_down.weight"], act_hid, qt, f16w, 2 if deferred else 1)
+        down = gemm_pieces(model.tensors[f"blk.{l}.ffn_down.weight"], act_hid, qt, f16w, 2 if deferred else 1, kern["ffn_down"])
         if rec:
             put("n1.x", x)
             put_planes("n1.act", planes)
@@ -171,10 +176,11 @@ def oracle_pass(model, pos0, n, layer, kv_f16, f16w, h_done, fused=True):
             if len(down) > 1:
                 put("down.parts", np.stack(down[1:]))
                 plan["down_parts"] = len(down) - 1
-            # B' as each f16 GEMM finds it; v's own where q left none in v's order (a Q6_K attn_v behind a Q4_K / Q5_K attn_q)
+            # B' as each f16 GEMM finds it; v's own where neither q nor k left one in v's order (a Q6_K attn_v behind a Q4_K / Q5_K attn_q;
+            # behind a q the range check refused, k's GEMM makes it -- untapped -- and v finds it)
             if f16["attn_q"]:
                 put("n1.xh", xh_of(planes, qt), o.F16)
-            if f16["attn_v"] and not (f16["attn_q"] and W["attn_v"].typ == W["attn_q"].typ):
+            if f16["attn_v"] and not any(f16[nm] and W["attn_v"].typ == W[nm].typ for nm in ("attn_q", "attn_k")):
                 put("n1.xh.v", xh_of(planes, qt), o.F16)
             if f16["attn_output"]:
                 put("attn.xh", xh_of(act_attn, qt), o.F16)
