@@ -8,7 +8,10 @@ import pytest
 # share a hardware queue (the second would sit behind the first until its poll times out).  The HIP runtime maps streams onto 4
 # hardware queues by default (GPU_MAX_HW_QUEUES); with the session's other devices alive a 4-rank group then collides on some
 # boxes.  Set before the runtime loads; a production group is one process -- one stream -- per rank and is not affected.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# A machine may preset the variable to the runtime's default of 4 (a setdefault then does nothing and a 3- or 4-rank group times
+# out now and then): a preset below 16 is raised to 16, a larger one is kept.
+if not os.environ.get("GPU_MAX_HW_QUEUES", "").isdigit() or int(os.environ["GPU_MAX_HW_QUEUES"]) < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
