@@ -167,6 +167,7 @@ struct StepPlan {
   bool flash_ticket = false;   // A/B: the merge by the last-arriving workgroup inside k_attn_flash instead of its own launch
   size_t flash_ticket_until = 0;  // > 0: positions [attn_long_from, this) run variant 2
   bool attn_flash_rows = false;   // the batched prefill's attention runs k_attn_flash_rows (fast step, f16 cache, head_dim 64 / 128)
+  bool flash_rows_split = false;  // ... or, for the passes flash_rows_slices names, its split-KV form (no plan word: the same family)
   int flash_S = 0;                // position slices (workgroups) per kv head
   int flash_min_rows = FLASH_MIN_ROWS;  // cached rows per active slice, at least
   int attn_s_rows = 0;         // > 0: variant 0 runs k_attn_s (K / V staged through LDS) with room for this many cached rows
@@ -266,6 +267,7 @@ struct crabml_hip_llama {
   void* pf_xh = nullptr;  // the fast pass's f16 GEMMs: the current rhs rows as pre-scaled f16 (gemm_f16w.hip), gemm_f16w_xh_bytes(cap, max(dim, hidden))
   float* pf_scores = nullptr;          // long prompts: [PF_LONG_ROWS][n_heads][seq_len] f32 scores
   unsigned short* pf_p16 = nullptr;    //               and f16 probabilities, allocated on first use
+  float* pf_flash_part = nullptr;      // k_attn_flash_rows_split's partials, on the first pass that runs it (flash_rows_part_cap floats)
   std::vector<std::pair<void*, size_t>> allocs;
   // token / pos / step of the next step are staged in pinned host memory owned by the context (a ring, one slot per
   // set_state): the async copy reads it when the stream gets there, long after the caller's stack frame is gone
@@ -421,6 +423,10 @@ typedef decltype(&k_attn_s<0>) AttnSFn;
 AttnSFn attn_s_kernel(int hd) { return hd == 128 ? k_attn_s<128> : k_attn_s<0>; }
 typedef decltype(&k_attn_flash_rows<64>) FlashRowsFn;
 FlashRowsFn flash_rows_kernel(int hd) { return hd == 128 ? k_attn_flash_rows<128> : hd == 64 ? k_attn_flash_rows<64> : nullptr; }
+typedef decltype(&k_attn_flash_rows_split<64>) FlashRowsSplitFn;
+FlashRowsSplitFn flash_rows_split_kernel(int hd) {
+  return hd == 128 ? k_attn_flash_rows_split<128> : hd == 64 ? k_attn_flash_rows_split<64> : nullptr;
+}
 // strict-order Q4_K step: k_gemv_res_nq<Q4_K, SPLIT, QIN, .., ORD> (qin 1 = quantize the f32 rhs, 2 = copy finished planes) ...
 typedef decltype(&k_gemv_res_nq<CRABML_HIP_Q4_K, 1, 1, false, false, true>) NqOrdKFn;
 NqOrdKFn nq_ord_k_kernel(int split, int qin) {
@@ -1586,8 +1592,45 @@ int launch_attn_long_rows(crabml_hip_llama* c, int l, int B) {
   return rc == 0 ? 1 : -1;
 }
 
+// Position slices of a pass that runs the flash-rows family: 1 = k_attn_flash_rows as one launch, more = k_attn_flash_rows_split with
+// that many slices and its merge.  More than 1 only where the one-launch grid -- ceil(rows / 64) x n_heads workgroups -- leaves the
+// device under-filled (at most one workgroup per two CUs) AND the pass ends FLASH_ROWS_SPLIT_FROM positions deep or deeper; then about
+// two workgroups per CU, at most one slice per tile, at most FLASH_ROWS_MAX_SLICES.
+// FLASH_ROWS_SPLIT_FROM: the smallest measured end position from which the split form was not slower at any deeper measured point
+// (Llama-3-8B shape, 32- and 64-row passes ending at 512 .. 30000, profiles/long_context.md).
+constexpr size_t FLASH_ROWS_SPLIT_FROM = 512;
+int flash_rows_slices(int n_cu, size_t n_heads, size_t n_kv, size_t rows, size_t pos0) {
+  if (rows == 0 || n_kv == 0 || n_heads % n_kv != 0) return 1;
+  if ((rows + 63) / 64 * n_heads * 2 > (size_t)n_cu) return 1;
+  if (pos0 + rows < FLASH_ROWS_SPLIT_FROM) return 1;
+  const size_t wgs = n_kv * (size_t)flash_rows_split_geom((int)(n_heads / n_kv), (int)rows).nwg;  // workgroups of one slice
+  const size_t tiles = (pos0 + rows - 1) / FLASH_ROWS_BN + 1;
+  const size_t S = std::min({(2 * (size_t)n_cu + wgs - 1) / wgs, tiles, (size_t)FLASH_ROWS_MAX_SLICES});
+  return S < 2 ? 1 : (int)S;
+}
+// the most partial floats any pass of this context can ask for (flash_rows_slices without its depth and tile clauses)
+size_t flash_rows_part_cap(const crabml_hip_llama* c) {
+  size_t most = 0;
+  for (size_t rows = 1; rows <= c->pf_cap; rows++) {
+    const int S = flash_rows_slices(c->dev->n_cu, (size_t)c->n_heads_l, (size_t)c->n_kv_l, rows, (size_t)FLASH_ROWS_MAX_SLICES * FLASH_ROWS_BN + FLASH_ROWS_SPLIT_FROM);
+    if (S > 1) most = std::max(most, flash_rows_part_floats(S, (int)rows, c->n_heads_l, c->hd));
+  }
+  return most;
+}
+// the two launches of the split form: `slices` (<= the pass's tiles) slices into `part`, merged into out
+void launch_flash_rows_split(hipStream_t st, int hd, const float* q, const unsigned short* k, const unsigned short* v, const int* pos_d, float* part,
+                             float* out, int n_heads, int n_kv, int seq_cap, int B, int slices) {
+  const FlashRowsSplitGeom ge = flash_rows_split_geom(n_heads / n_kv, B);
+  flash_rows_split_kernel(hd)<<<dim3((unsigned)ge.nwg, (unsigned)n_kv, (unsigned)slices), 64 * ge.fpw, flash_rows_lds_bytes(hd), st>>>(
+      q, k, v, pos_d, part, n_heads, n_kv, seq_cap, B, slices);
+  if (hd == 128)
+    k_attn_flash_rows_merge<128><<<(unsigned)(B * n_heads), 128, 0, st>>>(part, out, B * n_heads, slices);
+  else
+    k_attn_flash_rows_merge<64><<<(unsigned)(B * n_heads), 64, 0, st>>>(part, out, B * n_heads, slices);
+}
+
 // The causal attention of a prompt pass for layer l (pf_qr x KV cache -> pf_attn): the one place that chooses among the four forms.
-// Returns the kernel as CRABML_HIP_PFPLAN_ATTN_KERNEL names it (1 flash rows, 2 tile, 3 long rows, 4 per (head, row)), < 0 = error.
+// Returns the kernel as CRABML_HIP_PFPLAN_ATTN_KERNEL names it (1 the flash-rows family, 2 tile, 3 long rows, 4 per (head, row)), < 0 = error.
 int launch_prefill_attention(crabml_hip_llama* c, int l, size_t B, size_t pos0) {
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
@@ -1597,7 +1640,15 @@ int launch_prefill_attention(crabml_hip_llama* c, int l, size_t B, size_t pos0) 
   // (a pass whose every row sees fewer cached positions than the decode step's switch to the f32 kernels -- attn_long_from --
   // keeps the exact tile kernel, so that prefill(prompt) and a token loop over the same short prompt agree bit for bit)
   if (c->plan.attn_flash_rows && kv16 && pos0 + B >= c->plan.attn_long_from) {
-    // fast step: causal flash attention on the f16 matrix cores (k_attn_flash_rows; the deviation stated for k_attn_flash)
+    // fast step: causal flash attention on the f16 matrix cores (k_attn_flash_rows; the deviation stated for k_attn_flash) -- a short
+    // pass deep in the cache in its split-KV form
+    const int slices = c->plan.flash_rows_split ? flash_rows_slices(dev->n_cu, (size_t)n_heads, (size_t)n_kv, B, pos0) : 1;
+    if (slices > 1) {
+      if (!c->pf_flash_part && dalloc(c, flash_rows_part_cap(c) * 4, (void**)&c->pf_flash_part) != 0) return -1;
+      launch_flash_rows_split(st, hd, (const float*)c->pf_qr, (const unsigned short*)c->kc[l], (const unsigned short*)c->vc[l], pos_d,
+                              c->pf_flash_part, c->pf_attn, n_heads, n_kv, seq_cap, (int)B, slices);
+      return 1;
+    }
     const dim3 fg((unsigned)((B + 63) / 64), (unsigned)n_heads);
     flash_rows_kernel(hd)<<<fg, 512, flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
                                                                       (const unsigned short*)c->vc[l], pos_d, c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
@@ -2412,7 +2463,7 @@ static bool lds_fits(const crabml_hip_device* dev, const void* fn, size_t bytes,
 static bool past_k_attn_row(size_t seq, size_t hd) { return k_attn_lds_bytes(seq, hd) > K_ATTN_LDS; }
 
 // The attention forms of a plan.  Each kernel's limit is asked for where the plan first needs that kernel, in this order: the exact
-// softmax, k_attn_pv_split, k_attn_flash, its ticket form, k_attn_flash_rows, k_attn_s -- a refusal turns that form off, nothing else.
+// softmax, k_attn_pv_split, k_attn_flash, its ticket form, k_attn_flash_rows, k_attn_flash_rows_split, k_attn_s -- a refusal turns that form off, nothing else.
 static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llama_config_t& g, const ModelFacts& f, const FlashHooks& hooks,
                              StepPlan* p) {
   const auto has = [&](int bits) { return (g.flags & bits) != 0; };
@@ -2455,6 +2506,9 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
     // the prompt pass's causal attention of the fast step (k_attn_flash_rows): 70 KB of LDS at head_dim 128
     p->attn_flash_rows =
         rows_geom && flash_rows_kernel(hd) != nullptr && lds_fits(dev, (const void*)flash_rows_kernel(hd), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
+    // ... and its split-KV form for short passes deep in the cache (k_attn_flash_rows_split: the same tiles, the same LDS)
+    p->flash_rows_split = p->attn_flash_rows && !has(CRABML_HIP_LLAMA_NO_FLASH_ROWS_SPLIT) &&
+                          lds_fits(dev, (const void*)flash_rows_split_kernel(hd), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
   }
   p->attn_long_ok = p->exact_long_ok || p->attn_flash;
   // the exact kernels: measured crossover on MI355X (Llama-3-8B shape) ~200-220.  k_attn_flash + merge overtake the staged one-workgroup
@@ -3131,7 +3185,7 @@ int crabml_hip_llama_debug_poison(crabml_hip_llama_t* c, uint32_t what, uint16_t
   }
   if ((what & 4) && c->pf_cap) {
     for (void* p : {(void*)c->pf_x, (void*)c->pf_xn, (void*)c->pf_q, (void*)c->pf_k, (void*)c->pf_v, (void*)c->pf_qr, (void*)c->pf_attn,
-                    (void*)c->pf_tmp, (void*)c->pf_g, (void*)c->pf_u, (void*)c->pf_split, (void*)c->pf_scores})
+                    (void*)c->pf_tmp, (void*)c->pf_g, (void*)c->pf_u, (void*)c->pf_split, (void*)c->pf_scores, (void*)c->pf_flash_part})
       CH_TRY(fill(p, false));
     for (void* p : {(void*)c->pf_act_dim, (void*)c->pf_act_hid, c->pf_xh, c->pf_xh2, (void*)c->pf_p16}) CH_TRY(fill(p, true));
   }
@@ -3438,6 +3492,55 @@ int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float*
   (void)hipFree(base);
   if (e != hipSuccess) return hip_fail(dev, e, "debug_flash_attention_rows", __FILE__, __LINE__);
   return 0;
+}
+
+// parity hook (crabml_hip_debug.h): k_attn_flash_rows_split and its merge by themselves, with a forced slice count
+int crabml_hip_debug_flash_attention_rows_split(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
+                                                size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, size_t slices, float* out) {
+  if (!dev || !q || !k || !v || !out || rows == 0 || n_kv == 0 || n_heads % n_kv != 0 || seq_cap < pos0 + rows || slices < 1)
+    return CRABML_HIP_BAD_INPUT;
+  if (head_dim != 128 && head_dim != 64) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_rows_split: head_dim 64 / 128");
+  if (n_heads / n_kv > 8 || pos0 + rows > (size_t)1 << 30)
+    CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_rows_split: groups 1 .. 8, at most 2^30 positions");
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  const int hd = (int)head_dim;
+  if (raise_dyn_lds(dev, (const void*)flash_rows_split_kernel(hd), (int)flash_rows_lds_bytes(hd)) != hipSuccess)
+    CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "debug_flash_attention_rows_split: LDS");
+  const size_t tiles = (pos0 + rows - 1) / FLASH_ROWS_BN + 1;
+  const int S = (int)std::min({slices, tiles, (size_t)FLASH_ROWS_MAX_SLICES});
+  const size_t nq = rows * n_heads * head_dim * 4, nkv = n_kv * seq_cap * head_dim * 2, npart = flash_rows_part_floats(S, (int)rows, (int)n_heads, hd) * 4;
+  const size_t o_q = 0, o_k = align_up(o_q + nq, 256), o_v = align_up(o_k + nkv, 256), o_out = align_up(o_v + nkv, 256),
+               o_part = align_up(o_out + nq, 256), o_pos = align_up(o_part + npart, 256), total = o_pos + 256;
+  char* base = nullptr;
+  CH_HIP(dev, hipMalloc((void**)&base, total));
+  hipStream_t st = dev->stream;
+  const int p0 = (int)pos0;
+  // the partials start as NaN words: a partial the merge reads and the first launch did not write shows in the output
+  hipError_t e = hipMemsetAsync(base + o_part, 0xFF, npart, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_q, q, nq, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_k, k, nkv, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, v, nkv, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_pos, &p0, 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) {
+    launch_flash_rows_split(st, hd, (const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
+                            (const int*)(base + o_pos), (float*)(base + o_part), (float*)(base + o_out), (int)n_heads, (int)n_kv, (int)seq_cap,
+                            (int)rows, S);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, base + o_out, nq, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(base);
+  if (e != hipSuccess) return hip_fail(dev, e, "debug_flash_attention_rows_split", __FILE__, __LINE__);
+  return 0;
+}
+
+// the decision hook (crabml_hip_debug.h): flash_rows_slices for this device
+int crabml_hip_debug_flash_rows_slices(crabml_hip_device_t* dev, size_t n_heads, size_t n_kv, size_t rows, size_t pos0) {
+  if (!dev) return 0;
+  return flash_rows_slices(dev->n_cu, n_heads, n_kv, rows, pos0);
 }
 
 }  // extern "C"

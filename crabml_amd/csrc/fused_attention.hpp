@@ -1324,6 +1324,228 @@ __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict
   }
 }
 
+// ---- the split-KV form of k_attn_flash_rows: short passes deep in the cache ----------------------------------------------------------
+// k_attn_flash_rows launches ceil(rows / 64) x n_heads workgroups that each walk the whole cache: 32 rows of the 8B shape at position
+// 30000 are 32 workgroups (of 256 CUs) x 470 tiles, half of their row waves on a clamped row, every K / V tile fetched once per q head
+// of its kv head.  This form keeps that kernel's arithmetic (f16 operands, S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_f16,
+// f32 online softmax, probabilities rounded to f16 with the normaliser summing the rounded values, causal mask on the C registers) and
+// splits the work its own way:
+//   fragment  = 16 prompt rows of one q head; a wave owns one fragment from the first tile to the last (no wave pairs, so no {m, l, O}
+//               hand-over inside the workgroup)
+//   workgroup = one kv head x one slice of the cached positions x up to 8 fragments of that kv head (row-block major: fragment f is
+//               head f % G of row block f / G; flash_rows_split_geom spreads them evenly: 32 rows of group 4 fill one workgroup of 8
+//               waves, 32 rows of group 7 are two workgroups of 7).  A K / V tile of 64 positions is staged to LDS once -- V
+//               transposed -- and read by every fragment: the G-fold refetch and the idle row waves are gone
+//   slice     = a run of whole 64-position tiles of [0, pos0 + rows), tiles s NT / S .. (s + 1) NT / S of NT: the last slice holds the
+//               causal diagonal.  A workgroup stops at the last tile any of its rows sees; a row that sees nothing of a slice keeps
+//               m = -inf, l = 0, O = 0.  Every (slice, row < rows, head) writes its unnormalised f32 O[HD] and {m, l}:
+//               part = [S][rows][n_heads][HD] O, then [S][rows][n_heads]{m, l} -- S rows n_heads (HD + 2) floats, every word the
+//               merge reads written by this launch
+//   k_attn_flash_rows_merge: per (row, head) M = max m_s, out = sum e^(m_s - M) O_s / sum e^(m_s - M) l_s, a slice with m_s = -inf
+//               weighing exactly 0 (slice 0 holds position 0, which every row sees: M is finite)
+// Staging as in k_attn_flash_rows (two buffers, loads requested a tile ahead, one barrier per tile; V zeroed at positions no row of the
+// workgroup sees, K left to the mask, reads past the cache clamped), its loops strided by the launched block size: a thread carries up
+// to PIECES / 256 pieces of K and of V across a tile in registers, which covers a tile from 4 waves on; a workgroup of fewer waves
+// fetches the rest at commit time, without the overlap.
+// Budget: 163 VGPRs at head_dim 128 (32 accumulator + 16 q + 32 staging, the two steps of a tile unrolled side by side), 111 at 64, no
+// scratch: a workgroup of 8 waves is 2 waves per SIMD, so registers allow one workgroup of 8 waves per CU at 128 (three waves per SIMD)
+// and two at 64; LDS flash_rows_lds_bytes = 69632 bytes (head_dim 64: 35840), which allows two.  The grid targets two workgroups per CU
+// and is capped at 32 slices: 256 workgroups for 32 rows of the 8B shape.
+struct FlashRowsSplitGeom {
+  int nfrag, nwg, fpw;  // fragments of a kv head, workgroups they take, fragments (waves) per workgroup
+};
+__host__ __device__ inline FlashRowsSplitGeom flash_rows_split_geom(int G, int rows) {
+  const int nfrag = G * ((rows + 15) / 16), nwg = (nfrag + 7) / 8;
+  return FlashRowsSplitGeom{nfrag, nwg, (nfrag + nwg - 1) / nwg};
+}
+#define FLASH_ROWS_MAX_SLICES 32
+__host__ __device__ inline size_t flash_rows_part_floats(int slices, int rows, int n_heads, int hd) {
+  return (size_t)slices * rows * n_heads * (hd + 2);
+}
+// (both kernels keep their f32 vector arithmetic -- the accumulator rescale -- on the one-value VALU forms)
+#define FLASH_ROWS_SPLIT_TARGET __attribute__((target("no-packed-fp32-ops")))
+// the staging of one workgroup's K / V tiles: global -> registers (issue) -> LDS (commit)
+template <int HD>
+struct FrsTiles {
+  static constexpr int BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD, PIECES = BN * HD / 8, NPR = PIECES / 256;
+  const unsigned short *kb, *vb;
+  unsigned short *vt0, *kt0;
+  int seq_cap, last_wg, tid, nthr;
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void fetch(int tile, int piece, i32x4& kk, i32x4& vv) const {
+    const int pr = piece / (HD / 8), pc = piece % (HD / 8);
+    int pos = tile * BN + pr;
+    pos = pos < seq_cap ? pos : seq_cap - 1;  // (past the cache only in its last tile; those positions are dead)
+    kk = *(const i32x4*)(kb + (size_t)pos * HD + 8 * pc);
+    vv = *(const i32x4*)(vb + (size_t)pos * HD + 8 * pc);
+  }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void place(int buf, int tile, int piece, const i32x4& kk, const i32x4& vv) const {
+    unsigned short* vt = vt0 + buf * HD * VSTR;
+    unsigned short* kt = kt0 + buf * BN * KSTR;
+    const int pr = piece / (HD / 8), pc = piece % (HD / 8);
+    // positions no row of the workgroup sees hold whatever the allocator or an earlier sequence left in the cache: their
+    // probabilities are exactly 0, but 0 x NaN / Inf is not -- V enters the product as zeros there (K: the scores are masked)
+    const bool live = tile * BN + pr <= last_wg;
+    *(i32x4*)(kt + pr * KSTR + 8 * pc) = kk;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const unsigned w = live ? (unsigned)vv[i] : 0u;
+      vt[(8 * pc + 2 * i) * VSTR + pr] = (unsigned short)(w & 0xffffu);
+      vt[(8 * pc + 2 * i + 1) * VSTR + pr] = (unsigned short)(w >> 16);
+    }
+  }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void issue(int tile, i32x4 (&kreg)[NPR], i32x4 (&vreg)[NPR]) const {
+#pragma unroll
+    for (int u = 0; u < NPR; u++)
+      if (tid + nthr * u < PIECES) fetch(tile, tid + nthr * u, kreg[u], vreg[u]);
+  }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void commit(int buf, int tile, const i32x4 (&kreg)[NPR], const i32x4 (&vreg)[NPR]) const {
+#pragma unroll
+    for (int u = 0; u < NPR; u++)
+      if (tid + nthr * u < PIECES) place(buf, tile, tid + nthr * u, kreg[u], vreg[u]);
+    for (int piece = tid + nthr * NPR; piece < PIECES; piece += nthr) {  // fewer than 4 waves: the rest of the tile, fetched here
+      i32x4 kk, vv;
+      fetch(tile, piece, kk, vv);
+      place(buf, tile, piece, kk, vv);
+    }
+  }
+};
+template <int HD>
+FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(512) void k_attn_flash_rows_split(const float* __restrict__ q, const unsigned short* __restrict__ kc,
+                                                               const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
+                                                               float* __restrict__ part, int n_heads, int n_kv, int seq_cap, int B, int S) {
+  constexpr int KS = HD / 32, DT = HD / 16, BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD;
+  constexpr int PIECES = BN * HD / 8, NPR = PIECES / 256;  // 16-byte pieces of a K (or V) tile; of them in registers per thread
+  extern __shared__ __attribute__((aligned(16))) unsigned short fr_lds[];
+  unsigned short* vt0 = fr_lds;
+  unsigned short* kt0 = fr_lds + 2 * HD * VSTR;
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6;
+  const int n = lane & 15, g = lane >> 4;
+  const int G = n_heads / n_kv, j = blockIdx.y, s = blockIdx.z;
+  const FlashRowsSplitGeom ge = flash_rows_split_geom(G, B);
+  const int pos0 = *pos_d;
+  // this wave's fragment (a wave past the kv head's last fragment stages tiles and computes nothing)
+  const int f0 = blockIdx.x * ge.fpw, f1 = f0 + ge.fpw < ge.nfrag ? f0 + ge.fpw : ge.nfrag;
+  if (f0 >= f1) return;  // (workgroup-uniform; flash_rows_split_geom leaves no workgroup empty)
+  const bool owner = f0 + wave < f1;
+  const int f = owner ? f0 + wave : f1 - 1;
+  const int head = j * G + f % G, row_w = (f / G) * 16;
+  const int row = row_w + n < B ? row_w + n : B - 1;  // (rows past the batch recompute the last row; never stored)
+  f16x8 qb[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ks++) {
+    const f32x4* qp = (const f32x4*)(q + ((size_t)row * n_heads + head) * HD + 32 * ks + 8 * g);
+    const f32x4 a = qp[0], b = qp[1];
+    qb[ks] = f16x8{(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3], (_Float16)b[0], (_Float16)b[1], (_Float16)b[2], (_Float16)b[3]};
+  }
+  const unsigned short* kb = kc + (size_t)j * seq_cap * HD;
+  const unsigned short* vb = vc + (size_t)j * seq_cap * HD;
+  const int rlast_wg = ((f1 - 1) / G) * 16 + 15;                     // the workgroup's fragments are row-block major: its last one's rows
+  const int last_wg = pos0 + (rlast_wg < B ? rlast_wg : B - 1);      // last cached position any row of the workgroup sees
+  const int last_w = pos0 + (row_w + 15 < B ? row_w + 15 : B - 1);   // ... any row of this wave
+  const int my_last = pos0 + row;                                    // ... this lane's row
+  const int NT = (pos0 + B - 1) / BN + 1;                            // tiles of the pass
+  const int t0 = (int)((long long)s * NT / S), t1s = (int)((long long)(s + 1) * NT / S);
+  const int t1 = t1s < last_wg / BN + 1 ? t1s : last_wg / BN + 1;   // (t1 <= t0: the workgroup sees nothing of the slice)
+  f32x4 acc[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; dt++) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, lsum = 0.f;
+  i32x4 vreg[NPR], kreg[NPR];
+  const FrsTiles<HD> tl{kb, vb, vt0, kt0, seq_cap, last_wg, tid, nthr};
+  if (t0 < t1) {
+    tl.issue(t0, kreg, vreg);
+    tl.commit(0, t0, kreg, vreg);
+  }
+  __syncthreads();
+  for (int tile = t0; tile < t1; tile++) {
+    const int buf = (tile - t0) & 1;
+    const unsigned short* vt = vt0 + buf * HD * VSTR;
+    const unsigned short* kt = kt0 + buf * BN * KSTR;
+    if (tile + 1 < t1) tl.issue(tile + 1, kreg, vreg);
+#pragma unroll
+    for (int c2 = 0; c2 < 2; c2++) {
+      // k_attn_flash_rows' 32-position step: two 16-position chunks a / b, two independent S^T chains, one agreement on the running
+      // maximum, the second product on 16x16x32 with k-slot (g, i) = position 4 g + i of chunk a, (g, 4 + i) = the same of chunk b
+      const int ca0 = tile * BN + 32 * c2, cb0 = ca0 + 16;
+      if (owner && ca0 <= last_w) {  // wave-uniform: some row of this wave sees the step
+        f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) {
+          sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + (32 * c2 + n) * KSTR + 32 * ks + 8 * g), qb[ks], sa, 0, 0, 0);
+          sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + (32 * c2 + 16 + n) * KSTR + 32 * ks + 8 * g), qb[ks], sb, 0, 0, 0);
+        }
+        float cm = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {  // causal mask (also: dead cache rows, whatever they hold)
+          if (ca0 + 4 * g + i > my_last) sa[i] = -INFINITY;
+          if (cb0 + 4 * g + i > my_last) sb[i] = -INFINITY;
+          cm = fmaxf(cm, fmaxf(sa[i], sb[i]));
+        }
+        cm = fmaxf(cm, __shfl_xor(cm, 16));
+        cm = fmaxf(cm, __shfl_xor(cm, 32));
+        // (a row that has seen nothing of the slice yet: m = mn = -inf, alpha = 1, p = 0)
+        const float mn = fmaxf(m, cm);
+        if (__any(mn > m)) {  // the running maximum of some row moved: rescale (rare after the first steps)
+          const float alpha = mn == -INFINITY ? 1.0f : __expf(m - mn);
+          lsum *= alpha;
+#pragma unroll
+          for (int dt = 0; dt < DT; dt++) acc[dt] = acc[dt] * alpha;
+          m = mn;
+        }
+        f16x8 pT;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const _Float16 pa = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sa[i] - m);
+          const _Float16 pb = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sb[i] - m);
+          pT[i] = pa;
+          pT[4 + i] = pb;
+          lsum += (float)pa + (float)pb;  // the normalizer sums what the second product multiplies
+        }
+#pragma unroll
+        for (int dt = 0; dt < DT; dt++) {
+          const unsigned short* vr = vt + (16 * dt + n) * VSTR + 32 * c2 + 4 * g;
+          const f16x4 va = *(const f16x4*)vr, vb2 = *(const f16x4*)(vr + 16);
+          const f16x8 vf = {va[0], va[1], va[2], va[3], vb2[0], vb2[1], vb2[2], vb2[3]};
+          acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pT, acc[dt], 0, 0, 0);
+        }
+      }
+    }
+    if (tile + 1 < t1) tl.commit(buf ^ 1, tile + 1, kreg, vreg);  // those buffers were last read one tile ago (barrier below)
+    __syncthreads();
+  }
+  lsum += __shfl_xor(lsum, 16);
+  lsum += __shfl_xor(lsum, 32);
+  if (owner && row_w + n < B) {  // C layout: acc[dt][i] = O^T[dim 16 dt + 4 g + i][row n]
+    const size_t rec = ((size_t)s * B + row_w + n) * n_heads + head;
+    float* o = part + rec * HD;
+#pragma unroll
+    for (int dt = 0; dt < DT; dt++) *(f32x4*)(o + 16 * dt + 4 * g) = acc[dt];
+    if (g == 0) {
+      float* ml = part + (size_t)S * B * n_heads * HD + rec * 2;
+      ml[0] = m;
+      ml[1] = lsum;
+    }
+  }
+}
+
+// The merge of k_attn_flash_rows_split's partials: one workgroup per (row, head), one thread per output dim; the decode merge's
+// operation (k_attn_flash_merge) over the S slices the launch before it wrote, in slice order.
+template <int HD>
+FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(HD) void k_attn_flash_rows_merge(const float* __restrict__ part, float* __restrict__ out, int n_rec, int S) {
+  const int rec = blockIdx.x, d = threadIdx.x;
+  const float* ml = part + (size_t)S * n_rec * HD;
+  float M = -INFINITY;
+  for (int s = 0; s < S; s++) M = fmaxf(M, ml[((size_t)s * n_rec + rec) * 2]);
+  float o = 0.f, L = 0.f;
+  for (int s = 0; s < S; s++) {
+    const size_t r = (size_t)s * n_rec + rec;
+    const float ms = ml[r * 2], w = ms == -INFINITY ? 0.0f : __expf(ms - M);
+    L = __builtin_fmaf(ml[r * 2 + 1], w, L);
+    o = __builtin_fmaf(part[r * HD + d], w, o);
+  }
+  out[(size_t)rec * HD + d] = o / L;
+}
+
 // ---- batched-prefill attention: one workgroup = one kv head x R consecutive prompt rows x the G q heads of its
 // group (Q = G * R queries).  Per (row, head) the arithmetic is k_attn's, value for value -- f32 dots in k order,
 // softmax_row's table exp / sequential row sum (rows up to 1024 positions; longer prompts use k_attn) / true

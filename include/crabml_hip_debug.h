@@ -92,6 +92,17 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
 int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
                                           size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, float* out);
 
+/* The split-KV form of that attention (k_attn_flash_rows_split + k_attn_flash_rows_merge: what a short pass deep in the cache runs) by
+ * itself, its two launches with a forced slice count.  Arguments and host-pointer conventions as above; slices >= 1, clamped to the
+ * pass's 64-position tiles ((pos0 + rows - 1) / 64 + 1) and to 32; n_heads / n_kv from 1 to 8.  The partials scratch holds 0xFF bytes
+ * before the first launch, so a partial the merge reads and the first launch did not write shows as NaN in out.  Blocks. */
+int crabml_hip_debug_flash_attention_rows_split(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
+                                                size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, size_t slices, float* out);
+/* The slice count the prompt pass picks on this device for a pass of `rows` rows at pos0 that runs the flash-rows family (n_heads /
+ * n_kv: the context's local head counts): 1 = k_attn_flash_rows as one launch, more = the split-KV form with that many slices.  Returns
+ * the count itself (>= 1), 0 for a null device; no device work. */
+int crabml_hip_debug_flash_rows_slices(crabml_hip_device_t* dev, size_t n_heads, size_t n_kv, size_t rows, size_t pos0);
+
 /* The decode step's sampler (crabml_hip_llama_decode_sample: k_sample_max / k_sample_keys / k_sample_pick, or the arg-max
  * kernels at temperature 0) on n arbitrary f32 logits (host pointer) with one coin, on this device's tier (strict order:
  * the reference's token bit for bit).  Same argument checks and errors as decode_sample.  Blocks. */
@@ -137,7 +148,13 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
                                                       devices, tensor parallelism, matmul_vec, shorter passes and decode ignore it;
                                                       CRABML_HIP_LLAMA_PREFILL_INT8_GEMM overrides it.  Declared here because the public
                                                       header holds its eight flag bits already; tools/generate.py --q5k-gemm sets it */
-#define CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K 268435456 /* test hook: crabml_hip_llama_debug_prefill_tap also serves contexts whose layer
+#define CRABML_HIP_LLAMA_NO_FLASH_ROWS_SPLIT 1073741824 /* A/B (NOT bit-identical): every prompt pass of the flash-rows family runs k_attn_flash_rows as
+                                                          one launch.  Off (the default), a pass whose one-launch grid leaves the device
+                                                          under-filled and that ends deep in the cache runs the split-KV form
+                                                          (k_attn_flash_rows_split + its merge: the same arithmetic per tile, the partials of
+                                                          the position slices merged in f32; both forms within the launch pins' FLASH_ROWS_REL
+                                                          of float64).  With the flag a context chooses exactly as it did before that form existed */
+#define CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K 268435456/* test hook: crabml_hip_llama_debug_prefill_tap also serves contexts whose layer
                                                          matrices or classifier are Q2_K / Q3_K (the checker restates their kernels:
                                                          tests/q23k_f16w_ref.py).  Off, the tap refuses such a context with
                                                          NOT_IMPLEMENTED, as it always has.  Changes nothing the pass computes */
@@ -356,7 +373,7 @@ enum {
   CRABML_HIP_PFPLAN_DOWN_F = 21,     /*   ffn_down; all 0 in an int8 / GEMV pass */
   CRABML_HIP_PFPLAN_DOWN_T = 22,
   CRABML_HIP_PFPLAN_DOWN_KSPLIT = 23,
-  CRABML_HIP_PFPLAN_ATTN_KERNEL = 24,/* 1 k_attn_flash_rows, 2 the exact tile kernel, 3 the exact long-row kernels, 4 k_attn per (head, row) */
+  CRABML_HIP_PFPLAN_ATTN_KERNEL = 24,/* 1 the flash-rows family (k_attn_flash_rows, or its split-KV form), 2 the exact tile kernel, 3 the exact long-row kernels, 4 k_attn per (head, row) */
   CRABML_HIP_PFPLAN_KERNEL_Q = 25,   /* the kernel each matrix of the layer took: 1 k_gemm_f16w, 2 the int8 matrix-core GEMM (k_gemm_mfma*), 3 the */
   CRABML_HIP_PFPLAN_KERNEL_K = 26,   /*   wave-per-row GEMV, row by row.  One word per matrix: a launch_gemm_f16w that declines falls through to */
   CRABML_HIP_PFPLAN_KERNEL_V = 27,   /*   launch_gemv, which takes the int8 GEMM from 16 rows where the format has one.  PLAN_F16W says what the */

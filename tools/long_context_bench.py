@@ -1,13 +1,15 @@
 """Contexts of 32768 positions on the fused decode step: decode and prompt rates deep in the cache, against the per-op runner (the
 only way a build without them serves such a context) and against a context at the old create-time bound.
 Usage: python tools/long_context_bench.py [--runs llama3-8b:Q4_0,llama3-8b:Q4_K,qwen2.5-7b:Q4_0] [--sections decode,prompt,short,memory,baseline]
-                                          [--seq-len 32768] [--at 4096,16000,24576,32760] [--baseline-to 32768] [--baseline-budget SECONDS] [--baseline-mode per-op|lazy] [--tree DIR]
+                                          [--seq-len 32768] [--at 4096,16000,24576,32760] [--short-ends 128,512,...] [--baseline-to 32768] [--baseline-budget SECONDS] [--baseline-mode per-op|lazy] [--tree DIR]
 Synthetic weights, f16 KV cache, one process.  Per SHAPE:FORMAT, markdown rows:
   decode    crabml_hip_llama_decode_greedy tok/s at each --at position of a --seq-len context (cache filled by prefill; 64 steps, 8 at
             the cache's end; median of 3)
   prompt    prefill tok/s of a prompt of --seq-len tokens (second of two runs)
-  short     one 32-row pass at pos0 = 30000 against the same pass at pos0 = 96 (median of 5): the difference is what its attention
-            (k_attn_flash_rows: n_heads workgroups walking ~470 tiles each) costs -- the prompt pass's launches carry no event pairs
+  short     32-row and 64-row passes that end at each --short-ends position, in a context created with
+            CRABML_HIP_LLAMA_NO_FLASH_ROWS_SPLIT (k_attn_flash_rows as one launch: n_heads workgroups walking every tile) and in a default
+            context (the split-KV form where flash_rows_slices picks it), alternating pass by pass: median of 5 [min .. max].  The pass
+            that ends at 128 is the shallow one: the difference to it is what the attention costs at depth
   memory    crabml_hip_device_mem_in_use before and after the context is created and after its first prompt pass (taken first: the
             pool keeps the blocks that earlier contexts of the process freed)
   baseline  Llama2Runner<HipTensor> on a per-op device (one launch per Tensor call) at --seq-len, token by token from position 0 to
@@ -62,20 +64,28 @@ def prompt_rate(ca, dev, conf, w, seq):
     return seq / timed(lambda: r.prefill(prompt))
 
 
-def short_pass(ca, dev, conf, w, seq, deep=30000, shallow=96, rows=32):
-    r = ca.HipLlamaRunner(conf, w, dev, seq, True)
+NO_FLASH_ROWS_SPLIT = 1073741824  # CRABML_HIP_LLAMA_NO_FLASH_ROWS_SPLIT
+
+
+def short_pass(ca, dev, conf, w, seq, rows, ends):
+    """-> {end: ([seconds, flag set: one launch], [seconds, default: split-KV where flash_rows_slices says so])}: five passes of `rows`
+    rows each, the first ending at `end`, the two contexts alternating pass by pass"""
+    runners = [ca.HipLlamaRunner(conf, w, dev, seq, True, extra_flags=f) for f in (NO_FLASH_ROWS_SPLIT, 0)]
     prompt = [(11 * i + 5) % conf.vocab_size for i in range(seq)]
     out = {}
-    for pos0 in (shallow, deep):
-        r.reset()
-        r.prefill(prompt[:pos0])
-        r.prefill(prompt[pos0:pos0 + rows])  # warm: the pass's buffers and kernels
-        ts = []
-        for i in range(1, 6):
-            dev.sync()
-            ts.append(timed(lambda: r.prefill(prompt[pos0 + i * rows:pos0 + (i + 1) * rows])))
-        out[pos0] = statistics.median(ts)
-    return out[shallow], out[deep]
+    for end in ends:
+        pos0 = end - rows
+        for r in runners:
+            r.reset()
+            r.prefill(prompt[:pos0 - rows])
+            r.prefill(prompt[pos0 - rows:pos0])  # warm: the pass's buffers and kernels
+        ts = ([], [])
+        for i in range(5):
+            for r, t in zip(runners, ts):
+                dev.sync()
+                t.append(timed(lambda: r.prefill(prompt[pos0 + i * rows:pos0 + (i + 1) * rows])))
+        out[end] = ts
+    return out
 
 
 def memory(ca, dev, conf, w, model, seq):
@@ -126,6 +136,8 @@ def main():
     ap.add_argument("--sections", default="memory,decode,prompt,short")
     ap.add_argument("--seq-len", type=int, default=32768)
     ap.add_argument("--at", default="4096,16000,24576,32760")
+    ap.add_argument("--short-ends", type=lambda v: [int(x) for x in v.split(",")], default=[128, 512, 1024, 2048, 4096, 8192, 30000],
+                    help="the position at which the first of a short leg's five passes ends")
     ap.add_argument("--baseline-to", type=int, default=32768)
     ap.add_argument("--baseline-budget", type=float, default=0.0, help="seconds after which the per-op token loop ends (0: never)")
     ap.add_argument("--baseline-mode", default="per-op", choices=["per-op", "lazy"],
@@ -152,10 +164,15 @@ def main():
             print(head + " decode tok/s | " + " | ".join("@%d %.1f" % (p, d[p]) for p in at) + " |", flush=True)
         if "prompt" in sections:
             print(head + " prompt of %d tokens | %.0f tok/s |" % (seq, prompt_rate(ca, dev, conf, w, seq)), flush=True)
-        if "short" in sections and seq >= 30000 + 6 * 32:
-            t0, t1 = short_pass(ca, dev, conf, w, seq)
-            print(head + " 32-row pass | at pos0 96: %.2f ms | at pos0 30000: %.2f ms | attention's share at depth %.0f %% |"
-                  % (t0 * 1e3, t1 * 1e3, 100 * (t1 - t0) / t1), flush=True)
+        if "short" in sections:
+            s = model.shape
+            for rows in (32, 64):
+                ends = [e for e in a.short_ends if 2 * rows < e and e + 5 * rows <= seq]
+                for end, (off, on) in short_pass(ca, dev, conf, w, seq, rows, ends).items():
+                    ms = lambda t: "%.3f ms [%.3f .. %.3f]" % (statistics.median(t) * 1e3, min(t) * 1e3, max(t) * 1e3)  # noqa: E731
+                    print(head + " %d-row pass ending at %d | one launch: %s | default (%d slices): %s | one launch / default %.2f |"
+                          % (rows, end, ms(off), dev.debug_flash_rows_slices(s.n_heads, s.n_kv_heads, rows, end - rows), ms(on),
+                             statistics.median(off) / statistics.median(on)), flush=True)
         del w, dev
         gc.collect()
         if "baseline" in sections:
