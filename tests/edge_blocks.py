@@ -273,7 +273,7 @@ def dequant_f64(raw, fmt):
     once (products of an 11-bit scale, a 6- or 8-bit sub-scale and a level fit f32; the roundings are Q4_1 / Q5_1 n d + m, the K-quant
     n d sc - dmin m, Q6_K's 25-bit product, Q8_K's f32 d times q).  Q4_1: the reference's OWN dequantize writes the nibbles
     interleaved (buf_q4_1.rs:19-30) while its vec_dot pairs them in element order; this is element order."""
-    from tests.test_hip_f16w_gemm import weight_operands
+    from tests.f16w_gemm_ref import weight_operands
     from tests.test_hip_kquant_ints import scale_min_k4
     typ = synth.TYPE_BY_NAME[fmt]
     bb = o.BLOCK_BYTES[typ]

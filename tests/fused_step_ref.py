@@ -88,11 +88,8 @@ import numpy as np
 
 from crabml_amd import synth
 from oracle import oracle as o
-from tests.helpers import GEMV_REL
+from tests.weight_formats import C_DOT, C_K, FAMILY, FORMATS, U, _u16, chunk_dots, f16v, k_values, weight_rows  # noqa: F401
 
-U = 2.0 ** -24
-C_DOT = 3
-C_K = 3      # K-quant row dots: see the module docstring
 EXCUSED_CAP = 0.20
 FLASH_REL = 2e-5  # tests/test_hip_flash_attention.py: k_attn_flash against float64 on the same f16 inputs, of max|out|
 
@@ -138,28 +135,33 @@ def shrink_residual(model, log2=7):
     0.5 * eps / (mean square + eps) relative.  The synthetic models' residual stream has a mean square of 0.3 .. 200: taking 1e-6 for
     1e-5 there changes 1 / rms by 1.3e-5 at the low end (about 250 f32 ulps), by one ulp near 40 and by nothing from ~75 on --
     mostly inside what re-association alone may do to a row dot.  On the shrunk model (mean square 2e-5 .. 1e-2) it is 3e-4 .. 0.2:
-    the model on which a wrong eps cannot pass in any launch."""
+    the model on which a wrong eps cannot pass in any launch.  (Where the f16 scales of a format sit: tests/weight_formats.py.)"""
     f = np.float16(2.0 ** -log2)
     for name, t in model.tensors.items():
         if not (name == "token_embd.weight" or name.endswith("attn_output.weight") or name.endswith("ffn_down.weight")):
             continue
-        assert t.typ in (synth.Q4_0, synth.Q8_0, synth.Q4_1, synth.Q4_K, synth.Q6_K), name
+        assert t.typ in FORMATS, name
         blk = t.data.reshape(-1, synth.BLOCK_BYTES[t.typ])
-        for lo in {synth.Q4_1: (0, 2), synth.Q4_K: (0, 2), synth.Q6_K: (208,)}.get(t.typ, (0,)):  # d | m; d | dmin; Q6_K's d behind the quants
+        for lo in FORMATS[t.typ].scales_at:  # d; d | m; d | dmin
             d = blk[:, lo:lo + 2].copy().view(np.float16)
             blk[:, lo:lo + 2] = (d * f).astype(np.float16).view(np.uint8)
     return model
 
 
+def flip_signs(model, seed=5):
+    """block scales of either sign: the sign bit of every f16 block scale of every quantized tensor, each field its own draw (Q4_1's
+    and Q5_1's m stay as they are: d and m no longer tied)"""
+    rng = np.random.default_rng(seed)
+    for t in model.tensors.values():
+        F = FORMATS.get(t.typ)
+        at = () if F is None else (F.scales_at if F.signs_at is None else F.signs_at)
+        blk = t.data.reshape(-1, synth.BLOCK_BYTES[t.typ]) if at else None
+        for lo in at:
+            blk[:, lo + 1] ^= (rng.integers(0, 2, size=blk.shape[0], dtype=np.uint8) << 7)
+    return model
+
+
 # ---- block byte layouts (the reference's: buf_q8_0.rs:8-13, buf_q8_1.rs:73-79, buf_q8_k.rs:6-12, buf_q4_0.rs, buf_q4_1.rs, buf_q6_k.rs) ----
-def f16v(bits):
-    return np.ascontiguousarray(bits).view(np.float16).astype(np.float64)
-
-
-def _u16(b):
-    return np.ascontiguousarray(b).view(np.uint16)[..., 0]
-
-
 def parse_act(raw, qt):
     """activation blocks -> dict(d [nb] f64, q [nb, be] int64, s [nb] f64 (Q8_1), d_bits)"""
     raw = np.ascontiguousarray(raw).view(np.uint8)
@@ -208,143 +210,11 @@ def act_values(a):
     return (a["q"] * a["d"][:, None]).reshape(-1)
 
 
-def weight_rows(t, r0, r1):
-    """rows [r0, r1) of a weight tensor (synth.RawTensor) -> per-format dict of exact integer / f64 fields, [rows, nb, ...]"""
-    rows, k = t.shape
-    typ = t.typ
-    bb, be = synth.BLOCK_BYTES[typ], synth.BLOCK_ELEMS[typ]
-    nb = k // be
-    b = np.ascontiguousarray(t.data).view(np.uint8).reshape(rows, nb, bb)[r0:r1]
-    if typ == synth.Q8_0:
-        return {"typ": typ, "d": f16v(_u16(b[:, :, 0:2])), "q": np.ascontiguousarray(b[:, :, 2:]).view(np.int8).astype(np.float64)}
-    if typ in (synth.Q4_0, synth.Q4_1):
-        qs = b[:, :, (2 if typ == synth.Q4_0 else 4):]
-        nib = np.concatenate([qs & 0x0F, qs >> 4], axis=2).astype(np.float64)  # element j < 16: low nibble of byte j; j >= 16: high nibble of byte j - 16
-        w = {"typ": typ, "d": f16v(_u16(b[:, :, 0:2]))}
-        if typ == synth.Q4_0:
-            w["q"] = nib - 8.0
-        else:
-            w["q"] = nib
-            w["m"] = f16v(_u16(b[:, :, 2:4]))
-        return w
-    if typ == synth.Q6_K:  # ql[128] | qh[64] | scales i8[16] | d f16 (buf_q6_k.rs:11-18); element order of dequantize (buf_q6_k.rs:93-120)
-        ql, qh = b[:, :, 0:128].astype(np.int64), b[:, :, 128:192].astype(np.int64)
-        sc = np.ascontiguousarray(b[:, :, 192:208]).view(np.int8).astype(np.float64)
-        q = np.empty(b.shape[:2] + (256,), dtype=np.float64)
-        scale = np.empty_like(q)
-        for half in range(2):
-            lq, hq = ql[:, :, 64 * half:64 * half + 64], qh[:, :, 32 * half:32 * half + 32]
-            for j, (lo, sh) in enumerate(((lq[:, :, 0:32] & 0xF, 0), (lq[:, :, 32:64] & 0xF, 2), (lq[:, :, 0:32] >> 4, 4), (lq[:, :, 32:64] >> 4, 6))):
-                base = 128 * half + 32 * j
-                q[:, :, base:base + 32] = (lo | (((hq >> sh) & 3) << 4)) - 32
-                for g in range(2):
-                    scale[:, :, base + 16 * g:base + 16 * g + 16] = sc[:, :, 8 * half + 2 * j + g][:, :, None]
-        return {"typ": typ, "d": f16v(_u16(b[:, :, 208:210])), "q": q * scale, "q6": q, "sc": sc}
-    if typ == synth.Q4_K:  # d f16 | dmin f16 | scales[12] | qs[128] (buf_q4_k.rs:13-19); the 6-bit fields: util.rs:19-27; order: buf_q4_k.rs:24-47
-        s12 = b[:, :, 4:16].astype(np.int64)
-        sc, mn = np.empty(b.shape[:2] + (8,)), np.empty(b.shape[:2] + (8,))
-        for j in range(4):
-            sc[:, :, j], mn[:, :, j] = s12[:, :, j] & 63, s12[:, :, j + 4] & 63
-            sc[:, :, j + 4] = (s12[:, :, j + 8] & 0xF) | ((s12[:, :, j] >> 6) << 4)
-            mn[:, :, j + 4] = (s12[:, :, j + 8] >> 4) | ((s12[:, :, j + 4] >> 6) << 4)
-        qs = b[:, :, 16:144].reshape(b.shape[0], b.shape[1], 4, 32)
-        q = np.stack([qs & 0x0F, qs >> 4], axis=3).reshape(b.shape[0], b.shape[1], 256).astype(np.float64)  # pair p: 32 low nibbles, 32 high
-        return {"typ": typ, "d": f16v(_u16(b[:, :, 0:2])), "dmin": f16v(_u16(b[:, :, 2:4])), "sc": sc, "mn": mn, "q": q}
-    raise ValueError(f"weight type {typ}")
-
-
-def k_values(w):
-    """the dequantized elements of K-quant weight rows (weight_rows), f64, [rows, nsb * 256] -- sum |w_i x_i| of the project's bound"""
-    if w["typ"] == synth.Q6_K:
-        return (w["q"] * w["d"][:, :, None]).reshape(w["q"].shape[0], -1)
-    r, nsb = w["d"].shape
-    v = (w["d"][:, :, None] * w["sc"])[:, :, :, None] * w["q"].reshape(r, nsb, 8, 32) - (w["dmin"][:, :, None] * w["mn"])[:, :, :, None]
-    return v.reshape(r, -1)
-
-
-def k_pieces(w, act, wrong=None):
-    """Q4_K / Q6_K weight rows (weight_rows) against one row's Q8_K blocks: per piece of every row (the kernels' 16-byte unit, 8 per
-    super-block) the exact term and the magnitude A its roundings act on -> (terms, A), each [rows, nsb, 8].  wrong: a kernel that is
-    subtly wrong in the named way (the checker's own tests)"""
-    typ = w["typ"]
-    r, nsb = w["d"].shape
-    d8, bs = act["d"], act["bsums"].astype(np.float64)
-    assert d8.size == nsb, (d8.size, nsb)
-    if typ == synth.Q4_K:
-        # a lane's piece (pair p, class half h) takes, of either 32-group of the pair, the elements e with e % 8 in 4 h .. 4 h + 3 (dwords
-        # 4 h .. of the class-major planes: q4k_loadx / q4k_ints): [32-group g, e / 8, class half h, class within the half]
-        x = act.get("qp_q", act["q"]).astype(np.float64).reshape(nsb, 8, 4, 2, 4)
-        S = np.einsum("rsgahi,sgahi->rsgh", w["q"].reshape(r, nsb, 8, 4, 2, 4), x)
-        sc, mn = w["sc"].copy(), w["mn"].copy()
-        if wrong == "scale_neighbour":
-            sc[:, 0, 2] = w["sc"][:, 0, 3]
-        if wrong == "min_neighbour":
-            mn[:, 0, 2] = w["mn"][:, 0, 3]
-        T = sc[:, :, :, None] * S
-        # (the minimum term only needs every bsums entry once per super-block: piece (p, h) takes entries 4 p + h and 4 p + 2 + h, the
-        # CONTIGUOUS halves h of its two groups, as q4k_loadx does)
-        M = mn[:, :, :, None] * bs.reshape(nsb, 8, 2)[None]
-        isum, msum = T[:, :, 0::2] + T[:, :, 1::2], M[:, :, 0::2] + M[:, :, 1::2]  # piece (pair p, half h): groups 2 p and 2 p + 1
-        a = (w["d"] * d8[None])[:, :, None, None] * isum
-        b = (w["dmin"] * d8[None])[:, :, None, None] * msum
-        terms = a - b
-        if wrong == "dmin_plus":
-            terms[:, 0, 1, 0] = (a + b)[:, 0, 1, 0]
-        return terms.reshape(r, nsb, 8), (np.abs(a) + np.abs(b)).reshape(r, nsb, 8)
-    assert typ == synth.Q6_K
-    x = act["q"].astype(np.float64).reshape(nsb, 16, 16)
-    # sum (q6 - 32) q8 as the kernel forms it: the 6-bit levels against q8, minus 32 times the bsums entry it read
-    G = np.einsum("rsgi,sgi->rsg", w["q6"].reshape(r, nsb, 16, 16) + 32.0, x) - 32.0 * bs[None]
-    sc = w["sc"]
-    if wrong == "q6_scale_shift":
-        sc = sc.copy()
-        sc[:, 0, 5] = w["sc"][:, 0, 6]
-    G = (sc * G).reshape(r, nsb, 2, 2, 4)  # group 8 h + 4 hi + j; a piece: the low nibbles of group 8 h + j, the high of 8 h + 4 + j
-    dd = (w["d"] * d8[None])[:, :, None, None]
-    return (dd * (G[:, :, :, 0] + G[:, :, :, 1])).reshape(r, nsb, 8), (np.abs(dd) * (np.abs(G[:, :, :, 0]) + np.abs(G[:, :, :, 1]))).reshape(r, nsb, 8)
-
-
-def _chunk_dots(w, typ, act, k, drop_last_block, wrong=None):
-    """(exact, bound) of the weight rows `w` (weight_rows) against one row's activation blocks: row_dots' arithmetic"""
-    if typ == synth.Q4_1:
-        assert act["qt"] == o.Q8_1
-        nb = k // 32
-        keep = np.ones(nb)
-        if drop_last_block:
-            keep[-1] = 0.0
-        xq = act["q"].astype(np.float64)
-        xd = (act["q"] * act["d"][:, None]).astype(np.float64)
-        sumi = np.einsum("rbi,bi->rb", w["q"], xq)
-        P = (w["d"] * act["d"][None, :]).astype(np.float16).astype(np.float64)  # f16 products, rounded once (the exact product fits f64)
-        M = (w["m"] * act["s"][None, :]).astype(np.float16).astype(np.float64)
-        exact = ((P * sumi + M) * keep).sum(axis=1)
-        deq = np.einsum("rbi,bi->r", np.abs(w["q"] * w["d"][:, :, None] + w["m"][:, :, None]), np.abs(xd))
-        terms = (np.abs(P * sumi) + np.abs(M)).sum(axis=1)
-        return exact, np.minimum(8 * GEMV_REL * deq, (nb + C_DOT) * U * terms)
-    if typ in (synth.Q4_K, synth.Q6_K):  # x Q8_K: the bound of the module docstring, (n_terms + C_K) U sum A
-        assert act["qt"] == o.Q8_K
-        terms, A = k_pieces(w, act, wrong)
-        if drop_last_block:  # (a K-quant row's block is a super-block)
-            terms = terms[:, :-1]
-        return terms.sum(axis=(1, 2)), (A.shape[1] * 8 + C_K) * U * A.sum(axis=(1, 2))
-    # Q4_0 / Q8_0 x Q8_0: products of exact small integers and f16 scales
-    x = act_values(act)
-    assert x.size == k, (x.size, k)
-    if drop_last_block:
-        x = x.copy()
-        x[-32:] = 0.0
-    nblk = k // 32
-    x3 = x.reshape(nblk, 32)
-    wd = (w["q"] * w["d"][:, :, None]).reshape(w["q"].shape[0], nblk, 32)  # exact in f64
-    terms = np.einsum("rbi,bi->rb", wd, x3)
-    return terms.sum(axis=1), (nblk + C_DOT) * U * np.abs(terms).sum(axis=1)
-
-
 def row_dots(t, act, chunk=256, drop_last_block=False, wrong=None):
     """W . x for every row of t against the activation blocks `act`: (exact f64 [rows], bound f64 [rows]) -- the bound of the module
     docstring for an f32 evaluation of the reference's block expression in ANY order of the blocks.  drop_last_block: the dot
     without each row's last 32 elements (a K-quant row's: last super-block), what a kernel whose block loop stops one early computes;
-    wrong: the name of another wrong kernel of k_pieces (both: the checker's own tests)"""
+    wrong: the name of another wrong kernel or loader of the tensor's format (tests/weight_formats.py; both: the checker's own tests)"""
     e, b = row_dots_many(t, [act], None, chunk, drop_last_block, wrong)
     return e[0], b[0]
 
@@ -359,10 +229,10 @@ def row_dots_many(t, acts, wrows=None, chunk=256, drop_last_block=False, wrong=N
         at = np.flatnonzero((sel >= r0) & (sel < r0 + chunk))
         if at.size == 0:
             continue
-        w = weight_rows(t, r0, min(rows, r0 + chunk))
+        w = weight_rows(t, r0, min(rows, r0 + chunk), wrong)
         w = {key: (v[sel[at] - r0] if isinstance(v, np.ndarray) else v) for key, v in w.items()}
         for i, act in enumerate(acts):
-            exact[i, at], bound[i, at] = _chunk_dots(w, t.typ, act, k, drop_last_block, wrong)
+            exact[i, at], bound[i, at] = chunk_dots(w, act, drop_last_block, wrong)
     return exact, bound
 
 
@@ -910,7 +780,9 @@ def check_gateup_k(tap, model, l, ctx, twin=None):
 
 
 def check_layer_k(tap, kc_raw, vc_raw, model, l, pos, form, ctx, twin=None, token=None):
-    """every launch of the tapped layer of a K-quant step, in the form the tapped plan words name"""
+    """every launch of the tapped layer of a K-quant step, in the form the tapped plan words name.  Every tensor is read by the row of
+    its OWN format (tests/weight_formats.py), so a model that mixes the K-quants outside every recipe family is read as well: the body,
+    FAMILY and path assertions are check_layer's, which the pin files call, not this function's"""
     s, plan, out = model.shape, tap["plan"], {}
     if "qkv_in.xn" in tap:
         res = out["norm+quantize"] = Result("norm+quantize")
@@ -933,7 +805,16 @@ def check_layer_k(tap, kc_raw, vc_raw, model, l, pos, form, ctx, twin=None, toke
 
 
 def check_layer(tap, kc_raw, vc_raw, model, l, pos, form, ctx, twin=None, token=None):
-    """every launch of the tapped layer (and the classifier) -> {launch: Result}; the step's body from the tapped plan words"""
+    """every launch of the tapped layer (and the classifier) -> {launch: Result}; the step's body from the tapped plan words.  A
+    K-quant body other than Q4_K runs the K-quant step, and a body of a recipe family holds the family's formats where the recipe puts them"""
+    body = model.wtype
+    if body in (synth.Q2_K, synth.Q3_K, synth.Q5_K, synth.Q6_K):
+        assert tap["plan"]["path"] == 2, (body, tap["plan"])
+    if body in FAMILY:
+        for n in ("attn_q", "attn_k", "ffn_gate", "ffn_up"):
+            assert model.tensors[f"blk.{l}.{n}.weight"].typ == body, n
+        for n in ("attn_v", "attn_output", "ffn_down"):
+            assert model.tensors[f"blk.{l}.{n}.weight"].typ in FAMILY[body], n
     if tap.get("plan", {}).get("path") == 2:
         return check_layer_k(tap, kc_raw, vc_raw, model, l, pos, form, ctx, twin, token)
     out = {}

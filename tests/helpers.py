@@ -202,3 +202,78 @@ def read_gguf_py(path):
         nbytes = n // synth.BLOCK_ELEMS[typ] * synth.BLOCK_BYTES[typ]
         model.tensors[name] = synth.RawTensor(raw[start + off:start + off + nbytes], dims, typ)
     return model, kv
+
+
+# ---- the K-quant launch pins (tests/test_hip_q5k_fused.py, ..._q6k_, ..._q3k_, ..._q2k_): one tapped step per (layer, position) ----
+NOT_IMPLEMENTED = 9  # crabml_hip_status
+NO_K_NORM_IN = 16777216
+
+
+def error_kind(ca, call):
+    import pytest
+    with pytest.raises(ca.CrabmlError) as e:
+        call()
+    return int(str(e.value).split("ErrorKind(")[1].split(")")[0])
+
+
+def expect_flash_pow2(model, pos):
+    """k_attn_flash from 96 cached positions on, as the Q5_K / Q6_K / Q3_K files state it: they run GQA groups 1, 2, 4 and 8 that far"""
+    s = model.shape
+    return s.head_dim in (64, 128, 256) and s.n_heads // s.n_kv_heads in (1, 2, 4, 8) and pos + 1 >= 96
+
+
+def run_k_case(ca, key, model, body, seq, positions, layers, record_file, expect_flash=expect_flash_pow2, norm_epilogue=True, flags=0, want_path=2,
+               observed=None):
+    """`body`: the format of the body the calling pin file is about.  A runner is teacher-forced greedily on its own tokens up to `pos` (from the graph), then takes ONE tapped step; the tapped (eager)
+    step's logits equal a graph twin's bit for bit; where gate | up normalizes and quantizes wo's row in LDS a NO_K_NORM_IN twin leaves
+    the planes; every launch goes through tests/fused_step_ref.check_layer, and what it observed into tests/golden/<record_file> (observed:
+    the calling file's dict of entries so far) -> {(layer, pos): the tapped step's launch plan}"""
+    from tests import fused_step_ref as R
+    assert model.wtype == body, (key, model.wtype)
+    observed = {} if observed is None else observed
+    dev = ca.HipTensorDevice(0)
+    conf, w = synth.to_hip(model, dev)
+    mk = lambda fl: ca.HipLlamaRunner(conf, w, dev, seq, True, True, True, norm_epilogue=norm_epilogue, extra_flags=fl)  # noqa: E731
+    r, twin, planes_twin = mk(flags), mk(flags), None
+    fails, plans = [], {}
+    for pos in positions:
+        twin.reset()
+        tok = int(twin.decode_greedy(1, pos)[-1]) if pos else 1
+        want = twin.forward(tok, pos).copy()
+        for layer in layers:
+            ctx = f"{key} layer {layer} pos {pos}"
+            r.reset()
+            if pos:
+                assert int(r.decode_greedy(1, pos)[-1]) == tok, ctx
+            tap = r.debug_tap(tok, pos, layer)
+            assert r.kv_cache_len() == pos + 1
+            plan = plans[(layer, pos)] = tap["plan"]
+            assert plan["path"] == want_path, (ctx, plan)  # enqueue_segment_k
+            flash = plan["attn_variant"] >= 16
+            assert flash == expect_flash(model, pos), (ctx, plan)
+            assert np.array_equal(tap["logits"].view(np.uint32), want.view(np.uint32)), f"{ctx}: the tapped (eager) step's logits differ from the graph's"
+            twin_tap = None
+            if plan["wo_x_only"]:  # gate | up's planes exist in LDS only: the twin whose wo leaves them
+                if planes_twin is None:
+                    planes_twin = mk(flags | NO_K_NORM_IN)
+                planes_twin.reset()
+                if pos:
+                    assert int(planes_twin.decode_greedy(1, pos)[-1]) == tok, ctx
+                twin_tap = planes_twin.debug_tap(tok, pos, layer)
+                assert twin_tap["plan"]["wo_x_only"] == 0 and twin_tap["plan"]["norm_epi_k"] == 1, (ctx, twin_tap["plan"])
+                assert np.array_equal(twin_tap["logits"].view(np.uint32), want.view(np.uint32)), f"{ctx}: the NO_K_NORM_IN twin's logits differ"
+            form = R.Form(defer=False, kv_f16=True, seq_cap=seq, flash_from=pos + 1 if flash else 0)
+            kc, vc = r.debug_kv(layer, False, True), r.debug_kv(layer, True, True)
+            res = R.check_layer(tap, kc, vc, model, layer, pos, form, ctx, twin=twin_tap, token=tok)
+            for name, rr in res.items():
+                print(f"{ctx} {name}: error / bound {rr.worst:.3f} excused {rr.excused}")
+                for pname, share in rr.excused.items():
+                    if share > R.EXCUSED_CAP:
+                        fails.append(f"{ctx} {name}: {pname} excused share {share:.3f} > {R.EXCUSED_CAP}")
+            observed[f"{key}/L{layer}/p{pos}"] = {
+                "error_over_bound": {k: round(rr.worst, 4) for k, rr in res.items()},
+                "excused_share": {k: {n: round(v, 6) for n, v in rr.excused.items()} for k, rr in res.items() if rr.excused}}
+            record_observed(observed, record_file)
+            fails += R.failures(res)
+    assert not fails, "\n".join(fails)
+    return plans

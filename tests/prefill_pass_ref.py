@@ -45,8 +45,8 @@ cls.xn) no K launch needs an interval excuse:
                   sorted multiset per super-block (b_groups of the reading weight's format; n1.xh.v against attn_v's).  The k-slot
                   order itself is held by the GEMM check, which multiplies by A' in element order.
   f16 GEMM        GEMV_REL sum |A' B'| with A' = f16(n c1 - c2), c1 = f16(d sc), c2 = f16(dmin m) (Q4_K), f16((q - 32) f16(d sc)) (Q6_K):
-                  weight_operands of tests/test_hip_f16w_gemm.py.
-  row-by-row GEMV fused_step_ref.row_dots / q5k_step_ref.row_dots: (8 nsb + C_K) U sum A over the kernels' pieces.
+                  weight_operands of tests/f16w_gemm_ref.py (the format's f16w row of tests/weight_formats.py).
+  row-by-row GEMV fused_step_ref.row_dots (the format's rule of tests/weight_formats.py): (8 nsb + C_K) U sum A over the kernels' pieces.
   int8 GEMM       k_gemm_mfma_q4k, per super-block and output: the integers isum = sum_j sc_j dot_j (|isum| <= 256 * 15 * 127 * 63 = 3.1e7,
                   past 2^24: its conversion to f32 ROUNDS) and msum = sum_j m_j bsum_j (<= 8 * 63 * 32 * 127 = 2.0e6: exact), then
                   F += (d_w d8) (float)isum - (dmin_w d8) (float)msum with -ffp-contract=off: 2 conversions (one of which can round), 2
@@ -74,17 +74,17 @@ import numpy as np
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import fused_step_ref as R
-from tests import q5k_step_ref as Q5
 from tests.fused_step_ref import U, Result, check_f32
 from tests.helpers import GEMV_REL
-from tests.test_hip_f16w_gemm import b_groups, weight_operands
+from tests.f16w_gemm_ref import b_groups, weight_operands
+from tests.weight_formats import FORMATS
 
 FLASH_ROWS_REL = 1.5e-3  # tests/test_hip_flash_attention.py: k_attn_flash_rows against float64 on the same f16 inputs, of max|out|
 ATTN_FLASH_ROWS, ATTN_TILE, ATTN_LONG_ROWS, ATTN_PER_ROW = 1, 2, 3, 4  # CRABML_HIP_PFPLAN_ATTN_KERNEL
 KERNEL_F16W, KERNEL_INT8, KERNEL_GEMV = 1, 2, 3  # CRABML_HIP_PFPLAN_KERNEL_*
 KERNEL_WORD = {"attn_q": "kernel_q", "attn_k": "kernel_k", "attn_v": "kernel_v", "attn_output": "kernel_wo", "ffn_gate": "kernel_gate",
                "ffn_up": "kernel_up", "ffn_down": "kernel_down"}
-F16W_FMT = {synth.Q4_0: "Q4_0", synth.Q8_0: "Q8_0", synth.Q4_1: "Q4_1", synth.Q4_K: "Q4_K", synth.Q6_K: "Q6_K"}  # formats k_gemm_f16w takes
+F16W_FMT = {typ: F.name for typ, F in FORMATS.items() if F.f16w}  # formats k_gemm_f16w takes: by name, as tests/f16w_gemm_ref.py asks for them
 
 
 @dataclass
@@ -171,7 +171,8 @@ def norm_intervals(x, w, eps, n):
 
 
 def check_xh(res, tap, xh_name, act_name, ctx, model=None, wname=None):
-    """wname: the weight whose GEMM reads this B' (its format decides the slot groups: a 32-element block, a K-quant super-block)"""
+    """wname: the weight whose GEMM reads this B' (its format decides the slot groups: a Q8_0 / Q8_1-row B' is held to the same multiset
+    per 32-element block, a Q8_K-row B' to the same multiset per super-block of its 256-element reader)"""
     if xh_name not in tap:
         return
     acts = act_rows(tap, act_name)
@@ -180,7 +181,7 @@ def check_xh(res, tap, xh_name, act_name, ctx, model=None, wname=None):
     fmt = "Q4_0"
     if acts[0]["qt"] == o.Q8_K:
         fmt = F16W_FMT.get(_w(model, wname).typ)
-        if fmt not in ("Q4_K", "Q6_K"):
+        if fmt is None or not FORMATS[_w(model, wname).typ].kq:
             res.fails.append(f"{ctx} {res.launch}: {xh_name} is present, but {wname} is of a format the f16 GEMM does not take")
             return
     got = np.asarray(tap[xh_name], dtype=np.uint16).reshape(b, k)
@@ -250,7 +251,7 @@ def kernel_of(tap, wname):
 
 def gemm_reference(tap, model, wname, act_name, sample=None, drop_last_block=False, wrong=None):
     """(exact [rows, m], bound, prompt rows, weight rows) of W . planes for the kernel the plan names for this matrix.
-    drop_last_block / wrong: a kernel that is subtly wrong (the checker's own tests; wrong: fused_step_ref / q5k_step_ref k_pieces)"""
+    drop_last_block / wrong: a kernel that is subtly wrong (the checker's own tests; wrong: the format's row of tests/weight_formats.py)"""
     t = _w(model, wname)
     m, k = t.shape
     acts = act_rows(tap, act_name)
@@ -267,8 +268,7 @@ def gemm_reference(tap, model, wname, act_name, sample=None, drop_last_block=Fal
             bp = bp.copy()
             bp[:, -synth.BLOCK_ELEMS[t.typ]:] = 0.0
         return bp @ ap.T, GEMV_REL * (np.abs(bp) @ np.abs(ap).T) + 1e-30, pr, wr
-    with Q5.q5k_rows():  # (Q5_K rows through q5k_step_ref; every other format dispatches back)
-        e, b = R.row_dots_many(t, acts, wr, drop_last_block=drop_last_block, wrong=wrong)
+    e, b = R.row_dots_many(t, acts, wr, drop_last_block=drop_last_block, wrong=wrong)
     return e, b + 1e-30, pr, wr
 
 
@@ -549,8 +549,7 @@ def check_tail(tap, model, l, ctx):
     else:
         R.QuantIntervals(lo, hi, ref, tap["qtype"]["cls.act"]).check(tap["cls.act"], res, "cls.act", ctx)
     t = model.tensors["output.weight"] if "output.weight" in model.tensors else model.tensors["token_embd.weight"]
-    with Q5.q5k_rows():
-        e, b = R.row_dots(t, act_rows(tap, "cls.act")[0])
+    e, b = R.row_dots(t, act_rows(tap, "cls.act")[0])
     check_f32(res, tap["logits"], e, b + 1e-30, "logits", ctx)
     return res
 

@@ -17,7 +17,6 @@ import pytest
 from crabml_amd import synth
 from tests import fused_step_ref as R
 from tests import prefill_pass_ref as P
-from tests import q5k_step_ref as Q5
 from tests.helpers import record_observed
 from tests.test_hip_fused_k_launches import flip_signs
 from tests.test_hip_fused_launches import SHAPE_8B, SHAPE_WIDE
@@ -236,9 +235,8 @@ def test_mixed_sign_block_fields(ca, fmt):
 @pytest.mark.parametrize("fmt", ["Q4_K_M", "Q5_K_M"])
 def test_shrunk_residual_stream(ca, fmt, n):
     """a residual stream small enough for RMSNorm's eps to matter in every norm launch of either arm (by 2^-9, as the decode pins'
-    device case: fused_step_ref.shrink_residual / q5k_step_ref.shrink_residual)"""
-    shrink = Q5.shrink_residual if fmt == "Q5_K_M" else R.shrink_residual
-    model = shrink(k_model("tiny-gqa", fmt, 72), 9)
+    device case: fused_step_ref.shrink_residual)"""
+    model = R.shrink_residual(k_model("tiny-gqa", fmt, 72), 9)
     plans = case(ca, f"shrunk/tiny-gqa/{fmt}", model, 256, n, [0, 1], sample=P.Sample(extra=8, col_tile=16) if (fmt, n) == ("Q5_K_M", 200) else None)
     for layer, plan in plans.items():
         expect_kernels(plan, model, layer, F16W)

@@ -3,11 +3,11 @@ WF_Q2_K / WF_Q3_K, one B' k-slot order for both), the Q4_K / Q6_K tensors of the
 matrix on the row-by-row GEMV.
 
 Part 1, every launch of a tapped pass (modelled on tests/test_hip_prefill_k_launches.py, through the same run_case and
-tests/prefill_pass_ref.check_pass, which reads the two formats inside q23k_f16w_ref.q23k_pass): plain Q3_K, the Q3_K_S and Q3_K_M
+tests/prefill_pass_ref.check_pass, which reads every format from tests/weight_formats.py): plain Q3_K, the Q3_K_S and Q3_K_M
 recipes, plain Q2_K, the Q2_K recipe and Q2_K_S, on tiny-gqa (GQA group 4: the Q2_K recipe's attn_v is Q4_K) and tiny-hd128 (group 2:
 attn_v is Q3_K).  The launch plan must say k_gemm_f16w for every Q2_K / Q3_K / Q4_K / Q6_K matrix and the GEMV for a Q5_K one, one
 launch for q | k | v and for gate | up where the formats agree, and B' re-made for attn_v only where its k-slot order differs from
-attn_q's.  Every GEMM output is held to GEMV_REL sum |A' B'| with A' restated by tests/q23k_f16w_ref.py.  Observed error / bound
+attn_q's.  Every GEMM output is held to GEMV_REL sum |A' B'| with A' restated by the formats' rows of tests/weight_formats.py.  Observed error / bound
 ratios: tests/golden/prefill_q23k_launch_pins_observed.json (evidence only).
 
 Part 2, end to end against the oracle's token loop, in the form of tests/test_hip_prefill.test_fast_prompt_pass_f16_weight_gemm."""
@@ -17,7 +17,6 @@ import pytest
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import prefill_pass_ref as P
-from tests import q23k_f16w_ref as Q
 from tests.helpers import FAST_TOL, record_observed, to_oracle
 from tests.test_hip_prefill_k_launches import GEMV, F16W, MATS, NORM_ROWS_K, expect_norm
 from tests.test_hip_prefill_launches import INT8_GEMM, POS0_CASES, expect_attn, run_case
@@ -47,8 +46,7 @@ TAP_Q2K_Q3K = 268435456  # CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K: without it the 
 
 
 def case(ca, key, model, seq, n, layers, **kw):
-    with Q.q23k_pass():
-        return run_case(ca, key, model, seq, kw.pop("kv_f16", True), n, layers, rec=record, flags=kw.pop("flags", 0) | TAP_Q2K_Q3K, **kw)
+    return run_case(ca, key, model, seq, kw.pop("kv_f16", True), n, layers, rec=record, flags=kw.pop("flags", 0) | TAP_Q2K_Q3K, **kw)
 
 
 def test_tap_is_opt_in(ca):

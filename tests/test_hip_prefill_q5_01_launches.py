@@ -1,18 +1,18 @@
 """Every launch of one chunk pass of the fast prompt path over Q5_0 / Q5_1 BODIES pinned against float64, launch by launch and ROW BY
-ROW, through tests/test_hip_prefill_launches.run_case and tests/prefill_pass_ref.check_pass, which reads the two formats inside
-q5_01_f16w_ref.q5_01_pass (the checker's own tests for them: tests/test_q5_01_pass_ref.py).  From 32 rows every layer matrix runs on
+ROW, through tests/test_hip_prefill_launches.run_case and tests/prefill_pass_ref.check_pass, which reads every format from
+tests/weight_formats.py (the checker's own tests for them: tests/test_q5_01_pass_ref.py).  From 32 rows every layer matrix runs on
 k_gemm_f16w (gemm_f16w.hip: WF_Q5_0 / WF_Q5_1, B' shared with Q4_0 / Q4_1 in slot order 0); a shorter pass, the PREFILL_INT8_GEMM form
 and the recomputation of a chunk whose B' overflowed keep the wave-per-row GEMV -- the int8 matrix-core GEMM does not take the two
 formats, so their plan words say 3 and never 2.
 
 run_case asserts that the tapped pass's logits and every layer's caches equal a plain prefill's bit for bit and that the tapped layer
 passes check_pass; every case here also asserts from the plan that it took the path it is named for.  Gates: GEMV_REL sum |A' B'| (the
-f16 GEMM, A' = f16((q5 - 16) d) / f16(q5 d + m) restated by tests/q5_01_f16w_ref.py), row_dots' (nb + C_DOT) U sum |t_b| (the GEMV and the
-classifier: Q4_0's derivation for Q5_0, Q4_1's for Q5_1, tests/q5_01_step_ref.py), the interval checks with EXCUSED_CAP, FLASH_ROWS_REL,
+f16 GEMM, A' = f16((q5 - 16) d) / f16(q5 d + m) restated by the formats' rows of tests/weight_formats.py), row_dots' (nb + C_DOT) U sum |t_b| (the GEMV and the
+classifier: Q4_0's derivation for Q5_0, Q4_1's for Q5_1, tests/weight_formats.py), the interval checks with EXCUSED_CAP, FLASH_ROWS_REL,
 bit equality.  No bound is this file's own.
 
 Also here, for every format: a pass in which the range check (f16w_range_ok) refuses ONE matrix of a body whose other matrices take the
-GEMM.  The two formats reach it with a block whose weights are all exactly zero (q5_01_f16w_ref.refuse_matrix), so nothing downstream
+GEMM.  The two formats reach it with a block whose weights are all exactly zero (f16w_gemm_ref.refuse_matrix), so nothing downstream
 moves: the one-launch sites for q | k | v and gate | up fall apart, the refused reader gets no B', the next reader still finds one, and
 the plan says 3 for exactly that matrix.
 
@@ -24,9 +24,9 @@ import pytest
 
 from crabml_amd import synth
 from tests import edge_blocks as eb
+from tests import fused_step_ref as R
 from tests import prefill_pass_ref as P
-from tests import q5_01_f16w_ref as Q
-from tests import q5_01_step_ref as S
+from tests.f16w_gemm_ref import refuse_matrix
 from tests.helpers import record_observed
 from tests.test_hip_fused_launches import SHAPE_8B, SHAPE_WIDE
 from tests.test_hip_prefill_launches import (EXACT_ATTENTION, FLAG_CASES, INT8_GEMM, NORM_ROWS, NORM_ROWS_H, NORM_ROWS_W, NORM_SEPARATE,
@@ -35,7 +35,7 @@ from tests.test_q5_01_pass_ref import OVERFLOW_LOG2, REFUSED, XH, XH_WITH, overf
 
 pytestmark = pytest.mark.gpu
 
-FMTS = list(Q.FMTS)
+FMTS = ["Q5_0", "Q5_1"]
 WORDS = tuple(P.KERNEL_WORD.values())
 F16W, GEMV = P.KERNEL_F16W, P.KERNEL_GEMV
 _OBSERVED = {}
@@ -52,8 +52,7 @@ def build(shape, fmt, seed):
 
 
 def case(ca, key, model, seq, n, layers, kv_f16=True, **kw):
-    with Q.q5_01_pass():
-        return run_case(ca, key, model, seq, kv_f16, n, layers, rec=record, **kw)
+    return run_case(ca, key, model, seq, kv_f16, n, layers, rec=record, **kw)
 
 
 def all_words(plan, kernel):
@@ -244,7 +243,7 @@ def test_one_matrix_refused_by_the_range_check(ca, fmt, nm, n):
 def test_refused_ffn_down_behind_the_row_quantizer(ca):
     """wide-ffn (hidden 12288), where gate | up quantize h themselves (h_done == 2): with ffn_down refused the launch writes planes and NO
     B' (F16wHQuant.xh == nullptr), and ffn_down's GEMV reads the planes"""
-    model = Q.refuse_matrix(build(WIDE_FFN, "Q5_0", 47), "blk.0.ffn_down.weight")
+    model = refuse_matrix(build(WIDE_FFN, "Q5_0", 47), "blk.0.ffn_down.weight")
     plans = case(ca, "refused/ffn_down/wide-ffn/Q5_0", model, 160, 136, [0], sample=P.Sample(extra=8, col_tile=16))
     p = plans[0]
     assert p["h_done"] == 2 and p["kernel_down"] == GEMV and "hid.xh" not in p["fields"] and p["f16w"] == 1 and p["recomputed"] == 0, p
@@ -254,7 +253,7 @@ def test_refused_ffn_down_behind_the_row_quantizer(ca):
 # ---- case 10 ----
 @pytest.mark.parametrize("fmt", FMTS)
 def test_block_scales_of_either_sign(ca, fmt):
-    model = S.flip_signs(build("tiny-gqa", fmt, 49))
+    model = R.flip_signs(build("tiny-gqa", fmt, 49))
     for plan in case(ca, f"signs/tiny-gqa/{fmt}", model, 128, 77, [0, 1]).values():
         expect_gemm(plan, model)
 
@@ -272,7 +271,7 @@ def test_mixed_sign_block_fields(ca, shape, fmt):
 @pytest.mark.parametrize("fmt", FMTS)
 def test_shrunk_residual_stream(ca, fmt):
     """a residual stream small enough for RMSNorm's eps to matter in every norm launch, on the GEMM (77 rows) and row by row (23)"""
-    model = S.shrink_residual(build("tiny-gqa", fmt, 50))
+    model = R.shrink_residual(build("tiny-gqa", fmt, 50))
     for plan in case(ca, f"shrunk/tiny-gqa/{fmt}", model, 128, 77, [0, 1]).values():
         expect_gemm(plan, model)
     for plan in case(ca, f"shrunk-row-dots/tiny-gqa/{fmt}", model, 128, 23, [0, 1]).values():
@@ -316,14 +315,13 @@ def test_overflow_recomputation_of_a_q5_1_pass_up_to_h(ca):
     expect_row_dots(plan)
     assert np.array_equal(tap["logits"].view(np.uint32), want.view(np.uint32))
     form, ctx, sample = P.Form(kv_f16=True, seq_cap=seq), "overflow/tiny-gqa/Q5_1 layer 0", P.Sample(extra=8, col_tile=16)
-    with Q.q5_01_pass():
-        res = {"embedding": P.check_embedding(tap, model, toks, ctx), "norm n1": P.check_norm(tap, model, layer, "n1", ctx),
-               "q|k|v gemm": P.check_qkv_gemm(tap, model, layer, ctx, sample), "k_qkv_epi_rows": P.check_epi(tap, before, after, model, layer, form, ctx),
-               "attention": P.check_attention(tap, after, model, layer, form, ctx), "wo": P.check_wo(tap, model, layer, ctx, sample),
-               "norm n2": P.check_norm(tap, model, layer, "n2", ctx)}
-        gu = res["gate, up gemv"] = P.Result("gate, up gemv")
-        for nm, wn in (("g", "ffn_gate"), ("u", "ffn_up")):
-            P.check_gemm(gu, tap, model, f"blk.{layer}.{wn}.weight", "n2.act", nm, None, nm, ctx, sample)
+    res = {"embedding": P.check_embedding(tap, model, toks, ctx), "norm n1": P.check_norm(tap, model, layer, "n1", ctx),
+           "q|k|v gemm": P.check_qkv_gemm(tap, model, layer, ctx, sample), "k_qkv_epi_rows": P.check_epi(tap, before, after, model, layer, form, ctx),
+           "attention": P.check_attention(tap, after, model, layer, form, ctx), "wo": P.check_wo(tap, model, layer, ctx, sample),
+           "norm n2": P.check_norm(tap, model, layer, "n2", ctx)}
+    gu = res["gate, up gemv"] = P.Result("gate, up gemv")
+    for nm, wn in (("g", "ffn_gate"), ("u", "ffn_up")):
+        P.check_gemm(gu, tap, model, f"blk.{layer}.{wn}.weight", "n2.act", nm, None, nm, ctx, sample)
     record(f"overflow/tiny-gqa/Q5_1/L{layer}/n{n}/p0", res)
     assert not P.failures(res), "\n".join(P.failures(res)[:40])
     h = np.abs(np.asarray(tap["g"], dtype=np.float64))  # (g, not h: SiLU * mul happens inside the quantizer launch)

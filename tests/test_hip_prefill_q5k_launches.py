@@ -4,10 +4,10 @@ Q5_K matrix keeps the GEMV in every body (tests/test_hip_prefill_k_launches.py, 
 the form is opt-in.
 
 Part 1, every launch of a tapped pass (through tests/test_hip_prefill_launches.run_case and tests/prefill_pass_ref.check_pass, which
-reads the format inside q5k_f16w_ref.q5k_pass): Q5_K, Q5_K_M, Q3_K_M and Q3_K_L bodies on tiny-gqa and tiny-hd128.  The launch plan must
+reads every format from tests/weight_formats.py): Q5_K, Q5_K_M, Q3_K_M and Q3_K_L bodies on tiny-gqa and tiny-hd128.  The launch plan must
 say k_gemm_f16w for every matrix, one launch for q | k | v exactly where the three share a format and for gate | up, and B' re-made
 for attn_v only where its k-slot order differs from attn_q's: a Q6_K attn_v of Q5_K_M, never a Q5_K attn_v beside Q3_K.  Every GEMM
-output is held to GEMV_REL sum |A' B'| with A' restated by tests/q5k_f16w_ref.py.  Observed error / bound ratios:
+output is held to GEMV_REL sum |A' B'| with A' restated by Q5_K's row of tests/weight_formats.py.  Observed error / bound ratios:
 tests/golden/prefill_q5k_launch_pins_observed.json (evidence only).
 
 Part 2, the flag is opt-in.  Part 3, end to end against the oracle's token loop, in the form of
@@ -18,7 +18,6 @@ import pytest
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import prefill_pass_ref as P
-from tests import q5k_f16w_ref as Q
 from tests.helpers import FAST_TOL, record_observed, to_oracle
 from tests.test_hip_prefill_k_launches import GEMV, F16W, MATS, NORM_ROWS_K, expect_norm
 from tests.test_hip_prefill_launches import INT8_GEMM, POS0_CASES, expect_attn, run_case, tokens_of
@@ -51,9 +50,8 @@ def body_model(shape, body, seed):
 
 
 def case(ca, key, model, seq, n, layers, **kw):
-    with Q.q5k_pass():
-        return run_case(ca, key, model, seq, kw.pop("kv_f16", True), n, layers, rec=record,
-                        flags=kw.pop("flags", 0) | Q5K_GEMM | TAP_Q2K_Q3K, **kw)
+    return run_case(ca, key, model, seq, kw.pop("kv_f16", True), n, layers, rec=record,
+                    flags=kw.pop("flags", 0) | Q5K_GEMM | TAP_Q2K_Q3K, **kw)
 
 
 def flag_routes_q5_k_to_the_gemm(ca, model, seq, n):

@@ -1,7 +1,7 @@
 """Every launch of the fast K-quant decode step over a Q2_K BODY (enqueue_segment_k<Q2_K>: k_qkv<Q2_K> with its V hand-over, attention,
 k_gemv_res_nq<F, SPLIT, QIN> for wo with F the tensor's own format, k_gateup_k_lds<QOUT, false, NORMIN, Q2_K>, k_gemv_res_nq for
 ffn_down, the classifier) pinned against float64, launch by launch, as tests/test_hip_q3k_fused.py and tests/test_hip_q6k_fused.py
-pin their bodies: the checker is tests/q2k_step_ref.py (its derivation: that module's docstring; its own tests, and the excused
+pin their bodies: the checker is tests/fused_step_ref.py with the format's row of tests/weight_formats.py (its derivation: that module's docstring; its own tests, and the excused
 shares of the Q8_K interval check for the models below, from the reference alone: tests/test_q2k_step_ref.py, whose CASES list this
 file runs).
 
@@ -16,9 +16,8 @@ import pytest
 
 from crabml_amd import synth
 from oracle import oracle as o
-from tests import q2k_step_ref as Q
-from tests import test_hip_q6k_fused as H6
-from tests.helpers import check_fast, record_observed, to_oracle
+from tests import fused_step_ref as R
+from tests.helpers import NOT_IMPLEMENTED, check_fast, error_kind, run_k_case, to_oracle
 from tests.test_hip_q3k_fused import FLAG_CASES, SPLIT_ALWAYS, SPLIT_NEVER
 from tests.test_q2k_step_ref import CASES, build
 
@@ -29,12 +28,6 @@ BY_KEY = {c[0]: c for c in CASES}
 Q2K, Q3K, Q4K = synth.Q2_K, synth.Q3_K, synth.Q4_K
 
 
-def record(key, results):
-    _OBSERVED[key] = {"error_over_bound": {k: round(r.worst, 4) for k, r in results.items()},
-                      "excused_share": {k: {n: round(v, 6) for n, v in r.excused.items()} for k, r in results.items() if r.excused}}
-    record_observed(_OBSERVED, "fused_q2k_launch_pins.json")
-
-
 def expect_flash(model, pos):
     """k_attn_flash from 96 cached positions on, for every GQA group up to 8 (decide_attention, fused.hip).  The Q6_K file's own
     predicate names groups 1, 2, 4 and 8 only -- it never ran another group that far --, and this file runs group 7 at position 100."""
@@ -43,14 +36,8 @@ def expect_flash(model, pos):
 
 
 def run_case(ca, key, model, seq, positions, layers, **kw):
-    """tests/test_hip_q6k_fused.run_case (one tapped step per (layer, position), its graph and NO_K_NORM_IN twins, every launch through
-    the checker, plan["path"] == 2) with this file's checker and record -> {(layer, pos): the tapped step's launch plan}"""
-    saved = H6.Q, H6.record, H6.expect_flash
-    H6.Q, H6.record, H6.expect_flash = Q, record, expect_flash
-    try:
-        return H6.run_case(ca, key, model, seq, positions, layers, **kw)
-    finally:
-        H6.Q, H6.record, H6.expect_flash = saved
+    """tests/helpers.run_k_case with this file's record and its attention predicate -> {(layer, pos): the tapped step's launch plan}"""
+    return run_k_case(ca, key, model, synth.Q2_K, seq, positions, layers, "fused_q2k_launch_pins.json", expect_flash=expect_flash, observed=_OBSERVED, **kw)
 
 
 def run_listed(ca, key, **kw):
@@ -139,7 +126,7 @@ def test_without_the_norm_epilogue_q2k_runs_per_op(ca):
     conf, w = synth.to_hip(model, dev)
     assert ca.debug_step_plan(conf, w, dev, 64, True, norm_epilogue=False)["path"] == 0
     r = ca.HipLlamaRunner(conf, w, dev, 64, True, True, True, norm_epilogue=False)
-    assert H6.error_kind(ca, lambda: r.debug_tap(1, 0, 0)) == H6.NOT_IMPLEMENTED and r.kv_cache_len() == 0
+    assert error_kind(ca, lambda: r.debug_tap(1, 0, 0)) == NOT_IMPLEMENTED and r.kv_cache_len() == 0
 
 
 def test_block_field_edges(ca):
@@ -217,11 +204,11 @@ def test_tap_still_refuses_what_it_does_not_serve(ca):
     sdev = ca.HipTensorDevice(0, False, 0, True)
     sconf, sw = synth.to_hip(model, sdev)
     strict = ca.HipLlamaRunner(sconf, sw, sdev, 64, True)
-    assert H6.error_kind(ca, lambda: strict.debug_tap(1, 0, 0)) == H6.NOT_IMPLEMENTED
+    assert error_kind(ca, lambda: strict.debug_tap(1, 0, 0)) == NOT_IMPLEMENTED
     dev = ca.HipTensorDevice(0)
     other = synth.build_model(synth.SHAPES["tiny-gqa"], Q2K, seed=91, layer_types={1: {"attn_v": synth.Q5_K}})
     oconf, ow = synth.to_hip(other, dev)
     assert ca.debug_step_plan(oconf, ow, dev, 64, True)["path"] == 0
     per_op = ca.HipLlamaRunner(oconf, ow, dev, 64, True)
-    assert H6.error_kind(ca, lambda: per_op.debug_tap(1, 0, 0)) == H6.NOT_IMPLEMENTED
+    assert error_kind(ca, lambda: per_op.debug_tap(1, 0, 0)) == NOT_IMPLEMENTED
     assert strict.kv_cache_len() == per_op.kv_cache_len() == 0

@@ -1,7 +1,7 @@
 """Every launch of the fast fused decode step over Q5_0 / Q5_1 layers (enqueue_segment_t<Q5_0 / Q5_1>: k_qkv, attention, k_gemv_res_nq
 for wo, k_gateup_q, k_gemv_res_nq for ffn_down, the classifier; a Q5_1 body in front of a Q6_K classifier: enqueue_segment_k<Q5_1>)
 pinned against float64, launch by launch, as tests/test_hip_fused_launches.py pins Q4_0 / Q8_0 / Q4_1.  The checker is
-tests/q5_01_step_ref.py (its derivation: that module's docstring; its own tests, and the excused shares of the interval checks for
+tests/fused_step_ref.py with the format's row of tests/weight_formats.py (its derivation: that module's docstring; its own tests, and the excused shares of the interval checks for
 the models below from the reference alone: tests/test_q5_01_step_ref.py, whose CASES list this file runs).
 
 A runner is teacher-forced greedily on its own tokens up to `pos` (from the graph), then takes ONE tapped step; the tapped (eager)
@@ -24,7 +24,6 @@ import pytest
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import fused_step_ref as R
-from tests import q5_01_step_ref as Q
 from tests.helpers import EXACT_NORM, FAST_TOL, record_observed, to_oracle
 from tests.test_q5_01_step_ref import CASES, FMT, SPLIT_ALWAYS, build
 
@@ -77,11 +76,12 @@ def run_case(ca, key):
             assert np.array_equal(tap["logits"].view(np.uint32), want.view(np.uint32)), f"{ctx}: the tapped (eager) step's logits differ from the graph's"
             form = R.Form(defer=defer, kv_f16=True, seq_cap=seq, flash_from=pos + 1 if flash else 0)
             kc, vc = r.debug_kv(layer, False, True), r.debug_kv(layer, True, True)
-            res = Q.check_layer(tap, kc, vc, model, layer, pos, form, ctx, token=tok)
+            assert synth.TYPE_NAMES[model.wtype] == fmt, ctx
+            res = R.check_layer(tap, kc, vc, model, layer, pos, form, ctx, token=tok)
             for name, rr in res.items():
                 print(f"{ctx} {name}: error / bound {rr.worst:.3f} excused {rr.excused}")
             record(f"{key}/L{layer}/p{pos}", res)
-            fails += Q.failures(res)
+            fails += R.failures(res)
     assert not fails, "\n".join(fails)
     return plans
 

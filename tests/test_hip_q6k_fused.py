@@ -1,7 +1,7 @@
 """Every launch of the fast K-quant decode step over a Q6_K BODY (enqueue_segment_k<Q6_K>: k_qkv<Q6_K>, attention, k_gemv_res_nq<Q6_K,
 SPLIT, QIN> for wo, k_gateup_k_lds<QOUT, false, NORMIN, Q6_K>, k_gemv_res_nq for ffn_down, the classifier) pinned against float64,
 launch by launch, as tests/test_hip_fused_k_launches.py pins the Q4_K body and tests/test_hip_q5k_fused.py the Q5_K one: the checker
-is tests/q6k_step_ref.py (its derivation: that module's docstring; its own tests, and the excused shares of the Q8_K interval check
+is tests/fused_step_ref.py with the format's row of tests/weight_formats.py (its derivation: that module's docstring; its own tests, and the excused shares of the Q8_K interval check
 for the models below, from the reference alone: tests/test_q6k_step_ref.py, whose CASES list this file runs).
 
 A runner is teacher-forced greedily on its own tokens up to `pos` (from the graph), then takes ONE tapped step; the tapped (eager)
@@ -16,8 +16,7 @@ import pytest
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import fused_step_ref as R
-from tests import q6k_step_ref as Q
-from tests.helpers import check_fast, record_observed, to_oracle
+from tests.helpers import NOT_IMPLEMENTED, check_fast, error_kind, run_k_case, to_oracle
 from tests.test_q6k_step_ref import CASES, build
 
 pytestmark = pytest.mark.gpu
@@ -27,62 +26,9 @@ _OBSERVED = {}
 BY_KEY = {c[0]: c for c in CASES}
 
 
-def record(key, results):
-    _OBSERVED[key] = {"error_over_bound": {k: round(r.worst, 4) for k, r in results.items()},
-                      "excused_share": {k: {n: round(v, 6) for n, v in r.excused.items()} for k, r in results.items() if r.excused}}
-    record_observed(_OBSERVED, "fused_q6k_launch_pins.json")
-
-
-def expect_flash(model, pos):
-    s = model.shape
-    return s.head_dim in (64, 128, 256) and s.n_heads // s.n_kv_heads in (1, 2, 4, 8) and pos + 1 >= 96
-
-
-def run_case(ca, key, model, seq, positions, layers, norm_epilogue=True, flags=0, want_path=2):
-    """-> {(layer, pos): the tapped step's launch plan}"""
-    dev = ca.HipTensorDevice(0)
-    conf, w = synth.to_hip(model, dev)
-    mk = lambda fl: ca.HipLlamaRunner(conf, w, dev, seq, True, True, True, norm_epilogue=norm_epilogue, extra_flags=fl)  # noqa: E731
-    r, twin, planes_twin = mk(flags), mk(flags), None
-    fails, plans = [], {}
-    for pos in positions:
-        twin.reset()
-        tok = int(twin.decode_greedy(1, pos)[-1]) if pos else 1
-        want = twin.forward(tok, pos).copy()
-        for layer in layers:
-            ctx = f"{key} layer {layer} pos {pos}"
-            r.reset()
-            if pos:
-                assert int(r.decode_greedy(1, pos)[-1]) == tok, ctx
-            tap = r.debug_tap(tok, pos, layer)
-            assert r.kv_cache_len() == pos + 1
-            plan = plans[(layer, pos)] = tap["plan"]
-            assert plan["path"] == want_path, (ctx, plan)  # enqueue_segment_k
-            flash = plan["attn_variant"] >= 16
-            assert flash == expect_flash(model, pos), (ctx, plan)
-            assert np.array_equal(tap["logits"].view(np.uint32), want.view(np.uint32)), f"{ctx}: the tapped (eager) step's logits differ from the graph's"
-            twin_tap = None
-            if plan["wo_x_only"]:  # gate | up's planes exist in LDS only: the twin whose wo leaves them
-                if planes_twin is None:
-                    planes_twin = mk(flags | NO_K_NORM_IN)
-                planes_twin.reset()
-                if pos:
-                    assert int(planes_twin.decode_greedy(1, pos)[-1]) == tok, ctx
-                twin_tap = planes_twin.debug_tap(tok, pos, layer)
-                assert twin_tap["plan"]["wo_x_only"] == 0 and twin_tap["plan"]["norm_epi_k"] == 1, (ctx, twin_tap["plan"])
-                assert np.array_equal(twin_tap["logits"].view(np.uint32), want.view(np.uint32)), f"{ctx}: the NO_K_NORM_IN twin's logits differ"
-            form = R.Form(defer=False, kv_f16=True, seq_cap=seq, flash_from=pos + 1 if flash else 0)
-            kc, vc = r.debug_kv(layer, False, True), r.debug_kv(layer, True, True)
-            res = Q.check_layer(tap, kc, vc, model, layer, pos, form, ctx, twin=twin_tap, token=tok)
-            for name, rr in res.items():
-                print(f"{ctx} {name}: error / bound {rr.worst:.3f} excused {rr.excused}")
-                for pname, share in rr.excused.items():
-                    if share > Q.EXCUSED_CAP:
-                        fails.append(f"{ctx} {name}: {pname} excused share {share:.3f} > {Q.EXCUSED_CAP}")
-            record(f"{key}/L{layer}/p{pos}", res)
-            fails += Q.failures(res)
-    assert not fails, "\n".join(fails)
-    return plans
+def run_case(ca, key, model, seq, positions, layers, **kw):
+    """tests/helpers.run_k_case with this file's record -> {(layer, pos): the tapped step's launch plan}"""
+    return run_k_case(ca, key, model, synth.Q6_K, seq, positions, layers, "fused_q6k_launch_pins.json", observed=_OBSERVED, **kw)
 
 
 def run_listed(ca, key, **kw):
@@ -207,15 +153,6 @@ def test_q6_k_end_to_end(ca):
         lg = eager.forward(tok, pos)
         tok, pos = int(o.argmax_last(lg)), pos + 1
         assert tok == int(want)
-
-
-NOT_IMPLEMENTED = 9  # crabml_hip_status
-
-
-def error_kind(ca, call):
-    with pytest.raises(ca.CrabmlError) as e:
-        call()
-    return int(str(e.value).split("ErrorKind(")[1].split(")")[0])
 
 
 def test_tap_still_refuses_what_it_does_not_serve(ca):

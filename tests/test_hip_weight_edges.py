@@ -27,8 +27,9 @@ import pytest
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import edge_blocks as eb
-from tests import test_hip_f16w_gemm as f16w
+from tests import f16w_gemm_ref as f16w
 from tests.helpers import GEMV_REL, gemv_order_bound, record_observed
+from tests.test_hip_f16w_gemm import BIG_SCALE, FMTS as F16W_FMTS
 from tests.test_hip_gemv import HT
 from tests.test_hip_kquant_ints import ref_ints_q4k, ref_ints_q6k, ref_q6k_offset_parts
 
@@ -271,21 +272,21 @@ F16W_TOP = 1.0  # the "range" set's largest member here: the launcher refuses wh
 
 
 @pytest.mark.parametrize("kind", ["sign", "range", "mixed"])
-@pytest.mark.parametrize("fmt", f16w.FMTS)
+@pytest.mark.parametrize("fmt", F16W_FMTS)
 def test_f16_gemm_operands_on_signed_and_subnormal_scales(ca, hdev, fmt, kind):
     """check_f16_operands' tier 2 (f16 operands summed in float64) and tier 3 (the dequantized operation) as they stand: both are
     derived from the roundings and do not know a scale's sign; u(v) = max(2^-11 |v|, 2^-25) already charges a subnormal A' half its
     spacing.  "range" / "mixed": d down to 2^-24 -- such matrices are taken, and a kernel that flushed f16 subnormals would lose their
     blocks whole."""
     for i, (m, k, b, force) in enumerate(((60, 512, 17, (1, 4, 1, 0)), (100, 768, 33, (2, 8, 1, 0)), (36, 256, 40, (0, 0, 0, -1)))):
-        if fmt not in f16w.KQ:
+        if not f16w.kq(fmt):
             k = {512: 160, 768: 288, 256: 96}[k]
         rng = np.random.default_rng([eb.FORMATS.index(fmt), eb.KINDS.index(kind), i])
         raw = eb.edge_blocks(rng, fmt, m, k, kind, top=F16W_TOP)
         f16w.check_f16_operands(ca, hdev, fmt, m, k, b, force, 100 + i, raw=raw)
 
 
-@pytest.mark.parametrize("fmt", f16w.FMTS)
+@pytest.mark.parametrize("fmt", F16W_FMTS)
 def test_negative_weight_scales_that_put_a_past_f16_are_refused(ca, hdev, fmt):
     """test_weight_scales_that_put_a_past_f16_are_refused with the NEGATED pair: the first scale still refused, the second still taken
     and finite -- a matrix whose only out-of-range block is negative is refused like its positive twin (the upload scan compares
@@ -295,7 +296,7 @@ def test_negative_weight_scales_that_put_a_past_f16_are_refused(ca, hdev, fmt):
     typ = synth.TYPE_BY_NAME[fmt]
     bb = o.BLOCK_BYTES[typ]
     x = rng.standard_normal(b * k).astype(np.float32)
-    for scale, refused in zip(f16w.BIG_SCALE[fmt], (True, False)):
+    for scale, refused in zip(BIG_SCALE[fmt], (True, False)):
         for twin in (-1.0, 1.0):
             raw = synth.random_blocks(rng, m * k, typ).reshape(-1, bb).copy()
             at = {"Q6_K": 208}.get(fmt, 0)

@@ -15,11 +15,11 @@ from crabml_amd import synth
 from oracle import oracle as o
 from tests import fused_step_ref as R
 from tests import prefill_pass_ref as P
-from tests import q5k_step_ref as Q5
+from tests import weight_formats as WF
 from tests.helpers import to_oracle
 from tests.qwen2_ref import OracleQwen2Runner, to_oracle_qwen2
 from tests.test_fused_step_ref import TOKS, exact_norm, mv, rope, silu_mul
-from tests.test_hip_f16w_gemm import weight_operands
+from tests.f16w_gemm_ref import weight_operands
 
 SEQ = 24
 PASS_TOKS = [3, 77, 500, 31, 8, 19, 64, 128, 5, 900, 12]
@@ -695,7 +695,7 @@ def k_model(shape, fmt, shrunk=False):
     wtype, mix = K_FMTS[fmt]
     model = synth.build_model(synth.SHAPES[shape], wtype, seed=21, n_layers=2, k_m_mix=mix)
     if shrunk:
-        model = (Q5.shrink_residual if wtype == synth.Q5_K else R.shrink_residual)(model, 7)
+        model = R.shrink_residual(model, 7)
     return model
 
 
@@ -757,7 +757,7 @@ def _m_q5k(wrong):
     return m
 
 
-Q5K_MUTATIONS = [_m_q5k(w) for w in Q5.WRONG]
+Q5K_MUTATIONS = [_m_q5k(w) for w in WF.WRONG_Q5_K]
 
 
 def q8k_pos(order, E):

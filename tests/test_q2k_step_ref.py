@@ -1,4 +1,4 @@
-"""The Q2_K checker (tests/q2k_step_ref.py) checked on the CPU: its unpack of the raw 84-byte block against the reference's dequantizer,
+"""The Q2_K checker (tests/fused_step_ref.py with the format's row of tests/weight_formats.py) checked on the CPU: its unpack of the raw 84-byte block against the reference's dequantizer,
 its bound against an f32 emulation of the kernel's term in permuted add orders, every subtly wrong kernel it must reject, and -- from
 the reference alone, an oracle-built tap of the step -- that it accepts the reference's own order and that the Q8_K interval check
 excuses no more than EXCUSED_CAP of any plane set for the shapes, seeds and positions tests/test_hip_q2k_fused.py uses (CASES below
@@ -9,7 +9,7 @@ import pytest
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import fused_step_ref as R
-from tests import q2k_step_ref as Q
+from tests import weight_formats as WF
 from tests import test_q5k_step_ref as T5
 from tests.test_q5k_step_ref import _tap, oracle_tokens, q8k
 
@@ -78,7 +78,7 @@ def test_q2_k_rows_of_the_restatement_equal_the_reference_dequantizer(oracle):
     first, then dl * level - ml); and against tests/edge_blocks' float64 dequantizer (an unpack written independently of this one)"""
     rng = np.random.default_rng(4)
     t = q2k_tensor(rng, 8, 512)
-    w = Q.weight_rows(t, 0, 8)
+    w = R.weight_rows(t, 0, 8)
     f = np.float32
     lv = w["lv"].reshape(8, 2, 16, 16)
     assert lv.max() == 3 and lv.min() == 0 and w["sc"].max() == 15 and w["sc"].min() == 0 and w["mn"].max() == 15 and w["mn"].min() == 0
@@ -86,9 +86,9 @@ def test_q2_k_rows_of_the_restatement_equal_the_reference_dequantizer(oracle):
     ml = (w["dmin"].astype(f)[:, :, None] * w["mn"].astype(f))[:, :, :, None]
     mine = dl * lv.astype(f) - ml
     assert np.array_equal(mine.reshape(-1), o.dequantize(t.data, o.Q2_K))
-    assert np.allclose(Q.k_values(w).reshape(-1), mine.reshape(-1).astype(np.float64), rtol=1e-5, atol=1e-7)
+    assert np.allclose(R.k_values(w).reshape(-1), mine.reshape(-1).astype(np.float64), rtol=1e-5, atol=1e-7)
     from tests import edge_blocks as eb
-    assert np.array_equal(Q.k_values(w).reshape(-1), np.asarray(eb.dequant_f64(t.data, "Q2_K"), dtype=np.float64).reshape(-1))
+    assert np.array_equal(R.k_values(w).reshape(-1), np.asarray(eb.dequant_f64(t.data, "Q2_K"), dtype=np.float64).reshape(-1))
 
 
 def test_q2_k_row_dots_equal_the_reference_vec_dot(oracle):
@@ -99,7 +99,7 @@ def test_q2_k_row_dots_equal_the_reference_vec_dot(oracle):
         t = q2k_tensor(rng, 16, k)
         x = (rng.standard_normal(k) * 1.5).astype(np.float32)
         xq = o.quantize(x, o.Q8_K)
-        exact, bound = Q.row_dots(t, R.parse_act(xq, o.Q8_K))
+        exact, bound = R.row_dots(t, R.parse_act(xq, o.Q8_K))
         rows = np.ascontiguousarray(t.data).reshape(16, -1)
         got = np.array([o.vec_dot(rows[r], o.Q2_K, xq, k) for r in range(16)], dtype=np.float64)
         assert np.all(np.abs(got - exact) <= bound), (k, float(np.max(np.abs(got - exact) / bound)))
@@ -111,7 +111,7 @@ def f32_terms(w, act):
     f = np.float32
     rows, nsb = w["d"].shape
     x = act["q"].astype(np.int64).reshape(nsb, 16, 16)
-    G = np.einsum("rsgi,sgi->rsg", Q.levels(w["qs"]).reshape(rows, nsb, 16, 16), x)
+    G = np.einsum("rsgi,sgi->rsg", WF.q2_levels(w["qs"]).reshape(rows, nsb, 16, 16), x)
     isum = ((w["s16"] & 15) * G).sum(axis=2)
     summs = ((w["s16"] >> 4) * act["bsums"].astype(np.int64)[None]).sum(axis=2)
     assert np.abs(isum).max() < 2 ** 24 and np.abs(summs).max() < 2 ** 24
@@ -135,8 +135,8 @@ def test_bound_holds_an_f32_emulation_in_permuted_orders(oracle, k):
             blk[:, 81] ^= (rng.integers(0, 2, size=blk.shape[0], dtype=np.uint8) << 7)
             blk[:, 83] ^= (rng.integers(0, 2, size=blk.shape[0], dtype=np.uint8) << 7)
         act = q8k(rng, k)
-        exact, bound = Q.row_dots(t, act)
-        w = Q.weight_rows(t, 0, rows)
+        exact, bound = R.row_dots(t, act)
+        w = R.weight_rows(t, 0, rows)
         terms = f32_terms(w, act)
         n = terms.shape[1]
         f = np.float32
@@ -152,7 +152,7 @@ def test_bound_holds_an_f32_emulation_in_permuted_orders(oracle, k):
         assert np.all(bound <= 8 * proj), (k, float(np.max(bound / proj)))
 
 
-@pytest.mark.parametrize("wrong", list(Q.WRONG) + ["last_block_dropped"])
+@pytest.mark.parametrize("wrong", list(WF.FORMATS[synth.Q2_K].wrong) + ["last_block_dropped"])
 def test_every_wrong_kernel_is_rejected(oracle, wrong):
     """a kernel that exchanges the scale and min nibbles, adds the min term, exchanges d and dmin, exchanges field and half-piece in the
     group index, reads a neighbouring bsums entry, masks the quants as a 4-bit format does, drops the min term of the h = 1 pieces,
@@ -161,11 +161,11 @@ def test_every_wrong_kernel_is_rejected(oracle, wrong):
     for k in (512, 1792):
         t = q2k_tensor(rng, 64, k)
         act = q8k(rng, k)
-        exact, bound = Q.row_dots(t, act)
+        exact, bound = R.row_dots(t, act)
         if wrong == "last_block_dropped":
-            got, _ = Q.row_dots(t, act, drop_last_block=True)
+            got, _ = R.row_dots(t, act, drop_last_block=True)
         else:
-            got, _ = Q.row_dots(t, act, wrong=wrong)
+            got, _ = R.row_dots(t, act, wrong=wrong)
         out = np.abs(got.astype(np.float32).astype(np.float64) - exact) > bound
         assert out.mean() > 0.9, (wrong, k, float(out.mean()))
 
@@ -173,21 +173,21 @@ def test_every_wrong_kernel_is_rejected(oracle, wrong):
 def test_wrong_rows_fail_in_the_launch_that_owns_them(oracle):
     """through check_layer: wo's x built from each wrong kernel's dots fails at `wo` (the oracle's own tap passes); and on a mixed
     layer the chained wrappers read the Q4_K V rows and the Q3_K wo"""
-    model = Q.flip_signs(synth.build_model(synth.SHAPES["tiny-gqa"], Q2K, seed=22, n_layers=2))
+    model = R.flip_signs(synth.build_model(synth.SHAPES["tiny-gqa"], Q2K, seed=22, n_layers=2))
     tap, kc, vc, form, aux = _tap(model, 7, 1)
-    res = Q.check_layer(tap, kc, vc, model, 1, 7, form, "oracle", twin=aux["twin"])
-    assert not Q.failures(res), Q.failures(res)
+    res = R.check_layer(tap, kc, vc, model, 1, 7, form, "oracle", twin=aux["twin"])
+    assert not R.failures(res), R.failures(res)
     rhs = R._rhs(tap, "attn.act_attn", "attn.attn", o.Q8_K)
-    for wrong in list(Q.WRONG) + [True]:
-        dots = Q.row_dots(model.tensors["blk.1.attn_output.weight"], rhs, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
+    for wrong in list(WF.FORMATS[synth.Q2_K].wrong) + [True]:
+        dots = R.row_dots(model.tensors["blk.1.attn_output.weight"], rhs, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
         bad = dict(tap)
         bad["wo.x"] = (np.asarray(tap["qkv_in.x"], dtype=np.float64) + dots).astype(np.float32)
-        got = Q.check_layer(bad, kc, vc, model, 1, 7, form, "mutant", twin=aux["twin"])["wo"]
+        got = R.check_layer(bad, kc, vc, model, 1, 7, form, "mutant", twin=aux["twin"])["wo"]
         assert any("x row" in f for f in got.fails), (wrong, got.fails, got.worst)
     mixed = synth.build_model(synth.SHAPES["tiny-gqa"], Q2K, seed=23, n_layers=2, layer_types=MIX_LAYERS, output_type=Q6K)
     tap, kc, vc, form, aux = _tap(mixed, 3, 0)
-    res = Q.check_layer(tap, kc, vc, mixed, 0, 3, form, "oracle mix", twin=aux["twin"])
-    assert not Q.failures(res), Q.failures(res)
+    res = R.check_layer(tap, kc, vc, mixed, 0, 3, form, "oracle mix", twin=aux["twin"])
+    assert not R.failures(res), R.failures(res)
 
 
 def test_shrink_residual_knows_the_family(oracle):
@@ -195,7 +195,7 @@ def test_shrink_residual_knows_the_family(oracle):
     of the writers of the residual stream is the old one times 2^-9 rounded to f16, no other byte of the model moves"""
     from tests import edge_blocks as eb
     kw = dict(seed=24, n_layers=2, layer_types=MIX_LAYERS, output_type=Q6K)
-    a, b = synth.build_model(synth.SHAPES["tiny-gqa"], Q2K, **kw), Q.shrink_residual(synth.build_model(synth.SHAPES["tiny-gqa"], Q2K, **kw))
+    a, b = synth.build_model(synth.SHAPES["tiny-gqa"], Q2K, **kw), R.shrink_residual(synth.build_model(synth.SHAPES["tiny-gqa"], Q2K, **kw), log2=9)
     seen = set()
     for name, t in a.tensors.items():
         writer = name == "token_embd.weight" or name.endswith("attn_output.weight") or name.endswith("ffn_down.weight")
@@ -247,11 +247,11 @@ def test_oracle_step_passes_and_excused_shares_stay_under_the_cap(oracle, case):
                 for form in (("default", "no-k-norm-in", "no-rhs-prologue") if key.startswith("flags/") else ("default",)):  # (the forms that case taps)
                     tap, kc, vc, frm, aux = _tap(model, pos, layer, form)
                     ctx = f"{key} {form} layer {layer} pos {pos}"
-                    res = Q.check_layer(tap, kc, vc, model, layer, pos, frm, ctx, twin=aux["twin"])
-                    assert not Q.failures(res), Q.failures(res)
+                    res = R.check_layer(tap, kc, vc, model, layer, pos, frm, ctx, twin=aux["twin"])
+                    assert not R.failures(res), R.failures(res)
                     for r in res.values():
                         for name, share in r.excused.items():
                             shares.append(share)
-                            assert share <= Q.EXCUSED_CAP, (ctx, r.launch, name, share)
+                            assert share <= R.EXCUSED_CAP, (ctx, r.launch, name, share)
     assert shares
     print(f"{key}: excused shares of the Q8_K interval check: max {max(shares):.2e}, mean {np.mean(shares):.2e} over {len(shares)} plane sets")

@@ -1,4 +1,4 @@
-"""The Q3_K checker (tests/q3k_step_ref.py) checked on the CPU: its unpack of the raw 110-byte block against the reference's dequantizer,
+"""The Q3_K checker (tests/fused_step_ref.py with the format's row of tests/weight_formats.py) checked on the CPU: its unpack of the raw 110-byte block against the reference's dequantizer,
 its bound against an f32 emulation of the kernel's term in permuted add orders, every subtly wrong kernel it must reject, and -- from
 the reference alone, an oracle-built tap of the step -- that it accepts the reference's own order and that the Q8_K interval check
 excuses no more than EXCUSED_CAP of any plane set for the shapes, seeds and positions tests/test_hip_q3k_fused.py uses (CASES below
@@ -9,7 +9,7 @@ import pytest
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import fused_step_ref as R
-from tests import q3k_step_ref as Q
+from tests import weight_formats as WF
 from tests.test_q5k_step_ref import _tap, oracle_tokens, q8k, shape_of
 
 Q3K, Q4K, Q5K, Q6K = synth.Q3_K, synth.Q4_K, synth.Q5_K, synth.Q6_K
@@ -52,16 +52,16 @@ def test_q3_k_rows_of_the_restatement_equal_the_reference_dequantizer(oracle):
     times the level)"""
     rng = np.random.default_rng(4)
     t = q3k_tensor(rng, 8, 512)
-    w = Q.weight_rows(t, 0, 8)
+    w = R.weight_rows(t, 0, 8)
     f = np.float32
     lv = w["lv"].reshape(8, 2, 16, 16)
     assert lv.max() == 3 and lv.min() == -4 and 24 < w["sc"].max() <= 31 and -32 <= w["sc"].min() < -24  # (256 scales drawn: both ends' neighbourhood)
     mine = (w["d"].astype(f)[:, :, None] * w["sc"].astype(f))[:, :, :, None] * lv.astype(f)
     assert np.array_equal(mine.reshape(-1), o.dequantize(t.data, o.Q3_K))
-    assert np.allclose(Q.k_values(w).reshape(-1), mine.reshape(-1).astype(np.float64), rtol=1e-6, atol=0)
+    assert np.allclose(R.k_values(w).reshape(-1), mine.reshape(-1).astype(np.float64), rtol=1e-6, atol=0)
     # ... and the scales are tests/edge_blocks' (an unpack written independently of this one)
     from tests import edge_blocks as eb
-    assert np.array_equal(Q.scales(w["s12"]).reshape(-1, 16) + 32, eb._q3k_scales(w["s12"].reshape(-1, 12)).reshape(-1, 16) & 63)
+    assert np.array_equal(WF.q3_scales(w["s12"]).reshape(-1, 16) + 32, eb._q3k_scales(w["s12"].reshape(-1, 12)).reshape(-1, 16) & 63)
 
 
 def test_q3_k_row_dots_equal_the_reference_vec_dot(oracle):
@@ -72,7 +72,7 @@ def test_q3_k_row_dots_equal_the_reference_vec_dot(oracle):
         t = q3k_tensor(rng, 16, k)
         x = (rng.standard_normal(k) * 1.5).astype(np.float32)
         xq = o.quantize(x, o.Q8_K)
-        exact, bound = Q.row_dots(t, R.parse_act(xq, o.Q8_K))
+        exact, bound = R.row_dots(t, R.parse_act(xq, o.Q8_K))
         rows = np.ascontiguousarray(t.data).reshape(16, -1)
         got = np.array([o.vec_dot(rows[r], o.Q3_K, xq, k) for r in range(16)], dtype=np.float64)
         assert np.all(np.abs(got - exact) <= bound), (k, float(np.max(np.abs(got - exact) / bound)))
@@ -87,14 +87,14 @@ def test_bound_holds_an_f32_emulation_in_permuted_orders(oracle, k):
     rows = 48
     t = q3k_tensor(rng, rows, k)
     act = q8k(rng, k)
-    exact, bound = Q.row_dots(t, act)
-    w = Q.weight_rows(t, 0, rows)
+    exact, bound = R.row_dots(t, act)
+    w = R.weight_rows(t, 0, rows)
     f = np.float32
     # the exact integers, formed here in int64 (not taken from k_terms): levels 0 .. 7 against q8, minus 4 bsums, times the scale - 32
     nsb = k // 256
     x = act["q"].astype(np.int64).reshape(nsb, 16, 16)
-    S = np.einsum("rsgi,sgi->rsg", Q.levels(w["q2"], w["hmask"]).reshape(rows, nsb, 16, 16), x) - 4 * act["bsums"].astype(np.int64)[None]
-    tot = (Q.scales(w["s12"]) * S).sum(axis=2)
+    S = np.einsum("rsgi,sgi->rsg", WF.q3_levels(w["q2"], w["hmask"]).reshape(rows, nsb, 16, 16), x) - 4 * act["bsums"].astype(np.int64)[None]
+    tot = (WF.q3_scales(w["s12"]) * S).sum(axis=2)
     assert np.abs(tot).max() < 2 ** 24
     terms = ((w["d"].astype(f) * act["d"].astype(f)[None]).astype(f) * tot.astype(f)).astype(f)
     n = terms.shape[1]
@@ -103,11 +103,11 @@ def test_bound_holds_an_f32_emulation_in_permuted_orders(oracle, k):
         for j in order:
             acc = (acc + terms[:, j]).astype(f)
         assert np.all(np.abs(acc.astype(np.float64) - exact) <= bound), (k, float(np.max(np.abs(acc - exact) / bound)))
-    proj = GEMV_REL * (np.abs(Q.k_values(w)) @ np.abs(R.act_values(act)))
+    proj = GEMV_REL * (np.abs(R.k_values(w)) @ np.abs(R.act_values(act)))
     assert np.all(bound <= 8 * proj), (k, float(np.max(bound / proj)))
 
 
-@pytest.mark.parametrize("wrong", list(Q.WRONG) + ["last_block_dropped"])
+@pytest.mark.parametrize("wrong", list(WF.FORMATS[synth.Q3_K].wrong) + ["last_block_dropped"])
 def test_every_wrong_kernel_is_rejected(oracle, wrong):
     """a kernel that drops the hmask bit, takes it from the other half's bit (off by 4) or from the twin lane's piece, drops the -4 *
     bsum offset, takes a scale's high two bits from the neighbouring byte, forgets the -32, reads a neighbouring bsums entry, or stops
@@ -116,11 +116,11 @@ def test_every_wrong_kernel_is_rejected(oracle, wrong):
     for k in (512, 1792):
         t = q3k_tensor(rng, 64, k)
         act = q8k(rng, k)
-        exact, bound = Q.row_dots(t, act)
+        exact, bound = R.row_dots(t, act)
         if wrong == "last_block_dropped":
-            got, _ = Q.row_dots(t, act, drop_last_block=True)
+            got, _ = R.row_dots(t, act, drop_last_block=True)
         else:
-            got, _ = Q.row_dots(t, act, wrong=wrong)
+            got, _ = R.row_dots(t, act, wrong=wrong)
         out = np.abs(got.astype(np.float32).astype(np.float64) - exact) > bound
         assert out.mean() > 0.9, (wrong, k, float(out.mean()))
 
@@ -128,21 +128,21 @@ def test_every_wrong_kernel_is_rejected(oracle, wrong):
 def test_wrong_rows_fail_in_the_launch_that_owns_them(oracle):
     """through check_layer: wo's x built from each wrong kernel's dots fails at `wo` (the oracle's own tap passes); and on a mixed
     layer the chained wrappers read the Q5_K V rows and the Q4_K wo"""
-    model = Q.flip_signs(synth.build_model(synth.SHAPES["tiny-gqa"], Q3K, seed=22, n_layers=2))
+    model = R.flip_signs(synth.build_model(synth.SHAPES["tiny-gqa"], Q3K, seed=22, n_layers=2))
     tap, kc, vc, form, aux = _tap(model, 7, 1)
-    res = Q.check_layer(tap, kc, vc, model, 1, 7, form, "oracle", twin=aux["twin"])
-    assert not Q.failures(res), Q.failures(res)
+    res = R.check_layer(tap, kc, vc, model, 1, 7, form, "oracle", twin=aux["twin"])
+    assert not R.failures(res), R.failures(res)
     rhs = R._rhs(tap, "attn.act_attn", "attn.attn", o.Q8_K)
-    for wrong in list(Q.WRONG) + [True]:
-        dots = Q.row_dots(model.tensors["blk.1.attn_output.weight"], rhs, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
+    for wrong in list(WF.FORMATS[synth.Q3_K].wrong) + [True]:
+        dots = R.row_dots(model.tensors["blk.1.attn_output.weight"], rhs, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
         bad = dict(tap)
         bad["wo.x"] = (np.asarray(tap["qkv_in.x"], dtype=np.float64) + dots).astype(np.float32)
-        got = Q.check_layer(bad, kc, vc, model, 1, 7, form, "mutant", twin=aux["twin"])["wo"]
+        got = R.check_layer(bad, kc, vc, model, 1, 7, form, "mutant", twin=aux["twin"])["wo"]
         assert any("x row" in f for f in got.fails), (wrong, got.fails, got.worst)
     mixed = synth.build_model(synth.SHAPES["tiny-gqa"], Q3K, seed=23, n_layers=2, layer_types=MIX_LAYERS, output_type=Q6K)
     tap, kc, vc, form, aux = _tap(mixed, 3, 0)
-    res = Q.check_layer(tap, kc, vc, mixed, 0, 3, form, "oracle mix", twin=aux["twin"])
-    assert not Q.failures(res), Q.failures(res)
+    res = R.check_layer(tap, kc, vc, mixed, 0, 3, form, "oracle mix", twin=aux["twin"])
+    assert not R.failures(res), R.failures(res)
 
 
 def test_shrink_residual_knows_the_family(oracle):
@@ -151,7 +151,7 @@ def test_shrink_residual_knows_the_family(oracle):
     dequantizes to 2^-9 of itself"""
     from tests import edge_blocks as eb
     kw = dict(seed=24, n_layers=2, layer_types=MIX_LAYERS, output_type=Q6K)
-    a, b = synth.build_model(synth.SHAPES["tiny-gqa"], Q3K, **kw), Q.shrink_residual(synth.build_model(synth.SHAPES["tiny-gqa"], Q3K, **kw))
+    a, b = synth.build_model(synth.SHAPES["tiny-gqa"], Q3K, **kw), R.shrink_residual(synth.build_model(synth.SHAPES["tiny-gqa"], Q3K, **kw), log2=9)
     for name, t in a.tensors.items():
         writer = name == "token_embd.weight" or name.endswith("attn_output.weight") or name.endswith("ffn_down.weight")
         if not writer:
@@ -186,11 +186,11 @@ def test_oracle_step_passes_and_excused_shares_stay_under_the_cap(oracle, case):
                 for form in (("default", "no-k-norm-in", "no-rhs-prologue") if key.startswith("flags/") else ("default",)):  # (the forms that case taps)
                     tap, kc, vc, frm, aux = _tap(model, pos, layer, form)
                     ctx = f"{key} {form} layer {layer} pos {pos}"
-                    res = Q.check_layer(tap, kc, vc, model, layer, pos, frm, ctx, twin=aux["twin"])
-                    assert not Q.failures(res), Q.failures(res)
+                    res = R.check_layer(tap, kc, vc, model, layer, pos, frm, ctx, twin=aux["twin"])
+                    assert not R.failures(res), R.failures(res)
                     for r in res.values():
                         for name, share in r.excused.items():
                             shares.append(share)
-                            assert share <= Q.EXCUSED_CAP, (ctx, r.launch, name, share)
+                            assert share <= R.EXCUSED_CAP, (ctx, r.launch, name, share)
     assert shares
     print(f"{key}: excused shares of the Q8_K interval check: max {max(shares):.2e}, mean {np.mean(shares):.2e} over {len(shares)} plane sets")

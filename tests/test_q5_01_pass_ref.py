@@ -1,8 +1,8 @@
-"""tests/prefill_pass_ref.check_pass reading Q5_0 / Q5_1 bodies (inside q5_01_f16w_ref.q5_01_pass) decides what
+"""tests/prefill_pass_ref.check_pass reading Q5_0 / Q5_1 bodies decides what
 tests/test_hip_prefill_q5_01_launches.py can see, so it is tested first, without a device, in the form of
 tests/test_prefill_pass_ref.py: oracle-made taps of both arms -- every matrix on the f16 GEMM (h stored, or only its planes), every
 matrix on the row-by-row GEMV -- must be ACCEPTED with every excused share under the cap, then every mutation of
-test_prefill_pass_ref.MUTATIONS and every one of the six subtly wrong loaders of q5_01_step_ref.WRONG must be REJECTED, on every model.
+test_prefill_pass_ref.MUTATIONS and every one of the six subtly wrong loaders of weight_formats.WRONG_Q5_01 must be REJECTED, on every model.
 
 Also here, before any device value exists: the taps of a pass in which the range check refuses ONE matrix (its neighbours keep the GEMM)
 are built and accepted, field presence included; the models of the GPU file's interval-check cases (flipped scale signs, a shrunk
@@ -12,34 +12,18 @@ s = d * sum q overflows with h.
 
 Seeds.  Every model here is the first seed tried: 21 (the checker's own tests), 49 / 50 (flip_signs / shrink_residual, the seeds of the
 Q4_0 / Q8_0 cases they mirror), 5 (the overflow model), 53 (the refused-matrix models)."""
-import contextlib
-
 import numpy as np
 import pytest
 
 from crabml_amd import synth
 from tests import fused_step_ref as R
 from tests import prefill_pass_ref as P
-from tests import q5_01_f16w_ref as Q
-from tests import q5_01_step_ref as S
-from tests import test_hip_f16w_gemm as G
-from tests import test_prefill_pass_ref as TP
+from tests import f16w_gemm_ref as G
+from tests import weight_formats as WF
 from tests.test_prefill_pass_ref import CHECK, MUTATIONS, PASS_TOKS, Case, oracle_pass
 
-FMTS = Q.FMTS
+FMTS = ["Q5_0", "Q5_1"]
 N = len(PASS_TOKS)
-
-
-@contextlib.contextmanager
-def q5_pass():
-    """q5_01_pass for the checker, and the oracle-pass builder's own weight_operands through the same dispatch"""
-    saved = TP.weight_operands
-    with Q.q5_01_pass():
-        TP.weight_operands = G.weight_operands
-        try:
-            yield
-        finally:
-            TP.weight_operands = saved
 
 
 def all_on(kernel):
@@ -67,28 +51,27 @@ FORMS = [("plain", False, 0), ("plain", True, 1), ("shrunk", True, 2)]
 @pytest.mark.parametrize("fmt", FMTS)
 @pytest.mark.parametrize("shape", ["tiny-gqa", "tiny-hd128", "tiny-qwen2"])
 def test_checker_accepts_the_oracle_pass_and_rejects_every_mutation(oracle, shape, fmt, pos0):
-    models = {"plain": build(shape, fmt, n_layers=2), "shrunk": S.shrink_residual(build(shape, fmt, n_layers=2))}
+    models = {"plain": build(shape, fmt, n_layers=2), "shrunk": R.shrink_residual(build(shape, fmt, n_layers=2))}
     applied = set()
-    with q5_pass():
-        for kind, f16w, h_done in FORMS:
-            model, small = models[kind], kind == "shrunk"
-            for layer in (0, 1):
-                kv_f16 = (pos0 + layer) % 2 == 0
-                ctx = f"{shape} ({kind}) {fmt} {'f16' if f16w else 'row dots'} h_done={h_done} kv_f16={kv_f16} layer {layer} pos0 {pos0}"
-                tap, kvb, kva, form, aux = oracle_pass(model, pos0, N, layer, kv_f16, f16w, h_done,
-                                                       kernel_of=all_on(P.KERNEL_F16W if f16w else P.KERNEL_GEMV))
-                want = P.KERNEL_F16W if f16w else P.KERNEL_GEMV
-                assert all(tap["plan"][w] == want for w in P.KERNEL_WORD.values()), tap["plan"]
-                base = Case(model, layer, tap, kvb, kva, form, aux, small)
-                accept(tap, kvb, kva, model, layer, form, ctx, base.twin)
-                for m in MUTATIONS:
-                    c = base.fork()
-                    launch = m(c)
-                    if launch is None:
-                        continue
-                    applied.add(m.__name__)
-                    got = CHECK[launch](c, ctx)
-                    assert got.fails, f"{ctx}: the checker let {m.__name__} through at {launch} (worst error / bound {got.worst:.3g}, excused {got.excused})"
+    for kind, f16w, h_done in FORMS:
+        model, small = models[kind], kind == "shrunk"
+        for layer in (0, 1):
+            kv_f16 = (pos0 + layer) % 2 == 0
+            ctx = f"{shape} ({kind}) {fmt} {'f16' if f16w else 'row dots'} h_done={h_done} kv_f16={kv_f16} layer {layer} pos0 {pos0}"
+            tap, kvb, kva, form, aux = oracle_pass(model, pos0, N, layer, kv_f16, f16w, h_done,
+                                                   kernel_of=all_on(P.KERNEL_F16W if f16w else P.KERNEL_GEMV))
+            want = P.KERNEL_F16W if f16w else P.KERNEL_GEMV
+            assert all(tap["plan"][w] == want for w in P.KERNEL_WORD.values()), tap["plan"]
+            base = Case(model, layer, tap, kvb, kva, form, aux, small)
+            accept(tap, kvb, kva, model, layer, form, ctx, base.twin)
+            for m in MUTATIONS:
+                c = base.fork()
+                launch = m(c)
+                if launch is None:
+                    continue
+                applied.add(m.__name__)
+                got = CHECK[launch](c, ctx)
+                assert got.fails, f"{ctx}: the checker let {m.__name__} through at {launch} (worst error / bound {got.worst:.3g}, excused {got.excused})"
     skipped = {m.__name__ for m in MUTATIONS} - applied
     allowed = set()
     if synth.SHAPES[shape].arch != "qwen2":
@@ -114,10 +97,9 @@ def wrong_output(c, nm, act_name, wrong):
     acts = P.act_rows(c.tap, act_name)
     if P.kernel_of(c.tap, wname) == P.KERNEL_F16W:
         raw = np.ascontiguousarray(t.data).view(np.uint8).reshape(-1)
-        ap = Q.weight_operands(raw, synth.TYPE_NAMES[t.typ], list(range(m)), k, wrong)[0].astype(np.float32)
+        ap = G.weight_operands(raw, synth.TYPE_NAMES[t.typ], list(range(m)), k, wrong)[0].astype(np.float32)
         return P.b_prime(acts)[1].astype(np.float32) @ ap.T
-    with S.q5_rows(wrong):
-        return R.row_dots_many(t, acts, np.arange(m))[0].astype(np.float32)
+    return R.row_dots_many(t, acts, np.arange(m), wrong=wrong)[0].astype(np.float32)
 
 
 @pytest.mark.parametrize("fmt", FMTS)
@@ -125,23 +107,22 @@ def wrong_output(c, nm, act_name, wrong):
 def test_every_wrong_loader_lands_outside_the_bound_on_both_arms(oracle, shape, fmt):
     model = build(shape, fmt, n_layers=2)
     let_through = []
-    with q5_pass():
-        for f16w, h_done in ((True, 1), (False, 0)):
-            for layer in (0, 1):
-                ctx = f"{shape} {fmt} {'f16' if f16w else 'row dots'} layer {layer}"
-                tap, kvb, kva, form, aux = oracle_pass(model, 0, N, layer, True, f16w, h_done, kernel_of=all_on(P.KERNEL_F16W if f16w else P.KERNEL_GEMV))
-                base = Case(model, layer, tap, kvb, kva, form, aux, False)
-                for wrong in S.WRONG:
-                    for nm, act_name, out_name, parts_name, launch in SITES:
-                        c = base.fork()
-                        out = wrong_output(c, nm, act_name, wrong)
-                        if parts_name in c.tap:  # (the pieces left to the norm launch stay; piece 0 carries the difference)
-                            out = out - np.asarray(c.tap[parts_name], dtype=np.float32).reshape(-1, *out.shape).sum(axis=0)
-                        assert not np.array_equal(out.reshape(-1), np.asarray(c.tap[out_name])), (ctx, wrong, nm)
-                        c.tap[out_name] = np.ascontiguousarray(out, dtype=np.float32).reshape(-1)
-                        got = CHECK[launch](c, ctx)
-                        if not got.fails:
-                            let_through.append((ctx, wrong, nm, round(got.worst, 3)))
+    for f16w, h_done in ((True, 1), (False, 0)):
+        for layer in (0, 1):
+            ctx = f"{shape} {fmt} {'f16' if f16w else 'row dots'} layer {layer}"
+            tap, kvb, kva, form, aux = oracle_pass(model, 0, N, layer, True, f16w, h_done, kernel_of=all_on(P.KERNEL_F16W if f16w else P.KERNEL_GEMV))
+            base = Case(model, layer, tap, kvb, kva, form, aux, False)
+            for wrong in WF.WRONG_Q5_01:
+                for nm, act_name, out_name, parts_name, launch in SITES:
+                    c = base.fork()
+                    out = wrong_output(c, nm, act_name, wrong)
+                    if parts_name in c.tap:  # (the pieces left to the norm launch stay; piece 0 carries the difference)
+                        out = out - np.asarray(c.tap[parts_name], dtype=np.float32).reshape(-1, *out.shape).sum(axis=0)
+                    assert not np.array_equal(out.reshape(-1), np.asarray(c.tap[out_name])), (ctx, wrong, nm)
+                    c.tap[out_name] = np.ascontiguousarray(out, dtype=np.float32).reshape(-1)
+                    got = CHECK[launch](c, ctx)
+                    if not got.fails:
+                        let_through.append((ctx, wrong, nm, round(got.worst, 3)))
     assert not let_through, let_through
 
 
@@ -156,7 +137,7 @@ XH_WITH = {"attn_q": {"attn.xh", "n2.xh", "hid.xh"}, "attn_k": XH - {"n1.xh.v"},
 
 def refused_model(fmt, nm, shape="tiny-gqa"):
     """(the model whose layer-0 matrix nm the range check refuses, the kernel each matrix then takes)"""
-    model = Q.refuse_matrix(build(shape, fmt, seed=53), f"blk.0.{nm}.weight")
+    model = G.refuse_matrix(build(shape, fmt, seed=53), f"blk.0.{nm}.weight")
     return model, (lambda name, t, l: P.KERNEL_GEMV if (l == 0 and name == nm) else P.KERNEL_F16W)
 
 
@@ -165,19 +146,18 @@ def refused_model(fmt, nm, shape="tiny-gqa"):
 def test_mixed_kernel_taps_are_built_and_accepted(oracle, fmt, nm):
     model, kernel_of = refused_model(fmt, nm)
     h_done = 0 if nm == "ffn_up" else 1  # (gate | up fall apart: g and u are stored)
-    with q5_pass():
-        for layer in (0, 1):
-            ctx = f"tiny-gqa {fmt} refused {nm} layer {layer}"
-            tap, kvb, kva, form, aux = oracle_pass(model, 0, N, layer, True, True, h_done, kernel_of=kernel_of)
-            plan = tap["plan"]
-            accept(tap, kvb, kva, model, layer, form, ctx)
-            took = {k: plan[w] for k, w in P.KERNEL_WORD.items()}
-            if layer == 1:  # the control: the default plan
-                assert set(took.values()) == {P.KERNEL_F16W} and plan["qkv_one"] == plan["gu_one"] == 1 and XH & set(tap) == XH - {"n1.xh.v"}, plan
-                continue
-            assert took == {k: (P.KERNEL_GEMV if k == nm else P.KERNEL_F16W) for k in P.KERNEL_WORD}, plan
-            assert plan["qkv_one"] == (0 if nm in ("attn_q", "attn_k") else 1) and plan["gu_one"] == (0 if nm == "ffn_up" else 1), plan
-            assert XH & set(tap) == XH_WITH[nm], (nm, XH & set(tap))
+    for layer in (0, 1):
+        ctx = f"tiny-gqa {fmt} refused {nm} layer {layer}"
+        tap, kvb, kva, form, aux = oracle_pass(model, 0, N, layer, True, True, h_done, kernel_of=kernel_of)
+        plan = tap["plan"]
+        accept(tap, kvb, kva, model, layer, form, ctx)
+        took = {k: plan[w] for k, w in P.KERNEL_WORD.items()}
+        if layer == 1:  # the control: the default plan
+            assert set(took.values()) == {P.KERNEL_F16W} and plan["qkv_one"] == plan["gu_one"] == 1 and XH & set(tap) == XH - {"n1.xh.v"}, plan
+            continue
+        assert took == {k: (P.KERNEL_GEMV if k == nm else P.KERNEL_F16W) for k in P.KERNEL_WORD}, plan
+        assert plan["qkv_one"] == (0 if nm in ("attn_q", "attn_k") else 1) and plan["gu_one"] == (0 if nm == "ffn_up" else 1), plan
+        assert XH & set(tap) == XH_WITH[nm], (nm, XH & set(tap))
 
 
 # ---- the caps are conditions on the reference: evaluated before any device value ----
@@ -187,13 +167,12 @@ def test_interval_check_models_of_the_gpu_cases_stay_under_the_cap(oracle, kind,
     """the models tests/test_hip_prefill_q5_01_launches.py builds for its flipped-sign and shrunk-residual cases (tiny-gqa; seeds 49 and
     50, the first tried): oracle-made taps of layers 0 and 1 are accepted with every excused share of the Q8_0 / Q8_1 interval checks
     under EXCUSED_CAP"""
-    model = S.flip_signs(build("tiny-gqa", fmt, seed=49)) if kind == "signs" else S.shrink_residual(build("tiny-gqa", fmt, seed=50))
+    model = R.flip_signs(build("tiny-gqa", fmt, seed=49)) if kind == "signs" else R.shrink_residual(build("tiny-gqa", fmt, seed=50))
     f16w = kind != "shrunk-row-dots"
-    with q5_pass():
-        for layer in (0, 1):
-            ctx = f"{kind} tiny-gqa {fmt} layer {layer}"
-            tap, kvb, kva, form, aux = oracle_pass(model, 0, N, layer, True, f16w, 1 if f16w else 0, kernel_of=all_on(P.KERNEL_F16W if f16w else P.KERNEL_GEMV))
-            accept(tap, kvb, kva, model, layer, form, ctx)
+    for layer in (0, 1):
+        ctx = f"{kind} tiny-gqa {fmt} layer {layer}"
+        tap, kvb, kva, form, aux = oracle_pass(model, 0, N, layer, True, f16w, 1 if f16w else 0, kernel_of=all_on(P.KERNEL_F16W if f16w else P.KERNEL_GEMV))
+        accept(tap, kvb, kva, model, layer, form, ctx)
 
 
 # ---- the overflow case's model: h past 65504 (B' of ffn_down overflows f16), below 127 * 65504 (the rows' f16 scales stay finite) ----
@@ -219,8 +198,7 @@ def overflow_tokens(model, n=64):
 def overflow_pass(fmt, log2=None):
     """the oracle's ops on the 64 tokens the GPU case runs, row by row (what the recomputation runs), layer 0 tapped"""
     model = overflow_model(fmt, log2)
-    with q5_pass():
-        return oracle_pass(model, 0, 64, 0, True, False, 0, kernel_of=all_on(P.KERNEL_GEMV), toks=overflow_tokens(model), seq=80)
+    return oracle_pass(model, 0, 64, 0, True, False, 0, kernel_of=all_on(P.KERNEL_GEMV), toks=overflow_tokens(model), seq=80)
 
 
 def test_q5_0_overflow_model_puts_h_past_f16_and_below_the_rows_scale_range(oracle):

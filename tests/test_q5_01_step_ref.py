@@ -1,4 +1,4 @@
-"""The Q5_0 / Q5_1 checker (tests/q5_01_step_ref.py) checked on the CPU: its unpack against the reference's dequantizer bit for bit
+"""The Q5_0 / Q5_1 checker (tests/fused_step_ref.py with the format's row of tests/weight_formats.py) checked on the CPU: its unpack against the reference's dequantizer bit for bit
 (random blocks and tests/edge_blocks.py's: every qh bit set, none, levels at both ends), its bound against an f32 emulation of the
 kernels' terms in permuted add orders, every subtly wrong loader it must reject, and -- from the reference alone, an oracle-built
 tap of the step (tests/test_fused_step_ref.oracle_tap) -- that it accepts the reference's own order, rejects every mutation of
@@ -11,7 +11,7 @@ from crabml_amd import synth
 from oracle import oracle as o
 from tests import edge_blocks as eb
 from tests import fused_step_ref as R
-from tests import q5_01_step_ref as Q
+from tests import weight_formats as WF
 from tests import test_fused_step_ref as T
 from tests.helpers import EXACT_NORM, GEMV_REL
 from tests.test_q5k_step_ref import oracle_tokens
@@ -44,9 +44,9 @@ def build(case):
     key, shape, fmt, seed, kw = case[:5]
     model = synth.build_model(shape_of(shape), FMT[fmt], seed=seed, **kw)
     if key.startswith("signs/"):
-        Q.flip_signs(model)
+        R.flip_signs(model)
     if key.startswith("shrunk/"):
-        Q.shrink_residual(model)
+        R.shrink_residual(model)
     return model
 
 
@@ -62,7 +62,7 @@ def rhs(rng, typ, k):
 def restated_f32(t):
     """the dequantized elements as the restatement gives them, in the reference's own f32 steps: (level - 16) as f32 times d
     (buf_q5_0.rs:22-37), level as f32 times d plus m (buf_q5_1.rs:20-36)"""
-    w = Q.weight_rows(t, 0, t.shape[0])
+    w = R.weight_rows(t, 0, t.shape[0])
     f = np.float32
     if t.typ == synth.Q5_0:
         return (w["q"].astype(f) * w["d"].astype(f)[:, :, None]).reshape(-1)
@@ -82,9 +82,9 @@ def test_restated_rows_equal_the_reference_dequantizer(oracle, fmt):
     rng = np.random.default_rng(4)
     t = tensor(rng, typ, 8, 512)
     assert same_bits(restated_f32(t), o.dequantize(t.data, typ))
-    w = Q.weight_rows(t, 0, 8)
+    w = R.weight_rows(t, 0, 8)
     assert w["q"].max() == (15 if fmt == "Q5_0" else 31) and w["q"].min() == (-16 if fmt == "Q5_0" else 0)
-    assert np.any(Q.levels(w["qs"], w["qh"]) != Q.levels(w["qs"], w["qh"], "qh_bits_dropped"))
+    assert np.any(WF.q5_levels(w["qs"], w["qh"]) != WF.q5_levels(w["qs"], w["qh"], "qh_bits_dropped"))
     for kind in ("saturated", "sign", "mixed"):
         raw = eb.edge_blocks(rng, fmt, 8, 512, kind)
         if kind == "saturated":  # alternating fifth bits, both phases
@@ -95,7 +95,7 @@ def test_restated_rows_equal_the_reference_dequantizer(oracle, fmt):
         te = synth.RawTensor(raw, [8, 512], typ)
         assert same_bits(restated_f32(te), o.dequantize(te.data, typ)), kind
         if kind == "saturated":
-            lv = Q.levels(Q.weight_rows(te, 0, 8)["qs"], Q.weight_rows(te, 0, 8)["qh"])
+            lv = WF.q5_levels(R.weight_rows(te, 0, 8)["qs"], R.weight_rows(te, 0, 8)["qh"])
             assert {0, 15, 16, 31} <= set(np.unique(lv).tolist())
 
 
@@ -110,10 +110,10 @@ def test_bound_holds_an_f32_emulation_in_permuted_orders(oracle, fmt, k):
     rows = 48
     t = tensor(rng, typ, rows, k)
     act = rhs(rng, typ, k)
-    exact, bound = Q.row_dots(t, act)
-    w = Q.weight_rows(t, 0, rows)
+    exact, bound = R.row_dots(t, act)
+    w = R.weight_rows(t, 0, rows)
     f = np.float32
-    lv = Q.levels(w["qs"], w["qh"])
+    lv = WF.q5_levels(w["qs"], w["qh"])
     sumi = np.einsum("rbi,bi->rb", lv - (16 if fmt == "Q5_0" else 0), act["q"].astype(np.int64))
     assert np.abs(sumi).max() < 2 ** 24
     if fmt == "Q5_0":
@@ -148,7 +148,7 @@ def _blocks_of(act, like):
     return b.reshape(-1).view(like.dtype)
 
 
-@pytest.mark.parametrize("wrong", list(Q.WRONG) + ["last_block_dropped"])
+@pytest.mark.parametrize("wrong", list(WF.WRONG_Q5_01) + ["last_block_dropped"])
 @pytest.mark.parametrize("fmt", ["Q5_0", "Q5_1"])
 def test_every_wrong_loader_is_rejected(oracle, fmt, wrong):
     typ = FMT[fmt]
@@ -156,11 +156,11 @@ def test_every_wrong_loader_is_rejected(oracle, fmt, wrong):
     for k in (288, 4160):
         t = tensor(rng, typ, 64, k)
         act = rhs(rng, typ, k)
-        exact, bound = Q.row_dots(t, act)
+        exact, bound = R.row_dots(t, act)
         if wrong == "last_block_dropped":
-            got, _ = Q.row_dots(t, act, drop_last_block=True)
+            got, _ = R.row_dots(t, act, drop_last_block=True)
         else:
-            got, _ = Q.row_dots(t, act, wrong=wrong)
+            got, _ = R.row_dots(t, act, wrong=wrong)
         out = np.abs(got.astype(np.float32).astype(np.float64) - exact) > bound
         assert out.mean() > 0.9, (fmt, wrong, k, float(out.mean()))
 
@@ -186,29 +186,28 @@ def test_checker_accepts_the_oracle_step_and_rejects_every_mutation(oracle, shap
     residual stream, where a wrong eps cannot pass), Q5_1 in the exact-norm form; layers 0 and 1"""
     typ = FMT[fmt]
     plain = synth.build_model(synth.SHAPES[shape], typ, seed=21, n_layers=2)
-    shrunk = Q.shrink_residual(synth.build_model(synth.SHAPES[shape], typ, seed=21, n_layers=2))
+    shrunk = R.shrink_residual(synth.build_model(synth.SHAPES[shape], typ, seed=21, n_layers=2))
     applied = set()
     forms = [(plain, False, False)] + ([(plain, True, False), (shrunk, True, True)] if fmt == "Q5_0" else [])
-    with Q.q5_rows():
-        for model, hop_free, small in forms:
-            for layer in (0, 1):
-                kv_f16 = (pos + layer) % 2 == 0
-                ctx = f"{shape}{' (shrunk residual)' if small else ''} {fmt} {'hop-free' if hop_free else 'exact-norm'} kv_f16={kv_f16} layer {layer} pos {pos}"
-                tap, kc, vc, form, aux = T.oracle_tap(model, pos, layer, kv_f16, hop_free)
-                res = R.check_layer(tap, kc, vc, model, layer, pos, form, ctx)
-                assert not R.failures(res), R.failures(res)
-                for r in res.values():
-                    for name, share in r.excused.items():
-                        assert share <= R.EXCUSED_CAP, (ctx, r.launch, name, share)
-                base = T.Case(model, layer, pos, tap, kc, vc, form, aux, small)
-                for m in T.MUTATIONS:
-                    c = base.fork()
-                    launch = m(c)
-                    if launch is None:
-                        continue
-                    applied.add(m.__name__)
-                    got = T.CHECK[launch](c, ctx)
-                    assert got.fails, f"{ctx}: the checker let {m.__name__} through at {launch} (worst error / bound {got.worst:.3g}, excused {got.excused})"
+    for model, hop_free, small in forms:
+        for layer in (0, 1):
+            kv_f16 = (pos + layer) % 2 == 0
+            ctx = f"{shape}{' (shrunk residual)' if small else ''} {fmt} {'hop-free' if hop_free else 'exact-norm'} kv_f16={kv_f16} layer {layer} pos {pos}"
+            tap, kc, vc, form, aux = T.oracle_tap(model, pos, layer, kv_f16, hop_free)
+            res = R.check_layer(tap, kc, vc, model, layer, pos, form, ctx)
+            assert not R.failures(res), R.failures(res)
+            for r in res.values():
+                for name, share in r.excused.items():
+                    assert share <= R.EXCUSED_CAP, (ctx, r.launch, name, share)
+            base = T.Case(model, layer, pos, tap, kc, vc, form, aux, small)
+            for m in T.MUTATIONS:
+                c = base.fork()
+                launch = m(c)
+                if launch is None:
+                    continue
+                applied.add(m.__name__)
+                got = T.CHECK[launch](c, ctx)
+                assert got.fails, f"{ctx}: the checker let {m.__name__} through at {launch} (worst error / bound {got.worst:.3g}, excused {got.excused})"
     skipped = {m.__name__ for m in T.MUTATIONS} - applied
     allowed = set()
     if synth.SHAPES[shape].arch != "qwen2":
@@ -227,15 +226,15 @@ def test_checker_accepts_the_oracle_step_and_rejects_every_mutation(oracle, shap
 @pytest.mark.parametrize("fmt", ["Q5_0", "Q5_1"])
 def test_wrong_rows_fail_in_the_launch_that_owns_them(oracle, fmt):
     """through check_layer: wo's x built from each wrong loader's dots fails at `wo`"""
-    model = Q.flip_signs(synth.build_model(synth.SHAPES["tiny-gqa"], FMT[fmt], seed=22, n_layers=2))
+    model = R.flip_signs(synth.build_model(synth.SHAPES["tiny-gqa"], FMT[fmt], seed=22, n_layers=2))
     tap, kc, vc, form, _ = T.oracle_tap(model, 7, 1, True, fmt == "Q5_0")
-    assert not Q.failures(Q.check_layer(tap, kc, vc, model, 1, 7, form, "oracle"))
+    assert not R.failures(R.check_layer(tap, kc, vc, model, 1, 7, form, "oracle"))
     act = R.parse_act(tap["attn.act_attn"], tap["qtype"]["attn.act_attn"])
-    for wrong in list(Q.WRONG) + [True]:
-        dots = Q.row_dots(model.tensors["blk.1.attn_output.weight"], act, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
+    for wrong in list(WF.WRONG_Q5_01) + [True]:
+        dots = R.row_dots(model.tensors["blk.1.attn_output.weight"], act, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
         bad = dict(tap)
         bad["wo.x"] = (np.asarray(tap["qkv_in.x"], dtype=np.float64) + dots).astype(np.float32)
-        got = Q.check_layer(bad, kc, vc, model, 1, 7, form, "mutant")["wo"]
+        got = R.check_layer(bad, kc, vc, model, 1, 7, form, "mutant")["wo"]
         assert any("x row" in f for f in got.fails), (wrong, got.fails, got.worst)
 
 
@@ -255,13 +254,12 @@ def test_oracle_step_passes_and_excused_shares_stay_under_the_cap(oracle, case):
                 cls_stand_in = path == 1 and "output.weight" in model.tensors and model.tensors["output.weight"].typ != model.wtype
                 if cls_stand_in:
                     tap = {k: v for k, v in tap.items() if k != "logits"}
-                with Q.q5_rows():
-                    res = {k: v for k, v in _check(tap, kc, vc, model, layer, pos, form, ctx, cls_stand_in).items()}
-                assert not Q.failures(res), Q.failures(res)
+                res = {k: v for k, v in _check(tap, kc, vc, model, layer, pos, form, ctx, cls_stand_in).items()}
+                assert not R.failures(res), R.failures(res)
                 for r in res.values():
                     for name, share in r.excused.items():
                         shares.append(share)
-                        assert share <= Q.EXCUSED_CAP, (ctx, r.launch, name, share)
+                        assert share <= R.EXCUSED_CAP, (ctx, r.launch, name, share)
     assert shares or path == 2  # (the stand-alone quantizer launches of path 2 are held byte for byte: nothing to excuse)
     if shares:
         print(f"{key}: excused shares: max {max(shares):.3f}, mean {np.mean(shares):.3f} over {len(shares)} plane sets")

@@ -1,4 +1,4 @@
-"""The Q5_K checker (tests/q5k_step_ref.py) checked on the CPU: its unpack against the reference's dequantizer, its bound against an f32
+"""The Q5_K checker (tests/fused_step_ref.py with the format's row of tests/weight_formats.py) checked on the CPU: its unpack against the reference's dequantizer, its bound against an f32
 emulation of the kernel's term in permuted add orders, every subtly wrong kernel it must reject, and -- from the reference alone, an
 oracle-built tap of the step -- that it accepts the reference's own order and that the Q8_K interval check excuses no more than
 EXCUSED_CAP of any plane set for the shapes, seeds and positions tests/test_hip_q5k_fused.py uses (CASES below is that file's list:
@@ -11,7 +11,7 @@ import pytest
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import fused_step_ref as R
-from tests import q5k_step_ref as Q
+from tests import weight_formats as WF
 from tests import test_fused_step_ref as T
 
 # (key, shape, seed, build_model keywords, seq, positions, layers): the models of the GPU file.  A Llama / Qwen2 shape gets a Q6_K
@@ -42,9 +42,9 @@ def build(case):
     key, shape, seed, kw, _, _, _ = case
     model = synth.build_model(shape_of(shape), synth.Q5_K, seed=seed, **kw)
     if key.startswith("signs/"):
-        Q.flip_signs(model)
+        R.flip_signs(model)
     if key.startswith("shrunk/"):
-        Q.shrink_residual(model, log2=9)
+        R.shrink_residual(model, log2=9)
     if key.startswith("mixed-signs/"):
         from tests import edge_blocks as eb
         model = eb.flip_scale_signs(model, np.random.default_rng([seed, 1]))
@@ -75,14 +75,14 @@ def test_q5_k_rows_of_the_restatement_equal_the_reference_dequantizer(oracle):
     dequantize, in its own f32 steps"""
     rng = np.random.default_rng(4)
     t = q5k_tensor(rng, 8, 512)
-    w = Q.weight_rows(t, 0, 8)
+    w = R.weight_rows(t, 0, 8)
     f = np.float32
     d1 = (w["d"].astype(f)[:, :, None] * w["sc"].astype(f))[:, :, :, None]
     m1 = (w["dmin"].astype(f)[:, :, None] * w["mn"].astype(f))[:, :, :, None]
     mine = d1 * w["q"].reshape(8, 2, 8, 32).astype(f) - m1
     assert np.array_equal(mine.reshape(-1), o.dequantize(t.data, o.Q5_K))
     assert w["q"].max() == 31 and w["q"].min() == 0 and np.any(w["q"] != w["nib"])
-    assert np.allclose(Q.k_values(w).reshape(-1), mine.reshape(-1).astype(np.float64), rtol=1e-6, atol=0)
+    assert np.allclose(R.k_values(w).reshape(-1), mine.reshape(-1).astype(np.float64), rtol=1e-6, atol=0)
 
 
 @pytest.mark.parametrize("k", [512, 1792, 4096, 14336])
@@ -96,8 +96,8 @@ def test_bound_holds_an_f32_emulation_in_permuted_orders(oracle, k):
     rows = 48
     t = q5k_tensor(rng, rows, k)
     act = q8k(rng, k)
-    exact, bound = Q.row_dots(t, act)
-    w = Q.weight_rows(t, 0, rows)
+    exact, bound = R.row_dots(t, act)
+    w = R.weight_rows(t, 0, rows)
     f = np.float32
     # the exact integers, formed here in int64 (not taken from k_pieces)
     nsb = k // 256
@@ -116,11 +116,11 @@ def test_bound_holds_an_f32_emulation_in_permuted_orders(oracle, k):
         for j in order:
             acc = (acc + terms[:, j]).astype(f)
         assert np.all(np.abs(acc.astype(np.float64) - exact) <= bound), (k, float(np.max(np.abs(acc - exact) / bound)))
-    proj = GEMV_REL * (np.abs(Q.k_values(w)) @ np.abs(R.act_values(act)))
+    proj = GEMV_REL * (np.abs(R.k_values(w)) @ np.abs(R.act_values(act)))
     assert np.all(bound <= 8 * proj), (k, float(np.max(bound / proj)))
 
 
-@pytest.mark.parametrize("wrong", list(Q.WRONG) + ["last_block_dropped"])
+@pytest.mark.parametrize("wrong", list(WF.FORMATS[synth.Q5_K].wrong) + ["last_block_dropped"])
 def test_every_wrong_kernel_is_rejected(oracle, wrong):
     """a kernel that drops the fifth bit, swaps the low / high nibbles' fifth bits, shifts qh for the wrong pair, takes a neighbouring
     sub-block's scale or minimum, adds the minimum term, or stops one super-block early lands outside the bound"""
@@ -128,11 +128,11 @@ def test_every_wrong_kernel_is_rejected(oracle, wrong):
     for k in (512, 1792):
         t = q5k_tensor(rng, 64, k)
         act = q8k(rng, k)
-        exact, bound = Q.row_dots(t, act)
+        exact, bound = R.row_dots(t, act)
         if wrong == "last_block_dropped":
-            got, _ = Q.row_dots(t, act, drop_last_block=True)
+            got, _ = R.row_dots(t, act, drop_last_block=True)
         else:
-            got, _ = Q.row_dots(t, act, wrong=wrong)
+            got, _ = R.row_dots(t, act, wrong=wrong)
         out = np.abs(got.astype(np.float32).astype(np.float64) - exact) > bound
         # (a neighbouring scale / minimum may equal the right one on a row: 6-bit fields)
         assert out.mean() > 0.9, (wrong, k, float(out.mean()))
@@ -147,14 +147,14 @@ def test_wrong_rows_fail_in_the_launch_that_owns_them(oracle):
     """through check_layer: wo's x built from each wrong kernel's dots fails at `wo` (the oracle's own tap passes)"""
     model = synth.build_model(synth.SHAPES["tiny-gqa"], synth.Q5_K, seed=22, n_layers=2, output_type=synth.Q6_K)
     tap, kc, vc, form, aux = _tap(model, 7, 1)
-    res = Q.check_layer(tap, kc, vc, model, 1, 7, form, "oracle", twin=aux["twin"])
-    assert not Q.failures(res), Q.failures(res)
+    res = R.check_layer(tap, kc, vc, model, 1, 7, form, "oracle", twin=aux["twin"])
+    assert not R.failures(res), R.failures(res)
     rhs = R._rhs(tap, "attn.act_attn", "attn.attn", o.Q8_K)
-    for wrong in list(Q.WRONG) + [True]:
-        dots = Q.row_dots(model.tensors["blk.1.attn_output.weight"], rhs, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
+    for wrong in list(WF.FORMATS[synth.Q5_K].wrong) + [True]:
+        dots = R.row_dots(model.tensors["blk.1.attn_output.weight"], rhs, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
         bad = dict(tap)
         bad["wo.x"] = (np.asarray(tap["qkv_in.x"], dtype=np.float64) + dots).astype(np.float32)
-        got = Q.check_layer(bad, kc, vc, model, 1, 7, form, "mutant", twin=aux["twin"])["wo"]
+        got = R.check_layer(bad, kc, vc, model, 1, 7, form, "mutant", twin=aux["twin"])["wo"]
         assert any("x row" in f for f in got.fails), (wrong, got.fails, got.worst)
 
 
@@ -173,11 +173,11 @@ def test_oracle_step_passes_and_excused_shares_stay_under_the_cap(oracle, case):
                 for form in (("default", "no-k-norm-in", "no-rhs-prologue") if key.startswith("flags/") else ("default",)):  # (the forms that case taps)
                     tap, kc, vc, frm, aux = _tap(model, pos, layer, form)
                     ctx = f"{key} {form} layer {layer} pos {pos}"
-                    res = Q.check_layer(tap, kc, vc, model, layer, pos, frm, ctx, twin=aux["twin"])
-                    assert not Q.failures(res), Q.failures(res)
+                    res = R.check_layer(tap, kc, vc, model, layer, pos, frm, ctx, twin=aux["twin"])
+                    assert not R.failures(res), R.failures(res)
                     for r in res.values():
                         for name, share in r.excused.items():
                             shares.append(share)
-                            assert share <= Q.EXCUSED_CAP, (ctx, r.launch, name, share)
+                            assert share <= R.EXCUSED_CAP, (ctx, r.launch, name, share)
     assert shares
     print(f"{key}: excused shares of the Q8_K interval check: max {max(shares):.2e}, mean {np.mean(shares):.2e} over {len(shares)} plane sets")

@@ -1,4 +1,4 @@
-"""The Q6_K checker (tests/q6k_step_ref.py) checked on the CPU: its unpack against the reference's dequantizer, its bound against an f32
+"""The Q6_K checker (tests/fused_step_ref.py with the format's row of tests/weight_formats.py) checked on the CPU: its unpack against the reference's dequantizer, its bound against an f32
 emulation of the kernel's term in permuted add orders, every subtly wrong kernel it must reject, and -- from the reference alone, an
 oracle-built tap of the step -- that it accepts the reference's own order and that the Q8_K interval check excuses no more than
 EXCUSED_CAP of any plane set for the shapes, seeds and positions tests/test_hip_q6k_fused.py uses (CASES below is that file's list:
@@ -9,7 +9,7 @@ import pytest
 from crabml_amd import synth
 from oracle import oracle as o
 from tests import fused_step_ref as R
-from tests import q6k_step_ref as Q
+from tests import weight_formats as WF
 from tests.test_q5k_step_ref import _tap, oracle_tokens, q8k, shape_of
 
 # (key, shape, seed, build_model keywords, seq, positions, layers): the models of the GPU file, every layer matrix Q6_K.  The classifier
@@ -34,9 +34,9 @@ def build(case):
     key, shape, seed, kw, _, _, _ = case
     model = synth.build_model(shape_of(shape), synth.Q6_K, seed=seed, **kw)
     if key.startswith("signs/"):
-        Q.flip_signs(model)
+        R.flip_signs(model)
     if key.startswith("shrunk/"):
-        Q.shrink_residual(model, log2=9)
+        R.shrink_residual(model, log2=9)
     if key.startswith("mixed-signs/"):
         from tests import edge_blocks as eb
         model = eb.flip_scale_signs(model, np.random.default_rng([seed, 1]))
@@ -52,19 +52,34 @@ def test_q6_k_rows_of_the_restatement_equal_the_reference_dequantizer(oracle):
     oracle's dequantize, in its own f32 steps (buf_q6_k.rs:21-48: d * scale first, then times the level)"""
     rng = np.random.default_rng(4)
     t = q6k_tensor(rng, 8, 512)
-    w = Q.weight_rows(t, 0, 8)
+    w = R.weight_rows(t, 0, 8)
     f = np.float32
-    lv = (Q.levels(w["lo4"], w["qh"]) - 32).reshape(8, 2, 16, 16)
-    assert lv.max() == 31 and lv.min() == -32 and np.any(Q.levels(w["lo4"], w["qh"]) != Q.levels(w["lo4"], w["qh"], drop=True))
+    lv = (WF.q6_levels(w["lo4"], w["qh"]) - 32).reshape(8, 2, 16, 16)
+    assert lv.max() == 31 and lv.min() == -32 and np.any(WF.q6_levels(w["lo4"], w["qh"]) != WF.q6_levels(w["lo4"], w["qh"], drop=True))
     mine = (w["d"].astype(f)[:, :, None] * w["sc"].astype(f))[:, :, :, None] * lv.astype(f)
     assert np.array_equal(mine.reshape(-1), o.dequantize(t.data, o.Q6_K))
     assert np.allclose(R.k_values(w).reshape(-1), mine.reshape(-1).astype(np.float64), rtol=1e-6, atol=0)
-    # ... and this module's pieces are fused_step_ref's
+    # ... and the pieces from the raw fields (lo4, qh) are the pieces from the dequantizer-order levels q6
     act = q8k(rng, 512)
-    for mine_, theirs in zip(Q.k_pieces(w, act), R.k_pieces(w, act)):
-        assert np.array_equal(mine_, theirs)
-    for mine_, theirs in zip(Q.k_pieces(w, act, "q6_scale_shift"), R.k_pieces(w, act, "q6_scale_shift")):
-        assert np.array_equal(mine_, theirs)
+    for wrong in (None, "q6_scale_shift"):
+        for mine_, theirs in zip(WF.q6_k_dots(w, act, wrong), _pieces_of_q6(w, act, wrong)):
+            assert np.array_equal(mine_, theirs)
+
+
+def _pieces_of_q6(w, act, wrong=None):
+    """the Q6_K pieces formed from the reader's q6 (the levels in the dequantizer's order): sum (q6 - 32) q8 as the kernel forms it, the
+    6-bit levels against q8, minus 32 times the bsums entry it read"""
+    r, nsb = w["d"].shape
+    d8, bs = act["d"], act["bsums"].astype(np.float64)
+    x = act["q"].astype(np.float64).reshape(nsb, 16, 16)
+    G = np.einsum("rsgi,sgi->rsg", w["q6"].reshape(r, nsb, 16, 16) + 32.0, x) - 32.0 * bs[None]
+    sc = w["sc"]
+    if wrong == "q6_scale_shift":
+        sc = sc.copy()
+        sc[:, 0, 5] = w["sc"][:, 0, 6]
+    G = (sc * G).reshape(r, nsb, 2, 2, 4)  # group 8 h + 4 hi + j; a piece: the low nibbles of group 8 h + j, the high of 8 h + 4 + j
+    dd = (w["d"] * d8[None])[:, :, None, None]
+    return (dd * (G[:, :, :, 0] + G[:, :, :, 1])).reshape(r, nsb, 8), (np.abs(dd) * (np.abs(G[:, :, :, 0]) + np.abs(G[:, :, :, 1]))).reshape(r, nsb, 8)
 
 
 @pytest.mark.parametrize("k", [512, 1792, 4096, 14336])
@@ -78,13 +93,13 @@ def test_bound_holds_an_f32_emulation_in_permuted_orders(oracle, k):
     rows = 48
     t = q6k_tensor(rng, rows, k)
     act = q8k(rng, k)
-    exact, bound = Q.row_dots(t, act)
-    w = Q.weight_rows(t, 0, rows)
+    exact, bound = R.row_dots(t, act)
+    w = R.weight_rows(t, 0, rows)
     f = np.float32
     # the exact integers, formed here in int64 (not taken from k_pieces): levels 0 .. 63 against q8, minus 32 bsums, times the scale
     nsb = k // 256
     x = act["q"].astype(np.int64).reshape(nsb, 16, 16)
-    S = np.einsum("rsgi,sgi->rsg", Q.levels(w["lo4"], w["qh"]).reshape(rows, nsb, 16, 16), x) - 32 * act["bsums"].astype(np.int64)[None]
+    S = np.einsum("rsgi,sgi->rsg", WF.q6_levels(w["lo4"], w["qh"]).reshape(rows, nsb, 16, 16), x) - 32 * act["bsums"].astype(np.int64)[None]
     G = (w["sc"].astype(np.int64) * S).reshape(rows, nsb, 2, 2, 4)
     assert np.abs(G).max() < 2 ** 31
     dd = (w["d"].astype(f) * act["d"].astype(f)[None])[:, :, None, None]
@@ -99,7 +114,7 @@ def test_bound_holds_an_f32_emulation_in_permuted_orders(oracle, k):
     assert np.all(bound <= 8 * proj), (k, float(np.max(bound / proj)))
 
 
-@pytest.mark.parametrize("wrong", list(Q.WRONG) + ["last_block_dropped"])
+@pytest.mark.parametrize("wrong", list(WF.FORMATS[synth.Q6_K].wrong) + ["last_block_dropped"])
 def test_every_wrong_kernel_is_rejected(oracle, wrong):
     """a kernel that drops the two qh bits, takes them with the twin lane's shift, swaps the low / high scales, takes a neighbouring
     scale, drops the -32 * bsum offset, reads a neighbouring bsums entry, loses the sign of d, or stops one super-block early lands
@@ -111,11 +126,11 @@ def test_every_wrong_kernel_is_rejected(oracle, wrong):
             blk = t.data.reshape(-1, 210)
             blk[::2, 209] ^= 0x80
         act = q8k(rng, k)
-        exact, bound = Q.row_dots(t, act)
+        exact, bound = R.row_dots(t, act)
         if wrong == "last_block_dropped":
-            got, _ = Q.row_dots(t, act, drop_last_block=True)
+            got, _ = R.row_dots(t, act, drop_last_block=True)
         else:
-            got, _ = Q.row_dots(t, act, wrong=wrong)
+            got, _ = R.row_dots(t, act, wrong=wrong)
         out = np.abs(got.astype(np.float32).astype(np.float64) - exact) > bound
         # (a neighbouring scale may equal the right one on a row)
         assert out.mean() > 0.9, (wrong, k, float(out.mean()))
@@ -123,16 +138,16 @@ def test_every_wrong_kernel_is_rejected(oracle, wrong):
 
 def test_wrong_rows_fail_in_the_launch_that_owns_them(oracle):
     """through check_layer: wo's x built from each wrong kernel's dots fails at `wo` (the oracle's own tap passes)"""
-    model = Q.flip_signs(synth.build_model(synth.SHAPES["tiny-gqa"], synth.Q6_K, seed=22, n_layers=2))
+    model = R.flip_signs(synth.build_model(synth.SHAPES["tiny-gqa"], synth.Q6_K, seed=22, n_layers=2))
     tap, kc, vc, form, aux = _tap(model, 7, 1)
-    res = Q.check_layer(tap, kc, vc, model, 1, 7, form, "oracle", twin=aux["twin"])
-    assert not Q.failures(res), Q.failures(res)
+    res = R.check_layer(tap, kc, vc, model, 1, 7, form, "oracle", twin=aux["twin"])
+    assert not R.failures(res), R.failures(res)
     rhs = R._rhs(tap, "attn.act_attn", "attn.attn", o.Q8_K)
-    for wrong in list(Q.WRONG) + [True]:
-        dots = Q.row_dots(model.tensors["blk.1.attn_output.weight"], rhs, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
+    for wrong in list(WF.FORMATS[synth.Q6_K].wrong) + [True]:
+        dots = R.row_dots(model.tensors["blk.1.attn_output.weight"], rhs, drop_last_block=wrong is True, wrong=None if wrong is True else wrong)[0]
         bad = dict(tap)
         bad["wo.x"] = (np.asarray(tap["qkv_in.x"], dtype=np.float64) + dots).astype(np.float32)
-        got = Q.check_layer(bad, kc, vc, model, 1, 7, form, "mutant", twin=aux["twin"])["wo"]
+        got = R.check_layer(bad, kc, vc, model, 1, 7, form, "mutant", twin=aux["twin"])["wo"]
         assert any("x row" in f for f in got.fails), (wrong, got.fails, got.worst)
 
 
@@ -151,11 +166,11 @@ def test_oracle_step_passes_and_excused_shares_stay_under_the_cap(oracle, case):
                 for form in (("default", "no-k-norm-in", "no-rhs-prologue") if key.startswith("flags/") else ("default",)):  # (the forms that case taps)
                     tap, kc, vc, frm, aux = _tap(model, pos, layer, form)
                     ctx = f"{key} {form} layer {layer} pos {pos}"
-                    res = Q.check_layer(tap, kc, vc, model, layer, pos, frm, ctx, twin=aux["twin"])
-                    assert not Q.failures(res), Q.failures(res)
+                    res = R.check_layer(tap, kc, vc, model, layer, pos, frm, ctx, twin=aux["twin"])
+                    assert not R.failures(res), R.failures(res)
                     for r in res.values():
                         for name, share in r.excused.items():
                             shares.append(share)
-                            assert share <= Q.EXCUSED_CAP, (ctx, r.launch, name, share)
+                            assert share <= R.EXCUSED_CAP, (ctx, r.launch, name, share)
     assert shares
     print(f"{key}: excused shares of the Q8_K interval check: max {max(shares):.2e}, mean {np.mean(shares):.2e} over {len(shares)} plane sets")
