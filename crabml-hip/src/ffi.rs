@@ -67,6 +67,8 @@ pub struct crabml_hip_llama_config_t {
     pub seq_len: usize,
     pub rope_dim: usize,
     pub rms_norm_eps: f32,
+    // the kind of KV cache: 0 = f32, 1 = f16, 2 (CRABML_HIP_KV_CACHE_Q8) = 8-bit -- per 32 elements of a head's K or V row, int8 values
+    // and one f16 scale; served on the fast device, one GPU, the context's own cache, head_dim 64 / 128, GQA groups 1 .. 8
     pub use_f16_kv_cache: i32,
     pub flags: i32,
     pub tp_size: i32,

@@ -47,6 +47,8 @@ impl HipLlamaRunner {
         weights: Arc<LlamaWeights<HipTensor>>,
         device: HipTensorDeviceRef,
         seq_len: usize,
+        // (the C field also takes 2, CRABML_HIP_KV_CACHE_Q8 -- the 8-bit cache, int8 values and one f16 scale per 32 elements; the
+        // reference's runner knows the f32 and the f16 cache, so this constructor passes 0 or 1)
         use_f16_kv_cache: bool,
     ) -> Result<Self> {
         // Qwen2 = forward_llama + q / k / v biases + NEOX rope (llama2.rs:283-351)

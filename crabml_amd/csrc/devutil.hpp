@@ -152,6 +152,13 @@ __device__ __forceinline__ int q8_aux(int sum, float dd) {
   else
     return sum;
 }
+// The quantizer of the Q8 KV cache (use_f16_kv_cache == 2), per element.  The block stores d = f16(max|x| / 127); `d` here
+// is that stored scale as f32, so that q * d is what every reader computes: q = x / d rounded to nearest (ties to even), clamped to
+// +-127; d = 0 (an all-zero block, or a maximum whose scale underflows f16): q = 0.  Not q8_quant<false>: that is the reference's rhs
+// rule, which TRUNCATES x / d -- a full step of error, on a value that is read back by every later token.
+__device__ __forceinline__ int q8_kv_quant(float v, float d) {
+  return d == 0.0f ? 0 : (int)fminf(fmaxf(rintf(v / d), -127.0f), 127.0f);
+}
 // four quants -> the dword of their low bytes, first quant lowest
 __device__ __forceinline__ unsigned pack_q8x4(int q0, int q1, int q2, int q3) {
   return ((unsigned)q0 & 0xffu) | (((unsigned)q1 & 0xffu) << 8) | (((unsigned)q2 & 0xffu) << 16) | (((unsigned)q3 & 0xffu) << 24);

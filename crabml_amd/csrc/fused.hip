@@ -143,6 +143,13 @@ struct TapField {
 
 // What a context runs, as one value: decide_step makes it at create, every reader goes through c->plan, and
 // crabml_hip_debug_step_plan (crabml_hip_debug.h) hands it out.
+// The three kinds of KV cache, as crabml_hip_llama_config_t::use_f16_kv_cache numbers them (create admits no other value).  Q8: per
+// layer and per K / V one allocation of two planes, int8 [n_kv][seq_len][head_dim] and right behind it f16 [n_kv][seq_len][head_dim / 32]
+// (one scale per 32 elements); served by the flash forms alone (k_attn_flash / k_attn_flash_rows / k_attn_flash_rows_split, KV8).
+enum class KvKind { F32 = 0, F16 = 1, Q8 = 2 };
+static inline KvKind kv_kind(const crabml_hip_llama_config_t& g) { return (KvKind)g.use_f16_kv_cache; }
+// bytes of one (kv head, position) row of a cache plane pair
+static inline size_t kv_row_bytes(KvKind k, size_t hd) { return k == KvKind::Q8 ? hd + hd / 32 * 2 : hd * (k == KvKind::F16 ? 2 : 4); }
 enum class SegPath { PerOp = 0, Fused5 = 1, FusedK = 2 };  // enqueue_segment_generic / enqueue_segment_t / enqueue_segment_k
 struct StepPlan {
   SegPath path = SegPath::PerOp;
@@ -268,6 +275,9 @@ struct crabml_hip_llama {
   float* pf_scores = nullptr;          // long prompts: [PF_LONG_ROWS][n_heads][seq_len] f32 scores
   unsigned short* pf_p16 = nullptr;    //               and f16 probabilities, allocated on first use
   float* pf_flash_part = nullptr;      // k_attn_flash_rows_split's partials, on the first pass that runs it (flash_rows_part_cap floats)
+  // the Q8 cache (kv_kind == KvKind::Q8): the f32 K | V rows the q|k|v launches leave for k_kv_store_q8, [rows][2 kv_dim_l] -- one row
+  // for the decode step, pf_cap for the prompt pass
+  float *kv_stage = nullptr, *pf_kv_stage = nullptr;
   std::vector<std::pair<void*, size_t>> allocs;
   // token / pos / step of the next step are staged in pinned host memory owned by the context (a ring, one slot per
   // set_state): the async copy reads it when the stream gets there, long after the caller's stack frame is gone
@@ -422,9 +432,13 @@ PvSplitKernel pv_split_kernel(int grp) {
 typedef decltype(&k_attn_s<0>) AttnSFn;
 AttnSFn attn_s_kernel(int hd) { return hd == 128 ? k_attn_s<128> : k_attn_s<0>; }
 typedef decltype(&k_attn_flash_rows<64>) FlashRowsFn;
-FlashRowsFn flash_rows_kernel(int hd) { return hd == 128 ? k_attn_flash_rows<128> : hd == 64 ? k_attn_flash_rows<64> : nullptr; }
+FlashRowsFn flash_rows_kernel(int hd, bool kv8 = false) {
+  if (kv8) return hd == 128 ? k_attn_flash_rows<128, true> : hd == 64 ? k_attn_flash_rows<64, true> : nullptr;
+  return hd == 128 ? k_attn_flash_rows<128> : hd == 64 ? k_attn_flash_rows<64> : nullptr;
+}
 typedef decltype(&k_attn_flash_rows_split<64>) FlashRowsSplitFn;
-FlashRowsSplitFn flash_rows_split_kernel(int hd) {
+FlashRowsSplitFn flash_rows_split_kernel(int hd, bool kv8 = false) {
+  if (kv8) return hd == 128 ? k_attn_flash_rows_split<128, true> : hd == 64 ? k_attn_flash_rows_split<64, true> : nullptr;
   return hd == 128 ? k_attn_flash_rows_split<128> : hd == 64 ? k_attn_flash_rows_split<64> : nullptr;
 }
 // strict-order Q4_K step: k_gemv_res_nq<Q4_K, SPLIT, QIN, .., ORD> (qin 1 = quantize the f32 rhs, 2 = copy finished planes) ...
@@ -601,15 +615,17 @@ void launch_attn_long(crabml_hip_llama* c, int l, signed char* xq, unsigned shor
 // the k_attn_flash instantiation for (G, hd, rhs type of wo); nullptr = no such kernel
 typedef void (*FlashFn)(const float*, const unsigned short*, const unsigned short*, const int*, float*, unsigned*, float*, signed char*,
                         unsigned short*, void*, int, int, int);
-template <int G, int HD>
+template <int G, int HD, bool KV8 = false>
 FlashFn flash_kernel_gh(bool q81, bool ticket) {
-  if (ticket) return q81 ? (FlashFn)k_attn_flash<G, HD, true, true> : (FlashFn)k_attn_flash<G, HD, false, true>;
-  return (FlashFn)k_attn_flash<G, HD, false, false>;
+  if (ticket) return q81 ? (FlashFn)k_attn_flash<G, HD, true, true, KV8> : (FlashFn)k_attn_flash<G, HD, false, true, KV8>;
+  return (FlashFn)k_attn_flash<G, HD, false, false, KV8>;
 }
 // (groups 3, 5, 6 and 7 -- Llama-3.2-3B; Qwen2.5-14B / 32B; 1.5B; 7B / 0.5B -- exist at head_dim 64 and 128 only: no model served has one
 // of them at 256)
+// (kv8: the Q8 cache's form, head_dim 64 and 128)
 template <int G>
-FlashFn flash_kernel_g(int hd, bool q81, bool ticket) {
+FlashFn flash_kernel_g(int hd, bool q81, bool ticket, bool kv8) {
+  if (kv8) return hd == 128 ? flash_kernel_gh<G, 128, true>(q81, ticket) : hd == 64 ? flash_kernel_gh<G, 64, true>(q81, ticket) : nullptr;
   if constexpr (G == 1 || G == 2 || G == 4 || G == 8) {
     if (hd == 256) return flash_kernel_gh<G, 256>(q81, ticket);
   }
@@ -617,10 +633,16 @@ FlashFn flash_kernel_g(int hd, bool q81, bool ticket) {
   if (hd == 64) return flash_kernel_gh<G, 64>(q81, ticket);
   return nullptr;
 }
-FlashFn flash_kernel(int grp, int hd, bool q81, bool ticket) {
+FlashFn flash_kernel(int grp, int hd, bool q81, bool ticket, bool kv8 = false) {
   FlashFn fn = nullptr;
-  with_const<1, 2, 3, 4, 5, 6, 7, 8>(grp, [&](auto g) { fn = flash_kernel_g<decltype(g)::value>(hd, q81, ticket); });
+  with_const<1, 2, 3, 4, 5, 6, 7, 8>(grp, [&](auto g) { fn = flash_kernel_g<decltype(g)::value>(hd, q81, ticket, kv8); });
   return fn;
+}
+// the Q8 cache's append of `rows` staged rows at *pos_d .. (k_kv_store_q8)
+void launch_kv_store_q8(crabml_hip_llama* c, int l, const float* stage, const int* pos_d, int rows) {
+  const int blocks = rows * 2 * c->kv_dim_l / 32;  // 32-element blocks: 8 lanes each
+  k_kv_store_q8<<<dim3((unsigned)((blocks * 8 + 255) / 256)), dim3(256), 0, c->dev->stream>>>(stage, (signed char*)c->kc[l], (signed char*)c->vc[l], pos_d,
+                                                                                            rows, c->n_kv_l, c->hd, (int)c->cfg.seq_len);
 }
 // which attention form serves cache position `pos` (see attn_variant)
 int variant_of(const crabml_hip_llama* c, size_t pos) {
@@ -633,7 +655,7 @@ void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
   const int hd = c->hd, grp = c->n_heads_l / c->n_kv_l;
   const bool q81 = c->qt == CRABML_HIP_Q8_1;
   const bool ticket = c->plan.flash_ticket || c->attn_variant == 2;
-  const FlashFn fn = flash_kernel(grp, hd, q81, ticket);
+  const FlashFn fn = flash_kernel(grp, hd, q81, ticket, kv_kind(c->cfg) == KvKind::Q8);
   crabml_hip_device::ProfRec r[2];
   if (prof) prof_begin(dev, &r[0], CRABML_HIP_F32, 7, 0.0);
   launch_k(st, prof ? &r[0] : nullptr, fn, dim3(c->n_kv_l * c->plan.flash_S), dim3(flash_threads(grp)), flash_lds_bytes(grp, hd),
@@ -660,6 +682,10 @@ int enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned shor
   hipStream_t st = dev->stream;
   const int hd = c->hd, seq_cap = (int)c->cfg.seq_len, n_heads = c->n_heads_l, n_kv = c->n_kv_l;
   const int* pos_d = c->state + 1;
+  if (kv_kind(c->cfg) == KvKind::Q8) {  // the token's staged K | V row into the planes, then the flash form: no other kernel reads them
+    if (c->attn_variant < 1 || !c->plan.attn_flash) CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "llama: a Q8 kv cache is served by k_attn_flash alone");
+    launch_kv_store_q8(c, l, c->kv_stage, pos_d, 1);
+  }
   if (c->attn_variant >= 1 && c->plan.attn_flash) {
     launch_attn_flash(c, l, xq, xd, xisum, prof);
     return 0;
@@ -681,7 +707,7 @@ int enqueue_attention(crabml_hip_llama* c, int l, signed char* xq, unsigned shor
              (const unsigned short*)c->vc[l], pos_d, (const unsigned short*)dev->exp_table, c->attn, xq, xd, xisum, n_heads, n_kv, hd, seq_cap,
              c->plan.attn_s_rows, pf, (k8 ? 2 : c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr, k8 ? *k8 : AttnQ8K{});
   else
-    with_const_else<0, 1>(c->cfg.use_f16_kv_cache != 0, [&](auto kv16) {
+    with_const_else<0, 1>(kv_kind(c->cfg) == KvKind::F16, [&](auto kv16) {  // (a Q8 cache left above)
       launch_k(st, AR, k_attn<decltype(kv16)::value != 0>, dim3(n_heads + spare), dim3(256), attn_lds, (const float*)c->qbuf, (const void*)c->kc[l],
                (const void*)c->vc[l], pos_d, (const unsigned short*)dev->exp_table, c->attn, xq, xd, xisum, n_heads, n_kv, hd,
                seq_cap, seq_cap, pf, (c->qt == CRABML_HIP_Q8_1 ? 1 : 0) | sbit, (long long*)nullptr);
@@ -772,8 +798,10 @@ void with_qkv_epi(const crabml_hip_llama* c, const QkvEpi& e, int l, F&& f) {
 // what the three segment enqueuers share: the decode step's q|k|v epilogue arguments (rope + scale + KV append, llama2.rs:244-256,
 // 542-554, 561-565; local heads only) and the embedding row in front of layer 0
 QkvEpi decode_qkv_epi(const crabml_hip_llama* c, int l) {
-  return QkvEpi{c->qbuf, c->kc[l], c->vc[l], c->rope, c->state + 1, 1.0f / std::sqrt((float)c->hd), c->dim_l, c->kv_dim_l, c->hd,
-                (int)c->cfg.rope_dim, c->npairs, (int)c->cfg.seq_len, c->cfg.use_f16_kv_cache ? 1 : 0};
+  const bool q8 = kv_kind(c->cfg) == KvKind::Q8;  // K | V leave as a staged f32 row (enqueue_attention appends it)
+  return QkvEpi{c->qbuf, q8 ? (void*)c->kv_stage : c->kc[l], q8 ? (void*)(c->kv_stage + c->kv_dim_l) : c->vc[l], c->rope, c->state + 1,
+                1.0f / std::sqrt((float)c->hd), c->dim_l, c->kv_dim_l, c->hd,
+                (int)c->cfg.rope_dim, c->npairs, (int)c->cfg.seq_len, (int)kv_kind(c->cfg)};
 }
 void launch_embed(const crabml_hip_llama* c) {
   const int dim = (int)c->cfg.embedding_dim;
@@ -1495,6 +1523,7 @@ int prefill_alloc(crabml_hip_llama* c, size_t cap) {
   CH_TRY(A(cap * dim * 4, (void**)&c->pf_q));
   CH_TRY(A(cap * kv_dim * 4, (void**)&c->pf_k));
   CH_TRY(A(cap * kv_dim * 4, (void**)&c->pf_v));
+  if (kv_kind(g) == KvKind::Q8) CH_TRY(A(cap * 2 * kv_dim * 4, (void**)&c->pf_kv_stage));
   CH_TRY(A(cap * dim * 4, (void**)&c->pf_qr));
   CH_TRY(A(cap * dim * 4, (void**)&c->pf_attn));
   CH_TRY(A(cap * dim * 4, (void**)&c->pf_tmp));
@@ -1540,8 +1569,8 @@ bool launch_attn_tile_t(crabml_hip_llama* c, int l, int B, int pos0) {
 }
 bool launch_attn_tile(crabml_hip_llama* c, int l, int B, int pos0) {
   const int hd = c->hd, g = c->n_heads_l / c->n_kv_l;
-  const bool kv16 = c->cfg.use_f16_kv_cache != 0;
-  if (!exact_rows_on(c->cfg)) return false;
+  const bool kv16 = kv_kind(c->cfg) == KvKind::F16;
+  if (!exact_rows_on(c->cfg) || kv_kind(c->cfg) == KvKind::Q8) return false;
   if (pos0 + B > 1024 || hd > (kv16 ? 256 : 128) || hd % (kv16 ? 16 : 4) != 0 || c->n_heads_l % c->n_kv_l != 0) return false;
   bool ok = false;  // (other group sizes: not covered)
   with_const_else<0, 1>(kv16, [&](auto kv) {
@@ -1619,9 +1648,9 @@ size_t flash_rows_part_cap(const crabml_hip_llama* c) {
 }
 // the two launches of the split form: `slices` (<= the pass's tiles) slices into `part`, merged into out
 void launch_flash_rows_split(hipStream_t st, int hd, const float* q, const unsigned short* k, const unsigned short* v, const int* pos_d, float* part,
-                             float* out, int n_heads, int n_kv, int seq_cap, int B, int slices) {
+                             float* out, int n_heads, int n_kv, int seq_cap, int B, int slices, bool kv8 = false) {
   const FlashRowsSplitGeom ge = flash_rows_split_geom(n_heads / n_kv, B);
-  flash_rows_split_kernel(hd)<<<dim3((unsigned)ge.nwg, (unsigned)n_kv, (unsigned)slices), 64 * ge.fpw, flash_rows_lds_bytes(hd), st>>>(
+  flash_rows_split_kernel(hd, kv8)<<<dim3((unsigned)ge.nwg, (unsigned)n_kv, (unsigned)slices), 64 * ge.fpw, flash_rows_lds_bytes(hd), st>>>(
       q, k, v, pos_d, part, n_heads, n_kv, seq_cap, B, slices);
   if (hd == 128)
     k_attn_flash_rows_merge<128><<<(unsigned)(B * n_heads), 128, 0, st>>>(part, out, B * n_heads, slices);
@@ -1635,23 +1664,30 @@ int launch_prefill_attention(crabml_hip_llama* c, int l, size_t B, size_t pos0) 
   crabml_hip_device* dev = c->dev;
   hipStream_t st = dev->stream;
   const int hd = c->hd, n_heads = c->n_heads_l, n_kv = c->n_kv_l, seq_cap = (int)c->cfg.seq_len;
-  const bool kv16 = c->cfg.use_f16_kv_cache != 0;
+  const bool kv16 = kv_kind(c->cfg) == KvKind::F16, kv8 = kv_kind(c->cfg) == KvKind::Q8;
   const int* pos_d = c->state + 6;
+  if (kv8) {  // the pass's staged K | V rows into the planes; then the flash-rows family, which alone reads them (attn_long_from = 1)
+    if (!c->plan.attn_flash_rows) {
+      (void)set_error(dev, CRABML_HIP_UNEXPECTED, "llama prefill: a Q8 kv cache is served by the flash-rows kernels alone");
+      return -1;
+    }
+    launch_kv_store_q8(c, l, c->pf_kv_stage, pos_d, (int)B);
+  }
   // (a pass whose every row sees fewer cached positions than the decode step's switch to the f32 kernels -- attn_long_from --
   // keeps the exact tile kernel, so that prefill(prompt) and a token loop over the same short prompt agree bit for bit)
-  if (c->plan.attn_flash_rows && kv16 && pos0 + B >= c->plan.attn_long_from) {
+  if (c->plan.attn_flash_rows && (kv16 || kv8) && pos0 + B >= c->plan.attn_long_from) {
     // fast step: causal flash attention on the f16 matrix cores (k_attn_flash_rows; the deviation stated for k_attn_flash) -- a short
     // pass deep in the cache in its split-KV form
     const int slices = c->plan.flash_rows_split ? flash_rows_slices(dev->n_cu, (size_t)n_heads, (size_t)n_kv, B, pos0) : 1;
     if (slices > 1) {
       if (!c->pf_flash_part && dalloc(c, flash_rows_part_cap(c) * 4, (void**)&c->pf_flash_part) != 0) return -1;
       launch_flash_rows_split(st, hd, (const float*)c->pf_qr, (const unsigned short*)c->kc[l], (const unsigned short*)c->vc[l], pos_d,
-                              c->pf_flash_part, c->pf_attn, n_heads, n_kv, seq_cap, (int)B, slices);
+                              c->pf_flash_part, c->pf_attn, n_heads, n_kv, seq_cap, (int)B, slices, kv8);
       return 1;
     }
     const dim3 fg((unsigned)((B + 63) / 64), (unsigned)n_heads);
-    flash_rows_kernel(hd)<<<fg, 512, flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
-                                                                      (const unsigned short*)c->vc[l], pos_d, c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
+    flash_rows_kernel(hd, kv8)<<<fg, 512, flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
+                                                                           (const unsigned short*)c->vc[l], pos_d, c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
     return 1;
   }
   if (launch_attn_tile(c, l, (int)B, (int)pos0)) return 2;
@@ -1696,7 +1732,7 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   const auto& g = c->cfg;
   const int dim = (int)g.embedding_dim, kv_dim = c->kv_dim_l, hidden = (int)g.hidden_dim, hd = c->hd, seq_cap = (int)g.seq_len;
   const int L = (int)g.n_layers;
-  const bool kv16 = g.use_f16_kv_cache != 0, strict = dev->strict_order;
+  const bool strict = dev->strict_order;
   const int half = strict ? 0 : 1;
   const unsigned rows = (unsigned)B;
   {
@@ -1914,8 +1950,9 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_Q, c->pf_q, xb_dim));
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_K, c->pf_k, xb_kv));
     CH_TRY(PT(tl, CRABML_HIP_PFTAP_V, c->pf_v, xb_kv));
-    QkvEpi e{c->pf_qr, c->kc[l], c->vc[l], c->rope, pos_d, 1.0f / std::sqrt((float)hd), dim, kv_dim, hd,
-             (int)g.rope_dim, c->npairs, seq_cap, kv16 ? 1 : 0};
+    const bool q8 = kv_kind(g) == KvKind::Q8;  // K | V leave as staged f32 rows (launch_prefill_attention appends them)
+    QkvEpi e{c->pf_qr, q8 ? (void*)c->pf_kv_stage : c->kc[l], q8 ? (void*)(c->pf_kv_stage + kv_dim) : c->vc[l], c->rope, pos_d,
+             1.0f / std::sqrt((float)hd), dim, kv_dim, hd, (int)g.rope_dim, c->npairs, seq_cap, (int)kv_kind(g)};
     const int pairs = (dim + 2 * kv_dim) / 2;
     with_qkv_epi(c, e, l, [&](auto ep) {
       k_qkv_epi_rows<QkvArchOf<decltype(ep)>::value><<<dim3((pairs + 255) / 256, rows), 256, 0, st>>>(c->pf_q, c->pf_k, c->pf_v, ep);
@@ -2320,6 +2357,8 @@ static int validate_config(crabml_hip_device_t* dev, const crabml_hip_llama_conf
   const int tp = f->tp = g.tp_size > 1 ? g.tp_size : 1;
   if (!g.n_heads || !g.n_kv_heads || !g.n_layers || g.embedding_dim % g.n_heads || g.n_heads % g.n_kv_heads)
     CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: inconsistent head configuration");
+  if (g.use_f16_kv_cache < 0 || g.use_f16_kv_cache > 2)
+    CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: use_f16_kv_cache %d is no kind of kv cache (0 f32, 1 f16, 2 Q8)", (int)g.use_f16_kv_cache);
   // (asked before the divisibility checks: Gemma-2B has ONE kv head, which no tp_size > 1 divides -- the answer is "not implemented")
   if (arch && arch->architecture == CRABML_HIP_ARCH_GEMMA && tp > 1)
     CH_BAIL(dev, CRABML_HIP_NOT_IMPLEMENTED, "gemma: tensor parallelism is not implemented");
@@ -2469,7 +2508,11 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
   const auto has = [&](int bits) { return (g.flags & bits) != 0; };
   const int grp = (int)(f.n_heads_l / f.n_kv_l), hd = (int)f.hd, n_kv_l = (int)f.n_kv_l;
   const size_t seq = g.seq_len;
-  const bool kv16 = g.use_f16_kv_cache != 0, q81 = f.qt == CRABML_HIP_Q8_1;
+  // A Q8 cache is read by the flash forms alone: no exact kernel, no staged kernel, and the flash forms from the first position on --
+  // attn_long_from = 1, so variant_of never answers 0 -- with the prompt pass on the flash-rows family for every group up to 8 (the
+  // group-agnostic kernel).  kv_q8_refusal turns away a context whose plan lacks one of them.
+  const bool kv8 = kv_kind(g) == KvKind::Q8;
+  const bool kv16 = kv_kind(g) == KvKind::F16, q81 = f.qt == CRABML_HIP_Q8_1;
   // One predicate per use.  The decode step's kernels (k_attn_flash; k_attn_scores / k_attn_softmax / k_attn_pv) serve every group up to 8;
   // the prompt pass's (k_attn_flash_rows here, the tile and long-rows kernels through their own lists) serve 1, 2, 4 and 8 only -- any
   // other group keeps its prompt on the per-(head, row) kernel.  That kernel's score row ends at 64 KiB, so in a cache past
@@ -2489,9 +2532,11 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
   // the fast step's long-context attention: split-KV with f32 accumulation (k_attn_flash) unless the exact chain is asked for
   // (k_attn_flash reads the cache rows only -- head_dim halves each --, so any seq_len will do: a cache of 1001 positions must not
   // fall back to one workgroup per head, 45 us per layer at 900 positions)
-  const bool want_flash = long_geom && !dev->strict_order && !has(CRABML_HIP_LLAMA_EXACT_ATTENTION);
+  // (NO_LONG_ATTENTION switches the flash forms off for a Q8 cache as for an f16 one: kv_q8_refusal then turns the context away)
+  const bool q8_geom = kv8 && (hd == 64 || hd == 128) && grp >= 1 && grp <= 8 && !has(CRABML_HIP_LLAMA_NO_LONG_ATTENTION);
+  const bool want_flash = (long_geom || q8_geom) && !dev->strict_order && !has(CRABML_HIP_LLAMA_EXACT_ATTENTION);
   p->flash_ticket = want_flash && has(CRABML_HIP_LLAMA_FLASH_TICKET);
-  const FlashFn fn = want_flash ? flash_kernel(grp, hd, q81, p->flash_ticket) : nullptr;
+  const FlashFn fn = want_flash ? flash_kernel(grp, hd, q81, p->flash_ticket, kv8) : nullptr;
   p->attn_flash = fn != nullptr && lds_fits(dev, (const void*)fn, flash_lds_bytes(grp, hd), LDS_NO_CAP, 0);
   if (p->attn_flash) {
     const int S = dev->n_cu / n_kv_l;
@@ -2500,21 +2545,22 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
     // Below ~768 cached positions the merge inside the launch (last-arriving workgroup of a kv head, ticket word) beats the
     // second launch -- 7.4 vs 5.1 + 4.1 us per layer at 128 positions, 8.7 vs 10.0 at 512, 10.8 vs 9.95 at 1024
     // (profiles/r05_flash_ticket_sweep.md; same partials, same merge order: bit-identical): a third graph variant serves that range.
-    const FlashFn tfn = flash_kernel(grp, hd, q81, true);
+    const FlashFn tfn = flash_kernel(grp, hd, q81, true, kv8);
     if (!p->flash_ticket && hooks.ticket_until > 0 && tfn != nullptr && lds_fits(dev, (const void*)tfn, flash_lds_bytes(grp, hd), LDS_NO_CAP, 0))
       p->flash_ticket_until = hooks.ticket_until;
     // the prompt pass's causal attention of the fast step (k_attn_flash_rows): 70 KB of LDS at head_dim 128
     p->attn_flash_rows =
-        rows_geom && flash_rows_kernel(hd) != nullptr && lds_fits(dev, (const void*)flash_rows_kernel(hd), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
+        (rows_geom || q8_geom) && flash_rows_kernel(hd, kv8) != nullptr &&
+        lds_fits(dev, (const void*)flash_rows_kernel(hd, kv8), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
     // ... and its split-KV form for short passes deep in the cache (k_attn_flash_rows_split: the same tiles, the same LDS)
     p->flash_rows_split = p->attn_flash_rows && !has(CRABML_HIP_LLAMA_NO_FLASH_ROWS_SPLIT) &&
-                          lds_fits(dev, (const void*)flash_rows_split_kernel(hd), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
+                          lds_fits(dev, (const void*)flash_rows_split_kernel(hd, kv8), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
   }
   p->attn_long_ok = p->exact_long_ok || p->attn_flash;
   // the exact kernels: measured crossover on MI355X (Llama-3-8B shape) ~200-220.  k_attn_flash + merge overtake the staged one-workgroup
   // kernel between 64 and 96 cached positions (8B shape, per layer: 51.0 vs 51.6 us at 64, 52.2 vs 51.4 at 96, 59.0 vs 51.8 at 224;
   // profiles/r04_flash_sweep.log)
-  p->attn_long_from = g.attn_long_from ? g.attn_long_from : p->attn_flash ? 96 : 224;
+  p->attn_long_from = kv8 ? 1 : g.attn_long_from ? g.attn_long_from : p->attn_flash ? 96 : 224;
   // short-context attention with K / V staged through LDS (f16 cache): variant 0 serves positions < S
   if (kv16 && hd % 8 == 0 && !has(CRABML_HIP_LLAMA_NO_STAGED_ATTENTION)) {
     const size_t S = p->attn_long_ok && p->attn_long_from < seq ? p->attn_long_from : seq;
@@ -2541,15 +2587,31 @@ static const char* long_cache_refusal(const crabml_hip_llama_config_t& g, const 
   if (!past_k_attn_row(g.seq_len, f.hd)) return nullptr;
   if (g.seq_len > MAX_SEQ_LEN) return "more positions than the limit";
   if (f.tp > 1) return "tensor-parallel ranks keep the one-workgroup-per-head attention within reach";
-  if (!g.use_f16_kv_cache) return "an f32 kv cache has no long-context attention kernels";
+  if (kv_kind(g) == KvKind::F32) return "an f32 kv cache has no long-context attention kernels";
   if (!plan) return nullptr;
   const StepPlan& p = *plan;
+  if (kv_kind(g) == KvKind::Q8) return nullptr;  // (kv_q8_refusal holds every Q8 plan to the flash forms, at any length)
   if (!p.attn_long_ok) return "the decode step has no long-context attention (flags, head_dim, a group above 8, seq_len % 8 on the exact kernels)";
   if (p.attn_long_from >= g.seq_len) return "attn_long_from leaves the whole cache to the short-context attention";
   if (p.attn_s_rows <= 0) return "the decode step's short-context attention would need the whole score row in LDS (k_attn_s is off or does not fit)";
   const bool exact_rows = p.exact_long_ok && exact_rows_group((int)(f.n_heads_l / f.n_kv_l)) && exact_rows_on(g);
   if (!p.attn_flash_rows && !exact_rows)
     return "the prompt pass has no attention kernel for this cache (exact kernels: groups 1, 2, 4, 8, seq_len % 8 == 0, tile attention on)";
+  return nullptr;
+}
+
+// Why a Q8 kv cache (use_f16_kv_cache == 2) cannot be served (nullptr: it can, or the cache is another kind).  plan == nullptr: the
+// clauses the configuration and the device settle, as long_cache_refusal asks them.
+static const char* kv_q8_refusal(const crabml_hip_device* dev, const crabml_hip_llama_config_t& g, const ModelFacts& f, const StepPlan* plan) {
+  if (kv_kind(g) != KvKind::Q8) return nullptr;
+  if (dev->strict_order) return "the strict-order device keeps the reference's f16 chains, which no Q8 kernel has";
+  if (f.tp > 1) return "tensor-parallel ranks have no Q8 cache";
+  if (f.hd != 64 && f.hd != 128) return "the Q8 attention kernels exist for head_dim 64 and 128";
+  if (f.n_heads_l / f.n_kv_l > 8) return "the Q8 attention kernels serve GQA groups 1 .. 8";
+  if (!plan) return nullptr;
+  if (plan->path == SegPath::PerOp) return "the per-op segments (a weight format or mix without fused kernels) have no Q8 cache";
+  if (!plan->attn_flash) return "the decode step's split-KV attention is off (flags) or does not fit";
+  if (!plan->attn_flash_rows) return "the prompt pass's flash-rows attention does not fit";
   return nullptr;
 }
 
@@ -2754,13 +2816,14 @@ static int alloc_step_buffers(crabml_hip_llama* c, crabml_hip_buf* const* ext_kc
   auto A = [&](size_t bytes, auto** ptr) {
     if (rc == 0) rc = dalloc(c, bytes, (void**)ptr);
   };
-  const size_t es = g.use_f16_kv_cache ? 2 : 4;
-  c->kv_bytes = n_kv_l * g.seq_len * c->hd * es;
+  const size_t es = kv_kind(g) == KvKind::F16 ? 2 : 4;  // (the caller's cache tensors: never Q8)
+  c->kv_bytes = n_kv_l * g.seq_len * kv_row_bytes(kv_kind(g), c->hd);  // (Q8: the int8 plane, then the scale plane)
+  if (kv_kind(g) == KvKind::Q8) A(2 * kv_dim_l * 4, &c->kv_stage);
   c->kc.resize(g.n_layers);
   c->vc.resize(g.n_layers);
   for (size_t l = 0; l < g.n_layers; l++) {
     if (c->ext_kv) {
-      const uint32_t kvt = g.use_f16_kv_cache ? CRABML_HIP_F16 : CRABML_HIP_F32;
+      const uint32_t kvt = kv_kind(g) == KvKind::F16 ? CRABML_HIP_F16 : CRABML_HIP_F32;
       if (!ext_kc[l] || !ext_vc[l] || ext_kc[l]->dtype != kvt || ext_vc[l]->dtype != kvt || ext_kc[l]->n_elems * es != c->kv_bytes ||
           ext_vc[l]->n_elems * es != c->kv_bytes) {
         if (rc == 0) rc = set_error(dev, CRABML_HIP_BAD_INPUT, "llama: external kv cache of layer %zu has the wrong type or size", l);
@@ -2859,7 +2922,8 @@ static bool capture_graphs(crabml_hip_llama* c, const ModelFacts& f) {
   if (!want_graph) return true;
   const int nvar = c->plan.attn_long_ok ? (c->plan.flash_ticket_until > 0 ? 3 : 2) : 1;
   bool ok = true;
-  for (int v = 0; v < nvar && ok; v++) ok = capture_step(c, v, &c->graph[v], &c->exec[v]);
+  // (a Q8 cache has no variant 0: variant_of never answers it)
+  for (int v = kv_kind(g) == KvKind::Q8 ? 1 : 0; v < nvar && ok; v++) ok = capture_step(c, v, &c->graph[v], &c->exec[v]);
   (void)hipGetLastError();
   c->use_graph = ok;
   c->attn_variant = 0;
@@ -2881,8 +2945,13 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
                      cfg->seq_len, (size_t)(K_ATTN_LDS / 4 - f.hd), MAX_SEQ_LEN, why);
   };
   if (const char* why = long_cache_refusal(*cfg, f, nullptr)) return refuse(why);
+  if (kv_kind(*cfg) == KvKind::Q8 && ext_kc != nullptr)
+    CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: a Q8 kv cache is the context's own (the caller's cache tensors are f32 or f16)");
+  const auto refuse_q8 = [&](const char* why) { return set_error(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: no Q8 kv cache here: %s", why); };
+  if (const char* why = kv_q8_refusal(dev, *cfg, f, nullptr)) return refuse_q8(why);
   const StepPlan plan = decide_step(dev, *cfg, f, read_flash_hooks());
   if (const char* why = long_cache_refusal(*cfg, f, &plan)) return refuse(why);
+  if (const char* why = kv_q8_refusal(dev, *cfg, f, &plan)) return refuse_q8(why);
   crabml_hip_llama* c = nullptr;
   CH_TRY(new_context(dev, *cfg, f, plan, ext_kc != nullptr, &c));
   int rc = retain_weights(c, w, arch, f);
@@ -3170,22 +3239,28 @@ int crabml_hip_llama_debug_poison(crabml_hip_llama_t* c, uint32_t what, uint16_t
   };
   if (what & 1) {
     const auto& g = c->cfg;
-    const bool kv16 = g.use_f16_kv_cache != 0;
-    const size_t es = kv16 ? 2 : 4, hd = (size_t)c->hd, live = c->kv_len < g.seq_len ? c->kv_len : g.seq_len;
+    const bool kv16 = kv_kind(g) == KvKind::F16, kv8 = kv_kind(g) == KvKind::Q8;
+    const size_t es = kv8 ? 1 : kv16 ? 2 : 4, hd = (size_t)c->hd, live = c->kv_len < g.seq_len ? c->kv_len : g.seq_len;
     const size_t tail = (g.seq_len - live) * hd * es;
+    const size_t plane = (size_t)c->n_kv_l * g.seq_len * hd, nb = hd / 32;  // Q8: the scale plane behind the int8 plane, filled alike (fill16)
     for (size_t l = 0; l < g.n_layers && tail; l++)
       for (void* base : {c->kc[l], c->vc[l]})
-        for (size_t h = 0; h < (size_t)c->n_kv_l; h++) CH_TRY(words((char*)base + (h * g.seq_len + live) * hd * es, tail, kv16));
+        for (size_t h = 0; h < (size_t)c->n_kv_l; h++) {
+          CH_TRY(words((char*)base + (h * g.seq_len + live) * hd * es, tail, kv16 || kv8));
+          if (kv8) CH_TRY(words((char*)base + plane + (h * g.seq_len + live) * nb * 2, (g.seq_len - live) * nb * 2, true));
+        }
   }
   if (what & 2) {
     for (void* p : {(void*)c->x, (void*)c->partial, (void*)c->qbuf, (void*)c->attn, (void*)c->h, (void*)c->tmp, (void*)c->xn, (void*)c->logits,
-                    (void*)c->rsums, (void*)c->scores_g, (void*)c->flash_part, (void*)c->am_val, (void*)c->out_tokens})
+                    (void*)c->rsums, (void*)c->scores_g, (void*)c->flash_part, (void*)c->am_val, (void*)c->out_tokens,
+                    (void*)c->kv_stage})
       CH_TRY(fill(p, false));
     for (void* p : {(void*)c->act_dim, (void*)c->act_attn, (void*)c->act_hid, (void*)c->p16}) CH_TRY(fill(p, true));
   }
   if ((what & 4) && c->pf_cap) {
     for (void* p : {(void*)c->pf_x, (void*)c->pf_xn, (void*)c->pf_q, (void*)c->pf_k, (void*)c->pf_v, (void*)c->pf_qr, (void*)c->pf_attn,
-                    (void*)c->pf_tmp, (void*)c->pf_g, (void*)c->pf_u, (void*)c->pf_split, (void*)c->pf_scores, (void*)c->pf_flash_part})
+                    (void*)c->pf_tmp, (void*)c->pf_g, (void*)c->pf_u, (void*)c->pf_split, (void*)c->pf_scores, (void*)c->pf_flash_part,
+                    (void*)c->pf_kv_stage})
       CH_TRY(fill(p, false));
     for (void* p : {(void*)c->pf_act_dim, (void*)c->pf_act_hid, c->pf_xh, c->pf_xh2, (void*)c->pf_p16}) CH_TRY(fill(p, true));
   }
@@ -3400,20 +3475,23 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
   return 0;
 }
 
-int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
-                                     size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap, size_t slices, float* out, float* out2) {
-  if (!dev || !q || !k || !v || !out || seq == 0 || seq_cap < seq || n_kv == 0 || n_heads % n_kv != 0) return CRABML_HIP_BAD_INPUT;
+// kd / vd != nullptr: the Q8 form -- k / v are int8 planes, kd / vd their f16 scale planes, laid out on the device as a context's are
+static int debug_flash_attention_impl(crabml_hip_device_t* dev, const float* q, const void* k, const uint16_t* kd, const void* v, const uint16_t* vd,
+                                      size_t n_heads, size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap, size_t slices, float* out, float* out2) {
+  const bool kv8 = kd != nullptr;
+  if (!dev || !q || !k || !v || !out || seq == 0 || seq_cap < seq || n_kv == 0 || n_heads % n_kv != 0 || (kv8 && !vd)) return CRABML_HIP_BAD_INPUT;
   CH_LIVE(dev);
   CH_USE(dev);
   CH_FLUSH(dev);
   const int grp = (int)(n_heads / n_kv), hd = (int)head_dim;
-  const FlashFn fn = flash_kernel(grp, hd, false, false), fnt = flash_kernel(grp, hd, false, true);
+  const FlashFn fn = flash_kernel(grp, hd, false, false, kv8), fnt = flash_kernel(grp, hd, false, true, kv8);
   const bool ticket_form = out2 != nullptr;
   if (fn == nullptr || slices < 1 || slices > FLASH_MAX_SLICES) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention: unsupported group / head_dim / slices");
   if (raise_dyn_lds(dev, (const void*)fn, (int)flash_lds_bytes(grp, hd)) != hipSuccess ||
       raise_dyn_lds(dev, (const void*)fnt, (int)flash_lds_bytes(grp, hd)) != hipSuccess)
     CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "debug_flash_attention: LDS");
-  const size_t nq = n_heads * head_dim * 4, nkv = n_kv * seq_cap * head_dim * 2, npart = n_kv * slices * flash_part_floats(grp, hd) * 4;
+  const size_t nq = n_heads * head_dim * 4, npl = n_kv * seq_cap * head_dim * (kv8 ? 1 : 2), nsc = kv8 ? n_kv * seq_cap * (head_dim / 32) * 2 : 0,
+               nkv = npl + nsc, npart = n_kv * slices * flash_part_floats(grp, hd) * 4;
   char* base = nullptr;
   const size_t o_q = 0, o_k = align_up(o_q + nq, 256), o_v = align_up(o_k + nkv, 256), o_out = align_up(o_v + nkv, 256),
                o_part = align_up(o_out + nq, 256), o_tick = align_up(o_part + npart, 256), o_pos = o_tick + align_up(n_kv * 4, 256),
@@ -3423,8 +3501,10 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
   const int pos = (int)seq - 1;
   hipError_t e = hipMemsetAsync(base + o_tick, 0, n_kv * 4, st);
   if (e == hipSuccess) e = hipMemcpyAsync(base + o_q, q, nq, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(base + o_k, k, nkv, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, v, nkv, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_k, k, npl, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, v, npl, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && kv8) e = hipMemcpyAsync(base + o_k + npl, kd, nsc, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && kv8) e = hipMemcpyAsync(base + o_v + npl, vd, nsc, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(base + o_pos, &pos, 4, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);  // (`pos` leaves scope)
   if (e == hipSuccess) {
@@ -3456,20 +3536,33 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
   if (e != hipSuccess) return hip_fail(dev, e, "debug_flash_attention", __FILE__, __LINE__);
   return 0;
 }
+int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
+                                     size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap, size_t slices, float* out, float* out2) {
+  return debug_flash_attention_impl(dev, q, k, nullptr, v, nullptr, n_heads, n_kv, head_dim, seq, seq_cap, slices, out, out2);
+}
+int crabml_hip_debug_flash_attention_q8(crabml_hip_device_t* dev, const float* q, const int8_t* kq, const uint16_t* kd, const int8_t* vq,
+                                        const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap,
+                                        size_t slices, float* out, float* out2) {
+  if (!kd || !vd || (head_dim != 64 && head_dim != 128)) return CRABML_HIP_BAD_INPUT;
+  return debug_flash_attention_impl(dev, q, kq, kd, vq, vd, n_heads, n_kv, head_dim, seq, seq_cap, slices, out, out2);
+}
 
 // parity hook (crabml_hip_debug.h): the fast prompt pass's causal attention kernel by itself
-int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
-                                          size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, float* out) {
-  if (!dev || !q || !k || !v || !out || rows == 0 || n_kv == 0 || n_heads % n_kv != 0 || seq_cap < pos0 + rows) return CRABML_HIP_BAD_INPUT;
+static int debug_flash_attention_rows_impl(crabml_hip_device_t* dev, const float* q, const void* k, const uint16_t* kd, const void* v,
+                                           const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t pos0, size_t rows,
+                                           size_t seq_cap, float* out) {
+  const bool kv8 = kd != nullptr;
+  if (!dev || !q || !k || !v || !out || (kv8 && !vd) || rows == 0 || n_kv == 0 || n_heads % n_kv != 0 || seq_cap < pos0 + rows) return CRABML_HIP_BAD_INPUT;
   if (head_dim != 128 && head_dim != 64) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_rows: head_dim 64 / 128");
   CH_LIVE(dev);
   CH_USE(dev);
   CH_FLUSH(dev);
-  const FlashRowsFn fn = flash_rows_kernel((int)head_dim);
+  const FlashRowsFn fn = flash_rows_kernel((int)head_dim, kv8);
   if (raise_dyn_lds(dev, (const void*)fn, (int)flash_rows_lds_bytes((int)head_dim)) != hipSuccess)
     CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "debug_flash_attention_rows: LDS");
   const size_t seq = seq_cap;
-  const size_t nq = rows * n_heads * head_dim * 4, nkv = n_kv * seq * head_dim * 2;
+  const size_t nq = rows * n_heads * head_dim * 4, npl = n_kv * seq * head_dim * (kv8 ? 1 : 2), nsc = kv8 ? n_kv * seq * (head_dim / 32) * 2 : 0,
+               nkv = npl + nsc;
   const size_t o_q = 0, o_k = align_up(o_q + nq, 256), o_v = align_up(o_k + nkv, 256), o_out = align_up(o_v + nkv, 256),
                o_pos = align_up(o_out + nq, 256), total = o_pos + 256;
   char* base = nullptr;
@@ -3477,8 +3570,10 @@ int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float*
   hipStream_t st = dev->stream;
   const int p0 = (int)pos0;
   hipError_t e = hipMemcpyAsync(base + o_q, q, nq, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(base + o_k, k, nkv, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, v, nkv, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_k, k, npl, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, v, npl, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && kv8) e = hipMemcpyAsync(base + o_k + npl, kd, nsc, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && kv8) e = hipMemcpyAsync(base + o_v + npl, vd, nsc, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(base + o_pos, &p0, 4, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e == hipSuccess) {
@@ -3493,11 +3588,17 @@ int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float*
   if (e != hipSuccess) return hip_fail(dev, e, "debug_flash_attention_rows", __FILE__, __LINE__);
   return 0;
 }
+int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
+                                          size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, float* out) {
+  return debug_flash_attention_rows_impl(dev, q, k, nullptr, v, nullptr, n_heads, n_kv, head_dim, pos0, rows, seq_cap, out);
+}
 
 // parity hook (crabml_hip_debug.h): k_attn_flash_rows_split and its merge by themselves, with a forced slice count
-int crabml_hip_debug_flash_attention_rows_split(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
-                                                size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, size_t slices, float* out) {
-  if (!dev || !q || !k || !v || !out || rows == 0 || n_kv == 0 || n_heads % n_kv != 0 || seq_cap < pos0 + rows || slices < 1)
+static int debug_flash_attention_rows_split_impl(crabml_hip_device_t* dev, const float* q, const void* k, const uint16_t* kd, const void* v,
+                                                 const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t pos0, size_t rows,
+                                                 size_t seq_cap, size_t slices, float* out) {
+  const bool kv8 = kd != nullptr;
+  if (!dev || !q || !k || !v || !out || (kv8 && !vd) || rows == 0 || n_kv == 0 || n_heads % n_kv != 0 || seq_cap < pos0 + rows || slices < 1)
     return CRABML_HIP_BAD_INPUT;
   if (head_dim != 128 && head_dim != 64) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_rows_split: head_dim 64 / 128");
   if (n_heads / n_kv > 8 || pos0 + rows > (size_t)1 << 30)
@@ -3506,11 +3607,12 @@ int crabml_hip_debug_flash_attention_rows_split(crabml_hip_device_t* dev, const 
   CH_USE(dev);
   CH_FLUSH(dev);
   const int hd = (int)head_dim;
-  if (raise_dyn_lds(dev, (const void*)flash_rows_split_kernel(hd), (int)flash_rows_lds_bytes(hd)) != hipSuccess)
+  if (raise_dyn_lds(dev, (const void*)flash_rows_split_kernel(hd, kv8), (int)flash_rows_lds_bytes(hd)) != hipSuccess)
     CH_BAIL(dev, CRABML_HIP_UNEXPECTED, "debug_flash_attention_rows_split: LDS");
   const size_t tiles = (pos0 + rows - 1) / FLASH_ROWS_BN + 1;
   const int S = (int)std::min({slices, tiles, (size_t)FLASH_ROWS_MAX_SLICES});
-  const size_t nq = rows * n_heads * head_dim * 4, nkv = n_kv * seq_cap * head_dim * 2, npart = flash_rows_part_floats(S, (int)rows, (int)n_heads, hd) * 4;
+  const size_t nq = rows * n_heads * head_dim * 4, npl = n_kv * seq_cap * head_dim * (kv8 ? 1 : 2), nsc = kv8 ? n_kv * seq_cap * (head_dim / 32) * 2 : 0,
+               nkv = npl + nsc, npart = flash_rows_part_floats(S, (int)rows, (int)n_heads, hd) * 4;
   const size_t o_q = 0, o_k = align_up(o_q + nq, 256), o_v = align_up(o_k + nkv, 256), o_out = align_up(o_v + nkv, 256),
                o_part = align_up(o_out + nq, 256), o_pos = align_up(o_part + npart, 256), total = o_pos + 256;
   char* base = nullptr;
@@ -3520,20 +3622,56 @@ int crabml_hip_debug_flash_attention_rows_split(crabml_hip_device_t* dev, const 
   // the partials start as NaN words: a partial the merge reads and the first launch did not write shows in the output
   hipError_t e = hipMemsetAsync(base + o_part, 0xFF, npart, st);
   if (e == hipSuccess) e = hipMemcpyAsync(base + o_q, q, nq, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(base + o_k, k, nkv, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, v, nkv, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_k, k, npl, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, v, npl, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && kv8) e = hipMemcpyAsync(base + o_k + npl, kd, nsc, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && kv8) e = hipMemcpyAsync(base + o_v + npl, vd, nsc, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(base + o_pos, &p0, 4, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e == hipSuccess) {
     launch_flash_rows_split(st, hd, (const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
                             (const int*)(base + o_pos), (float*)(base + o_part), (float*)(base + o_out), (int)n_heads, (int)n_kv, (int)seq_cap,
-                            (int)rows, S);
+                            (int)rows, S, kv8);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, base + o_out, nq, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   (void)hipFree(base);
   if (e != hipSuccess) return hip_fail(dev, e, "debug_flash_attention_rows_split", __FILE__, __LINE__);
+  return 0;
+}
+int crabml_hip_debug_flash_attention_rows_split(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
+                                                size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, size_t slices, float* out) {
+  return debug_flash_attention_rows_split_impl(dev, q, k, nullptr, v, nullptr, n_heads, n_kv, head_dim, pos0, rows, seq_cap, slices, out);
+}
+// slices == 1: k_attn_flash_rows<.., KV8>; more: k_attn_flash_rows_split<.., KV8> and its merge
+int crabml_hip_debug_flash_attention_rows_q8(crabml_hip_device_t* dev, const float* q, const int8_t* kq, const uint16_t* kd, const int8_t* vq,
+                                             const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t pos0, size_t rows,
+                                             size_t seq_cap, size_t slices, float* out) {
+  if (!kd || !vd) return CRABML_HIP_BAD_INPUT;
+  if (slices <= 1) return debug_flash_attention_rows_impl(dev, q, kq, kd, vq, vd, n_heads, n_kv, head_dim, pos0, rows, seq_cap, out);
+  return debug_flash_attention_rows_split_impl(dev, q, kq, kd, vq, vd, n_heads, n_kv, head_dim, pos0, rows, seq_cap, slices, out);
+}
+// a Q8 context's planes of `rows` positions from pos0, every kv head: kq / vq [n_kv][rows][head_dim] int8, kd / vd [n_kv][rows][head_dim / 32] f16
+int crabml_hip_llama_debug_kv_q8_read(crabml_hip_llama_t* c, size_t layer, size_t pos0, size_t rows, int8_t* kq, uint16_t* kd, int8_t* vq,
+                                      uint16_t* vd) {
+  if (!c || !kq || !kd || !vq || !vd) return CRABML_HIP_BAD_INPUT;
+  crabml_hip_device* dev = c->dev;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  const size_t seq = c->cfg.seq_len, hd = (size_t)c->hd, nb = hd / 32, n_kv = (size_t)c->n_kv_l;
+  if (kv_kind(c->cfg) != KvKind::Q8 || layer >= c->cfg.n_layers || rows == 0 || pos0 + rows > seq)
+    CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama debug_kv_q8_read: a Q8 context, a layer and positions inside the cache");
+  const struct { const void* src; int8_t* q; uint16_t* d; } pl[2] = {{c->kc[layer], kq, kd}, {c->vc[layer], vq, vd}};
+  for (const auto& p : pl)
+    for (size_t h = 0; h < n_kv; h++) {
+      const char* q0 = (const char*)p.src + (h * seq + pos0) * hd;
+      const char* d0 = (const char*)p.src + n_kv * seq * hd + (h * seq + pos0) * nb * 2;
+      CH_HIP(dev, hipMemcpyAsync(p.q + h * rows * hd, q0, rows * hd, hipMemcpyDeviceToHost, dev->stream));
+      CH_HIP(dev, hipMemcpyAsync(p.d + h * rows * nb, d0, rows * nb * 2, hipMemcpyDeviceToHost, dev->stream));
+    }
+  CH_HIP(dev, hipStreamSynchronize(dev->stream));
   return 0;
 }
 

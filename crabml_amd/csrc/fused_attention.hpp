@@ -878,20 +878,57 @@ struct FlashGeom {
   static constexpr int NW = flash_geom_waves(G);
 };
 __host__ __device__ inline unsigned flash_threads(int G) { return (unsigned)flash_geom_waves(G) * 64; }
+// (both cache forms: the Q8 form's instruction covers 2 rpi rows, and it folds neighbouring row classes in registers before they meet
+// -- nw * (2 rpi) / 2 classes reach LDS)
 __host__ __device__ inline size_t flash_lds_bytes(int G, int hd) {
   const int nw = flash_geom_waves(G), rpi = 64 / (hd / 8), ncls = nw * rpi;
   return (size_t)ncls * G * hd * 4 + (size_t)ncls * G * 4 * 3 + 64;
 }
 __host__ __device__ inline size_t flash_part_floats(int G, int hd) { return (size_t)G * (hd + 2); }
-template <int G, int HD, bool Q81, bool TICKET>
+// KV8: the cache is the Q8 form (use_f16_kv_cache == 2): kc / vc point at a plane pair, int8 [n_kv][seq_cap][HD] with
+// f16 [n_kv][seq_cap][HD / 32] -- one scale per 32 elements -- right behind it (n_kv = gridDim.x / Smax).  A design of its own, not a
+// cast in the load:
+//   a lane's 16-byte load holds 16 elements, so a row is LPR = HD / 16 lanes and an instruction covers RPI = 1024 / HD rows -- twice the
+//   positions of the f16 form per load round; the lane's block scale (lanes 2 b, 2 b + 1 hold block b) is one more 2-byte request of
+//   the SAME round, not a dependent one
+//   scores  s_t = sum_lanes d_lane * (sum_{i in lane} f16(q_i) * k_t,i): q rounded to f16 as the f16 form rounds it, the int8 values
+//           made f16 exactly (bytes ^ 0x80 under the exponent of 1024, minus 1152: one v_perm + one v_pk_add per pair), v_dot2 with
+//           f32 accumulation, the scale applied once per lane = twice per block, in f32
+//   PV      O += (e_t * d_v) * v_t,i: the scale folded into the probability once per (position, lane), then one f32 FMA per int8 value
+//   the 2 NW RPI (wave, row class) states would double the LDS of the meeting: neighbouring classes (lane ^ LPR) are folded in
+//   registers first, so NCLS -- and flash_lds_bytes -- are the f16 form's
+//   groups 5 .. 7 (eight waves: 256 registers each) keep 8 elements per lane, the f16 form's lanes on 8-byte loads, and fold nothing
+// Nothing is rounded that the f16 form does not round: int8 x f16 is exact in f32; the deviation is the cache's quantization alone.
+template <int LPR>
+__device__ __forceinline__ float flash_lanes_sum(float v) {  // over the LPR = 4, 8 or 16 lanes of a Q8 row
+  v += dpp_f<0xB1>(v);
+  v += dpp_f<0x4E>(v);
+  if constexpr (LPR >= 8) v += dpp_f<0x141>(v);
+  if constexpr (LPR >= 16) v += dpp_f<0x140>(v);
+  return v;
+}
+// four int8 of a dword -> two f16 pairs (elements 0, 1 and 2, 3), exactly
+__device__ __forceinline__ void q8x4_to_h16(unsigned w, h16x2& lo, h16x2& hi) {
+  const unsigned u = w ^ 0x80808080u;  // q + 128 in every byte
+  const h16x2 off = {(_Float16)1152.0f, (_Float16)1152.0f};
+  lo = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(0x64646464u, u, 0x04010400u)) - off;  // f16 bits 0x6400 | b = 1024 + b
+  hi = __builtin_bit_cast(h16x2, __builtin_amdgcn_perm(0x64646464u, u, 0x04030402u)) - off;
+}
+template <int G, int HD, bool Q81, bool TICKET, bool KV8 = false>
 __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const float* __restrict__ q, const unsigned short* __restrict__ kc,
                                                                      const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
                                                                      float* __restrict__ part, unsigned* __restrict__ tick,
                                                                      float* __restrict__ out, signed char* __restrict__ xq,
                                                                      unsigned short* __restrict__ xd, void* __restrict__ xisum, int seq_cap,
                                                                      int Smax, int min_rows) {
-  constexpr int NW = FlashGeom<G>::NW, LPR = HD / 8, RPI = 64 / LPR, NCLS = NW * RPI, U = 4, NT = NW * 64;
-  static_assert(HD == 64 || HD == 128 || HD == 256, "a K / V row is 8, 16 or 32 lanes x 16 bytes");
+  // EPL: elements per lane and load.  Q8 at groups 5 .. 7 -- eight waves, so 256 registers each, against 16 G accumulators + 8 G of q --
+  // keeps the f16 form's 8 elements per lane (8-byte loads, nothing to fold): 16 would spill.  Group 8 runs four waves, 512 registers
+  // each, and keeps 16: the compiler's report for <8, 128, KV8> is 256 VGPRs + 76 AGPRs and 6 SGPR spills, no scratch, one workgroup
+  // per CU (group 4: 167 VGPRs against the f16 form's 90).  Its decode speed with this cache is not measured.
+  constexpr int NW = FlashGeom<G>::NW, EPL = KV8 && !(G >= 5 && G <= 7) ? 16 : 8, LPR = HD / EPL, RPI = 64 / LPR, U = 4, NT = NW * 64;
+  constexpr bool FOLD = KV8 && EPL == 16;
+  constexpr int NCLS = NW * (FOLD ? RPI / 2 : RPI);
+  static_assert(HD == 64 || HD == 128 || (HD == 256 && !KV8), "a K / V row is 8, 16 or 32 lanes x 16 bytes (Q8: 4 or 8)");
   extern __shared__ __attribute__((aligned(16))) float fl_lds[];
   float* sacc = fl_lds;                 // [NCLS][G][HD]
   float* sm = sacc + NCLS * G * HD;     // [NCLS][G]
@@ -901,13 +938,13 @@ __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const floa
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int rc = lane / LPR, dl = lane % LPR;
   const int j = blockIdx.x / Smax, sp = blockIdx.x % Smax;
-  // q of the G heads that share kv head j: this lane's 8 dims (requested before the position is read: the two round trips overlap)
-  f32x4 qa[G], qb[G];
+  // q of the G heads that share kv head j: this lane's EPL dims (requested before the position is read: the two round trips overlap)
+  f32x4 qf[G][EPL / 4];
 #pragma unroll
   for (int g = 0; g < G; g++) {
-    const f32x4* qp = (const f32x4*)(q + (size_t)(j * G + g) * HD + 8 * dl);
-    qa[g] = qp[0];
-    qb[g] = qp[1];
+    const f32x4* qp = (const f32x4*)(q + (size_t)(j * G + g) * HD + EPL * dl);
+#pragma unroll
+    for (int w = 0; w < EPL / 4; w++) qf[g][w] = qp[w];
   }
   const int seq = *pos_d + 1;
   // The grid is sized for the longest context (Smax slices per kv head); a step uses S <= Smax of them -- at least min_rows
@@ -920,21 +957,91 @@ __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const floa
   const int r0 = sp * chunk, r1 = r0 + chunk < seq ? r0 + chunk : seq;
   const int ngroups = r1 > r0 ? (r1 - r0 + RPI - 1) / RPI : 0;
   // rounded to f16 (batch_matmul.rs:39)
-  i32x4 qh[G];
+  i32x4 qh[G][EPL / 8];
 #pragma unroll
   for (int g = 0; g < G; g++) {
-    const f32x4 a = qa[g], b = qb[g];
-    qh[g] = i32x4{(int)((unsigned)f2h(a[0]) | ((unsigned)f2h(a[1]) << 16)), (int)((unsigned)f2h(a[2]) | ((unsigned)f2h(a[3]) << 16)),
-                  (int)((unsigned)f2h(b[0]) | ((unsigned)f2h(b[1]) << 16)), (int)((unsigned)f2h(b[2]) | ((unsigned)f2h(b[3]) << 16))};
+#pragma unroll
+    for (int w = 0; w < EPL / 8; w++) {
+      const f32x4 a = qf[g][2 * w], b = qf[g][2 * w + 1];
+      qh[g][w] = i32x4{(int)((unsigned)f2h(a[0]) | ((unsigned)f2h(a[1]) << 16)), (int)((unsigned)f2h(a[2]) | ((unsigned)f2h(a[3]) << 16)),
+                       (int)((unsigned)f2h(b[0]) | ((unsigned)f2h(b[1]) << 16)), (int)((unsigned)f2h(b[2]) | ((unsigned)f2h(b[3]) << 16))};
+    }
   }
-  float m[G], l[G], acc[G][8];
+  float m[G], l[G], acc[G][EPL];
 #pragma unroll
   for (int g = 0; g < G; g++) {
     m[g] = -INFINITY;
     l[g] = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; i++) acc[g][i] = 0.f;
+    for (int i = 0; i < EPL; i++) acc[g][i] = 0.f;
   }
+  if constexpr (KV8) {
+    constexpr int NB = HD / 32;
+    typedef int kvec __attribute__((ext_vector_type(EPL / 4)));  // a lane's EPL int8
+    const size_t plane = (size_t)(gridDim.x / Smax) * seq_cap * HD;  // bytes of an int8 plane: its scales lie right behind it
+    const signed char* kq = (const signed char*)kc + (size_t)j * seq_cap * HD + EPL * dl;
+    const signed char* vq = (const signed char*)vc + (size_t)j * seq_cap * HD + EPL * dl;
+    const unsigned short* ks = (const unsigned short*)((const signed char*)kc + plane) + (size_t)j * seq_cap * NB + EPL * dl / 32;
+    const unsigned short* vs = (const unsigned short*)((const signed char*)vc + plane) + (size_t)j * seq_cap * NB + EPL * dl / 32;
+    for (int g0 = wave; g0 < ngroups; g0 += NW * U) {
+      kvec kk[U], vv[U];
+      unsigned short kd[U], vd[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {  // every load of the round -- the scales among them -- is in flight before the first dot
+        const int row = r0 + (g0 + u * NW) * RPI + rc;
+        const int rowc = row < r1 ? row : r1 - 1;
+        kk[u] = __builtin_nontemporal_load((const kvec*)(kq + (size_t)rowc * HD));
+        vv[u] = __builtin_nontemporal_load((const kvec*)(vq + (size_t)rowc * HD));
+        kd[u] = ks[(size_t)rowc * NB];
+        vd[u] = vs[(size_t)rowc * NB];
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        if (g0 + u * NW >= ngroups) break;  // wave-uniform
+        const bool live = r0 + (g0 + u * NW) * RPI + rc < r1;
+        const float dk = h2f(kd[u]), dv = h2f(vd[u]);
+        h16x2 kh[EPL / 2];
+        float vf[EPL];
+#pragma unroll
+        for (int i = 0; i < EPL / 4; i++) {
+          q8x4_to_h16((unsigned)kk[u][i], kh[2 * i], kh[2 * i + 1]);
+          h16x2 a, b;
+          q8x4_to_h16((unsigned)vv[u][i], a, b);
+          vf[4 * i] = (float)a[0];
+          vf[4 * i + 1] = (float)a[1];
+          vf[4 * i + 2] = (float)b[0];
+          vf[4 * i + 3] = (float)b[1];
+        }
+#pragma unroll
+        for (int g = 0; g < G; g++) {
+          float s = 0.f;
+#pragma unroll
+          for (int i = 0; i < EPL / 2; i++) s = __builtin_amdgcn_fdot2(kh[i], __builtin_bit_cast(h16x2, (unsigned)qh[g][i >> 2][i & 3]), s, false);
+          s = flash_lanes_sum<LPR>(s * dk);
+          s = live ? s : -INFINITY;
+          const float mn = fmaxf(m[g], s);
+          const float alpha = mn == -INFINITY ? 1.0f : __expf(m[g] - mn);
+          const float pe = mn == -INFINITY ? 0.0f : __expf(s - mn);
+          m[g] = mn;
+          l[g] = l[g] * alpha + pe;
+          const float pd = pe * dv;
+#pragma unroll
+          for (int i = 0; i < EPL; i++) acc[g][i] = __builtin_fmaf(pd, vf[i], acc[g][i] * alpha);
+        }
+      }
+    }
+    // neighbouring row classes meet in registers: class rc takes class rc ^ 1 (lane ^ LPR) in; the even ones go on to LDS
+#pragma unroll
+    for (int g = 0; g < (FOLD ? G : 0); g++) {
+      const float mo = __shfl_xor(m[g], LPR), lo = __shfl_xor(l[g], LPR);
+      const float M = fmaxf(m[g], mo);
+      const float wa = m[g] == -INFINITY ? 0.0f : __expf(m[g] - M), wb = mo == -INFINITY ? 0.0f : __expf(mo - M);
+      l[g] = l[g] * wa + lo * wb;
+#pragma unroll
+      for (int i = 0; i < EPL; i++) acc[g][i] = acc[g][i] * wa + __shfl_xor(acc[g][i], LPR) * wb;
+      m[g] = M;
+    }
+  } else {
   const unsigned short* kb = kc + (size_t)j * seq_cap * HD + 8 * dl;
   const unsigned short* vb = vc + (size_t)j * seq_cap * HD + 8 * dl;
   for (int g0 = wave; g0 < ngroups; g0 += NW * U) {
@@ -962,7 +1069,7 @@ __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const floa
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; i++)
-          s = __builtin_amdgcn_fdot2(__builtin_bit_cast(h16x2, (unsigned)kk[u][i]), __builtin_bit_cast(h16x2, (unsigned)qh[g][i]), s, false);
+          s = __builtin_amdgcn_fdot2(__builtin_bit_cast(h16x2, (unsigned)kk[u][i]), __builtin_bit_cast(h16x2, (unsigned)qh[g][0][i]), s, false);
         s = flash_row_sum<HD>(s);
         s = live ? s : -INFINITY;
         const float mn = fmaxf(m[g], s);
@@ -976,16 +1083,19 @@ __global__ __launch_bounds__(FlashGeom<G>::NW * 64) void k_attn_flash(const floa
       }
     }
   }
+  }
   // ---- the NCLS (wave, row class) states meet in LDS ---------------------------------------------------------------
-  const int cls = wave * RPI + rc;
+  const int cls = FOLD ? wave * (RPI / 2) + (rc >> 1) : wave * RPI + rc;
+  if (!FOLD || (rc & 1) == 0) {
 #pragma unroll
-  for (int g = 0; g < G; g++) {
-    f32x4* dst = (f32x4*)(sacc + ((size_t)cls * G + g) * HD + 8 * dl);
-    dst[0] = f32x4{acc[g][0], acc[g][1], acc[g][2], acc[g][3]};
-    dst[1] = f32x4{acc[g][4], acc[g][5], acc[g][6], acc[g][7]};
-    if (dl == 0) {
-      sm[cls * G + g] = m[g];
-      sl[cls * G + g] = l[g];
+    for (int g = 0; g < G; g++) {
+      f32x4* dst = (f32x4*)(sacc + ((size_t)cls * G + g) * HD + EPL * dl);
+#pragma unroll
+      for (int w = 0; w < EPL / 4; w++) dst[w] = f32x4{acc[g][4 * w], acc[g][4 * w + 1], acc[g][4 * w + 2], acc[g][4 * w + 3]};
+      if (dl == 0) {
+        sm[cls * G + g] = m[g];
+        sl[cls * G + g] = l[g];
+      }
     }
   }
   __syncthreads();
@@ -1169,11 +1279,38 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 __host__ __device__ inline size_t flash_rows_lds_bytes(int hd) {
   return (size_t)2 * ((size_t)hd * FLASH_ROWS_VSTR + (size_t)FLASH_ROWS_BN * (hd + FLASH_ROWS_KPAD)) * 2;
 }
-template <int HD>
+// KV8 (this kernel and k_attn_flash_rows_split): the cache is the Q8 plane pair k_attn_flash<.., KV8> describes.  The matrix products
+// keep their f16 LDS tiles; the staging differs: a 16-byte piece is 16 int8 of one position -- half a block, so one scale, requested
+// with the piece -- and a tile of 64 positions is 4 HD pieces, expanded on the way into LDS: K^ = f16(d * q), V^ = f16(d * q) (d * q
+// is exact in f32; that f16 rounding, 2^-11 relative per element, is the ONE rounding this form adds to k_attn_flash_rows').  V is
+// zeroed AFTER the product at positions no row of the workgroup sees and K is left to the mask, so junk there -- NaN / Inf scales
+// included -- reaches no output.
+__device__ __forceinline__ unsigned short q8_to_h16(unsigned w, int byte, float d) {
+  return hraw((_Float16)(d * (float)(int)(signed char)(w >> (8 * byte))));
+}
+// one Q8 piece into the tiles: K as the cache row holds it, V transposed
+template <int VSTR>
+__device__ __forceinline__ void flash_rows_place_q8(unsigned short* krow, unsigned short* vcol, const i32x4& kk, const i32x4& vv, unsigned dd, bool live) {
+  const float dk = h2f((unsigned short)(dd & 0xffffu)), dv = h2f((unsigned short)(dd >> 16));
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    i32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const unsigned w = (unsigned)kk[2 * h + (i >> 1)];
+      o[i] = (int)((unsigned)q8_to_h16(w, 2 * (i & 1), dk) | ((unsigned)q8_to_h16(w, 2 * (i & 1) + 1, dk) << 16));
+    }
+    *(i32x4*)(krow + 8 * h) = o;
+  }
+#pragma unroll
+  for (int e = 0; e < 16; e++) vcol[e * VSTR] = live ? q8_to_h16((unsigned)vv[e >> 2], e & 3, dv) : (unsigned short)0;
+}
+template <int HD, bool KV8 = false>
 __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict__ q, const unsigned short* __restrict__ kc,
                                                          const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
                                                          float* __restrict__ out, int n_heads, int n_kv, int seq_cap, int B) {
-  constexpr int KS = HD / 32, DT = HD / 16, BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD, NP = HD / 64;
+  constexpr int KS = HD / 32, DT = HD / 16, BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD, NP = KV8 ? 1 : HD / 64;
+  constexpr int PPR = HD / 16, NB = HD / 32;  // KV8: pieces and scales of a cache row; a tile is BN * PPR <= 512 pieces, one per thread
   static_assert(BN == 64, "a fill is two 32-position steps: one per wave of a pair");
   // LDS, two buffers each: V^T tile [HD][VSTR] (filled transposed), K tile [BN][KSTR] (as the cache holds it)
   extern __shared__ __attribute__((aligned(16))) unsigned short fr_lds[];
@@ -1209,7 +1346,23 @@ __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict
   // staging: thread t moves NP 16-byte pieces of the K tile and of the V tile per fill (piece = 8 dims of one position); a whole
   // tile of compute lies between the request and the commit
   i32x4 vreg[NP], kreg[NP];
+  unsigned dreg = 0;  // KV8: the piece's K scale | V scale << 16
+  const signed char* kq = (const signed char*)kc + (size_t)j * seq_cap * HD;
+  const signed char* vq = (const signed char*)vc + (size_t)j * seq_cap * HD;
+  const unsigned short* ks = (const unsigned short*)((const signed char*)kc + (size_t)n_kv * seq_cap * HD) + (size_t)j * seq_cap * NB;
+  const unsigned short* vs = (const unsigned short*)((const signed char*)vc + (size_t)n_kv * seq_cap * HD) + (size_t)j * seq_cap * NB;
   auto issue = [&](int tile) {
+    if constexpr (KV8) {
+      if (tid < BN * PPR) {
+        const int pr = tid / PPR, pc = tid % PPR;
+        int pos = tile * BN + pr;
+        pos = pos < seq_cap ? pos : seq_cap - 1;
+        kreg[0] = *(const i32x4*)(kq + (size_t)pos * HD + 16 * pc);
+        vreg[0] = *(const i32x4*)(vq + (size_t)pos * HD + 16 * pc);
+        dreg = (unsigned)ks[(size_t)pos * NB + (pc >> 1)] | ((unsigned)vs[(size_t)pos * NB + (pc >> 1)] << 16);
+      }
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < NP; u++) {
       const int piece = tid + 512 * u, pr = piece / (HD / 8), pc = piece % (HD / 8);
@@ -1222,6 +1375,13 @@ __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict
   auto commit = [&](int buf, int tile) {
     unsigned short* vt = vt0 + buf * HD * VSTR;
     unsigned short* kt = kt0 + buf * BN * KSTR;
+    if constexpr (KV8) {
+      if (tid < BN * PPR) {
+        const int pr = tid / PPR, pc = tid % PPR;
+        flash_rows_place_q8<VSTR>(kt + pr * KSTR + 16 * pc, vt + (16 * pc) * VSTR + pr, kreg[0], vreg[0], dreg, tile * BN + pr <= last_wg);
+      }
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < NP; u++) {
       const int piece = tid + 512 * u, pr = piece / (HD / 8), pc = piece % (HD / 8);
@@ -1365,26 +1525,39 @@ __host__ __device__ inline size_t flash_rows_part_floats(int slices, int rows, i
 // (both kernels keep their f32 vector arithmetic -- the accumulator rescale -- on the one-value VALU forms)
 #define FLASH_ROWS_SPLIT_TARGET __attribute__((target("no-packed-fp32-ops")))
 // the staging of one workgroup's K / V tiles: global -> registers (issue) -> LDS (commit)
-template <int HD>
+// (KV8: a piece is 16 int8 of a position and carries its two scales, `dd` = K scale | V scale << 16; ks / vs = the kv head's scale rows)
+template <int HD, bool KV8 = false>
 struct FrsTiles {
-  static constexpr int BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD, PIECES = BN * HD / 8, NPR = PIECES / 256;
+  static constexpr int BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD, EPP = KV8 ? 16 : 8, PIECES = BN * HD / EPP,
+                       NPR = PIECES / 256;
   const unsigned short *kb, *vb;
   unsigned short *vt0, *kt0;
   int seq_cap, last_wg, tid, nthr;
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void fetch(int tile, int piece, i32x4& kk, i32x4& vv) const {
-    const int pr = piece / (HD / 8), pc = piece % (HD / 8);
+  const unsigned short *ks, *vs;
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void fetch(int tile, int piece, i32x4& kk, i32x4& vv, unsigned& dd) const {
+    const int pr = piece / (HD / EPP), pc = piece % (HD / EPP);
     int pos = tile * BN + pr;
     pos = pos < seq_cap ? pos : seq_cap - 1;  // (past the cache only in its last tile; those positions are dead)
+    if constexpr (KV8) {
+      kk = *(const i32x4*)((const signed char*)kb + (size_t)pos * HD + 16 * pc);
+      vv = *(const i32x4*)((const signed char*)vb + (size_t)pos * HD + 16 * pc);
+      dd = (unsigned)ks[(size_t)pos * (HD / 32) + (pc >> 1)] | ((unsigned)vs[(size_t)pos * (HD / 32) + (pc >> 1)] << 16);
+      return;
+    }
     kk = *(const i32x4*)(kb + (size_t)pos * HD + 8 * pc);
     vv = *(const i32x4*)(vb + (size_t)pos * HD + 8 * pc);
   }
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void place(int buf, int tile, int piece, const i32x4& kk, const i32x4& vv) const {
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void place(int buf, int tile, int piece, const i32x4& kk, const i32x4& vv, unsigned dd) const {
     unsigned short* vt = vt0 + buf * HD * VSTR;
     unsigned short* kt = kt0 + buf * BN * KSTR;
-    const int pr = piece / (HD / 8), pc = piece % (HD / 8);
+    const int pr = piece / (HD / EPP), pc = piece % (HD / EPP);
     // positions no row of the workgroup sees hold whatever the allocator or an earlier sequence left in the cache: their
     // probabilities are exactly 0, but 0 x NaN / Inf is not -- V enters the product as zeros there (K: the scores are masked)
     const bool live = tile * BN + pr <= last_wg;
+    if constexpr (KV8) {
+      flash_rows_place_q8<VSTR>(kt + pr * KSTR + 16 * pc, vt + (16 * pc) * VSTR + pr, kk, vv, dd, live);
+      return;
+    }
     *(i32x4*)(kt + pr * KSTR + 8 * pc) = kk;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -1393,28 +1566,30 @@ struct FrsTiles {
       vt[(8 * pc + 2 * i + 1) * VSTR + pr] = (unsigned short)(w >> 16);
     }
   }
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void issue(int tile, i32x4 (&kreg)[NPR], i32x4 (&vreg)[NPR]) const {
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void issue(int tile, i32x4 (&kreg)[NPR], i32x4 (&vreg)[NPR], unsigned (&dreg)[NPR]) const {
 #pragma unroll
     for (int u = 0; u < NPR; u++)
-      if (tid + nthr * u < PIECES) fetch(tile, tid + nthr * u, kreg[u], vreg[u]);
+      if (tid + nthr * u < PIECES) fetch(tile, tid + nthr * u, kreg[u], vreg[u], dreg[u]);
   }
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void commit(int buf, int tile, const i32x4 (&kreg)[NPR], const i32x4 (&vreg)[NPR]) const {
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void commit(int buf, int tile, const i32x4 (&kreg)[NPR], const i32x4 (&vreg)[NPR],
+                                                                 const unsigned (&dreg)[NPR]) const {
 #pragma unroll
     for (int u = 0; u < NPR; u++)
-      if (tid + nthr * u < PIECES) place(buf, tile, tid + nthr * u, kreg[u], vreg[u]);
+      if (tid + nthr * u < PIECES) place(buf, tile, tid + nthr * u, kreg[u], vreg[u], dreg[u]);
     for (int piece = tid + nthr * NPR; piece < PIECES; piece += nthr) {  // fewer than 4 waves: the rest of the tile, fetched here
       i32x4 kk, vv;
-      fetch(tile, piece, kk, vv);
-      place(buf, tile, piece, kk, vv);
+      unsigned dd = 0;
+      fetch(tile, piece, kk, vv, dd);
+      place(buf, tile, piece, kk, vv, dd);
     }
   }
 };
-template <int HD>
+template <int HD, bool KV8 = false>
 FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(512) void k_attn_flash_rows_split(const float* __restrict__ q, const unsigned short* __restrict__ kc,
                                                                const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
                                                                float* __restrict__ part, int n_heads, int n_kv, int seq_cap, int B, int S) {
   constexpr int KS = HD / 32, DT = HD / 16, BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD;
-  constexpr int PIECES = BN * HD / 8, NPR = PIECES / 256;  // 16-byte pieces of a K (or V) tile; of them in registers per thread
+  constexpr int NPR = FrsTiles<HD, KV8>::NPR;  // 16-byte pieces of a K (or V) tile in registers per thread
   extern __shared__ __attribute__((aligned(16))) unsigned short fr_lds[];
   unsigned short* vt0 = fr_lds;
   unsigned short* kt0 = fr_lds + 2 * HD * VSTR;
@@ -1451,17 +1626,24 @@ FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(512) void k_attn_flash_rows
   for (int dt = 0; dt < DT; dt++) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, lsum = 0.f;
   i32x4 vreg[NPR], kreg[NPR];
-  const FrsTiles<HD> tl{kb, vb, vt0, kt0, seq_cap, last_wg, tid, nthr};
+  unsigned dreg[NPR];
+  // (KV8: kb / vb are the kv head's int8 rows -- HD bytes each, half the f16 rows' offset -- and the scale planes lie behind the int8 planes)
+  const size_t plane = (size_t)n_kv * seq_cap * HD, srow = (size_t)j * seq_cap * (HD / 32);
+  const FrsTiles<HD, KV8> tl{KV8 ? (const unsigned short*)((const signed char*)kc + (size_t)j * seq_cap * HD) : kb,
+                             KV8 ? (const unsigned short*)((const signed char*)vc + (size_t)j * seq_cap * HD) : vb,
+                             vt0, kt0, seq_cap, last_wg, tid, nthr,
+                             KV8 ? (const unsigned short*)((const signed char*)kc + plane) + srow : nullptr,
+                             KV8 ? (const unsigned short*)((const signed char*)vc + plane) + srow : nullptr};
   if (t0 < t1) {
-    tl.issue(t0, kreg, vreg);
-    tl.commit(0, t0, kreg, vreg);
+    tl.issue(t0, kreg, vreg, dreg);
+    tl.commit(0, t0, kreg, vreg, dreg);
   }
   __syncthreads();
   for (int tile = t0; tile < t1; tile++) {
     const int buf = (tile - t0) & 1;
     const unsigned short* vt = vt0 + buf * HD * VSTR;
     const unsigned short* kt = kt0 + buf * BN * KSTR;
-    if (tile + 1 < t1) tl.issue(tile + 1, kreg, vreg);
+    if (tile + 1 < t1) tl.issue(tile + 1, kreg, vreg, dreg);
 #pragma unroll
     for (int c2 = 0; c2 < 2; c2++) {
       // k_attn_flash_rows' 32-position step: two 16-position chunks a / b, two independent S^T chains, one agreement on the running
@@ -1510,7 +1692,7 @@ FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(512) void k_attn_flash_rows
         }
       }
     }
-    if (tile + 1 < t1) tl.commit(buf ^ 1, tile + 1, kreg, vreg);  // those buffers were last read one tile ago (barrier below)
+    if (tile + 1 < t1) tl.commit(buf ^ 1, tile + 1, kreg, vreg, dreg);  // those buffers were last read one tile ago (barrier below)
     __syncthreads();
   }
   lsum += __shfl_xor(lsum, 16);
@@ -1544,6 +1726,33 @@ FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(HD) void k_attn_flash_rows_
     o = __builtin_fmaf(part[r * HD + d], w, o);
   }
   out[(size_t)rec * HD + d] = o / L;
+}
+
+// ---- the Q8 KV cache's append (use_f16_kv_cache == 2): R staged rows -> both planes of K and of V at positions *pos_d .. + R ----------
+// `stage` is what the q|k|v launches leave in their staging form (QkvEpi::kv16 == 2): [R][2 kv_dim] f32, the roped K row then the V
+// row.  A 32-element block is 8 lanes x one f32x4: a wave takes 8 blocks, the block maximum is agreed across the 8 lanes on DPP, every
+// lane stores its 4 int8 as one dword and the block's first lane the f16 scale (q8_kv_quant: the one copy of the rule).
+__global__ __launch_bounds__(256) void k_kv_store_q8(const float* __restrict__ stage, signed char* __restrict__ kc, signed char* __restrict__ vc,
+                                                     const int* __restrict__ pos_d, int rows, int n_kv, int hd, int seq_cap) {
+  const int kv_dim = n_kv * hd, bpr = 2 * kv_dim / 32, total = rows * bpr;  // blocks of a staged row, of the launch
+  const int t = blockIdx.x * 256 + threadIdx.x, gb = t >> 3, sub = t & 7;
+  const int b = gb < total ? gb : total - 1;  // (whole 8-lane groups: the lanes past the last block redo it and store nothing)
+  const int r = b / bpr, e = (b % bpr) * 32;
+  const f32x4 x = *(const f32x4*)(stage + (size_t)r * 2 * kv_dim + e + 4 * sub);
+  float a = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
+  a = fmaxf(a, dpp_f<0xB1>(a));
+  a = fmaxf(a, dpp_f<0x4E>(a));
+  a = fmaxf(a, dpp_f<0x141>(a));
+  const unsigned short dh = f2h(a / 127.0f);
+  const float d = h2f(dh);
+  const unsigned packed = pack_q8x4(q8_kv_quant(x[0], d), q8_kv_quant(x[1], d), q8_kv_quant(x[2], d), q8_kv_quant(x[3], d));
+  if (gb >= total) return;
+  const bool is_v = e >= kv_dim;
+  const int el = is_v ? e - kv_dim : e;
+  signed char* plane = is_v ? vc : kc;
+  const size_t row = (size_t)(el / hd) * seq_cap + (size_t)(*pos_d + r);
+  *(unsigned*)(plane + row * hd + el % hd + 4 * sub) = packed;
+  if (sub == 0) ((unsigned short*)(plane + (size_t)n_kv * seq_cap * hd))[row * (hd / 32) + (el % hd) / 32] = dh;
 }
 
 // ---- batched-prefill attention: one workgroup = one kv head x R consecutive prompt rows x the G q heads of its

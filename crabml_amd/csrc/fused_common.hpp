@@ -335,8 +335,13 @@ struct QkvEpi {
   const float* rope;  // [seq_cap][npairs][2] (cos, sin)
   const int* pos_d;
   float scale;        // 1 / sqrt(hd)
-  int dim, kv_dim, hd, rope_dim, npairs, seq_cap, kv16;
+  int dim, kv_dim, hd, rope_dim, npairs, seq_cap, kv16;  // kv16: the cache kind -- 0 f32, 1 f16, 2 Q8 (kc / vc = the staging rows)
 };
+// kv16 == 2, the Q8 cache: K and V leave the launch as f32 in a staging buffer, [row of the pass][2 kv_dim] = the K row, then the V row
+// (kc = its base, vc = kc + kv_dim); k_kv_store_q8 quantizes them into the planes.  `r`: the row inside K (or V).
+__device__ __forceinline__ size_t qkv_stage_at(const QkvEpi& e, int pos, int r) {
+  return (size_t)(pos - *e.pos_d) * (2 * e.kv_dim) + r;
+}
 
 // position + rotation for the pair starting at row0, loaded early (before the weight stream is consumed)
 struct QkvPre {
@@ -389,8 +394,8 @@ __device__ __forceinline__ void qkv_epilogue(const QkvEpi& e, const QkvPre& pre,
       e.q_out[row0 + 1] = r1 * e.scale;
     } else {
       const int kr = row0 - e.dim;
-      const size_t o = ((size_t)(kr / e.hd) * e.seq_cap + pos) * e.hd + i;
-      if (e.kv16) {
+      const size_t o = e.kv16 == 2 ? qkv_stage_at(e, pos, kr) : ((size_t)(kr / e.hd) * e.seq_cap + pos) * e.hd + i;
+      if (e.kv16 == 1) {
         ((unsigned short*)e.kc)[o] = f2h(r0);
         ((unsigned short*)e.kc)[o + 1] = f2h(r1);
       } else {
@@ -400,8 +405,8 @@ __device__ __forceinline__ void qkv_epilogue(const QkvEpi& e, const QkvPre& pre,
     }
   } else {
     const int vr = row0 - e.dim - e.kv_dim;
-    const size_t o = ((size_t)(vr / e.hd) * e.seq_cap + pos) * e.hd + (vr % e.hd);
-    if (e.kv16) {
+    const size_t o = e.kv16 == 2 ? qkv_stage_at(e, pos, vr) : ((size_t)(vr / e.hd) * e.seq_cap + pos) * e.hd + (vr % e.hd);
+    if (e.kv16 == 1) {
       ((unsigned short*)e.vc)[o] = f2h(s0);
       ((unsigned short*)e.vc)[o + 1] = f2h(s1);
     } else {
@@ -495,8 +500,8 @@ __device__ __forceinline__ void qkv_epilogue_neox(const E& e, const P& pre, int 
       e.q_out[row0 + rs] = r1 * e.scale;
     } else {
       const int kr = row0 - e.dim;
-      const size_t o = ((size_t)(kr / e.hd) * e.seq_cap + pos) * e.hd + kr % e.hd;
-      if (e.kv16) {
+      const size_t o = e.kv16 == 2 ? qkv_stage_at(e, pos, kr) : ((size_t)(kr / e.hd) * e.seq_cap + pos) * e.hd + kr % e.hd;
+      if (e.kv16 == 1) {
         ((unsigned short*)e.kc)[o] = f2h(r0);
         ((unsigned short*)e.kc)[o + rs] = f2h(r1);
       } else {
@@ -506,8 +511,8 @@ __device__ __forceinline__ void qkv_epilogue_neox(const E& e, const P& pre, int 
     }
   } else {
     const int vr = row0 - e.dim - e.kv_dim;
-    const size_t o = ((size_t)(vr / e.hd) * e.seq_cap + pos) * e.hd + (vr % e.hd);
-    if (e.kv16) {
+    const size_t o = e.kv16 == 2 ? qkv_stage_at(e, pos, vr) : ((size_t)(vr / e.hd) * e.seq_cap + pos) * e.hd + (vr % e.hd);
+    if (e.kv16 == 1) {
       ((unsigned short*)e.vc)[o] = f2h(s0);
       ((unsigned short*)e.vc)[o + 1] = f2h(s1);
     } else {

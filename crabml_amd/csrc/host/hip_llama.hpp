@@ -68,7 +68,7 @@ class HipLlamaRunner {
     crabml_hip_llama_arch_t arch{};
     bool plain = false;  // a Llama model without biases: the plain create serves it
     std::vector<const crabml_hip_buf_t*> att, ffn, wq, wk, wv, wo, gate, down, up, bq, bk, bv;
-    CreateArgs(const LlamaConfig& conf, const LlamaWeights<HipTensor>& W, size_t seq_len, bool use_f16_kv_cache, bool use_graph, bool prefetch,
+    CreateArgs(const LlamaConfig& conf, const LlamaWeights<HipTensor>& W, size_t seq_len, int use_f16_kv_cache, bool use_graph, bool prefetch,
                int tp_size, int tp_rank, const TpComm* comm, bool norm_epilogue, int extra_flags, size_t attn_long_from, size_t prefill_chunk) {
       c.embedding_dim = conf.embedding_dim;
       c.hidden_dim = conf.hidden_dim;
@@ -79,7 +79,7 @@ class HipLlamaRunner {
       c.seq_len = seq_len;
       c.rope_dim = conf.rope_dim.value_or(conf.head_size());
       c.rms_norm_eps = conf.rms_norm_eps;
-      c.use_f16_kv_cache = use_f16_kv_cache ? 1 : 0;
+      c.use_f16_kv_cache = use_f16_kv_cache;  // 0 f32, 1 f16, 2 Q8 (CRABML_HIP_KV_CACHE_Q8); Python's False / True arrive as 0 / 1
       c.flags = (use_graph ? 0 : CRABML_HIP_LLAMA_NO_GRAPH) | (prefetch ? 0 : CRABML_HIP_LLAMA_NO_PREFETCH) |
                 (norm_epilogue ? 0 : CRABML_HIP_LLAMA_NO_NORM_EPILOGUE) | extra_flags;
       c.tp_size = tp_size;
@@ -125,7 +125,7 @@ class HipLlamaRunner {
   // create_entry (tests): 0 = crabml_hip_llama_create for a Llama model without biases, crabml_hip_llama_create_arch otherwise;
   // 1 = create_arch with the architecture struct always; 2 = create_arch(NULL) (Llama models)
   HipLlamaRunner(const LlamaConfig& conf, std::shared_ptr<LlamaWeights<HipTensor>> w, HipTensorDeviceRef device,
-                 size_t seq_len, bool use_f16_kv_cache, bool use_graph = true, bool prefetch = true, int tp_size = 1,
+                 size_t seq_len, int use_f16_kv_cache, bool use_graph = true, bool prefetch = true, int tp_size = 1,
                  int tp_rank = 0, std::shared_ptr<TpComm> comm = nullptr, bool norm_epilogue = true, int extra_flags = 0,
                  size_t attn_long_from = 0, size_t prefill_chunk = 0, int create_entry = 0)
       : conf_(conf), weights_(std::move(w)), device_(std::move(device)), comm_(std::move(comm)), tp_size_(tp_size > 1 ? tp_size : 1) {
@@ -140,7 +140,7 @@ class HipLlamaRunner {
   }
   // crabml_hip_debug_step_plan: the plan words (CRABML_HIP_STEPPLAN_*) of the context the constructor would create for these arguments
   static std::vector<int32_t> step_plan(const LlamaConfig& conf, const LlamaWeights<HipTensor>& w, HipTensorDevice& device, size_t seq_len,
-                                        bool use_f16_kv_cache, bool use_graph, bool prefetch, int tp_size, int tp_rank, bool norm_epilogue,
+                                        int use_f16_kv_cache, bool use_graph, bool prefetch, int tp_size, int tp_rank, bool norm_epilogue,
                                         int extra_flags, size_t attn_long_from) {
     const CreateArgs a(conf, w, seq_len, use_f16_kv_cache, use_graph, prefetch, tp_size, tp_rank, nullptr, norm_epilogue, extra_flags,
                        attn_long_from, 0);

@@ -198,6 +198,35 @@ PYBIND11_MODULE(_host, m) {
                                                                  seq_cap, slices, out.mutable_data()));
              return out;
            })
+      // the Q8-cache forms: kq, vq [n_kv][seq_cap][head_dim] int8; kd, vd [n_kv][seq_cap][head_dim / 32] f16 bits
+      .def("debug_flash_attention_q8",
+           [](HipTensorDevice& d, py::array_t<float, py::array::c_style | py::array::forcecast> q,
+              py::array_t<int8_t, py::array::c_style | py::array::forcecast> kq, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> kd,
+              py::array_t<int8_t, py::array::c_style | py::array::forcecast> vq, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> vd,
+              size_t n_heads, size_t n_kv, size_t head_dim, size_t seq, size_t slices) {
+             if (n_kv == 0 || head_dim % 32 != 0 || head_dim == 0 || (size_t)q.size() != n_heads * head_dim || (size_t)kq.size() % (n_kv * head_dim) != 0 ||
+                 kq.size() != vq.size() || kd.size() != vd.size() || kd.size() * 32 != kq.size())
+               throw Error(ErrorKind::BadInput, "debug_flash_attention_q8: array sizes");
+             const size_t seq_cap = (size_t)kq.size() / (n_kv * head_dim);
+             py::array_t<float> out(n_heads * head_dim), out2(n_heads * head_dim);
+             d.check(crabml_hip_debug_flash_attention_q8(d.raw(), q.data(), kq.data(), kd.data(), vq.data(), vd.data(), n_heads, n_kv, head_dim, seq,
+                                                         seq_cap, slices, out.mutable_data(), out2.mutable_data()));
+             return py::make_tuple(out, out2);
+           })
+      .def("debug_flash_attention_rows_q8",
+           [](HipTensorDevice& d, py::array_t<float, py::array::c_style | py::array::forcecast> q,
+              py::array_t<int8_t, py::array::c_style | py::array::forcecast> kq, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> kd,
+              py::array_t<int8_t, py::array::c_style | py::array::forcecast> vq, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> vd,
+              size_t n_heads, size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t slices) {
+             if (n_kv == 0 || head_dim % 32 != 0 || head_dim == 0 || (size_t)q.size() != rows * n_heads * head_dim ||
+                 (size_t)kq.size() % (n_kv * head_dim) != 0 || kq.size() != vq.size() || kd.size() != vd.size() || kd.size() * 32 != kq.size())
+               throw Error(ErrorKind::BadInput, "debug_flash_attention_rows_q8: array sizes");
+             const size_t seq_cap = (size_t)kq.size() / (n_kv * head_dim);
+             py::array_t<float> out(rows * n_heads * head_dim);
+             d.check(crabml_hip_debug_flash_attention_rows_q8(d.raw(), q.data(), kq.data(), kd.data(), vq.data(), vd.data(), n_heads, n_kv, head_dim,
+                                                              pos0, rows, seq_cap, slices, out.mutable_data()));
+             return out;
+           })
       .def("debug_flash_rows_slices",
            [](HipTensorDevice& d, size_t n_heads, size_t n_kv, size_t rows, size_t pos0) {
              return crabml_hip_debug_flash_rows_slices(d.raw(), n_heads, n_kv, rows, pos0);
@@ -487,7 +516,7 @@ PYBIND11_MODULE(_host, m) {
 
   py::class_<HipLlamaRunner>(m, "HipLlamaRunner")
       .def(py::init([](const LlamaConfig& conf, std::shared_ptr<Weights> w, std::shared_ptr<HipTensorDevice> dev,
-                       size_t seq_len, bool use_f16_kv_cache, bool use_graph, bool prefetch, int tp_size, int tp_rank,
+                       size_t seq_len, int use_f16_kv_cache, bool use_graph, bool prefetch, int tp_size, int tp_rank,
                        std::shared_ptr<TpComm> comm, bool norm_epilogue, int extra_flags, size_t attn_long_from,
                        size_t prefill_chunk, int create_entry) {
              auto* r = new HipLlamaRunner(conf, std::move(w), std::move(dev), seq_len, use_f16_kv_cache, use_graph, prefetch,
@@ -572,6 +601,15 @@ PYBIND11_MODULE(_host, m) {
         std::vector<uint8_t> b = r.debug_kv(layer, v, f16);
         return py::array_t<uint8_t>(b.size(), b.data());
       })
+      // crabml_hip_llama_debug_kv_q8_read: (kq, kd, vq, vd) of positions pos0 .. pos0 + rows, [n_kv][rows][head_dim] int8 / [.. / 32] f16 bits
+      .def("debug_kv_q8_read", [](HipLlamaRunner& r, size_t layer, size_t pos0, size_t rows) {
+        const size_t n = r.conf().n_kv_heads * rows * r.conf().head_size();
+        py::array_t<int8_t> kq(n), vq(n);
+        py::array_t<uint16_t> kd(n / 32), vd(n / 32);
+        r.device()->check(crabml_hip_llama_debug_kv_q8_read(r.raw(), layer, pos0, rows, kq.mutable_data(), kd.mutable_data(), vq.mutable_data(),
+                                                            vd.mutable_data()));
+        return py::make_tuple(kq, kd, vq, vd);
+      })
       // one eager step with `layer` tapped (crabml_hip_llama_debug_tap); the dictionary: tap_dict
       .def("debug_tap", [](HipLlamaRunner& r, size_t token, size_t pos, size_t layer) {
         static const char* names[CRABML_HIP_TAP_FIELDS] = {"qkv_in.x", "qkv_in.act_dim", "qkv_in.rsums", "qkv.qbuf", "attn.attn", "attn.act_attn", "wo.x",
@@ -610,7 +648,7 @@ PYBIND11_MODULE(_host, m) {
   // what the context HipLlamaRunner(conf, weights, device, ...) would create runs (crabml_hip_debug_step_plan; the record-only device too)
   m.def(
       "debug_step_plan",
-      [](const LlamaConfig& conf, std::shared_ptr<Weights> w, std::shared_ptr<HipTensorDevice> dev, size_t seq_len, bool use_f16_kv_cache,
+      [](const LlamaConfig& conf, std::shared_ptr<Weights> w, std::shared_ptr<HipTensorDevice> dev, size_t seq_len, int use_f16_kv_cache,
          bool use_graph, bool prefetch, int tp_size, int tp_rank, bool norm_epilogue, int extra_flags, size_t attn_long_from) {
         static const char* names[CRABML_HIP_STEPPLAN_WORDS] = {
             "path", "ordered", "norm_epi", "norm_epi_k", "defer_norm", "gu_rows", "q8k_producers", "k_norm_in", "attn_long_ok", "exact_long_ok",

@@ -241,6 +241,7 @@ typedef struct crabml_hip_llama crabml_hip_llama_t;
                                           inboxes (rank order; the later index wins a tie across shards as it does inside one).
                                           Logits copied out by forward(): this rank's shard at its global offsets, -inf elsewhere
                                           (an element-wise max over the ranks' buffers is the all-gather) */
+#define CRABML_HIP_KV_CACHE_Q8 2 /* crabml_hip_llama_config_t::use_f16_kv_cache */
 typedef struct crabml_hip_llama_config { /* crabml-llama2/src/model.rs:30-53 */
   size_t embedding_dim, hidden_dim, n_layers, n_heads, n_kv_heads, vocab_size;
   size_t seq_len;  /* KV cache capacity (Llama2Runner::new seq_len, llama2.rs:46-86).  Any context with (seq_len + head_dim) * 4
@@ -248,7 +249,11 @@ typedef struct crabml_hip_llama_config { /* crabml-llama2/src/model.rs:30-53 */
                     * serve the whole cache (the fused-step block above), else CRABML_HIP_NOT_IMPLEMENTED */
   size_t rope_dim; /* conf.rope_dim.unwrap_or(head_dim) */
   float rms_norm_eps;
-  int32_t use_f16_kv_cache;
+  int32_t use_f16_kv_cache; /* the kind of KV cache: 0 = f32, 1 = f16, 2 (CRABML_HIP_KV_CACHE_Q8) = 8-bit -- per 32 elements of a
+                             * head's K or V row, int8 values and one f16 scale (d = f16(max|x| / 127), q = x / d rounded to nearest):
+                             * 0.53 of the f16 cache's bytes, read by the fast step's flash attention kernels alone.  2 is served
+                             * on the fast device, on one GPU, for the context's own cache, head_dim 64 / 128 and GQA groups 1 .. 8,
+                             * else CRABML_HIP_NOT_IMPLEMENTED (an external cache: BAD_INPUT); any other value: BAD_INPUT */
   int32_t flags;
   /* tensor parallelism: this context holds rank tp_rank of tp_size shards -- wq/wk/wv split by
    * heads and ffn_gate/ffn_up by rows (column-parallel), wo/ffn_down split along k (row-parallel); the two

@@ -98,6 +98,16 @@ int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float*
  * before the first launch, so a partial the merge reads and the first launch did not write shows as NaN in out.  Blocks. */
 int crabml_hip_debug_flash_attention_rows_split(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
                                                 size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, size_t slices, float* out);
+/* The same three kernels in their Q8-cache form (use_f16_kv_cache == 2; k_attn_flash / k_attn_flash_rows / k_attn_flash_rows_split with
+ * KV8): kq, vq [n_kv][seq_cap][head_dim] int8 and kd, vd [n_kv][seq_cap][head_dim / 32] f16 bits, one scale per 32 elements, laid out
+ * on the device as a context lays its planes out.  head_dim 64 / 128, n_heads / n_kv from 1 to 8.  Everything else as the f16 hooks
+ * above; the rows hook runs the one-launch kernel at slices <= 1 and the split form with its merge above that. */
+int crabml_hip_debug_flash_attention_q8(crabml_hip_device_t* dev, const float* q, const int8_t* kq, const uint16_t* kd, const int8_t* vq,
+                                        const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap,
+                                        size_t slices, float* out, float* out2);
+int crabml_hip_debug_flash_attention_rows_q8(crabml_hip_device_t* dev, const float* q, const int8_t* kq, const uint16_t* kd, const int8_t* vq,
+                                             const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t pos0, size_t rows,
+                                             size_t seq_cap, size_t slices, float* out);
 /* The slice count the prompt pass picks on this device for a pass of `rows` rows at pos0 that runs the flash-rows family (n_heads /
  * n_kv: the context's local head counts): 1 = k_attn_flash_rows as one launch, more = the split-KV form with that many slices.  Returns
  * the count itself (>= 1), 0 for a null device; no device work. */
@@ -175,19 +185,24 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
 
 /* parity hook: copies the layer's K or V cache (raw f16/f32 bytes, [n_kv_heads][seq_len][head_dim]) */
 int crabml_hip_llama_debug_kv(crabml_hip_llama_t* ctx, size_t layer, int32_t which_v, void* dst, size_t nbytes);
+/* A Q8 context's cache planes of one layer, positions pos0 .. pos0 + rows of every local kv head: kq, vq [n_kv][rows][head_dim] int8,
+ * kd, vd [n_kv][rows][head_dim / 32] f16 bits.  Host pointers; blocks.  Another kind of cache: BAD_INPUT. */
+int crabml_hip_llama_debug_kv_q8_read(crabml_hip_llama_t* ctx, size_t layer, size_t pos0, size_t rows, int8_t* kq, uint16_t* kd, int8_t* vq,
+                                      uint16_t* vd);
 
 /* test hook: fills what no launch may consume, on the context's stream (stream-ordered with the steps and passes around it; does
  * not block).  The invariant it serves: no launch's result depends on cache rows past the live positions or on
  * scratch bytes it did not write in the same step or pass.  fill16 goes to f16 data and, repeated, to the quantized activation
  * planes (their scale fields then read as the pattern); fill32 to f32 data.  A buffer is filled as the whole allocation behind it.
- *   what & 1, the cache tail: rows kv_len .. seq_len - 1 of every layer and kv head, K and V (f16 cache: fill16, f32 cache: fill32).
+ *   what & 1, the cache tail: rows kv_len .. seq_len - 1 of every layer and kv head, K and V (f16 cache: fill16, f32 cache: fill32; Q8 cache:
+ *     fill16 over both planes, the int8 values and the f16 scales).
  *   what & 2, the step's data scratch -- every buffer a step writes before it reads it:
  *     fill32: x (k_embed writes it first), partial (unused on one device), qbuf, attn, h, tmp, xn, logits, rsums, scores_g,
  *             flash_part (the merge reads the active slices' partials only), am_val (all ARGMAX_BLOCKS written by k_argmax_partial),
- *             out_tokens (read by the host only, the entries of the call's own steps);
+ *             out_tokens (read by the host only, the entries of the call's own steps), kv_stage (Q8 cache: the token's K | V row);
  *     fill16: act_dim, act_attn, act_hid (every plane of a set is written by its producer), p16.
  *   what & 4, the prompt pass's row buffers, if allocated (otherwise nothing):
- *     fill32: pf_x, pf_xn, pf_q, pf_k, pf_v, pf_qr, pf_attn, pf_tmp, pf_g, pf_u, pf_split, pf_scores;
+ *     fill32: pf_x, pf_xn, pf_q, pf_k, pf_v, pf_qr, pf_attn, pf_tmp, pf_g, pf_u, pf_split, pf_scores, pf_flash_part, pf_kv_stage (Q8 cache);
  *     fill16: pf_act_dim, pf_act_hid, pf_xh, pf_xh2 (B': rows past the pass feed output rows nobody reads), pf_p16.
  * Never written, in any mode:
  *   state, slots, a8gran, h8gran, flash_tick, pf_ovf, the sampler's histogram, the inboxes of a P2P group: words that kernels poll or

@@ -27,6 +27,8 @@ ap.add_argument("--prompt", default="1,365,400,282,7,9,11,13")
 ap.add_argument("--steps", type=int, default=32)
 ap.add_argument("--seq-len", type=int, default=0)
 ap.add_argument("--f32-kv", action="store_true")
+ap.add_argument("--kv", default=None, choices=["f32", "f16", "q8"], help="the KV cache: f16 (default), f32 (= --f32-kv), or q8 -- int8 values "
+                "and one f16 scale per 32 elements, 0.53 of the f16 cache's bytes (fast device, head_dim 64 / 128)")
 ap.add_argument("--strict", action="store_true", help="strict-order device: the reference's scalar summation order, bit for bit")
 ap.add_argument("--temperature", type=float, default=0.0, help="0 (default): greedy; the CLI's default is 1.0")
 ap.add_argument("--topp", type=float, default=0.9)
@@ -62,7 +64,8 @@ dev.sync()
 print(f"loaded + uploaded in {time.perf_counter() - t0:.2f} s")
 prompt = [int(t) for t in a.prompt.split(",") if t]
 seq_len = a.seq_len or min(conf.seq_len, len(prompt) + a.steps + 8)
-r = ca.HipLlamaRunner(conf, weights, dev, seq_len, not a.f32_kv, extra_flags=536870912 if a.q5k_gemm else 0)
+kv = {"f32": 0, "f16": 1, "q8": 2}[a.kv] if a.kv else (0 if a.f32_kv else 1)  # crabml_hip_llama_config_t::use_f16_kv_cache
+r = ca.HipLlamaRunner(conf, weights, dev, seq_len, kv, extra_flags=536870912 if a.q5k_gemm else 0)
 t0 = time.perf_counter()
 logits = r.prefill(prompt)
 t_prefill = time.perf_counter() - t0

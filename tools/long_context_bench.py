@@ -15,6 +15,8 @@ Synthetic weights, f16 KV cache, one process.  Per SHAPE:FORMAT, markdown rows:
   baseline  Llama2Runner<HipTensor> on a per-op device (one launch per Tensor call) at --seq-len, token by token from position 0 to
             --baseline-to: tok/s in a 64-token window at each --at position, and over the whole loop (the prompt rate of that path);
             --baseline-mode lazy --tree DIR: the recorded-op queue of the build in DIR (the parent commit: its fallback for such a context)
+  kvq8      (not in the default sections) the Q8 KV cache against the f16 one: two contexts alternating run by run -- context bytes,
+            decode tok/s at each --at position (median of 3), five 32-row passes from --kvq8-pass-at (median)
 --tree DIR: import crabml_amd from another checkout (a build of the parent commit) -- with --seq-len 16256 --sections decode the
 A/B of the unchanged kernels at 4096 and 16000 positions."""
 import argparse
@@ -101,6 +103,50 @@ def memory(ca, dev, conf, w, model, seq):
     return m0, m1, m2, kv
 
 
+def kv_q8_ab(ca, dev, conf, w, seq, at, pass_at):
+    """the Q8 KV cache (use_f16_kv_cache = 2) against the f16 cache, two contexts of one process alternating run by run:
+    -> (context bytes {kind: mem_in_use difference}, {pos: {kind: median decode tok/s of 3 runs}}, {kind: median seconds of five 32-row
+    passes from pass_at}).  Both caches are filled once, front to back; a run is min(64, (seq - pos) / 3) decode steps, its three
+    repetitions at consecutive positions -- at the cache's end the three runs END at seq."""
+    runners, mem = {}, {}
+    for kind in (1, 2):
+        dev.sync()
+        m0 = dev.mem_in_use()
+        runners[kind] = ca.HipLlamaRunner(conf, w, dev, seq, kind)
+        mem[kind] = dev.mem_in_use() - m0
+    prompt = [(11 * i + 5) % conf.vocab_size for i in range(seq)]
+    filled = 0
+
+    def fill_to(pos):
+        nonlocal filled
+        for lo in range(filled, pos, 2048):
+            for r in runners.values():
+                r.prefill(prompt[lo:min(lo + 2048, pos)])
+        filled = pos
+
+    rates, passes = {}, {1: [], 2: []}
+    for pos in sorted(set(at) | {pass_at}):
+        if pos == pass_at and pos + 6 * 32 <= seq:
+            fill_to(pos - 32)
+            fill_to(pos)  # warm: a 32-row pass's buffers and kernels
+            for i in range(5):
+                for kind, r in runners.items():
+                    dev.sync()
+                    passes[kind].append(timed(lambda: r.prefill(prompt[pos + 32 * i:pos + 32 * (i + 1)])))
+            filled = pos + 160
+        if pos not in at:
+            continue
+        n = min(64, (seq - pos) // 3)
+        fill_to(max(filled, min(pos, seq - 3 * n)))
+        rates[pos] = {1: [], 2: []}
+        for _ in range(3):
+            for kind, r in runners.items():
+                dev.sync()
+                rates[pos][kind].append(n / timed(lambda: r.decode_greedy(1, n)))
+            filled += n
+    return mem, {p: {k: statistics.median(v) for k, v in d.items()} for p, d in rates.items()}, {k: statistics.median(v) for k, v in passes.items() if v}
+
+
 def baseline(ca, synth, model, seq, at, upto, budget, mode):
     """the per-op runner's token loop from position 0: -> ({pos: tok/s over the 64 tokens from pos}, tok/s of the whole loop, its length);
     budget > 0: the loop ends after that many seconds, the windows it did not reach are left out"""
@@ -138,6 +184,7 @@ def main():
     ap.add_argument("--at", default="4096,16000,24576,32760")
     ap.add_argument("--short-ends", type=lambda v: [int(x) for x in v.split(",")], default=[128, 512, 1024, 2048, 4096, 8192, 30000],
                     help="the position at which the first of a short leg's five passes ends")
+    ap.add_argument("--kvq8-pass-at", type=int, default=30000, help="section kvq8: where its five 32-row passes start")
     ap.add_argument("--baseline-to", type=int, default=32768)
     ap.add_argument("--baseline-budget", type=float, default=0.0, help="seconds after which the per-op token loop ends (0: never)")
     ap.add_argument("--baseline-mode", default="per-op", choices=["per-op", "lazy"],
@@ -173,6 +220,13 @@ def main():
                     print(head + " %d-row pass ending at %d | one launch: %s | default (%d slices): %s | one launch / default %.2f |"
                           % (rows, end, ms(off), dev.debug_flash_rows_slices(s.n_heads, s.n_kv_heads, rows, end - rows), ms(on),
                              statistics.median(off) / statistics.median(on)), flush=True)
+        if "kvq8" in sections:
+            mem, d, p = kv_q8_ab(ca, dev, conf, w, seq, at, a.kvq8_pass_at)
+            print(head + " context | f16 cache +%.3f GiB | Q8 cache +%.3f GiB |" % (mem[1] / 2**30, mem[2] / 2**30), flush=True)
+            print(head + " decode tok/s, f16 / Q8 cache | " + " | ".join("@%d %.1f / %.1f (x%.3f)" % (q, d[q][1], d[q][2], d[q][2] / d[q][1]) for q in sorted(d)) + " |",
+                  flush=True)
+            if p:
+                print(head + " 32-row pass at %d, f16 / Q8 cache | %.3f ms / %.3f ms |" % (a.kvq8_pass_at, p[1] * 1e3, p[2] * 1e3), flush=True)
         del w, dev
         gc.collect()
         if "baseline" in sections:
