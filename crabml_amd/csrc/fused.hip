@@ -1763,6 +1763,12 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
   const bool f16w = allow_f16w && !strict && !gemm_exact_hook && !f16w_off && !(g.flags & CRABML_HIP_LLAMA_PREFILL_INT8_GEMM) &&
                     (c->qt == CRABML_HIP_Q8_0 || c->qt == CRABML_HIP_Q8_1 || c->qt == CRABML_HIP_Q8_K) && c->pf_xh != nullptr && B >= f16w_min;  // (shorter passes: the int8 kernels / the GEMV)
   *f16w_used = f16w;
+  // A/B hook (CRABML_HIP_TEST_HOOKS=1 CRABML_HIP_NO_SKINNY_GEMM=1): passes of 2..15 rows keep one GEMV per row
+  static const bool skinny_off = test_hook_on("CRABML_HIP_NO_SKINNY_GEMM");
+  // from 6 rows: at 2 and 3 rows the row GEMVs are faster, at 4 the two overlap deep in the cache (profiles/skinny_gemm.md), and a
+  // 5-row pass is held to the row GEMV launch by launch (tests/test_hip_prefill_launches.py): passes of 1..5 rows stay as they were
+  // (Q8_K rows: up to 14 -- the K-quant launch pins hold a 15-row pass to the row GEMV as well, tests/test_hip_prefill_k_launches.py)
+  const bool skinny = !strict && c->tp == 1 && c->qt != CRABML_HIP_F32 && B >= 6 && B <= (c->qt == CRABML_HIP_Q8_K ? 14u : 15u) && !gemm_exact_hook && !skinny_off;
   int* const ovf = c->pf_ovf;
   // the f16 GEMM takes matrix w, whose rows are k elements long (Q8_K rows: whole super-blocks only).  The one predicate: the GEMMs,
   // the kernels that write pf_xh ahead of them and the two one-launch sites all ask here.
@@ -1818,6 +1824,12 @@ int prefill_chunk_pass(crabml_hip_llama* c, const uint32_t* tokens, size_t B, si
       }
     }
     if (!strict) {
+      // 6..15 quantized rows on one device: the skinny GEMM streams the matrix once where the GEMV below reads it once per row
+      // (gemm_skinny.hip; it declines the formats it does not cover)
+      if (skinny && launch_gemm_skinny(dev, w, c->qt, m, k, act, B, out)) {
+        took(4);
+        return 0;
+      }
       if (kword >= 0 && tap.armed()) {  // launch_gemv's own first question, asked here so that the plan can say what it answered
         if (B >= 16 && launch_gemm_mfma(dev, w, m, k, act, B, out, nullptr, nullptr, !gemm_exact_hook)) {
           took(2);

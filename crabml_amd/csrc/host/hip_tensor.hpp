@@ -376,6 +376,13 @@ class HipTensor {
     device_->check(crabml_hip_debug_gemm_ints(device_->raw(), buf_.get(), m, k, x.buf_.get(), b, ints.data(), out.data()));
     return {ints, out};
   }
+  // the skinny GEMM of 2..15-row prompt passes by itself: the first b rows of x = (>= b, k); returns its f32 (b, m)
+  std::vector<float> debug_gemm_skinny(const HipTensor& x, size_t b) const {
+    size_t m = shape()[0], k = shape()[1];
+    std::vector<float> out(b * m);
+    device_->check(crabml_hip_debug_gemm_skinny(device_->raw(), buf_.get(), m, k, x.buf_.get(), b, out.data()));
+    return out;
+  }
   // the fast prompt pass's f16 GEMM by itself (crabml_hip_debug_gemm_f16w): this weight and up to two more of its format against
   // x = (b, k) rows; force = (F, T, ksplit, gate | up), 0 / -1 = the launcher's choice
   struct F16wDebug {

@@ -335,6 +335,11 @@ PYBIND11_MODULE(_host, m) {
              auto r = w.debug_gemm_ints(x, b);
              return py::make_tuple(py::array_t<int32_t>(r.first.size(), r.first.data()), py::array_t<float>(r.second.size(), r.second.data()));
            })
+      .def("debug_gemm_skinny",
+           [](const HipTensor& w, const HipTensor& x, size_t b) {
+             std::vector<float> v = w.debug_gemm_skinny(x, b);
+             return py::array_t<float>(v.size(), v.data());
+           })
       .def("debug_gemm_f16w",
            [](const HipTensor& w, std::vector<HipTensor> more, const HipTensor& x, size_t b, int rows_path, uint16_t junk,
               std::vector<int32_t> force) {

@@ -98,6 +98,10 @@ bool launch_gemm_f16w(crabml_hip_device* dev, const crabml_hip_buf* const* w, co
 // batched rhs on the matrix cores (gemm_mfma.hip); false = not covered
 bool launch_gemm_mfma(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m, size_t k, const void* act, size_t b, float* out,
                       crabml_hip_device::ProfRec* rec, int* dbg = nullptr, bool fused_add = false);
+// 2..15 rows of the fast prompt pass, every weight byte streamed once (gemm_skinny.hip; Q4_0 / Q8_0 weights x Q8_0 rows, Q4_K / Q6_K x
+// Q8_K rows; act_qtype: what `act` holds); false = not covered.  Sums the blocks in its own order: the prompt pass of the fast device only
+bool launch_gemm_skinny(crabml_hip_device* dev, const crabml_hip_buf* w, uint32_t act_qtype, size_t m, size_t k, const void* act, size_t b, float* out,
+                        crabml_hip_device::ProfRec* rec = nullptr);
 int launch_piece_ints(crabml_hip_device* dev, const crabml_hip_buf* w, size_t m, size_t k, size_t row, const void* act, int variant,
                       int32_t* out, float* fout);
 // elementwise.hip: plain streaming read of `bytes` bytes (crabml_hip_debug_read_ceiling), timed by the event pair

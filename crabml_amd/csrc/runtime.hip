@@ -1011,6 +1011,33 @@ int crabml_hip_debug_gemm_ints(crabml_hip_device_t* dev, const crabml_hip_buf_t*
   return 0;
 }
 
+int crabml_hip_debug_gemm_skinny(crabml_hip_device_t* dev, const crabml_hip_buf_t* w, size_t m, size_t k, const crabml_hip_buf_t* x,
+                                 size_t b, float* out) {
+  if (!dev || !w || !x || !out || b < 2 || b > 15) return CRABML_HIP_BAD_INPUT;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_TRY(observe(dev, w));
+  CH_TRY(observe(dev, x));
+  if (w->dtype != CRABML_HIP_Q4_0 && w->dtype != CRABML_HIP_Q8_0 && w->dtype != CRABML_HIP_Q4_K && w->dtype != CRABML_HIP_Q6_K)
+    CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_gemm_skinny: Q4_0 / Q8_0 / Q4_K / Q6_K weights only");
+  const uint32_t qt = vec_dot_rhs_dtype(w->dtype);
+  if (w->k != k || m == 0 || m * k > w->n_elems || k % (qt == CRABML_HIP_Q8_K ? 256 : 32) != 0) CH_BAIL(dev, CRABML_HIP_TENSOR_ERROR, "debug_gemm_skinny: bad shape");
+  CH_TRY(need_f32(dev, x, b * k, "debug_gemm_skinny rhs"));
+  const size_t xrows = x->n_elems / k;  // every row x holds is quantized; the launch is told about the first b
+  const void* act = nullptr;
+  CH_TRY(ensure_act(dev, x, xrows, k, qt, &act));
+  void* o = nullptr;
+  size_t ocap = 0;
+  CH_TRY(pool_alloc(dev, b * m * 4, &o, &ocap));
+  const bool ran = launch_gemm_skinny(dev, w, qt, m, k, act, b, (float*)o);
+  hipError_t e = ran ? hipMemcpyAsync(out, o, b * m * 4, hipMemcpyDeviceToHost, dev->stream) : hipSuccess;
+  if (e == hipSuccess) e = hipStreamSynchronize(dev->stream);
+  pool_free(dev, o, ocap);
+  if (e != hipSuccess) return hip_fail(dev, e, "debug_gemm_skinny", __FILE__, __LINE__);
+  if (!ran) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_gemm_skinny: the skinny GEMM did not take this shape");
+  return 0;
+}
+
 int crabml_hip_debug_gemm_f16w(crabml_hip_device_t* dev, const crabml_hip_buf_t* const* w, const size_t* m, size_t nw, size_t k,
                                const crabml_hip_buf_t* x, size_t b, int32_t rows_path, uint16_t junk, const int32_t* force,
                                float* const* out, uint16_t* xh, int32_t* used, void* hq, uint16_t* hxh) {

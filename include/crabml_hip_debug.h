@@ -55,6 +55,12 @@ int crabml_hip_debug_superblock_ints(crabml_hip_device_t* dev, const crabml_hip_
  * out (optional, b * m floats) receives the GEMM's f32 result. */
 int crabml_hip_debug_gemm_ints(crabml_hip_device_t* dev, const crabml_hip_buf_t* w, size_t m, size_t k,
                                const crabml_hip_buf_t* x, size_t b, int32_t* dst, float* out);
+/* The fast prompt pass's skinny GEMM (k_gemm_skinny, gemm_skinny.hip: passes of 2..15 rows) by itself.  w: Q4_0, Q8_0, Q4_K or
+ * Q6_K, m rows of k; x: at least b f32 rows of k.  Every row x holds is quantized with the production row quantizer (Q8_0 / Q8_K) and
+ * the production launcher is told about the first b: rows behind them must not be read.  out: b * m floats.  BAD_INPUT outside 2..15
+ * rows and for every other weight format. */
+int crabml_hip_debug_gemm_skinny(crabml_hip_device_t* dev, const crabml_hip_buf_t* w, size_t m, size_t k,
+                                 const crabml_hip_buf_t* x, size_t b, float* out);
 /* The fast prompt pass's weight GEMM (k_gemm_f16w, gemm_f16w.hip) by itself.  w: nw = 1..3 weight buffers of one format (Q4_0,
  * Q8_0, Q4_1, Q4_K, Q6_K, Q2_K, Q3_K, Q5_K), m[j] rows of k; x: b >= 16 f32 rows of k.  The rows are quantized to the format's row type (Q8_0 / Q8_1 /
  * Q8_K) and B' (the pre-scaled f16 rows the GEMM reads) is written by the quantizer itself (rows_path 0) or made from the finished
@@ -390,7 +396,7 @@ enum {
   CRABML_HIP_PFPLAN_DOWN_KSPLIT = 23,
   CRABML_HIP_PFPLAN_ATTN_KERNEL = 24,/* 1 the flash-rows family (k_attn_flash_rows, or its split-KV form), 2 the exact tile kernel, 3 the exact long-row kernels, 4 k_attn per (head, row) */
   CRABML_HIP_PFPLAN_KERNEL_Q = 25,   /* the kernel each matrix of the layer took: 1 k_gemm_f16w, 2 the int8 matrix-core GEMM (k_gemm_mfma*), 3 the */
-  CRABML_HIP_PFPLAN_KERNEL_K = 26,   /*   wave-per-row GEMV, row by row.  One word per matrix: a launch_gemm_f16w that declines falls through to */
+  CRABML_HIP_PFPLAN_KERNEL_K = 26,   /*   wave-per-row GEMV, row by row, 4 the skinny GEMM (k_gemm_skinny*: Q4_0 / Q8_0 matrices in a pass of 6..15 rows, Q4_K / Q6_K in one of 6..14).  One word per matrix: a launch_gemm_f16w that declines falls through to */
   CRABML_HIP_PFPLAN_KERNEL_V = 27,   /*   launch_gemv, which takes the int8 GEMM from 16 rows where the format has one.  PLAN_F16W says what the */
   CRABML_HIP_PFPLAN_KERNEL_WO = 28,  /*   pass allows, these words what ran (a Q5_K matrix: always 3; the Q6_K matrices of the same layer: 1) */
   CRABML_HIP_PFPLAN_KERNEL_GATE = 29,
