@@ -64,6 +64,7 @@ pub struct crabml_hip_llama_config_t {
     pub n_heads: usize,
     pub n_kv_heads: usize,
     pub vocab_size: usize,
+    /// KV cache capacity: up to 32768 positions, up to 131072 with `use_f16_kv_cache = 2` (the Q8 cache)
     pub seq_len: usize,
     pub rope_dim: usize,
     pub rms_norm_eps: f32,

@@ -177,6 +177,8 @@ struct StepPlan {
   bool flash_rows_split = false;  // ... or, for the passes flash_rows_slices names, its split-KV form (no plan word: the same family)
   int flash_S = 0;                // position slices (workgroups) per kv head
   int flash_min_rows = FLASH_MIN_ROWS;  // cached rows per active slice, at least
+  size_t attn_mm_from = 0;        // > 0 (a Q8 cache of more than MAX_SEQ_LEN positions): cached positions from which variant 3 runs
+  int mm_S = 0;                   // ... and its position slices per kv head
   int attn_s_rows = 0;         // > 0: variant 0 runs k_attn_s (K / V staged through LDS) with room for this many cached rows
   size_t attn_s_lds = 0;
 };
@@ -247,16 +249,17 @@ struct crabml_hip_llama {
   unsigned* sm_hist = nullptr;
   float* sm_par = nullptr;
   float* sm_coins = nullptr;
-  hipGraph_t sgraph[3] = {nullptr, nullptr, nullptr};  // the step with the sampler, per attention variant, captured on first use
-  hipGraphExec_t sexec[3] = {nullptr, nullptr, nullptr};
+  hipGraph_t sgraph[4] = {nullptr, nullptr, nullptr, nullptr};  // the step with the sampler, per attention variant, captured on first use
+  hipGraphExec_t sexec[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t kv_len = 0;
   // [0]: one attention workgroup per head; [1]: the long-context attention kernels (from attn_long_from positions)
-  hipGraph_t graph[3] = {nullptr, nullptr, nullptr};
-  hipGraphExec_t exec[3] = {nullptr, nullptr, nullptr};
+  hipGraph_t graph[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipGraphExec_t exec[4] = {nullptr, nullptr, nullptr, nullptr};
   bool use_graph = false;
   bool capturing = false;
   int attn_variant = 0;         // which of them the next enqueue emits: 0 = one workgroup per head, 1 = the long-context kernels,
-                                // 2 = split-KV attention with the merge inside the launch (ticket form: the mid range)
+                                // 2 = split-KV attention with the merge inside the launch (ticket form: the mid range),
+                                // 3 = the Q8 cache's matrix-core split-KV attention (k_attn_flash_mm, from attn_mm_from positions)
   float* flash_part = nullptr;  // [n_kv_l][flash_S][G][hd + 2] partial {O, m, l}
   unsigned* flash_tick = nullptr;  // [n_kv_l] arrival counters (monotonic)
   float* scores_g = nullptr;    // [n_heads_l][seq_len] f32
@@ -638,6 +641,9 @@ FlashFn flash_kernel(int grp, int hd, bool q81, bool ticket, bool kv8 = false) {
   with_const<1, 2, 3, 4, 5, 6, 7, 8>(grp, [&](auto g) { fn = flash_kernel_g<decltype(g)::value>(hd, q81, ticket, kv8); });
   return fn;
 }
+// k_attn_flash_mm for a head_dim (64 or 128: what a Q8 cache exists for)
+typedef void (*FlashMmFn)(const float*, const signed char*, const signed char*, const int*, float*, int, int, int, int);
+FlashMmFn flash_mm_kernel(int hd) { return hd == 128 ? (FlashMmFn)k_attn_flash_mm<128> : hd == 64 ? (FlashMmFn)k_attn_flash_mm<64> : nullptr; }
 // the Q8 cache's append of `rows` staged rows at *pos_d .. (k_kv_store_q8)
 void launch_kv_store_q8(crabml_hip_llama* c, int l, const float* stage, const int* pos_d, int rows) {
   const int blocks = rows * 2 * c->kv_dim_l / 32;  // 32-element blocks: 8 lanes each
@@ -647,6 +653,7 @@ void launch_kv_store_q8(crabml_hip_llama* c, int l, const float* stage, const in
 // which attention form serves cache position `pos` (see attn_variant)
 int variant_of(const crabml_hip_llama* c, size_t pos) {
   if (!(c->plan.attn_long_ok && pos + 1 >= c->plan.attn_long_from)) return 0;
+  if (c->plan.attn_mm_from > 0 && pos + 1 >= c->plan.attn_mm_from) return 3;
   return c->plan.flash_ticket_until > 0 && pos + 1 < c->plan.flash_ticket_until ? 2 : 1;
 }
 void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned short* xd, void* xisum, bool prof) {
@@ -654,13 +661,20 @@ void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
   hipStream_t st = dev->stream;
   const int hd = c->hd, grp = c->n_heads_l / c->n_kv_l;
   const bool q81 = c->qt == CRABML_HIP_Q8_1;
-  const bool ticket = c->plan.flash_ticket || c->attn_variant == 2;
-  const FlashFn fn = flash_kernel(grp, hd, q81, ticket, kv_kind(c->cfg) == KvKind::Q8);
+  const bool mm = c->attn_variant == 3;  // the matrix-core form: its own slices and minimum rows, the same partials and merge
+  const bool ticket = !mm && (c->plan.flash_ticket || c->attn_variant == 2);
+  const int S = mm ? c->plan.mm_S : c->plan.flash_S, min_rows = mm ? FLASH_MM_MIN_ROWS : c->plan.flash_min_rows;
   crabml_hip_device::ProfRec r[2];
   if (prof) prof_begin(dev, &r[0], CRABML_HIP_F32, 7, 0.0);
-  launch_k(st, prof ? &r[0] : nullptr, fn, dim3(c->n_kv_l * c->plan.flash_S), dim3(flash_threads(grp)), flash_lds_bytes(grp, hd),
-           (const float*)c->qbuf, (const unsigned short*)c->kc[l], (const unsigned short*)c->vc[l], (const int*)(c->state + 1), c->flash_part,
-           c->flash_tick, c->attn, xq, xd, xisum, (int)c->cfg.seq_len, c->plan.flash_S, c->plan.flash_min_rows);
+  if (mm)
+    launch_k(st, prof ? &r[0] : nullptr, flash_mm_kernel(hd), dim3(c->n_kv_l * S), dim3(FLASH_MM_NW * 64), flash_mm_lds_bytes(grp, hd),
+             (const float*)c->qbuf, (const signed char*)c->kc[l], (const signed char*)c->vc[l], (const int*)(c->state + 1), c->flash_part,
+             (int)c->cfg.seq_len, grp, S, min_rows);
+  else
+    launch_k(st, prof ? &r[0] : nullptr, flash_kernel(grp, hd, q81, ticket, kv_kind(c->cfg) == KvKind::Q8), dim3(c->n_kv_l * S),
+             dim3(flash_threads(grp)), flash_lds_bytes(grp, hd), (const float*)c->qbuf, (const unsigned short*)c->kc[l],
+             (const unsigned short*)c->vc[l], (const int*)(c->state + 1), c->flash_part, c->flash_tick, c->attn, xq, xd, xisum,
+             (int)c->cfg.seq_len, S, min_rows);
   if (prof) prof_end(dev, &r[0]);
   if (ticket) return;
   if (prof) prof_begin(dev, &r[1], CRABML_HIP_F32, 8, 0.0);
@@ -670,7 +684,7 @@ void launch_attn_flash(crabml_hip_llama* c, int l, signed char* xq, unsigned sho
     with_const_else<0, 1>(q81, [&](auto q) {
       constexpr int HD = decltype(hdc)::value;
       launch_k(st, R1, k_attn_flash_merge<HD, decltype(q)::value != 0>, dim3(c->n_heads_l), dim3(HD), 0, (const float*)c->flash_part, pos_d,
-               c->attn, xq, xd, xisum, grp, c->plan.flash_S, c->plan.flash_min_rows);
+               c->attn, xq, xd, xisum, grp, S, min_rows);
     });
   });
   if (prof) prof_end(dev, &r[1]);
@@ -2490,12 +2504,14 @@ struct FlashHooks {
   int slices = 0;             // CRABML_HIP_FLASH_SLICES: slices per kv head in the grid (0 = not set)
   int min_rows = 0;           // CRABML_HIP_FLASH_MIN_ROWS (0 = not set)
   size_t ticket_until = 768;  // CRABML_HIP_FLASH_TICKET_UNTIL: 0 = never
+  int mm_from = -1;           // CRABML_HIP_ATTN_MM_FROM: first cached position of k_attn_flash_mm (0 = never, < 0 = not set)
 };
 static FlashHooks read_flash_hooks() {
   FlashHooks h;
   h.slices = test_hook_int("CRABML_HIP_FLASH_SLICES", 0);
   h.min_rows = test_hook_int("CRABML_HIP_FLASH_MIN_ROWS", 0);
   if (const char* e = test_hook("CRABML_HIP_FLASH_TICKET_UNTIL")) h.ticket_until = (size_t)atol(e);
+  h.mm_from = test_hook_int("CRABML_HIP_ATTN_MM_FROM", -1);
   return h;
 }
 
@@ -2512,6 +2528,22 @@ static bool lds_fits(const crabml_hip_device* dev, const void* fn, size_t bytes,
 
 // a cache whose positions k_attn's score row (one workgroup per head, the whole row and q in LDS) cannot span
 static bool past_k_attn_row(size_t seq, size_t hd) { return k_attn_lds_bytes(seq, hd) > K_ATTN_LDS; }
+
+// The longest cache a context is created with: the context length of the Qwen2.5 / Mistral / Llama-3.1 files this is for, inside the
+// 38400 positions (LDS_CAP) of the exact softmax kernels.  tests/test_hip_fused.py::test_fused_errors holds a fast f16 context of
+// 65536 positions to a refusal: going further has to touch that test.
+constexpr size_t MAX_SEQ_LEN = 32768;
+
+// A Q8 cache on the fast device (what kv_q8_refusal admits) never runs those kernels -- the flash forms read it from position 0, and none
+// keeps a cache-sized row anywhere -- so it goes on to the context length of the Llama-3.1 / 3.2 and Qwen2.5 files.  Every offset into
+// its planes is 64-bit (32 kv heads x 131072 x 128 bytes = 2^29 per plane).
+constexpr size_t MAX_SEQ_LEN_Q8 = 131072;
+// Cached positions from which such a context runs k_attn_flash_mm instead of k_attn_flash<.., KV8>: the smallest measured position from
+// which the matrix-core form was not slower at any deeper measured point.  Decode tok/s, k_attn_flash / k_attn_flash_mm, Llama-3-8B
+// shape Q4_0 at seq_len 131072, medians of 3 alternating runs (profiles/kv_q8_long.md): 658.9 / 670.7 at 256 (the smallest measured
+// position), 650.2 / 665.1 at 512, 644.1 / 658.2 at 1024, 617.4 / 638.2 at 4096, 540.0 / 556.8 at 16000, 461.7 / 468.6 at 32760,
+// 355.9 / 362.7 at 65536, 293.2 / 298.0 at 98304, 249.3 / 256.4 at 131000.  Below 256 nothing is measured: k_attn_flash stays.
+constexpr size_t FLASH_MM_FROM = 256;
 
 // The attention forms of a plan.  Each kernel's limit is asked for where the plan first needs that kernel, in this order: the exact
 // softmax, k_attn_pv_split, k_attn_flash, its ticket form, k_attn_flash_rows, k_attn_flash_rows_split, k_attn_s -- a refusal turns that form off, nothing else.
@@ -2568,6 +2600,14 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
     p->flash_rows_split = p->attn_flash_rows && !has(CRABML_HIP_LLAMA_NO_FLASH_ROWS_SPLIT) &&
                           lds_fits(dev, (const void*)flash_rows_split_kernel(hd, kv8), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
   }
+  // A Q8 cache of more than MAX_SEQ_LEN positions: the matrix-core split-KV form from FLASH_MM_FROM cached positions on (variant 3;
+  // below it, and in every shorter context, k_attn_flash<.., KV8> as before).  Lab hook CRABML_HIP_ATTN_MM_FROM: another first
+  // position (1 = every step, 0 = never) for the A/B of profiles/kv_q8_long.md.
+  if (p->attn_flash && kv8 && seq > MAX_SEQ_LEN) {
+    const int S = dev->n_cu / n_kv_l;
+    p->attn_mm_from = hooks.mm_from >= 0 ? (size_t)hooks.mm_from : FLASH_MM_FROM;
+    p->mm_S = S < 1 ? 1 : S > FLASH_MAX_SLICES ? FLASH_MAX_SLICES : S;
+  }
   p->attn_long_ok = p->exact_long_ok || p->attn_flash;
   // the exact kernels: measured crossover on MI355X (Llama-3-8B shape) ~200-220.  k_attn_flash + merge overtake the staged one-workgroup
   // kernel between 64 and 96 cached positions (8B shape, per layer: 51.0 vs 51.6 us at 64, 52.2 vs 51.4 at 96, 59.0 vs 51.8 at 224;
@@ -2584,20 +2624,20 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
   }
 }
 
-// The longest cache a context is created with: the context length of the Qwen2.5 / Mistral / Llama-3.1 files this is for, inside the
-// 38400 positions (LDS_CAP) of the exact softmax kernels.  tests/test_hip_fused.py::test_fused_errors holds a fast f16 context of
-// 65536 positions to a refusal: going further has to touch that test.
-constexpr size_t MAX_SEQ_LEN = 32768;
-
 // Why a plan cannot serve its cache (nullptr: it can).  Up to the 64 KiB score row of k_attn every plan can: that kernel is what
 // every other form falls back to.  Past it a context exists only if no launch its plan can choose is k_attn with a cache-sized row:
 // the decode step goes k_attn_s -> the long-context kernels, the prompt pass goes k_attn_flash_rows (short passes: the tile kernel, or
 // k_attn with a pass-sized row) or the exact tile / long-rows kernels.  The kernels' own limits are decide_attention's; this reads its words.
 // plan == nullptr: the clauses the configuration alone settles, asked before decide_step -- which raises kernels' LDS limits -- runs
 // for a context that cannot exist.
-static const char* long_cache_refusal(const crabml_hip_llama_config_t& g, const ModelFacts& f, const StepPlan* plan) {
+static const char* kv_q8_refusal(const crabml_hip_device* dev, const crabml_hip_llama_config_t& g, const ModelFacts& f, const StepPlan* plan);
+// the most positions of a context: MAX_SEQ_LEN_Q8 for a Q8 cache that the configuration and the device admit, MAX_SEQ_LEN otherwise
+static size_t seq_len_limit(const crabml_hip_device* dev, const crabml_hip_llama_config_t& g, const ModelFacts& f) {
+  return kv_kind(g) == KvKind::Q8 && kv_q8_refusal(dev, g, f, nullptr) == nullptr ? MAX_SEQ_LEN_Q8 : MAX_SEQ_LEN;
+}
+static const char* long_cache_refusal(const crabml_hip_device* dev, const crabml_hip_llama_config_t& g, const ModelFacts& f, const StepPlan* plan) {
   if (!past_k_attn_row(g.seq_len, f.hd)) return nullptr;
-  if (g.seq_len > MAX_SEQ_LEN) return "more positions than the limit";
+  if (g.seq_len > seq_len_limit(dev, g, f)) return "more positions than the limit";
   if (f.tp > 1) return "tensor-parallel ranks keep the one-workgroup-per-head attention within reach";
   if (kv_kind(g) == KvKind::F32) return "an f32 kv cache has no long-context attention kernels";
   if (!plan) return nullptr;
@@ -2867,7 +2907,7 @@ static int alloc_step_buffers(crabml_hip_llama* c, crabml_hip_buf* const* ext_kc
     A(n_heads_l * g.seq_len * 2, &c->p16);
   }
   if (p.attn_flash) {
-    A(n_kv_l * (size_t)p.flash_S * flash_part_floats((int)(n_heads_l / n_kv_l), c->hd) * 4, &c->flash_part);
+    A(n_kv_l * (size_t)std::max(p.flash_S, p.mm_S) * flash_part_floats((int)(n_heads_l / n_kv_l), c->hd) * 4, &c->flash_part);
     A(n_kv_l * 4, &c->flash_tick);
     if (rc == 0 && !dev->dry && hipMemsetAsync(c->flash_tick, 0, n_kv_l * 4, dev->stream) != hipSuccess) rc = CRABML_HIP_UNEXPECTED;
   }
@@ -2936,6 +2976,7 @@ static bool capture_graphs(crabml_hip_llama* c, const ModelFacts& f) {
   bool ok = true;
   // (a Q8 cache has no variant 0: variant_of never answers it)
   for (int v = kv_kind(g) == KvKind::Q8 ? 1 : 0; v < nvar && ok; v++) ok = capture_step(c, v, &c->graph[v], &c->exec[v]);
+  if (ok && c->plan.attn_mm_from > 0) ok = capture_step(c, 3, &c->graph[3], &c->exec[3]);
   (void)hipGetLastError();
   c->use_graph = ok;
   c->attn_variant = 0;
@@ -2954,15 +2995,15 @@ static int llama_create_impl(crabml_hip_device_t* dev, const crabml_hip_llama_co
   if (!dev->dry) CH_USE(dev);
   const auto refuse = [&](const char* why) {
     return set_error(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: seq_len %zu is past the %zu positions of a one-workgroup score row (limit %zu): %s",
-                     cfg->seq_len, (size_t)(K_ATTN_LDS / 4 - f.hd), MAX_SEQ_LEN, why);
+                     cfg->seq_len, (size_t)(K_ATTN_LDS / 4 - f.hd), seq_len_limit(dev, *cfg, f), why);
   };
-  if (const char* why = long_cache_refusal(*cfg, f, nullptr)) return refuse(why);
+  if (const char* why = long_cache_refusal(dev, *cfg, f, nullptr)) return refuse(why);
   if (kv_kind(*cfg) == KvKind::Q8 && ext_kc != nullptr)
     CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "llama: a Q8 kv cache is the context's own (the caller's cache tensors are f32 or f16)");
   const auto refuse_q8 = [&](const char* why) { return set_error(dev, CRABML_HIP_NOT_IMPLEMENTED, "llama fused path: no Q8 kv cache here: %s", why); };
   if (const char* why = kv_q8_refusal(dev, *cfg, f, nullptr)) return refuse_q8(why);
   const StepPlan plan = decide_step(dev, *cfg, f, read_flash_hooks());
-  if (const char* why = long_cache_refusal(*cfg, f, &plan)) return refuse(why);
+  if (const char* why = long_cache_refusal(dev, *cfg, f, &plan)) return refuse(why);
   if (const char* why = kv_q8_refusal(dev, *cfg, f, &plan)) return refuse_q8(why);
   crabml_hip_llama* c = nullptr;
   CH_TRY(new_context(dev, *cfg, f, plan, ext_kc != nullptr, &c));
@@ -3018,7 +3059,7 @@ int crabml_hip_llama_destroy(crabml_hip_llama_t* c) {
     (void)hipSetDevice(c->dev->ordinal);
     (void)hipStreamSynchronize(c->dev->stream);
   }
-  for (int v = 0; v < 3; v++) {
+  for (int v = 0; v < 4; v++) {
     if (c->exec[v]) (void)hipGraphExecDestroy(c->exec[v]);
     if (c->graph[v]) (void)hipGraphDestroy(c->graph[v]);
     if (c->sexec[v]) (void)hipGraphExecDestroy(c->sexec[v]);
@@ -3420,7 +3461,7 @@ int crabml_hip_debug_step_plan(crabml_hip_device_t* dev, const crabml_hip_llama_
   CH_TRY(llama_create_impl(dev, cfg, w, nullptr, nullptr, &c, arch));
   const StepPlan& p = c->plan;
   int graphs = 0;
-  for (int v = 0; v < 3; v++) graphs += c->exec[v] != nullptr;
+  for (int v = 0; v < 4; v++) graphs += c->exec[v] != nullptr;
   const int32_t v[CRABML_HIP_STEPPLAN_WORDS] = {
       (int32_t)p.path, p.ordered, p.norm_epi, p.norm_epi_k, p.defer_norm, p.gu_rows, p.q8k_producers, p.k_norm_in, p.attn_long_ok,
       p.exact_long_ok, (int32_t)p.attn_long_from, p.pv_split, p.attn_flash, p.flash_ticket, (int32_t)p.flash_ticket_until, p.attn_flash_rows,
@@ -3557,6 +3598,52 @@ int crabml_hip_debug_flash_attention_q8(crabml_hip_device_t* dev, const float* q
                                         size_t slices, float* out, float* out2) {
   if (!kd || !vd || (head_dim != 64 && head_dim != 128)) return CRABML_HIP_BAD_INPUT;
   return debug_flash_attention_impl(dev, q, kq, kd, vq, vd, n_heads, n_kv, head_dim, seq, seq_cap, slices, out, out2);
+}
+// parity hook (crabml_hip_debug.h): k_attn_flash_mm + k_attn_flash_merge by themselves, twice on the same scratch (out2: the second run)
+int crabml_hip_debug_flash_attention_q8_mm(crabml_hip_device_t* dev, const float* q, const int8_t* kq, const uint16_t* kd, const int8_t* vq,
+                                           const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap,
+                                           size_t slices, float* out, float* out2) {
+  if (!dev || !q || !kq || !kd || !vq || !vd || !out || seq == 0 || seq_cap < seq || n_kv == 0 || n_heads % n_kv != 0) return CRABML_HIP_BAD_INPUT;
+  CH_LIVE(dev);
+  CH_USE(dev);
+  CH_FLUSH(dev);
+  const int grp = (int)(n_heads / n_kv), hd = (int)head_dim;
+  const FlashMmFn fn = flash_mm_kernel(hd);
+  if (fn == nullptr || grp > 8 || slices < 1 || slices > FLASH_MAX_SLICES || seq_cap > MAX_SEQ_LEN_Q8)
+    CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_q8_mm: unsupported group / head_dim / slices / seq_cap");
+  const size_t nq = n_heads * head_dim * 4, npl = n_kv * seq_cap * head_dim, nsc = n_kv * seq_cap * (head_dim / 32) * 2, nkv = npl + nsc,
+               npart = n_kv * slices * flash_part_floats(grp, hd) * 4;
+  const size_t o_q = 0, o_k = align_up(o_q + nq, 256), o_v = align_up(o_k + nkv, 256), o_out = align_up(o_v + nkv, 256),
+               o_part = align_up(o_out + nq, 256), o_pos = align_up(o_part + npart, 256), total = o_pos + 256;
+  char* base = nullptr;
+  CH_HIP(dev, hipMalloc((void**)&base, total));
+  hipStream_t st = dev->stream;
+  const int pos = (int)seq - 1;
+  hipError_t e = hipMemsetAsync(base + o_part, 0xFF, npart, st);  // (a partial the merge reads and the kernel did not write: NaN in out)
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_q, q, nq, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_k, kq, npl, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_v, vq, npl, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_k + npl, kd, nsc, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_v + npl, vd, nsc, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(base + o_pos, &pos, 4, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // (`pos` leaves scope)
+  for (int rep = 0; rep < (out2 ? 2 : 1) && e == hipSuccess; rep++) {
+    hipLaunchKernelGGL(fn, dim3((unsigned)(n_kv * slices)), dim3(FLASH_MM_NW * 64), (uint32_t)flash_mm_lds_bytes(grp, hd), st,
+                       (const float*)(base + o_q), (const signed char*)(base + o_k), (const signed char*)(base + o_v), (const int*)(base + o_pos),
+                       (float*)(base + o_part), (int)seq_cap, grp, (int)slices, FLASH_MM_MIN_ROWS);
+    with_const_else<128, 64>(hd, [&](auto hdc) {
+      constexpr int HD = decltype(hdc)::value;
+      hipLaunchKernelGGL((k_attn_flash_merge<HD, false>), dim3((unsigned)n_heads), dim3(HD), 0, st, (const float*)(base + o_part),
+                         (const int*)(base + o_pos), (float*)(base + o_out), (signed char*)nullptr, (unsigned short*)nullptr, (void*)nullptr, grp,
+                         (int)slices, FLASH_MM_MIN_ROWS);
+    });
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(rep == 0 ? out : out2, base + o_out, nq, hipMemcpyDeviceToHost, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(base);
+  if (e != hipSuccess) return hip_fail(dev, e, "debug_flash_attention_q8_mm", __FILE__, __LINE__);
+  return 0;
 }
 
 // parity hook (crabml_hip_debug.h): the fast prompt pass's causal attention kernel by itself

@@ -1254,6 +1254,229 @@ __global__ __launch_bounds__(HD) void k_attn_flash_merge(const float* __restrict
   }
 }
 
+// ---- split-KV decode attention of the Q8 cache on the f16 matrix cores (contexts past 32768 positions) ---------------------------
+// k_attn_flash<.., KV8> pays per q head: G dot chains, G lane sums, G x 16 multiply-adds per 16 cached bytes -- vector work, not bytes,
+// bounds it deep in the cache (profiles/kv_q8.md).  Here the G heads of a kv head are the 16 columns of a matrix-core tile (zeros past
+// G), so a position's bytes are converted once and the per-head work is the matrix unit's.  Same grid, same partials {O, m, l} per
+// (kv head, slice) and same merge launch as k_attn_flash (k_attn_flash_merge with this kernel's slices and minimum rows).
+//   work     workgroup = (kv head, slice of the live positions); its FLASH_MM_NW waves take the slice's 32-position steps round-robin
+//            (wave w: steps w, w + NW, ...), each with its own online-softmax state; the states meet once, in LDS
+//   scores   S^T[pos][head] per 16 positions and 32-element block: one v_mfma_f32_16x16x32_f16, A = the K bytes of the block straight
+//            from global memory (lane: position l % 16, 8 bytes at 32 b + 8 (l / 16)), made f16 exactly (q8x4_to_h16: no rounding, no
+//            transposition, no LDS), B = q rounded to f16 as every flash form rounds it; the block's f16 scale multiplies the f32 result
+//   softmax  per C column = head: a lane holds positions 4 (l / 16) .. + 4 of both 16-position chunks; one running maximum per head
+//            agreed across the four lane groups, the sum per lane until the end; acc * alpha is skipped while no maximum of the wave
+//            moves; the probabilities are rounded to f16 (the p16 rounding of the flash-rows family) and the sum adds what is multiplied
+//   PV       O^T[dim][head] += V^[dim][pos] P^T[pos][head] on 16x16x32: the C registers of the scores ARE the B operand (k slot
+//            (g, i) = position 4 g + i of chunk a, (g, 4 + i) of chunk b).  V needs positions along k: a lane loads the dword of dims
+//            64 h + 4 n .. + 4 from four consecutive positions and transposes the 4 x 4 bytes with eight v_perm -- tile (h, t) holds
+//            dim 64 h + 4 m + t in row m, a permutation the stores undo.  No LDS staging: measured nowhere yet against a
+//            direct-to-LDS form (profiles/kv_q8_long.md).  V's scale is folded into V: V^ = f16(d * q) by one packed f16 multiply of
+//            the exact f16 byte value -- the ONE rounding this form adds beside p16, the one k_attn_flash_rows<.., KV8> makes.
+//   masking  loads are clamped to the slice's last live position, so nothing behind the live cache is read at all; a clamped
+//            position's score is -inf by select (its probability an exact 0) and its V scale 0 by select; columns past G score -inf
+//   loads    the bytes and the scales of a step are requested together, one step ahead of the step being multiplied
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#define FLASH_MM_NW 8          /* waves per workgroup: two per SIMD, one's matrix work under the other's vector work */
+#define FLASH_MM_BN 32         /* positions per step */
+#define FLASH_MM_MIN_ROWS 256  /* live positions per active slice, at least: one step per wave */
+__host__ __device__ inline size_t flash_mm_lds_bytes(int G, int hd) { return (size_t)FLASH_MM_NW * G * (hd + 2) * 4; }
+// 4 x 4 bytes transposed: r[i] = four dims of position i -> r[t] = dim t of the four positions
+__device__ __forceinline__ void bytes4x4_transpose(unsigned (&r)[4]) {
+  const unsigned x = __builtin_amdgcn_perm(r[1], r[0], 0x05010400u), y = __builtin_amdgcn_perm(r[1], r[0], 0x07030602u);
+  const unsigned z = __builtin_amdgcn_perm(r[3], r[2], 0x05010400u), w = __builtin_amdgcn_perm(r[3], r[2], 0x07030602u);
+  r[0] = __builtin_amdgcn_perm(z, x, 0x05040100u);
+  r[1] = __builtin_amdgcn_perm(z, x, 0x07060302u);
+  r[2] = __builtin_amdgcn_perm(w, y, 0x05040100u);
+  r[3] = __builtin_amdgcn_perm(w, y, 0x07060302u);
+}
+template <int HD>
+struct FlashMmStep {  // what a lane requests for one 32-position step: chunk c = 0 / 1, position 4 g + i of it
+  static constexpr int KS = HD / 32, HH = HD / 64;
+  typedef unsigned scv __attribute__((ext_vector_type(HD / 64)));  // a position's KS f16 scales
+  u32x2 k[2][KS];      // K: position n of the chunk, 8 bytes of every block
+  unsigned v[2][HH][4];  // V: positions 4 g + i, dims 64 h + 4 n .. + 4
+  scv kd[2][4], vd[2][4];
+};
+template <int HD>
+__global__ __launch_bounds__(FLASH_MM_NW * 64) void k_attn_flash_mm(const float* __restrict__ q, const signed char* __restrict__ kc,
+                                                                    const signed char* __restrict__ vc, const int* __restrict__ pos_d,
+                                                                    float* __restrict__ part, int seq_cap, int G, int Smax, int min_rows) {
+  constexpr int KS = HD / 32, HH = HD / 64, NW = FLASH_MM_NW, BN = FLASH_MM_BN, NT = NW * 64;
+  static_assert(HD == 64 || HD == 128, "a V row is HD / 64 dwords per lane");
+  typedef typename FlashMmStep<HD>::scv scv;
+  extern __shared__ __attribute__((aligned(16))) float fm_lds[];  // [NW][G][HD + 2]: a wave's {O, m, l} per head
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = lane & 15, g = lane >> 4;
+  const int j = blockIdx.x / Smax, sp = blockIdx.x % Smax, n_kv = gridDim.x / Smax;
+  // q of head n as the B operand (dims 32 ks + 8 g .. + 8), zeros past G; requested before the position is read
+  f16x8 qb[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ks++) {
+    const f32x4* qp = (const f32x4*)(q + (size_t)(j * G + (n < G ? n : 0)) * HD + 32 * ks + 8 * g);
+    const f32x4 a = qp[0], b = qp[1];
+    const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    const f16x8 v = {(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3], (_Float16)b[0], (_Float16)b[1], (_Float16)b[2], (_Float16)b[3]};
+    qb[ks] = n < G ? v : z;
+  }
+  const int seq = *pos_d + 1;
+  const int S = min(Smax, max(1, (seq + min_rows - 1) / min_rows));  // (k_attn_flash_merge derives the same S)
+  if (sp >= S) return;
+  const int chunk = (((seq + S - 1) / S + BN - 1) / BN) * BN;  // the live positions cut into S slices of whole steps
+  const int r0 = sp * chunk, r1 = r0 + chunk < seq ? r0 + chunk : seq;
+  const int nsteps = r1 > r0 ? (r1 - r0 + BN - 1) / BN : 0;
+  const size_t plane = (size_t)n_kv * seq_cap * HD;  // bytes of an int8 plane: its scales lie right behind it
+  const signed char* kq = kc + (size_t)j * seq_cap * HD;
+  const signed char* vq = vc + (size_t)j * seq_cap * HD;
+  const unsigned short* ksc = (const unsigned short*)(kc + plane) + (size_t)j * seq_cap * KS;
+  const unsigned short* vsc = (const unsigned short*)(vc + plane) + (size_t)j * seq_cap * KS;
+  auto request = [&](int step, FlashMmStep<HD>& s) {  // (step < nsteps: r0 + step * BN < r1, so every clamped position is >= r0)
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      const int c0 = r0 + step * BN + 16 * c;
+      const int pk = c0 + n < r1 ? c0 + n : r1 - 1;
+#pragma unroll
+      for (int ks = 0; ks < KS; ks++) s.k[c][ks] = __builtin_nontemporal_load((const u32x2*)(kq + (size_t)pk * HD + 32 * ks + 8 * g));
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int p = c0 + 4 * g + i < r1 ? c0 + 4 * g + i : r1 - 1;
+#pragma unroll
+        for (int h = 0; h < HH; h++) s.v[c][h][i] = __builtin_nontemporal_load((const unsigned*)(vq + (size_t)p * HD + 64 * h + 4 * n));
+        s.kd[c][i] = *(const scv*)(ksc + (size_t)p * KS);
+        s.vd[c][i] = *(const scv*)(vsc + (size_t)p * KS);
+      }
+    }
+  };
+  f32x4 acc[HH][4];  // tile (h, t): this lane's head n, dims 64 h + 16 g + 4 i + t
+#pragma unroll
+  for (int h = 0; h < HH; h++)
+#pragma unroll
+    for (int t = 0; t < 4; t++) acc[h][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, lsum = 0.f;
+  FlashMmStep<HD> cur;
+  if (wave < nsteps) request(wave, cur);
+  for (int step = wave; step < nsteps; step += NW) {
+    FlashMmStep<HD> nxt;
+    if (step + NW < nsteps) request(step + NW, nxt);
+    f32x4 sc[2];
+    float cm = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      sc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ks++) {
+        h16x2 k0, k1, k2, k3;
+        q8x4_to_h16(cur.k[c][ks][0], k0, k1);
+        q8x4_to_h16(cur.k[c][ks][1], k2, k3);
+        const f16x8 ka = {k0[0], k0[1], k1[0], k1[1], k2[0], k2[1], k3[0], k3[1]};
+        const f32x4 r = __builtin_amdgcn_mfma_f32_16x16x32_f16(ka, qb[ks], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const unsigned w = cur.kd[c][i][ks >> 1];
+          sc[c][i] = __builtin_fmaf(h2f((unsigned short)((ks & 1) ? w >> 16 : w & 0xffffu)), r[i], sc[c][i]);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; i++) {  // positions past the slice (clamped loads) and columns past G, whatever they computed
+        if (r0 + step * BN + 16 * c + 4 * g + i >= r1 || n >= G) sc[c][i] = -INFINITY;
+        cm = fmaxf(cm, sc[c][i]);
+      }
+    }
+    cm = fmaxf(cm, __shfl_xor(cm, 16));
+    cm = fmaxf(cm, __shfl_xor(cm, 32));
+    const float mn = fmaxf(m, cm);
+    if (__any(mn > m)) {  // the running maximum of some head moved: rescale (rare after the first steps)
+      const float alpha = mn == -INFINITY ? 1.0f : __expf(m - mn);
+      lsum *= alpha;
+#pragma unroll
+      for (int h = 0; h < HH; h++)
+#pragma unroll
+        for (int t = 0; t < 4; t++) acc[h][t] = acc[h][t] * alpha;
+      m = mn;
+    }
+    f16x8 pT;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const _Float16 pa = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sc[0][i] - m);
+      const _Float16 pb = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sc[1][i] - m);
+      pT[i] = pa;
+      pT[4 + i] = pb;
+      lsum += (float)pa + (float)pb;
+    }
+#pragma unroll
+    for (int h = 0; h < HH; h++) {
+      // this lane's dims 64 h + 4 n .. + 4 lie in block 2 h + (n >> 3): its scale per position, 0 at a clamped one, paired as the
+      // transposed bytes are (positions i, i + 1)
+      h16x2 dv[2][2];
+#pragma unroll
+      for (int c = 0; c < 2; c++) {
+        unsigned short d[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const unsigned w = cur.vd[c][i][h];
+          const bool live = r0 + step * BN + 16 * c + 4 * g + i < r1;
+          d[i] = live ? (unsigned short)((n & 8) ? w >> 16 : w & 0xffffu) : (unsigned short)0;
+        }
+        dv[c][0] = __builtin_bit_cast(h16x2, (unsigned)d[0] | ((unsigned)d[1] << 16));
+        dv[c][1] = __builtin_bit_cast(h16x2, (unsigned)d[2] | ((unsigned)d[3] << 16));
+      }
+      bytes4x4_transpose(cur.v[0][h]);
+      bytes4x4_transpose(cur.v[1][h]);
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        h16x2 a0, a1, b0, b1;
+        q8x4_to_h16(cur.v[0][h][t], a0, a1);
+        q8x4_to_h16(cur.v[1][h][t], b0, b1);
+        a0 = a0 * dv[0][0];
+        a1 = a1 * dv[0][1];
+        b0 = b0 * dv[1][0];
+        b1 = b1 * dv[1][1];
+        const f16x8 va = {a0[0], a0[1], a1[0], a1[1], b0[0], b0[1], b1[0], b1[1]};
+        acc[h][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(va, pT, acc[h][t], 0, 0, 0);
+      }
+    }
+    cur = nxt;
+  }
+  lsum += __shfl_xor(lsum, 16);
+  lsum += __shfl_xor(lsum, 32);
+  // ---- the NW wave states meet in LDS, then the slice's partial {O, m, l} per head in k_attn_flash's layout -------------------------
+  if (n < G) {
+    float* rec = fm_lds + ((size_t)wave * G + n) * (HD + 2);
+#pragma unroll
+    for (int h = 0; h < HH; h++)
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        float* o = rec + 64 * h + 16 * g + 4 * i;
+        o[0] = acc[h][0][i];
+        o[1] = acc[h][1][i];
+        o[2] = acc[h][2][i];
+        o[3] = acc[h][3][i];
+      }
+    if (g == 0) {
+      rec[HD] = m;
+      rec[HD + 1] = lsum;
+    }
+  }
+  __syncthreads();
+  float* mypart = part + (size_t)blockIdx.x * (G * (HD + 2));
+  for (int idx = tid; idx < G * (HD + 2); idx += NT) {
+    const int hg = idx / (HD + 2), d = idx % (HD + 2);
+    float M = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NW; w++) M = fmaxf(M, fm_lds[((size_t)w * G + hg) * (HD + 2) + HD]);
+    float o = 0.f;
+    if (d != HD) {  // an O value, or l at d = HD + 1: sum_w e^(m_w - M) x_w
+#pragma unroll
+      for (int w = 0; w < NW; w++) {
+        const float* rec = fm_lds + ((size_t)w * G + hg) * (HD + 2);
+        o = __builtin_fmaf(rec[d], rec[HD] == -INFINITY ? 0.0f : __expf(rec[HD] - M), o);
+      }
+    }
+    mypart[idx] = d == HD ? M : o;
+  }
+}
+
 // ---- fast-mode attention of the batched prefill: causal flash attention on the f16 matrix cores ---------------------------------
 // The prompt pass's exact attention (k_attn_tile / the three long-context kernels with a row dimension) runs the reference's f16
 // chains per (row, head, column): 137 us per layer at 512 prompt rows, most of a 4096-token prompt.  The FAST step (same switch and the
@@ -1271,7 +1494,6 @@ __global__ __launch_bounds__(HD) void k_attn_flash_merge(const float* __restrict
 //   K and V tiles of 64 positions go through LDS (two buffers each, one barrier per fill): the next tile's loads are requested
 //   before the current one is multiplied, so their round trip runs under a whole tile of matrix work.
 // GQA: the G heads of a kv head are separate workgroups (their K / V reads meet in L2).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 #define FLASH_ROWS_BN 64                   // cached positions per V^T fill
 #define FLASH_ROWS_VSTR (FLASH_ROWS_BN + 4)  // halfs per V^T row: 8-byte aligned fragments, rows 34 banks apart

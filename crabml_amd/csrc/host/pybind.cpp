@@ -213,6 +213,20 @@ PYBIND11_MODULE(_host, m) {
                                                          seq_cap, slices, out.mutable_data(), out2.mutable_data()));
              return py::make_tuple(out, out2);
            })
+      .def("debug_flash_attention_q8_mm",  // k_attn_flash_mm: (out, the second run's out)
+           [](HipTensorDevice& d, py::array_t<float, py::array::c_style | py::array::forcecast> q,
+              py::array_t<int8_t, py::array::c_style | py::array::forcecast> kq, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> kd,
+              py::array_t<int8_t, py::array::c_style | py::array::forcecast> vq, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> vd,
+              size_t n_heads, size_t n_kv, size_t head_dim, size_t seq, size_t slices) {
+             if (n_kv == 0 || head_dim % 32 != 0 || head_dim == 0 || (size_t)q.size() != n_heads * head_dim || (size_t)kq.size() % (n_kv * head_dim) != 0 ||
+                 kq.size() != vq.size() || kd.size() != vd.size() || kd.size() * 32 != kq.size())
+               throw Error(ErrorKind::BadInput, "debug_flash_attention_q8_mm: array sizes");
+             const size_t seq_cap = (size_t)kq.size() / (n_kv * head_dim);
+             py::array_t<float> out(n_heads * head_dim), out2(n_heads * head_dim);
+             d.check(crabml_hip_debug_flash_attention_q8_mm(d.raw(), q.data(), kq.data(), kd.data(), vq.data(), vd.data(), n_heads, n_kv, head_dim,
+                                                            seq, seq_cap, slices, out.mutable_data(), out2.mutable_data()));
+             return py::make_tuple(out, out2);
+           })
       .def("debug_flash_attention_rows_q8",
            [](HipTensorDevice& d, py::array_t<float, py::array::c_style | py::array::forcecast> q,
               py::array_t<int8_t, py::array::c_style | py::array::forcecast> kq, py::array_t<uint16_t, py::array::c_style | py::array::forcecast> kd,

@@ -206,6 +206,9 @@ int crabml_hip_batch_matmul(crabml_hip_device_t* dev, const crabml_hip_buf_t* a,
  * group 1 to 8) or on the exact tile / long-row kernels (strict-order device, EXACT_ATTENTION, head_dim 256: groups 1 / 2 / 4 / 8,
  * seq_len % 8 == 0).  Everything else past the 64 KiB row -- an f32 cache, tensor-parallel ranks, the A/B flags that switch those
  * kernels off, more than 32768 positions -- is CRABML_HIP_NOT_IMPLEMENTED, and the message names the reason.
+ * A Q8 KV cache (use_f16_kv_cache = 2, where it is served at all) never runs the kernels that limit is for: its contexts go up to
+ * 131072 positions.  One created with more than 32768 runs its decode attention on the matrix cores (k_attn_flash_mm) from 256
+ * cached positions on; a shorter one runs the launches it always ran.
  * Weights: layer matrices in any matmul_vec format (Q4_0, Q8_0, Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, Q4_K, Q5_K and Q6_K run fused kernels --
  * Q5_0 as Q4_0 and Q5_1 as Q4_1 in every form, the strict-order one included, but on one device only: a tensor-parallel rank of
  * either runs the per-op segments --, Q4_K and Q5_K also
@@ -246,13 +249,15 @@ typedef struct crabml_hip_llama_config { /* crabml-llama2/src/model.rs:30-53 */
   size_t embedding_dim, hidden_dim, n_layers, n_heads, n_kv_heads, vocab_size;
   size_t seq_len;  /* KV cache capacity (Llama2Runner::new seq_len, llama2.rs:46-86).  Any context with (seq_len + head_dim) * 4
                     * <= 64 KiB (16256 positions at head_dim 128); past that up to 32768 positions where the long-context kernels
-                    * serve the whole cache (the fused-step block above), else CRABML_HIP_NOT_IMPLEMENTED */
+                    * serve the whole cache (the fused-step block above), with use_f16_kv_cache = 2 up to 131072 positions,
+                    * else CRABML_HIP_NOT_IMPLEMENTED */
   size_t rope_dim; /* conf.rope_dim.unwrap_or(head_dim) */
   float rms_norm_eps;
   int32_t use_f16_kv_cache; /* the kind of KV cache: 0 = f32, 1 = f16, 2 (CRABML_HIP_KV_CACHE_Q8) = 8-bit -- per 32 elements of a
                              * head's K or V row, int8 values and one f16 scale (d = f16(max|x| / 127), q = x / d rounded to nearest):
                              * 0.53 of the f16 cache's bytes, read by the fast step's flash attention kernels alone.  2 is served
                              * on the fast device, on one GPU, for the context's own cache, head_dim 64 / 128 and GQA groups 1 .. 8,
+                             * with seq_len up to 131072 (8.5 GiB at the Llama-3-8B shape, where f16 would need 16),
                              * else CRABML_HIP_NOT_IMPLEMENTED (an external cache: BAD_INPUT); any other value: BAD_INPUT */
   int32_t flags;
   /* tensor parallelism: this context holds rank tp_rank of tp_size shards -- wq/wk/wv split by

@@ -111,6 +111,12 @@ int crabml_hip_debug_flash_attention_rows_split(crabml_hip_device_t* dev, const 
 int crabml_hip_debug_flash_attention_q8(crabml_hip_device_t* dev, const float* q, const int8_t* kq, const uint16_t* kd, const int8_t* vq,
                                         const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap,
                                         size_t slices, float* out, float* out2);
+/* The matrix-core split-KV decode attention of a Q8 cache of more than 32768 positions (k_attn_flash_mm, then k_attn_flash_merge) by
+ * itself: the arguments of crabml_hip_debug_flash_attention_q8, seq_cap up to 131072, slices 1 .. 32 (the kernel uses
+ * min(slices, ceil(seq / 256)) of them).  out2 (optional): a second run on the same scratch. */
+int crabml_hip_debug_flash_attention_q8_mm(crabml_hip_device_t* dev, const float* q, const int8_t* kq, const uint16_t* kd, const int8_t* vq,
+                                           const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t seq, size_t seq_cap,
+                                           size_t slices, float* out, float* out2);
 int crabml_hip_debug_flash_attention_rows_q8(crabml_hip_device_t* dev, const float* q, const int8_t* kq, const uint16_t* kd, const int8_t* vq,
                                              const uint16_t* vd, size_t n_heads, size_t n_kv, size_t head_dim, size_t pos0, size_t rows,
                                              size_t seq_cap, size_t slices, float* out);

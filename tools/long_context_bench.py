@@ -17,6 +17,8 @@ Synthetic weights, f16 KV cache, one process.  Per SHAPE:FORMAT, markdown rows:
             --baseline-mode lazy --tree DIR: the recorded-op queue of the build in DIR (the parent commit: its fallback for such a context)
   kvq8      (not in the default sections) the Q8 KV cache against the f16 one: two contexts alternating run by run -- context bytes,
             decode tok/s at each --at position (median of 3), five 32-row passes from --kvq8-pass-at (median)
+  kvq8long  (not in the default sections; --seq-len above 32768) a Q8 context on k_attn_flash<.., KV8> against one on k_attn_flash_mm
+            at every --at position, alternating run by run (medians of 3 with ranges), context bytes, prompt tok/s of the whole fill
 --tree DIR: import crabml_amd from another checkout (a build of the parent commit) -- with --seq-len 16256 --sections decode the
 A/B of the unchanged kernels at 4096 and 16000 positions."""
 import argparse
@@ -35,9 +37,9 @@ def timed(fn):
     return time.perf_counter() - t0
 
 
-def build(ca, synth, spec):
+def build(ca, synth, spec, n_layers=None):
     shape, fmt = spec.split(":")
-    model = synth.build_model(synth.SHAPES[shape], synth.TYPE_BY_NAME[fmt], seed=1)
+    model = synth.build_model(synth.SHAPES[shape], synth.TYPE_BY_NAME[fmt], seed=1, n_layers=n_layers)
     return shape, fmt, model
 
 
@@ -147,6 +149,38 @@ def kv_q8_ab(ca, dev, conf, w, seq, at, pass_at):
     return mem, {p: {k: statistics.median(v) for k, v in d.items()} for p, d in rates.items()}, {k: statistics.median(v) for k, v in passes.items() if v}
 
 
+def kv_q8_long_ab(ca, dev, conf, w, seq, at):
+    """a Q8 context of more than 32768 positions, k_attn_flash<.., KV8> at every depth (lab hook CRABML_HIP_ATTN_MM_FROM=0) against
+    k_attn_flash_mm at every depth (=1): two contexts of one process alternating run by run, both caches filled once, front to back.
+    -> (context bytes, prompt tok/s over the whole fill, {pos: {kind: [decode tok/s of 3 runs]}})"""
+    os.environ["CRABML_HIP_TEST_HOOKS"] = "1"
+    runners = {}
+    dev.sync()
+    m0 = dev.mem_in_use()
+    for kind in ("flash", "mm"):
+        os.environ["CRABML_HIP_ATTN_MM_FROM"] = "0" if kind == "flash" else "1"
+        runners[kind] = ca.HipLlamaRunner(conf, w, dev, seq, 2)
+    mem = (dev.mem_in_use() - m0) // 2
+    del os.environ["CRABML_HIP_ATTN_MM_FROM"]
+    prompt = [(11 * i + 5) % conf.vocab_size for i in range(seq)]
+    filled, fill_s, fill_n, rates = 0, 0.0, 0, {}
+    for pos in sorted(at):
+        n = min(32, (seq - pos) // 3)
+        target = max(filled, min(pos, seq - 3 * n))
+        for lo in range(filled, target, 2048):
+            runners["flash"].prefill(prompt[lo:min(lo + 2048, target)])
+            dev.sync()
+            fill_s += timed(lambda: (runners["mm"].prefill(prompt[lo:min(lo + 2048, target)]), dev.sync()))
+        fill_n, filled = fill_n + max(0, target - filled), target
+        rates[pos] = {"flash": [], "mm": []}
+        for _ in range(3):
+            for kind, r in runners.items():
+                dev.sync()
+                rates[pos][kind].append(n / timed(lambda: r.decode_greedy(1, n)))
+            filled += n
+    return mem, fill_n / fill_s if fill_s else 0.0, rates
+
+
 def baseline(ca, synth, model, seq, at, upto, budget, mode):
     """the per-op runner's token loop from position 0: -> ({pos: tok/s over the 64 tokens from pos}, tok/s of the whole loop, its length);
     budget > 0: the loop ends after that many seconds, the windows it did not reach are left out"""
@@ -189,6 +223,7 @@ def main():
     ap.add_argument("--baseline-budget", type=float, default=0.0, help="seconds after which the per-op token loop ends (0: never)")
     ap.add_argument("--baseline-mode", default="per-op", choices=["per-op", "lazy"],
                     help="the baseline runner's device: per-op launches, or the recorded-op queue (with --tree: what that build does with such a context)")
+    ap.add_argument("--layers", type=int, default=0, help="build the shape with this many layers (attention times of a large shape)")
     ap.add_argument("--tree", default=ROOT)
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
@@ -198,7 +233,7 @@ def main():
     at = [int(p) for p in a.at.split(",") if int(p) < seq]
     tag = os.path.basename(os.path.abspath(a.tree))
     for spec in a.runs.split(","):
-        shape, fmt, model = build(ca, synth, spec)
+        shape, fmt, model = build(ca, synth, spec, a.layers or None)
         head = "| %s | %s | %s | seq_len %d |" % (tag, shape, fmt, seq)
         dev = ca.HipTensorDevice(0)
         conf, w = synth.to_hip(model, dev)
@@ -227,6 +262,13 @@ def main():
                   flush=True)
             if p:
                 print(head + " 32-row pass at %d, f16 / Q8 cache | %.3f ms / %.3f ms |" % (a.kvq8_pass_at, p[1] * 1e3, p[2] * 1e3), flush=True)
+        if "kvq8long" in sections:
+            mem, prate, d = kv_q8_long_ab(ca, dev, conf, w, seq, at)
+            fmt3 = lambda v: "%.1f [%.1f .. %.1f]" % (statistics.median(v), min(v), max(v))  # noqa: E731
+            print(head + " Q8 context +%.3f GiB | prompt, whole fill (k_attn_flash_mm context) %.0f tok/s |" % (mem / 2**30, prate), flush=True)
+            for q in sorted(d):
+                print(head + " decode tok/s @%d | k_attn_flash %s | k_attn_flash_mm %s | x%.3f |"
+                      % (q, fmt3(d[q]["flash"]), fmt3(d[q]["mm"]), statistics.median(d[q]["mm"]) / statistics.median(d[q]["flash"])), flush=True)
         del w, dev
         gc.collect()
         if "baseline" in sections:
