@@ -173,7 +173,7 @@ struct StepPlan {
   bool attn_flash = false;     // variant 1 of the FAST step: k_attn_flash (split-KV, f32 accumulation) instead of the three exact kernels
   bool flash_ticket = false;   // A/B: the merge by the last-arriving workgroup inside k_attn_flash instead of its own launch
   size_t flash_ticket_until = 0;  // > 0: positions [attn_long_from, this) run variant 2
-  bool attn_flash_rows = false;   // the batched prefill's attention runs k_attn_flash_rows (fast step, f16 cache, head_dim 64 / 128)
+  bool attn_flash_rows = false;   // the batched prefill's attention runs k_attn_flash_rows (fast step, head_dim 64 / 128; 256: f16 cache, opt-in)
   bool flash_rows_split = false;  // ... or, for the passes flash_rows_slices names, its split-KV form (no plan word: the same family)
   int flash_S = 0;                // position slices (workgroups) per kv head
   int flash_min_rows = FLASH_MIN_ROWS;  // cached rows per active slice, at least
@@ -437,12 +437,12 @@ AttnSFn attn_s_kernel(int hd) { return hd == 128 ? k_attn_s<128> : k_attn_s<0>; 
 typedef decltype(&k_attn_flash_rows<64>) FlashRowsFn;
 FlashRowsFn flash_rows_kernel(int hd, bool kv8 = false) {
   if (kv8) return hd == 128 ? k_attn_flash_rows<128, true> : hd == 64 ? k_attn_flash_rows<64, true> : nullptr;
-  return hd == 128 ? k_attn_flash_rows<128> : hd == 64 ? k_attn_flash_rows<64> : nullptr;
+  return hd == 256 ? k_attn_flash_rows_w<256> : hd == 128 ? k_attn_flash_rows<128> : hd == 64 ? k_attn_flash_rows<64> : nullptr;
 }
 typedef decltype(&k_attn_flash_rows_split<64>) FlashRowsSplitFn;
 FlashRowsSplitFn flash_rows_split_kernel(int hd, bool kv8 = false) {
   if (kv8) return hd == 128 ? k_attn_flash_rows_split<128, true> : hd == 64 ? k_attn_flash_rows_split<64, true> : nullptr;
-  return hd == 128 ? k_attn_flash_rows_split<128> : hd == 64 ? k_attn_flash_rows_split<64> : nullptr;
+  return hd == 256 ? k_attn_flash_rows_split_w<256> : hd == 128 ? k_attn_flash_rows_split<128> : hd == 64 ? k_attn_flash_rows_split<64> : nullptr;
 }
 // strict-order Q4_K step: k_gemv_res_nq<Q4_K, SPLIT, QIN, .., ORD> (qin 1 = quantize the f32 rhs, 2 = copy finished planes) ...
 typedef decltype(&k_gemv_res_nq<CRABML_HIP_Q4_K, 1, 1, false, false, true>) NqOrdKFn;
@@ -1642,11 +1642,12 @@ int launch_attn_long_rows(crabml_hip_llama* c, int l, int B) {
 // FLASH_ROWS_SPLIT_FROM: the smallest measured end position from which the split form was not slower at any deeper measured point
 // (Llama-3-8B shape, 32- and 64-row passes ending at 512 .. 30000, profiles/long_context.md).
 constexpr size_t FLASH_ROWS_SPLIT_FROM = 512;
-int flash_rows_slices(int n_cu, size_t n_heads, size_t n_kv, size_t rows, size_t pos0) {
+// frag_cap: the most fragments of a split-form workgroup (flash_rows_frag_cap of the context's head_dim).
+int flash_rows_slices(int n_cu, size_t n_heads, size_t n_kv, size_t rows, size_t pos0, int frag_cap = 8) {
   if (rows == 0 || n_kv == 0 || n_heads % n_kv != 0) return 1;
   if ((rows + 63) / 64 * n_heads * 2 > (size_t)n_cu) return 1;
   if (pos0 + rows < FLASH_ROWS_SPLIT_FROM) return 1;
-  const size_t wgs = n_kv * (size_t)flash_rows_split_geom((int)(n_heads / n_kv), (int)rows).nwg;  // workgroups of one slice
+  const size_t wgs = n_kv * (size_t)flash_rows_split_geom((int)(n_heads / n_kv), (int)rows, frag_cap).nwg;  // workgroups of one slice
   const size_t tiles = (pos0 + rows - 1) / FLASH_ROWS_BN + 1;
   const size_t S = std::min({(2 * (size_t)n_cu + wgs - 1) / wgs, tiles, (size_t)FLASH_ROWS_MAX_SLICES});
   return S < 2 ? 1 : (int)S;
@@ -1655,7 +1656,8 @@ int flash_rows_slices(int n_cu, size_t n_heads, size_t n_kv, size_t rows, size_t
 size_t flash_rows_part_cap(const crabml_hip_llama* c) {
   size_t most = 0;
   for (size_t rows = 1; rows <= c->pf_cap; rows++) {
-    const int S = flash_rows_slices(c->dev->n_cu, (size_t)c->n_heads_l, (size_t)c->n_kv_l, rows, (size_t)FLASH_ROWS_MAX_SLICES * FLASH_ROWS_BN + FLASH_ROWS_SPLIT_FROM);
+    const int S = flash_rows_slices(c->dev->n_cu, (size_t)c->n_heads_l, (size_t)c->n_kv_l, rows, (size_t)FLASH_ROWS_MAX_SLICES * FLASH_ROWS_BN + FLASH_ROWS_SPLIT_FROM,
+                                    flash_rows_frag_cap(c->hd));
     if (S > 1) most = std::max(most, flash_rows_part_floats(S, (int)rows, c->n_heads_l, c->hd));
   }
   return most;
@@ -1663,10 +1665,12 @@ size_t flash_rows_part_cap(const crabml_hip_llama* c) {
 // the two launches of the split form: `slices` (<= the pass's tiles) slices into `part`, merged into out
 void launch_flash_rows_split(hipStream_t st, int hd, const float* q, const unsigned short* k, const unsigned short* v, const int* pos_d, float* part,
                              float* out, int n_heads, int n_kv, int seq_cap, int B, int slices, bool kv8 = false) {
-  const FlashRowsSplitGeom ge = flash_rows_split_geom(n_heads / n_kv, B);
+  const FlashRowsSplitGeom ge = flash_rows_split_geom(n_heads / n_kv, B, flash_rows_frag_cap(hd));
   flash_rows_split_kernel(hd, kv8)<<<dim3((unsigned)ge.nwg, (unsigned)n_kv, (unsigned)slices), 64 * ge.fpw, flash_rows_lds_bytes(hd), st>>>(
       q, k, v, pos_d, part, n_heads, n_kv, seq_cap, B, slices);
-  if (hd == 128)
+  if (hd == 256)
+    k_attn_flash_rows_merge<256><<<(unsigned)(B * n_heads), 256, 0, st>>>(part, out, B * n_heads, slices);
+  else if (hd == 128)
     k_attn_flash_rows_merge<128><<<(unsigned)(B * n_heads), 128, 0, st>>>(part, out, B * n_heads, slices);
   else
     k_attn_flash_rows_merge<64><<<(unsigned)(B * n_heads), 64, 0, st>>>(part, out, B * n_heads, slices);
@@ -1692,7 +1696,7 @@ int launch_prefill_attention(crabml_hip_llama* c, int l, size_t B, size_t pos0) 
   if (c->plan.attn_flash_rows && (kv16 || kv8) && pos0 + B >= c->plan.attn_long_from) {
     // fast step: causal flash attention on the f16 matrix cores (k_attn_flash_rows; the deviation stated for k_attn_flash) -- a short
     // pass deep in the cache in its split-KV form
-    const int slices = c->plan.flash_rows_split ? flash_rows_slices(dev->n_cu, (size_t)n_heads, (size_t)n_kv, B, pos0) : 1;
+    const int slices = c->plan.flash_rows_split ? flash_rows_slices(dev->n_cu, (size_t)n_heads, (size_t)n_kv, B, pos0, flash_rows_frag_cap(hd)) : 1;
     if (slices > 1) {
       if (!c->pf_flash_part && dalloc(c, flash_rows_part_cap(c) * 4, (void**)&c->pf_flash_part) != 0) return -1;
       launch_flash_rows_split(st, hd, (const float*)c->pf_qr, (const unsigned short*)c->kc[l], (const unsigned short*)c->vc[l], pos_d,
@@ -1700,7 +1704,7 @@ int launch_prefill_attention(crabml_hip_llama* c, int l, size_t B, size_t pos0) 
       return 1;
     }
     const dim3 fg((unsigned)((B + 63) / 64), (unsigned)n_heads);
-    flash_rows_kernel(hd, kv8)<<<fg, 512, flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
+    flash_rows_kernel(hd, kv8)<<<fg, flash_rows_threads(hd), flash_rows_lds_bytes(hd), st>>>((const float*)c->pf_qr, (const unsigned short*)c->kc[l],
                                                                            (const unsigned short*)c->vc[l], pos_d, c->pf_attn, n_heads, n_kv, seq_cap, (int)B);
     return 1;
   }
@@ -2593,8 +2597,10 @@ static void decide_attention(const crabml_hip_device* dev, const crabml_hip_llam
     if (!p->flash_ticket && hooks.ticket_until > 0 && tfn != nullptr && lds_fits(dev, (const void*)tfn, flash_lds_bytes(grp, hd), LDS_NO_CAP, 0))
       p->flash_ticket_until = hooks.ticket_until;
     // the prompt pass's causal attention of the fast step (k_attn_flash_rows): 70 KB of LDS at head_dim 128
+    // (head_dim 256 -- k_attn_flash_rows_w -- only in a context created with CRABML_HIP_LLAMA_PREFILL_FLASH_ROWS_HD256: the recorded
+    // plans of the Gemma contexts hold the default to the exact kernels)
     p->attn_flash_rows =
-        (rows_geom || q8_geom) && flash_rows_kernel(hd, kv8) != nullptr &&
+        (rows_geom || q8_geom) && flash_rows_kernel(hd, kv8) != nullptr && (hd <= 128 || has(CRABML_HIP_LLAMA_PREFILL_FLASH_ROWS_HD256)) &&
         lds_fits(dev, (const void*)flash_rows_kernel(hd, kv8), flash_rows_lds_bytes(hd), LDS_NO_CAP, 0);
     // ... and its split-KV form for short passes deep in the cache (k_attn_flash_rows_split: the same tiles, the same LDS)
     p->flash_rows_split = p->attn_flash_rows && !has(CRABML_HIP_LLAMA_NO_FLASH_ROWS_SPLIT) &&
@@ -3652,7 +3658,7 @@ static int debug_flash_attention_rows_impl(crabml_hip_device_t* dev, const float
                                            size_t seq_cap, float* out) {
   const bool kv8 = kd != nullptr;
   if (!dev || !q || !k || !v || !out || (kv8 && !vd) || rows == 0 || n_kv == 0 || n_heads % n_kv != 0 || seq_cap < pos0 + rows) return CRABML_HIP_BAD_INPUT;
-  if (head_dim != 128 && head_dim != 64) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_rows: head_dim 64 / 128");
+  if (!flash_rows_kernel((int)head_dim, kv8)) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_rows: head_dim 64 / 128 (f16 cache: 256 as well)");
   CH_LIVE(dev);
   CH_USE(dev);
   CH_FLUSH(dev);
@@ -3677,7 +3683,7 @@ static int debug_flash_attention_rows_impl(crabml_hip_device_t* dev, const float
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e == hipSuccess) {
     const dim3 fg((unsigned)((rows + 63) / 64), (unsigned)n_heads);
-    fn<<<fg, 512, flash_rows_lds_bytes((int)head_dim), st>>>((const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
+    fn<<<fg, flash_rows_threads((int)head_dim), flash_rows_lds_bytes((int)head_dim), st>>>((const float*)(base + o_q), (const unsigned short*)(base + o_k), (const unsigned short*)(base + o_v),
                                                              (const int*)(base + o_pos), (float*)(base + o_out), (int)n_heads, (int)n_kv, (int)seq, (int)rows);
     e = hipGetLastError();
   }
@@ -3699,7 +3705,8 @@ static int debug_flash_attention_rows_split_impl(crabml_hip_device_t* dev, const
   const bool kv8 = kd != nullptr;
   if (!dev || !q || !k || !v || !out || (kv8 && !vd) || rows == 0 || n_kv == 0 || n_heads % n_kv != 0 || seq_cap < pos0 + rows || slices < 1)
     return CRABML_HIP_BAD_INPUT;
-  if (head_dim != 128 && head_dim != 64) CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_rows_split: head_dim 64 / 128");
+  if (!flash_rows_split_kernel((int)head_dim, kv8))
+    CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_rows_split: head_dim 64 / 128 (f16 cache: 256 as well)");
   if (n_heads / n_kv > 8 || pos0 + rows > (size_t)1 << 30)
     CH_BAIL(dev, CRABML_HIP_BAD_INPUT, "debug_flash_attention_rows_split: groups 1 .. 8, at most 2^30 positions");
   CH_LIVE(dev);

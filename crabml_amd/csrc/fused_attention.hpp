@@ -1498,9 +1498,19 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 #define FLASH_ROWS_BN 64                   // cached positions per V^T fill
 #define FLASH_ROWS_VSTR (FLASH_ROWS_BN + 4)  // halfs per V^T row: 8-byte aligned fragments, rows 34 banks apart
 #define FLASH_ROWS_KPAD 8                   // halfs of padding per K row in LDS (16-byte aligned fragments, rows 4 banks apart)
+// head_dim 256 (k_attn_flash_rows_w / k_attn_flash_rows_split_w below): fills of 32 positions, workgroups of at most 4 row waves
+#define FLASH_ROWS_W_BN 32
+#define FLASH_ROWS_W_VSTR (FLASH_ROWS_W_BN + 8)  // halfs per V^T row: rows 20 banks apart (the fragment reads AND the fill's stores spread evenly)
+#define FLASH_ROWS_W_FRAGS 4
+// two workgroups of 4 waves per CU are 2 waves per SIMD: the kernels are held to 256 registers (VGPRs + AGPRs) for that
+#define FLASH_ROWS_W_TWO_PER_CU __attribute__((amdgpu_waves_per_eu(2)))
 __host__ __device__ inline size_t flash_rows_lds_bytes(int hd) {
+  if (hd > 128) return (size_t)2 * ((size_t)hd * FLASH_ROWS_W_VSTR + (size_t)FLASH_ROWS_W_BN * (hd + FLASH_ROWS_KPAD)) * 2;
   return (size_t)2 * ((size_t)hd * FLASH_ROWS_VSTR + (size_t)FLASH_ROWS_BN * (hd + FLASH_ROWS_KPAD)) * 2;
 }
+// threads of a k_attn_flash_rows launch / most fragments (waves) of a k_attn_flash_rows_split workgroup, by head_dim
+__host__ __device__ inline int flash_rows_threads(int hd) { return hd > 128 ? 64 * FLASH_ROWS_W_FRAGS : 512; }
+__host__ __device__ inline int flash_rows_frag_cap(int hd) { return hd > 128 ? FLASH_ROWS_W_FRAGS : 8; }
 // KV8 (this kernel and k_attn_flash_rows_split): the cache is the Q8 plane pair k_attn_flash<.., KV8> describes.  The matrix products
 // keep their f16 LDS tiles; the staging differs: a 16-byte piece is 16 int8 of one position -- half a block, so one scale, requested
 // with the piece -- and a tile of 64 positions is 4 HD pieces, expanded on the way into LDS: K^ = f16(d * q), V^ = f16(d * q) (d * q
@@ -1736,8 +1746,8 @@ __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict
 struct FlashRowsSplitGeom {
   int nfrag, nwg, fpw;  // fragments of a kv head, workgroups they take, fragments (waves) per workgroup
 };
-__host__ __device__ inline FlashRowsSplitGeom flash_rows_split_geom(int G, int rows) {
-  const int nfrag = G * ((rows + 15) / 16), nwg = (nfrag + 7) / 8;
+__host__ __device__ inline FlashRowsSplitGeom flash_rows_split_geom(int G, int rows, int frag_cap = 8) {
+  const int nfrag = G * ((rows + 15) / 16), nwg = (nfrag + frag_cap - 1) / frag_cap;
   return FlashRowsSplitGeom{nfrag, nwg, (nfrag + nwg - 1) / nwg};
 }
 #define FLASH_ROWS_MAX_SLICES 32
@@ -1948,6 +1958,260 @@ FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(HD) void k_attn_flash_rows_
     o = __builtin_fmaf(part[r * HD + d], w, o);
   }
   out[(size_t)rec * HD + d] = o / L;
+}
+
+// ---- head_dim 256 (Gemma): the flash-rows pair in a geometry of its own ---------------------------------------------------------------
+// The arithmetic is k_attn_flash_rows' (q rounded to f16 once, S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_f16, f32 online
+// softmax, P packed to f16 straight from the C registers with the normaliser summing the rounded values, causal mask on the C
+// registers, V zeroed at positions no row of the workgroup sees, rows past the batch never stored).  The 64 / 128 geometry scaled to
+// 256 would be 137216 bytes of LDS: one 512-thread workgroup per CU and nothing beside it to run under its fills and barriers, 64
+// accumulator + 32 q + 32 staging VGPRs per lane.  This one:
+//   fill      = 32 cached positions (FLASH_ROWS_W_BN): one 32-position step per wave per fill; LDS 2 x (256 x 40 + 32 x 264) x 2 =
+//               74752 bytes, so TWO workgroups share a CU
+//   workgroup = at most 4 waves (FLASH_ROWS_W_FRAGS), each owning 16 prompt rows of one head from the first tile to the last: no wave
+//               pairs, so no {m, l, O} hand-over; two workgroups of 4 waves are the same 2 waves per SIMD the 512-thread workgroup
+//               was (256 VGPRs each), but they meet at separate barriers: one's matrix work runs under the other's fill
+//   V^T fill  = a thread takes the same 8 dims of two adjacent positions and stores whole dwords {v[p][d], v[p + 1][d]}: half the
+//               stores of the 2-byte form.  Lane = (position pair l % 16, piece column l / 16); rows of 40 halfs put dim d at bank
+//               20 d: lane groups 0 / 1 differ by 8 dims = 32 banks, and groups 2 / 3 store their dims in the order 4..7, 0..3 (a
+//               swap of register halves), another 16 banks on: every store of a wave covers the 64 banks once.  The fragment reads
+//               (lane = dim n, positions 4 g .. + 4: 8 bytes at bank 20 n + 2 g) fall on every bank pair exactly twice, the floor.
+//   K tile    = [32][HD + 8] as the cache holds it, 16-byte stores and fragment reads as in the family
+// One tile body (frw_step) and one staging struct (FrwTiles) serve both forms; the one-launch kernel is workgroup = (64 rows, head),
+// the split form spreads a kv head's fragments over workgroups of at most 4 (flash_rows_split_geom with that cap) and writes the
+// family's partials, which k_attn_flash_rows_merge<256> merges.
+template <int HD>
+struct FrwTiles {
+  static constexpr int BN = FLASH_ROWS_W_BN, VSTR = FLASH_ROWS_W_VSTR, KSTR = HD + FLASH_ROWS_KPAD, PC = HD / 8, NT = 64 * FLASH_ROWS_W_FRAGS,
+                       NK = BN * PC / NT, NV = NK / 2;  // K pieces / V piece pairs a thread of a full workgroup carries in registers
+  static_assert(BN == 32 && PC == 32, "a wave is 2 K rows of 32 pieces, or 4 piece columns of the 16 V position pairs");
+  // A workgroup is whole waves, so thread t keeps its K piece column t % 32 and its V position pair t % 16 from fill to fill and
+  // steps through K rows t / 32 + (nthr / 32) u and V piece columns t / 16 + (nthr / 16) u: one address each, scalar strides.
+  const unsigned short *kb, *vb;
+  unsigned short *vt0, *kt0;
+  int seq_cap, last_wg, tid, nthr;
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ int clamp(int pos) const {
+    return pos < seq_cap ? pos : seq_cap - 1;  // (past the cache only in its last tile; those positions are dead)
+  }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void fetch_k(int tile, int pr, i32x4& kk) const {
+    kk = *(const i32x4*)(kb + (size_t)clamp(tile * BN + pr) * HD + 8 * (tid % PC));
+  }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void place_k(int buf, int pr, const i32x4& kk) const {
+    *(i32x4*)(kt0 + (buf * BN + pr) * KSTR + 8 * (tid % PC)) = kk;
+  }
+  // V pair: positions 2 (t % 16), + 1 of the tile, dims 8 pc .. + 8
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void fetch_v(int tile, int pc, i32x4& v0, i32x4& v1) const {
+    const int p0 = tile * BN + 2 * (tid % 16);
+    v0 = *(const i32x4*)(vb + (size_t)clamp(p0) * HD + 8 * pc);
+    v1 = *(const i32x4*)(vb + (size_t)clamp(p0 + 1) * HD + 8 * pc);
+  }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void place_v(int buf, int tile, int pc, const i32x4& v0, const i32x4& v1) const {
+    const int pq = tid % 16, p0 = tile * BN + 2 * pq;
+    // positions no row of the workgroup sees hold whatever the allocator or an earlier sequence left in the cache: their
+    // probabilities are exactly 0, but 0 x NaN / Inf is not -- V enters the product as zeros there (K: the scores are masked)
+    const bool live0 = p0 <= last_wg, live1 = p0 + 1 <= last_wg;
+    unsigned w[8];  // w[e] = {v[p0][8 pc + e], v[p0 + 1][8 pc + e]}
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const unsigned a = live0 ? (unsigned)v0[i] : 0u, b = live1 ? (unsigned)v1[i] : 0u;
+      w[2 * i] = (a & 0xffffu) | (b << 16);
+      w[2 * i + 1] = (a >> 16) | (b & 0xffff0000u);
+    }
+    const bool swap = (tid & 32) != 0;  // lane groups 2 / 3 (pc & 2: the column steps are multiples of 4): dims 4 .. 7 first
+    unsigned short* col = vt0 + (buf * HD + 8 * pc) * VSTR + 2 * pq;
+    unsigned short* first = col + (swap ? 4 * VSTR : 0);
+    unsigned short* second = col + (swap ? 0 : 4 * VSTR);
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      *(unsigned*)(first + e * VSTR) = swap ? w[4 + e] : w[e];
+      *(unsigned*)(second + e * VSTR) = swap ? w[e] : w[4 + e];
+    }
+  }
+  // global -> registers for what a workgroup of NT threads carries across a tile ...
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void issue(int tile, i32x4 (&kreg)[NK], i32x4 (&vreg)[2 * NV]) const {
+#pragma unroll
+    for (int u = 0; u < NK; u++)
+      if (tid / PC + nthr / PC * u < BN) fetch_k(tile, tid / PC + nthr / PC * u, kreg[u]);
+#pragma unroll
+    for (int u = 0; u < NV; u++)
+      if (tid / 16 + nthr / 16 * u < PC) fetch_v(tile, tid / 16 + nthr / 16 * u, vreg[2 * u], vreg[2 * u + 1]);
+  }
+  // ... registers -> LDS; a workgroup of fewer waves fetches the rest of the tile here, without the overlap
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void commit(int buf, int tile, const i32x4 (&kreg)[NK], const i32x4 (&vreg)[2 * NV]) const {
+#pragma unroll
+    for (int u = 0; u < NK; u++)
+      if (tid / PC + nthr / PC * u < BN) place_k(buf, tid / PC + nthr / PC * u, kreg[u]);
+#pragma unroll
+    for (int u = 0; u < NV; u++)
+      if (tid / 16 + nthr / 16 * u < PC) place_v(buf, tile, tid / 16 + nthr / 16 * u, vreg[2 * u], vreg[2 * u + 1]);
+    for (int pr = tid / PC + nthr / PC * NK; pr < BN; pr += nthr / PC) {
+      i32x4 kk;
+      fetch_k(tile, pr, kk);
+      place_k(buf, pr, kk);
+    }
+    for (int pc = tid / 16 + nthr / 16 * NV; pc < PC; pc += nthr / 16) {
+      i32x4 v0, v1;
+      fetch_v(tile, pc, v0, v1);
+      place_v(buf, tile, pc, v0, v1);
+    }
+  }
+};
+// this wave's q rows as the B operand: lane (row n, dims 32 ks + 8 g .. + 8), rounded to f16 once
+template <int HD>
+FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void frw_load_q(const float* qrow, int g, f16x8 (&qb)[HD / 32]) {
+#pragma unroll
+  for (int ks = 0; ks < HD / 32; ks++) {
+    const f32x4* qp = (const f32x4*)(qrow + 32 * ks + 8 * g);
+    const f32x4 a = qp[0], b = qp[1];
+    qb[ks] = f16x8{(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3], (_Float16)b[0], (_Float16)b[1], (_Float16)b[2], (_Float16)b[3]};
+  }
+}
+// The tile body of both forms: one wave's 16 rows against the 32 positions from ca0 (kt / vt: that tile's buffers).  k_attn_flash_rows'
+// 32-position step: two 16-position chunks a / b, two independent S^T chains, one agreement on the running maximum, the second product
+// on 16x16x32 with k-slot (g, i) = position 4 g + i of chunk a, (g, 4 + i) = the same of chunk b.
+template <int HD>
+FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void frw_step(const unsigned short* kt, const unsigned short* vt, const f16x8 (&qb)[HD / 32],
+                                                                 f32x4 (&acc)[HD / 16], float& m, float& lsum, int ca0, int my_last, int n, int g) {
+  constexpr int KS = HD / 32, DT = HD / 16, VSTR = FLASH_ROWS_W_VSTR, KSTR = HD + FLASH_ROWS_KPAD;
+  const int cb0 = ca0 + 16;
+  f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < KS; ks++) {
+    sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + n * KSTR + 32 * ks + 8 * g), qb[ks], sa, 0, 0, 0);
+    sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + (16 + n) * KSTR + 32 * ks + 8 * g), qb[ks], sb, 0, 0, 0);
+  }
+  // (the V^T fragments are not to be requested above this line: 16 K fragments and 16 V fragments in flight at once are 128 VGPRs
+  // beside the 128 of accumulators, q and staging)
+  __builtin_amdgcn_sched_barrier(0);
+  float cm = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {  // causal mask (also: dead cache rows, whatever they hold)
+    if (ca0 + 4 * g + i > my_last) sa[i] = -INFINITY;
+    if (cb0 + 4 * g + i > my_last) sb[i] = -INFINITY;
+    cm = fmaxf(cm, fmaxf(sa[i], sb[i]));
+  }
+  cm = fmaxf(cm, __shfl_xor(cm, 16));
+  cm = fmaxf(cm, __shfl_xor(cm, 32));
+  // (a row that has seen nothing of the slice yet: m = mn = -inf, alpha = 1, p = 0)
+  const float mn = fmaxf(m, cm);
+  if (__any(mn > m)) {  // the running maximum of some row moved: rescale (rare after the first steps)
+    const float alpha = mn == -INFINITY ? 1.0f : __expf(m - mn);
+    lsum *= alpha;
+#pragma unroll
+    for (int dt = 0; dt < DT; dt++) acc[dt] = acc[dt] * alpha;
+    m = mn;
+  }
+  f16x8 pT;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const _Float16 pa = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sa[i] - m);
+    const _Float16 pb = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sb[i] - m);
+    pT[i] = pa;
+    pT[4 + i] = pb;
+    lsum += (float)pa + (float)pb;  // the normalizer sums what the second product multiplies
+  }
+#pragma unroll
+  for (int dt = 0; dt < DT; dt++) {
+    const unsigned short* vr = vt + (16 * dt + n) * VSTR + 4 * g;
+    const f16x4 va = *(const f16x4*)vr, vb2 = *(const f16x4*)(vr + 16);
+    const f16x8 vf = {va[0], va[1], va[2], va[3], vb2[0], vb2[1], vb2[2], vb2[3]};
+    acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pT, acc[dt], 0, 0, 0);
+  }
+}
+// One fragment (16 rows from row_w of `head`; `owner` false: the wave only stages) over the workgroup's tiles t0 .. t1: the loop both
+// forms run -- two buffers, the next tile's loads requested before this one is multiplied, one barrier per tile.  Leaves the
+// unnormalised O^T in acc (C layout: acc[dt][i] = O^T[dim 16 dt + 4 g + i][row n]), the row's m, and its l summed over the lane groups.
+template <int HD>
+FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void frw_walk(const float* __restrict__ q, const unsigned short* kb, const unsigned short* vb,
+                                                                 unsigned short* lds, int n_heads, int seq_cap, int B, int pos0, int head, int row_w,
+                                                                 bool owner, int last_wg, int t0, int t1, f32x4 (&acc)[HD / 16], float& m, float& lsum) {
+  constexpr int DT = HD / 16, BN = FLASH_ROWS_W_BN, VSTR = FLASH_ROWS_W_VSTR, KSTR = HD + FLASH_ROWS_KPAD;
+  const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, g = lane >> 4;
+  unsigned short* vt0 = lds;
+  unsigned short* kt0 = lds + 2 * HD * VSTR;
+  const int row = row_w + n < B ? row_w + n : B - 1;  // (rows past the batch recompute the last row; never stored)
+  f16x8 qb[HD / 32];
+  frw_load_q<HD>(q + ((size_t)row * n_heads + head) * HD, g, qb);
+  const int last_w = pos0 + (row_w + 15 < B ? row_w + 15 : B - 1);  // last cached position any row of this wave sees
+  const int my_last = pos0 + row;                                   // ... this lane's row
+#pragma unroll
+  for (int dt = 0; dt < DT; dt++) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  m = -INFINITY, lsum = 0.f;
+  i32x4 kreg[FrwTiles<HD>::NK], vreg[2 * FrwTiles<HD>::NV];
+  const FrwTiles<HD> tl{kb, vb, vt0, kt0, seq_cap, last_wg, tid, (int)blockDim.x};
+  if (t0 < t1) {
+    tl.issue(t0, kreg, vreg);
+    tl.commit(0, t0, kreg, vreg);
+  }
+  __syncthreads();
+  for (int tile = t0; tile < t1; tile++) {
+    const int buf = (tile - t0) & 1;
+    if (tile + 1 < t1) tl.issue(tile + 1, kreg, vreg);
+    if (owner && tile * BN <= last_w)  // wave-uniform: some row of this wave sees the tile
+      frw_step<HD>(kt0 + buf * BN * KSTR, vt0 + buf * HD * VSTR, qb, acc, m, lsum, tile * BN, my_last, n, g);
+    if (tile + 1 < t1) tl.commit(buf ^ 1, tile + 1, kreg, vreg);  // those buffers were last read one tile ago (barrier below)
+    __syncthreads();
+  }
+  lsum += __shfl_xor(lsum, 16);
+  lsum += __shfl_xor(lsum, 32);
+}
+// the one-launch causal kernel: grid (ceil(B / 64), n_heads), 256 threads, flash_rows_lds_bytes(HD) of LDS; k_attn_flash_rows' arguments
+template <int HD>
+FLASH_ROWS_SPLIT_TARGET FLASH_ROWS_W_TWO_PER_CU __global__ __launch_bounds__(64 * FLASH_ROWS_W_FRAGS) void k_attn_flash_rows_w(
+    const float* __restrict__ q, const unsigned short* __restrict__ kc, const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
+    float* __restrict__ out, int n_heads, int n_kv, int seq_cap, int B) {
+  extern __shared__ __attribute__((aligned(16))) unsigned short fr_lds[];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = lane & 15, g = lane >> 4;  // (wave: an SGPR, and so what follows from it)
+  const int head = blockIdx.y, j = head / (n_heads / n_kv), pos0 = *pos_d;
+  const int row_wg = blockIdx.x * 64, row_w = row_wg + 16 * wave;
+  const int last_wg = pos0 + (row_wg + 63 < B ? row_wg + 63 : B - 1);  // last cached position any row of the workgroup sees
+  f32x4 acc[HD / 16];
+  float m, lsum;
+  // (a wave whose 16 rows all lie past the batch stages tiles and computes nothing)
+  frw_walk<HD>(q, kc + (size_t)j * seq_cap * HD, vc + (size_t)j * seq_cap * HD, fr_lds, n_heads, seq_cap, B, pos0, head, row_w, row_w < B, last_wg,
+               0, last_wg / FLASH_ROWS_W_BN + 1, acc, m, lsum);
+  if (row_w + n < B) {  // (the row saw position 0: l > 0)
+    const float inv = 1.0f / lsum;
+    float* o = out + ((size_t)(row_w + n) * n_heads + head) * HD;
+#pragma unroll
+    for (int dt = 0; dt < HD / 16; dt++) *(f32x4*)(o + 16 * dt + 4 * g) = acc[dt] * inv;
+  }
+}
+// the split-KV form: grid (flash_rows_split_geom(G, B, 4).nwg, n_kv, S), 64 fpw threads; k_attn_flash_rows_split's arguments, slices and partials
+template <int HD>
+FLASH_ROWS_SPLIT_TARGET FLASH_ROWS_W_TWO_PER_CU __global__ __launch_bounds__(64 * FLASH_ROWS_W_FRAGS) void k_attn_flash_rows_split_w(
+    const float* __restrict__ q, const unsigned short* __restrict__ kc, const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
+    float* __restrict__ part, int n_heads, int n_kv, int seq_cap, int B, int S) {
+  constexpr int BN = FLASH_ROWS_W_BN;
+  extern __shared__ __attribute__((aligned(16))) unsigned short fr_lds[];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = lane & 15, g = lane >> 4;  // (wave: an SGPR, and so what follows from it)
+  const int G = n_heads / n_kv, j = blockIdx.y, s = blockIdx.z, pos0 = *pos_d;
+  const FlashRowsSplitGeom ge = flash_rows_split_geom(G, B, FLASH_ROWS_W_FRAGS);
+  const int f0 = blockIdx.x * ge.fpw, f1 = f0 + ge.fpw < ge.nfrag ? f0 + ge.fpw : ge.nfrag;
+  if (f0 >= f1) return;  // (workgroup-uniform; flash_rows_split_geom leaves no workgroup empty)
+  const bool owner = f0 + wave < f1;
+  const int f = owner ? f0 + wave : f1 - 1;
+  const int head = j * G + f % G, row_w = (f / G) * 16;
+  const int rlast_wg = ((f1 - 1) / G) * 16 + 15;                 // the workgroup's fragments are row-block major: its last one's rows
+  const int last_wg = pos0 + (rlast_wg < B ? rlast_wg : B - 1);  // last cached position any row of the workgroup sees
+  const int NT = (pos0 + B - 1) / BN + 1;                        // tiles of the pass (at least as many as the 64-position tiles S is capped by)
+  const int t0 = (int)((long long)s * NT / S), t1s = (int)((long long)(s + 1) * NT / S);
+  const int t1 = t1s < last_wg / BN + 1 ? t1s : last_wg / BN + 1;  // (t1 <= t0: the workgroup sees nothing of the slice)
+  f32x4 acc[HD / 16];
+  float m, lsum;
+  frw_walk<HD>(q, kc + (size_t)j * seq_cap * HD, vc + (size_t)j * seq_cap * HD, fr_lds, n_heads, seq_cap, B, pos0, head, row_w, owner, last_wg, t0,
+               t1, acc, m, lsum);
+  if (owner && row_w + n < B) {
+    const size_t rec = ((size_t)s * B + row_w + n) * n_heads + head;
+    float* o = part + rec * HD;
+#pragma unroll
+    for (int dt = 0; dt < HD / 16; dt++) *(f32x4*)(o + 16 * dt + 4 * g) = acc[dt];
+    if (g == 0) {
+      float* ml = part + (size_t)S * B * n_heads * HD + rec * 2;
+      ml[0] = m;
+      ml[1] = lsum;
+    }
+  }
 }
 
 // ---- the Q8 KV cache's append (use_f16_kv_cache == 2): R staged rows -> both planes of K and of V at positions *pos_d .. + R ----------

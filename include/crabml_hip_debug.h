@@ -94,13 +94,16 @@ int crabml_hip_debug_flash_attention(crabml_hip_device_t* dev, const float* q, c
 /* The fast prompt pass's causal attention (k_attn_flash_rows: flash attention on the f16 matrix cores) by itself.  q: rows *
  * n_heads * head_dim f32 (row r is the prompt row at position pos0 + r); k, v: [n_kv][seq_cap][head_dim] f16 bits (the cache
  * after the pass's appends: positions 0 .. pos0 + rows - 1 are live, whatever lies beyond must not matter); out: rows * n_heads *
- * head_dim f32, row r = softmax(q_r k^T over positions 0 .. pos0 + r) v.  head_dim 64 / 128.  Host pointers; blocks. */
+ * head_dim f32, row r = softmax(q_r k^T over positions 0 .. pos0 + r) v.  head_dim 64 / 128, and 256 (k_attn_flash_rows_w: the
+ * family's arithmetic in fills of 32 positions, what a context created with CRABML_HIP_LLAMA_PREFILL_FLASH_ROWS_HD256 runs).  Host
+ * pointers; blocks. */
 int crabml_hip_debug_flash_attention_rows(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
                                           size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, float* out);
 
 /* The split-KV form of that attention (k_attn_flash_rows_split + k_attn_flash_rows_merge: what a short pass deep in the cache runs) by
  * itself, its two launches with a forced slice count.  Arguments and host-pointer conventions as above; slices >= 1, clamped to the
- * pass's 64-position tiles ((pos0 + rows - 1) / 64 + 1) and to 32; n_heads / n_kv from 1 to 8.  The partials scratch holds 0xFF bytes
+ * pass's 64-position tiles ((pos0 + rows - 1) / 64 + 1) and to 32; n_heads / n_kv from 1 to 8; head_dim 64 / 128, and 256
+ * (k_attn_flash_rows_split_w: workgroups of at most 4 fragments).  The partials scratch holds 0xFF bytes
  * before the first launch, so a partial the merge reads and the first launch did not write shows as NaN in out.  Blocks. */
 int crabml_hip_debug_flash_attention_rows_split(crabml_hip_device_t* dev, const float* q, const uint16_t* k, const uint16_t* v, size_t n_heads,
                                                 size_t n_kv, size_t head_dim, size_t pos0, size_t rows, size_t seq_cap, size_t slices, float* out);
@@ -176,6 +179,15 @@ int crabml_hip_debug_sample(crabml_hip_device_t* dev, const float* logits, size_
                                                           (k_attn_flash_rows_split + its merge: the same arithmetic per tile, the partials of
                                                           the position slices merged in f32; both forms within the launch pins' FLASH_ROWS_REL
                                                           of float64).  With the flag a context chooses exactly as it did before that form existed */
+#define CRABML_HIP_LLAMA_PREFILL_FLASH_ROWS_HD256 (-2147483647 - 1) /* opt-in kernel variant (NOT bit-identical), bit 31 of the int32 flags:
+                                                          fast device, f16 cache, head_dim 256 (Gemma), GQA groups the flash-rows family serves:
+                                                          the prompt pass's attention runs the flash-rows family on the f16 matrix cores
+                                                          (k_attn_flash_rows_w, and k_attn_flash_rows_split_w + the merge for short passes deep in
+                                                          the cache; the family's stated deviation) instead of the exact tile /
+                                                          long-rows kernels.  Off, a head_dim-256 context plans and runs exactly as it always has
+                                                          (tests/golden/step_plan_mi355x.json records that plan).  The strict-order device,
+                                                          EXACT_ATTENTION, NO_LONG_ATTENTION and a Q8 cache ignore it; at head_dim 64 / 128 it
+                                                          changes nothing.  tools/generate.py --flash-rows-256 sets it */
 #define CRABML_HIP_LLAMA_PREFILL_TAP_Q2K_Q3K 268435456/* test hook: crabml_hip_llama_debug_prefill_tap also serves contexts whose layer
                                                          matrices or classifier are Q2_K / Q3_K (the checker restates their kernels:
                                                          tests/q23k_f16w_ref.py).  Off, the tap refuses such a context with

@@ -12,7 +12,10 @@ Per SHAPE:FORMAT one markdown table row; every decode figure is tok/s of a windo
              kernels that existed before the Gemma decode step did.  The baseline: nothing else could run the model.  16 tokens
   prompt     prefill tok/s of 512 rows
 --sweep: the crossover of the split-KV kernel against the staged one-workgroup-per-head kernel at this geometry -- 16 decode steps
-from each start position with attn_long_from = 1 (k_attn_flash from the first position) and = seq_len (never), alternately."""
+from each start position with attn_long_from = 1 (k_attn_flash from the first position) and = seq_len (never), alternately.
+--prompt-pass: ONLY the prompt-pass section -- prompt tok/s of 512 and of 4096 tokens, and of one 32-row pass that ends deep in an 8192
+cache (behind 8000 cached positions), each on a context created with CRABML_HIP_LLAMA_PREFILL_FLASH_ROWS_HD256 (the matrix-core
+flash-rows kernels at head_dim 256) and on one without it (the exact tile / long-rows kernels), alternately, repeat by repeat."""
 import argparse
 import json
 import os
@@ -28,6 +31,7 @@ import crabml_amd as ca  # noqa: E402
 from crabml_amd import synth  # noqa: E402
 
 EXACT_ATTENTION = 4194304  # CRABML_HIP_LLAMA_EXACT_ATTENTION (include/crabml_hip.h)
+FLASH_ROWS_HD256 = -2147483648  # CRABML_HIP_LLAMA_PREFILL_FLASH_ROWS_HD256 (include/crabml_hip_debug.h): bit 31
 
 
 def timed(fn, n):
@@ -134,18 +138,48 @@ def sweep(spec, reps):
     return res
 
 
+def prompt_pass(spec, reps):
+    shape, fmt = spec.split(":")
+    model = synth.build_model(synth.SHAPES[shape], synth.TYPE_BY_NAME[fmt], seed=1)
+    dev = ca.HipTensorDevice(0)
+    conf, w = synth.to_hip(model, dev)
+    on = ca.HipLlamaRunner(conf, w, dev, 8192, True, extra_flags=FLASH_ROWS_HD256)
+    off = ca.HipLlamaRunner(conf, w, dev, 8192, True)
+    prompt = [(11 * i + 5) % conf.vocab_size for i in range(8032)]
+    print("\n| %s %s: prompt tok/s | flash-rows 256 (flag) | exact kernels (default) |" % (shape, fmt))
+    print("|---|---|---|")
+    res = {}
+    for name, behind, n in (("512 tokens", 0, 512), ("4096 tokens", 0, 4096), ("32 rows behind 8000", 8000, 32)):
+        a, b = [], []
+        for rep in range(reps + 1):  # alternately; the first repeat is the warm-up
+            for ctx, acc in ((on, a), (off, b)):
+                ctx.reset()
+                if behind:
+                    ctx.prefill(prompt[:behind])
+                v = timed(lambda: ctx.prefill(prompt[behind:behind + n]), n)
+                if rep:
+                    acc.append(v)
+        res[name] = {"flag": stats(a), "default": stats(b)}
+        print("| %s | %s | %s |" % (name, fmt_stat(stats(a)), fmt_stat(stats(b))), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", default="gemma-2b:Q8_0,gemma-2b:Q4_0")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--prompt-pass", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     cols = ["fused", "@1024", "@1024 exact", "@4096", "@4096 exact", "unchanged", "per-op", "prompt"]
-    print("| shape | format | GB / token | " + " | ".join(cols) + " | fused / per-op |")
-    print("|---|---|---|" + "---|" * len(cols) + "---|")
+    if not a.prompt_pass:
+        print("| shape | format | GB / token | " + " | ".join(cols) + " | fused / per-op |")
+        print("|---|---|---|" + "---|" * len(cols) + "---|")
     all_out = {}
-    for spec in a.runs.split(","):
+    for spec in a.runs.split(",") if a.prompt_pass else []:
+        all_out[spec + "/prompt-pass"] = prompt_pass(spec, a.reps)
+    for spec in [] if a.prompt_pass else a.runs.split(","):
         shape, fmt, o = row(spec, a.reps)
         all_out[spec] = o
         print("| %s | %s | %.2f | " % (shape, fmt, o["GB"]) + " | ".join(fmt_stat(o[c]) for c in cols) +

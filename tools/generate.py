@@ -35,6 +35,8 @@ ap.add_argument("--topp", type=float, default=0.9)
 ap.add_argument("--seed", type=int, default=0, help="seed of the coins (one uniform [0, 1) f32 per token)")
 ap.add_argument("--q5k-gemm", action="store_true", help="CRABML_HIP_LLAMA_PREFILL_Q5K_GEMM: prompt passes of 32 rows or more run Q5_K matrices on "
                 "the f16 matrix-core GEMM instead of the row-by-row GEMV (opt-in; a stated deviation of the fast tier like the other K-quants')")
+ap.add_argument("--flash-rows-256", action="store_true", help="CRABML_HIP_LLAMA_PREFILL_FLASH_ROWS_HD256: a head_dim-256 (Gemma) context runs its "
+                "prompt attention on the matrix-core flash-rows kernels instead of the exact tile / long-rows kernels (opt-in; fast device, f16 cache)")
 a = ap.parse_args()
 
 path = a.gguf
@@ -65,7 +67,7 @@ print(f"loaded + uploaded in {time.perf_counter() - t0:.2f} s")
 prompt = [int(t) for t in a.prompt.split(",") if t]
 seq_len = a.seq_len or min(conf.seq_len, len(prompt) + a.steps + 8)
 kv = {"f32": 0, "f16": 1, "q8": 2}[a.kv] if a.kv else (0 if a.f32_kv else 1)  # crabml_hip_llama_config_t::use_f16_kv_cache
-r = ca.HipLlamaRunner(conf, weights, dev, seq_len, kv, extra_flags=536870912 if a.q5k_gemm else 0)
+r = ca.HipLlamaRunner(conf, weights, dev, seq_len, kv, extra_flags=(536870912 if a.q5k_gemm else 0) | (-2147483648 if a.flash_rows_256 else 0))
 t0 = time.perf_counter()
 logits = r.prefill(prompt)
 t_prefill = time.perf_counter() - t0
