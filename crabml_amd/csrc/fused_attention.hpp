@@ -1511,7 +1511,7 @@ __host__ __device__ inline size_t flash_rows_lds_bytes(int hd) {
 // threads of a k_attn_flash_rows launch / most fragments (waves) of a k_attn_flash_rows_split workgroup, by head_dim
 __host__ __device__ inline int flash_rows_threads(int hd) { return hd > 128 ? 64 * FLASH_ROWS_W_FRAGS : 512; }
 __host__ __device__ inline int flash_rows_frag_cap(int hd) { return hd > 128 ? FLASH_ROWS_W_FRAGS : 8; }
-// KV8 (this kernel and k_attn_flash_rows_split): the cache is the Q8 plane pair k_attn_flash<.., KV8> describes.  The matrix products
+// KV8 (k_attn_flash_rows and k_attn_flash_rows_split): the cache is the Q8 plane pair k_attn_flash<.., KV8> describes.  The matrix products
 // keep their f16 LDS tiles; the staging differs: a 16-byte piece is 16 int8 of one position -- half a block, so one scale, requested
 // with the piece -- and a tile of 64 positions is 4 HD pieces, expanded on the way into LDS: K^ = f16(d * q), V^ = f16(d * q) (d * q
 // is exact in f32; that f16 rounding, 2^-11 relative per element, is the ONE rounding this form adds to k_attn_flash_rows').  V is
@@ -1537,17 +1537,170 @@ __device__ __forceinline__ void flash_rows_place_q8(unsigned short* krow, unsign
 #pragma unroll
   for (int e = 0; e < 16; e++) vcol[e * VSTR] = live ? q8_to_h16((unsigned)vv[e >> 2], e & 3, dv) : (unsigned short)0;
 }
+// (the split kernels keep their f32 vector arithmetic -- the accumulator rescale -- on the one-value VALU forms, and so do the family's
+// helpers where they are inlined into those; inlined into k_attn_flash_rows, which does not carry the attribute, a helper takes that
+// kernel's packed forms)
+#define FLASH_ROWS_SPLIT_TARGET __attribute__((target("no-packed-fp32-ops")))
+// The staging of one workgroup's K / V tiles at head_dim 64 / 128: global -> registers (issue) -> LDS (commit), thread t moving the
+// 16-byte pieces t, t + threads, .. of the K tile and of the V tile (a piece = 8 dims of one position); a whole tile of compute lies
+// between the request and the commit.  NTHR = the workgroup's threads where the kernel fixes them (k_attn_flash_rows, 512: a thread
+// carries every piece it moves across the tile); 0 = the launched block size (k_attn_flash_rows_split: a thread carries up to
+// PIECES / 256 pieces of K and of V, which covers a tile from 4 waves on; a workgroup of fewer waves fetches the rest at commit time,
+// without the overlap).
+// (KV8: a piece is 16 int8 of a position and carries its two scales, `dd` = K scale | V scale << 16; ks / vs = the kv head's scale rows)
+template <int HD, bool KV8 = false, int NTHR = 0>
+struct FrsTiles {
+  static constexpr int BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD, EPP = KV8 ? 16 : 8, PIECES = BN * HD / EPP,
+                       NPR = NTHR ? (PIECES + NTHR - 1) / NTHR : PIECES / 256;
+  struct Regs {  // what a thread carries across a tile
+    i32x4 k[NPR], v[NPR];
+    unsigned d[NPR];
+  };
+  const unsigned short *kb, *vb;
+  unsigned short *vt0, *kt0;
+  int seq_cap, last_wg, tid, nthr;
+  const unsigned short *ks, *vs;
+  // kv head j of the cache planes kc / vc; lds, two buffers each: V^T tile [HD][VSTR] (filled transposed), K tile [BN][KSTR] (as the
+  // cache holds it).  (KV8: the kv head's int8 rows are HD bytes each -- half the f16 rows' offset -- and the scale planes lie behind
+  // the int8 planes)
+  FLASH_ROWS_SPLIT_TARGET static __device__ __forceinline__ FrsTiles of(const unsigned short* kc, const unsigned short* vc, int j, int n_kv, int seq_cap,
+                                                                        unsigned short* lds, int last_wg) {
+    const size_t rows = (size_t)j * seq_cap * HD, plane = (size_t)n_kv * seq_cap * HD, srow = (size_t)j * seq_cap * (HD / 32);
+    const int tid = threadIdx.x, nthr = NTHR ? NTHR : (int)blockDim.x;
+    if constexpr (KV8)
+      return FrsTiles{(const unsigned short*)((const signed char*)kc + rows), (const unsigned short*)((const signed char*)vc + rows),
+                      lds, lds + 2 * HD * VSTR, seq_cap, last_wg, tid, nthr,
+                      (const unsigned short*)((const signed char*)kc + plane) + srow, (const unsigned short*)((const signed char*)vc + plane) + srow};
+    else
+      return FrsTiles{kc + rows, vc + rows, lds, lds + 2 * HD * VSTR, seq_cap, last_wg, tid, nthr, nullptr, nullptr};
+  }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void fetch(int tile, int piece, i32x4& kk, i32x4& vv, unsigned& dd) const {
+    const int pr = piece / (HD / EPP), pc = piece % (HD / EPP);
+    int pos = tile * BN + pr;
+    pos = pos < seq_cap ? pos : seq_cap - 1;  // (past the cache only in its last tile; those positions are dead)
+    if constexpr (KV8) {
+      kk = *(const i32x4*)((const signed char*)kb + (size_t)pos * HD + 16 * pc);
+      vv = *(const i32x4*)((const signed char*)vb + (size_t)pos * HD + 16 * pc);
+      dd = (unsigned)ks[(size_t)pos * (HD / 32) + (pc >> 1)] | ((unsigned)vs[(size_t)pos * (HD / 32) + (pc >> 1)] << 16);
+      return;
+    }
+    kk = *(const i32x4*)(kb + (size_t)pos * HD + 8 * pc);
+    vv = *(const i32x4*)(vb + (size_t)pos * HD + 8 * pc);
+  }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void place(int buf, int tile, int piece, const i32x4& kk, const i32x4& vv, unsigned dd) const {
+    unsigned short* vt = vt0 + buf * HD * VSTR;
+    unsigned short* kt = kt0 + buf * BN * KSTR;
+    const int pr = piece / (HD / EPP), pc = piece % (HD / EPP);
+    // positions no row of the workgroup sees hold whatever the allocator or an earlier sequence left in the cache: their
+    // probabilities are exactly 0, but 0 x NaN / Inf is not -- V enters the product as zeros there (K: the scores are masked)
+    const bool live = tile * BN + pr <= last_wg;
+    if constexpr (KV8) {
+      flash_rows_place_q8<VSTR>(kt + pr * KSTR + 16 * pc, vt + (16 * pc) * VSTR + pr, kk, vv, dd, live);
+      return;
+    }
+    *(i32x4*)(kt + pr * KSTR + 8 * pc) = kk;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const unsigned w = live ? (unsigned)vv[i] : 0u;
+      vt[(8 * pc + 2 * i) * VSTR + pr] = (unsigned short)(w & 0xffffu);
+      vt[(8 * pc + 2 * i + 1) * VSTR + pr] = (unsigned short)(w >> 16);
+    }
+  }
+  // thread t has a piece in round u.  The f16 rounds of a fixed workgroup are whole; its KV8 round is not at head_dim 64 (256 pieces)
+  // and keeps the test at 128, where it is always true: k_attn_flash_rows<.., KV8> has been compiled with it from the start, and
+  // with it the compiler unrolls that kernel's tile loop twice
+  static_assert(KV8 || !NTHR || PIECES % NTHR == 0, "a fixed workgroup moves whole rounds of an f16 tile");
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ bool has(int u) const { return (NTHR && !KV8) || tid + nthr * u < PIECES; }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void issue(int tile, Regs& r) const {
+#pragma unroll
+    for (int u = 0; u < NPR; u++)
+      if (has(u)) fetch(tile, tid + nthr * u, r.k[u], r.v[u], r.d[u]);
+  }
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void commit(int buf, int tile, const Regs& r) const {
+#pragma unroll
+    for (int u = 0; u < NPR; u++)
+      if (has(u)) place(buf, tile, tid + nthr * u, r.k[u], r.v[u], r.d[u]);
+    if constexpr (NTHR == 0)
+      for (int piece = tid + nthr * NPR; piece < PIECES; piece += nthr) {  // fewer than 4 waves: the rest of the tile, fetched here
+        i32x4 kk, vv;
+        unsigned dd = 0;
+        fetch(tile, piece, kk, vv, dd);
+        place(buf, tile, piece, kk, vv, dd);
+      }
+  }
+};
+// this wave's q rows as the B operand: lane (row n, dims 32 ks + 8 g .. + 8), rounded to f16 once
+template <int HD>
+FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void flash_rows_load_q(const float* qrow, int g, f16x8 (&qb)[HD / 32]) {
+#pragma unroll
+  for (int ks = 0; ks < HD / 32; ks++) {
+    const f32x4* qp = (const f32x4*)(qrow + 32 * ks + 8 * g);
+    const f32x4 a = qp[0], b = qp[1];
+    qb[ks] = f16x8{(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3], (_Float16)b[0], (_Float16)b[1], (_Float16)b[2], (_Float16)b[3]};
+  }
+}
+// The family's 32-position step: one wave's 16 rows against the positions ca0 .. ca0 + 32, kt = their 32 rows of the K tile, vt = their
+// 32 columns of the V^T tile (rows of VSTR halfs).  Two 16-position chunks a / b: two independent S^T chains, ONE agreement on the
+// running maximum, and the second product on 16x16x32 with k-slot (g, i) = position 4 g + i of chunk a, (g, 4 + i) = the same of
+// chunk b -- for both operands.
+template <int HD, int VSTR>
+FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void flash_rows_step(const unsigned short* kt, const unsigned short* vt, const f16x8 (&qb)[HD / 32],
+                                                                        f32x4 (&acc)[HD / 16], float& m, float& lsum, int ca0, int my_last, int n, int g) {
+  constexpr int KS = HD / 32, DT = HD / 16, KSTR = HD + FLASH_ROWS_KPAD;
+  const int cb0 = ca0 + 16;
+  f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < KS; ks++) {
+    sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + n * KSTR + 32 * ks + 8 * g), qb[ks], sa, 0, 0, 0);
+    sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + (16 + n) * KSTR + 32 * ks + 8 * g), qb[ks], sb, 0, 0, 0);
+  }
+  // (head_dim 256: the V^T fragments are not to be requested above this line: 16 K fragments and 16 V fragments in flight at once are
+  // 128 VGPRs beside the 128 of accumulators, q and staging)
+  if constexpr (HD > 128) __builtin_amdgcn_sched_barrier(0);
+  float cm = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {  // causal mask (also: dead cache rows, whatever they hold)
+    if (ca0 + 4 * g + i > my_last) sa[i] = -INFINITY;
+    if (cb0 + 4 * g + i > my_last) sb[i] = -INFINITY;
+    cm = fmaxf(cm, fmaxf(sa[i], sb[i]));
+  }
+  cm = fmaxf(cm, __shfl_xor(cm, 16));
+  cm = fmaxf(cm, __shfl_xor(cm, 32));
+  // (a row may have seen nothing yet -- of its slice, or as the odd-step wave of a k_attn_flash_rows pair, which starts at position
+  // 32: m = mn = -inf, alpha = 1, p = 0)
+  const float mn = fmaxf(m, cm);
+  if (__any(mn > m)) {  // the running maximum of some row moved: rescale (rare after the first steps)
+    const float alpha = mn == -INFINITY ? 1.0f : __expf(m - mn);
+    lsum *= alpha;
+#pragma unroll
+    for (int dt = 0; dt < DT; dt++) acc[dt] = acc[dt] * alpha;
+    m = mn;
+  }
+  f16x8 pT;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const _Float16 pa = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sa[i] - m);
+    const _Float16 pb = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sb[i] - m);
+    pT[i] = pa;
+    pT[4 + i] = pb;
+    lsum += (float)pa + (float)pb;  // the normalizer sums what the second product multiplies
+  }
+#pragma unroll
+  for (int dt = 0; dt < DT; dt++) {
+    const unsigned short* vr = vt + (16 * dt + n) * VSTR + 4 * g;
+    const f16x4 va = *(const f16x4*)vr, vb2 = *(const f16x4*)(vr + 16);
+    const f16x8 vf = {va[0], va[1], va[2], va[3], vb2[0], vb2[1], vb2[2], vb2[3]};
+    acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pT, acc[dt], 0, 0, 0);
+  }
+}
 template <int HD, bool KV8 = false>
 __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict__ q, const unsigned short* __restrict__ kc,
                                                          const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
                                                          float* __restrict__ out, int n_heads, int n_kv, int seq_cap, int B) {
-  constexpr int KS = HD / 32, DT = HD / 16, BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD, NP = KV8 ? 1 : HD / 64;
-  constexpr int PPR = HD / 16, NB = HD / 32;  // KV8: pieces and scales of a cache row; a tile is BN * PPR <= 512 pieces, one per thread
+  typedef FrsTiles<HD, KV8, 512> Tiles;  // (KV8: a tile is at most 512 pieces, one per thread)
+  constexpr int DT = HD / 16, BN = Tiles::BN, VSTR = Tiles::VSTR, KSTR = Tiles::KSTR;
   static_assert(BN == 64, "a fill is two 32-position steps: one per wave of a pair");
-  // LDS, two buffers each: V^T tile [HD][VSTR] (filled transposed), K tile [BN][KSTR] (as the cache holds it)
   extern __shared__ __attribute__((aligned(16))) unsigned short fr_lds[];
-  unsigned short* vt0 = fr_lds;
-  unsigned short* kt0 = fr_lds + 2 * HD * VSTR;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = lane & 15, g = lane >> 4;
   const int head = blockIdx.y, j = head / (n_heads / n_kv);
@@ -1557,16 +1710,8 @@ __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict
   const int rw = wave & 3, par = wave >> 2;
   const int row_wg = blockIdx.x * 64, row_w = row_wg + rw * 16;
   const int row = row_w + n < B ? row_w + n : B - 1;  // (rows past the batch recompute the last row; never stored)
-  // this wave's q rows as the B operand: lane (row n, dims 32 ks + 8 g .. + 8)
-  f16x8 qb[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ks++) {
-    const f32x4* qp = (const f32x4*)(q + ((size_t)row * n_heads + head) * HD + 32 * ks + 8 * g);
-    const f32x4 a = qp[0], b = qp[1];
-    qb[ks] = f16x8{(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3], (_Float16)b[0], (_Float16)b[1], (_Float16)b[2], (_Float16)b[3]};
-  }
-  const unsigned short* kb = kc + (size_t)j * seq_cap * HD;
-  const unsigned short* vb = vc + (size_t)j * seq_cap * HD;
+  f16x8 qb[HD / 32];
+  flash_rows_load_q<HD>(q + ((size_t)row * n_heads + head) * HD, g, qb);
   const int last_wg = pos0 + (row_wg + 63 < B ? row_wg + 63 : B - 1);  // last cached position any row of the workgroup sees
   const int last_w = pos0 + (row_w + 15 < B ? row_w + 15 : B - 1);     // ... any row of this wave
   const int my_last = pos0 + row;                                      // ... this lane's row
@@ -1575,118 +1720,19 @@ __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict
 #pragma unroll
   for (int dt = 0; dt < DT; dt++) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, lsum = 0.f;
-  // staging: thread t moves NP 16-byte pieces of the K tile and of the V tile per fill (piece = 8 dims of one position); a whole
-  // tile of compute lies between the request and the commit
-  i32x4 vreg[NP], kreg[NP];
-  unsigned dreg = 0;  // KV8: the piece's K scale | V scale << 16
-  const signed char* kq = (const signed char*)kc + (size_t)j * seq_cap * HD;
-  const signed char* vq = (const signed char*)vc + (size_t)j * seq_cap * HD;
-  const unsigned short* ks = (const unsigned short*)((const signed char*)kc + (size_t)n_kv * seq_cap * HD) + (size_t)j * seq_cap * NB;
-  const unsigned short* vs = (const unsigned short*)((const signed char*)vc + (size_t)n_kv * seq_cap * HD) + (size_t)j * seq_cap * NB;
-  auto issue = [&](int tile) {
-    if constexpr (KV8) {
-      if (tid < BN * PPR) {
-        const int pr = tid / PPR, pc = tid % PPR;
-        int pos = tile * BN + pr;
-        pos = pos < seq_cap ? pos : seq_cap - 1;
-        kreg[0] = *(const i32x4*)(kq + (size_t)pos * HD + 16 * pc);
-        vreg[0] = *(const i32x4*)(vq + (size_t)pos * HD + 16 * pc);
-        dreg = (unsigned)ks[(size_t)pos * NB + (pc >> 1)] | ((unsigned)vs[(size_t)pos * NB + (pc >> 1)] << 16);
-      }
-      return;
-    }
-#pragma unroll
-    for (int u = 0; u < NP; u++) {
-      const int piece = tid + 512 * u, pr = piece / (HD / 8), pc = piece % (HD / 8);
-      int pos = tile * BN + pr;
-      pos = pos < seq_cap ? pos : seq_cap - 1;  // (past the cache only in its last tile; those positions are dead)
-      kreg[u] = *(const i32x4*)(kb + (size_t)pos * HD + 8 * pc);
-      vreg[u] = *(const i32x4*)(vb + (size_t)pos * HD + 8 * pc);
-    }
-  };
-  auto commit = [&](int buf, int tile) {
-    unsigned short* vt = vt0 + buf * HD * VSTR;
-    unsigned short* kt = kt0 + buf * BN * KSTR;
-    if constexpr (KV8) {
-      if (tid < BN * PPR) {
-        const int pr = tid / PPR, pc = tid % PPR;
-        flash_rows_place_q8<VSTR>(kt + pr * KSTR + 16 * pc, vt + (16 * pc) * VSTR + pr, kreg[0], vreg[0], dreg, tile * BN + pr <= last_wg);
-      }
-      return;
-    }
-#pragma unroll
-    for (int u = 0; u < NP; u++) {
-      const int piece = tid + 512 * u, pr = piece / (HD / 8), pc = piece % (HD / 8);
-      // positions no row of the workgroup sees hold whatever the allocator or an earlier sequence left in the cache: their
-      // probabilities are exactly 0, but 0 x NaN / Inf is not -- V enters the product as zeros there (K: the scores are masked)
-      const bool live = tile * BN + pr <= last_wg;
-      *(i32x4*)(kt + pr * KSTR + 8 * pc) = kreg[u];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const unsigned w = live ? (unsigned)vreg[u][i] : 0u;
-        vt[(8 * pc + 2 * i) * VSTR + pr] = (unsigned short)(w & 0xffffu);
-        vt[(8 * pc + 2 * i + 1) * VSTR + pr] = (unsigned short)(w >> 16);
-      }
-    }
-  };
-  issue(0);
-  commit(0, 0);
+  const Tiles tl = Tiles::of(kc, vc, j, n_kv, seq_cap, fr_lds, last_wg);
+  typename Tiles::Regs r;
+  tl.issue(0, r);
+  tl.commit(0, 0, r);
   __syncthreads();
+  // (this kernel's own walk, not flash_rows_walk's: a wave takes every other step and the pair's states meet below)
   for (int tile = 0; tile < ntiles; tile++) {
     const int buf = tile & 1;
-    const unsigned short* vt = vt0 + buf * HD * VSTR;
-    const unsigned short* kt = kt0 + buf * BN * KSTR;
-    if (tile + 1 < ntiles) issue(tile + 1);
-    {
-      // 32 positions per step as two 16-position chunks a / b: two independent S^T chains, ONE agreement on the running maximum, and
-      // the second product on 16x16x32 with k-slot (g, i) = position 4 g + i of chunk a, (g, 4 + i) = the same of chunk b -- for
-      // both operands.  This wave's step of the tile: c2 = par.
-      const int c2 = par;
-      const int ca0 = tile * BN + 32 * c2, cb0 = ca0 + 16;
-      if (ca0 <= last_w) {  // wave-uniform: some row of this wave sees the step
-      f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < KS; ks++) {
-        sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + (32 * c2 + n) * KSTR + 32 * ks + 8 * g), qb[ks], sa, 0, 0, 0);
-        sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + (32 * c2 + 16 + n) * KSTR + 32 * ks + 8 * g), qb[ks], sb, 0, 0, 0);
-      }
-      float cm = -INFINITY;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {  // causal mask (also: dead cache rows, whatever they hold)
-        if (ca0 + 4 * g + i > my_last) sa[i] = -INFINITY;
-        if (cb0 + 4 * g + i > my_last) sb[i] = -INFINITY;
-        cm = fmaxf(cm, fmaxf(sa[i], sb[i]));
-      }
-      cm = fmaxf(cm, __shfl_xor(cm, 16));
-      cm = fmaxf(cm, __shfl_xor(cm, 32));
-      // (a row may have seen nothing yet -- the odd-step wave of a pair starts at position 32: m = mn = -inf, alpha = 1, p = 0)
-      const float mn = fmaxf(m, cm);
-      if (__any(mn > m)) {  // the running maximum of some row moved: rescale (rare after the first steps)
-        const float alpha = mn == -INFINITY ? 1.0f : __expf(m - mn);
-        lsum *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < DT; dt++) acc[dt] = acc[dt] * alpha;
-        m = mn;
-      }
-      f16x8 pT;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const _Float16 pa = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sa[i] - m);
-        const _Float16 pb = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sb[i] - m);
-        pT[i] = pa;
-        pT[4 + i] = pb;
-        lsum += (float)pa + (float)pb;  // the normalizer sums what the second product multiplies
-      }
-#pragma unroll
-      for (int dt = 0; dt < DT; dt++) {
-        const unsigned short* vr = vt + (16 * dt + n) * VSTR + 32 * c2 + 4 * g;
-        const f16x4 va = *(const f16x4*)vr, vb2 = *(const f16x4*)(vr + 16);
-        const f16x8 vf = {va[0], va[1], va[2], va[3], vb2[0], vb2[1], vb2[2], vb2[3]};
-        acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pT, acc[dt], 0, 0, 0);
-      }
-      }
-    }
-    if (tile + 1 < ntiles) commit(buf ^ 1, tile + 1);  // those buffers were last read one tile ago (barrier below)
+    if (tile + 1 < ntiles) tl.issue(tile + 1, r);
+    const int ca0 = tile * BN + 32 * par;  // this wave's step of the tile
+    if (ca0 <= last_w)                     // wave-uniform: some row of this wave sees the step
+      flash_rows_step<HD, VSTR>(tl.kt0 + (buf * BN + 32 * par) * KSTR, tl.vt0 + buf * HD * VSTR + 32 * par, qb, acc, m, lsum, ca0, my_last, n, g);
+    if (tile + 1 < ntiles) tl.commit(buf ^ 1, tile + 1, r);  // those buffers were last read one tile ago (barrier below)
     __syncthreads();
   }
   lsum += __shfl_xor(lsum, 16);
@@ -1735,13 +1781,11 @@ __global__ __launch_bounds__(512) void k_attn_flash_rows(const float* __restrict
 //               merge reads written by this launch
 //   k_attn_flash_rows_merge: per (row, head) M = max m_s, out = sum e^(m_s - M) O_s / sum e^(m_s - M) l_s, a slice with m_s = -inf
 //               weighing exactly 0 (slice 0 holds position 0, which every row sees: M is finite)
-// Staging as in k_attn_flash_rows (two buffers, loads requested a tile ahead, one barrier per tile; V zeroed at positions no row of the
-// workgroup sees, K left to the mask, reads past the cache clamped), its loops strided by the launched block size: a thread carries up
-// to PIECES / 256 pieces of K and of V across a tile in registers, which covers a tile from 4 waves on; a workgroup of fewer waves
-// fetches the rest at commit time, without the overlap.
-// Budget: 163 VGPRs at head_dim 128 (32 accumulator + 16 q + 32 staging, the two steps of a tile unrolled side by side), 111 at 64, no
-// scratch: a workgroup of 8 waves is 2 waves per SIMD, so registers allow one workgroup of 8 waves per CU at 128 (three waves per SIMD)
-// and two at 64; LDS flash_rows_lds_bytes = 69632 bytes (head_dim 64: 35840), which allows two.  The grid targets two workgroups per CU
+// Staging is k_attn_flash_rows' (FrsTiles above: two buffers, loads requested a tile ahead, one barrier per tile; V zeroed at positions
+// no row of the workgroup sees, K left to the mask, reads past the cache clamped), its loops strided by the launched block size.
+// Budget: 151 VGPRs at head_dim 128 (32 accumulator + 16 q + 32 staging, the two steps of a tile unrolled side by side), 95 at 64, no
+// scratch: a workgroup of 8 waves is 2 waves per SIMD, so registers allow one workgroup of 8 waves per CU at 128 (three waves per SIMD:
+// at most 168 registers) and two at 64; LDS flash_rows_lds_bytes = 69632 bytes (head_dim 64: 35840), which allows two.  The grid targets two workgroups per CU
 // and is capped at 32 slices: 256 workgroups for 32 rows of the 8B shape.
 struct FlashRowsSplitGeom {
   int nfrag, nwg, fpw;  // fragments of a kv head, workgroups they take, fragments (waves) per workgroup
@@ -1754,192 +1798,98 @@ __host__ __device__ inline FlashRowsSplitGeom flash_rows_split_geom(int G, int r
 __host__ __device__ inline size_t flash_rows_part_floats(int slices, int rows, int n_heads, int hd) {
   return (size_t)slices * rows * n_heads * (hd + 2);
 }
-// (both kernels keep their f32 vector arithmetic -- the accumulator rescale -- on the one-value VALU forms)
-#define FLASH_ROWS_SPLIT_TARGET __attribute__((target("no-packed-fp32-ops")))
-// the staging of one workgroup's K / V tiles: global -> registers (issue) -> LDS (commit)
-// (KV8: a piece is 16 int8 of a position and carries its two scales, `dd` = K scale | V scale << 16; ks / vs = the kv head's scale rows)
-template <int HD, bool KV8 = false>
-struct FrsTiles {
-  static constexpr int BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD, EPP = KV8 ? 16 : 8, PIECES = BN * HD / EPP,
-                       NPR = PIECES / 256;
-  const unsigned short *kb, *vb;
-  unsigned short *vt0, *kt0;
-  int seq_cap, last_wg, tid, nthr;
-  const unsigned short *ks, *vs;
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void fetch(int tile, int piece, i32x4& kk, i32x4& vv, unsigned& dd) const {
-    const int pr = piece / (HD / EPP), pc = piece % (HD / EPP);
-    int pos = tile * BN + pr;
-    pos = pos < seq_cap ? pos : seq_cap - 1;  // (past the cache only in its last tile; those positions are dead)
-    if constexpr (KV8) {
-      kk = *(const i32x4*)((const signed char*)kb + (size_t)pos * HD + 16 * pc);
-      vv = *(const i32x4*)((const signed char*)vb + (size_t)pos * HD + 16 * pc);
-      dd = (unsigned)ks[(size_t)pos * (HD / 32) + (pc >> 1)] | ((unsigned)vs[(size_t)pos * (HD / 32) + (pc >> 1)] << 16);
-      return;
-    }
-    kk = *(const i32x4*)(kb + (size_t)pos * HD + 8 * pc);
-    vv = *(const i32x4*)(vb + (size_t)pos * HD + 8 * pc);
-  }
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void place(int buf, int tile, int piece, const i32x4& kk, const i32x4& vv, unsigned dd) const {
-    unsigned short* vt = vt0 + buf * HD * VSTR;
-    unsigned short* kt = kt0 + buf * BN * KSTR;
-    const int pr = piece / (HD / EPP), pc = piece % (HD / EPP);
-    // positions no row of the workgroup sees hold whatever the allocator or an earlier sequence left in the cache: their
-    // probabilities are exactly 0, but 0 x NaN / Inf is not -- V enters the product as zeros there (K: the scores are masked)
-    const bool live = tile * BN + pr <= last_wg;
-    if constexpr (KV8) {
-      flash_rows_place_q8<VSTR>(kt + pr * KSTR + 16 * pc, vt + (16 * pc) * VSTR + pr, kk, vv, dd, live);
-      return;
-    }
-    *(i32x4*)(kt + pr * KSTR + 8 * pc) = kk;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const unsigned w = live ? (unsigned)vv[i] : 0u;
-      vt[(8 * pc + 2 * i) * VSTR + pr] = (unsigned short)(w & 0xffffu);
-      vt[(8 * pc + 2 * i + 1) * VSTR + pr] = (unsigned short)(w >> 16);
-    }
-  }
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void issue(int tile, i32x4 (&kreg)[NPR], i32x4 (&vreg)[NPR], unsigned (&dreg)[NPR]) const {
-#pragma unroll
-    for (int u = 0; u < NPR; u++)
-      if (tid + nthr * u < PIECES) fetch(tile, tid + nthr * u, kreg[u], vreg[u], dreg[u]);
-  }
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void commit(int buf, int tile, const i32x4 (&kreg)[NPR], const i32x4 (&vreg)[NPR],
-                                                                 const unsigned (&dreg)[NPR]) const {
-#pragma unroll
-    for (int u = 0; u < NPR; u++)
-      if (tid + nthr * u < PIECES) place(buf, tile, tid + nthr * u, kreg[u], vreg[u], dreg[u]);
-    for (int piece = tid + nthr * NPR; piece < PIECES; piece += nthr) {  // fewer than 4 waves: the rest of the tile, fetched here
-      i32x4 kk, vv;
-      unsigned dd = 0;
-      fetch(tile, piece, kk, vv, dd);
-      place(buf, tile, piece, kk, vv, dd);
-    }
-  }
+// What a wave of a split workgroup (blockIdx = {workgroup of the kv head's fragments, kv head, slice}) works on, in tiles of BN positions
+struct FlashRowsSplitWork {
+  bool any, owner;             // the workgroup has a fragment at all; this wave has one of its own (otherwise it stages tiles and computes nothing)
+  int head, row_w;             // the wave's fragment: 16 rows from row_w of `head`
+  int last_wg;                 // last cached position any row of the workgroup sees
+  int t0, t1;                  // the workgroup's tiles of the slice (t1 <= t0: it sees nothing of the slice)
 };
-template <int HD, bool KV8 = false>
-FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(512) void k_attn_flash_rows_split(const float* __restrict__ q, const unsigned short* __restrict__ kc,
-                                                               const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
-                                                               float* __restrict__ part, int n_heads, int n_kv, int seq_cap, int B, int S) {
-  constexpr int KS = HD / 32, DT = HD / 16, BN = FLASH_ROWS_BN, VSTR = FLASH_ROWS_VSTR, KSTR = HD + FLASH_ROWS_KPAD;
-  constexpr int NPR = FrsTiles<HD, KV8>::NPR;  // 16-byte pieces of a K (or V) tile in registers per thread
-  extern __shared__ __attribute__((aligned(16))) unsigned short fr_lds[];
-  unsigned short* vt0 = fr_lds;
-  unsigned short* kt0 = fr_lds + 2 * HD * VSTR;
-  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6;
-  const int n = lane & 15, g = lane >> 4;
-  const int G = n_heads / n_kv, j = blockIdx.y, s = blockIdx.z;
-  const FlashRowsSplitGeom ge = flash_rows_split_geom(G, B);
-  const int pos0 = *pos_d;
-  // this wave's fragment (a wave past the kv head's last fragment stages tiles and computes nothing)
+template <int BN>
+FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ FlashRowsSplitWork flash_rows_split_work(int G, int B, int S, int pos0, int frag_cap, int wave) {
+  const int j = blockIdx.y, s = blockIdx.z;
+  const FlashRowsSplitGeom ge = flash_rows_split_geom(G, B, frag_cap);
   const int f0 = blockIdx.x * ge.fpw, f1 = f0 + ge.fpw < ge.nfrag ? f0 + ge.fpw : ge.nfrag;
-  if (f0 >= f1) return;  // (workgroup-uniform; flash_rows_split_geom leaves no workgroup empty)
   const bool owner = f0 + wave < f1;
   const int f = owner ? f0 + wave : f1 - 1;
-  const int head = j * G + f % G, row_w = (f / G) * 16;
-  const int row = row_w + n < B ? row_w + n : B - 1;  // (rows past the batch recompute the last row; never stored)
-  f16x8 qb[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ks++) {
-    const f32x4* qp = (const f32x4*)(q + ((size_t)row * n_heads + head) * HD + 32 * ks + 8 * g);
-    const f32x4 a = qp[0], b = qp[1];
-    qb[ks] = f16x8{(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3], (_Float16)b[0], (_Float16)b[1], (_Float16)b[2], (_Float16)b[3]};
-  }
-  const unsigned short* kb = kc + (size_t)j * seq_cap * HD;
-  const unsigned short* vb = vc + (size_t)j * seq_cap * HD;
-  const int rlast_wg = ((f1 - 1) / G) * 16 + 15;                     // the workgroup's fragments are row-block major: its last one's rows
-  const int last_wg = pos0 + (rlast_wg < B ? rlast_wg : B - 1);      // last cached position any row of the workgroup sees
-  const int last_w = pos0 + (row_w + 15 < B ? row_w + 15 : B - 1);   // ... any row of this wave
-  const int my_last = pos0 + row;                                    // ... this lane's row
-  const int NT = (pos0 + B - 1) / BN + 1;                            // tiles of the pass
+  const int rlast_wg = ((f1 - 1) / G) * 16 + 15;                 // the workgroup's fragments are row-block major: its last one's rows
+  const int last_wg = pos0 + (rlast_wg < B ? rlast_wg : B - 1);
+  const int NT = (pos0 + B - 1) / BN + 1;                        // tiles of the pass (at least as many as the 64-position tiles S is capped by)
   const int t0 = (int)((long long)s * NT / S), t1s = (int)((long long)(s + 1) * NT / S);
-  const int t1 = t1s < last_wg / BN + 1 ? t1s : last_wg / BN + 1;   // (t1 <= t0: the workgroup sees nothing of the slice)
-  f32x4 acc[DT];
+  const int t1 = t1s < last_wg / BN + 1 ? t1s : last_wg / BN + 1;
+  return FlashRowsSplitWork{f0 < f1, owner, j * G + f % G, (f / G) * 16, last_wg, t0, t1};
+}
+// One fragment's partial of slice s: the unnormalised O^T (C layout: acc[dt][i] = O^T[dim 16 dt + 4 g + i][row n]), then {m, l} from
+// lane group 0
+template <int HD>
+FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void flash_rows_store_partial(float* part, const f32x4 (&acc)[HD / 16], float m, float lsum, int S,
+                                                                                 int B, int n_heads, int s, int row, int head, int g) {
+  const size_t rec = ((size_t)s * B + row) * n_heads + head;
+  float* o = part + rec * HD;
+#pragma unroll
+  for (int dt = 0; dt < HD / 16; dt++) *(f32x4*)(o + 16 * dt + 4 * g) = acc[dt];
+  if (g == 0) {
+    float* ml = part + (size_t)S * B * n_heads * HD + rec * 2;
+    ml[0] = m;
+    ml[1] = lsum;
+  }
+}
+// One fragment (16 rows from row_w of `head`; `owner` false: the wave only stages) over the workgroup's tiles t0 .. t1 of `tl` (FrsTiles
+// or FrwTiles): the loop of every kernel in which a wave owns its rows from the first tile to the last -- two buffers, the next tile's
+// loads requested before this one is multiplied, one barrier per tile.  Leaves the unnormalised O^T in acc (C layout), the row's m,
+// and its l summed over the lane groups.
+template <int HD, class Tiles>
+FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void flash_rows_walk(const float* __restrict__ q, const Tiles& tl, int n_heads, int B, int pos0, int head,
+                                                                        int row_w, bool owner, int t0, int t1, f32x4 (&acc)[HD / 16], float& m,
+                                                                        float& lsum) {
+  constexpr int DT = HD / 16, BN = Tiles::BN, VSTR = Tiles::VSTR, KSTR = Tiles::KSTR;
+  const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
+  const int row = row_w + n < B ? row_w + n : B - 1;  // (rows past the batch recompute the last row; never stored)
+  f16x8 qb[HD / 32];
+  flash_rows_load_q<HD>(q + ((size_t)row * n_heads + head) * HD, g, qb);
+  const int last_w = pos0 + (row_w + 15 < B ? row_w + 15 : B - 1);  // last cached position any row of this wave sees
+  const int my_last = pos0 + row;                                   // ... this lane's row
 #pragma unroll
   for (int dt = 0; dt < DT; dt++) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m = -INFINITY, lsum = 0.f;
-  i32x4 vreg[NPR], kreg[NPR];
-  unsigned dreg[NPR];
-  // (KV8: kb / vb are the kv head's int8 rows -- HD bytes each, half the f16 rows' offset -- and the scale planes lie behind the int8 planes)
-  const size_t plane = (size_t)n_kv * seq_cap * HD, srow = (size_t)j * seq_cap * (HD / 32);
-  const FrsTiles<HD, KV8> tl{KV8 ? (const unsigned short*)((const signed char*)kc + (size_t)j * seq_cap * HD) : kb,
-                             KV8 ? (const unsigned short*)((const signed char*)vc + (size_t)j * seq_cap * HD) : vb,
-                             vt0, kt0, seq_cap, last_wg, tid, nthr,
-                             KV8 ? (const unsigned short*)((const signed char*)kc + plane) + srow : nullptr,
-                             KV8 ? (const unsigned short*)((const signed char*)vc + plane) + srow : nullptr};
+  m = -INFINITY, lsum = 0.f;
+  typename Tiles::Regs r;
   if (t0 < t1) {
-    tl.issue(t0, kreg, vreg, dreg);
-    tl.commit(0, t0, kreg, vreg, dreg);
+    tl.issue(t0, r);
+    tl.commit(0, t0, r);
   }
   __syncthreads();
   for (int tile = t0; tile < t1; tile++) {
     const int buf = (tile - t0) & 1;
-    const unsigned short* vt = vt0 + buf * HD * VSTR;
-    const unsigned short* kt = kt0 + buf * BN * KSTR;
-    if (tile + 1 < t1) tl.issue(tile + 1, kreg, vreg, dreg);
+    const unsigned short* vt = tl.vt0 + buf * HD * VSTR;
+    const unsigned short* kt = tl.kt0 + buf * BN * KSTR;
+    if (tile + 1 < t1) tl.issue(tile + 1, r);
 #pragma unroll
-    for (int c2 = 0; c2 < 2; c2++) {
-      // k_attn_flash_rows' 32-position step: two 16-position chunks a / b, two independent S^T chains, one agreement on the running
-      // maximum, the second product on 16x16x32 with k-slot (g, i) = position 4 g + i of chunk a, (g, 4 + i) = the same of chunk b
-      const int ca0 = tile * BN + 32 * c2, cb0 = ca0 + 16;
-      if (owner && ca0 <= last_w) {  // wave-uniform: some row of this wave sees the step
-        f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) {
-          sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + (32 * c2 + n) * KSTR + 32 * ks + 8 * g), qb[ks], sa, 0, 0, 0);
-          sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + (32 * c2 + 16 + n) * KSTR + 32 * ks + 8 * g), qb[ks], sb, 0, 0, 0);
-        }
-        float cm = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {  // causal mask (also: dead cache rows, whatever they hold)
-          if (ca0 + 4 * g + i > my_last) sa[i] = -INFINITY;
-          if (cb0 + 4 * g + i > my_last) sb[i] = -INFINITY;
-          cm = fmaxf(cm, fmaxf(sa[i], sb[i]));
-        }
-        cm = fmaxf(cm, __shfl_xor(cm, 16));
-        cm = fmaxf(cm, __shfl_xor(cm, 32));
-        // (a row that has seen nothing of the slice yet: m = mn = -inf, alpha = 1, p = 0)
-        const float mn = fmaxf(m, cm);
-        if (__any(mn > m)) {  // the running maximum of some row moved: rescale (rare after the first steps)
-          const float alpha = mn == -INFINITY ? 1.0f : __expf(m - mn);
-          lsum *= alpha;
-#pragma unroll
-          for (int dt = 0; dt < DT; dt++) acc[dt] = acc[dt] * alpha;
-          m = mn;
-        }
-        f16x8 pT;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const _Float16 pa = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sa[i] - m);
-          const _Float16 pb = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sb[i] - m);
-          pT[i] = pa;
-          pT[4 + i] = pb;
-          lsum += (float)pa + (float)pb;  // the normalizer sums what the second product multiplies
-        }
-#pragma unroll
-        for (int dt = 0; dt < DT; dt++) {
-          const unsigned short* vr = vt + (16 * dt + n) * VSTR + 32 * c2 + 4 * g;
-          const f16x4 va = *(const f16x4*)vr, vb2 = *(const f16x4*)(vr + 16);
-          const f16x8 vf = {va[0], va[1], va[2], va[3], vb2[0], vb2[1], vb2[2], vb2[3]};
-          acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pT, acc[dt], 0, 0, 0);
-        }
-      }
+    for (int c2 = 0; c2 < BN / 32; c2++) {  // the tile's 32-position steps
+      const int ca0 = tile * BN + 32 * c2;
+      if (owner && ca0 <= last_w)  // wave-uniform: some row of this wave sees the step
+        flash_rows_step<HD, VSTR>(kt + 32 * c2 * KSTR, vt + 32 * c2, qb, acc, m, lsum, ca0, my_last, n, g);
     }
-    if (tile + 1 < t1) tl.commit(buf ^ 1, tile + 1, kreg, vreg, dreg);  // those buffers were last read one tile ago (barrier below)
+    if (tile + 1 < t1) tl.commit(buf ^ 1, tile + 1, r);  // those buffers were last read one tile ago (barrier below)
     __syncthreads();
   }
   lsum += __shfl_xor(lsum, 16);
   lsum += __shfl_xor(lsum, 32);
-  if (owner && row_w + n < B) {  // C layout: acc[dt][i] = O^T[dim 16 dt + 4 g + i][row n]
-    const size_t rec = ((size_t)s * B + row_w + n) * n_heads + head;
-    float* o = part + rec * HD;
-#pragma unroll
-    for (int dt = 0; dt < DT; dt++) *(f32x4*)(o + 16 * dt + 4 * g) = acc[dt];
-    if (g == 0) {
-      float* ml = part + (size_t)S * B * n_heads * HD + rec * 2;
-      ml[0] = m;
-      ml[1] = lsum;
-    }
-  }
+}
+template <int HD, bool KV8 = false>
+FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(512) void k_attn_flash_rows_split(const float* __restrict__ q, const unsigned short* __restrict__ kc,
+                                                               const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
+                                                               float* __restrict__ part, int n_heads, int n_kv, int seq_cap, int B, int S) {
+  typedef FrsTiles<HD, KV8> Tiles;
+  extern __shared__ __attribute__((aligned(16))) unsigned short fr_lds[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+  const int pos0 = *pos_d;
+  const FlashRowsSplitWork w = flash_rows_split_work<Tiles::BN>(n_heads / n_kv, B, S, pos0, flash_rows_frag_cap(HD), wave);
+  if (!w.any) return;  // (workgroup-uniform; flash_rows_split_geom leaves no workgroup empty)
+  f32x4 acc[HD / 16];
+  float m, lsum;
+  flash_rows_walk<HD>(q, Tiles::of(kc, vc, blockIdx.y, n_kv, seq_cap, fr_lds, w.last_wg), n_heads, B, pos0, w.head, w.row_w, w.owner, w.t0, w.t1, acc,
+                      m, lsum);
+  if (w.owner && w.row_w + n < B) flash_rows_store_partial<HD>(part, acc, m, lsum, S, B, n_heads, blockIdx.z, w.row_w + n, w.head, g);
 }
 
 // The merge of k_attn_flash_rows_split's partials: one workgroup per (row, head), one thread per output dim; the decode merge's
@@ -1977,7 +1927,7 @@ FLASH_ROWS_SPLIT_TARGET __global__ __launch_bounds__(HD) void k_attn_flash_rows_
 //               swap of register halves), another 16 banks on: every store of a wave covers the 64 banks once.  The fragment reads
 //               (lane = dim n, positions 4 g .. + 4: 8 bytes at bank 20 n + 2 g) fall on every bank pair exactly twice, the floor.
 //   K tile    = [32][HD + 8] as the cache holds it, 16-byte stores and fragment reads as in the family
-// One tile body (frw_step) and one staging struct (FrwTiles) serve both forms; the one-launch kernel is workgroup = (64 rows, head),
+// The family's step and walk (flash_rows_step, flash_rows_walk) over one staging struct (FrwTiles) serve both forms; the one-launch kernel is workgroup = (64 rows, head),
 // the split form spreads a kv head's fragments over workgroups of at most 4 (flash_rows_split_geom with that cap) and writes the
 // family's partials, which k_attn_flash_rows_merge<256> merges.
 template <int HD>
@@ -1987,9 +1937,18 @@ struct FrwTiles {
   static_assert(BN == 32 && PC == 32, "a wave is 2 K rows of 32 pieces, or 4 piece columns of the 16 V position pairs");
   // A workgroup is whole waves, so thread t keeps its K piece column t % 32 and its V position pair t % 16 from fill to fill and
   // steps through K rows t / 32 + (nthr / 32) u and V piece columns t / 16 + (nthr / 16) u: one address each, scalar strides.
+  struct Regs {  // what a thread carries across a tile
+    i32x4 k[NK], v[2 * NV];
+  };
   const unsigned short *kb, *vb;
   unsigned short *vt0, *kt0;
   int seq_cap, last_wg, tid, nthr;
+  // kv head j of the f16 cache; lds as FrsTiles lays it out
+  FLASH_ROWS_SPLIT_TARGET static __device__ __forceinline__ FrwTiles of(const unsigned short* kc, const unsigned short* vc, int j, int seq_cap,
+                                                                        unsigned short* lds, int last_wg) {
+    const size_t rows = (size_t)j * seq_cap * HD;
+    return FrwTiles{kc + rows, vc + rows, lds, lds + 2 * HD * VSTR, seq_cap, last_wg, (int)threadIdx.x, (int)blockDim.x};
+  }
   FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ int clamp(int pos) const {
     return pos < seq_cap ? pos : seq_cap - 1;  // (past the cache only in its last tile; those positions are dead)
   }
@@ -2028,22 +1987,22 @@ struct FrwTiles {
     }
   }
   // global -> registers for what a workgroup of NT threads carries across a tile ...
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void issue(int tile, i32x4 (&kreg)[NK], i32x4 (&vreg)[2 * NV]) const {
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void issue(int tile, Regs& r) const {
 #pragma unroll
     for (int u = 0; u < NK; u++)
-      if (tid / PC + nthr / PC * u < BN) fetch_k(tile, tid / PC + nthr / PC * u, kreg[u]);
+      if (tid / PC + nthr / PC * u < BN) fetch_k(tile, tid / PC + nthr / PC * u, r.k[u]);
 #pragma unroll
     for (int u = 0; u < NV; u++)
-      if (tid / 16 + nthr / 16 * u < PC) fetch_v(tile, tid / 16 + nthr / 16 * u, vreg[2 * u], vreg[2 * u + 1]);
+      if (tid / 16 + nthr / 16 * u < PC) fetch_v(tile, tid / 16 + nthr / 16 * u, r.v[2 * u], r.v[2 * u + 1]);
   }
   // ... registers -> LDS; a workgroup of fewer waves fetches the rest of the tile here, without the overlap
-  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void commit(int buf, int tile, const i32x4 (&kreg)[NK], const i32x4 (&vreg)[2 * NV]) const {
+  FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void commit(int buf, int tile, const Regs& r) const {
 #pragma unroll
     for (int u = 0; u < NK; u++)
-      if (tid / PC + nthr / PC * u < BN) place_k(buf, tid / PC + nthr / PC * u, kreg[u]);
+      if (tid / PC + nthr / PC * u < BN) place_k(buf, tid / PC + nthr / PC * u, r.k[u]);
 #pragma unroll
     for (int u = 0; u < NV; u++)
-      if (tid / 16 + nthr / 16 * u < PC) place_v(buf, tile, tid / 16 + nthr / 16 * u, vreg[2 * u], vreg[2 * u + 1]);
+      if (tid / 16 + nthr / 16 * u < PC) place_v(buf, tile, tid / 16 + nthr / 16 * u, r.v[2 * u], r.v[2 * u + 1]);
     for (int pr = tid / PC + nthr / PC * NK; pr < BN; pr += nthr / PC) {
       i32x4 kk;
       fetch_k(tile, pr, kk);
@@ -2056,105 +2015,6 @@ struct FrwTiles {
     }
   }
 };
-// this wave's q rows as the B operand: lane (row n, dims 32 ks + 8 g .. + 8), rounded to f16 once
-template <int HD>
-FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void frw_load_q(const float* qrow, int g, f16x8 (&qb)[HD / 32]) {
-#pragma unroll
-  for (int ks = 0; ks < HD / 32; ks++) {
-    const f32x4* qp = (const f32x4*)(qrow + 32 * ks + 8 * g);
-    const f32x4 a = qp[0], b = qp[1];
-    qb[ks] = f16x8{(_Float16)a[0], (_Float16)a[1], (_Float16)a[2], (_Float16)a[3], (_Float16)b[0], (_Float16)b[1], (_Float16)b[2], (_Float16)b[3]};
-  }
-}
-// The tile body of both forms: one wave's 16 rows against the 32 positions from ca0 (kt / vt: that tile's buffers).  k_attn_flash_rows'
-// 32-position step: two 16-position chunks a / b, two independent S^T chains, one agreement on the running maximum, the second product
-// on 16x16x32 with k-slot (g, i) = position 4 g + i of chunk a, (g, 4 + i) = the same of chunk b.
-template <int HD>
-FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void frw_step(const unsigned short* kt, const unsigned short* vt, const f16x8 (&qb)[HD / 32],
-                                                                 f32x4 (&acc)[HD / 16], float& m, float& lsum, int ca0, int my_last, int n, int g) {
-  constexpr int KS = HD / 32, DT = HD / 16, VSTR = FLASH_ROWS_W_VSTR, KSTR = HD + FLASH_ROWS_KPAD;
-  const int cb0 = ca0 + 16;
-  f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < KS; ks++) {
-    sa = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + n * KSTR + 32 * ks + 8 * g), qb[ks], sa, 0, 0, 0);
-    sb = __builtin_amdgcn_mfma_f32_16x16x32_f16(*(const f16x8*)(kt + (16 + n) * KSTR + 32 * ks + 8 * g), qb[ks], sb, 0, 0, 0);
-  }
-  // (the V^T fragments are not to be requested above this line: 16 K fragments and 16 V fragments in flight at once are 128 VGPRs
-  // beside the 128 of accumulators, q and staging)
-  __builtin_amdgcn_sched_barrier(0);
-  float cm = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {  // causal mask (also: dead cache rows, whatever they hold)
-    if (ca0 + 4 * g + i > my_last) sa[i] = -INFINITY;
-    if (cb0 + 4 * g + i > my_last) sb[i] = -INFINITY;
-    cm = fmaxf(cm, fmaxf(sa[i], sb[i]));
-  }
-  cm = fmaxf(cm, __shfl_xor(cm, 16));
-  cm = fmaxf(cm, __shfl_xor(cm, 32));
-  // (a row that has seen nothing of the slice yet: m = mn = -inf, alpha = 1, p = 0)
-  const float mn = fmaxf(m, cm);
-  if (__any(mn > m)) {  // the running maximum of some row moved: rescale (rare after the first steps)
-    const float alpha = mn == -INFINITY ? 1.0f : __expf(m - mn);
-    lsum *= alpha;
-#pragma unroll
-    for (int dt = 0; dt < DT; dt++) acc[dt] = acc[dt] * alpha;
-    m = mn;
-  }
-  f16x8 pT;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const _Float16 pa = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sa[i] - m);
-    const _Float16 pb = m == -INFINITY ? (_Float16)0.0f : (_Float16)__expf(sb[i] - m);
-    pT[i] = pa;
-    pT[4 + i] = pb;
-    lsum += (float)pa + (float)pb;  // the normalizer sums what the second product multiplies
-  }
-#pragma unroll
-  for (int dt = 0; dt < DT; dt++) {
-    const unsigned short* vr = vt + (16 * dt + n) * VSTR + 4 * g;
-    const f16x4 va = *(const f16x4*)vr, vb2 = *(const f16x4*)(vr + 16);
-    const f16x8 vf = {va[0], va[1], va[2], va[3], vb2[0], vb2[1], vb2[2], vb2[3]};
-    acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pT, acc[dt], 0, 0, 0);
-  }
-}
-// One fragment (16 rows from row_w of `head`; `owner` false: the wave only stages) over the workgroup's tiles t0 .. t1: the loop both
-// forms run -- two buffers, the next tile's loads requested before this one is multiplied, one barrier per tile.  Leaves the
-// unnormalised O^T in acc (C layout: acc[dt][i] = O^T[dim 16 dt + 4 g + i][row n]), the row's m, and its l summed over the lane groups.
-template <int HD>
-FLASH_ROWS_SPLIT_TARGET __device__ __forceinline__ void frw_walk(const float* __restrict__ q, const unsigned short* kb, const unsigned short* vb,
-                                                                 unsigned short* lds, int n_heads, int seq_cap, int B, int pos0, int head, int row_w,
-                                                                 bool owner, int last_wg, int t0, int t1, f32x4 (&acc)[HD / 16], float& m, float& lsum) {
-  constexpr int DT = HD / 16, BN = FLASH_ROWS_W_BN, VSTR = FLASH_ROWS_W_VSTR, KSTR = HD + FLASH_ROWS_KPAD;
-  const int tid = threadIdx.x, lane = tid & 63, n = lane & 15, g = lane >> 4;
-  unsigned short* vt0 = lds;
-  unsigned short* kt0 = lds + 2 * HD * VSTR;
-  const int row = row_w + n < B ? row_w + n : B - 1;  // (rows past the batch recompute the last row; never stored)
-  f16x8 qb[HD / 32];
-  frw_load_q<HD>(q + ((size_t)row * n_heads + head) * HD, g, qb);
-  const int last_w = pos0 + (row_w + 15 < B ? row_w + 15 : B - 1);  // last cached position any row of this wave sees
-  const int my_last = pos0 + row;                                   // ... this lane's row
-#pragma unroll
-  for (int dt = 0; dt < DT; dt++) acc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  m = -INFINITY, lsum = 0.f;
-  i32x4 kreg[FrwTiles<HD>::NK], vreg[2 * FrwTiles<HD>::NV];
-  const FrwTiles<HD> tl{kb, vb, vt0, kt0, seq_cap, last_wg, tid, (int)blockDim.x};
-  if (t0 < t1) {
-    tl.issue(t0, kreg, vreg);
-    tl.commit(0, t0, kreg, vreg);
-  }
-  __syncthreads();
-  for (int tile = t0; tile < t1; tile++) {
-    const int buf = (tile - t0) & 1;
-    if (tile + 1 < t1) tl.issue(tile + 1, kreg, vreg);
-    if (owner && tile * BN <= last_w)  // wave-uniform: some row of this wave sees the tile
-      frw_step<HD>(kt0 + buf * BN * KSTR, vt0 + buf * HD * VSTR, qb, acc, m, lsum, tile * BN, my_last, n, g);
-    if (tile + 1 < t1) tl.commit(buf ^ 1, tile + 1, kreg, vreg);  // those buffers were last read one tile ago (barrier below)
-    __syncthreads();
-  }
-  lsum += __shfl_xor(lsum, 16);
-  lsum += __shfl_xor(lsum, 32);
-}
 // the one-launch causal kernel: grid (ceil(B / 64), n_heads), 256 threads, flash_rows_lds_bytes(HD) of LDS; k_attn_flash_rows' arguments
 template <int HD>
 FLASH_ROWS_SPLIT_TARGET FLASH_ROWS_W_TWO_PER_CU __global__ __launch_bounds__(64 * FLASH_ROWS_W_FRAGS) void k_attn_flash_rows_w(
@@ -2168,13 +2028,14 @@ FLASH_ROWS_SPLIT_TARGET FLASH_ROWS_W_TWO_PER_CU __global__ __launch_bounds__(64 
   f32x4 acc[HD / 16];
   float m, lsum;
   // (a wave whose 16 rows all lie past the batch stages tiles and computes nothing)
-  frw_walk<HD>(q, kc + (size_t)j * seq_cap * HD, vc + (size_t)j * seq_cap * HD, fr_lds, n_heads, seq_cap, B, pos0, head, row_w, row_w < B, last_wg,
-               0, last_wg / FLASH_ROWS_W_BN + 1, acc, m, lsum);
+  flash_rows_walk<HD>(q, FrwTiles<HD>::of(kc, vc, j, seq_cap, fr_lds, last_wg), n_heads, B, pos0, head, row_w, row_w < B, 0,
+                      last_wg / FLASH_ROWS_W_BN + 1, acc, m, lsum);
   if (row_w + n < B) {  // (the row saw position 0: l > 0)
-    const float inv = 1.0f / lsum;
+    // O / l, the quotient k_attn_flash_rows_merge stores -- not O * (1 / l), which rounds twice: the split form with one slice walks the
+    // same tiles to the same {O, m, l}, and the two forms then agree bit for bit (tests/test_hip_flash_rows_256.py)
     float* o = out + ((size_t)(row_w + n) * n_heads + head) * HD;
 #pragma unroll
-    for (int dt = 0; dt < HD / 16; dt++) *(f32x4*)(o + 16 * dt + 4 * g) = acc[dt] * inv;
+    for (int dt = 0; dt < HD / 16; dt++) *(f32x4*)(o + 16 * dt + 4 * g) = acc[dt] / lsum;
   }
 }
 // the split-KV form: grid (flash_rows_split_geom(G, B, 4).nwg, n_kv, S), 64 fpw threads; k_attn_flash_rows_split's arguments, slices and partials
@@ -2182,36 +2043,16 @@ template <int HD>
 FLASH_ROWS_SPLIT_TARGET FLASH_ROWS_W_TWO_PER_CU __global__ __launch_bounds__(64 * FLASH_ROWS_W_FRAGS) void k_attn_flash_rows_split_w(
     const float* __restrict__ q, const unsigned short* __restrict__ kc, const unsigned short* __restrict__ vc, const int* __restrict__ pos_d,
     float* __restrict__ part, int n_heads, int n_kv, int seq_cap, int B, int S) {
-  constexpr int BN = FLASH_ROWS_W_BN;
   extern __shared__ __attribute__((aligned(16))) unsigned short fr_lds[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), n = lane & 15, g = lane >> 4;  // (wave: an SGPR, and so what follows from it)
-  const int G = n_heads / n_kv, j = blockIdx.y, s = blockIdx.z, pos0 = *pos_d;
-  const FlashRowsSplitGeom ge = flash_rows_split_geom(G, B, FLASH_ROWS_W_FRAGS);
-  const int f0 = blockIdx.x * ge.fpw, f1 = f0 + ge.fpw < ge.nfrag ? f0 + ge.fpw : ge.nfrag;
-  if (f0 >= f1) return;  // (workgroup-uniform; flash_rows_split_geom leaves no workgroup empty)
-  const bool owner = f0 + wave < f1;
-  const int f = owner ? f0 + wave : f1 - 1;
-  const int head = j * G + f % G, row_w = (f / G) * 16;
-  const int rlast_wg = ((f1 - 1) / G) * 16 + 15;                 // the workgroup's fragments are row-block major: its last one's rows
-  const int last_wg = pos0 + (rlast_wg < B ? rlast_wg : B - 1);  // last cached position any row of the workgroup sees
-  const int NT = (pos0 + B - 1) / BN + 1;                        // tiles of the pass (at least as many as the 64-position tiles S is capped by)
-  const int t0 = (int)((long long)s * NT / S), t1s = (int)((long long)(s + 1) * NT / S);
-  const int t1 = t1s < last_wg / BN + 1 ? t1s : last_wg / BN + 1;  // (t1 <= t0: the workgroup sees nothing of the slice)
+  const int pos0 = *pos_d;
+  const FlashRowsSplitWork w = flash_rows_split_work<FLASH_ROWS_W_BN>(n_heads / n_kv, B, S, pos0, FLASH_ROWS_W_FRAGS, wave);
+  if (!w.any) return;  // (workgroup-uniform; flash_rows_split_geom leaves no workgroup empty)
   f32x4 acc[HD / 16];
   float m, lsum;
-  frw_walk<HD>(q, kc + (size_t)j * seq_cap * HD, vc + (size_t)j * seq_cap * HD, fr_lds, n_heads, seq_cap, B, pos0, head, row_w, owner, last_wg, t0,
-               t1, acc, m, lsum);
-  if (owner && row_w + n < B) {
-    const size_t rec = ((size_t)s * B + row_w + n) * n_heads + head;
-    float* o = part + rec * HD;
-#pragma unroll
-    for (int dt = 0; dt < HD / 16; dt++) *(f32x4*)(o + 16 * dt + 4 * g) = acc[dt];
-    if (g == 0) {
-      float* ml = part + (size_t)S * B * n_heads * HD + rec * 2;
-      ml[0] = m;
-      ml[1] = lsum;
-    }
-  }
+  flash_rows_walk<HD>(q, FrwTiles<HD>::of(kc, vc, blockIdx.y, seq_cap, fr_lds, w.last_wg), n_heads, B, pos0, w.head, w.row_w, w.owner, w.t0, w.t1, acc,
+                      m, lsum);
+  if (w.owner && w.row_w + n < B) flash_rows_store_partial<HD>(part, acc, m, lsum, S, B, n_heads, blockIdx.z, w.row_w + n, w.head, g);
 }
 
 // ---- the Q8 KV cache's append (use_f16_kv_cache == 2): R staged rows -> both planes of K and of V at positions *pos_d .. + R ----------

@@ -70,6 +70,20 @@ def test_split_form_and_merge_equal_float64_arithmetic(ca, n_heads, n_kv):
     print(f"flash rows 256 split vs float64, {n_heads} heads / {n_kv} kv: worst {worst:.2e} of max|out|")
 
 
+def test_one_forced_slice_equals_the_one_launch_kernel_bit_for_bit(ca):
+    """both forms run flash_rows_walk, every wave owning its 16 rows from the first tile to the last: 33 rows (a ragged third
+    fragment) at position 100, the split hook with one slice against the one-launch hook, compared as words.  Both normalise by
+    the quotient O / l (k_attn_flash_rows_merge<256>: fma(O, e^0, 0) / fma(l, e^0, 0)); with O * (1 / l) in the one-launch kernel
+    16890 of the 67584 words differed by one unit in the last place."""
+    dev = ca.HipTensorDevice(0)
+    q, k, v = inputs(np.random.default_rng(256), 8, 2, 100, 33)
+    one = dev.debug_flash_attention_rows(q, k.reshape(-1), v.reshape(-1), 8, 2, HD, 100, 33)
+    got = dev.debug_flash_attention_rows_split(q, k.reshape(-1), v.reshape(-1), 8, 2, HD, 100, 33, 1)
+    a, b = one.view(np.uint32).astype(np.int64), got.view(np.uint32).astype(np.int64)
+    print(f"flash rows 256, one slice vs one launch: {int(np.count_nonzero(a != b))} of {a.size} words differ, by at most {int(np.max(np.abs(a - b)))}")
+    assert np.array_equal(one.view(np.uint32), got.view(np.uint32))
+
+
 @pytest.mark.parametrize("shape", ["tiny-gemma", "tiny-gemma-g8"])
 def test_flagged_gemma_context_runs_the_family(ca, shape):
     """prefill in passes at pos0 = 0, 72, 144 (the last one short), then 4 decode steps on the cache the passes wrote, against the
